@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CalSurfG hot path on MI355X: (period, source) eikonal solves per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2] / configs[3]): 1025x1025 propagation grid
@@ -453,6 +453,8 @@ def spawn_ranks(args):
             cmd.append("--no-cpu-baseline")
         if args.no_secondary:
             cmd.append("--no-secondary")
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", args.dump_outputs]
         procs.append(subprocess.Popen(cmd, env=env))
     # poll: when one rank dies (build error, bad device, out of memory) the others would sit in the rendezvous or the
     # collective until the backend's timeout -- end them and fail at once; an overall limit covers a silent hang
@@ -489,7 +491,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="headline only (the counter passes of tools/profile_bench.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the receiver times, in the reference's order) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
@@ -598,6 +604,11 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        # the timed path's result of its last step, whole: total_units x NREC receiver times (2 MB), float32 as the path returns them
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        got = last.detach().cpu().numpy() if hasattr(last, "detach") else np.asarray(last)
+        np.save(os.path.join(args.dump_outputs, "receiver_times.npy"), np.ascontiguousarray(got, np.float32).reshape(total_units, NREC))
 
     # the other ranks are done: their engines' memory goes back before rank 0 runs the secondary legs (ranks sharing a device -- the 1-GPU rehearsal --
     # had a memory budget each; rank 0's is lifted)

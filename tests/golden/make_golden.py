@@ -1,6 +1,6 @@
 """Generate the golden vectors in this directory from the reference's own build (oracle/_ref).
 
-    python tests/golden/make_golden.py      # only where /root/reference exists (make -C oracle ref)
+    python tests/golden/make_golden.py [lsmr | digests]     # only where the reference build exists (make -C oracle ref)
 
 Every array comes out of the reference's compiled Fortran through the white-box handles of
 oracle/ref_whitebox.f90 -- nothing here is computed by this repository's code.  The fixtures are
@@ -124,12 +124,23 @@ def main_lsmr():
     print("b_lsmr ->", path, "%.1f KB" % (os.path.getsize(path) / 1024.0), "itn", a["itn"], "istop", a["istop"])
 
 
+def main_digests():
+    """ref_digests.json: the reference's side of the bit-exact tests of test_oracle_vs_ref.py / test_oracle_lsmr.py
+    (tests/refrecord.py), one SHA-256 per compared array"""
+    import refrecord
+    import test_oracle_lsmr
+    import test_oracle_vs_ref
+    data = refrecord.record(list(test_oracle_vs_ref.recorded_cases()) + list(test_oracle_lsmr.recorded_cases()))
+    print("ref_digests ->", refrecord.RECORD, "%d checks, %d arrays" % (len(data), sum(len(v) for v in data.values())))
+
+
 if __name__ == "__main__":
     import sys
-    if len(sys.argv) > 1 and sys.argv[1] == "lsmr":
-        main_lsmr()
+    if len(sys.argv) > 1 and sys.argv[1] in ("lsmr", "digests"):
+        {"lsmr": main_lsmr, "digests": main_digests}[sys.argv[1]]()
         sys.exit(0)
     main()
     main_dispersion()
     main_taipei()
     main_lsmr()
+    main_digests()

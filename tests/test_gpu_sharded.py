@@ -103,3 +103,15 @@ def test_bench_collective_path_over_rccl_with_one_rank():
     assert len(lines) == 1
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["config"]["units_per_step"] == 16000
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: the receiver times of the last timed step, every unit's, as DIR/receiver_times.npy"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-secondary",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+    assert rec["steps"] == 2
+    t = np.load(tmp_path / "receiver_times.npy")
+    assert t.dtype == np.float32 and t.shape == (16000, 32)
+    assert np.isfinite(t).all() and (t > 0).all()

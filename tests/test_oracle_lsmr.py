@@ -1,5 +1,5 @@
-"""Oracle side of the inversion step (lsmr_oracle.c) against the reference's own objects (oracle/_ref) and the
-committed golden vectors."""
+"""Oracle side of the inversion step (lsmr_oracle.c) against the reference's own objects (recorded in
+tests/golden/ref_digests.json, and live where oracle/_ref is built) and the committed golden vectors."""
 import ctypes as C
 import os
 
@@ -8,6 +8,7 @@ import pytest
 
 import _libs as L
 import inversion as inv
+import refrecord
 import synth
 
 GDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -25,14 +26,19 @@ def small_system(seed=0, damp_rows=True):
     return c, fwd, inv.build_system(c, fwd, obst, 3.0, 2.0)
 
 
-needs_ref = pytest.mark.skipif(L.ref() is None, reason="reference build not available")
-
-
-@needs_ref
-def test_blas_and_percentile_bitwise_against_reference():
-    R, O = L.ref(), L.oracle()
-    O.dso_dnrm2.restype = C.c_float; O.dso_dnrm2.argtypes = [C.c_int, C.c_void_p]
-    R.dnrm2_.restype = C.c_float
+def blas_and_percentile(side):
+    if side.name == "oracle":
+        O = side.lib
+        O.dso_dnrm2.restype = C.c_float; O.dso_dnrm2.argtypes = [C.c_int, C.c_void_p]
+        O.dso_getpercentile.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        dnrm2 = lambda n, x: O.dso_dnrm2(n, L.ptr(x))
+        percentile = lambda n, x, lo, hi: O.dso_getpercentile(n, L.ptr(x), L.ptr(lo), L.ptr(hi))
+    else:
+        R = side.lib
+        R.dnrm2_.restype = C.c_float
+        dnrm2 = lambda n, x: R.dnrm2_(C.byref(C.c_int(n)), L.ptr(x), C.byref(C.c_int(1)))
+        percentile = lambda n, x, lo, hi: R.getpercentile_(C.byref(C.c_int(n)), L.ptr(x), L.ptr(lo), L.ptr(hi))
+    out = {}
     r = synth.LCG(5)
     for n in (1, 2, 7, 64, 1000, 4097):
         for kind in range(4):
@@ -40,27 +46,40 @@ def test_blas_and_percentile_bitwise_against_reference():
             if kind == 1: x[::3] = 0.0
             if kind == 2: x = np.sort(np.abs(x)).astype(np.float32)                 # every element a new maximum
             if kind == 3: x *= np.float32(1e-20)
-            a = np.float32(O.dso_dnrm2(n, L.ptr(x)))
-            b = np.float32(R.dnrm2_(C.byref(C.c_int(n)), L.ptr(x), C.byref(C.c_int(1))))
-            assert a.view(np.uint32) == b.view(np.uint32), (n, kind)
-    O.dso_getpercentile.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            out["dnrm2_%d_%d" % (n, kind)] = np.float32(dnrm2(n, x))
     for n in (5, 100, 2061):
         x = (r.uniform(n) - 0.3).astype(np.float32)
-        qa, qb = np.zeros(2, np.float32), np.zeros(2, np.float32)
-        O.dso_getpercentile(n, L.ptr(x), L.ptr(qa[0:]), L.ptr(qa[1:]))
-        R.getpercentile_(C.byref(C.c_int(n)), L.ptr(x), L.ptr(qb[0:]), L.ptr(qb[1:]))
-        assert (bits(qa) == bits(qb)).all()
+        q = np.zeros(2, np.float32)
+        percentile(n, x, q[0:], q[1:])
+        out["percentile_%d" % n] = q
+    return out
 
 
-@needs_ref
-@pytest.mark.parametrize("damp,local_size,itnlim", [(1.0, 10, 400), (0.0, 10, 60), (0.5, 0, 100), (1.0, 3, 7)])
+def test_blas_and_percentile_bitwise_against_reference():
+    refrecord.check("blas_and_percentile", blas_and_percentile)
+
+
+LSMR = [(1.0, 10, 400), (0.0, 10, 60), (0.5, 0, 100), (1.0, 3, 7)]
+
+
+def lsmr(side, damp, local_size, itnlim):
+    c, fwd, S = small_system()
+    a = inv.call_lsmr(side.lsmr, S, damp, itnlim=itnlim, local_size=local_size)
+    return {k: (np.int32(v) if k in ("istop", "itn") else np.asarray(v, np.float32)) for k, v in a.items()}
+
+
+@pytest.mark.parametrize("damp,local_size,itnlim", LSMR)
 def test_lsmr_bitwise_against_reference(damp, local_size, itnlim):
     """oracle LSMR == the reference's module procedure on a regularised system from the boundary case"""
-    c, fwd, S = small_system()
-    a = inv.call_lsmr(L.oracle().dso_lsmr, S, damp, itnlim=itnlim, local_size=local_size)
-    b = inv.call_lsmr(L.ref().ref_wb_lsmr, S, damp, itnlim=itnlim, local_size=local_size)
+    a = refrecord.check("lsmr[%g-%d-%d]" % (damp, local_size, itnlim), lambda side: lsmr(side, damp, local_size, itnlim))
     assert a["itn"] > 3 and np.abs(a["x"]).max() > 0
-    assert inv.same(a, b) == []
+
+
+def recorded_cases():
+    """(name, body) of every refrecord check above, for tests/golden/make_golden.py"""
+    yield "blas_and_percentile", blas_and_percentile
+    for damp, local_size, itnlim in LSMR:
+        yield "lsmr[%g-%d-%d]" % (damp, local_size, itnlim), lambda side, a=(damp, local_size, itnlim): lsmr(side, *a)
 
 
 def test_iteration_system_shape():
