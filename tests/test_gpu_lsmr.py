@@ -156,3 +156,51 @@ def test_device_resident_rows_match_the_host_path():
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
     assert a["dws"] == b["dws"]
     assert np.array_equal(va.view(np.uint32), vb.view(np.uint32))
+
+
+# ---- multi-block systems: more than kSpmvBlock = 32 768 rows and columns (csrc/spmv.hip build_order / run_ordering) ---------------
+
+@pytest.mark.parametrize("device_vectors", [0, 1])
+def test_lsmr_multiblock_system(device_vectors):
+    """LSMR on a 100 001 x 68 479 system (tests/synth_matrix.py: ray-like data rows, then the regularisation rows): A x over 3
+    blocks of x plus the unblocked regularisation rows, A^T y over 4 blocks of y, all with k_spmv_block<512>; every iteration
+    carries partial sums from block to block.  Solution, itn, istop and the five estimates equal the oracle's bits."""
+    import synth_matrix as SM
+    M = SM.system(31522, 47, 47, 31, seed=11)
+    m, n, nar = M["m"], M["n"], M["rw"].size
+    assert (m + SM.BLOCK - 1) // SM.BLOCK == 4 and (n + SM.BLOCK - 1) // SM.BLOCK == 3 and (m + 63) // 64 < 16 * 200
+    b = np.zeros(m, np.float32)
+    b[:31522] = (SM.mix(np.arange(31522), 12) - 0.5).astype(np.float32)        # data residuals; the regularisation rows' are 0
+    S = dict(m=m, n=n, nar=nar, iw=np.concatenate([[nar], M["row"], M["col"]]).astype(np.int32), rw=M["rw"], b=b)
+    want = inv.call_lsmr(L.oracle().dso_lsmr, S, 0.7, itnlim=35)
+    got = device_lsmr(S, 0.7, device_vectors, itnlim=35)
+    assert want["itn"] > 3
+    assert inv.same(got, want) == []
+
+
+def test_device_resident_rows_match_the_host_path_multiblock():
+    """test_device_resident_rows_match_the_host_path on a 67 x 67 x 9 model: 33 800 parameters and, with the regularisation rows,
+    more than 32 768 rows, so the orderings that dsa_iteration_system_device builds from rows that never left the device have two
+    blocks per product, and its DWS column sums (k_spmv_sliced<true> over data_len) run block by block.  Every output equals the
+    host path's bit for bit (the host path is pinned to the oracle by the tests above)."""
+    import synth_matrix as SM
+    from dsurftomo_amd import invert
+    lib = invert.bind(load_library())
+    c = synth.boundary_case(nx=67, ny=67, nz=9, nsrc=6, nrcf=6)
+    c.update(spfra=0.5, threshold0=np.float32(3.0), weight0=np.float32(2.0), damp=np.float32(0.5), minvel=np.float32(1.5), maxvel=np.float32(5.5))
+    assert c["nparpi"] > SM.BLOCK
+    fwd = L.call_boundary(lib.dsa_calsurfg, c)
+    obst = np.ascontiguousarray(fwd["dsurf"] * (1.0 + 0.04 * (SM.mix(np.arange(c["ndata"]), 13) - 0.5)), np.float32)
+    out = []
+    for fn in (invert.iteration, invert.iteration_device):
+        vsf = np.asfortranarray(c["vels"].copy())
+        st = fn(lib, c, vsf, obst, lambda *_: None)
+        out.append((st, vsf))
+    (a, va), (b, vb) = out
+    assert a["m"] > SM.BLOCK and a["m"] == c["ndata"] + c["nparpi"]
+    assert a["nar"] == b["nar"] and a["m"] == b["m"] and a["itn"] == b["itn"] and a["istop"] == b["istop"]
+    assert a["itn"] > 3 and np.abs(a["dv"]).max() > 0
+    for k in ("dsyn", "datweight", "norm", "cbst", "dv"):
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    assert a["dws"] == b["dws"] and a["dws"][0] > 0
+    assert np.array_equal(va.view(np.uint32), vb.view(np.uint32))
