@@ -30,6 +30,7 @@
 
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
+#include "lsmr_core.h"
 #include "spmv_state.h"
 
 namespace dsa {
@@ -142,15 +143,6 @@ __global__ void k_update(int n, float c1, float c2, float c3, const float* __res
         x[i] = x[i] + c2 * hb;
         h[i] = v[i] - c3 * h[i];
     }
-}
-
-// lsmrModule.f90:686-711
-float d2norm(float a, float b)
-{
-    const float scale = fabsf(a) + fabsf(b);
-    if (scale == 0.0f) return 0.0f;
-    const float p = a / scale, q = b / scale;
-    return scale * sqrtf(p * p + q * q);
 }
 
 #define LS_TRY(e, call)                                                                        \
@@ -308,7 +300,7 @@ struct HostVectors {
 
 #define LS_DO(call) do { if ((rc = (call)) != 0) return rc; } while (0)
 
-// lsmrModule.f90:380-651 over a vector backend V
+// lsmrModule.f90:380-651 over a vector backend V; the scalar recurrences are dsa::LsmrScalars (lsmr_core.h), shared with dsa_lsmr_batch
 template <class V>
 int lsmr_loop(V& W, const float* b, float damp, float atol, float btol, float conlim, int itnlim, int localVecs,
               float* x, int* istop, int* itn, float* normA, float* condA, float* normr, float* normAr, float* normx)
@@ -323,98 +315,32 @@ int lsmr_loop(V& W, const float* b, float damp, float atol, float btol, float co
         LS_DO(W.norm_v(&alpha));
     }
     if (alpha > 0.0f) LS_DO(W.scal_v(1.0f / alpha));
-    *itn = 0; *istop = 0; *normA = 0.0f; *condA = 0.0f; *normx = 0.0f;
-    *normr = beta;
-    *normAr = alpha * beta;
-    const bool damped = damp > 0.0f;
-    if (*normAr != 0.0f) {
-        bool localOrtho = false, localVQueueFull = false;
-        int localPointer = 0;
-        if (localVecs > 0) {                                                                     // :408-413
-            localPointer = 1; localOrtho = true;
-            LS_DO(W.enqueue(0));
-        }
-        float zetabar = alpha * beta, alphabar = alpha, rho = 1.0f, rhobar = 1.0f, cbar = 1.0f, sbar = 0.0f;
+    dsa::LsmrScalars P(damp, atol, btol, conlim, itnlim, localVecs);
+    if (P.start(alpha, beta)) {
+        if (P.localOrtho) LS_DO(W.enqueue(0));                                                   // :408-413
         LS_DO(W.h_from_v());
-        float betadd = beta, betad = 0.0f, rhodold = 1.0f, tautildeold = 0.0f, thetatilde = 0.0f, zeta = 0.0f, d = 0.0f;
-        float normA2 = alpha * alpha, maxrbar = 0.0f, minrbar = 1e+30f;
-        const float normb = beta;
-        float ctol = 0.0f;
-        if (conlim > 0.0f) ctol = 1.0f / conlim;
         for (;;) {                                                                               // :480
-            *itn += 1;
-            LS_DO(W.scal_u(-alpha));
+            P.itn += 1;
+            LS_DO(W.scal_u(-P.alpha));
             LS_DO(W.aprod1());                                                                   // u = A v - alpha u
-            LS_DO(W.norm_u(&beta));
-            if (beta > 0.0f) {
-                LS_DO(W.scal_u(1.0f / beta));
-                if (localOrtho) {                                                                // localVEnqueue, :715-727
-                    if (localPointer < localVecs) localPointer += 1;
-                    else { localPointer = 1; localVQueueFull = true; }
-                    LS_DO(W.enqueue(localPointer - 1));
-                }
-                LS_DO(W.scal_v(-beta));
+            LS_DO(W.norm_u(&P.beta));
+            if (P.beta > 0.0f) {
+                LS_DO(W.scal_u(1.0f / P.beta));
+                if (P.localOrtho) LS_DO(W.enqueue(P.enqueue_slot()));                            // localVEnqueue, :715-727
+                LS_DO(W.scal_v(-P.beta));
                 LS_DO(W.aprod2());                                                               // v = A'u - beta v
-                if (localOrtho) LS_DO(W.ortho(localVQueueFull ? localVecs : localPointer));
-                LS_DO(W.norm_v(&alpha));
-                if (alpha > 0.0f) LS_DO(W.scal_v(1.0f / alpha));
+                if (P.localOrtho) LS_DO(W.ortho(P.ortho_count()));
+                LS_DO(W.norm_v(&P.alpha));
+                if (P.alpha > 0.0f) LS_DO(W.scal_v(1.0f / P.alpha));
             }
-            // plane rotations and estimates, :516-600, in the reference's order
-            const float alphahat = dsa::d2norm(alphabar, damp);
-            const float chat = alphabar / alphahat, shat = damp / alphahat;
-            const float rhoold = rho;
-            rho = dsa::d2norm(alphahat, beta);
-            const float c = alphahat / rho, s = beta / rho;
-            const float thetanew = s * alpha;
-            alphabar = c * alpha;
-            const float rhobarold = rhobar, zetaold = zeta;
-            const float thetabar = sbar * rho, rhotemp = cbar * rho;
-            rhobar = dsa::d2norm(cbar * rho, thetanew);
-            cbar = cbar * rho / rhobar;
-            sbar = thetanew / rhobar;
-            zeta = cbar * zetabar;
-            zetabar = -sbar * zetabar;
-            LS_DO(W.update(thetabar * rho / (rhoold * rhobarold), zeta / (rho * rhobar), thetanew / rho));   // :545-547
-            const float betaacute = chat * betadd, betacheck = -shat * betadd;
-            const float betahat = c * betaacute;
-            betadd = -s * betaacute;
-            const float thetatildeold = thetatilde;
-            const float rhotildeold = dsa::d2norm(rhodold, thetabar);
-            const float ctildeold = rhodold / rhotildeold, stildeold = thetabar / rhotildeold;
-            thetatilde = stildeold * rhobar;
-            rhodold = ctildeold * rhobar;
-            betad = -stildeold * betad + ctildeold * betahat;
-            tautildeold = (zetaold - thetatildeold * tautildeold) / rhotildeold;
-            const float taud = (zeta - thetatilde * tautildeold) / rhodold;
-            d = d + betacheck * betacheck;
-            {
-                const float e1 = betad - taud;
-                *normr = sqrtf(d + e1 * e1 + betadd * betadd);
-            }
-            normA2 = normA2 + beta * beta;
-            *normA = sqrtf(normA2);
-            normA2 = normA2 + alpha * alpha;
-            maxrbar = maxrbar > rhobarold ? maxrbar : rhobarold;
-            if (*itn > 1) minrbar = minrbar < rhobarold ? minrbar : rhobarold;
-            *condA = (maxrbar > rhotemp ? maxrbar : rhotemp) / (minrbar < rhotemp ? minrbar : rhotemp);
-            *normAr = fabsf(zetabar);
-            LS_DO(W.norm_x(normx));
-            const float test1 = *normr / normb;
-            const float test2 = *normAr / (*normA * *normr);
-            const float test3 = 1.0f / *condA;
-            const float t1 = test1 / (1.0f + *normA * *normx / normb);
-            const float rtol = btol + atol * *normA * *normx / normb;
-            if (*itn >= itnlim) *istop = 7;                                                      // :607-613
-            if (1.0f + test3 <= 1.0f) *istop = 6;
-            if (1.0f + test2 <= 1.0f) *istop = 5;
-            if (1.0f + t1 <= 1.0f) *istop = 4;
-            if (test3 <= ctol) *istop = 3;
-            if (test2 <= atol) *istop = 2;
-            if (test1 <= rtol) *istop = 1;
-            if (*istop != 0) break;
+            P.rotate();                                                                          // :516-600
+            LS_DO(W.update(P.c1, P.c2, P.c3));                                                   // :545-547
+            LS_DO(W.norm_x(&P.normx));
+            if (P.converged(P.normx)) break;
         }
     }
-    if (damped && *istop == 2) *istop = 3;                                                       // :651
+    P.finish();
+    *istop = P.istop; *itn = P.itn; *normA = P.normA; *condA = P.condA; *normr = P.normr; *normAr = P.normAr; *normx = P.normx;
     return W.fetch_x(x);
 }
 

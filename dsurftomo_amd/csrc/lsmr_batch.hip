@@ -1,0 +1,563 @@
+// Many LSMR solves on one resident matrix (dsa_lsmr_batch): realisation r solves the row-scaled system diag(s_r) A x = diag(s_r) b,
+// the linear step of a bootstrap over the data rows.  Every realisation is bit-identical to dsa_lsmr on its explicitly scaled
+// system (entries fl(a * s_r[row]), right-hand side fl(b * s_r)), i.e. to the reference's LSMR on that system.
+//
+// Why on the device: a lone solve's ordered fp32 reductions are serial chains, and on one wavefront a dependent add costs ~18
+// cycles (lsmr.hip); so dsa_lsmr keeps them on the host.  With R realisations there are R independent chains: lane l of group g
+// runs the chain of realisation 64 g + l, and a chain costs a lane what it costs one wavefront.  Likewise a matrix entry is read
+// once for R products, and its R input operands are one coalesced 256-byte load.
+//
+// Layout: every batch vector is [group][element][64 realisations] (element i of realisation 64 g + l at (g * len + i) * 64 + l),
+// the row scales too.  Realisations past nreal (padding lanes of the last group) have scale 0 and never run.
+//
+// The order of every sum is the reference's:
+//   * products: one wavefront per (output element, group); the entries of the element are read in storage order from a contiguous
+//     copy of the resident orderings (SpmvState::Contiguous, built once per loaded matrix) -- value and index wave-uniform, scalar
+//     loads -- and each lane adds fl(fl(a * s_r[row]) * in_r[idx]) to its own accumulator;
+//   * dnrm2 (lsmrblas.f90:247-277) and dot_product (lsmrModule.f90:744): one workgroup per group stages the terms through LDS and
+//     its first wavefront walks them, each lane its own chain (k_b_chain).  dnrm2's running scale is a running maximum of |x|, so
+//     wide kernels form it and every element's division ahead of the chain, which is left with the additions;
+//   * element-wise updates with per-realisation coefficients and masks.
+// The scalar recurrences are dsa::LsmrScalars (lsmr_core.h), the same code dsa_lsmr runs, one per realisation.  A realisation that
+// stops is frozen: no kernel writes its lanes again.  Three host synchronisations per iteration (beta, alpha, normx: nreal values each).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/dsurftomo_amd.h"
+#include "engine.h"
+#include "lsmr_core.h"
+#include "spmv_state.h"
+
+namespace dsa {
+
+namespace {
+
+// per-realisation parameters, fields of Rp values each: coefficients (float), then flags (int)
+enum { C_PRE_U, C_IBETA, C_PRE_V, C_IALPHA, C_C1, C_C2, C_C3, NCOEF };
+enum { F_ACT, F_BPOS, F_SLOT, F_LIM, F_APOS, NFLAG };
+constexpr int kNParam = NCOEF + NFLAG;
+
+// Element-wise kernels: blockIdx.y is the group, the x dimension strides over its len * 64 elements (lane = realisation % 64).
+#define LB_GROUP_LOOP(len)                                                                                            \
+    const int g = blockIdx.y;                                                                                         \
+    const size_t gbase = (size_t)g * (size_t)(len) * 64;                                                              \
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)(len) * 64; t += (size_t)gridDim.x * blockDim.x)
+
+// (g, i, l) of the batch layout <- realisation-major input: scale = s_r[i] (0 past nreal), u = fl(b[i] * s_r[i])
+__global__ void k_b_init(int m, int nreal, const float* __restrict__ b, const float* __restrict__ rs, float* __restrict__ scale, float* __restrict__ u)
+{
+    LB_GROUP_LOOP(m) {
+        const int r = g * 64 + (int)(t & 63);
+        const size_t i = t >> 6;
+        const float s = r < nreal ? rs[(size_t)r * (size_t)m + i] : 0.0f;
+        scale[gbase + t] = s;
+        u[gbase + t] = b[i] * s;
+    }
+}
+
+// realisation-major copy of a batch vector of length n: out[r * n + i]; the y dimension strides over the realisations
+__global__ void k_b_gather(int n, int nreal, const float* __restrict__ x, float* __restrict__ out)
+{
+    for (int r = blockIdx.y; r < nreal; r += gridDim.y) {
+        const float* __restrict__ xg = x + (size_t)(r >> 6) * (size_t)n * 64 + (r & 63);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[(size_t)r * n + i] = xg[(size_t)i * 64];
+    }
+}
+
+// x = c_r * x where flag_r (the reference's dscal: one multiply)
+__global__ void k_b_scal(int len, const float* __restrict__ coef, const int* __restrict__ flag, float* __restrict__ x)
+{
+    LB_GROUP_LOOP(len) {
+        const int r = g * 64 + (int)(t & 63);
+        if (flag[r]) x[gbase + t] = coef[r] * x[gbase + t];
+    }
+}
+
+// localVEnqueue (lsmrModule.f90:715-727): queue slot slot_r <- v where slot_r >= 0; the queue is [slot][group][n][64], slots `stride` apart
+__global__ void k_b_enqueue(int n, size_t stride, const int* __restrict__ slot, const float* __restrict__ v, float* __restrict__ lv)
+{
+    LB_GROUP_LOOP(n) {
+        const int s = slot[g * 64 + (int)(t & 63)];
+        if (s >= 0) lv[(size_t)s * stride + gbase + t] = v[gbase + t];
+    }
+}
+
+// v = v - d_r * lv where k < lim_r (localVOrtho, lsmrModule.f90:745)
+__global__ void k_b_axmy(int n, int k, const float* __restrict__ d, const int* __restrict__ lim, const float* __restrict__ lv, float* __restrict__ v)
+{
+    LB_GROUP_LOOP(n) {
+        const int r = g * 64 + (int)(t & 63);
+        if (k < lim[r]) v[gbase + t] = v[gbase + t] - d[r] * lv[gbase + t];
+    }
+}
+
+// v = v / alpha where apos_r (lsmrModule.f90:508), then where act_r lsmrModule.f90:545-547: hbar = h - c1*hbar; x = x + c2*hbar; h = v - c3*h
+__global__ void k_b_update(int n, const float* __restrict__ coef, const int* __restrict__ flag, float* __restrict__ v, float* __restrict__ h,
+                           float* __restrict__ hbar, float* __restrict__ x, int Rp)
+{
+    LB_GROUP_LOOP(n) {
+        const int r = g * 64 + (int)(t & 63);
+        const size_t e = gbase + t;
+        float vv = v[e];
+        if (flag[F_APOS * Rp + r]) { vv = coef[C_IALPHA * Rp + r] * vv; v[e] = vv; }
+        if (flag[F_ACT * Rp + r]) {
+            const float hi = h[e];
+            const float hb = hi - coef[C_C1 * Rp + r] * hbar[e];
+            hbar[e] = hb;
+            x[e] = x[e] + coef[C_C2 * Rp + r] * hb;
+            h[e] = vv - coef[C_C3 * Rp + r] * hi;
+        }
+    }
+}
+
+// The ordered reductions.  A lane's chain is cheap: one dependent add (dot_product), or one multiply-add and a select (dnrm2) per
+// element.  What would make it expensive is on one side memory -- a wavefront alone keeps too few 256-byte loads in flight -- and
+// on the other dnrm2's divisions, a dozen instructions each.  So:
+//   * dnrm2's divisions leave the chain.  The running scale of lsmrblas.f90:261-272 is, before element i, exactly the running
+//     maximum of |x(1..i-1)| (it is replaced by |x(i)| iff scale < |x(i)|; a NaN never replaces it, as in fmaxf), which does not
+//     depend on the sums.  Wide kernels form it (k_pm_blockmax, k_pm_scan, k_pm_terms: block maxima, their running maximum, then
+//     within the block) and with it every element's term: +(|x|/scale)**2 where scale >= |x| (the reference's else branch), or
+//     -(scale/|x|)**2 with the sign bit set where |x| is a new maximum (its `ssq = 1 + ssq*q**2` branch), +0 for a zero (skipped:
+//     ssq + 0 = ssq).  The chain then only adds (or multiplies and adds) in order: the same operations on the same operands.
+//   * k_b_chain: a workgroup of kCT threads stages the group's terms chunk by chunk (kCE elements x 64 realisations) into LDS, two
+//     chunks of loads ahead in registers, and its first wavefront runs the 64 chains out of LDS while the others stage the next
+//     chunk: one barrier per chunk.
+constexpr int kCT = 1024;                   // threads of a chain workgroup
+constexpr int kCE = 128;                    // elements per chunk: 128 x 64 x 4 B = 32 KB, two buffers
+constexpr int kPer = kCE * 64 / kCT;        // floats a thread stages per chunk
+constexpr int kPB = 256;                    // elements per block of the running maximum (four wavefronts of 64)
+
+// bm[g][b][lane] = max over the block's elements of |x| (fmaxf: a NaN is passed over, as the reference's scale passes it over)
+__global__ __launch_bounds__(256) void k_pm_blockmax(int len, int nblk, const float* __restrict__ x, float* __restrict__ bm)
+{
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, b = blockIdx.x;
+    const float* __restrict__ p = x + (size_t)g * len * 64 + lane;
+    const int e0 = b * kPB + w * 64, e1 = min(e0 + 64, len);
+    float mx = 0.0f;
+    for (int e = e0; e < e1; ++e) mx = fmaxf(mx, fabsf(p[(size_t)e * 64]));
+    red[w][lane] = mx;
+    __syncthreads();
+    if (w == 0) bm[((size_t)g * nblk + b) * 64 + lane] = fmaxf(fmaxf(red[0][lane], red[1][lane]), fmaxf(red[2][lane], red[3][lane]));
+}
+
+// per group and lane: bm <- the running maximum before each block (exclusive), tot <- the maximum of the whole vector (dnrm2's final scale)
+__global__ __launch_bounds__(64) void k_pm_scan(int nblk, float* __restrict__ bm, float* __restrict__ tot)
+{
+    const int lane = threadIdx.x;
+    float* __restrict__ p = bm + (size_t)blockIdx.x * nblk * 64 + lane;
+    float run = 0.0f;
+    int b = 0;
+    for (; b + 8 <= nblk; b += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(b + u) * 64];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { p[(size_t)(b + u) * 64] = run; run = fmaxf(run, v[u]); }
+    }
+    for (; b < nblk; ++b) { const float v = p[(size_t)b * 64]; p[(size_t)b * 64] = run; run = fmaxf(run, v); }
+    tot[(size_t)blockIdx.x * 64 + lane] = run;
+}
+
+// T(i) = dnrm2's term of element i (see above) with scale = the lane's running maximum before i
+__global__ __launch_bounds__(256) void k_pm_terms(int len, int nblk, const float* __restrict__ x, const float* __restrict__ bm, float* __restrict__ T)
+{
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, b = blockIdx.x;
+    const size_t off = (size_t)g * len * 64 + lane;
+    const float* __restrict__ p = x + off;
+    float* __restrict__ q = T + off;
+    const int e0 = b * kPB + w * 64, e1 = min(e0 + 64, len);
+    float mx = 0.0f;
+    for (int e = e0; e < e1; ++e) mx = fmaxf(mx, fabsf(p[(size_t)e * 64]));
+    red[w][lane] = mx;
+    __syncthreads();
+    float scale = bm[((size_t)g * nblk + b) * 64 + lane];
+    for (int k = 0; k < w; ++k) scale = fmaxf(scale, red[k][lane]);
+    for (int e = e0; e < e1; ++e) {
+        const float a = fabsf(p[(size_t)e * 64]);
+        const bool nm = scale < a;                       // a new maximum (false for a NaN)
+        const float qv = nm ? scale / a : a / scale;
+        const float t = qv * qv;
+        q[(size_t)e * 64] = a == 0.0f ? 0.0f : (nm ? -t : t);
+        scale = nm ? a : scale;
+    }
+}
+
+// out_r = the in-order chain of realisation r's terms: DOT: acc = 0, acc + x(i) * y(i) (dot_product, lsmrModule.f90:744);
+// else dnrm2 (lsmrblas.f90:247-277) over the terms T = x of k_pm_terms: ssq = 1, then ssq + T or, where T's sign bit is set,
+// 1 + ssq * (-T); the result tot_r * sqrt(ssq).  One workgroup per group.
+template <bool DOT>
+__global__ __launch_bounds__(kCT) void k_b_chain(int len, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ tot,
+                                                 const float* __restrict__ x1, float* __restrict__ out)
+{
+    __shared__ float buf[2][kCE * 64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const size_t gb = (size_t)blockIdx.x * len * 64, total = (size_t)len * 64;
+    const int nchunk = (len + kCE - 1) / kCE;
+    float a0[kPer], b0[kPer], a1[kPer], b1[kPer];
+    // loads past the vector read its last element (no branches: the loads of a chunk stay in flight across the barriers); stage() zeroes them
+    auto load = [&](int c, float* av, float* bv) {
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const size_t f = min((size_t)c * kCE * 64 + (size_t)j * kCT + tid, total - 1);
+            av[j] = x[gb + f];
+            if (DOT) bv[j] = y[gb + f];
+        }
+    };
+    auto stage = [&](int c, float* s, const float* av, const float* bv) {
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const bool in = (size_t)c * kCE * 64 + (size_t)j * kCT + tid < total;
+            s[j * kCT + tid] = in ? (DOT ? av[j] * bv[j] : av[j]) : 0.0f;
+        }
+    };
+    float acc = DOT ? 0.0f : 1.0f;                   // (the chain wavefront's: the dot's sum, or dnrm2's ssq)
+    auto chain = [&](int c, const float* s) {
+        const int cnt = min(kCE, len - c * kCE);      // elements of this chunk (wave-uniform)
+        for (int e = 0; e < cnt; ++e) {
+            const float t = s[e * 64 + lane];
+            if (DOT) acc = acc + t;
+            else {
+                const float renew = 1.0f + acc * (-t);
+                const float add = acc + t;
+                acc = ((__float_as_uint(t) >> 31) && t == t) ? renew : add;     // (a NaN term is never a new maximum)
+            }
+        }
+    };
+    load(0, a0, b0);
+    load(1, a1, b1);
+    for (int c = 0; c < nchunk; c += 2) {            // two chunks per trip: the register sets alternate without copies
+        stage(c, buf[0], a0, b0);
+        load(c + 2, a0, b0);
+        __syncthreads();
+        if (tid < 64) chain(c, buf[0]);
+        stage(c + 1, buf[1], a1, b1);
+        load(c + 3, a1, b1);
+        __syncthreads();
+        if (tid < 64 && c + 1 < nchunk) chain(c + 1, buf[1]);
+    }
+    if (tid < 64) {
+        float res;
+        if (DOT) res = acc;
+        else if (len < 1) res = 0.0f;
+        else if (len == 1) res = fabsf(x1[gb + lane]);
+        else res = tot[(size_t)blockIdx.x * 64 + lane] * sqrtf(acc);
+        out[(size_t)blockIdx.x * 64 + lane] = res;
+    }
+}
+
+// out_r[seg] = pre_r * out_r[seg] + sum over the segment's entries, in storage order, of fl(fl(a * s_r[row]) * in_r[idx]), where
+// flag_r.  One wavefront per (segment, group): the entries' values and indices are wave-uniform, the 64 realisations' operands
+// of an entry one 256-byte load.  ROW: segments are rows (u += A v), the row scale is the segment's; else segments are columns
+// (v += A^T u) and the row scale sits beside the gathered operand.
+template <bool ROW>
+__global__ __launch_bounds__(256) void k_b_spmv(int nseg, int nin, const long long* __restrict__ ptr, const float* __restrict__ val, const int* __restrict__ idx,
+                                                const float* __restrict__ scale, const float* __restrict__ in, float* __restrict__ out,
+                                                const float* __restrict__ pre, const int* __restrict__ flag)
+{
+    const int lane = threadIdx.x & 63, g = blockIdx.y;
+    const int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (seg >= nseg) return;
+    const int r = g * 64 + lane;
+    const bool on = flag[r] != 0;
+    if (__ballot(on) == 0) return;
+    float* __restrict__ o = out + ((size_t)g * nseg + seg) * 64 + lane;
+    const float* __restrict__ x = in + (size_t)g * nin * 64 + lane;
+    // [g][m][64]: by rows the output is the row, by columns the input is
+    const float* __restrict__ sc = scale + (size_t)g * (ROW ? nseg : nin) * 64 + lane;
+    const float srow = ROW ? sc[(size_t)seg * 64] : 0.0f;
+    float acc = *o;
+    if (pre) acc = pre[r] * acc;
+    long long k = ptr[seg];
+    const long long k1 = ptr[seg + 1];
+    constexpr int U = 8;
+    for (; k + U <= k1; k += U) {
+        float a[U], xi[U], s[U];
+        int ix[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { a[u] = val[k + u]; ix[u] = idx[k + u]; }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { xi[u] = x[(size_t)ix[u] * 64]; s[u] = ROW ? srow : sc[(size_t)ix[u] * 64]; }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const float as = a[u] * s[u]; acc = acc + as * xi[u]; }
+    }
+    for (; k < k1; ++k) {
+        const int i = idx[k];
+        const float as = val[k] * (ROW ? srow : sc[(size_t)i * 64]);
+        acc = acc + as * x[(size_t)i * 64];
+    }
+    if (on) *o = acc;
+}
+
+// one block of an ordering copied into the contiguous layout: entry k of the segment of (slice j, lane l) goes to start[j*64+l] + k
+__global__ void k_contig_fill(int nslots, const long long* __restrict__ off, const int* __restrict__ len, const long long* __restrict__ start,
+                              const float* __restrict__ val, const int* __restrict__ idx, const unsigned short* __restrict__ idx16, int base,
+                              float* __restrict__ cval, int* __restrict__ cidx)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nslots) return;
+    const int n = len[i];
+    if (n == 0) return;
+    const long long src = off[i >> 6] + (i & 63), dst = start[i];
+    for (int k = 0; k < n; ++k) {
+        const long long p = src + (long long)k * 64;
+        cval[dst + k] = val[p];
+        cidx[dst + k] = idx16 ? base + (int)idx16[p] : idx[p];
+    }
+}
+
+#define LB_TRY(e, call)                                                                        \
+    do {                                                                                       \
+        hipError_t _r = (call);                                                                \
+        if (_r != hipSuccess) { (e)->fail(DSA_ERR_DEVICE, "lsmr_batch: %s failed: %s", #call, hipGetErrorString(_r)); return DSA_ERR_DEVICE; } \
+    } while (0)
+
+// A segment's entries lie in the blocks of its ordering in storage order: in blocks 0, 1, ... (segments stored in ascending input
+// order) or all in the unblocked rest.  So the contiguous copy of segment s is its part of block 0, then of block 1, ...
+int build_contiguous(Engine* e, const SpmvState::Ordering& O, int nseg, long long nar, SpmvState::Contiguous& C)
+{
+    if (e->ensure(C.ptr, (size_t)nseg + 1) || e->ensure(C.val, std::max<size_t>((size_t)nar, 1)) || e->ensure(C.idx, std::max<size_t>((size_t)nar, 1)))
+        return e->status;
+    const int nb1 = (int)O.blocks.size();
+    std::vector<std::vector<int>> seg(nb1), len(nb1);
+    for (int b = 0; b < nb1; ++b) {
+        const SpmvState::Sliced& L = O.blocks[b];
+        if (L.padded <= 0) continue;
+        const size_t ns = (size_t)L.nslices * 64;
+        seg[b].resize(ns); len[b].resize(ns);
+        LB_TRY(e, hipMemcpyAsync(seg[b].data(), L.seg.p, ns * 4, hipMemcpyDeviceToHost, e->stream));
+        LB_TRY(e, hipMemcpyAsync(len[b].data(), L.len.p, ns * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    LB_TRY(e, hipStreamSynchronize(e->stream));
+    std::vector<long long> ptr((size_t)nseg + 1, 0);
+    for (int b = 0; b < nb1; ++b)
+        for (size_t i = 0; i < len[b].size(); ++i)
+            if (len[b][i] > 0) {
+                if (seg[b][i] < 0 || seg[b][i] >= nseg) { e->fail(DSA_ERR_INTERNAL, "lsmr_batch: segment %d of an ordering outside 0..%d", seg[b][i], nseg - 1); return DSA_ERR_INTERNAL; }
+                ptr[(size_t)seg[b][i] + 1] += len[b][i];
+            }
+    for (int s = 0; s < nseg; ++s) ptr[(size_t)s + 1] += ptr[s];
+    if (ptr[nseg] != nar) { e->fail(DSA_ERR_INTERNAL, "lsmr_batch: an ordering holds %lld entries, the matrix %lld", ptr[nseg], nar); return DSA_ERR_INTERNAL; }
+    LB_TRY(e, hipMemcpyAsync(C.ptr.p, ptr.data(), ((size_t)nseg + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    std::vector<long long> cur(ptr.begin(), ptr.end() - 1);
+    DevBuf<long long> d_start;
+    std::vector<long long> start;
+    int rc = 0;
+    for (int b = 0; b < nb1 && rc == 0; ++b) {
+        const SpmvState::Sliced& L = O.blocks[b];
+        if (L.padded <= 0) continue;
+        const size_t ns = len[b].size();
+        start.assign(ns, 0);
+        for (size_t i = 0; i < ns; ++i)
+            if (len[b][i] > 0) { start[i] = cur[(size_t)seg[b][i]]; cur[(size_t)seg[b][i]] += len[b][i]; }
+        if (e->ensure(d_start, ns)) { rc = e->status; break; }
+        if (hipMemcpyAsync(d_start.p, start.data(), ns * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "lsmr_batch: upload failed"); rc = DSA_ERR_DEVICE; break; }
+        const bool local = b < O.nblocks;
+        hipLaunchKernelGGL(k_contig_fill, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, e->stream, (int)ns, L.off.p, L.len.p, d_start.p, L.val.p,
+                           local ? nullptr : L.idx.p, local ? L.idx16.p : nullptr, local ? b * O.block : 0, C.val.p, C.idx.p);
+        if (hipStreamSynchronize(e->stream) != hipSuccess || hipGetLastError() != hipSuccess) { e->fail(DSA_ERR_DEVICE, "lsmr_batch: contiguous copy failed"); rc = DSA_ERR_DEVICE; }
+    }
+    if (d_start.p) (void)hipFree(d_start.p);
+    return rc;
+}
+
+// element-wise launch over every group's len * 64 elements
+dim3 grid_of(int len, int G) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, ((size_t)len * 64 + 255) / 256)), (unsigned)G); }
+
+}  // namespace
+
+}  // namespace dsa
+
+using dsa::Engine;
+using dsa::SpmvState;
+
+extern "C" {
+
+int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_scale, float damp, float atol, float btol, float conlim, int itnlim,
+                   int localSize, float* x, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (nreal < 1 || nreal > 64 * 65535 || !b || !row_scale || !x || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_batch: nreal < 1 or a null argument"); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_batch: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    SpmvState& S = *e->spmv;
+    const int m = S.m, n = S.n, G = (nreal + 63) / 64, Rp = 64 * G;
+    const int localVecs = std::max(0, std::min(localSize, std::min(m, n)));                      // :365
+    const size_t vm = (size_t)G * m * 64, vn = (size_t)G * n * 64;
+    hipStream_t st = e->stream;
+    LB_TRY(e, hipSetDevice(e->device));
+    if (!S.contiguous_valid) {
+        int rc = build_contiguous(e, S.by_row, m, S.nar, S.row_csr);
+        if (rc == 0) rc = build_contiguous(e, S.by_col, n, S.nar, S.col_csr);
+        if (rc != 0) return rc;
+        S.contiguous_valid = true;
+    }
+    const size_t tmp = std::max((size_t)nreal * m + m, (size_t)nreal * n);
+    if (e->ensure(S.bu, vm) || e->ensure(S.bscale, vm) || e->ensure(S.bv, vn) || e->ensure(S.bh, vn) || e->ensure(S.bhbar, vn) || e->ensure(S.bx, vn) ||
+        e->ensure(S.blocalV, std::max<size_t>(vn * (size_t)localVecs, 1)) || e->ensure(S.bparam, (size_t)kNParam * Rp) || e->ensure(S.bred, 3 * (size_t)Rp) ||
+        e->ensure(S.bterm, std::max(vm, vn)) || e->ensure(S.bpmax, (size_t)G * ((std::max(m, n) + kPB - 1) / kPB) * 64) ||
+        e->ensure(S.btmp, tmp)) return e->status;
+    const size_t hwords = (size_t)(kNParam + 1) * Rp;
+    if (S.hbatch_cap < hwords) {
+        if (S.hbatch) (void)hipHostFree(S.hbatch);
+        S.hbatch = nullptr; S.hbatch_cap = 0;
+        LB_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&S.hbatch), hwords * 4, hipHostMallocDefault));
+        S.hbatch_cap = hwords;
+    }
+    // host mirror of bparam, then nreal norms.  The host writes the mirror only after a synchronisation that follows the previous upload.
+    float* hc = S.hbatch;
+    int* hf = reinterpret_cast<int*>(S.hbatch + (size_t)NCOEF * Rp);
+    float* hred = S.hbatch + (size_t)kNParam * Rp;
+    std::memset(S.hbatch, 0, hwords * 4);
+    const float* dc = S.bparam.p;
+    const int* df = reinterpret_cast<const int*>(S.bparam.p + (size_t)NCOEF * Rp);
+    auto coef = [&](int f) { return dc + (size_t)f * Rp; };
+    auto flag = [&](int f) { return df + (size_t)f * Rp; };
+    auto upload = [&]() -> int { LB_TRY(e, hipMemcpyAsync(S.bparam.p, S.hbatch, (size_t)kNParam * Rp * 4, hipMemcpyHostToDevice, st)); return 0; };
+    // dnrm2 of every realisation's v (len elements): terms and scales by the wide kernels, then the chains
+    auto norm = [&](int len, const float* v) -> int {
+        const int nb = (len + kPB - 1) / kPB;
+        hipLaunchKernelGGL(k_pm_blockmax, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, S.bpmax.p);
+        hipLaunchKernelGGL(k_pm_scan, dim3(G), dim3(64), 0, st, nb, S.bpmax.p, S.bred.p + 2 * (size_t)Rp);
+        hipLaunchKernelGGL(k_pm_terms, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, (const float*)S.bpmax.p, S.bterm.p);
+        hipLaunchKernelGGL(k_b_chain<false>, dim3(G), dim3(kCT), 0, st, len, (const float*)S.bterm.p, (const float*)nullptr,
+                           (const float*)(S.bred.p + 2 * (size_t)Rp), v, S.bred.p);
+        LB_TRY(e, hipMemcpyAsync(hred, S.bred.p, (size_t)Rp * 4, hipMemcpyDeviceToHost, st));
+        LB_TRY(e, hipStreamSynchronize(st));
+        return 0;
+    };
+    auto product = [&](int mode, const float* pre, const int* fl) {
+        if (mode == 1)
+            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S.row_csr.ptr.p, S.row_csr.val.p, S.row_csr.idx.p,
+                               (const float*)S.bscale.p, (const float*)S.bv.p, S.bu.p, pre, fl);
+        else
+            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S.col_csr.ptr.p, S.col_csr.val.p, S.col_csr.idx.p,
+                               (const float*)S.bscale.p, (const float*)S.bu.p, S.bv.p, pre, fl);
+    };
+    int rc = 0;
+#define LB_DO(call) do { if ((rc = (call)) != 0) return rc; } while (0)
+
+    // u = diag(s_r) b, v = x = hbar = 0 (:383-385)
+    float* d_rs = S.btmp.p;
+    float* d_b = S.btmp.p + (size_t)nreal * m;
+    LB_TRY(e, hipMemcpyAsync(d_rs, row_scale, (size_t)nreal * m * 4, hipMemcpyHostToDevice, st));
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b_init, grid_of(m, G), dim3(256), 0, st, m, nreal, (const float*)d_b, (const float*)d_rs, S.bscale.p, S.bu.p);
+    LB_TRY(e, hipMemsetAsync(S.bv.p, 0, vn * 4, st));
+    LB_TRY(e, hipMemsetAsync(S.bx.p, 0, vn * 4, st));
+    LB_TRY(e, hipMemsetAsync(S.bhbar.p, 0, vn * 4, st));
+    std::vector<LsmrScalars> P((size_t)nreal, LsmrScalars(damp, atol, btol, conlim, itnlim, localVecs));
+    std::vector<char> running((size_t)nreal, 0);
+    std::vector<float> alpha0((size_t)nreal, 0.0f), beta0((size_t)nreal, 0.0f);
+    LB_DO(norm(m, S.bu.p));                                                                      // beta = |u|
+    bool any = false;
+    for (int r = 0; r < nreal; ++r) {
+        beta0[r] = hred[r];
+        const bool pos = beta0[r] > 0.0f;
+        hf[F_BPOS * Rp + r] = pos;
+        hc[C_IBETA * Rp + r] = pos ? 1.0f / beta0[r] : 0.0f;
+        any = any || pos;
+    }
+    if (any) {
+        LB_DO(upload());
+        hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, coef(C_IBETA), flag(F_BPOS), S.bu.p);      // u = u / beta
+        product(2, nullptr, flag(F_BPOS));                                                                       // v = A'u
+        LB_DO(norm(n, S.bv.p));                                                                                  // alpha = |v|
+        for (int r = 0; r < nreal; ++r) {
+            alpha0[r] = hf[F_BPOS * Rp + r] ? hred[r] : 0.0f;
+            hf[F_APOS * Rp + r] = alpha0[r] > 0.0f;
+            hc[C_IALPHA * Rp + r] = alpha0[r] > 0.0f ? 1.0f / alpha0[r] : 0.0f;
+        }
+        LB_DO(upload());
+        hipLaunchKernelGGL(k_b_scal, grid_of(n, G), dim3(256), 0, st, n, coef(C_IALPHA), flag(F_APOS), S.bv.p);     // v = v / alpha
+    }
+    int nrun = 0;
+    for (int r = 0; r < nreal; ++r) nrun += (running[r] = P[r].start(alpha0[r], beta0[r]));
+    const bool localOrtho = localVecs > 0;
+    if (nrun > 0) {
+        if (localOrtho) LB_TRY(e, hipMemcpyAsync(S.blocalV.p, S.bv.p, vn * 4, hipMemcpyDeviceToDevice, st));                // :408-413
+        LB_TRY(e, hipMemcpyAsync(S.bh.p, S.bv.p, vn * 4, hipMemcpyDeviceToDevice, st));
+        LB_TRY(e, hipStreamSynchronize(st));                  // (the last upload has landed before the host mirror changes)
+    }
+    while (nrun > 0) {                                                                           // :480
+        for (int r = 0; r < Rp; ++r) {
+            const bool on = r < nreal && running[r];
+            hf[F_ACT * Rp + r] = on;
+            if (on) { P[r].itn += 1; hc[C_PRE_U * Rp + r] = -P[r].alpha; }
+        }
+        LB_DO(upload());
+        product(1, coef(C_PRE_U), flag(F_ACT));                                                  // u = A v - alpha u
+        LB_DO(norm(m, S.bu.p));                                                                  // beta = |u|
+        int maxlim = 0;
+        any = false;
+        for (int r = 0; r < nreal; ++r) {
+            hf[F_BPOS * Rp + r] = 0; hf[F_SLOT * Rp + r] = -1; hf[F_LIM * Rp + r] = 0; hf[F_APOS * Rp + r] = 0;
+            if (!running[r]) continue;
+            LsmrScalars& p = P[r];
+            p.beta = hred[r];
+            if (!(p.beta > 0.0f)) continue;
+            any = true;
+            hf[F_BPOS * Rp + r] = 1;
+            hc[C_IBETA * Rp + r] = 1.0f / p.beta;
+            hc[C_PRE_V * Rp + r] = -p.beta;
+            if (p.localOrtho) {                                                                  // localVEnqueue, :715-727
+                hf[F_SLOT * Rp + r] = p.enqueue_slot();
+                hf[F_LIM * Rp + r] = p.ortho_count();
+                maxlim = std::max(maxlim, p.ortho_count());
+            }
+        }
+        if (any) {
+            LB_DO(upload());
+            hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, coef(C_IBETA), flag(F_BPOS), S.bu.p);  // u = u / beta
+            if (localOrtho)
+                hipLaunchKernelGGL(k_b_enqueue, grid_of(n, G), dim3(256), 0, st, n, vn, flag(F_SLOT), (const float*)S.bv.p, S.blocalV.p);
+            product(2, coef(C_PRE_V), flag(F_BPOS));                                             // v = A'u - beta v
+            for (int k = 0; k < maxlim; ++k) {                                                   // localVOrtho, :731-748
+                const float* lv = S.blocalV.p + (size_t)k * vn;
+                hipLaunchKernelGGL(k_b_chain<true>, dim3(G), dim3(kCT), 0, st, n, (const float*)S.bv.p, lv, (const float*)nullptr, (const float*)nullptr,
+                                   S.bred.p + Rp);
+                hipLaunchKernelGGL(k_b_axmy, grid_of(n, G), dim3(256), 0, st, n, k, (const float*)(S.bred.p + Rp), flag(F_LIM), lv, S.bv.p);
+            }
+            LB_DO(norm(n, S.bv.p));                                                              // alpha = |v|
+            for (int r = 0; r < nreal; ++r) {
+                if (!hf[F_BPOS * Rp + r]) continue;
+                LsmrScalars& p = P[r];
+                p.alpha = hred[r];
+                if (p.alpha > 0.0f) { hf[F_APOS * Rp + r] = 1; hc[C_IALPHA * Rp + r] = 1.0f / p.alpha; }
+            }
+        }
+        for (int r = 0; r < nreal; ++r) {
+            if (!running[r]) continue;
+            LsmrScalars& p = P[r];
+            p.rotate();                                                                          // :516-600
+            hc[C_C1 * Rp + r] = p.c1; hc[C_C2 * Rp + r] = p.c2; hc[C_C3 * Rp + r] = p.c3;
+        }
+        LB_DO(upload());
+        hipLaunchKernelGGL(k_b_update, grid_of(n, G), dim3(256), 0, st, n, dc, df, S.bv.p, S.bh.p, S.bhbar.p, S.bx.p, Rp);   // :508, :545-547
+        LB_DO(norm(n, S.bx.p));                                                                  // normx
+        for (int r = 0; r < nreal; ++r)
+            if (running[r] && P[r].converged(hred[r])) { running[r] = 0; --nrun; }
+    }
+#undef LB_DO
+    for (int r = 0; r < nreal; ++r) {
+        LsmrScalars& p = P[r];
+        p.finish();
+        istop[r] = p.istop; itn[r] = p.itn;
+        float* q = est + (size_t)5 * r;
+        q[0] = p.normA; q[1] = p.condA; q[2] = p.normr; q[3] = p.normAr; q[4] = p.normx;
+    }
+    hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, nreal, (const float*)S.bx.p,
+                       S.btmp.p);
+    LB_TRY(e, hipMemcpyAsync(x, S.btmp.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // extern "C"

@@ -317,6 +317,7 @@ int load_from_device(Engine* e, int m, int n, long long nar, const float* d_rw, 
     if (!e->spmv) e->spmv = new SpmvState();
     SpmvState& S = *e->spmv;
     S.m = m; S.n = n; S.nar = nar;
+    dsa::spmv_invalidate_contiguous(&S);
     int rc = 0;
     if (e->ensure(S.x, (size_t)n) || e->ensure(S.y, (size_t)m)) rc = e->status;
     if (rc == 0) rc = build_order(e, nar, m, n, d_row, d_col, d_rw, -1, S.by_row);
@@ -441,6 +442,9 @@ void release_spmv(SpmvState* s)
     }
     rel(s->x); rel(s->y);
     rel(s->u); rel(s->v); rel(s->h); rel(s->hbar); rel(s->xs); rel(s->localV); rel(s->scal);
+    for (SpmvState::Contiguous* c : { &s->row_csr, &s->col_csr }) { rel(c->ptr); rel(c->val); rel(c->idx); }
+    rel(s->bu); rel(s->bv); rel(s->bh); rel(s->bhbar); rel(s->bx); rel(s->blocalV); rel(s->bscale); rel(s->bparam); rel(s->bred); rel(s->btmp); rel(s->bterm); rel(s->bpmax);
+    if (s->hbatch) (void)hipHostFree(s->hbatch);
     if (s->hu) (void)hipHostFree(s->hu);
     if (s->hv) (void)hipHostFree(s->hv);
     delete s;

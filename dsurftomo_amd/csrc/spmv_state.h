@@ -40,10 +40,25 @@ struct SpmvState {
     // pinned host copies of u and v for the host-vector placement (they cross PCIe twice per LSMR iteration)
     float* hu = nullptr; float* hv = nullptr;
     size_t hu_cap = 0, hv_cap = 0;
+    // dsa_lsmr_batch (lsmr_batch.hip): each ordering once more as plain CSR / CSC -- a segment's entries contiguous, in storage
+    // order, global input indices -- built from the orderings above on the first batch after a load (valid = false: rebuild)
+    struct Contiguous {
+        DevBuf<long long> ptr;       // nseg + 1
+        DevBuf<float> val;
+        DevBuf<int> idx;
+    };
+    Contiguous row_csr, col_csr;
+    bool contiguous_valid = false;
+    // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
+    DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
+    float* hbatch = nullptr;         // pinned: per-realisation coefficients and flags (bparam) on their way to the device, norms on their way back
+    size_t hbatch_cap = 0;
 };
 
 // y += A x (mode 1; x: n, y: m) or x += A^T y (mode 2) on device vectors, on the engine's stream; every output
 // element adds its entries in storage order (reference aprod.f90:7-60)
 void spmv_device(Engine* e, int mode, float* d_x, float* d_y);
+// the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch are stale
+inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = false; }
 
 }  // namespace dsa

@@ -69,6 +69,7 @@ def load_library():
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_spmv.argtypes = [_vp, _i32, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp] + [_vp] * 7
+    L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
     L.dsa_dropin_error.restype = C.c_char_p
@@ -263,6 +264,24 @@ class Engine:
                                      *[C.byref(v) for v in ii], *[C.byref(v) for v in ff]))
         names = ("normA", "condA", "normr", "normAr", "normx")
         return dict(x=x, istop=ii[0].value, itn=ii[1].value, **{k: np.float32(v.value) for k, v in zip(names, ff)})
+
+    def lsmr_batch(self, b, row_scale, damp, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
+        """R LSMR solves on the matrix of the last spmv_load: realisation r with its rows scaled by row_scale[r] (shape (R, m)),
+        each bit-identical to lsmr() on that explicitly scaled system.  Returns dict(x=(R, n), istop=(R,), itn=(R,), normA=(R,), condA,
+        normr, normAr, normx)"""
+        b = np.ascontiguousarray(b, np.float32)
+        s = np.ascontiguousarray(row_scale, np.float32)
+        m, n = self._mn
+        assert b.size == m and s.ndim == 2 and s.shape[1] == m
+        R = s.shape[0]
+        x = np.zeros((R, n), np.float32)
+        istop = np.zeros(R, np.int32)
+        itn = np.zeros(R, np.int32)
+        est = np.zeros((R, 5), np.float32)
+        self._check(self._L.dsa_lsmr_batch(self._h, R, _p(b), _p(s), damp, atol, btol, conlim, int(itnlim), int(local_size), _p(x), _p(istop),
+                                           _p(itn), _p(est)))
+        names = ("normA", "condA", "normr", "normAr", "normx")
+        return dict(x=x, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
 
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)

@@ -1,6 +1,7 @@
 """The reference's inversion loop (main.f90:346-590) driven through this library, without the Fortran host program.
 
     python -m dsurftomo_amd.invert <directory with DSurfTomo.in, the data file and MOD> [--maxiter N] [--out DIR]
+                                   [--bootstrap R [--bootstrap-seed S]]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -12,6 +13,12 @@ arrays the way the reference does (dsa_calsurfg -> dsa_iteration_system -> dsa_l
 Synthetic tests (ifsyn = 1, main.f90:326-343) forward-model MOD.true; the noise there comes from this module's own
 generator, not from the reference's gaussian().  There is no CPU path: without a usable GPU this fails with the engine's
 error text.
+
+--bootstrap R (R >= 2) adds what the reference declared and never filled (main.f90:67, :290-291: dvsub, dvstd, dvall): a
+standard deviation of the last iteration's velocity update.  The data rows of that iteration's system are resampled with
+replacement R times (bootstrap_row_scales: row r of realisation k weighted by sqrt(how often it was drawn)), the R weighted
+systems are solved by dsa_lsmr_batch on the matrix dsa_lsmr just used, and <input>Std.dat lists the sample standard deviation
+(ddof 1) of the R raw updates per vertex in the layout of <input>Measure.dat.  Device-resident rows only (not with --host-rows).
 """
 import argparse
 import ctypes as C
@@ -46,15 +53,37 @@ def write_model(path, c, vsf):
                     fh.write(_f10(lon) + _f10(lat) + _f10(c["depz"][k]) + _f10(vsf[i + 1, j + 1, k]) + "\n")
 
 
+def write_std(path, c, std):
+    """write_model's layout with the per-parameter values std (maxvp, the order of the LSMR unknowns: i fastest, then j, then k) as
+    the fourth column"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    v = np.zeros((nx, ny, nz), np.float64)
+    v[1:-1, 1:-1, :-1] = np.asarray(std, np.float64).reshape(nz - 1, ny - 2, nx - 2).transpose(2, 1, 0)
+    write_model(path, c, v)
+
+
+def bootstrap_row_scales(ndata, m, nreal, seed):
+    """(nreal, m) float32 row scales of a bootstrap over the ndata data rows: per realisation ndata draws of a row, uniform with
+    replacement (numpy default_rng(seed)), each data row scaled by sqrt(how often it was drawn); the regularisation rows
+    (ndata .. m-1) keep 1"""
+    rng = np.random.default_rng(seed)
+    s = np.ones((nreal, m), np.float32)
+    for r in range(nreal):
+        cnt = np.bincount(rng.integers(0, ndata, size=ndata), minlength=ndata)
+        s[r, :ndata] = np.sqrt(cnt).astype(np.float32)
+    return s
+
+
 def write_residuals(path, c, dsyn, obst, datweight):
     """list-directed rows: dist, dsyn, obst, dsyn*w, obst*w, w (main.f90:397-403)"""
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
-def iteration_device(lib, c, vsf, obst, log):
+def iteration_device(lib, c, vsf, obst, log, bootstrap=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
-    both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit)."""
+    both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit).
+    bootstrap = (R, seed): after dsa_lsmr, R row-resampled solves of the same system by dsa_lsmr_batch (returned as "boot")."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -86,15 +115,38 @@ def iteration_device(lib, c, vsf, obst, log):
     if rc != 0:
         raise RuntimeError("dsa_lsmr: %s" % lib.dsa_error_string(eng).decode())
     t_lsmr = time.perf_counter() - t0
+    boot = None
+    if bootstrap:
+        boot = lsmr_bootstrap(lib, eng, c, cbst, m.value, *bootstrap)
     r = cbst[:dall]
     mean = f(r.sum(dtype=f) / f(dall))
     std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
     rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))
     dv_raw = (f(dv.min()), f(dv.max()))
     lib.dsa_model_update(nx, ny, nz, _p(dv), _p(vsf), c["minvel"], c["maxvel"])
-    return dict(dsyn=dsyn, datweight=datweight, mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(dv_raw[0]),
-                dv_max=float(dv_raw[1]), itn=ii[1].value, istop=ii[0].value, nar=nar2.value, m=m.value, dws=(float(dws[0]), float(dws[1])),
-                seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), dv=dv, norm=norm, cbst=cbst)
+    out = dict(dsyn=dsyn, datweight=datweight, mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(dv_raw[0]),
+               dv_max=float(dv_raw[1]), itn=ii[1].value, istop=ii[0].value, nar=nar2.value, m=m.value, dws=(float(dws[0]), float(dws[1])),
+               seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), dv=dv, norm=norm, cbst=cbst)
+    if boot is not None:
+        out["boot"] = boot
+    return out
+
+
+def lsmr_bootstrap(lib, eng, c, cbst, m, nreal, seed):
+    """nreal solves of the resident system with bootstrap row scales (dsa_lsmr_batch, the arguments of the dsa_lsmr call above).
+    Returns dict(x=(nreal, maxvp) raw updates, std=(maxvp,) float64 sample standard deviation, itn, istop, est=(nreal, 5), seconds)."""
+    f = np.float32
+    maxvp = c["nparpi"]
+    scales = bootstrap_row_scales(c["ndata"], m, nreal, seed)
+    x = np.zeros((nreal, maxvp), f)
+    istop = np.zeros(nreal, np.int32); itn = np.zeros(nreal, np.int32); est = np.zeros((nreal, 5), f)
+    t0 = time.perf_counter()
+    rc = lib.dsa_lsmr_batch(eng, nreal, _p(cbst), _p(scales), C.c_float(c["damp"]), C.c_float(1e-6), C.c_float(1e-6), C.c_float(100.0), 400, 10,
+                            _p(x), _p(istop), _p(itn), _p(est))
+    if rc != 0:
+        raise RuntimeError("dsa_lsmr_batch: %s" % lib.dsa_error_string(eng).decode())
+    seconds = time.perf_counter() - t0
+    return dict(x=x, std=x.astype(np.float64).std(axis=0, ddof=1), itn=itn, istop=istop, est=est, seconds=seconds)
 
 
 def iteration(lib, c, vsf, obst, log):
@@ -153,12 +205,22 @@ def bind(lib):
     lib.dsa_dropin_engine.restype = C.c_void_p
     lib.dsa_dropin_engine.argtypes = []
     lib.dsa_lsmr.argtypes = [C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 8
+    lib.dsa_lsmr_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
     lib.dsa_error_string.restype = C.c_char_p
     lib.dsa_error_string.argtypes = [C.c_void_p]
     return lib
 
 
-def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False):
+def check_bootstrap(bootstrap, host_rows):
+    """the bootstrap's preconditions, checked before anything touches the GPU"""
+    if bootstrap and bootstrap < 2:
+        raise ValueError("--bootstrap needs at least 2 realisations (got %d)" % bootstrap)
+    if bootstrap and host_rows:
+        raise ValueError("--bootstrap solves on the device-resident system: it cannot be combined with --host-rows")
+
+
+def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1):
+    check_bootstrap(bootstrap, host_rows)
     lib = bind(load_library())
     c = io.load(directory)
     maxiter = c["maxiter"] if maxiter is None else maxiter
@@ -174,7 +236,10 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
     name = os.path.join(out_dir, "DSurfTomo.in")
     history = []
     for it in range(1, maxiter + 1):
-        st = (iteration if host_rows else iteration_device)(lib, c, vsf, obst, log)
+        if host_rows:
+            st = iteration(lib, c, vsf, obst, log)
+        else:
+            st = iteration_device(lib, c, vsf, obst, log, (bootstrap, bootstrap_seed) if bootstrap and it == maxiter else None)
         log("%2dth iteration..." % it)
         log(" mean,std_devs and rms of residual after weighting: %8.1fms %8.2fms %8.3f" % (st["mean_ms"], st["std_ms"], st["rms"]))
         log(" min and max velocity variation %7.4f%7.4f" % (st["dv_min"], st["dv_max"]))
@@ -185,7 +250,19 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        history.append({k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst")})
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot")}
+        if "boot" in st:
+            b = st["boot"]
+            write_std(name + "Std.dat", c, b["std"])
+            stops = {int(k): int(v) for k, v in zip(*np.unique(b["istop"], return_counts=True))}
+            h["bootstrap"] = dict(realisations=int(b["itn"].size), itn_min=int(b["itn"].min()), itn_median=float(np.median(b["itn"])),
+                                  itn_max=int(b["itn"].max()), istop=stops, std_max=float(b["std"].max()), std_mean=float(b["std"].mean()),
+                                  seconds=b["seconds"])
+            hb = h["bootstrap"]
+            log(" bootstrap: %d realisations, itn min/median/max %d/%g/%d, istop %s, std of the update max %.5f mean %.5f km/s (%.3f s)" %
+                (hb["realisations"], hb["itn_min"], hb["itn_median"], hb["itn_max"], " ".join("%d:%d" % kv for kv in sorted(stops.items())),
+                 hb["std_max"], hb["std_mean"], hb["seconds"]))
+        history.append(h)
     if vsftrue is not None:
         write_model(os.path.join(out_dir, "Vs_model.real"), c, vsftrue)
         write_model(name + "Syn.dat", c, vsf)
@@ -201,9 +278,18 @@ def main(argv=None):
     ap.add_argument("--maxiter", type=int, default=None)
     ap.add_argument("--out", default=".")
     ap.add_argument("--host-rows", action="store_true", help="hand the matrix through host arrays like the reference (default: it stays on the device)")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                    help="R >= 2 row-resampled solves of the last iteration's system: <input>Std.dat, the standard deviation of the update. "
+                         "The R solves run side by side and cost about the same for any R up to a few hundred: below about R = 8 to 16 "
+                         "they take about as long as, or longer than, R separate solves (NOTEBOOK.md)")
+    ap.add_argument("--bootstrap-seed", type=int, default=1, metavar="S", help="seed of the bootstrap's resampling (default 1)")
     args = ap.parse_args(argv)
+    try:
+        check_bootstrap(args.bootstrap, args.host_rows)
+    except ValueError as exc:
+        ap.error(str(exc))
     os.makedirs(args.out, exist_ok=True)
-    run(args.directory, args.maxiter, args.out, host_rows=args.host_rows)
+    run(args.directory, args.maxiter, args.out, host_rows=args.host_rows, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed)
     return 0
 
 

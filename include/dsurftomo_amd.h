@@ -201,6 +201,15 @@ int dsa_lsmr(dsa_engine* e, const float* b, float damp, float atol, float btol, 
              int localSize, float* x, int* istop, int* itn, float* normA, float* condA, float* normr,
              float* normAr, float* normx);
 
+/* nreal LSMR solves on the matrix of the last dsa_spmv_load / dsa_iteration_system_device.  Realisation r solves
+ * min || diag(s_r) (A x - b) ||^2 + damp^2 ||x||^2 with s_r = row_scale[r*m .. r*m+m-1] (host, not modified) and the
+ * shared right-hand side b[m].  x: nreal*n (realisation-major), istop/itn: nreal, est: 5*nreal (normA condA normr
+ * normAr normx per realisation).  Realisation r is bit-identical to dsa_lsmr on the explicitly scaled system
+ * (entries fl(a*s_r[row]), right-hand side fl(b*s_r)).  The resident matrix and dsa_lsmr are left as they were.
+ * Errors: DSA_ERR_ARGUMENT (nreal < 1, a null pointer), DSA_ERR_STATE (no matrix), DSA_ERR_DEVICE. */
+int dsa_lsmr_batch(dsa_engine* e, int nreal, const float* b, const float* row_scale, float damp, float atol, float btol,
+                   float conlim, int itnlim, int localSize, float* x, int* istop, int* itn, float* est);
+
 /* One outer iteration's host glue (reference main.f90:361-466 and :520-535; plain host code, no device):
  * iteration_system: residual cbst = obst - dsyn, percentile weights (getpercentile.f90), rows scaled by their weights,
  *   DWS norm[maxvp] with dws = {max, mean}, regularisation rows appended.  In/out rw, col (capacity entries) and iw

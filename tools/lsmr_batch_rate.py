@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""dsa_lsmr_batch against R sequential dsa_lsmr calls (default placement: products on the device, ordered sums on the host).
+
+    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256]
+
+Per system and R: bootstrap row scales (dsurftomo_amd.invert.bootstrap_row_scales), one warm-up of each path, then the batch
+once and R sequential solves of the explicitly scaled systems (the scaled matrices are loaded outside the timed region; each
+solve is timed alone).  Prints one line per (system, R) and checks realisation 0 of the batch against its sequential solve bit
+for bit.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
+The systems are the product's own (dsa_calsurfg + dsa_iteration_system, or tests/synth_matrix.py): nothing here loads oracle/."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ctypes as C           # noqa: E402
+import _libs as L            # noqa: E402
+import inversion as inv      # noqa: E402  (inv.same only: a bitwise comparison)
+import synth                 # noqa: E402
+from dsurftomo_amd import invert                       # noqa: E402
+from dsurftomo_amd import io as taipei                 # noqa: E402
+from dsurftomo_amd.engine import Engine, load_library  # noqa: E402
+
+
+def product_system(c, fwd, obst, threshold0, weight0):
+    """the system of main.f90:361-466 by the library's dsa_iteration_system: dict(m, n, nar, iw = [nar, rows, cols], rw, b)"""
+    lib = invert.bind(load_library())
+    nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
+    maxvp = (nx - 2) * (ny - 2) * (nz - 1)
+    cap = fwd["nar"] + 7 * maxvp
+    rw = np.zeros(cap, np.float32); rw[:fwd["nar"]] = fwd["rw"]
+    col = np.zeros(cap, np.int32); col[:fwd["nar"]] = fwd["col"]
+    iw = np.zeros(2 * cap + 1, np.int32); iw[1:fwd["nar"] + 1] = fwd["iw"]
+    cbst = np.zeros(dall + maxvp, np.float32); datweight = np.zeros(dall, np.float32)
+    norm = np.zeros(maxvp, np.float32); dws = np.zeros(2, np.float32)
+    m, nar = C.c_int(0), C.c_longlong(0)
+    p = L.ptr
+    rc = lib.dsa_iteration_system(nx, ny, nz, dall, fwd["nar"], cap, p(rw), p(iw), p(col), p(np.ascontiguousarray(obst, np.float32)),
+                                  p(np.ascontiguousarray(fwd["dsurf"], np.float32)), threshold0, weight0, p(cbst), p(datweight), p(norm),
+                                  C.byref(m), C.byref(nar), p(dws))
+    assert rc == 0, rc
+    n = nar.value
+    return dict(m=m.value, n=maxvp, nar=n, iw=iw[:2 * n + 1].copy(), rw=rw[:n].copy(), b=cbst[:m.value].copy())
+
+
+def taipei_system():
+    c = taipei.load()
+    fwd = L.call_boundary(load_library().dsa_calsurfg, c)
+    return product_system(c, fwd, c["obst"], 3.0, 4.0), c["ndata"], 1.0, 400
+
+
+def multiblock_system():
+    import synth_matrix as SM
+    M = SM.system(31522, 47, 47, 31, seed=11)
+    m, n, nar = M["m"], M["n"], M["rw"].size
+    b = np.zeros(m, np.float32)
+    b[:31522] = (SM.mix(np.arange(31522), 12) - 0.5).astype(np.float32)
+    return dict(m=m, n=n, nar=nar, iw=np.concatenate([[nar], M["row"], M["col"]]).astype(np.int32), rw=M["rw"], b=b), 31522, 0.7, 35
+
+
+def headline_system():
+    c = synth.boundary_case(nx=131, ny=131, nz=9, kRc=16, kRg=0, kLc=0, kLg=0, nsrc=1000, nrcf=8, dvd=0.01, ragged=False, stations=True)
+    c["tRc"] = np.linspace(2.0, 17.0, 16)
+    fwd = L.call_boundary(load_library().dsa_calsurfg, c)
+    r = synth.LCG(77)
+    obst = (fwd["dsurf"] * (1.0 + 0.04 * (r.uniform(c["ndata"]) - 0.5))).astype(np.float32)
+    return product_system(c, fwd, obst, 3.0, 2.0), c["ndata"], 1.0, 20
+
+
+def load(e, S, rw=None):
+    nar = S["nar"]
+    e.spmv_load(S["m"], S["n"], S["rw"] if rw is None else rw, S["iw"][1:nar + 1], S["iw"][nar + 1:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--systems", default="taipei,multiblock")
+    ap.add_argument("--R", default="1,8,64,256")
+    ap.add_argument("--seq-max", type=int, default=64, help="sequential solves actually run per R (the rest extrapolated from their mean)")
+    args = ap.parse_args()
+    Rs = [int(v) for v in args.R.split(",")]
+    make = dict(taipei=taipei_system, multiblock=multiblock_system, headline=headline_system)
+    for name in args.systems.split(","):
+        t0 = time.perf_counter()
+        S, ndata, damp, itnlim = make[name]()
+        print("%s: m %d n %d nar %d (set-up %.1f s), damp %g, itnlim %d" % (name, S["m"], S["n"], S["nar"], time.perf_counter() - t0, damp, itnlim), flush=True)
+        rows = S["iw"][1:S["nar"] + 1] - 1
+        e = Engine(0)
+        try:
+            scales = invert.bootstrap_row_scales(ndata, S["m"], max(Rs), seed=1)
+            load(e, S)
+            e.lsmr_batch(S["b"], scales[:2], damp, itnlim=2)              # warm-up: contiguous copies, allocations, code
+            e.lsmr(S["b"], damp, itnlim=2)
+            for R in Rs:
+                load(e, S)
+                e.lsmr_batch(S["b"], scales[:R], damp, itnlim=2)
+                t0 = time.perf_counter()
+                B = e.lsmr_batch(S["b"], scales[:R], damp, itnlim=itnlim)
+                t_batch = time.perf_counter() - t0
+                nseq = min(R, args.seq_max)
+                t_seq, itn_seq, first = 0.0, 0, None
+                for r in range(nseq):
+                    s = scales[r]
+                    load(e, S, (S["rw"] * s[rows]).astype(np.float32))
+                    bs = (S["b"] * s).astype(np.float32)
+                    t0 = time.perf_counter()
+                    got = e.lsmr(bs, damp, itnlim=itnlim)
+                    t_seq += time.perf_counter() - t0
+                    itn_seq += got["itn"]
+                    if r == 0:
+                        first = got
+                t_seq_all = t_seq * R / nseq
+                b0 = dict(x=B["x"][0], istop=int(B["istop"][0]), itn=int(B["itn"][0]), **{k: B[k][0] for k in ("normA", "condA", "normr", "normAr", "normx")})
+                print("%s R %4d: batch %9.1f ms (itn max %d, total %d) | %s%d sequential dsa_lsmr %9.1f ms (%.2f ms per solve, %.1f itn) | "
+                      "speed-up %.1fx | realisation 0 identical: %s" %
+                      (name, R, 1e3 * t_batch, int(B["itn"].max()), int(B["itn"].sum()), "" if nseq == R else "%d of " % nseq, R, 1e3 * t_seq_all,
+                       1e3 * t_seq / nseq, itn_seq / nseq, t_seq_all / t_batch, inv.same(b0, first) == []), flush=True)
+        finally:
+            e.close()
+
+
+if __name__ == "__main__":
+    main()
