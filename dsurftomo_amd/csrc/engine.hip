@@ -939,7 +939,8 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
             if (h_flags[(size_t)u * 4 + 1]) { fail(DSA_ERR_INTERNAL, "unit %d: serial march guard %d (1/17 window, 2/18 tree, 32 exception table)", first + u, h_flags[(size_t)u * 4 + 1]); return DSA_ERR_INTERNAL; }
             // (a coarse solve that never ran a round is NOT an error: for some sources in the last cell before a high edge the reference's own start-up
             // march ends with nothing alive and its field stays zero -- tests/tools/fuzz_parity.py "degenerate in the reference" --, and the engine
-            // returns the same zeros.  The one case of round 6 that looked the same and was a bug -- refined boxes in bundles overwriting the records of
+            // returns the same receiver times, zeros.  Its coarse field there reads infinite (dsa_get_field) where the reference's is zero; the rays
+            // on either take NaN gradients and trace the same path and rows (ray_core.h: cell_of; tests/test_gpu_rows.py).  The one case of round 6 that looked the same and was a bug -- refined boxes in bundles overwriting the records of
             // a unit whose start-up march had ended the refined stage -- is covered by tests/test_gpu_bundles.py.)
             stats[DSA_STAT_ROUNDS_MAX] = std::max(stats[DSA_STAT_ROUNDS_MAX], (double)fi[8]);
             h_unit_rounds[(size_t)(first + u)] = fi[8];

@@ -38,14 +38,26 @@ DSA_HD float sinf_libm(float y)
     return (float)(sgn * (c + x6 * c2));
 }
 
+// (int)v the way the reference's x86 build converts a ray coordinate to a cell index: truncation, and for NaN or a value out of range the
+// "integer indefinite" -2^31 of cvttss2si.  The device's v_cvt_i32_f32 gives 0 for NaN, so a ray whose gradient is NaN (a field without a
+// finite neighbourhood: inf - inf, 0 / 0 -- some sources in the last cell before a high edge) would take cell 1 and stay unclamped where the
+// reference clamps it at the low edge (rbint) and goes on.
+DSA_HD int cell_of(float v)
+{
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (-2147483647 - 1);
+}
+
 // fp32 division by a denominator that stays the same for the whole ray (round 5).  The compiler expands `x / d` into v_div_scale (x2), v_rcp, one
 // Newton step on the reciprocal, the quotient refined twice, v_div_fmas and v_div_fixup -- eleven instructions, and a step of a ray divides
 // some fifty times by the cell sizes of the three grids.  recipf_of / divf_by are that expansion split at the denominator: its reciprocal once
 // per ray, six instructions per quotient; the same instructions on the same operands, minus the rescaling of v_div_scale / v_div_fmas, which
 // acts only when the denominator is denormal or beyond 2^126, the exponents lie 96 apart, the quotient is denormal or the numerator lies
-// below 2^-104.  It is used only where that cannot happen: denominators that are cell sizes in radians (1e-6 .. 1) or twice a cell size in
-// km, numerators that are differences of coordinates in radians or of travel times in seconds -- zero, or no smaller than an ulp of such a
-// number (> 1e-12); zeros and their signs come out of v_div_fixup as the full division has them.  The host build divides.
+// below 2^-104.  Without that rescaling the refinement's residual x - d q leaves the normal range for numerators below 2^-102 (it is a
+// multiple of 2^(e-47) for a numerator of exponent e), and there quotients do differ: measured 15 of 2e8 in [2^-104, 2^-103), 1 of 1e8 in
+// [2^-103, 2^-102), none from 2^-102 up (weights_plain).  It is used only where numerators are at least 2^-100: denominators that are cell
+// sizes in radians (1e-6 .. 1), twice a cell size in km or squared velocities, numerators that are differences of coordinates in radians or
+// of travel times in seconds -- zero, or no smaller than an ulp of such a number (> 1e-12) -- or products of B-spline weights of at least
+// 2^-50; zeros and their signs come out of v_div_fixup as the full division has them.  The host build divides.
 struct RecipF { float d, r; };
 DSA_HD RecipF recipf_of(float d)
 {
@@ -85,13 +97,16 @@ DSA_HD void bspline4_by(float u, float w[4], const RecipF& by_6)
     w[3] = divf_by(u3, by_6);
 }
 
-// four B-spline weights, each zero or at least 2^-52 (see trace_ray's vertex sums); the host build, which divides, does not ask
+// four B-spline weights, each zero or at least 2^-50 (see trace_ray's vertex sums); the host build, which divides, does not ask.
+// Measured (tests/test_gpu_rows.py): with denominators 2^-7 .. 2^15 the shared-reciprocal quotient equals the compiler's division for
+// every fp32 numerator from 2^-102 up in 4e8 pairs, but 15 of 2e8 numerators in [2^-104, 2^-103) and 1 of 1e8 in [2^-103, 2^-102) round
+// differently -- the residual of the refinement leaves the normal range there.  A product of two weights of at least 2^-50 is at least 2^-100.
 DSA_HD bool weights_plain(const float w[4])
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(DSA_RAY_PLAIN_DIV)
     bool ok = true;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) ok = ok && (w[q] == 0.0f || fabsf(w[q]) >= 0x1p-52f);
+    for (int q = 0; q < 4; ++q) ok = ok && (w[q] == 0.0f || fabsf(w[q]) >= 0x1p-50f);
     return ok;
 #else
     return false;
@@ -189,12 +204,12 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
     const int gdx = g.gdx, gdz = g.gdz, ldr = s.rnz;
     const long maxrp = (long)nnx * (long)nnz;
     const float dpl = 0.5f * dpl_cell;
-    const int isx = (int)((scx - goxr) / dnxr) + 1;
-    const int isz = (int)((scz - gozr) / dnzr) + 1;
+    const int isx = cell_of((scx - goxr) / dnxr) + 1;
+    const int isz = cell_of((scz - gozr) / dnzr) + 1;
     int steps = 0;
 
-    int ipx = (int)((rcx - gox) / dnx) + 1;
-    int ipz = (int)((rcz - goz) / dnz) + 1;
+    int ipx = cell_of((rcx - gox) / dnx) + 1;
+    int ipz = cell_of((rcz - goz) / dnz) + 1;
     if (ipx < 1 || ipx >= nnx || ipz < 1 || ipz >= nnz) { *nsteps = 0; return -1; }
 
     float rgx = rcx, rgz = rcz;
@@ -203,8 +218,8 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
     sred = sred + sq((scz - rgz) * earth * sin_at);
     sred = sqrtf(sred);
     bool sw = sred < 2.0f * dpl;
-    int ipxr = (int)((rcx - goxr) / dnxr) + 1;
-    int ipzr = (int)((rcz - gozr) / dnzr) + 1;
+    int ipxr = cell_of((rcx - goxr) / dnxr) + 1;
+    int ipzr = cell_of((rcz - gozr) / dnzr) + 1;
     bool igref = refined_cell_alive(s, f.Sr, ipxr, ipzr);
     if (!sw && igref && ipxr == isx && ipzr == isz) sw = true;
     if (path) { path->push(rgx, rgz); if (sw) path->push(scx, scz); }
@@ -243,11 +258,11 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
         steps += 1;
 
         const int ipxo = ipx, ipzo = ipz;
-        ipxr = (int)divf_by(rgx1 - goxr, by_dnxr) + 1;
-        ipzr = (int)divf_by(rgz1 - gozr, by_dnzr) + 1;
+        ipxr = cell_of(divf_by(rgx1 - goxr, by_dnxr)) + 1;
+        ipzr = cell_of(divf_by(rgz1 - gozr, by_dnzr)) + 1;
         igref = refined_cell_alive(s, f.Sr, ipxr, ipzr);
-        ipx = (int)divf_by(rgx1 - gox, by_dnx) + 1;
-        ipz = (int)divf_by(rgz1 - goz, by_dnz) + 1;
+        ipx = cell_of(divf_by(rgx1 - gox, by_dnx)) + 1;
+        ipz = cell_of(divf_by(rgz1 - goz, by_dnz)) + 1;
 
         sred = sq((scx - rgx1) * earth);
         sin_at = sinf_libm(rgx1);
@@ -316,8 +331,8 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
             const float vrat = (k == nhp) ? 1.0f : (k == 1 ? vr0 : vr1);
             const float rigz = rgz + vrat * (rgz1 - rgz);
             const float rigx = rgx + vrat * (rgx1 - rgx);
-            const int ipxt = (int)divf_by(rigx - gox, by_dnx) + 1;
-            const int ipzt = (int)divf_by(rigz - goz, by_dnz) + 1;
+            const int ipxt = cell_of(divf_by(rigx - gox, by_dnx)) + 1;
+            const int ipzt = cell_of(divf_by(rigz - goz, by_dnz)) + 1;
             drx = (rigx - gox) - (float)(ipxt - 1) * dnx;
             drz = (rigz - goz) - (float)(ipzt - 1) * dnz;
             vel = 0.0f;
@@ -339,8 +354,9 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
             const bool wok_old = wok;
             wok = weights_plain(vi) && weights_plain(wi);
             if (LPR == 1 && wok && wok_old) {
-                // (the thirty-two quotients of a sub-segment through two reciprocals: every weight is zero or at least 2^-52, so a product of two is
-                // zero or at least 2^-104 and the squared velocities are of order ten -- outside v_div_scale's reach, see divf_by)
+                // (the thirty-two quotients of a sub-segment through two reciprocals: every weight is zero or at least 2^-50, so a product of two is
+                // zero or at least 2^-100 and the squared velocities are of order ten -- where the quotients measure equal to the division, see
+                // weights_plain)
                 const RecipF by_v2 = recipf_of(v2), by_vo2 = recipf_of(vo2);
 #pragma unroll
                 for (int l = 0; l < 4; ++l)

@@ -60,6 +60,7 @@ def load_library():
     L.dsa_get_velocity.argtypes = [_vp, _i32, _vp]
     L.dsa_get_refined.argtypes = [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]
     L.dsa_get_stats.argtypes = [_vp, _vp]
+    L.dsa_ray_diagnostics.argtypes = [_vp, C.POINTER(C.c_longlong), C.POINTER(_i32)]
     L.dsa_unit_ties.argtypes = [_vp, _i32, _vp, _vp]
     L.dsa_unit_rounds.argtypes = [_vp, _i32, _vp]
     if hasattr(L, "dsa_unit_tie_sums"):          # (absent from libraries of rounds 1-5: same-box A/B runs against an old build, DSA_LIB_PATH)
@@ -286,6 +287,16 @@ class Engine:
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)
         return self.solve()
+
+    def keep_fields(self, on):
+        """keep every planned unit's fields resident after a solve (field / refined of any unit); plan fails when they do not fit one chunk"""
+        self._check(self._L.dsa_keep_fields(self._h, int(bool(on))))
+
+    def ray_diagnostics(self):
+        """rays of the last solve_rows clamped at the model edge (reference rbint) and the planned unit of the first of them (-1: none)"""
+        n, u = C.c_longlong(0), _i32(0)
+        self._check(self._L.dsa_ray_diagnostics(self._h, C.byref(n), C.byref(u)))
+        return n.value, u.value
 
     def field(self, unit):
         """coarse travel-time field of a unit of the last chunk, indexed [ix, iz]"""

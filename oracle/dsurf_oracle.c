@@ -956,11 +956,10 @@ static inline float r2(float x) { return x * x; }
 static inline float r3(float x) { return (x * x) * x; }
 static inline float r4(float x) { return ((x * x) * x) * x; }
 
-/* Frechet row of one ray from its vertex kernel fdm; CalSurfG.f90:1383-1432.
- * sen_*: (nx*ny, kmax, nz) doubles; slot: 0-based period slot. Appends to rw/iw/col. */
-static void assemble_row(int nx, int ny, int nz, const float *vels, const float *depz, const float *fdm,
-                         const double *sen_vs, const double *sen_vp, const double *sen_rho, int kmax, int slot,
-                         float *row, int rownum, float *rw, int *iw, int *col, int *nar)
+/* Frechet row of one ray from its vertex kernel fdm; CalSurfG.f90:1383-1432 (declared in dsurf_oracle.h). */
+void dso_assemble_row(int nx, int ny, int nz, const float *vels, const float *depz, const float *fdm,
+                      const double *sen_vs, const double *sen_vp, const double *sen_rho, int kmax, int slot,
+                      float *row, int rownum, float *rw, int *iw, int *col, int *nar)
 {
     const int nvx = nx - 2, nvz = ny - 2, nparpi = nvx * nvz * (nz - 1);
     const size_t ncol = (size_t)nx * ny;
@@ -1072,7 +1071,7 @@ int dso_calsurfg(const int *pnx, const int *pny, const int *pnz, const int *pnpa
                     if (gr == 0 || (ig == 2 && gr == 1)) {
                         count11 += 1;
                         if (dso_rpaths(&g, &b, veln, ttn, ttnr, nstsr, x, z, rcxf[ri], rczf[ri], fdm, &rbint, NULL) != 0) { rc = -3; break; }
-                        assemble_row(nx, ny, nz, vels, depz, fdm, sen_vs, sen_vp, sen_rho, kmax, knumi - 1, row, count11, rw, iw, col, nar);
+                        dso_assemble_row(nx, ny, nz, vels, depz, fdm, sen_vs, sen_vp, sen_rho, kmax, knumi - 1, row, count11, rw, iw, col, nar);
                     }
                 }
             }

@@ -79,6 +79,15 @@ int dso_rpaths_path(const dso_grid *g, const dso_box *b, const float *veln, cons
                     const float *ttnr, const int *nstsr, float scx, float scz, float surfrcx, float surfrcz,
                     float *fdm, int *rbint, int *nsteps, float *path, int cap, int *npath);
 
+/* Frechet row of one ray from its vertex kernel fdm (as dso_rpaths leaves it); CalSurfG.f90:1383-1432.
+ * vels: (nx, ny, nz) floats column-major; sen_*: (nx*ny, kmax, nz) doubles; slot: 0-based period slot; row: nparpi floats of
+ * scratch; rownum: 1-based row (datum).  Appends the row's entries above 1e-4 in magnitude, columns ascending:
+ * rw[*nar] value, iw[*nar + 1] = rownum (iw[0] is left for the entry count, the layout aprod takes), col[*nar] 1-based column;
+ * *nar counts them. */
+void dso_assemble_row(int nx, int ny, int nz, const float *vels, const float *depz, const float *fdm,
+                      const double *sen_vs, const double *sen_vp, const double *sen_rho, int kmax, int slot,
+                      float *row, int rownum, float *rw, int *iw, int *col, int *nar);
+
 /* dispersion side (surfdisp_oracle.c) ------------------------------------------------------- */
 
 /* surfdisp96, surfdisp96.f:52-350. thk/vp/vs/rho: nlayer floats; t: kmax doubles; cg out */

@@ -77,6 +77,8 @@ def oracle():
         L.dso_srtimes.argtypes = [C.POINTER(Grid), vp, vp, f32, f32, f32, f32, C.POINTER(f32)]
         L.dso_rpaths.argtypes = [C.POINTER(Grid), C.POINTER(Box), vp, vp, vp, vp, f32, f32, f32, f32, vp,
                                  C.POINTER(i32), C.POINTER(i32)]
+        L.dso_assemble_row.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]
+        L.dso_assemble_row.restype = None
         _oracle = L
     return _oracle
 
@@ -150,6 +152,31 @@ def o_rpaths(g, sol, veln, sx, sz, rx, rz):
     if rc != 0:
         raise ValueError("receiver outside grid")
     return fdm, rb.value, ns.value
+
+
+class RowAssembler:
+    """dso_assemble_row with its depth kernels: vels (nz, ny, nx) fp32 [Fortran vels(nx,ny,nz)], sen_* (nz, kmax, ny*nx) fp64
+    [Fortran (nx*ny, kmax, nz)], as Engine.set_depth_kernels takes them.  One instance per thread (it owns its scratch)."""
+
+    def __init__(self, vels, depz, sen_vs, sen_vp, sen_rho):
+        self.vels = np.ascontiguousarray(vels, np.float32)
+        self.depz = np.ascontiguousarray(depz, np.float32)
+        self.sen = [np.ascontiguousarray(a, np.float64) for a in (sen_vs, sen_vp, sen_rho)]
+        self.nz, self.ny, self.nx = self.vels.shape
+        self.kmax = self.sen[0].shape[1]
+        npar = (self.nx - 2) * (self.ny - 2) * (self.nz - 1)
+        self.row = np.zeros(npar, np.float32)
+        self.rw, self.iw, self.col = np.zeros(npar, np.float32), np.zeros(npar + 1, np.int32), np.zeros(npar, np.int32)
+
+    def __call__(self, fdm, slot, rownum):
+        """the row of one ray (fdm as o_rpaths returns it) as (rw, iw, col), iw and col 1-based"""
+        fdm = np.ascontiguousarray(fdm, np.float32)
+        assert fdm.shape == (self.nx, self.ny) and 0 <= slot < self.kmax
+        n = i32(0)
+        oracle().dso_assemble_row(self.nx, self.ny, self.nz, ptr(self.vels), ptr(self.depz), ptr(fdm), *[ptr(a) for a in self.sen],
+                                  self.kmax, int(slot), ptr(self.row), int(rownum), ptr(self.rw), ptr(self.iw), ptr(self.col), C.byref(n))
+        k = n.value
+        return self.rw[:k].copy(), self.iw[1:k + 1].copy(), self.col[:k].copy()
 
 
 def o_ray_path(g, sol, veln, sx, sz, rx, rz, cap=1 << 16):
