@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CalSurfG hot path on MI355X: (period, source) eikonal solves per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2] / configs[3]): 1025x1025 propagation grid
@@ -18,16 +18,22 @@ receiver-time vector is completed on every rank by an RCCL all-gather and put in
 order: total work is fixed ("strong" scaling, as configs[3] states).  `python bench.py --gpus N` without a launcher starts the N ranks itself (one
 child process per GPU, before anything in the parent touches the GPU).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, the settling and warm-up
+passes, the K timed steps, --dump-outputs, and the line, whose figures come from the timed steps themselves (HIP
+events and engine counters) or from records already in the tree:
   roofline      dominant kernel (the coarse fixed-point solve): algorithmic bytes / launch time from HIP
                 events recorded on the engine's own stream; `traffic` (fabric bytes per launch) and
                 `valu_issue` come from the rocprofv3 --pmc passes of tools/profile_bench.sh, which
                 records the hash of the kernel sources: a file made from other sources is ignored (null)
+--full adds, after the timed steps, everything that takes runs of its own (minutes on one MI355X):
   cpu_baseline  the reference's own Fortran (oracle/_ref, single core) -- or the C oracle if that library
-                is absent -- on a bounded sample of the same workload
+                is absent -- on a bounded sample of the same workload (not with --no-cpu-baseline)
   max_abs_err   the parity half of the metric: largest |t_gpu - t_ref| over the receiver times of the
                 sampled units (the reference times are the ones cpu_baseline computes), with the count
-                beyond the 1e-4 s bar
+                beyond the 1e-4 s bar (not with --no-cpu-baseline; null in a plain run)
+  secondary     the other media, modes, sizes and kernels (not with --no-secondary)
+  tolerance_violation / tolerance_checks
+                whether any default-mode time those checks hold lies beyond 1e-4 s (null when none ran)
 """
 import argparse
 import hashlib
@@ -236,7 +242,8 @@ def headline_all_receivers(eng, units, pv, default_times):
 
 def tolerance_summary(line):
     """ every place this line holds default-mode times checked against the reference -- or against exact_ties = 2, which is the
-    reference bit for bit -- and how many of them lie beyond 1e-4 s; `tolerance_violation` at the top of the line is true when any does."""
+    reference bit for bit -- and how many of them lie beyond 1e-4 s; `tolerance_violation` at the top of the line is true when any does, and
+    null when the line holds no such check (a plain run: they are --full's)."""
     checks = {}
     par = line.get("parity")
     if par:
@@ -254,7 +261,7 @@ def tolerance_summary(line):
         checks["config4_share_default_sample_vs_reference"] = c4["vs_reference_sample"].get("beyond_1e-4_s")
     if "units_left_to_the_fixed_point" in c4:
         checks["config4_share_default_units_left_alone"] = c4["units_left_to_the_fixed_point"].get("receiver_times_beyond_1e-4_s")
-    return bool(any(v for v in checks.values() if v)), checks
+    return (bool(any(v for v in checks.values() if v)) if checks else None), checks
 
 
 def config4_share(device_index, with_reference=True):
@@ -449,6 +456,8 @@ def spawn_ranks(args):
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        if args.full:
+            cmd.append("--full")
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.no_secondary:
@@ -489,13 +498,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (the counter passes of tools/profile_bench.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: the CPU baseline and the checks against the reference, "
+                         "and the secondary legs (other media, modes, sizes and kernels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no comparison with the reference's path")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (the receiver times, in the reference's order) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    with_reference = args.full and not args.no_cpu_baseline
+    with_secondary = args.full and not args.no_secondary
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
@@ -641,7 +655,7 @@ def main():
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "configs[2]: 1025x1025 grid (nx=ny=131, dicing 8), 16 periods x 1000 sources, 32 receivers each, smooth +-10% velocity",
                        "medium_note": "the 16 maps are one pattern times a scale per period (BASELINE configs[2]): the best case for the bundle kernel, which solves the periods of a "
-                                      "source under one shared schedule; secondary.bundling_on_unrelated_maps holds the figure for maps that have nothing in common",
+                                      "source under one shared schedule; secondary.bundling_on_unrelated_maps (--full) holds the figure for maps that have nothing in common",
                        "grid": n, "units_per_step": total_units, "receivers_per_step": total_units * NREC,
                        "parallelism": "sources (all their periods) sharded over %d rank(s) on %d GPU(s), %s all-gather of receiver times" % (world, min(world, ndev), "gloo (shared devices)" if shared else "RCCL")},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -678,11 +692,11 @@ def main():
                              "largest_tie_influence_s": float(st.get("tie_influence_max", 0.0)),
                              "note": "no tie on these maps reaches tie_threshold (largest: one or two ulps of the travel time), so nothing is marched; the units that hold such "
                                      "small ties stay with the fixed point, whose times are the reference's to 1e-4 s by measurement, not by construction: "
-                                     "secondary.headline_all_receivers checks every receiver time of the call against exact_ties = 2.  The measurement behind it is an envelope -- at "
+                                     "secondary.headline_all_receivers (--full) checks every receiver time of the call against exact_ties = 2.  The measurement behind it is an envelope -- at "
                                      "most 26 ulps of the travel time at a receiver on grids up to 1025^2 in all but about one unit in 400 000 (36 ulps seen), i.e. within 1e-4 s while the times stay below 64 s, as this call's do; a unit "
                                      "that holds a tie and lies outside (longer paths, larger grids) is marched (option tie_scale_guard; DESIGN.md 'Ties')"},
         }
-        if not args.no_cpu_baseline:
+        if with_reference:
             # N = 1: the bounded CPU baseline (its times are the parity reference).  N > 1: no baseline line (contract), but the
             # gathered vector is still checked against the reference on a smaller sample of units
             rec, pick, ref_times = cpu_baseline(64 if world == 1 else 16)
@@ -698,25 +712,26 @@ def main():
             line["parity"] = {"checked_receiver_times": int(d.size), "units": int(len(pick)), "beyond_1e-4_s": int((d > TOL).sum()),
                               "not_bit_identical": int((got.view(np.uint32) != ref_times.view(np.uint32)).sum()),
                               "against": rec["kind"], "tolerance_s": TOL}
-        # secondary legs (rank 0, after the timed region; none of them may take the headline line down with it)
-        line["secondary"] = {}
-        full_units = dict(map_index=units["map_index"], scx=units["scx"], scz=units["scz"], nrec=units["nrec"], rcx=units["rcx"], rcz=units["rcz"])
-        last_host_all = last.detach().cpu().numpy() if hasattr(last, "detach") else np.asarray(last, np.float32)
-        legs = [("headline_all_receivers", lambda: headline_all_receivers(eng, full_units, pv, last_host_all)),
-                ("tie_modes_headline", lambda: tie_modes_headline(eng, full_units, pv)),
-                ("exact_mode", lambda: exact_secondary(eng, with_reference=not args.no_cpu_baseline)), ("bundling_on_unrelated_maps", lambda: bundling_secondary(eng)),
-                ("rays", lambda: rays_secondary(eng)), ("dispersion", lambda: dispersion_secondary(eng)),
-                ("config4_share", lambda: (eng.close(), config4_share(device_index, with_reference=not args.no_cpu_baseline))[1])]
-        if world > 1:          # (the other ranks wait in the closing barrier: the two long legs -- 16 000 and 3 072 marching units -- belong to the N = 1 line)
-            legs = [l for l in legs if l[0] not in ("exact_mode", "config4_share", "headline_all_receivers")]
-            line["secondary"]["note"] = "N > 1: headline_all_receivers, exact_mode and config4_share are legs of the N = 1 line"
-        for name, leg in legs:
-            if args.no_secondary:
-                break
-            try:
-                line["secondary"][name] = leg()
-            except Exception as ex:
-                line["secondary"][name] = {"error": str(ex)[:300]}
+        if args.full:
+            # secondary legs (rank 0, after the timed region; none of them may take the headline line down with it)
+            line["secondary"] = {}
+            full_units = dict(map_index=units["map_index"], scx=units["scx"], scz=units["scz"], nrec=units["nrec"], rcx=units["rcx"], rcz=units["rcz"])
+            last_host_all = last.detach().cpu().numpy() if hasattr(last, "detach") else np.asarray(last, np.float32)
+            legs = [("headline_all_receivers", lambda: headline_all_receivers(eng, full_units, pv, last_host_all)),
+                    ("tie_modes_headline", lambda: tie_modes_headline(eng, full_units, pv)),
+                    ("exact_mode", lambda: exact_secondary(eng, with_reference=with_reference)), ("bundling_on_unrelated_maps", lambda: bundling_secondary(eng)),
+                    ("rays", lambda: rays_secondary(eng)), ("dispersion", lambda: dispersion_secondary(eng)),
+                    ("config4_share", lambda: (eng.close(), config4_share(device_index, with_reference=with_reference))[1])]
+            if world > 1:          # (the other ranks wait in the closing barrier: the two long legs -- 16 000 and 3 072 marching units -- belong to the N = 1 line)
+                legs = [l for l in legs if l[0] not in ("exact_mode", "config4_share", "headline_all_receivers")]
+                line["secondary"]["note"] = "N > 1: headline_all_receivers, exact_mode and config4_share are legs of the N = 1 line"
+            for name, leg in legs:
+                if not with_secondary:
+                    break
+                try:
+                    line["secondary"][name] = leg()
+                except Exception as ex:
+                    line["secondary"][name] = {"error": str(ex)[:300]}
         viol, checks = tolerance_summary(line)
         line = {**{k: line[k] for k in ("metric", "value", "unit")}, "tolerance_violation": viol, "tolerance_checks": checks, **{k: v for k, v in line.items() if k not in ("metric", "value", "unit")}}
         print(json.dumps(line), flush=True)

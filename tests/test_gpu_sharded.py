@@ -115,3 +115,33 @@ def test_bench_dump_outputs(tmp_path):
     t = np.load(tmp_path / "receiver_times.npy")
     assert t.dtype == np.float32 and t.shape == (16000, 32)
     assert np.isfinite(t).all() and (t > 0).all()
+
+
+def _bench_line(*args):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", *args], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """without --full the line holds the headline's figures and nothing that takes runs of its own: no CPU baseline, no comparison with
+    the reference, no secondary legs, and so no tolerance verdict (null, not false)"""
+    rec = _bench_line()
+    assert rec["unit"] == "solves/s" and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["roofline"]["achieved"] > 0 and rec["config"]["units_per_step"] == 16000
+    assert not {"cpu_baseline", "parity", "secondary"} & rec.keys()
+    assert rec["max_abs_err"] is None and rec["vs_baseline"] is None
+    assert rec["tolerance_violation"] is None and rec["tolerance_checks"] == {}
+
+
+def test_bench_full_checks_the_headline_against_the_reference():
+    """--full (secondary legs left out here: they take minutes) still runs the CPU baseline and checks the timed step's receiver times
+    against the reference's on the sampled units"""
+    rec = _bench_line("--full", "--no-secondary")
+    assert rec["cpu_baseline"]["value"] > 0 and rec["vs_baseline"] > 0
+    assert rec["parity"]["checked_receiver_times"] == 64 * 32 and rec["parity"]["beyond_1e-4_s"] == 0
+    assert 0 <= rec["max_abs_err"] <= 1e-4
+    assert rec["tolerance_violation"] is False and rec["tolerance_checks"] == {"headline_sample_vs_reference": 0}
+    assert rec["secondary"] == {}

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 # (round 6: the trace pass profiles the HEADLINE alone -- with the secondary legs in it the dominant-kernel rows mixed the headline's launches with the
 # legs' and k_xmarch of the checkerboard legs topped the table: VERDICT r05 weak 6; DSA_PROFILE_SECONDARY=1 adds a second trace of the whole command)
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o r -- python3 bench.py --no-cpu-baseline --no-secondary > $OUT/trace.log 2>&1
-if [ -n "${DSA_PROFILE_SECONDARY:-}" ]; then timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace_all -o r -- python3 bench.py --no-cpu-baseline > $OUT/trace_all.log 2>&1; fi
+if [ -n "${DSA_PROFILE_SECONDARY:-}" ]; then timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace_all -o r -- python3 bench.py --full --no-cpu-baseline > $OUT/trace_all.log 2>&1; fi
 for g in "fetch FETCH_SIZE" "write WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" "busy SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" \
          "insts SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS" "wait SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVES"; do
   set -- $g; n=$1; shift

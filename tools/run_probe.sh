@@ -5,7 +5,7 @@
 #   tests            the GPU test suite (pytest -m gpu)
 #   tests:<expr>     ... restricted with -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            python3 bench.py --steps 5 --warmup 2
+#   bench            python3 bench.py --steps 5 --warmup 2 --full
 #   profile          tools/profile_bench.sh <tag> (rocprofv3 kernel trace + counter passes of the bench command)
 #   exact:<args>     tools/exact_probe.py <args with , for spaces>          e.g. exact:131,4096,checker,0,0
 #   bundle:<args>    tools/bundle_probe.py <args with , for spaces>
@@ -20,7 +20,7 @@ for job in "$@"; do
   case $name in
     tests)   if [ -n "$arg" ]; then timeout $T python3 -m pytest tests -m gpu -x -q -k "$arg" > $log 2>&1; else timeout $T python3 -m pytest tests -m gpu -x -q > $log 2>&1; fi ;;
     smoke)   timeout $T python3 -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 ;;
-    bench)   timeout $T python3 bench.py --steps 5 --warmup 2 > $log 2>&1 ;;
+    bench)   timeout $T python3 bench.py --steps 5 --warmup 2 --full > $log 2>&1 ;;
     profile) bash tools/profile_bench.sh $TAG > $log 2>&1 ;;
     exact)   timeout $T python3 tools/exact_probe.py ${arg//,/ } > $log 2>&1 ;;
     bundle)  timeout $T python3 tools/bundle_probe.py ${arg//,/ } > $log 2>&1 ;;
