@@ -20,6 +20,11 @@
 //   * element-wise updates with per-realisation coefficients and masks.
 // The scalar recurrences are dsa::LsmrScalars (lsmr_core.h), the same code dsa_lsmr runs, one per realisation.  A realisation that
 // stops is frozen: no kernel writes its lanes again.  Three host synchronisations per iteration (beta, alpha, normx: nreal values each).
+//
+// dsa_lsmr_resolution runs the same loop (batch_begin, then its own way of filling u and the row scales, then batch_solve) on the
+// right-hand sides of test models, formed on the device: v = the models (unit spikes made in place, or host models), row scales 1,
+// u = A v by k_b_spmv<true> (fl(a * 1) = a: the chain of dsa_spmv mode 1 from y = 0), then the regularisation rows zeroed.  For
+// spikes, k_b_psf_part / k_b_psf_sum reduce each solution to its PSF measures on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -369,28 +374,157 @@ int build_contiguous(Engine* e, const SpmvState::Ordering& O, int nseg, long lon
 // element-wise launch over every group's len * 64 elements
 dim3 grid_of(int len, int G) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, ((size_t)len * 64 + 255) / 256)), (unsigned)G); }
 
-}  // namespace
+// ---- dsa_lsmr_resolution: the right-hand sides b_r = A m_r (data rows), formed on the device, and the PSF measures ----
 
-}  // namespace dsa
-
-using dsa::Engine;
-using dsa::SpmvState;
-
-extern "C" {
-
-int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_scale, float damp, float atol, float btol, float conlim, int itnlim,
-                   int localSize, float* x, int* istop, int* itn, float* est)
+// (g, i, l) of the batch layout <- realisation-major input[r * len + i] (0 past nreal)
+__global__ void k_b_scatter(int len, int nreal, const float* __restrict__ in, float* __restrict__ out)
 {
-    using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (nreal < 1 || nreal > 64 * 65535 || !b || !row_scale || !x || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_batch: nreal < 1 or a null argument"); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_batch: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    LB_GROUP_LOOP(len) {
+        const int r = g * 64 + (int)(t & 63);
+        out[gbase + t] = r < nreal ? in[(size_t)r * (size_t)len + (t >> 6)] : 0.0f;
+    }
+}
+
+// unit spikes: element i of realisation r is 1 where i == first + r (r < nreal), else 0
+__global__ void k_b_spike(int n, int nreal, int first, float* __restrict__ out)
+{
+    LB_GROUP_LOOP(n) {
+        const int r = g * 64 + (int)(t & 63);
+        out[gbase + t] = (r < nreal && (long long)(t >> 6) == (long long)first + r) ? 1.0f : 0.0f;
+    }
+}
+
+// row scales of the unscaled matrix: 1 (0 past nreal, as k_b_init leaves them)
+__global__ void k_b_ones(int m, int nreal, float* __restrict__ scale)
+{
+    LB_GROUP_LOOP(m) scale[gbase + t] = g * 64 + (int)(t & 63) < nreal ? 1.0f : 0.0f;
+}
+
+// rows [ndata, m) of every group's u <- +0 (the regularisation rows of the right-hand side)
+__global__ void k_b_zero_rows(int m, int ndata, float* __restrict__ u)
+{
+    float* __restrict__ p = u + ((size_t)blockIdx.y * (size_t)m + (size_t)ndata) * 64;
+    const size_t len = (size_t)(m - ndata) * 64;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < len; t += (size_t)gridDim.x * blockDim.x) p[t] = 0.0f;
+}
+
+// PSF measures of spike realisation r (unknown j = first + r) over its solution x_r: sum x^2, sum x^2 dh^2, sum x^2 dz^2 in fp64, dh the
+// great-circle distance (haversine, sphere of kEarthKm) and dz the depth difference from unknown j; coords = (lat deg, lon deg, depth km)
+// per unknown.  k_b_psf_part: block (b, g), four wavefronts, wavefront w the elements [b kPsfE + w kPsfE/4, +kPsfE/4) in order, one
+// coalesced 256-byte load of bx per element; the four wavefronts' sums added in order.  k_b_psf_sum: the blocks' partials in order.
+constexpr int kPsfE = 1024;                 // elements per block
+constexpr double kEarthKm = 6371.0;
+
+constexpr double kD2R = 3.14159265358979323846 / 180.0;
+
+// cosl[i] = cos(latitude of unknown i), once per call (psf_dh needs it for both ends of every distance)
+__global__ void k_psf_cos(int n, const double* __restrict__ coords, double* __restrict__ cosl)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) cosl[i] = cos(coords[3 * (size_t)i] * kD2R);
+}
+
+__device__ inline double psf_dh(double lat_i, double lon_i, double cos_i, double lat_j, double lon_j, double cos_j)
+{
+    const double sp = sin((lat_i - lat_j) * kD2R * 0.5), sl = sin((lon_i - lon_j) * kD2R * 0.5);
+    const double a = sp * sp + cos_i * cos_j * sl * sl;
+    return 2.0 * kEarthKm * asin(fmin(1.0, sqrt(a)));
+}
+
+__global__ __launch_bounds__(256) void k_b_psf_part(int n, int nb, int first, const double* __restrict__ coords, const double* __restrict__ cosl,
+                                                    const float* __restrict__ x, double* __restrict__ part)
+{
+    __shared__ double red[3][4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, b = blockIdx.x;
+    const long long jj = (long long)first + g * 64 + lane;
+    const int j = jj < n ? (int)jj : n - 1;                           // (padding lanes: any unknown, never read back)
+    const double lat_j = coords[3 * (size_t)j], lon_j = coords[3 * (size_t)j + 1], dep_j = coords[3 * (size_t)j + 2], cos_j = cosl[j];
+    const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
+    const int e0 = b * kPsfE + w * (kPsfE / 4), e1 = min(e0 + kPsfE / 4, n);
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int e = e0; e < e1; ++e) {
+        const double xv = (double)p[(size_t)e * 64];
+        if (xv == 0.0) continue;                                          // (its terms are +0)
+        const double q = xv * xv;
+        const double dh = psf_dh(coords[3 * (size_t)e], coords[3 * (size_t)e + 1], cosl[e], lat_j, lon_j, cos_j);
+        const double dz = coords[3 * (size_t)e + 2] - dep_j;
+        s1 = s1 + q;
+        s2 = s2 + q * (dh * dh);
+        s3 = s3 + q * (dz * dz);
+    }
+    red[0][w][lane] = s1; red[1][w][lane] = s2; red[2][w][lane] = s3;
+    __syncthreads();
+    if (w == 0) {
+        double* __restrict__ o = part + (((size_t)g * nb + b) * 64 + lane) * 3;
+        for (int c = 0; c < 3; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
+    }
+}
+
+// psf[4 r .. 4 r + 3] = {x_r[j], the three sums}; one thread per realisation
+__global__ __launch_bounds__(64) void k_b_psf_sum(int n, int nb, int nreal, int first, const float* __restrict__ x, const double* __restrict__ part,
+                                                  double* __restrict__ psf)
+{
+    const int lane = threadIdx.x, g = blockIdx.x, r = g * 64 + lane;
+    if (r >= nreal) return;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int b = 0; b < nb; ++b) {
+        const double* __restrict__ q = part + (((size_t)g * nb + b) * 64 + lane) * 3;
+        for (int c = 0; c < 3; ++c) s[c] = s[c] + q[c];
+    }
+    psf[4 * (size_t)r] = (double)x[((size_t)g * n + (size_t)(first + r)) * 64 + lane];
+    for (int c = 0; c < 3; ++c) psf[4 * (size_t)r + 1 + c] = s[c];
+}
+
+// ---- the batch shared by dsa_lsmr_batch and dsa_lsmr_resolution: set-up, then (the caller fills u and the row scales) the LSMR loop ----
+struct Batch {
+    Engine* e = nullptr;
+    SpmvState* S = nullptr;
+    int m = 0, n = 0, G = 0, Rp = 0, localVecs = 0;
+    size_t vm = 0, vn = 0;
+    hipStream_t st = nullptr;
+    // host mirror of bparam, then Rp norms.  The host writes the mirror only after a synchronisation that follows the previous upload.
+    float* hc = nullptr;
+    int* hf = nullptr;
+    float* hred = nullptr;
+
+    const float* coef(int f) const { return S->bparam.p + (size_t)f * Rp; }
+    const int* flag(int f) const { return reinterpret_cast<const int*>(S->bparam.p + (size_t)NCOEF * Rp) + (size_t)f * Rp; }
+    int upload() { LB_TRY(e, hipMemcpyAsync(S->bparam.p, S->hbatch, (size_t)kNParam * Rp * 4, hipMemcpyHostToDevice, st)); return 0; }
+    // dnrm2 of every realisation's v (len elements): terms and scales by the wide kernels, then the chains
+    int norm(int len, const float* v)
+    {
+        const int nb = (len + kPB - 1) / kPB;
+        hipLaunchKernelGGL(k_pm_blockmax, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, S->bpmax.p);
+        hipLaunchKernelGGL(k_pm_scan, dim3(G), dim3(64), 0, st, nb, S->bpmax.p, S->bred.p + 2 * (size_t)Rp);
+        hipLaunchKernelGGL(k_pm_terms, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, (const float*)S->bpmax.p, S->bterm.p);
+        hipLaunchKernelGGL(k_b_chain<false>, dim3(G), dim3(kCT), 0, st, len, (const float*)S->bterm.p, (const float*)nullptr,
+                           (const float*)(S->bred.p + 2 * (size_t)Rp), v, S->bred.p);
+        LB_TRY(e, hipMemcpyAsync(hred, S->bred.p, (size_t)Rp * 4, hipMemcpyDeviceToHost, st));
+        LB_TRY(e, hipStreamSynchronize(st));
+        return 0;
+    }
+    // mode 1: u = pre_r u + A v; mode 2: v = pre_r v + A' u (where the flag is set)
+    void product(int mode, const float* pre, const int* fl)
+    {
+        if (mode == 1)
+            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S->row_csr.ptr.p, S->row_csr.val.p, S->row_csr.idx.p,
+                               (const float*)S->bscale.p, (const float*)S->bv.p, S->bu.p, pre, fl);
+        else
+            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S->col_csr.ptr.p, S->col_csr.val.p, S->col_csr.idx.p,
+                               (const float*)S->bscale.p, (const float*)S->bu.p, S->bv.p, pre, fl);
+    }
+};
+
+// contiguous copies, buffers for nreal realisations (btmp: `tmp` floats), the host mirror cleared
+int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B)
+{
     SpmvState& S = *e->spmv;
+    B.e = e; B.S = &S;
     const int m = S.m, n = S.n, G = (nreal + 63) / 64, Rp = 64 * G;
-    const int localVecs = std::max(0, std::min(localSize, std::min(m, n)));                      // :365
-    const size_t vm = (size_t)G * m * 64, vn = (size_t)G * n * 64;
-    hipStream_t st = e->stream;
+    B.m = m; B.n = n; B.G = G; B.Rp = Rp;
+    B.localVecs = std::max(0, std::min(localSize, std::min(m, n)));                              // :365
+    B.vm = (size_t)G * m * 64; B.vn = (size_t)G * n * 64;
+    B.st = e->stream;
+    const size_t vm = B.vm, vn = B.vn;
     LB_TRY(e, hipSetDevice(e->device));
     if (!S.contiguous_valid) {
         int rc = build_contiguous(e, S.by_row, m, S.nar, S.row_csr);
@@ -398,11 +532,10 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
         if (rc != 0) return rc;
         S.contiguous_valid = true;
     }
-    const size_t tmp = std::max((size_t)nreal * m + m, (size_t)nreal * n);
     if (e->ensure(S.bu, vm) || e->ensure(S.bscale, vm) || e->ensure(S.bv, vn) || e->ensure(S.bh, vn) || e->ensure(S.bhbar, vn) || e->ensure(S.bx, vn) ||
-        e->ensure(S.blocalV, std::max<size_t>(vn * (size_t)localVecs, 1)) || e->ensure(S.bparam, (size_t)kNParam * Rp) || e->ensure(S.bred, 3 * (size_t)Rp) ||
+        e->ensure(S.blocalV, std::max<size_t>(vn * (size_t)B.localVecs, 1)) || e->ensure(S.bparam, (size_t)kNParam * Rp) || e->ensure(S.bred, 3 * (size_t)Rp) ||
         e->ensure(S.bterm, std::max(vm, vn)) || e->ensure(S.bpmax, (size_t)G * ((std::max(m, n) + kPB - 1) / kPB) * 64) ||
-        e->ensure(S.btmp, tmp)) return e->status;
+        e->ensure(S.btmp, std::max<size_t>(tmp, 1))) return e->status;
     const size_t hwords = (size_t)(kNParam + 1) * Rp;
     if (S.hbatch_cap < hwords) {
         if (S.hbatch) (void)hipHostFree(S.hbatch);
@@ -410,52 +543,37 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
         LB_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&S.hbatch), hwords * 4, hipHostMallocDefault));
         S.hbatch_cap = hwords;
     }
-    // host mirror of bparam, then nreal norms.  The host writes the mirror only after a synchronisation that follows the previous upload.
-    float* hc = S.hbatch;
-    int* hf = reinterpret_cast<int*>(S.hbatch + (size_t)NCOEF * Rp);
-    float* hred = S.hbatch + (size_t)kNParam * Rp;
+    B.hc = S.hbatch;
+    B.hf = reinterpret_cast<int*>(S.hbatch + (size_t)NCOEF * Rp);
+    B.hred = S.hbatch + (size_t)kNParam * Rp;
     std::memset(S.hbatch, 0, hwords * 4);
-    const float* dc = S.bparam.p;
-    const int* df = reinterpret_cast<const int*>(S.bparam.p + (size_t)NCOEF * Rp);
-    auto coef = [&](int f) { return dc + (size_t)f * Rp; };
-    auto flag = [&](int f) { return df + (size_t)f * Rp; };
-    auto upload = [&]() -> int { LB_TRY(e, hipMemcpyAsync(S.bparam.p, S.hbatch, (size_t)kNParam * Rp * 4, hipMemcpyHostToDevice, st)); return 0; };
-    // dnrm2 of every realisation's v (len elements): terms and scales by the wide kernels, then the chains
-    auto norm = [&](int len, const float* v) -> int {
-        const int nb = (len + kPB - 1) / kPB;
-        hipLaunchKernelGGL(k_pm_blockmax, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, S.bpmax.p);
-        hipLaunchKernelGGL(k_pm_scan, dim3(G), dim3(64), 0, st, nb, S.bpmax.p, S.bred.p + 2 * (size_t)Rp);
-        hipLaunchKernelGGL(k_pm_terms, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, len, nb, v, (const float*)S.bpmax.p, S.bterm.p);
-        hipLaunchKernelGGL(k_b_chain<false>, dim3(G), dim3(kCT), 0, st, len, (const float*)S.bterm.p, (const float*)nullptr,
-                           (const float*)(S.bred.p + 2 * (size_t)Rp), v, S.bred.p);
-        LB_TRY(e, hipMemcpyAsync(hred, S.bred.p, (size_t)Rp * 4, hipMemcpyDeviceToHost, st));
-        LB_TRY(e, hipStreamSynchronize(st));
-        return 0;
-    };
-    auto product = [&](int mode, const float* pre, const int* fl) {
-        if (mode == 1)
-            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S.row_csr.ptr.p, S.row_csr.val.p, S.row_csr.idx.p,
-                               (const float*)S.bscale.p, (const float*)S.bv.p, S.bu.p, pre, fl);
-        else
-            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S.col_csr.ptr.p, S.col_csr.val.p, S.col_csr.idx.p,
-                               (const float*)S.bscale.p, (const float*)S.bu.p, S.bv.p, pre, fl);
-    };
+    return 0;
+}
+
+// The LSMR loop of every realisation from u (bu) and the row scales (bscale) the caller filled: v = x = hbar = 0 (:383-385), ...;
+// istop, itn, est per realisation and, where x is not null, the solutions (realisation-major, through btmp).  bx keeps them.
+int batch_solve(Batch& B, int nreal, float damp, float atol, float btol, float conlim, int itnlim, float* x, int* istop, int* itn, float* est)
+{
+    Engine* e = B.e;
+    SpmvState& S = *B.S;
+    const int m = B.m, n = B.n, G = B.G, Rp = B.Rp, localVecs = B.localVecs;
+    const size_t vn = B.vn;
+    hipStream_t st = B.st;
+    float* hc = B.hc;
+    int* hf = B.hf;
+    const float* hred = B.hred;
+    const float* dc = B.coef(0);
+    const int* df = B.flag(0);
     int rc = 0;
 #define LB_DO(call) do { if ((rc = (call)) != 0) return rc; } while (0)
 
-    // u = diag(s_r) b, v = x = hbar = 0 (:383-385)
-    float* d_rs = S.btmp.p;
-    float* d_b = S.btmp.p + (size_t)nreal * m;
-    LB_TRY(e, hipMemcpyAsync(d_rs, row_scale, (size_t)nreal * m * 4, hipMemcpyHostToDevice, st));
-    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_b_init, grid_of(m, G), dim3(256), 0, st, m, nreal, (const float*)d_b, (const float*)d_rs, S.bscale.p, S.bu.p);
     LB_TRY(e, hipMemsetAsync(S.bv.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bx.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bhbar.p, 0, vn * 4, st));
     std::vector<LsmrScalars> P((size_t)nreal, LsmrScalars(damp, atol, btol, conlim, itnlim, localVecs));
     std::vector<char> running((size_t)nreal, 0);
     std::vector<float> alpha0((size_t)nreal, 0.0f), beta0((size_t)nreal, 0.0f);
-    LB_DO(norm(m, S.bu.p));                                                                      // beta = |u|
+    LB_DO(B.norm(m, S.bu.p));                                                                      // beta = |u|
     bool any = false;
     for (int r = 0; r < nreal; ++r) {
         beta0[r] = hred[r];
@@ -465,17 +583,17 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
         any = any || pos;
     }
     if (any) {
-        LB_DO(upload());
-        hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, coef(C_IBETA), flag(F_BPOS), S.bu.p);      // u = u / beta
-        product(2, nullptr, flag(F_BPOS));                                                                       // v = A'u
-        LB_DO(norm(n, S.bv.p));                                                                                  // alpha = |v|
+        LB_DO(B.upload());
+        hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, B.coef(C_IBETA), B.flag(F_BPOS), S.bu.p);      // u = u / beta
+        B.product(2,nullptr, B.flag(F_BPOS));                                                                       // v = A'u
+        LB_DO(B.norm(n, S.bv.p));                                                                                  // alpha = |v|
         for (int r = 0; r < nreal; ++r) {
             alpha0[r] = hf[F_BPOS * Rp + r] ? hred[r] : 0.0f;
             hf[F_APOS * Rp + r] = alpha0[r] > 0.0f;
             hc[C_IALPHA * Rp + r] = alpha0[r] > 0.0f ? 1.0f / alpha0[r] : 0.0f;
         }
-        LB_DO(upload());
-        hipLaunchKernelGGL(k_b_scal, grid_of(n, G), dim3(256), 0, st, n, coef(C_IALPHA), flag(F_APOS), S.bv.p);     // v = v / alpha
+        LB_DO(B.upload());
+        hipLaunchKernelGGL(k_b_scal, grid_of(n, G), dim3(256), 0, st, n, B.coef(C_IALPHA), B.flag(F_APOS), S.bv.p);     // v = v / alpha
     }
     int nrun = 0;
     for (int r = 0; r < nreal; ++r) nrun += (running[r] = P[r].start(alpha0[r], beta0[r]));
@@ -491,9 +609,9 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
             hf[F_ACT * Rp + r] = on;
             if (on) { P[r].itn += 1; hc[C_PRE_U * Rp + r] = -P[r].alpha; }
         }
-        LB_DO(upload());
-        product(1, coef(C_PRE_U), flag(F_ACT));                                                  // u = A v - alpha u
-        LB_DO(norm(m, S.bu.p));                                                                  // beta = |u|
+        LB_DO(B.upload());
+        B.product(1,B.coef(C_PRE_U), B.flag(F_ACT));                                                  // u = A v - alpha u
+        LB_DO(B.norm(m, S.bu.p));                                                                  // beta = |u|
         int maxlim = 0;
         any = false;
         for (int r = 0; r < nreal; ++r) {
@@ -513,18 +631,18 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
             }
         }
         if (any) {
-            LB_DO(upload());
-            hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, coef(C_IBETA), flag(F_BPOS), S.bu.p);  // u = u / beta
+            LB_DO(B.upload());
+            hipLaunchKernelGGL(k_b_scal, grid_of(m, G), dim3(256), 0, st, m, B.coef(C_IBETA), B.flag(F_BPOS), S.bu.p);  // u = u / beta
             if (localOrtho)
-                hipLaunchKernelGGL(k_b_enqueue, grid_of(n, G), dim3(256), 0, st, n, vn, flag(F_SLOT), (const float*)S.bv.p, S.blocalV.p);
-            product(2, coef(C_PRE_V), flag(F_BPOS));                                             // v = A'u - beta v
+                hipLaunchKernelGGL(k_b_enqueue, grid_of(n, G), dim3(256), 0, st, n, vn, B.flag(F_SLOT), (const float*)S.bv.p, S.blocalV.p);
+            B.product(2,B.coef(C_PRE_V), B.flag(F_BPOS));                                             // v = A'u - beta v
             for (int k = 0; k < maxlim; ++k) {                                                   // localVOrtho, :731-748
                 const float* lv = S.blocalV.p + (size_t)k * vn;
                 hipLaunchKernelGGL(k_b_chain<true>, dim3(G), dim3(kCT), 0, st, n, (const float*)S.bv.p, lv, (const float*)nullptr, (const float*)nullptr,
                                    S.bred.p + Rp);
-                hipLaunchKernelGGL(k_b_axmy, grid_of(n, G), dim3(256), 0, st, n, k, (const float*)(S.bred.p + Rp), flag(F_LIM), lv, S.bv.p);
+                hipLaunchKernelGGL(k_b_axmy, grid_of(n, G), dim3(256), 0, st, n, k, (const float*)(S.bred.p + Rp), B.flag(F_LIM), lv, S.bv.p);
             }
-            LB_DO(norm(n, S.bv.p));                                                              // alpha = |v|
+            LB_DO(B.norm(n, S.bv.p));                                                              // alpha = |v|
             for (int r = 0; r < nreal; ++r) {
                 if (!hf[F_BPOS * Rp + r]) continue;
                 LsmrScalars& p = P[r];
@@ -538,9 +656,9 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
             p.rotate();                                                                          // :516-600
             hc[C_C1 * Rp + r] = p.c1; hc[C_C2 * Rp + r] = p.c2; hc[C_C3 * Rp + r] = p.c3;
         }
-        LB_DO(upload());
+        LB_DO(B.upload());
         hipLaunchKernelGGL(k_b_update, grid_of(n, G), dim3(256), 0, st, n, dc, df, S.bv.p, S.bh.p, S.bhbar.p, S.bx.p, Rp);   // :508, :545-547
-        LB_DO(norm(n, S.bx.p));                                                                  // normx
+        LB_DO(B.norm(n, S.bx.p));                                                                  // normx
         for (int r = 0; r < nreal; ++r)
             if (running[r] && P[r].converged(hred[r])) { running[r] = 0; --nrun; }
     }
@@ -552,9 +670,94 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
         float* q = est + (size_t)5 * r;
         q[0] = p.normA; q[1] = p.condA; q[2] = p.normr; q[3] = p.normAr; q[4] = p.normx;
     }
-    hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, nreal, (const float*)S.bx.p,
-                       S.btmp.p);
-    LB_TRY(e, hipMemcpyAsync(x, S.btmp.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
+    if (x) {
+        hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, nreal,
+                           (const float*)S.bx.p, S.btmp.p);
+        LB_TRY(e, hipMemcpyAsync(x, S.btmp.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
+    }
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
+}  // namespace dsa
+
+using dsa::Engine;
+using dsa::SpmvState;
+
+extern "C" {
+
+int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_scale, float damp, float atol, float btol, float conlim, int itnlim,
+                   int localSize, float* x, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (nreal < 1 || nreal > 64 * 65535 || !b || !row_scale || !x || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_batch: nreal < 1 or a null argument"); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_batch: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    const int m = e->spmv->m, n = e->spmv->n;
+    Batch B;
+    if (int rc = batch_begin(e, nreal, localSize, std::max((size_t)nreal * m + m, (size_t)nreal * n), B)) return rc;
+    SpmvState& S = *e->spmv;
+    // u = diag(s_r) b
+    float* d_rs = S.btmp.p;
+    float* d_b = S.btmp.p + (size_t)nreal * m;
+    LB_TRY(e, hipMemcpyAsync(d_rs, row_scale, (size_t)nreal * m * 4, hipMemcpyHostToDevice, B.st));
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, B.st));
+    hipLaunchKernelGGL(k_b_init, grid_of(m, B.G), dim3(256), 0, B.st, m, nreal, (const float*)d_b, (const float*)d_rs, S.bscale.p, S.bu.p);
+    return batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est);
+}
+
+int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* models, int spike_first, const double* coords, float damp, float atol,
+                        float btol, float conlim, int itnlim, int localSize, float* x, double* psf, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (nreal < 1 || nreal > 64 * 65535 || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: nreal < 1 or a null istop / itn / est"); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_resolution: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    const int m = e->spmv->m, n = e->spmv->n;
+    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    if (!models && (spike_first < 0 || (long long)spike_first + nreal > n)) {
+        e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: spikes %d..%lld outside the %d unknowns", spike_first, (long long)spike_first + nreal - 1, n);
+        return DSA_ERR_ARGUMENT;
+    }
+    if (psf && (models || !coords)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: psf needs spikes (models NULL) and coords"); return DSA_ERR_ARGUMENT; }
+    Batch B;
+    if (int rc = batch_begin(e, nreal, localSize, (models || x) ? (size_t)nreal * n : 1, B)) return rc;
+    SpmvState& S = *e->spmv;
+    const int G = B.G, Rp = B.Rp;
+    hipStream_t st = B.st;
+    // v = the test models, row scales 1, u = 0; u = A v over every row (k_b_spmv: fl(a * 1) = a, the chain of dsa_spmv mode 1 from y = 0),
+    // then rows [ndata, m) = +0
+    if (models) {
+        LB_TRY(e, hipMemcpyAsync(S.btmp.p, models, (size_t)nreal * n * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_b_scatter, grid_of(n, G), dim3(256), 0, st, n, nreal, (const float*)S.btmp.p, S.bv.p);
+    } else
+        hipLaunchKernelGGL(k_b_spike, grid_of(n, G), dim3(256), 0, st, n, nreal, spike_first, S.bv.p);
+    hipLaunchKernelGGL(k_b_ones, grid_of(m, G), dim3(256), 0, st, m, nreal, S.bscale.p);
+    LB_TRY(e, hipMemsetAsync(S.bu.p, 0, B.vm * 4, st));
+    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 1;
+    if (int rc = B.upload()) return rc;
+    B.product(1, nullptr, B.flag(F_ACT));
+    if (ndata < m) hipLaunchKernelGGL(k_b_zero_rows, grid_of(m - ndata, G), dim3(256), 0, st, m, ndata, S.bu.p);
+    LB_TRY(e, hipStreamSynchronize(st));                      // (the upload has landed before the host mirror changes)
+    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 0;
+    if (int rc = batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
+    if (!psf) return 0;
+    const int nb = (n + kPsfE - 1) / kPsfE;
+    if (e->ensure(S.bcoord, 4 * (size_t)n) || e->ensure(S.bpsf, (size_t)G * nb * 64 * 3 + 4 * (size_t)Rp)) return e->status;
+    double* d_part = S.bpsf.p;
+    double* d_psf = S.bpsf.p + (size_t)G * nb * 64 * 3;
+    double* d_cos = S.bcoord.p + 3 * (size_t)n;
+    LB_TRY(e, hipMemcpyAsync(S.bcoord.p, coords, 3 * (size_t)n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_psf_cos, dim3((unsigned)std::min(1024, (n + 255) / 256)), dim3(256), 0, st, n, (const double*)S.bcoord.p, d_cos);
+    hipLaunchKernelGGL(k_b_psf_part, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, n, nb, spike_first, (const double*)S.bcoord.p, (const double*)d_cos,
+                       (const float*)S.bx.p, d_part);
+    hipLaunchKernelGGL(k_b_psf_sum, dim3((unsigned)G), dim3(64), 0, st, n, nb, nreal, spike_first, (const float*)S.bx.p, (const double*)d_part, d_psf);
+    LB_TRY(e, hipMemcpyAsync(psf, d_psf, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
     LB_TRY(e, hipGetLastError());
     LB_TRY(e, hipStreamSynchronize(st));
     return 0;

@@ -51,6 +51,7 @@ struct SpmvState {
     bool contiguous_valid = false;
     // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
     DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
+    DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results
     float* hbatch = nullptr;         // pinned: per-realisation coefficients and flags (bparam) on their way to the device, norms on their way back
     size_t hbatch_cap = 0;
 };

@@ -71,6 +71,7 @@ def load_library():
     L.dsa_spmv.argtypes = [_vp, _i32, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp] + [_vp] * 7
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
+    L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
     L.dsa_dropin_error.restype = C.c_char_p
@@ -283,6 +284,31 @@ class Engine:
                                            _p(itn), _p(est)))
         names = ("normA", "condA", "normr", "normAr", "normx")
         return dict(x=x, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+
+    def lsmr_resolution(self, ndata, damp, models=None, spikes=None, coords=None, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400,
+                        local_size=10):
+        """R LSMR solves on the matrix of the last spmv_load whose right-hand sides the device forms from test models: A m_r on the
+        rows below ndata, 0 from ndata up; each bit-identical to lsmr() on that right-hand side.  models: (R, n) host models, or
+        spikes = (first, R): the unit spikes at unknowns first .. first + R - 1; with spikes, coords ((n, 3) latitude, longitude,
+        depth) adds the PSF measures.  Returns dict(x=(R, n) or None when not want_x, psf=(R, 4) or None, istop=(R,), itn=(R,),
+        normA=(R,), condA, normr, normAr, normx)"""
+        m, n = self._mn
+        mod = None if models is None else np.ascontiguousarray(models, np.float32)
+        if mod is not None:
+            assert mod.ndim == 2 and mod.shape[1] == n
+            first, R = 0, mod.shape[0]
+        else:
+            first, R = int(spikes[0]), int(spikes[1])
+        xyz = None if coords is None else np.ascontiguousarray(coords, np.float64)
+        x = np.zeros((R, n), np.float32) if want_x else None
+        psf = np.zeros((R, 4)) if xyz is not None else None
+        istop = np.zeros(R, np.int32)
+        itn = np.zeros(R, np.int32)
+        est = np.zeros((R, 5), np.float32)
+        self._check(self._L.dsa_lsmr_resolution(self._h, R, int(ndata), _p(mod), first, _p(xyz), damp, atol, btol, conlim, int(itnlim),
+                                                int(local_size), _p(x), _p(psf), _p(istop), _p(itn), _p(est)))
+        names = ("normA", "condA", "normr", "normAr", "normx")
+        return dict(x=x, psf=psf, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
 
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)

@@ -210,6 +210,22 @@ int dsa_lsmr(dsa_engine* e, const float* b, float damp, float atol, float btol, 
 int dsa_lsmr_batch(dsa_engine* e, int nreal, const float* b, const float* row_scale, float damp, float atol, float btol,
                    float conlim, int itnlim, int localSize, float* x, int* istop, int* itn, float* est);
 
+/* Linearised resolution tests: nreal LSMR solves on the (m x n) matrix of the last dsa_spmv_load /
+ * dsa_iteration_system_device, realisation r with the right-hand side of a test model m_r formed on the device:
+ * b_r[i] = (A m_r)[i] for the data rows i < ndata (the bits of dsa_spmv mode 1 with x = m_r, y = 0), +0 for the rows
+ * from ndata up.  models: nreal*n host array (realisation-major), or NULL: m_r = the unit spike at unknown spike_first + r
+ * (made on the device; the spike range must lie in [0, n)).  Realisation r is bit-identical (x, istop, itn, est as in
+ * dsa_lsmr_batch) to dsa_lsmr on b_r; a zero b_r gives x = 0, itn 0, istop 0.  x (nreal*n) may be NULL: then nothing of
+ * size n*nreal leaves the device.  psf (spikes only, 4*nreal, may be NULL) needs coords (3*n: latitude deg, longitude
+ * deg, depth km per unknown): psf[4r..4r+3] = {R_jj = x_r[j], sum x^2, sum x^2 dh^2, sum x^2 dz^2} over the unknowns of
+ * x_r, j = spike_first + r, dh the great-circle distance in km (haversine, radius 6371 km) and dz the depth difference
+ * from unknown j; fp64 in a fixed order (repeated calls give the same bits).  The resident matrix, dsa_lsmr and
+ * dsa_lsmr_batch are left as they were.  Errors: DSA_ERR_ARGUMENT (nreal < 1, ndata outside [1, m], a spike range
+ * outside [0, n), psf without spikes or coords, a null istop / itn / est), DSA_ERR_STATE (no matrix), DSA_ERR_DEVICE. */
+int dsa_lsmr_resolution(dsa_engine* e, int nreal, int ndata, const float* models, int spike_first, const double* coords,
+                        float damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x, double* psf,
+                        int* istop, int* itn, float* est);
+
 /* One outer iteration's host glue (reference main.f90:361-466 and :520-535; plain host code, no device):
  * iteration_system: residual cbst = obst - dsyn, percentile weights (getpercentile.f90), rows scaled by their weights,
  *   DWS norm[maxvp] with dws = {max, mean}, regularisation rows appended.  In/out rw, col (capacity entries) and iw

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """dsa_lsmr_batch against R sequential dsa_lsmr calls (default placement: products on the device, ordered sums on the host).
 
-    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256]
+    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution]
 
 Per system and R: bootstrap row scales (dsurftomo_amd.invert.bootstrap_row_scales), one warm-up of each path, then the batch
 once and R sequential solves of the explicitly scaled systems (the scaled matrices are loaded outside the timed region; each
 solve is timed alone).  Prints one line per (system, R) and checks realisation 0 of the batch against its sequential solve bit
-for bit.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
+for bit.  Resolution leg (resolution_leg): every unknown's PSF by dsa_lsmr_resolution against sequential dsa_lsmr spike solves.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
 The systems are the product's own (dsa_calsurfg + dsa_iteration_system, or tests/synth_matrix.py): nothing here loads oracle/."""
 import argparse
 import os
@@ -51,7 +51,13 @@ def product_system(c, fwd, obst, threshold0, weight0):
 def taipei_system():
     c = taipei.load()
     fwd = L.call_boundary(load_library().dsa_calsurfg, c)
-    return product_system(c, fwd, c["obst"], 3.0, 4.0), c["ndata"], 1.0, 400
+    return product_system(c, fwd, c["obst"], 3.0, 4.0), c["ndata"], 1.0, 400, invert.unknown_coords(c)
+
+
+def grid_coords(ni, nj, nk):
+    """latitude, longitude, depth of a regular grid of unknowns, i fastest (the unknowns' order), 0.05 degrees and 2 km apart"""
+    k, j, i = np.meshgrid(np.arange(nk), np.arange(nj), np.arange(ni), indexing="ij")
+    return np.stack([25.0 - 0.05 * i.ravel(), 121.0 + 0.05 * j.ravel(), 2.0 * k.ravel()], axis=1).astype(np.float64)
 
 
 def multiblock_system():
@@ -60,7 +66,8 @@ def multiblock_system():
     m, n, nar = M["m"], M["n"], M["rw"].size
     b = np.zeros(m, np.float32)
     b[:31522] = (SM.mix(np.arange(31522), 12) - 0.5).astype(np.float32)
-    return dict(m=m, n=n, nar=nar, iw=np.concatenate([[nar], M["row"], M["col"]]).astype(np.int32), rw=M["rw"], b=b), 31522, 0.7, 35
+    S = dict(m=m, n=n, nar=nar, iw=np.concatenate([[nar], M["row"], M["col"]]).astype(np.int32), rw=M["rw"], b=b)
+    return S, 31522, 0.7, 35, grid_coords(47, 47, 31)
 
 
 def headline_system():
@@ -69,7 +76,49 @@ def headline_system():
     fwd = L.call_boundary(load_library().dsa_calsurfg, c)
     r = synth.LCG(77)
     obst = (fwd["dsurf"] * (1.0 + 0.04 * (r.uniform(c["ndata"]) - 0.5))).astype(np.float32)
-    return product_system(c, fwd, obst, 3.0, 2.0), c["ndata"], 1.0, 20
+    return product_system(c, fwd, obst, 3.0, 2.0), c["ndata"], 1.0, 20, invert.unknown_coords(c)
+
+
+EST = ("normA", "condA", "normr", "normAr", "normx")
+
+
+def resolution_leg(name, e, S, ndata, damp, itnlim, coords, seq_max):
+    """every unknown's PSF by dsa_lsmr_resolution in chunks of invert.resolution_chunk (x left on the device, PSF measures back)
+    against sequential dsa_lsmr spike solves: seq_max spikes spread over the unknowns, each timed alone (its right-hand side formed
+    outside the timing), scaled to all n; spike 0 of the sample checked bit for bit"""
+    n = S["n"]
+    chunk = invert.resolution_chunk(S["m"], n, 10)
+    load(e, S)
+    e.lsmr_resolution(ndata, damp, spikes=(0, min(chunk, n)), coords=coords, want_x=False, itnlim=2)      # warm-up: the largest chunk
+    t0 = time.perf_counter()
+    itn, calls = [], 0
+    for first in range(0, n, chunk):
+        D = e.lsmr_resolution(ndata, damp, spikes=(first, min(chunk, n - first)), coords=coords, want_x=False, itnlim=itnlim)
+        itn.append(D["itn"])
+        calls += 1
+    t_res = time.perf_counter() - t0
+    itn = np.concatenate(itn)
+    js = np.unique(np.linspace(0, n - 1, min(seq_max, n)).astype(int))
+    e.lsmr(S["b"], damp, itnlim=2)
+    t_seq, itn_seq, first_seq = 0.0, 0, None
+    for j in js:
+        sp = np.zeros(n, np.float32)
+        sp[j] = 1.0
+        b = e.spmv(1, sp, np.zeros(S["m"], np.float32))
+        b[ndata:] = 0.0
+        t0 = time.perf_counter()
+        got = e.lsmr(b, damp, itnlim=itnlim)
+        t_seq += time.perf_counter() - t0
+        itn_seq += got["itn"]
+        if first_seq is None:
+            first_seq = got
+    one = e.lsmr_resolution(ndata, damp, spikes=(int(js[0]), 1), itnlim=itnlim)
+    b0 = dict(x=one["x"][0], istop=int(one["istop"][0]), itn=int(one["itn"][0]), **{k: one[k][0] for k in EST})
+    t_seq_all = t_seq * n / len(js)
+    print("%s resolution: %d PSFs in %d calls of up to %d: %9.1f ms (itn max %d, total %d) | %d of %d sequential dsa_lsmr %9.1f ms "
+          "(%.2f ms per solve, %.1f itn) | speed-up %.1fx | spike %d identical: %s" %
+          (name, n, calls, chunk, 1e3 * t_res, int(itn.max()), int(itn.sum()), len(js), n, 1e3 * t_seq_all, 1e3 * t_seq / len(js),
+           itn_seq / len(js), t_seq_all / t_res, int(js[0]), inv.same(b0, first_seq) == []), flush=True)
 
 
 def load(e, S, rw=None):
@@ -82,16 +131,22 @@ def main():
     ap.add_argument("--systems", default="taipei,multiblock")
     ap.add_argument("--R", default="1,8,64,256")
     ap.add_argument("--seq-max", type=int, default=64, help="sequential solves actually run per R (the rest extrapolated from their mean)")
+    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch) and / or resolution (dsa_lsmr_resolution)")
     args = ap.parse_args()
     Rs = [int(v) for v in args.R.split(",")]
+    legs = args.legs.split(",")
     make = dict(taipei=taipei_system, multiblock=multiblock_system, headline=headline_system)
     for name in args.systems.split(","):
         t0 = time.perf_counter()
-        S, ndata, damp, itnlim = make[name]()
+        S, ndata, damp, itnlim, coords = make[name]()
         print("%s: m %d n %d nar %d (set-up %.1f s), damp %g, itnlim %d" % (name, S["m"], S["n"], S["nar"], time.perf_counter() - t0, damp, itnlim), flush=True)
         rows = S["iw"][1:S["nar"] + 1] - 1
         e = Engine(0)
         try:
+            if "resolution" in legs:
+                resolution_leg(name, e, S, ndata, damp, itnlim, coords, args.seq_max)
+            if "bootstrap" not in legs:
+                continue
             scales = invert.bootstrap_row_scales(ndata, S["m"], max(Rs), seed=1)
             load(e, S)
             e.lsmr_batch(S["b"], scales[:2], damp, itnlim=2)              # warm-up: contiguous copies, allocations, code
