@@ -25,6 +25,12 @@
 // right-hand sides of test models, formed on the device: v = the models (unit spikes made in place, or host models), row scales 1,
 // u = A v by k_b_spmv<true> (fl(a * 1) = a: the chain of dsa_spmv mode 1 from y = 0), then the regularisation rows zeroed.  For
 // spikes, k_b_psf_part / k_b_psf_sum reduce each solution to its PSF measures on the device.
+//
+// dsa_lsmr_tradeoff runs it on K (weight, damp) pairs of one system: the products read a coefficient copy of the
+// contiguous values whose regularisation entries hold their integer coefficient c (the resident entry is fl(c * weight0)), the row
+// scales are 1 on the data rows and weight_k on the regularisation rows, so member k multiplies by fl(a * 1) = a and fl(c * weight_k):
+// the system dsa_iteration_system builds with weight_k.  damp_k goes to member k's LsmrScalars.  k_b_meas_rows / k_b_meas_x /
+// k_b_meas_sum reduce each solution to its misfit, roughness and size on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -474,6 +480,118 @@ __global__ __launch_bounds__(64) void k_b_psf_sum(int n, int nb, int nreal, int 
     for (int c = 0; c < 3; ++c) psf[4 * (size_t)r + 1 + c] = s[c];
 }
 
+// ---- dsa_lsmr_tradeoff: the coefficient copy of the contiguous values, its row scales, and the measures of every solution ----
+
+// c of a regularisation entry a = fl(c * w0): rint(a / w0); `bad` unless c is a non-zero integer of at most 64 whose product gives a's bits back
+__device__ inline float coef_of(float a, float w0, bool& bad)
+{
+    const float c = rintf(a / w0);
+    bad = bad || !(fabsf(c) <= 64.0f) || c == 0.0f || __float_as_uint(c * w0) != __float_as_uint(a);
+    return c;
+}
+
+// row ordering: one thread per row of [ndata, m), its entries val[ptr[row] .. ptr[row + 1]) <- c (the data rows were copied)
+__global__ void k_coef_rows(int m, int ndata, float w0, const long long* __restrict__ ptr, float* __restrict__ val, int* __restrict__ flag)
+{
+    const int row = ndata + blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= m) return;
+    bool bad = false;
+    for (long long k = ptr[row]; k < ptr[row + 1]; ++k) val[k] = coef_of(val[k], w0, bad);
+    if (bad) atomicOr(flag, 1);
+}
+
+// column ordering: one thread per entry, those of the rows from ndata up (idx: 0-based row) <- c
+__global__ void k_coef_cols(long long nar, int ndata, float w0, const int* __restrict__ idx, float* __restrict__ val, int* __restrict__ flag)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nar || idx[k] < ndata) return;
+    bool bad = false;
+    val[k] = coef_of(val[k], w0, bad);
+    if (bad) atomicOr(flag, 1);
+}
+
+// (g, i, l) of the batch layout: scale = 1 on the data rows, weight_r from ndata up, u = b[i]; both 0 past nreal
+__global__ void k_b_tradeoff_init(int m, int ndata, int nreal, const float* __restrict__ b, const float* __restrict__ w, float* __restrict__ scale,
+                                  float* __restrict__ u)
+{
+    LB_GROUP_LOOP(m) {
+        const int r = g * 64 + (int)(t & 63);
+        const size_t i = t >> 6;
+        const bool in = r < nreal;
+        scale[gbase + t] = in ? (i < (size_t)ndata ? 1.0f : w[r]) : 0.0f;
+        u[gbase + t] = in ? b[i] : 0.0f;
+    }
+}
+
+// Measures of member r over its solution x_r: sum over the data rows of (b_i - (A x_r)_i)^2, sum over the rows from ndata up of
+// ((C x_r)_i)^2 (val: the row ordering's coefficient copy, so C = the integer coefficients), sum of x_r^2; fp64.  A row's sum adds its
+// entries in storage order (the float x float products are exact in fp64).  k_b_meas_rows: block (b, g), four wavefronts, wavefront w
+// the rows [b kMeasR + w kMeasR/4, + kMeasR/4) in order, value and index wave-uniform, one coalesced 256-byte load of bx per entry;
+// the four wavefronts' sums added in order.  k_b_meas_x: the same over the elements of x.  k_b_meas_sum: the blocks' partials in order.
+constexpr int kMeasR = 64;                  // rows per block
+constexpr int kMeasE = 1024;                // elements of x per block
+
+__global__ __launch_bounds__(256) void k_b_meas_rows(int m, int n, int ndata, int nb, const long long* __restrict__ ptr, const float* __restrict__ val,
+                                                     const int* __restrict__ idx, const float* __restrict__ b, const float* __restrict__ x,
+                                                     double* __restrict__ part)
+{
+    __shared__ double red[2][4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
+    const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
+    const int r0 = blk * kMeasR + w * (kMeasR / 4), r1 = min(r0 + kMeasR / 4, m);
+    double s0 = 0.0, s1 = 0.0;
+    for (int row = r0; row < r1; ++row) {
+        double acc = 0.0;
+        long long k = ptr[row];
+        const long long k1 = ptr[row + 1];
+        constexpr int U = 4;
+        for (; k + U <= k1; k += U) {
+            double a[U], xi[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) { a[u] = (double)val[k + u]; xi[u] = (double)p[(size_t)idx[k + u] * 64]; }
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc = acc + a[u] * xi[u];
+        }
+        for (; k < k1; ++k) acc = acc + (double)val[k] * (double)p[(size_t)idx[k] * 64];
+        if (row < ndata) { const double d = (double)b[row] - acc; s0 = s0 + d * d; }
+        else s1 = s1 + acc * acc;
+    }
+    red[0][w][lane] = s0; red[1][w][lane] = s1;
+    __syncthreads();
+    if (w == 0) {
+        double* __restrict__ o = part + (((size_t)g * nb + blk) * 64 + lane) * 2;
+        for (int c = 0; c < 2; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_b_meas_x(int n, int nb, const float* __restrict__ x, double* __restrict__ part)
+{
+    __shared__ double red[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
+    const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
+    const int e0 = blk * kMeasE + w * (kMeasE / 4), e1 = min(e0 + kMeasE / 4, n);
+    double s = 0.0;
+    for (int e = e0; e < e1; ++e) { const double xv = (double)p[(size_t)e * 64]; s = s + xv * xv; }
+    red[w][lane] = s;
+    __syncthreads();
+    if (w == 0) part[((size_t)g * nb + blk) * 64 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+// meas[3 r .. 3 r + 2] = {misfit, roughness, sum x^2}; one thread per member
+__global__ __launch_bounds__(64) void k_b_meas_sum(int nbr, int nbx, int nreal, const double* __restrict__ rows, const double* __restrict__ xs,
+                                                   double* __restrict__ meas)
+{
+    const int lane = threadIdx.x, g = blockIdx.x, r = g * 64 + lane;
+    if (r >= nreal) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int b = 0; b < nbr; ++b) {
+        const double* __restrict__ q = rows + (((size_t)g * nbr + b) * 64 + lane) * 2;
+        s0 = s0 + q[0]; s1 = s1 + q[1];
+    }
+    for (int b = 0; b < nbx; ++b) s2 = s2 + xs[((size_t)g * nbx + b) * 64 + lane];
+    meas[3 * (size_t)r] = s0; meas[3 * (size_t)r + 1] = s1; meas[3 * (size_t)r + 2] = s2;
+}
+
 // ---- the batch shared by dsa_lsmr_batch and dsa_lsmr_resolution: set-up, then (the caller fills u and the row scales) the LSMR loop ----
 struct Batch {
     Engine* e = nullptr;
@@ -485,6 +603,8 @@ struct Batch {
     float* hc = nullptr;
     int* hf = nullptr;
     float* hred = nullptr;
+    const float* rval = nullptr;     // values the products read beside row_csr / col_csr (batch_begin: the resident ones; dsa_lsmr_tradeoff: the coefficient copy)
+    const float* cval = nullptr;
 
     const float* coef(int f) const { return S->bparam.p + (size_t)f * Rp; }
     const int* flag(int f) const { return reinterpret_cast<const int*>(S->bparam.p + (size_t)NCOEF * Rp) + (size_t)f * Rp; }
@@ -506,10 +626,10 @@ struct Batch {
     void product(int mode, const float* pre, const int* fl)
     {
         if (mode == 1)
-            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S->row_csr.ptr.p, S->row_csr.val.p, S->row_csr.idx.p,
+            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S->row_csr.ptr.p, rval, S->row_csr.idx.p,
                                (const float*)S->bscale.p, (const float*)S->bv.p, S->bu.p, pre, fl);
         else
-            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S->col_csr.ptr.p, S->col_csr.val.p, S->col_csr.idx.p,
+            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S->col_csr.ptr.p, cval, S->col_csr.idx.p,
                                (const float*)S->bscale.p, (const float*)S->bu.p, S->bv.p, pre, fl);
     }
 };
@@ -532,6 +652,7 @@ int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B)
         if (rc != 0) return rc;
         S.contiguous_valid = true;
     }
+    B.rval = S.row_csr.val.p; B.cval = S.col_csr.val.p;
     if (e->ensure(S.bu, vm) || e->ensure(S.bscale, vm) || e->ensure(S.bv, vn) || e->ensure(S.bh, vn) || e->ensure(S.bhbar, vn) || e->ensure(S.bx, vn) ||
         e->ensure(S.blocalV, std::max<size_t>(vn * (size_t)B.localVecs, 1)) || e->ensure(S.bparam, (size_t)kNParam * Rp) || e->ensure(S.bred, 3 * (size_t)Rp) ||
         e->ensure(S.bterm, std::max(vm, vn)) || e->ensure(S.bpmax, (size_t)G * ((std::max(m, n) + kPB - 1) / kPB) * 64) ||
@@ -552,7 +673,8 @@ int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B)
 
 // The LSMR loop of every realisation from u (bu) and the row scales (bscale) the caller filled: v = x = hbar = 0 (:383-385), ...;
 // istop, itn, est per realisation and, where x is not null, the solutions (realisation-major, through btmp).  bx keeps them.
-int batch_solve(Batch& B, int nreal, float damp, float atol, float btol, float conlim, int itnlim, float* x, int* istop, int* itn, float* est)
+// damp: one per realisation.
+int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, float conlim, int itnlim, float* x, int* istop, int* itn, float* est)
 {
     Engine* e = B.e;
     SpmvState& S = *B.S;
@@ -570,7 +692,9 @@ int batch_solve(Batch& B, int nreal, float damp, float atol, float btol, float c
     LB_TRY(e, hipMemsetAsync(S.bv.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bx.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bhbar.p, 0, vn * 4, st));
-    std::vector<LsmrScalars> P((size_t)nreal, LsmrScalars(damp, atol, btol, conlim, itnlim, localVecs));
+    std::vector<LsmrScalars> P;
+    P.reserve((size_t)nreal);
+    for (int r = 0; r < nreal; ++r) P.emplace_back(damp[r], atol, btol, conlim, itnlim, localVecs);
     std::vector<char> running((size_t)nreal, 0);
     std::vector<float> alpha0((size_t)nreal, 0.0f), beta0((size_t)nreal, 0.0f);
     LB_DO(B.norm(m, S.bu.p));                                                                      // beta = |u|
@@ -680,6 +804,39 @@ int batch_solve(Batch& B, int nreal, float damp, float atol, float btol, float c
     return 0;
 }
 
+// The coefficient copy of both contiguous value arrays for data rows [0, ndata) and regularisation rows built with weight0: the
+// resident values, the entries of the rows from ndata up replaced by c = rint(a / weight0).  Kept until the matrix changes
+// (spmv_invalidate_contiguous) or the key (ndata, weight0) does.  DSA_ERR_ARGUMENT when an entry is not fl(c * weight0), 0 < |c| <= 64.
+int ensure_coef(Engine* e, int ndata, float weight0)
+{
+    SpmvState& S = *e->spmv;
+    if (S.coef_valid && S.coef_ndata == ndata && std::memcmp(&S.coef_weight0, &weight0, 4) == 0) return 0;
+    S.coef_valid = false;
+    hipStream_t st = e->stream;
+    const size_t nn = std::max<size_t>((size_t)S.nar, 1);
+    if (e->ensure(S.row_coef, nn) || e->ensure(S.col_coef, nn) || e->ensure(S.bflag, 1)) return e->status;
+    LB_TRY(e, hipMemsetAsync(S.bflag.p, 0, 4, st));
+    if (S.nar > 0) {
+        LB_TRY(e, hipMemcpyAsync(S.row_coef.p, S.row_csr.val.p, (size_t)S.nar * 4, hipMemcpyDeviceToDevice, st));
+        LB_TRY(e, hipMemcpyAsync(S.col_coef.p, S.col_csr.val.p, (size_t)S.nar * 4, hipMemcpyDeviceToDevice, st));
+        if (ndata < S.m)
+            hipLaunchKernelGGL(k_coef_rows, dim3((unsigned)((S.m - ndata + 255) / 256)), dim3(256), 0, st, S.m, ndata, weight0, (const long long*)S.row_csr.ptr.p,
+                               S.row_coef.p, S.bflag.p);
+        hipLaunchKernelGGL(k_coef_cols, dim3((unsigned)((S.nar + 255) / 256)), dim3(256), 0, st, S.nar, ndata, weight0, (const int*)S.col_csr.idx.p, S.col_coef.p,
+                           S.bflag.p);
+    }
+    int bad = 0;
+    LB_TRY(e, hipMemcpyAsync(&bad, S.bflag.p, 4, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    if (bad) {
+        e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: a regularisation entry (rows from %d up) is not an integer coefficient of 1..64 times weight0 = %g", ndata, (double)weight0);
+        return DSA_ERR_ARGUMENT;
+    }
+    S.coef_valid = true; S.coef_ndata = ndata; S.coef_weight0 = weight0;
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace dsa
@@ -707,7 +864,8 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
     LB_TRY(e, hipMemcpyAsync(d_rs, row_scale, (size_t)nreal * m * 4, hipMemcpyHostToDevice, B.st));
     LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, B.st));
     hipLaunchKernelGGL(k_b_init, grid_of(m, B.G), dim3(256), 0, B.st, m, nreal, (const float*)d_b, (const float*)d_rs, S.bscale.p, S.bu.p);
-    return batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est);
+    const std::vector<float> damps((size_t)nreal, damp);
+    return batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est);
 }
 
 int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* models, int spike_first, const double* coords, float damp, float atol,
@@ -745,7 +903,8 @@ int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* model
     if (ndata < m) hipLaunchKernelGGL(k_b_zero_rows, grid_of(m - ndata, G), dim3(256), 0, st, m, ndata, S.bu.p);
     LB_TRY(e, hipStreamSynchronize(st));                      // (the upload has landed before the host mirror changes)
     for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 0;
-    if (int rc = batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
+    const std::vector<float> damps((size_t)nreal, damp);
+    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
     if (!psf) return 0;
     const int nb = (n + kPsfE - 1) / kPsfE;
     if (e->ensure(S.bcoord, 4 * (size_t)n) || e->ensure(S.bpsf, (size_t)G * nb * 64 * 3 + 4 * (size_t)Rp)) return e->status;
@@ -758,6 +917,54 @@ int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* model
                        (const float*)S.bx.p, d_part);
     hipLaunchKernelGGL(k_b_psf_sum, dim3((unsigned)G), dim3(64), 0, st, n, nb, nreal, spike_first, (const float*)S.bx.p, (const double*)d_part, d_psf);
     LB_TRY(e, hipMemcpyAsync(psf, d_psf, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
+
+int dsa_lsmr_tradeoff(dsa_engine* h_, int nreal, int ndata, const float* b, float weight0, const float* weight, const float* damp, float atol, float btol,
+                      float conlim, int itnlim, int localSize, float* x, double* measures, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (nreal < 1 || nreal > 64 * 65535 || !b || !weight || !damp || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: nreal < 1 or a null b / weight / damp / istop / itn / est"); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_tradeoff: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    const int m = e->spmv->m, n = e->spmv->n;
+    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(weight0) || !(weight0 > 0.0f)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: weight0 %g is not a finite number > 0", (double)weight0); return DSA_ERR_ARGUMENT; }
+    for (int r = 0; r < nreal; ++r)
+        if (!std::isfinite(weight[r]) || weight[r] < 0.0f || !std::isfinite(damp[r]) || damp[r] < 0.0f) {
+            e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: member %d has weight %g, damp %g (both must be finite and >= 0)", r, (double)weight[r], (double)damp[r]);
+            return DSA_ERR_ARGUMENT;
+        }
+    Batch B;
+    // btmp: the solutions on their way out (realisation-major), then b and the weights (b stays for the measures)
+    const size_t xs = x ? (size_t)nreal * n : 0;
+    if (int rc = batch_begin(e, nreal, localSize, xs + (size_t)m + (size_t)nreal, B)) return rc;
+    if (int rc = ensure_coef(e, ndata, weight0)) return rc;
+    SpmvState& S = *e->spmv;
+    const int G = B.G, Rp = B.Rp;
+    hipStream_t st = B.st;
+    B.rval = S.row_coef.p; B.cval = S.col_coef.p;
+    float* d_b = S.btmp.p + xs;
+    float* d_w = d_b + m;
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    LB_TRY(e, hipMemcpyAsync(d_w, weight, (size_t)nreal * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b_tradeoff_init, grid_of(m, G), dim3(256), 0, st, m, ndata, nreal, (const float*)d_b, (const float*)d_w, S.bscale.p, S.bu.p);
+    if (int rc = batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
+    if (!measures) return 0;
+    const int nbr = (m + kMeasR - 1) / kMeasR, nbx = (n + kMeasE - 1) / kMeasE;
+    const size_t nrows = (size_t)G * nbr * 64 * 2, nx = (size_t)G * nbx * 64;
+    if (e->ensure(S.bpsf, nrows + nx + 3 * (size_t)Rp)) return e->status;
+    double* d_rows = S.bpsf.p;
+    double* d_x = d_rows + nrows;
+    double* d_meas = d_x + nx;
+    hipLaunchKernelGGL(k_b_meas_rows, dim3((unsigned)nbr, (unsigned)G), dim3(256), 0, st, m, n, ndata, nbr, (const long long*)S.row_csr.ptr.p, (const float*)S.row_coef.p,
+                       (const int*)S.row_csr.idx.p, (const float*)d_b, (const float*)S.bx.p, d_rows);
+    hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
+    hipLaunchKernelGGL(k_b_meas_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
+    LB_TRY(e, hipMemcpyAsync(measures, d_meas, 3 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
     LB_TRY(e, hipGetLastError());
     LB_TRY(e, hipStreamSynchronize(st));
     return 0;

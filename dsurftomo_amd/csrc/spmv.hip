@@ -445,6 +445,7 @@ void release_spmv(SpmvState* s)
     for (SpmvState::Contiguous* c : { &s->row_csr, &s->col_csr }) { rel(c->ptr); rel(c->val); rel(c->idx); }
     rel(s->bu); rel(s->bv); rel(s->bh); rel(s->bhbar); rel(s->bx); rel(s->blocalV); rel(s->bscale); rel(s->bparam); rel(s->bred); rel(s->btmp); rel(s->bterm); rel(s->bpmax);
     rel(s->bcoord); rel(s->bpsf);
+    rel(s->row_coef); rel(s->col_coef); rel(s->bflag);
     if (s->hbatch) (void)hipHostFree(s->hbatch);
     if (s->hu) (void)hipHostFree(s->hu);
     if (s->hv) (void)hipHostFree(s->hv);

@@ -49,9 +49,16 @@ struct SpmvState {
     };
     Contiguous row_csr, col_csr;
     bool contiguous_valid = false;
+    // dsa_lsmr_tradeoff: copies of row_csr.val / col_csr.val whose entries of the rows from coef_ndata up hold their integer
+    // coefficient c (the resident entry is fl(c * coef_weight0)); built on the first trade-off call after a load, or when the key changes
+    DevBuf<float> row_coef, col_coef;
+    bool coef_valid = false;
+    int coef_ndata = 0;
+    float coef_weight0 = 0.0f;
+    DevBuf<int> bflag;               // ... the flag its validation reports
     // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
     DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
-    DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results
+    DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results (bpsf: dsa_lsmr_tradeoff's measures too)
     float* hbatch = nullptr;         // pinned: per-realisation coefficients and flags (bparam) on their way to the device, norms on their way back
     size_t hbatch_cap = 0;
 };
@@ -59,7 +66,7 @@ struct SpmvState {
 // y += A x (mode 1; x: n, y: m) or x += A^T y (mode 2) on device vectors, on the engine's stream; every output
 // element adds its entries in storage order (reference aprod.f90:7-60)
 void spmv_device(Engine* e, int mode, float* d_x, float* d_y);
-// the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch are stale
-inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = false; }
+// the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch (and dsa_lsmr_tradeoff's coefficient copy of them) are stale
+inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = s->coef_valid = false; }
 
 }  // namespace dsa

@@ -72,6 +72,7 @@ def load_library():
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp] + [_vp] * 7
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+    L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
     L.dsa_dropin_error.restype = C.c_char_p
@@ -309,6 +310,29 @@ class Engine:
                                                 int(local_size), _p(x), _p(psf), _p(istop), _p(itn), _p(est)))
         names = ("normA", "condA", "normr", "normAr", "normx")
         return dict(x=x, psf=psf, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+
+    def lsmr_tradeoff(self, b, ndata, weight0, weights, damps, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
+        """K LSMR solves on the matrix of the last spmv_load, whose rows from ndata up are regularisation rows built with weight0:
+        member k on the system with those rows rebuilt with weights[k] (entries fl(c * weights[k]), c their integer coefficient) and
+        damping damps[k], each bit-identical to lsmr(b, damps[k]) on that system.  Returns dict(x=(K, n) or None when not want_x,
+        measures=(K, 3) float64 {sum of squared data residuals, sum of squared C x (unweighted roughness), sum of x^2}, istop=(K,),
+        itn=(K,), normA=(K,), condA, normr, normAr, normx)"""
+        b = np.ascontiguousarray(b, np.float32)
+        w = np.ascontiguousarray(weights, np.float32).ravel()
+        d = np.ascontiguousarray(damps, np.float32).ravel()
+        m, n = self._mn
+        assert b.size == m and w.size == d.size
+        K = w.size
+        x = np.zeros((K, n), np.float32) if want_x else None
+        meas = np.zeros((K, 3))
+        istop = np.zeros(K, np.int32)
+        itn = np.zeros(K, np.int32)
+        est = np.zeros((K, 5), np.float32)
+        self._check(self._L.dsa_lsmr_tradeoff(self._h, K, int(ndata), _p(b), weight0, w.ctypes.data_as(_vp), d.ctypes.data_as(_vp), atol, btol, conlim,
+                                              int(itnlim), int(local_size), _p(x), _p(meas), istop.ctypes.data_as(_vp), itn.ctypes.data_as(_vp),
+                                              est.ctypes.data_as(_vp)))
+        names = ("normA", "condA", "normr", "normAr", "normx")
+        return dict(x=x, measures=meas, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
 
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)

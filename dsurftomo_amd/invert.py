@@ -2,6 +2,7 @@
 
     python -m dsurftomo_amd.invert <directory with DSurfTomo.in, the data file and MOD> [--maxiter N] [--out DIR]
                                    [--bootstrap R [--bootstrap-seed S]] [--resolution] [--checkerboard NX,NY,NZ ...]
+                                   [--tradeoff-weights W1,W2,... [--tradeoff-damps D1,...] [--tradeoff-iter N]]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -32,6 +33,17 @@ NY along longitude, NZ along depth, first block positive (checkerboard()); all p
 lists longitude, latitude, depth, input and recovered update, and the log and the history give the Pearson correlation and the
 gain <m,x>/<m,m>, whole model and per depth layer.  Device-resident rows only (not with --host-rows); they combine with
 --bootstrap.
+
+--tradeoff-weights W1,W2,... adds the regularisation trade-off (L-) curve of one outer iteration's linearised step (--tradeoff-iter N,
+default 1): after that iteration's dsa_lsmr, dsa_lsmr_tradeoff solves the same resident system once per (weight, damp) pair of the grid
+weights x damps (--tradeoff-damps, default the input file's damp; weight-major, tradeoff_grid), member k with the regularisation rows
+rebuilt with its weight in place of weight0 and its own damp: what a rerun of this program with those two parameters would solve in that
+iteration, bit for bit, without its forward call.  The calls are chunked in multiples of 64 members (tradeoff_chunk).
+<input>Tradeoff.dat lists per member: weight, damp, the data misfit ||r||, the roughness ||C x|| (C the integer coefficients of the
+regularisation rows: free of the weight), ||x||, itn, istop, min and max of the update; the log and the history add, per damp, the corner
+of the curve (lcurve_corner: the largest Menger curvature of (log ||C x||, log ||r||) over increasing weight).  The inversion itself
+runs on with the input file's parameters: no other output changes.  Device-resident rows only (not with --host-rows); combines with
+--bootstrap / --resolution / --checkerboard.
 """
 import argparse
 import ctypes as C
@@ -160,6 +172,107 @@ def resolution_chunk(m, n, local_size, budget=32 << 30, cap=4096):
     return k
 
 
+def tradeoff_bytes(m, n, nar, local_size, nreal):
+    """device bytes of a dsa_lsmr_tradeoff call for nreal members on an m x n system of nar entries: the batch buffers (batch_bytes,
+    whose temporary bounds the call's nreal n + m + nreal), the two coefficient copies of the values (nar floats each) and the measures'
+    block partials and results (fp64: two per 64 rows, one per 1024 unknowns, three per member, in groups of 64)"""
+    Rp = 64 * ((nreal + 63) // 64)
+    return batch_bytes(m, n, local_size, nreal) + 8 * nar + 8 * Rp * (2 * -(-m // 64) + -(-n // 1024) + 3)
+
+
+def tradeoff_chunk(m, n, nar, local_size, budget=32 << 30, cap=4096):
+    """members per dsa_lsmr_tradeoff call on an m x n system of nar entries: cap, lowered in multiples of 64 until tradeoff_bytes fits
+    `budget` (64 at the least)"""
+    k = cap
+    while k > 64 and tradeoff_bytes(m, n, nar, local_size, k) > budget:
+        k -= 64
+    return k
+
+
+def parse_tradeoff_list(text):
+    """'V1,V2,...' -> [V1, V2, ...]: at least one float, every one finite and >= 0 (ValueError otherwise)"""
+    try:
+        vals = [float(p) for p in text.split(",")]
+    except ValueError:
+        vals = []
+    if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
+        raise ValueError("a trade-off list is V1,V2,...: at least one finite number >= 0 (got %r)" % text)
+    return vals
+
+
+def _tradeoff_arg(text):
+    try:
+        return parse_tradeoff_list(text)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
+def tradeoff_grid(weights, damps):
+    """(weight, damp) float32 arrays of the len(weights) * len(damps) members, weight-major: member i * len(damps) + j = (weights[i], damps[j])"""
+    w = np.asarray(weights, np.float32).ravel()
+    d = np.asarray(damps, np.float32).ravel()
+    return np.repeat(w, d.size), np.tile(d, w.size)
+
+
+def lcurve_corner(misfit, rough):
+    """Index of the corner of a trade-off curve given in order of increasing weight, or None.  Points where either value is not a
+    finite number > 0 are skipped; every three consecutive remaining points P1 P2 P3 = (log rough, log misfit) give P2 the Menger
+    curvature 2 |P1P2 x P2P3| / (|P1P2| |P2P3| |P1P3|), signed so that the vertex of an L-shaped curve is positive: with increasing
+    weight the roughness falls at first at little cost in misfit (the curve runs towards -x), then the misfit rises (towards +y), a
+    clockwise turn.  Returns the index (into the arrays given) of the largest positive curvature; None with fewer than three usable
+    points or no positive curvature (a turn whose sine is below 1e-12 counts as none)."""
+    mis = np.asarray(misfit, np.float64).ravel()
+    rou = np.asarray(rough, np.float64).ravel()
+    use = [i for i in range(min(mis.size, rou.size)) if np.isfinite(mis[i]) and np.isfinite(rou[i]) and mis[i] > 0 and rou[i] > 0]
+    best, where = 0.0, None
+    for a, b, c in zip(use, use[1:], use[2:]):
+        x1, y1, x2, y2, x3, y3 = (np.log(v) for v in (rou[a], mis[a], rou[b], mis[b], rou[c], mis[c]))
+        cross = (x2 - x1) * (y3 - y2) - (y2 - y1) * (x3 - x2)
+        legs = np.hypot(x2 - x1, y2 - y1) * np.hypot(x3 - x2, y3 - y2)
+        den = legs * np.hypot(x3 - x1, y3 - y1)
+        if abs(cross) <= 1e-12 * legs:                      # (the sine of the turn is rounding noise of the logarithms: a straight line)
+            continue
+        if den > 0 and -2.0 * cross / den > best:
+            best, where = -2.0 * cross / den, b
+    return where
+
+
+TRADEOFF_COLUMNS = ("weight", "damp", "misfit", "rough", "xnorm", "itn", "istop", "dv_min", "dv_max")
+
+
+def write_tradeoff(path, members):
+    """one line per member: weight damp ||r|| ||C x|| ||x|| itn istop min(dv) max(dv); the float32 values with 9 significant digits,
+    the norms (float64) with 17: read_tradeoff gives the same values back"""
+    with open(path, "w") as fh:
+        for t in members:
+            fh.write("%.9g %.9g %.17g %.17g %.17g %d %d %.9g %.9g\n" % tuple(t[k] for k in TRADEOFF_COLUMNS))
+
+
+def read_tradeoff(path):
+    """the members of a file of write_tradeoff: a list of dicts with the keys TRADEOFF_COLUMNS (weight, damp and the update's extremes
+    are float32 values, the norms float64)"""
+    out = []
+    with open(path) as fh:
+        for line in fh:
+            v = line.split()
+            if len(v) != len(TRADEOFF_COLUMNS):
+                raise ValueError("%s: a line of %d columns, not %d" % (path, len(v), len(TRADEOFF_COLUMNS)))
+            kind = lambda k: int if k in ("itn", "istop") else float if k in ("misfit", "rough", "xnorm") else lambda t: float(np.float32(t))
+            out.append({k: kind(k)(t) for k, t in zip(TRADEOFF_COLUMNS, v)})
+    return out
+
+
+def tradeoff_corners(members):
+    """per damp (in order of first appearance) the corner of its curve over increasing weight: [dict(damp, weight, member)], weight and
+    member (index into members) None where lcurve_corner finds none"""
+    out = []
+    for d in dict.fromkeys(t["damp"] for t in members):
+        idx = sorted((i for i, t in enumerate(members) if t["damp"] == d), key=lambda i: members[i]["weight"])
+        k = lcurve_corner([members[i]["misfit"] for i in idx], [members[i]["rough"] for i in idx])
+        out.append(dict(damp=d, weight=None if k is None else members[idx[k]]["weight"], member=None if k is None else idx[k]))
+    return out
+
+
 def psf_columns(psf):
     """(R_jj, horizontal PSF length, vertical PSF length, unknowns without data) from dsa_lsmr_resolution's measures (maxvp, 4):
     lengths sqrt(sum x^2 dh^2 / sum x^2), sqrt(sum x^2 dz^2 / sum x^2) in km; an unknown with sum x^2 = 0 gets zeros"""
@@ -207,13 +320,15 @@ def write_residuals(path, c, dsyn, obst, datweight):
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
-def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None):
+def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
     both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit).
     bootstrap = (R, seed): after dsa_lsmr, R row-resampled solves of the same system by dsa_lsmr_batch (returned as "boot").
     resolution = dict(psf=bool, chunk=int or None, cells=[(NX, NY, NZ), ...]): after dsa_lsmr, the resolution tests of the same
-    system (returned as "res": "psf" from resolution_psf, "checker" from checkerboard_tests)."""
+    system (returned as "res": "psf" from resolution_psf, "checker" from checkerboard_tests).
+    tradeoff = dict(weights=[...], damps=[...], chunk=int or None): after dsa_lsmr, the trade-off sweep of the same system (returned as
+    "trade" from lsmr_tradeoff_sweep)."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -255,6 +370,9 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None):
             res["psf"] = resolution_psf(lib, eng, c, m.value, resolution.get("chunk"))
         if resolution.get("cells"):
             res["checker"] = checkerboard_tests(lib, eng, c, resolution["cells"])
+    trade = None
+    if tradeoff:
+        trade = lsmr_tradeoff_sweep(lib, eng, c, cbst, m.value, nar2.value, tradeoff["weights"], tradeoff["damps"], tradeoff.get("chunk"))
     r = cbst[:dall]
     mean = f(r.sum(dtype=f) / f(dall))
     std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
@@ -268,6 +386,8 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None):
         out["boot"] = boot
     if res is not None:
         out["res"] = res
+    if trade is not None:
+        out["trade"] = trade
     return out
 
 
@@ -330,6 +450,39 @@ def checkerboard_tests(lib, eng, c, cells):
     return dict(models=models, x=x, itn=itn, istop=istop, metrics=metrics, seconds=seconds)
 
 
+def lsmr_tradeoff_sweep(lib, eng, c, cbst, m, nar, weights, damps, chunk=None):
+    """The trade-off sweep of the resident m-row system of nar entries (regularisation rows built with the input file's weight0): the
+    members of tradeoff_grid(weights, damps) in chunks of `chunk` (default tradeoff_chunk(m, maxvp, nar, 10)), one dsa_lsmr_tradeoff call
+    each with the arguments of the dsa_lsmr call above.  Returns dict(weight, damp (K,), x=(K, maxvp) raw updates, measures=(K, 3)
+    {sum r^2, sum (C x)^2, sum x^2}, itn, istop, est=(K, 5), chunk, calls, seconds)."""
+    f = np.float32
+    n = c["nparpi"]
+    w, d = tradeoff_grid(weights, damps)
+    K = w.size
+    chunk = int(chunk or tradeoff_chunk(m, n, nar, 10))
+    x = np.zeros((K, n), f); meas = np.zeros((K, 3))
+    istop = np.zeros(K, np.int32); itn = np.zeros(K, np.int32); est = np.zeros((K, 5), f)
+    t0 = time.perf_counter()
+    calls = 0
+    for first in range(0, K, chunk):
+        q = slice(first, min(first + chunk, K))
+        wk, dk = np.ascontiguousarray(w[q]), np.ascontiguousarray(d[q])
+        rc = lib.dsa_lsmr_tradeoff(eng, wk.size, c["ndata"], _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), C.c_float(1e-6), C.c_float(1e-6),
+                                   C.c_float(100.0), 400, 10, _p(x[q]), _p(meas[q]), _p(istop[q]), _p(itn[q]), _p(est[q]))
+        if rc != 0:
+            raise RuntimeError("dsa_lsmr_tradeoff: %s" % lib.dsa_error_string(eng).decode())
+        calls += 1
+    return dict(weight=w, damp=d, x=x, measures=meas, itn=itn, istop=istop, est=est, chunk=chunk, calls=calls, seconds=time.perf_counter() - t0)
+
+
+def tradeoff_members(t):
+    """the rows of <input>Tradeoff.dat from lsmr_tradeoff_sweep's result: dicts with the keys TRADEOFF_COLUMNS"""
+    nrm = np.sqrt(t["measures"])
+    return [dict(weight=float(t["weight"][k]), damp=float(t["damp"][k]), misfit=float(nrm[k, 0]), rough=float(nrm[k, 1]), xnorm=float(nrm[k, 2]),
+                 itn=int(t["itn"][k]), istop=int(t["istop"][k]), dv_min=float(t["x"][k].min()), dv_max=float(t["x"][k].max()))
+            for k in range(t["weight"].size)]
+
+
 def iteration(lib, c, vsf, obst, log):
     """One pass of main.f90:349-535 on the model vsf (updated in place), the matrix going through host arrays like in the
     reference (dsa_calsurfg -> dsa_iteration_system -> dsa_lsmr_dropin).  Returns the statistics of the pass."""
@@ -388,6 +541,7 @@ def bind(lib):
     lib.dsa_lsmr.argtypes = [C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 8
     lib.dsa_lsmr_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
     lib.dsa_lsmr_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
+    lib.dsa_lsmr_tradeoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p] + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5
     lib.dsa_error_string.restype = C.c_char_p
     lib.dsa_error_string.argtypes = [C.c_void_p]
     return lib
@@ -412,6 +566,26 @@ def check_resolution(resolution, checkerboards, host_rows, chunk=None):
         raise ValueError("resolution_chunk must be at least 1 (got %d)" % chunk)
 
 
+def check_tradeoff(weights, damps, iteration, host_rows, maxiter=None, chunk=None):
+    """the trade-off sweep's preconditions, checked before anything touches the GPU (weights None: no sweep)"""
+    if weights is None:
+        if damps is not None:
+            raise ValueError("--tradeoff-damps needs --tradeoff-weights")
+        return
+    for name, vals in (("--tradeoff-weights", weights), ("--tradeoff-damps", damps)):
+        if vals is None:
+            continue
+        vals = list(vals)
+        if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
+            raise ValueError("%s takes at least one value, every one finite and >= 0 (got %r)" % (name, vals))
+    if host_rows:
+        raise ValueError("--tradeoff-weights solves on the device-resident system: it cannot be combined with --host-rows")
+    if iteration < 1 or (maxiter is not None and iteration > maxiter):
+        raise ValueError("--tradeoff-iter must be an outer iteration 1..maxiter (got %d%s)" % (iteration, "" if maxiter is None else ", maxiter %d" % maxiter))
+    if chunk is not None and (chunk < 64 or chunk % 64):
+        raise ValueError("tradeoff_chunk must be a multiple of 64 (got %d)" % chunk)
+
+
 def _solve_stats(itn, istop):
     stops = {int(k): int(v) for k, v in zip(*np.unique(istop, return_counts=True))}
     return dict(realisations=int(itn.size), itn_min=int(itn.min()), itn_median=float(np.median(itn)), itn_max=int(itn.max()), istop=stops)
@@ -423,13 +597,18 @@ def _solve_text(h):
 
 
 def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1, resolution=False, checkerboard=(),
-        resolution_chunk=None):
+        resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None):
     check_bootstrap(bootstrap, host_rows)
     check_resolution(resolution, checkerboard, host_rows, resolution_chunk)
+    check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
     cells = [tuple(int(v) for v in cell) for cell in checkerboard or ()]
     lib = bind(load_library())
     c = io.load(directory)
     maxiter = c["maxiter"] if maxiter is None else maxiter
+    check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
+    sweep = None
+    if tradeoff_weights is not None:
+        sweep = dict(weights=list(tradeoff_weights), damps=[float(c["damp"])] if tradeoff_damps is None else list(tradeoff_damps), chunk=tradeoff_chunk)
     vsf = np.asfortranarray(c["vels"].copy())
     obst = np.ascontiguousarray(c["obst"])
     vsftrue = None
@@ -447,7 +626,8 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         else:
             last = it == maxiter
             st = iteration_device(lib, c, vsf, obst, log, (bootstrap, bootstrap_seed) if bootstrap and last else None,
-                                  dict(psf=resolution, chunk=resolution_chunk, cells=cells) if (resolution or cells) and last else None)
+                                  dict(psf=resolution, chunk=resolution_chunk, cells=cells) if (resolution or cells) and last else None,
+                                  sweep if it == tradeoff_iter else None)
         log("%2dth iteration..." % it)
         log(" mean,std_devs and rms of residual after weighting: %8.1fms %8.2fms %8.3f" % (st["mean_ms"], st["std_ms"], st["rms"]))
         log(" min and max velocity variation %7.4f%7.4f" % (st["dv_min"], st["dv_max"]))
@@ -458,7 +638,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res")}
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade")}
         if "boot" in st:
             b = st["boot"]
             write_std(name + "Std.dat", c, b["std"])
@@ -489,6 +669,16 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                 log(" checkerboard k%02d %d,%d,%d: correlation %.3f gain %.3f; by layer correlation %s gain %s" %
                     ((q + 1,) + cell + (mt["corr"], mt["gain"], " ".join("%.2f" % v for v in mt["corr_layers"]),
                                         " ".join("%.2f" % v for v in mt["gain_layers"]))))
+        if "trade" in st:
+            t = st["trade"]
+            members = tradeoff_members(t)
+            write_tradeoff(name + "Tradeoff.dat", members)
+            ht = h["tradeoff"] = dict(_solve_stats(t["itn"], t["istop"]), iteration=it, weights=sweep["weights"], damps=sweep["damps"], chunk=t["chunk"],
+                                      calls=t["calls"], seconds=t["seconds"], members=members, corners=tradeoff_corners(members))
+            log(" tradeoff: %d weights x %d damps at iteration %d: %s, %d calls of up to %d (%.3f s)" %
+                (len(sweep["weights"]), len(sweep["damps"]), it, _solve_text(ht), ht["calls"], ht["chunk"], ht["seconds"]))
+            for cn in ht["corners"]:
+                log(" tradeoff damp %g: corner %s" % (cn["damp"], "not found" if cn["weight"] is None else "at weight %g" % cn["weight"]))
         history.append(h)
     if vsftrue is not None:
         write_model(os.path.join(out_dir, "Vs_model.real"), c, vsftrue)
@@ -516,15 +706,22 @@ def main(argv=None):
     ap.add_argument("--checkerboard", type=_checkerboard_arg, action="append", default=[], metavar="NX,NY,NZ",
                     help="a +-0.1 km/s block checkerboard through the last iteration's step (may be repeated): <input>Checker.dat.kNN and "
                          "its recovery in the log")
+    ap.add_argument("--tradeoff-weights", type=_tradeoff_arg, default=None, metavar="W1,W2,...",
+                    help="the trade-off curve of one iteration's step over these smoothing weights (and --tradeoff-damps): <input>Tradeoff.dat, "
+                         "misfit against roughness per (weight, damp), and the curve's corner per damp in the log")
+    ap.add_argument("--tradeoff-damps", type=_tradeoff_arg, default=None, metavar="D1,...", help="damps of the trade-off sweep (default: the input file's damp)")
+    ap.add_argument("--tradeoff-iter", type=int, default=1, metavar="N", help="the outer iteration whose step is swept, 1..maxiter (default 1)")
     args = ap.parse_args(argv)
     try:
         check_bootstrap(args.bootstrap, args.host_rows)
         check_resolution(args.resolution, args.checkerboard, args.host_rows)
+        check_tradeoff(args.tradeoff_weights, args.tradeoff_damps, args.tradeoff_iter, args.host_rows, args.maxiter)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(args.out, exist_ok=True)
     run(args.directory, args.maxiter, args.out, host_rows=args.host_rows, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
-        resolution=args.resolution, checkerboard=args.checkerboard)
+        resolution=args.resolution, checkerboard=args.checkerboard, tradeoff_weights=args.tradeoff_weights, tradeoff_damps=args.tradeoff_damps,
+        tradeoff_iter=args.tradeoff_iter)
     return 0
 
 

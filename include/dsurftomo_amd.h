@@ -226,6 +226,24 @@ int dsa_lsmr_resolution(dsa_engine* e, int nreal, int ndata, const float* models
                         float damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x, double* psf,
                         int* istop, int* itn, float* est);
 
+/* Regularisation trade-off sweep: nreal LSMR solves on the (m x n) matrix of the last dsa_spmv_load /
+ * dsa_iteration_system_device, whose rows below ndata are data rows and whose rows from ndata up are regularisation rows
+ * built with weight0 (every entry fl(c*weight0), c a non-zero integer, |c| <= 64).  Member k solves the system that keeps
+ * the data rows and gives every regularisation entry the value fl(c*weight[k]) -- what dsa_iteration_system(_device)
+ * builds with weight[k] in place of weight0 -- with damping damp[k] and the shared right-hand side b[m]; it is
+ * bit-identical (x, istop, itn, est as in dsa_lsmr_batch) to dsa_lsmr(b, damp[k], ...) on that system.  weight[k] = 0
+ * and damp[k] = 0 are valid.  x (nreal*n) may be NULL: then nothing of size n*nreal leaves the device.  measures
+ * (3*nreal, may be NULL): measures[3k..3k+2] = {sum over i < ndata of (b_i - (A x_k)_i)^2, sum over i >= ndata of
+ * ((C x_k)_i)^2, sum of x_k[j]^2}, C the integer coefficients (free of the weight: comparable across members); fp64,
+ * every row's sum over its entries in storage order, in a fixed order (repeated calls give the same bits).  The resident
+ * matrix, dsa_lsmr, dsa_lsmr_batch and dsa_lsmr_resolution are left as they were.  Errors: DSA_ERR_ARGUMENT (nreal < 1,
+ * ndata outside [1, m], a null b / weight / damp / istop / itn / est, weight0 not finite or not > 0, a negative or
+ * non-finite weight[k] or damp[k], a regularisation entry that is not fl(c*weight0)), DSA_ERR_STATE (no matrix),
+ * DSA_ERR_DEVICE. */
+int dsa_lsmr_tradeoff(dsa_engine* e, int nreal, int ndata, const float* b, float weight0, const float* weight,
+                      const float* damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x,
+                      double* measures, int* istop, int* itn, float* est);
+
 /* One outer iteration's host glue (reference main.f90:361-466 and :520-535; plain host code, no device):
  * iteration_system: residual cbst = obst - dsyn, percentile weights (getpercentile.f90), rows scaled by their weights,
  *   DWS norm[maxvp] with dws = {max, mean}, regularisation rows appended.  In/out rw, col (capacity entries) and iw

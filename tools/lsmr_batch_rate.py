@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """dsa_lsmr_batch against R sequential dsa_lsmr calls (default placement: products on the device, ordered sums on the host).
 
-    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution]
+    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution[,tradeoff]]
 
 Per system and R: bootstrap row scales (dsurftomo_amd.invert.bootstrap_row_scales), one warm-up of each path, then the batch
 once and R sequential solves of the explicitly scaled systems (the scaled matrices are loaded outside the timed region; each
 solve is timed alone).  Prints one line per (system, R) and checks realisation 0 of the batch against its sequential solve bit
-for bit.  Resolution leg (resolution_leg): every unknown's PSF by dsa_lsmr_resolution against sequential dsa_lsmr spike solves.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
+for bit.  Resolution leg (resolution_leg): every unknown's PSF by dsa_lsmr_resolution against sequential dsa_lsmr spike solves.
+Trade-off leg (tradeoff_leg, --legs tradeoff): K = each --R (weight, damp) members by dsa_lsmr_tradeoff against sequential rebuilds of
+the system with each member's weight + dsa_lsmr, a sample of --seq-max members timed and scaled to K.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
 The systems are the product's own (dsa_calsurfg + dsa_iteration_system, or tests/synth_matrix.py): nothing here loads oracle/."""
 import argparse
 import os
@@ -121,6 +123,52 @@ def resolution_leg(name, e, S, ndata, damp, itnlim, coords, seq_max):
            itn_seq / len(js), t_seq_all / t_res, int(js[0]), inv.same(b0, first_seq) == []), flush=True)
 
 
+WEIGHT0 = dict(taipei=4.0, multiblock=2.0, headline=2.0)      # the weight the systems' regularisation rows are built with
+
+
+def tradeoff_leg(name, e, S, ndata, weight0, damp, itnlim, Ks, seq_max):
+    """K (weight, damp) members by one dsa_lsmr_tradeoff call (x and the measures back) against what a rerun per member does after its
+    forward call: the system rebuilt with the member's weight (its regularisation entries fl(c * weight), loaded: both orderings built)
+    and dsa_lsmr with the member's damp.  Up to seq_max members spread over the grid are run that way, each step timed alone, and
+    scaled to K; member 0 is checked bit for bit.  Weights: weight0 / 16 .. 16 weight0 (geometric), damps: damp x {0.25, 0.5, 1, 2}
+    (K divisible by 4) or damp alone."""
+    rows = S["iw"][1:S["nar"] + 1] - 1
+    reg = rows >= ndata
+    coef = np.rint(S["rw"][reg] / np.float32(weight0)).astype(np.float32)
+    assert np.array_equal(coef * np.float32(weight0), S["rw"][reg])
+    for K in Ks:
+        damps = [0.25 * damp, 0.5 * damp, damp, 2.0 * damp] if K % 4 == 0 else [damp]
+        w, d = invert.tradeoff_grid(np.geomspace(weight0 / 16.0, weight0 * 16.0, K // len(damps)), damps)
+        load(e, S)
+        e.lsmr_tradeoff(S["b"], ndata, weight0, w, d, itnlim=2)            # warm-up: contiguous and coefficient copies, allocations, code
+        t0 = time.perf_counter()
+        T = e.lsmr_tradeoff(S["b"], ndata, weight0, w, d, itnlim=itnlim)
+        t_sweep = time.perf_counter() - t0
+        ks = np.unique(np.linspace(0, K - 1, min(seq_max, K)).astype(int))
+        e.lsmr(S["b"], damp, itnlim=2)
+        t_load, t_seq, itn_seq, first = 0.0, 0.0, 0, None
+        for k in ks:
+            rw = S["rw"].copy()
+            t0 = time.perf_counter()
+            rw[reg] = coef * w[k]
+            load(e, S, rw)
+            t_load += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            got = e.lsmr(S["b"], float(d[k]), itnlim=itnlim)
+            t_seq += time.perf_counter() - t0
+            itn_seq += got["itn"]
+            if first is None:
+                first = got
+        k0 = int(ks[0])
+        b0 = dict(x=T["x"][k0], istop=int(T["istop"][k0]), itn=int(T["itn"][k0]), **{q: T[q][k0] for q in EST})
+        scale = K / len(ks)
+        print("%s tradeoff K %4d: sweep %9.1f ms (itn max %d, total %d) | %d of %d sequential: rebuild + load %9.1f ms, dsa_lsmr %9.1f ms "
+              "(%.2f + %.2f ms per member, %.1f itn) | speed-up %.1fx over the solves, %.1fx with the rebuilds | member %d identical: %s" %
+              (name, K, 1e3 * t_sweep, int(T["itn"].max()), int(T["itn"].sum()), len(ks), K, 1e3 * t_load * scale, 1e3 * t_seq * scale,
+               1e3 * t_load / len(ks), 1e3 * t_seq / len(ks), itn_seq / len(ks), t_seq * scale / t_sweep, (t_seq + t_load) * scale / t_sweep, k0,
+               inv.same(b0, first) == []), flush=True)
+
+
 def load(e, S, rw=None):
     nar = S["nar"]
     e.spmv_load(S["m"], S["n"], S["rw"] if rw is None else rw, S["iw"][1:nar + 1], S["iw"][nar + 1:])
@@ -131,7 +179,7 @@ def main():
     ap.add_argument("--systems", default="taipei,multiblock")
     ap.add_argument("--R", default="1,8,64,256")
     ap.add_argument("--seq-max", type=int, default=64, help="sequential solves actually run per R (the rest extrapolated from their mean)")
-    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch) and / or resolution (dsa_lsmr_resolution)")
+    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch), resolution (dsa_lsmr_resolution) and / or tradeoff (dsa_lsmr_tradeoff)")
     args = ap.parse_args()
     Rs = [int(v) for v in args.R.split(",")]
     legs = args.legs.split(",")
@@ -145,6 +193,8 @@ def main():
         try:
             if "resolution" in legs:
                 resolution_leg(name, e, S, ndata, damp, itnlim, coords, args.seq_max)
+            if "tradeoff" in legs:
+                tradeoff_leg(name, e, S, ndata, WEIGHT0[name], damp, itnlim, Rs, args.seq_max)
             if "bootstrap" not in legs:
                 continue
             scales = invert.bootstrap_row_scales(ndata, S["m"], max(Rs), seed=1)
