@@ -31,7 +31,14 @@
 // scales are 1 on the data rows and weight_k on the regularisation rows, so member k multiplies by fl(a * 1) = a and fl(c * weight_k):
 // the system dsa_iteration_system builds with weight_k.  damp_k goes to member k's LsmrScalars.  k_b_meas_rows / k_b_meas_x /
 // k_b_meas_sum reduce each solution to its misfit, roughness and size on the device.
+//
+// dsa_lsmr_voronoi runs it on K random Voronoi projections of the data rows: member k's unknowns are the ncells cells of
+// its tessellation, its matrix M_k the resident data rows with every column j relabelled cell_k(j).  The batch vectors have the lengths
+// (ndata, ncells), and Batch::product is swapped for the projected one: mode 1 expands v to the unknowns through the cell map and runs
+// k_b_spmv<true> over the resident data rows, mode 2 walks, per (member, cell), the member's list of CSR positions sorted by cell
+// (k_v_colprod).  k_v_assign makes the tessellations, k_v_stats the ensemble mean and standard deviation per unknown.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -592,11 +599,154 @@ __global__ __launch_bounds__(64) void k_b_meas_sum(int nbr, int nbx, int nreal, 
     meas[3 * (size_t)r] = s0; meas[3 * (size_t)r + 1] = s1; meas[3 * (size_t)r + 2] = s2;
 }
 
+// ---- dsa_lsmr_voronoi: the tessellations, every member's list for the transposed product, the projected products, the ensemble statistics ----
+
+constexpr int kVorTile = 1024;              // seed points staged per pass: 1024 x 3 x 8 B = 24 KB of LDS
+
+// cell_mm[r * n + j] = the seed s in [0, ncells) of member r nearest to unknown j: d2 = ((xj-xs)^2 + (yj-ys)^2) + (zj-zs)^2 in fp64 in that
+// association (no contraction), the lowest s on ties.  One thread per (member, unknown): blockIdx.x the unknowns, the y dimension strides
+// over the members; the member's seed points pass through LDS in tiles of kVorTile, every thread reads the same one (a broadcast).
+__global__ __launch_bounds__(256) void k_v_assign(int n, int ncells, int nreal, const double* __restrict__ xyz, const int* __restrict__ seeds,
+                                                  int* __restrict__ cell_mm)
+{
+    __shared__ double sx[kVorTile], sy[kVorTile], sz[kVorTile];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const size_t jj = (size_t)min(j, n - 1);
+    const double x = xyz[3 * jj], y = xyz[3 * jj + 1], z = xyz[3 * jj + 2];
+    for (int r = blockIdx.y; r < nreal; r += gridDim.y) {
+        const int* __restrict__ sd = seeds + (size_t)r * ncells;
+        double best = INFINITY;
+        int bi = 0;
+        for (int s0 = 0; s0 < ncells; s0 += kVorTile) {
+            const int cnt = min(kVorTile, ncells - s0);
+            __syncthreads();
+            for (int t = threadIdx.x; t < cnt; t += 256) {
+                const size_t q = 3 * (size_t)sd[s0 + t];
+                sx[t] = xyz[q]; sy[t] = xyz[q + 1]; sz[t] = xyz[q + 2];
+            }
+            __syncthreads();
+            for (int t = 0; t < cnt; ++t) {
+                const double dx = x - sx[t], dy = y - sy[t], dz = z - sz[t];
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 < best) { best = d2; bi = s0 + t; }
+            }
+        }
+        if (j < n) cell_mm[(size_t)r * n + j] = bi;
+    }
+}
+
+// (g, j, l) of the batch layout <- the member-major cells (0 in the padding lanes)
+__global__ void k_v_cellmap(int n, int nreal, const int* __restrict__ cell_mm, int* __restrict__ cell)
+{
+    LB_GROUP_LOOP(n) {
+        const int r = g * 64 + (int)(t & 63);
+        cell[gbase + t] = r < nreal ? cell_mm[(size_t)r * (size_t)n + (t >> 6)] : 0;
+    }
+}
+
+// rowof[p] = the row whose segment of the CSR copy holds position p < nnz = ptr[ndata] (the last row with ptr[row] <= p)
+__global__ void k_v_rowof(int ndata, long long nnz, const long long* __restrict__ ptr, int* __restrict__ rowof)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    int lo = 0, hi = ndata;                                           // ptr[lo] <= p < ptr[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (ptr[mid] <= p) lo = mid; else hi = mid;
+    }
+    rowof[p] = lo;
+}
+
+// The sort of one lane group's lists: item i = (member rl = i / nnz of the group, position p = i % nnz) gets the key rl * ncells + cell of
+// member rl at the column of p, and the value p.  A stable sort by key leaves member rl's positions at [rl * nnz, (rl + 1) * nnz), by
+// cell, ascending within a cell: the listing order of the member's system.
+__global__ void k_v_keys(long long items, long long nnz, int n, int ncells, const int* __restrict__ cell_mm, const int* __restrict__ idx,
+                         int* __restrict__ keys, int* __restrict__ pos)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= items) return;
+    const long long rl = i / nnz, p = i - rl * nnz;
+    keys[i] = (int)rl * ncells + cell_mm[(size_t)rl * (size_t)n + (size_t)idx[p]];
+    pos[i] = (int)p;
+}
+
+// cptr[rl * (ncells + 1) + c] = where cell c begins in member rl's list: the first sorted item with a key >= rl * ncells + c, less rl * nnz
+__global__ void k_v_cptr(int members, int ncells, long long nnz, const int* __restrict__ keys, int* __restrict__ cptr)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)members * (ncells + 1)) return;
+    const long long rl = t / (ncells + 1);
+    const long long key = rl * ncells + (t - rl * (ncells + 1));
+    long long lo = 0, hi = (long long)members * nnz;                  // the first item with keys[item] >= key lies in [lo, hi]
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if ((long long)keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    cptr[t] = (int)(lo - rl * nnz);
+}
+
+// mode 1, first half: vfull(g, j, l) = v(g, cell(g, j, l), l), the member's vector on the unknowns; k_b_spmv<true> over the data rows follows
+__global__ void k_v_expand(int n, int ncells, const int* __restrict__ cell, const float* __restrict__ v, float* __restrict__ vfull)
+{
+    LB_GROUP_LOOP(n) vfull[gbase + t] = v[((size_t)g * ncells + (size_t)cell[gbase + t]) * 64 + (t & 63)];
+}
+
+// mode 2: v_r[c] = pre_r * v_r[c] + sum over the entries of member r's cell c, in listing order, of fl(a * u_r[row]), where flag_r.  One
+// wavefront per (member, cell), four per block, blocks member-major: the 64 lanes load 64 list entries at a time (position, then value,
+// row and operand) and form the products in parallel; the additions run in order onto one wave-uniform accumulator, every term
+// broadcast from its lane.  ut: u member-major (ut[r * ndata + row]), so a member's operands are one contiguous vector.
+__global__ __launch_bounds__(256) void k_v_colprod(int ncells, int ndata, long long nnz, int nblk, const int* __restrict__ list, const int* __restrict__ cptr,
+                                                   const float* __restrict__ val, const int* __restrict__ rowof, const float* __restrict__ ut,
+                                                   float* __restrict__ v, const float* __restrict__ pre, const int* __restrict__ flag)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)nblk));
+    const int c = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % (unsigned)nblk) * 4 + (int)(threadIdx.x >> 6));
+    if (c >= ncells || flag[r] == 0) return;
+    float* __restrict__ o = v + ((size_t)(r >> 6) * ncells + c) * 64 + (r & 63);
+    const int* __restrict__ L = list + (size_t)r * (size_t)nnz;
+    const float* __restrict__ u = ut + (size_t)r * ndata;
+    float acc = *o;
+    if (pre) acc = pre[r] * acc;
+    const int k1 = cptr[(size_t)r * (ncells + 1) + c + 1];
+    for (int k = cptr[(size_t)r * (ncells + 1) + c]; k < k1; k += 64) {
+        float t = 0.0f;
+        if (k + lane < k1) {
+            const int p = L[k + lane];
+            t = val[p] * u[rowof[p]];
+        }
+        const int cnt = min(64, k1 - k);                              // (wave-uniform; a lane past it holds no term and none is added)
+        if (cnt == 64) {
+#pragma unroll
+            for (int i = 0; i < 64; ++i) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), i));
+        } else
+            for (int i = 0; i < cnt; ++i) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), i));
+    }
+    if (lane == 0) *o = acc;
+}
+
+// stats[j] = the mean, stats[n + j] = the sample standard deviation (0 for nreal = 1) over the members k = 0 .. nreal - 1, in that order, of
+// xf(k, j) (xf: a batch vector over the unknowns); fp64, one thread per unknown
+__global__ void k_v_stats(int n, int nreal, const float* __restrict__ xf, double* __restrict__ stats)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    auto at = [&](int k) { return (double)xf[((size_t)(k >> 6) * n + j) * 64 + (k & 63)]; };
+    double s = 0.0;
+    for (int k = 0; k < nreal; ++k) s = s + at(k);
+    const double mean = s / (double)nreal;
+    double ss = 0.0;
+    for (int k = 0; k < nreal; ++k) { const double d = at(k) - mean; ss = ss + d * d; }
+    stats[j] = mean;
+    stats[(size_t)n + j] = nreal > 1 ? sqrt(ss / (double)(nreal - 1)) : 0.0;
+}
+
 // ---- the batch shared by dsa_lsmr_batch and dsa_lsmr_resolution: set-up, then (the caller fills u and the row scales) the LSMR loop ----
 struct Batch {
     Engine* e = nullptr;
     SpmvState* S = nullptr;
-    int m = 0, n = 0, G = 0, Rp = 0, localVecs = 0;
+    int m = 0, n = 0, G = 0, Rp = 0, localVecs = 0;      // m, n: lengths of the batch vectors (the solved system's)
+    int nfull = 0;                                       // columns of the resident matrix: n, but for dsa_lsmr_voronoi (n = ncells)
     size_t vm = 0, vn = 0;
     hipStream_t st = nullptr;
     // host mirror of bparam, then Rp norms.  The host writes the mirror only after a synchronisation that follows the previous upload.
@@ -605,6 +755,9 @@ struct Batch {
     float* hred = nullptr;
     const float* rval = nullptr;     // values the products read beside row_csr / col_csr (batch_begin: the resident ones; dsa_lsmr_tradeoff: the coefficient copy)
     const float* cval = nullptr;
+    bool projected = false;          // dsa_lsmr_voronoi: product() multiplies by the member's projected matrix
+    long long pnnz = 0;              // ... entries of the data rows
+    int preal = 0;                   // ... members
 
     const float* coef(int f) const { return S->bparam.p + (size_t)f * Rp; }
     const int* flag(int f) const { return reinterpret_cast<const int*>(S->bparam.p + (size_t)NCOEF * Rp) + (size_t)f * Rp; }
@@ -625,6 +778,7 @@ struct Batch {
     // mode 1: u = pre_r u + A v; mode 2: v = pre_r v + A' u (where the flag is set)
     void product(int mode, const float* pre, const int* fl)
     {
+        if (projected) { projected_product(mode, pre, fl); return; }
         if (mode == 1)
             hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S->row_csr.ptr.p, rval, S->row_csr.idx.p,
                                (const float*)S->bscale.p, (const float*)S->bv.p, S->bu.p, pre, fl);
@@ -632,23 +786,41 @@ struct Batch {
             hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S->col_csr.ptr.p, cval, S->col_csr.idx.p,
                                (const float*)S->bscale.p, (const float*)S->bu.p, S->bv.p, pre, fl);
     }
+    // The same for member k's M_k (the data rows, column j relabelled cell_k(j); n = ncells).  Mode 1: v expanded to the unknowns, then the
+    // resident data rows (row scales 1: fl(a * 1) = a) -- row i adds a * v[cell(col)] in storage order.  Mode 2: u member-major, then
+    // every (member, cell) adds its list in order.
+    void projected_product(int mode, const float* pre, const int* fl)
+    {
+        if (mode == 1) {
+            hipLaunchKernelGGL(k_v_expand, grid_of(nfull, G), dim3(256), 0, st, nfull, n, (const int*)S->vcell.p, (const float*)S->bv.p, S->vfull.p);
+            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, nfull, S->row_csr.ptr.p, rval, S->row_csr.idx.p,
+                               (const float*)S->bscale.p, (const float*)S->vfull.p, S->bu.p, pre, fl);
+        } else {
+            hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (m + 255) / 256), (unsigned)std::min(preal, 65535)), dim3(256), 0, st, m, preal,
+                               (const float*)S->bu.p, S->vut.p);
+            const int nblk = (n + 3) / 4;
+            hipLaunchKernelGGL(k_v_colprod, dim3((unsigned)((size_t)nblk * preal)), dim3(256), 0, st, n, m, pnnz, nblk, (const int*)S->vlist.p, (const int*)S->vcptr.p,
+                               rval, (const int*)S->vrowof.p, (const float*)S->vut.p, S->bv.p, pre, fl);
+        }
+    }
 };
 
-// contiguous copies, buffers for nreal realisations (btmp: `tmp` floats), the host mirror cleared
-int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B)
+// contiguous copies, buffers for nreal realisations (btmp: `tmp` floats), the host mirror cleared.  rows / cols > 0: the batch vectors
+// have these lengths in place of the resident matrix's (dsa_lsmr_voronoi: ndata, ncells)
+int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B, int rows = 0, int cols = 0)
 {
     SpmvState& S = *e->spmv;
     B.e = e; B.S = &S;
-    const int m = S.m, n = S.n, G = (nreal + 63) / 64, Rp = 64 * G;
-    B.m = m; B.n = n; B.G = G; B.Rp = Rp;
+    const int m = rows > 0 ? rows : S.m, n = cols > 0 ? cols : S.n, G = (nreal + 63) / 64, Rp = 64 * G;
+    B.m = m; B.n = n; B.nfull = S.n; B.G = G; B.Rp = Rp;
     B.localVecs = std::max(0, std::min(localSize, std::min(m, n)));                              // :365
     B.vm = (size_t)G * m * 64; B.vn = (size_t)G * n * 64;
     B.st = e->stream;
     const size_t vm = B.vm, vn = B.vn;
     LB_TRY(e, hipSetDevice(e->device));
     if (!S.contiguous_valid) {
-        int rc = build_contiguous(e, S.by_row, m, S.nar, S.row_csr);
-        if (rc == 0) rc = build_contiguous(e, S.by_col, n, S.nar, S.col_csr);
+        int rc = build_contiguous(e, S.by_row, S.m, S.nar, S.row_csr);
+        if (rc == 0) rc = build_contiguous(e, S.by_col, S.n, S.nar, S.col_csr);
         if (rc != 0) return rc;
         S.contiguous_valid = true;
     }
@@ -965,6 +1137,87 @@ int dsa_lsmr_tradeoff(dsa_engine* h_, int nreal, int ndata, const float* b, floa
     hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
     hipLaunchKernelGGL(k_b_meas_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
     LB_TRY(e, hipMemcpyAsync(measures, d_meas, 3 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
+
+int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const float* b, const double* xyz, const int* seeds, float damp, float atol, float btol,
+                     float conlim, int itnlim, int localSize, float* z, int* cell, double* stats, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (nreal < 1 || nreal > 64 * 65535 || !b || !xyz || !seeds || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: nreal < 1 or a null b / xyz / seeds / istop / itn / est"); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_voronoi: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    const int m = e->spmv->m, n = e->spmv->n;
+    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    if (ncells < 1 || ncells > n) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ncells %d outside 1..%d", ncells, n); return DSA_ERR_ARGUMENT; }
+    if (ncells > (1 << 24)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ncells %d above %d (the sort keys are 64 ncells)", ncells, 1 << 24); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(damp)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: damp is not finite"); return DSA_ERR_ARGUMENT; }
+    for (size_t i = 0; i < 3 * (size_t)n; ++i)
+        if (!std::isfinite(xyz[i])) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: coordinate %d of unknown %zu is not finite", (int)(i % 3), i / 3); return DSA_ERR_ARGUMENT; }
+    for (size_t i = 0; i < (size_t)nreal * ncells; ++i)
+        if (seeds[i] < 0 || seeds[i] >= n) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: seed %zu of member %zu is %d, outside 0..%d", i % ncells, i / ncells, seeds[i], n - 1); return DSA_ERR_ARGUMENT; }
+    if ((size_t)((ncells + 3) / 4) * (size_t)nreal > 0x7fffffffu) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: %d members of %d cells are more than one call takes", nreal, ncells); return DSA_ERR_ARGUMENT; }
+    Batch B;
+    // btmp: the solutions on their way out (member-major), then b
+    const size_t zs = z ? (size_t)nreal * ncells : 0;
+    if (int rc = batch_begin(e, nreal, localSize, zs + (size_t)ndata, B, ndata, ncells)) return rc;
+    SpmvState& S = *e->spmv;
+    const int G = B.G, Rp = B.Rp;
+    hipStream_t st = B.st;
+    long long nnz = 0;                                                // entries of the data rows: the first ndata segments of the CSR copy
+    LB_TRY(e, hipMemcpyAsync(&nnz, S.row_csr.ptr.p + ndata, 8, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipStreamSynchronize(st));
+    if (nnz < 0 || nnz > (1ll << 31) / 64 - 1) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: the data rows hold %lld entries, more than the %lld one lane group's sort takes", nnz, (1ll << 31) / 64 - 1); return DSA_ERR_ARGUMENT; }
+    const size_t nz1 = std::max<size_t>((size_t)nnz, 1), vfull = (size_t)G * n * 64;
+    if (e->ensure(S.vxyz, 3 * (size_t)n) || e->ensure(S.vseeds, (size_t)nreal * ncells) || e->ensure(S.vcell_mm, (size_t)Rp * n) || e->ensure(S.vcell, vfull) ||
+        e->ensure(S.vfull, vfull) || e->ensure(S.vut, (size_t)Rp * ndata) || e->ensure(S.vrowof, nz1) || e->ensure(S.vlist, (size_t)Rp * nz1) ||
+        e->ensure(S.vcptr, (size_t)Rp * (ncells + 1)) || e->ensure(S.vkeys, 64 * nz1) || e->ensure(S.vkeys_out, 64 * nz1) || e->ensure(S.vpos, 64 * nz1) ||
+        (stats && e->ensure(S.vstats, 2 * (size_t)n))) return e->status;
+    // the tessellations
+    LB_TRY(e, hipMemcpyAsync(S.vxyz.p, xyz, 3 * (size_t)n * 8, hipMemcpyHostToDevice, st));
+    LB_TRY(e, hipMemcpyAsync(S.vseeds.p, seeds, (size_t)nreal * ncells * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_v_assign, dim3((unsigned)((n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, ncells, nreal, (const double*)S.vxyz.p,
+                       (const int*)S.vseeds.p, S.vcell_mm.p);
+    hipLaunchKernelGGL(k_v_cellmap, grid_of(n, G), dim3(256), 0, st, n, nreal, (const int*)S.vcell_mm.p, S.vcell.p);
+    // every member's list: the data rows' CSR positions, stably sorted by cell, one lane group per sort
+    LB_TRY(e, hipMemsetAsync(S.vcptr.p, 0, (size_t)Rp * (ncells + 1) * 4, st));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_v_rowof, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, ndata, nnz, (const long long*)S.row_csr.ptr.p, S.vrowof.p);
+        int bits = 1;
+        while ((1ll << bits) < 64ll * ncells) ++bits;
+        for (int g = 0; g < G; ++g) {
+            const int members = std::min(64, nreal - 64 * g);
+            const long long items = (long long)members * nnz;
+            int* list = S.vlist.p + (size_t)g * 64 * (size_t)nnz;
+            hipLaunchKernelGGL(k_v_keys, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, items, nnz, n, ncells, (const int*)(S.vcell_mm.p + (size_t)g * 64 * n),
+                               (const int*)S.row_csr.idx.p, S.vkeys.p, S.vpos.p);
+            size_t tmp_bytes = 0;
+            LB_TRY(e, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const int*)S.vkeys.p, S.vkeys_out.p, (const int*)S.vpos.p, list, (int)items, 0, bits, st));
+            if (e->ensure(S.vsort, std::max<size_t>(tmp_bytes, 1))) return e->status;
+            LB_TRY(e, hipcub::DeviceRadixSort::SortPairs(S.vsort.p, tmp_bytes, (const int*)S.vkeys.p, S.vkeys_out.p, (const int*)S.vpos.p, list, (int)items, 0, bits, st));
+            const long long np = (long long)members * (ncells + 1);
+            hipLaunchKernelGGL(k_v_cptr, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, members, ncells, nnz, (const int*)S.vkeys_out.p,
+                               S.vcptr.p + (size_t)g * 64 * (ncells + 1));
+        }
+    }
+    // u = b, row scales 1 (k_b_tradeoff_init with every row a data row: it reads no weight), then the loop on the projected products
+    float* d_b = S.btmp.p + zs;
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)ndata * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b_tradeoff_init, grid_of(ndata, G), dim3(256), 0, st, ndata, ndata, nreal, (const float*)d_b, (const float*)nullptr, S.bscale.p, S.bu.p);
+    LB_TRY(e, hipGetLastError());
+    B.projected = true; B.pnnz = nnz; B.preal = nreal;
+    const std::vector<float> damps((size_t)nreal, damp);
+    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, z, istop, itn, est)) return rc;
+    if (cell) LB_TRY(e, hipMemcpyAsync(cell, S.vcell_mm.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
+    if (stats) {
+        // x_k[j] = z_k[cell_k(j)] on the unknowns (the expansion of mode 1, of the solutions), then its statistics over k in order
+        hipLaunchKernelGGL(k_v_expand, grid_of(n, G), dim3(256), 0, st, n, ncells, (const int*)S.vcell.p, (const float*)S.bx.p, S.vfull.p);
+        hipLaunchKernelGGL(k_v_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, nreal, (const float*)S.vfull.p, S.vstats.p);
+        LB_TRY(e, hipMemcpyAsync(stats, S.vstats.p, 2 * (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    }
     LB_TRY(e, hipGetLastError());
     LB_TRY(e, hipStreamSynchronize(st));
     return 0;

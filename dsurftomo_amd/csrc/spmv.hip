@@ -446,6 +446,8 @@ void release_spmv(SpmvState* s)
     rel(s->bu); rel(s->bv); rel(s->bh); rel(s->bhbar); rel(s->bx); rel(s->blocalV); rel(s->bscale); rel(s->bparam); rel(s->bred); rel(s->btmp); rel(s->bterm); rel(s->bpmax);
     rel(s->bcoord); rel(s->bpsf);
     rel(s->row_coef); rel(s->col_coef); rel(s->bflag);
+    rel(s->vxyz); rel(s->vstats); rel(s->vseeds); rel(s->vcell_mm); rel(s->vcell); rel(s->vlist); rel(s->vcptr); rel(s->vrowof); rel(s->vkeys); rel(s->vkeys_out);
+    rel(s->vpos); rel(s->vfull); rel(s->vut); rel(s->vsort);
     if (s->hbatch) (void)hipHostFree(s->hbatch);
     if (s->hu) (void)hipHostFree(s->hu);
     if (s->hv) (void)hipHostFree(s->hv);

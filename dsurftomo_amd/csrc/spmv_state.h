@@ -59,6 +59,14 @@ struct SpmvState {
     // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
     DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
     DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results (bpsf: dsa_lsmr_tradeoff's measures too)
+    // dsa_lsmr_voronoi: per call, the tessellations (vxyz: points of the unknowns; vseeds: seed unknowns, member-major; vcell_mm: cell of every
+    // unknown, member-major; vcell: the same as [group][unknown][64]), the data rows' CSR positions sorted by cell per member (vlist, with
+    // vcptr: ncells + 1 pointers per member; vrowof: row of every position), the operands of the projected products (vfull: v expanded to the
+    // unknowns, [group][unknown][64]; vut: u member-major), the sort's buffers and the ensemble statistics
+    DevBuf<double> vxyz, vstats;
+    DevBuf<int> vseeds, vcell_mm, vcell, vlist, vcptr, vrowof, vkeys, vkeys_out, vpos;
+    DevBuf<float> vfull, vut;
+    DevBuf<unsigned char> vsort;
     float* hbatch = nullptr;         // pinned: per-realisation coefficients and flags (bparam) on their way to the device, norms on their way back
     size_t hbatch_cap = 0;
 };

@@ -73,6 +73,7 @@ def load_library():
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+    L.dsa_lsmr_voronoi.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
     L.dsa_dropin_error.restype = C.c_char_p
@@ -333,6 +334,32 @@ class Engine:
                                               est.ctypes.data_as(_vp)))
         names = ("normA", "condA", "normr", "normAr", "normx")
         return dict(x=x, measures=meas, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+
+    def lsmr_voronoi(self, b, ndata, ncells, xyz, seeds, damp, want_z=True, want_cell=True, want_stats=True, atol=1e-6, btol=1e-6, conlim=100.0,
+                     itnlim=400, local_size=10):
+        """K LSMR solves on random Voronoi projections of the data rows (rows below ndata) of the matrix of the last spmv_load: member k
+        on M_k, those rows with every column j relabelled cell_k(j), the nearest (fp64 squared distance between rows of xyz (n, 3),
+        lowest index on ties) of its seeds[k] (seeds: (K, ncells) 0-based unknowns); each bit-identical to lsmr(b[:ndata], damp) after
+        spmv_load(ndata, ncells, M_k).  Returns dict(z=(K, ncells) or None, cell=(K, n) int32 or None, stats=(2, n) float64 {mean, sample
+        standard deviation over the members of z_k[cell_k(j)]} or None, istop=(K,), itn=(K,), normA=(K,), condA, normr, normAr, normx)"""
+        b = np.ascontiguousarray(b, np.float32)
+        m, n = self._mn
+        pts = np.ascontiguousarray(xyz, np.float64)
+        sd = np.ascontiguousarray(seeds, np.int32)
+        assert b.size >= min(int(ndata), m) and pts.shape == (n, 3) and sd.ndim == 2
+        K = sd.shape[0]
+        assert ncells < 1 or sd.shape[1] == ncells
+        z = np.zeros((K, max(int(ncells), 0)), np.float32) if want_z else None
+        cell = np.zeros((K, n), np.int32) if want_cell else None
+        stats = np.zeros((2, n)) if want_stats else None
+        istop = np.zeros(K, np.int32)
+        itn = np.zeros(K, np.int32)
+        est = np.zeros((K, 5), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_vp)
+        self._check(self._L.dsa_lsmr_voronoi(self._h, K, int(ndata), int(ncells), ptr(b), ptr(pts), ptr(sd), damp, atol, btol, conlim, int(itnlim),
+                                             int(local_size), ptr(z), ptr(cell), ptr(stats), ptr(istop), ptr(itn), ptr(est)))
+        names = ("normA", "condA", "normr", "normAr", "normx")
+        return dict(z=z, cell=cell, stats=stats, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
 
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)

@@ -3,6 +3,7 @@
     python -m dsurftomo_amd.invert <directory with DSurfTomo.in, the data file and MOD> [--maxiter N] [--out DIR]
                                    [--bootstrap R [--bootstrap-seed S]] [--resolution] [--checkerboard NX,NY,NZ ...]
                                    [--tradeoff-weights W1,W2,... [--tradeoff-damps D1,...] [--tradeoff-iter N]]
+                                   [--voronoi K,NCELLS [--voronoi-seed S] [--voronoi-zscale F] [--voronoi-damp D] [--voronoi-update]]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -44,6 +45,19 @@ regularisation rows: free of the weight), ||x||, itn, istop, min and max of the 
 of the curve (lcurve_corner: the largest Menger curvature of (log ||C x||, log ||r||) over increasing weight).  The inversion itself
 runs on with the input file's parameters: no other output changes.  Device-resident rows only (not with --host-rows); combines with
 --bootstrap / --resolution / --checkerboard.
+
+--voronoi K,NCELLS adds a Poisson-Voronoi subspace ensemble (Fang et al. 2020) of the last iteration's step, after its dsa_lsmr and on the
+same resident system: each of K members draws NCELLS of the unknowns as seeds (voronoi_seeds: default_rng(--voronoi-seed + iteration - 1),
+without replacement within a member), every unknown joins its nearest seed (voronoi_xyz: a local Cartesian frame in km, the depth axis
+stretched by --voronoi-zscale; voronoi_cells restates the assignment), and dsa_lsmr_voronoi solves the data rows projected onto the cells
+with the damping --voronoi-damp (default the input file's damp) and no smoothing rows -- the projection is the regularisation.  A member's
+update is piecewise constant over its cells; <input>Voronoi.dat lists, in the layout of <input>Std.dat with two value columns, the ensemble
+mean and the sample standard deviation of the update per vertex.  The members go in calls of voronoi_chunk() (multiples of 64); one call
+returns the statistics from the device, several calls bring the members' updates to the host, which combines them in member order
+(voronoi_stats, the same fp64 loop).  --voronoi-update runs the ensemble in every outer iteration and applies float32(mean) as that
+iteration's update in place of dsa_lsmr's (which still runs and is logged).  The K solves run side by side: below about K = 8 to 16 they
+take as long as, or longer than, K separate solves.  Device-resident rows only (not with --host-rows); combines with
+--bootstrap / --resolution / --checkerboard / --tradeoff-*.
 """
 import argparse
 import ctypes as C
@@ -189,6 +203,124 @@ def tradeoff_chunk(m, n, nar, local_size, budget=32 << 30, cap=4096):
     return k
 
 
+def voronoi_xyz(c, zscale=1.0):
+    """(maxvp, 3) float64 points in km of the unknowns (unknown_coords) for the Voronoi assignment: coords_xyz of them"""
+    return coords_xyz(unknown_coords(c), zscale)
+
+
+def coords_xyz(coords, zscale=1.0):
+    """(n, 3) float64 points in km from (n, 3) latitude, longitude (degrees) and depth (km), a local Cartesian frame about the mean
+    latitude and longitude: x = 6371 (lat - mean lat) pi/180, y = 6371 cos(mean lat) (lon - mean lon) pi/180, z = zscale depth"""
+    co = np.asarray(coords, np.float64).reshape(-1, 3)
+    d2r = np.pi / 180.0
+    lat0, lon0 = co[:, 0].mean(), co[:, 1].mean()
+    out = np.empty((co.shape[0], 3))
+    out[:, 0] = EARTH_KM * (co[:, 0] - lat0) * d2r
+    out[:, 1] = EARTH_KM * np.cos(lat0 * d2r) * (co[:, 1] - lon0) * d2r
+    out[:, 2] = float(zscale) * co[:, 2]
+    return out
+
+
+def voronoi_seeds(n, ncells, nreal, seed):
+    """(nreal, ncells) int32 seed unknowns (0-based) of nreal tessellations: per member ncells of the n unknowns drawn without
+    replacement, members in order from numpy default_rng(seed)"""
+    if not 1 <= ncells <= n:
+        raise ValueError("ncells must lie in 1..%d (got %d)" % (n, ncells))
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.choice(n, size=ncells, replace=False) for _ in range(nreal)]).astype(np.int32)
+
+
+def voronoi_cells(xyz, seeds, block=4096):
+    """(nreal, n) int32: cell_k(j), the index s of the seed of member k nearest to unknown j -- the numpy restatement of
+    dsa_lsmr_voronoi's assignment: d2 = ((xj-xs)*(xj-xs) + (yj-ys)*(yj-ys)) + (zj-zs)*(zj-zs) in float64 in that association, the
+    lowest s on ties (argmin's first minimum)"""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    seeds = np.asarray(seeds).reshape(len(seeds), -1)
+    out = np.zeros((seeds.shape[0], xyz.shape[0]), np.int32)
+    for k, sd in enumerate(seeds):
+        p = xyz[sd]
+        for j0 in range(0, xyz.shape[0], block):
+            q = xyz[j0:j0 + block]
+            dx = q[:, None, 0] - p[None, :, 0]
+            dy = q[:, None, 1] - p[None, :, 1]
+            dz = q[:, None, 2] - p[None, :, 2]
+            out[k, j0:j0 + block] = np.argmin((dx * dx + dy * dy) + dz * dz, axis=1)
+    return out
+
+
+def voronoi_stats(x):
+    """(2, n) float64 {mean, sample standard deviation} over the members of x (K, n), dsa_lsmr_voronoi's fixed order: every sum float64
+    over k = 0 .. K-1 in order, mean = sum / K, std = sqrt(sum (x - mean)^2 / (K - 1)), 0 for K = 1"""
+    x = np.asarray(x)
+    K, n = x.shape
+    s = np.zeros(n)
+    for k in range(K):
+        s = s + x[k].astype(np.float64)
+    mean = s / float(K)
+    ss = np.zeros(n)
+    for k in range(K):
+        d = x[k].astype(np.float64) - mean
+        ss = ss + d * d
+    return np.stack([mean, np.sqrt(ss / float(K - 1)) if K > 1 else np.zeros(n)])
+
+
+def voronoi_bytes(ndata, n, ncells, nnz, local_size, nreal):
+    """device bytes of a dsa_lsmr_voronoi call for nreal members of ncells cells on ndata data rows of nnz entries over n unknowns: the
+    batch buffers at (ndata, ncells) (batch_bytes, whose temporary bounds the call's nreal ncells + ndata), per member (in groups of 64) the
+    expanded temporary and the two cell maps (3 n), u member-major (ndata), the sorted list (nnz) and its cell pointers (ncells + 1); the
+    row of every position (nnz), one lane group's sort (keys in and out, positions: 3 x 64 nnz, and as much again for the radix sort's
+    own double buffers), the points (fp64, 3 n), the seeds and the statistics (fp64, 2 n: they have no block partials)"""
+    Rp = 64 * ((nreal + 63) // 64)
+    ints = Rp * (3 * n + ndata + nnz + ncells + 1) + nnz + 6 * 64 * nnz + nreal * ncells
+    return batch_bytes(ndata, ncells, local_size, nreal) + 4 * ints + 8 * 5 * n
+
+
+def voronoi_chunk(ndata, n, ncells, nnz, local_size, budget=32 << 30, cap=4096):
+    """members per dsa_lsmr_voronoi call: cap, lowered in multiples of 64 until voronoi_bytes fits `budget` (64 at the least)"""
+    k = cap
+    while k > 64 and voronoi_bytes(ndata, n, ncells, nnz, local_size, k) > budget:
+        k -= 64
+    return k
+
+
+def parse_voronoi(text):
+    """'K,NCELLS' -> (K, NCELLS), two integers >= 1 (ValueError otherwise)"""
+    parts = text.split(",")
+    try:
+        v = tuple(int(p) for p in parts)
+    except ValueError:
+        v = ()
+    if len(parts) != 2 or len(v) != 2 or min(v) < 1:
+        raise ValueError("--voronoi takes K,NCELLS: two integers >= 1 (got %r)" % text)
+    return v
+
+
+def _voronoi_arg(text):
+    try:
+        return parse_voronoi(text)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
+def write_voronoi(path, c, mean, std):
+    """write_model's layout with the per-unknown ensemble mean and standard deviation (maxvp each, the order of the LSMR unknowns) as
+    the fourth and fifth columns"""
+    write_model(path, c, unknowns_grid(c, mean), unknowns_grid(c, std))
+
+
+def read_voronoi(path):
+    """(mean, std) float64 arrays in the order of the LSMR unknowns from a file of write_voronoi ('(5f10.5)' lines)"""
+    rows = []
+    with open(path) as fh:
+        for line in fh:
+            line = line.rstrip("\n")
+            if len(line) != 50:
+                raise ValueError("%s: a line of %d characters, not 50" % (path, len(line)))
+            rows.append((float(line[30:40]), float(line[40:50])))
+    a = np.array(rows, np.float64).reshape(-1, 2)
+    return a[:, 0].copy(), a[:, 1].copy()
+
+
 def parse_tradeoff_list(text):
     """'V1,V2,...' -> [V1, V2, ...]: at least one float, every one finite and >= 0 (ValueError otherwise)"""
     try:
@@ -320,7 +452,7 @@ def write_residuals(path, c, dsyn, obst, datweight):
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
-def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None):
+def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
     both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit).
@@ -328,7 +460,10 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     resolution = dict(psf=bool, chunk=int or None, cells=[(NX, NY, NZ), ...]): after dsa_lsmr, the resolution tests of the same
     system (returned as "res": "psf" from resolution_psf, "checker" from checkerboard_tests).
     tradeoff = dict(weights=[...], damps=[...], chunk=int or None): after dsa_lsmr, the trade-off sweep of the same system (returned as
-    "trade" from lsmr_tradeoff_sweep)."""
+    "trade" from lsmr_tradeoff_sweep).
+    voronoi = dict(nreal, ncells, seed, zscale, damp, chunk, update): after dsa_lsmr, the Poisson-Voronoi ensemble of the same system's
+    data rows (returned as "voronoi" from lsmr_voronoi_ensemble); with update, float32 of its mean is the update applied to vsf and
+    returned as "dv" (dv_min / dv_max are its), dsa_lsmr's own stays in "dv_lsmr"."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -373,6 +508,13 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     trade = None
     if tradeoff:
         trade = lsmr_tradeoff_sweep(lib, eng, c, cbst, m.value, nar2.value, tradeoff["weights"], tradeoff["damps"], tradeoff.get("chunk"))
+    vor = None
+    dv_lsmr = dv
+    if voronoi:
+        vor = lsmr_voronoi_ensemble(lib, eng, c, cbst, nar.value, voronoi["nreal"], voronoi["ncells"], voronoi["seed"], voronoi.get("zscale", 1.0),
+                                    voronoi.get("damp"), voronoi.get("chunk"))
+        if voronoi.get("update"):
+            dv = np.ascontiguousarray(vor["mean"].astype(f))
     r = cbst[:dall]
     mean = f(r.sum(dtype=f) / f(dall))
     std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
@@ -388,6 +530,9 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
         out["res"] = res
     if trade is not None:
         out["trade"] = trade
+    if vor is not None:
+        out["voronoi"] = vor
+        out["dv_lsmr"] = dv_lsmr
     return out
 
 
@@ -475,6 +620,45 @@ def lsmr_tradeoff_sweep(lib, eng, c, cbst, m, nar, weights, damps, chunk=None):
     return dict(weight=w, damp=d, x=x, measures=meas, itn=itn, istop=istop, est=est, chunk=chunk, calls=calls, seconds=time.perf_counter() - t0)
 
 
+def lsmr_voronoi_ensemble(lib, eng, c, cbst, nnz, nreal, ncells, seed, zscale=1.0, damp=None, chunk=None):
+    """The Poisson-Voronoi ensemble of the resident system's data rows (nnz entries, or a bound of them: it sizes the calls): nreal members
+    of ncells cells from voronoi_seeds(maxvp, ncells, nreal, seed) on the points voronoi_xyz(c, zscale), damping damp (default the input
+    file's), in calls of `chunk` members (default voronoi_chunk(...)) with the other arguments of the dsa_lsmr call above.  One call: z and
+    the cells stay on the device and the statistics come from it.  Several calls: every call returns z and its cells, the host expands them
+    to x_k[j] = z_k[cell_k(j)] and voronoi_stats combines all members in order -- the same fp64 loop, so the same bits as one call.
+    Returns dict(mean, std (maxvp,) float64, itn, istop, est=(nreal, 5), seeds, chunk, calls, seconds)."""
+    f = np.float32
+    n, nd = c["nparpi"], c["ndata"]
+    damp = float(c["damp"]) if damp is None else float(damp)
+    xyz = np.ascontiguousarray(voronoi_xyz(c, zscale))
+    seeds = np.ascontiguousarray(voronoi_seeds(n, ncells, nreal, seed))
+    chunk = int(chunk or voronoi_chunk(nd, n, ncells, int(nnz), 10))
+    istop = np.zeros(nreal, np.int32); itn = np.zeros(nreal, np.int32); est = np.zeros((nreal, 5), f)
+    single = nreal <= chunk
+    stats = np.zeros((2, n))
+    x = None if single else np.zeros((nreal, n), f)
+    t0 = time.perf_counter()
+    calls = 0
+    for first in range(0, nreal, chunk):
+        q = slice(first, min(first + chunk, nreal))
+        k = q.stop - q.start
+        sd = np.ascontiguousarray(seeds[q])
+        z = None if single else np.zeros((k, ncells), f)
+        cell = None if single else np.zeros((k, n), np.int32)
+        opt = lambda a: None if a is None else _p(a)
+        rc = lib.dsa_lsmr_voronoi(eng, k, nd, ncells, _p(cbst), _p(xyz), _p(sd), C.c_float(damp), C.c_float(1e-6), C.c_float(1e-6), C.c_float(100.0), 400, 10,
+                                  opt(z), opt(cell), _p(stats) if single else None, _p(istop[q]), _p(itn[q]), _p(est[q]))
+        if rc != 0:
+            raise RuntimeError("dsa_lsmr_voronoi: %s" % lib.dsa_error_string(eng).decode())
+        if not single:
+            x[q] = np.take_along_axis(z, cell, axis=1)
+        calls += 1
+    if not single:
+        stats = voronoi_stats(x)
+    return dict(mean=stats[0].copy(), std=stats[1].copy(), itn=itn, istop=istop, est=est, seeds=seeds, chunk=chunk, calls=calls,
+                seconds=time.perf_counter() - t0)
+
+
 def tradeoff_members(t):
     """the rows of <input>Tradeoff.dat from lsmr_tradeoff_sweep's result: dicts with the keys TRADEOFF_COLUMNS"""
     nrm = np.sqrt(t["measures"])
@@ -542,6 +726,7 @@ def bind(lib):
     lib.dsa_lsmr_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
     lib.dsa_lsmr_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
     lib.dsa_lsmr_tradeoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p] + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5
+    lib.dsa_lsmr_voronoi.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 6
     lib.dsa_error_string.restype = C.c_char_p
     lib.dsa_error_string.argtypes = [C.c_void_p]
     return lib
@@ -586,6 +771,31 @@ def check_tradeoff(weights, damps, iteration, host_rows, maxiter=None, chunk=Non
         raise ValueError("tradeoff_chunk must be a multiple of 64 (got %d)" % chunk)
 
 
+def check_voronoi(voronoi, update=False, host_rows=False, zscale=1.0, damp=None, nunknowns=None, chunk=None):
+    """the Voronoi ensemble's preconditions, checked before anything touches the GPU (voronoi None: no ensemble; nunknowns: the number
+    of unknowns once the input is read)"""
+    if voronoi is None:
+        if update:
+            raise ValueError("--voronoi-update needs --voronoi")
+        return
+    try:
+        ok = len(voronoi) == 2 and all(int(v) == v and v >= 1 for v in voronoi)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("--voronoi takes K,NCELLS: two integers >= 1 (got %r)" % (voronoi,))
+    if host_rows:
+        raise ValueError("--voronoi solves on the device-resident system: it cannot be combined with --host-rows")
+    if not (np.isfinite(zscale) and zscale >= 0):
+        raise ValueError("--voronoi-zscale must be a finite number >= 0 (got %r)" % (zscale,))
+    if damp is not None and not (np.isfinite(damp) and damp >= 0):
+        raise ValueError("--voronoi-damp must be a finite number >= 0 (got %r)" % (damp,))
+    if nunknowns is not None and voronoi[1] > nunknowns:
+        raise ValueError("--voronoi: %d cells are more than the %d unknowns" % (voronoi[1], nunknowns))
+    if chunk is not None and (chunk < 64 or chunk % 64):
+        raise ValueError("voronoi_chunk must be a multiple of 64 (got %d)" % chunk)
+
+
 def _solve_stats(itn, istop):
     stops = {int(k): int(v) for k, v in zip(*np.unique(istop, return_counts=True))}
     return dict(realisations=int(itn.size), itn_min=int(itn.min()), itn_median=float(np.median(itn)), itn_max=int(itn.max()), istop=stops)
@@ -597,8 +807,10 @@ def _solve_text(h):
 
 
 def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1, resolution=False, checkerboard=(),
-        resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None):
+        resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None, voronoi=None, voronoi_seed=1,
+        voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None):
     check_bootstrap(bootstrap, host_rows)
+    check_voronoi(voronoi, voronoi_update, host_rows, voronoi_zscale, voronoi_damp, None, voronoi_chunk)
     check_resolution(resolution, checkerboard, host_rows, resolution_chunk)
     check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
     cells = [tuple(int(v) for v in cell) for cell in checkerboard or ()]
@@ -606,6 +818,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
     c = io.load(directory)
     maxiter = c["maxiter"] if maxiter is None else maxiter
     check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
+    check_voronoi(voronoi, voronoi_update, host_rows, voronoi_zscale, voronoi_damp, c["nparpi"], voronoi_chunk)
     sweep = None
     if tradeoff_weights is not None:
         sweep = dict(weights=list(tradeoff_weights), damps=[float(c["damp"])] if tradeoff_damps is None else list(tradeoff_damps), chunk=tradeoff_chunk)
@@ -625,9 +838,13 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
             st = iteration(lib, c, vsf, obst, log)
         else:
             last = it == maxiter
+            vor = None
+            if voronoi is not None and (last or voronoi_update):
+                vor = dict(nreal=int(voronoi[0]), ncells=int(voronoi[1]), seed=voronoi_seed + it - 1, zscale=voronoi_zscale, damp=voronoi_damp,
+                           chunk=voronoi_chunk, update=voronoi_update)
             st = iteration_device(lib, c, vsf, obst, log, (bootstrap, bootstrap_seed) if bootstrap and last else None,
                                   dict(psf=resolution, chunk=resolution_chunk, cells=cells) if (resolution or cells) and last else None,
-                                  sweep if it == tradeoff_iter else None)
+                                  sweep if it == tradeoff_iter else None, vor)
         log("%2dth iteration..." % it)
         log(" mean,std_devs and rms of residual after weighting: %8.1fms %8.2fms %8.3f" % (st["mean_ms"], st["std_ms"], st["rms"]))
         log(" min and max velocity variation %7.4f%7.4f" % (st["dv_min"], st["dv_max"]))
@@ -638,7 +855,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade")}
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr")}
         if "boot" in st:
             b = st["boot"]
             write_std(name + "Std.dat", c, b["std"])
@@ -679,6 +896,14 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                 (len(sweep["weights"]), len(sweep["damps"]), it, _solve_text(ht), ht["calls"], ht["chunk"], ht["seconds"]))
             for cn in ht["corners"]:
                 log(" tradeoff damp %g: corner %s" % (cn["damp"], "not found" if cn["weight"] is None else "at weight %g" % cn["weight"]))
+        if "voronoi" in st:
+            v = st["voronoi"]
+            write_voronoi(name + "Voronoi.dat", c, v["mean"], v["std"])
+            hv = h["voronoi"] = dict(_solve_stats(v["itn"], v["istop"]), iteration=it, cells=int(voronoi[1]), seed=voronoi_seed + it - 1, applied=bool(voronoi_update),
+                                     std_max=float(v["std"].max()), std_mean=float(v["std"].mean()), seconds=v["seconds"], chunk=v["chunk"], calls=v["calls"])
+            log(" voronoi: %d cells, %s, std of the update max %.5f mean %.5f km/s%s, %d calls of up to %d (%.3f s)" %
+                (hv["cells"], _solve_text(hv), hv["std_max"], hv["std_mean"], ", the mean applied as the update" if voronoi_update else "", hv["calls"],
+                 hv["chunk"], hv["seconds"]))
         history.append(h)
     if vsftrue is not None:
         write_model(os.path.join(out_dir, "Vs_model.real"), c, vsftrue)
@@ -711,9 +936,20 @@ def main(argv=None):
                          "misfit against roughness per (weight, damp), and the curve's corner per damp in the log")
     ap.add_argument("--tradeoff-damps", type=_tradeoff_arg, default=None, metavar="D1,...", help="damps of the trade-off sweep (default: the input file's damp)")
     ap.add_argument("--tradeoff-iter", type=int, default=1, metavar="N", help="the outer iteration whose step is swept, 1..maxiter (default 1)")
+    ap.add_argument("--voronoi", type=_voronoi_arg, default=None, metavar="K,NCELLS",
+                    help="a Poisson-Voronoi ensemble of the last iteration's step: K members, each the data rows projected onto NCELLS random "
+                         "Voronoi cells of the unknowns and solved with damping only: <input>Voronoi.dat, the ensemble mean and standard deviation "
+                         "of the update.  The K solves run side by side and cost about the same for any K up to a few hundred: below about "
+                         "K = 8 to 16 they take as long as, or longer than, K separate solves (DESIGN.md section 14)")
+    ap.add_argument("--voronoi-seed", type=int, default=1, metavar="S", help="seed of the tessellations (default 1; iteration it uses S + it - 1)")
+    ap.add_argument("--voronoi-zscale", type=float, default=1.0, metavar="F", help="stretch of the depth axis in the cells' metric (default 1.0)")
+    ap.add_argument("--voronoi-damp", type=float, default=None, metavar="D", help="damping of the members' solves (default: the input file's damp)")
+    ap.add_argument("--voronoi-update", action="store_true",
+                    help="run the ensemble in every outer iteration and apply its mean as that iteration's update (dsa_lsmr still runs and is logged)")
     args = ap.parse_args(argv)
     try:
         check_bootstrap(args.bootstrap, args.host_rows)
+        check_voronoi(args.voronoi, args.voronoi_update, args.host_rows, args.voronoi_zscale, args.voronoi_damp)
         check_resolution(args.resolution, args.checkerboard, args.host_rows)
         check_tradeoff(args.tradeoff_weights, args.tradeoff_damps, args.tradeoff_iter, args.host_rows, args.maxiter)
     except ValueError as exc:
@@ -721,7 +957,8 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     run(args.directory, args.maxiter, args.out, host_rows=args.host_rows, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
         resolution=args.resolution, checkerboard=args.checkerboard, tradeoff_weights=args.tradeoff_weights, tradeoff_damps=args.tradeoff_damps,
-        tradeoff_iter=args.tradeoff_iter)
+        tradeoff_iter=args.tradeoff_iter, voronoi=args.voronoi, voronoi_seed=args.voronoi_seed, voronoi_zscale=args.voronoi_zscale,
+        voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update)
     return 0
 
 

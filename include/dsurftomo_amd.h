@@ -244,6 +244,28 @@ int dsa_lsmr_tradeoff(dsa_engine* e, int nreal, int ndata, const float* b, float
                       const float* damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x,
                       double* measures, int* istop, int* itn, float* est);
 
+/* Poisson-Voronoi subspace ensemble: nreal LSMR solves on random Voronoi projections of the data rows of the (m x n) matrix
+ * of the last dsa_spmv_load / dsa_iteration_system_device.  Rows below ndata are the data rows; the rows from ndata up (the
+ * smoothing rows) take no part.  Tessellation: xyz holds 3*n doubles, one Cartesian point per unknown (the host chooses the
+ * metric); seeds holds nreal*ncells 0-based unknown indices, member-major, distinct within a member; cell_k(j) is the index
+ * s in [0, ncells) that minimises d2 = ((xj-xs)*(xj-xs) + (yj-ys)*(yj-ys)) + (zj-zs)*(zj-zs), evaluated in fp64 in exactly
+ * that association without contraction, ties to the lowest s (only exactly rounded basic operations: a numpy restatement
+ * gives the same integers).  Member k's system M_k lists the data rows row by row (rows ascending, each row's entries in the
+ * resident storage order) with every column index j replaced by cell_k(j), duplicates not merged: ncells unknowns,
+ * right-hand side b[0..ndata), damping damp.  z[k*ncells ..], istop[k], itn[k], est[5k..] are bit-identical to dsa_lsmr after
+ * dsa_spmv_load(ndata, ncells, M_k), with localVecs = min(localSize, ndata, ncells); a cell no data entry touches gets z = 0.
+ * z (nreal*ncells) and cell (nreal*n ints: cell_k(j) at cell[k*n + j]) may be NULL.  stats (2*n doubles, may be NULL):
+ * stats[j] = the ensemble mean and stats[n + j] = the sample standard deviation of x_k[j] = z_k[cell_k(j)] over the members;
+ * all sums fp64 over k = 0 .. nreal-1 in order, mean = sum / nreal, std = sqrt(sum (x - mean)^2 / (nreal - 1)), 0 for
+ * nreal = 1 (repeated calls give the same bits).  With z and cell NULL nothing of size nreal*n or nreal*ncells leaves the
+ * device.  The resident matrix, dsa_lsmr, dsa_lsmr_batch, dsa_lsmr_resolution and dsa_lsmr_tradeoff are left as they were.
+ * Errors: DSA_ERR_ARGUMENT (nreal < 1, ndata outside [1, m], ncells outside [1, n] or above 2^24, a null b / xyz / seeds /
+ * istop / itn / est, a seed outside [0, n), a non-finite damp or coordinate, data rows of more than 2^25 - 1 entries),
+ * DSA_ERR_STATE (no matrix), DSA_ERR_DEVICE.  After a failure the engine is as it was. */
+int dsa_lsmr_voronoi(dsa_engine* e, int nreal, int ndata, int ncells, const float* b, const double* xyz, const int* seeds,
+                     float damp, float atol, float btol, float conlim, int itnlim, int localSize, float* z, int* cell,
+                     double* stats, int* istop, int* itn, float* est);
+
 /* One outer iteration's host glue (reference main.f90:361-466 and :520-535; plain host code, no device):
  * iteration_system: residual cbst = obst - dsyn, percentile weights (getpercentile.f90), rows scaled by their weights,
  *   DWS norm[maxvp] with dws = {max, mean}, regularisation rows appended.  In/out rw, col (capacity entries) and iw

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """dsa_lsmr_batch against R sequential dsa_lsmr calls (default placement: products on the device, ordered sums on the host).
 
-    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution[,tradeoff]]
+    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution[,tradeoff][,voronoi]] [--cells 300,1000]
 
 Per system and R: bootstrap row scales (dsurftomo_amd.invert.bootstrap_row_scales), one warm-up of each path, then the batch
 once and R sequential solves of the explicitly scaled systems (the scaled matrices are loaded outside the timed region; each
 solve is timed alone).  Prints one line per (system, R) and checks realisation 0 of the batch against its sequential solve bit
 for bit.  Resolution leg (resolution_leg): every unknown's PSF by dsa_lsmr_resolution against sequential dsa_lsmr spike solves.
 Trade-off leg (tradeoff_leg, --legs tradeoff): K = each --R (weight, damp) members by dsa_lsmr_tradeoff against sequential rebuilds of
-the system with each member's weight + dsa_lsmr, a sample of --seq-max members timed and scaled to K.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
+the system with each member's weight + dsa_lsmr, a sample of --seq-max members timed and scaled to K.
+Voronoi leg (voronoi_leg, --legs voronoi): K = each --R members of each --cells cells by dsa_lsmr_voronoi against, per member, the numpy
+relabelling of the data rows + dsa_spmv_load + dsa_lsmr, a sample of at most 16 members timed and scaled to K.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
 The systems are the product's own (dsa_calsurfg + dsa_iteration_system, or tests/synth_matrix.py): nothing here loads oracle/."""
 import argparse
 import os
@@ -169,6 +171,57 @@ def tradeoff_leg(name, e, S, ndata, weight0, damp, itnlim, Ks, seq_max):
                inv.same(b0, first) == []), flush=True)
 
 
+def voronoi_leg(name, e, S, ndata, damp, itnlim, coords, Ks, cells, seq_max):
+    """K members of ncells cells by one dsa_lsmr_voronoi call (the statistics back, z and the cells left on the device) against what K
+    separate solves do: per member the data rows relabelled in numpy (the cells from the call itself, outside the timing), loaded
+    (dsa_spmv_load: both orderings built) and solved by dsa_lsmr.  At most min(seq_max, 16) members spread over the ensemble are run
+    that way, each step timed alone, and scaled to K; the first of them is checked bit for bit.  Every call ends in a device
+    synchronisation, so the host clock around it is the call's time."""
+    nar = S["nar"]
+    rows, cols = S["iw"][1:nar + 1], S["iw"][nar + 1:]
+    keep = np.flatnonzero(rows <= ndata)
+    keep = keep[np.argsort(rows[keep], kind="stable")]
+    r_d, c_d, v_d = rows[keep], cols[keep] - 1, np.ascontiguousarray(S["rw"][keep])
+    b_d = np.ascontiguousarray(S["b"][:ndata])
+    xyz = invert.coords_xyz(coords, 1.0)
+    n = S["n"]
+    for ncells in cells:
+        for K in Ks:
+            seeds = invert.voronoi_seeds(n, ncells, K, seed=1)
+            load(e, S)
+            e.lsmr_voronoi(S["b"], ndata, ncells, xyz, seeds, damp, want_z=False, want_cell=False, itnlim=2)      # warm-up: copies, allocations, code
+            runs = []
+            for _ in range(3):                                                # (the spread of the ensemble's own time: three runs, the median reported)
+                t0 = time.perf_counter()
+                V = e.lsmr_voronoi(S["b"], ndata, ncells, xyz, seeds, damp, want_z=False, want_cell=False, itnlim=itnlim)
+                runs.append(time.perf_counter() - t0)
+            t_ens = sorted(runs)[1]
+            ks = np.unique(np.linspace(0, K - 1, min(seq_max, 16, K)).astype(int))
+            W = e.lsmr_voronoi(S["b"], ndata, ncells, xyz, seeds[ks], damp, itnlim=itnlim)                         # the sample's cells and solutions
+            t_rel, t_load, t_seq, itn_seq, same = 0.0, 0.0, 0, 0, None
+            for q, k in enumerate(ks):
+                t0 = time.perf_counter()
+                cc = (W["cell"][q][c_d] + 1).astype(np.int32)
+                t_rel += time.perf_counter() - t0
+                t0 = time.perf_counter()
+                e.spmv_load(ndata, ncells, v_d, r_d, cc)
+                t_load += time.perf_counter() - t0
+                t0 = time.perf_counter()
+                got = e.lsmr(b_d, damp, itnlim=itnlim)
+                t_seq += time.perf_counter() - t0
+                itn_seq += got["itn"]
+                if same is None:
+                    same = inv.same(dict(x=W["z"][q], istop=int(W["istop"][q]), itn=int(W["itn"][q]), **{f: W[f][q] for f in EST}), got) == []
+            scale = K / len(ks)
+            t_all = (t_rel + t_load + t_seq) * scale
+            print("%s voronoi K %4d cells %5d: ensemble %9.1f ms (three runs %.1f .. %.1f; itn max %d, total %d) | %d of %d sequential: relabel %9.1f ms, load %9.1f ms, dsa_lsmr "
+                  "%9.1f ms (%.2f + %.2f + %.2f ms per member, %.1f itn) | speed-up %.1fx over the solves, %.1fx with relabel + load | member %d "
+                  "identical: %s" %
+                  (name, K, ncells, 1e3 * t_ens, 1e3 * min(runs), 1e3 * max(runs), int(V["itn"].max()), int(V["itn"].sum()), len(ks), K, 1e3 * t_rel * scale, 1e3 * t_load * scale,
+                   1e3 * t_seq * scale, 1e3 * t_rel / len(ks), 1e3 * t_load / len(ks), 1e3 * t_seq / len(ks), itn_seq / len(ks), t_seq * scale / t_ens,
+                   t_all / t_ens, int(ks[0]), same), flush=True)
+
+
 def load(e, S, rw=None):
     nar = S["nar"]
     e.spmv_load(S["m"], S["n"], S["rw"] if rw is None else rw, S["iw"][1:nar + 1], S["iw"][nar + 1:])
@@ -179,7 +232,8 @@ def main():
     ap.add_argument("--systems", default="taipei,multiblock")
     ap.add_argument("--R", default="1,8,64,256")
     ap.add_argument("--seq-max", type=int, default=64, help="sequential solves actually run per R (the rest extrapolated from their mean)")
-    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch), resolution (dsa_lsmr_resolution) and / or tradeoff (dsa_lsmr_tradeoff)")
+    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch), resolution (dsa_lsmr_resolution) tradeoff (dsa_lsmr_tradeoff) and / or voronoi (dsa_lsmr_voronoi)")
+    ap.add_argument("--cells", default="300,1000", help="cells per member of the voronoi leg")
     args = ap.parse_args()
     Rs = [int(v) for v in args.R.split(",")]
     legs = args.legs.split(",")
@@ -195,6 +249,8 @@ def main():
                 resolution_leg(name, e, S, ndata, damp, itnlim, coords, args.seq_max)
             if "tradeoff" in legs:
                 tradeoff_leg(name, e, S, ndata, WEIGHT0[name], damp, itnlim, Rs, args.seq_max)
+            if "voronoi" in legs:
+                voronoi_leg(name, e, S, ndata, damp, itnlim, coords, Rs, [int(v) for v in args.cells.split(",")], args.seq_max)
             if "bootstrap" not in legs:
                 continue
             scales = invert.bootstrap_row_scales(ndata, S["m"], max(Rs), seed=1)
