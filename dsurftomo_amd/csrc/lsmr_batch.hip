@@ -32,6 +32,11 @@
 // the system dsa_iteration_system builds with weight_k.  damp_k goes to member k's LsmrScalars.  k_b_meas_rows / k_b_meas_x /
 // k_b_meas_sum reduce each solution to its misfit, roughness and size on the device.
 //
+// dsa_lsmr_crossval runs the trade-off's loop on ncombo (weight, damp) pairs x (nfolds hold-outs + the full data): the
+// row scales of the data rows are 0 where the member holds the row out and 1 elsewhere (k_b_crossval_init, from the fold of every datum),
+// u = fl(b * scale).  k_b_cv_rows is k_b_meas_rows with a per-lane hold predicate: kept and held-out misfit apart, and the held-out and
+// full-fit residual of every datum stored by the lane that formed it.
+//
 // dsa_lsmr_voronoi runs it on K random Voronoi projections of the data rows: member k's unknowns are the ncells cells of
 // its tessellation, its matrix M_k the resident data rows with every column j relabelled cell_k(j).  The batch vectors have the lengths
 // (ndata, ncells), and Batch::product is swapped for the projected one: mode 1 expands v to the unknowns through the cell map and runs
@@ -599,6 +604,89 @@ __global__ __launch_bounds__(64) void k_b_meas_sum(int nbr, int nbx, int nreal, 
     meas[3 * (size_t)r] = s0; meas[3 * (size_t)r + 1] = s1; meas[3 * (size_t)r + 2] = s2;
 }
 
+// ---- dsa_lsmr_crossval: the fold masks, and the measures and held-out residuals of every solution ----
+
+// Member r = q * stride + f (stride = nfolds + 1) holds out fold f of the data rows with the weight of combo q; f = nfolds holds out nothing.
+// (g, i, l) of the batch layout: on the data rows scale = 0 where fold[i] == f, else 1, and u = fl(b[i] * scale); from ndata up
+// scale = w[q], u = b[i]; both 0 past nreal
+__global__ void k_b_crossval_init(int m, int ndata, int nreal, int stride, const float* __restrict__ b, const float* __restrict__ w,
+                                  const int* __restrict__ fold, float* __restrict__ scale, float* __restrict__ u)
+{
+    LB_GROUP_LOOP(m) {
+        const int r = g * 64 + (int)(t & 63);
+        const size_t i = t >> 6;
+        float s = 0.0f, uu = 0.0f;
+        if (r < nreal) {
+            const int q = r / stride, f = r - q * stride;
+            if (i < (size_t)ndata) { s = fold[i] == f ? 0.0f : 1.0f; uu = b[i] * s; }
+            else { s = w[q]; uu = b[i]; }
+        }
+        scale[gbase + t] = s;
+        u[gbase + t] = uu;
+    }
+}
+
+// k_b_meas_rows with a hold predicate per lane: the squared residual d^2 of a data row goes to the member's held-out sum where the member
+// holds the row out (fold[row] == f), else to its kept sum -- the full member (f = nfolds) keeps every row, so its kept sum and its roughness
+// are k_b_meas_rows' additions in k_b_meas_rows' order.  The lane that holds row i out stores d to resid[(2 q) ndata + i], the full
+// member's lane to resid[(2 q + 1) ndata + i]: every (combo, datum) is written once in each half.  part: three sums per (g, block, lane).
+__global__ __launch_bounds__(256) void k_b_cv_rows(int m, int n, int ndata, int nb, int nreal, int stride, const long long* __restrict__ ptr,
+                                                   const float* __restrict__ val, const int* __restrict__ idx, const float* __restrict__ b,
+                                                   const int* __restrict__ fold, const float* __restrict__ x, double* __restrict__ part,
+                                                   double* __restrict__ resid)
+{
+    __shared__ double red[3][4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
+    const int r = g * 64 + lane, q = r / stride, f = r - q * stride;
+    const bool in = r < nreal, full = f == stride - 1;
+    const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
+    const int r0 = blk * kMeasR + w * (kMeasR / 4), r1 = min(r0 + kMeasR / 4, m);
+    double s0 = 0.0, sh = 0.0, s1 = 0.0;
+    for (int row = r0; row < r1; ++row) {
+        double acc = 0.0;
+        long long k = ptr[row];
+        const long long k1 = ptr[row + 1];
+        constexpr int U = 4;
+        for (; k + U <= k1; k += U) {
+            double a[U], xi[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) { a[u] = (double)val[k + u]; xi[u] = (double)p[(size_t)idx[k + u] * 64]; }
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc = acc + a[u] * xi[u];
+        }
+        for (; k < k1; ++k) acc = acc + (double)val[k] * (double)p[(size_t)idx[k] * 64];
+        if (row < ndata) {
+            const double d = (double)b[row] - acc;
+            const bool held = fold[row] == f;
+            if (held) sh = sh + d * d;
+            else s0 = s0 + d * d;
+            if (resid && in && (held || full)) resid[(2 * (size_t)q + (full ? 1 : 0)) * (size_t)ndata + (size_t)row] = d;
+        }
+        else s1 = s1 + acc * acc;
+    }
+    red[0][w][lane] = s0; red[1][w][lane] = sh; red[2][w][lane] = s1;
+    __syncthreads();
+    if (w == 0) {
+        double* __restrict__ o = part + (((size_t)g * nb + blk) * 64 + lane) * 3;
+        for (int c = 0; c < 3; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
+    }
+}
+
+// meas[4 r .. 4 r + 3] = {kept misfit, held-out misfit, roughness, sum x^2}; one thread per member
+__global__ __launch_bounds__(64) void k_b_cv_sum(int nbr, int nbx, int nreal, const double* __restrict__ rows, const double* __restrict__ xs,
+                                                 double* __restrict__ meas)
+{
+    const int lane = threadIdx.x, g = blockIdx.x, r = g * 64 + lane;
+    if (r >= nreal) return;
+    double s0 = 0.0, sh = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int b = 0; b < nbr; ++b) {
+        const double* __restrict__ q = rows + (((size_t)g * nbr + b) * 64 + lane) * 3;
+        s0 = s0 + q[0]; sh = sh + q[1]; s1 = s1 + q[2];
+    }
+    for (int b = 0; b < nbx; ++b) s2 = s2 + xs[((size_t)g * nbx + b) * 64 + lane];
+    meas[4 * (size_t)r] = s0; meas[4 * (size_t)r + 1] = sh; meas[4 * (size_t)r + 2] = s1; meas[4 * (size_t)r + 3] = s2;
+}
+
 // ---- dsa_lsmr_voronoi: the tessellations, every member's list for the transposed product, the projected products, the ensemble statistics ----
 
 constexpr int kVorTile = 1024;              // seed points staged per pass: 1024 x 3 x 8 B = 24 KB of LDS
@@ -1137,6 +1225,75 @@ int dsa_lsmr_tradeoff(dsa_engine* h_, int nreal, int ndata, const float* b, floa
     hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
     hipLaunchKernelGGL(k_b_meas_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
     LB_TRY(e, hipMemcpyAsync(measures, d_meas, 3 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
+
+int dsa_lsmr_crossval(dsa_engine* h_, int ncombo, int nfolds, int ndata, const float* b, float weight0, const float* weight, const float* damp, const int* fold,
+                      float atol, float btol, float conlim, int itnlim, int localSize, float* x, double* measures, double* resid, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    if (!h_) return DSA_ERR_ARGUMENT;
+    Engine* e = reinterpret_cast<Engine*>(h_);
+    if (ncombo < 1 || nfolds < 1 || !b || !weight || !damp || !fold || !istop || !itn || !est) {
+        e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: ncombo < 1, nfolds < 1 or a null b / weight / damp / fold / istop / itn / est");
+        return DSA_ERR_ARGUMENT;
+    }
+    const long long members = (long long)ncombo * ((long long)nfolds + 1);
+    if (members > 64 * 65535) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: %d combos x (%d folds + 1) are more than the %d members one call takes", ncombo, nfolds, 64 * 65535); return DSA_ERR_ARGUMENT; }
+    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_crossval: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
+    const int m = e->spmv->m, n = e->spmv->n, stride = nfolds + 1, nreal = (int)members;
+    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    size_t nres = 0;
+    if (resid && (__builtin_mul_overflow((size_t)2 * (size_t)ncombo, (size_t)ndata, &nres) || nres > ((size_t)1 << 60) / 8)) {
+        e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: resid of 2 x %d x %d values is more than one call takes", ncombo, ndata);
+        return DSA_ERR_ARGUMENT;
+    }
+    if (!std::isfinite(weight0) || !(weight0 > 0.0f)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: weight0 %g is not a finite number > 0", (double)weight0); return DSA_ERR_ARGUMENT; }
+    for (int q = 0; q < ncombo; ++q)
+        if (!std::isfinite(weight[q]) || weight[q] < 0.0f || !std::isfinite(damp[q]) || damp[q] < 0.0f) {
+            e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: combo %d has weight %g, damp %g (both must be finite and >= 0)", q, (double)weight[q], (double)damp[q]);
+            return DSA_ERR_ARGUMENT;
+        }
+    for (int i = 0; i < ndata; ++i)
+        if (fold[i] < 0 || fold[i] >= nfolds) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: datum %d is in fold %d, outside 0..%d", i, fold[i], nfolds - 1); return DSA_ERR_ARGUMENT; }
+    Batch B;
+    // btmp: the solutions on their way out (member-major), then b, the combos' weights and the fold of every datum (b and fold stay for the measures)
+    const size_t xs = x ? (size_t)nreal * n : 0;
+    if (int rc = batch_begin(e, nreal, localSize, xs + (size_t)m + (size_t)ncombo + (size_t)ndata, B)) return rc;
+    if (int rc = ensure_coef(e, ndata, weight0)) return rc;
+    SpmvState& S = *e->spmv;
+    const int G = B.G, Rp = B.Rp;
+    hipStream_t st = B.st;
+    B.rval = S.row_coef.p; B.cval = S.col_coef.p;
+    float* d_b = S.btmp.p + xs;
+    float* d_w = d_b + m;
+    int* d_fold = reinterpret_cast<int*>(d_w + ncombo);
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    LB_TRY(e, hipMemcpyAsync(d_w, weight, (size_t)ncombo * 4, hipMemcpyHostToDevice, st));
+    LB_TRY(e, hipMemcpyAsync(d_fold, fold, (size_t)ndata * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b_crossval_init, grid_of(m, G), dim3(256), 0, st, m, ndata, nreal, stride, (const float*)d_b, (const float*)d_w, (const int*)d_fold,
+                       S.bscale.p, S.bu.p);
+    std::vector<float> damps((size_t)nreal);
+    for (int r = 0; r < nreal; ++r) damps[r] = damp[r / stride];
+    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
+    if (!measures && !resid) return 0;
+    const int nbr = (m + kMeasR - 1) / kMeasR, nbx = (n + kMeasE - 1) / kMeasE;
+    const size_t nrows = (size_t)G * nbr * 64 * 3, nx = (size_t)G * nbx * 64;
+    if (e->ensure(S.bpsf, nrows + nx + 4 * (size_t)Rp + nres)) return e->status;
+    double* d_rows = S.bpsf.p;
+    double* d_x = d_rows + nrows;
+    double* d_meas = d_x + nx;
+    double* d_resid = resid ? d_meas + 4 * (size_t)Rp : nullptr;
+    hipLaunchKernelGGL(k_b_cv_rows, dim3((unsigned)nbr, (unsigned)G), dim3(256), 0, st, m, n, ndata, nbr, nreal, stride, (const long long*)S.row_csr.ptr.p,
+                       (const float*)S.row_coef.p, (const int*)S.row_csr.idx.p, (const float*)d_b, (const int*)d_fold, (const float*)S.bx.p, d_rows, d_resid);
+    if (measures) {
+        hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
+        hipLaunchKernelGGL(k_b_cv_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
+        LB_TRY(e, hipMemcpyAsync(measures, d_meas, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (resid) LB_TRY(e, hipMemcpyAsync(resid, d_resid, nres * 8, hipMemcpyDeviceToHost, st));
     LB_TRY(e, hipGetLastError());
     LB_TRY(e, hipStreamSynchronize(st));
     return 0;

@@ -73,6 +73,7 @@ def load_library():
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+    L.dsa_lsmr_crossval.argtypes = [_vp, _i32, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.dsa_lsmr_voronoi.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
@@ -334,6 +335,34 @@ class Engine:
                                               est.ctypes.data_as(_vp)))
         names = ("normA", "condA", "normr", "normAr", "normx")
         return dict(x=x, measures=meas, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+
+    def lsmr_crossval(self, b, ndata, weight0, weights, damps, fold, nfolds, want_x=True, want_resid=True, atol=1e-6, btol=1e-6, conlim=100.0,
+                      itnlim=400, local_size=10):
+        """K-fold cross-validation of the combos (weights[q], damps[q]) on the matrix of the last spmv_load (rows from ndata up built with
+        weight0, as for lsmr_tradeoff): K = ncombo * (nfolds + 1) solves, member q * (nfolds + 1) + f without the data rows i with
+        fold[i] == f (f == nfolds: with all of them), each bit-identical to lsmr() on the system with those rows zeroed and the
+        regularisation rows rebuilt with weights[q].  Returns dict(x=(K, n) or None when not want_x, measures=(K, 4) float64 {kept misfit,
+        held-out misfit, unweighted roughness, sum of x^2 (sums of squares)}, resid=(ncombo, 2, ndata) float64 {held-out, full-fit residual
+        of every datum} or None when not want_resid, istop=(K,), itn=(K,), normA=(K,), condA, normr, normAr, normx)"""
+        b = np.ascontiguousarray(b, np.float32)
+        w = np.ascontiguousarray(weights, np.float32).ravel()
+        d = np.ascontiguousarray(damps, np.float32).ravel()
+        fo = np.ascontiguousarray(fold, np.int32).ravel()
+        m, n = self._mn
+        assert b.size == m and w.size == d.size and fo.size >= min(max(int(ndata), 0), m)
+        nc, nd = w.size, max(int(ndata), 0)
+        K = nc * (max(int(nfolds), 0) + 1)
+        x = np.zeros((K, n), np.float32) if want_x else None
+        meas = np.zeros((K, 4))
+        resid = np.zeros((nc, 2, nd)) if want_resid else None
+        istop = np.zeros(K, np.int32)
+        itn = np.zeros(K, np.int32)
+        est = np.zeros((K, 5), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_vp)
+        self._check(self._L.dsa_lsmr_crossval(self._h, nc, int(nfolds), int(ndata), ptr(b), weight0, ptr(w), ptr(d), ptr(fo), atol, btol, conlim,
+                                              int(itnlim), int(local_size), ptr(x), ptr(meas), ptr(resid), ptr(istop), ptr(itn), ptr(est)))
+        names = ("normA", "condA", "normr", "normAr", "normx")
+        return dict(x=x, measures=meas, resid=resid, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
 
     def lsmr_voronoi(self, b, ndata, ncells, xyz, seeds, damp, want_z=True, want_cell=True, want_stats=True, atol=1e-6, btol=1e-6, conlim=100.0,
                      itnlim=400, local_size=10):

@@ -4,6 +4,8 @@
                                    [--bootstrap R [--bootstrap-seed S]] [--resolution] [--checkerboard NX,NY,NZ ...]
                                    [--tradeoff-weights W1,W2,... [--tradeoff-damps D1,...] [--tradeoff-iter N]]
                                    [--voronoi K,NCELLS [--voronoi-seed S] [--voronoi-zscale F] [--voronoi-damp D] [--voronoi-update]]
+                                   [--crossval NFOLDS --crossval-weights W1,W2,... [--crossval-damps D1,...] [--crossval-by datum|path]
+                                    [--crossval-seed S] [--crossval-iter N]]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -58,6 +60,18 @@ returns the statistics from the device, several calls bring the members' updates
 iteration's update in place of dsa_lsmr's (which still runs and is logged).  The K solves run side by side: below about K = 8 to 16 they
 take as long as, or longer than, K separate solves.  Device-resident rows only (not with --host-rows); combines with
 --bootstrap / --resolution / --checkerboard / --tradeoff-*.
+
+--crossval NFOLDS (>= 2) with --crossval-weights adds the K-fold cross-validation of one outer iteration's linearised step (--crossval-iter N,
+default 1), the objective counterpart of the trade-off curve's corner: the data are dealt into NFOLDS folds (crossval_folds: --crossval-by datum
+at random, or path, all data of one station pair in one fold; --crossval-seed), and after that iteration's dsa_lsmr, dsa_lsmr_crossval solves,
+for every (weight, damp) pair of the grid weights x damps (--crossval-damps, default the input file's damp; weight-major), the system without
+each fold in turn and the full system -- NFOLDS + 1 members per pair, all on the resident matrix: a held-out row is a row scaled by 0, which
+gives LSMR what deleting the row gives, bit for bit.  <input>Crossval.dat lists per pair: weight, damp, the held-out rms cv_rms, the standard
+error cv_se of its square, the training rms, the full fit's ||r||, ||C x||, ||x|| and the smallest and largest itn (crossval_members); the log
+and the history name the pair of the smallest cv_rms (best) and the smoothest pair within one standard error of it (one_se, crossval_select);
+<input>CrossvalResiduals.dat lists, for the one_se pair, every datum's held-out and full-fit residual.  The calls hold whole pairs
+(crossval_chunk).  The inversion itself runs on with the input file's parameters: no other output changes.  Device-resident rows only (not with
+--host-rows); combines with the other analysis flags.
 """
 import argparse
 import ctypes as C
@@ -405,6 +419,142 @@ def tradeoff_corners(members):
     return out
 
 
+def datum_table(c):
+    """per datum, in the data order of dsurf (period slot, then source, then receiver: CalSurfG's loops): (slot (ndata,) int32 0-based
+    period slot, src (ndata, 2) and rec (ndata, 2) uint32: the float32 bits of the source's and the receiver's two coordinates)"""
+    slot, src, rec = [], [], []
+    for k in range(c["kmax"]):
+        for s in range(int(c["nsrcsurf1"][k])):
+            nr = int(c["nrc1"][s, k])
+            slot.append(np.full(nr, k, np.int32))
+            one = np.array([c["scxf"][s, k], c["sczf"][s, k]], np.float32).view(np.uint32)
+            src.append(np.broadcast_to(one, (nr, 2)))
+            rec.append(np.stack([np.asarray(c["rcxf"][:nr, s, k], np.float32), np.asarray(c["rczf"][:nr, s, k], np.float32)], axis=1).view(np.uint32))
+    cat = lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape, np.uint32)
+    return (np.concatenate(slot) if slot else np.zeros(0, np.int32)), cat(src, (0, 2)), cat(rec, (0, 2))
+
+
+def crossval_folds(c, nfolds, by="datum", seed=1):
+    """(ndata,) int32 fold of every datum, each in [0, nfolds).  by 'datum': default_rng(seed).permutation(ndata) % nfolds (sizes differ by
+    at most 1).  by 'path': the data of one unordered station pair -- across all periods and wave types -- share a fold: stations are told
+    apart by the float32 bits of their coordinates (datum_table), the distinct pairs (in sorted order) are shuffled by
+    default_rng(seed).permutation and dealt round-robin.  A pair's dispersion curve is strongly correlated along period, so holding out
+    single data of it flatters the fit: 'path' is the honest hold-out for surface-wave data."""
+    nfolds = int(nfolds)
+    if nfolds < 1:
+        raise ValueError("nfolds must be at least 1 (got %d)" % nfolds)
+    nd = int(c["ndata"])
+    rng = np.random.default_rng(seed)
+    if by == "datum":
+        return (rng.permutation(nd) % nfolds).astype(np.int32)
+    if by != "path":
+        raise ValueError("folds are made by 'datum' or by 'path' (got %r)" % (by,))
+    _, src, rec = datum_table(c)
+    a = (src[:, 0].astype(np.uint64) << np.uint64(32)) | src[:, 1].astype(np.uint64)
+    b = (rec[:, 0].astype(np.uint64) << np.uint64(32)) | rec[:, 1].astype(np.uint64)
+    pairs = np.stack([np.minimum(a, b), np.maximum(a, b)], axis=1)
+    uniq, inverse = np.unique(pairs, axis=0, return_inverse=True)
+    of_pair = np.zeros(len(uniq), np.int32)
+    of_pair[rng.permutation(len(uniq))] = np.arange(len(uniq)) % nfolds
+    return of_pair[np.asarray(inverse).ravel()].astype(np.int32)
+
+
+CROSSVAL_COLUMNS = ("weight", "damp", "cv_rms", "cv_se", "train_rms", "misfit", "rough", "xnorm", "itn_min", "itn_max")
+
+
+def crossval_members(result, fold):
+    """one dict per combo (keys CROSSVAL_COLUMNS) from a cross-validation result (weight, damp (ncombo,), nfolds, measures (K, 4), itn) and
+    the fold of every datum.  With held_f / kept_f the held-out / kept sum of squares of the member that holds out fold f and cnt_f the
+    fold's size: cv_rms = sqrt(sum_f held_f / sum_f cnt_f); cv_se = the sample standard deviation (ddof 1) over the non-empty folds of
+    held_f / cnt_f, divided by sqrt(their number) (0 with fewer than two), the standard error of cv_rms^2; train_rms = sqrt(sum_f kept_f /
+    sum_f (ndata - cnt_f)); misfit, rough, xnorm = the full member's ||r||, ||C x||, ||x||; itn_min / itn_max over the combo's members"""
+    fold = np.asarray(fold).ravel()
+    nf = int(result["nfolds"])
+    S = nf + 1
+    cnt = np.bincount(fold, minlength=nf).astype(np.float64)
+    meas = np.asarray(result["measures"], np.float64).reshape(-1, S, 4)
+    itn = np.asarray(result["itn"]).reshape(-1, S)
+    used = cnt > 0
+    out = []
+    for q in range(meas.shape[0]):
+        held, kept = meas[q, :nf, 1], meas[q, :nf, 0]
+        per = held[used] / cnt[used]
+        se = float(per.std(ddof=1) / np.sqrt(per.size)) if per.size > 1 else 0.0
+        ntrain = float((fold.size - cnt).sum())
+        out.append(dict(weight=float(result["weight"][q]), damp=float(result["damp"][q]), cv_rms=float(np.sqrt(held.sum() / cnt.sum())), cv_se=se,
+                        train_rms=float(np.sqrt(kept.sum() / ntrain)) if ntrain > 0 else 0.0, misfit=float(np.sqrt(meas[q, nf, 0])),
+                        rough=float(np.sqrt(meas[q, nf, 2])), xnorm=float(np.sqrt(meas[q, nf, 3])), itn_min=int(itn[q].min()), itn_max=int(itn[q].max())))
+    return out
+
+
+def crossval_select(members):
+    """dict(best, one_se): indices into members.  best: the smallest cv_rms^2, ties to the larger weight, then the larger damp.  one_se
+    (the one-standard-error rule): among the combos whose cv_rms^2 is at most best's cv_rms^2 + best's cv_se, the largest weight, then the
+    largest damp -- the smoothest model that predicts unseen data as well as the best one, within the noise of the estimate"""
+    if not members:
+        raise ValueError("no members to select from")
+    sq = [t["cv_rms"] ** 2 for t in members]
+    best = min(range(len(members)), key=lambda i: (sq[i], -members[i]["weight"], -members[i]["damp"]))
+    lim = sq[best] + members[best]["cv_se"]
+    one = max((i for i in range(len(members)) if sq[i] <= lim), key=lambda i: (members[i]["weight"], members[i]["damp"]))
+    return dict(best=best, one_se=one)
+
+
+def crossval_bytes(m, n, nar, local_size, ncombo, nfolds, ndata):
+    """device bytes of a dsa_lsmr_crossval call for ncombo combos of nfolds folds on an m x n system of nar entries with ndata data rows:
+    tradeoff_bytes of its ncombo (nfolds + 1) members, the combos' weights and the folds, one more block partial per 64 rows and one more
+    measure per member (fp64, in groups of 64) and the residuals (fp64, 2 ncombo ndata)"""
+    nreal = ncombo * (nfolds + 1)
+    Rp = 64 * ((nreal + 63) // 64)
+    return tradeoff_bytes(m, n, nar, local_size, nreal) + 4 * (ncombo + ndata) + 8 * Rp * (-(-m // 64) + 1) + 16 * ncombo * ndata
+
+
+def crossval_chunk(m, n, nar, local_size, ncombo, nfolds, ndata, budget=32 << 30, cap=4096):
+    """combos per dsa_lsmr_crossval call: a call holds whole combos (its members are a multiple of nfolds + 1, so every datum's held-out
+    and full member sit in one call) -- as many as give at most `cap` members, lowered one combo at a time until crossval_bytes fits
+    `budget` (1 at the least)"""
+    k = max(1, min(int(ncombo), cap // (nfolds + 1)))
+    while k > 1 and crossval_bytes(m, n, nar, local_size, k, nfolds, ndata) > budget:
+        k -= 1
+    return k
+
+
+def write_crossval(path, members):
+    """one line per combo: weight damp cv_rms cv_se train_rms ||r|| ||C x|| ||x|| itn_min itn_max (the last five of the full member / over
+    the combo's members); the float32 values with 9 significant digits, the float64 ones with 17: read_crossval gives the same values back"""
+    with open(path, "w") as fh:
+        for t in members:
+            fh.write("%.9g %.9g %.17g %.17g %.17g %.17g %.17g %.17g %d %d\n" % tuple(t[k] for k in CROSSVAL_COLUMNS))
+
+
+def read_crossval(path):
+    """the members of a file of write_crossval: a list of dicts with the keys CROSSVAL_COLUMNS"""
+    out = []
+    with open(path) as fh:
+        for line in fh:
+            v = line.split()
+            if len(v) != len(CROSSVAL_COLUMNS):
+                raise ValueError("%s: a line of %d columns, not %d" % (path, len(v), len(CROSSVAL_COLUMNS)))
+            kind = lambda k: int if k in ("itn_min", "itn_max") else (lambda t: float(np.float32(t))) if k in ("weight", "damp") else float
+            out.append({k: kind(k)(t) for k, t in zip(CROSSVAL_COLUMNS, v)})
+    return out
+
+
+def write_crossval_residuals(path, slot, dist, fold, datweight, held, full):
+    """one line per datum: index (1-based), period slot (1-based), dist (km), fold, datweight, the residual in the member that held the
+    datum out and in the full fit -- weighted seconds, as the system holds them (float64, 17 significant digits)"""
+    with open(path, "w") as fh:
+        for i in range(len(fold)):
+            fh.write("%d %d %.9g %d %.9g %.17g %.17g\n" % (i + 1, slot[i] + 1, dist[i], fold[i], datweight[i], held[i], full[i]))
+
+
+def crossval_by_slot(slot, held, nslots):
+    """per period slot the root mean square of the held-out residuals of its data (None for a slot without data)"""
+    slot = np.asarray(slot)
+    sq = np.asarray(held, np.float64) ** 2
+    return [float(np.sqrt(sq[slot == k].mean())) if (slot == k).any() else None for k in range(nslots)]
+
+
 def psf_columns(psf):
     """(R_jj, horizontal PSF length, vertical PSF length, unknowns without data) from dsa_lsmr_resolution's measures (maxvp, 4):
     lengths sqrt(sum x^2 dh^2 / sum x^2), sqrt(sum x^2 dz^2 / sum x^2) in km; an unknown with sum x^2 = 0 gets zeros"""
@@ -452,7 +602,7 @@ def write_residuals(path, c, dsyn, obst, datweight):
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
-def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None):
+def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None, crossval=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
     both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit).
@@ -463,7 +613,9 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     "trade" from lsmr_tradeoff_sweep).
     voronoi = dict(nreal, ncells, seed, zscale, damp, chunk, update): after dsa_lsmr, the Poisson-Voronoi ensemble of the same system's
     data rows (returned as "voronoi" from lsmr_voronoi_ensemble); with update, float32 of its mean is the update applied to vsf and
-    returned as "dv" (dv_min / dv_max are its), dsa_lsmr's own stays in "dv_lsmr"."""
+    returned as "dv" (dv_min / dv_max are its), dsa_lsmr's own stays in "dv_lsmr".
+    crossval = dict(weights=[...], damps=[...], fold=(ndata,) int32, nfolds, chunk=int or None, want_x=bool): after dsa_lsmr, the K-fold
+    cross-validation of the same system (returned as "crossval" from lsmr_crossval_sweep)."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -508,6 +660,10 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     trade = None
     if tradeoff:
         trade = lsmr_tradeoff_sweep(lib, eng, c, cbst, m.value, nar2.value, tradeoff["weights"], tradeoff["damps"], tradeoff.get("chunk"))
+    cv = None
+    if crossval:
+        cv = lsmr_crossval_sweep(lib, eng, c, cbst, m.value, nar2.value, crossval["weights"], crossval["damps"], crossval["fold"], crossval["nfolds"],
+                                 crossval.get("chunk"), crossval.get("want_x", False))
     vor = None
     dv_lsmr = dv
     if voronoi:
@@ -530,6 +686,8 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
         out["res"] = res
     if trade is not None:
         out["trade"] = trade
+    if cv is not None:
+        out["crossval"] = cv
     if vor is not None:
         out["voronoi"] = vor
         out["dv_lsmr"] = dv_lsmr
@@ -618,6 +776,38 @@ def lsmr_tradeoff_sweep(lib, eng, c, cbst, m, nar, weights, damps, chunk=None):
             raise RuntimeError("dsa_lsmr_tradeoff: %s" % lib.dsa_error_string(eng).decode())
         calls += 1
     return dict(weight=w, damp=d, x=x, measures=meas, itn=itn, istop=istop, est=est, chunk=chunk, calls=calls, seconds=time.perf_counter() - t0)
+
+
+def lsmr_crossval_sweep(lib, eng, c, cbst, m, nar, weights, damps, fold, nfolds, chunk=None, want_x=False):
+    """K-fold cross-validation on the resident m-row system of nar entries (regularisation rows built with the input file's weight0): the
+    combos of tradeoff_grid(weights, damps), each with the nfolds hold-outs of `fold` and its full member, in calls of `chunk` combos
+    (default crossval_chunk(...)) with the arguments of the dsa_lsmr call above.  A call holds whole combos and returns every datum's
+    held-out and full-fit residual, so several calls give what one gives.  Returns dict(weight, damp (ncombo,), nfolds, measures=(K, 4)
+    {kept, held-out sum r^2, sum (C x)^2, sum x^2}, resid=(ncombo, 2, ndata), x=(K, maxvp) raw updates or None, itn, istop, est=(K, 5),
+    chunk, calls, seconds), K = ncombo (nfolds + 1)."""
+    f = np.float32
+    n, nd = c["nparpi"], c["ndata"]
+    w, d = tradeoff_grid(weights, damps)
+    nc, S = w.size, int(nfolds) + 1
+    K = nc * S
+    fold = np.ascontiguousarray(fold, np.int32)
+    chunk = int(chunk or crossval_chunk(m, n, nar, 10, nc, int(nfolds), nd))
+    x = np.zeros((K, n), f) if want_x else None
+    meas = np.zeros((K, 4)); resid = np.zeros((nc, 2, nd))
+    istop = np.zeros(K, np.int32); itn = np.zeros(K, np.int32); est = np.zeros((K, 5), f)
+    t0 = time.perf_counter()
+    calls = 0
+    for first in range(0, nc, chunk):
+        q = slice(first, min(first + chunk, nc))
+        k = slice(q.start * S, q.stop * S)
+        wk, dk = np.ascontiguousarray(w[q]), np.ascontiguousarray(d[q])
+        rc = lib.dsa_lsmr_crossval(eng, wk.size, int(nfolds), nd, _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), _p(fold), C.c_float(1e-6), C.c_float(1e-6),
+                                   C.c_float(100.0), 400, 10, _p(x[k]) if want_x else None, _p(meas[k]), _p(resid[q]), _p(istop[k]), _p(itn[k]), _p(est[k]))
+        if rc != 0:
+            raise RuntimeError("dsa_lsmr_crossval: %s" % lib.dsa_error_string(eng).decode())
+        calls += 1
+    return dict(weight=w, damp=d, nfolds=int(nfolds), measures=meas, resid=resid, x=x, itn=itn, istop=istop, est=est, chunk=chunk, calls=calls,
+                seconds=time.perf_counter() - t0)
 
 
 def lsmr_voronoi_ensemble(lib, eng, c, cbst, nnz, nreal, ncells, seed, zscale=1.0, damp=None, chunk=None):
@@ -726,6 +916,7 @@ def bind(lib):
     lib.dsa_lsmr_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
     lib.dsa_lsmr_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
     lib.dsa_lsmr_tradeoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p] + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5
+    lib.dsa_lsmr_crossval.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_float] + [C.c_void_p] * 3 + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 6
     lib.dsa_lsmr_voronoi.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 6
     lib.dsa_error_string.restype = C.c_char_p
     lib.dsa_error_string.argtypes = [C.c_void_p]
@@ -771,6 +962,32 @@ def check_tradeoff(weights, damps, iteration, host_rows, maxiter=None, chunk=Non
         raise ValueError("tradeoff_chunk must be a multiple of 64 (got %d)" % chunk)
 
 
+def check_crossval(nfolds, weights=None, damps=None, by="datum", iteration=1, host_rows=False, maxiter=None, chunk=None):
+    """the cross-validation's preconditions, checked before anything touches the GPU (nfolds None: no cross-validation)"""
+    if nfolds is None:
+        if weights is not None or damps is not None:
+            raise ValueError("--crossval-weights / --crossval-damps need --crossval")
+        return
+    if int(nfolds) != nfolds or nfolds < 2:
+        raise ValueError("--crossval needs at least 2 folds (got %r)" % (nfolds,))
+    if weights is None:
+        raise ValueError("--crossval needs --crossval-weights")
+    for name, vals in (("--crossval-weights", weights), ("--crossval-damps", damps)):
+        if vals is None:
+            continue
+        vals = list(vals)
+        if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
+            raise ValueError("%s takes at least one value, every one finite and >= 0 (got %r)" % (name, vals))
+    if by not in ("datum", "path"):
+        raise ValueError("--crossval-by is datum or path (got %r)" % (by,))
+    if host_rows:
+        raise ValueError("--crossval solves on the device-resident system: it cannot be combined with --host-rows")
+    if iteration < 1 or (maxiter is not None and iteration > maxiter):
+        raise ValueError("--crossval-iter must be an outer iteration 1..maxiter (got %d%s)" % (iteration, "" if maxiter is None else ", maxiter %d" % maxiter))
+    if chunk is not None and chunk < 1:
+        raise ValueError("crossval_chunk must be at least 1 combo (got %d)" % chunk)
+
+
 def check_voronoi(voronoi, update=False, host_rows=False, zscale=1.0, damp=None, nunknowns=None, chunk=None):
     """the Voronoi ensemble's preconditions, checked before anything touches the GPU (voronoi None: no ensemble; nunknowns: the number
     of unknowns once the input is read)"""
@@ -808,8 +1025,10 @@ def _solve_text(h):
 
 def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1, resolution=False, checkerboard=(),
         resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None, voronoi=None, voronoi_seed=1,
-        voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None):
+        voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None, crossval=None, crossval_weights=None, crossval_damps=None,
+        crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None):
     check_bootstrap(bootstrap, host_rows)
+    check_crossval(crossval, crossval_weights, crossval_damps, crossval_by, crossval_iter, host_rows, maxiter, crossval_chunk)
     check_voronoi(voronoi, voronoi_update, host_rows, voronoi_zscale, voronoi_damp, None, voronoi_chunk)
     check_resolution(resolution, checkerboard, host_rows, resolution_chunk)
     check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
@@ -819,6 +1038,11 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
     maxiter = c["maxiter"] if maxiter is None else maxiter
     check_tradeoff(tradeoff_weights, tradeoff_damps, tradeoff_iter, host_rows, maxiter, tradeoff_chunk)
     check_voronoi(voronoi, voronoi_update, host_rows, voronoi_zscale, voronoi_damp, c["nparpi"], voronoi_chunk)
+    check_crossval(crossval, crossval_weights, crossval_damps, crossval_by, crossval_iter, host_rows, maxiter, crossval_chunk)
+    cvrun = None
+    if crossval is not None:
+        cvrun = dict(weights=list(crossval_weights), damps=[float(c["damp"])] if crossval_damps is None else list(crossval_damps), nfolds=int(crossval),
+                     fold=crossval_folds(c, int(crossval), crossval_by, crossval_seed), chunk=crossval_chunk)
     sweep = None
     if tradeoff_weights is not None:
         sweep = dict(weights=list(tradeoff_weights), damps=[float(c["damp"])] if tradeoff_damps is None else list(tradeoff_damps), chunk=tradeoff_chunk)
@@ -844,7 +1068,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                            chunk=voronoi_chunk, update=voronoi_update)
             st = iteration_device(lib, c, vsf, obst, log, (bootstrap, bootstrap_seed) if bootstrap and last else None,
                                   dict(psf=resolution, chunk=resolution_chunk, cells=cells) if (resolution or cells) and last else None,
-                                  sweep if it == tradeoff_iter else None, vor)
+                                  sweep if it == tradeoff_iter else None, vor, cvrun if it == crossval_iter else None)
         log("%2dth iteration..." % it)
         log(" mean,std_devs and rms of residual after weighting: %8.1fms %8.2fms %8.3f" % (st["mean_ms"], st["std_ms"], st["rms"]))
         log(" min and max velocity variation %7.4f%7.4f" % (st["dv_min"], st["dv_max"]))
@@ -855,7 +1079,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr")}
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr", "crossval")}
         if "boot" in st:
             b = st["boot"]
             write_std(name + "Std.dat", c, b["std"])
@@ -896,6 +1120,24 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                 (len(sweep["weights"]), len(sweep["damps"]), it, _solve_text(ht), ht["calls"], ht["chunk"], ht["seconds"]))
             for cn in ht["corners"]:
                 log(" tradeoff damp %g: corner %s" % (cn["damp"], "not found" if cn["weight"] is None else "at weight %g" % cn["weight"]))
+        if "crossval" in st:
+            v = st["crossval"]
+            fold = cvrun["fold"]
+            members = crossval_members(v, fold)
+            sel = crossval_select(members)
+            write_crossval(name + "Crossval.dat", members)
+            slot = datum_table(c)[0]
+            one = sel["one_se"]
+            write_crossval_residuals(name + "CrossvalResiduals.dat", slot, c["dist"], fold, st["datweight"], v["resid"][one, 0], v["resid"][one, 1])
+            hx = h["crossval"] = dict(_solve_stats(v["itn"], v["istop"]), iteration=it, nfolds=cvrun["nfolds"], by=crossval_by, seed=crossval_seed,
+                                      weights=cvrun["weights"], damps=cvrun["damps"], chunk=v["chunk"], calls=v["calls"], seconds=v["seconds"], members=members,
+                                      best=sel["best"], one_se=sel["one_se"], cv_rms_by_slot=crossval_by_slot(slot, v["resid"][one, 0], c["kmax"]))
+            log(" crossval: %d folds by %s, %d weights x %d damps at iteration %d: %s, %d calls of up to %d combos (%.3f s)" %
+                (hx["nfolds"], crossval_by, len(cvrun["weights"]), len(cvrun["damps"]), it, _solve_text(hx), hx["calls"], hx["chunk"], hx["seconds"]))
+            for tag, i in (("best", sel["best"]), ("one-SE", sel["one_se"])):
+                t = members[i]
+                log(" crossval %s: weight %g damp %g, held-out rms %.6g (se of its square %.3g), training rms %.6g" %
+                    (tag, t["weight"], t["damp"], t["cv_rms"], t["cv_se"], t["train_rms"]))
         if "voronoi" in st:
             v = st["voronoi"]
             write_voronoi(name + "Voronoi.dat", c, v["mean"], v["std"])
@@ -946,9 +1188,22 @@ def main(argv=None):
     ap.add_argument("--voronoi-damp", type=float, default=None, metavar="D", help="damping of the members' solves (default: the input file's damp)")
     ap.add_argument("--voronoi-update", action="store_true",
                     help="run the ensemble in every outer iteration and apply its mean as that iteration's update (dsa_lsmr still runs and is logged)")
+    ap.add_argument("--crossval", type=int, default=None, metavar="NFOLDS",
+                    help="K-fold cross-validation (NFOLDS >= 2) of one iteration's step over --crossval-weights x --crossval-damps: every pair is "
+                         "solved once per held-out fold and once on all data, side by side on the resident system: <input>Crossval.dat (held-out and "
+                         "training rms per pair), <input>CrossvalResiduals.dat (per datum, for the one-standard-error pair) and both selections in the log")
+    ap.add_argument("--crossval-weights", type=_tradeoff_arg, default=None, metavar="W1,W2,...", help="smoothing weights of the cross-validation")
+    ap.add_argument("--crossval-damps", type=_tradeoff_arg, default=None, metavar="D1,...", help="damps of the cross-validation (default: the input file's damp)")
+    ap.add_argument("--crossval-by", choices=("datum", "path"), default="datum",
+                    help="how the folds are made: datum deals single data at random; path keeps all data of one station pair, across periods and wave "
+                         "types, in one fold.  A pair's dispersion curve is strongly correlated along period, so path is the honest hold-out for "
+                         "surface-wave data (default datum)")
+    ap.add_argument("--crossval-seed", type=int, default=1, metavar="S", help="seed of the folds (default 1)")
+    ap.add_argument("--crossval-iter", type=int, default=1, metavar="N", help="the outer iteration whose step is cross-validated, 1..maxiter (default 1)")
     args = ap.parse_args(argv)
     try:
         check_bootstrap(args.bootstrap, args.host_rows)
+        check_crossval(args.crossval, args.crossval_weights, args.crossval_damps, args.crossval_by, args.crossval_iter, args.host_rows, args.maxiter)
         check_voronoi(args.voronoi, args.voronoi_update, args.host_rows, args.voronoi_zscale, args.voronoi_damp)
         check_resolution(args.resolution, args.checkerboard, args.host_rows)
         check_tradeoff(args.tradeoff_weights, args.tradeoff_damps, args.tradeoff_iter, args.host_rows, args.maxiter)
@@ -958,7 +1213,8 @@ def main(argv=None):
     run(args.directory, args.maxiter, args.out, host_rows=args.host_rows, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
         resolution=args.resolution, checkerboard=args.checkerboard, tradeoff_weights=args.tradeoff_weights, tradeoff_damps=args.tradeoff_damps,
         tradeoff_iter=args.tradeoff_iter, voronoi=args.voronoi, voronoi_seed=args.voronoi_seed, voronoi_zscale=args.voronoi_zscale,
-        voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update)
+        voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update, crossval=args.crossval, crossval_weights=args.crossval_weights,
+        crossval_damps=args.crossval_damps, crossval_by=args.crossval_by, crossval_seed=args.crossval_seed, crossval_iter=args.crossval_iter)
     return 0
 
 

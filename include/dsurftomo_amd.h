@@ -244,6 +244,29 @@ int dsa_lsmr_tradeoff(dsa_engine* e, int nreal, int ndata, const float* b, float
                       const float* damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x,
                       double* measures, int* istop, int* itn, float* est);
 
+/* K-fold cross-validation of (weight, damp) pairs: ncombo*(nfolds+1) LSMR solves on the (m x n) matrix of the last dsa_spmv_load /
+ * dsa_iteration_system_device, rows and weight0 as for dsa_lsmr_tradeoff.  fold[i] in [0, nfolds) is the fold of datum i < ndata.
+ * With S = nfolds + 1 and nreal = ncombo*S, member k = q*S + f (f < nfolds) holds out fold f with (weight[q], damp[q]); member
+ * q*S + nfolds holds out nothing (the full member of combo q).  Member k is bit-identical (x, istop, itn, est as in dsa_lsmr_batch)
+ * to dsa_lsmr(b_k, damp[q], ...) on the explicitly written system: every data row i with entries fl(a*s) and right-hand side
+ * fl(b_i*s), s = 0 where fold[i] = f and 1 otherwise; every regularisation entry fl(c*weight[q]) with its b_i unscaled.  A zeroed
+ * row gives LSMR what deleting it gives, so the member is the cross-validation solve itself.  A member whose masked right-hand
+ * side is all zero returns x = 0, itn 0, istop 0; a fold id no datum has makes its member equal to the full one; nfolds = 1 is
+ * valid.  x (nreal*n) may be NULL: then nothing of size n*nreal leaves the device.  measures (4*nreal, may be NULL):
+ * measures[4k..4k+3] = {sum over the kept data rows of (b_i - (A x_k)_i)^2, the same over the held-out rows, sum over i >= ndata
+ * of ((C x_k)_i)^2, sum of x_k[j]^2}, A and b unscaled, C the integer coefficients; fp64 in the fixed order of
+ * dsa_lsmr_tradeoff's measures, so a full member's kept sum, roughness and size have the bits of that call's measures for the same
+ * (weight, damp), and its held-out sum is +0.  resid (2*ncombo*ndata, may be NULL): resid[(2q)*ndata + i] = b_i - (A x_h)_i with
+ * h = q*S + fold[i], the residual of datum i in the member that held it out; resid[(2q+1)*ndata + i] the same in the full member
+ * (the values the measures square).  The resident matrix and the five other solvers are left as they were.  Errors:
+ * DSA_ERR_ARGUMENT (ncombo or nfolds < 1, more than 64*65535 members, ndata outside [1, m], a null b / weight / damp / fold /
+ * istop / itn / est, a resid whose 2*ncombo*ndata overflows, weight0 not finite or not > 0, a negative or non-finite weight[q] or
+ * damp[q], a fold id outside [0, nfolds), a regularisation entry that is not fl(c*weight0)), DSA_ERR_STATE (no matrix),
+ * DSA_ERR_DEVICE. */
+int dsa_lsmr_crossval(dsa_engine* e, int ncombo, int nfolds, int ndata, const float* b, float weight0, const float* weight,
+                      const float* damp, const int* fold, float atol, float btol, float conlim, int itnlim, int localSize,
+                      float* x, double* measures, double* resid, int* istop, int* itn, float* est);
+
 /* Poisson-Voronoi subspace ensemble: nreal LSMR solves on random Voronoi projections of the data rows of the (m x n) matrix
  * of the last dsa_spmv_load / dsa_iteration_system_device.  Rows below ndata are the data rows; the rows from ndata up (the
  * smoothing rows) take no part.  Tessellation: xyz holds 3*n doubles, one Cartesian point per unknown (the host chooses the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """dsa_lsmr_batch against R sequential dsa_lsmr calls (default placement: products on the device, ordered sums on the host).
 
-    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution[,tradeoff][,voronoi]] [--cells 300,1000]
+    python tools/lsmr_batch_rate.py [--systems taipei,multiblock[,headline]] [--R 1,8,64,256] [--legs bootstrap,resolution[,tradeoff][,voronoi][,crossval]] [--cells 300,1000]
+                                    [--cv 13x5,39x5]
 
 Per system and R: bootstrap row scales (dsurftomo_amd.invert.bootstrap_row_scales), one warm-up of each path, then the batch
 once and R sequential solves of the explicitly scaled systems (the scaled matrices are loaded outside the timed region; each
@@ -10,7 +11,9 @@ for bit.  Resolution leg (resolution_leg): every unknown's PSF by dsa_lsmr_resol
 Trade-off leg (tradeoff_leg, --legs tradeoff): K = each --R (weight, damp) members by dsa_lsmr_tradeoff against sequential rebuilds of
 the system with each member's weight + dsa_lsmr, a sample of --seq-max members timed and scaled to K.
 Voronoi leg (voronoi_leg, --legs voronoi): K = each --R members of each --cells cells by dsa_lsmr_voronoi against, per member, the numpy
-relabelling of the data rows + dsa_spmv_load + dsa_lsmr, a sample of at most 16 members timed and scaled to K.  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
+relabelling of the data rows + dsa_spmv_load + dsa_lsmr, a sample of at most 16 members timed and scaled to K.
+Cross-validation leg (crossval_leg, --legs crossval): each --cv NCOMBOxNFOLDS by one dsa_lsmr_crossval call against, per member, the masked and
+re-weighted system rebuilt in numpy + dsa_spmv_load + dsa_lsmr, a sample of at most 16 members timed and scaled to K = NCOMBO (NFOLDS + 1).  headline: the 1025^2 boundary of tests/tools/headline_boundary.py with 8 receivers per source (minutes of set-up).
 The systems are the product's own (dsa_calsurfg + dsa_iteration_system, or tests/synth_matrix.py): nothing here loads oracle/."""
 import argparse
 import os
@@ -222,6 +225,60 @@ def voronoi_leg(name, e, S, ndata, damp, itnlim, coords, Ks, cells, seq_max):
                    t_all / t_ens, int(ks[0]), same), flush=True)
 
 
+def crossval_leg(name, e, S, ndata, weight0, damp, itnlim, shapes, seq_max):
+    """ncombo combos x (nfolds hold-outs + the full data) by one dsa_lsmr_crossval call (the measures and residuals back, x left on the
+    device) against what a rerun per member does after its forward call: the system rebuilt with the combo's weight and the fold's data
+    rows zeroed (values and right-hand side), loaded (both orderings built) and solved by dsa_lsmr with the combo's damp.  At most
+    min(seq_max, 16) members spread over the grid are run that way, each step timed alone, and scaled to K; the first is checked bit for
+    bit.  Weights: weight0 / 16 .. 16 weight0 (geometric); damps: damp x {0.5, 1, 2} where ncombo is divisible by 3, else damp alone;
+    folds by datum, seed 1."""
+    rows = S["iw"][1:S["nar"] + 1] - 1
+    reg = rows >= ndata
+    coef = np.rint(S["rw"][reg] / np.float32(weight0)).astype(np.float32)
+    assert np.array_equal(coef * np.float32(weight0), S["rw"][reg])
+    for ncombo, nfolds in shapes:
+        damps = [0.5 * damp, damp, 2.0 * damp] if ncombo % 3 == 0 else [damp]
+        w, d = invert.tradeoff_grid(np.geomspace(weight0 / 16.0, weight0 * 16.0, ncombo // len(damps)), damps)
+        fold = invert.crossval_folds(dict(ndata=ndata), nfolds, "datum", 1)
+        S1, K = nfolds + 1, ncombo * (nfolds + 1)
+        load(e, S)
+        e.lsmr_crossval(S["b"], ndata, weight0, w, d, fold, nfolds, want_x=False, itnlim=2)      # warm-up: copies, allocations, code
+        runs = []
+        for _ in range(3):                                                # (three runs, the median reported)
+            t0 = time.perf_counter()
+            T = e.lsmr_crossval(S["b"], ndata, weight0, w, d, fold, nfolds, want_x=False, itnlim=itnlim)
+            runs.append(time.perf_counter() - t0)
+        t_cv = sorted(runs)[1]
+        ks = np.unique(np.linspace(0, K - 1, min(seq_max, 16, K)).astype(int))
+        W = e.lsmr_crossval(S["b"], ndata, weight0, w, d, fold, nfolds, itnlim=itnlim)
+        e.lsmr(S["b"], damp, itnlim=2)
+        t_load, t_seq, itn_seq, same = 0.0, 0.0, 0, None
+        for k in ks:
+            q, f = divmod(int(k), S1)
+            t0 = time.perf_counter()
+            s = np.ones(S["m"], np.float32)
+            s[:ndata][fold == f] = 0.0
+            rw = S["rw"].copy()
+            rw[reg] = coef * w[q]
+            rw *= s[rows]
+            bk = S["b"] * s
+            load(e, S, rw)
+            t_load += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            got = e.lsmr(bk, float(d[q]), itnlim=itnlim)
+            t_seq += time.perf_counter() - t0
+            itn_seq += got["itn"]
+            if same is None:
+                same = inv.same(dict(x=W["x"][k], istop=int(W["istop"][k]), itn=int(W["itn"][k]), **{g: W[g][k] for g in EST}), got) == []
+        scale = K / len(ks)
+        print("%s crossval %d combos x %d folds (K %4d): %9.1f ms (three runs %.1f .. %.1f; itn max %d, total %d) | %d of %d sequential: rebuild + load "
+              "%9.1f ms, dsa_lsmr %9.1f ms (%.2f + %.2f ms per member, %.1f itn) | speed-up %.1fx over the solves, %.1fx with the rebuilds | member %d "
+              "identical: %s" %
+              (name, ncombo, nfolds, K, 1e3 * t_cv, 1e3 * min(runs), 1e3 * max(runs), int(T["itn"].max()), int(T["itn"].sum()), len(ks), K,
+               1e3 * t_load * scale, 1e3 * t_seq * scale, 1e3 * t_load / len(ks), 1e3 * t_seq / len(ks), itn_seq / len(ks), t_seq * scale / t_cv,
+               (t_seq + t_load) * scale / t_cv, int(ks[0]), same), flush=True)
+
+
 def load(e, S, rw=None):
     nar = S["nar"]
     e.spmv_load(S["m"], S["n"], S["rw"] if rw is None else rw, S["iw"][1:nar + 1], S["iw"][nar + 1:])
@@ -232,7 +289,8 @@ def main():
     ap.add_argument("--systems", default="taipei,multiblock")
     ap.add_argument("--R", default="1,8,64,256")
     ap.add_argument("--seq-max", type=int, default=64, help="sequential solves actually run per R (the rest extrapolated from their mean)")
-    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch), resolution (dsa_lsmr_resolution) tradeoff (dsa_lsmr_tradeoff) and / or voronoi (dsa_lsmr_voronoi)")
+    ap.add_argument("--legs", default="bootstrap,resolution", help="bootstrap (dsa_lsmr_batch), resolution (dsa_lsmr_resolution) tradeoff (dsa_lsmr_tradeoff), voronoi (dsa_lsmr_voronoi) and / or crossval (dsa_lsmr_crossval)")
+    ap.add_argument("--cv", default="13x5,39x5", help="NCOMBOxNFOLDS shapes of the crossval leg")
     ap.add_argument("--cells", default="300,1000", help="cells per member of the voronoi leg")
     args = ap.parse_args()
     Rs = [int(v) for v in args.R.split(",")]
@@ -251,6 +309,8 @@ def main():
                 tradeoff_leg(name, e, S, ndata, WEIGHT0[name], damp, itnlim, Rs, args.seq_max)
             if "voronoi" in legs:
                 voronoi_leg(name, e, S, ndata, damp, itnlim, coords, Rs, [int(v) for v in args.cells.split(",")], args.seq_max)
+            if "crossval" in legs:
+                crossval_leg(name, e, S, ndata, WEIGHT0[name], damp, itnlim, [tuple(int(v) for v in t.split("x")) for t in args.cv.split(",")], args.seq_max)
             if "bootstrap" not in legs:
                 continue
             scales = invert.bootstrap_row_scales(ndata, S["m"], max(Rs), seed=1)
