@@ -63,6 +63,18 @@ __device__ __forceinline__ unsigned far_sides(float lo, float hi, float margin)
     return hi < lo ? 2u : 1u;
 }
 
+// a | b | c in one instruction (the compiler pairs the sign tests' ORs two by two)
+__device__ __forceinline__ unsigned or3(unsigned a, unsigned b, unsigned c)
+{
+    unsigned r;
+    asm("v_or3_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// The change hash of a round (cycle detection: a sum over the round's changes, compared with the last four rounds').  One word per change, a function
+// of (key, value, acceptance time): key C1 ^ c C2 ^ (c ^ k) C3.  On the regular path of pass B the acceptance time IS the value, so the last term
+// vanishes there, and key = key0 + m: one multiply per changed member, key0 C1 once per trip.
+constexpr unsigned kHashKey = 2654435761u, kHashVal = 40503u, kHashTau = 2246822519u;
+
 // OR over the lanes of a node (CH consecutive lanes): quad permutes
 template <int CH>
 __device__ __forceinline__ unsigned node_or(unsigned v)
@@ -96,7 +108,8 @@ __device__ __forceinline__ unsigned node_or(unsigned v)
 // its x+ and z+ neighbours (the members of a node side by side in one 16-byte vector), and only the tied (node, member) pairs are evaluated once
 // more, by solve_node_t<true>, for the tie's influence on the node; influences above the unit's threshold go into the unit's tie record
 // (count, largest influence).  That sweep reads the whole field once more (72 MB per bundle: +4.5 % of the step), so it is the FALLBACK:
-// the round loop marks CANDIDATES -- solve_regular says for six instructions whether a member's walk stopped at a tie; a final tie between
+// the round loop marks CANDIDATES -- behind a trip's member loop, a member whose value equals a near neighbour's bit for bit (every walk that stops
+// at a tie ends so; the census' state stays out of the member bodies' registers); a final tie between
 // two nodes is seen by the last evaluation of the one evaluated later, so the candidates of the iteration contain every tie of the converged
 // field -- into a list per bundle (FimBundle::cand: a wave collects them in LDS and appends once per half-round), and behind the loop only
 // the listed (node, member) pairs are looked at: still tied in the converged field?  then the influence.  A list that overflows (a medium
@@ -369,7 +382,7 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
         *(BGF32*)(Bb + (unsigned)id * GB + mb) = newv;
         if (mo == 0) { *(BGF32*)(Pb + ((unsigned)id << 2)) = newv; kmin_lane = fminf(kmin_lane, k); }
         ++nchanged;
-        hv_lane += ((unsigned)key * 2654435761u) ^ (bf2u(c) * 40503u) ^ (bf2u(k) * 2246822519u);
+        hv_lane += ((unsigned)key * kHashKey) ^ (bf2u(c) * kHashVal) ^ ((bf2u(c) ^ bf2u(k)) * kHashTau);
         {   // (a change far behind the front: see pass B)
             const float pt = mo == 0 ? newv : pv(id);
             if (!__builtin_signbit(pt) && pt < stale) smin_lane = fminf(smin_lane, pt);
@@ -424,6 +437,8 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
     int qn = 0;
     int cn = 0;                                         // (TIE) tie candidates of the half-round, kept from the queue's top end downwards
     int* const cand_g = (TIE && bd->cand && bd->cand_list) ? bd->cand + (size_t)my_slot * bd->cand_stride : nullptr;
+    // (the same for every lane, and said so: left to the compiler the test is a lane mask, and the counters of the list live in vector registers)
+    const bool listing = TIE && __builtin_amdgcn_readfirstlane(cand_g != nullptr ? 1 : 0) != 0;
     // a candidate per lane with `on` (wave-uniform control flow): into the LDS list while it has room beside the slow queue, else the count alone
     // grows -- the flush then reports more candidates than the list holds and the census sweeps the field
     bool clost = false;                                 // (a candidate found no room beside the slow queue: the bundle's list counts as overflowed)
@@ -709,53 +724,58 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
                 }
                 const NodeGeom geom = { p.ri, risti[ix], p.dnx, p.dnz };
                 __builtin_amdgcn_s_setprio(0);
-                BV outv = vown;
-                unsigned wm = 0u;                                    // dependents some member wants activated: bit q near, bit 4 + q outer
+                BV outv;                                             // (every element is set by its member: the new value or the one read)
+                // dependents some member wants activated, near and outer neighbour q: kept as lane masks over the member loop (a comparison and two
+                // scalar operations per condition) and turned into the bits of `wm` once per trip
+                bool actn[4] = { false, false, false, false }, acto[4] = { false, false, false, false };
                 bool any_changed = false;
-                const int key0 = id * G + sub * MPL;
+                unsigned hkey0 = (unsigned)(id * G + sub * MPL) * kHashKey;
+                asm("" : "+v"(hkey0));                               // (once per trip: left alone the multiply sinks into every member's branch)
                 // Round 4: the member bodies below are the REGULAR case only -- no exceptional node (a pinned one, or one whose acceptance time
                 // differs from its value: ~0.2 % of the evaluations) in the member's neighbourhood, and a result that is causal (tau = T).  A member
                 // that is not regular is left for the slow pass behind the store (bit m of `slow`), which evaluates it from memory with the
                 // exception table at hand.  What this buys is registers: the table look-ups and the table insert, inlined into every member
                 // body, kept ~30 more VGPRs alive (profiles/r04_bundle_vgprs.txt), and 168 is the line for a third workgroup per CU.
-                unsigned slow = 0u, tiem = 0u;                               // (tiem, TIE: members whose walk stopped at an exact tie)
+                bool slowm[MPL], donem[MPL];                                 // (lane masks: member m goes to the slow pass / was evaluated here)
                 const bool interior = in[0] && in[1] && in[2] && in[3];      // (a node on the grid's edge: the general walk's business)
 #pragma unroll
                 for (int m = 0; m < MPL; ++m) {
                     float tn[4], t2[4];
-                    bool flagged = !interior;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        tn[q] = vn[q][m]; t2[q] = vo[q][m];
-                        flagged = flagged | __builtin_signbit(tn[q]) | __builtin_signbit(t2[q]);
-                    }
+                    for (int q = 0; q < 4; ++q) { tn[q] = vn[q][m]; t2[q] = vo[q][m]; }
                     const float raw = vown[m];
                     const bool valid = act && ((vmask >> m) & 1u);
-                    flagged = flagged | __builtin_signbit(raw);
+                    // (a sign bit among the nine: the OR of their bit patterns, three at a time; the NaN of an outer value not fetched has none)
+                    unsigned sg = or3(bf2u(tn[0]), bf2u(tn[1]), bf2u(tn[2]));
+                    sg = or3(sg, bf2u(tn[3]), bf2u(t2[0]));
+                    sg = or3(sg, bf2u(t2[1]), bf2u(t2[2]));
+                    sg = or3(sg, bf2u(t2[3]), bf2u(raw));
                     float c = 0.0f, k = kInf;
-                    bool changed = false;
-                    if (valid && !flagged) {
+                    bool changed = false, done = false;
+                    if (valid && interior && (int)sg >= 0) {
                         // (round 4) the walk written out for the regular neighbourhood: straight-line code, about half the instructions of
                         // solve_node_t's loop; where it does not apply (a third neighbour taken in, the opposite neighbour second: ~1 % of
                         // the evaluations) it says so and the member goes to the slow pass like an exceptional one
-                        bool ok, tie = false;
-                        c = solve_regular(tn, t2, sl[m], geom, &k, &ok, TIE ? &tie : nullptr);
-                        if (!ok || bf2u(c) != bf2u(k)) flagged = true;               // (a non-causal result: the table's business)
-                        else { ++evals; changed = bf2u(c) != bf2u(raw); if (TIE && tie) tiem |= 1u << m; }
+                        bool ok;
+                        c = solve_regular(tn, t2, sl[m], geom, &k, &ok);
+                        if (ok && bf2u(c) == bf2u(k)) { ++evals; changed = bf2u(c) != bf2u(raw); done = true; }      // (else a non-causal result: the table's business)
                     }
-                    if (valid && flagged) slow |= 1u << m;
+                    outv[m] = changed ? c : raw;
+                    slowm[m] = valid && !done;
+                    donem[m] = done;
                     if (changed) {
-                        outv[m] = c;
                         ++nchanged;
                         any_changed = true;
-                        hv_lane += ((unsigned)(key0 + m) * 2654435761u) ^ (bf2u(c) * 40503u) ^ (bf2u(k) * 2246822519u);
-                        if (sub == 0 && m == 0) kmin_lane = fminf(kmin_lane, k);                 // the pilot's changes hold the window back
-                        const float t_lo = fminf(raw, c), k_lo = t_lo;
+                        hv_lane += (hkey0 + (unsigned)m * kHashKey) ^ (bf2u(c) * kHashVal);            // (k == c bit for bit: see kHashKey)
+                        if (sub == 0 && m == 0) kmin_lane = min_canon(kmin_lane, k);             // the pilot's changes hold the window back
+                    }
+                    {
+                        const float t_lo = min_canon(raw, c), k_lo = t_lo;                       // (a changed member: both regular, positive or +inf)
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const float ky = tn[q];
-                            if (k_lo <= ky) wm |= 1u << q;                               // (interior: the four near neighbours exist)
-                            if (in_outer[q] && ky < kInf && ky > t_lo && !(k_lo >= t2[q])) wm |= 16u << q;      // (t2 NaN: not fetched, see above)
+                            actn[q] = actn[q] | (changed & (k_lo <= ky));                        // (interior: the four near neighbours exist)
+                            acto[q] = acto[q] | (changed & (ky < kInf) & (ky > t_lo) & !(k_lo >= t2[q]));      // (t2 NaN: not fetched, see above)
                         }
                     }
                 }
@@ -766,11 +786,14 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
                 }
                 // the members left out above go to the wave's queue (node, member of the bundle); a full queue (it holds the pinned neighbourhood of
                 // the first rounds several times over) puts the node back on its tile's mask instead: it is listed again next round
-                if (__any(slow != 0u)) {
+                bool any_slow = false;
+#pragma unroll
+                for (int m = 0; m < MPL; ++m) any_slow = any_slow | slowm[m];
+                if (__any(any_slow)) {
                     bool again = false;
 #pragma unroll
                     for (int m = 0; m < MPL; ++m) {
-                        const bool push = ((slow >> m) & 1u) != 0u;
+                        const bool push = slowm[m];
                         const unsigned long long bal = __ballot(push);
                         const int pos = qn + __popcll(bal & ((1ull << lane) - 1ull));
                         if (push && pos < kSlowQ - 1 - cn) wq[pos] = (id << 4) | (sub * MPL + m);      // (the queue's top end holds the half-round's tie candidates)
@@ -779,12 +802,27 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
                     }
                     if (again) { atomicOr((unsigned long long*)(mask_at(id >> 6) + half), 1ull << (id & 63)); atomicOr(&tb[(id >> 6) >> 5], 1u << ((id >> 6) & 31)); }
                 }
-                if (TIE && cand_g && __any(tiem != 0u)) {
+                // (TIE) the census' candidates of this trip, from what is live behind the member loop: a walk stops at an exact tie only with its value equal,
+                // bit for bit, to a near neighbour's, so a regular member whose value (new or unchanged) equals one of the four is listed.  That is every
+                // evaluation solve_regular's own tie flag named and a few more (equal to a neighbour the walk did not stop at); the census' second look decides.
+                if (listing) {
+                    unsigned tiem = 0u;
 #pragma unroll
-                    for (int m = 0; m < MPL; ++m) cand_push(((tiem >> m) & 1u) != 0u, (id << 4) | (sub * MPL + m));
+                    for (int m = 0; m < MPL; ++m) {
+                        const float v = outv[m];
+                        const bool eq = (v == vn[0][m]) | (v == vn[1][m]) | (v == vn[2][m]) | (v == vn[3][m]);
+                        tiem |= (eq & (v < kInf) & donem[m]) ? 1u << m : 0u;
+                    }
+                    if (__any(tiem != 0u)) {
+#pragma nounroll
+                        for (int m = 0; m < MPL; ++m) cand_push(((tiem >> m) & 1u) != 0u, (id << 4) | (sub * MPL + m));       // (rare: one copy of the push)
+                    }
                 }
                 // dependents: the members' OR, one lane per node issues the activations (fim_kernel.hip: the mask bits are constant shifts
                 // of the node's own bit)
+                unsigned wm = 0u;                                    // bit q near, bit 4 + q outer
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wm |= (actn[q] ? 1u << q : 0u) | ((acto[q] & in_outer[q]) ? 16u << q : 0u);
                 wm = node_or<CH>(wm);
                 // A change far BEHIND the front (the window's lower edge has been kStaleWindows windows beyond this node) is a member that lags
                 // that much, a late refinement on its way downstream -- or a cycle (exact 2-cycles among ulp-tied nodes, fim_kernel.hip), which
@@ -808,7 +846,7 @@ __global__ __launch_bounds__(NT) DSA_BUNDLE_OCC(G, NT, MPL) void k_fim_bundle(co
                 const int e = base + lane < qn ? wq[base + lane] : -1;
                 bool tied = false;
                 if (e >= 0) tied = slow_member(e >> 4, e & 15, half, stale, evals, nchanged, hv_lane, kmin_lane, smin_lane);
-                if (TIE && cand_g) cand_push(tied, (int)((unsigned)e | kCandAlways));      // (the detector's walk found it: not a matter of equal values, the second look decides)
+                if (listing) cand_push(tied, (int)((unsigned)e | kCandAlways));      // (the detector's walk found it: not a matter of equal values, the second look decides)
             }
             qn = 0;
             if (TIE) cand_flush();

@@ -162,6 +162,54 @@ DSA_HD float sqrt_pos(float x)
 #endif
 }
 
+// sqrtf for an argument that is zero, +inf, NaN or a positive number of at least 2^-96 (the discriminant of the two-sided step: clamped at
+// zero, a difference of two products of the size of 1e2 .. 1e5 otherwise -- zero, or no smaller than an ulp of those; inf - inf = NaN where a
+// neighbour is unreached).  The compiler's sqrtf is sqrt_pos's body inside a rescaling for arguments below 2^-96 and a class test that passes
+// zero and infinity through; sqrt_pos's body returns those two, and NaN, unchanged by itself (0: both neighbours of the root give a NaN or zero
+// residual, inf: NaN residuals).  What is left of the wrapper is the guard: for a positive argument below 2^-96 *outside is set and the
+// result is not to be used -- the caller takes the plain sqrtf (solve_regular: the member goes to the general walk).  Seven instructions less
+// per two-sided step; bit for bit sqrtf wherever *outside stays false (dsa_selfcheck_trip, tests/test_gpu_trip_exact.py).
+DSA_HD float sqrt_nonneg(float x, bool* outside)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    *outside = __float_as_uint(x) - 1u < 0x0f800000u - 1u;       // 0 < x < 2^-96 (zero wraps round; a sign bit, inf and NaN lie above)
+    return sqrt_pos(x);
+#else
+    *outside = false;
+    return sqrtf(x);
+#endif
+}
+
+// Minima of values known to be canonical: no signalling NaN, no negative zero (travel times and the sums they enter are positive, +inf, or the
+// quiet NaN of inf - inf).  fminf, and the selects the compiler turns into it, quiet a possible signalling NaN first -- a v_max_f32 x, x in
+// front of every operand that comes from memory; the bare instruction gives the same bits for every other operand: the smaller value, the
+// number where one operand is a quiet NaN (IEEE mode).  min3_sel is `a < inf ? a : inf`, then `b < . ? b : .`, then `c < . ? c : .`, which
+// differs from the IEEE minimum only in returning +inf where all three are NaN; no caller reads that case (solve_regular: one-sided values are
+// never NaN).  The deliberate quiet NaN of an outer value that was not fetched (bundle_kernel.hip) never reaches these: solve_regular selects
+// by comparisons with it, which are false, and refuses the member (`missing`) where it would have been an operand.
+DSA_HD float min_canon(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fminf(a, b);
+#endif
+}
+DSA_HD float min3_sel(float a, float b, float c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#else
+    float m = a < kInf ? a : kInf;
+    m = b < m ? b : m;
+    return c < m ? c : m;
+#endif
+}
+
 DSA_HD float div3(float x)
 {
     const float c = 0x1.555556p-2f;
@@ -572,17 +620,16 @@ DSA_HD float solve_regular(const float* tn, const float* t2, float slown, const 
     const float cc = (both ? 4.0f : 1.0f) * (U * (sq(em) - S));
     float rd1 = sq(b) - 4.0f * a * cc;
     if (rd1 < 0.0f) rd1 = 0.0f;
-    const float tdsh = (-b + sqrtf(rd1)) / (2.0f * a);
+    bool tiny;                                                  // (a discriminant sqrt_nonneg does not take: never seen, the general walk's business)
+    const float tdsh = (-b + sqrt_nonneg(rd1, &tiny)) / (2.0f * a);
     float trav = tref + tdsh;
     if (both) trav = div3(trav);
-    float c2 = onex < kInf ? onex : kInf;
-    c2 = onez < c2 ? onez : c2;
-    c2 = trav < c2 ? trav : c2;
+    const float c2 = min3_sel(onex, onez, trav);               // (trav is NaN where a direction is unreached: inf - inf; the one-sided values never are)
     const bool stop2 = !(k2 < kInf && c2 > k2);
     // (round 5, bundle_kernel.hip: an outer value the caller did not fetch arrives as NaN; the walk never reads the downwind ones, and a
     // member whose UPWIND outer value is missing -- its near neighbour reached -- is not this function's business)
     const bool missing = (tx2 != tx2 && tx < kInf) || (tz2 != tz2 && tz < kInf);
-    *ok = (stop1 || (std2 && stop2)) && !missing;
+    *ok = (stop1 || (std2 && stop2)) && !missing && !tiny;
     if (tie) *tie = stop1 ? (k1 < kInf && c1 == k1) : (std2 && stop2 && k2 < kInf && c2 == k2);
     const float c = stop1 ? c1 : c2, tnow = stop1 ? k0 : k1;
     *tau_out = (c > tnow) ? c : tnow;

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "dispersion_core.h"
 #include "ray_core.h"
+#include "eikonal_core.h"
 
 namespace dsa {
 
@@ -62,7 +63,94 @@ __global__ void k_selfcheck_divisions(unsigned long long seed, int per_thread, i
     atomicAdd(out + 0, n64); atomicAdd(out + 1, bad64); atomicAdd(out + 2, n32); atomicAdd(out + 3, bad32);
 }
 
+// The node trip's arithmetic helpers (eikonal_core.h: sqrt_nonneg, min_canon, min3_sel) against their plain forms, bit for bit.
+// out[0]: square roots tried, out[1]: that differ from sqrtf (outside the guard), out[2]: arguments the guard sent to the plain sqrtf;
+// out[3]: minima tried, out[4]: that differ.  Half of the square roots take the two-sided step's discriminant as solve_regular forms it -- all four
+// variants of (a, b, c), cell sizes of 1e-5 .. 1e-1 rad, radii 6371 +- 100 km, slowness 0.1 .. 1 s/km, time differences of 0 and 1e-12 .. 1e3 s, with
+// exact zeros and cancellation (the difference set to the value that makes c vanish) --, half a positive number of any exponent, with 0, +inf,
+// NaN and the range below 2^-96 now and then.  The minima take travel times (1e-12 .. 1e3 s), +inf, equal operands and a quiet NaN.
+__global__ void k_selfcheck_trip(unsigned long long seed, int per_thread, unsigned long long* __restrict__ out)
+{
+    unsigned long long s = seed ^ ((unsigned long long)(blockIdx.x * blockDim.x + threadIdx.x) * 0x9e3779b97f4a7c15ull);
+    unsigned long long nsq = 0, badsq = 0, guarded = 0, nmin = 0, badmin = 0;
+    const float nanq = __uint_as_float(0x7fc00000u);
+    for (int i = 0; i < per_thread; ++i) {
+        float x;
+        const unsigned long long pick = sc_next(s);
+        if (pick & 1ull) {
+            const float ri = 6271.0f + 200.0f * (float)((pick >> 8) & 0xffffull) * (1.0f / 65535.0f);
+            const float risti = ri * (0.1f + 0.9f * (float)((pick >> 24) & 0xffffull) * (1.0f / 65535.0f));
+            const float dnx = fabsf(sc_f32(s, -17, -4)), dnz = fabsf(sc_f32(s, -17, -4));        // 7.6e-6 .. 0.125 rad
+            const float slown = 0.1f + 0.9f * (float)((pick >> 40) & 0xffffull) * (1.0f / 65535.0f);
+            const int var = (int)((pick >> 1) & 3ull);
+            const bool sx = (var & 1) != 0, sz = (var & 2) != 0, both = sx && sz, one = sx != sz;
+            const float s2 = sq(slown), A = sq(ri * dnx), B = sq(risti * dnz), s2A = A * s2, s2B = B * s2;
+            const float U = (sx && !sz) ? B : A;
+            const float S = (sx && !sz) ? 4.0f * s2A : (sz ? 4.0f * s2B : s2B);
+            const float a00 = A + B;
+            const float a = sx ? (sz ? 4.0f * a00 : 4.0f * A + 9.0f * B) : (sz ? 4.0f * B + 9.0f * A : a00);
+            float em = sc_f32(s, -40, 10);                                                         // 9e-13 .. 2e3 s, either sign
+            const unsigned sp = (unsigned)((pick >> 3) & 31ull);
+            if (sp == 0) em = 0.0f;
+            else if (sp < 8) em = (sp & 1u ? 1.0f : -1.0f) * sqrt_pos(S) * (1.0f + (float)((int)(sp >> 1) - 2) * 1.1920929e-7f);      // c = U (em^2 - S) cancels
+            else if (sp < 16) {                                                                   // the discriminant itself cancels: b^2 = 4 a c (a grazing front)
+                const float f = both ? 8.0f : (one ? 6.0f : -2.0f), g4a = 4.0f * a * (both ? 4.0f : 1.0f), den = g4a - sq(f) * U;
+                if (den > 0.0f) em = (sp & 1u ? 1.0f : -1.0f) * sqrtf(g4a * S / den) * (1.0f + (float)((int)(sp >> 1) - 6) * 1.1920929e-7f);
+            }
+            const float b = (both ? 8.0f : (one ? 1.0f : -2.0f)) * (((one ? 6.0f : 1.0f) * em) * U);
+            const float cc = (both ? 4.0f : 1.0f) * (U * (sq(em) - S));
+            x = sq(b) - 4.0f * a * cc;
+            if (x < 0.0f) x = 0.0f;
+        } else {
+            x = fabsf(sc_f32(s, -96, 100));
+            const unsigned sp = (unsigned)((pick >> 3) & 1023ull);
+            if (sp == 0) x = 0.0f; else if (sp == 1) x = kInf; else if (sp == 2) x = nanq;
+            else if (sp < 6) x = fabsf(sc_f32(s, -126, -97));                                      // the guard's range
+            else if (sp == 6) x = __uint_as_float((unsigned)(sc_next(s) & 0x7fffffull) | 1u);      // denormal
+        }
+        bool outside;
+        const float h = sqrt_nonneg(x, &outside), plain = sqrtf(x);
+        ++nsq;
+        if (outside) ++guarded;
+        else if (!(h != h && plain != plain) && __float_as_uint(h) != __float_as_uint(plain)) ++badsq;
+
+        float t[3];
+        const unsigned long long pm = sc_next(s);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t[k] = fabsf(sc_f32(s, -40, 10));
+            const unsigned sp = (unsigned)((pm >> (8 * k)) & 15ull);
+            if (sp == 0) t[k] = kInf; else if (sp == 1 && k > 0) t[k] = t[0]; else if (sp == 2 && k > 0) t[k] = nanq;      // (the first operand is never NaN: see min3_sel)
+        }
+        const float m2 = min_canon(t[0], t[1]), p2 = fminf(t[0], t[1]);
+        float p3 = t[0] < kInf ? t[0] : kInf;
+        p3 = t[1] < p3 ? t[1] : p3;
+        p3 = t[2] < p3 ? t[2] : p3;
+        const float m3 = min3_sel(t[0], t[1], t[2]);
+        nmin += 2;
+        if (__float_as_uint(m2) != __float_as_uint(p2)) ++badmin;
+        if (__float_as_uint(m3) != __float_as_uint(p3)) ++badmin;
+    }
+    atomicAdd(out + 0, nsq); atomicAdd(out + 1, badsq); atomicAdd(out + 2, guarded); atomicAdd(out + 3, nmin); atomicAdd(out + 4, badmin);
+}
+
 }  // namespace dsa
+
+extern "C" int dsa_selfcheck_trip(unsigned long long seed, int millions, unsigned long long* out5)
+{
+    using namespace dsa;
+    if (!out5 || millions < 1 || millions > 4096) return DSA_ERR_ARGUMENT;
+    unsigned long long* d_out = nullptr;
+    if (hipMalloc(&d_out, 5 * sizeof(unsigned long long)) != hipSuccess) return DSA_ERR_DEVICE;
+    if (hipMemset(d_out, 0, 5 * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(d_out); return DSA_ERR_DEVICE; }
+    const int per_thread = 64, threads = 256;
+    const long long n = (long long)millions * 1000000ll;
+    const int blocks = (int)((n + (long long)threads * per_thread - 1) / ((long long)threads * per_thread));
+    hipLaunchKernelGGL(k_selfcheck_trip, dim3(blocks), dim3(threads), 0, 0, seed, per_thread, d_out);
+    const hipError_t rc = hipMemcpy(out5, d_out, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_out);
+    return rc == hipSuccess ? 0 : DSA_ERR_INTERNAL;
+}
 
 extern "C" int dsa_selfcheck_divisions(unsigned long long seed, int millions, const int* exponents8, unsigned long long* out4)
 {

@@ -77,6 +77,8 @@ def load_library():
     L.dsa_lsmr_voronoi.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
+    if hasattr(L, "dsa_selfcheck_trip"):         # (absent from older libraries: same-box A/B runs, DSA_LIB_PATH)
+        L.dsa_selfcheck_trip.argtypes = [C.c_ulonglong, _i32, _vp]
     L.dsa_dropin_error.restype = C.c_char_p
     L.dsa_dropin_set_capacity.argtypes = [C.c_longlong]
     L.dsa_aprod_invalidate.argtypes = []
@@ -97,6 +99,17 @@ def selfcheck_divisions(seed, millions, exponents8):
     rc = L.dsa_selfcheck_divisions(int(seed), int(millions), _p(ex), _p(out))
     if rc != 0:
         raise EngineError("dsa_selfcheck_divisions failed (%d)" % rc)
+    return tuple(int(v) for v in out)
+
+
+def selfcheck_trip(seed, millions):
+    """device self-check of the node trip's arithmetic helpers (include/dsurftomo_amd.h: dsa_selfcheck_trip): (square roots tried, that differ
+    from sqrtf bitwise, arguments the guard left to sqrtf, minima tried, that differ)"""
+    L = load_library()
+    out = np.zeros(5, np.uint64)
+    rc = L.dsa_selfcheck_trip(int(seed), int(millions), _p(out))
+    if rc != 0:
+        raise EngineError("dsa_selfcheck_trip failed (%d)" % rc)
     return tuple(int(v) for v in out)
 
 

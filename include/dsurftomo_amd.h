@@ -390,6 +390,10 @@ int dsa_unit_rounds(const dsa_engine* e, int nunits, int* rounds);
  * ranges {numerator lo, hi, denominator lo, hi} for fp64, then for fp32.  out4: fp64 pairs, fp64 quotients that differ bitwise, fp32 pairs, fp32
  * quotients that differ.  Needs no engine; uses the current device. */
 int dsa_selfcheck_divisions(unsigned long long seed, int millions, const int* exponents8, unsigned long long* out4);
+/* device self-check of the bundled node trip's arithmetic helpers (csrc/eikonal_core.h: sqrt_nonneg, min_canon, min3_sel) against their plain forms,
+   `millions` * 1e6 operands each: out5 = { square roots tried, that differ from sqrtf bitwise, arguments the helper's guard left to sqrtf,
+   minima tried, that differ } */
+int dsa_selfcheck_trip(unsigned long long seed, int millions, unsigned long long* out5);
 
 /* probe builds only (-DDSA_LEDGER, tools/isa_ledger.py): trip counters of the coarse solve's phases, summed over the units of the last solve */
 int dsa_debug_counters(const dsa_engine* e, double* out24);

@@ -54,5 +54,16 @@ for size, lo, hi in around:
 if picked and sum(picked[0][0] <= i <= picked[0][1] for i in sq) > 3:      # the default build: the member body four times inside the node-trip loop, no member loop
     names = ["node-trip loop (16 nodes x 4 lanes per wave trip; four member evaluations, unrolled)"] + names[2:]
 for nm, (lo, hi) in zip(names, picked): show(nm, mix(lo, hi))
+# the node trip as the smallest loop that holds the trip's ten 16-byte loads and its twelve hardware square roots (the pick above goes by nesting
+# and lands elsewhere when the compiler unrolls the member loop): the count the NOTEBOOK's trip ledger quotes
+trip = [(hi - lo, lo, hi) for lo, hi in loops if sum("v_sqrt_f32" in x for x in lines[lo:hi + 1]) >= 12 and sum("global_load_dwordx4" in x for x in lines[lo:hi + 1]) >= 10]
+if trip:
+    _, lo, hi = min(trip)
+    ins = [l.strip() for l in lines[lo:hi + 1] if l.startswith("\t") and not l.strip().startswith((".", ";"))]
+    cnt = lambda pat: sum(1 for x in ins if re.match(pat, x))
+    print("trip loop (smallest loop with the ten 16-byte loads and twelve v_sqrt_f32): %d instructions = %d VALU + %d SALU (%d s_nop);  s_cbranch_execz %d, *_saveexec %d, v_cndmask %d, v_mov %d, "
+          "v_readlane %d, v_max_f32 %d, v_min* %d, v_mul_lo_u32 %d, v_or_b32 %d, v_or3_b32 %d, v_div_scale %d, scratch %d" %
+          (len(ins), cnt(r"v_"), cnt(r"s_"), cnt(r"s_nop"), cnt(r"s_cbranch_execz"), cnt(r"s_\w+_saveexec"), cnt(r"v_cndmask"), cnt(r"v_mov"), cnt(r"v_readlane"), cnt(r"v_max_f32"), cnt(r"v_min"),
+           cnt(r"v_mul_lo_u32"), cnt(r"v_or_b32"), cnt(r"v_or3_b32"), cnt(r"v_div_scale"), cnt(r"scratch_")))
 print("(static counts; rare paths -- exception-table probes, the inactive-member path -- are inside them.  Dynamic, per solve at 1025^2, profiles/pmc_latest.json:")
 print(" VALU / SALU wave instructions, fabric bytes, valu_issue.)")
