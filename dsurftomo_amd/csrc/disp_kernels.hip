@@ -153,6 +153,27 @@ void launch_depth_kernels(const float* d_vels, int ncol, int nz, int kmax, const
                        with_kernels, d_pv, d_sen_vs, d_sen_vp, d_sen_rho, kmax_total, slot0);
 }
 
+// Multi-model run (Engine::dispersion_run with disp_nmodels > 1): the models are extra columns of k_dispersion, so its curves come out
+// (period, model, column); the map store is model-major.  One thread per value.
+__global__ void k_pv_models(const double* __restrict__ curves, int ncol, int nmodels, int kmax, int nmaps_per_model, int map_first,
+                            double* __restrict__ pv)
+{
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t ncm = (size_t)ncol * nmodels;
+    if (id >= ncm * kmax) return;
+    const int k = (int)(id / ncm);
+    const size_t mc = id - (size_t)k * ncm;
+    const int model = (int)(mc / ncol), c = (int)(mc - (size_t)model * ncol);
+    pv[((size_t)model * nmaps_per_model + map_first + k) * ncol + c] = curves[id];
+}
+
+void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, int nmaps_per_model, int map_first, double* d_pv, hipStream_t stream)
+{
+    const size_t n = (size_t)ncol * nmodels * kmax;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_pv_models, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_curves, ncol, nmodels, kmax, nmaps_per_model, map_first, d_pv);
+}
+
 // velv = real(pv) for the maps of a call (CalSurfG.f90:1492)
 __global__ void k_to_float(const double* __restrict__ in, float* __restrict__ out, size_t n)
 {

@@ -500,4 +500,130 @@ int dsa_synthetic(const int* nx, const int* ny, const int* nz, const int* nparpi
     return 0;
 }
 
+// K models through the dispersion stage and the eikonal solves in one call: times only (include/dsurftomo_amd.h).
+// The translation is dsa_calsurfg's (dicing 8) or dsa_synthetic's (dicing 5) with a model dimension in front: model m's maps are
+// [m * L.nmaps, (m + 1) * L.nmaps) of the store, its units are the call's units on those maps, its data column m of dsurf.
+int dsa_forward_models(const int* nx, const int* ny, const int* nz, const int* nmodels, const float* vels,
+                       float* dsurf, const int* ldd, const int* dicing, long long* disp_failures,
+                       const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                       const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                       const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                       const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                       const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                       const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                       const int* nsrcsurf, const int* nrcf)
+{
+    if (!nx || !ny || !nz || !nmodels || !vels || !dsurf || !ldd || !dicing || !goxdf || !gozdf || !dvxdf || !dvzdf || !kmaxRc || !kmaxRg || !kmaxLc || !kmaxLg ||
+        (*kmaxRc > 0 && !tRc) || (*kmaxRg > 0 && !tRg) || (*kmaxLc > 0 && !tLc) || (*kmaxLg > 0 && !tLg) || !wavetype || !igrt || !periods || !depz || !minthk || !scxf || !sczf || !rcxf || !rczf || !nrc1 || !nsrcsurf1 || !kmax ||
+        !nsrcsurf || !nrcf) { g_dropin_error = "dsa_forward_models: null argument"; return DSA_ERR_ARGUMENT; }
+    if (*nmodels < 1) { g_dropin_error = "dsa_forward_models: nmodels must be at least 1"; return DSA_ERR_ARGUMENT; }
+    if (*dicing != 5 && *dicing != 8) { g_dropin_error = "dsa_forward_models: dicing must be 8 (CalSurfG's grid) or 5 (synthetic's)"; return DSA_ERR_ARGUMENT; }
+    int rc = engine();
+    if (rc != 0) return rc;
+    if (g_pool.size() != 1) { g_dropin_error = "dsa_forward_models: one engine only (DSA_DEVICES unset): models are not sharded over GPUs"; return DSA_ERR_STATE; }
+    dsa_engine* e = g_engine;
+    dsa::Engine* en = reinterpret_cast<dsa::Engine*>(e);
+    const bool cal = *dicing == 8;
+    const Layout L = make_layout(*kmaxRc, *kmaxRg, *kmaxLc, *kmaxLg, *kmax, cal);
+    if (cal && L.kRc + L.kRg + L.kLc + L.kLg != L.kmax) { g_dropin_error = "dsa_forward_models: kmax must equal kmaxRc+kmaxRg+kmaxLc+kmaxLg"; return DSA_ERR_ARGUMENT; }
+    Units U;
+    if ((rc = make_units(L, false, *nsrcsurf, *nrcf, wavetype, igrt, periods, nrc1, nsrcsurf1, scxf, sczf, rcxf, rczf, U)) != 0) return rc;
+    if (*ldd < U.ndata) { g_dropin_error = "dsa_forward_models: ldd is below the number of data"; return DSA_ERR_ARGUMENT; }
+    const int K = *nmodels, nu = (int)U.map.size(), nmaps = std::max(L.nmaps, 1);
+    const size_t ncol = (size_t)*nx * *ny, nd = (size_t)U.ndata;
+    tie_reset();
+    g_rbint_notes = 0; g_disp_count = 0; g_disp_period = 0.0;
+    for (int q = 0; q < 5; ++q) g_disp_first[q] = 0;
+    if (disp_failures) for (int m = 0; m < K; ++m) disp_failures[m] = 0;
+
+    // models per pass: the option, or what the budget holds maps for -- a map costs its vertex values (fp64 store, fp32 copy), its
+    // diced nodes and two copies of its tiled slowness (the bundles read a member-minor one, whose byte offsets are 32-bit)
+    int per_pass = en->forward_models_chunk > 0 ? std::min(en->forward_models_chunk, K) : K;
+    if (en->forward_models_chunk == 0 && *nx >= 4 && *ny >= 4) {
+        dsa::GridDesc gd{};
+        dsa::make_grid(gd, *nx, *ny, *goxdf, *gozdf, *dvxdf, *dvzdf, *dicing);
+        const size_t nrec_c = (size_t)gd.nbx * gd.nbz * dsa::kTileRecs;
+        const size_t per_map = ncol * 12 + (size_t)gd.nnx * gd.nnz * 4 + nrec_c * 8;
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(en->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { g_dropin_error = "dsa_forward_models: no memory information from the device"; return DSA_ERR_DEVICE; }
+        const size_t budget = en->mem_budget ? en->mem_budget : (size_t)(0.6 * (double)free_b);
+        size_t maps = std::max<size_t>((size_t)(0.25 * (double)budget) / per_map, 1);
+        maps = std::min<size_t>(maps, (((size_t)1 << 32) - 1) / (nrec_c * 4));
+        per_pass = (int)std::min<size_t>((size_t)K, std::max<size_t>(maps / (size_t)nmaps, 1));
+    }
+
+    std::vector<int> m_map, m_nrec, m_mode, m_data;
+    std::vector<float> m_sx, m_sz, m_rx, m_rz, times;
+    std::vector<size_t> ray0((size_t)nu + 1, 0);
+    for (int u = 0; u < nu; ++u) ray0[(size_t)u + 1] = ray0[(size_t)u] + (size_t)U.nrec[(size_t)u];
+    std::vector<long long> fails;
+    long long disp_count = 0;
+    // the passes run from the last models to the first, so that the store is left with model 0's maps at its head (dsa_dropin_velocity_maps)
+    const int npass = (K + per_pass - 1) / per_pass;
+    for (int pass = npass - 1; pass >= 0; --pass) {
+        const int m0 = pass * per_pass, nm = std::min(per_pass, K - m0);
+        if ((rc = dsa_dispersion_begin_models(e, *nx, *ny, *nz, nm, vels + (size_t)m0 * ncol * (size_t)*nz, depz, *minthk, nmaps)) != 0) return fail(rc);
+        if (cal) {
+            // CalSurfG.f90:1100-1140 without the depth kernels: the phase velocities at the group periods overwrite the head of the phase block
+            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, tRc, 0, 0, L.oRc)) != 0) return fail(rc);
+            if (L.kRg > 0) {
+                if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, tRg, 0, 0, L.oRg)) != 0) return fail(rc);
+                if ((rc = dsa_dispersion_run(e, 2, 0, L.kRg, tRg, 0, 0, L.oRc)) != 0) return fail(rc);
+            }
+            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, tLc, 0, 0, L.oLc)) != 0) return fail(rc);
+            if (L.kLg > 0) {
+                if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, tLg, 0, 0, L.oLg)) != 0) return fail(rc);
+                if ((rc = dsa_dispersion_run(e, 1, 0, L.kLg, tLg, 0, 0, L.oLc)) != 0) return fail(rc);
+            }
+        } else {
+            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, tRc, 0, 0, L.oRc)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, tRg, 0, 0, L.oRg)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, tLc, 0, 0, L.oLc)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, tLg, 0, 0, L.oLg)) != 0) return fail(rc);
+        }
+        if ((rc = dsa_maps_from_dispersion(e, *goxdf, *gozdf, *dvxdf, *dvzdf, *dicing)) != 0) return fail(rc);
+        remember(L, *nx * *ny, cal);
+        fails.assign((size_t)nm, 0);
+        if ((rc = dsa_dispersion_model_failures(e, nm, fails.data())) != 0) return fail(rc);
+        for (int m = 0; m < nm; ++m) { disp_count += fails[(size_t)m]; if (disp_failures) disp_failures[m0 + m] = fails[(size_t)m]; }
+        {   // (the first failing curve reported is that of the lowest pass that had one: the passes run downwards, so a later pass overwrites)
+            long long c = 0; int first[5]; double period = 0.0;
+            if (dsa_dispersion_diagnostics(e, &c, first, &period) == 0 && c > 0) {
+                for (int q = 0; q < 5; ++q) g_disp_first[q] = first[q];
+                g_disp_first[2] += m0 * (int)ncol;
+                g_disp_period = period;
+            }
+        }
+        // the pass's units: every model's copy of the call's unit list on its own maps, data in its own column.  Model-major keeps the
+        // periods of a (model, source) consecutive: a bundle's members then read neighbouring maps of the member-minor slowness
+        const size_t n = (size_t)nu * nm;
+        m_map.resize(n); m_nrec.resize(n); m_mode.resize(n); m_data.resize(n); m_sx.resize(n); m_sz.resize(n);
+        m_rx.clear(); m_rz.clear();
+        m_rx.reserve(ray0[(size_t)nu] * nm); m_rz.reserve(ray0[(size_t)nu] * nm);
+        size_t q = 0;
+        auto put = [&](int m, int u) {
+            m_map[q] = m * nmaps + U.map[(size_t)u]; m_nrec[q] = U.nrec[(size_t)u]; m_mode[q] = U.mode[(size_t)u];
+            // (plan wants the data indices non-decreasing in unit order: model-major a column per model, period-major the models of a unit side by side)
+            m_data[q] = en->forward_models_order == 0 ? (int)((size_t)m * nd) + U.data[(size_t)u] : (int)((size_t)nm * (size_t)U.data[(size_t)u] + (size_t)m * (size_t)U.nrec[(size_t)u]);
+            m_sx[q] = U.sx[(size_t)u]; m_sz[q] = U.sz[(size_t)u];
+            m_rx.insert(m_rx.end(), U.rx.begin() + (long)ray0[(size_t)u], U.rx.begin() + (long)ray0[(size_t)u + 1]);
+            m_rz.insert(m_rz.end(), U.rz.begin() + (long)ray0[(size_t)u], U.rz.begin() + (long)ray0[(size_t)u + 1]);
+            ++q;
+        };
+        if (en->forward_models_order == 0) { for (int m = 0; m < nm; ++m) for (int u = 0; u < nu; ++u) put(m, u); }
+        else { for (int u = 0; u < nu; ++u) for (int m = 0; m < nm; ++m) put(m, u); }
+        if ((unsigned long long)nd * (unsigned long long)nm > (unsigned long long)INT_MAX) { g_dropin_error = "dsa_forward_models: more than 2^31-1 data in a pass (set option forward_models_chunk)"; return DSA_ERR_ARGUMENT; }
+        if ((rc = dsa_plan_units(e, (int)n, m_map.data(), m_sx.data(), m_sz.data(), m_nrec.data(), m_rx.data(), m_rz.data(), m_mode.data(), nullptr, m_data.data())) != 0) return fail(rc);
+        times.assign(std::max<size_t>(nd * nm, 1), 0.0f);
+        if ((rc = dsa_solve(e, times.data())) != 0) return fail(rc);
+        tie_collect(e);
+        for (size_t k = 0; k < n; ++k) {
+            const int u = en->forward_models_order == 0 ? (int)(k % (size_t)nu) : (int)(k / (size_t)nm), m = en->forward_models_order == 0 ? (int)(k / (size_t)nu) : (int)(k % (size_t)nm);
+            if (U.nrec[(size_t)u]) std::memcpy(dsurf + (size_t)(m0 + m) * (size_t)*ldd + (size_t)U.data[(size_t)u], times.data() + (size_t)m_data[k], (size_t)U.nrec[(size_t)u] * 4);
+        }
+    }
+    g_disp_count = disp_count;
+    return 0;
+}
+
 }  // extern "C"

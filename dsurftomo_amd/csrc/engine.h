@@ -223,6 +223,13 @@ struct Engine {
     // dispersion stage (disp_kernels.hip): Vs model -> pv maps + depth kernels, all resident
     bool disp_ready = false;
     int disp_nx = 0, disp_ny = 0, disp_nz = 0, disp_kmax_total = 0, disp_nmaps = 0;
+    // model dimension (dsa_dispersion_begin_models): disp_nmodels Vs models share one launch per dispersion_run.  The models sit side by side as
+    // columns -- vels_d / h_vels are (depth, model, column), a curve is model * ncol + column -- so k_dispersion runs unchanged on
+    // ncol * nmodels columns; the map store is model-major, disp_nmaps maps per model (global map = model * disp_nmaps + m)
+    int disp_nmodels = 1;
+    std::vector<long long> disp_model_fail;      // curves without a root per model since begin (dsa_dispersion_model_failures)
+    int forward_models_chunk = 0;                // option forward_models_chunk: models per pass of dsa_forward_models, 0 = from the memory budget
+    int forward_models_order = 0;                // option forward_models_order: unit order of dsa_forward_models, 0 = model-major (default), 1 = period-major (A/B)
     std::vector<float> h_depz;
     LayerGeom h_geom{};
     DevBuf<LayerGeom> geom;
@@ -275,7 +282,7 @@ struct Engine {
              const int* mode, const int* sen_slot, const int* data_first);
     int set_sensitivity(int nz, int kmax, const float* vels, const float* depz, const double* svs, const double* svp, const double* srho, bool on_device);
     int finish_maps(int nm);
-    int dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total);
+    int dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels = 1);
     int dispersion_run(int iwave, int igr, int nper, const double* t, int with_kernels, int sen_slot, int map_first);
     int dispersion_copy_map(int from, int to, int n);
     int dispersion_fetch(int map_first, int nper, double* pv, int with_kernels, int sen_slot, double* svs, double* svp, double* srho);

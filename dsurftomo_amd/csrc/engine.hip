@@ -176,27 +176,37 @@ int Engine::finish_maps(int nm)
 }
 
 // ---- dispersion stage -----------------------------------------------------------------------------
-int Engine::dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total)
+int Engine::dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels)
 {
-    if (nx < 1 || ny < 1 || nz < 2 || nz > 64 || !vels || !depz || kmax_total < 1 || nmaps_total < 1 || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d)", nx, ny, nz, kmax_total); return DSA_ERR_ARGUMENT; }
+    if (nx < 1 || ny < 1 || nz < 2 || nz > 64 || !vels || !depz || kmax_total < 1 || nmaps_total < 1 || nmodels < 1 || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, nmodels); return DSA_ERR_ARGUMENT; }
+    if ((unsigned long long)nx * ny * nmodels > 0x7fffffffull || (unsigned long long)nmaps_total * nmodels > 0x7fffffffull) { fail(DSA_ERR_ARGUMENT, "dispersion: %d models of %d x %d columns and %d maps exceed the index range", nmodels, nx, ny, nmaps_total); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
     if (make_layer_geom(nz, depz, minthk, h_geom) != 0) { fail(DSA_ERR_ARGUMENT, "dispersion: the refined column exceeds %d layers", kMaxLayers); return DSA_ERR_ARGUMENT; }
     const size_t ncol = (size_t)nx * ny;
-    disp_nx = nx; disp_ny = ny; disp_nz = nz; disp_kmax_total = kmax_total; disp_nmaps = nmaps_total;
+    disp_ready = false;
+    disp_nx = nx; disp_ny = ny; disp_nz = nz; disp_kmax_total = kmax_total; disp_nmaps = nmaps_total; disp_nmodels = nmodels;
     h_depz.assign(depz, depz + nz);
-    const size_t nsen = ncol * kmax_total * nz;
-    if (ensure(geom, 1) || ensure(vels_d, ncol * nz) || ensure(pvstore, ncol * nmaps_total) || ensure(sen_vs, nsen) || ensure(sen_vp, nsen) || ensure(sen_rho, nsen)) return status;
+    // (depth kernels exist for one model only: dispersion_run refuses them otherwise)
+    const size_t nsen = nmodels == 1 ? ncol * kmax_total * nz : 0, npv = ncol * nmaps_total * nmodels;
+    // the model of one call is (column, depth); several are given model slowest and kept (depth, model, column): extra columns to the kernel
+    h_vels.resize(ncol * nz * nmodels);
+    for (int m = 0; m < nmodels; ++m)
+        for (int k = 0; k < nz; ++k)
+            std::memcpy(h_vels.data() + ((size_t)k * nmodels + m) * ncol, vels + ((size_t)m * nz + k) * ncol, ncol * 4);
+    if (ensure(geom, 1) || ensure(vels_d, h_vels.size()) || ensure(pvstore, npv) || ensure(sen_vs, nsen) || ensure(sen_vp, nsen) || ensure(sen_rho, nsen)) return status;
     HIP_TRY(this, hipMemcpyAsync(geom.p, &h_geom, sizeof(LayerGeom), hipMemcpyHostToDevice, stream));
-    HIP_TRY(this, hipMemcpyAsync(vels_d.p, vels, ncol * nz * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(this, hipMemsetAsync(pvstore.p, 0, ncol * nmaps_total * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(sen_vs.p, 0, nsen * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(sen_vp.p, 0, nsen * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(sen_rho.p, 0, nsen * 8, stream));
+    HIP_TRY(this, hipMemcpyAsync(vels_d.p, h_vels.data(), h_vels.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemsetAsync(pvstore.p, 0, npv * 8, stream));
+    if (nsen) {
+        HIP_TRY(this, hipMemsetAsync(sen_vs.p, 0, nsen * 8, stream));
+        HIP_TRY(this, hipMemsetAsync(sen_vp.p, 0, nsen * 8, stream));
+        HIP_TRY(this, hipMemsetAsync(sen_rho.p, 0, nsen * 8, stream));
+    }
     HIP_TRY(this, hipStreamSynchronize(stream));
     disp_ready = true;
     disp_fail_count = 0;
+    disp_model_fail.assign((size_t)nmodels, 0);
     disp_failures.clear();
-    h_vels.assign(vels, vels + ncol * nz);
     have_sens = false;
     stats[DSA_STAT_MS_DISPERSION] = 0.0;
     stats[DSA_STAT_CURVES] = 0.0;
@@ -211,8 +221,11 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
     if (nper <= 0) return 0;
     if ((iwave != 1 && iwave != 2) || nper > kMaxPeriods || !t || map_first < 0 || map_first + nper > disp_nmaps ||
         (with_kernels && (sen_slot < 0 || sen_slot + nper > disp_kmax_total))) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (iwave=%d nper=%d map=%d slot=%d)", iwave, nper, map_first, sen_slot); return DSA_ERR_ARGUMENT; }
+    if (with_kernels && disp_nmodels > 1) { fail(DSA_ERR_ARGUMENT, "dispersion: depth kernels are computed for one model, not for %d", disp_nmodels); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
-    const int ncol = disp_nx * disp_ny;
+    // (several models: their columns side by side, so every count below -- the lanes-per-curve choice too -- is over all models)
+    const int ncol = disp_nx * disp_ny * disp_nmodels;
+    const bool models = disp_nmodels > 1;
     const int npert = with_kernels ? 1 + 6 * disp_nz : 1;
     const size_t nlanes = (size_t)ncol * npert;
     if (ensure(curves, nlanes * nper) || ensure(disp_ws, (size_t)4 * h_geom.rmax * nlanes) || ensure(tper, kMaxPeriods) || ensure(disp_diag, 2)) return status;
@@ -231,11 +244,14 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
     }
     // (the device lists failing curves in arrival order: room for every curve of the run, so that the FIRST disp_failure_log of the
     // reference's call order can be picked after the host sort -- a list of disp_failure_log entries kept an arbitrary subset)
-    if (disp_failure_log > 0 && ensure(disp_fail_list, nlanes)) return status;
+    // (several models: the list also tells which model a failing curve belongs to)
+    const bool listed = disp_failure_log > 0 || models;
+    if (listed && ensure(disp_fail_list, nlanes)) return status;
     launch_dispersion(iwave, geom.p, vels_d.p, ncol, npert, igr, nper, tper.p, disp_ws.p, nlanes, curves.p, h_geom.rmax, in_lds, gshift, disp_diag.p,
-                      disp_failure_log > 0 ? disp_fail_list.p : nullptr, disp_failure_log > 0 ? (int)std::min<size_t>(nlanes, (size_t)0x7fffffff) : 0, stream);
-    launch_depth_kernels(vels_d.p, ncol, disp_nz, nper, curves.p, with_kernels, pvstore.p + (size_t)map_first * ncol, sen_vs.p, sen_vp.p, sen_rho.p,
-                         disp_kmax_total, sen_slot, stream);
+                      listed ? disp_fail_list.p : nullptr, listed ? (int)std::min<size_t>(nlanes, (size_t)0x7fffffff) : 0, stream);
+    if (models) launch_pv_models(curves.p, disp_nx * disp_ny, disp_nmodels, nper, disp_nmaps, map_first, pvstore.p, stream);
+    else launch_depth_kernels(vels_d.p, ncol, disp_nz, nper, curves.p, with_kernels, pvstore.p + (size_t)map_first * ncol, sen_vs.p, sen_vp.p, sen_rho.p,
+                              disp_kmax_total, sen_slot, stream);
     HIP_TRY(this, hipEventRecord(events[2], stream));
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
@@ -254,7 +270,8 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
             disp_fail_period = k >= 1 && k <= nper ? t[k - 1] : 0.0;
         }
         disp_fail_count += (long long)diag[0];
-        if (disp_failure_log > 0) {
+        if (!models) disp_model_fail[0] += (long long)diag[0];
+        if (listed) {
             // the failing curves of this run in the reference's call order: column by column, the model itself, then its perturbations
             // (CalSurfG.f90:44-150 on one thread; the device reports them in any order)
             const size_t nl = (size_t)std::min<unsigned long long>(diag[0], (unsigned long long)nlanes);
@@ -267,6 +284,7 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
                 r.iwave = iwave; r.igr = igr; r.nper = nper; r.k = (int)(v & 0xffull);
                 r.column = (int)(curve % (unsigned long long)ncol) + 1; r.pert = (int)(curve / (unsigned long long)ncol);
                 for (int q = 0; q < nper && q < 60; ++q) r.t[q] = t[q];
+                if (models) ++disp_model_fail[(size_t)((r.column - 1) / (disp_nx * disp_ny))];
                 recs.push_back(r);
             }
             std::sort(recs.begin(), recs.end(), [](const DispFailRec& a, const DispFailRec& b) { return a.column != b.column ? a.column < b.column : a.pert < b.pert; });
@@ -283,7 +301,7 @@ int Engine::dispersion_failure(int index, int* info, double* vals, float* table,
 {
     if (index < 0 || index >= (int)disp_failures.size() || !info || !vals || !table || !c) return DSA_ERR_ARGUMENT;
     const DispFailRec& r = disp_failures[(size_t)index];
-    const size_t ncol = (size_t)disp_nx * disp_ny;
+    const size_t ncol = (size_t)disp_nx * disp_ny * disp_nmodels;      // (h_vels: depth, model, column; r.column counts over the models)
     float vs[64];
     for (int k = 0; k < disp_nz; ++k) vs[k] = h_vels[(size_t)k * ncol + (size_t)(r.column - 1)];
     int mmax = 0;
@@ -296,7 +314,7 @@ int Engine::dispersion_failure(int index, int* info, double* vals, float* table,
 
 int Engine::dispersion_copy_map(int from, int to, int n)
 {
-    if (!disp_ready || from < 0 || to < 0 || n < 0 || from + n > disp_nmaps || to + n > disp_nmaps) { fail(DSA_ERR_ARGUMENT, "dispersion: bad map copy"); return DSA_ERR_ARGUMENT; }
+    if (!disp_ready || from < 0 || to < 0 || n < 0 || from + n > disp_nmaps * disp_nmodels || to + n > disp_nmaps * disp_nmodels) { fail(DSA_ERR_ARGUMENT, "dispersion: bad map copy"); return DSA_ERR_ARGUMENT; }
     const size_t ncol = (size_t)disp_nx * disp_ny;
     HIP_TRY(this, hipSetDevice(device));
     if (n) HIP_TRY(this, hipMemcpyAsync(pvstore.p + (size_t)to * ncol, pvstore.p + (size_t)from * ncol, (size_t)n * ncol * 8, hipMemcpyDeviceToDevice, stream));
@@ -307,7 +325,7 @@ int Engine::dispersion_copy_map(int from, int to, int n)
 // host copies in the reference's per-type layouts: pv(ncol, nper), sen(ncol, nper, nz)
 int Engine::dispersion_fetch(int map_first, int nper, double* pv, int with_kernels, int sen_slot, double* svs, double* svp, double* srho)
 {
-    if (!disp_ready || nper < 0 || map_first < 0 || map_first + nper > disp_nmaps) { fail(DSA_ERR_ARGUMENT, "dispersion: bad fetch"); return DSA_ERR_ARGUMENT; }
+    if (!disp_ready || nper < 0 || map_first < 0 || map_first + nper > disp_nmaps * disp_nmodels || (with_kernels && disp_nmodels > 1)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad fetch"); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
     const size_t ncol = (size_t)disp_nx * disp_ny;
     if (pv && nper) HIP_TRY(this, hipMemcpy(pv, pvstore.p + (size_t)map_first * ncol, (size_t)nper * ncol * 8, hipMemcpyDeviceToHost));
@@ -328,7 +346,8 @@ int Engine::maps_from_dispersion(float goxd, float gozd, float dvxd, float dvzd,
     if (disp_nx < 4 || disp_ny < 4 || dicing < 1 || dicing > 16) { fail(DSA_ERR_ARGUMENT, "maps: bad arguments"); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
     make_grid(g, disp_nx, disp_ny, goxd, gozd, dvxd, dvzd, dicing);
-    const size_t n = (size_t)disp_nx * disp_ny * disp_nmaps;
+    const int nm = disp_nmaps * disp_nmodels;      // all models' maps, model-major
+    const size_t n = (size_t)disp_nx * disp_ny * nm;
     if (ensure(velv, n)) return status;
     launch_to_float(pvstore.p, velv.p, n, stream);
     std::vector<float> hv(n);
@@ -337,13 +356,14 @@ int Engine::maps_from_dispersion(float goxd, float gozd, float dvxd, float dvzd,
     hmin_slow = 1e30f;
     for (float v : hv) if (v > 0.0f && 1.0f / v < hmin_slow) hmin_slow = 1.0f / v;
     if (!(hmin_slow < 1e30f)) { fail(DSA_ERR_INTERNAL, "maps: no positive phase velocity came out of the dispersion stage"); return DSA_ERR_INTERNAL; }
-    mean_slowness_of_maps(hv.data(), (size_t)disp_nx * disp_ny, disp_nmaps);
-    return finish_maps(disp_nmaps);
+    mean_slowness_of_maps(hv.data(), (size_t)disp_nx * disp_ny, nm);
+    return finish_maps(nm);
 }
 
 int Engine::kernels_from_dispersion()
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "depth kernels: call dsa_dispersion_begin / run first"); return DSA_ERR_STATE; }
+    if (disp_nmodels > 1) { fail(DSA_ERR_STATE, "depth kernels: the dispersion stage holds %d models, depth kernels exist for one", disp_nmodels); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
     const size_t ncol = (size_t)disp_nx * disp_ny;
     if (ensure(Srow, ncol * disp_kmax_total * (disp_nz - 1))) return status;
@@ -1683,6 +1703,8 @@ int dsa_set_option(dsa_engine* e, const char* name, double value)
     if (n == "tie_tolerance" && value > 0) { en->tie_tolerance = (float)value; return 0; }
     if (n == "bundle_order" && (value == 0 || value == 1 || value == 2 || value == 3)) { en->bundle_order_opt = (int)value; return 0; }
     if (n == "tie_list" && (value == 0 || value == 1)) { en->tie_list_opt = (int)value; return 0; }
+    if (n == "forward_models_chunk" && value >= 0 && value <= (1 << 20)) { en->forward_models_chunk = (int)value; return 0; }
+    if (n == "forward_models_order" && (value == 0 || value == 1)) { en->forward_models_order = (int)value; return 0; }
     if (n == "disp_failure_log" && value >= 0 && value <= 65536) { en->disp_failure_log = (int)value; return 0; }
     if (n == "exact_heap_blocked" && (value == 0 || value == 1 || value == 2)) { en->exact_heap_blocked = (int)value; return 0; }
     if (n == "exact_lds_slots" && (value == 0 || (value >= 63 && value <= 4975))) { en->exact_lds_slots = (int)value; return 0; }
@@ -1749,6 +1771,12 @@ int dsa_dispersion_begin(dsa_engine* e, int nx, int ny, int nz, const float* vel
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->dispersion_begin(nx, ny, nz, vels, depz, minthk, kmax_total, nmaps_total);
+}
+
+int dsa_dispersion_begin_models(dsa_engine* e, int nx, int ny, int nz, int nmodels, const float* vels, const float* depz, float minthk, int nmaps_per_model)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->dispersion_begin(nx, ny, nz, vels, depz, minthk, nmaps_per_model, nmaps_per_model, nmodels);
 }
 
 int dsa_dispersion_run(dsa_engine* e, int iwave, int igr, int nper, const double* t, int with_kernels, int sen_slot, int map_first)
@@ -1872,6 +1900,16 @@ int dsa_dispersion_failure(const dsa_engine* e, int index, int* info, double* va
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<const Engine*>(e)->dispersion_failure(index, info, vals, table, c);
+}
+
+int dsa_dispersion_model_failures(const dsa_engine* e, int nmodels, long long* count)
+{
+    if (!e || !count) return DSA_ERR_ARGUMENT;
+    const Engine* en = reinterpret_cast<const Engine*>(e);
+    if (!en->disp_ready) return DSA_ERR_STATE;
+    if (nmodels != en->disp_nmodels) return DSA_ERR_ARGUMENT;
+    for (int m = 0; m < nmodels; ++m) count[m] = en->disp_model_fail[(size_t)m];
+    return 0;
 }
 
 int dsa_dispersion_diagnostics(const dsa_engine* e, long long* count, int* first, double* period)

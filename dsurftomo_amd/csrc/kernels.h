@@ -282,6 +282,8 @@ int disp_replay_failure(const LayerGeom& G, const float* vs, int pert, int iwave
                         int* mmax, float* table, double* cc_cm_c1, double* c);
 void launch_depth_kernels(const float* d_vels, int ncol, int nz, int kmax, const double* d_curves, int with_kernels, double* d_pv,
                           double* d_sen_vs, double* d_sen_vp, double* d_sen_rho, int kmax_total, int slot0, hipStream_t stream);
+// curves of a multi-model run, (period, model, column), into the model-major map store: map model * nmaps_per_model + map_first + period
+void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, int nmaps_per_model, int map_first, double* d_pv, hipStream_t stream);
 void launch_to_float(const double* d_in, float* d_out, size_t n, hipStream_t stream);
 
 }  // namespace dsa

@@ -49,6 +49,8 @@ def load_library():
     L.dsa_set_depth_kernels.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     L.dsa_solve_rows.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_dispersion_begin.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _i32, _i32]
+    L.dsa_dispersion_begin_models.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _i32]
+    L.dsa_dispersion_model_failures.argtypes = [_vp, _i32, _vp]
     L.dsa_dispersion_run.argtypes = [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32]
     L.dsa_dispersion_copy_maps.argtypes = [_vp, _i32, _i32, _i32]
     L.dsa_dispersion_fetch.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]
@@ -231,6 +233,21 @@ class Engine:
         self._disp = (nx, ny, nz)
         self._check(self._L.dsa_dispersion_begin(self._h, nx, ny, nz, _p(vels), _p(np.ascontiguousarray(depz, np.float32)),
                                                  float(minthk), int(kmax_total), int(nmaps_total)))
+
+    def dispersion_begin_models(self, vels, depz, minthk, nmaps_per_model):
+        """vels: (nmodels, nz, ny, nx) fp32 [Fortran vels(nx,ny,nz,nmodels)]: every dispersion_run afterwards computes all models in one
+        launch; the maps are model-major (global map = model * nmaps_per_model + m: dispersion_fetch, plan's map_index)"""
+        vels = np.ascontiguousarray(vels, np.float32)
+        nm, nz, ny, nx = vels.shape
+        self._disp = (nx, ny, nz)
+        self._check(self._L.dsa_dispersion_begin_models(self._h, nx, ny, nz, nm, _p(vels), _p(np.ascontiguousarray(depz, np.float32)),
+                                                        float(minthk), int(nmaps_per_model)))
+
+    def dispersion_model_failures(self, nmodels):
+        """dispersion curves without a root per model since dispersion_begin / dispersion_begin_models"""
+        out = np.zeros(int(nmodels), np.int64)
+        self._check(self._L.dsa_dispersion_model_failures(self._h, int(nmodels), out.ctypes.data_as(_vp)))
+        return out
 
     def dispersion_run(self, iwave, igr, t, kernels, sen_slot=0, map_first=0):
         t = np.ascontiguousarray(t, np.float64)

@@ -72,6 +72,15 @@ and the history name the pair of the smallest cv_rms (best) and the smoothest pa
 <input>CrossvalResiduals.dat lists, for the one_se pair, every datum's held-out and full-fit residual.  The calls hold whole pairs
 (crossval_chunk).  The inversion itself runs on with the input file's parameters: no other output changes.  Device-resident rows only (not with
 --host-rows); combines with the other analysis flags.
+
+--line-search A1,A2,... (finite, each >= 0; duplicates dropped, order kept) adds a step-length line search on the TRUE travel-time misfit to
+every outer iteration -- the reference applies every LSMR step at full length and never checks it.  After dsa_lsmr, candidate k is the model
+updated by dsa_model_update with float32(Ak) * dv (line_search_candidates); all candidates are forward-modelled in ONE dsa_forward_models call
+(times only) and scored by the rms of the weighted residual with this iteration's weights (line_search_scores: at Ak = 0
+the `rms` of the log line, bit for bit).  A candidate with a dispersion curve without a root is not eligible; the smallest score wins, ties to
+the first listed (line_search_select); the winner's model is the one the iteration leaves.  <input>LineSearch.dat lists per (iteration,
+candidate): iteration, alpha, weighted rms, plain rms, dispersion failures, chosen 0/1 (io.write_line_search / read_line_search).  --line-search 1
+writes the model files of a plain run, byte for byte.  Device-resident rows only (not with --host-rows); combines with the analysis flags.
 """
 import argparse
 import ctypes as C
@@ -597,12 +606,92 @@ def bootstrap_row_scales(ndata, m, nreal, seed):
     return s
 
 
+def parse_line_search(text):
+    """'A1,A2,...' -> the step lengths of --line-search: finite values >= 0, duplicates (as float32, which is what scales the update)
+    dropped, the order kept"""
+    try:
+        vals = [float(t) for t in str(text).split(",") if t.strip()]
+    except ValueError:
+        raise ValueError("--line-search takes comma-separated numbers (got %r)" % (text,))
+    if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
+        raise ValueError("--line-search takes at least one step length, every one finite and >= 0 (got %r)" % (text,))
+    out = []
+    for v in vals:
+        if float(np.float32(v)) not in [float(np.float32(u)) for u in out]:
+            out.append(v)
+    return out
+
+
+def _line_search_arg(text):
+    try:
+        return parse_line_search(text)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
+def line_search_candidates(lib, c, vsf, dv, alphas):
+    """the candidate models of a step: candidate k is a copy of vsf (nx, ny, nz; Fortran order) updated by dsa_model_update with
+    float32(alphas[k]) * dv -- on a copy of dv, which dsa_model_update clips in place.  Host only.  Returns a list of Fortran-ordered arrays."""
+    f = np.float32
+    out = []
+    for a in alphas:
+        step = np.ascontiguousarray(f(a) * np.asarray(dv, f), f)
+        cand = np.asfortranarray(np.array(vsf, f, copy=True))
+        if lib.dsa_model_update(c["nx"], c["ny"], c["nz"], _p(step), _p(cand), c["minvel"], c["maxvel"]) != 0:
+            raise RuntimeError("dsa_model_update failed")
+        out.append(cand)
+    return out
+
+
+def line_search_scores(obst, dsyn, datweight):
+    """per candidate (rows of dsyn): the rms of the weighted residual float32(w_i * r_i), r = obst - dsyn_k in float32, summed in float64 --
+    the data term LSMR has just minimised, evaluated as the `rms` of the iteration's log line (so that step 0 reproduces it exactly) --
+    and the rms of the plain residual.  Returns (weighted (K,), plain (K,)) float64."""
+    f = np.float32
+    obst = np.asarray(obst, f); w = np.asarray(datweight, f)
+    dsyn = np.asarray(dsyn, f).reshape(-1, obst.size)
+    dall = obst.size
+    wr, pr = [], []
+    for row in dsyn:
+        r = (obst - row).astype(f)
+        wr.append(float(f(np.sqrt(((w * r).astype(f).astype(np.float64) ** 2).sum()) / np.sqrt(dall))))
+        pr.append(float(f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))))
+    return np.array(wr), np.array(pr)
+
+
+def line_search_select(scores, failures):
+    """index of the winning candidate: the smallest score among the candidates without a dispersion failure (and with a finite score);
+    ties go to the candidate listed first.  Raises when no candidate is eligible."""
+    best = None
+    for k, (sc, nf) in enumerate(zip(scores, failures)):
+        if nf != 0 or not np.isfinite(sc):
+            continue
+        if best is None or sc < scores[best]:
+            best = k
+    if best is None:
+        raise RuntimeError("line search: no candidate is eligible (every one has a dispersion curve without a root or no finite misfit)")
+    return best
+
+
+def line_search_step(lib, c, vsf, dv, obst, datweight, alphas):
+    """the step-length line search of one outer iteration: every candidate of line_search_candidates through ONE dsa_forward_models call
+    (CalSurfG's grid), scored by line_search_scores, the winner picked by line_search_select.  Returns dict(alphas, weighted_rms, rms,
+    failures, chosen, models, dsyn (K, ndata), seconds)."""
+    cands = line_search_candidates(lib, c, vsf, dv, alphas)
+    t0 = time.perf_counter()
+    dsyn, fails = io.call_forward_models(c, cands, 8, lib=lib)
+    dt = time.perf_counter() - t0
+    wr, pr = line_search_scores(obst, dsyn, datweight)
+    k = line_search_select(wr, fails)
+    return dict(alphas=[float(a) for a in alphas], weighted_rms=wr, rms=pr, failures=[int(v) for v in fails], chosen=k, models=cands, dsyn=dsyn, seconds=dt)
+
+
 def write_residuals(path, c, dsyn, obst, datweight):
     """list-directed rows: dist, dsyn, obst, dsyn*w, obst*w, w (main.f90:397-403)"""
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
-def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None, crossval=None):
+def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None, crossval=None, line_search=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
     both orderings in place, dsa_lsmr solves.  Same numbers as iteration() (tests/test_gpu_lsmr.py compares every bit).
@@ -615,7 +704,9 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     data rows (returned as "voronoi" from lsmr_voronoi_ensemble); with update, float32 of its mean is the update applied to vsf and
     returned as "dv" (dv_min / dv_max are its), dsa_lsmr's own stays in "dv_lsmr".
     crossval = dict(weights=[...], damps=[...], fold=(ndata,) int32, nfolds, chunk=int or None, want_x=bool): after dsa_lsmr, the K-fold
-    cross-validation of the same system (returned as "crossval" from lsmr_crossval_sweep)."""
+    cross-validation of the same system (returned as "crossval" from lsmr_crossval_sweep).
+    line_search = [A1, A2, ...]: the update is applied at the step length among these whose model has the smallest true misfit
+    (line_search_step, returned as "line_search"); "dv" stays the full-length update."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -676,10 +767,17 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
     rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))
     dv_raw = (f(dv.min()), f(dv.max()))
-    lib.dsa_model_update(nx, ny, nz, _p(dv), _p(vsf), c["minvel"], c["maxvel"])
+    ls = None
+    if line_search:
+        ls = line_search_step(lib, c, vsf, dv, obst, datweight, line_search)
+        vsf[...] = ls["models"][ls["chosen"]]
+    else:
+        lib.dsa_model_update(nx, ny, nz, _p(dv), _p(vsf), c["minvel"], c["maxvel"])
     out = dict(dsyn=dsyn, datweight=datweight, mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(dv_raw[0]),
                dv_max=float(dv_raw[1]), itn=ii[1].value, istop=ii[0].value, nar=nar2.value, m=m.value, dws=(float(dws[0]), float(dws[1])),
                seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), dv=dv, norm=norm, cbst=cbst)
+    if ls is not None:
+        out["line_search"] = ls
     if boot is not None:
         out["boot"] = boot
     if res is not None:
@@ -931,6 +1029,17 @@ def check_bootstrap(bootstrap, host_rows):
         raise ValueError("--bootstrap solves on the device-resident system: it cannot be combined with --host-rows")
 
 
+def check_line_search(alphas, host_rows):
+    """the line search's preconditions, checked before anything touches the GPU (alphas None: no line search)"""
+    if alphas is None:
+        return
+    alphas = list(alphas)
+    if not alphas or not all(np.isfinite(a) and a >= 0 for a in alphas):
+        raise ValueError("--line-search takes at least one step length, every one finite and >= 0 (got %r)" % (alphas,))
+    if host_rows:
+        raise ValueError("--line-search forward-models its candidates beside the device-resident system: it cannot be combined with --host-rows")
+
+
 def check_resolution(resolution, checkerboards, host_rows, chunk=None):
     """the resolution tests' preconditions, checked before anything touches the GPU"""
     for cell in checkerboards or ():
@@ -1026,8 +1135,9 @@ def _solve_text(h):
 def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1, resolution=False, checkerboard=(),
         resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None, voronoi=None, voronoi_seed=1,
         voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None, crossval=None, crossval_weights=None, crossval_damps=None,
-        crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None):
+        crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None, line_search=None):
     check_bootstrap(bootstrap, host_rows)
+    check_line_search(line_search, host_rows)
     check_crossval(crossval, crossval_weights, crossval_damps, crossval_by, crossval_iter, host_rows, maxiter, crossval_chunk)
     check_voronoi(voronoi, voronoi_update, host_rows, voronoi_zscale, voronoi_damp, None, voronoi_chunk)
     check_resolution(resolution, checkerboard, host_rows, resolution_chunk)
@@ -1057,6 +1167,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         obst = (obst * (np.float32(1.0) + c["noiselevel"] * g)).astype(np.float32)
     name = os.path.join(out_dir, "DSurfTomo.in")
     history = []
+    ls_rows = []
     for it in range(1, maxiter + 1):
         if host_rows:
             st = iteration(lib, c, vsf, obst, log)
@@ -1068,7 +1179,8 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                            chunk=voronoi_chunk, update=voronoi_update)
             st = iteration_device(lib, c, vsf, obst, log, (bootstrap, bootstrap_seed) if bootstrap and last else None,
                                   dict(psf=resolution, chunk=resolution_chunk, cells=cells) if (resolution or cells) and last else None,
-                                  sweep if it == tradeoff_iter else None, vor, cvrun if it == crossval_iter else None)
+                                  sweep if it == tradeoff_iter else None, vor, cvrun if it == crossval_iter else None,
+                                  list(line_search) if line_search is not None else None)
         log("%2dth iteration..." % it)
         log(" mean,std_devs and rms of residual after weighting: %8.1fms %8.2fms %8.3f" % (st["mean_ms"], st["std_ms"], st["rms"]))
         log(" min and max velocity variation %7.4f%7.4f" % (st["dv_min"], st["dv_max"]))
@@ -1079,7 +1191,19 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr", "crossval")}
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr", "crossval", "line_search")}
+        if "line_search" in st:
+            ls = st["line_search"]
+            k = ls["chosen"]
+            for q, a in enumerate(ls["alphas"]):
+                ls_rows.append(dict(iteration=it, alpha=a, weighted_rms=float(ls["weighted_rms"][q]), rms=float(ls["rms"][q]),
+                                    disp_failures=ls["failures"][q], chosen=int(q == k)))
+            io.write_line_search(name + "LineSearch.dat", ls_rows)
+            h["line_search"] = dict(alphas=ls["alphas"], weighted_rms=[float(v) for v in ls["weighted_rms"]], rms=[float(v) for v in ls["rms"]],
+                                    failures=ls["failures"], chosen=k, alpha=ls["alphas"][k], seconds=ls["seconds"])
+            log(" line search: step %g of %s taken, rms of the weighted residual %s -> %.6g (%d candidates in one forward call, %.3f s)" %
+                (ls["alphas"][k], ",".join("%g" % a for a in ls["alphas"]), " ".join("%.6g" % v for v in ls["weighted_rms"]), ls["weighted_rms"][k],
+                 len(ls["alphas"]), ls["seconds"]))
         if "boot" in st:
             b = st["boot"]
             write_std(name + "Std.dat", c, b["std"])
@@ -1200,9 +1324,14 @@ def main(argv=None):
                          "surface-wave data (default datum)")
     ap.add_argument("--crossval-seed", type=int, default=1, metavar="S", help="seed of the folds (default 1)")
     ap.add_argument("--crossval-iter", type=int, default=1, metavar="N", help="the outer iteration whose step is cross-validated, 1..maxiter (default 1)")
+    ap.add_argument("--line-search", type=_line_search_arg, default=None, metavar="A1,A2,...",
+                    help="step-length line search: in every outer iteration the update is tried at these fractions of its length (each >= 0; 0 keeps "
+                         "the model), all candidate models are forward-modelled in one call, and the one with the smallest rms of the weighted "
+                         "travel-time residual is applied: <input>LineSearch.dat, one row per (iteration, step)")
     args = ap.parse_args(argv)
     try:
         check_bootstrap(args.bootstrap, args.host_rows)
+        check_line_search(args.line_search, args.host_rows)
         check_crossval(args.crossval, args.crossval_weights, args.crossval_damps, args.crossval_by, args.crossval_iter, args.host_rows, args.maxiter)
         check_voronoi(args.voronoi, args.voronoi_update, args.host_rows, args.voronoi_zscale, args.voronoi_damp)
         check_resolution(args.resolution, args.checkerboard, args.host_rows)
@@ -1214,7 +1343,8 @@ def main(argv=None):
         resolution=args.resolution, checkerboard=args.checkerboard, tradeoff_weights=args.tradeoff_weights, tradeoff_damps=args.tradeoff_damps,
         tradeoff_iter=args.tradeoff_iter, voronoi=args.voronoi, voronoi_seed=args.voronoi_seed, voronoi_zscale=args.voronoi_zscale,
         voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update, crossval=args.crossval, crossval_weights=args.crossval_weights,
-        crossval_damps=args.crossval_damps, crossval_by=args.crossval_by, crossval_seed=args.crossval_seed, crossval_iter=args.crossval_iter)
+        crossval_damps=args.crossval_damps, crossval_by=args.crossval_by, crossval_seed=args.crossval_seed, crossval_iter=args.crossval_iter,
+        line_search=args.line_search)
     return 0
 
 

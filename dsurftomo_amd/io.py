@@ -168,6 +168,57 @@ def call_synthetic(c, noiselevel=0.0):
     return obst
 
 
+def call_forward_models(c, models, dicing=8, ldd=None, lib=None):
+    """dsa_forward_models on a loaded case: `models` is a sequence of K Vs models shaped like c["vels"] (nx, ny, nz).  Times only.
+    Returns (dsurf (K, ldd) float32 -- row k holds model k's receiver times in the reference's data order, entries from ndata on are
+    left 0 --, failures (K,) int64: dispersion curves without a root per model).  dicing 8: dsa_calsurfg's times, 5: dsa_synthetic's."""
+    if lib is None:
+        from .engine import load_library
+        lib = load_library()
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    K = len(models)
+    vels = np.zeros((K, nz, ny, nx), np.float32)                 # C order of Fortran vels(nx, ny, nz, K)
+    for k, m in enumerate(models):
+        m = np.asarray(m, np.float32)
+        if m.shape != (nx, ny, nz):
+            raise ValueError("model %d has shape %r, expected %r" % (k, m.shape, (nx, ny, nz)))
+        vels[k] = m.transpose(2, 1, 0)
+    ldd = c["ndata"] if ldd is None else int(ldd)
+    dsurf = np.zeros((K, max(ldd, 1)), np.float32)
+    fails = np.zeros(max(K, 1), np.int64)
+    i32 = lambda v: C.byref(C.c_int(int(v)))
+    _, tail = _args(c)
+    rc = lib.dsa_forward_models(i32(nx), i32(ny), i32(nz), i32(K), _ptr(vels), _ptr(dsurf), i32(ldd), i32(dicing), _ptr(fails), *tail)
+    if rc != 0:
+        raise RuntimeError("dsa_forward_models: %s" % lib.dsa_dropin_error().decode())
+    return dsurf[:, :ldd], fails[:K]
+
+
+LINE_SEARCH_COLUMNS = ("iteration", "alpha", "weighted_rms", "rms", "disp_failures", "chosen")
+
+
+def write_line_search(path, rows):
+    """<input>LineSearch.dat: one row per (iteration, candidate) -- iteration, alpha, rms of the weighted residual (the score), rms of the
+    plain residual, dispersion curves without a root, chosen 0/1.  rows: dicts with the keys LINE_SEARCH_COLUMNS.  The floating-point
+    columns are written with 17 significant digits, so that read_line_search returns them bit for bit."""
+    with open(path, "w") as fh:
+        fh.write("# " + " ".join(LINE_SEARCH_COLUMNS) + "\n")
+        for r in rows:
+            fh.write("%4d %.17g %.17g %.17g %d %d\n" % (r["iteration"], r["alpha"], r["weighted_rms"], r["rms"], r["disp_failures"], int(bool(r["chosen"]))))
+
+
+def read_line_search(path):
+    """the rows write_line_search wrote, as a list of dicts"""
+    rows = []
+    with open(path) as fh:
+        for line in fh:
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            rows.append(dict(iteration=int(t[0]), alpha=float(t[1]), weighted_rms=float(t[2]), rms=float(t[3]), disp_failures=int(t[4]), chosen=int(t[5])))
+    return rows
+
+
 def write_raypaths(path, paths):
     """raypath.out as the reference's (disabled) dump writes it and its scripts/plotpath.py reads it
     (CalSurfG.f90:2276-2283): '# nrp', then nrp lines 'latitude longitude' in degrees.  paths: Engine.ray_paths()."""

@@ -107,6 +107,8 @@ int dsa_set_memory_budget(dsa_engine* e, size_t bytes);
  *     rows_on_device           [0]     1 = dsa_solve_rows leaves the COO rows on the device (dsa_iteration_system_device, dsa_lsmr)
  *     disp_layers_lds          [-1]    layer tables of the dispersion kernel: 1 LDS | 0 global scratch | -1 LDS when they fit
  *     disp_group_shift         [-1]    lanes per dispersion curve = 2^shift, 0 .. 3; -1 = 8 lanes up to 4096 curves, 4 up to 32768, else 1
+ *     forward_models_chunk     [0]     dsa_forward_models: models per pass; 0 = as many as the memory budget holds maps for (same results)
+ *     forward_models_order     [0]     dsa_forward_models: unit order, 0 model-major | 1 period-major (A/B switch; same results under exact_ties = 2)
  *     disp_failure_log         [0]     keep the first N curves without a root in the reference's call order (dsa_dispersion_failure)
  *     lsmr_device_vectors      [0]     dsa_lsmr: 0 ordered reductions on the host | 1 all vectors on the device (same results)
  *
@@ -164,6 +166,22 @@ int dsa_dispersion_fetch(dsa_engine* e, int map_first, int nper, double* pv, int
                          int sen_slot, double* sen_vs, double* sen_vp, double* sen_rho);
 int dsa_maps_from_dispersion(dsa_engine* e, float goxd, float gozd, float dvxd, float dvzd, int dicing);
 int dsa_kernels_from_dispersion(dsa_engine* e);
+
+/* The dispersion stage with a model dimension: `nmodels` Vs models vels(nx,ny,nz,nmodels), model slowest, on one set of depths.
+ *   begin_models: room for nmaps_per_model maps per model.  The store is model-major: global map = model * nmaps_per_model + m.
+ *   dsa_dispersion_run(iwave, igr, nper, t, 0, 0, map_first) afterwards computes the curves of ALL models in one launch (the models
+ *          are further columns of the kernel: the lanes-per-curve choice of option disp_group_shift is made on nx*ny*nmodels curves)
+ *          and writes maps [model * nmaps_per_model + map_first, .. + nper) of every model.
+ *   dsa_dispersion_fetch / dsa_dispersion_copy_maps take global map indices; dsa_maps_from_dispersion hands all
+ *          nmodels * nmaps_per_model maps to the solve (dsa_plan_units' map_index is the global one).
+ * Model k's maps are bit-identical to dsa_dispersion_begin + run + fetch on model k alone, whatever the group width.  nmodels = 1 IS
+ * dsa_dispersion_begin with kmax_total = nmaps_total = nmaps_per_model, depth kernels included.  Depth kernels exist for one model only:
+ * with_kernels = 1 (run or fetch) with nmodels > 1 returns DSA_ERR_ARGUMENT, dsa_kernels_from_dispersion DSA_ERR_STATE.
+ * dsa_dispersion_diagnostics counts over all models, its column field being model * nx*ny + column (1-based);
+ * model_failures: curves without a root per model since begin (nmodels must be the begin's). */
+int dsa_dispersion_begin_models(dsa_engine* e, int nx, int ny, int nz, int nmodels, const float* vels, const float* depz,
+                                float minthk, int nmaps_per_model);
+int dsa_dispersion_model_failures(const dsa_engine* e, int nmodels, long long* count);
 
 /* Solve every planned unit: eikonal field per unit, then receiver times into dsurf (host,
  * one float per datum, unit-major order == the reference's (knumi, srcnum, istep) order). */
@@ -441,6 +459,32 @@ int dsa_synthetic(const int* nx, const int* ny, const int* nz, const int* nparpi
                   const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
                   const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
                   const int* nsrcsurf, const int* nrcf, const float* noiselevel);
+
+/* Forward-model `nmodels` Vs models vels(nx,ny,nz,nmodels), model slowest, in ONE call: times only, no rays, no rows (extension; the
+ * reference has no such entry).  goxdf .. nrcf are the arguments of dsa_synthetic between obst and noiselevel, with the same meaning.
+ * Column k of dsurf(ldd, nmodels) receives model k's receiver times in the reference's data order; rows beyond the data are left alone.
+ *   dicing = 8: the times dsa_calsurfg returns in dsurf for that model (CalSurfG's grid, the phase velocities at the group periods
+ *               written over the head of the phase-velocity maps as there);
+ *   dicing = 5: the times dsa_synthetic returns with noiselevel 0.
+ * Under exact_ties = 2 column k is bit-identical to the single-model call; in the default mode every time is within tie_tolerance
+ * (1e-4 s) of it -- the units of a source bundle across models, so a unit's fixed point may run beside other members than alone.
+ * All models go through the dispersion stage in one launch per wave type (dsa_dispersion_begin_models) and through the eikonal solves
+ * as one unit list, model-major (option forward_models_order).  When the maps of all models do not fit the memory budget the models
+ * are processed in passes (option forward_models_chunk; the results do not depend on the split; the pass that holds model 0 runs last).
+ * disp_failures (may be NULL) receives the curves without a root per model.  dsa_dropin_tie_diagnostics / _tie_census afterwards sum
+ * over all units of the call, dsa_dropin_velocity_maps serves model 0's maps, dsa_dropin_diagnostics the dispersion counts over all
+ * models (no rays: rbint_notes 0).
+ * DSA_ERR_ARGUMENT: nmodels < 1, ldd below the number of data, dicing not 5 or 8, a null pointer.  DSA_ERR_STATE: more than one engine
+ * in the pool (DSA_DEVICES): models are not sharded over GPUs.  After a failure the engine is as usable as after a failed dsa_synthetic. */
+int dsa_forward_models(const int* nx, const int* ny, const int* nz, const int* nmodels, const float* vels,
+                       float* dsurf, const int* ldd, const int* dicing, long long* disp_failures,
+                       const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                       const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                       const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                       const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                       const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                       const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                       const int* nsrcsurf, const int* nrcf);
 
 /* Capacity (entries) of the rw / iw(2:) / col arrays handed to dsa_calsurfg from now on.  The reference's interface
  * (CalSurfG.f90:939-943) does not carry it -- main.f90:287 sizes the arrays as spfra*dall*nx*ny*nz and only checks
