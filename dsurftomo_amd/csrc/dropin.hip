@@ -16,6 +16,7 @@
 
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
+#include "spmv_state.h"
 
 namespace {
 
@@ -157,6 +158,192 @@ void remember(const Layout& L, int ncol, bool clobbered)
     g_last_count[0] = L.kRc; g_last_count[1] = L.kRg; g_last_count[2] = L.kLc; g_last_count[3] = L.kLg;
     g_last_ncol = ncol;
 }
+
+// What dsa_forward_models and dsa_forward_steps share: the passes over the models, the dispersion sequence, the unit lists, the tie
+// bookkeeping.  The two differ at the ends of a pass.  Models: `vels` is uploaded, the times come back to the host.  Steps: the models of
+// the pass are built on the device in the dispersion stage's layout (k_step_models), the times stay there (dsa_solve_device), the misfit
+// sums are reduced from them (k_misfit_sums), and only what the caller asked for returns.
+struct Forward {
+    const char* who;
+    int nx, ny, nz, K, dicing, ldd;
+    const float* vels = nullptr;         // dsa_forward_models: K models, model slowest
+    bool steps_mode = false;             // dsa_forward_steps
+    const float* vsf = nullptr; const float* steps = nullptr; const float* alpha = nullptr;
+    float minvel = 0.0f, maxvel = 0.0f;
+    float* models_out = nullptr;
+    const float* obst = nullptr; const float* datweight = nullptr; const int* group = nullptr;
+    int ngroups = 1;
+    double* measures = nullptr;
+    float* dsurf = nullptr;
+    long long* disp_failures = nullptr;
+    float goxdf, gozdf, dvxdf, dvzdf, minthk;
+    const double* tRc; const double* tRg; const double* tLc; const double* tLg;
+    const float* depz;
+};
+
+#define FWD_HIP(call) do { if ((call) != hipSuccess) { g_dropin_error = std::string(F.who) + ": " #call " failed"; return DSA_ERR_DEVICE; } } while (0)
+
+int forward_passes(dsa_engine* e, const Forward& F, const Layout& L, const Units& U)
+{
+    dsa::Engine* en = reinterpret_cast<dsa::Engine*>(e);
+    const std::string who = F.who;
+    const bool cal = F.dicing == 8;
+    int rc = 0;
+    const int K = F.K, nu = (int)U.map.size(), nmaps = std::max(L.nmaps, 1);
+    const size_t ncol = (size_t)F.nx * F.ny, nd = (size_t)U.ndata;
+    const size_t nn = ncol * (size_t)F.nz, nunk = (size_t)(F.nx - 2) * (size_t)(F.ny - 2) * (size_t)(F.nz - 1);
+    tie_reset();
+    g_rbint_notes = 0; g_disp_count = 0; g_disp_period = 0.0;
+    for (int q = 0; q < 5; ++q) g_disp_first[q] = 0;
+    if (F.disp_failures) for (int m = 0; m < K; ++m) F.disp_failures[m] = 0;
+
+    // models per pass: the option, or what the budget holds maps for -- a map costs its vertex values (fp64 store, fp32 copy), its
+    // diced nodes and two copies of its tiled slowness (the bundles read a member-minor one, whose byte offsets are 32-bit)
+    int per_pass = en->forward_models_chunk > 0 ? std::min(en->forward_models_chunk, K) : K;
+    if (en->forward_models_chunk == 0 && F.nx >= 4 && F.ny >= 4) {
+        dsa::GridDesc gd{};
+        dsa::make_grid(gd, F.nx, F.ny, F.goxdf, F.gozdf, F.dvxdf, F.dvzdf, F.dicing);
+        const size_t nrec_c = (size_t)gd.nbx * gd.nbz * dsa::kTileRecs;
+        const size_t per_map = ncol * 12 + (size_t)gd.nnx * gd.nnz * 4 + nrec_c * 8;
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(en->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { g_dropin_error = who + ": no memory information from the device"; return DSA_ERR_DEVICE; }
+        const size_t budget = en->mem_budget ? en->mem_budget : (size_t)(0.6 * (double)free_b);
+        size_t maps = std::max<size_t>((size_t)(0.25 * (double)budget) / per_map, 1);
+        maps = std::min<size_t>(maps, (((size_t)1 << 32) - 1) / (nrec_c * 4));
+        per_pass = (int)std::min<size_t>((size_t)K, std::max<size_t>(maps / (size_t)nmaps, 1));
+    }
+
+    std::vector<int> m_map, m_nrec, m_mode, m_data;
+    std::vector<float> m_sx, m_sz, m_rx, m_rz, times;
+    std::vector<size_t> ray0((size_t)nu + 1, 0);
+    for (int u = 0; u < nu; ++u) ray0[(size_t)u + 1] = ray0[(size_t)u] + (size_t)U.nrec[(size_t)u];
+    std::vector<long long> fails;
+    long long disp_count = 0;
+    const bool meas = F.steps_mode && F.measures;
+    const int* d_group = nullptr;
+    if (F.steps_mode) {
+        // what every pass reads: the base model and the factors; for the sums, obst, the weights, the group and the unit of every datum
+        FWD_HIP(hipSetDevice(en->device));
+        if (en->ensure(en->fs_vsf, nn) || (F.alpha && en->ensure(en->fs_alpha, (size_t)K))) return fail(en->status);
+        FWD_HIP(hipMemcpyAsync(en->fs_vsf.p, F.vsf, nn * 4, hipMemcpyHostToDevice, en->stream));
+        if (F.alpha) FWD_HIP(hipMemcpyAsync(en->fs_alpha.p, F.alpha, (size_t)K * 4, hipMemcpyHostToDevice, en->stream));
+        if (meas) {
+            std::vector<int> idx(std::max<size_t>(3 * nd, 1), 0);
+            for (int u = 0; u < nu; ++u)
+                for (int r = 0; r < U.nrec[(size_t)u]; ++r) { idx[(size_t)U.data[(size_t)u] + r] = U.data[(size_t)u]; idx[nd + (size_t)U.data[(size_t)u] + r] = U.nrec[(size_t)u]; }
+            if (F.group) std::memcpy(idx.data() + 2 * nd, F.group, nd * 4);
+            if (en->ensure(en->fs_obs, std::max<size_t>(2 * nd, 1)) || en->ensure(en->fs_idx, idx.size()) || en->ensure(en->fs_meas, (size_t)per_pass * F.ngroups * 2)) return fail(en->status);
+            if (nd) {
+                FWD_HIP(hipMemcpyAsync(en->fs_obs.p, F.obst, nd * 4, hipMemcpyHostToDevice, en->stream));
+                if (F.datweight) FWD_HIP(hipMemcpyAsync(en->fs_obs.p + nd, F.datweight, nd * 4, hipMemcpyHostToDevice, en->stream));
+            }
+            FWD_HIP(hipMemcpyAsync(en->fs_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, en->stream));
+            FWD_HIP(hipStreamSynchronize(en->stream));       // (idx leaves scope)
+            if (F.group) d_group = en->fs_idx.p + 2 * nd;
+        }
+    }
+    // the passes run from the last models to the first, so that the store is left with model 0's maps at its head (dsa_dropin_velocity_maps)
+    const int npass = (K + per_pass - 1) / per_pass;
+    for (int pass = npass - 1; pass >= 0; --pass) {
+        const int m0 = pass * per_pass, nm = std::min(per_pass, K - m0);
+        if (!F.steps_mode) {
+            if ((rc = dsa_dispersion_begin_models(e, F.nx, F.ny, F.nz, nm, F.vels + (size_t)m0 * ncol * (size_t)F.nz, F.depz, F.minthk, nmaps)) != 0) return fail(rc);
+        } else {
+            // the pass's models, written where dsa_dispersion_begin_models would have uploaded them
+            if ((rc = en->dispersion_setup(F.nx, F.ny, F.nz, F.depz, F.minthk, nmaps, nmaps, nm)) != 0) return fail(rc);
+            if (F.steps) {
+                if (en->ensure(en->fs_steps, nunk * (size_t)nm)) return fail(en->status);
+                FWD_HIP(hipMemcpyAsync(en->fs_steps.p, F.steps + (size_t)m0 * nunk, nunk * (size_t)nm * 4, hipMemcpyHostToDevice, en->stream));
+            }
+            dsa::launch_step_models(F.nx, F.ny, F.nz, nm, m0, en->fs_vsf.p, F.steps ? en->fs_steps.p : nullptr, F.steps ? nullptr : en->spmv->bx.p, (int)nunk,
+                                    F.alpha ? en->fs_alpha.p : nullptr, F.minvel, F.maxvel, en->vels_d.p, (size_t)nm * ncol, ncol, en->stream);
+            if (F.models_out)       // (depth, model, column) -> model slowest: per depth, nm rows of ncol floats
+                for (int k = 0; k < F.nz; ++k)
+                    FWD_HIP(hipMemcpy2DAsync(F.models_out + (size_t)m0 * nn + (size_t)k * ncol, nn * 4, en->vels_d.p + (size_t)k * nm * ncol, ncol * 4, ncol * 4, (size_t)nm,
+                                             hipMemcpyDeviceToHost, en->stream));
+            if ((rc = en->dispersion_commit(true)) != 0) return fail(rc);
+        }
+        if (cal) {
+            // CalSurfG.f90:1100-1140 without the depth kernels: the phase velocities at the group periods overwrite the head of the phase block
+            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, F.tRc, 0, 0, L.oRc)) != 0) return fail(rc);
+            if (L.kRg > 0) {
+                if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, F.tRg, 0, 0, L.oRg)) != 0) return fail(rc);
+                if ((rc = dsa_dispersion_run(e, 2, 0, L.kRg, F.tRg, 0, 0, L.oRc)) != 0) return fail(rc);
+            }
+            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, F.tLc, 0, 0, L.oLc)) != 0) return fail(rc);
+            if (L.kLg > 0) {
+                if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, F.tLg, 0, 0, L.oLg)) != 0) return fail(rc);
+                if ((rc = dsa_dispersion_run(e, 1, 0, L.kLg, F.tLg, 0, 0, L.oLc)) != 0) return fail(rc);
+            }
+        } else {
+            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, F.tRc, 0, 0, L.oRc)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, F.tRg, 0, 0, L.oRg)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, F.tLc, 0, 0, L.oLc)) != 0) return fail(rc);
+            if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, F.tLg, 0, 0, L.oLg)) != 0) return fail(rc);
+        }
+        if ((rc = dsa_maps_from_dispersion(e, F.goxdf, F.gozdf, F.dvxdf, F.dvzdf, F.dicing)) != 0) return fail(rc);
+        remember(L, F.nx * F.ny, cal);
+        fails.assign((size_t)nm, 0);
+        if ((rc = dsa_dispersion_model_failures(e, nm, fails.data())) != 0) return fail(rc);
+        for (int m = 0; m < nm; ++m) { disp_count += fails[(size_t)m]; if (F.disp_failures) F.disp_failures[m0 + m] = fails[(size_t)m]; }
+        {   // (the first failing curve reported is that of the lowest pass that had one: the passes run downwards, so a later pass overwrites)
+            long long c = 0; int first[5]; double period = 0.0;
+            if (dsa_dispersion_diagnostics(e, &c, first, &period) == 0 && c > 0) {
+                for (int q = 0; q < 5; ++q) g_disp_first[q] = first[q];
+                g_disp_first[2] += m0 * (int)ncol;
+                g_disp_period = period;
+            }
+        }
+        // the pass's units: every model's copy of the call's unit list on its own maps, data in its own column.  Model-major keeps the
+        // periods of a (model, source) consecutive: a bundle's members then read neighbouring maps of the member-minor slowness
+        const size_t n = (size_t)nu * nm;
+        m_map.resize(n); m_nrec.resize(n); m_mode.resize(n); m_data.resize(n); m_sx.resize(n); m_sz.resize(n);
+        m_rx.clear(); m_rz.clear();
+        m_rx.reserve(ray0[(size_t)nu] * nm); m_rz.reserve(ray0[(size_t)nu] * nm);
+        size_t q = 0;
+        auto put = [&](int m, int u) {
+            m_map[q] = m * nmaps + U.map[(size_t)u]; m_nrec[q] = U.nrec[(size_t)u]; m_mode[q] = U.mode[(size_t)u];
+            // (plan wants the data indices non-decreasing in unit order: model-major a column per model, period-major the models of a unit side by side)
+            m_data[q] = en->forward_models_order == 0 ? (int)((size_t)m * nd) + U.data[(size_t)u] : (int)((size_t)nm * (size_t)U.data[(size_t)u] + (size_t)m * (size_t)U.nrec[(size_t)u]);
+            m_sx[q] = U.sx[(size_t)u]; m_sz[q] = U.sz[(size_t)u];
+            m_rx.insert(m_rx.end(), U.rx.begin() + (long)ray0[(size_t)u], U.rx.begin() + (long)ray0[(size_t)u + 1]);
+            m_rz.insert(m_rz.end(), U.rz.begin() + (long)ray0[(size_t)u], U.rz.begin() + (long)ray0[(size_t)u + 1]);
+            ++q;
+        };
+        if (en->forward_models_order == 0) { for (int m = 0; m < nm; ++m) for (int u = 0; u < nu; ++u) put(m, u); }
+        else { for (int u = 0; u < nu; ++u) for (int m = 0; m < nm; ++m) put(m, u); }
+        if ((unsigned long long)nd * (unsigned long long)nm > (unsigned long long)INT_MAX) { g_dropin_error = who + ": more than 2^31-1 data in a pass (set option forward_models_chunk)"; return DSA_ERR_ARGUMENT; }
+        if ((rc = dsa_plan_units(e, (int)n, m_map.data(), m_sx.data(), m_sz.data(), m_nrec.data(), m_rx.data(), m_rz.data(), m_mode.data(), nullptr, m_data.data())) != 0) return fail(rc);
+        if (!F.steps_mode) {
+            times.assign(std::max<size_t>(nd * nm, 1), 0.0f);
+            if ((rc = dsa_solve(e, times.data())) != 0) return fail(rc);
+        } else {
+            // the times stay on the device; the sums are taken there, and the times come back only for a caller who wants dsurf
+            if (en->ensure(en->fs_times, std::max<size_t>(nd * nm, 1))) return fail(en->status);
+            if ((rc = dsa_solve_device(e, en->fs_times.p)) != 0) return fail(rc);
+            if (meas) {
+                dsa::launch_misfit_sums(en->fs_times.p, en->forward_models_order, nm, (int)nd, en->fs_idx.p, en->fs_idx.p + nd, en->fs_obs.p,
+                                        F.datweight ? en->fs_obs.p + nd : nullptr, d_group, F.ngroups, en->fs_meas.p, en->stream);
+                FWD_HIP(hipGetLastError());
+                FWD_HIP(hipMemcpyAsync(F.measures + (size_t)m0 * F.ngroups * 2, en->fs_meas.p, (size_t)nm * F.ngroups * 2 * 8, hipMemcpyDeviceToHost, en->stream));
+            }
+            if (F.dsurf && nd) {
+                times.resize(nd * nm);
+                FWD_HIP(hipMemcpyAsync(times.data(), en->fs_times.p, nd * nm * 4, hipMemcpyDeviceToHost, en->stream));
+            }
+            FWD_HIP(hipStreamSynchronize(en->stream));
+        }
+        tie_collect(e);
+        if (F.dsurf)
+            for (size_t k = 0; k < n; ++k) {
+                const int u = en->forward_models_order == 0 ? (int)(k % (size_t)nu) : (int)(k / (size_t)nm), m = en->forward_models_order == 0 ? (int)(k / (size_t)nu) : (int)(k % (size_t)nm);
+                if (U.nrec[(size_t)u]) std::memcpy(F.dsurf + (size_t)(m0 + m) * (size_t)F.ldd + (size_t)U.data[(size_t)u], times.data() + (size_t)m_data[k], (size_t)U.nrec[(size_t)u] * 4);
+            }
+    }
+    g_disp_count = disp_count;
+    return 0;
+}
+#undef FWD_HIP
 
 }  // namespace
 
@@ -522,108 +709,71 @@ int dsa_forward_models(const int* nx, const int* ny, const int* nz, const int* n
     if (rc != 0) return rc;
     if (g_pool.size() != 1) { g_dropin_error = "dsa_forward_models: one engine only (DSA_DEVICES unset): models are not sharded over GPUs"; return DSA_ERR_STATE; }
     dsa_engine* e = g_engine;
-    dsa::Engine* en = reinterpret_cast<dsa::Engine*>(e);
     const bool cal = *dicing == 8;
     const Layout L = make_layout(*kmaxRc, *kmaxRg, *kmaxLc, *kmaxLg, *kmax, cal);
     if (cal && L.kRc + L.kRg + L.kLc + L.kLg != L.kmax) { g_dropin_error = "dsa_forward_models: kmax must equal kmaxRc+kmaxRg+kmaxLc+kmaxLg"; return DSA_ERR_ARGUMENT; }
     Units U;
     if ((rc = make_units(L, false, *nsrcsurf, *nrcf, wavetype, igrt, periods, nrc1, nsrcsurf1, scxf, sczf, rcxf, rczf, U)) != 0) return rc;
     if (*ldd < U.ndata) { g_dropin_error = "dsa_forward_models: ldd is below the number of data"; return DSA_ERR_ARGUMENT; }
-    const int K = *nmodels, nu = (int)U.map.size(), nmaps = std::max(L.nmaps, 1);
-    const size_t ncol = (size_t)*nx * *ny, nd = (size_t)U.ndata;
-    tie_reset();
-    g_rbint_notes = 0; g_disp_count = 0; g_disp_period = 0.0;
-    for (int q = 0; q < 5; ++q) g_disp_first[q] = 0;
-    if (disp_failures) for (int m = 0; m < K; ++m) disp_failures[m] = 0;
+    Forward F{};
+    F.who = "dsa_forward_models";
+    F.nx = *nx; F.ny = *ny; F.nz = *nz; F.K = *nmodels; F.dicing = *dicing; F.ldd = *ldd;
+    F.vels = vels; F.dsurf = dsurf; F.disp_failures = disp_failures;
+    F.goxdf = *goxdf; F.gozdf = *gozdf; F.dvxdf = *dvxdf; F.dvzdf = *dvzdf; F.minthk = *minthk;
+    F.tRc = tRc; F.tRg = tRg; F.tLc = tLc; F.tLg = tLg; F.depz = depz;
+    return forward_passes(e, F, L, U);
+}
 
-    // models per pass: the option, or what the budget holds maps for -- a map costs its vertex values (fp64 store, fp32 copy), its
-    // diced nodes and two copies of its tiled slowness (the bundles read a member-minor one, whose byte offsets are 32-bit)
-    int per_pass = en->forward_models_chunk > 0 ? std::min(en->forward_models_chunk, K) : K;
-    if (en->forward_models_chunk == 0 && *nx >= 4 && *ny >= 4) {
-        dsa::GridDesc gd{};
-        dsa::make_grid(gd, *nx, *ny, *goxdf, *gozdf, *dvxdf, *dvzdf, *dicing);
-        const size_t nrec_c = (size_t)gd.nbx * gd.nbz * dsa::kTileRecs;
-        const size_t per_map = ncol * 12 + (size_t)gd.nnx * gd.nnz * 4 + nrec_c * 8;
-        size_t free_b = 0, total_b = 0;
-        if (hipSetDevice(en->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { g_dropin_error = "dsa_forward_models: no memory information from the device"; return DSA_ERR_DEVICE; }
-        const size_t budget = en->mem_budget ? en->mem_budget : (size_t)(0.6 * (double)free_b);
-        size_t maps = std::max<size_t>((size_t)(0.25 * (double)budget) / per_map, 1);
-        maps = std::min<size_t>(maps, (((size_t)1 << 32) - 1) / (nrec_c * 4));
-        per_pass = (int)std::min<size_t>((size_t)K, std::max<size_t>(maps / (size_t)nmaps, 1));
+// K models built on the device from a base model and K steps (host steps, or the solutions a batch solve left on the drop-in engine),
+// forward-modelled as dsa_forward_models does, and judged where the times are: misfit sums per (model, group) (include/dsurftomo_amd.h).
+int dsa_forward_steps(const int* nx, const int* ny, const int* nz, const int* nmodels, const float* vsf,
+                      const float* steps, const float* alpha, const float* minvel, const float* maxvel,
+                      float* models_out, float* dsurf, const int* ldd, const int* dicing, long long* disp_failures,
+                      const float* obst, const float* datweight, const int* group, const int* ngroups, double* measures,
+                      const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                      const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                      const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                      const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                      const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                      const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                      const int* nsrcsurf, const int* nrcf)
+{
+    if (!nx || !ny || !nz || !nmodels || !vsf || !minvel || !maxvel || (dsurf && !ldd) || !dicing || !goxdf || !gozdf || !dvxdf || !dvzdf || !kmaxRc || !kmaxRg || !kmaxLc || !kmaxLg ||
+        (*kmaxRc > 0 && !tRc) || (*kmaxRg > 0 && !tRg) || (*kmaxLc > 0 && !tLc) || (*kmaxLg > 0 && !tLg) || !wavetype || !igrt || !periods || !depz || !minthk || !scxf || !sczf || !rcxf || !rczf || !nrc1 || !nsrcsurf1 || !kmax ||
+        !nsrcsurf || !nrcf) { g_dropin_error = "dsa_forward_steps: null argument"; return DSA_ERR_ARGUMENT; }
+    if (*nmodels < 1) { g_dropin_error = "dsa_forward_steps: nmodels must be at least 1"; return DSA_ERR_ARGUMENT; }
+    if (*nx < 3 || *ny < 3 || *nz < 2) { g_dropin_error = "dsa_forward_steps: nx and ny must be at least 3, nz at least 2"; return DSA_ERR_ARGUMENT; }
+    if (*dicing != 5 && *dicing != 8) { g_dropin_error = "dsa_forward_steps: dicing must be 8 (CalSurfG's grid) or 5 (synthetic's)"; return DSA_ERR_ARGUMENT; }
+    if (measures && !obst) { g_dropin_error = "dsa_forward_steps: measures needs obst"; return DSA_ERR_ARGUMENT; }
+    const int ng = ngroups ? *ngroups : 1;
+    if (ng < 1) { g_dropin_error = "dsa_forward_steps: ngroups must be at least 1"; return DSA_ERR_ARGUMENT; }
+    const bool cal = *dicing == 8;
+    const Layout L = make_layout(*kmaxRc, *kmaxRg, *kmaxLc, *kmaxLg, *kmax, cal);
+    if (cal && L.kRc + L.kRg + L.kLc + L.kLg != L.kmax) { g_dropin_error = "dsa_forward_steps: kmax must equal kmaxRc+kmaxRg+kmaxLc+kmaxLg"; return DSA_ERR_ARGUMENT; }
+    Units U;
+    int rc;
+    if ((rc = make_units(L, false, *nsrcsurf, *nrcf, wavetype, igrt, periods, nrc1, nsrcsurf1, scxf, sczf, rcxf, rczf, U)) != 0) return rc;
+    if (dsurf && *ldd < U.ndata) { g_dropin_error = "dsa_forward_steps: ldd is below the number of data"; return DSA_ERR_ARGUMENT; }
+    if (group)
+        for (int i = 0; i < U.ndata; ++i)
+            if (group[i] < 0 || group[i] >= ng) { g_dropin_error = "dsa_forward_steps: datum " + std::to_string(i) + " is in group " + std::to_string(group[i]) + ", outside 0.." + std::to_string(ng - 1); return DSA_ERR_ARGUMENT; }
+    if ((unsigned long long)(*nx - 2) * (unsigned long long)(*ny - 2) * (unsigned long long)(*nz - 1) > (unsigned long long)INT_MAX) { g_dropin_error = "dsa_forward_steps: more than 2^31-1 unknowns"; return DSA_ERR_ARGUMENT; }
+    if ((rc = engine()) != 0) return rc;
+    if (g_pool.size() != 1) { g_dropin_error = "dsa_forward_steps: one engine only (DSA_DEVICES unset): models are not sharded over GPUs"; return DSA_ERR_STATE; }
+    dsa_engine* e = g_engine;
+    if (!steps) {
+        const int n = (*nx - 2) * (*ny - 2) * (*nz - 1);
+        if ((rc = reinterpret_cast<dsa::Engine*>(e)->resident_steps_check("dsa_forward_steps", *nmodels, n)) != 0) return fail(rc);
     }
-
-    std::vector<int> m_map, m_nrec, m_mode, m_data;
-    std::vector<float> m_sx, m_sz, m_rx, m_rz, times;
-    std::vector<size_t> ray0((size_t)nu + 1, 0);
-    for (int u = 0; u < nu; ++u) ray0[(size_t)u + 1] = ray0[(size_t)u] + (size_t)U.nrec[(size_t)u];
-    std::vector<long long> fails;
-    long long disp_count = 0;
-    // the passes run from the last models to the first, so that the store is left with model 0's maps at its head (dsa_dropin_velocity_maps)
-    const int npass = (K + per_pass - 1) / per_pass;
-    for (int pass = npass - 1; pass >= 0; --pass) {
-        const int m0 = pass * per_pass, nm = std::min(per_pass, K - m0);
-        if ((rc = dsa_dispersion_begin_models(e, *nx, *ny, *nz, nm, vels + (size_t)m0 * ncol * (size_t)*nz, depz, *minthk, nmaps)) != 0) return fail(rc);
-        if (cal) {
-            // CalSurfG.f90:1100-1140 without the depth kernels: the phase velocities at the group periods overwrite the head of the phase block
-            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, tRc, 0, 0, L.oRc)) != 0) return fail(rc);
-            if (L.kRg > 0) {
-                if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, tRg, 0, 0, L.oRg)) != 0) return fail(rc);
-                if ((rc = dsa_dispersion_run(e, 2, 0, L.kRg, tRg, 0, 0, L.oRc)) != 0) return fail(rc);
-            }
-            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, tLc, 0, 0, L.oLc)) != 0) return fail(rc);
-            if (L.kLg > 0) {
-                if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, tLg, 0, 0, L.oLg)) != 0) return fail(rc);
-                if ((rc = dsa_dispersion_run(e, 1, 0, L.kLg, tLg, 0, 0, L.oLc)) != 0) return fail(rc);
-            }
-        } else {
-            if ((rc = dsa_dispersion_run(e, 2, 0, L.kRc, tRc, 0, 0, L.oRc)) != 0) return fail(rc);
-            if ((rc = dsa_dispersion_run(e, 2, 1, L.kRg, tRg, 0, 0, L.oRg)) != 0) return fail(rc);
-            if ((rc = dsa_dispersion_run(e, 1, 0, L.kLc, tLc, 0, 0, L.oLc)) != 0) return fail(rc);
-            if ((rc = dsa_dispersion_run(e, 1, 1, L.kLg, tLg, 0, 0, L.oLg)) != 0) return fail(rc);
-        }
-        if ((rc = dsa_maps_from_dispersion(e, *goxdf, *gozdf, *dvxdf, *dvzdf, *dicing)) != 0) return fail(rc);
-        remember(L, *nx * *ny, cal);
-        fails.assign((size_t)nm, 0);
-        if ((rc = dsa_dispersion_model_failures(e, nm, fails.data())) != 0) return fail(rc);
-        for (int m = 0; m < nm; ++m) { disp_count += fails[(size_t)m]; if (disp_failures) disp_failures[m0 + m] = fails[(size_t)m]; }
-        {   // (the first failing curve reported is that of the lowest pass that had one: the passes run downwards, so a later pass overwrites)
-            long long c = 0; int first[5]; double period = 0.0;
-            if (dsa_dispersion_diagnostics(e, &c, first, &period) == 0 && c > 0) {
-                for (int q = 0; q < 5; ++q) g_disp_first[q] = first[q];
-                g_disp_first[2] += m0 * (int)ncol;
-                g_disp_period = period;
-            }
-        }
-        // the pass's units: every model's copy of the call's unit list on its own maps, data in its own column.  Model-major keeps the
-        // periods of a (model, source) consecutive: a bundle's members then read neighbouring maps of the member-minor slowness
-        const size_t n = (size_t)nu * nm;
-        m_map.resize(n); m_nrec.resize(n); m_mode.resize(n); m_data.resize(n); m_sx.resize(n); m_sz.resize(n);
-        m_rx.clear(); m_rz.clear();
-        m_rx.reserve(ray0[(size_t)nu] * nm); m_rz.reserve(ray0[(size_t)nu] * nm);
-        size_t q = 0;
-        auto put = [&](int m, int u) {
-            m_map[q] = m * nmaps + U.map[(size_t)u]; m_nrec[q] = U.nrec[(size_t)u]; m_mode[q] = U.mode[(size_t)u];
-            // (plan wants the data indices non-decreasing in unit order: model-major a column per model, period-major the models of a unit side by side)
-            m_data[q] = en->forward_models_order == 0 ? (int)((size_t)m * nd) + U.data[(size_t)u] : (int)((size_t)nm * (size_t)U.data[(size_t)u] + (size_t)m * (size_t)U.nrec[(size_t)u]);
-            m_sx[q] = U.sx[(size_t)u]; m_sz[q] = U.sz[(size_t)u];
-            m_rx.insert(m_rx.end(), U.rx.begin() + (long)ray0[(size_t)u], U.rx.begin() + (long)ray0[(size_t)u + 1]);
-            m_rz.insert(m_rz.end(), U.rz.begin() + (long)ray0[(size_t)u], U.rz.begin() + (long)ray0[(size_t)u + 1]);
-            ++q;
-        };
-        if (en->forward_models_order == 0) { for (int m = 0; m < nm; ++m) for (int u = 0; u < nu; ++u) put(m, u); }
-        else { for (int u = 0; u < nu; ++u) for (int m = 0; m < nm; ++m) put(m, u); }
-        if ((unsigned long long)nd * (unsigned long long)nm > (unsigned long long)INT_MAX) { g_dropin_error = "dsa_forward_models: more than 2^31-1 data in a pass (set option forward_models_chunk)"; return DSA_ERR_ARGUMENT; }
-        if ((rc = dsa_plan_units(e, (int)n, m_map.data(), m_sx.data(), m_sz.data(), m_nrec.data(), m_rx.data(), m_rz.data(), m_mode.data(), nullptr, m_data.data())) != 0) return fail(rc);
-        times.assign(std::max<size_t>(nd * nm, 1), 0.0f);
-        if ((rc = dsa_solve(e, times.data())) != 0) return fail(rc);
-        tie_collect(e);
-        for (size_t k = 0; k < n; ++k) {
-            const int u = en->forward_models_order == 0 ? (int)(k % (size_t)nu) : (int)(k / (size_t)nm), m = en->forward_models_order == 0 ? (int)(k / (size_t)nu) : (int)(k % (size_t)nm);
-            if (U.nrec[(size_t)u]) std::memcpy(dsurf + (size_t)(m0 + m) * (size_t)*ldd + (size_t)U.data[(size_t)u], times.data() + (size_t)m_data[k], (size_t)U.nrec[(size_t)u] * 4);
-        }
-    }
-    g_disp_count = disp_count;
-    return 0;
+    Forward F{};
+    F.who = "dsa_forward_steps";
+    F.nx = *nx; F.ny = *ny; F.nz = *nz; F.K = *nmodels; F.dicing = *dicing; F.ldd = dsurf ? *ldd : 0;
+    F.steps_mode = true; F.vsf = vsf; F.steps = steps; F.alpha = alpha; F.minvel = *minvel; F.maxvel = *maxvel; F.models_out = models_out;
+    F.obst = obst; F.datweight = datweight; F.group = group; F.ngroups = ng; F.measures = measures;
+    F.dsurf = dsurf; F.disp_failures = disp_failures;
+    F.goxdf = *goxdf; F.gozdf = *gozdf; F.dvxdf = *dvxdf; F.dvzdf = *dvzdf; F.minthk = *minthk;
+    F.tRc = tRc; F.tRg = tRg; F.tLc = tLc; F.tLg = tLg; F.depz = depz;
+    return forward_passes(e, F, L, U);
 }
 
 }  // extern "C"

@@ -230,6 +230,12 @@ struct Engine {
     std::vector<long long> disp_model_fail;      // curves without a root per model since begin (dsa_dispersion_model_failures)
     int forward_models_chunk = 0;                // option forward_models_chunk: models per pass of dsa_forward_models, 0 = from the memory budget
     int forward_models_order = 0;                // option forward_models_order: unit order of dsa_forward_models, 0 = model-major (default), 1 = period-major (A/B)
+    // dsa_forward_steps / dsa_step_models (step_kernels.hip): the base model, the steps of a pass and their factors; the receiver times of a
+    // pass, what they are compared with (obst, then datweight) and per datum { first datum, receiver count } of its unit, then its group;
+    // the misfit sums of a pass
+    DevBuf<float> fs_vsf, fs_steps, fs_alpha, fs_models, fs_times, fs_obs;
+    DevBuf<int> fs_idx;
+    DevBuf<double> fs_meas;
     std::vector<float> h_depz;
     LayerGeom h_geom{};
     DevBuf<LayerGeom> geom;
@@ -283,6 +289,13 @@ struct Engine {
     int set_sensitivity(int nz, int kmax, const float* vels, const float* depz, const double* svs, const double* svp, const double* srho, bool on_device);
     int finish_maps(int nm);
     int dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels = 1);
+    // the two halves of dispersion_begin, for models that are built on the device: setup sizes and clears the stage for nmodels models and
+    // leaves vels_d (depth, model, column) to be written on the stream; commit declares it written (host_copy: h_vels fetched from it)
+    int dispersion_setup(int nx, int ny, int nz, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels);
+    int dispersion_commit(bool host_copy);
+    // steps of a device-built model: d_steps (the pass's, member-major) or, null, the resident batch solutions after resident_steps_check
+    int resident_steps_check(const char* who, int nmodels, int n);
+    int step_models(int nx, int ny, int nz, int nmodels, const float* vsf, const float* steps, const float* alpha, float minvel, float maxvel, float* models_out);
     int dispersion_run(int iwave, int igr, int nper, const double* t, int with_kernels, int sen_slot, int map_first);
     int dispersion_copy_map(int from, int to, int n);
     int dispersion_fetch(int map_first, int nper, double* pv, int with_kernels, int sen_slot, double* svs, double* svp, double* srho);

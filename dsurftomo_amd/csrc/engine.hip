@@ -15,6 +15,7 @@
 
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
+#include "spmv_state.h"
 
 namespace dsa {
 
@@ -91,6 +92,7 @@ Engine::~Engine()
     rel(Srow); rel(sen_vs); rel(sen_vp); rel(sen_rho); rel(vels_d); rel(trace_ids); rel(vlist); rel(nvv); rel(counts); rel(offsets);
     rel(coo_col); rel(coo_iw); rel(slabs); rel(coo_rw); rel(rayinfo); rel(G_rw); rel(G_row); rel(G_col);
     rel(geom); rel(pvstore); rel(curves); rel(tper); rel(disp_ws);
+    rel(fs_vsf); rel(fs_steps); rel(fs_alpha); rel(fs_models); rel(fs_times); rel(fs_obs); rel(fs_idx); rel(fs_meas);
     if (stream2) { (void)hipStreamDestroy(stream2); (void)hipEventDestroy(ev_b0); (void)hipEventDestroy(ev_b1); stream2 = nullptr; }
     rel(cand_b); rel(bundles_r_d); rel(ends_r); rel(Br_pool); rel(slowIr); rel(exc_br); rel(lists_br); rel(cand_br);
     rel(lists_c); rel(pool_gen); rel(ends_c); rel(disp_diag); rel(disp_fail_list); rel(X_pool); rel(X_heap); rel(X_tt); rel(X_tp); rel(X_ring); rel(X_free); rel(X_pins); rel(x_starts); rel(x_nstart); rel(x_units); rel(xinfo); rel(tieinfo);
@@ -178,7 +180,21 @@ int Engine::finish_maps(int nm)
 // ---- dispersion stage -----------------------------------------------------------------------------
 int Engine::dispersion_begin(int nx, int ny, int nz, const float* vels, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels)
 {
-    if (nx < 1 || ny < 1 || nz < 2 || nz > 64 || !vels || !depz || kmax_total < 1 || nmaps_total < 1 || nmodels < 1 || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, nmodels); return DSA_ERR_ARGUMENT; }
+    if (!vels) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, nmodels); return DSA_ERR_ARGUMENT; }
+    if (int rc = dispersion_setup(nx, ny, nz, depz, minthk, kmax_total, nmaps_total, nmodels)) return rc;
+    const size_t ncol = (size_t)nx * ny;
+    // the model of one call is (column, depth); several are given model slowest and kept (depth, model, column): extra columns to the kernel
+    h_vels.resize(ncol * nz * nmodels);
+    for (int m = 0; m < nmodels; ++m)
+        for (int k = 0; k < nz; ++k)
+            std::memcpy(h_vels.data() + ((size_t)k * nmodels + m) * ncol, vels + ((size_t)m * nz + k) * ncol, ncol * 4);
+    HIP_TRY(this, hipMemcpyAsync(vels_d.p, h_vels.data(), h_vels.size() * 4, hipMemcpyHostToDevice, stream));
+    return dispersion_commit(false);
+}
+
+int Engine::dispersion_setup(int nx, int ny, int nz, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels)
+{
+    if (nx < 1 || ny < 1 || nz < 2 || nz > 64 || !depz || kmax_total < 1 || nmaps_total < 1 || nmodels < 1 || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, nmodels); return DSA_ERR_ARGUMENT; }
     if ((unsigned long long)nx * ny * nmodels > 0x7fffffffull || (unsigned long long)nmaps_total * nmodels > 0x7fffffffull) { fail(DSA_ERR_ARGUMENT, "dispersion: %d models of %d x %d columns and %d maps exceed the index range", nmodels, nx, ny, nmaps_total); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
     if (make_layer_geom(nz, depz, minthk, h_geom) != 0) { fail(DSA_ERR_ARGUMENT, "dispersion: the refined column exceeds %d layers", kMaxLayers); return DSA_ERR_ARGUMENT; }
@@ -188,28 +204,61 @@ int Engine::dispersion_begin(int nx, int ny, int nz, const float* vels, const fl
     h_depz.assign(depz, depz + nz);
     // (depth kernels exist for one model only: dispersion_run refuses them otherwise)
     const size_t nsen = nmodels == 1 ? ncol * kmax_total * nz : 0, npv = ncol * nmaps_total * nmodels;
-    // the model of one call is (column, depth); several are given model slowest and kept (depth, model, column): extra columns to the kernel
-    h_vels.resize(ncol * nz * nmodels);
-    for (int m = 0; m < nmodels; ++m)
-        for (int k = 0; k < nz; ++k)
-            std::memcpy(h_vels.data() + ((size_t)k * nmodels + m) * ncol, vels + ((size_t)m * nz + k) * ncol, ncol * 4);
-    if (ensure(geom, 1) || ensure(vels_d, h_vels.size()) || ensure(pvstore, npv) || ensure(sen_vs, nsen) || ensure(sen_vp, nsen) || ensure(sen_rho, nsen)) return status;
+    if (ensure(geom, 1) || ensure(vels_d, ncol * nz * nmodels) || ensure(pvstore, npv) || ensure(sen_vs, nsen) || ensure(sen_vp, nsen) || ensure(sen_rho, nsen)) return status;
     HIP_TRY(this, hipMemcpyAsync(geom.p, &h_geom, sizeof(LayerGeom), hipMemcpyHostToDevice, stream));
-    HIP_TRY(this, hipMemcpyAsync(vels_d.p, h_vels.data(), h_vels.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(this, hipMemsetAsync(pvstore.p, 0, npv * 8, stream));
     if (nsen) {
         HIP_TRY(this, hipMemsetAsync(sen_vs.p, 0, nsen * 8, stream));
         HIP_TRY(this, hipMemsetAsync(sen_vp.p, 0, nsen * 8, stream));
         HIP_TRY(this, hipMemsetAsync(sen_rho.p, 0, nsen * 8, stream));
     }
+    return 0;
+}
+
+int Engine::dispersion_commit(bool host_copy)
+{
+    if (host_copy) {
+        // (only the replay of a logged failure reads h_vels: without the log the models never visit the host)
+        h_vels.resize(disp_failure_log > 0 ? (size_t)disp_nx * disp_ny * disp_nz * disp_nmodels : 0);
+        if (!h_vels.empty()) HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
     disp_ready = true;
     disp_fail_count = 0;
-    disp_model_fail.assign((size_t)nmodels, 0);
+    disp_model_fail.assign((size_t)disp_nmodels, 0);
     disp_failures.clear();
     have_sens = false;
     stats[DSA_STAT_MS_DISPERSION] = 0.0;
     stats[DSA_STAT_CURVES] = 0.0;
+    return 0;
+}
+
+// the solutions of the last batch solve as the steps of nmodels models of n unknowns
+int Engine::resident_steps_check(const char* who, int nmodels, int n)
+{
+    if (!spmv || !spmv->bx_valid || !spmv->bx.p) { fail(DSA_ERR_STATE, "%s: steps is NULL and no batch solutions are resident (none solved yet, the matrix changed since, or the last batch was dsa_lsmr_voronoi's)", who); return DSA_ERR_STATE; }
+    if (nmodels != spmv->bx_nreal) { fail(DSA_ERR_STATE, "%s: steps is NULL and nmodels = %d, but the resident batch holds %d solutions", who, nmodels, spmv->bx_nreal); return DSA_ERR_STATE; }
+    if (n != spmv->bx_n || n != spmv->n) { fail(DSA_ERR_STATE, "%s: steps is NULL and the grid has %d unknowns, but the resident matrix has %d columns", who, n, spmv->n); return DSA_ERR_STATE; }
+    return 0;
+}
+
+// dsa_step_models: the models alone, model slowest, through the kernel of dsa_forward_steps
+int Engine::step_models(int nx, int ny, int nz, int nmodels, const float* vsf, const float* steps, const float* alpha, float minvel, float maxvel, float* models_out)
+{
+    const size_t ncol = (size_t)nx * ny, nn = ncol * nz, n = (size_t)(nx - 2) * (ny - 2) * (nz - 1);
+    if (n > 0x7fffffffull || nn > ((size_t)1 << 42) / (size_t)nmodels) { fail(DSA_ERR_ARGUMENT, "step_models: the grid exceeds the index range"); return DSA_ERR_ARGUMENT; }
+    if (!steps) { if (int rc = resident_steps_check("step_models", nmodels, (int)n)) return rc; }
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(fs_vsf, nn) || ensure(fs_models, nn * nmodels) || (steps && ensure(fs_steps, n * nmodels)) || (alpha && ensure(fs_alpha, (size_t)nmodels))) return status;
+    HIP_TRY(this, hipMemcpyAsync(fs_vsf.p, vsf, nn * 4, hipMemcpyHostToDevice, stream));
+    if (steps) HIP_TRY(this, hipMemcpyAsync(fs_steps.p, steps, n * nmodels * 4, hipMemcpyHostToDevice, stream));
+    if (alpha) HIP_TRY(this, hipMemcpyAsync(fs_alpha.p, alpha, (size_t)nmodels * 4, hipMemcpyHostToDevice, stream));
+    launch_step_models(nx, ny, nz, nmodels, 0, fs_vsf.p, steps ? fs_steps.p : nullptr, steps ? nullptr : spmv->bx.p, (int)n, alpha ? fs_alpha.p : nullptr, minvel, maxvel,
+                       fs_models.p, ncol, nn, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(models_out, fs_models.p, nn * nmodels * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -301,6 +350,7 @@ int Engine::dispersion_failure(int index, int* info, double* vals, float* table,
 {
     if (index < 0 || index >= (int)disp_failures.size() || !info || !vals || !table || !c) return DSA_ERR_ARGUMENT;
     const DispFailRec& r = disp_failures[(size_t)index];
+    if (h_vels.size() != (size_t)disp_nx * disp_ny * disp_nz * disp_nmodels) return DSA_ERR_STATE;
     const size_t ncol = (size_t)disp_nx * disp_ny * disp_nmodels;      // (h_vels: depth, model, column; r.column counts over the models)
     float vs[64];
     for (int k = 0; k < disp_nz; ++k) vs[k] = h_vels[(size_t)k * ncol + (size_t)(r.column - 1)];
@@ -1777,6 +1827,15 @@ int dsa_dispersion_begin_models(dsa_engine* e, int nx, int ny, int nz, int nmode
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->dispersion_begin(nx, ny, nz, vels, depz, minthk, nmaps_per_model, nmaps_per_model, nmodels);
+}
+
+int dsa_step_models(dsa_engine* e, int nx, int ny, int nz, int nmodels, const float* vsf, const float* steps, const float* alpha, float minvel, float maxvel,
+                    float* models_out)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    Engine* en = reinterpret_cast<Engine*>(e);
+    if (!vsf || !models_out || nmodels < 1 || nx < 3 || ny < 3 || nz < 2) { en->fail(DSA_ERR_ARGUMENT, "step_models: a null vsf / models_out, nmodels < 1, nx or ny < 3, or nz < 2"); return DSA_ERR_ARGUMENT; }
+    return en->step_models(nx, ny, nz, nmodels, vsf, steps, alpha, minvel, maxvel, models_out);
 }
 
 int dsa_dispersion_run(dsa_engine* e, int iwave, int igr, int nper, const double* t, int with_kernels, int sen_slot, int map_first)

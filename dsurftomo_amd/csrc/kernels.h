@@ -286,4 +286,11 @@ void launch_depth_kernels(const float* d_vels, int ncol, int nz, int kmax, const
 void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, int nmaps_per_model, int map_first, double* d_pv, hipStream_t stream);
 void launch_to_float(const double* d_in, float* d_out, size_t n, hipStream_t stream);
 
+// step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
+// batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times
+void launch_step_models(int nx, int ny, int nz, int nm, int m0, const float* d_vsf, const float* d_steps, const float* d_bx, int n, const float* d_alpha,
+                        float minvel, float maxvel, float* d_out, size_t stride_depth, size_t stride_model, hipStream_t stream);
+void launch_misfit_sums(const float* d_times, int order, int nm, int nd, const int* d_first, const int* d_count, const float* d_obst, const float* d_w,
+                        const int* d_group, int ngroups, double* d_measures, hipStream_t stream);
+
 }  // namespace dsa

@@ -899,6 +899,7 @@ int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B, int r
 {
     SpmvState& S = *e->spmv;
     B.e = e; B.S = &S;
+    S.bx_valid = false;                                       // (bx is about to change; batch_solve marks what it leaves)
     const int m = rows > 0 ? rows : S.m, n = cols > 0 ? cols : S.n, G = (nreal + 63) / 64, Rp = 64 * G;
     B.m = m; B.n = n; B.nfull = S.n; B.G = G; B.Rp = Rp;
     B.localVecs = std::max(0, std::min(localSize, std::min(m, n)));                              // :365
@@ -1061,6 +1062,8 @@ int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, 
     }
     LB_TRY(e, hipGetLastError());
     LB_TRY(e, hipStreamSynchronize(st));
+    // what bx holds now can be a later call's steps (dsa_forward_steps), unless it is in cell space (dsa_lsmr_voronoi)
+    S.bx_valid = !B.projected; S.bx_nreal = nreal; S.bx_n = n;
     return 0;
 }
 

@@ -58,6 +58,11 @@ struct SpmvState {
     DevBuf<int> bflag;               // ... the flag its validation reports
     // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
     DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
+    // the solutions a batch solve left in bx, for dsa_forward_steps / dsa_step_models with steps == NULL: set by a successful batch solve in the
+    // space of the unknowns (bx_n = the matrix's columns then), cleared when a batch begins, when the resident matrix is loaded or edited, and
+    // by dsa_lsmr_voronoi, whose bx is in cell space
+    bool bx_valid = false;
+    int bx_nreal = 0, bx_n = 0;
     DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results (bpsf: dsa_lsmr_tradeoff's measures too)
     // dsa_lsmr_voronoi: per call, the tessellations (vxyz: points of the unknowns; vseeds: seed unknowns, member-major; vcell_mm: cell of every
     // unknown, member-major; vcell: the same as [group][unknown][64]), the data rows' CSR positions sorted by cell per member (vlist, with
@@ -74,7 +79,8 @@ struct SpmvState {
 // y += A x (mode 1; x: n, y: m) or x += A^T y (mode 2) on device vectors, on the engine's stream; every output
 // element adds its entries in storage order (reference aprod.f90:7-60)
 void spmv_device(Engine* e, int mode, float* d_x, float* d_y);
-// the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch (and dsa_lsmr_tradeoff's coefficient copy of them) are stale
-inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = s->coef_valid = false; }
+// the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch (and dsa_lsmr_tradeoff's coefficient copy of them) are stale,
+// and the batch solutions in bx no longer belong to it
+inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = s->coef_valid = s->bx_valid = false; }
 
 }  // namespace dsa

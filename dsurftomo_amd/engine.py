@@ -51,6 +51,7 @@ def load_library():
     L.dsa_dispersion_begin.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _i32, _i32]
     L.dsa_dispersion_begin_models.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _i32]
     L.dsa_dispersion_model_failures.argtypes = [_vp, _i32, _vp]
+    L.dsa_step_models.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _vp]
     L.dsa_dispersion_run.argtypes = [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32]
     L.dsa_dispersion_copy_maps.argtypes = [_vp, _i32, _i32, _i32]
     L.dsa_dispersion_fetch.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]
@@ -248,6 +249,26 @@ class Engine:
         out = np.zeros(int(nmodels), np.int64)
         self._check(self._L.dsa_dispersion_model_failures(self._h, int(nmodels), out.ctypes.data_as(_vp)))
         return out
+
+    def step_models(self, vsf, steps, minvel, maxvel, alpha=None, nmodels=None):
+        """dsa_step_models: K models from the base model vsf (nx, ny, nz) and K steps (K, (nx-2)(ny-2)(nz-1)), what K dsa_model_update calls
+        leave in copies of vsf (step k scaled by float32(alpha[k]) first where alpha is given), built on the device.  steps None: the
+        solutions the last batch solve left on this engine, nmodels of them.  Returns (K, nx, ny, nz) float32."""
+        vsf = np.asarray(vsf, np.float32)
+        nx, ny, nz = vsf.shape
+        base = np.ascontiguousarray(vsf.transpose(2, 1, 0))             # C order of Fortran vsf(nx, ny, nz)
+        if steps is not None:
+            steps = np.ascontiguousarray(steps, np.float32).reshape(-1, (nx - 2) * (ny - 2) * (nz - 1))
+            K = steps.shape[0]
+        else:
+            K = int(nmodels)
+        if alpha is not None:
+            alpha = np.ascontiguousarray(alpha, np.float32)
+            if alpha.size != K:
+                raise ValueError("alpha has %d values for %d models" % (alpha.size, K))
+        out = np.zeros((K, nz, ny, nx), np.float32)
+        self._check(self._L.dsa_step_models(self._h, nx, ny, nz, K, _p(base), _p(steps), _p(alpha), float(minvel), float(maxvel), _p(out)))
+        return out.transpose(0, 3, 2, 1)
 
     def dispersion_run(self, iwave, igr, t, kernels, sen_slot=0, map_first=0):
         t = np.ascontiguousarray(t, np.float64)

@@ -5,7 +5,8 @@
                                    [--tradeoff-weights W1,W2,... [--tradeoff-damps D1,...] [--tradeoff-iter N]]
                                    [--voronoi K,NCELLS [--voronoi-seed S] [--voronoi-zscale F] [--voronoi-damp D] [--voronoi-update]]
                                    [--crossval NFOLDS --crossval-weights W1,W2,... [--crossval-damps D1,...] [--crossval-by datum|path]
-                                    [--crossval-seed S] [--crossval-iter N]]
+                                    [--crossval-seed S] [--crossval-iter N] [--crossval-nonlinear]]
+                                   [--tradeoff-nonlinear] [--line-search A1,A2,...]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -81,6 +82,21 @@ the `rms` of the log line, bit for bit).  A candidate with a dispersion curve wi
 the first listed (line_search_select); the winner's model is the one the iteration leaves.  <input>LineSearch.dat lists per (iteration,
 candidate): iteration, alpha, weighted rms, plain rms, dispersion failures, chosen 0/1 (io.write_line_search / read_line_search).  --line-search 1
 writes the model files of a plain run, byte for byte.  Device-resident rows only (not with --host-rows); combines with the analysis flags.
+
+--tradeoff-nonlinear (with --tradeoff-weights) and --crossval-nonlinear (with --crossval) judge the members of those two sweeps by the TRUE
+travel times through the models they would produce, not by the linearised residual b - A x alone.  After all linear
+analyses of the swept iteration, just before the line search / the model update, every member's raw update goes through dsa_forward_steps
+(io.call_forward_steps: dicing 8, no alpha, the input file's minvel / maxvel, this iteration's datweight, in chunks): the member's model --
+what a rerun with its (weight, damp) would hold after that iteration -- is built on the device, forward-modelled with the others, and its
+misfit sums { sum (w r)^2, sum r^2 } (nonlinear_measures restates them) are reduced there.  <input>TradeoffNonlinear.dat lists per member:
+weight, damp, the weighted rms the linear system predicts (sqrt(measures[0] / ndata) of the sweep), the true weighted rms, the true plain rms
+(rms = sqrt(sum / ndata)) and its dispersion curves without a root; the log names, per damp, the member with the smallest true weighted rms
+and the corner of (roughness, true misfit) beside the linear one.  The cross-validation passes the fold of every datum as its group:
+<input>CrossvalNonlinear.dat lists per pair: weight, damp, the true held-out rms (over the folds f, group f's weighted sum of the member that
+held f out, divided by ndata), the true full-fit rms of the full member, the linear cv_rms and the dispersion failures summed over the pair's
+members; the log names the pair with the smallest true held-out rms.  Where one dsa_lsmr_crossval call holds all pairs and no other batch
+solve follows it, the members' updates never leave the device (dsa_forward_steps with steps = NULL).  17 significant digits
+(io.read_tradeoff_nonlinear / read_crossval_nonlinear return the numbers bit for bit).  No other output changes.  Device-resident rows only.
 """
 import argparse
 import ctypes as C
@@ -686,6 +702,103 @@ def line_search_step(lib, c, vsf, dv, obst, datweight, alphas):
     return dict(alphas=[float(a) for a in alphas], weighted_rms=wr, rms=pr, failures=[int(v) for v in fails], chosen=k, models=cands, dsyn=dsyn, seconds=dt)
 
 
+def nonlinear_measures(obst, dsyn, datweight, group=None, ngroups=1):
+    """the misfit sums of dsa_forward_steps restated in numpy: per row k of dsyn (K, ndata) and group g of data, { sum (double)wr^2, sum
+    (double)r^2 } over the data of the group, r = float32(obst - dsyn_k), wr = float32(datweight * r) (datweight None: w = 1), squared and
+    summed in float64.  group: (ndata,) ids in [0, ngroups), None = one group; an empty group gives 0.  Returns (K, ngroups, 2) float64."""
+    f = np.float32
+    obst = np.asarray(obst, f).ravel()
+    dsyn = np.asarray(dsyn, f).reshape(-1, obst.size)
+    ngroups = int(ngroups)
+    if ngroups < 1:
+        raise ValueError("ngroups must be at least 1 (got %d)" % ngroups)
+    if group is None:
+        group = np.zeros(obst.size, np.int64)
+    group = np.asarray(group).ravel()
+    if group.size != obst.size or (group.size and (group.min() < 0 or group.max() >= ngroups)):
+        raise ValueError("group holds one id in [0, %d) per datum" % ngroups)
+    out = np.zeros((dsyn.shape[0], ngroups, 2))
+    for k, row in enumerate(dsyn):
+        r = (obst - row).astype(f)
+        wr = r if datweight is None else (np.asarray(datweight, f).ravel() * r).astype(f)
+        for g in range(ngroups):
+            sel = group == g
+            out[k, g, 0] = (wr[sel].astype(np.float64) ** 2).sum()
+            out[k, g, 1] = (r[sel].astype(np.float64) ** 2).sum()
+    return out
+
+
+def tradeoff_nonlinear_rows(weight, damp, predicted, measures, failures, ndata):
+    """the rows of <input>TradeoffNonlinear.dat (keys io.TRADEOFF_NONLINEAR_COLUMNS): per member its weight and damp, predicted_rms =
+    sqrt(predicted[k] / ndata) from the sweep's linear sum of squared data residuals, weighted_rms and rms = sqrt(sum / ndata) of the true
+    sums measures (K, 1, 2) = { sum (w r)^2, sum r^2 }, and its dispersion failures"""
+    meas = np.asarray(measures, np.float64).reshape(-1, 2)
+    nd = float(ndata)
+    return [dict(weight=float(weight[k]), damp=float(damp[k]), predicted_rms=float(np.sqrt(predicted[k] / nd)), weighted_rms=float(np.sqrt(meas[k, 0] / nd)),
+                 rms=float(np.sqrt(meas[k, 1] / nd)), disp_failures=int(failures[k])) for k in range(meas.shape[0])]
+
+
+def tradeoff_nonlinear_select(rows, rough):
+    """per damp (in order of first appearance): dict(damp, best = the member (index into rows) with the smallest true weighted rms among
+    those with a finite one, ties to the first, None where there is none; weight = its weight; corner / corner_weight = the member and the
+    weight lcurve_corner finds on (rough, true weighted rms) over increasing weight, None where it finds none).  rough: ||C x|| per member."""
+    out = []
+    for d in dict.fromkeys(t["damp"] for t in rows):
+        idx = sorted((i for i, t in enumerate(rows) if t["damp"] == d), key=lambda i: rows[i]["weight"])
+        ok = [i for i in idx if np.isfinite(rows[i]["weighted_rms"])]
+        best = min(ok, key=lambda i: (rows[i]["weighted_rms"], i)) if ok else None
+        k = lcurve_corner([rows[i]["weighted_rms"] for i in idx], [rough[i] for i in idx])
+        out.append(dict(damp=d, best=best, weight=None if best is None else rows[best]["weight"], corner=None if k is None else idx[k],
+                        corner_weight=None if k is None else rows[idx[k]]["weight"]))
+    return out
+
+
+def crossval_nonlinear_rows(weight, damp, nfolds, measures, failures, cv_rms, ndata):
+    """the rows of <input>CrossvalNonlinear.dat (keys io.CROSSVAL_NONLINEAR_COLUMNS) from the true sums measures (ncombo (nfolds + 1), nfolds, 2)
+    of the members' models with the fold as group: per pair q, heldout_rms = sqrt(sum_f measures[q S + f, f, 0] / ndata) -- every datum judged
+    by the member that never saw it --, full_rms = sqrt(sum_g measures[q S + nfolds, g, 0] / ndata) of the full member, the linear cv_rms,
+    and the dispersion failures summed over the pair's S = nfolds + 1 members"""
+    nf = int(nfolds)
+    S = nf + 1
+    meas = np.asarray(measures, np.float64).reshape(-1, S, nf, 2)
+    fails = np.asarray(failures).reshape(-1, S)
+    nd = float(ndata)
+    out = []
+    for q in range(meas.shape[0]):
+        held = sum(meas[q, f, f, 0] for f in range(nf))
+        full = sum(meas[q, nf, g, 0] for g in range(nf))
+        out.append(dict(weight=float(weight[q]), damp=float(damp[q]), heldout_rms=float(np.sqrt(held / nd)), full_rms=float(np.sqrt(full / nd)),
+                        cv_rms=float(cv_rms[q]), disp_failures=int(fails[q].sum())))
+    return out
+
+
+def crossval_nonlinear_select(rows):
+    """index of the pair with the smallest finite true held-out rms (ties to the larger weight, then the larger damp, as crossval_select), or None"""
+    ok = [i for i, t in enumerate(rows) if np.isfinite(t["heldout_rms"])]
+    return min(ok, key=lambda i: (rows[i]["heldout_rms"], -rows[i]["weight"], -rows[i]["damp"])) if ok else None
+
+
+def forward_steps_members(lib, c, vsf, steps, obst, datweight, group=None, ngroups=1, chunk=None, nmembers=None):
+    """the true misfit of the members of a sweep: their raw updates `steps` (K, nparpi) through dsa_forward_steps on the model vsf (dicing 8,
+    no alpha, the case's minvel / maxvel), `chunk` members per call (default 256); steps None: the nmembers solutions the last batch solve
+    left on the drop-in engine, in one call.  Returns dict(measures (K, ngroups, 2), failures (K,), dsyn (K, ndata), calls, resident, seconds)."""
+    t0 = time.perf_counter()
+    if steps is None:
+        r = io.call_forward_steps(c, vsf, int(nmembers), None, 8, obst, datweight, group, ngroups, lib=lib)
+        return dict(measures=r["measures"], failures=r["failures"], dsyn=r["dsurf"], calls=1, resident=True, seconds=time.perf_counter() - t0)
+    steps = np.asarray(steps, np.float32).reshape(-1, c["nparpi"])
+    K = steps.shape[0]
+    chunk = int(chunk or 256)
+    meas = np.zeros((K, int(ngroups), 2)); fails = np.zeros(K, np.int64); dsyn = np.zeros((K, c["ndata"]), np.float32)
+    calls = 0
+    for first in range(0, K, chunk):
+        q = slice(first, min(first + chunk, K))
+        r = io.call_forward_steps(c, vsf, steps[q], None, 8, obst, datweight, group, ngroups, lib=lib)
+        meas[q] = r["measures"]; fails[q] = r["failures"]; dsyn[q] = r["dsurf"]
+        calls += 1
+    return dict(measures=meas, failures=fails, dsyn=dsyn, calls=calls, resident=False, seconds=time.perf_counter() - t0)
+
+
 def write_residuals(path, c, dsyn, obst, datweight):
     """list-directed rows: dist, dsyn, obst, dsyn*w, obst*w, w (main.f90:397-403)"""
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
@@ -706,7 +819,11 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     crossval = dict(weights=[...], damps=[...], fold=(ndata,) int32, nfolds, chunk=int or None, want_x=bool): after dsa_lsmr, the K-fold
     cross-validation of the same system (returned as "crossval" from lsmr_crossval_sweep).
     line_search = [A1, A2, ...]: the update is applied at the step length among these whose model has the smallest true misfit
-    (line_search_step, returned as "line_search"); "dv" stays the full-length update."""
+    (line_search_step, returned as "line_search"); "dv" stays the full-length update.
+    tradeoff["nonlinear"] / crossval["nonlinear"]: after all of the above and before the line search / the update, the sweep's members
+    through forward_steps_members on the model as it stands (returned as "trade_nl" / "crossval_nl"; the forward call re-dices the maps
+    and leaves the resident matrix alone).  The cross-validation's updates stay on the device where one call held all pairs and no
+    other batch solve follows it."""
     f = np.float32
     nx, ny, nz, dall = c["nx"], c["ny"], c["nz"], c["ndata"]
     maxvp = c["nparpi"]
@@ -752,9 +869,13 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     if tradeoff:
         trade = lsmr_tradeoff_sweep(lib, eng, c, cbst, m.value, nar2.value, tradeoff["weights"], tradeoff["damps"], tradeoff.get("chunk"))
     cv = None
+    cv_resident = False
     if crossval:
+        ncombo = len(crossval["weights"]) * len(crossval["damps"])
+        cv_chunk = int(crossval.get("chunk") or crossval_chunk(m.value, maxvp, nar2.value, 10, ncombo, int(crossval["nfolds"]), dall))
+        cv_resident = bool(crossval.get("nonlinear")) and ncombo <= cv_chunk and not voronoi
         cv = lsmr_crossval_sweep(lib, eng, c, cbst, m.value, nar2.value, crossval["weights"], crossval["damps"], crossval["fold"], crossval["nfolds"],
-                                 crossval.get("chunk"), crossval.get("want_x", False))
+                                 cv_chunk, crossval.get("want_x", False) or (bool(crossval.get("nonlinear")) and not cv_resident))
     vor = None
     dv_lsmr = dv
     if voronoi:
@@ -767,6 +888,13 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
     rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))
     dv_raw = (f(dv.min()), f(dv.max()))
+    trade_nl = cv_nl = None
+    if crossval and crossval.get("nonlinear"):
+        K = cv["weight"].size * (cv["nfolds"] + 1)
+        cv_nl = forward_steps_members(lib, c, vsf, None if cv_resident else cv["x"], obst, datweight, crossval["fold"], cv["nfolds"],
+                                      crossval.get("nonlinear_chunk"), K)
+    if tradeoff and tradeoff.get("nonlinear"):
+        trade_nl = forward_steps_members(lib, c, vsf, trade["x"], obst, datweight, chunk=tradeoff.get("nonlinear_chunk"))
     ls = None
     if line_search:
         ls = line_search_step(lib, c, vsf, dv, obst, datweight, line_search)
@@ -786,6 +914,10 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
         out["trade"] = trade
     if cv is not None:
         out["crossval"] = cv
+    if trade_nl is not None:
+        out["trade_nl"] = trade_nl
+    if cv_nl is not None:
+        out["crossval_nl"] = cv_nl
     if vor is not None:
         out["voronoi"] = vor
         out["dv_lsmr"] = dv_lsmr
@@ -1097,6 +1229,26 @@ def check_crossval(nfolds, weights=None, damps=None, by="datum", iteration=1, ho
         raise ValueError("crossval_chunk must be at least 1 combo (got %d)" % chunk)
 
 
+def check_tradeoff_nonlinear(nonlinear, weights, host_rows):
+    """--tradeoff-nonlinear's preconditions, checked before anything touches the GPU"""
+    if not nonlinear:
+        return
+    if weights is None:
+        raise ValueError("--tradeoff-nonlinear needs --tradeoff-weights")
+    if host_rows:
+        raise ValueError("--tradeoff-nonlinear judges the members of the sweep on the device-resident system: it cannot be combined with --host-rows")
+
+
+def check_crossval_nonlinear(nonlinear, nfolds, host_rows):
+    """--crossval-nonlinear's preconditions, checked before anything touches the GPU"""
+    if not nonlinear:
+        return
+    if nfolds is None:
+        raise ValueError("--crossval-nonlinear needs --crossval")
+    if host_rows:
+        raise ValueError("--crossval-nonlinear judges the members of the cross-validation on the device-resident system: it cannot be combined with --host-rows")
+
+
 def check_voronoi(voronoi, update=False, host_rows=False, zscale=1.0, damp=None, nunknowns=None, chunk=None):
     """the Voronoi ensemble's preconditions, checked before anything touches the GPU (voronoi None: no ensemble; nunknowns: the number
     of unknowns once the input is read)"""
@@ -1135,7 +1287,10 @@ def _solve_text(h):
 def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False, bootstrap=0, bootstrap_seed=1, resolution=False, checkerboard=(),
         resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None, voronoi=None, voronoi_seed=1,
         voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None, crossval=None, crossval_weights=None, crossval_damps=None,
-        crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None, line_search=None):
+        crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None, line_search=None, tradeoff_nonlinear=False,
+        crossval_nonlinear=False):
+    check_tradeoff_nonlinear(tradeoff_nonlinear, tradeoff_weights, host_rows)
+    check_crossval_nonlinear(crossval_nonlinear, crossval, host_rows)
     check_bootstrap(bootstrap, host_rows)
     check_line_search(line_search, host_rows)
     check_crossval(crossval, crossval_weights, crossval_damps, crossval_by, crossval_iter, host_rows, maxiter, crossval_chunk)
@@ -1152,10 +1307,11 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
     cvrun = None
     if crossval is not None:
         cvrun = dict(weights=list(crossval_weights), damps=[float(c["damp"])] if crossval_damps is None else list(crossval_damps), nfolds=int(crossval),
-                     fold=crossval_folds(c, int(crossval), crossval_by, crossval_seed), chunk=crossval_chunk)
+                     fold=crossval_folds(c, int(crossval), crossval_by, crossval_seed), chunk=crossval_chunk, nonlinear=bool(crossval_nonlinear))
     sweep = None
     if tradeoff_weights is not None:
-        sweep = dict(weights=list(tradeoff_weights), damps=[float(c["damp"])] if tradeoff_damps is None else list(tradeoff_damps), chunk=tradeoff_chunk)
+        sweep = dict(weights=list(tradeoff_weights), damps=[float(c["damp"])] if tradeoff_damps is None else list(tradeoff_damps), chunk=tradeoff_chunk,
+                     nonlinear=bool(tradeoff_nonlinear))
     vsf = np.asfortranarray(c["vels"].copy())
     obst = np.ascontiguousarray(c["obst"])
     vsftrue = None
@@ -1191,7 +1347,7 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         if it == maxiter:
             write_residuals(os.path.join(out_dir, "residualLast.dat"), c, st["dsyn"], obst, st["datweight"])
         write_model(name + "Measure.dat.iter%03d" % it, c, vsf)
-        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr", "crossval", "line_search")}
+        h = {k: v for k, v in st.items() if k not in ("dsyn", "datweight", "dv", "norm", "cbst", "boot", "res", "trade", "voronoi", "dv_lsmr", "crossval", "line_search", "trade_nl", "crossval_nl")}
         if "line_search" in st:
             ls = st["line_search"]
             k = ls["chosen"]
@@ -1262,6 +1418,31 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                 t = members[i]
                 log(" crossval %s: weight %g damp %g, held-out rms %.6g (se of its square %.3g), training rms %.6g" %
                     (tag, t["weight"], t["damp"], t["cv_rms"], t["cv_se"], t["train_rms"]))
+        if "trade_nl" in st:
+            t, nl = st["trade"], st["trade_nl"]
+            rows = tradeoff_nonlinear_rows(t["weight"], t["damp"], t["measures"][:, 0], nl["measures"], nl["failures"], c["ndata"])
+            io.write_tradeoff_nonlinear(name + "TradeoffNonlinear.dat", rows)
+            picks = tradeoff_nonlinear_select(rows, [mb["rough"] for mb in h["tradeoff"]["members"]])
+            h["tradeoff_nonlinear"] = dict(iteration=it, members=rows, picks=picks, calls=nl["calls"], seconds=nl["seconds"], dsyn=nl["dsyn"])
+            log(" tradeoff nonlinear: %d members through %d forward call%s (%.3f s), %d dispersion curves without a root" %
+                (len(rows), nl["calls"], "" if nl["calls"] == 1 else "s", nl["seconds"], int(np.sum(nl["failures"]))))
+            for pk, cn in zip(picks, h["tradeoff"]["corners"]):
+                log(" tradeoff nonlinear damp %g: smallest true weighted rms %s; corner on the true misfit %s (linear: %s)" %
+                    (pk["damp"], "none" if pk["best"] is None else "%.6g at weight %g (predicted %.6g)" % (rows[pk["best"]]["weighted_rms"], pk["weight"], rows[pk["best"]]["predicted_rms"]),
+                     "not found" if pk["corner"] is None else "at weight %g" % pk["corner_weight"], "not found" if cn["weight"] is None else "at weight %g" % cn["weight"]))
+        if "crossval_nl" in st:
+            v, nl = st["crossval"], st["crossval_nl"]
+            rows = crossval_nonlinear_rows(v["weight"], v["damp"], v["nfolds"], nl["measures"], nl["failures"], [mb["cv_rms"] for mb in h["crossval"]["members"]], c["ndata"])
+            io.write_crossval_nonlinear(name + "CrossvalNonlinear.dat", rows)
+            best = crossval_nonlinear_select(rows)
+            h["crossval_nonlinear"] = dict(iteration=it, members=rows, best=best, calls=nl["calls"], resident=nl["resident"], seconds=nl["seconds"], dsyn=nl["dsyn"])
+            log(" crossval nonlinear: %d members through %d forward call%s (%.3f s; updates %s), %d dispersion curves without a root" %
+                (len(nl["failures"]), nl["calls"], "" if nl["calls"] == 1 else "s", nl["seconds"], "resident on the device" if nl["resident"] else "from the host",
+                 int(np.sum(nl["failures"]))))
+            if best is not None:
+                t = rows[best]
+                log(" crossval nonlinear best: weight %g damp %g, true held-out rms %.6g (linear %.6g), true full-fit rms %.6g" %
+                    (t["weight"], t["damp"], t["heldout_rms"], t["cv_rms"], t["full_rms"]))
         if "voronoi" in st:
             v = st["voronoi"]
             write_voronoi(name + "Voronoi.dat", c, v["mean"], v["std"])
@@ -1324,12 +1505,21 @@ def main(argv=None):
                          "surface-wave data (default datum)")
     ap.add_argument("--crossval-seed", type=int, default=1, metavar="S", help="seed of the folds (default 1)")
     ap.add_argument("--crossval-iter", type=int, default=1, metavar="N", help="the outer iteration whose step is cross-validated, 1..maxiter (default 1)")
+    ap.add_argument("--tradeoff-nonlinear", action="store_true",
+                    help="with --tradeoff-weights: judge every member of the sweep by the true travel times through the model it would produce "
+                         "(built and forward-modelled on the device in one call per chunk): <input>TradeoffNonlinear.dat, predicted against true rms "
+                         "per (weight, damp), and the best member and the corner on the true misfit per damp in the log")
+    ap.add_argument("--crossval-nonlinear", action="store_true",
+                    help="with --crossval: the same for the cross-validation's members, every datum judged by the model of the member that held its "
+                         "fold out: <input>CrossvalNonlinear.dat, true held-out and full-fit rms per pair beside the linear cv_rms")
     ap.add_argument("--line-search", type=_line_search_arg, default=None, metavar="A1,A2,...",
                     help="step-length line search: in every outer iteration the update is tried at these fractions of its length (each >= 0; 0 keeps "
                          "the model), all candidate models are forward-modelled in one call, and the one with the smallest rms of the weighted "
                          "travel-time residual is applied: <input>LineSearch.dat, one row per (iteration, step)")
     args = ap.parse_args(argv)
     try:
+        check_tradeoff_nonlinear(args.tradeoff_nonlinear, args.tradeoff_weights, args.host_rows)
+        check_crossval_nonlinear(args.crossval_nonlinear, args.crossval, args.host_rows)
         check_bootstrap(args.bootstrap, args.host_rows)
         check_line_search(args.line_search, args.host_rows)
         check_crossval(args.crossval, args.crossval_weights, args.crossval_damps, args.crossval_by, args.crossval_iter, args.host_rows, args.maxiter)
@@ -1344,7 +1534,7 @@ def main(argv=None):
         tradeoff_iter=args.tradeoff_iter, voronoi=args.voronoi, voronoi_seed=args.voronoi_seed, voronoi_zscale=args.voronoi_zscale,
         voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update, crossval=args.crossval, crossval_weights=args.crossval_weights,
         crossval_damps=args.crossval_damps, crossval_by=args.crossval_by, crossval_seed=args.crossval_seed, crossval_iter=args.crossval_iter,
-        line_search=args.line_search)
+        line_search=args.line_search, tradeoff_nonlinear=args.tradeoff_nonlinear, crossval_nonlinear=args.crossval_nonlinear)
     return 0
 
 

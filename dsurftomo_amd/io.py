@@ -194,6 +194,98 @@ def call_forward_models(c, models, dicing=8, ldd=None, lib=None):
     return dsurf[:, :ldd], fails[:K]
 
 
+def call_forward_steps(c, vsf, steps, alpha=None, dicing=8, obst=None, datweight=None, group=None, ngroups=1, want_dsurf=True, want_models=False, lib=None):
+    """dsa_forward_steps on a loaded case: K models built on the device from the base model vsf (nx, ny, nz) and the K steps `steps`
+    (K, nparpi) -- or, steps = K (an int), from the K solutions the last batch solve left on the drop-in engine --, each scaled by
+    float32(alpha[k]) where alpha is given, clipped as dsa_model_update clips with the case's minvel / maxvel, forward-modelled in one
+    call and judged on the device.  Returns dict(dsurf (K, ndata) float32 or None, failures (K,) int64, measures (K, ngroups, 2) float64
+    {sum (w r)^2, sum r^2} per group of data or None (it needs obst), models (K, nx, ny, nz) float32 or None)."""
+    if lib is None:
+        from .engine import load_library
+        lib = load_library()
+    f = np.float32
+    nx, ny, nz, nd, n = c["nx"], c["ny"], c["nz"], c["ndata"], c["nparpi"]
+    vsf = np.asarray(vsf, f)
+    if vsf.shape != (nx, ny, nz):
+        raise ValueError("vsf has shape %r, expected %r" % (vsf.shape, (nx, ny, nz)))
+    base = np.ascontiguousarray(vsf.transpose(2, 1, 0))                 # C order of Fortran vsf(nx, ny, nz)
+    if isinstance(steps, (int, np.integer)):
+        K, steps = int(steps), None
+    else:
+        steps = np.ascontiguousarray(steps, f).reshape(-1, n)
+        K = steps.shape[0]
+    opt = lambda a, t: None if a is None else np.ascontiguousarray(a, t)
+    alpha, obst, datweight, group = opt(alpha, f), opt(obst, f), opt(datweight, f), opt(group, np.int32)
+    for name, a, size in (("alpha", alpha, K), ("obst", obst, nd), ("datweight", datweight, nd), ("group", group, nd)):
+        if a is not None and a.size != size:
+            raise ValueError("%s has %d values, expected %d" % (name, a.size, size))
+    ngroups = int(ngroups)
+    dsurf = np.zeros((K, max(nd, 1)), f) if want_dsurf else None
+    models = np.zeros((K, nz, ny, nx), f) if want_models else None
+    measures = np.zeros((K, max(ngroups, 1), 2)) if obst is not None else None
+    fails = np.zeros(max(K, 1), np.int64)
+    i32 = lambda v: C.byref(C.c_int(int(v)))
+    f32 = lambda v: C.byref(C.c_float(float(v)))
+    p = lambda a: None if a is None else _ptr(a)
+    _, tail = _args(c)
+    rc = lib.dsa_forward_steps(i32(nx), i32(ny), i32(nz), i32(K), _ptr(base), p(steps), p(alpha), f32(c["minvel"]), f32(c["maxvel"]), p(models), p(dsurf),
+                               i32(nd), i32(dicing), _ptr(fails), p(obst), p(datweight), p(group), i32(ngroups), p(measures), *tail)
+    if rc != 0:
+        raise RuntimeError("dsa_forward_steps: %s" % lib.dsa_dropin_error().decode())
+    return dict(dsurf=None if dsurf is None else dsurf[:, :nd], failures=fails[:K], measures=measures,
+                models=None if models is None else models.transpose(0, 3, 2, 1))
+
+
+TRADEOFF_NONLINEAR_COLUMNS = ("weight", "damp", "predicted_rms", "weighted_rms", "rms", "disp_failures")
+CROSSVAL_NONLINEAR_COLUMNS = ("weight", "damp", "heldout_rms", "full_rms", "cv_rms", "disp_failures")
+
+
+def _write_nonlinear(path, columns, rows):
+    with open(path, "w") as fh:
+        fh.write("# " + " ".join(columns) + "\n")
+        for r in rows:
+            fh.write(" ".join("%.17g" % r[k] for k in columns[:-1]) + " %d\n" % r[columns[-1]])
+
+
+def _read_nonlinear(path, columns):
+    rows = []
+    with open(path) as fh:
+        for line in fh:
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            r = {k: float(v) for k, v in zip(columns[:-1], t)}
+            r[columns[-1]] = int(t[len(columns) - 1])
+            rows.append(r)
+    return rows
+
+
+def write_tradeoff_nonlinear(path, rows):
+    """<input>TradeoffNonlinear.dat: one row per member of the trade-off sweep -- weight, damp, the rms of the weighted residual the
+    linearised system predicts for the member's update, the rms of the weighted and of the plain residual of the travel times through
+    the member's model (rms = sqrt(sum / ndata)), dispersion curves without a root.  rows: dicts with the keys TRADEOFF_NONLINEAR_COLUMNS.
+    17 significant digits: read_tradeoff_nonlinear returns the numbers bit for bit."""
+    _write_nonlinear(path, TRADEOFF_NONLINEAR_COLUMNS, rows)
+
+
+def read_tradeoff_nonlinear(path):
+    """the rows write_tradeoff_nonlinear wrote, as a list of dicts"""
+    return _read_nonlinear(path, TRADEOFF_NONLINEAR_COLUMNS)
+
+
+def write_crossval_nonlinear(path, rows):
+    """<input>CrossvalNonlinear.dat: one row per (weight, damp) pair of the cross-validation -- weight, damp, the rms of the held-out weighted
+    travel-time residuals through the folds' models, the rms of the weighted residual through the full member's model, the linear cv_rms
+    for comparison, dispersion curves without a root summed over the pair's members.  rows: dicts with the keys
+    CROSSVAL_NONLINEAR_COLUMNS.  17 significant digits: read_crossval_nonlinear returns the numbers bit for bit."""
+    _write_nonlinear(path, CROSSVAL_NONLINEAR_COLUMNS, rows)
+
+
+def read_crossval_nonlinear(path):
+    """the rows write_crossval_nonlinear wrote, as a list of dicts"""
+    return _read_nonlinear(path, CROSSVAL_NONLINEAR_COLUMNS)
+
+
 LINE_SEARCH_COLUMNS = ("iteration", "alpha", "weighted_rms", "rms", "disp_failures", "chosen")
 
 

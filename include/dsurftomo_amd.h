@@ -317,6 +317,13 @@ int dsa_iteration_system(int nx, int ny, int nz, int dall, long long nar_in, lon
                          int* col, const float* obst, const float* dsyn, float threshold0, float weight0, float* cbst,
                          float* datweight, float* norm, int* m_out, long long* nar_out, float* dws);
 int dsa_model_update(int nx, int ny, int nz, float* dv, float* vsf, float minvel, float maxvel);
+/* model_update for nmodels steps at once, on the device, without touching its inputs: models_out (nmodels * nx*ny*nz floats, model
+ * slowest) receives what nmodels dsa_model_update calls leave in copies of vsf, given steps[k n .. (k+1) n) (n = (nx-2)(ny-2)(nz-1)),
+ * scaled by alpha[k] first (one rounded product) where alpha is not NULL -- bit for bit, a NaN step giving a NaN node.  steps == NULL:
+ * the solutions the last batch solve left on e (see dsa_forward_steps, whose models these are; DSA_ERR_STATE where it has none that fit).
+ * DSA_ERR_ARGUMENT: a null e / vsf / models_out, nmodels < 1, nx or ny < 3, nz < 2. */
+int dsa_step_models(dsa_engine* e, int nx, int ny, int nz, int nmodels, const float* vsf, const float* steps, const float* alpha,
+                    float minvel, float maxvel, float* models_out);
 /* The same system built where the rows are: on the COO rows that dsa_solve_rows (option rows_on_device) or dsa_calsurfg
  * (called with null rw / iw / col) left on the device.  Weights, regularisation rows, DWS and both orderings of the matrix
  * are made on the device; the matrix (12 bytes per entry) never crosses PCIe (reference: main.f90:349-359 -> :361-466 ->
@@ -485,6 +492,39 @@ int dsa_forward_models(const int* nx, const int* ny, const int* nz, const int* n
                        const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
                        const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
                        const int* nsrcsurf, const int* nrcf);
+
+/* Forward-model `nmodels` models that are built ON THE DEVICE from one base model vsf(nx,ny,nz) and `nmodels` steps, and judge them where
+ * their times are (extension).  goxdf .. nrcf as in dsa_forward_models.  Member k's model is dsa_model_update's on a copy:
+ * for unknown j = (l (ny-2) + jj)(nx-2) + i, s = steps[k n + j] (n = (nx-2)(ny-2)(nz-1)), s = fl(alpha[k] s) where alpha is not NULL, s
+ * clipped to +-0.5, v = vsf(i+1, jj+1, l) + s clipped to [minvel, maxvel], with dsa_model_update's comparisons (a NaN step gives a NaN
+ * node); the outer ring in x and y and the bottom layer keep the base value.  No input is modified.
+ *   steps == NULL: the steps are the solutions the last batch solve on the drop-in engine (dsa_dropin_engine) left on the device --
+ *     dsa_lsmr_batch, _resolution, _tradeoff or _crossval, also when called with x = NULL.  DSA_ERR_STATE unless such solutions are
+ *     resident (no batch yet; the matrix was loaded or edited since; the last batch was dsa_lsmr_voronoi's, whose solutions are in cell
+ *     space), nmodels equals their number and n the matrix's column count.
+ *   models_out (may be NULL): the models, nmodels * nx*ny*nz floats, model slowest -- bit-identical to nmodels dsa_model_update calls.
+ *   dsurf(ldd, nmodels) (may be NULL, ldd is ignored then): as dsa_forward_models'; bit-identical to it on those models under
+ *     exact_ties = 2, within tie_tolerance in the default mode.  With dsurf NULL nothing of size nmodels * ndata leaves the device.
+ *   disp_failures (may be NULL): curves without a root per model.
+ *   measures (may be NULL; needs obst): measures[(k ngroups + g) 2 + {0, 1}] = { sum (double)wr^2, sum (double)r^2 } over the data i of
+ *     group g, r = fl(obst[i] - t_k[i]), wr = fl(datweight[i] r) (datweight NULL: w = 1).  group[i] in [0, ngroups) (NULL: one group;
+ *     ngroups NULL: 1); an empty group gives +0.  fp64 sums in an order fixed by the datum index: the same bits on every call, for either
+ *     forward_models_order and any forward_models_chunk.
+ * Passes, unit orders, the dispersion sequence and the diagnostics afterwards are dsa_forward_models'.
+ * DSA_ERR_ARGUMENT (checked before the engine is created): a null required pointer, nmodels < 1, nx or ny < 3, nz < 2, dicing not 5 or
+ * 8, ldd below the number of data when dsurf is given, measures without obst, ngroups < 1, a group id out of range.  DSA_ERR_STATE: as
+ * above, or more than one engine (DSA_DEVICES).  After a failure the engine is as usable as after a failed dsa_forward_models. */
+int dsa_forward_steps(const int* nx, const int* ny, const int* nz, const int* nmodels, const float* vsf,
+                      const float* steps, const float* alpha, const float* minvel, const float* maxvel,
+                      float* models_out, float* dsurf, const int* ldd, const int* dicing, long long* disp_failures,
+                      const float* obst, const float* datweight, const int* group, const int* ngroups, double* measures,
+                      const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                      const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                      const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                      const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                      const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                      const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                      const int* nsrcsurf, const int* nrcf);
 
 /* Capacity (entries) of the rw / iw(2:) / col arrays handed to dsa_calsurfg from now on.  The reference's interface
  * (CalSurfG.f90:939-943) does not carry it -- main.f90:287 sizes the arrays as spfra*dall*nx*ny*nz and only checks
