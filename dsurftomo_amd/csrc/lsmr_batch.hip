@@ -21,27 +21,24 @@
 // The scalar recurrences are dsa::LsmrScalars (lsmr_core.h), the same code dsa_lsmr runs, one per realisation.  A realisation that
 // stops is frozen: no kernel writes its lanes again.  Three host synchronisations per iteration (beta, alpha, normx: nreal values each).
 //
-// dsa_lsmr_resolution runs the same loop (batch_begin, then its own way of filling u and the row scales, then batch_solve) on the
-// right-hand sides of test models, formed on the device: v = the models (unit spikes made in place, or host models), row scales 1,
-// u = A v by k_b_spmv<true> (fl(a * 1) = a: the chain of dsa_spmv mode 1 from y = 0), then the regularisation rows zeroed.  For
-// spikes, k_b_psf_part / k_b_psf_sum reduce each solution to its PSF measures on the device.
-//
-// dsa_lsmr_tradeoff runs it on K (weight, damp) pairs of one system: the products read a coefficient copy of the
-// contiguous values whose regularisation entries hold their integer coefficient c (the resident entry is fl(c * weight0)), the row
-// scales are 1 on the data rows and weight_k on the regularisation rows, so member k multiplies by fl(a * 1) = a and fl(c * weight_k):
-// the system dsa_iteration_system builds with weight_k.  damp_k goes to member k's LsmrScalars.  k_b_meas_rows / k_b_meas_x /
-// k_b_meas_sum reduce each solution to its misfit, roughness and size on the device.
-//
-// dsa_lsmr_crossval runs the trade-off's loop on ncombo (weight, damp) pairs x (nfolds hold-outs + the full data): the
-// row scales of the data rows are 0 where the member holds the row out and 1 elsewhere (k_b_crossval_init, from the fold of every datum),
-// u = fl(b * scale).  k_b_cv_rows is k_b_meas_rows with a per-lane hold predicate: kept and held-out misfit apart, and the held-out and
-// full-fit residual of every datum stored by the lane that formed it.
-//
-// dsa_lsmr_voronoi runs it on K random Voronoi projections of the data rows: member k's unknowns are the ncells cells of
-// its tessellation, its matrix M_k the resident data rows with every column j relabelled cell_k(j).  The batch vectors have the lengths
-// (ndata, ncells), and Batch::product is swapped for the projected one: mode 1 expands v to the unknowns through the cell map and runs
-// k_b_spmv<true> over the resident data rows, mode 2 walks, per (member, cell), the member's list of CSR positions sorted by cell
-// (k_v_colprod).  k_v_assign makes the tessellations, k_v_stats the ensemble mean and standard deviation per unknown.
+// Five entry points run that loop.  Each is: the front door (Entry: the argument checks they share), the layout of its pieces of btmp
+// (Carve), batch_begin, u and the row scales by k_b_fill under its rule (Fill), batch_solve, then its own measures.  bx keeps the
+// solutions for a later call (dsa_forward_steps, SpmvState::bx_valid).
+//   * dsa_lsmr_batch: the bootstrap above (FILL_ROWS).
+//   * dsa_lsmr_resolution: the right-hand sides of test models, formed on the device: v = unit spikes made in place or host
+//     models, row scales 1 and u = 0 (FILL_ONE without b), u = A v by k_b_spmv<true> (fl(a * 1) = a: the chain of dsa_spmv mode 1 from
+//     y = 0), then the regularisation rows zeroed.  For spikes, k_b_psf_part / k_b_psf_sum reduce each solution to its PSF measures.
+//   * dsa_lsmr_tradeoff (§13): K (weight, damp) pairs.  The products read a coefficient copy of the contiguous values whose regularisation
+//     entries hold their integer coefficient c (the resident entry is fl(c * weight0)); with row scales 1 on the data rows and weight_k
+//     from ndata up (FILL_WEIGHT) member k multiplies by fl(a * 1) = a and fl(c * weight_k): the system dsa_iteration_system builds with
+//     weight_k.  damp_k goes to member k's LsmrScalars.  batch_measures: each solution's misfit, roughness and size.
+//   * dsa_lsmr_crossval (§15): the same (weighted_solve) on ncombo pairs x (nfolds hold-outs + the full data): the data rows' scales are 0
+//     where the member holds the row out, else 1, and u = fl(b * scale) there (FILL_FOLD); the measures take a hold predicate per lane
+//     (HoldFold): kept and held-out misfit apart, and every datum's held-out and full-fit residual stored by the lane that formed it.
+//   * dsa_lsmr_voronoi (§14): K random Voronoi projections of the data rows: member k's unknowns are the ncells cells of its tessellation
+//     (k_v_assign), its matrix the resident data rows with column j relabelled cell_k(j).  Batch vectors of (ndata, ncells), u = b and row
+//     scales 1 (FILL_ONE); Batch::product is the projected one: mode 1 expands v through the cell map and runs k_b_spmv<true> over the data
+//     rows, mode 2 walks per (member, cell) the member's CSR positions sorted by cell (k_v_colprod).  k_v_stats: the ensemble statistics.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -70,15 +67,61 @@ constexpr int kNParam = NCOEF + NFLAG;
     const size_t gbase = (size_t)g * (size_t)(len) * 64;                                                              \
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)(len) * 64; t += (size_t)gridDim.x * blockDim.x)
 
-// (g, i, l) of the batch layout <- realisation-major input: scale = s_r[i] (0 past nreal), u = fl(b[i] * s_r[i])
-__global__ void k_b_init(int m, int nreal, const float* __restrict__ b, const float* __restrict__ rs, float* __restrict__ scale, float* __restrict__ u)
+// How k_b_fill scales the rows of member r (par: the rule's values)
+enum Fill {
+    FILL_ROWS,      // dsa_lsmr_batch: row i by par[r * m + i], the realisation's own row scales
+    FILL_ONE,       // dsa_lsmr_resolution, dsa_lsmr_voronoi: every row by 1
+    FILL_WEIGHT,    // dsa_lsmr_tradeoff: the data rows by 1, the rows from ndata up by par[r]
+    FILL_FOLD,      // dsa_lsmr_crossval, member r = q * stride + f: the data rows by 0 where fold[i] == f, else 1, the rows from ndata up by par[q]
+};
+
+// (g, i, l) of the batch layout: scale = the rule's row scale, u = fl(b[i] * scale) on the rows whose right-hand side the rule scales (all
+// of FILL_ROWS, the data rows of FILL_FOLD) and b[i] on the others (there the scale is 1, or a weight that multiplies the matrix alone: b is
+// stored as it is, not as fl(b * 1)); u = +0 without b.  Both +0 in the padding lanes (r >= nreal), which never run.
+__global__ void k_b_fill(Fill rule, int m, int ndata, int nreal, int stride, const float* __restrict__ b, const float* __restrict__ par,
+                         const int* __restrict__ fold, float* __restrict__ scale, float* __restrict__ u)
 {
     LB_GROUP_LOOP(m) {
         const int r = g * 64 + (int)(t & 63);
         const size_t i = t >> 6;
-        const float s = r < nreal ? rs[(size_t)r * (size_t)m + i] : 0.0f;
+        float s = 0.0f, uu = 0.0f;
+        if (r < nreal) {
+            bool mul = false;
+            if (rule == FILL_ROWS) { s = par[(size_t)r * (size_t)m + i]; mul = true; }
+            else if (rule == FILL_ONE) s = 1.0f;
+            else if (i >= (size_t)ndata) s = par[rule == FILL_FOLD ? r / stride : r];
+            else if (rule == FILL_FOLD) { s = fold[i] == r % stride ? 0.0f : 1.0f; mul = true; }
+            else s = 1.0f;
+            if (b) uu = mul ? b[i] * s : b[i];
+        }
         scale[gbase + t] = s;
-        u[gbase + t] = b[i] * s;
+        u[gbase + t] = uu;
+    }
+}
+
+// (g, i, l) of the batch layout <- realisation-major in[r * len + i] (0 past nreal); T: float (models) or int (cell maps)
+template <typename T>
+__global__ void k_b_scatter(int len, int nreal, const T* __restrict__ in, T* __restrict__ out)
+{
+    LB_GROUP_LOOP(len) {
+        const int r = g * 64 + (int)(t & 63);
+        out[gbase + t] = r < nreal ? in[(size_t)r * (size_t)len + (t >> 6)] : T(0);
+    }
+}
+
+// The tail of the fp64 block reductions (blocks of four wavefronts): every wavefront leaves its lanes' NS sums in LDS and wavefront 0
+// stores, per lane, ((w0 + w1) + w2) + w3 of each to out[0 .. NS)
+template <int NS>
+__device__ inline void block_sum4(const double (&s)[NS], double* __restrict__ out)
+{
+    __shared__ double red[NS][4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) red[c][w][lane] = s[c];
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) out[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
     }
 }
 
@@ -339,6 +382,15 @@ __global__ void k_contig_fill(int nslots, const long long* __restrict__ off, con
         hipError_t _r = (call);                                                                \
         if (_r != hipSuccess) { (e)->fail(DSA_ERR_DEVICE, "lsmr_batch: %s failed: %s", #call, hipGetErrorString(_r)); return DSA_ERR_DEVICE; } \
     } while (0)
+#define LB_DO(call) do { if (int _rc = (call)) return _rc; } while (0)
+
+// the end of a call's device work: launch errors, then the stream drained
+int drain(Engine* e, hipStream_t st)
+{
+    LB_TRY(e, hipGetLastError());
+    LB_TRY(e, hipStreamSynchronize(st));
+    return 0;
+}
 
 // A segment's entries lie in the blocks of its ordering in storage order: in blocks 0, 1, ... (segments stored in ascending input
 // order) or all in the unblocked rest.  So the contiguous copy of segment s is its part of block 0, then of block 1, ...
@@ -392,16 +444,7 @@ int build_contiguous(Engine* e, const SpmvState::Ordering& O, int nseg, long lon
 // element-wise launch over every group's len * 64 elements
 dim3 grid_of(int len, int G) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, ((size_t)len * 64 + 255) / 256)), (unsigned)G); }
 
-// ---- dsa_lsmr_resolution: the right-hand sides b_r = A m_r (data rows), formed on the device, and the PSF measures ----
-
-// (g, i, l) of the batch layout <- realisation-major input[r * len + i] (0 past nreal)
-__global__ void k_b_scatter(int len, int nreal, const float* __restrict__ in, float* __restrict__ out)
-{
-    LB_GROUP_LOOP(len) {
-        const int r = g * 64 + (int)(t & 63);
-        out[gbase + t] = r < nreal ? in[(size_t)r * (size_t)len + (t >> 6)] : 0.0f;
-    }
-}
+// ---- dsa_lsmr_resolution: the test models, and the PSF measures ----
 
 // unit spikes: element i of realisation r is 1 where i == first + r (r < nreal), else 0
 __global__ void k_b_spike(int n, int nreal, int first, float* __restrict__ out)
@@ -410,12 +453,6 @@ __global__ void k_b_spike(int n, int nreal, int first, float* __restrict__ out)
         const int r = g * 64 + (int)(t & 63);
         out[gbase + t] = (r < nreal && (long long)(t >> 6) == (long long)first + r) ? 1.0f : 0.0f;
     }
-}
-
-// row scales of the unscaled matrix: 1 (0 past nreal, as k_b_init leaves them)
-__global__ void k_b_ones(int m, int nreal, float* __restrict__ scale)
-{
-    LB_GROUP_LOOP(m) scale[gbase + t] = g * 64 + (int)(t & 63) < nreal ? 1.0f : 0.0f;
 }
 
 // rows [ndata, m) of every group's u <- +0 (the regularisation rows of the right-hand side)
@@ -451,30 +488,24 @@ __device__ inline double psf_dh(double lat_i, double lon_i, double cos_i, double
 __global__ __launch_bounds__(256) void k_b_psf_part(int n, int nb, int first, const double* __restrict__ coords, const double* __restrict__ cosl,
                                                     const float* __restrict__ x, double* __restrict__ part)
 {
-    __shared__ double red[3][4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, b = blockIdx.x;
     const long long jj = (long long)first + g * 64 + lane;
     const int j = jj < n ? (int)jj : n - 1;                           // (padding lanes: any unknown, never read back)
     const double lat_j = coords[3 * (size_t)j], lon_j = coords[3 * (size_t)j + 1], dep_j = coords[3 * (size_t)j + 2], cos_j = cosl[j];
     const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
     const int e0 = b * kPsfE + w * (kPsfE / 4), e1 = min(e0 + kPsfE / 4, n);
-    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
     for (int e = e0; e < e1; ++e) {
         const double xv = (double)p[(size_t)e * 64];
         if (xv == 0.0) continue;                                          // (its terms are +0)
         const double q = xv * xv;
         const double dh = psf_dh(coords[3 * (size_t)e], coords[3 * (size_t)e + 1], cosl[e], lat_j, lon_j, cos_j);
         const double dz = coords[3 * (size_t)e + 2] - dep_j;
-        s1 = s1 + q;
-        s2 = s2 + q * (dh * dh);
-        s3 = s3 + q * (dz * dz);
+        s[0] = s[0] + q;
+        s[1] = s[1] + q * (dh * dh);
+        s[2] = s[2] + q * (dz * dz);
     }
-    red[0][w][lane] = s1; red[1][w][lane] = s2; red[2][w][lane] = s3;
-    __syncthreads();
-    if (w == 0) {
-        double* __restrict__ o = part + (((size_t)g * nb + b) * 64 + lane) * 3;
-        for (int c = 0; c < 3; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
-    }
+    block_sum4(s, part + (((size_t)g * nb + b) * 64 + lane) * 3);
 }
 
 // psf[4 r .. 4 r + 3] = {x_r[j], the three sums}; one thread per realisation
@@ -492,7 +523,7 @@ __global__ __launch_bounds__(64) void k_b_psf_sum(int n, int nb, int nreal, int 
     for (int c = 0; c < 3; ++c) psf[4 * (size_t)r + 1 + c] = s[c];
 }
 
-// ---- dsa_lsmr_tradeoff: the coefficient copy of the contiguous values, its row scales, and the measures of every solution ----
+// ---- dsa_lsmr_tradeoff, dsa_lsmr_crossval: the coefficient copy of the contiguous values ----
 
 // c of a regularisation entry a = fl(c * w0): rint(a / w0); `bad` unless c is a non-zero integer of at most 64 whose product gives a's bits back
 __device__ inline float coef_of(float a, float w0, bool& bad)
@@ -522,169 +553,110 @@ __global__ void k_coef_cols(long long nar, int ndata, float w0, const int* __res
     if (bad) atomicOr(flag, 1);
 }
 
-// (g, i, l) of the batch layout: scale = 1 on the data rows, weight_r from ndata up, u = b[i]; both 0 past nreal
-__global__ void k_b_tradeoff_init(int m, int ndata, int nreal, const float* __restrict__ b, const float* __restrict__ w, float* __restrict__ scale,
-                                  float* __restrict__ u)
-{
-    LB_GROUP_LOOP(m) {
-        const int r = g * 64 + (int)(t & 63);
-        const size_t i = t >> 6;
-        const bool in = r < nreal;
-        scale[gbase + t] = in ? (i < (size_t)ndata ? 1.0f : w[r]) : 0.0f;
-        u[gbase + t] = in ? b[i] : 0.0f;
-    }
-}
+// ---- the measures of dsa_lsmr_tradeoff and dsa_lsmr_crossval, and the held-out residuals of the latter ----
 
-// Measures of member r over its solution x_r: sum over the data rows of (b_i - (A x_r)_i)^2, sum over the rows from ndata up of
-// ((C x_r)_i)^2 (val: the row ordering's coefficient copy, so C = the integer coefficients), sum of x_r^2; fp64.  A row's sum adds its
-// entries in storage order (the float x float products are exact in fp64).  k_b_meas_rows: block (b, g), four wavefronts, wavefront w
-// the rows [b kMeasR + w kMeasR/4, + kMeasR/4) in order, value and index wave-uniform, one coalesced 256-byte load of bx per entry;
-// the four wavefronts' sums added in order.  k_b_meas_x: the same over the elements of x.  k_b_meas_sum: the blocks' partials in order.
+// Measures of member r over its solution x_r: sum over the data rows of (b_i - (A x_r)_i)^2 -- for dsa_lsmr_crossval the rows the member
+// keeps and those it holds out apart --, sum over the rows from ndata up of ((C x_r)_i)^2 (val: the row ordering's coefficient copy, so
+// C = the integer coefficients), sum of x_r^2; fp64.  k_b_meas_rows: block (b, g), four wavefronts, wavefront w the rows
+// [b kMeasR + w kMeasR/4, + kMeasR/4) in order, row_product each; the four wavefronts' sums added in order (block_sum4).  k_b_meas_x: the
+// same over the elements of x.  k_b_meas_sum: the blocks' partials in order.
 constexpr int kMeasR = 64;                  // rows per block
 constexpr int kMeasE = 1024;                // elements of x per block
 
+// (A x)_row of the lane's member (p: its x), fp64: the row's entries added in storage order, value and index wave-uniform, one coalesced
+// 256-byte load of x per entry, four entries' loads ahead of their additions (the float x float products are exact in fp64)
+__device__ inline double row_product(const long long* __restrict__ ptr, const float* __restrict__ val, const int* __restrict__ idx,
+                                     const float* __restrict__ p, int row)
+{
+    double acc = 0.0;
+    long long k = ptr[row];
+    const long long k1 = ptr[row + 1];
+    constexpr int U = 4;
+    for (; k + U <= k1; k += U) {
+        double a[U], xi[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { a[u] = (double)val[k + u]; xi[u] = (double)p[(size_t)idx[k + u] * 64]; }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = acc + a[u] * xi[u];
+    }
+    for (; k < k1; ++k) acc = acc + (double)val[k] * (double)p[(size_t)idx[k] * 64];
+    return acc;
+}
+
+// The hold predicates of k_b_meas_rows: lane() takes the lane's member, row() says whether the member holds data row `row` (residual d) out.
+// kSums sums per lane: {kept misfit, roughness} or {kept misfit, held-out misfit, roughness}.
+struct KeepAll {                            // dsa_lsmr_tradeoff: every member keeps every row
+    static constexpr int kSums = 2;
+    __device__ void lane(int) {}
+    __device__ bool row(int, double, double*) const { return false; }
+};
+// dsa_lsmr_crossval: member r = q * stride + f holds out fold f; the full member (f = stride - 1 = nfolds, no datum's fold) keeps every row,
+// so its kept sum and its roughness are KeepAll's additions in KeepAll's order.  The lane that holds row i out stores d to
+// resid[(2 q) ndata + i], the full member's lane to resid[(2 q + 1) ndata + i]: every (combo, datum) is written once in each half.
+struct HoldFold {
+    static constexpr int kSums = 3;
+    const int* fold;
+    int ndata, nreal, stride;
+    int r = 0, q = 0, f = 0;                // the lane's member and its (combo, fold)
+    __device__ void lane(int r_) { r = r_; q = r / stride; f = r - q * stride; }
+    __device__ bool row(int row, double d, double* __restrict__ resid) const
+    {
+        const bool held = fold[row] == f, full = f == stride - 1;
+        if (resid && r < nreal && (held || full)) resid[(2 * (size_t)q + (full ? 1 : 0)) * (size_t)ndata + (size_t)row] = d;
+        return held;
+    }
+};
+
+// part: Hold::kSums sums per (g, block, lane)
+template <class Hold>
 __global__ __launch_bounds__(256) void k_b_meas_rows(int m, int n, int ndata, int nb, const long long* __restrict__ ptr, const float* __restrict__ val,
                                                      const int* __restrict__ idx, const float* __restrict__ b, const float* __restrict__ x,
-                                                     double* __restrict__ part)
+                                                     double* __restrict__ part, double* __restrict__ resid, Hold hold)
 {
-    __shared__ double red[2][4][64];
+    constexpr int NS = Hold::kSums;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
+    hold.lane(g * 64 + lane);
     const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
     const int r0 = blk * kMeasR + w * (kMeasR / 4), r1 = min(r0 + kMeasR / 4, m);
-    double s0 = 0.0, s1 = 0.0;
+    double s[NS] = {};
     for (int row = r0; row < r1; ++row) {
-        double acc = 0.0;
-        long long k = ptr[row];
-        const long long k1 = ptr[row + 1];
-        constexpr int U = 4;
-        for (; k + U <= k1; k += U) {
-            double a[U], xi[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) { a[u] = (double)val[k + u]; xi[u] = (double)p[(size_t)idx[k + u] * 64]; }
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc = acc + a[u] * xi[u];
+        const double acc = row_product(ptr, val, idx, p, row);
+        if (row < ndata) {
+            const double d = (double)b[row] - acc;
+            if (hold.row(row, d, resid)) s[1] = s[1] + d * d;
+            else s[0] = s[0] + d * d;
         }
-        for (; k < k1; ++k) acc = acc + (double)val[k] * (double)p[(size_t)idx[k] * 64];
-        if (row < ndata) { const double d = (double)b[row] - acc; s0 = s0 + d * d; }
-        else s1 = s1 + acc * acc;
+        else s[NS - 1] = s[NS - 1] + acc * acc;
     }
-    red[0][w][lane] = s0; red[1][w][lane] = s1;
-    __syncthreads();
-    if (w == 0) {
-        double* __restrict__ o = part + (((size_t)g * nb + blk) * 64 + lane) * 2;
-        for (int c = 0; c < 2; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
-    }
+    block_sum4(s, part + (((size_t)g * nb + blk) * 64 + lane) * NS);
 }
 
 __global__ __launch_bounds__(256) void k_b_meas_x(int n, int nb, const float* __restrict__ x, double* __restrict__ part)
 {
-    __shared__ double red[4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
     const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
     const int e0 = blk * kMeasE + w * (kMeasE / 4), e1 = min(e0 + kMeasE / 4, n);
-    double s = 0.0;
-    for (int e = e0; e < e1; ++e) { const double xv = (double)p[(size_t)e * 64]; s = s + xv * xv; }
-    red[w][lane] = s;
-    __syncthreads();
-    if (w == 0) part[((size_t)g * nb + blk) * 64 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    double s[1] = {0.0};
+    for (int e = e0; e < e1; ++e) { const double xv = (double)p[(size_t)e * 64]; s[0] = s[0] + xv * xv; }
+    block_sum4(s, part + ((size_t)g * nb + blk) * 64 + lane);
 }
 
-// meas[3 r .. 3 r + 2] = {misfit, roughness, sum x^2}; one thread per member
+// meas[(NS + 1) r ..] = the NS row sums of k_b_meas_rows, then sum x^2; one thread per member
+template <int NS>
 __global__ __launch_bounds__(64) void k_b_meas_sum(int nbr, int nbx, int nreal, const double* __restrict__ rows, const double* __restrict__ xs,
                                                    double* __restrict__ meas)
 {
     const int lane = threadIdx.x, g = blockIdx.x, r = g * 64 + lane;
     if (r >= nreal) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double s[NS + 1] = {};
     for (int b = 0; b < nbr; ++b) {
-        const double* __restrict__ q = rows + (((size_t)g * nbr + b) * 64 + lane) * 2;
-        s0 = s0 + q[0]; s1 = s1 + q[1];
-    }
-    for (int b = 0; b < nbx; ++b) s2 = s2 + xs[((size_t)g * nbx + b) * 64 + lane];
-    meas[3 * (size_t)r] = s0; meas[3 * (size_t)r + 1] = s1; meas[3 * (size_t)r + 2] = s2;
-}
-
-// ---- dsa_lsmr_crossval: the fold masks, and the measures and held-out residuals of every solution ----
-
-// Member r = q * stride + f (stride = nfolds + 1) holds out fold f of the data rows with the weight of combo q; f = nfolds holds out nothing.
-// (g, i, l) of the batch layout: on the data rows scale = 0 where fold[i] == f, else 1, and u = fl(b[i] * scale); from ndata up
-// scale = w[q], u = b[i]; both 0 past nreal
-__global__ void k_b_crossval_init(int m, int ndata, int nreal, int stride, const float* __restrict__ b, const float* __restrict__ w,
-                                  const int* __restrict__ fold, float* __restrict__ scale, float* __restrict__ u)
-{
-    LB_GROUP_LOOP(m) {
-        const int r = g * 64 + (int)(t & 63);
-        const size_t i = t >> 6;
-        float s = 0.0f, uu = 0.0f;
-        if (r < nreal) {
-            const int q = r / stride, f = r - q * stride;
-            if (i < (size_t)ndata) { s = fold[i] == f ? 0.0f : 1.0f; uu = b[i] * s; }
-            else { s = w[q]; uu = b[i]; }
-        }
-        scale[gbase + t] = s;
-        u[gbase + t] = uu;
-    }
-}
-
-// k_b_meas_rows with a hold predicate per lane: the squared residual d^2 of a data row goes to the member's held-out sum where the member
-// holds the row out (fold[row] == f), else to its kept sum -- the full member (f = nfolds) keeps every row, so its kept sum and its roughness
-// are k_b_meas_rows' additions in k_b_meas_rows' order.  The lane that holds row i out stores d to resid[(2 q) ndata + i], the full
-// member's lane to resid[(2 q + 1) ndata + i]: every (combo, datum) is written once in each half.  part: three sums per (g, block, lane).
-__global__ __launch_bounds__(256) void k_b_cv_rows(int m, int n, int ndata, int nb, int nreal, int stride, const long long* __restrict__ ptr,
-                                                   const float* __restrict__ val, const int* __restrict__ idx, const float* __restrict__ b,
-                                                   const int* __restrict__ fold, const float* __restrict__ x, double* __restrict__ part,
-                                                   double* __restrict__ resid)
-{
-    __shared__ double red[3][4][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, blk = blockIdx.x;
-    const int r = g * 64 + lane, q = r / stride, f = r - q * stride;
-    const bool in = r < nreal, full = f == stride - 1;
-    const float* __restrict__ p = x + (size_t)g * n * 64 + lane;
-    const int r0 = blk * kMeasR + w * (kMeasR / 4), r1 = min(r0 + kMeasR / 4, m);
-    double s0 = 0.0, sh = 0.0, s1 = 0.0;
-    for (int row = r0; row < r1; ++row) {
-        double acc = 0.0;
-        long long k = ptr[row];
-        const long long k1 = ptr[row + 1];
-        constexpr int U = 4;
-        for (; k + U <= k1; k += U) {
-            double a[U], xi[U];
+        const double* __restrict__ q = rows + (((size_t)g * nbr + b) * 64 + lane) * NS;
 #pragma unroll
-            for (int u = 0; u < U; ++u) { a[u] = (double)val[k + u]; xi[u] = (double)p[(size_t)idx[k + u] * 64]; }
+        for (int c = 0; c < NS; ++c) s[c] = s[c] + q[c];
+    }
+    for (int b = 0; b < nbx; ++b) s[NS] = s[NS] + xs[((size_t)g * nbx + b) * 64 + lane];
 #pragma unroll
-            for (int u = 0; u < U; ++u) acc = acc + a[u] * xi[u];
-        }
-        for (; k < k1; ++k) acc = acc + (double)val[k] * (double)p[(size_t)idx[k] * 64];
-        if (row < ndata) {
-            const double d = (double)b[row] - acc;
-            const bool held = fold[row] == f;
-            if (held) sh = sh + d * d;
-            else s0 = s0 + d * d;
-            if (resid && in && (held || full)) resid[(2 * (size_t)q + (full ? 1 : 0)) * (size_t)ndata + (size_t)row] = d;
-        }
-        else s1 = s1 + acc * acc;
-    }
-    red[0][w][lane] = s0; red[1][w][lane] = sh; red[2][w][lane] = s1;
-    __syncthreads();
-    if (w == 0) {
-        double* __restrict__ o = part + (((size_t)g * nb + blk) * 64 + lane) * 3;
-        for (int c = 0; c < 3; ++c) o[c] = ((red[c][0][lane] + red[c][1][lane]) + red[c][2][lane]) + red[c][3][lane];
-    }
-}
-
-// meas[4 r .. 4 r + 3] = {kept misfit, held-out misfit, roughness, sum x^2}; one thread per member
-__global__ __launch_bounds__(64) void k_b_cv_sum(int nbr, int nbx, int nreal, const double* __restrict__ rows, const double* __restrict__ xs,
-                                                 double* __restrict__ meas)
-{
-    const int lane = threadIdx.x, g = blockIdx.x, r = g * 64 + lane;
-    if (r >= nreal) return;
-    double s0 = 0.0, sh = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int b = 0; b < nbr; ++b) {
-        const double* __restrict__ q = rows + (((size_t)g * nbr + b) * 64 + lane) * 3;
-        s0 = s0 + q[0]; sh = sh + q[1]; s1 = s1 + q[2];
-    }
-    for (int b = 0; b < nbx; ++b) s2 = s2 + xs[((size_t)g * nbx + b) * 64 + lane];
-    meas[4 * (size_t)r] = s0; meas[4 * (size_t)r + 1] = sh; meas[4 * (size_t)r + 2] = s1; meas[4 * (size_t)r + 3] = s2;
+    for (int c = 0; c <= NS; ++c) meas[(NS + 1) * (size_t)r + c] = s[c];
 }
 
 // ---- dsa_lsmr_voronoi: the tessellations, every member's list for the transposed product, the projected products, the ensemble statistics ----
@@ -720,15 +692,6 @@ __global__ __launch_bounds__(256) void k_v_assign(int n, int ncells, int nreal, 
             }
         }
         if (j < n) cell_mm[(size_t)r * n + j] = bi;
-    }
-}
-
-// (g, j, l) of the batch layout <- the member-major cells (0 in the padding lanes)
-__global__ void k_v_cellmap(int n, int nreal, const int* __restrict__ cell_mm, int* __restrict__ cell)
-{
-    LB_GROUP_LOOP(n) {
-        const int r = g * 64 + (int)(t & 63);
-        cell[gbase + t] = r < nreal ? cell_mm[(size_t)r * (size_t)n + (t >> 6)] : 0;
     }
 }
 
@@ -829,7 +792,59 @@ __global__ void k_v_stats(int n, int nreal, const float* __restrict__ xf, double
     stats[(size_t)n + j] = nreal > 1 ? sqrt(ss / (double)(nreal - 1)) : 0.0;
 }
 
-// ---- the batch shared by dsa_lsmr_batch and dsa_lsmr_resolution: set-up, then (the caller fills u and the row scales) the LSMR loop ----
+// ---- the front door and the layouts of the shared buffers ----
+
+constexpr int kMaxReal = 64 * 65535;        // members of one call (gridDim.y lane groups)
+
+// The checks the five entry points share, in the order they fire, their texts carrying the entry point's name.  Each returns 0 or the
+// error it has reported.
+struct Entry {
+    const char* name;
+    Engine* e = nullptr;
+    int m = 0, n = 0;
+    // the handle, then `ok`: the caller's own test of its count (1 .. kMaxReal) and of the pointers it requires, `what` its words for them
+    int open(dsa_engine* h, bool ok, const char* what)
+    {
+        if (!h) return DSA_ERR_ARGUMENT;
+        e = reinterpret_cast<Engine*>(h);
+        if (!ok) { e->fail(DSA_ERR_ARGUMENT, "%s: %s", name, what); return DSA_ERR_ARGUMENT; }
+        return 0;
+    }
+    // a resident matrix (m, n <- its shape) and, where the entry point has data rows (ndata not null), ndata in 1 .. m
+    int matrix(const int* ndata)
+    {
+        if (!e->spmv) { e->fail(DSA_ERR_STATE, "%s: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)", name); return DSA_ERR_STATE; }
+        m = e->spmv->m; n = e->spmv->n;
+        if (ndata && (*ndata < 1 || *ndata > m)) { e->fail(DSA_ERR_ARGUMENT, "%s: ndata %d outside 1..%d", name, *ndata, m); return DSA_ERR_ARGUMENT; }
+        return 0;
+    }
+    // weight0 finite and > 0, then the `count` (weight, damp) pairs of the `noun`s ("member", "combo") finite and >= 0
+    int weights(float weight0, int count, const char* noun, const float* weight, const float* damp)
+    {
+        if (!std::isfinite(weight0) || !(weight0 > 0.0f)) { e->fail(DSA_ERR_ARGUMENT, "%s: weight0 %g is not a finite number > 0", name, (double)weight0); return DSA_ERR_ARGUMENT; }
+        for (int r = 0; r < count; ++r)
+            if (!std::isfinite(weight[r]) || weight[r] < 0.0f || !std::isfinite(damp[r]) || damp[r] < 0.0f) {
+                e->fail(DSA_ERR_ARGUMENT, "%s: %s %d has weight %g, damp %g (both must be finite and >= 0)", name, noun, r, (double)weight[r], (double)damp[r]);
+                return DSA_ERR_ARGUMENT;
+            }
+        return 0;
+    }
+};
+
+// A bump allocator over one shared device buffer (btmp: floats, ints through at<int>; bpsf: doubles).  An entry point declares its pieces
+// once, in order: take() returns a piece's offset and grows `total`, which sizes the buffer; once the buffer stands, at() is the piece's
+// pointer.  reuse() starts again at the bottom: what is taken after it lies over pieces that are dead by the time it is written.
+template <class T>
+struct Carve {
+    size_t top = 0, total = 0;
+    size_t take(size_t count) { const size_t off = top; top += count; total = std::max(total, top); return off; }
+    void reuse() { top = 0; }
+    template <class V = T>
+    V* at(const DevBuf<T>& buf, size_t off) const { static_assert(sizeof(V) == sizeof(T), "pieces are counted in units of T"); return reinterpret_cast<V*>(buf.p + off); }
+};
+
+// ---- the batch of all five entry points: set-up (batch_begin), then -- once the caller has filled u and the row scales -- the LSMR loop
+// (batch_solve) and, for two of them, the measures (batch_measures) ----
 struct Batch {
     Engine* e = nullptr;
     SpmvState* S = nullptr;
@@ -846,6 +861,7 @@ struct Batch {
     bool projected = false;          // dsa_lsmr_voronoi: product() multiplies by the member's projected matrix
     long long pnnz = 0;              // ... entries of the data rows
     int preal = 0;                   // ... members
+    float* xout = nullptr;           // the entry point's piece of btmp for the solutions on their way out (batch_solve with x)
 
     const float* coef(int f) const { return S->bparam.p + (size_t)f * Rp; }
     const int* flag(int f) const { return reinterpret_cast<const int*>(S->bparam.p + (size_t)NCOEF * Rp) + (size_t)f * Rp; }
@@ -867,12 +883,21 @@ struct Batch {
     void product(int mode, const float* pre, const int* fl)
     {
         if (projected) { projected_product(mode, pre, fl); return; }
-        if (mode == 1)
-            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, n, S->row_csr.ptr.p, rval, S->row_csr.idx.p,
-                               (const float*)S->bscale.p, (const float*)S->bv.p, S->bu.p, pre, fl);
-        else
-            hipLaunchKernelGGL(k_b_spmv<false>, dim3((unsigned)((n + 3) / 4), (unsigned)G), dim3(256), 0, st, n, m, S->col_csr.ptr.p, cval, S->col_csr.idx.p,
-                               (const float*)S->bscale.p, (const float*)S->bu.p, S->bv.p, pre, fl);
+        if (mode == 1) spmv<true>(m, n, S->row_csr, rval, S->bv.p, S->bu.p, pre, fl);
+        else spmv<false>(n, m, S->col_csr, cval, S->bu.p, S->bv.p, pre, fl);
+    }
+    // k_b_spmv over the nseg segments of a contiguous ordering M with the values val: out = pre_r out + (rows or columns) in, in of nin elements
+    template <bool ROW>
+    void spmv(int nseg, int nin, const SpmvState::Contiguous& M, const float* val, const float* in, float* out, const float* pre, const int* fl)
+    {
+        hipLaunchKernelGGL(k_b_spmv<ROW>, dim3((unsigned)((nseg + 3) / 4), (unsigned)G), dim3(256), 0, st, nseg, nin, M.ptr.p, val, M.idx.p,
+                           (const float*)S->bscale.p, in, out, pre, fl);
+    }
+    // u and the row scales of every member under `rule` from the device copies of b (none: u = 0) and of what the rule reads: par, and for
+    // FILL_WEIGHT / FILL_FOLD the first regularisation row ndata, for FILL_FOLD the members per combo and the folds
+    void fill(Fill rule, int nreal, const float* b, const float* par = nullptr, int ndata = 0, int stride = 1, const int* fold = nullptr)
+    {
+        hipLaunchKernelGGL(k_b_fill, grid_of(m, G), dim3(256), 0, st, rule, m, ndata, nreal, stride, b, par, fold, S->bscale.p, S->bu.p);
     }
     // The same for member k's M_k (the data rows, column j relabelled cell_k(j); n = ncells).  Mode 1: v expanded to the unknowns, then the
     // resident data rows (row scales 1: fl(a * 1) = a) -- row i adds a * v[cell(col)] in storage order.  Mode 2: u member-major, then
@@ -881,8 +906,7 @@ struct Batch {
     {
         if (mode == 1) {
             hipLaunchKernelGGL(k_v_expand, grid_of(nfull, G), dim3(256), 0, st, nfull, n, (const int*)S->vcell.p, (const float*)S->bv.p, S->vfull.p);
-            hipLaunchKernelGGL(k_b_spmv<true>, dim3((unsigned)((m + 3) / 4), (unsigned)G), dim3(256), 0, st, m, nfull, S->row_csr.ptr.p, rval, S->row_csr.idx.p,
-                               (const float*)S->bscale.p, (const float*)S->vfull.p, S->bu.p, pre, fl);
+            spmv<true>(m, nfull, S->row_csr, rval, S->vfull.p, S->bu.p, pre, fl);
         } else {
             hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (m + 255) / 256), (unsigned)std::min(preal, 65535)), dim3(256), 0, st, m, preal,
                                (const float*)S->bu.p, S->vut.p);
@@ -933,9 +957,9 @@ int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B, int r
 }
 
 // The LSMR loop of every realisation from u (bu) and the row scales (bscale) the caller filled: v = x = hbar = 0 (:383-385), ...;
-// istop, itn, est per realisation and, where x is not null, the solutions (realisation-major, through btmp).  bx keeps them.
-// damp: one per realisation.
-int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, float conlim, int itnlim, float* x, int* istop, int* itn, float* est)
+// istop, itn, est per realisation and, where x is not null, the solutions (realisation-major, through B.xout).  bx keeps them.
+// Realisation r is damped by damp[r / per] (per = 1: one each; nreal: one for all; nfolds + 1: one per combo).
+int batch_solve(Batch& B, int nreal, const float* damp, int per, float atol, float btol, float conlim, int itnlim, float* x, int* istop, int* itn, float* est)
 {
     Engine* e = B.e;
     SpmvState& S = *B.S;
@@ -947,15 +971,12 @@ int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, 
     const float* hred = B.hred;
     const float* dc = B.coef(0);
     const int* df = B.flag(0);
-    int rc = 0;
-#define LB_DO(call) do { if ((rc = (call)) != 0) return rc; } while (0)
-
     LB_TRY(e, hipMemsetAsync(S.bv.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bx.p, 0, vn * 4, st));
     LB_TRY(e, hipMemsetAsync(S.bhbar.p, 0, vn * 4, st));
     std::vector<LsmrScalars> P;
     P.reserve((size_t)nreal);
-    for (int r = 0; r < nreal; ++r) P.emplace_back(damp[r], atol, btol, conlim, itnlim, localVecs);
+    for (int r = 0; r < nreal; ++r) P.emplace_back(damp[r / per], atol, btol, conlim, itnlim, localVecs);
     std::vector<char> running((size_t)nreal, 0);
     std::vector<float> alpha0((size_t)nreal, 0.0f), beta0((size_t)nreal, 0.0f);
     LB_DO(B.norm(m, S.bu.p));                                                                      // beta = |u|
@@ -1047,7 +1068,6 @@ int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, 
         for (int r = 0; r < nreal; ++r)
             if (running[r] && P[r].converged(hred[r])) { running[r] = 0; --nrun; }
     }
-#undef LB_DO
     for (int r = 0; r < nreal; ++r) {
         LsmrScalars& p = P[r];
         p.finish();
@@ -1057,11 +1077,10 @@ int batch_solve(Batch& B, int nreal, const float* damp, float atol, float btol, 
     }
     if (x) {
         hipLaunchKernelGGL(k_b_gather, dim3((unsigned)std::min(1024, (n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, nreal,
-                           (const float*)S.bx.p, S.btmp.p);
-        LB_TRY(e, hipMemcpyAsync(x, S.btmp.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
+                           (const float*)S.bx.p, B.xout);
+        LB_TRY(e, hipMemcpyAsync(x, B.xout, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
     }
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
+    LB_DO(drain(e, st));
     // what bx holds now can be a later call's steps (dsa_forward_steps), unless it is in cell space (dsa_lsmr_voronoi)
     S.bx_valid = !B.projected; S.bx_nreal = nreal; S.bx_n = n;
     return 0;
@@ -1090,8 +1109,7 @@ int ensure_coef(Engine* e, int ndata, float weight0)
     }
     int bad = 0;
     LB_TRY(e, hipMemcpyAsync(&bad, S.bflag.p, 4, hipMemcpyDeviceToHost, st));
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
+    LB_DO(drain(e, st));
     if (bad) {
         e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: a regularisation entry (rows from %d up) is not an integer coefficient of 1..64 times weight0 = %g", ndata, (double)weight0);
         return DSA_ERR_ARGUMENT;
@@ -1100,12 +1118,64 @@ int ensure_coef(Engine* e, int ndata, float weight0)
     return 0;
 }
 
+// The measures of every solution in bx over the system's b (d_b) and, for HoldFold, every datum's residuals: the layout of bpsf (block
+// partials of the rows and of x, the results, the nres residuals), three launches, the copies back.  measures: Hold::kSums + 1 per member,
+// or null (then resid is not: the rows' kernel alone)
+template <class Hold>
+int batch_measures(Batch& B, int nreal, int ndata, const float* d_b, Hold hold, double* measures, double* resid, size_t nres)
+{
+    constexpr int NS = Hold::kSums;
+    Engine* e = B.e;
+    SpmvState& S = *B.S;
+    const int m = B.m, n = B.n, G = B.G;
+    hipStream_t st = B.st;
+    const int nbr = (m + kMeasR - 1) / kMeasR, nbx = (n + kMeasE - 1) / kMeasE;
+    Carve<double> P;
+    const size_t o_rows = P.take((size_t)G * nbr * 64 * NS), o_x = P.take((size_t)G * nbx * 64), o_meas = P.take((NS + 1) * (size_t)B.Rp), o_resid = P.take(nres);
+    if (e->ensure(S.bpsf, P.total)) return e->status;
+    double *d_rows = P.at(S.bpsf, o_rows), *d_x = P.at(S.bpsf, o_x), *d_meas = P.at(S.bpsf, o_meas), *d_resid = resid ? P.at(S.bpsf, o_resid) : nullptr;
+    hipLaunchKernelGGL(k_b_meas_rows<Hold>, dim3((unsigned)nbr, (unsigned)G), dim3(256), 0, st, m, n, ndata, nbr, (const long long*)S.row_csr.ptr.p,
+                       (const float*)S.row_coef.p, (const int*)S.row_csr.idx.p, d_b, (const float*)S.bx.p, d_rows, d_resid, hold);
+    if (measures) {
+        hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
+        hipLaunchKernelGGL(k_b_meas_sum<NS>, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
+        LB_TRY(e, hipMemcpyAsync(measures, d_meas, (NS + 1) * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (resid) LB_TRY(e, hipMemcpyAsync(resid, d_resid, nres * 8, hipMemcpyDeviceToHost, st));
+    return drain(e, st);
+}
+
+// dsa_lsmr_tradeoff and dsa_lsmr_crossval from the layout of btmp to the measures: nreal members on the coefficient copy, member r with
+// weight[r / per] and damp[r / per]; fold null (per = 1: every member keeps every row) or the fold of every datum (per = nfolds + 1)
+int weighted_solve(Entry& in, int nreal, int per, int ndata, const float* b, float weight0, const float* weight, const float* damp, const int* fold, float atol,
+                   float btol, float conlim, int itnlim, int localSize, float* x, double* measures, double* resid, size_t nres, int* istop, int* itn, float* est)
+{
+    Engine* e = in.e;
+    const int m = in.m, n = in.n, npar = nreal / per;
+    // btmp: the solutions on their way out (member-major), then b, the weights and the fold of every datum (b and fold stay for the measures)
+    Carve<float> T;
+    const size_t o_x = T.take(x ? (size_t)nreal * n : 0), o_b = T.take((size_t)m), o_w = T.take((size_t)npar), o_fold = T.take(fold ? (size_t)ndata : 0);
+    Batch B;
+    LB_DO(batch_begin(e, nreal, localSize, T.total, B));
+    LB_DO(ensure_coef(e, ndata, weight0));
+    SpmvState& S = *e->spmv;
+    B.rval = S.row_coef.p; B.cval = S.col_coef.p;
+    B.xout = T.at(S.btmp, o_x);
+    float *d_b = T.at(S.btmp, o_b), *d_w = T.at(S.btmp, o_w);
+    int* d_fold = fold ? T.at<int>(S.btmp, o_fold) : nullptr;
+    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, B.st));
+    LB_TRY(e, hipMemcpyAsync(d_w, weight, (size_t)npar * 4, hipMemcpyHostToDevice, B.st));
+    if (fold) LB_TRY(e, hipMemcpyAsync(d_fold, fold, (size_t)ndata * 4, hipMemcpyHostToDevice, B.st));
+    B.fill(fold ? FILL_FOLD : FILL_WEIGHT, nreal, d_b, d_w, ndata, per, d_fold);
+    LB_DO(batch_solve(B, nreal, damp, per, atol, btol, conlim, itnlim, x, istop, itn, est));
+    if (!measures && !resid) return 0;
+    if (fold) return batch_measures(B, nreal, ndata, d_b, HoldFold{d_fold, ndata, nreal, per}, measures, resid, nres);
+    return batch_measures(B, nreal, ndata, d_b, KeepAll{}, measures, nullptr, 0);
+}
+
 }  // namespace
 
 }  // namespace dsa
-
-using dsa::Engine;
-using dsa::SpmvState;
 
 extern "C" {
 
@@ -1113,205 +1183,126 @@ int dsa_lsmr_batch(dsa_engine* h_, int nreal, const float* b, const float* row_s
                    int localSize, float* x, int* istop, int* itn, float* est)
 {
     using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (nreal < 1 || nreal > 64 * 65535 || !b || !row_scale || !x || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_batch: nreal < 1 or a null argument"); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_batch: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
-    const int m = e->spmv->m, n = e->spmv->n;
+    Entry in{"lsmr_batch"};
+    LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && b && row_scale && x && istop && itn && est, "nreal < 1 or a null argument"));
+    LB_DO(in.matrix(nullptr));
+    Engine* e = in.e;
+    const int m = in.m, n = in.n;
+    // btmp: the row scales and b, dead once u is filled; the solutions on their way out lie over them
+    Carve<float> T;
+    const size_t o_rs = T.take((size_t)nreal * m), o_b = T.take((size_t)m);
+    T.reuse();
+    const size_t o_x = T.take((size_t)nreal * n);
     Batch B;
-    if (int rc = batch_begin(e, nreal, localSize, std::max((size_t)nreal * m + m, (size_t)nreal * n), B)) return rc;
+    LB_DO(batch_begin(e, nreal, localSize, T.total, B));
     SpmvState& S = *e->spmv;
-    // u = diag(s_r) b
-    float* d_rs = S.btmp.p;
-    float* d_b = S.btmp.p + (size_t)nreal * m;
+    float *d_rs = T.at(S.btmp, o_rs), *d_b = T.at(S.btmp, o_b);
+    B.xout = T.at(S.btmp, o_x);
     LB_TRY(e, hipMemcpyAsync(d_rs, row_scale, (size_t)nreal * m * 4, hipMemcpyHostToDevice, B.st));
     LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, B.st));
-    hipLaunchKernelGGL(k_b_init, grid_of(m, B.G), dim3(256), 0, B.st, m, nreal, (const float*)d_b, (const float*)d_rs, S.bscale.p, S.bu.p);
-    const std::vector<float> damps((size_t)nreal, damp);
-    return batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est);
+    B.fill(FILL_ROWS, nreal, d_b, d_rs);
+    return batch_solve(B, nreal, &damp, nreal, atol, btol, conlim, itnlim, x, istop, itn, est);
 }
 
 int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* models, int spike_first, const double* coords, float damp, float atol,
                         float btol, float conlim, int itnlim, int localSize, float* x, double* psf, int* istop, int* itn, float* est)
 {
     using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (nreal < 1 || nreal > 64 * 65535 || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: nreal < 1 or a null istop / itn / est"); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_resolution: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
-    const int m = e->spmv->m, n = e->spmv->n;
-    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    Entry in{"lsmr_resolution"};
+    LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && istop && itn && est, "nreal < 1 or a null istop / itn / est"));
+    LB_DO(in.matrix(&ndata));
+    Engine* e = in.e;
+    const int m = in.m, n = in.n;
     if (!models && (spike_first < 0 || (long long)spike_first + nreal > n)) {
         e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: spikes %d..%lld outside the %d unknowns", spike_first, (long long)spike_first + nreal - 1, n);
         return DSA_ERR_ARGUMENT;
     }
     if (psf && (models || !coords)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: psf needs spikes (models NULL) and coords"); return DSA_ERR_ARGUMENT; }
+    // btmp: the host models (realisation-major), dead once they are scattered; the solutions on their way out lie over them
+    Carve<float> T;
+    const size_t o_mod = T.take(models ? (size_t)nreal * n : 0);
+    T.reuse();
+    const size_t o_x = T.take(x ? (size_t)nreal * n : 0);
     Batch B;
-    if (int rc = batch_begin(e, nreal, localSize, (models || x) ? (size_t)nreal * n : 1, B)) return rc;
+    LB_DO(batch_begin(e, nreal, localSize, T.total, B));
     SpmvState& S = *e->spmv;
     const int G = B.G, Rp = B.Rp;
     hipStream_t st = B.st;
+    B.xout = T.at(S.btmp, o_x);
     // v = the test models, row scales 1, u = 0; u = A v over every row (k_b_spmv: fl(a * 1) = a, the chain of dsa_spmv mode 1 from y = 0),
     // then rows [ndata, m) = +0
     if (models) {
-        LB_TRY(e, hipMemcpyAsync(S.btmp.p, models, (size_t)nreal * n * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_b_scatter, grid_of(n, G), dim3(256), 0, st, n, nreal, (const float*)S.btmp.p, S.bv.p);
+        float* d_mod = T.at(S.btmp, o_mod);
+        LB_TRY(e, hipMemcpyAsync(d_mod, models, (size_t)nreal * n * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_b_scatter<float>, grid_of(n, G), dim3(256), 0, st, n, nreal, (const float*)d_mod, S.bv.p);
     } else
         hipLaunchKernelGGL(k_b_spike, grid_of(n, G), dim3(256), 0, st, n, nreal, spike_first, S.bv.p);
-    hipLaunchKernelGGL(k_b_ones, grid_of(m, G), dim3(256), 0, st, m, nreal, S.bscale.p);
-    LB_TRY(e, hipMemsetAsync(S.bu.p, 0, B.vm * 4, st));
+    B.fill(FILL_ONE, nreal, nullptr);
     for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 1;
-    if (int rc = B.upload()) return rc;
+    LB_DO(B.upload());
     B.product(1, nullptr, B.flag(F_ACT));
     if (ndata < m) hipLaunchKernelGGL(k_b_zero_rows, grid_of(m - ndata, G), dim3(256), 0, st, m, ndata, S.bu.p);
     LB_TRY(e, hipStreamSynchronize(st));                      // (the upload has landed before the host mirror changes)
     for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 0;
-    const std::vector<float> damps((size_t)nreal, damp);
-    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
+    LB_DO(batch_solve(B, nreal, &damp, nreal, atol, btol, conlim, itnlim, x, istop, itn, est));
     if (!psf) return 0;
+    // bpsf: the blocks' partials, then the results
     const int nb = (n + kPsfE - 1) / kPsfE;
-    if (e->ensure(S.bcoord, 4 * (size_t)n) || e->ensure(S.bpsf, (size_t)G * nb * 64 * 3 + 4 * (size_t)Rp)) return e->status;
-    double* d_part = S.bpsf.p;
-    double* d_psf = S.bpsf.p + (size_t)G * nb * 64 * 3;
-    double* d_cos = S.bcoord.p + 3 * (size_t)n;
+    Carve<double> P;
+    const size_t o_part = P.take((size_t)G * nb * 64 * 3), o_psf = P.take(4 * (size_t)Rp);
+    if (e->ensure(S.bcoord, 4 * (size_t)n) || e->ensure(S.bpsf, P.total)) return e->status;
+    double *d_part = P.at(S.bpsf, o_part), *d_psf = P.at(S.bpsf, o_psf), *d_cos = S.bcoord.p + 3 * (size_t)n;
     LB_TRY(e, hipMemcpyAsync(S.bcoord.p, coords, 3 * (size_t)n * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_psf_cos, dim3((unsigned)std::min(1024, (n + 255) / 256)), dim3(256), 0, st, n, (const double*)S.bcoord.p, d_cos);
     hipLaunchKernelGGL(k_b_psf_part, dim3((unsigned)nb, (unsigned)G), dim3(256), 0, st, n, nb, spike_first, (const double*)S.bcoord.p, (const double*)d_cos,
                        (const float*)S.bx.p, d_part);
     hipLaunchKernelGGL(k_b_psf_sum, dim3((unsigned)G), dim3(64), 0, st, n, nb, nreal, spike_first, (const float*)S.bx.p, (const double*)d_part, d_psf);
     LB_TRY(e, hipMemcpyAsync(psf, d_psf, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
-    return 0;
+    return drain(e, st);
 }
 
 int dsa_lsmr_tradeoff(dsa_engine* h_, int nreal, int ndata, const float* b, float weight0, const float* weight, const float* damp, float atol, float btol,
                       float conlim, int itnlim, int localSize, float* x, double* measures, int* istop, int* itn, float* est)
 {
     using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (nreal < 1 || nreal > 64 * 65535 || !b || !weight || !damp || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: nreal < 1 or a null b / weight / damp / istop / itn / est"); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_tradeoff: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
-    const int m = e->spmv->m, n = e->spmv->n;
-    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(weight0) || !(weight0 > 0.0f)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: weight0 %g is not a finite number > 0", (double)weight0); return DSA_ERR_ARGUMENT; }
-    for (int r = 0; r < nreal; ++r)
-        if (!std::isfinite(weight[r]) || weight[r] < 0.0f || !std::isfinite(damp[r]) || damp[r] < 0.0f) {
-            e->fail(DSA_ERR_ARGUMENT, "lsmr_tradeoff: member %d has weight %g, damp %g (both must be finite and >= 0)", r, (double)weight[r], (double)damp[r]);
-            return DSA_ERR_ARGUMENT;
-        }
-    Batch B;
-    // btmp: the solutions on their way out (realisation-major), then b and the weights (b stays for the measures)
-    const size_t xs = x ? (size_t)nreal * n : 0;
-    if (int rc = batch_begin(e, nreal, localSize, xs + (size_t)m + (size_t)nreal, B)) return rc;
-    if (int rc = ensure_coef(e, ndata, weight0)) return rc;
-    SpmvState& S = *e->spmv;
-    const int G = B.G, Rp = B.Rp;
-    hipStream_t st = B.st;
-    B.rval = S.row_coef.p; B.cval = S.col_coef.p;
-    float* d_b = S.btmp.p + xs;
-    float* d_w = d_b + m;
-    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    LB_TRY(e, hipMemcpyAsync(d_w, weight, (size_t)nreal * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_b_tradeoff_init, grid_of(m, G), dim3(256), 0, st, m, ndata, nreal, (const float*)d_b, (const float*)d_w, S.bscale.p, S.bu.p);
-    if (int rc = batch_solve(B, nreal, damp, atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
-    if (!measures) return 0;
-    const int nbr = (m + kMeasR - 1) / kMeasR, nbx = (n + kMeasE - 1) / kMeasE;
-    const size_t nrows = (size_t)G * nbr * 64 * 2, nx = (size_t)G * nbx * 64;
-    if (e->ensure(S.bpsf, nrows + nx + 3 * (size_t)Rp)) return e->status;
-    double* d_rows = S.bpsf.p;
-    double* d_x = d_rows + nrows;
-    double* d_meas = d_x + nx;
-    hipLaunchKernelGGL(k_b_meas_rows, dim3((unsigned)nbr, (unsigned)G), dim3(256), 0, st, m, n, ndata, nbr, (const long long*)S.row_csr.ptr.p, (const float*)S.row_coef.p,
-                       (const int*)S.row_csr.idx.p, (const float*)d_b, (const float*)S.bx.p, d_rows);
-    hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
-    hipLaunchKernelGGL(k_b_meas_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
-    LB_TRY(e, hipMemcpyAsync(measures, d_meas, 3 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
-    return 0;
+    Entry in{"lsmr_tradeoff"};
+    LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && b && weight && damp && istop && itn && est, "nreal < 1 or a null b / weight / damp / istop / itn / est"));
+    LB_DO(in.matrix(&ndata));
+    LB_DO(in.weights(weight0, nreal, "member", weight, damp));
+    return weighted_solve(in, nreal, 1, ndata, b, weight0, weight, damp, nullptr, atol, btol, conlim, itnlim, localSize, x, measures, nullptr, 0, istop, itn, est);
 }
 
 int dsa_lsmr_crossval(dsa_engine* h_, int ncombo, int nfolds, int ndata, const float* b, float weight0, const float* weight, const float* damp, const int* fold,
                       float atol, float btol, float conlim, int itnlim, int localSize, float* x, double* measures, double* resid, int* istop, int* itn, float* est)
 {
     using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (ncombo < 1 || nfolds < 1 || !b || !weight || !damp || !fold || !istop || !itn || !est) {
-        e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: ncombo < 1, nfolds < 1 or a null b / weight / damp / fold / istop / itn / est");
-        return DSA_ERR_ARGUMENT;
-    }
+    Entry in{"lsmr_crossval"};
+    LB_DO(in.open(h_, ncombo >= 1 && nfolds >= 1 && b && weight && damp && fold && istop && itn && est,
+                  "ncombo < 1, nfolds < 1 or a null b / weight / damp / fold / istop / itn / est"));
+    Engine* e = in.e;
     const long long members = (long long)ncombo * ((long long)nfolds + 1);
-    if (members > 64 * 65535) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: %d combos x (%d folds + 1) are more than the %d members one call takes", ncombo, nfolds, 64 * 65535); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_crossval: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
-    const int m = e->spmv->m, n = e->spmv->n, stride = nfolds + 1, nreal = (int)members;
-    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    if (members > kMaxReal) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: %d combos x (%d folds + 1) are more than the %d members one call takes", ncombo, nfolds, kMaxReal); return DSA_ERR_ARGUMENT; }
+    LB_DO(in.matrix(&ndata));
     size_t nres = 0;
     if (resid && (__builtin_mul_overflow((size_t)2 * (size_t)ncombo, (size_t)ndata, &nres) || nres > ((size_t)1 << 60) / 8)) {
         e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: resid of 2 x %d x %d values is more than one call takes", ncombo, ndata);
         return DSA_ERR_ARGUMENT;
     }
-    if (!std::isfinite(weight0) || !(weight0 > 0.0f)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: weight0 %g is not a finite number > 0", (double)weight0); return DSA_ERR_ARGUMENT; }
-    for (int q = 0; q < ncombo; ++q)
-        if (!std::isfinite(weight[q]) || weight[q] < 0.0f || !std::isfinite(damp[q]) || damp[q] < 0.0f) {
-            e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: combo %d has weight %g, damp %g (both must be finite and >= 0)", q, (double)weight[q], (double)damp[q]);
-            return DSA_ERR_ARGUMENT;
-        }
+    LB_DO(in.weights(weight0, ncombo, "combo", weight, damp));
     for (int i = 0; i < ndata; ++i)
         if (fold[i] < 0 || fold[i] >= nfolds) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: datum %d is in fold %d, outside 0..%d", i, fold[i], nfolds - 1); return DSA_ERR_ARGUMENT; }
-    Batch B;
-    // btmp: the solutions on their way out (member-major), then b, the combos' weights and the fold of every datum (b and fold stay for the measures)
-    const size_t xs = x ? (size_t)nreal * n : 0;
-    if (int rc = batch_begin(e, nreal, localSize, xs + (size_t)m + (size_t)ncombo + (size_t)ndata, B)) return rc;
-    if (int rc = ensure_coef(e, ndata, weight0)) return rc;
-    SpmvState& S = *e->spmv;
-    const int G = B.G, Rp = B.Rp;
-    hipStream_t st = B.st;
-    B.rval = S.row_coef.p; B.cval = S.col_coef.p;
-    float* d_b = S.btmp.p + xs;
-    float* d_w = d_b + m;
-    int* d_fold = reinterpret_cast<int*>(d_w + ncombo);
-    LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    LB_TRY(e, hipMemcpyAsync(d_w, weight, (size_t)ncombo * 4, hipMemcpyHostToDevice, st));
-    LB_TRY(e, hipMemcpyAsync(d_fold, fold, (size_t)ndata * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_b_crossval_init, grid_of(m, G), dim3(256), 0, st, m, ndata, nreal, stride, (const float*)d_b, (const float*)d_w, (const int*)d_fold,
-                       S.bscale.p, S.bu.p);
-    std::vector<float> damps((size_t)nreal);
-    for (int r = 0; r < nreal; ++r) damps[r] = damp[r / stride];
-    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, x, istop, itn, est)) return rc;
-    if (!measures && !resid) return 0;
-    const int nbr = (m + kMeasR - 1) / kMeasR, nbx = (n + kMeasE - 1) / kMeasE;
-    const size_t nrows = (size_t)G * nbr * 64 * 3, nx = (size_t)G * nbx * 64;
-    if (e->ensure(S.bpsf, nrows + nx + 4 * (size_t)Rp + nres)) return e->status;
-    double* d_rows = S.bpsf.p;
-    double* d_x = d_rows + nrows;
-    double* d_meas = d_x + nx;
-    double* d_resid = resid ? d_meas + 4 * (size_t)Rp : nullptr;
-    hipLaunchKernelGGL(k_b_cv_rows, dim3((unsigned)nbr, (unsigned)G), dim3(256), 0, st, m, n, ndata, nbr, nreal, stride, (const long long*)S.row_csr.ptr.p,
-                       (const float*)S.row_coef.p, (const int*)S.row_csr.idx.p, (const float*)d_b, (const int*)d_fold, (const float*)S.bx.p, d_rows, d_resid);
-    if (measures) {
-        hipLaunchKernelGGL(k_b_meas_x, dim3((unsigned)nbx, (unsigned)G), dim3(256), 0, st, n, nbx, (const float*)S.bx.p, d_x);
-        hipLaunchKernelGGL(k_b_cv_sum, dim3((unsigned)G), dim3(64), 0, st, nbr, nbx, nreal, (const double*)d_rows, (const double*)d_x, d_meas);
-        LB_TRY(e, hipMemcpyAsync(measures, d_meas, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (resid) LB_TRY(e, hipMemcpyAsync(resid, d_resid, nres * 8, hipMemcpyDeviceToHost, st));
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
-    return 0;
+    return weighted_solve(in, (int)members, nfolds + 1, ndata, b, weight0, weight, damp, fold, atol, btol, conlim, itnlim, localSize, x, measures, resid, nres, istop, itn, est);
 }
 
 int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const float* b, const double* xyz, const int* seeds, float damp, float atol, float btol,
                      float conlim, int itnlim, int localSize, float* z, int* cell, double* stats, int* istop, int* itn, float* est)
 {
     using namespace dsa;
-    if (!h_) return DSA_ERR_ARGUMENT;
-    Engine* e = reinterpret_cast<Engine*>(h_);
-    if (nreal < 1 || nreal > 64 * 65535 || !b || !xyz || !seeds || !istop || !itn || !est) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: nreal < 1 or a null b / xyz / seeds / istop / itn / est"); return DSA_ERR_ARGUMENT; }
-    if (!e->spmv) { e->fail(DSA_ERR_STATE, "lsmr_voronoi: no matrix (call dsa_spmv_load or dsa_iteration_system_device first)"); return DSA_ERR_STATE; }
-    const int m = e->spmv->m, n = e->spmv->n;
-    if (ndata < 1 || ndata > m) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ndata %d outside 1..%d", ndata, m); return DSA_ERR_ARGUMENT; }
+    Entry in{"lsmr_voronoi"};
+    LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && b && xyz && seeds && istop && itn && est, "nreal < 1 or a null b / xyz / seeds / istop / itn / est"));
+    LB_DO(in.matrix(&ndata));
+    Engine* e = in.e;
+    const int n = in.n;
     if (ncells < 1 || ncells > n) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ncells %d outside 1..%d", ncells, n); return DSA_ERR_ARGUMENT; }
     if (ncells > (1 << 24)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: ncells %d above %d (the sort keys are 64 ncells)", ncells, 1 << 24); return DSA_ERR_ARGUMENT; }
     if (!std::isfinite(damp)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: damp is not finite"); return DSA_ERR_ARGUMENT; }
@@ -1320,10 +1311,11 @@ int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const flo
     for (size_t i = 0; i < (size_t)nreal * ncells; ++i)
         if (seeds[i] < 0 || seeds[i] >= n) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: seed %zu of member %zu is %d, outside 0..%d", i % ncells, i / ncells, seeds[i], n - 1); return DSA_ERR_ARGUMENT; }
     if ((size_t)((ncells + 3) / 4) * (size_t)nreal > 0x7fffffffu) { e->fail(DSA_ERR_ARGUMENT, "lsmr_voronoi: %d members of %d cells are more than one call takes", nreal, ncells); return DSA_ERR_ARGUMENT; }
-    Batch B;
     // btmp: the solutions on their way out (member-major), then b
-    const size_t zs = z ? (size_t)nreal * ncells : 0;
-    if (int rc = batch_begin(e, nreal, localSize, zs + (size_t)ndata, B, ndata, ncells)) return rc;
+    Carve<float> T;
+    const size_t o_z = T.take(z ? (size_t)nreal * ncells : 0), o_b = T.take((size_t)ndata);
+    Batch B;
+    LB_DO(batch_begin(e, nreal, localSize, T.total, B, ndata, ncells));
     SpmvState& S = *e->spmv;
     const int G = B.G, Rp = B.Rp;
     hipStream_t st = B.st;
@@ -1341,7 +1333,7 @@ int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const flo
     LB_TRY(e, hipMemcpyAsync(S.vseeds.p, seeds, (size_t)nreal * ncells * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_v_assign, dim3((unsigned)((n + 255) / 256), (unsigned)std::min(nreal, 65535)), dim3(256), 0, st, n, ncells, nreal, (const double*)S.vxyz.p,
                        (const int*)S.vseeds.p, S.vcell_mm.p);
-    hipLaunchKernelGGL(k_v_cellmap, grid_of(n, G), dim3(256), 0, st, n, nreal, (const int*)S.vcell_mm.p, S.vcell.p);
+    hipLaunchKernelGGL(k_b_scatter<int>, grid_of(n, G), dim3(256), 0, st, n, nreal, (const int*)S.vcell_mm.p, S.vcell.p);      // [group][unknown][64]
     // every member's list: the data rows' CSR positions, stably sorted by cell, one lane group per sort
     LB_TRY(e, hipMemsetAsync(S.vcptr.p, 0, (size_t)Rp * (ncells + 1) * 4, st));
     if (nnz > 0) {
@@ -1363,14 +1355,14 @@ int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const flo
                                S.vcptr.p + (size_t)g * 64 * (ncells + 1));
         }
     }
-    // u = b, row scales 1 (k_b_tradeoff_init with every row a data row: it reads no weight), then the loop on the projected products
-    float* d_b = S.btmp.p + zs;
+    // u = b, row scales 1, then the loop on the projected products
+    B.xout = T.at(S.btmp, o_z);
+    float* d_b = T.at(S.btmp, o_b);
     LB_TRY(e, hipMemcpyAsync(d_b, b, (size_t)ndata * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_b_tradeoff_init, grid_of(ndata, G), dim3(256), 0, st, ndata, ndata, nreal, (const float*)d_b, (const float*)nullptr, S.bscale.p, S.bu.p);
+    B.fill(FILL_ONE, nreal, d_b);
     LB_TRY(e, hipGetLastError());
     B.projected = true; B.pnnz = nnz; B.preal = nreal;
-    const std::vector<float> damps((size_t)nreal, damp);
-    if (int rc = batch_solve(B, nreal, damps.data(), atol, btol, conlim, itnlim, z, istop, itn, est)) return rc;
+    LB_DO(batch_solve(B, nreal, &damp, nreal, atol, btol, conlim, itnlim, z, istop, itn, est));
     if (cell) LB_TRY(e, hipMemcpyAsync(cell, S.vcell_mm.p, (size_t)nreal * n * 4, hipMemcpyDeviceToHost, st));
     if (stats) {
         // x_k[j] = z_k[cell_k(j)] on the unknowns (the expansion of mode 1, of the solutions), then its statistics over k in order
@@ -1378,9 +1370,7 @@ int dsa_lsmr_voronoi(dsa_engine* h_, int nreal, int ndata, int ncells, const flo
         hipLaunchKernelGGL(k_v_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, nreal, (const float*)S.vfull.p, S.vstats.p);
         LB_TRY(e, hipMemcpyAsync(stats, S.vstats.p, 2 * (size_t)n * 8, hipMemcpyDeviceToHost, st));
     }
-    LB_TRY(e, hipGetLastError());
-    LB_TRY(e, hipStreamSynchronize(st));
-    return 0;
+    return drain(e, st);
 }
 
 }  // extern "C"

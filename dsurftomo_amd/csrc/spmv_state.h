@@ -56,14 +56,18 @@ struct SpmvState {
     int coef_ndata = 0;
     float coef_weight0 = 0.0f;
     DevBuf<int> bflag;               // ... the flag its validation reports
-    // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l
+    // batch vectors, realisations in groups of 64, one per lane: element i of realisation 64 g + l at (g * len + i) * 64 + l.  btmp is not
+    // one of them: every entry point of lsmr_batch.hip carves it into its own pieces (the solutions on their way out, b, weights, folds,
+    // row scales or host models, realisation-major), which live for that call alone
     DevBuf<float> bu, bv, bh, bhbar, bx, blocalV, bscale, bparam, bred, btmp, bterm, bpmax;
     // the solutions a batch solve left in bx, for dsa_forward_steps / dsa_step_models with steps == NULL: set by a successful batch solve in the
     // space of the unknowns (bx_n = the matrix's columns then), cleared when a batch begins, when the resident matrix is loaded or edited, and
     // by dsa_lsmr_voronoi, whose bx is in cell space
     bool bx_valid = false;
     int bx_nreal = 0, bx_n = 0;
-    DevBuf<double> bcoord, bpsf;     // dsa_lsmr_resolution: coordinates of the unknowns, the PSF measures' block partials and results (bpsf: dsa_lsmr_tradeoff's measures too)
+    // bcoord: dsa_lsmr_resolution's coordinates of the unknowns and their cosines.  bpsf: the fp64 measures of a call, carved per call into
+    // block partials, results and (dsa_lsmr_crossval) residuals -- dsa_lsmr_resolution's PSFs, dsa_lsmr_tradeoff's and dsa_lsmr_crossval's measures
+    DevBuf<double> bcoord, bpsf;
     // dsa_lsmr_voronoi: per call, the tessellations (vxyz: points of the unknowns; vseeds: seed unknowns, member-major; vcell_mm: cell of every
     // unknown, member-major; vcell: the same as [group][unknown][64]), the data rows' CSR positions sorted by cell per member (vlist, with
     // vcptr: ncells + 1 pointers per member; vrowof: row of every position), the operands of the projected products (vfull: v expanded to the

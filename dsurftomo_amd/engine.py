@@ -37,8 +37,6 @@ def load_library():
     L.dsa_create.argtypes = [C.POINTER(_vp), _i32]
     L.dsa_destroy.argtypes = [_vp]
     L.dsa_destroy.restype = None
-    L.dsa_error_string.argtypes = [_vp]
-    L.dsa_error_string.restype = C.c_char_p
     L.dsa_set_memory_budget.argtypes = [_vp, C.c_size_t]
     L.dsa_set_option.argtypes = [_vp, C.c_char_p, C.c_double]
     L.dsa_set_maps.argtypes = [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp]
@@ -72,12 +70,6 @@ def load_library():
     L.dsa_ray_paths.argtypes = [_vp, _vp, _vp, _vp]
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_spmv.argtypes = [_vp, _i32, _vp, _vp]
-    L.dsa_lsmr.argtypes = [_vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp] + [_vp] * 7
-    L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]
-    L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
-    L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
-    L.dsa_lsmr_crossval.argtypes = [_vp, _i32, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.dsa_lsmr_voronoi.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
     if hasattr(L, "dsa_selfcheck_trip"):         # (absent from older libraries: same-box A/B runs, DSA_LIB_PATH)
@@ -85,12 +77,36 @@ def load_library():
     L.dsa_dropin_error.restype = C.c_char_p
     L.dsa_dropin_set_capacity.argtypes = [C.c_longlong]
     L.dsa_aprod_invalidate.argtypes = []
-    _lib = L
+    _lib = declare_solvers(L)
+    return L
+
+
+def declare_solvers(L):
+    """argtypes / restype of the dsa_lsmr* family and of what the inversion driver calls around it (the system builders, the model update,
+    the drop-in engine, the error text), on any handle of the library: load_library's own, or a bare ctypes.CDLL (invert.bind).  The one
+    place they are declared.  Returns L."""
+    solve = [_f32] * 3 + [_i32] * 2                                   # atol, btol, conlim, itnlim, localSize
+    L.dsa_error_string.argtypes = [_vp]
+    L.dsa_error_string.restype = C.c_char_p
+    L.dsa_dropin_engine.argtypes = []
+    L.dsa_dropin_engine.restype = _vp
+    L.dsa_iteration_system.argtypes = [_i32] * 4 + [C.c_longlong] * 2 + [_vp] * 5 + [_f32] * 2 + [_vp] * 6
+    L.dsa_iteration_system_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 2 + [_vp] * 6
+    L.dsa_model_update.argtypes = [_i32] * 3 + [_vp] * 2 + [_f32] * 2
+    L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
+    L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
+    L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32] + solve + [_vp] * 5
+    L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp] + solve + [_vp] * 5
+    L.dsa_lsmr_crossval.argtypes = [_vp] + [_i32] * 3 + [_vp, _f32] + [_vp] * 3 + solve + [_vp] * 6
+    L.dsa_lsmr_voronoi.argtypes = [_vp] + [_i32] * 3 + [_vp] * 3 + [_f32] + solve + [_vp] * 6
     return L
 
 
 def _p(a):
     return a.ctypes.data_as(_vp) if a is not None and a.size else None
+
+
+EST_NAMES = ("normA", "condA", "normr", "normAr", "normx")
 
 
 def selfcheck_divisions(seed, millions, exponents8):
@@ -318,8 +334,16 @@ class Engine:
         ff = [C.c_float(0.0) for _ in range(5)]
         self._check(self._L.dsa_lsmr(self._h, _p(b), damp, atol, btol, conlim, int(itnlim), int(local_size), _p(x),
                                      *[C.byref(v) for v in ii], *[C.byref(v) for v in ff]))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(x=x, istop=ii[0].value, itn=ii[1].value, **{k: np.float32(v.value) for k, v in zip(names, ff)})
+        return dict(x=x, istop=ii[0].value, itn=ii[1].value, **{k: np.float32(v.value) for k, v in zip(EST_NAMES, ff)})
+
+    def _batch(self, fn, R, head, solve, **out):
+        """One call of a batch entry point: fn(handle, *head, atol, btol, conlim, itnlim, localSize, *out, istop, itn, est) for R solves,
+        arrays passed by pointer and None as NULL.  Returns dict(**out, istop=(R,), itn=(R,), one (R,) array per name of EST_NAMES)."""
+        ptr = lambda a: _p(a) if isinstance(a, np.ndarray) else a
+        istop, itn, est = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros((R, 5), np.float32)
+        atol, btol, conlim, itnlim, local_size = solve
+        self._check(fn(self._h, *map(ptr, head), atol, btol, conlim, int(itnlim), int(local_size), *map(ptr, out.values()), ptr(istop), ptr(itn), ptr(est)))
+        return dict(**out, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(EST_NAMES)})
 
     def lsmr_batch(self, b, row_scale, damp, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
         """R LSMR solves on the matrix of the last spmv_load: realisation r with its rows scaled by row_scale[r] (shape (R, m)),
@@ -331,13 +355,7 @@ class Engine:
         assert b.size == m and s.ndim == 2 and s.shape[1] == m
         R = s.shape[0]
         x = np.zeros((R, n), np.float32)
-        istop = np.zeros(R, np.int32)
-        itn = np.zeros(R, np.int32)
-        est = np.zeros((R, 5), np.float32)
-        self._check(self._L.dsa_lsmr_batch(self._h, R, _p(b), _p(s), damp, atol, btol, conlim, int(itnlim), int(local_size), _p(x), _p(istop),
-                                           _p(itn), _p(est)))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(x=x, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+        return self._batch(self._L.dsa_lsmr_batch, R, (R, b, s, damp), (atol, btol, conlim, itnlim, local_size), x=x)
 
     def lsmr_resolution(self, ndata, damp, models=None, spikes=None, coords=None, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400,
                         local_size=10):
@@ -356,13 +374,7 @@ class Engine:
         xyz = None if coords is None else np.ascontiguousarray(coords, np.float64)
         x = np.zeros((R, n), np.float32) if want_x else None
         psf = np.zeros((R, 4)) if xyz is not None else None
-        istop = np.zeros(R, np.int32)
-        itn = np.zeros(R, np.int32)
-        est = np.zeros((R, 5), np.float32)
-        self._check(self._L.dsa_lsmr_resolution(self._h, R, int(ndata), _p(mod), first, _p(xyz), damp, atol, btol, conlim, int(itnlim),
-                                                int(local_size), _p(x), _p(psf), _p(istop), _p(itn), _p(est)))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(x=x, psf=psf, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+        return self._batch(self._L.dsa_lsmr_resolution, R, (R, int(ndata), mod, first, xyz, damp), (atol, btol, conlim, itnlim, local_size), x=x, psf=psf)
 
     def lsmr_tradeoff(self, b, ndata, weight0, weights, damps, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
         """K LSMR solves on the matrix of the last spmv_load, whose rows from ndata up are regularisation rows built with weight0:
@@ -378,14 +390,7 @@ class Engine:
         K = w.size
         x = np.zeros((K, n), np.float32) if want_x else None
         meas = np.zeros((K, 3))
-        istop = np.zeros(K, np.int32)
-        itn = np.zeros(K, np.int32)
-        est = np.zeros((K, 5), np.float32)
-        self._check(self._L.dsa_lsmr_tradeoff(self._h, K, int(ndata), _p(b), weight0, w.ctypes.data_as(_vp), d.ctypes.data_as(_vp), atol, btol, conlim,
-                                              int(itnlim), int(local_size), _p(x), _p(meas), istop.ctypes.data_as(_vp), itn.ctypes.data_as(_vp),
-                                              est.ctypes.data_as(_vp)))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(x=x, measures=meas, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+        return self._batch(self._L.dsa_lsmr_tradeoff, K, (K, int(ndata), b, weight0, w, d), (atol, btol, conlim, itnlim, local_size), x=x, measures=meas)
 
     def lsmr_crossval(self, b, ndata, weight0, weights, damps, fold, nfolds, want_x=True, want_resid=True, atol=1e-6, btol=1e-6, conlim=100.0,
                       itnlim=400, local_size=10):
@@ -406,14 +411,8 @@ class Engine:
         x = np.zeros((K, n), np.float32) if want_x else None
         meas = np.zeros((K, 4))
         resid = np.zeros((nc, 2, nd)) if want_resid else None
-        istop = np.zeros(K, np.int32)
-        itn = np.zeros(K, np.int32)
-        est = np.zeros((K, 5), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_vp)
-        self._check(self._L.dsa_lsmr_crossval(self._h, nc, int(nfolds), int(ndata), ptr(b), weight0, ptr(w), ptr(d), ptr(fo), atol, btol, conlim,
-                                              int(itnlim), int(local_size), ptr(x), ptr(meas), ptr(resid), ptr(istop), ptr(itn), ptr(est)))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(x=x, measures=meas, resid=resid, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+        return self._batch(self._L.dsa_lsmr_crossval, K, (nc, int(nfolds), int(ndata), b, weight0, w, d, fo), (atol, btol, conlim, itnlim, local_size),
+                           x=x, measures=meas, resid=resid)
 
     def lsmr_voronoi(self, b, ndata, ncells, xyz, seeds, damp, want_z=True, want_cell=True, want_stats=True, atol=1e-6, btol=1e-6, conlim=100.0,
                      itnlim=400, local_size=10):
@@ -432,14 +431,8 @@ class Engine:
         z = np.zeros((K, max(int(ncells), 0)), np.float32) if want_z else None
         cell = np.zeros((K, n), np.int32) if want_cell else None
         stats = np.zeros((2, n)) if want_stats else None
-        istop = np.zeros(K, np.int32)
-        itn = np.zeros(K, np.int32)
-        est = np.zeros((K, 5), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_vp)
-        self._check(self._L.dsa_lsmr_voronoi(self._h, K, int(ndata), int(ncells), ptr(b), ptr(pts), ptr(sd), damp, atol, btol, conlim, int(itnlim),
-                                             int(local_size), ptr(z), ptr(cell), ptr(stats), ptr(istop), ptr(itn), ptr(est)))
-        names = ("normA", "condA", "normr", "normAr", "normx")
-        return dict(z=z, cell=cell, stats=stats, istop=istop, itn=itn, **{k: est[:, j].copy() for j, k in enumerate(names)})
+        return self._batch(self._L.dsa_lsmr_voronoi, K, (K, int(ndata), int(ncells), b, pts, sd, damp), (atol, btol, conlim, itnlim, local_size),
+                           z=z, cell=cell, stats=stats)
 
     def traveltimes(self, map_index, scx, scz, nrec, rcx, rcz):
         self.plan(map_index, scx, scz, nrec, rcx, rcz)

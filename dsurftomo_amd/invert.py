@@ -107,13 +107,16 @@ import time
 import numpy as np
 
 from . import io
-from .engine import load_library
+from .engine import declare_solvers, load_library
 
 EARTH_KM = 6371.0                # the sphere of the PSF lengths (dsa_lsmr_resolution)
+# atol, btol, conlim, itnlim, localSize of every LSMR solve here (main.f90:470-489); LOCAL_SIZE is what the *_chunk defaults size for
+LSMR_ARGS = (1e-6, 1e-6, 100.0, 400, 10)
+LOCAL_SIZE = LSMR_ARGS[4]
 
 
 def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _f10(v):
@@ -216,13 +219,17 @@ def batch_bytes(m, n, local_size, nreal):
     return 4 * floats
 
 
+def _fit(k, step, bytes_of, budget):
+    """k lowered in steps of `step` until bytes_of(k) fits `budget` (step at the least)"""
+    while k > step and bytes_of(k) > budget:
+        k -= step
+    return k
+
+
 def resolution_chunk(m, n, local_size, budget=32 << 30, cap=4096):
     """spikes per dsa_lsmr_resolution call on an m x n system: cap, lowered in multiples of 64 until batch_bytes fits `budget`
     (64 at the least)"""
-    k = cap
-    while k > 64 and batch_bytes(m, n, local_size, k) > budget:
-        k -= 64
-    return k
+    return _fit(cap, 64, lambda k: batch_bytes(m, n, local_size, k), budget)
 
 
 def tradeoff_bytes(m, n, nar, local_size, nreal):
@@ -236,10 +243,7 @@ def tradeoff_bytes(m, n, nar, local_size, nreal):
 def tradeoff_chunk(m, n, nar, local_size, budget=32 << 30, cap=4096):
     """members per dsa_lsmr_tradeoff call on an m x n system of nar entries: cap, lowered in multiples of 64 until tradeoff_bytes fits
     `budget` (64 at the least)"""
-    k = cap
-    while k > 64 and tradeoff_bytes(m, n, nar, local_size, k) > budget:
-        k -= 64
-    return k
+    return _fit(cap, 64, lambda k: tradeoff_bytes(m, n, nar, local_size, k), budget)
 
 
 def voronoi_xyz(c, zscale=1.0):
@@ -316,10 +320,7 @@ def voronoi_bytes(ndata, n, ncells, nnz, local_size, nreal):
 
 def voronoi_chunk(ndata, n, ncells, nnz, local_size, budget=32 << 30, cap=4096):
     """members per dsa_lsmr_voronoi call: cap, lowered in multiples of 64 until voronoi_bytes fits `budget` (64 at the least)"""
-    k = cap
-    while k > 64 and voronoi_bytes(ndata, n, ncells, nnz, local_size, k) > budget:
-        k -= 64
-    return k
+    return _fit(cap, 64, lambda k: voronoi_bytes(ndata, n, ncells, nnz, local_size, k), budget)
 
 
 def parse_voronoi(text):
@@ -538,10 +539,7 @@ def crossval_chunk(m, n, nar, local_size, ncombo, nfolds, ndata, budget=32 << 30
     """combos per dsa_lsmr_crossval call: a call holds whole combos (its members are a multiple of nfolds + 1, so every datum's held-out
     and full member sit in one call) -- as many as give at most `cap` members, lowered one combo at a time until crossval_bytes fits
     `budget` (1 at the least)"""
-    k = max(1, min(int(ncombo), cap // (nfolds + 1)))
-    while k > 1 and crossval_bytes(m, n, nar, local_size, k, nfolds, ndata) > budget:
-        k -= 1
-    return k
+    return _fit(max(1, min(int(ncombo), cap // (nfolds + 1))), 1, lambda k: crossval_bytes(m, n, nar, local_size, k, nfolds, ndata), budget)
 
 
 def write_crossval(path, members):
@@ -804,6 +802,19 @@ def write_residuals(path, c, dsyn, obst, datweight):
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
 
 
+def _pass_result(r, dv, ii, **arrays):
+    """what iteration() and iteration_device() return of a pass: the statistics of the weighted residuals r (mean and standard deviation in
+    fp32 as main.f90 forms them, in ms; rms) and of the update dv as it stands (before it is clamped into the model), LSMR's (istop, itn) = ii,
+    dv and the pass's own arrays"""
+    f = np.float32
+    nd = r.size
+    mean = f(r.sum(dtype=f) / f(nd))
+    std = f(np.sqrt(f((r * r).sum(dtype=f) / f(nd)) - mean * mean))
+    rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(nd))
+    return dict(mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(f(dv.min())), dv_max=float(f(dv.max())),
+                itn=ii[1].value, istop=ii[0].value, dv=dv, **arrays)
+
+
 def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tradeoff=None, voronoi=None, crossval=None, line_search=None):
     """One pass of main.f90:349-535 with the matrix resident on the device from CalSurfG to LSMR: dsa_calsurfg leaves the
     rows there (null rw / iw / col), dsa_iteration_system_device applies weights / appends the regularisation rows / builds
@@ -850,8 +861,7 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     ii = [C.c_int(0), C.c_int(0)]
     ff = [C.c_float(0) for _ in range(5)]
     t0 = time.perf_counter()
-    rc = lib.dsa_lsmr(eng, _p(cbst), C.c_float(c["damp"]), C.c_float(1e-6), C.c_float(1e-6), C.c_float(100.0), 400, 10, _p(dv),
-                      C.byref(ii[0]), C.byref(ii[1]), *[C.byref(v) for v in ff])
+    rc = lib.dsa_lsmr(eng, _p(cbst), C.c_float(c["damp"]), *LSMR_ARGS, _p(dv), C.byref(ii[0]), C.byref(ii[1]), *[C.byref(v) for v in ff])
     if rc != 0:
         raise RuntimeError("dsa_lsmr: %s" % lib.dsa_error_string(eng).decode())
     t_lsmr = time.perf_counter() - t0
@@ -872,7 +882,7 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
     cv_resident = False
     if crossval:
         ncombo = len(crossval["weights"]) * len(crossval["damps"])
-        cv_chunk = int(crossval.get("chunk") or crossval_chunk(m.value, maxvp, nar2.value, 10, ncombo, int(crossval["nfolds"]), dall))
+        cv_chunk = int(crossval.get("chunk") or crossval_chunk(m.value, maxvp, nar2.value, LOCAL_SIZE, ncombo, int(crossval["nfolds"]), dall))
         cv_resident = bool(crossval.get("nonlinear")) and ncombo <= cv_chunk and not voronoi
         cv = lsmr_crossval_sweep(lib, eng, c, cbst, m.value, nar2.value, crossval["weights"], crossval["damps"], crossval["fold"], crossval["nfolds"],
                                  cv_chunk, crossval.get("want_x", False) or (bool(crossval.get("nonlinear")) and not cv_resident))
@@ -883,11 +893,8 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
                                     voronoi.get("damp"), voronoi.get("chunk"))
         if voronoi.get("update"):
             dv = np.ascontiguousarray(vor["mean"].astype(f))
-    r = cbst[:dall]
-    mean = f(r.sum(dtype=f) / f(dall))
-    std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
-    rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))
-    dv_raw = (f(dv.min()), f(dv.max()))
+    out = _pass_result(cbst[:dall], dv, ii, dsyn=dsyn, datweight=datweight, nar=nar2.value, m=m.value, dws=(float(dws[0]), float(dws[1])),
+                       seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), norm=norm, cbst=cbst)
     trade_nl = cv_nl = None
     if crossval and crossval.get("nonlinear"):
         K = cv["weight"].size * (cv["nfolds"] + 1)
@@ -901,9 +908,6 @@ def iteration_device(lib, c, vsf, obst, log, bootstrap=None, resolution=None, tr
         vsf[...] = ls["models"][ls["chosen"]]
     else:
         lib.dsa_model_update(nx, ny, nz, _p(dv), _p(vsf), c["minvel"], c["maxvel"])
-    out = dict(dsyn=dsyn, datweight=datweight, mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(dv_raw[0]),
-               dv_max=float(dv_raw[1]), itn=ii[1].value, istop=ii[0].value, nar=nar2.value, m=m.value, dws=(float(dws[0]), float(dws[1])),
-               seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), dv=dv, norm=norm, cbst=cbst)
     if ls is not None:
         out["line_search"] = ls
     if boot is not None:
@@ -933,8 +937,7 @@ def lsmr_bootstrap(lib, eng, c, cbst, m, nreal, seed):
     x = np.zeros((nreal, maxvp), f)
     istop = np.zeros(nreal, np.int32); itn = np.zeros(nreal, np.int32); est = np.zeros((nreal, 5), f)
     t0 = time.perf_counter()
-    rc = lib.dsa_lsmr_batch(eng, nreal, _p(cbst), _p(scales), C.c_float(c["damp"]), C.c_float(1e-6), C.c_float(1e-6), C.c_float(100.0), 400, 10,
-                            _p(x), _p(istop), _p(itn), _p(est))
+    rc = lib.dsa_lsmr_batch(eng, nreal, _p(cbst), _p(scales), C.c_float(c["damp"]), *LSMR_ARGS, _p(x), _p(istop), _p(itn), _p(est))
     if rc != 0:
         raise RuntimeError("dsa_lsmr_batch: %s" % lib.dsa_error_string(eng).decode())
     seconds = time.perf_counter() - t0
@@ -944,19 +947,17 @@ def lsmr_bootstrap(lib, eng, c, cbst, m, nreal, seed):
 def _lsmr_resolution(lib, eng, c, nreal, istop, itn, models=None, first=0, coords=None, x=None, psf=None):
     """one dsa_lsmr_resolution call with the arguments of the dsa_lsmr call above; istop / itn / x / psf filled in place"""
     est = np.zeros((nreal, 5), np.float32)
-    opt = lambda a: None if a is None else _p(a)
-    rc = lib.dsa_lsmr_resolution(eng, nreal, c["ndata"], opt(models), first, opt(coords), C.c_float(c["damp"]), C.c_float(1e-6), C.c_float(1e-6),
-                                 C.c_float(100.0), 400, 10, opt(x), opt(psf), _p(istop), _p(itn), _p(est))
+    rc = lib.dsa_lsmr_resolution(eng, nreal, c["ndata"], _p(models), first, _p(coords), C.c_float(c["damp"]), *LSMR_ARGS, _p(x), _p(psf), _p(istop), _p(itn), _p(est))
     if rc != 0:
         raise RuntimeError("dsa_lsmr_resolution: %s" % lib.dsa_error_string(eng).decode())
 
 
 def resolution_psf(lib, eng, c, m, chunk=None):
     """The point-spread function of every unknown of the resident m-row system: spikes in chunks of `chunk` (default
-    resolution_chunk(m, maxvp, 10)), one dsa_lsmr_resolution call each, x left on the device, only the PSF measures returned.
+    resolution_chunk(m, maxvp, LOCAL_SIZE)), one dsa_lsmr_resolution call each, x left on the device, only the PSF measures returned.
     Returns dict(psf=(maxvp, 4) {R_jj, sum x^2, sum x^2 dh^2, sum x^2 dz^2}, itn, istop, chunk, calls, seconds)."""
     n = c["nparpi"]
-    chunk = int(chunk or resolution_chunk(m, n, 10))
+    chunk = int(chunk or resolution_chunk(m, n, LOCAL_SIZE))
     coords = np.ascontiguousarray(unknown_coords(c))
     psf = np.zeros((n, 4))
     istop = np.zeros(n, np.int32); itn = np.zeros(n, np.int32)
@@ -985,14 +986,14 @@ def checkerboard_tests(lib, eng, c, cells):
 
 def lsmr_tradeoff_sweep(lib, eng, c, cbst, m, nar, weights, damps, chunk=None):
     """The trade-off sweep of the resident m-row system of nar entries (regularisation rows built with the input file's weight0): the
-    members of tradeoff_grid(weights, damps) in chunks of `chunk` (default tradeoff_chunk(m, maxvp, nar, 10)), one dsa_lsmr_tradeoff call
+    members of tradeoff_grid(weights, damps) in chunks of `chunk` (default tradeoff_chunk(m, maxvp, nar, LOCAL_SIZE)), one dsa_lsmr_tradeoff call
     each with the arguments of the dsa_lsmr call above.  Returns dict(weight, damp (K,), x=(K, maxvp) raw updates, measures=(K, 3)
     {sum r^2, sum (C x)^2, sum x^2}, itn, istop, est=(K, 5), chunk, calls, seconds)."""
     f = np.float32
     n = c["nparpi"]
     w, d = tradeoff_grid(weights, damps)
     K = w.size
-    chunk = int(chunk or tradeoff_chunk(m, n, nar, 10))
+    chunk = int(chunk or tradeoff_chunk(m, n, nar, LOCAL_SIZE))
     x = np.zeros((K, n), f); meas = np.zeros((K, 3))
     istop = np.zeros(K, np.int32); itn = np.zeros(K, np.int32); est = np.zeros((K, 5), f)
     t0 = time.perf_counter()
@@ -1000,8 +1001,8 @@ def lsmr_tradeoff_sweep(lib, eng, c, cbst, m, nar, weights, damps, chunk=None):
     for first in range(0, K, chunk):
         q = slice(first, min(first + chunk, K))
         wk, dk = np.ascontiguousarray(w[q]), np.ascontiguousarray(d[q])
-        rc = lib.dsa_lsmr_tradeoff(eng, wk.size, c["ndata"], _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), C.c_float(1e-6), C.c_float(1e-6),
-                                   C.c_float(100.0), 400, 10, _p(x[q]), _p(meas[q]), _p(istop[q]), _p(itn[q]), _p(est[q]))
+        rc = lib.dsa_lsmr_tradeoff(eng, wk.size, c["ndata"], _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), *LSMR_ARGS, _p(x[q]), _p(meas[q]),
+                                   _p(istop[q]), _p(itn[q]), _p(est[q]))
         if rc != 0:
             raise RuntimeError("dsa_lsmr_tradeoff: %s" % lib.dsa_error_string(eng).decode())
         calls += 1
@@ -1021,7 +1022,7 @@ def lsmr_crossval_sweep(lib, eng, c, cbst, m, nar, weights, damps, fold, nfolds,
     nc, S = w.size, int(nfolds) + 1
     K = nc * S
     fold = np.ascontiguousarray(fold, np.int32)
-    chunk = int(chunk or crossval_chunk(m, n, nar, 10, nc, int(nfolds), nd))
+    chunk = int(chunk or crossval_chunk(m, n, nar, LOCAL_SIZE, nc, int(nfolds), nd))
     x = np.zeros((K, n), f) if want_x else None
     meas = np.zeros((K, 4)); resid = np.zeros((nc, 2, nd))
     istop = np.zeros(K, np.int32); itn = np.zeros(K, np.int32); est = np.zeros((K, 5), f)
@@ -1031,8 +1032,8 @@ def lsmr_crossval_sweep(lib, eng, c, cbst, m, nar, weights, damps, fold, nfolds,
         q = slice(first, min(first + chunk, nc))
         k = slice(q.start * S, q.stop * S)
         wk, dk = np.ascontiguousarray(w[q]), np.ascontiguousarray(d[q])
-        rc = lib.dsa_lsmr_crossval(eng, wk.size, int(nfolds), nd, _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), _p(fold), C.c_float(1e-6), C.c_float(1e-6),
-                                   C.c_float(100.0), 400, 10, _p(x[k]) if want_x else None, _p(meas[k]), _p(resid[q]), _p(istop[k]), _p(itn[k]), _p(est[k]))
+        rc = lib.dsa_lsmr_crossval(eng, wk.size, int(nfolds), nd, _p(cbst), C.c_float(c["weight0"]), _p(wk), _p(dk), _p(fold), *LSMR_ARGS,
+                                   _p(x[k]) if want_x else None, _p(meas[k]), _p(resid[q]), _p(istop[k]), _p(itn[k]), _p(est[k]))
         if rc != 0:
             raise RuntimeError("dsa_lsmr_crossval: %s" % lib.dsa_error_string(eng).decode())
         calls += 1
@@ -1052,7 +1053,7 @@ def lsmr_voronoi_ensemble(lib, eng, c, cbst, nnz, nreal, ncells, seed, zscale=1.
     damp = float(c["damp"]) if damp is None else float(damp)
     xyz = np.ascontiguousarray(voronoi_xyz(c, zscale))
     seeds = np.ascontiguousarray(voronoi_seeds(n, ncells, nreal, seed))
-    chunk = int(chunk or voronoi_chunk(nd, n, ncells, int(nnz), 10))
+    chunk = int(chunk or voronoi_chunk(nd, n, ncells, int(nnz), LOCAL_SIZE))
     istop = np.zeros(nreal, np.int32); itn = np.zeros(nreal, np.int32); est = np.zeros((nreal, 5), f)
     single = nreal <= chunk
     stats = np.zeros((2, n))
@@ -1065,9 +1066,8 @@ def lsmr_voronoi_ensemble(lib, eng, c, cbst, nnz, nreal, ncells, seed, zscale=1.
         sd = np.ascontiguousarray(seeds[q])
         z = None if single else np.zeros((k, ncells), f)
         cell = None if single else np.zeros((k, n), np.int32)
-        opt = lambda a: None if a is None else _p(a)
-        rc = lib.dsa_lsmr_voronoi(eng, k, nd, ncells, _p(cbst), _p(xyz), _p(sd), C.c_float(damp), C.c_float(1e-6), C.c_float(1e-6), C.c_float(100.0), 400, 10,
-                                  opt(z), opt(cell), _p(stats) if single else None, _p(istop[q]), _p(itn[q]), _p(est[q]))
+        rc = lib.dsa_lsmr_voronoi(eng, k, nd, ncells, _p(cbst), _p(xyz), _p(sd), C.c_float(damp), *LSMR_ARGS, _p(z), _p(cell), _p(stats) if single else None,
+                                  _p(istop[q]), _p(itn[q]), _p(est[q]))
         if rc != 0:
             raise RuntimeError("dsa_lsmr_voronoi: %s" % lib.dsa_error_string(eng).decode())
         if not single:
@@ -1120,37 +1120,20 @@ def iteration(lib, c, vsf, obst, log):
     f32 = lambda v: C.byref(C.c_float(float(v)))
     n = nar2.value
     t0 = time.perf_counter()
-    rc = lib.dsa_lsmr_dropin(i32(m.value), i32(maxvp), i32(2 * n + 1), i32(n), _p(iw), _p(rw), _p(cbst), f32(c["damp"]), f32(1e-6), f32(1e-6),
-                             f32(100.0), i32(400), i32(10), i32(0), _p(dv), C.byref(ii[0]), C.byref(ii[1]), *[C.byref(v) for v in ff])
+    rc = lib.dsa_lsmr_dropin(i32(m.value), i32(maxvp), i32(2 * n + 1), i32(n), _p(iw), _p(rw), _p(cbst), f32(c["damp"]), *map(f32, LSMR_ARGS[:3]),
+                             *map(i32, LSMR_ARGS[3:]), i32(0), _p(dv), C.byref(ii[0]), C.byref(ii[1]), *[C.byref(v) for v in ff])
     if rc != 0:
         raise RuntimeError("dsa_lsmr_dropin: %s" % lib.dsa_dropin_error().decode())
     t_lsmr = time.perf_counter() - t0
-    r = cbst[:dall]
-    mean = f(r.sum(dtype=f) / f(dall))
-    std = f(np.sqrt(f((r * r).sum(dtype=f) / f(dall)) - mean * mean))
-    rms = f(np.sqrt((r.astype(np.float64) ** 2).sum()) / np.sqrt(dall))
-    dv_raw = (f(dv.min()), f(dv.max()))
+    out = _pass_result(cbst[:dall], dv, ii, dsyn=dsyn, datweight=datweight, nar=n, m=m.value, dws=(float(dws[0]), float(dws[1])),
+                       seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), norm=norm, cbst=cbst)
     lib.dsa_model_update(nx, ny, nz, _p(dv), _p(vsf), c["minvel"], c["maxvel"])
-    return dict(dsyn=dsyn, datweight=datweight, mean_ms=1e3 * float(mean), std_ms=1e3 * float(std), rms=float(rms), dv_min=float(dv_raw[0]),
-                dv_max=float(dv_raw[1]), itn=ii[1].value, istop=ii[0].value, nar=n, m=m.value, dws=(float(dws[0]), float(dws[1])),
-                seconds=dict(forward=t_fwd, glue=t_glue, lsmr=t_lsmr), dv=dv, norm=norm, cbst=cbst)
+    return out
 
 
 def bind(lib):
-    lib.dsa_iteration_system.argtypes = [C.c_int] * 4 + [C.c_longlong] * 2 + [C.c_void_p] * 5 + [C.c_float] * 2 + [C.c_void_p] * 6
-    lib.dsa_iteration_system_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float] * 2 + [C.c_void_p] * 6
-    lib.dsa_model_update.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_float] * 2
-    lib.dsa_dropin_engine.restype = C.c_void_p
-    lib.dsa_dropin_engine.argtypes = []
-    lib.dsa_lsmr.argtypes = [C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 8
-    lib.dsa_lsmr_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 4
-    lib.dsa_lsmr_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 5
-    lib.dsa_lsmr_tradeoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p] + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5
-    lib.dsa_lsmr_crossval.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_float] + [C.c_void_p] * 3 + [C.c_float] * 3 + [C.c_int] * 2 + [C.c_void_p] * 6
-    lib.dsa_lsmr_voronoi.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_void_p] * 6
-    lib.dsa_error_string.restype = C.c_char_p
-    lib.dsa_error_string.argtypes = [C.c_void_p]
-    return lib
+    """the argtypes of what this module calls, on load_library()'s handle or a bare ctypes.CDLL of the library (engine.declare_solvers)"""
+    return declare_solvers(lib)
 
 
 def check_bootstrap(bootstrap, host_rows):
@@ -1183,22 +1166,32 @@ def check_resolution(resolution, checkerboards, host_rows, chunk=None):
         raise ValueError("resolution_chunk must be at least 1 (got %d)" % chunk)
 
 
+def _check_values(*options):
+    """every (option name, value list or None) given: at least one value, every one finite and >= 0"""
+    for name, vals in options:
+        if vals is None:
+            continue
+        vals = list(vals)
+        if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
+            raise ValueError("%s takes at least one value, every one finite and >= 0 (got %r)" % (name, vals))
+
+
+def _check_outer(name, iteration, maxiter):
+    """the outer iteration an option names lies in 1..maxiter"""
+    if iteration < 1 or (maxiter is not None and iteration > maxiter):
+        raise ValueError("%s must be an outer iteration 1..maxiter (got %d%s)" % (name, iteration, "" if maxiter is None else ", maxiter %d" % maxiter))
+
+
 def check_tradeoff(weights, damps, iteration, host_rows, maxiter=None, chunk=None):
     """the trade-off sweep's preconditions, checked before anything touches the GPU (weights None: no sweep)"""
     if weights is None:
         if damps is not None:
             raise ValueError("--tradeoff-damps needs --tradeoff-weights")
         return
-    for name, vals in (("--tradeoff-weights", weights), ("--tradeoff-damps", damps)):
-        if vals is None:
-            continue
-        vals = list(vals)
-        if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
-            raise ValueError("%s takes at least one value, every one finite and >= 0 (got %r)" % (name, vals))
+    _check_values(("--tradeoff-weights", weights), ("--tradeoff-damps", damps))
     if host_rows:
         raise ValueError("--tradeoff-weights solves on the device-resident system: it cannot be combined with --host-rows")
-    if iteration < 1 or (maxiter is not None and iteration > maxiter):
-        raise ValueError("--tradeoff-iter must be an outer iteration 1..maxiter (got %d%s)" % (iteration, "" if maxiter is None else ", maxiter %d" % maxiter))
+    _check_outer("--tradeoff-iter", iteration, maxiter)
     if chunk is not None and (chunk < 64 or chunk % 64):
         raise ValueError("tradeoff_chunk must be a multiple of 64 (got %d)" % chunk)
 
@@ -1213,18 +1206,12 @@ def check_crossval(nfolds, weights=None, damps=None, by="datum", iteration=1, ho
         raise ValueError("--crossval needs at least 2 folds (got %r)" % (nfolds,))
     if weights is None:
         raise ValueError("--crossval needs --crossval-weights")
-    for name, vals in (("--crossval-weights", weights), ("--crossval-damps", damps)):
-        if vals is None:
-            continue
-        vals = list(vals)
-        if not vals or not all(np.isfinite(v) and v >= 0 for v in vals):
-            raise ValueError("%s takes at least one value, every one finite and >= 0 (got %r)" % (name, vals))
+    _check_values(("--crossval-weights", weights), ("--crossval-damps", damps))
     if by not in ("datum", "path"):
         raise ValueError("--crossval-by is datum or path (got %r)" % (by,))
     if host_rows:
         raise ValueError("--crossval solves on the device-resident system: it cannot be combined with --host-rows")
-    if iteration < 1 or (maxiter is not None and iteration > maxiter):
-        raise ValueError("--crossval-iter must be an outer iteration 1..maxiter (got %d%s)" % (iteration, "" if maxiter is None else ", maxiter %d" % maxiter))
+    _check_outer("--crossval-iter", iteration, maxiter)
     if chunk is not None and chunk < 1:
         raise ValueError("crossval_chunk must be at least 1 combo (got %d)" % chunk)
 
