@@ -363,15 +363,17 @@ int dsa_dropin_set_capacity(long long maxnar)
     return 0;
 }
 
-int dsa_calsurfg(const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
-                 int* iw, float* rw, int* col, float* dsurf,
-                 const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
-                 const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
-                 const double* tRc, const double* tRg, const double* tLc, const double* tLg,
-                 const int* wavetype, const int* igrt, const int* periods, const float* depz,
-                 const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
-                 const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
-                 const int* nsrcsurf, const int* nrcf, int* nar)
+// dsa_calsurfg, and (azimuthal) dsa_calsurfg_azimuthal: the same call whose rays keep the 2psi slabs and whose rows carry the gc and gs
+// blocks behind the isotropic entries, for the Rayleigh depth-kernel slots (engine.hip: solve_azimuthal)
+static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
+                         int* iw, float* rw, int* col, float* dsurf,
+                         const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                         const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                         const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                         const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                         const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                         const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                         const int* nsrcsurf, const int* nrcf, int* nar)
 {
     (void)nparpi;
     // rw, iw and col may be null TOGETHER: the rows then stay on the device (extension; dsa_iteration_system_device / dsa_lsmr
@@ -381,6 +383,8 @@ int dsa_calsurfg(const int* nx, const int* ny, const int* nz, const int* nparpi,
     int rc = engine();
     if (rc != 0) return rc;
     if (device_rows && g_pool.size() != 1) { g_dropin_error = "dsa_calsurfg: rows can only stay on the device with one engine (DSA_DEVICES unset)"; return DSA_ERR_STATE; }
+    if (azimuthal && device_rows) { g_dropin_error = "dsa_calsurfg_azimuthal: null argument (the azimuthal rows are host rows)"; return DSA_ERR_ARGUMENT; }
+    if (azimuthal && g_pool.size() != 1) { g_dropin_error = "dsa_calsurfg_azimuthal: one engine only (DSA_DEVICES unset): the azimuthal call is not sharded over GPUs"; return DSA_ERR_STATE; }
     const Layout L = make_layout(*kmaxRc, *kmaxRg, *kmaxLc, *kmaxLg, *kmax, true);
     if (L.kRc + L.kRg + L.kLc + L.kLg != L.kmax) { g_dropin_error = "dsa_calsurfg: kmax must equal kmaxRc+kmaxRg+kmaxLc+kmaxLg"; return DSA_ERR_ARGUMENT; }
     Units U;
@@ -451,6 +455,12 @@ int dsa_calsurfg(const int* nx, const int* ny, const int* nz, const int* nparpi,
         if (ne == 1) {
             if ((r = dsa_plan_units(e, nu, U.map.data(), U.sx.data(), U.sz.data(), U.nrec.data(), U.rx.data(), U.rz.data(), U.mode.data(), U.slot.data(), U.data.data())) != 0) return bad(r);
             en->rows_on_device = device_rows;
+            if (azimuthal) {       // Rayleigh slots (phase, then group) on, Love slots off
+                std::vector<int> on((size_t)L.kmax, 0);
+                for (int q = 0; q < L.sLc; ++q) on[(size_t)q] = 1;
+                if ((r = dsa_set_azimuthal_slots(e, L.kmax, on.data())) != 0) return bad(r);
+                r = dsa_solve_rows_azimuthal(e, dsurf, rw, iw + 1, col, cap, &P.n);
+            } else
             r = dsa_solve_rows(e, dsurf, rw, device_rows ? nullptr : iw + 1, col, cap, &P.n);          // the reference fills iw(nar+1)
         } else {
             // this engine's units, in call order, with their receivers gathered; data indices stay those of the whole call
@@ -519,8 +529,37 @@ int dsa_calsurfg(const int* nx, const int* ny, const int* nz, const int* nparpi,
     g_rbint_notes = first_clamped >= 0 ? U.niter - U.iter[(size_t)first_clamped] : 0;
     if (n > INT_MAX) { g_dropin_error = "dsa_calsurfg: more than 2^31-1 matrix entries"; return DSA_ERR_ARGUMENT; }
     *nar = (int)n;
+    if (azimuthal) iw[0] = (int)n;
     remember(L, *nx * *ny, true);
     return 0;
+}
+
+int dsa_calsurfg(const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
+                 int* iw, float* rw, int* col, float* dsurf,
+                 const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                 const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                 const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                 const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                 const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                 const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                 const int* nsrcsurf, const int* nrcf, int* nar)
+{
+    return calsurfg_call(false, nx, ny, nz, nparpi, vels, iw, rw, col, dsurf, goxdf, gozdf, dvxdf, dvzdf, kmaxRc, kmaxRg, kmaxLc, kmaxLg, tRc, tRg, tLc, tLg,
+                         wavetype, igrt, periods, depz, minthk, scxf, sczf, rcxf, rczf, nrc1, nsrcsurf1, kmax, nsrcsurf, nrcf, nar);
+}
+
+int dsa_calsurfg_azimuthal(const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
+                           int* iw, float* rw, int* col, float* dsurf,
+                           const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                           const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                           const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                           const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                           const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                           const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                           const int* nsrcsurf, const int* nrcf, int* nar)
+{
+    return calsurfg_call(true, nx, ny, nz, nparpi, vels, iw, rw, col, dsurf, goxdf, gozdf, dvxdf, dvzdf, kmaxRc, kmaxRg, kmaxLc, kmaxLg, tRc, tRg, tLc, tLg,
+                         wavetype, igrt, periods, depz, minthk, scxf, sczf, rcxf, rczf, nrc1, nsrcsurf1, kmax, nsrcsurf, nrcf, nar);
 }
 
 int dsa_dropin_dispersion_failure(int index, int* info, double* vals, float* table, double* c)

@@ -219,6 +219,17 @@ struct Engine {
     int ray_path_cap = 0;              // > 0: keep up to that many points of every traced ray (dsa_ray_paths)
     DevBuf<float> paths;               // [traced ray][point][colatitude, longitude]
     DevBuf<int> path_n;                // points of every traced ray
+    // azimuthal rows (dsa_solve_rows_azimuthal): a ray keeps three slabs [iso | c | s], its row the isotropic block and
+    // the gc and gs blocks behind it.  Nothing here is allocated before the first azimuthal solve.
+    bool azi_now = false;              // the running solve is an azimuthal one (trace_chunk)
+    bool sazi_ready = false;           // Sazi is that of the current depth kernels
+    DevBuf<double> Sazi;               // depth factor of the gc / gs entries (ray_kernels.hip: k_sen_azimuthal)
+    std::vector<unsigned char> h_azi_slot_on;      // dsa_set_azimuthal_slots: per depth-kernel slot, 0 = no gc / gs entries; empty = all on
+    DevBuf<unsigned char> azi_slot_on;
+    bool have_azi = false;             // the last azimuthal solve of this plan succeeded: the sums below are its rays'
+    std::vector<float> h_azi_sums;     // per traced ray of the plan (position in h_trace, like the path store): sum of cos 2psi, of sin 2psi over its steps
+    std::vector<int> h_azi_steps;      // ... and its steps
+    int solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar);
 
     // dispersion stage (disp_kernels.hip): Vs model -> pv maps + depth kernels, all resident
     bool disp_ready = false;

@@ -88,7 +88,7 @@ Engine::~Engine()
     rel(src); rel(rays); rel(out); rel(err);
     rel(slow_r); rel(F_r); rel(Tfin_r); rel(S_r); rel(risti_r); rel(vcorner); rel(seed_r); rel(nseed_r); rel(launch_rank); rel(slowI); rel(B_pool); rel(exc_b); rel(lists_b); rel(bpool_gen); rel(member_flag); rel(bundles_d);
     rel(rst); rel(cst); rel(cinit); rel(heap); rel(flags); rel(T_c); rel(exc_c); rel(W_c); rel(seed_c); rel(nseed_c);
-    rel(prob_r); rel(prob_c); rel(paths); rel(path_n); rel(info); rel(clocks); rel(lists);
+    rel(prob_r); rel(prob_c); rel(paths); rel(path_n); rel(Sazi); rel(azi_slot_on); rel(info); rel(clocks); rel(lists);
     rel(Srow); rel(sen_vs); rel(sen_vp); rel(sen_rho); rel(vels_d); rel(trace_ids); rel(vlist); rel(nvv); rel(counts); rel(offsets);
     rel(coo_col); rel(coo_iw); rel(slabs); rel(coo_rw); rel(rayinfo); rel(G_rw); rel(G_row); rel(G_col);
     rel(geom); rel(pvstore); rel(curves); rel(tper); rel(disp_ws);
@@ -228,7 +228,7 @@ int Engine::dispersion_commit(bool host_copy)
     disp_fail_count = 0;
     disp_model_fail.assign((size_t)disp_nmodels, 0);
     disp_failures.clear();
-    have_sens = false;
+    have_sens = false; sazi_ready = false;
     stats[DSA_STAT_MS_DISPERSION] = 0.0;
     stats[DSA_STAT_CURVES] = 0.0;
     return 0;
@@ -420,7 +420,7 @@ int Engine::kernels_from_dispersion()
     launch_sen_combine((int)ncol, disp_kmax_total, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, Srow.p, stream);
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
-    sens_nz = disp_nz; sens_kmax = disp_kmax_total; have_sens = true;
+    sens_nz = disp_nz; sens_kmax = disp_kmax_total; have_sens = true; sazi_ready = false;
     return 0;
 }
 
@@ -453,6 +453,7 @@ int Engine::plan(int nunits, const int* map_index, const float* scx, const float
     if (nr > 0 && (!rcx || !rcz)) { fail(DSA_ERR_ARGUMENT, "plan: receivers missing"); return DSA_ERR_ARGUMENT; }
     h_rays.resize(nr);
     h_trace.clear();
+    have_azi = false;
     ndata = 0;
     for (int u = 0; u < nunits; ++u)
         for (int k = 0; k < h_src[u].nrec; ++k) {
@@ -1516,7 +1517,7 @@ int Engine::set_sensitivity(int nz, int kmax, const float* vels, const float* de
     launch_sen_combine((int)ncol, kmax, nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, depz[nz - 2] < 35.0f ? 1 : 0, Srow.p, stream);
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
-    sens_nz = nz; sens_kmax = kmax; have_sens = true;
+    sens_nz = nz; sens_kmax = kmax; have_sens = true; sazi_ready = false;
     return 0;
 }
 
@@ -1529,7 +1530,9 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
     const size_t t0 = std::lower_bound(h_trace.begin(), h_trace.end(), r0) - h_trace.begin();
     const size_t t1 = std::lower_bound(h_trace.begin(), h_trace.end(), r1) - h_trace.begin();
     if (t1 <= t0) return 0;
-    const size_t slab_stride = (size_t)(g.nvx + 2) * (g.nvz + 2), vlist_stride = (size_t)g.nvx * g.nvz;
+    // (an azimuthal solve: three slabs per ray [iso | c | s] and four info words, ray_kernels.hip)
+    const size_t slab_len = (size_t)(g.nvx + 2) * (g.nvz + 2), slab_stride = (azi_now ? 3 : 1) * slab_len, vlist_stride = (size_t)g.nvx * g.nvz;
+    const size_t info_words = azi_now ? 4 : 2;
     const size_t per_ray = (slab_stride + vlist_stride) * 4 + 32;
     size_t budget = ray_budget;
     if (!budget) {
@@ -1540,13 +1543,16 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
     size_t per = std::max<size_t>(budget / per_ray, 64);
     per = std::max<size_t>(std::min(per, t1 - t0), 1);
     if (ensure(slabs, per * slab_stride) || ensure(vlist, per * vlist_stride) || ensure(nvv, per) || ensure(counts, per) ||
-        ensure(offsets, per + 1) || ensure(rayinfo, per * 2)) return status;
+        ensure(offsets, per + 1) || ensure(rayinfo, per * info_words)) return status;
+    RowAziArgs z{};
+    z.Sazi = Sazi.p; z.slab_len = slab_len; z.slot_on = azi_slot_on.p; z.maxvp = g.nvx * g.nvz * (sens_nz - 1);
+    auto emit = [&](const RowArgs& a, bool write) { if (azi_now) launch_row_emit_azi(g, a, z, write, stream); else launch_row_emit(g, a, write, stream); };
     std::vector<int32_t> h_info;
     hipEvent_t ea = events[1], eb = events[2], ec = events[3];
     for (size_t t = t0; t < t1; t += per) {
         const int m = (int)std::min(per, t1 - t);
         HIP_TRY(this, hipEventRecord(ea, stream));
-        HIP_TRY(this, hipMemsetAsync(slabs.p, 0, (size_t)m * slab_stride * 4, stream));
+        HIP_TRY(this, hipMemsetAsync(slabs.p, 0, (size_t)m * slab_stride * 4, stream));      // (all three slabs of an azimuthal ray)
         float* d_paths = nullptr;
         int* d_path_n = nullptr;
         if (ray_path_cap > 0) {     // the store covers all traced rays of the plan (position in h_trace)
@@ -1554,19 +1560,19 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
             d_paths = paths.p + t * (size_t)ray_path_cap * 2; d_path_n = path_n.p + t;
         }
         launch_rays(g, batch(), first_unit, rays.p, trace_ids.p + t, m, veln.p, nfield, dpl, slabs.p, slab_stride, rayinfo.p, err.p,
-                    d_paths, ray_path_cap, d_path_n, stream, ray_lanes_opt ? ray_lanes_opt : (m <= kRayGroupMax ? 4 : 1));
+                    d_paths, ray_path_cap, d_path_n, stream, ray_lanes_opt ? ray_lanes_opt : (m <= kRayGroupMax ? 4 : 1), azi_now);
         HIP_TRY(this, hipEventRecord(eb, stream));
         RowArgs a{};
         a.rays = rays.p; a.trace_ids = trace_ids.p + t; a.n = m; a.src = src.p; a.unit_base = first_unit;
         a.slabs = slabs.p; a.slab_stride = slab_stride; a.vlist = vlist.p; a.vlist_stride = vlist_stride; a.nv = nvv.p;
         a.S = Srow.p; a.kmax = sens_kmax; a.nz = sens_nz; a.counts = counts.p; a.offsets = offsets.p;
         launch_row_list(g, a, stream);
-        launch_row_emit(g, a, false, stream);
+        emit(a, false);
         launch_scan(counts.p, m, offsets.p, stream);
         long long total = 0;
         HIP_TRY(this, hipMemcpyAsync(&total, offsets.p + m, 8, hipMemcpyDeviceToHost, stream));
-        h_info.resize((size_t)m * 2);
-        HIP_TRY(this, hipMemcpyAsync(h_info.data(), rayinfo.p, (size_t)m * 8, hipMemcpyDeviceToHost, stream));
+        h_info.resize((size_t)m * info_words);
+        HIP_TRY(this, hipMemcpyAsync(h_info.data(), rayinfo.p, (size_t)m * info_words * 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(this, hipStreamSynchronize(stream));
         if (*nar + total > cap) { fail(DSA_ERR_CAPACITY, "Frechet rows need more than the %lld entries provided", cap); return DSA_ERR_CAPACITY; }
         if (total > 0 && grow_rw && grow_iw && grow_col) {
@@ -1578,7 +1584,7 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
             const size_t need = (size_t)(*nar + total);
             if (ensure_keep(G_rw, need, (size_t)*nar) || ensure_keep(G_row, need, (size_t)*nar) || ensure_keep(G_col, need, (size_t)*nar)) return status;
             a.rw = G_rw.p + *nar; a.iw = G_row.p + *nar; a.col = G_col.p + *nar;
-            launch_row_emit(g, a, true, stream);
+            emit(a, true);
             if (rw && iw && col) {
                 HIP_TRY(this, hipMemcpyAsync(rw + *nar, a.rw, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
                 HIP_TRY(this, hipMemcpyAsync(iw + *nar, a.iw, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
@@ -1588,7 +1594,7 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
         } else if (total > 0) {
             if (ensure(coo_rw, (size_t)total) || ensure(coo_iw, (size_t)total) || ensure(coo_col, (size_t)total)) return status;
             a.rw = coo_rw.p; a.iw = coo_iw.p; a.col = coo_col.p;
-            launch_row_emit(g, a, true, stream);
+            emit(a, true);
             HIP_TRY(this, hipMemcpyAsync(rw + *nar, coo_rw.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
             HIP_TRY(this, hipMemcpyAsync(iw + *nar, coo_iw.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
             HIP_TRY(this, hipMemcpyAsync(col + *nar, coo_col.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
@@ -1601,9 +1607,15 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
         HIP_TRY(this, hipEventElapsedTime(&ms, ea, eb)); stats[DSA_STAT_MS_RAYS] += ms;
         HIP_TRY(this, hipEventElapsedTime(&ms, eb, ec)); stats[DSA_STAT_MS_ROWS] += ms;
         stats[DSA_STAT_RAYS] += m;
+        stats[DSA_STAT_RAY_LAUNCHES] += 1;
         for (int q = 0; q < m; ++q) {
-            stats[DSA_STAT_RAY_STEPS] += h_info[2 * q + 1]; stats[DSA_STAT_RAYS_CLAMPED] += h_info[2 * q] & 1;
-            if (h_info[2 * q] & 1) {
+            const int32_t* hi = &h_info[info_words * (size_t)q];
+            if (azi_now) {
+                h_azi_steps[t + (size_t)q] = hi[1];
+                std::memcpy(&h_azi_sums[2 * (t + (size_t)q)], hi + 2, 8);
+            }
+            stats[DSA_STAT_RAY_STEPS] += hi[1]; stats[DSA_STAT_RAYS_CLAMPED] += hi[0] & 1;
+            if (hi[0] & 1) {
                 const int unit = h_rays[(size_t)h_trace[t + (size_t)q]].src;
                 rays_clamped += 1;
                 if (first_clamped_unit < 0 || unit < first_clamped_unit) first_clamped_unit = unit;
@@ -1612,6 +1624,40 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
     }
     stats[DSA_STAT_NAR] = (double)*nar;
     return 0;
+}
+
+// dsa_solve_rows_azimuthal: solve() with three slabs per ray and the gc / gs blocks behind every ray's isotropic entries (ray_kernels.hip:
+// k_rays<., true>, k_row_emit_azi).  The depth factor Sazi is built here, the first time it is needed for the current depth kernels.
+int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar)
+{
+    have_azi = false;
+    if (rows_on_device) { fail(DSA_ERR_STATE, "solve_rows_azimuthal: host rows only (option rows_on_device is set)"); return DSA_ERR_STATE; }
+    if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_azimuthal: one engine only"); return DSA_ERR_STATE; }
+    if (!planned) { fail(DSA_ERR_STATE, "solve: call dsa_plan first"); return DSA_ERR_STATE; }
+    if (!have_sens) { fail(DSA_ERR_STATE, "solve: Frechet rows need the depth kernels (dsa_set_depth_kernels / dsa_depthkernel) first"); return DSA_ERR_STATE; }
+    const long long maxvp = (long long)g.nvx * g.nvz * (sens_nz - 1);
+    if (3 * maxvp > 0x7fffffffLL) { fail(DSA_ERR_ARGUMENT, "solve_rows_azimuthal: %lld columns do not fit an int", 3 * maxvp); return DSA_ERR_ARGUMENT; }
+    if (!h_azi_slot_on.empty() && (int)h_azi_slot_on.size() != sens_kmax) { fail(DSA_ERR_ARGUMENT, "solve_rows_azimuthal: dsa_set_azimuthal_slots gave %d slots, the depth kernels have %d", (int)h_azi_slot_on.size(), sens_kmax); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)g.nx * g.ny;
+    if (!sazi_ready) {
+        if (ensure(Sazi, ncol * sens_kmax * (sens_nz - 1))) return status;
+        launch_sen_azimuthal((int)ncol, sens_kmax, sens_nz, vels_d.p, sen_vs.p, Sazi.p, stream);
+        HIP_TRY(this, hipGetLastError());
+        sazi_ready = true;
+    }
+    std::vector<unsigned char> on = h_azi_slot_on;
+    if (on.empty()) on.assign((size_t)sens_kmax, 1);
+    if (ensure(azi_slot_on, on.size())) return status;
+    HIP_TRY(this, hipMemcpyAsync(azi_slot_on.p, on.data(), on.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    h_azi_sums.assign(2 * h_trace.size(), 0.0f);
+    h_azi_steps.assign(h_trace.size(), 0);
+    azi_now = true;
+    const int rc = solve(dsurf, rw, iw, col, cap, nar);
+    azi_now = false;
+    have_azi = rc == 0;
+    return rc;
 }
 
 // download tiled records and untile on the host: which = 0 -> T (raw), 1 -> tau (raw)
@@ -1897,6 +1943,37 @@ int dsa_solve_rows(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, lo
     if ((!rw || !iw || !col) && !en->rows_on_device) return DSA_ERR_ARGUMENT;
     if (!rw || !iw || !col) { rw = nullptr; iw = nullptr; col = nullptr; }
     return en->solve(dsurf, rw, iw, col, capacity, nar);
+}
+
+int dsa_solve_rows_azimuthal(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar)
+{
+    if (!e || !nar || !rw || !iw || !col) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->solve_azimuthal(dsurf, rw, iw, col, capacity, nar);
+}
+
+int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on)
+{
+    if (!e || (on && kmax < 1)) return DSA_ERR_ARGUMENT;
+    Engine* en = reinterpret_cast<Engine*>(e);
+    en->h_azi_slot_on.clear();
+    if (on) for (int k = 0; k < kmax; ++k) en->h_azi_slot_on.push_back(on[k] != 0 ? 1 : 0);
+    return 0;
+}
+
+// for the R traced rays (DSA_STAT_RAYS) of the last dsa_solve_rows_azimuthal, in data order: the datum (1-based row), the gradient steps
+// taken and the sums of cos 2psi and sin 2psi over them (sums[2 r], sums[2 r + 1])
+int dsa_ray_azimuths(dsa_engine* e, int* datum, int* nsteps, float* sums)
+{
+    if (!e || !datum || !nsteps || !sums) return DSA_ERR_ARGUMENT;
+    Engine* en = reinterpret_cast<Engine*>(e);
+    if (!en->have_azi) { en->fail(DSA_ERR_STATE, "ray_azimuths: call dsa_solve_rows_azimuthal first"); return DSA_ERR_STATE; }
+    const size_t nr = en->h_trace.size();
+    for (size_t r = 0; r < nr; ++r) {
+        datum[r] = en->h_rays[(size_t)en->h_trace[r]].data + 1;
+        nsteps[r] = en->h_azi_steps[r];
+        sums[2 * r] = en->h_azi_sums[2 * r]; sums[2 * r + 1] = en->h_azi_sums[2 * r + 1];
+    }
+    return 0;
 }
 
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz)

@@ -244,12 +244,16 @@ void launch_srtimes(const GridDesc& g, const BatchPtrs& b, int unit_base, const 
 // launch owns slab t (slab_stride floats, zeroed by the caller) and rayinfo[2t..2t+1] = (flags, steps); lanes_per_ray: 1, or 4 (small launches)
 void launch_rays(const GridDesc& g, const BatchPtrs& b, int unit_base, const RayDesc* d_rays, const int* d_trace_ids, int n,
                  const float* d_veln_all, size_t field_stride, float dpl, float* d_slabs, size_t slab_stride,
-                 int32_t* d_rayinfo, int32_t* d_err, float* d_paths, int path_cap, int* d_path_n, hipStream_t stream, int lanes_per_ray = 1);
+                 int32_t* d_rayinfo, int32_t* d_err, float* d_paths, int path_cap, int* d_path_n, hipStream_t stream, int lanes_per_ray = 1,
+                 bool azimuthal = false /* slab_stride spans the ray's three slabs [iso | c | s]; d_rayinfo: four words per ray (ray_kernels.hip) */);
 
 // S[(k * kmax + slot) * ncol + c] = (sen_vp * coe_a + sen_rho * coe_rho) + sen_vs, the depth-kernel
 // factor of a Frechet row entry (reference CalSurfG.f90:1395-1423); vels: (nz, ny*nx) fp32
 void launch_sen_combine(int ncol, int kmax, int nz, const float* d_vels, const double* d_sen_vs, const double* d_sen_vp,
                         const double* d_sen_rho, int shallow, double* d_S, hipStream_t stream);
+
+// Sazi[(k * kmax + slot) * ncol + c] = sen_vs * (double)(0.5f * vels): the depth factor of the gc / gs entries
+void launch_sen_azimuthal(int ncol, int kmax, int nz, const float* d_vels, const double* d_sen_vs, double* d_Sazi, hipStream_t stream);
 
 struct RowArgs {
     const RayDesc* rays; const int* trace_ids; int n;      // the rays of this launch
@@ -263,6 +267,13 @@ struct RowArgs {
 };
 void launch_row_list(const GridDesc& g, const RowArgs& a, hipStream_t stream);
 void launch_row_emit(const GridDesc& g, const RowArgs& a, bool write, hipStream_t stream);
+// azimuthal rows: a.slab_stride spans a ray's three slabs of slab_len floats; per ray the isotropic block, then gc, then gs
+struct RowAziArgs {
+    const double* Sazi; size_t slab_len;
+    const unsigned char* slot_on;                          // [kmax]: 0 = units of that depth-kernel slot emit no gc / gs entries
+    int maxvp;                                             // nvx * nvz * (nz - 1): columns of one block
+};
+void launch_row_emit_azi(const GridDesc& g, const RowArgs& a, const RowAziArgs& z, bool write, hipStream_t stream);
 // offsets[0..n] = exclusive prefix sums of counts[0..n-1]
 void launch_scan(const int* d_counts, int n, long long* d_offsets, hipStream_t stream);
 

@@ -192,10 +192,15 @@ struct RayPath {
 };
 
 // returns 0, or -1 when the receiver lies outside the grid; *flags bit 0 = the ray was clamped at
-// the model edge (reference rbint), *nsteps = gradient steps taken
-template <int LPR = 1>
+// the model edge (reference rbint), *nsteps = gradient steps taken.
+// AZI (azimuthal anisotropy): `slab` is the ray's three slabs [iso | c | s], (nvx+2)(nvz+2) floats each; every
+// sub-segment contribution r1 of the isotropic sum goes into the c and s slabs as r1 cos 2psi and r1 sin 2psi of its step, through two more
+// patches that move with the isotropic one (the same order of operations per vertex), and azi_sums[2] receives the sums of cos 2psi
+// and sin 2psi over the steps taken (sequential, fp32).  psi = azimuth of propagation, clockwise from north, from the step's gradient:
+// dtx points south, dtz east, and 2 psi is the same for either sense of travel.
+template <int LPR = 1, bool AZI = false>
 DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f, float rcx, float rcz,
-                     float dpl_cell, float* slab, int* flags, int* nsteps, RayPath* path = nullptr, int sub = 0)
+                     float dpl_cell, float* slab, int* flags, int* nsteps, RayPath* path = nullptr, int sub = 0, float* azi_sums = nullptr)
 {
     const int nnx = g.nnx, nnz = g.nnz;
     const float gox = g.gox, goz = g.goz, dnx = g.dnx, dnz = g.dnz, earth = g.earth;
@@ -226,6 +231,13 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
 
     PatchAcc<LPR> acc;
     acc.init(slab, g.nvx + 2, sub);
+    PatchAcc<LPR> acc_c, acc_s;            // AZI: the same patch of the c and the s slab; they move with acc
+    if (AZI) {
+        const size_t slab_len = (size_t)(g.nvx + 2) * (size_t)(g.nvz + 2);
+        acc_c.init(slab + slab_len, g.nvx + 2, sub);
+        acc_s.init(slab + 2 * slab_len, g.nvx + 2, sub);
+    }
+    float sum_c2 = 0.0f, sum_s2 = 0.0f;
     const RecipF by_dnx = recipf_of(dnx), by_dnz = recipf_of(dnz), by_dnxr = recipf_of(dnxr), by_dnzr = recipf_of(dnzr);
     const RecipF by_dvx = recipf_of(dvx), by_dvz = recipf_of(dvz);
     const RecipF by_gx = recipf_of(2.0f * earth * dnx), by_gxr = recipf_of(2.0f * earth * dnxr), by_6 = recipf_of(6.0f);
@@ -253,6 +265,16 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
             dtz = dtz / (2.0f * earth * sin_rgx * dnz);
         }
         const float rd1 = sqrtf(sq(dtx) + sq(dtz));
+        float c2 = 0.0f, s2 = 0.0f;             // cos 2psi, sin 2psi of this step (a clamped step keeps its gradient's)
+        if (AZI) {
+            const float q = sq(dtx) + sq(dtz);
+            if (q > 0.0f && q < kInf) {
+                c2 = (sq(dtx) - sq(dtz)) / q;
+                s2 = -((2.0f * dtx) * dtz) / q;
+            }
+            sum_c2 = sum_c2 + c2;
+            sum_s2 = sum_s2 + s2;
+        }
         float rgx1 = rgx - dpl * dtx / (earth * rd1);
         float rgz1 = rgz - dpl * dtz / (earth * sin_rgx * rd1);
         steps += 1;
@@ -350,6 +372,7 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
             const float dinc = (k == 1) ? vrat * dpl : (vrat - vprev) * dpl;
             vprev = vrat;
             acc.move(ivxt - 1, ivzt - 1);
+            if (AZI) { acc_c.move(ivxt - 1, ivzt - 1); acc_s.move(ivxt - 1, ivzt - 1); }
             const float v2 = sq(vel), vo2 = sq(velo);
             const bool wok_old = wok;
             wok = weights_plain(vi) && weights_plain(wi);
@@ -366,6 +389,7 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
                         const float r2 = divf_by(vio[m] * wio[l], by_vo2);
                         r1 = -(r1 + r2) * dinc / 2.0f;
                         acc.a[l][m] = r1 + acc.a[l][m];
+                        if (AZI) { acc_c.a[l][m] = r1 * c2 + acc_c.a[l][m]; acc_s.a[l][m] = r1 * s2 + acc_s.a[l][m]; }
                     }
             } else if (LPR == 1) {
 #pragma unroll
@@ -376,6 +400,7 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
                         const float r2 = vio[m] * wio[l] / vo2;
                         r1 = -(r1 + r2) * dinc / 2.0f;
                         acc.a[l][m] = r1 + acc.a[l][m];
+                        if (AZI) { acc_c.a[l][m] = r1 * c2 + acc_c.a[l][m]; acc_s.a[l][m] = r1 * s2 + acc_s.a[l][m]; }
                     }
             } else {
                 const int l = acc.my_row();
@@ -387,13 +412,16 @@ DSA_HD int trace_ray(const GridDesc& g, const SourceDesc& s, const RayFields& f,
                     const float r2 = vio[m] * wol / vo2;
                     r1 = -(r1 + r2) * dinc / 2.0f;
                     acc.a[0][m] = r1 + acc.a[0][m];
+                    if (AZI) { acc_c.a[0][m] = r1 * c2 + acc_c.a[0][m]; acc_s.a[0][m] = r1 * s2 + acc_s.a[0][m]; }
                 }
             }
         }
         rgx = rgx1; rgz = rgz1;
     }
     acc.store();
+    if (AZI) { acc_c.store(); acc_s.store(); }
     *nsteps = steps;
+    if (AZI && azi_sums) { azi_sums[0] = sum_c2; azi_sums[1] = sum_s2; }
     return 0;
 }
 

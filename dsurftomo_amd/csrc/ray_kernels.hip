@@ -12,7 +12,9 @@
 
 namespace dsa {
 
-template <int LPR>
+// AZI (azimuthal anisotropy): a ray's slab_stride floats are three slabs [iso | c | s], and rayinfo holds four words
+// per ray instead of two: flags, steps and the bits of its fp32 sums of cos 2psi and sin 2psi over the steps (ray_core.h)
+template <int LPR, bool AZI = false>
 __global__ __launch_bounds__(64) void k_rays(GridDesc g, BatchPtrs b, int unit_base, const RayDesc* __restrict__ rays,
                                              const int* __restrict__ trace_ids, int n, const float* __restrict__ veln_all,
                                              size_t field_stride, float dpl, float* __restrict__ slabs, size_t slab_stride,
@@ -35,27 +37,47 @@ __global__ __launch_bounds__(64) void k_rays(GridDesc g, BatchPtrs b, int unit_b
     int flags = 0, steps = 0;
     RayPath path;
     if (paths && sub == 0) { path.pts = paths + (size_t)t * (size_t)path_cap * 2; path.cap = path_cap; }
-    const int rc = trace_ray<LPR>(g, sd, f, rd.rx, rd.rz, dpl, slabs + (size_t)t * slab_stride, &flags, &steps, paths ? &path : nullptr, sub);
+    float sums[2] = { 0.0f, 0.0f };
+    const int rc = trace_ray<LPR, AZI>(g, sd, f, rd.rx, rd.rz, dpl, slabs + (size_t)t * slab_stride, &flags, &steps, paths ? &path : nullptr, sub,
+                                       AZI ? sums : nullptr);
     if (sub != 0) return;
     if (paths) path_n[t] = path.n;
     if (rc != 0) atomicExch(err, r + 1);
+    if (AZI) {
+        rayinfo[4 * t] = flags;
+        rayinfo[4 * t + 1] = steps;
+        rayinfo[4 * t + 2] = __float_as_int(sums[0]);
+        rayinfo[4 * t + 3] = __float_as_int(sums[1]);
+        return;
+    }
     rayinfo[2 * t] = flags;
     rayinfo[2 * t + 1] = steps;
 }
 
 void launch_rays(const GridDesc& g, const BatchPtrs& b, int unit_base, const RayDesc* d_rays, const int* d_trace_ids, int n,
                  const float* d_veln_all, size_t field_stride, float dpl, float* d_slabs, size_t slab_stride,
-                 int32_t* d_rayinfo, int32_t* d_err, float* d_paths, int path_cap, int* d_path_n, hipStream_t stream, int lanes_per_ray)
+                 int32_t* d_rayinfo, int32_t* d_err, float* d_paths, int path_cap, int* d_path_n, hipStream_t stream, int lanes_per_ray,
+                 bool azimuthal)
 {
     if (n <= 0) return;
+    const dim3 grid1((n + 63) / 64), grid4((unsigned)(((size_t)n * 4 + 63) / 64));
+    if (azimuthal) {       // slab_stride spans the ray's three slabs, d_rayinfo holds four words per ray
+        if (lanes_per_ray == 4)
+            hipLaunchKernelGGL((k_rays<4, true>), grid4, dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
+                               field_stride, dpl, d_slabs, slab_stride, d_rayinfo, d_err, d_paths, path_cap, d_path_n);
+        else
+            hipLaunchKernelGGL((k_rays<1, true>), grid1, dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
+                               field_stride, dpl, d_slabs, slab_stride, d_rayinfo, d_err, d_paths, path_cap, d_path_n);
+        return;
+    }
     // A ray is a chain of ~2 steps per node crossed, ~3 000 instructions a step of which the sixteen vertex sums are half: a small launch (one
     // wavefront or less per SIMD) is bound by that chain, and four lanes per ray shorten it; a large one is bound by the instructions issued, of
     // which four lanes per ray issue three times as many per ray (profiles/r05_ab_rays.log)
     if (lanes_per_ray == 4)
-        hipLaunchKernelGGL(k_rays<4>, dim3((unsigned)(((size_t)n * 4 + 63) / 64)), dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
+        hipLaunchKernelGGL((k_rays<4, false>), grid4, dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
                            field_stride, dpl, d_slabs, slab_stride, d_rayinfo, d_err, d_paths, path_cap, d_path_n);
     else
-        hipLaunchKernelGGL(k_rays<1>, dim3((n + 63) / 64), dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
+        hipLaunchKernelGGL((k_rays<1, false>), grid1, dim3(64), 0, stream, g, b, unit_base, d_rays, d_trace_ids, n, d_veln_all,
                            field_stride, dpl, d_slabs, slab_stride, d_rayinfo, d_err, d_paths, path_cap, d_path_n);
 }
 
@@ -81,6 +103,26 @@ void launch_sen_combine(int ncol, int kmax, int nz, const float* d_vels, const d
     if (n == 0) return;
     hipLaunchKernelGGL(k_sen_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ncol, kmax, nz, d_vels, d_sen_vs,
                        d_sen_vp, d_sen_rho, shallow, d_S);
+}
+
+// Sazi[(k * kmax + slot) * ncol + c] = sen_vs * (double)(0.5f * vels[k * ncol + c]): the depth factor of the gc / gs entries,
+// d c / d (Gc/L) = (Vs / 2) d c / d Vs per layer; fp64, one rounding
+__global__ void k_sen_azimuthal(int ncol, int kmax, int nz, const float* __restrict__ vels, const double* __restrict__ sen_vs,
+                                double* __restrict__ Sazi)
+{
+    const size_t n = (size_t)ncol * kmax * (nz - 1);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % ncol);
+    const int k = (int)(i / ((size_t)ncol * kmax));
+    Sazi[i] = sen_vs[i] * (double)(0.5f * vels[(size_t)k * ncol + c]);
+}
+
+void launch_sen_azimuthal(int ncol, int kmax, int nz, const float* d_vels, const double* d_sen_vs, double* d_Sazi, hipStream_t stream)
+{
+    const size_t n = (size_t)ncol * kmax * (nz - 1);
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_sen_azimuthal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ncol, kmax, nz, d_vels, d_sen_vs, d_Sazi);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -167,6 +209,60 @@ void launch_row_emit(const GridDesc& g, const RowArgs& a, bool write, hipStream_
     if (a.n <= 0) return;
     if (write) hipLaunchKernelGGL(k_row_emit<true>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a);
     else hipLaunchKernelGGL(k_row_emit<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a);
+}
+
+// The azimuthal row of a ray: the isotropic entries exactly as k_row_emit writes them, then block gc and block gs over the same kept
+// vertices (|fdm_c|, |fdm_s| <= |fdm|: the isotropic list is a superset) with the depth factor Sazi and the c / s slab, columns
+// B * maxvp + k * layer + i + 1.  A ray whose depth-kernel slot is switched off (z.slot_on) has the isotropic block only.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_row_emit_azi(GridDesc g, RowArgs a, RowAziArgs z)
+{
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= a.n) return;
+    const RayDesc rd = a.rays[a.trace_ids[t]];
+    const int slot = a.src[rd.src - a.unit_base].sen_slot;
+    const int* vl = a.vlist + (size_t)t * a.vlist_stride;
+    const int nv = a.nv[t];
+    const int nvx = g.nvx, ldx = g.nvx + 2, ncol = g.nx * g.ny, layer = g.nvx * g.nvz;
+    const long long off = WRITE ? a.offsets[t] : 0;
+    const int nblocks = z.slot_on[slot] ? 3 : 1;
+    int cnt = 0;
+    for (int B = 0; B < nblocks; ++B) {
+        const float* slab = a.slabs + (size_t)t * a.slab_stride + (size_t)B * z.slab_len;
+        const double* SB = B == 0 ? a.S : z.Sazi;
+        for (int k = 0; k < a.nz - 1; ++k) {
+            const double* Sk = SB + ((size_t)k * a.kmax + slot) * ncol;
+            for (int base = 0; base < nv; base += 64) {
+                const int e = base + lane;
+                bool keep = false;
+                float val = 0.0f;
+                int i = 0;
+                if (e < nv) {
+                    i = vl[e];
+                    const int jj = i / nvx + 1, kk = i - (jj - 1) * nvx + 1;
+                    const float f = slab[(size_t)jj * ldx + kk];
+                    val = (float)(Sk[jj * g.nx + kk] * (double)f);
+                    keep = fabsf(val) > kFtol;
+                }
+                const unsigned long long m = __ballot(keep);
+                if (WRITE && keep) {
+                    const long long p = off + cnt + lanes_below(m);
+                    a.rw[p] = val;
+                    a.iw[p] = rd.data + 1;
+                    a.col[p] = B * z.maxvp + k * layer + i + 1;
+                }
+                cnt += __popcll(m);
+            }
+        }
+    }
+    if (!WRITE && lane == 0) a.counts[t] = cnt;
+}
+
+void launch_row_emit_azi(const GridDesc& g, const RowArgs& a, const RowAziArgs& z, bool write, hipStream_t stream)
+{
+    if (a.n <= 0) return;
+    if (write) hipLaunchKernelGGL(k_row_emit_azi<true>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
+    else hipLaunchKernelGGL(k_row_emit_azi<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
 }
 
 // one workgroup: per-thread segment sums, scan of the 1024 sums in LDS, segment rewrite

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("DSA_LIB_PATH") or os.path.join(_HERE, "libdsurftomo_a
 
 STAT_NAMES = ("ms_total", "ms_fim_coarse", "ms_fim_refined", "ms_stages", "launches_fim_coarse", "units",
               "rounds_max", "evals_total", "chunk", "rescans", "freezes", "rays", "ray_steps", "rays_clamped",
-              "ms_rays", "ms_rows", "nar", "ms_dispersion", "curves", "changes_total", "tie_units", "exact_units", "exact_pops", "ms_exact", "field_slots", "footprint_mb", "bundle_size", "bundles", "bundled_units", "bundle_slots", "bundle_threads", "tie_units_left", "tie_influence_max", "exact_pool", "exact_tiles", "tie_units_strict", "tie_prone_maps", "tie_units_tied", "tie_units_by_scale", "handoffs_replayed")
+              "ms_rays", "ms_rows", "nar", "ms_dispersion", "curves", "changes_total", "tie_units", "exact_units", "exact_pops", "ms_exact", "field_slots", "footprint_mb", "bundle_size", "bundles", "bundled_units", "bundle_slots", "bundle_threads", "tie_units_left", "tie_influence_max", "exact_pool", "exact_tiles", "tie_units_strict", "tie_prone_maps", "tie_units_tied", "tie_units_by_scale", "handoffs_replayed", "ray_launches")
 
 _f32, _i32, _vp = C.c_float, C.c_int, C.c_void_p
 _lib = None
@@ -68,7 +68,9 @@ def load_library():
         L.dsa_unit_tie_sums.argtypes = [_vp, _i32, _vp, _vp, _vp]
     L.dsa_debug_counters.argtypes = [_vp, _vp]
     L.dsa_ray_paths.argtypes = [_vp, _vp, _vp, _vp]
-    L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
+    L.dsa_solve_rows_azimuthal.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dsa_set_azimuthal_slots.argtypes = [_vp, _i32, _vp]
+    L.dsa_ray_azimuths.argtypes = [_vp, _vp, _vp, _vp]
     L.dsa_spmv.argtypes = [_vp, _i32, _vp, _vp]
     L.dsa_debug_field.argtypes = [_vp, _i32, _i32, _vp]
     L.dsa_selfcheck_divisions.argtypes = [C.c_ulonglong, _i32, _vp, _vp]
@@ -90,9 +92,11 @@ def declare_solvers(L):
     L.dsa_error_string.restype = C.c_char_p
     L.dsa_dropin_engine.argtypes = []
     L.dsa_dropin_engine.restype = _vp
+    L.dsa_calsurfg_azimuthal.argtypes = [_vp] * 36            # dsa_calsurfg's list: every argument by reference
     L.dsa_iteration_system.argtypes = [_i32] * 4 + [C.c_longlong] * 2 + [_vp] * 5 + [_f32] * 2 + [_vp] * 6
     L.dsa_iteration_system_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 2 + [_vp] * 6
     L.dsa_model_update.argtypes = [_i32] * 3 + [_vp] * 2 + [_f32] * 2
+    L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
     L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32] + solve + [_vp] * 5
@@ -230,6 +234,34 @@ class Engine:
         nar = C.c_longlong(0)
         self._check(self._L.dsa_solve_rows(self._h, _p(out), None, None, None, C.c_longlong(1 << 62), C.byref(nar)))
         return out, nar.value
+
+    def solve_rows_azimuthal(self, capacity):
+        """solve_rows with the gc and gs blocks behind every ray's isotropic entries (dsa_solve_rows_azimuthal): columns
+        B * maxvp + isotropic column, B = 1 (gc), 2 (gs)"""
+        out = np.zeros(self._ndata, np.float32)
+        rw = np.zeros(capacity, np.float32)
+        iw = np.zeros(capacity, np.int32)
+        col = np.zeros(capacity, np.int32)
+        nar = C.c_longlong(0)
+        self._check(self._L.dsa_solve_rows_azimuthal(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
+                                                     capacity, C.byref(nar)))
+        n = nar.value
+        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+
+    def set_azimuthal_slots(self, on):
+        """on: one flag per depth-kernel slot, 0 = units of that slot emit no gc / gs entries; None = every slot emits"""
+        if on is None:
+            self._check(self._L.dsa_set_azimuthal_slots(self._h, 0, None))
+            return
+        on = np.ascontiguousarray(on, np.int32)
+        self._check(self._L.dsa_set_azimuthal_slots(self._h, on.size, on.ctypes.data_as(_vp)))
+
+    def ray_azimuths(self):
+        """per traced ray of the last solve_rows_azimuthal, in data order: (datum (1-based), steps, sums (R, 2) of cos 2psi and sin 2psi)"""
+        nr = int(self.stats()["rays"])
+        datum = np.zeros(nr, np.int32); steps = np.zeros(nr, np.int32); sums = np.zeros((nr, 2), np.float32)
+        self._check(self._L.dsa_ray_azimuths(self._h, datum.ctypes.data_as(_vp), steps.ctypes.data_as(_vp), sums.ctypes.data_as(_vp)))
+        return datum, steps, sums
 
     def ray_paths(self, cap):
         """paths of the rays traced by the last solve_rows (set_option('ray_path_cap', cap) before it): list of

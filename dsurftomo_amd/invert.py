@@ -7,6 +7,7 @@
                                    [--crossval NFOLDS --crossval-weights W1,W2,... [--crossval-damps D1,...] [--crossval-by datum|path]
                                     [--crossval-seed S] [--crossval-iter N] [--crossval-nonlinear]]
                                    [--tradeoff-nonlinear] [--line-search A1,A2,...]
+                                   [--azimuthal [--azimuthal-weight W] [--azimuthal-damp D]]
 
 Per outer iteration: CalSurfG on the device (dsa_calsurfg: dispersion, depth kernels, eikonal solves, rays, Frechet rows),
 the glue of main.f90:361-466 (residuals, percentile weights, DWS, regularisation rows), LSMR on the device (bit-identical
@@ -97,6 +98,16 @@ held f out, divided by ndata), the true full-fit rms of the full member, the lin
 members; the log names the pair with the smallest true held-out rms.  Where one dsa_lsmr_crossval call holds all pairs and no other batch
 solve follows it, the members' updates never leave the device (dsa_forward_steps with steps = NULL).  17 significant digits
 (io.read_tradeoff_nonlinear / read_crossval_nonlinear return the numbers bit for bit).  No other output changes.  Device-resident rows only.
+
+--azimuthal adds one joint step for Vs and 2psi azimuthal anisotropy (Liu et al. 2019) after the last outer iteration:
+c(psi) = c0 + A1 cos 2psi + A2 sin 2psi with A1 = int (Vs/2)(dc/dVs) gc dz, A2 likewise with gs; the unknowns gc = Gc/L and gs = Gs/L live on
+the Vs unknowns' grid.  azimuthal_step calls dsa_calsurfg_azimuthal once on the final model (the rays carry the 2psi weights of every step into
+two more blocks of columns, Rayleigh periods only) and assembles the joint system in NumPy (azimuthal_system): the reference's 0/1 data
+weights (azimuthal_weights: its percentile rule), rows scaled by them, and its first-difference Laplacian rows once per block -- weight0 on
+the Vs block, --azimuthal-weight W (default weight0) on gc and gs -- then dsa_spmv_load and dsa_lsmr with this module's LSMR arguments and
+--azimuthal-damp D (default the input file's damp).  <input>Azim.dat lists longitude, latitude, depth, Vs, gc, gs, the strength
+50 sqrt(gc^2 + gs^2) in per cent of Vs and the fast axis 0.5 atan2(gs, gc) in degrees clockwise from north (write_azimuthal /
+read_azimuthal).  The Vs block of the joint solution is logged (min / max) and NOT applied: every other file is a plain run's, byte for byte.
 """
 import argparse
 import ctypes as C
@@ -797,6 +808,161 @@ def forward_steps_members(lib, c, vsf, steps, obst, datweight, group=None, ngrou
     return dict(measures=meas, failures=fails, dsyn=dsyn, calls=calls, resident=False, seconds=time.perf_counter() - t0)
 
 
+def azimuthal_weights(res, threshold0):
+    """the reference's 0/1 data weights of the residuals res (main.f90:361-372 with getpercentile.f90:27-30): weight 0 outside
+    [q25, q75] * threshold0, q25 / q75 the elements int(0.25 N) and int(0.75 N) (1-based) of the sorted residuals; fp32 like
+    dsa_iteration_system"""
+    f = np.float32
+    res = np.ascontiguousarray(res, f).ravel()
+    n = res.size
+    i25, i75 = int(f(0.25) * f(n)), int(f(0.75) * f(n))
+    if i25 < 1 or i75 < 1:
+        raise ValueError("azimuthal_weights: %d residuals are too few for the quartile rule" % n)
+    ra = np.sort(res)
+    lo, hi = f(ra[i25 - 1] * f(threshold0)), f(ra[i75 - 1] * f(threshold0))
+    return np.where((res < lo) | (res > hi), f(0), f(1)).astype(f)
+
+
+def laplacian_rows(nvx, nvz, nl, weight, row0, col0):
+    """the reference's first-difference Laplacian rows (main.f90:420-457; dsa_iteration_system's) for one block of nvx*nvz*nl unknowns,
+    one row per unknown in (k, j, i) order: 2 w on the block's faces, 6 w and six -w inside, fp32.  Rows row0 + 1 .., columns col0 + 1 ..
+    (1-based).  Returns (rw, row, col)."""
+    f = np.float32
+    w = f(weight)
+    plane = nvz * nvx
+    rw, row, col = [], [], []
+    r = row0
+    for k in range(1, nl + 1):
+        for j in range(1, nvz + 1):
+            for i in range(1, nvx + 1):
+                r += 1
+                here = (k - 1) * plane + (j - 1) * nvx + i
+                if i in (1, nvx) or j in (1, nvz) or k in (1, nl):
+                    rw.append(f(2.0) * w); row.append(r); col.append(col0 + here)
+                else:
+                    for q, nb in enumerate((here, here - 1, here + 1, here - nvx, here + nvx, here - plane, here + plane)):
+                        rw.append(f(6.0) * w if q == 0 else f(-1.0) * w); row.append(r); col.append(col0 + nb)
+    return np.array(rw, f), np.array(row, np.int32), np.array(col, np.int32)
+
+
+def azimuthal_system(c, rw, row, col, res, datweight, weight0, weight_azi):
+    """The joint system of the azimuthal step from dsa_calsurfg_azimuthal's rows (rw, row, col: 1-based, columns up to 3 maxvp, blocks
+    Vs | gc | gs) and the residuals res: every entry scaled by its datum's weight, the right-hand side the weighted residuals, and below the
+    dall data rows the Laplacian rows of the three blocks -- block B's at rows dall + B maxvp + index, weight0 on Vs, weight_azi on gc and
+    gs.  Returns dict(m, n, rw, row, col, b): m = dall + 3 maxvp rows, n = 3 maxvp columns, COO 1-based, fp32."""
+    f = np.float32
+    nvx, nvz, nl, dall = c["nx"] - 2, c["ny"] - 2, c["nz"] - 1, c["ndata"]
+    maxvp = nvx * nvz * nl
+    rw = np.ascontiguousarray(rw, f); row = np.ascontiguousarray(row, np.int32); col = np.ascontiguousarray(col, np.int32)
+    res = np.ascontiguousarray(res, f); datweight = np.ascontiguousarray(datweight, f)
+    if not (rw.size == row.size == col.size) or res.size != dall or datweight.size != dall:
+        raise ValueError("azimuthal_system: rw / row / col differ in length, or res / datweight do not hold ndata = %d values" % dall)
+    if rw.size and (row.min() < 1 or row.max() > dall or col.min() < 1 or col.max() > 3 * maxvp):
+        raise ValueError("azimuthal_system: a row outside 1..%d or a column outside 1..%d" % (dall, 3 * maxvp))
+    if not (np.isfinite(weight0) and np.isfinite(weight_azi) and weight0 >= 0 and weight_azi >= 0):
+        raise ValueError("azimuthal_system: the smoothing weights must be finite and >= 0")
+    parts = [(rw * datweight[row - 1], row, col)]
+    for B in range(3):
+        parts.append(laplacian_rows(nvx, nvz, nl, weight0 if B == 0 else weight_azi, dall + B * maxvp, B * maxvp))
+    b = np.zeros(dall + 3 * maxvp, f)
+    b[:dall] = res * datweight
+    return dict(m=dall + 3 * maxvp, n=3 * maxvp, rw=np.concatenate([q[0] for q in parts]).astype(f),
+                row=np.concatenate([q[1] for q in parts]).astype(np.int32), col=np.concatenate([q[2] for q in parts]).astype(np.int32), b=b)
+
+
+def azimuthal_strength(gc, gs):
+    """peak-to-peak 2psi variation of Vs in per cent: 50 sqrt(gc^2 + gs^2)"""
+    return 50.0 * np.hypot(np.asarray(gc, np.float64), np.asarray(gs, np.float64))
+
+
+def azimuthal_axis(gc, gs):
+    """fast axis in degrees clockwise from north, in (-90, 90]: 0.5 atan2(gs, gc)"""
+    return np.degrees(0.5 * np.arctan2(np.asarray(gs, np.float64), np.asarray(gc, np.float64)))
+
+
+def write_azimuthal(path, c, vsf, gc, gs):
+    """<input>Azim.dat: per interior vertex in write_model's order longitude, latitude, depth, Vs ('(4f10.5)'), gc, gs ('(2f13.8)'), strength in
+    per cent of Vs and fast axis in degrees from north ('(2f11.5)'); gc / gs: (maxvp,) in the order of the LSMR unknowns"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    gc = np.asarray(gc, np.float64).reshape(nz - 1, ny - 2, nx - 2); gs = np.asarray(gs, np.float64).reshape(nz - 1, ny - 2, nx - 2)
+    st, ax = azimuthal_strength(gc, gs), azimuthal_axis(gc, gs)
+    with open(path, "w") as fh:
+        for k in range(nz - 1):
+            for j in range(ny - 2):
+                for i in range(nx - 2):
+                    lon, lat = _lonlat(c, i, j)
+                    fh.write(_f10(lon) + _f10(lat) + _f10(c["depz"][k]) + _f10(vsf[i + 1, j + 1, k]) +
+                             "%13.8f%13.8f%11.5f%11.5f\n" % (gc[k, j, i], gs[k, j, i], st[k, j, i], ax[k, j, i]))
+
+
+def read_azimuthal(path):
+    """the columns of <input>Azim.dat as a dict of float64 arrays, one entry per line: lon, lat, depth, vs, gc, gs, strength, axis"""
+    a = np.loadtxt(path, ndmin=2)
+    if a.shape[1] != 8:
+        raise ValueError("%s: %d columns, not the 8 of an Azim.dat" % (path, a.shape[1]))
+    return dict(zip(("lon", "lat", "depth", "vs", "gc", "gs", "strength", "axis"), a.T.copy()))
+
+
+def check_azimuthal(azimuthal, weight=None, damp=None):
+    """the azimuthal step's preconditions, checked before anything touches the GPU"""
+    if not azimuthal:
+        if weight is not None or damp is not None:
+            raise ValueError("--azimuthal-weight / --azimuthal-damp need --azimuthal")
+        return
+    for name, v in (("--azimuthal-weight", weight), ("--azimuthal-damp", damp)):
+        if v is not None and not (np.isfinite(v) and v >= 0):
+            raise ValueError("%s must be finite and >= 0, not %r" % (name, v))
+
+
+def azimuthal_step(lib, c, vsf, obst, log, weight=None, damp=None):
+    """The joint Vs / gc / gs step on the model vsf (not modified): one dsa_calsurfg_azimuthal, azimuthal_system, dsa_spmv_load and dsa_lsmr
+    on the drop-in engine.  weight: the smoothing weight of the gc and gs blocks (default weight0), damp: LSMR's (default the input file's).
+    Returns dict(dvs, gc, gs (maxvp,), x, itn, istop, dsyn, datweight, rw / row / col (the call's rows as they came: unweighted), system,
+    seconds)."""
+    check_azimuthal(True, weight, damp)
+    f = np.float32
+    nx, ny, nz, dall, maxvp = c["nx"], c["ny"], c["nz"], c["ndata"], c["nparpi"]
+    weight = float(c["weight0"]) if weight is None else float(weight)
+    damp = float(c["damp"]) if damp is None else float(damp)
+    maxnar = 3 * int(f(c["spfra"]) * dall * nx * ny * nz)                               # main.f90:287, once per block
+    rw = np.zeros(maxnar, f); col = np.zeros(maxnar, np.int32); iw = np.zeros(maxnar + 1, np.int32)
+    dsyn = np.zeros(dall, f)
+    nar = C.c_int(0)
+    cc = dict(c); cc["vels"] = vsf
+    head, tail = io._args(cc)
+    lib.dsa_dropin_set_capacity(maxnar)
+    t0 = time.perf_counter()
+    rc = lib.dsa_calsurfg_azimuthal(*head, _p(iw), _p(rw), _p(col), _p(dsyn), *tail, C.byref(nar))
+    lib.dsa_dropin_set_capacity(0)
+    if rc != 0:
+        raise RuntimeError("dsa_calsurfg_azimuthal: %s" % lib.dsa_dropin_error().decode())
+    t_fwd = time.perf_counter() - t0
+    n = nar.value
+    rw, row, col = rw[:n].copy(), iw[1:n + 1].copy(), col[:n].copy()
+    obst = np.ascontiguousarray(obst, f)
+    res = (obst - dsyn).astype(f)
+    datweight = azimuthal_weights(res, c["threshold0"])
+    S = azimuthal_system(c, rw, row, col, res, datweight, c["weight0"], weight)
+    eng = lib.dsa_dropin_engine()
+    t0 = time.perf_counter()
+    if lib.dsa_spmv_load(eng, S["m"], S["n"], C.c_longlong(S["rw"].size), _p(S["rw"]), _p(S["row"]), _p(S["col"])) != 0:
+        raise RuntimeError("dsa_spmv_load: %s" % lib.dsa_error_string(eng).decode())
+    x = np.zeros(S["n"], f)
+    ii = [C.c_int(0), C.c_int(0)]
+    ff = [C.c_float(0) for _ in range(5)]
+    if lib.dsa_lsmr(eng, _p(S["b"]), C.c_float(damp), *LSMR_ARGS, _p(x), C.byref(ii[0]), C.byref(ii[1]), *[C.byref(v) for v in ff]) != 0:
+        raise RuntimeError("dsa_lsmr: %s" % lib.dsa_error_string(eng).decode())
+    t_lsmr = time.perf_counter() - t0
+    dvs, gc, gs = x[:maxvp], x[maxvp:2 * maxvp], x[2 * maxvp:]
+    log(" azimuthal step: %d x %d, %d entries (%d from the rays: %d Vs, %d gc, %d gs), weight %g damp %g, %d iterations, istop %d "
+        "(forward %.3f s, LSMR %.3f s)" % (S["m"], S["n"], S["rw"].size, n, int((col <= maxvp).sum()), int(((col > maxvp) & (col <= 2 * maxvp)).sum()),
+                                           int((col > 2 * maxvp).sum()), weight, damp, ii[1].value, ii[0].value, t_fwd, t_lsmr))
+    log(" azimuthal step: min and max velocity variation of its Vs block %7.4f%7.4f (not applied); strength max %.3f %% of Vs" %
+        (float(dvs.min()), float(dvs.max()), float(azimuthal_strength(gc, gs).max())))
+    return dict(dvs=dvs, gc=gc, gs=gs, x=x, itn=ii[1].value, istop=ii[0].value, dsyn=dsyn, datweight=datweight, rw=rw, row=row, col=col,
+                system=S, weight=weight, damp=damp, seconds=dict(forward=t_fwd, lsmr=t_lsmr))
+
+
 def write_residuals(path, c, dsyn, obst, datweight):
     """list-directed rows: dist, dsyn, obst, dsyn*w, obst*w, w (main.f90:397-403)"""
     np.savetxt(path, np.column_stack([c["dist"], dsyn, obst, dsyn * datweight, obst * datweight, datweight]), fmt="%16.8f")
@@ -1275,7 +1441,8 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
         resolution_chunk=None, tradeoff_weights=None, tradeoff_damps=None, tradeoff_iter=1, tradeoff_chunk=None, voronoi=None, voronoi_seed=1,
         voronoi_zscale=1.0, voronoi_damp=None, voronoi_update=False, voronoi_chunk=None, crossval=None, crossval_weights=None, crossval_damps=None,
         crossval_by="datum", crossval_seed=1, crossval_iter=1, crossval_chunk=None, line_search=None, tradeoff_nonlinear=False,
-        crossval_nonlinear=False):
+        crossval_nonlinear=False, azimuthal=False, azimuthal_weight=None, azimuthal_damp=None):
+    check_azimuthal(azimuthal, azimuthal_weight, azimuthal_damp)
     check_tradeoff_nonlinear(tradeoff_nonlinear, tradeoff_weights, host_rows)
     check_crossval_nonlinear(crossval_nonlinear, crossval, host_rows)
     check_bootstrap(bootstrap, host_rows)
@@ -1439,6 +1606,12 @@ def run(directory, maxiter=None, out_dir=".", log=print, seed=1, host_rows=False
                 (hv["cells"], _solve_text(hv), hv["std_max"], hv["std_mean"], ", the mean applied as the update" if voronoi_update else "", hv["calls"],
                  hv["chunk"], hv["seconds"]))
         history.append(h)
+    if azimuthal:           # the joint Vs / gc / gs step on the final model; nothing of it is applied
+        az = azimuthal_step(lib, c, vsf, obst, log, azimuthal_weight, azimuthal_damp)
+        write_azimuthal(name + "Azim.dat", c, vsf, az["gc"], az["gs"])
+        history.append(dict(azimuthal=dict(weight=az["weight"], damp=az["damp"], itn=az["itn"], istop=az["istop"], nar=int(az["rw"].size),
+                                           dvs_min=float(az["dvs"].min()), dvs_max=float(az["dvs"].max()),
+                                           strength_max=float(azimuthal_strength(az["gc"], az["gs"]).max()), seconds=az["seconds"])))
     if vsftrue is not None:
         write_model(os.path.join(out_dir, "Vs_model.real"), c, vsftrue)
         write_model(name + "Syn.dat", c, vsf)
@@ -1503,8 +1676,15 @@ def main(argv=None):
                     help="step-length line search: in every outer iteration the update is tried at these fractions of its length (each >= 0; 0 keeps "
                          "the model), all candidate models are forward-modelled in one call, and the one with the smallest rms of the weighted "
                          "travel-time residual is applied: <input>LineSearch.dat, one row per (iteration, step)")
+    ap.add_argument("--azimuthal", action="store_true",
+                    help="after the last iteration, one joint step for Vs and the 2psi azimuthal anisotropy gc = Gc/L, gs = Gs/L on the final model "
+                         "(Rayleigh periods): <input>Azim.dat (Vs, gc, gs, strength in per cent of Vs, fast axis in degrees from north); nothing of it "
+                         "is applied to the model")
+    ap.add_argument("--azimuthal-weight", type=float, default=None, metavar="W", help="smoothing weight of the gc and gs blocks (default: the input file's weight0)")
+    ap.add_argument("--azimuthal-damp", type=float, default=None, metavar="D", help="damping of the azimuthal step's solve (default: the input file's damp)")
     args = ap.parse_args(argv)
     try:
+        check_azimuthal(args.azimuthal, args.azimuthal_weight, args.azimuthal_damp)
         check_tradeoff_nonlinear(args.tradeoff_nonlinear, args.tradeoff_weights, args.host_rows)
         check_crossval_nonlinear(args.crossval_nonlinear, args.crossval, args.host_rows)
         check_bootstrap(args.bootstrap, args.host_rows)
@@ -1521,7 +1701,8 @@ def main(argv=None):
         tradeoff_iter=args.tradeoff_iter, voronoi=args.voronoi, voronoi_seed=args.voronoi_seed, voronoi_zscale=args.voronoi_zscale,
         voronoi_damp=args.voronoi_damp, voronoi_update=args.voronoi_update, crossval=args.crossval, crossval_weights=args.crossval_weights,
         crossval_damps=args.crossval_damps, crossval_by=args.crossval_by, crossval_seed=args.crossval_seed, crossval_iter=args.crossval_iter,
-        line_search=args.line_search, tradeoff_nonlinear=args.tradeoff_nonlinear, crossval_nonlinear=args.crossval_nonlinear)
+        line_search=args.line_search, tradeoff_nonlinear=args.tradeoff_nonlinear, crossval_nonlinear=args.crossval_nonlinear,
+        azimuthal=args.azimuthal, azimuthal_weight=args.azimuthal_weight, azimuthal_damp=args.azimuthal_damp)
     return 0
 
 

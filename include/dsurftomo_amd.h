@@ -203,6 +203,28 @@ int dsa_solve_rows(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, lo
  * C), latlon[R * C * 2] (latitude, longitude) in degrees: receiver first, source last. */
 int dsa_ray_paths(dsa_engine* e, int* datum, int* npts, float* latlon);
 
+/* ---- azimuthal anisotropy: 2psi Frechet rows traced with the rays (extension; Liu et al. 2019) ----
+ * c(psi) = c0 + A1 cos 2psi + A2 sin 2psi, psi the azimuth of propagation clockwise from north, A1 = int (Vs/2)(dc/dVs)(Gc/L) dz and A2
+ * likewise with Gs/L; the unknowns gc = Gc/L and gs = Gs/L live on the isotropic unknowns' grid.
+ * dsa_solve_rows_azimuthal is dsa_solve_rows with two more blocks of columns: every gradient step of a ray's back-trace has
+ * cos 2psi = (dtx^2 - dtz^2)/q and sin 2psi = -2 dtx dtz/q of its travel-time gradient (dtx south, dtz east, q = dtx^2 + dtz^2; both 0
+ * unless q is finite and positive), and every contribution r1 to a vertex sum of the isotropic kernel fdm also goes, times those, into
+ * fdm_c and fdm_s (fp32, r1*c2 + acc, the isotropic sum's order).  Per ray, in data order: the isotropic entries exactly as dsa_solve_rows
+ * writes them, then block gc, then block gs, each over the vertices the isotropic row lists, layers outer:
+ *   val = (float)(Sazi * (double)f), Sazi = sen_vs * (double)(0.5f * vels) of the layer and column, f = fdm_c (gc) or fdm_s (gs),
+ *   kept when |val| > 1e-4, col = B*maxvp + k*nvx*nvz + (jj-1)*nvx + kk with B = 1 (gc), 2 (gs), maxvp = nvx*nvz*(nz-1).
+ * dsurf and every statistic are dsa_solve_rows'.  Host COO only: DSA_ERR_STATE with option rows_on_device, DSA_ERR_ARGUMENT for a null
+ * array or when 3*maxvp does not fit an int, DSA_ERR_CAPACITY as dsa_solve_rows.  Calls that never ask for it use no memory for it. */
+int dsa_solve_rows_azimuthal(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity,
+                             long long* nar);
+/* on[kmax] (kmax = the depth kernels' slot count, checked by the next azimuthal solve): 0 = units of that depth-kernel slot (sen_slot of
+ * dsa_plan_units) emit no gc / gs entries -- Love periods, for which the 2psi terms above do not hold.  on = NULL: every slot emits. */
+int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on);
+/* For the R traced rays (DSA_STAT_RAYS) of the last dsa_solve_rows_azimuthal, in data order: datum[R] 1-based row, nsteps[R] gradient
+ * steps taken, sums[2 R] the sequential fp32 sums of cos 2psi and of sin 2psi over them (sums / nsteps = the ray's mean 2psi direction).
+ * DSA_ERR_STATE before an azimuthal solve of the current plan. */
+int dsa_ray_azimuths(dsa_engine* e, int* datum, int* nsteps, float* sums);
+
 /* ---- next to the path: the matrix-vector products of the inversion step (reference aprod.f90:7-60) ----
  * load: COO matrix (rw[k], 1-based row[k] <= m, col[k] <= n), kept on the device in row-major and
  * column-major order; spmv mode 1: y += A x, mode 2: x += A^T y on host vectors x[n], y[m].
@@ -443,6 +465,7 @@ enum { DSA_STAT_MS_TOTAL = 0, DSA_STAT_MS_FIM_COARSE, DSA_STAT_MS_FIM_REFINED, D
                                          fixed point's tie errors were measured to stay within the tolerance (option tie_scale_guard) */
        DSA_STAT_HANDOFFS_REPLAYED,    /* units whose refined box was marched literally behind the hand-off's probe (a node ranking equal with the one that ended the refined
                                          stage changed what the coarse grid receives: the reference's own tree decides; option handoff_replay) */
+       DSA_STAT_RAY_LAUNCHES,         /* launches of the ray kernel (option ray_budget bounds the rays of one) */
        DSA_STAT_COUNT };
 int dsa_get_stats(const dsa_engine* e, double* out /* DSA_STAT_COUNT + 8: counters, then 8 phase-clock sums (probe builds) */);
 
@@ -466,6 +489,21 @@ int dsa_synthetic(const int* nx, const int* ny, const int* nz, const int* nparpi
                   const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
                   const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
                   const int* nsrcsurf, const int* nrcf, const float* noiselevel);
+
+/* dsa_calsurfg with the azimuthal blocks of dsa_solve_rows_azimuthal (extension): the same argument list and conventions --
+ * iw(1) = nar on return, the rows behind it, the capacity of dsa_dropin_set_capacity (state it for 3 nparpi columns per datum).  The
+ * Rayleigh depth-kernel slots (phase and group periods) emit gc / gs entries, the Love slots none.  The isotropic entries, dsurf and the
+ * diagnostics afterwards are dsa_calsurfg's; columns run to 3*nparpi.  rw / iw / col must be host arrays.  DSA_ERR_STATE: more than one
+ * engine in the pool (DSA_DEVICES): the azimuthal call is not sharded over GPUs. */
+int dsa_calsurfg_azimuthal(const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
+                           int* iw, float* rw, int* col, float* dsurf,
+                           const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
+                           const int* kmaxRc, const int* kmaxRg, const int* kmaxLc, const int* kmaxLg,
+                           const double* tRc, const double* tRg, const double* tLc, const double* tLg,
+                           const int* wavetype, const int* igrt, const int* periods, const float* depz,
+                           const float* minthk, const float* scxf, const float* sczf, const float* rcxf,
+                           const float* rczf, const int* nrc1, const int* nsrcsurf1, const int* kmax,
+                           const int* nsrcsurf, const int* nrcf, int* nar);
 
 /* Forward-model `nmodels` Vs models vels(nx,ny,nz,nmodels), model slowest, in ONE call: times only, no rays, no rows (extension; the
  * reference has no such entry).  goxdf .. nrcf are the arguments of dsa_synthetic between obst and noiselevel, with the same meaning.
