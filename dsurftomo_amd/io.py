@@ -236,28 +236,52 @@ def call_forward_steps(c, vsf, steps, alpha=None, dicing=8, obst=None, datweight
                 models=None if models is None else models.transpose(0, 3, 2, 1))
 
 
-TRADEOFF_NONLINEAR_COLUMNS = ("weight", "damp", "predicted_rms", "weighted_rms", "rms", "disp_failures")
-CROSSVAL_NONLINEAR_COLUMNS = ("weight", "damp", "heldout_rms", "full_rms", "cv_rms", "disp_failures")
+_READ = {"int": int, "flag": int, "f64": float, "f32": lambda t: float(np.float32(t))}           # how a column of a table's kind is read back
 
 
-def _write_nonlinear(path, columns, rows):
+def column_names(table):
+    return tuple(name for name, _, _ in table[1])
+
+
+def write_table(path, table, rows):
+    """one line per dict of rows in the layout `table` = (header, ((name, format, kind), ...)): the columns in order, each in its format,
+    joined by blanks; with header, a first line '# name name ...'.  Kind 'flag' is written as 0 / 1."""
+    header, columns = table
     with open(path, "w") as fh:
-        fh.write("# " + " ".join(columns) + "\n")
+        if header:
+            fh.write("# " + " ".join(column_names(table)) + "\n")
         for r in rows:
-            fh.write(" ".join("%.17g" % r[k] for k in columns[:-1]) + " %d\n" % r[columns[-1]])
+            fh.write(" ".join(fmt % (int(bool(r[name])) if kind == "flag" else r[name]) for name, fmt, kind in columns) + "\n")
 
 
-def _read_nonlinear(path, columns):
+def read_table(path, table):
+    """the rows write_table wrote, as a list of dicts: kinds 'int' and 'flag' as int, 'f64' as float, 'f32' as the float32 value the text
+    rounds to.  In a file with a header, blank lines and lines that begin with '#' are skipped."""
+    header, columns = table
     rows = []
     with open(path) as fh:
         for line in fh:
             t = line.split()
-            if not t or t[0].startswith("#"):
+            if header and (not t or t[0].startswith("#")):
                 continue
-            r = {k: float(v) for k, v in zip(columns[:-1], t)}
-            r[columns[-1]] = int(t[len(columns) - 1])
-            rows.append(r)
+            if len(t) != len(columns):
+                raise ValueError("%s: a line of %d columns, not %d" % (path, len(t), len(columns)))
+            rows.append({name: _READ[kind](v) for (name, _, kind), v in zip(columns, t)})
     return rows
+
+
+def _f64_table(*names):
+    """the layout of the two nonlinear files: a header, float64 columns with 17 significant digits and a last integer column"""
+    return True, tuple((n, "%.17g", "f64") for n in names[:-1]) + ((names[-1], "%d", "int"),)
+
+
+TRADEOFF_NONLINEAR_TABLE = _f64_table("weight", "damp", "predicted_rms", "weighted_rms", "rms", "disp_failures")
+CROSSVAL_NONLINEAR_TABLE = _f64_table("weight", "damp", "heldout_rms", "full_rms", "cv_rms", "disp_failures")
+LINE_SEARCH_TABLE = (True, (("iteration", "%4d", "int"), ("alpha", "%.17g", "f64"), ("weighted_rms", "%.17g", "f64"), ("rms", "%.17g", "f64"),
+                            ("disp_failures", "%d", "int"), ("chosen", "%d", "flag")))
+TRADEOFF_NONLINEAR_COLUMNS = column_names(TRADEOFF_NONLINEAR_TABLE)
+CROSSVAL_NONLINEAR_COLUMNS = column_names(CROSSVAL_NONLINEAR_TABLE)
+LINE_SEARCH_COLUMNS = column_names(LINE_SEARCH_TABLE)
 
 
 def write_tradeoff_nonlinear(path, rows):
@@ -265,12 +289,12 @@ def write_tradeoff_nonlinear(path, rows):
     linearised system predicts for the member's update, the rms of the weighted and of the plain residual of the travel times through
     the member's model (rms = sqrt(sum / ndata)), dispersion curves without a root.  rows: dicts with the keys TRADEOFF_NONLINEAR_COLUMNS.
     17 significant digits: read_tradeoff_nonlinear returns the numbers bit for bit."""
-    _write_nonlinear(path, TRADEOFF_NONLINEAR_COLUMNS, rows)
+    write_table(path, TRADEOFF_NONLINEAR_TABLE, rows)
 
 
 def read_tradeoff_nonlinear(path):
     """the rows write_tradeoff_nonlinear wrote, as a list of dicts"""
-    return _read_nonlinear(path, TRADEOFF_NONLINEAR_COLUMNS)
+    return read_table(path, TRADEOFF_NONLINEAR_TABLE)
 
 
 def write_crossval_nonlinear(path, rows):
@@ -278,37 +302,24 @@ def write_crossval_nonlinear(path, rows):
     travel-time residuals through the folds' models, the rms of the weighted residual through the full member's model, the linear cv_rms
     for comparison, dispersion curves without a root summed over the pair's members.  rows: dicts with the keys
     CROSSVAL_NONLINEAR_COLUMNS.  17 significant digits: read_crossval_nonlinear returns the numbers bit for bit."""
-    _write_nonlinear(path, CROSSVAL_NONLINEAR_COLUMNS, rows)
+    write_table(path, CROSSVAL_NONLINEAR_TABLE, rows)
 
 
 def read_crossval_nonlinear(path):
     """the rows write_crossval_nonlinear wrote, as a list of dicts"""
-    return _read_nonlinear(path, CROSSVAL_NONLINEAR_COLUMNS)
-
-
-LINE_SEARCH_COLUMNS = ("iteration", "alpha", "weighted_rms", "rms", "disp_failures", "chosen")
+    return read_table(path, CROSSVAL_NONLINEAR_TABLE)
 
 
 def write_line_search(path, rows):
     """<input>LineSearch.dat: one row per (iteration, candidate) -- iteration, alpha, rms of the weighted residual (the score), rms of the
     plain residual, dispersion curves without a root, chosen 0/1.  rows: dicts with the keys LINE_SEARCH_COLUMNS.  The floating-point
     columns are written with 17 significant digits, so that read_line_search returns them bit for bit."""
-    with open(path, "w") as fh:
-        fh.write("# " + " ".join(LINE_SEARCH_COLUMNS) + "\n")
-        for r in rows:
-            fh.write("%4d %.17g %.17g %.17g %d %d\n" % (r["iteration"], r["alpha"], r["weighted_rms"], r["rms"], r["disp_failures"], int(bool(r["chosen"]))))
+    write_table(path, LINE_SEARCH_TABLE, rows)
 
 
 def read_line_search(path):
     """the rows write_line_search wrote, as a list of dicts"""
-    rows = []
-    with open(path) as fh:
-        for line in fh:
-            t = line.split()
-            if not t or t[0].startswith("#"):
-                continue
-            rows.append(dict(iteration=int(t[0]), alpha=float(t[1]), weighted_rms=float(t[2]), rms=float(t[3]), disp_failures=int(t[4]), chosen=int(t[5])))
-    return rows
+    return read_table(path, LINE_SEARCH_TABLE)
 
 
 def write_raypaths(path, paths):
