@@ -405,12 +405,12 @@ static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int
     const int ne = (int)g_pool.size(), nu = (int)U.map.size();
     std::vector<int> owner((size_t)nu, 0);
     if (ne > 1) {
-        std::map<std::pair<uint32_t, uint32_t>, int> src_of;       // source (coordinates bit for bit) -> index in order of first appearance
+        std::map<dsa::SourceKey, int> src_of;       // source (bundle_plan.h: source_key) -> index in order of first appearance
         std::vector<int> src_units, unit_src((size_t)nu);
         for (int u = 0; u < nu; ++u) {
-            uint32_t a, b2; std::memcpy(&a, &U.sx[(size_t)u], 4); std::memcpy(&b2, &U.sz[(size_t)u], 4);
-            auto it = src_of.find({ a, b2 });
-            if (it == src_of.end()) { it = src_of.insert({ { a, b2 }, (int)src_units.size() }).first; src_units.push_back(0); }
+            const dsa::SourceKey key = dsa::source_key(U.sx[(size_t)u], U.sz[(size_t)u]);
+            auto it = src_of.find(key);
+            if (it == src_of.end()) { it = src_of.insert({ key, (int)src_units.size() }).first; src_units.push_back(0); }
             unit_src[(size_t)u] = it->second; ++src_units[(size_t)it->second];
         }
         // blocks of consecutive sources with about nu / ne units each

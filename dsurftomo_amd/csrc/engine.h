@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "bundle_plan.h"
 #include "host_geometry.h"
 #include "kernels.h"
 
@@ -15,6 +16,17 @@ template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// A DevBuf that frees itself: every buffer the engine owns (nothing to list in ~Engine).  The plain DevBuf stays for the ones that
+// are copied as values and released by hand (spmv_state.h).
+template <class T>
+struct OwnedBuf : DevBuf<T> {
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf&) = delete;
+    OwnedBuf& operator=(const OwnedBuf&) = delete;
+    ~OwnedBuf() { this->release(); }
 };
 
 struct SpmvState;
@@ -55,7 +67,7 @@ struct Engine {
     bool have_maps = false;
     float dpl = 0.0f;          // minimum cell width (km)
     float hmin_slow = 0.0f;    // smallest slowness of the maps (window scale)
-    DevBuf<float> velv, veln, slow, risti_c, cbasis, rbasis;
+    OwnedBuf<float> velv, veln, slow, risti_c, cbasis, rbasis;
 
     // plan
     bool planned = false;
@@ -72,26 +84,26 @@ struct Engine {
     int last_chunk_first = -1, last_chunk_n = 0;
     bool fields_resident = false;      // the last chunk's coarse fields are still in their slots (not so after a launch that recycled them)
 
-    DevBuf<SourceDesc> src;
-    DevBuf<RayDesc> rays;
-    DevBuf<float> out;
-    DevBuf<int32_t> err;
-    DevBuf<float> slow_r, Tfin_r, risti_r, vcorner;
-    DevBuf<Rec> F_r, W_c;              // refined records; records of the coarse march windows
-    DevBuf<float> T_c;                 // compact coarse fields (eikonal_core.h)
-    DevBuf<unsigned long long> exc_c;  // their exception tables
+    OwnedBuf<SourceDesc> src;
+    OwnedBuf<RayDesc> rays;
+    OwnedBuf<float> out;
+    OwnedBuf<int32_t> err;
+    OwnedBuf<float> slow_r, Tfin_r, risti_r, vcorner;
+    OwnedBuf<Rec> F_r, W_c;            // refined records; records of the coarse march windows
+    OwnedBuf<float> T_c;               // compact coarse fields (eikonal_core.h)
+    OwnedBuf<unsigned long long> exc_c;  // their exception tables
     int exc_log2cap = 0;
     int exc_log2cap_opt = 0;           // option exc_log2cap: initial table size (0 = from the grid); the table grows by itself when it overflows
     int grown_nnx = 0, grown_nnz = 0;
     int exc_log2cap_grown = 0;         // ... and the size it grew to is kept for the later plans of this grid (an inversion solves the same geometry every iteration)
-    DevBuf<int> seed_r, nseed_r, seed_c, nseed_c, lists, launch_rank;
+    OwnedBuf<int> seed_r, nseed_r, seed_c, nseed_c, lists, launch_rank;
     // field slots of the coarse solve (kernels.h: FimEnds): T_c, exc_c and lists_c hold `pool_slots` slots; a launch with more units than
     // slots recycles them (only when nobody needs the fields afterwards: no rows, no exact mode, no keep_fields)
-    DevBuf<int> lists_c, pool_gen;
-    DevBuf<int32_t> replay_list;       // (round 6) units whose refined box is marched literally behind the hand-off's probe: [0] count, [1 ..] units (kernels.h launch_handoff)
-    DevBuf<unsigned char> replay_scratch;
+    OwnedBuf<int> lists_c, pool_gen;
+    OwnedBuf<int32_t> replay_list;     // (round 6) units whose refined box is marched literally behind the hand-off's probe: [0] count, [1 ..] units (kernels.h launch_handoff)
+    OwnedBuf<unsigned char> replay_scratch;
     int handoff_replay = 1;            // option handoff_replay: 1 = as above; 0 = a hand-off tie that changes what the coarse grid receives flags the unit (the whole unit marched)
-    DevBuf<FimEnds> ends_c;
+    OwnedBuf<FimEnds> ends_c;
     size_t lists_c_stride = 0;
     int pool_slots = 0;
     int field_pool_opt = 0;            // option field_pool: 0 = automatic (four times the workgroups the chip holds), -1 = one slot per unit, > 0 = that many slots
@@ -126,32 +138,31 @@ struct Engine {
     bool refined_bundles_failed = false;      // a refined bundle ran out of rounds / table space: unit by unit until the maps change
     bool refined_bundles_now = false;
     std::vector<FimBundle> h_bundles_r;
-    DevBuf<FimBundle> bundles_r_d;
-    DevBuf<FimEnds> ends_r;
-    DevBuf<float> Br_pool, slowIr;
-    DevBuf<unsigned long long> exc_br;
-    DevBuf<int> lists_br, cand_br;
+    OwnedBuf<FimBundle> bundles_r_d;
+    OwnedBuf<FimEnds> ends_r;
+    OwnedBuf<float> Br_pool, slowIr;
+    OwnedBuf<unsigned long long> exc_br;
+    OwnedBuf<int> lists_br, cand_br;
     size_t slowIr_off_b = 0;                   // floats from slowIr to the second group's block
     int bundle_pool_opt = 0;           // option bundle_pool: bundle field slots (0 = up to 1024; fewer than the bundles of a launch: recycled like the unit slots)
-    DevBuf<float> slowI, B_pool;       // member-minor slowness of all maps; bundle field slots
+    OwnedBuf<float> slowI, B_pool;     // member-minor slowness of all maps; bundle field slots
     bool slowI_ready = false;
     bool bundles_failed = false;       // a bundle of the current maps ran out of rounds: the automatic mode stays unit by unit until the maps change
-    DevBuf<unsigned long long> exc_b;  // exception tables of the bundle slots
-    DevBuf<int> lists_b, bpool_gen, member_flag, cand_b;      // (cand_b: tie candidates per bundle slot, kernels.h FimBundle::cand)
-    DevBuf<FimBundle> bundles_d;
+    OwnedBuf<unsigned long long> exc_b;  // exception tables of the bundle slots
+    OwnedBuf<int> lists_b, bpool_gen, member_flag, cand_b;    // (cand_b: tie candidates per bundle slot, kernels.h FimBundle::cand)
+    OwnedBuf<FimBundle> bundles_d;
     std::vector<FimBundle> h_bundles;
     std::vector<int> h_member_flag;
     int bundle_slots = 0;
     size_t solve_stage_bytes() const;
-    size_t bundle_room(size_t free_b) const;
+    hipError_t bundle_room(size_t* room) const;
     bool grow_unit_pool();
     void release_march_pool();
     bool march_pool_kept = false, released_bundles_for_march = false;      // (exact_ties = 1: the marching pool stays allocated between calls when the device has room, run_exact)
     int bundle_threads() const;
+    BundleOptions bundle_options() const;
     float bundle_window() const;
     float bundle_window_tail() const;
-    size_t bundles_resident(int G, int mpl, int threads = 0) const;
-    int bundle_mpl_of(int G, long nb) const;
     int choose_bundle_size(int step, long* solo_units = nullptr);
     int plan_bundles(int first, int n, int G, int* nsolo, int* nbundles);
     size_t lists_stride = 0;
@@ -168,16 +179,16 @@ struct Engine {
     int exact_heap_blocked = 1;        // option exact_heap_blocked: the march's tree beyond its LDS part in blocks of three levels (exact_kernel.hip: xg_gi): 0 never, 1 batches that fill the chip, 2 whenever the LDS part is whole levels
     int exact_pool = 0;                // units marching at a time (0 = by free memory, at most exact_pool_max)
     size_t exact_pool_max = 16384;     // option exact_pool_max: four units per wavefront, sixteen wavefronts per CU (measured at 1025^2: 10 240 units 1 500, 12 288 1 600, 16 384 1 700 solves/s)
-    DevBuf<unsigned> X_pool;                     // per marching unit: one packed word per node of the whole grid (exact_kernel.hip)
-    DevBuf<unsigned long long> X_heap;           // ... and the tree slots beyond the LDS part
+    OwnedBuf<unsigned> X_pool;                   // per marching unit: one packed word per node of the whole grid (exact_kernel.hip)
+    OwnedBuf<unsigned long long> X_heap;         // ... and the tree slots beyond the LDS part
     // pooled tiles of a times-only march on a large grid (kernels.h XTiles; run_exact)
-    DevBuf<unsigned short> X_tt, X_free;
-    DevBuf<unsigned> X_tp, X_ring, X_pins;
+    OwnedBuf<unsigned short> X_tt, X_free;
+    OwnedBuf<unsigned> X_tp, X_ring, X_pins;
     int exact_tiles_opt = 0, exact_tile_cap = 0;
     bool marched_in_tiles = false;
-    DevBuf<int> x_units, x_nstart;
-    DevBuf<unsigned long long> x_starts;         // the coarse stage's starting tree per marching unit (kernels.h: exact_start_bytes)
-    DevBuf<int32_t> xinfo, tieinfo;
+    OwnedBuf<int> x_units, x_nstart;
+    OwnedBuf<unsigned long long> x_starts;       // the coarse stage's starting tree per marching unit (kernels.h: exact_start_bytes)
+    OwnedBuf<int32_t> xinfo, tieinfo;
     std::vector<unsigned char> h_unit_flags;     // per planned unit after a solve: bit 0 tie met, bit 1 solved by the exact mode
     std::vector<int> h_unit_rounds;               // rounds of the unit's coarse solve (of its bundle's, for a bundled unit)
     std::vector<float> h_unit_tie;               // largest tie influence of the unit (s)
@@ -197,35 +208,35 @@ struct Engine {
     int tie_verdict(int unit, const int32_t* tie_words, const int32_t* info16, bool member);
     std::vector<char> tie_verdicts(int first, int n, const int32_t* tie_words, const int32_t* info16, bool bundled);
     int run_exact(int first, int n, const std::vector<int>& local_units, bool receivers, bool compact, bool may_pool_tiles = false);
-    DevBuf<int8_t> S_r, cinit;
-    DevBuf<int16_t> rst, cst;
-    DevBuf<int32_t> heap, flags, info;
-    DevBuf<FimProblem> prob_r, prob_c;
-    DevBuf<unsigned long long> clocks;
+    OwnedBuf<int8_t> S_r, cinit;
+    OwnedBuf<int16_t> rst, cst;
+    OwnedBuf<int32_t> heap, flags, info;
+    OwnedBuf<FimProblem> prob_r, prob_c;
+    OwnedBuf<unsigned long long> clocks;
     double phase_ticks[kClockSlots] = {};
 
     // Frechet rows: depth-kernel factor S (ray_kernels.hip) and per-launch ray scratch
     bool have_sens = false;
     int sens_nz = 0, sens_kmax = 0;
-    DevBuf<double> Srow, sen_vs, sen_vp, sen_rho;
-    DevBuf<float> vels_d;
+    OwnedBuf<double> Srow, sen_vs, sen_vp, sen_rho;
+    OwnedBuf<float> vels_d;
     std::vector<int> h_trace;          // ids of the rays to trace (flag kRayPath), ascending
     size_t ndata = 0;                  // data (travel times / rows) addressed by the planned rays
     size_t ray_budget = 0;             // bytes for ray slabs per launch (0 = default)
-    DevBuf<int> trace_ids, vlist, nvv, counts, coo_col, coo_iw;
-    DevBuf<long long> offsets;
-    DevBuf<float> slabs, coo_rw;
-    DevBuf<int32_t> rayinfo;
+    OwnedBuf<int> trace_ids, vlist, nvv, counts, coo_col, coo_iw;
+    OwnedBuf<long long> offsets;
+    OwnedBuf<float> slabs, coo_rw;
+    OwnedBuf<int32_t> rayinfo;
     int ray_path_cap = 0;              // > 0: keep up to that many points of every traced ray (dsa_ray_paths)
-    DevBuf<float> paths;               // [traced ray][point][colatitude, longitude]
-    DevBuf<int> path_n;                // points of every traced ray
+    OwnedBuf<float> paths;             // [traced ray][point][colatitude, longitude]
+    OwnedBuf<int> path_n;              // points of every traced ray
     // azimuthal rows (dsa_solve_rows_azimuthal): a ray keeps three slabs [iso | c | s], its row the isotropic block and
     // the gc and gs blocks behind it.  Nothing here is allocated before the first azimuthal solve.
     bool azi_now = false;              // the running solve is an azimuthal one (trace_chunk)
     bool sazi_ready = false;           // Sazi is that of the current depth kernels
-    DevBuf<double> Sazi;               // depth factor of the gc / gs entries (ray_kernels.hip: k_sen_azimuthal)
+    OwnedBuf<double> Sazi;             // depth factor of the gc / gs entries (ray_kernels.hip: k_sen_azimuthal)
     std::vector<unsigned char> h_azi_slot_on;      // dsa_set_azimuthal_slots: per depth-kernel slot, 0 = no gc / gs entries; empty = all on
-    DevBuf<unsigned char> azi_slot_on;
+    OwnedBuf<unsigned char> azi_slot_on;
     bool have_azi = false;             // the last azimuthal solve of this plan succeeded: the sums below are its rays'
     std::vector<float> h_azi_sums;     // per traced ray of the plan (position in h_trace, like the path store): sum of cos 2psi, of sin 2psi over its steps
     std::vector<int> h_azi_steps;      // ... and its steps
@@ -244,15 +255,15 @@ struct Engine {
     // dsa_forward_steps / dsa_step_models (step_kernels.hip): the base model, the steps of a pass and their factors; the receiver times of a
     // pass, what they are compared with (obst, then datweight) and per datum { first datum, receiver count } of its unit, then its group;
     // the misfit sums of a pass
-    DevBuf<float> fs_vsf, fs_steps, fs_alpha, fs_models, fs_times, fs_obs;
-    DevBuf<int> fs_idx;
-    DevBuf<double> fs_meas;
+    OwnedBuf<float> fs_vsf, fs_steps, fs_alpha, fs_models, fs_times, fs_obs;
+    OwnedBuf<int> fs_idx;
+    OwnedBuf<double> fs_meas;
     std::vector<float> h_depz;
     LayerGeom h_geom{};
-    DevBuf<LayerGeom> geom;
-    DevBuf<double> pvstore, curves, tper;
-    DevBuf<float> disp_ws;
-    DevBuf<unsigned long long> disp_diag;
+    OwnedBuf<LayerGeom> geom;
+    OwnedBuf<double> pvstore, curves, tper;
+    OwnedBuf<float> disp_ws;
+    OwnedBuf<unsigned long long> disp_diag;
     // non-fatal diagnostics of the boundary since dispersion_begin / the last plan (dsa_dispersion_diagnostics, dsa_ray_diagnostics)
     long long disp_fail_count = 0;     // dispersion curves that ended with "no zero found" (surfdisp96.f:308-339)
     int disp_fail_first[5] = {};       // first of them in call order: iwave, igr, column (1-based), perturbation (0 = the model itself), period index k
@@ -264,7 +275,7 @@ struct Engine {
     struct DispFailRec { int iwave, igr, nper, column, pert, k; double t[60]; };
     std::vector<DispFailRec> disp_failures;
     std::vector<float> h_vels;         // the model of dsa_dispersion_begin (ncol * nz): the replay's input
-    DevBuf<unsigned long long> disp_fail_list;
+    OwnedBuf<unsigned long long> disp_fail_list;
     int dispersion_failure(int index, int* info, double* vals, float* table, double* c) const;
     long long rays_clamped = 0;        // traced rays that were clamped at the model boundary (reference rbint, CalSurfG.f90:2082-2101)
     int first_clamped_unit = -1;       // planned unit of the first of them
@@ -279,8 +290,8 @@ struct Engine {
     // COO rows kept on the device across the chunks of a solve (rows_on_device): what dsa_iteration_system_device and LSMR
     // work on without the matrix ever visiting the host (reference: rw / iw / col of main.f90:349-359, 487-489)
     bool rows_on_device = false;
-    DevBuf<float> G_rw;
-    DevBuf<int> G_row, G_col;          // 1-based datum (row) and model parameter (column)
+    OwnedBuf<float> G_rw;
+    OwnedBuf<int> G_row, G_col;        // 1-based datum (row) and model parameter (column)
     long long G_nar = 0;
     template <class T> int ensure_keep(DevBuf<T>& b, size_t n, size_t used);
 

@@ -45,7 +45,7 @@ template <class T>
 int Engine::ensure(DevBuf<T>& b, size_t n)
 {
     if (b.cap >= n) return 0;
-    if (b.p) { HIP_TRY(this, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    b.release();
     if (n == 0) return 0;
     HIP_TRY(this, hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T)));
     b.cap = n;
@@ -83,19 +83,7 @@ template int Engine::ensure<FimBundle>(DevBuf<FimBundle>&, size_t);
 Engine::~Engine()
 {
     release_spmv(spmv);
-    auto rel = [](auto& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; };
-    rel(velv); rel(veln); rel(slow); rel(risti_c); rel(cbasis); rel(rbasis);
-    rel(src); rel(rays); rel(out); rel(err);
-    rel(slow_r); rel(F_r); rel(Tfin_r); rel(S_r); rel(risti_r); rel(vcorner); rel(seed_r); rel(nseed_r); rel(launch_rank); rel(slowI); rel(B_pool); rel(exc_b); rel(lists_b); rel(bpool_gen); rel(member_flag); rel(bundles_d);
-    rel(rst); rel(cst); rel(cinit); rel(heap); rel(flags); rel(T_c); rel(exc_c); rel(W_c); rel(seed_c); rel(nseed_c);
-    rel(prob_r); rel(prob_c); rel(paths); rel(path_n); rel(Sazi); rel(azi_slot_on); rel(info); rel(clocks); rel(lists);
-    rel(Srow); rel(sen_vs); rel(sen_vp); rel(sen_rho); rel(vels_d); rel(trace_ids); rel(vlist); rel(nvv); rel(counts); rel(offsets);
-    rel(coo_col); rel(coo_iw); rel(slabs); rel(coo_rw); rel(rayinfo); rel(G_rw); rel(G_row); rel(G_col);
-    rel(geom); rel(pvstore); rel(curves); rel(tper); rel(disp_ws);
-    rel(fs_vsf); rel(fs_steps); rel(fs_alpha); rel(fs_models); rel(fs_times); rel(fs_obs); rel(fs_idx); rel(fs_meas);
     if (stream2) { (void)hipStreamDestroy(stream2); (void)hipEventDestroy(ev_b0); (void)hipEventDestroy(ev_b1); stream2 = nullptr; }
-    rel(cand_b); rel(bundles_r_d); rel(ends_r); rel(Br_pool); rel(slowIr); rel(exc_br); rel(lists_br); rel(cand_br);
-    rel(lists_c); rel(pool_gen); rel(ends_c); rel(disp_diag); rel(disp_fail_list); rel(X_pool); rel(X_heap); rel(X_tt); rel(X_tp); rel(X_ring); rel(X_free); rel(X_pins); rel(x_starts); rel(x_nstart); rel(x_units); rel(xinfo); rel(tieinfo);
     for (auto& ev : events) if (ev) (void)hipEventDestroy(ev);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -573,8 +561,7 @@ void Engine::release_march_pool()
     if (exact_ties == 2 || (!X_pool.cap && !X_tp.cap)) return;
     if (exact_ties == 1 && march_pool_kept) return;          // (round 6: kept by the last march because the device had room for it beside everything else)
     (void)hipStreamSynchronize(stream);
-    auto release = [](auto& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; };
-    release(X_pool); release(X_heap); release(X_tt); release(X_tp); release(X_ring); release(X_free); release(X_pins);
+    X_pool.release(); X_heap.release(); X_tt.release(); X_tp.release(); X_ring.release(); X_free.release(); X_pins.release();
     march_pool_kept = false;
 }
 
@@ -604,27 +591,6 @@ size_t Engine::solve_stage_bytes() const
     return b(lists) + b(lists_c) + b(pool_gen) + b(ends_c) + b(src) + b(slow_r) + b(F_r) + b(Tfin_r) + b(S_r) + b(risti_r) + b(vcorner) + b(seed_r) + b(nseed_r) +
            b(rst) + b(cst) + b(cinit) + b(heap) + b(flags) + b(T_c) + b(exc_c) + b(W_c) + b(seed_c) + b(nseed_c) + b(launch_rank) + b(prob_r) + b(prob_c) +
            b(info) + b(clocks) + b(tieinfo) + b(xinfo) + b(x_units) + b(B_pool) + b(exc_b) + b(lists_b) + b(bpool_gen) + b(bundles_d) + b(member_flag);
-}
-
-// bundles the chip holds at a time: one workgroup of 512 threads per CU, two of 256 (four members per lane: 204 VGPRs) or three (two
-// members per lane: 168 VGPRs, round 4)
-size_t Engine::bundles_resident(int G, int mpl, int threads) const
-{
-    if (threads <= 0) threads = bundle_threads();
-#ifdef DSA_BUNDLE_WAVES          // (probe builds: bundle_kernel.hip compiled for that many waves per SIMD whatever the members per lane)
-    if (threads == 256) return (size_t)256 * DSA_BUNDLE_WAVES;
-#endif
-    // (bundle_kernel.hip: DSA_BUNDLE_OCC -- three workgroups of 256 threads per CU with two members per lane and for bundles of 16)
-    return (size_t)256 * (threads >= 512 ? 1 : (mpl == 2 || G == 16) ? 3 : 2);
-}
-
-// Members per lane of a launch of nb bundles of G: the option, or 16 members four per lane; 8 and 4 members two per lane (three workgroups
-// per CU) when the launch holds more than the 512 bundles that two per CU take, else four
-int Engine::bundle_mpl_of(int G, long nb) const
-{
-    if (bundle_mpl) return bundle_mpl;
-    if (bundle_threads() != 256 || G == 16) return 4;
-    return nb > 512 ? 2 : 4;
 }
 
 // Causal window of the bundles in cells: the option (default 0.6: at full occupancy the evaluations are what costs); a small launch of
@@ -657,6 +623,11 @@ int Engine::bundle_threads() const
     if (bundle_threads_opt == 256 || bundle_threads_opt == 512 || bundle_threads_opt == 768) return bundle_threads_opt;
     if (std::max(g.nnx, g.nnz) > 1500) return 768;
     return bundle_wide ? 768 : 256;
+}
+
+BundleOptions Engine::bundle_options() const
+{
+    return { bundle_opt, bundle_mpl, bundle_tail_opt, bundle_order_opt, bundle_threads(), bundle_threads_opt == 0 };
 }
 
 BatchPtrs Engine::batch() const
@@ -822,30 +793,13 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
         HIP_TRY(this, hipMemcpyAsync(risti_r.p, h_risti_r.data() + (size_t)first * kRefMax, (size_t)n * kRefMax * 4, hipMemcpyHostToDevice, stream));
         HIP_TRY(this, hipEventRecord(events[1], stream));
         HIP_TRY(this, hipMemsetAsync(pool_gen.p, 0, (size_t)pool_slots * sizeof(int), stream));       // (the coarse solve itself resets its field slot: FimEnds)
-        {   // Launch order of the coarse solves: a launch ends with its slowest workgroups, and the rounds of a solve grow with the
-            // distance from the source to the farthest corner of the grid, so the units with the longest fronts get the lowest
-            // workgroup numbers (dispatched first) and the short ones fill the tail.
-            h_launch_rank.resize((size_t)n);
-            std::vector<std::pair<float, int>> far((size_t)n);
-            for (int u = 0; u < n; ++u) {
-                const SourceDesc& s = h_src[first + u];
-                const float fx = (s.scx - g.gox) / g.dnx, fz = (s.scz - g.goz) / g.dnz;
-                const float dx = std::max(fx, (float)(g.nnx - 1) - fx), dz = std::max(fz, (float)(g.nnz - 1) - fz);
-                far[u] = { -(dx * dx + dz * dz), u };
-            }
-            std::stable_sort(far.begin(), far.end());
-            for (int r = 0; r < n; ++r) h_launch_rank[(size_t)far[r].second] = r;
-            HIP_TRY(this, hipMemcpyAsync(launch_rank.p, h_launch_rank.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        }
         // the tie detector runs in the fixed-point modes (round 5: in exact_ties = 0 too, option tie_detect, so that a call that leaves tie-prone
         // units to the fixed point can say so: DSA_STAT_TIE_UNITS / DSA_STAT_TIE_UNITS_LEFT, dsa_unit_ties)
         const bool detect = exact_ties == 1 || (exact_ties == 0 && tie_detect);
-        // bundles: the units of one source side by side in one workgroup (bundle_kernel.hip).  Solo units keep the launch ranks
-        // 0 .. nsolo-1 (and the field slots those select), the members of the bundles follow, bundle by bundle.
+        // bundles: the units of one source side by side in one workgroup (bundle_kernel.hip).  Launch order (bundle_plan.h): solo units keep
+        // the launch ranks 0 .. nsolo-1 (and the field slots those select), the members of the bundles follow, bundle by bundle.
         int nsolo = n, nbundles = 0;
-        if (bundle_G > 0 && !bundle_off_chunk) {
-            if (plan_bundles(first, n, bundle_G, &nsolo, &nbundles) != 0) return status;
-        }
+        if (plan_bundles(first, n, bundle_off_chunk ? 0 : bundle_G, &nsolo, &nbundles) != 0) return status;
         const bool refined_b = nbundles > 0 && refined_bundles_now && !bundle_off_chunk;
         // (what the bundles hold, recorded now: a memory-bound march below gives the bundle buffers back before the statistic is written)
         const double bundle_mb = nbundles ? (double)(B_pool.cap * 4 + exc_b.cap * 8 + lists_b.cap * 4 + slowI.cap * 4 + cand_b.cap * 4 + Br_pool.cap * 4 + exc_br.cap * 8 + lists_br.cap * 4 + cand_br.cap * 4 + slowIr.cap * 4) / 1.0e6 : 0.0;
@@ -862,7 +816,7 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
             // solo units (launch ranks 0 .. nsolo-1) one by one; the bundles' members side by side: member-minor slowness, the bundle kernel on the
             // boxes (256 threads), the converged members back into their records
             launch_fim(prob_r.p, nsolo, sr, stream);
-            const int cnt[2] = { bundles_a, nbundles - bundles_a }, GG[2] = { bundle_G, bundle_Gb }, mpl[2] = { bundle_mpl_now, bundles_b > 0 && bundle_threads_b == 256 ? bundle_mpl_b : bundle_mpl_of(bundle_Gb ? bundle_Gb : bundle_G, nbundles) };
+            const int cnt[2] = { bundles_a, nbundles - bundles_a }, GG[2] = { bundle_G, bundle_Gb }, mpl[2] = { bundle_mpl_now, bundles_b > 0 && bundle_threads_b == 256 ? bundle_mpl_b : bundle_mpl_of(bundle_options(), bundle_Gb ? bundle_Gb : bundle_G, nbundles) };
             for (int q = 0; q < 2; ++q) {
                 if (cnt[q] <= 0) continue;
                 const FimBundle* const bq = bundles_r_d.p + (q ? bundles_a : 0);
@@ -1046,239 +1000,71 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
     return 0;
 }
 
-// What the bundle field slots may take: the free memory, or -- a memory budget is set (dsa_set_memory_budget: several ranks on one device) --
-// what the budget leaves beside the unit slots and the per-unit arrays, so that two ranks planning at once cannot both claim the device
-// (ADVICE r03).  (The callers take 70 % of it.)
-size_t Engine::bundle_room(size_t free_b) const
+// What the bundle field slots may share: the free memory and what a previous call's slots hold (reused), or -- a memory budget is set
+// (dsa_set_memory_budget: several ranks on one device) -- what the budget leaves beside the unit slots and the per-unit arrays, so that
+// two ranks planning at once cannot both claim the device.  (bundle_plan.h: the slots take kBundleShare of it.)
+hipError_t Engine::bundle_room(size_t* room) const
 {
-    if (mem_budget == 0) return free_b;
+    size_t free_b = 0, total_b = 0;
+    const hipError_t rc = hipMemGetInfo(&free_b, &total_b);
+    if (rc != hipSuccess) return rc;
+    free_b += B_pool.cap * 4 + exc_b.cap * 8 + lists_b.cap * 4;
+    *room = free_b;
+    if (mem_budget == 0) return hipSuccess;
     const size_t held = (size_t)pool_slots * per_slot_bytes + (size_t)chunk * per_unit_bytes;
-    const size_t room = plan_budget > held ? plan_budget - held : 0;
-    return std::min(free_b, (size_t)((double)room / 0.7));
+    const size_t left = plan_budget > held ? plan_budget - held : 0;
+    *room = std::min(free_b, (size_t)((double)left / kBundleShare));
+    return hipSuccess;
 }
 
-// Members per bundle for this call: the option, or (automatic) the largest of 16 / 8 / 4 that still gives the chip enough workgroups
-// and whose field slots fit the memory; 0 = no bundles.  `step` = units per launch.
+// Members per bundle for this call (bundle_plan.h: choose_bundle_size), 0 = no bundles; sets bundle_wide.  `step` = units per launch.
 int Engine::choose_bundle_size(int step, long* solo_units)
 {
     if (solo_units) *solo_units = (long)h_src.size();
     bundle_wide = false;
-    if (bundle_opt == 0 || h_src.empty() || (bundles_failed && bundle_opt == 1)) return 0;
-    // units per source (same coordinates bit for bit), in planned order
-    std::map<std::pair<uint32_t, uint32_t>, int> count;
-    for (const SourceDesc& sd : h_src) { uint32_t a, b2; std::memcpy(&a, &sd.scx, 4); std::memcpy(&b2, &sd.scz, 4); ++count[{ a, b2 }]; }
-    auto bundles_with = [&](int G) { long nb = 0; for (auto& kv : count) { nb += kv.second / G; if (kv.second % G >= 2) ++nb; } return nb; };
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
-    free_b += B_pool.cap * 4 + exc_b.cap * 8 + lists_b.cap * 4;          // (what a previous call holds is reused)
-    free_b = bundle_room(free_b);
-    auto slot_bytes = [&](int G) { int lg = G == 16 ? 4 : G == 8 ? 3 : 2; return (size_t)(G * DSA_BSTRIDE + 1) * nrec_c * 4 + ((size_t)8 << (exc_log2cap + lg)) + lists_c_stride * 4; };
-    auto fits = [&](int G) {
-        if ((unsigned long long)nrec_c * (unsigned long long)G * 4ull * DSA_BSTRIDE >= (1ull << 32)) return false;          // 32-bit byte offsets inside a bundle field
-        if (nrec_c >= ((size_t)1 << 27)) return false;                                                          // (record indices share the ready-list word with the far-load code, and -- shifted by four -- the tie candidates' word with a flag bit)
-        if ((unsigned long long)nrec_c * (unsigned long long)G >= (1ull << 30)) return false;                // exception keys
-        if ((unsigned long long)nrec_c * (unsigned long long)nmaps * 4ull >= (1ull << 32)) return false;      // ... and inside the member-minor slowness
-        const long nb = std::min<long>(bundles_with(G), (long)step);
-        const size_t want = (size_t)std::min<long>(std::max<long>(nb, 1), (long)(bundles_resident(G, bundle_mpl_of(G, nb)) * 9 / 8));      // (bundles resident at a time, and a few more)
-        return want * slot_bytes(G) + (size_t)nmaps * nrec_c * 4 < (size_t)(0.7 * (double)free_b);      // (what plan_bundles allows itself)
-    };
-    if (bundle_opt == 4 || bundle_opt == 8 || bundle_opt == 16) {
-        if (!(fits(bundle_opt) && bundles_with(bundle_opt) > 0)) return 0;
-        if (solo_units) { long cov = 0; for (auto& kv : count) { cov += (kv.second / bundle_opt) * bundle_opt; if (kv.second % bundle_opt >= 2) cov += kv.second % bundle_opt; } *solo_units = (long)h_src.size() - cov; }
-        return bundle_opt;
-    }
-    // automatic: a bundle is one workgroup where its members would have been G, so it pays only while the bundles still fill the chip.
-    // The best of the estimates below wins: a launch-time model from times measured at 1025^2 (only the ratios decide; they hold from 129^2
-    // to 4097^2: profiles/r03_bundle_sizes.log, r04_bundle_occupancy.log).  Beyond 1500 nodes per side the bundle kernel runs wide (768
-    // threads, one workgroup per CU: a third as many bundles fill the chip); round 3's table of rates serves there.
-    // Grid size: round 3 kept grids below 400 nodes per side unit by unit.  With round 4's kernel the bundles win there too when the call
-    // has the sources (16 periods x 1000 sources: 385^2 66 k -> 141 k solves/s, 257^2 119 k -> 200 k, 129^2 232 k -> 288 k; 200 sources at
-    // 257^2: 101 k -> 116 k; profiles/r04_bundle_occupancy.log), so the floor is 120 nodes per side.
-    if (std::min(g.nnx, g.nnz) < 120) return 0;
-    // ... but only for launches that fill the chip: below 400 nodes per side a solve is a few hundred short rounds, many unit-by-unit
-    // workgroups share a CU, and a handful of bundles -- the Taipei example: 34 bundles for 449 units at 137^2 -- take longer than the
-    // units by themselves (coarse solves 2.9 -> 7.0 ms); there a size needs 384 bundles of at least 8 members and the wide variant stays off
-    const bool small_grid = std::min(g.nnx, g.nnz) < 400;
-    const double n_units = (double)std::min<size_t>(h_src.size(), (size_t)step);
-    const double solo_rate = 10.0 * std::min(1.0, n_units / 1100.0);          // k solves/s
-    double best = solo_rate * 1.05;
-    int pick = 0;
-    const int sizes[3] = { 16, 8, 4 };
-    // Round 4 (256-thread kernel): a launch's time from the measured time of ONE bundle at one / two / three workgroups per CU at 1025^2 (ms;
-    // the ratios hold at other sizes: only ratios decide) -- a bundle takes what its rounds take, whatever shares the chip with it, so a
-    // launch of nb <= 768 bundles takes one bundle's time at that occupancy, a longer one whole generations plus a last partial one that
-    // costs at least 45 % of a generation (profiles/r04_bundle_occupancy.log); between 768 and 1 500 bundles plan_bundles cuts the last
-    // ones in halves (1 000 bundles of 16: 383 ms)
-    const double t_one[3][3] = { { 189.5, 210.0, 241.0 }, { 130.8, 151.7, 187.2 }, { 104.8, 125.4, 164.3 } };
-    const double rate512[3] = { 24.5, 20.4, 15.5 };                             // (large grids, one wide workgroup per CU: round 3's table; only the ratios decide)
-    const double t_wide[3] = { 106.0, 77.0, 69.0 };                             // (768 threads at 1025^2, a CU per bundle: ms of one bundle of 16 / 8 / 4)
-    bool pick_wide = false;
-    for (int k = 0; k < 3; ++k) {
-        const int G = sizes[k];
-        long nb = 0, covered = 0;
-        for (auto& kv : count) { nb += kv.second / G; covered += (kv.second / G) * G; if (kv.second % G >= 2) { ++nb; covered += kv.second % G; } }
-        if (nb == 0 || !fits(G)) continue;
-        nb = std::min<long>(nb, (long)step);
-        if (small_grid && (nb < 384 || G < 8)) continue;      // (bundles of 4 lose there: 100 sources x 16 at 257^2 73 k against 93 k unit by unit)
-        const double frac = (double)covered / (double)h_src.size();                  // units that end up in bundles ...
-        const double fill = (double)covered / ((double)nb * G);                       // ... and how full the bundles are
-        double est;
-        if (bundle_threads() >= 512) est = frac * rate512[k] * fill * std::min(1.0, (double)nb / 280.0) + (1.0 - frac) * solo_rate;
-        else {
-            const double occ = (double)nb / 256.0;
-            double ms;
-            if (occ <= 1.0) ms = t_one[k][0];
-            else if (occ <= 2.0) ms = t_one[k][0] + (t_one[k][1] - t_one[k][0]) * (occ - 1.0);
-            else if (occ <= 3.0) ms = t_one[k][1] + (t_one[k][2] - t_one[k][1]) * (occ - 2.0);
-            else {
-                const double gens = std::floor((double)nb / 768.0), rem = (double)nb / 768.0 - gens;
-                ms = t_one[k][2] * (gens + (rem > 0.0 ? 0.45 + 0.55 * rem : 0.0));
-                if (G >= 8 && nb > 768 && nb < 1500) ms *= 0.98;                    // (the halved last bundles)
-                // (round 5) at most 256 bundles beyond the first generation: whole, 768 threads wide, a CU each as the first generation leaves
-                // (1 000 bundles of 16: 325 ms against 368 with halves, profiles/r05_ab_bundle_kernel.log)
-                if (bundle_tail_opt == 1 && G >= 8 && bundle_mpl == 0 && nb > 768 && nb <= 1024) ms = t_one[k][2] + 0.8 * (t_wide[k] + 12.0 * (double)(nb - 768) / 256.0);
-            }
-            // k solves/s (= units per ms) of the whole launch: the bundles in `ms` (a little less when they are not full: idle member lanes save no trips), the rest unit by unit behind them
-            const double units_s = n_units * (1.0 - frac);
-            est = n_units / (ms * (0.65 + 0.35 * fill) + units_s / std::max(solo_rate, 1e-9));
-        }
-        bool wide = false;
-        if (bundle_threads_opt == 0 && bundle_threads() == 256 && nb <= 256 && !small_grid) {
-            // ... or a CU per bundle, 768 threads wide (one bundle's time at that width, nearly flat in the number of bundles)
-            const double ms_w = t_wide[k] + 12.0 * (double)nb / 256.0;
-            const double est_w = n_units / (ms_w * (0.65 + 0.35 * fill) + n_units * (1.0 - frac) / std::max(solo_rate, 1e-9));
-            if (est_w > est) { est = est_w; wide = true; }
-        }
-        if (est > best) { best = est; pick = G; pick_wide = wide; if (solo_units) *solo_units = (long)h_src.size() - covered; }
-    }
-    bundle_wide = pick_wide;
-    return pick;
+    const BundleOptions o = bundle_options();
+    SizeInputs in;
+    if (!bundles_possible(o, bundles_failed) || h_src.empty() || bundle_room(&in.room) != hipSuccess) return 0;
+    in.nnx = g.nnx; in.nnz = g.nnz; in.nmaps = nmaps; in.nrec_c = nrec_c; in.exc_log2cap = exc_log2cap; in.lists_c_stride = lists_c_stride;
+    in.step = step; in.bstride = DSA_BSTRIDE; in.bundles_failed = bundles_failed;
+    const SizeChoice c = dsa::choose_bundle_size(source_unit_counts(h_src.data(), h_src.size()), in, o);
+    bundle_wide = c.wide;
+    if (solo_units) *solo_units = c.solo_units;
+    return c.G;
 }
 
-// Bundles of the resident chunk [first, first + n): launch ranks (solo units first, longest fronts first in both groups), the member
-// flags for k_make_problems, the bundle descriptors and their field slots.
+// The resident chunk [first, first + n) with bundles of G (0: unit by unit): the launch ranks and, for bundles, the member flags for
+// k_make_problems (bundle_plan.h: plan_layout), the bundle descriptors and their field slots.
 int Engine::plan_bundles(int first, int n, int G, int* nsolo_out, int* nbundles_out)
 {
-    std::map<std::pair<uint32_t, uint32_t>, std::vector<int>> groups;
-    for (int u = 0; u < n; ++u) {
-        const SourceDesc& sd = h_src[(size_t)(first + u)];
-        uint32_t a, b2; std::memcpy(&a, &sd.scx, 4); std::memcpy(&b2, &sd.scz, 4);
-        groups[{ a, b2 }].push_back(u);
-    }
-    auto farness = [&](int u) {
-        const SourceDesc& sd = h_src[(size_t)(first + u)];
-        const float fx = (sd.scx - g.gox) / g.dnx, fz = (sd.scz - g.goz) / g.dnz;
-        const float dx = std::max(fx, (float)(g.nnx - 1) - fx), dz = std::max(fz, (float)(g.nnz - 1) - fz);
-        return -(dx * dx + dz * dz);
-    };
-    h_member_flag.assign((size_t)n, 0);
-    std::vector<std::pair<float, std::vector<int>>> pieces;
-    for (auto& kv : groups) {
-        const std::vector<int>& v = kv.second;
-        for (size_t k = 0; k < v.size(); k += (size_t)G) {
-            const size_t m = std::min<size_t>((size_t)G, v.size() - k);
-            if (m < 2) continue;
-            pieces.push_back({ farness(v[k]), std::vector<int>(v.begin() + (long)k, v.begin() + (long)(k + m)) });
-            for (size_t q = k; q < k + m; ++q) h_member_flag[(size_t)v[q]] = 1;
-        }
-    }
-    std::stable_sort(pieces.begin(), pieces.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    std::vector<std::pair<float, int>> solo;
-    for (int u = 0; u < n; ++u) if (!h_member_flag[(size_t)u]) solo.push_back({ farness(u), u });
-    std::stable_sort(solo.begin(), solo.end());
-    const int nsolo = (int)solo.size();
-    int nb = (int)pieces.size();
+    const BundleLayout L = plan_layout(h_src.data() + first, n, g, G, bundle_options());
+    const int nsolo = L.nsolo, nb = L.bundles_a + L.bundles_b;
     *nsolo_out = nsolo; *nbundles_out = nb;
-    bundles_a = nb; bundles_b = 0; bundle_Gb = 0;
-    if (nb == 0) return 0;
-    // Members per lane and workgroups per CU (round 4, profiles/r04_bundle_occupancy.log; bundle_mpl_of, bundle_kernel.hip: DSA_BUNDLE_OCC):
-    // bundles of 16 run three workgroups per CU (768 resident), bundles of 8 / 4 too when the launch has more than 512 of them.  A bundle
-    // takes longer with two neighbours on its CU than with one (768 bundles of 16: 241 ms; 500: 210; 250: 190), but a CU finishes more of
-    // them per second.  The catch is a last generation that is nearly empty -- 1 000 bundles = 768 + 232 -- so, automatic mode, between 768
-    // and 1 500 bundles: the first 768 (the longest) as they are and the REST CUT IN HALVES -- bundles of G / 2, two members per lane, on a
-    // second stream, which fill the CUs the first launch frees one by one (1 000 sources x 16 periods: 383 ms against ~430 uncut).
-    const bool auto_mpl = bundle_mpl == 0 && bundle_threads() == 256;
-    const int res3 = 768;
-    bundle_mpl_now = bundle_mpl_of(G, nb);
-    bundle_mpl_b = bundle_mpl ? bundle_mpl : 2;
-    bundle_threads_b = bundle_threads();
-    std::vector<std::pair<float, std::vector<int>>> tail;
-    if (auto_mpl && bundle_opt == 1 && G >= 8 && nb > res3 && nb < 1500 && bundle_tail_opt == 1 && nb - res3 <= 256) {
-        // Round 5, option bundle_tail = 1: the bundles beyond the first generation stay WHOLE and run 768 threads wide on the second stream, a CU
-        // each as the first generation's workgroups leave (a bundle of 16 alone on a CU: 106 ms wide against 190 with 256 threads)
-        tail.assign(pieces.begin() + res3, pieces.end());
-        pieces.resize((size_t)res3);
-        for (const auto& pc : tail) for (int u : pc.second) h_member_flag[(size_t)u] = 2;      // (their own causal window: bundle_window_tail)
-        bundles_a = res3; bundles_b = (int)tail.size(); bundle_Gb = G;
-        bundle_mpl_b = 4; bundle_threads_b = 768;
-    } else if (auto_mpl && bundle_opt == 1 && G >= 8 && nb > res3 && nb < 1500) {
-        std::vector<std::pair<float, std::vector<int>>> keep(pieces.begin(), pieces.begin() + res3);
-        for (size_t k = (size_t)res3; k < pieces.size(); ++k) {
-            const std::vector<int>& v = pieces[k].second;
-            if ((int)v.size() >= G / 2 + 2) {
-                tail.push_back({ pieces[k].first, std::vector<int>(v.begin(), v.begin() + G / 2) });
-                tail.push_back({ pieces[k].first, std::vector<int>(v.begin() + G / 2, v.end()) });
-            } else keep.push_back(pieces[k]);
-        }
-        pieces.swap(keep);
-        bundles_a = (int)pieces.size(); bundles_b = (int)tail.size(); bundle_Gb = G / 2;
-        nb = bundles_a + bundles_b;
-        *nbundles_out = nb;
+    h_launch_rank = L.launch_rank;
+    if (G > 0) { h_member_flag = L.member_flag; bundles_a = L.bundles_a; bundles_b = L.bundles_b; bundle_Gb = L.bundle_Gb; }
+    if (nb == 0) {
+        HIP_TRY(this, hipMemcpyAsync(launch_rank.p, h_launch_rank.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        return 0;
     }
-    if (bundle_order_opt && bundles_b > 0 && bundle_threads_b == 768 && (int)pieces.size() == res3) {
-        // Round 6, option bundle_order (A/B switch, default 0): which bundles share a CU.  If the first generation's 768 workgroups went out round robin --
-        // k, k + 256 and k + 512 on one CU -- "longest first" would give every CU a long, a middle and a short bundle, and the wide tail, whose workgroups
-        // need whole CUs, could only start when the generation is all but over; position p holding rank 3 (p mod 256) + p / 256 would then put bundles of
-        // similar length on one CU.  Measured (profiles/r06_ab_bundle_order.log): 350.4 ms against 342.0 -- the dispatcher fills a CU with CONSECUTIVE
-        // workgroups, "longest first" already is the grouped order (the rocprof trace shows the tail starting with the generation and ending 84 ms after it),
-        // and the permutation un-groups it.
-        std::vector<std::pair<float, std::vector<int>>> perm((size_t)res3);
-        const int ncu = res3 / 3;
-        for (int p2 = 0; p2 < res3; ++p2) {
-            const int rank2 = bundle_order_opt == 1 ? 3 * (p2 % ncu) + p2 / ncu : p2;
-            perm[(size_t)p2] = pieces[(size_t)rank2];
-        }
-        if (bundle_order_opt == 1) pieces.swap(perm);
-    }
-    h_launch_rank.assign((size_t)n, 0);
-    for (int r = 0; r < nsolo; ++r) h_launch_rank[(size_t)solo[(size_t)r].second] = r;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(this, hipMemGetInfo(&free_b, &total_b));
-    free_b += B_pool.cap * 4 + exc_b.cap * 8 + lists_b.cap * 4;
-    free_b = bundle_room(free_b);
-    // field slots per group of bundles: one per bundle, or -- more bundles than the chip holds at a time -- as many as can be resident and a
-    // few more; a bundle claims a free one when it starts (FimBundle::slot_busy)
-    struct Group { int G, count, slots, xlog; size_t b_stride, b_off, exc_off, slot0; };
-    Group gr[2] = { { G, bundles_a, 0, 0, 0, 0, 0, 0 }, { bundle_Gb, bundles_b, 0, 0, 0, 0, 0, 0 } };
-    size_t b_total = 0, exc_total = 0, slots_total = 0;
-    for (int q = 0; q < 2; ++q) {
-        Group& r = gr[q];
-        if (r.count == 0) continue;
-        const int lg = r.G == 16 ? 4 : r.G == 8 ? 3 : 2;
-        r.xlog = exc_log2cap + lg;
-        r.b_stride = (size_t)(r.G * DSA_BSTRIDE + 1) * nrec_c;
-        const size_t slot_b = r.b_stride * 4 + ((size_t)8 << r.xlog) + lists_c_stride * 4;
-        const size_t room = (size_t)(0.7 * (double)free_b) / slot_b / (bundles_b ? 2 : 1);
-        if (room < 1) { fail(DSA_ERR_DEVICE, "bundles: no room for one bundle field slot (%zu B)", slot_b); return DSA_ERR_DEVICE; }
-        const size_t resident = bundles_resident(r.G, q == 0 ? bundle_mpl_now : bundle_mpl_b, q == 0 ? bundle_threads() : bundle_threads_b);
-        r.slots = (int)std::min<size_t>({ (size_t)r.count, (size_t)(bundle_pool_opt > 0 ? bundle_pool_opt : (int)(resident + resident / 8)), room });
-        r.b_off = b_total; r.exc_off = exc_total; r.slot0 = slots_total;
-        b_total += (size_t)r.slots * r.b_stride; exc_total += (size_t)r.slots << r.xlog; slots_total += (size_t)r.slots;
-    }
-    bundle_slots = gr[0].slots;
+    bundle_mpl_now = L.mpl_now; bundle_mpl_b = L.mpl_b; bundle_threads_b = L.threads_b;
+    size_t room = 0;
+    HIP_TRY(this, bundle_room(&room));
+    const SlotPlan sp = size_bundle_slots(L, G, bundle_threads(), nrec_c, exc_log2cap, lists_c_stride, DSA_BSTRIDE, bundle_pool_opt, room);
+    if (sp.no_room_for) { fail(DSA_ERR_DEVICE, "bundles: no room for one bundle field slot (%zu B)", sp.no_room_for); return DSA_ERR_DEVICE; }
+    const size_t slots_total = sp.slots_total;
+    bundle_slots = sp.gr[0].slots;
     // tie candidates per bundle slot (the census' list, bundle_kernel.hip): an eighth of the field's nodes, at least 65 535 entries
     const bool want_cand = exact_ties == 1 || (exact_ties == 0 && tie_detect);
     const size_t cand_cap = std::max<size_t>(65535, nrec_c / 8), cand_stride = ((cand_cap + 4) & ~(size_t)3) + kTieSeenSlots;
     if (want_cand && ensure(cand_b, slots_total * cand_stride)) return status;
-    if (ensure(B_pool, b_total) || ensure(exc_b, exc_total) || ensure(lists_b, slots_total * lists_c_stride) || ensure(bpool_gen, slots_total) ||
+    if (ensure(B_pool, sp.b_total) || ensure(exc_b, sp.exc_total) || ensure(lists_b, slots_total * lists_c_stride) || ensure(bpool_gen, slots_total) ||
         ensure(bundles_d, (size_t)nb) || ensure(member_flag, (size_t)n) || ensure(slowI, (size_t)nmaps * nrec_c)) return status;
     if (!slowI_ready) { launch_interleave_maps(slow.p, nrec_c, nmaps, slowI.p, stream); slowI_ready = true; }
     h_bundles.assign((size_t)nb, FimBundle{});
-    int rank = nsolo;
     for (int k = 0; k < nb; ++k) {
-        const Group& r = gr[k < bundles_a ? 0 : 1];
-        const std::vector<int>& mem = k < bundles_a ? pieces[(size_t)k].second : tail[(size_t)(k - bundles_a)].second;
+        const SlotGroup& r = sp.gr[k < bundles_a ? 0 : 1];
         const int kk = k < bundles_a ? k : k - bundles_a;
+        const std::vector<int>& mem = k < bundles_a ? L.whole[(size_t)kk] : L.tail[(size_t)kk];
         FimBundle& bd = h_bundles[(size_t)k];
         bd.B = B_pool.p + r.b_off; bd.b_stride = r.b_stride; bd.p_offset = (size_t)r.G * DSA_BSTRIDE * nrec_c;
         bd.exc = exc_b.p + r.exc_off; bd.exc_stride = (size_t)1 << r.xlog; bd.exc_log2cap = r.xlog;
@@ -1290,8 +1076,7 @@ int Engine::plan_bundles(int first, int n, int G, int* nsolo_out, int* nbundles_
         for (int m = 0; m < kBundleMax; ++m) { bd.member[m] = 0; bd.map[m] = 0; }
         for (int m = 0; m < bd.nmem; ++m) {
             const int u = mem[(size_t)m];
-            h_launch_rank[(size_t)u] = rank;
-            bd.member[m] = rank++;
+            bd.member[m] = h_launch_rank[(size_t)u];
             bd.map[m] = h_src[(size_t)(first + u)].period;
         }
     }
@@ -1307,19 +1092,19 @@ int Engine::plan_bundles(int first, int n, int G, int* nsolo_out, int* nbundles_
         size_t b_tot = 0, x_tot = 0, s_tot = 0;
         std::vector<size_t> b_off((size_t)nb), x_off((size_t)nb), s_off((size_t)nb);
         for (int k = 0; k < nb; ++k) {
-            const int GG = k < bundles_a ? G : bundle_Gb, lg = GG == 16 ? 4 : GG == 8 ? 3 : 2;
+            const int GG = k < bundles_a ? G : bundle_Gb;
             b_off[(size_t)k] = b_tot; x_off[(size_t)k] = x_tot; s_off[(size_t)k] = s_tot;
-            b_tot += (size_t)(GG * DSA_BSTRIDE + 1) * nrec_r; x_tot += (size_t)1 << (xlog_r0 + lg); s_tot += (size_t)GG * nrec_r;
+            b_tot += bundle_field_floats(GG, nrec_r, DSA_BSTRIDE); x_tot += (size_t)1 << (xlog_r0 + bundle_log2(GG)); s_tot += (size_t)GG * nrec_r;
             if (k + 1 == bundles_a) slowIr_off_b = s_tot;
         }
         if (ensure(Br_pool, b_tot) || ensure(exc_br, x_tot) || ensure(lists_br, (size_t)nb * lists_r_stride) || ensure(slowIr, s_tot) || ensure(bundles_r_d, (size_t)nb) ||
             ensure(ends_r, (size_t)n) || (want_cand && ensure(cand_br, (size_t)nb * cand_stride_r))) return status;
         h_bundles_r = h_bundles;
         for (int k = 0; k < nb; ++k) {
-            const int GG = k < bundles_a ? G : bundle_Gb, lg = GG == 16 ? 4 : GG == 8 ? 3 : 2;
+            const int GG = k < bundles_a ? G : bundle_Gb;
             FimBundle& bd = h_bundles_r[(size_t)k];
             bd.B = Br_pool.p + b_off[(size_t)k]; bd.b_stride = 0; bd.p_offset = (size_t)GG * DSA_BSTRIDE * nrec_r;
-            bd.exc = exc_br.p + x_off[(size_t)k]; bd.exc_stride = 0; bd.exc_log2cap = xlog_r0 + lg;
+            bd.exc = exc_br.p + x_off[(size_t)k]; bd.exc_stride = 0; bd.exc_log2cap = xlog_r0 + bundle_log2(GG);
             bd.lists = lists_br.p + (size_t)k * lists_r_stride; bd.lists_stride = 0;
             bd.slot_busy = nullptr; bd.nslots = 1; bd.slot = 0;
             bd.slowI = slowIr.p + s_off[(size_t)k]; bd.np = GG;
@@ -1385,12 +1170,11 @@ int Engine::run_exact(int first, int n, const std::vector<int>& xl, bool receive
             // exact_ties = 1 on a large grid: the bundles have converged and their field slots (164 GB at 4097^2) are what keeps the march
             // from holding its units side by side -- at 4097^2 the march's rate IS the number of units in flight.  They go back (the next
             // plan_bundles allocates them again) before the pool is sized.
-            auto release = [](auto& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; };
             HIP_TRY(this, hipStreamSynchronize(stream));
             if (stream2) HIP_TRY(this, hipStreamSynchronize(stream2));
             // (the candidate lists and the refined boxes' bundle buffers go with them -- GBs at 4097^2 --, and nothing may launch the
             // bundle descriptors that still point there: plan_bundles builds them again for the next chunk or call)
-            release(B_pool); release(exc_b); release(lists_b); release(cand_b); release(Br_pool); release(exc_br); release(lists_br); release(cand_br); release(slowIr);
+            B_pool.release(); exc_b.release(); lists_b.release(); cand_b.release(); Br_pool.release(); exc_br.release(); lists_br.release(); cand_br.release(); slowIr.release();
             bundles_a = bundles_b = 0; h_bundles.clear(); h_bundles_r.clear();
             released_bundles_for_march = true;
             HIP_TRY(this, hipMemGetInfo(&free_b, &total_b));
@@ -1462,8 +1246,7 @@ int Engine::run_exact(int first, int n, const std::vector<int>& xl, bool receive
         HIP_TRY(this, hipMemGetInfo(&free_b, &total_b));
         march_pool_kept = released_bundles_for_march ? false : free_b * 3 > total_b;
         if (!march_pool_kept) {
-            auto release = [](auto& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; };
-            release(X_pool); release(X_heap); release(X_tt); release(X_tp); release(X_ring); release(X_free); release(X_pins);
+            X_pool.release(); X_heap.release(); X_tt.release(); X_tp.release(); X_ring.release(); X_free.release(); X_pins.release();
         }
     }
     return 0;
