@@ -45,6 +45,9 @@ constexpr float kDefaultTieThreshold = 2.0e-5f;
 constexpr float kDefaultTieSumThreshold = 0.0f;
 constexpr int kDefaultTieCountThreshold = 0;
 constexpr int kDefaultTieFrozenBundles = 0;
+// the shortest lists dsa_set_option accepts for the list variant of the solve (k_fim: the refined boxes, kRefMax nodes per side): one layer of the
+// longest front a box holds -- its perimeter -- per list, half of it in the ready list (both colours)
+constexpr int kMinListCap = 4 * (kRefMax - 1), kMinReadyCap = 2 * (kRefMax - 1);
 constexpr int kDefaultTieMapStrict = 1;
 constexpr int kHandoffReplayCap = 256;       // units of a launch whose refined box the hand-off may march literally (the rest of such units are flagged: the whole unit marched)
 constexpr float kTieUlpsAt1025 = 26.0f;      // what a receiver time of the fixed point differs by from the reference's downstream of one-ulp ties, at most, in ulps, on grids up to 1025 nodes per side (measured: 26 = 9.92e-5 s at 32-64 s, the worst of the first 2.2 M fuzzed units; two units of the next 0.7 M reached 36 and 27: not a bound; Engine::tie_verdicts)
@@ -80,7 +83,7 @@ struct Engine {
     int chunk = 0;
     int max_chunk = 0;
     float window_cells = 1.25f;        // causal window of the coarse solve in cell travel times (measured optimum 1.0-1.5)
-    int list_cap = 0, ready_cap = 0;   // 0 = derive from the grid
+    int list_cap = 0, ready_cap = 0;   // 0 = derive from the grid; else at least kMinListCap / kMinReadyCap (dsa_set_option)
     int last_chunk_first = -1, last_chunk_n = 0;
     bool fields_resident = false;      // the last chunk's coarse fields are still in their slots (not so after a launch that recycled them)
 

@@ -1548,8 +1548,13 @@ int dsa_set_option(dsa_engine* e, const char* name, double value)
     const std::string n(name);
     if (n == "window_cells" && value > 0) { en->window_cells = (float)value; return 0; }
     if (n == "max_chunk" && value >= 0) { en->max_chunk = (int)value; return 0; }
-    if (n == "list_cap" && value >= 0) { en->planned = false; en->list_cap = (int)value; return 0; }
-    if (n == "ready_cap" && value >= 0) { en->planned = false; en->ready_cap = (int)value; return 0; }
+    // Lists of the list variant (k_fim, the refined boxes): 0 = from the grid.  Shorter ones than the front needs are legal -- entries that do not fit are
+    // dropped and a rescan of the field collects them -- but every rescan reopens the causal window, and below one layer of the box's longest front
+    // (its perimeter, kMinListCap nodes; half of it for the two colours of the ready list) the solve does not end within its round bound: measured on
+    // twelve boxes, 3-11 rescans at (512, 256), 300-650 and twenty times the time at (384, 192), "did not converge" at (256, 128)
+    // (tests/test_gpu_solve_shapes.py).  Such values are refused here instead of failing in the solve.
+    if (n == "list_cap" && (value == 0 || (value >= dsa::kMinListCap && value <= (1 << 24)))) { en->planned = false; en->list_cap = (int)value; return 0; }
+    if (n == "ready_cap" && (value == 0 || (value >= dsa::kMinReadyCap && value <= (1 << 24)))) { en->planned = false; en->ready_cap = (int)value; return 0; }
     if (n == "ray_budget" && value >= 0) { en->ray_budget = (size_t)value; return 0; }
     if (n == "fim_lds_pad" && value >= 0 && value <= 64 * 1024) { en->planned = false; en->fim_lds_pad = (int)value; return 0; }
     if (n == "fim_sorted" && (value == 0 || value == 1)) { en->planned = false; en->fim_sorted = (int)value; return 0; }   // (refined boxes only: the coarse solve exists in the ordered variant only)

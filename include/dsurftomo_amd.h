@@ -77,7 +77,7 @@ int dsa_set_memory_budget(dsa_engine* e, size_t bytes);
  *     fim_threads              [0]     workgroup size 128 | 256 | 512 | 1024; 0 = by grid size (128 up to 700 nodes per side, 256 up to 1500, 512 up to 3000, 1024 beyond)
  *     fim_sorted               [1]     refined boxes: 1 tile masks walked in record order | 0 lists in activation order (same fixed point)
  *     fim_lds_pad              [0]     extra dynamic LDS bytes per workgroup (limits the workgroups resident per CU; experiments)
- *     list_cap, ready_cap      [0]     active-list sizes of the list variant; 0 = from the grid
+ *     list_cap, ready_cap      [0]     active-list sizes of the list variant; 0 = from the grid, else at least 512 / 256
  *     field_pool               [0]     coarse field slots: 0 = four times the workgroups the GPU holds (a call with more units recycles them: a workgroup
  *                                      claims a free slot by compare-and-swap, resets it, solves, writes its unit's receiver times, frees it) | -1 one per
  *                                      unit | n > 0.  Fields stay readable (dsa_get_field) only when the call's units fit the slots; calls that need the

@@ -59,6 +59,11 @@ void untile(int nnx, int nnz, const Rec* F, float* T, float* tau)
         }
 }
 
+// evaluations of fixed_point (the refined and the coarse solve of hc_solve_source) that ended on an exact tie with an influence: what the
+// device's census counts per unit (dsa_unit_tie_sums), here under the worklist's schedule ([0]); what the device's hand-off probe counts or
+// flags (prepare) ([1]).  The caller resets them.
+long g_unit_ties[2] = { 0, 0 };
+
 long fixed_point(Field& f)
 {
     const size_t n = (size_t)f.nnx * f.nnz;
@@ -81,8 +86,9 @@ long fixed_point(Field& f)
         const Hood h = load_hood(f, iz, ix);
         const NodeGeom g = { f.ri, f.risti[ix - 1], f.dnx, f.dnz };
         Rec& r = f.F[ridx(f, iz, ix)];
-        float k;
-        const float c = solve_node(h, f.slow[ridx(f, iz, ix)], g, &k);
+        float k, tie;
+        const float c = solve_node_t<true>(h, f.slow[ridx(f, iz, ix)], g, &k, &tie);      // (same (T, tau) as solve_node: hc_solve_node_compare)
+        if (tie > 0.0f) ++g_unit_ties[0];
         ++evals;
         if (std::memcmp(&c, &r.T, 4) != 0 || std::memcmp(&k, &r.tau, 4) != 0) {
             r.T = c; r.tau = k;
@@ -168,6 +174,27 @@ int prepare(int nx, int ny, float goxd, float gozd, float dvxd, float dvzd, int 
             const size_t id = (size_t)(ix - 1) * s.rnz + (iz - 1);
             P.S_r[id] = (int8_t)handoff_node(g, s, w, ended, rstar, ez, ex, iz, ix, &P.Tfin[id]);
         }
+    // the hand-off's tie probe (stage_kernels.hip: k_handoff_probe): nodes whose acceptance rank ties with the terminating node's, and what the
+    // coarse grid receives (every kSgdl-th node: status, time) with such a node's answer inverted -- a difference, or more ties than the probe holds
+    if (!ended && ex > 0) {
+        std::vector<int> tied;
+        for (int ix = 1; ix <= s.rnx; ++ix)
+            for (int iz = 1; iz <= s.rnz; ++iz) {
+                const Rec r = P.F_r[rec_index(s.nbz_r, iz - 1, ix - 1)];
+                if (!(iz == ez && ix == ex) && !t_pinned(r.T) && t_value(r.T) < kInf && accept_rank(r.T, r.tau) == rstar) tied.push_back((ix - 1) * s.rnz + (iz - 1));
+            }
+        if (tied.size() > 8) ++g_unit_ties[1];
+        const int dxs[9] = { 0, -1, 1, 0, 0, -2, 2, 0, 0 }, dzs[9] = { 0, 0, 0, -1, 1, 0, 0, -2, 2 };
+        for (size_t k = 0; k < tied.size() && k < 8; ++k)
+            for (int q = 0; q < 9; ++q) {
+                const int zx = tied[k] / s.rnz + 1 + dxs[q], zz = tied[k] % s.rnz + 1 + dzs[q];
+                if (!(zx >= 1 && zx <= s.rnx && zz >= 1 && zz <= s.rnz && (zx - 1) % kSgdl == 0 && (zz - 1) % kSgdl == 0)) continue;
+                float t1;
+                const int st1 = handoff_node<true>(g, s, w, 0, rstar, ez, ex, zz, zx, &t1, tied[k]);
+                const size_t zid = (size_t)(zx - 1) * s.rnz + (zz - 1);
+                if (st1 != P.S_r[zid] || (st1 >= 0 && std::memcmp(&t1, &P.Tfin[zid], 4) != 0)) ++g_unit_ties[1];
+            }
+    }
     // injection + band promotion into the coarse window (records of the window only, like on the device)
     std::vector<Rec> W((size_t)s.cwnx * s.cwnz, Rec{ kInf, kInf });
     auto cs = [&](int iz, int ix) -> int16_t& { return P.cst[(size_t)(ix - 1 - s.cwx0) * s.cwnz + (iz - 1 - s.cwz0)]; };
@@ -374,7 +401,7 @@ int hc_depthkernel(int ncol, int nz, const float* vels, const float* depz, float
 // rule; the ready set is evaluated from the old states), used to study convergence on the CPU.
 // Interface arrays are row-major (nnz fastest); storage inside is tiled like on the device.
 // mode 0: all ready nodes at once; mode 1: two sub-passes by node parity (even first).
-extern "C" { int g_prune = 1; long g_regular_stats[8] = {}; long* hc_regular_stats() { return g_regular_stats; } }
+extern "C" { int g_prune = 1; long g_regular_stats[8] = {}; long* hc_regular_stats() { return g_regular_stats; } long* hc_unit_ties() { return g_unit_ties; } }
 extern "C" long hc_device_schedule(int nnx, int nnz, float* Tio, float* tauio, const float* slow_rm, const float* risti,
                                    float ri, float dnx, float dnz, float window, int mode, int max_rounds,
                                    long* out /* rounds, evals, last list size, freezes */, int* cyc_ids, int ncyc)
