@@ -365,6 +365,7 @@ int dsa_dropin_set_capacity(long long maxnar)
 
 // dsa_calsurfg, and (azimuthal) dsa_calsurfg_azimuthal: the same call whose rays keep the 2psi slabs and whose rows carry the gc and gs
 // blocks behind the isotropic entries, for the Rayleigh depth-kernel slots (engine.hip: solve_azimuthal)
+// (with null rw / iw / col its rows too stay on the device: dsa_solve_rows_azimuthal_device, for dsa_iteration_system_azimuthal_device)
 static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
                          int* iw, float* rw, int* col, float* dsurf,
                          const float* goxdf, const float* gozdf, const float* dvxdf, const float* dvzdf,
@@ -383,7 +384,6 @@ static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int
     int rc = engine();
     if (rc != 0) return rc;
     if (device_rows && g_pool.size() != 1) { g_dropin_error = "dsa_calsurfg: rows can only stay on the device with one engine (DSA_DEVICES unset)"; return DSA_ERR_STATE; }
-    if (azimuthal && device_rows) { g_dropin_error = "dsa_calsurfg_azimuthal: null argument (the azimuthal rows are host rows)"; return DSA_ERR_ARGUMENT; }
     if (azimuthal && g_pool.size() != 1) { g_dropin_error = "dsa_calsurfg_azimuthal: one engine only (DSA_DEVICES unset): the azimuthal call is not sharded over GPUs"; return DSA_ERR_STATE; }
     const Layout L = make_layout(*kmaxRc, *kmaxRg, *kmaxLc, *kmaxLg, *kmax, true);
     if (L.kRc + L.kRg + L.kLc + L.kLg != L.kmax) { g_dropin_error = "dsa_calsurfg: kmax must equal kmaxRc+kmaxRg+kmaxLc+kmaxLg"; return DSA_ERR_ARGUMENT; }
@@ -459,7 +459,8 @@ static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int
                 std::vector<int> on((size_t)L.kmax, 0);
                 for (int q = 0; q < L.sLc; ++q) on[(size_t)q] = 1;
                 if ((r = dsa_set_azimuthal_slots(e, L.kmax, on.data())) != 0) return bad(r);
-                r = dsa_solve_rows_azimuthal(e, dsurf, rw, iw + 1, col, cap, &P.n);
+                r = device_rows ? dsa_solve_rows_azimuthal_device(e, dsurf, nullptr, nullptr, nullptr, cap, &P.n)
+                                : dsa_solve_rows_azimuthal(e, dsurf, rw, iw + 1, col, cap, &P.n);
             } else
             r = dsa_solve_rows(e, dsurf, rw, device_rows ? nullptr : iw + 1, col, cap, &P.n);          // the reference fills iw(nar+1)
         } else {
@@ -529,7 +530,7 @@ static int calsurfg_call(bool azimuthal, const int* nx, const int* ny, const int
     g_rbint_notes = first_clamped >= 0 ? U.niter - U.iter[(size_t)first_clamped] : 0;
     if (n > INT_MAX) { g_dropin_error = "dsa_calsurfg: more than 2^31-1 matrix entries"; return DSA_ERR_ARGUMENT; }
     *nar = (int)n;
-    if (azimuthal) iw[0] = (int)n;
+    if (azimuthal && iw) iw[0] = (int)n;
     remember(L, *nx * *ny, true);
     return 0;
 }

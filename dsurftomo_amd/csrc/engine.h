@@ -243,7 +243,8 @@ struct Engine {
     bool have_azi = false;             // the last azimuthal solve of this plan succeeded: the sums below are its rays'
     std::vector<float> h_azi_sums;     // per traced ray of the plan (position in h_trace, like the path store): sum of cos 2psi, of sin 2psi over its steps
     std::vector<int> h_azi_steps;      // ... and its steps
-    int solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar);
+    // device_rows: the rows stay behind G_rw / G_row / G_col whatever the option rows_on_device says (dsa_solve_rows_azimuthal_device)
+    int solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar, bool device_rows = false);
 
     // dispersion stage (disp_kernels.hip): Vs model -> pv maps + depth kernels, all resident
     bool disp_ready = false;
@@ -296,6 +297,11 @@ struct Engine {
     OwnedBuf<float> G_rw;
     OwnedBuf<int> G_row, G_col;        // 1-based datum (row) and model parameter (column)
     long long G_nar = 0;
+    // what the G_nar resident entries are: set by the launch that writes them, cleared wherever G_nar is reset.  The isotropic builder
+    // (dsa_iteration_system_device) refuses azimuthal rows, the joint one (dsa_iteration_system_azimuthal_device) takes nothing else and
+    // leaves kRowsJoint (its system, Laplacian rows included: not rows to build from again).
+    enum RowsKind { kRowsNone, kRowsIsotropic, kRowsAzimuthal, kRowsJoint };
+    RowsKind G_kind = kRowsNone;
     template <class T> int ensure_keep(DevBuf<T>& b, size_t n, size_t used);
 
     bool spmv_attr_set = false;        // LDS attribute of the blocked SpmV kernels set on this engine's device

@@ -732,7 +732,7 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
     rays_clamped = 0; first_clamped_unit = -1;
     if (rows) {
         *nar = 0;
-        G_nar = 0;
+        G_nar = 0; G_kind = kRowsNone;
         for (const SourceDesc& s : h_src)
             if (s.sen_slot < 0 || s.sen_slot >= sens_kmax) { fail(DSA_ERR_ARGUMENT, "solve: a unit uses depth-kernel slot %d of %d", s.sen_slot, sens_kmax); return DSA_ERR_ARGUMENT; }
     }
@@ -1373,7 +1373,7 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
                 HIP_TRY(this, hipMemcpyAsync(iw + *nar, a.iw, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
                 HIP_TRY(this, hipMemcpyAsync(col + *nar, a.col, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
             }
-            G_nar = *nar + total;
+            G_nar = *nar + total; G_kind = azi_now ? kRowsAzimuthal : kRowsIsotropic;
         } else if (total > 0) {
             if (ensure(coo_rw, (size_t)total) || ensure(coo_iw, (size_t)total) || ensure(coo_col, (size_t)total)) return status;
             a.rw = coo_rw.p; a.iw = coo_iw.p; a.col = coo_col.p;
@@ -1411,10 +1411,10 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
 
 // dsa_solve_rows_azimuthal: solve() with three slabs per ray and the gc / gs blocks behind every ray's isotropic entries (ray_kernels.hip:
 // k_rays<., true>, k_row_emit_azi).  The depth factor Sazi is built here, the first time it is needed for the current depth kernels.
-int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar)
+int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar, bool device_rows)
 {
     have_azi = false;
-    if (rows_on_device) { fail(DSA_ERR_STATE, "solve_rows_azimuthal: host rows only (option rows_on_device is set)"); return DSA_ERR_STATE; }
+    if (rows_on_device && !device_rows) { fail(DSA_ERR_STATE, "solve_rows_azimuthal: host rows only (option rows_on_device is set)"); return DSA_ERR_STATE; }
     if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_azimuthal: one engine only"); return DSA_ERR_STATE; }
     if (!planned) { fail(DSA_ERR_STATE, "solve: call dsa_plan first"); return DSA_ERR_STATE; }
     if (!have_sens) { fail(DSA_ERR_STATE, "solve: Frechet rows need the depth kernels (dsa_set_depth_kernels / dsa_depthkernel) first"); return DSA_ERR_STATE; }
@@ -1437,7 +1437,10 @@ int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long lon
     h_azi_sums.assign(2 * h_trace.size(), 0.0f);
     h_azi_steps.assign(h_trace.size(), 0);
     azi_now = true;
+    const bool option = rows_on_device;       // (the device entry runs solve() as under the option and leaves the option as it found it)
+    if (device_rows) rows_on_device = true;
     const int rc = solve(dsurf, rw, iw, col, cap, nar);
+    rows_on_device = option;
     azi_now = false;
     have_azi = rc == 0;
     return rc;
@@ -1737,6 +1740,15 @@ int dsa_solve_rows_azimuthal(dsa_engine* e, float* dsurf, float* rw, int* iw, in
 {
     if (!e || !nar || !rw || !iw || !col) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->solve_azimuthal(dsurf, rw, iw, col, capacity, nar);
+}
+
+int dsa_solve_rows_azimuthal_device(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar)
+{
+    if (!e || !nar) return DSA_ERR_ARGUMENT;
+    Engine* en = reinterpret_cast<Engine*>(e);
+    const int given = (rw != nullptr) + (iw != nullptr) + (col != nullptr);
+    if (given != 0 && given != 3) { en->fail(DSA_ERR_ARGUMENT, "solve_rows_azimuthal_device: rw / iw / col are all given or all NULL"); return DSA_ERR_ARGUMENT; }
+    return en->solve_azimuthal(dsurf, rw, iw, col, capacity, nar, true);
 }
 
 int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on)

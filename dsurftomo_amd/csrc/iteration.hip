@@ -1,7 +1,7 @@
 // Host side of one outer iteration around the device calls: what the reference's main program
 // does between CalSurfG and LSMR (main.f90:361-466) and after LSMR (main.f90:520-535).  Plain host code with the
 // reference's fp32 arithmetic, so that an iteration driven through this library (dsurftomo_amd/invert.py) produces the
-// reference's numbers; O(nar) work, no device involved.
+// reference's numbers; O(nar) work, no device involved.  The two *_device builders do the same step where the rows are.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +10,7 @@
 
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
+#include "joint_system.h"
 #include "spmv_state.h"
 
 namespace {
@@ -83,6 +84,30 @@ __global__ void k_scale_rows(long long nar, float* __restrict__ rw, const int* _
     rw[k] = rw[k] * w[row[k] - 1];
 }
 
+// The Laplacian rows of the joint system's three blocks (joint_system.h), written where the data rows are: thread t = (block B, unknown
+// `index`) writes its 1 or 7 entries at first + B * per_block + joint_first_entry(index) -- row dall + B maxvp + index + 1, column
+// B maxvp + the block's column, value (float)c * w in one rounded product, w = weight0 on block 0 and weight_azi on blocks 1 and 2.
+__global__ __launch_bounds__(256) void k_laplacian_blocks(int nvx, int nvz, int nl, int dall, long long first, long long per_block, float weight0,
+                                                          float weight_azi, float* __restrict__ rw, int* __restrict__ row, int* __restrict__ col)
+{
+    const long long maxvp = (long long)nvx * nvz * nl;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 3 * maxvp) return;
+    const int B = (int)(t / maxvp);
+    const long long index = t - B * maxvp;
+    const float w = B == 0 ? weight0 : weight_azi;
+    const long long at = first + B * per_block + dsa::joint_first_entry(nvx, nvz, nl, index);
+    const int count = dsa::joint_row_entries(nvx, nvz, nl, index);
+    for (int q = 0; q < count; ++q) {
+        long long c1;
+        int coef;
+        dsa::joint_entry(nvx, nvz, nl, index, q, &c1, &coef);
+        rw[at + q] = (float)coef * w;
+        row[at + q] = (int)(dall + t + 1);
+        col[at + q] = (int)(B * maxvp + c1);
+    }
+}
+
 }  // namespace
 
 namespace dsa {
@@ -139,6 +164,7 @@ int dsa_iteration_system_device(dsa_engine* h, int nx, int ny, int nz, int dall,
     dsa::Engine* e = reinterpret_cast<dsa::Engine*>(h);
     if (nx < 3 || ny < 3 || nz < 2 || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_device: bad arguments"); return DSA_ERR_ARGUMENT; }
     if (!e->rows_on_device || (e->G_nar > 0 && !e->G_rw.p)) { e->fail(DSA_ERR_STATE, "iteration_system_device: no rows on the device (option rows_on_device + dsa_solve_rows, or dsa_calsurfg with null arrays)"); return DSA_ERR_STATE; }
+    if (e->G_kind == dsa::Engine::kRowsAzimuthal || e->G_kind == dsa::Engine::kRowsJoint) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are azimuthal rows (three blocks of columns): dsa_iteration_system_azimuthal_device builds their system"); return DSA_ERR_STATE; }
     const int nvx = nx - 2, nvz = ny - 2, nl = nz - 1;
     const long long maxvp = (long long)nvx * nvz * nl, nar_in = e->G_nar;
     { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_device: too few data"); return rc; } }
@@ -175,6 +201,71 @@ int dsa_iteration_system_device(dsa_engine* h, int nx, int ny, int nz, int dall,
     for (long long i = 0; i < maxvp; ++i) { total = total + norm[i]; if (norm[i] > top) top = norm[i]; }
     dws[0] = top; dws[1] = total / (float)maxvp;
     e->G_nar = nar;
+    *m_out = m;
+    *nar_out = nar;
+    return done(0);
+}
+
+// The joint Vs | gc | gs system of the azimuthal step built where dsa_solve_rows_azimuthal_device, or
+// dsa_calsurfg_azimuthal called with null rw / iw / col, left its rows: the data rows scaled by the 0/1 weights (residual_weights,
+// k_scale_rows: dsa_iteration_system_device's), and below the dall data rows the Laplacian rows of the three blocks, written by
+// k_laplacian_blocks -- block B's rows dall + B maxvp + index, columns B maxvp + ..., weight0 on Vs and weight_azi on gc and gs.
+// m = dall + 3 maxvp, n = 3 maxvp.  Same bits as analyses/azimuthal.py's azimuthal_weights + azimuthal_system + dsa_spmv_load on the
+// host rows of the same call; norm[3 maxvp] adds |entry| over a column's data entries in storage order, dws[2 B], dws[2 B + 1] are
+// block B's {max, mean} of it (main.f90:386-392).  Every argument is checked before the device is touched.
+int dsa_iteration_system_azimuthal_device(dsa_engine* h, int nx, int ny, int nz, int dall, const float* obst, const float* dsyn, float threshold0,
+                                          float weight0, float weight_azi, float* cbst, float* datweight, float* norm, int* m_out, long long* nar_out,
+                                          float* dws)
+{
+    if (!h) return DSA_ERR_ARGUMENT;
+    dsa::Engine* e = reinterpret_cast<dsa::Engine*>(h);
+    if (nx < 3 || ny < 3 || nz < 2 || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_azimuthal_device: bad arguments"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(weight0) || weight0 < 0.0f || !std::isfinite(weight_azi) || weight_azi < 0.0f) {
+        e->fail(DSA_ERR_ARGUMENT, "iteration_system_azimuthal_device: weight0 %g and weight_azi %g must be finite and >= 0", (double)weight0, (double)weight_azi);
+        return DSA_ERR_ARGUMENT;
+    }
+    const int nvx = nx - 2, nvz = ny - 2, nl = nz - 1;
+    const long long maxvp = (long long)nvx * nvz * nl;
+    if (3 * maxvp + dall > 0x7fffffffll) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_azimuthal_device: %lld rows do not fit an int", 3 * maxvp + dall); return DSA_ERR_ARGUMENT; }
+    if (e->G_kind != dsa::Engine::kRowsAzimuthal || e->G_nar < 1 || !e->G_rw.p) {
+        e->fail(DSA_ERR_STATE, "iteration_system_azimuthal_device: %s (dsa_solve_rows_azimuthal_device, or dsa_calsurfg_azimuthal with null arrays, first)",
+                e->G_kind == dsa::Engine::kRowsIsotropic ? "the rows on the device are isotropic rows" :
+                e->G_kind == dsa::Engine::kRowsJoint ? "the rows on the device are a joint system already" : "no azimuthal rows on the device");
+        return DSA_ERR_STATE;
+    }
+    const long long nar_in = e->G_nar, per_block = dsa::joint_block_entries(nvx, nvz, nl), nar = nar_in + 3 * per_block;
+    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_azimuthal_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_azimuthal_device: too few data"); return rc; } }
+    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
+    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
+    for (long long i = 0; i < 3 * maxvp; ++i) cbst[dall + i] = 0.0f;
+    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_azimuthal_device: hipSetDevice"); return DSA_ERR_DEVICE; }
+    dsa::DevBuf<float> d_w, d_norm;
+    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
+#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_azimuthal_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
+    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)(3 * maxvp)) ||
+        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
+    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
+    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)(3 * maxvp) * 4, e->stream));
+    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
+    hipLaunchKernelGGL(k_laplacian_blocks, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, nar_in, per_block, weight0,
+                       weight_azi, e->G_rw.p, e->G_row.p, e->G_col.p);
+    IT_TRY(hipGetLastError());
+    IT_TRY(hipStreamSynchronize(e->stream));
+    const int m = dall + (int)(3 * maxvp);
+    { const int rc = dsa::spmv_load_from_device(e, m, (int)(3 * maxvp), nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
+    dsa::spmv_abs_column_sums(e, d_norm.p);
+    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)(3 * maxvp) * 4, hipMemcpyDeviceToHost, e->stream));
+    IT_TRY(hipStreamSynchronize(e->stream));
+    IT_TRY(hipGetLastError());
+#undef IT_TRY
+    for (int B = 0; B < 3; ++B) {                                                              // :386-392, block by block
+        const float* nb = norm + (size_t)B * (size_t)maxvp;
+        float total = 0.0f, top = 0.0f;
+        for (long long i = 0; i < maxvp; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
+        dws[2 * B] = top; dws[2 * B + 1] = total / (float)maxvp;
+    }
+    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsJoint;
     *m_out = m;
     *nar_out = nar;
     return done(0);

@@ -21,13 +21,15 @@
 // The scalar recurrences are dsa::LsmrScalars (lsmr_core.h), the same code dsa_lsmr runs, one per realisation.  A realisation that
 // stops is frozen: no kernel writes its lanes again.  Three host synchronisations per iteration (beta, alpha, normx: nreal values each).
 //
-// Five entry points run that loop.  Each is: the front door (Entry: the argument checks they share), the layout of its pieces of btmp
+// Six entry points run that loop.  Each is: the front door (Entry: the argument checks they share), the layout of its pieces of btmp
 // (Carve), batch_begin, u and the row scales by k_b_fill under its rule (Fill), batch_solve, then its own measures.  bx keeps the
 // solutions for a later call (dsa_forward_steps, SpmvState::bx_valid).
 //   * dsa_lsmr_batch: the bootstrap above (FILL_ROWS).
 //   * dsa_lsmr_resolution: the right-hand sides of test models, formed on the device: v = unit spikes made in place or host
 //     models, row scales 1 and u = 0 (FILL_ONE without b), u = A v by k_b_spmv<true> (fl(a * 1) = a: the chain of dsa_spmv mode 1 from
 //     y = 0), then the regularisation rows zeroed.  For spikes, k_b_psf_part / k_b_psf_sum reduce each solution to its PSF measures.
+//   * dsa_resolution_blocks (§19): the same spike solves (resolution_solve), the measures taken per parameter block of the unknowns
+//     (k_b_psf_blocks_part / k_b_psf_blocks_sum): the joint Vs | gc | gs system of the azimuthal step.
 //   * dsa_lsmr_tradeoff (§13): K (weight, damp) pairs.  The products read a coefficient copy of the contiguous values whose regularisation
 //     entries hold their integer coefficient c (the resident entry is fl(c * weight0)); with row scales 1 on the data rows and weight_k
 //     from ndata up (FILL_WEIGHT) member k multiplies by fl(a * 1) = a and fl(c * weight_k): the system dsa_iteration_system builds with
@@ -523,6 +525,53 @@ __global__ __launch_bounds__(64) void k_b_psf_sum(int n, int nb, int nreal, int 
     for (int c = 0; c < 3; ++c) psf[4 * (size_t)r + 1 + c] = s[c];
 }
 
+// The same measures per parameter block (dsa_resolution_blocks): the n unknowns are nblocks blocks of nbc cells on one grid of cells,
+// coords and cosl per cell.  Spike r sits at unknown j = first + r, cell cj = j mod nbc; for every block B the three sums run over the
+// unknowns B nbc + e of x_r with dh, dz measured from cell cj to cell e.  k_b_psf_blocks_part: block (B nch + c, g), chunk c of block B =
+// its cells [c kPsfE, + kPsfE), wavefront w the cells [c kPsfE + w kPsfE/4, + kPsfE/4) in order, the loop body k_b_psf_part's term for
+// term; the four wavefronts' sums added in order (block_sum4).  k_b_psf_blocks_sum: block (g, B), the chunks' partials in order.  With
+// nblocks = 1 this is k_b_psf_part / k_b_psf_sum's partition and arithmetic: the same bits.
+__global__ __launch_bounds__(256) void k_b_psf_blocks_part(int n, int nbc, int nch, int first, const double* __restrict__ coords,
+                                                           const double* __restrict__ cosl, const float* __restrict__ x, double* __restrict__ part)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = blockIdx.y, B = blockIdx.x / nch, c = blockIdx.x % nch;
+    const long long jj = (long long)first + g * 64 + lane;
+    const int j = jj < n ? (int)jj : n - 1;                           // (padding lanes: any unknown, never read back)
+    const int cj = j % nbc;
+    const double lat_j = coords[3 * (size_t)cj], lon_j = coords[3 * (size_t)cj + 1], dep_j = coords[3 * (size_t)cj + 2], cos_j = cosl[cj];
+    const float* __restrict__ p = x + ((size_t)g * n + (size_t)B * nbc) * 64 + lane;
+    const int e0 = c * kPsfE + w * (kPsfE / 4), e1 = min(e0 + kPsfE / 4, nbc);
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int e = e0; e < e1; ++e) {
+        const double xv = (double)p[(size_t)e * 64];
+        if (xv == 0.0) continue;                                          // (its terms are +0)
+        const double q = xv * xv;
+        const double dh = psf_dh(coords[3 * (size_t)e], coords[3 * (size_t)e + 1], cosl[e], lat_j, lon_j, cos_j);
+        const double dz = coords[3 * (size_t)e + 2] - dep_j;
+        s[0] = s[0] + q;
+        s[1] = s[1] + q * (dh * dh);
+        s[2] = s[2] + q * (dz * dz);
+    }
+    block_sum4(s, part + (((size_t)g * gridDim.x + blockIdx.x) * 64 + lane) * 3);
+}
+
+// psf[(r nblocks + B) 4 .. + 3] = {x_r[B nbc + cj], block B's three sums}; one thread per (realisation, block)
+__global__ __launch_bounds__(64) void k_b_psf_blocks_sum(int n, int nbc, int nch, int nreal, int first, const float* __restrict__ x,
+                                                         const double* __restrict__ part, double* __restrict__ psf)
+{
+    const int lane = threadIdx.x, g = blockIdx.x, B = blockIdx.y, nblocks = gridDim.y, r = g * 64 + lane;
+    if (r >= nreal) return;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < nch; ++c) {
+        const double* __restrict__ q = part + (((size_t)g * nblocks * nch + (size_t)B * nch + c) * 64 + lane) * 3;
+        for (int k = 0; k < 3; ++k) s[k] = s[k] + q[k];
+    }
+    const int cj = (first + r) % nbc;
+    double* __restrict__ o = psf + ((size_t)r * nblocks + B) * 4;
+    o[0] = (double)x[((size_t)g * n + (size_t)B * nbc + cj) * 64 + lane];
+    for (int k = 0; k < 3; ++k) o[1 + k] = s[k];
+}
+
 // ---- dsa_lsmr_tradeoff, dsa_lsmr_crossval: the coefficient copy of the contiguous values ----
 
 // c of a regularisation entry a = fl(c * w0): rint(a / w0); `bad` unless c is a non-zero integer of at most 64 whose product gives a's bits back
@@ -796,7 +845,7 @@ __global__ void k_v_stats(int n, int nreal, const float* __restrict__ xf, double
 
 constexpr int kMaxReal = 64 * 65535;        // members of one call (gridDim.y lane groups)
 
-// The checks the five entry points share, in the order they fire, their texts carrying the entry point's name.  Each returns 0 or the
+// The checks the entry points share, in the order they fire, their texts carrying the entry point's name.  Each returns 0 or the
 // error it has reported.
 struct Entry {
     const char* name;
@@ -843,7 +892,7 @@ struct Carve {
     V* at(const DevBuf<T>& buf, size_t off) const { static_assert(sizeof(V) == sizeof(T), "pieces are counted in units of T"); return reinterpret_cast<V*>(buf.p + off); }
 };
 
-// ---- the batch of all five entry points: set-up (batch_begin), then -- once the caller has filled u and the row scales -- the LSMR loop
+// ---- the batch of all entry points: set-up (batch_begin), then -- once the caller has filled u and the row scales -- the LSMR loop
 // (batch_solve) and, for two of them, the measures (batch_measures) ----
 struct Batch {
     Engine* e = nullptr;
@@ -1173,6 +1222,48 @@ int weighted_solve(Entry& in, int nreal, int per, int ndata, const float* b, flo
     return batch_measures(B, nreal, ndata, d_b, KeepAll{}, measures, nullptr, 0);
 }
 
+// the spikes spike_first .. spike_first + nreal - 1 lie in [0, n)
+int spike_range(Entry& in, int spike_first, int nreal)
+{
+    if (spike_first >= 0 && (long long)spike_first + nreal <= in.n) return 0;
+    in.e->fail(DSA_ERR_ARGUMENT, "%s: spikes %d..%lld outside the %d unknowns", in.name, spike_first, (long long)spike_first + nreal - 1, in.n);
+    return DSA_ERR_ARGUMENT;
+}
+
+// The solves dsa_lsmr_resolution and dsa_resolution_blocks share, from the layout of btmp to batch_solve: v = the test models (host
+// models scattered, or unit spikes made in place), row scales 1 and u = 0, u = A v over every row (k_b_spmv: fl(a * 1) = a, the chain of
+// dsa_spmv mode 1 from y = 0), rows [ndata, m) = +0, then the LSMR loop.  B is left for the caller's measures.
+int resolution_solve(Entry& in, Batch& B, int nreal, int ndata, const float* models, int spike_first, float damp, float atol, float btol, float conlim,
+                     int itnlim, int localSize, float* x, int* istop, int* itn, float* est)
+{
+    Engine* e = in.e;
+    const int m = in.m, n = in.n;
+    // btmp: the host models (realisation-major), dead once they are scattered; the solutions on their way out lie over them
+    Carve<float> T;
+    const size_t o_mod = T.take(models ? (size_t)nreal * n : 0);
+    T.reuse();
+    const size_t o_x = T.take(x ? (size_t)nreal * n : 0);
+    LB_DO(batch_begin(e, nreal, localSize, T.total, B));
+    SpmvState& S = *e->spmv;
+    const int G = B.G, Rp = B.Rp;
+    hipStream_t st = B.st;
+    B.xout = T.at(S.btmp, o_x);
+    if (models) {
+        float* d_mod = T.at(S.btmp, o_mod);
+        LB_TRY(e, hipMemcpyAsync(d_mod, models, (size_t)nreal * n * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_b_scatter<float>, grid_of(n, G), dim3(256), 0, st, n, nreal, (const float*)d_mod, S.bv.p);
+    } else
+        hipLaunchKernelGGL(k_b_spike, grid_of(n, G), dim3(256), 0, st, n, nreal, spike_first, S.bv.p);
+    B.fill(FILL_ONE, nreal, nullptr);
+    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 1;
+    LB_DO(B.upload());
+    B.product(1, nullptr, B.flag(F_ACT));
+    if (ndata < m) hipLaunchKernelGGL(k_b_zero_rows, grid_of(m - ndata, G), dim3(256), 0, st, m, ndata, S.bu.p);
+    LB_TRY(e, hipStreamSynchronize(st));                      // (the upload has landed before the host mirror changes)
+    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 0;
+    return batch_solve(B, nreal, &damp, nreal, atol, btol, conlim, itnlim, x, istop, itn, est);
+}
+
 }  // namespace
 
 }  // namespace dsa
@@ -1212,39 +1303,14 @@ int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* model
     LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && istop && itn && est, "nreal < 1 or a null istop / itn / est"));
     LB_DO(in.matrix(&ndata));
     Engine* e = in.e;
-    const int m = in.m, n = in.n;
-    if (!models && (spike_first < 0 || (long long)spike_first + nreal > n)) {
-        e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: spikes %d..%lld outside the %d unknowns", spike_first, (long long)spike_first + nreal - 1, n);
-        return DSA_ERR_ARGUMENT;
-    }
+    const int n = in.n;
+    if (!models) LB_DO(spike_range(in, spike_first, nreal));
     if (psf && (models || !coords)) { e->fail(DSA_ERR_ARGUMENT, "lsmr_resolution: psf needs spikes (models NULL) and coords"); return DSA_ERR_ARGUMENT; }
-    // btmp: the host models (realisation-major), dead once they are scattered; the solutions on their way out lie over them
-    Carve<float> T;
-    const size_t o_mod = T.take(models ? (size_t)nreal * n : 0);
-    T.reuse();
-    const size_t o_x = T.take(x ? (size_t)nreal * n : 0);
     Batch B;
-    LB_DO(batch_begin(e, nreal, localSize, T.total, B));
+    LB_DO(resolution_solve(in, B, nreal, ndata, models, spike_first, damp, atol, btol, conlim, itnlim, localSize, x, istop, itn, est));
     SpmvState& S = *e->spmv;
     const int G = B.G, Rp = B.Rp;
     hipStream_t st = B.st;
-    B.xout = T.at(S.btmp, o_x);
-    // v = the test models, row scales 1, u = 0; u = A v over every row (k_b_spmv: fl(a * 1) = a, the chain of dsa_spmv mode 1 from y = 0),
-    // then rows [ndata, m) = +0
-    if (models) {
-        float* d_mod = T.at(S.btmp, o_mod);
-        LB_TRY(e, hipMemcpyAsync(d_mod, models, (size_t)nreal * n * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_b_scatter<float>, grid_of(n, G), dim3(256), 0, st, n, nreal, (const float*)d_mod, S.bv.p);
-    } else
-        hipLaunchKernelGGL(k_b_spike, grid_of(n, G), dim3(256), 0, st, n, nreal, spike_first, S.bv.p);
-    B.fill(FILL_ONE, nreal, nullptr);
-    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 1;
-    LB_DO(B.upload());
-    B.product(1, nullptr, B.flag(F_ACT));
-    if (ndata < m) hipLaunchKernelGGL(k_b_zero_rows, grid_of(m - ndata, G), dim3(256), 0, st, m, ndata, S.bu.p);
-    LB_TRY(e, hipStreamSynchronize(st));                      // (the upload has landed before the host mirror changes)
-    for (int r = 0; r < nreal; ++r) B.hf[F_ACT * Rp + r] = 0;
-    LB_DO(batch_solve(B, nreal, &damp, nreal, atol, btol, conlim, itnlim, x, istop, itn, est));
     if (!psf) return 0;
     // bpsf: the blocks' partials, then the results
     const int nb = (n + kPsfE - 1) / kPsfE;
@@ -1258,6 +1324,37 @@ int dsa_lsmr_resolution(dsa_engine* h_, int nreal, int ndata, const float* model
                        (const float*)S.bx.p, d_part);
     hipLaunchKernelGGL(k_b_psf_sum, dim3((unsigned)G), dim3(64), 0, st, n, nb, nreal, spike_first, (const float*)S.bx.p, (const double*)d_part, d_psf);
     LB_TRY(e, hipMemcpyAsync(psf, d_psf, 4 * (size_t)nreal * 8, hipMemcpyDeviceToHost, st));
+    return drain(e, st);
+}
+
+int dsa_resolution_blocks(dsa_engine* h_, int nreal, int ndata, int nblocks, int spike_first, const double* coords, float damp, float atol, float btol,
+                               float conlim, int itnlim, int localSize, float* x, double* psf, int* istop, int* itn, float* est)
+{
+    using namespace dsa;
+    Entry in{"resolution_blocks"};
+    LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && coords && psf && istop && itn && est, "nreal < 1 or a null coords / psf / istop / itn / est"));
+    LB_DO(in.matrix(&ndata));
+    Engine* e = in.e;
+    const int n = in.n;
+    if (nblocks < 1 || n % nblocks != 0) { e->fail(DSA_ERR_ARGUMENT, "resolution_blocks: the %d unknowns are not %d blocks of equal size", n, nblocks); return DSA_ERR_ARGUMENT; }
+    LB_DO(spike_range(in, spike_first, nreal));
+    Batch B;
+    LB_DO(resolution_solve(in, B, nreal, ndata, nullptr, spike_first, damp, atol, btol, conlim, itnlim, localSize, x, istop, itn, est));
+    SpmvState& S = *e->spmv;
+    const int G = B.G, nbc = n / nblocks, nch = (nbc + kPsfE - 1) / kPsfE;
+    hipStream_t st = B.st;
+    // bpsf: the chunks' partials, then the results
+    Carve<double> P;
+    const size_t o_part = P.take((size_t)G * nblocks * nch * 64 * 3), o_psf = P.take(4 * (size_t)nblocks * B.Rp);
+    if (e->ensure(S.bcoord, 4 * (size_t)nbc) || e->ensure(S.bpsf, P.total)) return e->status;
+    double *d_part = P.at(S.bpsf, o_part), *d_psf = P.at(S.bpsf, o_psf), *d_cos = S.bcoord.p + 3 * (size_t)nbc;
+    LB_TRY(e, hipMemcpyAsync(S.bcoord.p, coords, 3 * (size_t)nbc * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_psf_cos, dim3((unsigned)std::min(1024, (nbc + 255) / 256)), dim3(256), 0, st, nbc, (const double*)S.bcoord.p, d_cos);
+    hipLaunchKernelGGL(k_b_psf_blocks_part, dim3((unsigned)(nblocks * nch), (unsigned)G), dim3(256), 0, st, n, nbc, nch, spike_first, (const double*)S.bcoord.p,
+                       (const double*)d_cos, (const float*)S.bx.p, d_part);
+    hipLaunchKernelGGL(k_b_psf_blocks_sum, dim3((unsigned)G, (unsigned)nblocks), dim3(64), 0, st, n, nbc, nch, nreal, spike_first, (const float*)S.bx.p,
+                       (const double*)d_part, d_psf);
+    LB_TRY(e, hipMemcpyAsync(psf, d_psf, 4 * (size_t)nreal * nblocks * 8, hipMemcpyDeviceToHost, st));
     return drain(e, st);
 }
 

@@ -95,11 +95,14 @@ def declare_solvers(L):
     L.dsa_calsurfg_azimuthal.argtypes = [_vp] * 36            # dsa_calsurfg's list: every argument by reference
     L.dsa_iteration_system.argtypes = [_i32] * 4 + [C.c_longlong] * 2 + [_vp] * 5 + [_f32] * 2 + [_vp] * 6
     L.dsa_iteration_system_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 2 + [_vp] * 6
+    L.dsa_solve_rows_azimuthal_device.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dsa_iteration_system_azimuthal_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 3 + [_vp] * 6
     L.dsa_model_update.argtypes = [_i32] * 3 + [_vp] * 2 + [_f32] * 2
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
     L.dsa_lsmr_resolution.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp, _f32] + solve + [_vp] * 5
+    L.dsa_resolution_blocks.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _f32] + solve + [_vp] * 5
     L.dsa_lsmr_tradeoff.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp, _vp] + solve + [_vp] * 5
     L.dsa_lsmr_crossval.argtypes = [_vp] + [_i32] * 3 + [_vp, _f32] + [_vp] * 3 + solve + [_vp] * 6
     L.dsa_lsmr_voronoi.argtypes = [_vp] + [_i32] * 3 + [_vp] * 3 + [_f32] + solve + [_vp] * 6
@@ -245,6 +248,23 @@ class Engine:
         nar = C.c_longlong(0)
         self._check(self._L.dsa_solve_rows_azimuthal(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
                                                      capacity, C.byref(nar)))
+        n = nar.value
+        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+
+    def solve_rows_azimuthal_device(self, capacity, host_copy=True):
+        """solve_rows_azimuthal with the rows left on the device (dsa_solve_rows_azimuthal_device), whatever the option rows_on_device says.
+        host_copy: returns (times, rw, row, col), the copy bit for bit solve_rows_azimuthal's; else (times, number of entries) and no row
+        leaves the device"""
+        out = np.zeros(self._ndata, np.float32)
+        nar = C.c_longlong(0)
+        if not host_copy:
+            self._check(self._L.dsa_solve_rows_azimuthal_device(self._h, _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
+            return out, nar.value
+        rw = np.zeros(capacity, np.float32)
+        iw = np.zeros(capacity, np.int32)
+        col = np.zeros(capacity, np.int32)
+        self._check(self._L.dsa_solve_rows_azimuthal_device(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
+                                                            C.c_longlong(capacity), C.byref(nar)))
         n = nar.value
         return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
 
@@ -407,6 +427,18 @@ class Engine:
         x = np.zeros((R, n), np.float32) if want_x else None
         psf = np.zeros((R, 4)) if xyz is not None else None
         return self._batch(self._L.dsa_lsmr_resolution, R, (R, int(ndata), mod, first, xyz, damp), (atol, btol, conlim, itnlim, local_size), x=x, psf=psf)
+
+    def lsmr_resolution_blocks(self, ndata, damp, nblocks, spikes, coords, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
+        """lsmr_resolution's spike solves with the PSF measures per parameter block (dsa_resolution_blocks): the n unknowns are nblocks
+        blocks of n / nblocks cells, coords ((n / nblocks, 3) latitude, longitude, depth) per cell, spikes = (first, R).  Returns
+        dict(x=(R, n) or None when not want_x, psf=(R, nblocks, 4) {x_r at the spike's cell in block B, sum x^2, sum x^2 dh^2, sum x^2 dz^2
+        over block B}, istop=(R,), itn=(R,), normA=(R,), condA, normr, normAr, normx)"""
+        m, n = self._mn
+        first, R = int(spikes[0]), int(spikes[1])
+        xyz = None if coords is None else np.ascontiguousarray(coords, np.float64)
+        x = np.zeros((R, n), np.float32) if want_x else None
+        psf = np.zeros((R, max(int(nblocks), 1), 4))
+        return self._batch(self._L.dsa_resolution_blocks, R, (R, int(ndata), int(nblocks), first, xyz, damp), (atol, btol, conlim, itnlim, local_size), x=x, psf=psf)
 
     def lsmr_tradeoff(self, b, ndata, weight0, weights, damps, want_x=True, atol=1e-6, btol=1e-6, conlim=100.0, itnlim=400, local_size=10):
         """K LSMR solves on the matrix of the last spmv_load, whose rows from ndata up are regularisation rows built with weight0:

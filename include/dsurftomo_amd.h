@@ -213,10 +213,19 @@ int dsa_ray_paths(dsa_engine* e, int* datum, int* npts, float* latlon);
  * writes them, then block gc, then block gs, each over the vertices the isotropic row lists, layers outer:
  *   val = (float)(Sazi * (double)f), Sazi = sen_vs * (double)(0.5f * vels) of the layer and column, f = fdm_c (gc) or fdm_s (gs),
  *   kept when |val| > 1e-4, col = B*maxvp + k*nvx*nvz + (jj-1)*nvx + kk with B = 1 (gc), 2 (gs), maxvp = nvx*nvz*(nz-1).
- * dsurf and every statistic are dsa_solve_rows'.  Host COO only: DSA_ERR_STATE with option rows_on_device, DSA_ERR_ARGUMENT for a null
+ * dsurf and every statistic are dsa_solve_rows'.  Host COO only (dsa_solve_rows_azimuthal_device leaves the rows on the device):
+ * DSA_ERR_STATE with option rows_on_device, DSA_ERR_ARGUMENT for a null
  * array or when 3*maxvp does not fit an int, DSA_ERR_CAPACITY as dsa_solve_rows.  Calls that never ask for it use no memory for it. */
 int dsa_solve_rows_azimuthal(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity,
                              long long* nar);
+/* dsa_solve_rows_azimuthal with its rows left on the device: the COO is written behind the engine's resident rows exactly
+ * as dsa_solve_rows writes it under option rows_on_device, whatever that option says, and the option is left as it was found.  rw / iw /
+ * col are all given -- they then receive a copy, bit for bit dsa_solve_rows_azimuthal's, as are dsurf, *nar and every statistic -- or all
+ * NULL: nothing of 12 bytes per entry leaves the device.  Afterwards dsa_iteration_system_azimuthal_device builds the joint system on
+ * these rows; dsa_iteration_system_device refuses them (DSA_ERR_STATE).  Errors: DSA_ERR_ARGUMENT (a null e / nar, only some of rw / iw /
+ * col given, 3*maxvp beyond an int), DSA_ERR_STATE (no plan, no depth kernels, several engines sharing the call), DSA_ERR_CAPACITY. */
+int dsa_solve_rows_azimuthal_device(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity,
+                                    long long* nar);
 /* on[kmax] (kmax = the depth kernels' slot count, checked by the next azimuthal solve): 0 = units of that depth-kernel slot (sen_slot of
  * dsa_plan_units) emit no gc / gs entries -- Love periods, for which the 2psi terms above do not hold.  on = NULL: every slot emits. */
 int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on);
@@ -265,6 +274,22 @@ int dsa_lsmr_batch(dsa_engine* e, int nreal, const float* b, const float* row_sc
 int dsa_lsmr_resolution(dsa_engine* e, int nreal, int ndata, const float* models, int spike_first, const double* coords,
                         float damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x, double* psf,
                         int* istop, int* itn, float* est);
+
+/* dsa_lsmr_resolution's spike solves with the PSF measures taken per parameter block: the n unknowns are read as
+ * nblocks blocks of nb = n / nblocks cells each on one grid of cells (the joint system: Vs | gc | gs, nblocks = 3); coords holds 3*nb
+ * doubles, (latitude deg, longitude deg, depth km) per cell.  x, istop, itn, est are dsa_lsmr_resolution's for the same spikes, bit for
+ * bit.  For spike r at unknown j = spike_first + r, cell cj = j mod nb, and every block B:
+ *   psf[(r*nblocks + B)*4 + 0]      = x_r[B*nb + cj]: R_jj in the spike's own block, the co-located leakage in the others;
+ *   psf[(r*nblocks + B)*4 + 1 .. 3] = sum x^2, sum x^2 dh^2, sum x^2 dz^2 over the unknowns of block B, dh and dz measured from cell
+ *                                     cj to the unknown's cell as in dsa_lsmr_resolution.
+ * fp64 in a fixed order (repeated calls give the same bits): a block is cut into chunks of 1024 cells, a chunk's four runs of 256
+ * consecutive cells are summed in order and added as ((w0 + w1) + w2) + w3, the chunks are added in order.  With nblocks = 1 psf is
+ * dsa_lsmr_resolution's, bit for bit.  x (nreal*n) may be NULL: then nothing of size n*nreal leaves the device.  The resident matrix and
+ * the other solvers are left as they were.  Errors: DSA_ERR_ARGUMENT (nreal < 1, ndata outside [1, m], nblocks < 1 or not a divisor of
+ * n, a spike range outside [0, n), a null coords / psf / istop / itn / est), DSA_ERR_STATE (no matrix), DSA_ERR_DEVICE. */
+int dsa_resolution_blocks(dsa_engine* e, int nreal, int ndata, int nblocks, int spike_first, const double* coords,
+                               float damp, float atol, float btol, float conlim, int itnlim, int localSize, float* x,
+                               double* psf, int* istop, int* itn, float* est);
 
 /* Regularisation trade-off sweep: nreal LSMR solves on the (m x n) matrix of the last dsa_spmv_load /
  * dsa_iteration_system_device, whose rows below ndata are data rows and whose rows from ndata up are regularisation rows
@@ -354,6 +379,24 @@ int dsa_step_models(dsa_engine* e, int nx, int ny, int nz, int nmodels, const fl
 int dsa_iteration_system_device(dsa_engine* e, int nx, int ny, int nz, int dall, const float* obst, const float* dsyn,
                                 float threshold0, float weight0, float* cbst, float* datweight, float* norm, int* m_out,
                                 long long* nar_out, float* dws);
+
+/* The joint Vs | gc | gs system of the azimuthal step built on the azimuthal rows that
+ * dsa_solve_rows_azimuthal_device, or dsa_calsurfg_azimuthal called with null rw / iw / col, left on the device.  datweight[dall]: the
+ * reference's 0/1 percentile weights of the residuals obst - dsyn; cbst[i] = fl((obst[i] - dsyn[i]) * datweight[i]) (under a zero
+ * weight a zero with the residual's sign, as the host route's product leaves it); every data entry scaled by its datum's weight, and below the dall data rows the first-difference Laplacian rows of the three blocks, written by a kernel: block
+ * B = 0 (Vs), 1 (gc), 2 (gs) has rows dall + B*maxvp + index and columns B*maxvp + ..., 2 w on the block's faces, 6 w and six -w
+ * inside, w = weight0 on Vs and weight_azi on gc and gs, each value one rounded product.  m = *m_out = dall + 3*maxvp rows,
+ * n = 3*maxvp columns; cbst has dall + 3*maxvp elements (0 from dall up).  norm[3*maxvp]: per column the sequential fp32 sum of |entry|
+ * over its data entries in storage order; dws[6]: {max, mean} of norm per block.  Afterwards dsa_lsmr(e, cbst, ...) and every batched
+ * solver run on that matrix (dsa_lsmr_tradeoff / _crossval when weight_azi = weight0: one weight per call).  Bit-identical -- matrix
+ * in both orderings, cbst, datweight -- to the host route: dsa_calsurfg_azimuthal with arrays, the same weights, the same rows in the
+ * order data, Vs, gc, gs through dsa_spmv_load.  Every argument is checked before the device is touched.  Errors: DSA_ERR_ARGUMENT (a
+ * null pointer, nx or ny < 3, nz < 2, dall < 1, too few data for the quartile rule, dall + 3*maxvp beyond an int, a weight0 or
+ * weight_azi that is negative or not finite), DSA_ERR_STATE (no azimuthal rows on the device: none at all, isotropic ones, or a joint
+ * system already built from them), DSA_ERR_CAPACITY (more than 2^31-1 entries), DSA_ERR_DEVICE. */
+int dsa_iteration_system_azimuthal_device(dsa_engine* e, int nx, int ny, int nz, int dall, const float* obst, const float* dsyn,
+                                          float threshold0, float weight0, float weight_azi, float* cbst, float* datweight,
+                                          float* norm, int* m_out, long long* nar_out, float* dws);
 
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
@@ -493,7 +536,9 @@ int dsa_synthetic(const int* nx, const int* ny, const int* nz, const int* nparpi
 /* dsa_calsurfg with the azimuthal blocks of dsa_solve_rows_azimuthal (extension): the same argument list and conventions --
  * iw(1) = nar on return, the rows behind it, the capacity of dsa_dropin_set_capacity (state it for 3 nparpi columns per datum).  The
  * Rayleigh depth-kernel slots (phase and group periods) emit gc / gs entries, the Love slots none.  The isotropic entries, dsurf and the
- * diagnostics afterwards are dsa_calsurfg's; columns run to 3*nparpi.  rw / iw / col must be host arrays.  DSA_ERR_STATE: more than one
+ * diagnostics afterwards are dsa_calsurfg's; columns run to 3*nparpi.  rw / iw / col are host arrays, or NULL together: the rows then
+ * stay on the drop-in engine (dsa_solve_rows_azimuthal_device), as dsa_calsurfg's do, for dsa_iteration_system_azimuthal_device on
+ * dsa_dropin_engine(); iw(1) is then not written.  Only some of the three NULL: DSA_ERR_ARGUMENT.  DSA_ERR_STATE: more than one
  * engine in the pool (DSA_DEVICES): the azimuthal call is not sharded over GPUs. */
 int dsa_calsurfg_azimuthal(const int* nx, const int* ny, const int* nz, const int* nparpi, const float* vels,
                            int* iw, float* rw, int* col, float* dsurf,
