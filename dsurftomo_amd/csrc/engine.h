@@ -245,6 +245,12 @@ struct Engine {
     std::vector<int> h_azi_steps;      // ... and its steps
     // device_rows: the rows stay behind G_rw / G_row / G_col whatever the option rows_on_device says (dsa_solve_rows_azimuthal_device)
     int solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar, bool device_rows = false);
+    // map rows (dsa_solve_rows_maps): the running solve emits rows whose columns are (block, map, vertex) and needs no
+    // depth kernels; with azimuthal = 1 it is an azimuthal solve too (azi_now: three slabs per ray, the sums of dsa_ray_azimuths)
+    bool maps_now = false;
+    int solve_maps(int azimuthal, float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar);
+    int update_maps(int nm, const float* dv, float dvmax, float minvel, float maxvel);
+    int get_maps(int nm, float* out_v);
 
     // dispersion stage (disp_kernels.hip): Vs model -> pv maps + depth kernels, all resident
     bool disp_ready = false;
@@ -300,8 +306,11 @@ struct Engine {
     // what the G_nar resident entries are: set by the launch that writes them, cleared wherever G_nar is reset.  The isotropic builder
     // (dsa_iteration_system_device) refuses azimuthal rows, the joint one (dsa_iteration_system_azimuthal_device) takes nothing else and
     // leaves kRowsJoint (its system, Laplacian rows included: not rows to build from again).
-    enum RowsKind { kRowsNone, kRowsIsotropic, kRowsAzimuthal, kRowsJoint };
+    // kRowsMaps: map rows (dsa_solve_rows_maps) of G_map_blocks blocks on G_map_nmaps maps of an nx x ny vertex grid; only
+    // dsa_iteration_system_maps_device takes them, and leaves kRowsMapSystem
+    enum RowsKind { kRowsNone, kRowsIsotropic, kRowsAzimuthal, kRowsJoint, kRowsMaps, kRowsMapSystem };
     RowsKind G_kind = kRowsNone;
+    int G_map_blocks = 0, G_map_nmaps = 0, G_map_nx = 0, G_map_ny = 0;
     template <class T> int ensure_keep(DevBuf<T>& b, size_t n, size_t used);
 
     bool spmv_attr_set = false;        // LDS attribute of the blocked SpmV kernels set on this engine's device

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -728,12 +729,12 @@ int Engine::solve(float* dsurf, float* rw, int* iw, int* col, long long cap, lon
     if (!planned) { fail(DSA_ERR_STATE, "solve: call dsa_plan first"); return DSA_ERR_STATE; }
     const bool grow = grow_rw && grow_iw && grow_col;
     const bool rows = ((rw && iw && col) || grow || rows_on_device) && nar;
-    if (rows && !have_sens) { fail(DSA_ERR_STATE, "solve: Frechet rows need the depth kernels (dsa_set_depth_kernels / dsa_depthkernel) first"); return DSA_ERR_STATE; }
+    if (rows && !have_sens && !maps_now) { fail(DSA_ERR_STATE, "solve: Frechet rows need the depth kernels (dsa_set_depth_kernels / dsa_depthkernel) first"); return DSA_ERR_STATE; }
     rays_clamped = 0; first_clamped_unit = -1;
     if (rows) {
         *nar = 0;
         G_nar = 0; G_kind = kRowsNone;
-        for (const SourceDesc& s : h_src)
+        if (!maps_now) for (const SourceDesc& s : h_src)
             if (s.sen_slot < 0 || s.sen_slot >= sens_kmax) { fail(DSA_ERR_ARGUMENT, "solve: a unit uses depth-kernel slot %d of %d", s.sen_slot, sens_kmax); return DSA_ERR_ARGUMENT; }
     }
     HIP_TRY(this, hipSetDevice(device));
@@ -1329,7 +1330,13 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
         ensure(offsets, per + 1) || ensure(rayinfo, per * info_words)) return status;
     RowAziArgs z{};
     z.Sazi = Sazi.p; z.slab_len = slab_len; z.slot_on = azi_slot_on.p; z.maxvp = g.nvx * g.nvz * (sens_nz - 1);
-    auto emit = [&](const RowArgs& a, bool write) { if (azi_now) launch_row_emit_azi(g, a, z, write, stream); else launch_row_emit(g, a, write, stream); };
+    RowMapArgs zm{};
+    zm.slab_len = slab_len; zm.nblocks = azi_now ? 3 : 1; zm.nmaps = nmaps;
+    auto emit = [&](const RowArgs& a, bool write) {
+        if (maps_now) launch_row_emit_maps(g, a, zm, write, stream);
+        else if (azi_now) launch_row_emit_azi(g, a, z, write, stream);
+        else launch_row_emit(g, a, write, stream);
+    };
     std::vector<int32_t> h_info;
     hipEvent_t ea = events[1], eb = events[2], ec = events[3];
     for (size_t t = t0; t < t1; t += per) {
@@ -1373,7 +1380,8 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
                 HIP_TRY(this, hipMemcpyAsync(iw + *nar, a.iw, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
                 HIP_TRY(this, hipMemcpyAsync(col + *nar, a.col, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
             }
-            G_nar = *nar + total; G_kind = azi_now ? kRowsAzimuthal : kRowsIsotropic;
+            G_nar = *nar + total; G_kind = maps_now ? kRowsMaps : (azi_now ? kRowsAzimuthal : kRowsIsotropic);
+            if (maps_now) { G_map_blocks = azi_now ? 3 : 1; G_map_nmaps = nmaps; G_map_nx = g.nx; G_map_ny = g.ny; }
         } else if (total > 0) {
             if (ensure(coo_rw, (size_t)total) || ensure(coo_iw, (size_t)total) || ensure(coo_col, (size_t)total)) return status;
             a.rw = coo_rw.p; a.iw = coo_iw.p; a.col = coo_col.p;
@@ -1444,6 +1452,71 @@ int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long lon
     azi_now = false;
     have_azi = rc == 0;
     return rc;
+}
+
+// dsa_solve_rows_maps: solve() whose rays emit map rows (ray_kernels.hip: k_row_emit_maps) -- the slab elements
+// themselves in columns (block, map, vertex), no depth kernels involved.  azimuthal: the rays are traced by k_rays<., true> and keep the c and
+// s slabs for blocks 1 and 2, and their sums for dsa_ray_azimuths.  Host arrays, or (all three null) the rows stay on the device.
+int Engine::solve_maps(int azimuthal, float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar)
+{
+    have_azi = false;
+    const int given = (rw != nullptr) + (iw != nullptr) + (col != nullptr);
+    if (azimuthal != 0 && azimuthal != 1) { fail(DSA_ERR_ARGUMENT, "solve_rows_maps: azimuthal is 0 or 1, not %d", azimuthal); return DSA_ERR_ARGUMENT; }
+    if (given != 0 && given != 3) { fail(DSA_ERR_ARGUMENT, "solve_rows_maps: rw / iw / col are all given or all NULL"); return DSA_ERR_ARGUMENT; }
+    if (!have_maps) { fail(DSA_ERR_STATE, "solve_rows_maps: call dsa_set_maps first"); return DSA_ERR_STATE; }
+    if (!planned) { fail(DSA_ERR_STATE, "solve_rows_maps: call dsa_plan first"); return DSA_ERR_STATE; }
+    if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_maps: one engine only"); return DSA_ERR_STATE; }
+    const long long ncols = (long long)(azimuthal ? 3 : 1) * nmaps * g.nvx * g.nvz;
+    if (ncols > 0x7fffffffLL) { fail(DSA_ERR_ARGUMENT, "solve_rows_maps: %lld columns do not fit an int", ncols); return DSA_ERR_ARGUMENT; }
+    if (azimuthal) {
+        h_azi_sums.assign(2 * h_trace.size(), 0.0f);
+        h_azi_steps.assign(h_trace.size(), 0);
+    }
+    const bool option = rows_on_device;       // (as solve_azimuthal: the option is left as it was found)
+    rows_on_device = given == 0;
+    maps_now = true; azi_now = azimuthal != 0;
+    const int rc = solve(dsurf, rw, iw, col, cap, nar);
+    rows_on_device = option;
+    maps_now = false; azi_now = false;
+    have_azi = azimuthal && rc == 0;
+    return rc;
+}
+
+// dsa_update_maps: the step dv (nm * nvx * nvz, the c0 block of a solution) applied to the resident fp32 vertex maps by
+// k_update_maps, then everything set_maps derives from the vertex values once more from the updated values fetched back: hmin_slow, the
+// maps' mean slowness, the dicing (finish_maps), the flags; the plan is dropped as set_maps drops it.  Afterwards the engine is in the state
+// set_maps would leave with pv = (double) of the same fp32 values.
+int Engine::update_maps(int nm, const float* dv, float dvmax, float minvel, float maxvel)
+{
+    if (!have_maps) { fail(DSA_ERR_STATE, "update_maps: call dsa_set_maps first"); return DSA_ERR_STATE; }
+    if (nm != nmaps) { fail(DSA_ERR_ARGUMENT, "update_maps: %d maps, the engine holds %d", nm, nmaps); return DSA_ERR_ARGUMENT; }
+    if (!dv) { fail(DSA_ERR_ARGUMENT, "update_maps: dv is required (dsa_lsmr returns its solution to the host; pass its c0 block)"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(dvmax) || dvmax <= 0.0f) { fail(DSA_ERR_ARGUMENT, "update_maps: dvmax %g must be finite and > 0", (double)dvmax); return DSA_ERR_ARGUMENT; }
+    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "update_maps: minvel %g > maxvel %g", (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t nv = (size_t)g.nx * g.ny, nstep = (size_t)g.nvx * g.nvz * nm;
+    OwnedBuf<float> d_dv;
+    if (ensure(d_dv, nstep)) return status;
+    HIP_TRY(this, hipMemcpyAsync(d_dv.p, dv, nstep * 4, hipMemcpyHostToDevice, stream));
+    launch_update_maps(g, nm, d_dv.p, dvmax, minvel, maxvel, velv.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    std::vector<float> hv(nv * nm);
+    HIP_TRY(this, hipMemcpyAsync(hv.data(), velv.p, hv.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    hmin_slow = 1e30f;
+    for (float v : hv) if (v > 0.0f && 1.0f / v < hmin_slow) hmin_slow = 1.0f / v;
+    mean_slowness_of_maps(hv.data(), nv, nm);
+    return finish_maps(nm);
+}
+
+int Engine::get_maps(int nm, float* out_v)
+{
+    if (!have_maps) { fail(DSA_ERR_STATE, "get_maps: call dsa_set_maps first"); return DSA_ERR_STATE; }
+    if (nm != nmaps) { fail(DSA_ERR_ARGUMENT, "get_maps: %d maps, the engine holds %d", nm, nmaps); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    HIP_TRY(this, hipMemcpyAsync(out_v, velv.p, (size_t)g.nx * g.ny * nm * 4, hipMemcpyDeviceToHost, stream));       // (on the engine's stream: ordered behind whatever wrote velv)
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
 }
 
 // download tiled records and untile on the host: which = 0 -> T (raw), 1 -> tau (raw)
@@ -1749,6 +1822,24 @@ int dsa_solve_rows_azimuthal_device(dsa_engine* e, float* dsurf, float* rw, int*
     const int given = (rw != nullptr) + (iw != nullptr) + (col != nullptr);
     if (given != 0 && given != 3) { en->fail(DSA_ERR_ARGUMENT, "solve_rows_azimuthal_device: rw / iw / col are all given or all NULL"); return DSA_ERR_ARGUMENT; }
     return en->solve_azimuthal(dsurf, rw, iw, col, capacity, nar, true);
+}
+
+int dsa_solve_rows_maps(dsa_engine* e, int azimuthal, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar)
+{
+    if (!e || !nar) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->solve_maps(azimuthal, dsurf, rw, iw, col, capacity, nar);
+}
+
+int dsa_update_maps(dsa_engine* e, int nmaps, const float* dv, float dvmax, float minvel, float maxvel)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->update_maps(nmaps, dv, dvmax, minvel, maxvel);
+}
+
+int dsa_get_maps(dsa_engine* e, int nmaps, float* velv)
+{
+    if (!e || !velv) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->get_maps(nmaps, velv);
 }
 
 int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on)

@@ -11,6 +11,7 @@
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
 #include "joint_system.h"
+#include "map_system.h"
 #include "spmv_state.h"
 
 namespace {
@@ -108,6 +109,28 @@ __global__ __launch_bounds__(256) void k_laplacian_blocks(int nvx, int nvz, int 
     }
 }
 
+// The Laplacian rows of the map system (map_system.h), written where the data rows are: thread t = unknown `index` in column order writes
+// its 1 or 5 entries at first + map_first_entry(index) -- row dall + index + 1, value (float)c * w in one rounded product, w = weight0 on
+// the planes of block 0 (the first nmaps planes) and weight_azi on the others.
+__global__ __launch_bounds__(256) void k_laplacian_maps(int nvx, int nvz, int nmaps, long long n, int dall, long long first, float weight0, float weight_azi,
+                                                        float* __restrict__ rw, int* __restrict__ row, int* __restrict__ col)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const long long plane = t / ((long long)nvx * nvz);
+    const float w = plane < nmaps ? weight0 : weight_azi;
+    const long long at = first + dsa::map_first_entry(nvx, nvz, t);
+    const int count = dsa::map_row_entries(nvx, nvz, t);
+    for (int q = 0; q < count; ++q) {
+        long long c1;
+        int coef;
+        dsa::map_entry(nvx, nvz, t, q, &c1, &coef);
+        rw[at + q] = (float)coef * w;
+        row[at + q] = (int)(dall + t + 1);
+        col[at + q] = (int)c1;
+    }
+}
+
 }  // namespace
 
 namespace dsa {
@@ -165,6 +188,7 @@ int dsa_iteration_system_device(dsa_engine* h, int nx, int ny, int nz, int dall,
     if (nx < 3 || ny < 3 || nz < 2 || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_device: bad arguments"); return DSA_ERR_ARGUMENT; }
     if (!e->rows_on_device || (e->G_nar > 0 && !e->G_rw.p)) { e->fail(DSA_ERR_STATE, "iteration_system_device: no rows on the device (option rows_on_device + dsa_solve_rows, or dsa_calsurfg with null arrays)"); return DSA_ERR_STATE; }
     if (e->G_kind == dsa::Engine::kRowsAzimuthal || e->G_kind == dsa::Engine::kRowsJoint) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are azimuthal rows (three blocks of columns): dsa_iteration_system_azimuthal_device builds their system"); return DSA_ERR_STATE; }
+    if (e->G_kind == dsa::Engine::kRowsMaps || e->G_kind == dsa::Engine::kRowsMapSystem) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are map rows (columns per period): dsa_iteration_system_maps_device builds their system"); return DSA_ERR_STATE; }
     const int nvx = nx - 2, nvz = ny - 2, nl = nz - 1;
     const long long maxvp = (long long)nvx * nvz * nl, nar_in = e->G_nar;
     { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_device: too few data"); return rc; } }
@@ -266,6 +290,74 @@ int dsa_iteration_system_azimuthal_device(dsa_engine* h, int nx, int ny, int nz,
         dws[2 * B] = top; dws[2 * B + 1] = total / (float)maxvp;
     }
     e->G_nar = nar; e->G_kind = dsa::Engine::kRowsJoint;
+    *m_out = m;
+    *nar_out = nar;
+    return done(0);
+}
+
+// The per-period map system built where dsa_solve_rows_maps left its rows on the device: the data rows scaled by the
+// 0/1 weights exactly as in dsa_iteration_system_azimuthal_device (residual_weights, k_scale_rows, the right-hand side fl(residual * weight)),
+// and below the dall data rows one 2-D Laplacian row per unknown (k_laplacian_maps: map_system.h), weight0 on the planes of block 0 and
+// weight_azi on those of blocks 1 and 2.  n = nblocks nmaps layer columns, m = dall + n rows.  norm[n] adds |entry| over a column's data
+// entries in storage order; dws[2 B], dws[2 B + 1] are block B's {max, mean} of it.  Every argument is checked before the device is touched.
+int dsa_iteration_system_maps_device(dsa_engine* h, int nx, int ny, int nmaps, int nblocks, int dall, const float* obst, const float* dsyn, float threshold0,
+                                     float weight0, float weight_azi, float* cbst, float* datweight, float* norm, int* m_out, long long* nar_out, float* dws)
+{
+    if (!h) return DSA_ERR_ARGUMENT;
+    dsa::Engine* e = reinterpret_cast<dsa::Engine*>(h);
+    if (nx < 3 || ny < 3 || nmaps < 1 || (nblocks != 1 && nblocks != 3) || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_maps_device: bad arguments"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(weight0) || weight0 < 0.0f || !std::isfinite(weight_azi) || weight_azi < 0.0f) {
+        e->fail(DSA_ERR_ARGUMENT, "iteration_system_maps_device: weight0 %g and weight_azi %g must be finite and >= 0", (double)weight0, (double)weight_azi);
+        return DSA_ERR_ARGUMENT;
+    }
+    const int nvx = nx - 2, nvz = ny - 2;
+    const long long layer = (long long)nvx * nvz, n = (long long)nblocks * nmaps * layer;
+    if (n + dall > 0x7fffffffll) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_maps_device: %lld rows do not fit an int", n + dall); return DSA_ERR_ARGUMENT; }
+    if (e->G_kind != dsa::Engine::kRowsMaps || e->G_map_blocks != nblocks || e->G_nar < 1 || !e->G_rw.p) {
+        e->fail(DSA_ERR_STATE, "iteration_system_maps_device: %s (dsa_solve_rows_maps with azimuthal = %d first)",
+                e->G_kind == dsa::Engine::kRowsMapSystem ? "the rows on the device are a map system already" :
+                e->G_kind == dsa::Engine::kRowsMaps ? "the map rows on the device have another number of blocks" : "no map rows on the device", nblocks == 3 ? 1 : 0);
+        return DSA_ERR_STATE;
+    }
+    if (e->G_map_nx != nx || e->G_map_ny != ny || e->G_map_nmaps != nmaps) {
+        e->fail(DSA_ERR_ARGUMENT, "iteration_system_maps_device: nx %d ny %d nmaps %d, the map rows on the device were made with %d %d %d", nx, ny, nmaps, e->G_map_nx, e->G_map_ny, e->G_map_nmaps);
+        return DSA_ERR_ARGUMENT;
+    }
+    const long long nar_in = e->G_nar, nreg = (long long)nblocks * nmaps * dsa::map_plane_entries(nvx, nvz), nar = nar_in + nreg;
+    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_maps_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_maps_device: too few data"); return rc; } }
+    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
+    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
+    for (long long i = 0; i < n; ++i) cbst[dall + i] = 0.0f;
+    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_maps_device: hipSetDevice"); return DSA_ERR_DEVICE; }
+    dsa::DevBuf<float> d_w, d_norm;
+    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
+#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_maps_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
+    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)n) ||
+        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
+    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
+    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)n * 4, e->stream));
+    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
+    hipLaunchKernelGGL(k_laplacian_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nmaps, n, dall, nar_in, weight0, weight_azi,
+                       e->G_rw.p, e->G_row.p, e->G_col.p);
+    IT_TRY(hipGetLastError());
+    IT_TRY(hipStreamSynchronize(e->stream));
+    const int m = dall + (int)n;
+    // (from here on the resident entries are a system, not rows to build from again -- also when a later step fails)
+    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsMapSystem;
+    { const int rc = dsa::spmv_load_from_device(e, m, (int)n, nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
+    dsa::spmv_abs_column_sums(e, d_norm.p);
+    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    IT_TRY(hipStreamSynchronize(e->stream));
+    IT_TRY(hipGetLastError());
+#undef IT_TRY
+    const long long per_block = (long long)nmaps * layer;
+    for (int B = 0; B < nblocks; ++B) {                                                        // main.f90:386-392, block by block
+        const float* nb = norm + (size_t)B * (size_t)per_block;
+        float total = 0.0f, top = 0.0f;
+        for (long long i = 0; i < per_block; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
+        dws[2 * B] = top; dws[2 * B + 1] = total / (float)per_block;
+    }
     *m_out = m;
     *nar_out = nar;
     return done(0);

@@ -274,6 +274,9 @@ struct RowAziArgs {
     int maxvp;                                             // nvx * nvz * (nz - 1): columns of one block
 };
 void launch_row_emit_azi(const GridDesc& g, const RowArgs& a, const RowAziArgs& z, bool write, hipStream_t stream);
+// map rows: a.slab_stride spans nblocks slabs of slab_len floats; columns (B * nmaps + the unit's map) * layer + vertex
+struct RowMapArgs { size_t slab_len; int nblocks, nmaps; };
+void launch_row_emit_maps(const GridDesc& g, const RowArgs& a, const RowMapArgs& z, bool write, hipStream_t stream);
 // offsets[0..n] = exclusive prefix sums of counts[0..n-1]
 void launch_scan(const int* d_counts, int n, long long* d_offsets, hipStream_t stream);
 
@@ -296,6 +299,8 @@ void launch_depth_kernels(const float* d_vels, int ncol, int nz, int kmax, const
 // curves of a multi-model run, (period, model, column), into the model-major map store: map model * nmaps_per_model + map_first + period
 void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, int nmaps_per_model, int map_first, double* d_pv, hipStream_t stream);
 void launch_to_float(const double* d_in, float* d_out, size_t n, hipStream_t stream);
+// velv[m][jj][kk + 1] += clamp(dv[m][jj - 1][kk], -dvmax, dvmax), clamped to [minvel, maxvel], for the interior vertices of nm maps; the outer ring keeps its values (stage_kernels.hip)
+void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_velv, hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

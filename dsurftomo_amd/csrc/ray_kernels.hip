@@ -265,6 +265,56 @@ void launch_row_emit_azi(const GridDesc& g, const RowArgs& a, const RowAziArgs& 
     else hipLaunchKernelGGL(k_row_emit_azi<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
 }
 
+// The map row of a ray: no depth factor -- the slab element itself, over the kept vertices of the isotropic list,
+// block B = 0 (c0, iso slab), then with z.nblocks = 3 block 1 (A1, c slab) and block 2 (A2, s slab); kept when |f| > ftol; column
+// (B * nmaps + map) * layer + i + 1 with `map` the unit's velocity map.  What k_row_emit / k_row_emit_azi write under a depth factor of
+// exactly 1.0 on a single layer, with the columns of every map side by side.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_row_emit_maps(GridDesc g, RowArgs a, RowMapArgs z)
+{
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= a.n) return;
+    const RayDesc rd = a.rays[a.trace_ids[t]];
+    const int map = a.src[rd.src - a.unit_base].period;
+    const int* vl = a.vlist + (size_t)t * a.vlist_stride;
+    const int nv = a.nv[t];
+    const int nvx = g.nvx, ldx = g.nvx + 2, layer = g.nvx * g.nvz;
+    const long long off = WRITE ? a.offsets[t] : 0;
+    int cnt = 0;
+    for (int B = 0; B < z.nblocks; ++B) {
+        const float* slab = a.slabs + (size_t)t * a.slab_stride + (size_t)B * z.slab_len;
+        const int col0 = (B * z.nmaps + map) * layer + 1;
+        for (int base = 0; base < nv; base += 64) {
+            const int e = base + lane;
+            bool keep = false;
+            float f = 0.0f;
+            int i = 0;
+            if (e < nv) {
+                i = vl[e];
+                const int jj = i / nvx + 1, kk = i - (jj - 1) * nvx + 1;
+                f = slab[(size_t)jj * ldx + kk];
+                keep = fabsf(f) > kFtol;
+            }
+            const unsigned long long m = __ballot(keep);
+            if (WRITE && keep) {
+                const long long p = off + cnt + lanes_below(m);
+                a.rw[p] = f;
+                a.iw[p] = rd.data + 1;
+                a.col[p] = col0 + i;
+            }
+            cnt += __popcll(m);
+        }
+    }
+    if (!WRITE && lane == 0) a.counts[t] = cnt;
+}
+
+void launch_row_emit_maps(const GridDesc& g, const RowArgs& a, const RowMapArgs& z, bool write, hipStream_t stream)
+{
+    if (a.n <= 0) return;
+    if (write) hipLaunchKernelGGL(k_row_emit_maps<true>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
+    else hipLaunchKernelGGL(k_row_emit_maps<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
+}
+
 // one workgroup: per-thread segment sums, scan of the 1024 sums in LDS, segment rewrite
 __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ counts, int n, long long* __restrict__ offsets)
 {

@@ -61,6 +61,34 @@ void launch_gridder(const GridDesc& g, const float* d_velv, const float* d_basis
     hipLaunchKernelGGL(k_gridder, dim3((nrec + 255) / 256), dim3(256), 0, stream, g, d_velv, d_basis, d_veln, d_slow);
 }
 
+// The update of resident vertex maps (dsa_update_maps): interior vertex (kk, jj) of map m gets its element of dv clipped
+// to +-dvmax, then the clamp to [minvel, maxvel], in dsa_model_update's order of operations (plain fp32, a NaN stays a NaN); the outer ring
+// of vertices is not touched.  One thread per interior vertex of every map.
+__global__ void k_update_maps(int nvx, int nvz, int nm, const float* __restrict__ dv, float dvmax, float minvel, float maxvel, float* __restrict__ velv)
+{
+    const size_t layer = (size_t)nvx * nvz, n = layer * nm;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const size_t m = t / layer, i = t - m * layer;
+    const int jj = (int)(i / nvx) + 1, kk = (int)(i - (size_t)(jj - 1) * nvx) + 1;
+    float d = dv[t];
+    if (d >= dvmax) d = dvmax;
+    if (d <= -dvmax) d = -dvmax;
+    const size_t at = m * (size_t)(nvx + 2) * (nvz + 2) + (size_t)jj * (nvx + 2) + kk;
+    float v = velv[at];
+    v = v + d;
+    if (v < minvel) v = minvel;
+    if (v > maxvel) v = maxvel;
+    velv[at] = v;
+}
+
+void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_velv, hipStream_t stream)
+{
+    const size_t n = (size_t)g.nvx * g.nvz * nm;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_update_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g.nvx, g.nvz, nm, d_dv, dvmax, minvel, maxvel, d_velv);
+}
+
 // ---------------------------------------------------------------------------------------------
 // K2a: refined velocities of every source box; also resets the refined field and block state
 __global__ void k_refine(GridDesc g, BatchPtrs b, const float* __restrict__ velv_all, size_t velv_stride,

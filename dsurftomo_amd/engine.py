@@ -98,6 +98,10 @@ def declare_solvers(L):
     L.dsa_solve_rows_azimuthal_device.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_iteration_system_azimuthal_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 3 + [_vp] * 6
     L.dsa_model_update.argtypes = [_i32] * 3 + [_vp] * 2 + [_f32] * 2
+    L.dsa_solve_rows_maps.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dsa_iteration_system_maps_device.argtypes = [_vp] + [_i32] * 5 + [_vp] * 2 + [_f32] * 3 + [_vp] * 6
+    L.dsa_update_maps.argtypes = [_vp, _i32, _vp] + [_f32] * 3
+    L.dsa_get_maps.argtypes = [_vp, _i32, _vp]
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -267,6 +271,59 @@ class Engine:
                                                             C.c_longlong(capacity), C.byref(nar)))
         n = nar.value
         return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+
+    # ---- per-period 2-D maps -------------------------------------------------
+    def solve_rows_maps(self, capacity, azimuthal=False):
+        """receiver times plus the map rows as COO (rw, row, col), 1-based: columns (B * nmaps + map) * layer + vertex + 1, B = 0 (c0) and, with
+        azimuthal, 1 (A1, cos 2psi) and 2 (A2, sin 2psi) (dsa_solve_rows_maps); no depth kernels needed"""
+        out = np.zeros(self._ndata, np.float32)
+        rw = np.zeros(capacity, np.float32)
+        iw = np.zeros(capacity, np.int32)
+        col = np.zeros(capacity, np.int32)
+        nar = C.c_longlong(0)
+        self._check(self._L.dsa_solve_rows_maps(self._h, int(bool(azimuthal)), _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
+                                                C.c_longlong(capacity), C.byref(nar)))
+        n = nar.value
+        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+
+    def solve_rows_maps_device(self, azimuthal=False, capacity=1 << 62):
+        """solve_rows_maps with the rows left on the device for iteration_system_maps_device: returns (times, number of entries)"""
+        out = np.zeros(self._ndata, np.float32)
+        nar = C.c_longlong(0)
+        self._check(self._L.dsa_solve_rows_maps(self._h, int(bool(azimuthal)), _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
+        return out, nar.value
+
+    def iteration_system_maps_device(self, nx, ny, nmaps, nblocks, obst, dsyn, threshold0, weight0, weight_azi=None):
+        """dsa_iteration_system_maps_device on the map rows left on the device.  Returns dict(m, n, nar, cbst (m,), datweight (dall,), norm (n,),
+        dws (nblocks, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
+        f = np.float32
+        obst = np.ascontiguousarray(obst, f); dsyn = np.ascontiguousarray(dsyn, f)
+        dall = obst.size
+        if dsyn.size != dall:
+            raise ValueError("obst and dsyn differ in length")
+        n = max(int(nblocks), 0) * max(int(nmaps), 0) * max(nx - 2, 0) * max(ny - 2, 0)
+        cbst = np.zeros(dall + n, f); datweight = np.zeros(dall, f); norm = np.zeros(max(n, 1), f); dws = np.zeros(2 * max(int(nblocks), 1), f)
+        m, nar = C.c_int(0), C.c_longlong(0)
+        self._check(self._L.dsa_iteration_system_maps_device(self._h, int(nx), int(ny), int(nmaps), int(nblocks), dall, _p(obst), _p(dsyn), float(threshold0),
+                                                             float(weight0), float(weight0 if weight_azi is None else weight_azi), cbst.ctypes.data_as(_vp),
+                                                             datweight.ctypes.data_as(_vp), norm.ctypes.data_as(_vp), C.byref(m), C.byref(nar), dws.ctypes.data_as(_vp)))
+        self._mn = (m.value, n)
+        return dict(m=m.value, n=n, nar=nar.value, cbst=cbst, datweight=datweight, norm=norm[:n], dws=dws.reshape(-1, 2))
+
+    def update_maps(self, dv, dvmax, minvel, maxvel, nmaps, nx, ny):
+        """dsa_update_maps: dv, nmaps * (nx - 2) * (ny - 2) values (the c0 block of a solution; any shape), applied to the resident vertex maps of
+        an nx x ny grid; plan again afterwards.  ValueError when dv does not hold exactly that many values: the library reads that many."""
+        dv = np.ascontiguousarray(dv, np.float32)
+        want = int(nmaps) * (int(nx) - 2) * (int(ny) - 2)
+        if dv.size != want:
+            raise ValueError("update_maps: dv holds %d values, %d maps of %d x %d vertices need %d" % (dv.size, int(nmaps), nx, ny, want))
+        self._check(self._L.dsa_update_maps(self._h, int(nmaps), _p(dv), float(dvmax), float(minvel), float(maxvel)))
+
+    def get_maps(self, nmaps, nx, ny):
+        """the resident fp32 vertex maps, (nmaps, nx * ny) in set_maps' layout"""
+        out = np.zeros((int(nmaps), nx * ny), np.float32)
+        self._check(self._L.dsa_get_maps(self._h, int(nmaps), out.ctypes.data_as(_vp)))
+        return out
 
     def set_azimuthal_slots(self, on):
         """on: one flag per depth-kernel slot, 0 = units of that slot emit no gc / gs entries; None = every slot emits"""

@@ -398,6 +398,44 @@ int dsa_iteration_system_azimuthal_device(dsa_engine* e, int nx, int ny, int nz,
                                           float threshold0, float weight0, float weight_azi, float* cbst, float* datweight,
                                           float* norm, int* m_out, long long* nar_out, float* dws);
 
+/* ---- per-period 2-D maps on the bent rays.  layer = (nx-2)*(ny-2), nmaps = the maps of dsa_set_maps. ----
+ *
+ * dsa_solve_rows_maps: dsa_solve, and every unit whose mode has bit 1 traces its rays; the ray of datum d of a unit on map m adds, for
+ * block B = 0 (the map value c0; azimuthal = 1: also 1 = A1 with the cos 2psi slab and 2 = A2 with the sin 2psi slab, rays traced as by
+ * dsa_solve_rows_azimuthal) and every vertex i (0-based, the isotropic list: |fdm| >= 1e-4 on the isotropic slab, latitude index
+ * fastest) whose slab element f has |f| > 1e-4, the entry rw = f, iw = d + 1, col = (B*nmaps + m)*layer + i + 1; within a ray B outer,
+ * vertices inner; rays in data order.  These are dsa_solve_rows' / dsa_solve_rows_azimuthal's entries under a depth factor of exactly 1
+ * on one layer, with every map in columns of its own.  No depth kernels are needed.  rw, iw, col: host arrays of `capacity` entries, or
+ * all three NULL: the rows stay on the device for dsa_iteration_system_maps_device (the option rows_on_device is not consulted and left
+ * as it is).  dsa_ray_azimuths works after an azimuthal call.  Errors: DSA_ERR_ARGUMENT (azimuthal not 0 / 1, only some of the three
+ * arrays, more than 2^31-1 columns), DSA_ERR_STATE (no maps, no plan, several engines sharing the call), DSA_ERR_CAPACITY. */
+int dsa_solve_rows_maps(dsa_engine* e, int azimuthal, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar);
+
+/* The regularised system of the map rows left on the device (nblocks = 1 after azimuthal = 0, 3 after azimuthal = 1): datweight, cbst and
+ * the scaling of the data entries exactly as dsa_iteration_system_azimuthal_device; n = nblocks*nmaps*layer columns, m = dall + n rows,
+ * cbst has m elements (0 from dall up).  Unknown `index` (0-based, column order) has the row dall + index: on the edge of its plane -- one
+ * (block, map) pair of (nx-2) x (ny-2) unknowns -- the entry {index, 2 w}, inside {index, 4 w} and -w at -1, +1, -(nx-2), +(nx-2), in
+ * that order: the reference's rule without the depth axis; planes never couple.  w = weight0 on block 0, weight_azi on blocks 1 and 2,
+ * each value one rounded product.  norm[n]: per column the sequential fp32 sum of |entry| over its data entries in storage order;
+ * dws[2*nblocks]: {max, mean} of norm per block.  Afterwards dsa_lsmr(e, cbst, ...) and the batch solvers run on that matrix.  Every
+ * argument is checked before the device is touched.  Errors: DSA_ERR_ARGUMENT (a null pointer, nx or ny < 3, nmaps < 1, nblocks not 1 /
+ * 3, dall < 1, too few data for the quartile rule, dall + n beyond an int, a weight that is negative or not finite, nx / ny / nmaps
+ * other than the rows'), DSA_ERR_STATE (the resident rows are not map rows of this nblocks, or a system was already built from them),
+ * DSA_ERR_CAPACITY (more than 2^31-1 entries), DSA_ERR_DEVICE. */
+int dsa_iteration_system_maps_device(dsa_engine* e, int nx, int ny, int nmaps, int nblocks, int dall, const float* obst, const float* dsyn,
+                                     float threshold0, float weight0, float weight_azi, float* cbst, float* datweight, float* norm,
+                                     int* m_out, long long* nar_out, float* dws);
+
+/* dsa_update_maps: the resident fp32 vertex maps updated on the device.  dv: nmaps*layer floats, the c0 block of a solution (required:
+ * dsa_lsmr returns its solution to the host, a NULL dv is DSA_ERR_ARGUMENT).  Interior vertex i of map m becomes
+ * v + clamp(dv, -dvmax, dvmax), then clamped to [minvel, maxvel], plain fp32 in dsa_model_update's order of operations; the outer ring
+ * of vertices keeps its values.  Then everything dsa_set_maps derives from the vertex values is made again and the plan is dropped (plan
+ * again): the engine is in the state dsa_set_maps leaves with pv = (double) of the same fp32 values, bit for bit.
+ * dsa_get_maps: the resident vertex maps, nmaps*nx*ny floats in dsa_set_maps' layout.
+ * Errors: DSA_ERR_STATE (no maps), DSA_ERR_ARGUMENT (nmaps is not the engine's, dvmax not finite or <= 0, minvel > maxvel, a null pointer). */
+int dsa_update_maps(dsa_engine* e, int nmaps, const float* dv, float dvmax, float minvel, float maxvel);
+int dsa_get_maps(dsa_engine* e, int nmaps, float* velv);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);
