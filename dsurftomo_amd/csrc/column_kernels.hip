@@ -1,0 +1,54 @@
+// k_column_step: the depth step of every interior column of the resident model, one wavefront per column.  The
+// arithmetic is column_system.h's, shared out over the 64 lanes; a block is one wavefront, so the barrier between the phases costs one
+// instruction.  The work arrays lie in LDS, sized by the launch for the case's (M, K): K * M doubles of weighted sensitivities, the packed
+// triangle of N (then L), and five short vectors -- 2.5 KB for the Taipei example (M = 8, K = 26: a CU's 160 KB hold more blocks than its
+// wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
+#include "kernels.h"
+#include "column_system.h"
+
+namespace dsa {
+
+namespace {
+
+struct BlockBarrier {
+    __device__ __forceinline__ void operator()() const { __syncthreads(); }
+};
+
+// block b is interior column (i, j) = (1 + b % nvx, 1 + b / nvx), column c = j * nx + i of the (nz, ny, nx) model.  obs / wt: (K, ncol)
+// fp32; pv: (K, ncol); S: (M, K, ncol); dv: (M, ncol); nused / chi2 / flag: (ncol).  The ring's outputs are the caller's zeros.
+__global__ void __launch_bounds__(64) k_column_step(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                   const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp, float dvmax,
+                                                   float minvel, float maxvel, float* __restrict__ vels, float* __restrict__ dv, int* __restrict__ nused,
+                                                   double* __restrict__ chi2, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int nvx = nx - 2, M = nz - 1;
+    const long long ncol = (long long)nx * ny;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    if (bj >= ny - 2) return;
+    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    ColumnIn in;
+    in.M = M; in.K = K;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    const ColumnWork w = column_work(column_lds, M, K);
+    int n = 0;
+    double x2 = 0.0;
+    const int f = column_step(in, smooth, damp, dvmax, minvel, maxvel, w, vels + c, ncol, dv + c, ncol, &n, &x2, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n; chi2[c] = x2; flag[c] = f; }
+}
+
+}  // namespace
+
+void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                        float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return;
+    const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
+    hipLaunchKernelGGL(k_column_step, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, dvmax,
+                       minvel, maxvel, d_vels, d_dv, d_nused, d_chi2, d_flag);
+}
+
+}  // namespace dsa

@@ -291,6 +291,17 @@ struct Engine {
     int first_clamped_unit = -1;       // planned unit of the first of them
     int disp_group_shift = -1;         // lanes per Rayleigh curve = 2^shift; -1 = by the number of curves, 0 = one lane per curve
     int disp_layers_lds = -1;          // layer tables of k_dispersion: 1 LDS, 0 global scratch, -1 LDS when they fit
+    // depth step of the columns (dsa_columns_step, column_kernels.hip).  One mark per map and per kernel slot: what a
+    // dispersion_run with kernels wrote there (wave type, velocity kind, period) and whether it is of the present model -- set by the run,
+    // cleared by dispersion_commit, by the step and, for a map, by whatever else writes it.  The step needs map k and slot k fresh and alike.
+    struct DispMark { bool fresh = false; int iwave = 0, igr = 0; double t = 0.0; };
+    std::vector<DispMark> disp_map_mark, disp_slot_mark;
+    OwnedBuf<double> col_S, col_chi2;  // the combined sensitivities of all slots (M, K, ncol); the step's outputs
+    OwnedBuf<float> col_obs, col_wt, col_dv;
+    OwnedBuf<int> col_nused, col_flag;
+    int columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
+                     double* chi2, int* flag);
+    int dispersion_get_model(float* vels);
 
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;

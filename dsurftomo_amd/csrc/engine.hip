@@ -17,6 +17,7 @@
 #include "../../include/dsurftomo_amd.h"
 #include "engine.h"
 #include "spmv_state.h"
+#include "column_system.h"
 
 namespace dsa {
 
@@ -217,6 +218,8 @@ int Engine::dispersion_commit(bool host_copy)
     disp_fail_count = 0;
     disp_model_fail.assign((size_t)disp_nmodels, 0);
     disp_failures.clear();
+    disp_map_mark.assign((size_t)disp_nmaps * disp_nmodels, DispMark{});
+    disp_slot_mark.assign((size_t)disp_kmax_total, DispMark{});
     have_sens = false; sazi_ready = false;
     stats[DSA_STAT_MS_DISPERSION] = 0.0;
     stats[DSA_STAT_CURVES] = 0.0;
@@ -297,6 +300,13 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
     HIP_TRY(this, hipEventElapsedTime(&ms, events[1], events[2]));
     stats[DSA_STAT_MS_DISPERSION] += ms;
     stats[DSA_STAT_CURVES] += (double)nlanes;
+    if (!models)       // (what the maps and the kernel slots now hold, for dsa_columns_step; a run without kernels leaves a map no slot answers for)
+        for (int q = 0; q < nper; ++q) {
+            DispMark mark;
+            mark.fresh = with_kernels != 0; mark.iwave = iwave; mark.igr = igr; mark.t = t[q];
+            disp_map_mark[(size_t)(map_first + q)] = mark;
+            if (with_kernels) disp_slot_mark[(size_t)(sen_slot + q)] = mark;
+        }
     unsigned long long diag[2];
     HIP_TRY(this, hipMemcpy(diag, disp_diag.p, 16, hipMemcpyDeviceToHost));
     if (diag[0]) {
@@ -358,6 +368,7 @@ int Engine::dispersion_copy_map(int from, int to, int n)
     HIP_TRY(this, hipSetDevice(device));
     if (n) HIP_TRY(this, hipMemcpyAsync(pvstore.p + (size_t)to * ncol, pvstore.p + (size_t)from * ncol, (size_t)n * ncol * 8, hipMemcpyDeviceToDevice, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
+    for (int q = 0; q < n; ++q) disp_map_mark[(size_t)(to + q)].fresh = false;      // (no longer what its kernel slot was computed with)
     return 0;
 }
 
@@ -376,6 +387,70 @@ int Engine::dispersion_fetch(int map_first, int nper, double* pv, int with_kerne
             for (int i = 0; i < disp_nz; ++i)
                 HIP_TRY(this, hipMemcpy(dst[q] + (size_t)i * nper * ncol, srcs[q] + ((size_t)i * disp_kmax_total + sen_slot) * ncol, (size_t)nper * ncol * 8, hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// dsa_columns_step: one Gauss-Newton step of every interior column of the resident model towards the maps obs, from
+// the curves and depth kernels the dispersion runs left on the device.  Everything is checked before the device is touched.  The combined
+// sensitivities of all slots go to a buffer of the step's own (Srow, which the Frechet rows read, is not written); k_column_step moves
+// vels_d where it lies; h_vels follows, the marks are cleared: the next step needs new runs, which see the stepped model.
+int Engine::columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
+                         double* chi2, int* flag)
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "columns_step: call dsa_dispersion_begin and dsa_dispersion_run (with kernels) first"); return DSA_ERR_STATE; }
+    if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "columns_step: the dispersion stage holds %d models, the step moves one", disp_nmodels); return DSA_ERR_STATE; }
+    if (disp_nmaps != disp_kmax_total) { fail(DSA_ERR_STATE, "columns_step: the stage holds %d maps and %d kernel slots, the step needs one slot per map", disp_nmaps, disp_kmax_total); return DSA_ERR_STATE; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    if (nmaps_in != K) { fail(DSA_ERR_ARGUMENT, "columns_step: %d maps given, the stage holds %d", nmaps_in, K); return DSA_ERR_ARGUMENT; }
+    if (K > kColumnMaxK || M > kColumnMaxM || disp_nx < 3 || disp_ny < 3) { fail(DSA_ERR_ARGUMENT, "columns_step: %d maps (at most %d) on a %d x %d grid (at least 3 x 3)", K, kColumnMaxK, disp_nx, disp_ny); return DSA_ERR_ARGUMENT; }
+    if (!obs) { fail(DSA_ERR_ARGUMENT, "columns_step: obs is required"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(damp) || damp <= 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: damp %g must be finite and > 0", (double)damp); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(smooth) || smooth < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: smooth %g must be finite and >= 0", (double)smooth); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(dvmax) || dvmax <= 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: dvmax %g must be finite and > 0", (double)dvmax); return DSA_ERR_ARGUMENT; }
+    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "columns_step: minvel %g > maxvel %g", (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    for (size_t q = 0; q < nobs; ++q) {
+        if (!std::isfinite(obs[q])) { fail(DSA_ERR_ARGUMENT, "columns_step: obs[%zu] is not finite", q); return DSA_ERR_ARGUMENT; }
+        if (wt && !(std::isfinite(wt[q]) && wt[q] >= 0.0f)) { fail(DSA_ERR_ARGUMENT, "columns_step: wt[%zu] = %g must be finite and >= 0", q, (double)wt[q]); return DSA_ERR_ARGUMENT; }
+    }
+    for (int k = 0; k < K; ++k) {
+        const DispMark &a = disp_map_mark[(size_t)k], &b = disp_slot_mark[(size_t)k];
+        if (!a.fresh || !b.fresh) { fail(DSA_ERR_STATE, "columns_step: map / kernel slot %d has not been run with kernels since %s", k, "dsa_dispersion_begin or the last step"); return DSA_ERR_STATE; }
+        if (a.iwave != b.iwave || a.igr != b.igr || a.t != b.t) { fail(DSA_ERR_STATE, "columns_step: map %d and kernel slot %d hold different curves (wave %d / %d, kind %d / %d, period %g / %g)", k, k, a.iwave, b.iwave, a.igr, b.igr, a.t, b.t); return DSA_ERR_STATE; }
+    }
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, ncol * M) || ensure(col_nused, ncol) ||
+        ensure(col_chi2, ncol) || ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernel runs on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, ncol * M * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
+    launch_column_step(disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, dvmax, minvel, maxvel, vels_d.p,
+                       col_dv.p, col_nused.p, col_chi2.p, col_flag.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    for (DispMark& m : disp_map_mark) m.fresh = false;
+    for (DispMark& m : disp_slot_mark) m.fresh = false;
+    h_vels.resize(ncol * disp_nz);
+    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
+    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, ncol * M * 4, hipMemcpyDeviceToHost, stream));
+    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int Engine::dispersion_get_model(float* vels)
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model: call dsa_dispersion_begin first"); return DSA_ERR_STATE; }
+    if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "dispersion_get_model: the dispersion stage holds %d models", disp_nmodels); return DSA_ERR_STATE; }
+    HIP_TRY(this, hipSetDevice(device));
+    HIP_TRY(this, hipMemcpyAsync(vels, vels_d.p, (size_t)disp_nx * disp_ny * disp_nz * 4, hipMemcpyDeviceToHost, stream));       // (on the engine's stream: behind the step)
+    HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -1840,6 +1915,19 @@ int dsa_get_maps(dsa_engine* e, int nmaps, float* velv)
 {
     if (!e || !velv) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->get_maps(nmaps, velv);
+}
+
+int dsa_columns_step(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv,
+                     int* nused, double* chi2, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_step(nmaps, obs, wt, smooth, damp, dvmax, minvel, maxvel, dv, nused, chi2, flag);
+}
+
+int dsa_dispersion_get_model(dsa_engine* e, float* vels)
+{
+    if (!e || !vels) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->dispersion_get_model(vels);
 }
 
 int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on)

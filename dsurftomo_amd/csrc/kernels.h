@@ -301,6 +301,11 @@ void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, i
 void launch_to_float(const double* d_in, float* d_out, size_t n, hipStream_t stream);
 // velv[m][jj][kk + 1] += clamp(dv[m][jj - 1][kk], -dvmax, dvmax), clamped to [minvel, maxvel], for the interior vertices of nm maps; the outer ring keeps its values (stage_kernels.hip)
 void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_velv, hipStream_t stream);
+// column_kernels.hip: the depth step of the interior columns of the (nz, ny, nx) model d_vels in place, one wavefront per
+// column.  d_obs / d_wt (null: 1): (K, ncol) fp32; d_pv: (K, ncol); d_S: (nz - 1, K, ncol), launch_sen_combine's; d_dv: (nz - 1, ncol);
+// d_nused / d_chi2 / d_flag: (ncol).  Only interior columns are written: the caller zeroes the outputs for the ring.  nz <= 64, K <= 60.
+void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                        float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

@@ -102,6 +102,8 @@ def declare_solvers(L):
     L.dsa_iteration_system_maps_device.argtypes = [_vp] + [_i32] * 5 + [_vp] * 2 + [_f32] * 3 + [_vp] * 6
     L.dsa_update_maps.argtypes = [_vp, _i32, _vp] + [_f32] * 3
     L.dsa_get_maps.argtypes = [_vp, _i32, _vp]
+    L.dsa_columns_step.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 5 + [_vp] * 4
+    L.dsa_dispersion_get_model.argtypes = [_vp, _vp]
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -415,6 +417,31 @@ class Engine:
 
     def kernels_from_dispersion(self):
         self._check(self._L.dsa_kernels_from_dispersion(self._h))
+
+    def columns_step(self, obs, wt, smooth, damp, dvmax, minvel, maxvel):
+        """dsa_columns_step on the model of dispersion_begin: obs (nmaps, ny * nx) fp32 maps in get_maps' layout, wt the same shape or None
+        (all 1).  Returns dict(dv (nz - 1, ny * nx) fp32, nused (ny * nx) int32, chi2 (ny * nx) fp64, flag (ny * nx) int32).  ValueError when
+        obs and wt differ in size or do not fill whole maps: the library reads nmaps * nx * ny values of each."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        obs = np.ascontiguousarray(obs, np.float32)
+        if ncol == 0 or obs.size == 0 or obs.size % ncol:
+            raise ValueError("columns_step: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
+        if wt is not None:
+            wt = np.ascontiguousarray(wt, np.float32)
+            if wt.size != obs.size:
+                raise ValueError("columns_step: wt holds %d values, obs %d" % (wt.size, obs.size))
+        dv = np.zeros((nz - 1, ncol), np.float32); nused = np.zeros(ncol, np.int32); chi2 = np.zeros(ncol); flag = np.zeros(ncol, np.int32)
+        self._check(self._L.dsa_columns_step(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(dvmax),
+                                             float(minvel), float(maxvel), _p(dv), _p(nused), _p(chi2), _p(flag)))
+        return dict(dv=dv, nused=nused, chi2=chi2, flag=flag)
+
+    def dispersion_get_model(self):
+        """the dispersion stage's resident model, (nz, ny, nx) fp32 as dispersion_begin takes it"""
+        nx, ny, nz = self._disp
+        out = np.zeros((nz, ny, nx), np.float32)
+        self._check(self._L.dsa_dispersion_get_model(self._h, out.ctypes.data_as(_vp)))
+        return out
 
     # ---- matrix-vector products of the inversion step (reference aprod) ---------------------------
     def spmv_load(self, m, n, rw, row, col):

@@ -436,6 +436,29 @@ int dsa_iteration_system_maps_device(dsa_engine* e, int nx, int ny, int nmaps, i
 int dsa_update_maps(dsa_engine* e, int nmaps, const float* dv, float dvmax, float minvel, float maxvel);
 int dsa_get_maps(dsa_engine* e, int nmaps, float* velv);
 
+/* dsa_columns_step: the depth inversion of the period maps, one Gauss-Newton step of every interior column's Vs(z) on the device (extension;
+ * DESIGN.md 21).  The dispersion stage holds one model, as many maps as kernel slots (nmaps == nmaps_total == kmax_total of
+ * dsa_dispersion_begin, at most 60), and every map k and kernel slot k has been written by a dsa_dispersion_run with_kernels = 1 (sen_slot ==
+ * map_first) since dsa_dispersion_begin or since the last step.  obs: the maps, nmaps*nx*ny floats in dsa_get_maps' layout; wt: as many
+ * weights, or NULL for 1.  Datum k of a column is used iff wt > 0, obs > 0 and the column's own curve pv > 0 (0: no root).  Per column, with
+ * M = nz-1 unknowns (the bottom depth is kept), S = d c / d Vs of dsa_kernels_from_dispersion's rule, a = (double)wt, g = a S,
+ * rho = a ((double)obs - pv):  (G^T G + smooth^2 L^T L + damp^2 I) delta = G^T rho,  L the first-difference Laplacian (-1, 2, -1) closed by
+ * the rows (1, -1) and (-1, 1), solved by an L D L^T factorisation without square roots, everything fp64 and every sum sequential; then in fp32
+ * s = (float)delta clipped to +-dvmax, v = v + s clamped to [minvel, maxvel], dsa_model_update's comparisons.  The model is stepped where it
+ * lies: the next dsa_dispersion_run works on it.  The outer ring of columns keeps its values.
+ *   dv     (nz-1)*nx*ny floats, depth slowest like the model: the clipped step, 0 where the column was left alone
+ *   nused  nx*ny: data used;  chi2  nx*ny: sum of rho^2 before the step;  flag  nx*ny: 0 stepped (or ring), 1 a pivot of the
+ *          factorisation was not finite or <= 0 (column left alone), 2 no datum used (column left alone).  Any of the four may be NULL.
+ * The step clears the marks of all maps and slots: a second step without new runs is DSA_ERR_STATE.
+ * Errors, all found before the device is touched: DSA_ERR_STATE (no dispersion stage, several models, maps != slots, a map or slot not run
+ * with kernels since begin / the last step, or map k and slot k written by different runs), DSA_ERR_ARGUMENT (nmaps is not the stage's, a
+ * grid without interior columns, obs NULL or not finite, a wt negative or not finite, damp <= 0, smooth < 0, dvmax <= 0, minvel > maxvel).
+ * dsa_dispersion_get_model: the stage's resident model, nx*ny*nz floats in dsa_dispersion_begin's layout (DSA_ERR_STATE without a stage or
+ * with several models). */
+int dsa_columns_step(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel,
+                     float maxvel, float* dv, int* nused, double* chi2, int* flag);
+int dsa_dispersion_get_model(dsa_engine* e, float* vels);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);
