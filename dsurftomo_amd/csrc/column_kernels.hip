@@ -3,8 +3,10 @@
 // instruction.  The work arrays lie in LDS, sized by the launch for the case's (M, K): K * M doubles of weighted sensitivities, the packed
 // triangle of N (then L), and five short vectors -- 2.5 KB for the Taipei example (M = 8, K = 26: a CU's 160 KB hold more blocks than its
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
+// k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
 #include "kernels.h"
 #include "column_system.h"
+#include "column_resolution.h"
 
 namespace dsa {
 
@@ -40,6 +42,38 @@ __global__ void __launch_bounds__(64) k_column_step(int nx, int ny, int nz, int 
     if (threadIdx.x == 0) { nused[c] = n; chi2[c] = x2; flag[c] = f; }
 }
 
+// k_column_resolution: column_resolution.h on every interior column, the launch shape and the column of a block as
+// above.  The work arrays of the step and T lie in dynamic LDS: column_resolution_doubles(M, K) doubles -- 4.1 KB for the Taipei example
+// (M = 8, K = 26), 77.2 KB at the stage's limits (M = 63, K = 60: two columns per CU), which the launcher has to ask for.  depz: the nz
+// depths of the model; measures: (4, M, ncol); leverage: (K, ncol); trace / nused / flag: (ncol); R: null or (M, M, ncol).
+__global__ void __launch_bounds__(64) k_column_resolution(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                         const double* __restrict__ pv, const double* __restrict__ S, const float* __restrict__ depz,
+                                                         float smooth, float damp, double* __restrict__ measures, double* __restrict__ leverage,
+                                                         double* __restrict__ trace, double* __restrict__ R, int* __restrict__ nused, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int nvx = nx - 2, M = nz - 1;
+    const long long ncol = (long long)nx * ny;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    if (bj >= ny - 2) return;
+    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    ColumnIn in;
+    in.M = M; in.K = K;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    ColumnResOut out;
+    out.measures = measures + c; out.m_qstride = (long long)M * ncol; out.m_jstride = ncol;
+    out.leverage = leverage + c; out.h_stride = ncol;
+    out.R = R ? R + c : nullptr; out.r_stride = ncol;
+    const ColumnWork w = column_work(column_lds, M, K);
+    int n = 0;
+    double tr = 0.0;
+    const int f = column_resolution(in, depz, smooth, damp, w, column_resolution_t(column_lds, M, K), out, &tr, &n, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n; trace[c] = tr; flag[c] = f; }
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -49,6 +83,30 @@ void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const
     const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
     hipLaunchKernelGGL(k_column_step, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, dvmax,
                        minvel, maxvel, d_vels, d_dv, d_nused, d_chi2, d_flag);
+}
+
+size_t column_resolution_lds_bytes(int nz, int K) { return column_resolution_doubles(nz - 1, K) * sizeof(double); }
+
+// 0: launched; 1: the case needs more dynamic LDS than a block of this device may have (*limit_out); 2: the device refused the attribute
+int launch_column_resolution(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S,
+                             const float* d_depz, float smooth, float damp, double* d_measures, double* d_leverage, double* d_trace, double* d_R, int* d_nused,
+                             int* d_flag, hipStream_t stream, int* limit_out)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
+    const size_t lds = column_resolution_lds_bytes(nz, K);
+    if (lds > 64 * 1024) {          // (above what a block gets without asking; the attribute is per device: set every time)
+        int limit = 0;
+        if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
+        if (limit_out) *limit_out = limit;
+        if (lds > (size_t)limit) return 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_column_resolution), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return 2;
+        }
+    }
+    hipLaunchKernelGGL(k_column_resolution, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, d_depz, smooth,
+                       damp, d_measures, d_leverage, d_trace, d_R, d_nused, d_flag);
+    return 0;
 }
 
 }  // namespace dsa

@@ -301,6 +301,14 @@ struct Engine {
     OwnedBuf<int> col_nused, col_flag;
     int columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
                      double* chi2, int* flag);
+    // what dsa_columns_step and dsa_columns_resolution share (who: the caller's name in the messages): the state and the arguments both have,
+    // in the step's order of refusals; step: also dvmax, minvel, maxvel
+    int columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel, float maxvel);
+    // depth resolution of the columns (dsa_columns_resolution, k_column_resolution): reads what the step reads, changes nothing
+    OwnedBuf<double> col_meas, col_lev, col_trace, col_R;
+    OwnedBuf<float> col_depz;
+    int columns_resolution(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* measures, double* leverage, double* trace, double* R,
+                           int* nused, int* flag);
     int dispersion_get_model(float* vels);
 
     // optional growing host destination of the COO rows (used when several engines share one call)

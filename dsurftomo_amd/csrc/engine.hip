@@ -390,6 +390,35 @@ int Engine::dispersion_fetch(int map_first, int nper, double* pv, int with_kerne
     return 0;
 }
 
+// What dsa_columns_step and dsa_columns_resolution ask of the stage and of the arguments both have, one copy, in the step's order of
+// refusals; nothing on the device is touched.
+int Engine::columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel,
+                          float maxvel)
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "%s: call dsa_dispersion_begin and dsa_dispersion_run (with kernels) first", who); return DSA_ERR_STATE; }
+    if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "%s: the dispersion stage holds %d models, the step moves one", who, disp_nmodels); return DSA_ERR_STATE; }
+    if (disp_nmaps != disp_kmax_total) { fail(DSA_ERR_STATE, "%s: the stage holds %d maps and %d kernel slots, the step needs one slot per map", who, disp_nmaps, disp_kmax_total); return DSA_ERR_STATE; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    if (nmaps_in != K) { fail(DSA_ERR_ARGUMENT, "%s: %d maps given, the stage holds %d", who, nmaps_in, K); return DSA_ERR_ARGUMENT; }
+    if (K > kColumnMaxK || M > kColumnMaxM || disp_nx < 3 || disp_ny < 3) { fail(DSA_ERR_ARGUMENT, "%s: %d maps (at most %d) on a %d x %d grid (at least 3 x 3)", who, K, kColumnMaxK, disp_nx, disp_ny); return DSA_ERR_ARGUMENT; }
+    if (!obs) { fail(DSA_ERR_ARGUMENT, "%s: obs is required", who); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(damp) || damp <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: damp %g must be finite and > 0", who, (double)damp); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(smooth) || smooth < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: smooth %g must be finite and >= 0", who, (double)smooth); return DSA_ERR_ARGUMENT; }
+    if (step && (!std::isfinite(dvmax) || dvmax <= 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: dvmax %g must be finite and > 0", who, (double)dvmax); return DSA_ERR_ARGUMENT; }
+    if (step && !(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "%s: minvel %g > maxvel %g", who, (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    const size_t nobs = (size_t)disp_nx * disp_ny * K;
+    for (size_t q = 0; q < nobs; ++q) {
+        if (!std::isfinite(obs[q])) { fail(DSA_ERR_ARGUMENT, "%s: obs[%zu] is not finite", who, q); return DSA_ERR_ARGUMENT; }
+        if (wt && !(std::isfinite(wt[q]) && wt[q] >= 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: wt[%zu] = %g must be finite and >= 0", who, q, (double)wt[q]); return DSA_ERR_ARGUMENT; }
+    }
+    for (int k = 0; k < K; ++k) {
+        const DispMark &a = disp_map_mark[(size_t)k], &b = disp_slot_mark[(size_t)k];
+        if (!a.fresh || !b.fresh) { fail(DSA_ERR_STATE, "%s: map / kernel slot %d has not been run with kernels since %s", who, k, "dsa_dispersion_begin or the last step"); return DSA_ERR_STATE; }
+        if (a.iwave != b.iwave || a.igr != b.igr || a.t != b.t) { fail(DSA_ERR_STATE, "%s: map %d and kernel slot %d hold different curves (wave %d / %d, kind %d / %d, period %g / %g)", who, k, k, a.iwave, b.iwave, a.igr, b.igr, a.t, b.t); return DSA_ERR_STATE; }
+    }
+    return 0;
+}
+
 // dsa_columns_step: one Gauss-Newton step of every interior column of the resident model towards the maps obs, from
 // the curves and depth kernels the dispersion runs left on the device.  Everything is checked before the device is touched.  The combined
 // sensitivities of all slots go to a buffer of the step's own (Srow, which the Frechet rows read, is not written); k_column_step moves
@@ -397,27 +426,9 @@ int Engine::dispersion_fetch(int map_first, int nper, double* pv, int with_kerne
 int Engine::columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
                          double* chi2, int* flag)
 {
-    if (!disp_ready) { fail(DSA_ERR_STATE, "columns_step: call dsa_dispersion_begin and dsa_dispersion_run (with kernels) first"); return DSA_ERR_STATE; }
-    if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "columns_step: the dispersion stage holds %d models, the step moves one", disp_nmodels); return DSA_ERR_STATE; }
-    if (disp_nmaps != disp_kmax_total) { fail(DSA_ERR_STATE, "columns_step: the stage holds %d maps and %d kernel slots, the step needs one slot per map", disp_nmaps, disp_kmax_total); return DSA_ERR_STATE; }
+    if (int rc = columns_front("columns_step", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
     const int K = disp_nmaps, M = disp_nz - 1;
-    if (nmaps_in != K) { fail(DSA_ERR_ARGUMENT, "columns_step: %d maps given, the stage holds %d", nmaps_in, K); return DSA_ERR_ARGUMENT; }
-    if (K > kColumnMaxK || M > kColumnMaxM || disp_nx < 3 || disp_ny < 3) { fail(DSA_ERR_ARGUMENT, "columns_step: %d maps (at most %d) on a %d x %d grid (at least 3 x 3)", K, kColumnMaxK, disp_nx, disp_ny); return DSA_ERR_ARGUMENT; }
-    if (!obs) { fail(DSA_ERR_ARGUMENT, "columns_step: obs is required"); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(damp) || damp <= 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: damp %g must be finite and > 0", (double)damp); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(smooth) || smooth < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: smooth %g must be finite and >= 0", (double)smooth); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(dvmax) || dvmax <= 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step: dvmax %g must be finite and > 0", (double)dvmax); return DSA_ERR_ARGUMENT; }
-    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "columns_step: minvel %g > maxvel %g", (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
     const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
-    for (size_t q = 0; q < nobs; ++q) {
-        if (!std::isfinite(obs[q])) { fail(DSA_ERR_ARGUMENT, "columns_step: obs[%zu] is not finite", q); return DSA_ERR_ARGUMENT; }
-        if (wt && !(std::isfinite(wt[q]) && wt[q] >= 0.0f)) { fail(DSA_ERR_ARGUMENT, "columns_step: wt[%zu] = %g must be finite and >= 0", q, (double)wt[q]); return DSA_ERR_ARGUMENT; }
-    }
-    for (int k = 0; k < K; ++k) {
-        const DispMark &a = disp_map_mark[(size_t)k], &b = disp_slot_mark[(size_t)k];
-        if (!a.fresh || !b.fresh) { fail(DSA_ERR_STATE, "columns_step: map / kernel slot %d has not been run with kernels since %s", k, "dsa_dispersion_begin or the last step"); return DSA_ERR_STATE; }
-        if (a.iwave != b.iwave || a.igr != b.igr || a.t != b.t) { fail(DSA_ERR_STATE, "columns_step: map %d and kernel slot %d hold different curves (wave %d / %d, kind %d / %d, period %g / %g)", k, k, a.iwave, b.iwave, a.igr, b.igr, a.t, b.t); return DSA_ERR_STATE; }
-    }
     HIP_TRY(this, hipSetDevice(device));
     if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, ncol * M) || ensure(col_nused, ncol) ||
         ensure(col_chi2, ncol) || ensure(col_flag, ncol)) return status;
@@ -440,6 +451,49 @@ int Engine::columns_step(int nmaps_in, const float* obs, const float* wt, float 
     if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
     if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_resolution: the resolution measures of the same columns from the same resident curves and kernels.  The
+// stage is read only: no mark is cleared, vels_d, h_vels and Srow stay, so a dsa_columns_step after it gives the bits it would have given.
+int Engine::columns_resolution(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* measures, double* leverage, double* trace,
+                               double* R, int* nused, int* flag)
+{
+    if (int rc = columns_front("columns_resolution", nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f)) return rc;
+    if (!measures || !leverage || !trace || !nused || !flag) { fail(DSA_ERR_ARGUMENT, "columns_resolution: measures, leverage, trace, nused and flag are required"); return DSA_ERR_ARGUMENT; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_depz, (size_t)disp_nz) || ensure(col_meas, 4 * ncol * M) ||
+        ensure(col_lev, nobs) || ensure(col_trace, ncol) || (R && ensure(col_R, ncol * M * M)) || ensure(col_nused, ncol) || ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_depz.p, h_depz.data(), (size_t)disp_nz * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernel runs on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_meas.p, 0, 4 * ncol * M * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_lev.p, 0, nobs * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_trace.p, 0, ncol * 8, stream));
+    if (R) HIP_TRY(this, hipMemsetAsync(col_R.p, 0, ncol * M * M * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
+    int limit = 0;
+    const int rc = launch_column_resolution(device, disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_depz.p, smooth, damp,
+                                            col_meas.p, col_lev.p, col_trace.p, R ? col_R.p : nullptr, col_nused.p, col_flag.p, stream, &limit);
+    if (rc) {
+        HIP_TRY(this, hipStreamSynchronize(stream));
+        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_resolution: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", M, K, column_resolution_lds_bytes(disp_nz, K), limit);
+        else fail(DSA_ERR_DEVICE, "columns_resolution: the device refuses %zu bytes of dynamic LDS per workgroup", column_resolution_lds_bytes(disp_nz, K));
+        return DSA_ERR_DEVICE;
+    }
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(measures, col_meas.p, 4 * ncol * M * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(leverage, col_lev.p, nobs * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(trace, col_trace.p, ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (R) HIP_TRY(this, hipMemcpyAsync(R, col_R.p, ncol * M * M * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
@@ -1922,6 +1976,13 @@ int dsa_columns_step(dsa_engine* e, int nmaps, const float* obs, const float* wt
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_step(nmaps, obs, wt, smooth, damp, dvmax, minvel, maxvel, dv, nused, chi2, flag);
+}
+
+int dsa_columns_resolution(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* measures, double* leverage,
+                           double* trace, double* R, int* nused, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_resolution(nmaps, obs, wt, smooth, damp, measures, leverage, trace, R, nused, flag);
 }
 
 int dsa_dispersion_get_model(dsa_engine* e, float* vels)

@@ -306,6 +306,14 @@ void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvma
 // d_nused / d_chi2 / d_flag: (ncol).  Only interior columns are written: the caller zeroes the outputs for the ring.  nz <= 64, K <= 60.
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
                         float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
+// The depth resolution of the same columns, nothing stepped: d_depz the nz depths; d_measures (4, nz - 1, ncol): R_jj, m1,
+// m2, var; d_leverage (K, ncol); d_trace / d_nused / d_flag (ncol); d_R null or (nz - 1, nz - 1, ncol).  Only interior columns are written.
+// column_resolution_lds_bytes: the dynamic LDS of a block.  Returns 0 launched, 1 the case needs more LDS than a block of the device may
+// have (*limit_out: what it offers), 2 the device refused hipFuncAttributeMaxDynamicSharedMemorySize -- nothing is launched then.
+size_t column_resolution_lds_bytes(int nz, int K);
+int launch_column_resolution(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S,
+                             const float* d_depz, float smooth, float damp, double* d_measures, double* d_leverage, double* d_trace, double* d_R, int* d_nused,
+                             int* d_flag, hipStream_t stream, int* limit_out);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

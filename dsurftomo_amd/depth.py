@@ -1,7 +1,7 @@
 """Depth inversion of the period maps: per-column Vs(z) Gauss-Newton steps on the device.
 
     python -m dsurftomo_amd.depth <directory with DSurfTomo.in, the data file and MOD> [--maps FILE] [--iterations N] [--smooth L] [--damp D]
-                                  [--dvmax V] [--min-dws X] [--out DIR]
+                                  [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -19,6 +19,16 @@ The log gives, per iteration, the data used, the flagged columns (1: the factori
 sqrt(sum chi2 / sum nused) before the step.  <input>Depth.dat (write_depth / read_depth): longitude, latitude, depth, Vs of every node, 17
 significant digits.  <input>DepthFit.dat (write_fit / read_fit): per column longitude, latitude, the data used, the rms before the first and
 before the last step, and the flag of the last step.
+
+--resolution: after the last step the runs are done once more on the final model and columns_resolution asks the
+regularised normal matrix of every column, with the loop's weights, --smooth and --damp, how far its answer can be trusted.
+<input>DepthResolution.dat (write_resolution / read_resolution): per node above the bottom depth longitude, latitude, depth, R_jj (the
+diagonal of the model resolution matrix), the vertical length sqrt(m2 / m1) of the node's point-spread function in km (0 where m1 = 0),
+sd_unit = sqrt(var) (the standard deviation for unit variance of the weighted data) and sd = S sd_unit, S = --sigma in km/s or, by default,
+the rms before the last step.  <input>DepthLeverage.dat (write_leverage / read_leverage): per column and period in slot order longitude,
+latitude, wave type, velocity kind, period and the leverage h_k.  The log gives the flagged columns, the median and range of the trace of R
+over the others, and the depth below which the median R_jj falls under 0.1.  column_resolution_twin is the NumPy twin
+(csrc/column_resolution.h is the arithmetic).
 
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
@@ -39,6 +49,8 @@ DEFAULT_DVMAX = 0.5
 
 _F64 = lambda *names: tuple((n, "%.17g", "f64") for n in names)
 DEPTH_TABLE = (True, _F64("lon", "lat", "depth", "vs"))
+RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", "rjj", "length", "sd_unit", "sd"))
+LEVERAGE_TABLE = (True, _F64("lon", "lat") + (("wave", "%d", "int"), ("kind", "%d", "int")) + _F64("period", "leverage"))
 FIT_TABLE = (True, _F64("lon", "lat") + (("nused", "%d", "int"),) + _F64("rms_first", "rms_last") + (("flag", "%d", "int"),))
 
 
@@ -60,6 +72,52 @@ def column_ltl(M):
     """L^T L of column_l(M), (M, M) integers"""
     L = column_l(M)
     return np.rint(L.T @ L).astype(np.int64)
+
+
+def _twin_normal(G, used, rho, lam2, mu2):
+    """N = G^T G + lam2 L^T L + mu2 I and b = G^T rho, the sums over the used k ascending from 0.0 (column_system.h: column_assemble)"""
+    K, M = G.shape
+    N = np.zeros((M, M)); b = np.zeros(M)
+    for k in np.flatnonzero(used):
+        N = N + np.outer(G[k], G[k])
+        b = b + G[k] * rho[k]
+    N = N + lam2 * column_ltl(M).astype(np.float64)
+    N[np.diag_indices(M)] = N[np.diag_indices(M)] + mu2
+    return N, b
+
+
+def _twin_factor(N):
+    """N = L D L^T without a square root, column by column, every sum subtracted term by term with p ascending (column_factor).  Returns
+    (L (M, M) strictly lower, d (M)), or None at a pivot that is not finite or <= 0."""
+    M = N.shape[0]
+    Lm = np.zeros((M, M)); d = np.zeros(M)
+    for j in range(M):
+        v = Lm[j, :j] * d[:j]
+        col = N[j:, j].copy()                                          # (entry 0: the pivot; the others: column j below it)
+        for p in range(j):
+            col = col - Lm[j:, p] * v[p]
+        if not (np.isfinite(col[0]) and col[0] > 0):
+            return None
+        d[j] = col[0]
+        Lm[j + 1:, j] = col[1:] / d[j]
+    return Lm, d
+
+
+def _twin_solve(Lm, d, b):
+    """L D L^T x = b (column_solve): forward with p ascending, the division by d, back with i descending and p ascending.  b: (M) or (M, n),
+    one right-hand side per column."""
+    M = len(d)
+    b = np.asarray(b, np.float64)
+    x = b.reshape(M, -1).copy()
+    for p in range(M - 1):
+        x[p + 1:] = x[p + 1:] - Lm[p + 1:, p, None] * x[p]
+    x = x / d[:, None]
+    for i in range(M - 2, -1, -1):
+        s = x[i].copy()
+        for p in range(i + 1, M):
+            s = s - Lm[p, i] * x[p]
+        x[i] = s
+    return x.reshape(b.shape)
 
 
 def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, solver="ldlt", n_override=None):
@@ -93,35 +151,14 @@ def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, 
         rhs = np.concatenate([rho[used], np.zeros(A.shape[0] - int(used.sum()))])
         delta = np.linalg.lstsq(A, rhs, rcond=None)[0]
     else:
-        N = np.zeros((M, M)); b = np.zeros(M)
-        for k in np.flatnonzero(used):
-            N = N + np.outer(G[k], G[k])
-            b = b + G[k] * rho[k]
-        N = N + lam2 * column_ltl(M).astype(np.float64)
-        N[np.diag_indices(M)] = N[np.diag_indices(M)] + mu2
+        N, b = _twin_normal(G, used, rho, lam2, mu2)
         if n_override is not None:
             N = np.array(n_override, np.float64)
-        Lm = np.zeros((M, M)); d = np.zeros(M)
-        for j in range(M):
-            v = Lm[j, :j] * d[:j]
-            col = N[j:, j].copy()                                      # (entry 0: the pivot; the others: column j below it)
-            for p in range(j):
-                col = col - Lm[j:, p] * v[p]
-            if not (np.isfinite(col[0]) and col[0] > 0):
-                out["flag"] = 1
-                return out
-            d[j] = col[0]
-            Lm[j + 1:, j] = col[1:] / d[j]
-        x = b.copy()
-        for p in range(M - 1):
-            x[p + 1:] = x[p + 1:] - Lm[p + 1:, p] * x[p]
-        x = x / d
-        for i in range(M - 2, -1, -1):
-            s = x[i]
-            for p in range(i + 1, M):
-                s = s - Lm[p, i] * x[p]
-            x[i] = s
-        delta = x
+        factor = _twin_factor(N)
+        if factor is None:
+            out["flag"] = 1
+            return out
+        delta = _twin_solve(*factor, b)
     s = delta.astype(f)
     dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
     with np.errstate(invalid="ignore"):
@@ -132,6 +169,69 @@ def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, 
         v = np.where(v > maxvel, maxvel, v)
     vels[:M] = v
     out.update(delta=delta, dv=s.astype(f))
+    return out
+
+
+def _resolution_measures(T, G, used, depz):
+    """R = T^T G and what column_resolution.h reduces from it, every sum from 0.0 in the header's order: over the used k ascending, over l
+    and j ascending.  Returns dict(R (M, M), measures (4, M): R_jj, m1, m2, var; leverage (K); trace)."""
+    K, M = G.shape
+    z = np.asarray(depz, np.float32)[:M].astype(np.float64)
+    R = np.zeros((M, M)); var = np.zeros(M)
+    for k in np.flatnonzero(used):
+        R = R + np.outer(T[k], G[k])
+        var = var + T[k] * T[k]
+    m1 = np.zeros(M); m2 = np.zeros(M)
+    for l in range(M):
+        r2 = R[l] * R[l]
+        dz = z[l] - z
+        m1 = m1 + r2
+        m2 = m2 + r2 * (dz * dz)
+    h = np.zeros(K)
+    for l in range(M):
+        h = h + G[:, l] * T[:, l]
+    h[~used] = 0.0
+    trace = 0.0
+    for j in range(M):
+        trace = trace + R[j, j]
+    return dict(R=R, measures=np.stack([np.diag(R).copy(), m1, m2, var]), leverage=h, trace=float(trace))
+
+
+def column_resolution_twin(obs, wt, pv, S, depz, smooth, damp, n_override=None):
+    """dsa_columns_resolution on one column in NumPy (csrc/column_resolution.h).  obs, wt, pv, S as column_step_twin's; depz: the depths of
+    the unknowns (M or more, fp32).  N is built as column_step_twin builds it; row k of T (K, M) is the solution of N t = g_k through the
+    header's L D L^T order, rows of unused data 0; R = T^T G.  Returns dict(T, R (M, M), measures (4, M): R_jj, m1, m2, var; leverage (K);
+    trace; nused; flag; other) -- every array 0 where the flag is 1 or 2.  other: the same figures (T, R, measures, leverage, trace) by
+    another algorithm, numpy.linalg.pinv of the stacked [diag(a) S; smooth L; damp I], whose first K columns are N^-1 G^T -- for the size
+    of the rounding error; None where the column is flagged.  n_override: an (M, M) matrix in place of the assembled N (tests)."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64)
+    K, M = S.shape
+    wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
+    used = (wt > 0) & (obs > 0) & (pv > 0)
+    a = wt.astype(np.float64)
+    out = dict(T=np.zeros((K, M)), R=np.zeros((M, M)), measures=np.zeros((4, M)), leverage=np.zeros(K), trace=0.0, nused=int(used.sum()), flag=0, other=None)
+    if out["nused"] == 0:
+        out["flag"] = 2
+        return out
+    G = np.zeros((K, M))
+    G[used] = a[used, None] * S[used]
+    lam2, mu2 = float(f(smooth)) * float(f(smooth)), float(f(damp)) * float(f(damp))
+    N, _ = _twin_normal(G, used, np.zeros(K), lam2, mu2)
+    if n_override is not None:
+        N = np.array(n_override, np.float64)
+    factor = _twin_factor(N)
+    if factor is None:
+        out["flag"] = 1
+        return out
+    T = _twin_solve(*factor, G.T).T.copy()
+    T[~used] = 0.0
+    out.update(T=T, **_resolution_measures(T, G, used, depz))
+    if n_override is None:
+        A = np.vstack([G, float(f(smooth)) * column_l(M), float(f(damp)) * np.eye(M)])
+        T2 = np.linalg.pinv(A)[:, :K].T.copy()
+        T2[~used] = 0.0
+        out["other"] = dict(T=T2, **_resolution_measures(T2, G, used, depz))
     return out
 
 
@@ -176,14 +276,14 @@ def dws_weights(dws, min_dws):
 
 # ---- the loop ----
 
-def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None):
+def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None):
     """the driver's preconditions, checked before the library is loaded (ValueError)"""
     if iterations is not None and iterations < 1:
         raise ValueError("--iterations must be at least 1, not %r" % (iterations,))
     for name, v in (("--smooth", smooth), ("--min-dws", min_dws)):
         if v is not None and not (np.isfinite(v) and v >= 0):
             raise ValueError("%s must be finite and >= 0, not %r" % (name, v))
-    for name, v in (("--damp", damp), ("--dvmax", dvmax)):
+    for name, v in (("--damp", damp), ("--dvmax", dvmax), ("--sigma", sigma)):
         if v is not None and not (np.isfinite(v) and v > 0):
             raise ValueError("%s must be finite and > 0, not %r" % (name, v))
 
@@ -249,10 +349,96 @@ def read_fit(path):
     return io.read_table(path, FIT_TABLE)
 
 
+def psf_length(m1, m2):
+    """the vertical length sqrt(m2 / m1) of the point-spread functions, 0 where m1 = 0"""
+    m1 = np.asarray(m1, np.float64); m2 = np.asarray(m2, np.float64)
+    return np.sqrt(np.divide(m2, m1, out=np.zeros(m1.shape), where=m1 > 0))
+
+
+def write_resolution(path, c, measures, sigma):
+    """<input>DepthResolution.dat: measures (4, nz - 1, ny * nx) of columns_resolution, every node above the bottom depth: depth slowest,
+    then j, then i; sigma: the data's standard deviation S in km/s"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    m = np.asarray(measures, np.float64).reshape(4, nz - 1, ny, nx)
+    length = psf_length(m[1], m[2]); sd_unit = np.sqrt(m[3])
+    rows = []
+    for k in range(nz - 1):
+        for j in range(ny):
+            for i in range(nx):
+                lon, lat = _lonlat(c, i - 1, j - 1)
+                rows.append(dict(lon=float(lon), lat=float(lat), depth=float(c["depz"][k]), rjj=m[0, k, j, i], length=length[k, j, i], sd_unit=sd_unit[k, j, i],
+                                 sd=float(sigma) * sd_unit[k, j, i]))
+    io.write_table(path, RESOLUTION_TABLE, rows)
+
+
+def read_resolution(path):
+    return io.read_table(path, RESOLUTION_TABLE)
+
+
+def write_leverage(path, c, leverage):
+    """<input>DepthLeverage.dat: leverage (nmaps, ny * nx) of columns_resolution; one line per column (j, then i) and period in slot order"""
+    nx, ny = c["nx"], c["ny"]
+    per = maps.period_list(c)
+    h = np.asarray(leverage, np.float64).reshape(len(per), ny, nx)
+    rows = []
+    for j in range(ny):
+        for i in range(nx):
+            lon, lat = _lonlat(c, i - 1, j - 1)
+            for k, (wave, kind, t) in enumerate(per):
+                rows.append(dict(lon=float(lon), lat=float(lat), wave=int(wave), kind=int(kind), period=float(t), leverage=h[k, j, i]))
+    io.write_table(path, LEVERAGE_TABLE, rows)
+
+
+def read_leverage(path):
+    return io.read_table(path, LEVERAGE_TABLE)
+
+
+def resolution_summary(c, res):
+    """what the log says of columns_resolution's result: dict(flagged1, flagged2, columns (interior and not flagged), trace (median, min, max)
+    over them, depth: the shallowest depth from which the median R_jj over them stays under 0.1, or None)"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+    flag = np.asarray(res["flag"]).reshape(ny * nx)
+    ok = inner.ravel() & (flag == 0)
+    out = dict(flagged1=int((flag == 1).sum()), flagged2=int(((flag == 2) & inner.ravel()).sum()), columns=int(ok.sum()), trace=None, depth=None)
+    if ok.any():
+        tr = np.asarray(res["trace"])[ok]
+        out["trace"] = (float(np.median(tr)), float(tr.min()), float(tr.max()))
+        med = np.median(np.asarray(res["measures"])[0][:, ok], axis=1)
+        below = med < 0.1
+        k = nz - 1
+        while k > 0 and below[k - 1]:
+            k -= 1
+        out["depth"] = float(c["depz"][k]) if k < nz - 1 else None
+    return out
+
+
+def resolve(eng, c, plan, obs, wt, smooth, damp, sigma, out_dir, log=print):
+    """--resolution on an engine whose stage holds the final model: the runs of plan once more, columns_resolution, the two files, the log.
+    Returns dict(resolution: the call's result, sigma, summary, resolution_path, leverage_path)."""
+    for wave, kind, t, first in plan:
+        eng.dispersion_run(wave, kind, t, True, first, first)
+    res = eng.columns_resolution(obs, wt, smooth, damp)
+    rpath = os.path.join(out_dir, "DSurfTomo.inDepthResolution.dat")
+    lpath = os.path.join(out_dir, "DSurfTomo.inDepthLeverage.dat")
+    write_resolution(rpath, c, res["measures"], sigma)
+    write_leverage(lpath, c, res["leverage"])
+    sm = resolution_summary(c, res)
+    log(" depth resolution: %d columns resolved, %d flagged (%d not positive definite, %d without data)" %
+        (sm["columns"], sm["flagged1"] + sm["flagged2"], sm["flagged1"], sm["flagged2"]))
+    if sm["trace"] is not None:
+        log(" depth resolution: trace of R per column median %.4f, range %.4f to %.4f, of %d unknowns; the median R_jj %s" %
+            (sm["trace"] + (c["nz"] - 1, "stays under 0.1 from %g km down" % sm["depth"] if sm["depth"] is not None else "is 0.1 or more at the deepest unknown")))
+    log(" depth resolution: written to %s (sd for a data standard deviation of %.6f km/s), the leverages to %s" % (rpath, sigma, lpath))
+    return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
+
+
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
-        log=print):
-    """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat)"""
-    check(iterations, smooth, damp, dvmax, min_dws)
+        log=print, resolution=False, sigma=None):
+    """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
+    resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
+    last step."""
+    check(iterations, smooth, damp, dvmax, min_dws, sigma)
     c = io.load(directory)
     maps_file = os.path.join(out_dir, "DSurfTomo.inMaps.dat") if maps_file is None else maps_file
     obs, dws = maps_to_obs(maps.read_maps(maps_file), c)
@@ -267,6 +453,10 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
         eng.dispersion_begin(np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0)), c["depz"], c["minthk"], kmax, kmax)
         out = iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, float(c["minvel"]), float(c["maxvel"]), log)
         out["vels"] = eng.dispersion_get_model()
+        if resolution:
+            rms = out["history"][-1]["rms"]
+            log(" depth resolution: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
+            out.update(resolve(eng, c, plan, obs, wt, smooth, damp, rms if sigma is None else sigma, out_dir, log))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inDepth.dat")
@@ -287,6 +477,8 @@ def parser():
     ap.add_argument("--dvmax", type=float, default=DEFAULT_DVMAX, metavar="V", help="largest change of a node per iteration in km/s (default %g)" % DEFAULT_DVMAX)
     ap.add_argument("--min-dws", type=float, default=0.0, metavar="X", help="map vertices whose column DWS is below X get weight 0 (default 0: all count)")
     ap.add_argument("--out", default=".")
+    ap.add_argument("--resolution", action="store_true", help="after the last step write the resolution measures and the leverages of the final model")
+    ap.add_argument("--sigma", type=float, default=None, metavar="S", help="standard deviation of the map values in km/s for the sd column (default: the rms before the last step)")
     return ap
 
 
@@ -294,11 +486,11 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws)
+        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
-    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out)
+    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma)
     return 0
 
 

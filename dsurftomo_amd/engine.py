@@ -104,6 +104,7 @@ def declare_solvers(L):
     L.dsa_get_maps.argtypes = [_vp, _i32, _vp]
     L.dsa_columns_step.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 5 + [_vp] * 4
     L.dsa_dispersion_get_model.argtypes = [_vp, _vp]
+    L.dsa_columns_resolution.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 6
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -435,6 +436,28 @@ class Engine:
         self._check(self._L.dsa_columns_step(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(dvmax),
                                              float(minvel), float(maxvel), _p(dv), _p(nused), _p(chi2), _p(flag)))
         return dict(dv=dv, nused=nused, chi2=chi2, flag=flag)
+
+    def columns_resolution(self, obs, wt, smooth, damp, full=False):
+        """dsa_columns_resolution on the state columns_step needs, which it leaves as it is: obs and wt as columns_step's.  Returns
+        dict(measures (4, nz - 1, ny * nx): R_jj, m1, m2, var; leverage (nmaps, ny * nx); trace (ny * nx); nused, flag (ny * nx) int32; and
+        with full=True R (nz - 1, nz - 1, ny * nx), R[l, j] the response at depth l to unknown j), all fp64.  ValueError as columns_step."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        obs = np.ascontiguousarray(obs, np.float32)
+        if ncol == 0 or obs.size == 0 or obs.size % ncol:
+            raise ValueError("columns_resolution: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
+        if wt is not None:
+            wt = np.ascontiguousarray(wt, np.float32)
+            if wt.size != obs.size:
+                raise ValueError("columns_resolution: wt holds %d values, obs %d" % (wt.size, obs.size))
+        nmaps = obs.size // ncol
+        out = dict(measures=np.zeros((4, nz - 1, ncol)), leverage=np.zeros((nmaps, ncol)), trace=np.zeros(ncol), nused=np.zeros(ncol, np.int32),
+                   flag=np.zeros(ncol, np.int32))
+        if full:
+            out["R"] = np.zeros((nz - 1, nz - 1, ncol))
+        self._check(self._L.dsa_columns_resolution(self._h, nmaps, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), _p(out["measures"]),
+                                                   _p(out["leverage"]), _p(out["trace"]), _p(out["R"]) if full else None, _p(out["nused"]), _p(out["flag"])))
+        return out
 
     def dispersion_get_model(self):
         """the dispersion stage's resident model, (nz, ny, nx) fp32 as dispersion_begin takes it"""

@@ -459,6 +459,27 @@ int dsa_columns_step(dsa_engine* e, int nmaps, const float* obs, const float* wt
                      float maxvel, float* dv, int* nused, double* chi2, int* flag);
 int dsa_dispersion_get_model(dsa_engine* e, float* vels);
 
+/* dsa_columns_resolution: how far the depth step's answer can be trusted, per interior column, from the regularised normal matrix the step
+ * factors (extension).  The state and obs, wt, smooth, damp are dsa_columns_step's, with its rules and refusals; of obs only
+ * the sign is used (which data count).  Per column, with the definitions above, N = G^T G + smooth^2 L^T L + damp^2 I = L D L^T:
+ * T (nmaps x M) has in row k the solution of N t = g_k for a used datum (the step's substitutions, one solve per datum) and zeros for any
+ * other; R = T^T G is the model resolution matrix, its column j the point-spread function of unknown j.  Everything fp64, every sum
+ * sequential from 0.0 over the used data ascending.
+ *   measures  4*(nz-1)*nx*ny doubles, (measure, depth, column): R_jj;  m1 = sum_l R_lj^2;  m2 = sum_l R_lj^2 (depz_l - depz_j)^2 -- the
+ *             vertical length of the PSF is sqrt(m2 / m1);  var_j = sum_k T_kj^2, the variance of unknown j for unit variance of the
+ *             weighted data (the diagonal of N^-1 G^T G N^-1)
+ *   leverage  nmaps*nx*ny: h_k = sum_l g_kl T_kl, the diagonal of the data resolution matrix; 0 for a datum not used
+ *   trace     nx*ny: sum_j R_jj (= sum_k h_k in exact arithmetic);  nused, flag  nx*ny: as dsa_columns_step's
+ *   R         NULL, or (nz-1)*(nz-1)*nx*ny doubles: R_lj at (l*(nz-1) + j)*nx*ny + column.  NULL skips the store and changes no other bit.
+ * A column with flag 1 or 2 and the outer ring of columns have 0.0 everywhere.  R is not symmetric: R_jj may leave [0, 1].
+ * Nothing is changed: the model, the marks of the maps and slots and the Frechet rows' sensitivities stay, so a dsa_columns_step after
+ * the call gives the bits it would have given without it; after a step the call is DSA_ERR_STATE until the runs are repeated.
+ * Errors, all but the last found before the device is touched: DSA_ERR_STATE and DSA_ERR_ARGUMENT as dsa_columns_step, in its order;
+ * DSA_ERR_ARGUMENT for a NULL measures, leverage, trace, nused or flag; DSA_ERR_DEVICE when a column's work arrays (about 77 KB at
+ * nz = 64 with 60 maps) exceed the LDS a block of the device may have or the device refuses that size. */
+int dsa_columns_resolution(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* measures,
+                           double* leverage, double* trace, double* R, int* nused, int* flag);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);

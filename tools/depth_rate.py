@@ -5,6 +5,11 @@ median of `repeats` timed iterations after a warm-up one: the wall time of the c
 The step's call holds two uploads, k_sen_combine, k_column_step and five downloads; the kernel's own time is what a kernel trace of this
 script shows for k_column_step (rocprofv3 --kernel-trace --stats -- python tools/depth_rate.py).
 
+The resolution's leg: dsa_columns_resolution on the same grid and plan (K = 26, M = 8) after one set of runs, without
+and with the full R, and at the stage's limits on a 5 x 5 grid (nz = 64, K = 60: 15 phase and 15 group periods of each wave type, the one
+launch that asks for more than 64 KB of LDS) -- the wall time of the whole call, `repeats` timed calls after a warm-up one (the call leaves
+the state as it is, so the runs are not repeated); k_column_resolution's own time is the kernel trace's.
+
     python tools/depth_rate.py [repeats]      (needs the GPU)
 """
 import os
@@ -48,7 +53,35 @@ def main():
         assert not out["flag"].any() and out["nused"].sum() == kmax * (c["nx"] - 2) * (c["ny"] - 2)
         print("%-20s %d x %d x %d, K = %d, %d dispersion_run: median of %d -- runs %.3f ms wall (%.3f ms on the device), columns_step %.3f ms wall; all steps: %s" %
               (name, c["nx"], c["ny"], c["nz"], kmax, len(plan), repeats, np.median(runs), np.median(dev), np.median(step), " ".join("%.3f" % s for s in step)))
+    resolution_leg(e, repeats, "the example's grid", vel, c["depz"], c["minthk"], depth.slot_plan(c), kmax)
+    nz = 64
+    k = np.arange(nz)[:, None, None]; i = np.arange(5)[None, None, :]; j = np.arange(5)[None, :, None]
+    limits = np.ascontiguousarray((2.6 + 1.9 * k / (nz - 1)) * (1.0 + 0.05 * np.sin(0.7 * i + 0.3 * k) * np.cos(0.5 * j)), np.float32)
+    depz = np.concatenate([[0.0], np.cumsum(np.round(2.0 + 4.0 * np.arange(nz - 1) / (nz - 2)))]).astype(np.float32)
+    phase, group = np.linspace(3.0, 45.0, 15), np.linspace(4.0, 46.0, 15)
+    resolution_leg(e, repeats, "the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60)
     e.close()
+
+
+def resolution_leg(e, repeats, name, vel, depz, minthk, plan, kmax):
+    nz, ny, nx = vel.shape
+    e.dispersion_begin(vel, depz, minthk, kmax, kmax)
+    t0 = time.perf_counter()
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, True, first, first)
+    t1 = time.perf_counter()
+    obs = np.where(e.dispersion_fetch(0, kmax) > 0, 3.0, 0.0).astype(np.float32)
+    for full in (False, True):
+        wall = []
+        for it in range(repeats + 1):
+            t2 = time.perf_counter()
+            out = e.columns_resolution(obs, None, depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP, full)
+            if it:
+                wall.append(1e3 * (time.perf_counter() - t2))
+        ok = out["flag"].reshape(ny, nx)[1:-1, 1:-1] == 0
+        print("%-20s %d x %d x %d, K = %d (runs %.1f ms): columns_resolution %s, median of %d -- %.3f ms wall; %d of %d columns resolved, trace %.3f to %.3f; all calls: %s" %
+              (name, nx, ny, nz, kmax, 1e3 * (t1 - t0), "with the full R" if full else "without R", repeats, np.median(wall), int(ok.sum()), ok.size,
+               out["trace"].reshape(ny, nx)[1:-1, 1:-1][ok].min(), out["trace"].reshape(ny, nx)[1:-1, 1:-1][ok].max(), " ".join("%.3f" % w for w in wall)))
 
 
 if __name__ == "__main__":
