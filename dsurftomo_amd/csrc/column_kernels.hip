@@ -4,9 +4,11 @@
 // triangle of N (then L), and five short vectors -- 2.5 KB for the Taipei example (M = 8, K = 26: a CU's 160 KB hold more blocks than its
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
+// k_column_step_radial, last: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
+#include "column_radial.h"
 
 namespace dsa {
 
@@ -74,6 +76,37 @@ __global__ void __launch_bounds__(64) k_column_resolution(int nx, int ny, int nz
     if (threadIdx.x == 0) { nused[c] = n; trace[c] = tr; flag[c] = f; }
 }
 
+// k_column_step_radial: column_radial.h on every interior column of the two resident models, the launch shape and the
+// column of a block as above.  The work arrays lie in dynamic LDS: radial_work_doubles(M, K) doubles -- 5.1 KB for K = 26 on M = 8, 98 232 B
+// at the stage's limits (M = 63, K = 60: one column per CU), which the launcher has to ask for.  love: bit k set where slot k is a Love slot.
+// Sv / Sh: (M, K, ncol), k_sen_combine's rule on the Vsv and on the Vsh model; dv: (2, M, ncol), the Vsv block then the Vsh block; nused /
+// chi2: (2, ncol), Rayleigh then Love; flag: (ncol).
+__global__ void __launch_bounds__(64) k_column_step_radial(int nx, int ny, int nz, int K, unsigned long long love, const float* __restrict__ obs,
+                                                          const float* __restrict__ wt, const double* __restrict__ pv, const double* __restrict__ Sv,
+                                                          const double* __restrict__ Sh, float smooth, float damp, float aniso, float dvmax, float minvel,
+                                                          float maxvel, float* __restrict__ vsv, float* __restrict__ vsh, float* __restrict__ dv,
+                                                          int* __restrict__ nused, double* __restrict__ chi2, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int nvx = nx - 2, M = nz - 1;
+    const long long ncol = (long long)nx * ny;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    if (bj >= ny - 2) return;
+    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    RadialIn in;
+    in.M = M; in.K = K; in.love = love;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.Sv = Sv + c; in.Sh = Sh + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    const ColumnWork w = radial_work(column_lds, M, K);
+    int n[2] = { 0, 0 };
+    double x2[2] = { 0.0, 0.0 };
+    const int f = radial_step(in, smooth, damp, aniso, dvmax, minvel, maxvel, w, vsv + c, vsh + c, ncol, dv + c, dv + (long long)M * ncol + c, ncol, n, x2,
+                              (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -106,6 +139,30 @@ int launch_column_resolution(int device, int nx, int ny, int nz, int K, const fl
     }
     hipLaunchKernelGGL(k_column_resolution, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, d_depz, smooth,
                        damp, d_measures, d_leverage, d_trace, d_R, d_nused, d_flag);
+    return 0;
+}
+
+size_t column_radial_lds_bytes(int nz, int K) { return radial_work_doubles(nz - 1, K) * sizeof(double); }
+
+// launch_column_resolution's rule for the LDS and its return values
+int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                              const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
+                              float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
+    const size_t lds = column_radial_lds_bytes(nz, K);
+    if (lds > 64 * 1024) {
+        int limit = 0;
+        if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
+        if (limit_out) *limit_out = limit;
+        if (lds > (size_t)limit) return 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_column_step_radial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return 2;
+        }
+    }
+    hipLaunchKernelGGL(k_column_step_radial, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh,
+                       smooth, damp, aniso, dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv, d_nused, d_chi2, d_flag);
     return 0;
 }
 

@@ -302,14 +302,26 @@ struct Engine {
     int columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
                      double* chi2, int* flag);
     // what dsa_columns_step and dsa_columns_resolution share (who: the caller's name in the messages): the state and the arguments both have,
-    // in the step's order of refusals; step: also dvmax, minvel, maxvel
-    int columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel, float maxvel);
+    // in the step's order of refusals; step: also dvmax, minvel, maxvel; radial: the kind of stage the caller works on (the other kind is refused)
+    int columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel, float maxvel,
+                      bool radial = false);
     // depth resolution of the columns (dsa_columns_resolution, k_column_resolution): reads what the step reads, changes nothing
     OwnedBuf<double> col_meas, col_lev, col_trace, col_R;
     OwnedBuf<float> col_depz;
     int columns_resolution(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* measures, double* leverage, double* trace, double* R,
                            int* nused, int* flag);
     int dispersion_get_model(float* vels);
+    // radially anisotropic stage and step (dsa_dispersion_begin_radial, dsa_columns_step_radial, k_column_step_radial): a
+    // one-model stage in every other sense that keeps a second resident model -- vels_d / h_vels hold Vsv, which the Rayleigh runs read, vsh_d /
+    // h_vsh hold Vsh, which the Love runs read.  Set by dispersion_begin_radial, cleared by every other begin (dispersion_setup).
+    bool disp_radial = false;
+    OwnedBuf<float> vsh_d;
+    std::vector<float> h_vsh;
+    OwnedBuf<double> col_Sh;           // the combined sensitivities on the Vsh model (col_S: on the Vsv model)
+    int dispersion_begin_radial(int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total, int nmaps_total);
+    int columns_step_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel,
+                            float* dv, int* nused, double* chi2, int* flag);
+    int dispersion_get_model_radial(float* vsv, float* vsh);
 
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;

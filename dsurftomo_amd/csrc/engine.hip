@@ -18,6 +18,7 @@
 #include "engine.h"
 #include "spmv_state.h"
 #include "column_system.h"
+#include "column_radial.h"
 
 namespace dsa {
 
@@ -182,6 +183,23 @@ int Engine::dispersion_begin(int nx, int ny, int nz, const float* vels, const fl
     return dispersion_commit(false);
 }
 
+// dsa_dispersion_begin_radial: dispersion_begin on one model with a second one kept beside it.  vels_d / h_vels hold
+// Vsv, vsh_d / h_vsh hold Vsh; dispersion_run picks by wave type.
+int Engine::dispersion_begin_radial(int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total, int nmaps_total)
+{
+    if (!vsv || !vsh) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, 1); return DSA_ERR_ARGUMENT; }
+    if (int rc = dispersion_setup(nx, ny, nz, depz, minthk, kmax_total, nmaps_total, 1)) return rc;
+    const size_t nn = (size_t)nx * ny * nz;
+    if (ensure(vsh_d, nn)) return status;
+    h_vels.assign(vsv, vsv + nn);
+    h_vsh.assign(vsh, vsh + nn);
+    HIP_TRY(this, hipMemcpyAsync(vels_d.p, h_vels.data(), nn * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(vsh_d.p, h_vsh.data(), nn * 4, hipMemcpyHostToDevice, stream));
+    if (int rc = dispersion_commit(false)) return rc;
+    disp_radial = true;
+    return 0;
+}
+
 int Engine::dispersion_setup(int nx, int ny, int nz, const float* depz, float minthk, int kmax_total, int nmaps_total, int nmodels)
 {
     if (nx < 1 || ny < 1 || nz < 2 || nz > 64 || !depz || kmax_total < 1 || nmaps_total < 1 || nmodels < 1 || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "dispersion: bad arguments (nx=%d ny=%d nz=%d kmax=%d nmodels=%d)", nx, ny, nz, kmax_total, nmodels); return DSA_ERR_ARGUMENT; }
@@ -190,6 +208,7 @@ int Engine::dispersion_setup(int nx, int ny, int nz, const float* depz, float mi
     if (make_layer_geom(nz, depz, minthk, h_geom) != 0) { fail(DSA_ERR_ARGUMENT, "dispersion: the refined column exceeds %d layers", kMaxLayers); return DSA_ERR_ARGUMENT; }
     const size_t ncol = (size_t)nx * ny;
     disp_ready = false;
+    disp_radial = false;
     disp_nx = nx; disp_ny = ny; disp_nz = nz; disp_kmax_total = kmax_total; disp_nmaps = nmaps_total; disp_nmodels = nmodels;
     h_depz.assign(depz, depz + nz);
     // (depth kernels exist for one model only: dispersion_run refuses them otherwise)
@@ -288,10 +307,11 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
     // (several models: the list also tells which model a failing curve belongs to)
     const bool listed = disp_failure_log > 0 || models;
     if (listed && ensure(disp_fail_list, nlanes)) return status;
-    launch_dispersion(iwave, geom.p, vels_d.p, ncol, npert, igr, nper, tper.p, disp_ws.p, nlanes, curves.p, h_geom.rmax, in_lds, gshift, disp_diag.p,
+    const float* model_d = disp_radial && iwave == 1 ? vsh_d.p : vels_d.p;      // (a radial stage: Love reads Vsh, Rayleigh Vsv)
+    launch_dispersion(iwave, geom.p, model_d, ncol, npert, igr, nper, tper.p, disp_ws.p, nlanes, curves.p, h_geom.rmax, in_lds, gshift, disp_diag.p,
                       listed ? disp_fail_list.p : nullptr, listed ? (int)std::min<size_t>(nlanes, (size_t)0x7fffffff) : 0, stream);
     if (models) launch_pv_models(curves.p, disp_nx * disp_ny, disp_nmodels, nper, disp_nmaps, map_first, pvstore.p, stream);
-    else launch_depth_kernels(vels_d.p, ncol, disp_nz, nper, curves.p, with_kernels, pvstore.p + (size_t)map_first * ncol, sen_vs.p, sen_vp.p, sen_rho.p,
+    else launch_depth_kernels(model_d, ncol, disp_nz, nper, curves.p, with_kernels, pvstore.p + (size_t)map_first * ncol, sen_vs.p, sen_vp.p, sen_rho.p,
                               disp_kmax_total, sen_slot, stream);
     HIP_TRY(this, hipEventRecord(events[2], stream));
     HIP_TRY(this, hipGetLastError());
@@ -349,10 +369,11 @@ int Engine::dispersion_failure(int index, int* info, double* vals, float* table,
 {
     if (index < 0 || index >= (int)disp_failures.size() || !info || !vals || !table || !c) return DSA_ERR_ARGUMENT;
     const DispFailRec& r = disp_failures[(size_t)index];
-    if (h_vels.size() != (size_t)disp_nx * disp_ny * disp_nz * disp_nmodels) return DSA_ERR_STATE;
+    const std::vector<float>& h_model = disp_radial && r.iwave == 1 ? h_vsh : h_vels;      // (the model the failing run read)
+    if (h_model.size() != (size_t)disp_nx * disp_ny * disp_nz * disp_nmodels) return DSA_ERR_STATE;
     const size_t ncol = (size_t)disp_nx * disp_ny * disp_nmodels;      // (h_vels: depth, model, column; r.column counts over the models)
     float vs[64];
-    for (int k = 0; k < disp_nz; ++k) vs[k] = h_vels[(size_t)k * ncol + (size_t)(r.column - 1)];
+    for (int k = 0; k < disp_nz; ++k) vs[k] = h_model[(size_t)k * ncol + (size_t)(r.column - 1)];
     int mmax = 0;
     double ccc[3] = { 0.0, 0.0, 0.0 };
     const int k = disp_replay_failure(h_geom, vs, r.pert, r.iwave, r.igr, r.nper, r.t, &mmax, table, ccc, c);
@@ -393,10 +414,15 @@ int Engine::dispersion_fetch(int map_first, int nper, double* pv, int with_kerne
 // What dsa_columns_step and dsa_columns_resolution ask of the stage and of the arguments both have, one copy, in the step's order of
 // refusals; nothing on the device is touched.
 int Engine::columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel,
-                          float maxvel)
+                          float maxvel, bool radial)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "%s: call dsa_dispersion_begin and dsa_dispersion_run (with kernels) first", who); return DSA_ERR_STATE; }
     if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "%s: the dispersion stage holds %d models, the step moves one", who, disp_nmodels); return DSA_ERR_STATE; }
+    if (disp_radial != radial) {
+        if (radial) fail(DSA_ERR_STATE, "%s: the dispersion stage is not radial, call dsa_dispersion_begin_radial first", who);
+        else fail(DSA_ERR_STATE, "%s: the dispersion stage is radial (Vsv and Vsh), which dsa_columns_step_radial steps", who);
+        return DSA_ERR_STATE;
+    }
     if (disp_nmaps != disp_kmax_total) { fail(DSA_ERR_STATE, "%s: the stage holds %d maps and %d kernel slots, the step needs one slot per map", who, disp_nmaps, disp_kmax_total); return DSA_ERR_STATE; }
     const int K = disp_nmaps, M = disp_nz - 1;
     if (nmaps_in != K) { fail(DSA_ERR_ARGUMENT, "%s: %d maps given, the stage holds %d", who, nmaps_in, K); return DSA_ERR_ARGUMENT; }
@@ -502,8 +528,71 @@ int Engine::dispersion_get_model(float* vels)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model: call dsa_dispersion_begin first"); return DSA_ERR_STATE; }
     if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "dispersion_get_model: the dispersion stage holds %d models", disp_nmodels); return DSA_ERR_STATE; }
+    if (disp_radial) { fail(DSA_ERR_STATE, "dispersion_get_model: the dispersion stage is radial and holds Vsv and Vsh, which dsa_dispersion_get_model_radial returns"); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
     HIP_TRY(this, hipMemcpyAsync(vels, vels_d.p, (size_t)disp_nx * disp_ny * disp_nz * 4, hipMemcpyDeviceToHost, stream));       // (on the engine's stream: behind the step)
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+int Engine::dispersion_get_model_radial(float* vsv, float* vsh)
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model_radial: call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    if (!disp_radial) { fail(DSA_ERR_STATE, "dispersion_get_model_radial: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t nn = (size_t)disp_nx * disp_ny * disp_nz;
+    if (vsv) HIP_TRY(this, hipMemcpyAsync(vsv, vels_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
+    if (vsh) HIP_TRY(this, hipMemcpyAsync(vsh, vsh_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_step_radial: dsa_columns_step on a radial stage.  The state and argument rules are columns_front's, then
+// aniso; everything is checked before the device is touched.  The combined sensitivities are k_sen_combine's rule twice, on the Vsv and on
+// the Vsh model, into two buffers of the step's own (Srow is not written); the kernel reads the first at the Rayleigh slots and the second at
+// the Love slots, by the mask of the slots' marks.  Both models are stepped where they lie, the host copies follow, the marks are cleared.
+int Engine::columns_step_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel,
+                                float* dv, int* nused, double* chi2, int* flag)
+{
+    if (int rc = columns_front("columns_step_radial", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
+    if (!std::isfinite(aniso) || aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial: aniso %g must be finite and >= 0", (double)aniso); return DSA_ERR_ARGUMENT; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    unsigned long long love = 0ull;
+    for (int k = 0; k < K; ++k) if (disp_slot_mark[(size_t)k].iwave == 1) love |= 1ull << k;
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_S, ncol * K * M) || ensure(col_Sh, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, 2 * ncol * M) ||
+        ensure(col_nused, 2 * ncol) || ensure(col_chi2, 2 * ncol) || ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernel runs on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, 2 * ncol * M * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, 2 * ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, 2 * ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    const int shallow = h_depz[disp_nz - 2] < 35.0f ? 1 : 0;
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_S.p, stream);
+    launch_sen_combine((int)ncol, K, disp_nz, vsh_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_Sh.p, stream);
+    int limit = 0;
+    const int rc = launch_column_step_radial(device, disp_nx, disp_ny, disp_nz, K, love, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p, smooth, damp,
+                                             aniso, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, col_dv.p, col_nused.p, col_chi2.p, col_flag.p, stream, &limit);
+    if (rc) {
+        HIP_TRY(this, hipStreamSynchronize(stream));
+        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_step_radial: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", 2 * M, K, column_radial_lds_bytes(disp_nz, K), limit);
+        else fail(DSA_ERR_DEVICE, "columns_step_radial: the device refuses %zu bytes of dynamic LDS per workgroup", column_radial_lds_bytes(disp_nz, K));
+        return DSA_ERR_DEVICE;
+    }
+    HIP_TRY(this, hipGetLastError());
+    for (DispMark& m : disp_map_mark) m.fresh = false;
+    for (DispMark& m : disp_slot_mark) m.fresh = false;
+    h_vels.resize(ncol * disp_nz);
+    h_vsh.resize(ncol * disp_nz);
+    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, h_vsh.size() * 4, hipMemcpyDeviceToHost, stream));
+    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, 2 * ncol * M * 4, hipMemcpyDeviceToHost, stream));
+    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, 2 * ncol * 4, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
@@ -532,6 +621,7 @@ int Engine::kernels_from_dispersion()
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "depth kernels: call dsa_dispersion_begin / run first"); return DSA_ERR_STATE; }
     if (disp_nmodels > 1) { fail(DSA_ERR_STATE, "depth kernels: the dispersion stage holds %d models, depth kernels exist for one", disp_nmodels); return DSA_ERR_STATE; }
+    if (disp_radial) { fail(DSA_ERR_STATE, "depth kernels: the dispersion stage is radial, the combined sensitivities of the Frechet rows assume one model for all slots"); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
     const size_t ncol = (size_t)disp_nx * disp_ny;
     if (ensure(Srow, ncol * disp_kmax_total * (disp_nz - 1))) return status;
@@ -1989,6 +2079,26 @@ int dsa_dispersion_get_model(dsa_engine* e, float* vels)
 {
     if (!e || !vels) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->dispersion_get_model(vels);
+}
+
+int dsa_dispersion_begin_radial(dsa_engine* e, int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total,
+                                int nmaps_total)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->dispersion_begin_radial(nx, ny, nz, vsv, vsh, depz, minthk, kmax_total, nmaps_total);
+}
+
+int dsa_columns_step_radial(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel,
+                            float maxvel, float* dv, int* nused, double* chi2, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_step_radial(nmaps, obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel, dv, nused, chi2, flag);
+}
+
+int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->dispersion_get_model_radial(vsv, vsh);
 }
 
 int dsa_set_azimuthal_slots(dsa_engine* e, int kmax, const int* on)

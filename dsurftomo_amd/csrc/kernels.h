@@ -314,6 +314,14 @@ size_t column_resolution_lds_bytes(int nz, int K);
 int launch_column_resolution(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S,
                              const float* d_depz, float smooth, float damp, double* d_measures, double* d_leverage, double* d_trace, double* d_R, int* d_nused,
                              int* d_flag, hipStream_t stream, int* limit_out);
+// The radially anisotropic step: the interior columns of the two (nz, ny, nx) models d_vsv and d_vsh in place.  love: bit k
+// set where slot k is a Love slot; d_Sv / d_Sh: launch_sen_combine's on the Vsv and on the Vsh model; d_dv: (2, nz - 1, ncol), the Vsv block then
+// the Vsh block; d_nused / d_chi2: (2, ncol), Rayleigh then Love; d_flag: (ncol).  Only interior columns are written.  The return values and
+// *limit_out are launch_column_resolution's; column_radial_lds_bytes: the dynamic LDS of a block.
+size_t column_radial_lds_bytes(int nz, int K);
+int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                              const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
+                              float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

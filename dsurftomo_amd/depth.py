@@ -1,7 +1,7 @@
 """Depth inversion of the period maps: per-column Vs(z) Gauss-Newton steps on the device.
 
     python -m dsurftomo_amd.depth <directory with DSurfTomo.in, the data file and MOD> [--maps FILE] [--iterations N] [--smooth L] [--damp D]
-                                  [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]]
+                                  [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]] [--radial [--aniso G]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -30,6 +30,16 @@ latitude, wave type, velocity kind, period and the leverage h_k.  The log gives 
 over the others, and the depth below which the median R_jj falls under 0.1.  column_resolution_twin is the NumPy twin
 (csrc/column_resolution.h is the arithmetic).
 
+--radial: radial anisotropy.  The Rayleigh maps are explained by Vsv(z) and the Love maps by Vsh(z); both models start
+as the input's MOD and are stepped together by columns_step_radial, 2 (nz - 1) unknowns per column, tied by --aniso G (default 0.2, in the
+units of --damp): the weight of the penalty on the change of Vsh - Vsv, 0 for two independent inversions.  The input must list Rayleigh and
+Love periods; --resolution is refused (the resolution of the coupled system is not computed).  The log gives per iteration the rms per wave
+type and at the end the median and range of xi = (Vsh / Vsv)^2 over the nodes above the bottom depth of the interior columns that are not
+flagged.  <input>DepthRadial.dat (write_radial / read_radial): longitude, latitude, depth, Vsv, Vsh, the Voigt average
+sqrt((2 Vsv^2 + Vsh^2) / 3) and xi of every node.  <input>DepthRadialFit.dat (write_radial_fit / read_radial_fit): per column the data used
+and the rms before the first and the last step per wave type, and the flag of the last step.  Depth.dat and DepthFit.dat are not written.
+column_radial_twin is the NumPy twin (csrc/column_radial.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -46,12 +56,16 @@ DEFAULT_ITERATIONS = 4
 DEFAULT_SMOOTH = 0.5
 DEFAULT_DAMP = 0.1
 DEFAULT_DVMAX = 0.5
+DEFAULT_ANISO = 0.2
 
 _F64 = lambda *names: tuple((n, "%.17g", "f64") for n in names)
 DEPTH_TABLE = (True, _F64("lon", "lat", "depth", "vs"))
 RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", "rjj", "length", "sd_unit", "sd"))
 LEVERAGE_TABLE = (True, _F64("lon", "lat") + (("wave", "%d", "int"), ("kind", "%d", "int")) + _F64("period", "leverage"))
 FIT_TABLE = (True, _F64("lon", "lat") + (("nused", "%d", "int"),) + _F64("rms_first", "rms_last") + (("flag", "%d", "int"),))
+RADIAL_TABLE = (True, _F64("lon", "lat", "depth", "vsv", "vsh", "voigt", "xi"))
+RADIAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused_r", "%d", "int"), ("nused_l", "%d", "int")) + _F64("rms_first_r", "rms_last_r", "rms_first_l", "rms_last_l") +
+                    (("flag", "%d", "int"),))
 
 
 # ---- NumPy twins ----
@@ -172,6 +186,73 @@ def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, 
     return out
 
 
+def column_radial_twin(obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, dvmax, minvel, maxvel, solver="ldlt", n_override=None):
+    """dsa_columns_step_radial on one column in NumPy (csrc/column_radial.h).  obs, wt, pv as column_step_twin's; S (K, M): row k the
+    sensitivities of datum k to the model its slot was run on (Vsh where love[k], else Vsv); love (K) bool; vsv, vsh (M or more) fp32, of
+    which the first M are stepped.  The unknowns are [dVsv ; dVsh].  solver 'ldlt' follows the header operation by operation through
+    _twin_factor / _twin_solve on the 2M x 2M matrix; solver 'lstsq': the same step from numpy.linalg.lstsq on the stacked system
+    [G; smooth L (+) smooth L; damp I; aniso [-I I]] with right-hand side [rho; 0; 0; -aniso d], d = vsh - vsv -- another algorithm, for the
+    size of the rounding error.  n_override: a (2M, 2M) matrix in place of the assembled N (tests).  Returns dict(delta (2M) fp64, dv_sv,
+    dv_sh (M) fp32, vsv, vsh (the stepped copies), nused (2) and chi2 (2): Rayleigh, Love; flag)."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64); love = np.asarray(love, bool)
+    K, M = S.shape
+    wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
+    vsv = np.array(vsv, f, copy=True); vsh = np.array(vsh, f, copy=True)
+    used = (wt > 0) & (obs > 0) & (pv > 0)
+    a = wt.astype(np.float64)
+    rho = np.where(used, a * (obs.astype(np.float64) - pv), 0.0)
+    chi2 = [0.0, 0.0]
+    for k in np.flatnonzero(used):
+        chi2[int(love[k])] = chi2[int(love[k])] + rho[k] * rho[k]
+    out = dict(delta=np.zeros(2 * M), dv_sv=np.zeros(M, f), dv_sh=np.zeros(M, f), vsv=vsv, vsh=vsh, nused=[int((used & ~love).sum()), int((used & love).sum())],
+               chi2=[float(chi2[0]), float(chi2[1])], flag=0)
+    if not used.any():
+        out["flag"] = 2
+        return out
+    G = np.zeros((K, M))
+    G[used] = a[used, None] * S[used]
+    lam, mu, gam = float(f(smooth)), float(f(damp)), float(f(aniso))
+    lam2, mu2, gam2 = lam * lam, mu * mu, gam * gam
+    d = vsh[:M].astype(np.float64) - vsv[:M].astype(np.float64)
+    if solver == "lstsq":
+        nu = int(used.sum())
+        A = np.zeros((nu, 2 * M))
+        A[:, :M] = np.where(love[used, None], 0.0, G[used]); A[:, M:] = np.where(love[used, None], G[used], 0.0)
+        Lm = column_l(M); Z = np.zeros_like(Lm)
+        A = np.vstack([A, lam * np.hstack([Lm, Z]), lam * np.hstack([Z, Lm]), mu * np.eye(2 * M), gam * np.hstack([-np.eye(M), np.eye(M)])])
+        rhs = np.concatenate([rho[used], np.zeros(2 * Lm.shape[0] + 2 * M), -gam * d])
+        delta = np.linalg.lstsq(A, rhs, rcond=None)[0]
+    else:
+        N = np.zeros((2 * M, 2 * M)); b = np.zeros(2 * M)
+        for q, sel in enumerate((used & ~love, used & love)):
+            Nq, bq = _twin_normal(G, sel, rho, lam2, mu2)
+            Nq[np.diag_indices(M)] = Nq[np.diag_indices(M)] + gam2
+            N[q * M:(q + 1) * M, q * M:(q + 1) * M] = Nq
+            t = gam2 * d
+            b[q * M:(q + 1) * M] = bq - t if q else bq + t
+        N[M:, :M][np.diag_indices(M)] = 0.0 - gam2
+        N[:M, M:] = N[M:, :M].T
+        if n_override is not None:
+            N = np.array(n_override, np.float64)
+        factor = _twin_factor(N)
+        if factor is None:
+            out["flag"] = 1
+            return out
+        delta = _twin_solve(*factor, b)
+    s = delta.astype(f)
+    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
+    with np.errstate(invalid="ignore"):
+        s = np.where(s >= dvmax, dvmax, s)
+        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
+        for vel, part in ((vsv, s[:M]), (vsh, s[M:])):
+            v = (vel[:M] + part).astype(f)
+            v = np.where(v < minvel, minvel, v)
+            vel[:M] = np.where(v > maxvel, maxvel, v)
+    out.update(delta=delta, dv_sv=s[:M].copy(), dv_sh=s[M:].copy())
+    return out
+
+
 def _resolution_measures(T, G, used, depz):
     """R = T^T G and what column_resolution.h reduces from it, every sum from 0.0 in the header's order: over the used k ascending, over l
     and j ascending.  Returns dict(R (M, M), measures (4, M): R_jj, m1, m2, var; leverage (K); trace)."""
@@ -276,11 +357,11 @@ def dws_weights(dws, min_dws):
 
 # ---- the loop ----
 
-def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None):
+def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None, aniso=None):
     """the driver's preconditions, checked before the library is loaded (ValueError)"""
     if iterations is not None and iterations < 1:
         raise ValueError("--iterations must be at least 1, not %r" % (iterations,))
-    for name, v in (("--smooth", smooth), ("--min-dws", min_dws)):
+    for name, v in (("--smooth", smooth), ("--min-dws", min_dws), ("--aniso", aniso)):
         if v is not None and not (np.isfinite(v) and v >= 0):
             raise ValueError("%s must be finite and >= 0, not %r" % (name, v))
     for name, v in (("--damp", damp), ("--dvmax", dvmax), ("--sigma", sigma)):
@@ -433,13 +514,123 @@ def resolve(eng, c, plan, obs, wt, smooth, damp, sigma, out_dir, log=print):
     return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
 
 
+# ---- radial anisotropy ----
+
+def check_radial(c, resolution=False):
+    """what --radial asks of the other flags and of the input c (None: not read yet), before the engine is created (ValueError)"""
+    if resolution:
+        raise ValueError("--radial and --resolution exclude each other: the resolution of the coupled Vsv / Vsh system is not computed")
+    if c is None:
+        return
+    nr = len(c["tRc"]) + len(c["tRg"]); nl = len(c["tLc"]) + len(c["tLg"])
+    if nr == 0 or nl == 0:
+        raise ValueError("--radial needs Rayleigh and Love periods, the input lists %d and %d" % (nr, nl))
+
+
+def iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, minvel, maxvel, log=print):
+    """iterate on an engine whose stage is radial (dispersion_begin_radial): per iteration the runs of plan -- the Love runs read Vsh, the
+    Rayleigh runs Vsv -- then columns_step_radial.  Returns dict(history: one dict per iteration {iteration, nused, chi2, rms, nused_r,
+    nused_l, rms_r, rms_l (before the step), flagged1, flagged2}, steps: columns_step_radial's result per iteration)."""
+    history, steps = [], []
+    for it in range(1, iterations + 1):
+        for wave, kind, t, first in plan:
+            eng.dispersion_run(wave, kind, t, True, first, first)
+        out = eng.columns_step_radial(obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel)
+        h = dict(iteration=it, nused=int(out["nused"].sum()), chi2=float(out["chi2"].sum()), rms=rms_of(out["chi2"], out["nused"]),
+                 nused_r=int(out["nused"][0].sum()), nused_l=int(out["nused"][1].sum()), rms_r=rms_of(out["chi2"][0], out["nused"][0]),
+                 rms_l=rms_of(out["chi2"][1], out["nused"][1]), flagged1=int((out["flag"] == 1).sum()), flagged2=int((out["flag"] == 2).sum()))
+        log(" depth iteration %d (radial): %d Rayleigh data rms %.6f km/s, %d Love data rms %.6f km/s before the step, %d columns flagged (%d not positive definite, %d without data)" %
+            (it, h["nused_r"], h["rms_r"], h["nused_l"], h["rms_l"], h["flagged1"] + h["flagged2"], h["flagged1"], h["flagged2"]))
+        history.append(h)
+        steps.append(out)
+    return dict(history=history, steps=steps)
+
+
+def voigt_xi(vsv, vsh):
+    """the Voigt average sqrt((2 Vsv^2 + Vsh^2) / 3) and xi = (Vsh / Vsv)^2, fp64 (xi 0 where Vsv is 0)"""
+    v = np.asarray(vsv, np.float64); h = np.asarray(vsh, np.float64)
+    r = np.divide(h, v, out=np.zeros(v.shape), where=v != 0)
+    return np.sqrt((2.0 * v * v + h * h) / 3.0), r * r
+
+
+def xi_summary(c, vsv, vsh, flag):
+    """(median, min, max) of xi over the nodes above the bottom depth of the interior columns whose flag is 0, or None without any"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+    ok = inner.ravel() & (np.asarray(flag).reshape(ny * nx) == 0)
+    if not ok.any():
+        return None
+    xi = voigt_xi(np.asarray(vsv).reshape(nz, ny * nx)[:nz - 1, ok], np.asarray(vsh).reshape(nz, ny * nx)[:nz - 1, ok])[1]
+    return float(np.median(xi)), float(xi.min()), float(xi.max())
+
+
+def write_radial(path, c, vsv, vsh):
+    """<input>DepthRadial.dat: vsv, vsh (nz, ny, nx), every node in Depth.dat's order"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    v = np.asarray(vsv, np.float64).reshape(nz, ny, nx); h = np.asarray(vsh, np.float64).reshape(nz, ny, nx)
+    voigt, xi = voigt_xi(v, h)
+    rows = []
+    for k in range(nz):
+        for j in range(ny):
+            for i in range(nx):
+                lon, lat = _lonlat(c, i - 1, j - 1)
+                rows.append(dict(lon=float(lon), lat=float(lat), depth=float(c["depz"][k]), vsv=v[k, j, i], vsh=h[k, j, i], voigt=voigt[k, j, i], xi=xi[k, j, i]))
+    io.write_table(path, RADIAL_TABLE, rows)
+
+
+def read_radial(path):
+    return io.read_table(path, RADIAL_TABLE)
+
+
+def write_radial_fit(path, c, first, last):
+    """<input>DepthRadialFit.dat: first / last = columns_step_radial's results of the first and the last iteration; one line per column, j then i"""
+    nx, ny = c["nx"], c["ny"]
+    col_rms = lambda s, q: np.sqrt(np.divide(s["chi2"][q], s["nused"][q], out=np.zeros(nx * ny), where=s["nused"][q] > 0))
+    rows = []
+    r = [[col_rms(first, q), col_rms(last, q)] for q in range(2)]
+    for j in range(ny):
+        for i in range(nx):
+            lon, lat = _lonlat(c, i - 1, j - 1)
+            q = j * nx + i
+            rows.append(dict(lon=float(lon), lat=float(lat), nused_r=int(last["nused"][0][q]), nused_l=int(last["nused"][1][q]), rms_first_r=float(r[0][0][q]),
+                             rms_last_r=float(r[0][1][q]), rms_first_l=float(r[1][0][q]), rms_last_l=float(r[1][1][q]), flag=int(last["flag"][q])))
+    io.write_table(path, RADIAL_FIT_TABLE, rows)
+
+
+def read_radial_fit(path):
+    return io.read_table(path, RADIAL_FIT_TABLE)
+
+
+def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log=print):
+    """--radial on a fresh engine: both models start as the input's, the loop, the two files, the log's xi.  Returns (iterate_radial's result
+    with vsv, vsh (nz, ny, nx) and xi (xi_summary) added, the paths of DepthRadial.dat and DepthRadialFit.dat)."""
+    kmax = c["kmax"]
+    start = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
+    eng.dispersion_begin_radial(start, start, c["depz"], c["minthk"], kmax, kmax)
+    out = iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, float(c["minvel"]), float(c["maxvel"]), log)
+    out["vsv"], out["vsh"] = eng.dispersion_get_model_radial()
+    out["xi"] = xi_summary(c, out["vsv"], out["vsh"], out["steps"][-1]["flag"])
+    path = os.path.join(out_dir, "DSurfTomo.inDepthRadial.dat")
+    fit = os.path.join(out_dir, "DSurfTomo.inDepthRadialFit.dat")
+    write_radial(path, c, out["vsv"], out["vsh"])
+    write_radial_fit(fit, c, out["steps"][0], out["steps"][-1])
+    if out["xi"] is not None:
+        log(" depth (radial): xi = (Vsh / Vsv)^2 median %.4f, range %.4f to %.4f over the unflagged interior nodes above the bottom depth" % out["xi"])
+    log(" depth (radial): %d x %d x %d nodes of Vsv, Vsh, Voigt average and xi written to %s, the fit of %d columns to %s" % (c["nx"], c["ny"], c["nz"], path, c["nx"] * c["ny"], fit))
+    return out, path, fit
+
+
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
-        log=print, resolution=False, sigma=None):
+        log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
-    last step."""
-    check(iterations, smooth, damp, dvmax, min_dws, sigma)
+    last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files)."""
+    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None)
+    if radial:
+        check_radial(None, resolution)
     c = io.load(directory)
+    if radial:
+        check_radial(c)
     maps_file = os.path.join(out_dir, "DSurfTomo.inMaps.dat") if maps_file is None else maps_file
     obs, dws = maps_to_obs(maps.read_maps(maps_file), c)
     plan = slot_plan(c)
@@ -449,6 +640,11 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     wt = dws_weights(dws, min_dws) if min_dws > 0 else None
     from .engine import Engine
     eng = Engine(0)
+    if radial:
+        try:
+            return run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log)
+        finally:
+            eng.close()
     try:
         eng.dispersion_begin(np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0)), c["depz"], c["minthk"], kmax, kmax)
         out = iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, float(c["minvel"]), float(c["maxvel"]), log)
@@ -479,6 +675,8 @@ def parser():
     ap.add_argument("--out", default=".")
     ap.add_argument("--resolution", action="store_true", help="after the last step write the resolution measures and the leverages of the final model")
     ap.add_argument("--sigma", type=float, default=None, metavar="S", help="standard deviation of the map values in km/s for the sd column (default: the rms before the last step)")
+    ap.add_argument("--radial", action="store_true", help="radial anisotropy: invert the Rayleigh maps for Vsv(z) and the Love maps for Vsh(z) together")
+    ap.add_argument("--aniso", type=float, default=DEFAULT_ANISO, metavar="G", help="with --radial: weight of the tie between Vsh and Vsv, >= 0 (default %g)" % DEFAULT_ANISO)
     return ap
 
 
@@ -486,11 +684,13 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma)
+        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso)
+        if a.radial:
+            check_radial(None, a.resolution)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
-    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma)
+    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso)
     return 0
 
 

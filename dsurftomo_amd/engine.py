@@ -105,6 +105,9 @@ def declare_solvers(L):
     L.dsa_columns_step.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 5 + [_vp] * 4
     L.dsa_dispersion_get_model.argtypes = [_vp, _vp]
     L.dsa_columns_resolution.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 6
+    L.dsa_dispersion_begin_radial.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _i32]
+    L.dsa_columns_step_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [_vp] * 4
+    L.dsa_dispersion_get_model_radial.argtypes = [_vp, _vp, _vp]
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -465,6 +468,42 @@ class Engine:
         out = np.zeros((nz, ny, nx), np.float32)
         self._check(self._L.dsa_dispersion_get_model(self._h, out.ctypes.data_as(_vp)))
         return out
+
+    def dispersion_begin_radial(self, vsv, vsh, depz, minthk, kmax_total, nmaps_total):
+        """dsa_dispersion_begin_radial: vsv and vsh (nz, ny, nx) fp32 on one set of depths; afterwards the Love runs read vsh and the Rayleigh
+        runs vsv.  ValueError when the two shapes differ."""
+        vsv = np.ascontiguousarray(vsv, np.float32); vsh = np.ascontiguousarray(vsh, np.float32)
+        if vsv.ndim != 3 or vsv.shape != vsh.shape:
+            raise ValueError("dispersion_begin_radial: vsv is %r and vsh %r, both must be (nz, ny, nx)" % (vsv.shape, vsh.shape))
+        nz, ny, nx = vsv.shape
+        self._disp = (nx, ny, nz)
+        self._check(self._L.dsa_dispersion_begin_radial(self._h, nx, ny, nz, _p(vsv), _p(vsh), _p(np.ascontiguousarray(depz, np.float32)), float(minthk),
+                                                        int(kmax_total), int(nmaps_total)))
+
+    def columns_step_radial(self, obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel):
+        """dsa_columns_step_radial on the models of dispersion_begin_radial: obs and wt as columns_step's.  Returns dict(dv_sv, dv_sh (nz - 1,
+        ny * nx) fp32, nused (2, ny * nx) int32 and chi2 (2, ny * nx) fp64 -- Rayleigh, then Love -- flag (ny * nx) int32).  ValueError as
+        columns_step."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        obs = np.ascontiguousarray(obs, np.float32)
+        if ncol == 0 or obs.size == 0 or obs.size % ncol:
+            raise ValueError("columns_step_radial: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
+        if wt is not None:
+            wt = np.ascontiguousarray(wt, np.float32)
+            if wt.size != obs.size:
+                raise ValueError("columns_step_radial: wt holds %d values, obs %d" % (wt.size, obs.size))
+        dv = np.zeros((2, nz - 1, ncol), np.float32); nused = np.zeros((2, ncol), np.int32); chi2 = np.zeros((2, ncol)); flag = np.zeros(ncol, np.int32)
+        self._check(self._L.dsa_columns_step_radial(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(aniso),
+                                                    float(dvmax), float(minvel), float(maxvel), _p(dv), _p(nused), _p(chi2), _p(flag)))
+        return dict(dv_sv=dv[0], dv_sh=dv[1], nused=nused, chi2=chi2, flag=flag)
+
+    def dispersion_get_model_radial(self):
+        """the radial stage's two resident models, (vsv, vsh), each (nz, ny, nx) fp32"""
+        nx, ny, nz = self._disp
+        vsv = np.zeros((nz, ny, nx), np.float32); vsh = np.zeros((nz, ny, nx), np.float32)
+        self._check(self._L.dsa_dispersion_get_model_radial(self._h, vsv.ctypes.data_as(_vp), vsh.ctypes.data_as(_vp)))
+        return vsv, vsh
 
     # ---- matrix-vector products of the inversion step (reference aprod) ---------------------------
     def spmv_load(self, m, n, rw, row, col):

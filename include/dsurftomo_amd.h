@@ -480,6 +480,33 @@ int dsa_dispersion_get_model(dsa_engine* e, float* vels);
 int dsa_columns_resolution(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* measures,
                            double* leverage, double* trace, double* R, int* nused, int* flag);
 
+/* Radial anisotropy in the depth inversion (extension): Rayleigh waves see Vsv, Love waves see Vsh.
+ * dsa_dispersion_begin_radial: dsa_dispersion_begin with two models vsv and vsh (each in its layout) on one set of depths.  The stage stays a
+ * one-model stage -- depth kernels allowed, every size and limit dsa_dispersion_begin's -- that keeps Vsh resident beside Vsv: afterwards
+ * dsa_dispersion_run reads Vsh when iwave == 1 (Love) and Vsv when iwave == 2 (Rayleigh), for the curves, the depth kernels and the replay of a
+ * logged failure.  With vsh == vsv every map, kernel, mark and diagnostic is dsa_dispersion_begin's, bit for bit.  Any other begin ends the
+ * radial stage.  dsa_maps_from_dispersion, dsa_dispersion_fetch, dsa_dispersion_copy_maps and dsa_dispersion_diagnostics work as on any stage;
+ * dsa_columns_step, dsa_columns_resolution, dsa_dispersion_get_model and dsa_kernels_from_dispersion (whose combined sensitivities assume one
+ * model for all slots) are DSA_ERR_STATE on a radial stage.
+ * dsa_columns_step_radial: dsa_columns_step on a radial stage, with its state and argument rules, messages and order, and aniso finite and
+ * >= 0 (DSA_ERR_ARGUMENT); DSA_ERR_STATE on a stage that is not radial.  Slot k is a Love slot iff it was run with iwave == 1.  Per column,
+ * 2M unknowns x = [dVsv ; dVsh], M = nz-1: g_kl = a_k S_kl with S of dsa_kernels_from_dispersion's rule on the model the slot was run on; a
+ * Rayleigh datum touches only the Vsv block and a Love datum only the Vsh block (the cross sensitivities are neglected).  Minimised:
+ * |G x - rho|^2 + smooth^2 (|L x_v|^2 + |L x_h|^2) + damp^2 |x|^2 + aniso^2 |(vsh + x_h) - (vsv + x_v)|^2, by the step's L D L^T on the packed
+ * 2M x 2M normal matrix, fp64, every sum sequential; both models are clipped and stepped as dsa_columns_step steps one, where they lie.  At
+ * aniso = 0 each block's step has the bits of dsa_columns_step on that model with the other wave type's weights 0.
+ *   dv     2*(nz-1)*nx*ny floats: the Vsv block, then the Vsh block, each as dsa_columns_step's
+ *   nused, chi2  2*nx*ny: the Rayleigh data's, then the Love data's;  flag  nx*ny: 1 as dsa_columns_step's, 2 no datum of either type used
+ *          (whatever damp and aniso are); a column with one type unused still steps.  Any of the four may be NULL.
+ * Everything is checked before the device is touched, except DSA_ERR_DEVICE: a column's work arrays (98 232 bytes at nz = 64 with 60 maps)
+ * exceed the LDS a block of the device may have, or the device refuses that size.
+ * dsa_dispersion_get_model_radial: the two resident models; either pointer may be NULL.  DSA_ERR_STATE on a stage that is not radial. */
+int dsa_dispersion_begin_radial(dsa_engine* e, int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk,
+                                int kmax_total, int nmaps_total);
+int dsa_columns_step_radial(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax,
+                            float minvel, float maxvel, float* dv, int* nused, double* chi2, int* flag);
+int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);

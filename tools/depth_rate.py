@@ -10,6 +10,10 @@ and with the full R, and at the stage's limits on a 5 x 5 grid (nz = 64, K = 60:
 launch that asks for more than 64 KB of LDS) -- the wall time of the whole call, `repeats` timed calls after a warm-up one (the call leaves
 the state as it is, so the runs are not repeated); k_column_resolution's own time is the kernel trace's.
 
+The radial leg: the four-wave-type plan on a radial stage, Vsh 3 % above Vsv -- the iteration's runs next to
+dsa_columns_step_radial, timed as the first leg is -- and one step at the stage's limits (the one launch above 64 KB of LDS);
+k_column_step_radial's own time stands beside k_column_step's in the same kernel trace.
+
     python tools/depth_rate.py [repeats]      (needs the GPU)
 """
 import os
@@ -53,6 +57,7 @@ def main():
         assert not out["flag"].any() and out["nused"].sum() == kmax * (c["nx"] - 2) * (c["ny"] - 2)
         print("%-20s %d x %d x %d, K = %d, %d dispersion_run: median of %d -- runs %.3f ms wall (%.3f ms on the device), columns_step %.3f ms wall; all steps: %s" %
               (name, c["nx"], c["ny"], c["nz"], kmax, len(plan), repeats, np.median(runs), np.median(dev), np.median(step), " ".join("%.3f" % s for s in step)))
+    radial_leg(e, repeats, "radial, four types", vel, c["depz"], c["minthk"], depth.slot_plan(cases[1][1]), kmax, float(c["minvel"]), float(c["maxvel"]))
     resolution_leg(e, repeats, "the example's grid", vel, c["depz"], c["minthk"], depth.slot_plan(c), kmax)
     nz = 64
     k = np.arange(nz)[:, None, None]; i = np.arange(5)[None, None, :]; j = np.arange(5)[None, :, None]
@@ -60,7 +65,33 @@ def main():
     depz = np.concatenate([[0.0], np.cumsum(np.round(2.0 + 4.0 * np.arange(nz - 1) / (nz - 2)))]).astype(np.float32)
     phase, group = np.linspace(3.0, 45.0, 15), np.linspace(4.0, 46.0, 15)
     resolution_leg(e, repeats, "the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60)
+    radial_leg(e, 1, "radial, the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60, 0.5, 6.0)
     e.close()
+
+
+def radial_leg(e, repeats, name, vel, depz, minthk, plan, kmax, minvel, maxvel):
+    nz, ny, nx = vel.shape
+    vsh = vel.copy()
+    vsh[:-1] = vsh[:-1] * np.float32(1.03)
+    e.dispersion_begin_radial(vel, vsh, depz, minthk, kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    pv = e.dispersion_fetch(0, kmax)
+    obs = np.where(pv > 0, pv * 1.02, 0.0).astype(np.float32)
+    runs, dev, step = [], [], []
+    for it in range(repeats + 1):
+        ms0 = e.stats()["ms_dispersion"]
+        t0 = time.perf_counter()
+        for wave, kind, tt, first in plan:
+            e.dispersion_run(wave, kind, tt, True, first, first)
+        t1 = time.perf_counter()
+        out = e.columns_step_radial(obs, None, depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP, depth.DEFAULT_ANISO, 1e-4, minvel, maxvel)
+        t2 = time.perf_counter()
+        if it:
+            runs.append(1e3 * (t1 - t0)); dev.append(e.stats()["ms_dispersion"] - ms0); step.append(1e3 * (t2 - t1))
+    assert not out["flag"].any() and out["nused"].sum() == int((pv.reshape(kmax, ny, nx)[:, 1:-1, 1:-1] > 0).sum())
+    print("%-20s %d x %d x %d, K = %d, %d dispersion_run: median of %d -- runs %.3f ms wall (%.3f ms on the device), columns_step_radial %.3f ms wall; all steps: %s" %
+          (name, nx, ny, nz, kmax, len(plan), repeats, np.median(runs), np.median(dev), np.median(step), " ".join("%.3f" % s for s in step)))
 
 
 def resolution_leg(e, repeats, name, vel, depz, minthk, plan, kmax):
