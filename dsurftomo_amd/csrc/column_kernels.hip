@@ -4,11 +4,13 @@
 // triangle of N (then L), and five short vectors -- 2.5 KB for the Taipei example (M = 8, K = 26: a CU's 160 KB hold more blocks than its
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
-// k_column_step_radial, last: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
+// k_column_step_radial: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
+// k_lateral_* (DESIGN.md section 24), last: the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
 #include "column_radial.h"
+#include "column_lateral.h"
 
 namespace dsa {
 
@@ -107,6 +109,78 @@ __global__ void __launch_bounds__(64) k_column_step_radial(int nx, int ny, int n
     if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
 }
 
+// The laterally coupled step: column_lateral.h on every interior column, the launch shape and the column of a block as
+// above -- block b is interior column b of the header.  ws: lateral_ws_doubles(nvx, nvy, M) doubles in global memory, where N, the factor,
+// the vectors, the columns' dot products, the scalars and the done flag lie between the launches.  No kernel waits for another block: what
+// a column needs of its neighbours was written by an earlier launch.
+// k_lateral_setup: assemble and factor in LDS (k_column_step's arrays), N, the factor and b to the workspace; nused / chi2 / flag: (ncol).
+__global__ void __launch_bounds__(64) k_lateral_setup(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                     const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp, float lateral,
+                                                     double* __restrict__ ws_base, int* __restrict__ nused, double* __restrict__ chi2, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int nvx = nx - 2, M = nz - 1;
+    const long long ncol = (long long)nx * ny;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    if (bj >= ny - 2) return;
+    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    ColumnIn in;
+    in.M = M; in.K = K;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    const ColumnWork w = column_work(column_lds, M, K);
+    const LateralWs ws = lateral_ws(ws_base, nvx, ny - 2, M, lateral);
+    int n = 0;
+    double x2 = 0.0;
+    const int f = lateral_setup(in, smooth, damp, w, ws, (int)blockIdx.x, &n, &x2, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n; chi2[c] = x2; flag[c] = f; }
+}
+
+// the right-hand side with the edges' part, x0 and the columns' figures of rz0
+__global__ void __launch_bounds__(64) k_lateral_start(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, const float* __restrict__ vels)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    lateral_start(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, vels, (long long)(nvx + 2) * (nvy + 2), (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// r0, z0 and the columns' figures of the first rz
+__global__ void __launch_bounds__(64) k_lateral_residual(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    lateral_residual(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the two kernels of an iteration: the new direction and q = A p; the update of x and r, z = M^-1 r.  Both return at once when done is set.
+__global__ void __launch_bounds__(64) k_lateral_direction(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    lateral_direction(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+__global__ void __launch_bounds__(64) k_lateral_update(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    lateral_update(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the global sums, one wavefront: lane t is chain t; lane 0 adds the chains and sets the scalars
+__global__ void __launch_bounds__(64) k_lateral_reduce(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, int what, double tol, int maxit)
+{
+    __shared__ double chains[kLateralChains];
+    lateral_reduce(lateral_ws(ws_base, nvx, nvy, M, lateral), what, tol, maxit, chains, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the clipped steps and the stepped model; dv: (M, ncol)
+__global__ void __launch_bounds__(64) k_lateral_finish(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, float dvmax, float minvel, float maxvel,
+                                                      float* __restrict__ vels, float* __restrict__ dv)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    const long long ncol = (long long)(nvx + 2) * (nvy + 2);
+    lateral_finish(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, dvmax, minvel, maxvel, vels, ncol, dv, ncol, (int)threadIdx.x, 64);
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -165,5 +239,46 @@ int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigne
                        smooth, damp, aniso, dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv, d_nused, d_chi2, d_flag);
     return 0;
 }
+
+size_t column_lateral_ws_bytes(int nx, int ny, int nz) { return lateral_ws_doubles(nx - 2, ny - 2, nz - 1) * sizeof(double); }
+
+void launch_lateral_setup(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                          float lateral, double tol, double* d_ws, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return;
+    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
+    const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
+    hipLaunchKernelGGL(k_lateral_setup, grid, dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, lateral, d_ws, d_nused, d_chi2, d_flag);
+    hipLaunchKernelGGL(k_lateral_start, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, d_vels);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumRz0, tol, 0);
+}
+
+void launch_lateral_first(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    hipLaunchKernelGGL(k_lateral_residual, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumFirst, tol, maxit);
+}
+
+void launch_lateral_iteration(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
+    hipLaunchKernelGGL(k_lateral_direction, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumPq, tol, maxit);
+    hipLaunchKernelGGL(k_lateral_update, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumRz, tol, maxit);
+}
+
+void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    hipLaunchKernelGGL(k_lateral_finish, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, dvmax, minvel, maxvel,
+                       d_vels, d_dv);
+}
+
+// where the done flag, the count and the stop code (3 ints) and the scalars lie in the workspace, for the host's copies
+const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).ic; }
+const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).sc; }
 
 }  // namespace dsa

@@ -322,6 +322,12 @@ struct Engine {
     int columns_step_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel,
                             float* dv, int* nused, double* chi2, int* flag);
     int dispersion_get_model_radial(float* vsv, float* vsh);
+    // laterally coupled step (dsa_columns_step_lateral, k_lateral_*): dsa_columns_step's state, arguments and outputs; the
+    // workspace of the conjugate-gradient loop stays between calls.  The host looks at the loop's done flag every lateral_poll iterations.
+    OwnedBuf<double> col_lat;
+    static constexpr int lateral_poll = 16;
+    int columns_step_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel, float maxvel,
+                             double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
 
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;

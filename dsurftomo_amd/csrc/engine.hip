@@ -19,6 +19,7 @@
 #include "spmv_state.h"
 #include "column_system.h"
 #include "column_radial.h"
+#include "column_lateral.h"
 
 namespace dsa {
 
@@ -594,6 +595,68 @@ int Engine::columns_step_radial(int nmaps_in, const float* obs, const float* wt,
     if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
     if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_step_lateral: dsa_columns_step with the interior columns tied to their neighbours, column_lateral.h's
+// preconditioned conjugate gradients.  The state and argument rules are columns_front's, then lateral, tol, maxit and the size of the
+// workspace (alone against the whole of dsa_set_memory_budget, where one is set: not against what the budget leaves beside the other buffers);
+// everything is checked before the device is touched.  The loop is bounded by maxit here; its scalars and its done flag stay on
+// the device, an iteration started after the flag is set does nothing, so how often the host looks at the flag cannot change a bit.
+int Engine::columns_step_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel, float maxvel,
+                                 double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info)
+{
+    if (int rc = columns_front("columns_step_lateral", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
+    if (!std::isfinite(lateral) || lateral < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: lateral %g must be finite and >= 0", (double)lateral); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(tol) || tol <= 0.0) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: tol %g must be finite and > 0", tol); return DSA_ERR_ARGUMENT; }
+    if (maxit < 1) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: maxit %d must be at least 1", maxit); return DSA_ERR_ARGUMENT; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    const size_t ws_bytes = column_lateral_ws_bytes(disp_nx, disp_ny, disp_nz);
+    if (mem_budget && ws_bytes > mem_budget) {
+        fail(DSA_ERR_CAPACITY, "columns_step_lateral: the workspace of %d x %d columns of %d unknowns needs %zu bytes, the memory budget is %zu", disp_nx - 2, disp_ny - 2, M, ws_bytes, mem_budget);
+        return DSA_ERR_CAPACITY;
+    }
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, ncol * M) || ensure(col_nused, ncol) ||
+        ensure(col_chi2, ncol) || ensure(col_flag, ncol) || ensure(col_lat, ws_bytes / sizeof(double))) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernels run on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, ncol * M * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
+    launch_lateral_setup(disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, lateral, tol, col_lat.p, vels_d.p, col_nused.p,
+                         col_chi2.p, col_flag.p, stream);
+    launch_lateral_first(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, tol, maxit, stream);
+    HIP_TRY(this, hipGetLastError());
+    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
+    const int* d_ints = column_lateral_ints(col_lat.p, disp_nx, disp_ny, disp_nz);
+    for (int it = 1; lateral > 0.0f && it <= maxit; ++it) {
+        launch_lateral_iteration(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, tol, maxit, stream);
+        if (it % lateral_poll == 0 && it < maxit) {
+            HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(this, hipStreamSynchronize(stream));
+            if (ints[1]) break;
+        }
+    }
+    launch_lateral_finish(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, dvmax, minvel, maxvel, vels_d.p, col_dv.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    for (DispMark& m : disp_map_mark) m.fresh = false;
+    for (DispMark& m : disp_slot_mark) m.fresh = false;
+    h_vels.resize(ncol * disp_nz);
+    double rz[2] = { 0.0, 0.0 };          // the last rz, rz0
+    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(rz, column_lateral_scalars(col_lat.p, disp_nx, disp_ny, disp_nz), sizeof rz, hipMemcpyDeviceToHost, stream));
+    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, ncol * M * 4, hipMemcpyDeviceToHost, stream));
+    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    if (info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
     return 0;
 }
 
@@ -2093,6 +2156,13 @@ int dsa_columns_step_radial(dsa_engine* e, int nmaps, const float* obs, const fl
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_step_radial(nmaps, obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel, dv, nused, chi2, flag);
+}
+
+int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel,
+                             float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_step_lateral(nmaps, obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, tol, maxit, dv, nused, chi2, flag, info);
 }
 
 int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh)

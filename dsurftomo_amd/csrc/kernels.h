@@ -322,6 +322,19 @@ size_t column_radial_lds_bytes(int nz, int K);
 int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
                               const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
                               float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
+// The laterally coupled step (column_lateral.h).  d_ws: column_lateral_ws_bytes bytes.  launch_lateral_setup: assemble and
+// factor every interior column, the right-hand side, x0 and rz0 (three launches); launch_lateral_first: the first residual and the criterion
+// at iteration 0; launch_lateral_iteration: one iteration, four launches that do nothing once the done flag is set; launch_lateral_finish:
+// the clipped steps to d_dv (nz - 1, ncol) and the stepped model.  column_lateral_ints: the device address of the iteration count, the done
+// flag and the stop code (3 ints); column_lateral_scalars: of rz, rz0 (the first two doubles).
+size_t column_lateral_ws_bytes(int nx, int ny, int nz);
+void launch_lateral_setup(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                          float lateral, double tol, double* d_ws, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
+void launch_lateral_first(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream);
+void launch_lateral_iteration(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream);
+void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, hipStream_t stream);
+const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz);
+const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

@@ -2,6 +2,7 @@
 
     python -m dsurftomo_amd.depth <directory with DSurfTomo.in, the data file and MOD> [--maps FILE] [--iterations N] [--smooth L] [--damp D]
                                   [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]] [--radial [--aniso G]]
+                                  [--lateral W [--lateral-tol T] [--lateral-maxit N]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -40,6 +41,15 @@ sqrt((2 Vsv^2 + Vsh^2) / 3) and xi of every node.  <input>DepthRadialFit.dat (wr
 and the rms before the first and the last step per wave type, and the flag of the last step.  Depth.dat and DepthFit.dat are not written.
 column_radial_twin is the NumPy twin (csrc/column_radial.h is the arithmetic).
 
+--lateral W: the interior columns are stepped together by columns_step_lateral, tied by a penalty of weight W (in the
+units of --damp) on the difference of the stepped model between neighbouring columns -- the noise of the maps no longer goes straight into
+column-to-column speckle, and a column without a used datum (masked by --min-dws, or without roots) is carried by its neighbours in place
+of keeping its starting values.  The coupled system is solved by preconditioned conjugate gradients to the relative tolerance
+--lateral-tol T (default 1e-8) in at most --lateral-maxit N iterations (default 500).  --radial and --resolution are refused with it.
+Depth.dat and DepthFit.dat keep their formats; the log adds per iteration the conjugate-gradient iterations, how they stopped (1: the
+tolerance was met, 2: N was reached) and the number of columns without data that were carried.  Without the flag nothing changes.
+column_lateral_twin is the NumPy twin (csrc/column_lateral.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -57,6 +67,8 @@ DEFAULT_SMOOTH = 0.5
 DEFAULT_DAMP = 0.1
 DEFAULT_DVMAX = 0.5
 DEFAULT_ANISO = 0.2
+DEFAULT_LATERAL_TOL = 1e-8
+DEFAULT_LATERAL_MAXIT = 500
 
 _F64 = lambda *names: tuple((n, "%.17g", "f64") for n in names)
 DEPTH_TABLE = (True, _F64("lon", "lat", "depth", "vs"))
@@ -253,6 +265,156 @@ def column_radial_twin(obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, dvma
     return out
 
 
+def lateral_sum(part):
+    """the global sum of csrc/column_lateral.h: 64 chains -- chain t adds part[t], part[t + 64], ... from 0.0 -- added with t ascending"""
+    total = 0.0
+    for t in range(64):
+        c = 0.0
+        for v in part[t::64]:
+            c = c + float(v)
+        total = total + c
+    return total
+
+
+def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
+    """dsa_columns_step_lateral in NumPy (csrc/column_lateral.h) on an (ny, nx) grid of columns, the outer ring included as the engine holds
+    it: obs, wt (K, ny * nx) fp32 (wt may be None), pv (K, ny * nx), S (M, K, ny * nx), vels (M or more, ny * nx) fp32, of which the first M
+    rows of the interior columns are stepped.  Two answers: delta, the preconditioned conjugate gradients in the header's order (the
+    columns' N, b and factors through _twin_normal / _twin_factor / _twin_solve, every dot product per column and then lateral_sum), and,
+    independently of that, delta_lstsq from numpy.linalg.lstsq on the stacked [blockdiag(G_c); smooth L; damp I; lateral E] of the active
+    columns with right-hand side [rho; 0; 0; -lateral E v], E the edge differences -- another algorithm, for the size of the rounding error.
+    Returns dict(delta, delta_lstsq (M, ny * nx) fp64, dv (M,
+    ny * nx) fp32 and vels (the stepped copy) from delta, nused, chi2, flag (ny * nx), deg (ny * nx), itn, istop, rz0, rz)."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64)
+    M, K, ncol = S.shape
+    assert ncol == nx * ny and obs.shape == (K, ncol)
+    wt = np.ones((K, ncol), f) if wt is None else np.asarray(wt, f)
+    vels = np.array(vels, f, copy=True)
+    lam, mu, lat = float(f(smooth)), float(f(damp)), float(f(lateral))
+    lam2, mu2, lat2 = lam * lam, mu * mu, lat * lat
+    out = dict(delta=np.zeros((M, ncol)), delta_lstsq=np.zeros((M, ncol)), dv=np.zeros((M, ncol), f), vels=vels, nused=np.zeros(ncol, np.int32), chi2=np.zeros(ncol),
+               flag=np.zeros(ncol, np.int32), deg=np.zeros(ncol, np.int32), itn=0, istop=0, rz0=0.0, rz=0.0)
+    interior = [j * nx + i for j in range(1, ny - 1) for i in range(1, nx - 1)]
+    col = {}                                                            # the active columns: G, used, rho, N, factor, b
+    for c in interior:
+        used = (wt[:, c] > 0) & (obs[:, c] > 0) & (pv[:, c] > 0)
+        a = wt[:, c].astype(np.float64)
+        rho = np.where(used, a * (obs[:, c].astype(np.float64) - pv[:, c]), 0.0)
+        chi2 = 0.0
+        for k in np.flatnonzero(used):
+            chi2 = chi2 + rho[k] * rho[k]
+        out["nused"][c] = int(used.sum()); out["chi2"][c] = chi2
+        if not used.any() and lat == 0.0:
+            out["flag"][c] = 2
+            continue
+        G = np.zeros((K, M))
+        G[used] = a[used, None] * S[:, used, c].T
+        N, b = _twin_normal(G, used, rho, lam2, mu2)
+        factor = _twin_factor(N)
+        if factor is None:
+            out["flag"][c] = 1
+            continue
+        col[c] = dict(G=G, used=used, rho=rho, N=N, factor=factor, b=b)
+    edges = {c: [n for n in (c - 1, c + 1, c - nx, c + nx) if n in col] if lat > 0.0 else [] for c in col}
+    for c in col:
+        out["deg"][c] = len(edges[c])
+    v64 = vels[:M].astype(np.float64)
+    order = [c for c in interior]                                       # the dots' figures lie in interior-column order, 0.0 where not active
+    dot = lambda u, w: lateral_sum([_chain_dot(u[c], w[c]) if c in col else 0.0 for c in order])
+
+    def apply(y):
+        q = {}
+        for c, d in col.items():
+            t = np.zeros(M)
+            for j in range(M):
+                t = t + d["N"][:, j] * y[c][j]
+            s = np.zeros(M)
+            for n in edges[c]:
+                s = s + y[n]
+            q[c] = t + lat2 * (float(len(edges[c])) * y[c] - s)
+        return q
+
+    solve = lambda r: {c: _twin_solve(*col[c]["factor"], r[c]) for c in col}
+    bt = {}
+    for c, d in col.items():
+        s = np.zeros(M)
+        for n in edges[c]:
+            s = s + (v64[:, c] - v64[:, n])
+        bt[c] = d["b"] - lat2 * s if lat > 0.0 else d["b"].copy()
+    x = solve(bt)
+    rz0 = dot(bt, x)
+    thr = (float(tol) * float(tol)) * rz0
+    q = apply(x)
+    r = {c: bt[c] - q[c] for c in col}
+    z = solve(r)
+    rz = dot(r, z)
+    itn, istop = 0, 0
+    if lat == 0.0 or rz <= thr:
+        istop = 1
+    p_old = {c: np.zeros(M) for c in col}
+    beta = 0.0
+    while not istop:
+        p = {c: z[c] + beta * p_old[c] for c in col}
+        q = apply(p)
+        alpha = rz / dot(p, q)
+        x = {c: x[c] + alpha * p[c] for c in col}
+        r = {c: r[c] - alpha * q[c] for c in col}
+        z = solve(r)
+        new = dot(r, z)
+        beta = new / rz
+        rz = new
+        p_old = p
+        itn += 1
+        if rz <= thr:
+            istop = 1
+        elif itn >= maxit:
+            istop = 2
+    out.update(itn=itn, istop=istop, rz0=float(rz0), rz=float(rz))
+    for c in col:
+        out["delta"][:, c] = x[c]
+    # the other answer
+    if col:
+        index = {c: q for q, c in enumerate(col)}
+        rows, rhs = [], []
+        Lm = column_l(M)
+        for c, d in col.items():
+            o = index[c] * M
+            for block, right in ((d["G"][d["used"]], d["rho"][d["used"]]), (lam * Lm, np.zeros(Lm.shape[0])), (mu * np.eye(M), np.zeros(M))):
+                full = np.zeros((block.shape[0], len(col) * M))
+                full[:, o:o + M] = block
+                rows.append(full); rhs.append(right)
+        for c in col:
+            for n in edges[c]:
+                if n > c:
+                    full = np.zeros((M, len(col) * M))
+                    full[:, index[c] * M:index[c] * M + M] = lat * np.eye(M)
+                    full[:, index[n] * M:index[n] * M + M] = -lat * np.eye(M)
+                    rows.append(full); rhs.append(-lat * (v64[:, c] - v64[:, n]))
+        sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
+        for c in col:
+            out["delta_lstsq"][:, c] = sol[index[c] * M:index[c] * M + M]
+    s = out["delta"].astype(f)
+    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
+    with np.errstate(invalid="ignore"):
+        s = np.where(s >= dvmax, dvmax, s)
+        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
+        for c in col:
+            v = (vels[:M, c] + s[:, c]).astype(f)
+            v = np.where(v < minvel, minvel, v)
+            vels[:M, c] = np.where(v > maxvel, maxvel, v)
+    out["dv"] = s
+    return out
+
+
+def _chain_dot(u, w):
+    """sum_l u[l] w[l], l ascending from 0.0"""
+    s = 0.0
+    for a, b in zip(u, w):
+        s = s + float(a) * float(b)
+    return s
+
+
 def _resolution_measures(T, G, used, depz):
     """R = T^T G and what column_resolution.h reduces from it, every sum from 0.0 in the header's order: over the used k ascending, over l
     and j ascending.  Returns dict(R (M, M), measures (4, M): R_jj, m1, m2, var; leverage (K); trace)."""
@@ -357,8 +519,8 @@ def dws_weights(dws, min_dws):
 
 # ---- the loop ----
 
-def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None, aniso=None):
-    """the driver's preconditions, checked before the library is loaded (ValueError)"""
+def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None, aniso=None, lateral=None, lateral_tol=None, lateral_maxit=None):
+    """the driver's preconditions, checked before the library is loaded (ValueError); the lateral ones come after the others"""
     if iterations is not None and iterations < 1:
         raise ValueError("--iterations must be at least 1, not %r" % (iterations,))
     for name, v in (("--smooth", smooth), ("--min-dws", min_dws), ("--aniso", aniso)):
@@ -367,6 +529,12 @@ def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sig
     for name, v in (("--damp", damp), ("--dvmax", dvmax), ("--sigma", sigma)):
         if v is not None and not (np.isfinite(v) and v > 0):
             raise ValueError("%s must be finite and > 0, not %r" % (name, v))
+    if lateral is not None and not (np.isfinite(lateral) and lateral >= 0):
+        raise ValueError("--lateral must be finite and >= 0, not %r" % (lateral,))
+    if lateral_tol is not None and not (np.isfinite(lateral_tol) and lateral_tol > 0):
+        raise ValueError("--lateral-tol must be finite and > 0, not %r" % (lateral_tol,))
+    if lateral_maxit is not None and lateral_maxit < 1:
+        raise ValueError("--lateral-maxit must be at least 1, not %r" % (lateral_maxit,))
 
 
 def rms_of(chi2, nused):
@@ -375,19 +543,35 @@ def rms_of(chi2, nused):
     return float(np.sqrt(np.sum(np.asarray(chi2, np.float64)) / n)) if n > 0 else 0.0
 
 
-def iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, minvel, maxvel, log=print):
+def check_lateral(radial=False, resolution=False):
+    """what --lateral asks of the other flags, before the library is loaded (ValueError)"""
+    if radial or resolution:
+        raise ValueError("--lateral and %s exclude each other: the lateral coupling of the %s is not computed" %
+                         (("--radial", "radial step") if radial else ("--resolution", "resolution")))
+
+
+def iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, minvel, maxvel, log=print, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
+            lateral_maxit=DEFAULT_LATERAL_MAXIT):
     """The loop on an engine whose dispersion stage holds the starting model (dispersion_begin with as many maps as kernel slots): per
-    iteration one dispersion_run with kernels per entry of plan (slot_plan), then columns_step.  Returns dict(history: one dict per iteration
-    {iteration, nused, chi2, rms (before the step), flagged1, flagged2}, steps: columns_step's result per iteration)."""
+    iteration one dispersion_run with kernels per entry of plan (slot_plan), then columns_step -- or, with lateral (not None),
+    columns_step_lateral.  Returns dict(history: one dict per iteration {iteration, nused, chi2, rms (before the step), flagged1, flagged2;
+    with lateral also itn, istop, carried (the step's own count)}, steps: the step's result per iteration)."""
     history, steps = [], []
     for it in range(1, iterations + 1):
         for wave, kind, t, first in plan:
             eng.dispersion_run(wave, kind, t, True, first, first)
-        out = eng.columns_step(obs, wt, smooth, damp, dvmax, minvel, maxvel)
+        if lateral is None:
+            out = eng.columns_step(obs, wt, smooth, damp, dvmax, minvel, maxvel)
+        else:
+            out = eng.columns_step_lateral(obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
         h = dict(iteration=it, nused=int(out["nused"].sum()), chi2=float(out["chi2"].sum()), rms=rms_of(out["chi2"], out["nused"]),
                  flagged1=int((out["flag"] == 1).sum()), flagged2=int((out["flag"] == 2).sum()))
         log(" depth iteration %d: %d data used, rms %.6f km/s before the step, %d columns flagged (%d not positive definite, %d without data)" %
             (it, h["nused"], h["rms"], h["flagged1"] + h["flagged2"], h["flagged1"], h["flagged2"]))
+        if lateral is not None:
+            h.update(itn=out["itn"], istop=out["istop"], carried=out["carried"])
+            log(" depth iteration %d (lateral %g): %d conjugate-gradient iterations, istop %d (%s), %d columns without data carried by their neighbours" %
+                (it, lateral, h["itn"], h["istop"], "the tolerance was met" if h["istop"] == 1 else "--lateral-maxit was reached", h["carried"]))
         history.append(h)
         steps.append(out)
     return dict(history=history, steps=steps)
@@ -621,11 +805,16 @@ def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, ou
 
 
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
-        log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO):
+        log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
+        lateral_maxit=DEFAULT_LATERAL_MAXIT):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
-    last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files)."""
-    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None)
+    last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
+    None): the loop steps with columns_step_lateral; the files are the same two."""
+    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, lateral, lateral_tol if lateral is not None else None,
+          lateral_maxit if lateral is not None else None)
+    if lateral is not None:
+        check_lateral(radial, resolution)
     if radial:
         check_radial(None, resolution)
     c = io.load(directory)
@@ -647,7 +836,7 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
             eng.close()
     try:
         eng.dispersion_begin(np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0)), c["depz"], c["minthk"], kmax, kmax)
-        out = iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, float(c["minvel"]), float(c["maxvel"]), log)
+        out = iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, float(c["minvel"]), float(c["maxvel"]), log, lateral, lateral_tol, lateral_maxit)
         out["vels"] = eng.dispersion_get_model()
         if resolution:
             rms = out["history"][-1]["rms"]
@@ -677,6 +866,9 @@ def parser():
     ap.add_argument("--sigma", type=float, default=None, metavar="S", help="standard deviation of the map values in km/s for the sd column (default: the rms before the last step)")
     ap.add_argument("--radial", action="store_true", help="radial anisotropy: invert the Rayleigh maps for Vsv(z) and the Love maps for Vsh(z) together")
     ap.add_argument("--aniso", type=float, default=DEFAULT_ANISO, metavar="G", help="with --radial: weight of the tie between Vsh and Vsv, >= 0 (default %g)" % DEFAULT_ANISO)
+    ap.add_argument("--lateral", type=float, default=None, metavar="W", help="couple neighbouring columns: weight of the penalty on their differences, >= 0 (default: columns alone)")
+    ap.add_argument("--lateral-tol", type=float, default=DEFAULT_LATERAL_TOL, metavar="T", help="with --lateral: relative tolerance of the conjugate gradients, > 0 (default %g)" % DEFAULT_LATERAL_TOL)
+    ap.add_argument("--lateral-maxit", type=int, default=DEFAULT_LATERAL_MAXIT, metavar="N", help="with --lateral: most conjugate-gradient iterations per step (default %d)" % DEFAULT_LATERAL_MAXIT)
     return ap
 
 
@@ -684,13 +876,18 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso)
+        with_lateral = a.lateral is not None          # (--lateral-tol and --lateral-maxit are looked at only with --lateral, as run() does)
+        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.lateral, a.lateral_tol if with_lateral else None,
+              a.lateral_maxit if with_lateral else None)
+        if a.lateral is not None:
+            check_lateral(a.radial, a.resolution)
         if a.radial:
             check_radial(None, a.resolution)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
-    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso)
+    run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso,
+        lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit)
     return 0
 
 

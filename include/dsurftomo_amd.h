@@ -507,6 +507,27 @@ int dsa_columns_step_radial(dsa_engine* e, int nmaps, const float* obs, const fl
                             float minvel, float maxvel, float* dv, int* nused, double* chi2, int* flag);
 int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh);
 
+/* dsa_columns_step_lateral: dsa_columns_step with neighbouring columns coupled (extension).  The state, obs, wt, smooth, damp,
+ * dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step's, with its rules, messages and order of refusals.  The step
+ * of all interior columns together minimises
+ *   sum_c [ |G_c x_c - rho_c|^2 + smooth^2 |L x_c|^2 + damp^2 |x_c|^2 ] + lateral^2 sum_edges |(v_c + x_c) - (v_c' + x_c')|^2
+ * over the edges between interior columns at +-1 and +-nx that both take part: the roughness of the stepped model, so that iterations
+ * converge to a laterally smooth model.  A column takes part if the factorisation of its own normal matrix succeeds (flag 1 otherwise: left
+ * alone, no edge touches it); with lateral > 0 a column without a used datum takes part too (nused 0, flag 0) and is carried by its
+ * neighbours.  The outer ring is never an unknown and never a neighbour.  The normal equations are solved by conjugate gradients
+ * preconditioned with the columns' own factors, from x0 = the preconditioner applied to the right-hand side, until r^T z <= tol^2 rz0
+ * (rz0 = that right-hand side's own r^T z) or maxit iterations; fp64, every sum in a fixed order (csrc/column_lateral.h), so the result has
+ * one value whatever computes it.  lateral = 0 is no iteration: every output and the stepped model are dsa_columns_step's bit for bit,
+ * flag 2 for a column without a used datum included.
+ *   info   4 doubles: the iterations done, istop (1: the criterion was met, 2: maxit), rz0, the last r^T z
+ * Afterwards as dsa_columns_step: the marks are cleared, the ring and the bottom depth are kept.
+ * Errors, all found before the device is touched: DSA_ERR_STATE and DSA_ERR_ARGUMENT as dsa_columns_step, in its order (a radial stage is
+ * DSA_ERR_STATE); then DSA_ERR_ARGUMENT: lateral not finite or < 0, tol not finite or <= 0, maxit < 1; DSA_ERR_CAPACITY: the loop's
+ * workspace (two triangles and eight vectors per interior column) exceeds dsa_set_memory_budget, where one is set -- the workspace alone
+ * is held against the whole budget, not against what the budget leaves beside the engine's other buffers. */
+int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax,
+                             float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);

@@ -14,7 +14,12 @@ The radial leg: the four-wave-type plan on a radial stage
 dsa_columns_step_radial, timed as the first leg is -- and one step at the stage's limits (the one launch above 64 KB of LDS);
 k_column_step_radial's own time stands beside k_column_step's in the same kernel trace.
 
-    python tools/depth_rate.py [repeats]      (needs the GPU)
+The lateral leg: dsa_columns_step_lateral on the example's grid and plan at lateral 0.2 and 1 (tol 1e-8), each timed
+call after fresh runs, next to dsa_columns_step on the same state: the conjugate-gradient iterations, the call's wall time, and an upper bound of the
+time per iteration: the difference of the two calls' wall times over itn, which also holds the set-up's extra launches, the host's look at
+the done flag every 16th iteration and the up to 15 empty iterations launched after the flag was set.
+
+    python tools/depth_rate.py [repeats] [lateral]      (needs the GPU; `lateral`: that leg alone)
 """
 import os
 import sys
@@ -37,6 +42,10 @@ def main():
     vel = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
     kmax = c["kmax"]
     e = Engine(0)
+    if "lateral" in sys.argv[2:]:
+        lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+        e.close()
+        return
     for name, case in cases:
         plan = depth.slot_plan(case)
         e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
@@ -66,7 +75,40 @@ def main():
     phase, group = np.linspace(3.0, 45.0, 15), np.linspace(4.0, 46.0, 15)
     resolution_leg(e, repeats, "the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60)
     radial_leg(e, 1, "radial, the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60, 0.5, 6.0)
+    lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
     e.close()
+
+
+def lateral_leg(e, repeats, vel, c, plan, kmax):
+    nz, ny, nx = vel.shape
+    e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    # up to 2 % off the model's own curves, the sign changing across the grid: on a laterally uniform model equal misfits everywhere would
+    # give every column the same step, which the coupling leaves alone (itn 0)
+    i = np.arange(nx)[None, :]; j = np.arange(ny)[:, None]
+    obs = (e.dispersion_fetch(0, kmax) * (1.0 + 0.02 * np.cos(0.9 * i + 0.5 * j).ravel()[None, :])).astype(np.float32)
+    args = (depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP)
+    clip = (1e-4, float(c["minvel"]), float(c["maxvel"]))
+
+    def timed(call):
+        wall = []
+        for it in range(repeats + 1):
+            for wave, kind, tt, first in plan:
+                e.dispersion_run(wave, kind, tt, True, first, first)
+            t0 = time.perf_counter()
+            out = call()
+            if it:
+                wall.append(1e3 * (time.perf_counter() - t0))
+        return out, wall
+
+    _, alone = timed(lambda: e.columns_step(obs, None, *args, *clip))
+    for lateral in (0.2, 1.0):
+        out, wall = timed(lambda: e.columns_step_lateral(obs, None, *args, lateral, *clip, depth.DEFAULT_LATERAL_TOL, depth.DEFAULT_LATERAL_MAXIT))
+        assert not out["flag"].any() and out["istop"] == 1 and out["itn"] >= 1
+        print("%-20s %d x %d x %d, K = %d: median of %d -- columns_step_lateral %.3f ms wall, itn %d (at most %.1f us per iteration: the whole difference over itn), columns_step %.3f ms wall; all calls: %s" %
+              ("lateral %g" % lateral, nx, ny, nz, kmax, repeats, np.median(wall), out["itn"], 1e3 * (np.median(wall) - np.median(alone)) / max(out["itn"], 1),
+               np.median(alone), " ".join("%.3f" % w for w in wall)))
 
 
 def radial_leg(e, repeats, name, vel, depz, minthk, plan, kmax, minvel, maxvel):
