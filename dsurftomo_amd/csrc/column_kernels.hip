@@ -5,12 +5,14 @@
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
 // k_column_step_radial: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
-// k_lateral_* (DESIGN.md section 24), last: the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
+// k_lateral_* (DESIGN.md section 24): the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
+// k_radial_lateral_* (DESIGN.md section 25), last: that loop on the radial step's 2M unknowns per column, with k_lateral_update and k_lateral_reduce as they are.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
 #include "column_radial.h"
 #include "column_lateral.h"
+#include "column_radial_lateral.h"
 
 namespace dsa {
 
@@ -181,6 +183,72 @@ __global__ void __launch_bounds__(64) k_lateral_finish(int nvx, int nvy, int M, 
     lateral_finish(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, dvmax, minvel, maxvel, vels, ncol, dv, ncol, (int)threadIdx.x, 64);
 }
 
+// The laterally coupled radial step: column_radial_lateral.h on every interior column, block b interior column b.  ws:
+// radial_lateral_ws_doubles(nvx, nvy, M) doubles in global memory -- column_lateral.h's workspace of 2M unknowns per column, on which
+// k_lateral_update and k_lateral_reduce run as they are.  No kernel waits for another block.
+// k_radial_lateral_setup: radial_assemble and the factorisation in LDS (k_column_step_radial's arrays and sizes), N, the factor and b to the
+// workspace; Sv / Sh, love, nused / chi2 (2, ncol), flag (ncol) as k_column_step_radial's.
+__global__ void __launch_bounds__(64) k_radial_lateral_setup(int nx, int ny, int nz, int K, unsigned long long love, const float* __restrict__ obs,
+                                                            const float* __restrict__ wt, const double* __restrict__ pv, const double* __restrict__ Sv,
+                                                            const double* __restrict__ Sh, float smooth, float damp, float aniso, float lateral,
+                                                            float lateral_aniso, const float* __restrict__ vsv, const float* __restrict__ vsh,
+                                                            double* __restrict__ ws_base, int* __restrict__ nused, double* __restrict__ chi2,
+                                                            int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int nvx = nx - 2, M = nz - 1;
+    const long long ncol = (long long)nx * ny;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    if (bj >= ny - 2) return;
+    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    RadialIn in;
+    in.M = M; in.K = K; in.love = love;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.Sv = Sv + c; in.Sh = Sh + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    const ColumnWork w = radial_work(column_lds, M, K);
+    const RadialLateralWs rl = radial_lateral_ws(ws_base, nvx, ny - 2, M, lateral, lateral_aniso);
+    int n[2] = { 0, 0 };
+    double x2[2] = { 0.0, 0.0 };
+    const int f = radial_lateral_setup(in, smooth, damp, aniso, vsv + c, vsh + c, ncol, w, rl, (int)blockIdx.x, n, x2, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
+}
+
+// the right-hand side with the edges' parts, x0 and the columns' figures of rz0
+__global__ void __launch_bounds__(64) k_radial_lateral_start(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base,
+                                                            const float* __restrict__ vsv, const float* __restrict__ vsh)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    radial_lateral_start(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, vsv, vsh, (long long)(nvx + 2) * (nvy + 2),
+                         (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// r0, z0 and the columns' figures of the first rz
+__global__ void __launch_bounds__(64) k_radial_lateral_residual(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    radial_lateral_residual(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the first kernel of an iteration: the new direction and q = A p; returns at once when done is set.  The second is k_lateral_update.
+__global__ void __launch_bounds__(64) k_radial_lateral_direction(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    radial_lateral_direction(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the clipped steps and the two stepped models; dv: (2, M, ncol)
+__global__ void __launch_bounds__(64) k_radial_lateral_finish(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base,
+                                                             float dvmax, float minvel, float maxvel, float* __restrict__ vsv, float* __restrict__ vsh,
+                                                             float* __restrict__ dv)
+{
+    if ((int)blockIdx.x >= nvx * nvy) return;
+    const long long ncol = (long long)(nvx + 2) * (nvy + 2);
+    radial_lateral_finish(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, dvmax, minvel, maxvel, vsv, vsh, ncol, dv,
+                          dv + (long long)M * ncol, ncol, (int)threadIdx.x, 64);
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -280,5 +348,67 @@ void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, 
 // where the done flag, the count and the stop code (3 ints) and the scalars lie in the workspace, for the host's copies
 const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).ic; }
 const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).sc; }
+
+size_t column_radial_lateral_ws_bytes(int nx, int ny, int nz) { return radial_lateral_ws_doubles(nx - 2, ny - 2, nz - 1) * sizeof(double); }
+
+namespace {
+// what k_lateral_update and k_lateral_reduce get as their `lateral`: they ask it only whether there are edges
+float radial_lateral_edges(float lateral, float lateral_aniso) { return (lateral > 0.0f || lateral_aniso > 0.0f) ? 1.0f : 0.0f; }
+}
+
+// launch_column_step_radial's rule for the LDS of the set-up kernel and its return values; nothing is launched unless 0 is returned
+int launch_radial_lateral_setup(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float lateral, float lateral_aniso, double tol,
+                                double* d_ws, const float* d_vsv, const float* d_vsh, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
+    const size_t lds = column_radial_lds_bytes(nz, K);
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
+    if (limit_out) *limit_out = limit;
+    if (lds > (size_t)limit) return 1;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_radial_lateral_setup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return 2;
+    }
+    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
+    hipLaunchKernelGGL(k_radial_lateral_setup, grid, dim3(64), lds, stream, nx, ny, nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh, smooth, damp, aniso, lateral,
+                       lateral_aniso, d_vsv, d_vsh, d_ws, d_nused, d_chi2, d_flag);
+    hipLaunchKernelGGL(k_radial_lateral_start, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws, d_vsv, d_vsh);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), radial_lateral_edges(lateral, lateral_aniso), d_ws,
+                       (int)kLatSumRz0, tol, 0);
+    return 0;
+}
+
+void launch_radial_lateral_first(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    hipLaunchKernelGGL(k_radial_lateral_residual, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), radial_lateral_edges(lateral, lateral_aniso), d_ws,
+                       (int)kLatSumFirst, tol, maxit);
+}
+
+void launch_radial_lateral_iteration(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
+    const float edges = radial_lateral_edges(lateral, lateral_aniso);
+    hipLaunchKernelGGL(k_radial_lateral_direction, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws, (int)kLatSumPq, tol, maxit);
+    hipLaunchKernelGGL(k_lateral_update, grid, dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws, (int)kLatSumRz, tol, maxit);
+}
+
+void launch_radial_lateral_finish(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vsv,
+                                  float* d_vsh, float* d_dv, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2) return;
+    hipLaunchKernelGGL(k_radial_lateral_finish, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws,
+                       dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv);
+}
+
+const int* column_radial_lateral_ints(double* d_ws, int nx, int ny, int nz) { return radial_lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f, 0.0f).ws.ic; }
+const double* column_radial_lateral_scalars(double* d_ws, int nx, int ny, int nz) { return radial_lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f, 0.0f).ws.sc; }
 
 }  // namespace dsa

@@ -328,6 +328,11 @@ struct Engine {
     static constexpr int lateral_poll = 16;
     int columns_step_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel, float maxvel,
                              double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
+    // laterally coupled radial step (dsa_columns_step_radial_lateral, k_radial_lateral_*): dsa_columns_step_radial's state,
+    // arguments and outputs, the loop and the poll of the lateral step; a workspace of its own (2 (nz - 1) unknowns per column)
+    OwnedBuf<double> col_rlat;
+    int columns_step_radial_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral, float lateral_aniso,
+                                    float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
 
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;

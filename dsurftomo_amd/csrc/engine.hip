@@ -20,6 +20,7 @@
 #include "column_system.h"
 #include "column_radial.h"
 #include "column_lateral.h"
+#include "column_radial_lateral.h"
 
 namespace dsa {
 
@@ -654,6 +655,84 @@ int Engine::columns_step_lateral(int nmaps_in, const float* obs, const float* wt
     if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, ncol * M * 4, hipMemcpyDeviceToHost, stream));
     if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    if (info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
+    return 0;
+}
+
+// dsa_columns_step_radial_lateral: dsa_columns_step_radial with the interior columns tied to their neighbours,
+// column_radial_lateral.h's system in column_lateral.h's conjugate gradients.  The state and argument rules are columns_step_radial's, then
+// lateral, lateral_aniso, tol, maxit and the size of the workspace against dsa_set_memory_budget (as columns_step_lateral holds its own);
+// everything is checked before the device is touched, except the LDS of the set-up kernel (DSA_ERR_DEVICE before anything is launched).  The
+// loop is columns_step_lateral's: bounded by maxit, the done flag looked at every lateral_poll iterations, which cannot change a bit.
+int Engine::columns_step_radial_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral, float lateral_aniso,
+                                        float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info)
+{
+    if (int rc = columns_front("columns_step_radial_lateral", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
+    if (!std::isfinite(aniso) || aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: aniso %g must be finite and >= 0", (double)aniso); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(lateral) || lateral < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: lateral %g must be finite and >= 0", (double)lateral); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(lateral_aniso) || lateral_aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: lateral_aniso %g must be finite and >= 0", (double)lateral_aniso); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(tol) || tol <= 0.0) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: tol %g must be finite and > 0", tol); return DSA_ERR_ARGUMENT; }
+    if (maxit < 1) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: maxit %d must be at least 1", maxit); return DSA_ERR_ARGUMENT; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    const size_t ws_bytes = column_radial_lateral_ws_bytes(disp_nx, disp_ny, disp_nz);
+    if (mem_budget && ws_bytes > mem_budget) {
+        fail(DSA_ERR_CAPACITY, "columns_step_radial_lateral: the workspace of %d x %d columns of %d unknowns needs %zu bytes, the memory budget is %zu", disp_nx - 2, disp_ny - 2, 2 * M, ws_bytes, mem_budget);
+        return DSA_ERR_CAPACITY;
+    }
+    const bool edges = lateral > 0.0f || lateral_aniso > 0.0f;
+    unsigned long long love = 0ull;
+    for (int k = 0; k < K; ++k) if (disp_slot_mark[(size_t)k].iwave == 1) love |= 1ull << k;
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_S, ncol * K * M) || ensure(col_Sh, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, 2 * ncol * M) ||
+        ensure(col_nused, 2 * ncol) || ensure(col_chi2, 2 * ncol) || ensure(col_flag, ncol) || ensure(col_rlat, ws_bytes / sizeof(double))) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernels run on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, 2 * ncol * M * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, 2 * ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, 2 * ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    const int shallow = h_depz[disp_nz - 2] < 35.0f ? 1 : 0;
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_S.p, stream);
+    launch_sen_combine((int)ncol, K, disp_nz, vsh_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_Sh.p, stream);
+    int limit = 0;
+    const int rc = launch_radial_lateral_setup(device, disp_nx, disp_ny, disp_nz, K, love, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p, smooth, damp,
+                                               aniso, lateral, lateral_aniso, tol, col_rlat.p, vels_d.p, vsh_d.p, col_nused.p, col_chi2.p, col_flag.p, stream, &limit);
+    if (rc) {
+        HIP_TRY(this, hipStreamSynchronize(stream));
+        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_step_radial_lateral: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", 2 * M, K, column_radial_lds_bytes(disp_nz, K), limit);
+        else fail(DSA_ERR_DEVICE, "columns_step_radial_lateral: the device refuses %zu bytes of dynamic LDS per workgroup", column_radial_lds_bytes(disp_nz, K));
+        return DSA_ERR_DEVICE;
+    }
+    launch_radial_lateral_first(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, tol, maxit, stream);
+    HIP_TRY(this, hipGetLastError());
+    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
+    const int* d_ints = column_radial_lateral_ints(col_rlat.p, disp_nx, disp_ny, disp_nz);
+    for (int it = 1; edges && it <= maxit; ++it) {
+        launch_radial_lateral_iteration(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, tol, maxit, stream);
+        if (it % lateral_poll == 0 && it < maxit) {
+            HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(this, hipStreamSynchronize(stream));
+            if (ints[1]) break;
+        }
+    }
+    launch_radial_lateral_finish(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, col_dv.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    for (DispMark& m : disp_map_mark) m.fresh = false;
+    for (DispMark& m : disp_slot_mark) m.fresh = false;
+    h_vels.resize(ncol * disp_nz);
+    h_vsh.resize(ncol * disp_nz);
+    double rz[2] = { 0.0, 0.0 };          // the last rz, rz0
+    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, h_vsh.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(rz, column_radial_lateral_scalars(col_rlat.p, disp_nx, disp_ny, disp_nz), sizeof rz, hipMemcpyDeviceToHost, stream));
+    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, 2 * ncol * M * 4, hipMemcpyDeviceToHost, stream));
+    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, 2 * ncol * 4, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
     if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     if (info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
@@ -2163,6 +2242,15 @@ int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const f
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_step_lateral(nmaps, obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, tol, maxit, dv, nused, chi2, flag, info);
+}
+
+int dsa_columns_step_radial_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral,
+                                    float lateral_aniso, float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2,
+                                    int* flag, double* info)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_step_radial_lateral(nmaps, obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, tol, maxit, dv,
+                                                                     nused, chi2, flag, info);
 }
 
 int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh)

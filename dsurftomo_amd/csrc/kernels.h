@@ -335,6 +335,20 @@ void launch_lateral_iteration(int nx, int ny, int nz, float lateral, double* d_w
 void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, hipStream_t stream);
 const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz);
 const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz);
+// The laterally coupled radial step (column_radial_lateral.h): the launches above on the two models, 2 (nz - 1) unknowns
+// per column.  d_ws: column_radial_lateral_ws_bytes bytes; love, d_Sv / d_Sh, d_nused / d_chi2 (2, ncol), d_dv (2, nz - 1, ncol) as
+// launch_column_step_radial's.  launch_radial_lateral_setup returns launch_column_step_radial's values (*limit_out always set): 1 or 2 before
+// anything is launched.  The iteration runs k_lateral_update and k_lateral_reduce on the workspace as they are.
+size_t column_radial_lateral_ws_bytes(int nx, int ny, int nz);
+int launch_radial_lateral_setup(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float lateral, float lateral_aniso, double tol,
+                                double* d_ws, const float* d_vsv, const float* d_vsh, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
+void launch_radial_lateral_first(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream);
+void launch_radial_lateral_iteration(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream);
+void launch_radial_lateral_finish(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vsv,
+                                  float* d_vsh, float* d_dv, hipStream_t stream);
+const int* column_radial_lateral_ints(double* d_ws, int nx, int ny, int nz);
+const double* column_radial_lateral_scalars(double* d_ws, int nx, int ny, int nz);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

@@ -50,6 +50,14 @@ Depth.dat and DepthFit.dat keep their formats; the log adds per iteration the co
 tolerance was met, 2: N was reached) and the number of columns without data that were carried.  Without the flag nothing changes.
 column_lateral_twin is the NumPy twin (csrc/column_lateral.h is the arithmetic).
 
+--radial --radial-lateral W [--radial-lateral-aniso A]: the radial step of all interior columns together, by
+columns_step_radial_lateral (also at W = 0).  W is --lateral's weight on the differences of the stepped Vsv and of the stepped Vsh between
+neighbouring columns, A (default W) the weight on the differences of the stepped anisotropy field Vsh - Vsv, so that xi can be smoothed more
+strongly than the velocities; a column without a used datum gets its xi from its neighbours in place of staying at 1.  --lateral-tol and
+--lateral-maxit apply.  --radial-lateral without --radial, --radial-lateral-aniso without --radial-lateral, and either with --lateral or
+--resolution are refused (--lateral with --radial stays refused as it was).  DepthRadial.dat and DepthRadialFit.dat keep their formats; the
+log adds per iteration what --lateral's adds.  column_radial_lateral_twin is the NumPy twin (csrc/column_radial_lateral.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -407,6 +415,168 @@ def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvm
     return out
 
 
+def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
+    """dsa_columns_step_radial_lateral in NumPy (csrc/column_radial_lateral.h) on an (ny, nx) grid of columns, the outer ring included as the
+    engine holds it: obs, wt (K, ny * nx) fp32 (wt may be None), pv (K, ny * nx), S (M, K, ny * nx) -- slot k's sensitivities to the model it
+    was run on, Vsh where love[k], else Vsv, as column_radial_twin's -- love (K) bool, vsv, vsh (M or more, ny * nx) fp32, of which the first M
+    rows of the interior columns are stepped.  The unknowns of a column are [dVsv ; dVsh].  Two answers: delta, the preconditioned conjugate
+    gradients in the header's order (the columns' N and b as column_radial_twin's, the factors through _twin_factor / _twin_solve, every dot
+    product per column and then lateral_sum), and, independently of that, delta_lstsq from numpy.linalg.lstsq on the stacked
+    [blockdiag(G_c); smooth L (+) smooth L; damp I; aniso [-I I]; lateral E_v; lateral E_h; lateral_aniso E_a] of the active columns with
+    right-hand side [rho; 0; 0; -aniso d; -lateral E vsv; -lateral E vsh; -lateral_aniso E (vsh - vsv)], E the edge differences -- another
+    algorithm, for the size of the rounding error.  Returns dict(delta, delta_lstsq (2M, ny * nx) fp64, dv (2, M, ny * nx) fp32, vsv, vsh (the
+    stepped copies) from delta, nused, chi2 (2, ny * nx): Rayleigh, Love; flag, deg (ny * nx), itn, istop, rz0, rz)."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64); love = np.asarray(love, bool)
+    M, K, ncol = S.shape
+    B = 2 * M
+    assert ncol == nx * ny and obs.shape == (K, ncol) and love.shape == (K,)
+    wt = np.ones((K, ncol), f) if wt is None else np.asarray(wt, f)
+    vsv = np.array(vsv, f, copy=True); vsh = np.array(vsh, f, copy=True)
+    lam, mu, gam, lat, lata = float(f(smooth)), float(f(damp)), float(f(aniso)), float(f(lateral)), float(f(lateral_aniso))
+    lam2, mu2, gam2, w2, wa2 = lam * lam, mu * mu, gam * gam, lat * lat, lata * lata
+    with_edges = lat > 0.0 or lata > 0.0
+    out = dict(delta=np.zeros((B, ncol)), delta_lstsq=np.zeros((B, ncol)), dv=np.zeros((2, M, ncol), f), vsv=vsv, vsh=vsh, nused=np.zeros((2, ncol), np.int32),
+               chi2=np.zeros((2, ncol)), flag=np.zeros(ncol, np.int32), deg=np.zeros(ncol, np.int32), itn=0, istop=0, rz0=0.0, rz=0.0)
+    interior = [j * nx + i for j in range(1, ny - 1) for i in range(1, nx - 1)]
+    v64 = vsv[:M].astype(np.float64); h64 = vsh[:M].astype(np.float64)
+    a64 = h64 - v64
+    col = {}                                                            # the active columns: G, used, rho, N, factor, b
+    for c in interior:
+        used = (wt[:, c] > 0) & (obs[:, c] > 0) & (pv[:, c] > 0)
+        a = wt[:, c].astype(np.float64)
+        rho = np.where(used, a * (obs[:, c].astype(np.float64) - pv[:, c]), 0.0)
+        chi2 = [0.0, 0.0]
+        for k in np.flatnonzero(used):
+            chi2[int(love[k])] = chi2[int(love[k])] + rho[k] * rho[k]
+        out["nused"][:, c] = [int((used & ~love).sum()), int((used & love).sum())]; out["chi2"][:, c] = chi2
+        if not used.any() and not with_edges:
+            out["flag"][c] = 2
+            continue
+        G = np.zeros((K, M))
+        G[used] = a[used, None] * S[:, used, c].T
+        N = np.zeros((B, B)); b = np.zeros(B)
+        for q, sel in enumerate((used & ~love, used & love)):
+            Nq, bq = _twin_normal(G, sel, rho, lam2, mu2)
+            Nq[np.diag_indices(M)] = Nq[np.diag_indices(M)] + gam2
+            N[q * M:(q + 1) * M, q * M:(q + 1) * M] = Nq
+            t = gam2 * a64[:, c]
+            b[q * M:(q + 1) * M] = bq - t if q else bq + t
+        N[M:, :M][np.diag_indices(M)] = 0.0 - gam2
+        N[:M, M:] = N[M:, :M].T
+        factor = _twin_factor(N)
+        if factor is None:
+            out["flag"][c] = 1
+            continue
+        col[c] = dict(G=G, used=used, rho=rho, N=N, factor=factor, b=b)
+    edges = {c: [n for n in (c - 1, c + 1, c - nx, c + nx) if n in col] if with_edges else [] for c in col}
+    for c in col:
+        out["deg"][c] = len(edges[c])
+    dot = lambda u, w: lateral_sum([_chain_dot(u[c], w[c]) if c in col else 0.0 for c in interior])
+
+    def apply(y):
+        q = {}
+        for c, d in col.items():
+            t = np.zeros(B)
+            for j in range(B):
+                t = t + d["N"][:, j] * y[c][j]
+            s = np.zeros(B); su = np.zeros(M)
+            for n in edges[c]:
+                s = s + y[n]
+                su = su + (y[n][M:] - y[n][:M])
+            deg = float(len(edges[c]))
+            fig = t + w2 * (deg * y[c] - s)
+            g = wa2 * (deg * (y[c][M:] - y[c][:M]) - su)
+            q[c] = np.concatenate([fig[:M] - g, fig[M:] + g])
+        return q
+
+    solve = lambda r: {c: _twin_solve(*col[c]["factor"], r[c]) for c in col}
+    bt = {}
+    for c, d in col.items():
+        sv = np.zeros(M); sh = np.zeros(M); sa = np.zeros(M)
+        for n in edges[c]:
+            sv = sv + (v64[:, c] - v64[:, n])
+            sh = sh + (h64[:, c] - h64[:, n])
+            sa = sa + (a64[:, c] - a64[:, n])
+        bt[c] = np.concatenate([(d["b"][:M] - w2 * sv) + wa2 * sa, (d["b"][M:] - w2 * sh) - wa2 * sa]) if with_edges else d["b"].copy()
+    x = solve(bt)
+    rz0 = dot(bt, x)
+    thr = (float(tol) * float(tol)) * rz0
+    q = apply(x)
+    r = {c: bt[c] - q[c] for c in col}
+    z = solve(r)
+    rz = dot(r, z)
+    itn, istop = 0, 0
+    if not with_edges or rz <= thr:
+        istop = 1
+    p_old = {c: np.zeros(B) for c in col}
+    beta = 0.0
+    while not istop:
+        p = {c: z[c] + beta * p_old[c] for c in col}
+        q = apply(p)
+        alpha = rz / dot(p, q)
+        x = {c: x[c] + alpha * p[c] for c in col}
+        r = {c: r[c] - alpha * q[c] for c in col}
+        z = solve(r)
+        new = dot(r, z)
+        beta = new / rz
+        rz = new
+        p_old = p
+        itn += 1
+        if rz <= thr:
+            istop = 1
+        elif itn >= maxit:
+            istop = 2
+    out.update(itn=itn, istop=istop, rz0=float(rz0), rz=float(rz))
+    for c in col:
+        out["delta"][:, c] = x[c]
+    # the other answer
+    if col:
+        index = {c: q for q, c in enumerate(col)}
+        width = len(col) * B
+        rows, rhs = [], []
+        Lm = column_l(M); Z = np.zeros_like(Lm); I = np.eye(M)
+
+        def put(c, block, right):
+            full = np.zeros((block.shape[0], width))
+            full[:, index[c] * B:index[c] * B + B] = block
+            rows.append(full); rhs.append(right)
+
+        for c, d in col.items():
+            u = d["used"]
+            Gc = np.zeros((int(u.sum()), B))
+            Gc[:, :M] = np.where(love[u, None], 0.0, d["G"][u]); Gc[:, M:] = np.where(love[u, None], d["G"][u], 0.0)
+            put(c, Gc, d["rho"][u])
+            put(c, lam * np.hstack([Lm, Z]), np.zeros(Lm.shape[0]))
+            put(c, lam * np.hstack([Z, Lm]), np.zeros(Lm.shape[0]))
+            put(c, mu * np.eye(B), np.zeros(B))
+            put(c, gam * np.hstack([-I, I]), -gam * a64[:, c])
+        for c in col:
+            for n in edges[c]:
+                if n > c:
+                    for weight, pick, field in ((lat, np.hstack([I, 0 * I]), v64), (lat, np.hstack([0 * I, I]), h64), (lata, np.hstack([-I, I]), a64)):
+                        if weight > 0.0:
+                            full = np.zeros((M, width))
+                            full[:, index[c] * B:index[c] * B + B] = weight * pick
+                            full[:, index[n] * B:index[n] * B + B] = -weight * pick
+                            rows.append(full); rhs.append(-weight * (field[:, c] - field[:, n]))
+        sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
+        for c in col:
+            out["delta_lstsq"][:, c] = sol[index[c] * B:index[c] * B + B]
+    s = out["delta"].astype(f)
+    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
+    with np.errstate(invalid="ignore"):
+        s = np.where(s >= dvmax, dvmax, s)
+        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
+        for c in col:
+            for vel, part in ((vsv, s[:M, c]), (vsh, s[M:, c])):
+                v = (vel[:M, c] + part).astype(f)
+                v = np.where(v < minvel, minvel, v)
+                vel[:M, c] = np.where(v > maxvel, maxvel, v)
+    out["dv"] = np.ascontiguousarray(s.reshape(2, M, ncol))
+    return out
+
+
 def _chain_dot(u, w):
     """sum_l u[l] w[l], l ascending from 0.0"""
     s = 0.0
@@ -519,7 +689,8 @@ def dws_weights(dws, min_dws):
 
 # ---- the loop ----
 
-def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None, aniso=None, lateral=None, lateral_tol=None, lateral_maxit=None):
+def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sigma=None, aniso=None, lateral=None, lateral_tol=None, lateral_maxit=None,
+          radial_lateral=None, radial_lateral_aniso=None):
     """the driver's preconditions, checked before the library is loaded (ValueError); the lateral ones come after the others"""
     if iterations is not None and iterations < 1:
         raise ValueError("--iterations must be at least 1, not %r" % (iterations,))
@@ -531,6 +702,9 @@ def check(iterations=None, smooth=None, damp=None, dvmax=None, min_dws=None, sig
             raise ValueError("%s must be finite and > 0, not %r" % (name, v))
     if lateral is not None and not (np.isfinite(lateral) and lateral >= 0):
         raise ValueError("--lateral must be finite and >= 0, not %r" % (lateral,))
+    for name, v in (("--radial-lateral", radial_lateral), ("--radial-lateral-aniso", radial_lateral_aniso)):
+        if v is not None and not (np.isfinite(v) and v >= 0):
+            raise ValueError("%s must be finite and >= 0, not %r" % (name, v))
     if lateral_tol is not None and not (np.isfinite(lateral_tol) and lateral_tol > 0):
         raise ValueError("--lateral-tol must be finite and > 0, not %r" % (lateral_tol,))
     if lateral_maxit is not None and lateral_maxit < 1:
@@ -711,20 +885,45 @@ def check_radial(c, resolution=False):
         raise ValueError("--radial needs Rayleigh and Love periods, the input lists %d and %d" % (nr, nl))
 
 
-def iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, minvel, maxvel, log=print):
+def check_radial_lateral(radial_lateral=None, radial_lateral_aniso=None, radial=False, lateral=None, resolution=False):
+    """what --radial-lateral and --radial-lateral-aniso ask of the other flags, before the library is loaded (ValueError)"""
+    if radial_lateral is None and radial_lateral_aniso is None:
+        return
+    if radial_lateral is None:
+        raise ValueError("--radial-lateral-aniso needs --radial-lateral: it is the weight of that coupling on Vsh - Vsv")
+    if not radial:
+        raise ValueError("--radial-lateral needs --radial: it couples the columns of the radial step (--lateral couples those of the isotropic one)")
+    if lateral is not None or resolution:
+        raise ValueError("--radial-lateral and %s exclude each other: %s" % (("--lateral", "--lateral couples the columns of the isotropic step") if lateral is not None
+                                                                            else ("--resolution", "the resolution of the coupled system is not computed")))
+
+
+def iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, minvel, maxvel, log=print, lateral=None, lateral_aniso=None,
+                   lateral_tol=DEFAULT_LATERAL_TOL, lateral_maxit=DEFAULT_LATERAL_MAXIT):
     """iterate on an engine whose stage is radial (dispersion_begin_radial): per iteration the runs of plan -- the Love runs read Vsh, the
-    Rayleigh runs Vsv -- then columns_step_radial.  Returns dict(history: one dict per iteration {iteration, nused, chi2, rms, nused_r,
-    nused_l, rms_r, rms_l (before the step), flagged1, flagged2}, steps: columns_step_radial's result per iteration)."""
+    Rayleigh runs Vsv -- then columns_step_radial -- or, with lateral (not None), columns_step_radial_lateral with the weights lateral and
+    lateral_aniso (None: lateral).  Returns dict(history: one dict per iteration {iteration, nused, chi2, rms, nused_r, nused_l, rms_r, rms_l
+    (before the step), flagged1, flagged2; with lateral also itn, istop, carried (the step's own count)}, steps: the step's result per
+    iteration)."""
+    if lateral is not None and lateral_aniso is None:
+        lateral_aniso = lateral
     history, steps = [], []
     for it in range(1, iterations + 1):
         for wave, kind, t, first in plan:
             eng.dispersion_run(wave, kind, t, True, first, first)
-        out = eng.columns_step_radial(obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel)
+        if lateral is None:
+            out = eng.columns_step_radial(obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel)
+        else:
+            out = eng.columns_step_radial_lateral(obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
         h = dict(iteration=it, nused=int(out["nused"].sum()), chi2=float(out["chi2"].sum()), rms=rms_of(out["chi2"], out["nused"]),
                  nused_r=int(out["nused"][0].sum()), nused_l=int(out["nused"][1].sum()), rms_r=rms_of(out["chi2"][0], out["nused"][0]),
                  rms_l=rms_of(out["chi2"][1], out["nused"][1]), flagged1=int((out["flag"] == 1).sum()), flagged2=int((out["flag"] == 2).sum()))
         log(" depth iteration %d (radial): %d Rayleigh data rms %.6f km/s, %d Love data rms %.6f km/s before the step, %d columns flagged (%d not positive definite, %d without data)" %
             (it, h["nused_r"], h["rms_r"], h["nused_l"], h["rms_l"], h["flagged1"] + h["flagged2"], h["flagged1"], h["flagged2"]))
+        if lateral is not None:
+            h.update(itn=out["itn"], istop=out["istop"], carried=out["carried"])
+            log(" depth iteration %d (radial, lateral %g, on Vsh - Vsv %g): %d conjugate-gradient iterations, istop %d (%s), %d columns without data carried by their neighbours" %
+                (it, lateral, lateral_aniso, h["itn"], h["istop"], "the tolerance was met" if h["istop"] == 1 else "--lateral-maxit was reached", h["carried"]))
         history.append(h)
         steps.append(out)
     return dict(history=history, steps=steps)
@@ -785,13 +984,16 @@ def read_radial_fit(path):
     return io.read_table(path, RADIAL_FIT_TABLE)
 
 
-def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log=print):
-    """--radial on a fresh engine: both models start as the input's, the loop, the two files, the log's xi.  Returns (iterate_radial's result
-    with vsv, vsh (nz, ny, nx) and xi (xi_summary) added, the paths of DepthRadial.dat and DepthRadialFit.dat)."""
+def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log=print, lateral=None, lateral_aniso=None,
+               lateral_tol=DEFAULT_LATERAL_TOL, lateral_maxit=DEFAULT_LATERAL_MAXIT):
+    """--radial on a fresh engine: both models start as the input's, the loop (iterate_radial, to which lateral and its companions go), the
+    two files, the log's xi.  Returns (iterate_radial's result with vsv, vsh (nz, ny, nx) and xi (xi_summary) added, the paths of
+    DepthRadial.dat and DepthRadialFit.dat)."""
     kmax = c["kmax"]
     start = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
     eng.dispersion_begin_radial(start, start, c["depz"], c["minthk"], kmax, kmax)
-    out = iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, float(c["minvel"]), float(c["maxvel"]), log)
+    out = iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, float(c["minvel"]), float(c["maxvel"]), log, lateral, lateral_aniso, lateral_tol,
+                         lateral_maxit)
     out["vsv"], out["vsh"] = eng.dispersion_get_model_radial()
     out["xi"] = xi_summary(c, out["vsv"], out["vsh"], out["steps"][-1]["flag"])
     path = os.path.join(out_dir, "DSurfTomo.inDepthRadial.dat")
@@ -806,17 +1008,20 @@ def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, ou
 
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
         log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
-        lateral_maxit=DEFAULT_LATERAL_MAXIT):
+        lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
-    None): the loop steps with columns_step_lateral; the files are the same two."""
-    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, lateral, lateral_tol if lateral is not None else None,
-          lateral_maxit if lateral is not None else None)
+    None): the loop steps with columns_step_lateral; the files are the same two.  With radial and radial_lateral (not None): the radial loop
+    steps with columns_step_radial_lateral, radial_lateral_aniso (None: radial_lateral) the weight on Vsh - Vsv; the files are --radial's."""
+    with_cg = lateral is not None or radial_lateral is not None          # (the tolerance and the iteration limit are looked at with either coupling)
+    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, lateral, lateral_tol if with_cg else None, lateral_maxit if with_cg else None,
+          radial_lateral, radial_lateral_aniso)
     if lateral is not None:
         check_lateral(radial, resolution)
     if radial:
         check_radial(None, resolution)
+    check_radial_lateral(radial_lateral, radial_lateral_aniso, radial, lateral, resolution)
     c = io.load(directory)
     if radial:
         check_radial(c)
@@ -831,7 +1036,7 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     eng = Engine(0)
     if radial:
         try:
-            return run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log)
+            return run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log, radial_lateral, radial_lateral_aniso, lateral_tol, lateral_maxit)
         finally:
             eng.close()
     try:
@@ -869,6 +1074,8 @@ def parser():
     ap.add_argument("--lateral", type=float, default=None, metavar="W", help="couple neighbouring columns: weight of the penalty on their differences, >= 0 (default: columns alone)")
     ap.add_argument("--lateral-tol", type=float, default=DEFAULT_LATERAL_TOL, metavar="T", help="with --lateral: relative tolerance of the conjugate gradients, > 0 (default %g)" % DEFAULT_LATERAL_TOL)
     ap.add_argument("--lateral-maxit", type=int, default=DEFAULT_LATERAL_MAXIT, metavar="N", help="with --lateral: most conjugate-gradient iterations per step (default %d)" % DEFAULT_LATERAL_MAXIT)
+    ap.add_argument("--radial-lateral", type=float, default=None, metavar="W", help="with --radial: couple neighbouring columns, weight of the penalty on the differences of Vsv and of Vsh, >= 0 (default: columns alone); --lateral-tol and --lateral-maxit apply")
+    ap.add_argument("--radial-lateral-aniso", type=float, default=None, metavar="A", help="with --radial-lateral: weight of the penalty on the differences of Vsh - Vsv between neighbours, >= 0 (default: W)")
     return ap
 
 
@@ -876,18 +1083,19 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        with_lateral = a.lateral is not None          # (--lateral-tol and --lateral-maxit are looked at only with --lateral, as run() does)
+        with_lateral = a.lateral is not None or a.radial_lateral is not None          # (--lateral-tol and --lateral-maxit are looked at only with a coupling, as run() does)
         check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.lateral, a.lateral_tol if with_lateral else None,
-              a.lateral_maxit if with_lateral else None)
+              a.lateral_maxit if with_lateral else None, a.radial_lateral, a.radial_lateral_aniso)
         if a.lateral is not None:
             check_lateral(a.radial, a.resolution)
         if a.radial:
             check_radial(None, a.resolution)
+        check_radial_lateral(a.radial_lateral, a.radial_lateral_aniso, a.radial, a.lateral, a.resolution)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
     run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso,
-        lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit)
+        lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso)
     return 0
 
 

@@ -109,6 +109,7 @@ def declare_solvers(L):
     L.dsa_columns_step_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [_vp] * 4
     L.dsa_dispersion_get_model_radial.argtypes = [_vp, _vp, _vp]
     L.dsa_columns_step_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [C.c_double, _i32] + [_vp] * 5
+    L.dsa_columns_step_radial_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 8 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -519,6 +520,31 @@ class Engine:
         inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
         carried = int((inner.ravel() & (nused == 0) & (flag == 0)).sum())
         return dict(dv=dv, nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]), carried=carried)
+
+    def columns_step_radial_lateral(self, obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
+        """dsa_columns_step_radial_lateral on the models of dispersion_begin_radial: columns_step_radial with the interior columns tied to their
+        neighbours -- both stepped models by the weight lateral, the stepped anisotropy field Vsh - Vsv by the weight lateral_aniso (both 0:
+        columns_step_radial's bits) -- solved by preconditioned conjugate gradients to the relative tolerance tol in at most maxit iterations.
+        Returns columns_step_radial's dict with itn, istop (1 converged, 2 maxit), rz0, rz and carried (the interior columns without a used
+        datum of either type that were stepped all the same: nused 0 0, flag 0) added.  ValueError as columns_step."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        obs = np.ascontiguousarray(obs, np.float32)
+        if ncol == 0 or obs.size == 0 or obs.size % ncol:
+            raise ValueError("columns_step_radial_lateral: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
+        if wt is not None:
+            wt = np.ascontiguousarray(wt, np.float32)
+            if wt.size != obs.size:
+                raise ValueError("columns_step_radial_lateral: wt holds %d values, obs %d" % (wt.size, obs.size))
+        dv = np.zeros((2, nz - 1, ncol), np.float32); nused = np.zeros((2, ncol), np.int32); chi2 = np.zeros((2, ncol)); flag = np.zeros(ncol, np.int32)
+        info = np.zeros(4)
+        self._check(self._L.dsa_columns_step_radial_lateral(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(aniso),
+                                                            float(lateral), float(lateral_aniso), float(dvmax), float(minvel), float(maxvel), float(tol), int(maxit),
+                                                            _p(dv), _p(nused), _p(chi2), _p(flag), _p(info)))
+        inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+        carried = int((inner.ravel() & (nused.sum(axis=0) == 0) & (flag == 0)).sum())
+        return dict(dv_sv=dv[0], dv_sh=dv[1], nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]),
+                    carried=carried)
 
     def dispersion_get_model_radial(self):
         """the radial stage's two resident models, (vsv, vsh), each (nz, ny, nx) fp32"""

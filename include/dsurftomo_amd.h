@@ -528,6 +528,27 @@ int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh);
 int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax,
                              float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
 
+/* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
+ * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
+ * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of
+ * dsa_columns_step_radial's objectives of the columns, plus, over the edges of dsa_columns_step_lateral,
+ *   lateral^2 sum_edges [ |(vsv_c + xv_c) - (vsv_c' + xv_c')|^2 + |(vsh_c + xh_c) - (vsh_c' + xh_c')|^2 ]
+ *   + lateral_aniso^2 sum_edges |(a_c + u_c) - (a_c' + u_c')|^2,   a = vsh - vsv, u = xh - xv:
+ * the roughness of the two stepped models, and the roughness of the stepped anisotropy field Vsh - Vsv by a weight of its own, so that xi
+ * can be smoothed more strongly than the velocities.  Edges exist iff lateral > 0 or lateral_aniso > 0.  A column takes part as in
+ * dsa_columns_step_lateral: flag 1 is left alone and no edge touches it; with edges a column without a used datum of either type takes part
+ * (nused 0 0, flag 0) and both its models are carried by its neighbours.  Solved by dsa_columns_step_lateral's preconditioned conjugate
+ * gradients with the columns' own 2(nz-1) x 2(nz-1) factors, tol, maxit and info as there; fp64, every sum in a fixed order
+ * (csrc/column_radial_lateral.h).  lateral = 0 and lateral_aniso = 0 is no iteration: every output and both stepped models are
+ * dsa_columns_step_radial's bit for bit, flag 2 included, and info[3] is the residual of that direct solve.
+ * Afterwards as dsa_columns_step_radial: both models stepped where they lie, the marks cleared, the ring and the bottom depth kept.
+ * Errors, all found before the device is touched: as dsa_columns_step_radial, in its order; then DSA_ERR_ARGUMENT: lateral or lateral_aniso not
+ * finite or < 0, tol not finite or <= 0, maxit < 1; DSA_ERR_CAPACITY: the loop's workspace exceeds dsa_set_memory_budget, held against it as
+ * dsa_columns_step_lateral's.  DSA_ERR_DEVICE as dsa_columns_step_radial (the set-up needs its LDS), before anything is launched. */
+int dsa_columns_step_radial_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral,
+                                    float lateral_aniso, float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused,
+                                    double* chi2, int* flag, double* info);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);

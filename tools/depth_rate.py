@@ -19,7 +19,11 @@ call after fresh runs, next to dsa_columns_step on the same state: the conjugate
 time per iteration: the difference of the two calls' wall times over itn, which also holds the set-up's extra launches, the host's look at
 the done flag every 16th iteration and the up to 15 empty iterations launched after the flag was set.
 
-    python tools/depth_rate.py [repeats] [lateral]      (needs the GPU; `lateral`: that leg alone)
+The radial lateral leg: dsa_columns_step_radial_lateral on the radial leg's stage (the four-wave-type plan, Vsh 3 %
+above Vsv) at (lateral, lateral_aniso) = (0.2, 0.2), (0.3, 0.6) and (0, 1) (tol 1e-8), timed as the lateral leg is, next to
+dsa_columns_step_radial on the same state.
+
+    python tools/depth_rate.py [repeats] [lateral | radial-lateral]      (needs the GPU; with a name: that leg alone)
 """
 import os
 import sys
@@ -44,6 +48,10 @@ def main():
     e = Engine(0)
     if "lateral" in sys.argv[2:]:
         lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+        e.close()
+        return
+    if "radial-lateral" in sys.argv[2:]:
+        radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
         e.close()
         return
     for name, case in cases:
@@ -76,7 +84,42 @@ def main():
     resolution_leg(e, repeats, "the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60)
     radial_leg(e, 1, "radial, the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60, 0.5, 6.0)
     lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+    radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
     e.close()
+
+
+def radial_lateral_leg(e, repeats, vel, c, plan, kmax):
+    nz, ny, nx = vel.shape
+    vsh = vel.copy()
+    vsh[:-1] = vsh[:-1] * np.float32(1.03)
+    e.dispersion_begin_radial(vel, vsh, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    # the lateral leg's observations: up to 2 % off the models' own curves, the sign changing across the grid
+    i = np.arange(nx)[None, :]; j = np.arange(ny)[:, None]
+    pv = e.dispersion_fetch(0, kmax)
+    obs = np.where(pv > 0, pv * (1.0 + 0.02 * np.cos(0.9 * i + 0.5 * j).ravel()[None, :]), 0.0).astype(np.float32)
+    args = (depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP, depth.DEFAULT_ANISO)
+    clip = (1e-4, float(c["minvel"]), float(c["maxvel"]))
+
+    def timed(call):
+        wall = []
+        for it in range(repeats + 1):
+            for wave, kind, tt, first in plan:
+                e.dispersion_run(wave, kind, tt, True, first, first)
+            t0 = time.perf_counter()
+            out = call()
+            if it:
+                wall.append(1e3 * (time.perf_counter() - t0))
+        return out, wall
+
+    _, alone = timed(lambda: e.columns_step_radial(obs, None, *args, *clip))
+    for lateral, aniso in ((0.2, 0.2), (0.3, 0.6), (0.0, 1.0)):
+        out, wall = timed(lambda: e.columns_step_radial_lateral(obs, None, *args, lateral, aniso, *clip, depth.DEFAULT_LATERAL_TOL, depth.DEFAULT_LATERAL_MAXIT))
+        assert not out["flag"].any() and out["istop"] == 1 and out["itn"] >= 1
+        print("%-20s %d x %d x %d, K = %d: median of %d -- columns_step_radial_lateral %.3f ms wall, itn %d (at most %.1f us per iteration: the whole difference over itn), columns_step_radial %.3f ms wall; all calls: %s" %
+              ("radial lateral %g %g" % (lateral, aniso), nx, ny, nz, kmax, repeats, np.median(wall), out["itn"], 1e3 * (np.median(wall) - np.median(alone)) / max(out["itn"], 1),
+               np.median(alone), " ".join("%.3f" % w for w in wall)))
 
 
 def lateral_leg(e, repeats, vel, c, plan, kmax):
