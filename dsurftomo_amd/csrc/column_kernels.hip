@@ -6,7 +6,8 @@
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
 // k_column_step_radial: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
 // k_lateral_* (DESIGN.md section 24): the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
-// k_radial_lateral_* (DESIGN.md section 25), last: that loop on the radial step's 2M unknowns per column, with k_lateral_update and k_lateral_reduce as they are.
+// the same loop and kernels on the radial step's 2M unknowns per column; only k_radial_lateral_setup and
+// k_radial_lateral_start are that system's own.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -22,25 +23,39 @@ struct BlockBarrier {
     __device__ __forceinline__ void operator()() const { __syncthreads(); }
 };
 
-// block b is interior column (i, j) = (1 + b % nvx, 1 + b / nvx), column c = j * nx + i of the (nz, ny, nx) model.  obs / wt: (K, ncol)
-// fp32; pv: (K, ncol); S: (M, K, ncol); dv: (M, ncol); nused / chi2 / flag: (ncol).  The ring's outputs are the caller's zeros.
+// block b is interior column (i, j) = (1 + b % nvx, 1 + b / nvx): column c = j * nx + i of the (nz, ny, nx) model, or -1 for a block past
+// the interior
+__device__ __forceinline__ long long block_column(int nx, int ny)
+{
+    const int nvx = nx - 2;
+    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
+    return bj >= ny - 2 ? -1 : (long long)(bj + 1) * nx + (bi + 1);
+}
+
+// what ColumnIn and RadialIn share, for column c: obs / wt: (K, ncol) fp32; pv: (K, ncol); the strides of S (M, K, ncol)
+template <class In>
+__device__ __forceinline__ void column_in(In& in, int M, int K, long long c, long long ncol, const float* obs, const float* wt, const double* pv)
+{
+    in.M = M; in.K = K;
+    in.obs = obs + c; in.obs_stride = ncol;
+    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
+    in.pv = pv + c; in.pv_stride = ncol;
+    in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+}
+
+// dv: (M, ncol); nused / chi2 / flag: (ncol).  The ring's outputs are the caller's zeros.
 __global__ void __launch_bounds__(64) k_column_step(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
                                                    const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp, float dvmax,
                                                    float minvel, float maxvel, float* __restrict__ vels, float* __restrict__ dv, int* __restrict__ nused,
                                                    double* __restrict__ chi2, int* __restrict__ flag)
 {
     extern __shared__ double column_lds[];
-    const int nvx = nx - 2, M = nz - 1;
-    const long long ncol = (long long)nx * ny;
-    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
-    if (bj >= ny - 2) return;
-    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
     ColumnIn in;
-    in.M = M; in.K = K;
-    in.obs = obs + c; in.obs_stride = ncol;
-    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
-    in.pv = pv + c; in.pv_stride = ncol;
-    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.S = S + c;
     const ColumnWork w = column_work(column_lds, M, K);
     int n = 0;
     double x2 = 0.0;
@@ -58,17 +73,12 @@ __global__ void __launch_bounds__(64) k_column_resolution(int nx, int ny, int nz
                                                          double* __restrict__ trace, double* __restrict__ R, int* __restrict__ nused, int* __restrict__ flag)
 {
     extern __shared__ double column_lds[];
-    const int nvx = nx - 2, M = nz - 1;
-    const long long ncol = (long long)nx * ny;
-    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
-    if (bj >= ny - 2) return;
-    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
     ColumnIn in;
-    in.M = M; in.K = K;
-    in.obs = obs + c; in.obs_stride = ncol;
-    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
-    in.pv = pv + c; in.pv_stride = ncol;
-    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.S = S + c;
     ColumnResOut out;
     out.measures = measures + c; out.m_qstride = (long long)M * ncol; out.m_jstride = ncol;
     out.leverage = leverage + c; out.h_stride = ncol;
@@ -92,17 +102,12 @@ __global__ void __launch_bounds__(64) k_column_step_radial(int nx, int ny, int n
                                                           int* __restrict__ nused, double* __restrict__ chi2, int* __restrict__ flag)
 {
     extern __shared__ double column_lds[];
-    const int nvx = nx - 2, M = nz - 1;
-    const long long ncol = (long long)nx * ny;
-    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
-    if (bj >= ny - 2) return;
-    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
     RadialIn in;
-    in.M = M; in.K = K; in.love = love;
-    in.obs = obs + c; in.obs_stride = ncol;
-    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
-    in.pv = pv + c; in.pv_stride = ncol;
-    in.Sv = Sv + c; in.Sh = Sh + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.love = love; in.Sv = Sv + c; in.Sh = Sh + c;
     const ColumnWork w = radial_work(column_lds, M, K);
     int n[2] = { 0, 0 };
     double x2[2] = { 0.0, 0.0 };
@@ -111,142 +116,105 @@ __global__ void __launch_bounds__(64) k_column_step_radial(int nx, int ny, int n
     if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
 }
 
-// The laterally coupled step: column_lateral.h on every interior column, the launch shape and the column of a block as
-// above -- block b is interior column b of the header.  ws: lateral_ws_doubles(nvx, nvy, M) doubles in global memory, where N, the factor,
-// the vectors, the columns' dot products, the scalars and the done flag lie between the launches.  No kernel waits for another block: what
-// a column needs of its neighbours was written by an earlier launch.
+// The laterally coupled steps (DESIGN.md sections 24 and 25): column_lateral.h's conjugate gradients on every interior column, the launch
+// shape as above -- block b is interior column b of the header.  A system is passed to its kernels by value: LateralWs (section 24), or
+// RadialLateralWs (section 25: 2M unknowns per column) -- views of lateral_ws_doubles doubles in global memory, where N, the factor, the
+// vectors, the columns' dot products, the scalars and the done flag lie between the launches.  No kernel waits for another block: what a
+// column needs of its neighbours was written by an earlier launch.
 // k_lateral_setup: assemble and factor in LDS (k_column_step's arrays), N, the factor and b to the workspace; nused / chi2 / flag: (ncol).
 __global__ void __launch_bounds__(64) k_lateral_setup(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
-                                                     const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp, float lateral,
-                                                     double* __restrict__ ws_base, int* __restrict__ nused, double* __restrict__ chi2, int* __restrict__ flag)
+                                                     const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp, LateralWs ws,
+                                                     int* __restrict__ nused, double* __restrict__ chi2, int* __restrict__ flag)
 {
     extern __shared__ double column_lds[];
-    const int nvx = nx - 2, M = nz - 1;
-    const long long ncol = (long long)nx * ny;
-    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
-    if (bj >= ny - 2) return;
-    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
     ColumnIn in;
-    in.M = M; in.K = K;
-    in.obs = obs + c; in.obs_stride = ncol;
-    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
-    in.pv = pv + c; in.pv_stride = ncol;
-    in.S = S + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
-    const ColumnWork w = column_work(column_lds, M, K);
-    const LateralWs ws = lateral_ws(ws_base, nvx, ny - 2, M, lateral);
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.S = S + c;
     int n = 0;
     double x2 = 0.0;
-    const int f = lateral_setup(in, smooth, damp, w, ws, (int)blockIdx.x, &n, &x2, (int)threadIdx.x, 64, BlockBarrier());
+    const int f = lateral_setup(in, smooth, damp, column_work(column_lds, M, K), ws, (int)blockIdx.x, &n, &x2, (int)threadIdx.x, 64, BlockBarrier());
     if (threadIdx.x == 0) { nused[c] = n; chi2[c] = x2; flag[c] = f; }
 }
 
-// the right-hand side with the edges' part, x0 and the columns' figures of rz0
-__global__ void __launch_bounds__(64) k_lateral_start(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, const float* __restrict__ vels)
-{
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    lateral_start(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, vels, (long long)(nvx + 2) * (nvy + 2), (int)threadIdx.x, 64, BlockBarrier());
-}
-
-// r0, z0 and the columns' figures of the first rz
-__global__ void __launch_bounds__(64) k_lateral_residual(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
-{
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    lateral_residual(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
-}
-
-// the two kernels of an iteration: the new direction and q = A p; the update of x and r, z = M^-1 r.  Both return at once when done is set.
-__global__ void __launch_bounds__(64) k_lateral_direction(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
-{
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    lateral_direction(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
-}
-
-__global__ void __launch_bounds__(64) k_lateral_update(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base)
-{
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    lateral_update(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
-}
-
-// the global sums, one wavefront: lane t is chain t; lane 0 adds the chains and sets the scalars
-__global__ void __launch_bounds__(64) k_lateral_reduce(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, int what, double tol, int maxit)
-{
-    __shared__ double chains[kLateralChains];
-    lateral_reduce(lateral_ws(ws_base, nvx, nvy, M, lateral), what, tol, maxit, chains, (int)threadIdx.x, 64, BlockBarrier());
-}
-
-// the clipped steps and the stepped model; dv: (M, ncol)
-__global__ void __launch_bounds__(64) k_lateral_finish(int nvx, int nvy, int M, float lateral, double* __restrict__ ws_base, float dvmax, float minvel, float maxvel,
-                                                      float* __restrict__ vels, float* __restrict__ dv)
-{
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    const long long ncol = (long long)(nvx + 2) * (nvy + 2);
-    lateral_finish(lateral_ws(ws_base, nvx, nvy, M, lateral), (int)blockIdx.x, dvmax, minvel, maxvel, vels, ncol, dv, ncol, (int)threadIdx.x, 64);
-}
-
-// The laterally coupled radial step: column_radial_lateral.h on every interior column, block b interior column b.  ws:
-// radial_lateral_ws_doubles(nvx, nvy, M) doubles in global memory -- column_lateral.h's workspace of 2M unknowns per column, on which
-// k_lateral_update and k_lateral_reduce run as they are.  No kernel waits for another block.
 // k_radial_lateral_setup: radial_assemble and the factorisation in LDS (k_column_step_radial's arrays and sizes), N, the factor and b to the
 // workspace; Sv / Sh, love, nused / chi2 (2, ncol), flag (ncol) as k_column_step_radial's.
 __global__ void __launch_bounds__(64) k_radial_lateral_setup(int nx, int ny, int nz, int K, unsigned long long love, const float* __restrict__ obs,
                                                             const float* __restrict__ wt, const double* __restrict__ pv, const double* __restrict__ Sv,
-                                                            const double* __restrict__ Sh, float smooth, float damp, float aniso, float lateral,
-                                                            float lateral_aniso, const float* __restrict__ vsv, const float* __restrict__ vsh,
-                                                            double* __restrict__ ws_base, int* __restrict__ nused, double* __restrict__ chi2,
-                                                            int* __restrict__ flag)
+                                                            const double* __restrict__ Sh, float smooth, float damp, float aniso, const float* __restrict__ vsv,
+                                                            const float* __restrict__ vsh, RadialLateralWs rl, int* __restrict__ nused,
+                                                            double* __restrict__ chi2, int* __restrict__ flag)
 {
     extern __shared__ double column_lds[];
-    const int nvx = nx - 2, M = nz - 1;
-    const long long ncol = (long long)nx * ny;
-    const int bj = (int)blockIdx.x / nvx, bi = (int)blockIdx.x - bj * nvx;
-    if (bj >= ny - 2) return;
-    const long long c = (long long)(bj + 1) * nx + (bi + 1);
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
     RadialIn in;
-    in.M = M; in.K = K; in.love = love;
-    in.obs = obs + c; in.obs_stride = ncol;
-    in.wt = wt ? wt + c : nullptr; in.wt_stride = ncol;
-    in.pv = pv + c; in.pv_stride = ncol;
-    in.Sv = Sv + c; in.Sh = Sh + c; in.s_lstride = (long long)K * ncol; in.s_kstride = ncol;
-    const ColumnWork w = radial_work(column_lds, M, K);
-    const RadialLateralWs rl = radial_lateral_ws(ws_base, nvx, ny - 2, M, lateral, lateral_aniso);
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.love = love; in.Sv = Sv + c; in.Sh = Sh + c;
     int n[2] = { 0, 0 };
     double x2[2] = { 0.0, 0.0 };
-    const int f = radial_lateral_setup(in, smooth, damp, aniso, vsv + c, vsh + c, ncol, w, rl, (int)blockIdx.x, n, x2, (int)threadIdx.x, 64, BlockBarrier());
+    const int f = radial_lateral_setup(in, smooth, damp, aniso, vsv + c, vsh + c, ncol, radial_work(column_lds, M, K), rl, (int)blockIdx.x, n, x2, (int)threadIdx.x,
+                                       64, BlockBarrier());
     if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
 }
 
-// the right-hand side with the edges' parts, x0 and the columns' figures of rz0
-__global__ void __launch_bounds__(64) k_radial_lateral_start(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base,
-                                                            const float* __restrict__ vsv, const float* __restrict__ vsh)
+__device__ __forceinline__ bool past_interior(const LateralWs& ws) { return (int)blockIdx.x >= ws.nvx * ws.nvy; }
+__device__ __forceinline__ long long model_columns(const LateralWs& ws) { return (long long)(ws.nvx + 2) * (ws.nvy + 2); }
+
+// the right-hand side with the edges' part, x0 and the columns' figures of rz0: each system's own
+__global__ void __launch_bounds__(64) k_lateral_start(LateralWs ws, const float* __restrict__ vels)
 {
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    radial_lateral_start(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, vsv, vsh, (long long)(nvx + 2) * (nvy + 2),
-                         (int)threadIdx.x, 64, BlockBarrier());
+    if (past_interior(ws)) return;
+    lateral_start(ws, (int)blockIdx.x, vels, model_columns(ws), (int)threadIdx.x, 64, BlockBarrier());
 }
 
-// r0, z0 and the columns' figures of the first rz
-__global__ void __launch_bounds__(64) k_radial_lateral_residual(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base)
+__global__ void __launch_bounds__(64) k_radial_lateral_start(RadialLateralWs rl, const float* __restrict__ vsv, const float* __restrict__ vsh)
 {
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    radial_lateral_residual(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+    if (past_interior(rl.ws)) return;
+    radial_lateral_start(rl, (int)blockIdx.x, vsv, vsh, model_columns(rl.ws), (int)threadIdx.x, 64, BlockBarrier());
 }
 
-// the first kernel of an iteration: the new direction and q = A p; returns at once when done is set.  The second is k_lateral_update.
-__global__ void __launch_bounds__(64) k_radial_lateral_direction(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base)
+// r0, z0 and the columns' figures of the first rz, with the system's operator
+template <class Sys>
+__global__ void __launch_bounds__(64) k_lateral_residual(Sys sys)
 {
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    radial_lateral_direction(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+    if (past_interior(lateral_view(sys))) return;
+    lateral_residual(sys, (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
 }
 
-// the clipped steps and the two stepped models; dv: (2, M, ncol)
-__global__ void __launch_bounds__(64) k_radial_lateral_finish(int nvx, int nvy, int M, float lateral, float lateral_aniso, double* __restrict__ ws_base,
-                                                             float dvmax, float minvel, float maxvel, float* __restrict__ vsv, float* __restrict__ vsh,
-                                                             float* __restrict__ dv)
+// the two kernels of an iteration: the new direction and q = A p, with the system's operator; the update of x and r, z = M^-1 r, the same
+// for every system.  Both return at once when done is set.
+template <class Sys>
+__global__ void __launch_bounds__(64) k_lateral_direction(Sys sys)
 {
-    if ((int)blockIdx.x >= nvx * nvy) return;
-    const long long ncol = (long long)(nvx + 2) * (nvy + 2);
-    radial_lateral_finish(radial_lateral_ws(ws_base, nvx, nvy, M, lateral, lateral_aniso), (int)blockIdx.x, dvmax, minvel, maxvel, vsv, vsh, ncol, dv,
-                          dv + (long long)M * ncol, ncol, (int)threadIdx.x, 64);
+    if (past_interior(lateral_view(sys))) return;
+    lateral_direction(sys, (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+__global__ void __launch_bounds__(64) k_lateral_update(LateralWs ws)
+{
+    if (past_interior(ws)) return;
+    lateral_update(ws, (int)blockIdx.x, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the global sums, one wavefront: lane t is chain t; lane 0 adds the chains and sets the scalars
+__global__ void __launch_bounds__(64) k_lateral_reduce(LateralWs ws, int what, double tol, int maxit)
+{
+    __shared__ double chains[kLateralChains];
+    lateral_reduce(ws, what, tol, maxit, chains, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+// the clipped steps and the stepped model(s): one block of ws.M rows of vels0 and dv (M, ncol), or two of Mb = ws.M / 2 rows, vels0's and
+// vels1's, dv (2, Mb, ncol)
+__global__ void __launch_bounds__(64) k_lateral_finish(LateralWs ws, int Mb, float dvmax, float minvel, float maxvel, float* __restrict__ vels0,
+                                                      float* __restrict__ vels1, float* __restrict__ dv)
+{
+    if (past_interior(ws)) return;
+    const long long ncol = model_columns(ws);
+    lateral_finish_blocks(ws, (int)blockIdx.x, Mb, dvmax, minvel, maxvel, vels0, vels1, ncol, dv, dv + (long long)Mb * ncol, ncol, (int)threadIdx.x, 64);
 }
 
 }  // namespace
@@ -260,25 +228,32 @@ void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const
                        minvel, maxvel, d_vels, d_dv, d_nused, d_chi2, d_flag);
 }
 
+// The dynamic-LDS rule of a kernel whose work arrays may pass the 64 KB a block gets without asking (the attribute is per device: set every
+// time).  0: launch; 1: the case needs more than a block of this device may have (*limit_out); 2: the device refused the attribute
+static int column_lds_opt_in(int device, const void* kernel, size_t lds, int* limit_out)
+{
+    if (lds <= 64 * 1024) return 0;
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
+    if (limit_out) *limit_out = limit;
+    if (lds > (size_t)limit) return 1;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return 2;
+    }
+    return 0;
+}
+
 size_t column_resolution_lds_bytes(int nz, int K) { return column_resolution_doubles(nz - 1, K) * sizeof(double); }
 
-// 0: launched; 1: the case needs more dynamic LDS than a block of this device may have (*limit_out); 2: the device refused the attribute
+// column_lds_opt_in's return values: nothing is launched unless 0
 int launch_column_resolution(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S,
                              const float* d_depz, float smooth, float damp, double* d_measures, double* d_leverage, double* d_trace, double* d_R, int* d_nused,
                              int* d_flag, hipStream_t stream, int* limit_out)
 {
     if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
     const size_t lds = column_resolution_lds_bytes(nz, K);
-    if (lds > 64 * 1024) {          // (above what a block gets without asking; the attribute is per device: set every time)
-        int limit = 0;
-        if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
-        if (limit_out) *limit_out = limit;
-        if (lds > (size_t)limit) return 1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_column_resolution), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            return 2;
-        }
-    }
+    if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_resolution), lds, limit_out)) return rc;
     hipLaunchKernelGGL(k_column_resolution, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, d_depz, smooth,
                        damp, d_measures, d_leverage, d_trace, d_R, d_nused, d_flag);
     return 0;
@@ -286,129 +261,97 @@ int launch_column_resolution(int device, int nx, int ny, int nz, int K, const fl
 
 size_t column_radial_lds_bytes(int nz, int K) { return radial_work_doubles(nz - 1, K) * sizeof(double); }
 
-// launch_column_resolution's rule for the LDS and its return values
 int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
                               const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
                               float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out)
 {
     if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
     const size_t lds = column_radial_lds_bytes(nz, K);
-    if (lds > 64 * 1024) {
-        int limit = 0;
-        if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
-        if (limit_out) *limit_out = limit;
-        if (lds > (size_t)limit) return 1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_column_step_radial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            return 2;
-        }
-    }
+    if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_step_radial), lds, limit_out)) return rc;
     hipLaunchKernelGGL(k_column_step_radial, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh,
                        smooth, damp, aniso, dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv, d_nused, d_chi2, d_flag);
     return 0;
 }
 
-size_t column_lateral_ws_bytes(int nx, int ny, int nz) { return lateral_ws_doubles(nx - 2, ny - 2, nz - 1) * sizeof(double); }
+// ---- the coupled systems: the views of a CoupledSystem, the set-up of each, and one copy of the loop's launch sequences ----
 
-void launch_lateral_setup(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
-                          float lateral, double tol, double* d_ws, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream)
+static dim3 coupled_grid(const CoupledSystem& s) { return dim3((unsigned)((s.nx - 2) * (s.ny - 2))); }
+static bool coupled_empty(const CoupledSystem& s) { return s.nx < 3 || s.ny < 3 || s.nz < 2; }
+static LateralWs coupled_iso(const CoupledSystem& s) { return lateral_ws(s.d_ws, s.nx - 2, s.ny - 2, s.nz - 1, s.lateral); }
+static RadialLateralWs coupled_radial(const CoupledSystem& s) { return radial_lateral_ws(s.d_ws, s.nx - 2, s.ny - 2, s.nz - 1, s.lateral, s.lateral_aniso); }
+// what the kernels that are the same for every system run on
+static LateralWs coupled_view(const CoupledSystem& s) { return s.blocks == 2 ? coupled_radial(s).ws : coupled_iso(s); }
+
+size_t coupled_ws_bytes(int blocks, int nx, int ny, int nz) { return lateral_ws_doubles(nx - 2, ny - 2, blocks * (nz - 1)) * sizeof(double); }
+bool coupled_edges(const CoupledSystem& s) { return coupled_view(s).edges != 0; }
+const int* coupled_ints(const CoupledSystem& s) { return coupled_view(s).ic; }
+const double* coupled_scalars(const CoupledSystem& s) { return coupled_view(s).sc; }
+
+static void launch_reduce(const CoupledSystem& s, int what, double tol, int maxit, hipStream_t stream)
 {
-    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return;
-    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
-    const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
-    hipLaunchKernelGGL(k_lateral_setup, grid, dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, lateral, d_ws, d_nused, d_chi2, d_flag);
-    hipLaunchKernelGGL(k_lateral_start, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, d_vels);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumRz0, tol, 0);
+    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, coupled_view(s), what, tol, maxit);
 }
 
-void launch_lateral_first(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream)
+void launch_lateral_setup(const CoupledSystem& s, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                          double tol, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream)
 {
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    hipLaunchKernelGGL(k_lateral_residual, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumFirst, tol, maxit);
+    if (coupled_empty(s) || K < 1) return;
+    const size_t lds = column_work_doubles(s.nz - 1, K) * sizeof(double);
+    hipLaunchKernelGGL(k_lateral_setup, coupled_grid(s), dim3(64), lds, stream, s.nx, s.ny, s.nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, coupled_iso(s), d_nused,
+                       d_chi2, d_flag);
+    hipLaunchKernelGGL(k_lateral_start, coupled_grid(s), dim3(64), 0, stream, coupled_iso(s), d_vels);
+    launch_reduce(s, kLatSumRz0, tol, 0, stream);
 }
 
-void launch_lateral_iteration(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream)
+// column_lds_opt_in's return values for the set-up kernel: nothing is launched unless 0
+int launch_radial_lateral_setup(int device, const CoupledSystem& s, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, double tol, const float* d_vsv, const float* d_vsh,
+                                int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out)
 {
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
-    hipLaunchKernelGGL(k_lateral_direction, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumPq, tol, maxit);
-    hipLaunchKernelGGL(k_lateral_update, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, (int)kLatSumRz, tol, maxit);
-}
-
-void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, hipStream_t stream)
-{
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    hipLaunchKernelGGL(k_lateral_finish, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, d_ws, dvmax, minvel, maxvel,
-                       d_vels, d_dv);
-}
-
-// where the done flag, the count and the stop code (3 ints) and the scalars lie in the workspace, for the host's copies
-const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).ic; }
-const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz) { return lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f).sc; }
-
-size_t column_radial_lateral_ws_bytes(int nx, int ny, int nz) { return radial_lateral_ws_doubles(nx - 2, ny - 2, nz - 1) * sizeof(double); }
-
-namespace {
-// what k_lateral_update and k_lateral_reduce get as their `lateral`: they ask it only whether there are edges
-float radial_lateral_edges(float lateral, float lateral_aniso) { return (lateral > 0.0f || lateral_aniso > 0.0f) ? 1.0f : 0.0f; }
-}
-
-// launch_column_step_radial's rule for the LDS of the set-up kernel and its return values; nothing is launched unless 0 is returned
-int launch_radial_lateral_setup(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
-                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float lateral, float lateral_aniso, double tol,
-                                double* d_ws, const float* d_vsv, const float* d_vsh, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out)
-{
-    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
-    const size_t lds = column_radial_lds_bytes(nz, K);
-    int limit = 0;
-    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) limit = 0;
-    if (limit_out) *limit_out = limit;
-    if (lds > (size_t)limit) return 1;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_radial_lateral_setup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 2;
-    }
-    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
-    hipLaunchKernelGGL(k_radial_lateral_setup, grid, dim3(64), lds, stream, nx, ny, nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh, smooth, damp, aniso, lateral,
-                       lateral_aniso, d_vsv, d_vsh, d_ws, d_nused, d_chi2, d_flag);
-    hipLaunchKernelGGL(k_radial_lateral_start, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws, d_vsv, d_vsh);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), radial_lateral_edges(lateral, lateral_aniso), d_ws,
-                       (int)kLatSumRz0, tol, 0);
+    if (coupled_empty(s) || K < 1) return 0;
+    const size_t lds = column_radial_lds_bytes(s.nz, K);
+    if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_radial_lateral_setup), lds, limit_out)) return rc;
+    hipLaunchKernelGGL(k_radial_lateral_setup, coupled_grid(s), dim3(64), lds, stream, s.nx, s.ny, s.nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh, smooth, damp, aniso,
+                       d_vsv, d_vsh, coupled_radial(s), d_nused, d_chi2, d_flag);
+    hipLaunchKernelGGL(k_radial_lateral_start, coupled_grid(s), dim3(64), 0, stream, coupled_radial(s), d_vsv, d_vsh);
+    launch_reduce(s, kLatSumRz0, tol, 0, stream);
     return 0;
 }
 
-void launch_radial_lateral_first(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream)
+template <class Sys>
+static void coupled_first(const CoupledSystem& s, const Sys& sys, double tol, int maxit, hipStream_t stream)
 {
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    hipLaunchKernelGGL(k_radial_lateral_residual, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), radial_lateral_edges(lateral, lateral_aniso), d_ws,
-                       (int)kLatSumFirst, tol, maxit);
+    hipLaunchKernelGGL(k_lateral_residual<Sys>, coupled_grid(s), dim3(64), 0, stream, sys);
+    launch_reduce(s, kLatSumFirst, tol, maxit, stream);
 }
 
-void launch_radial_lateral_iteration(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream)
+template <class Sys>
+static void coupled_iteration(const CoupledSystem& s, const Sys& sys, double tol, int maxit, hipStream_t stream)
 {
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    const dim3 grid((unsigned)((nx - 2) * (ny - 2)));
-    const float edges = radial_lateral_edges(lateral, lateral_aniso);
-    hipLaunchKernelGGL(k_radial_lateral_direction, grid, dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws, (int)kLatSumPq, tol, maxit);
-    hipLaunchKernelGGL(k_lateral_update, grid, dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws);
-    hipLaunchKernelGGL(k_lateral_reduce, dim3(1), dim3(64), 0, stream, nx - 2, ny - 2, 2 * (nz - 1), edges, d_ws, (int)kLatSumRz, tol, maxit);
+    hipLaunchKernelGGL(k_lateral_direction<Sys>, coupled_grid(s), dim3(64), 0, stream, sys);
+    launch_reduce(s, kLatSumPq, tol, maxit, stream);
+    hipLaunchKernelGGL(k_lateral_update, coupled_grid(s), dim3(64), 0, stream, coupled_view(s));
+    launch_reduce(s, kLatSumRz, tol, maxit, stream);
 }
 
-void launch_radial_lateral_finish(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vsv,
-                                  float* d_vsh, float* d_dv, hipStream_t stream)
+void launch_coupled_first(const CoupledSystem& s, double tol, int maxit, hipStream_t stream)
 {
-    if (nx < 3 || ny < 3 || nz < 2) return;
-    hipLaunchKernelGGL(k_radial_lateral_finish, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), 0, stream, nx - 2, ny - 2, nz - 1, lateral, lateral_aniso, d_ws,
-                       dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv);
+    if (coupled_empty(s)) return;
+    if (s.blocks == 2) coupled_first(s, coupled_radial(s), tol, maxit, stream);
+    else coupled_first(s, coupled_iso(s), tol, maxit, stream);
 }
 
-const int* column_radial_lateral_ints(double* d_ws, int nx, int ny, int nz) { return radial_lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f, 0.0f).ws.ic; }
-const double* column_radial_lateral_scalars(double* d_ws, int nx, int ny, int nz) { return radial_lateral_ws(d_ws, nx - 2, ny - 2, nz - 1, 0.0f, 0.0f).ws.sc; }
+void launch_coupled_iteration(const CoupledSystem& s, double tol, int maxit, hipStream_t stream)
+{
+    if (coupled_empty(s)) return;
+    if (s.blocks == 2) coupled_iteration(s, coupled_radial(s), tol, maxit, stream);
+    else coupled_iteration(s, coupled_iso(s), tol, maxit, stream);
+}
+
+void launch_coupled_finish(const CoupledSystem& s, float dvmax, float minvel, float maxvel, float* d_vels0, float* d_vels1, float* d_dv, hipStream_t stream)
+{
+    if (coupled_empty(s)) return;
+    hipLaunchKernelGGL(k_lateral_finish, coupled_grid(s), dim3(64), 0, stream, coupled_view(s), s.nz - 1, dvmax, minvel, maxvel, d_vels0, d_vels1, d_dv);
+}
 
 }  // namespace dsa

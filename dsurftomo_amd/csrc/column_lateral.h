@@ -24,7 +24,11 @@
 // The directions are kept twice (p of the even and of the odd iterations): a column computes its neighbours' new p from their z and old p
 // itself, by the expression they use, so that no column waits for another.  The scalars, the iteration count and the done flag lie with
 // the vectors; every per-iteration function returns at once when done is set, so x is frozen from the iteration that met the criterion,
-// however many more are started.  fp64 under -ffp-contract=off, functions of (lane, nlanes, sync), every figure one sequential chain from
+// however many more are started.
+//
+// The phases of the loop -- the store-and-factor tail of the set-up, residual, direction, update -- are written once, over a system `sys`
+// that supplies lateral_view(sys), its LateralWs, and lateral_operator(sys, ...), its A y: this header's own system is the LateralWs itself;
+// column_radial_lateral.h adds one of 2M unknowns per column.  The operators stay two functions: their floating-point chains differ.  fp64 under -ffp-contract=off, functions of (lane, nlanes, sync), every figure one sequential chain from
 // 0.0 in the stated order: column_system.h's contract.
 #pragma once
 
@@ -58,12 +62,13 @@ struct LateralWs {
     int* active;
 };
 
-DSA_CS LateralWs lateral_ws(double* base, int nvx, int nvy, int M, float lateral)
+// edges: whether the columns are coupled at all (this system: lateral > 0)
+DSA_CS LateralWs lateral_ws(double* base, int nvx, int nvy, int M, float lateral, bool edges)
 {
     const size_t n = (size_t)nvx * nvy;
     LateralWs ws;
     ws.nvx = nvx; ws.nvy = nvy; ws.M = M;
-    ws.edges = lateral > 0.0f ? 1 : 0;
+    ws.edges = edges ? 1 : 0;
     ws.lam2 = (double)lateral * (double)lateral;
     ws.cols = base; base += n * lateral_column_doubles(M);
     ws.part = base; base += n;
@@ -72,6 +77,10 @@ DSA_CS LateralWs lateral_ws(double* base, int nvx, int nvy, int M, float lateral
     ws.active = ws.ic + kLatInts;
     return ws;
 }
+
+DSA_CS LateralWs lateral_ws(double* base, int nvx, int nvy, int M, float lateral) { return lateral_ws(base, nvx, nvy, M, lateral, lateral > 0.0f); }
+
+DSA_CS const LateralWs& lateral_view(const LateralWs& ws) { return ws; }
 
 struct LateralColumn { double *N, *F, *d, *b, *x, *r, *z, *q, *p0, *p1; };
 
@@ -150,20 +159,18 @@ DSA_CS void lateral_operator(const LateralWs& ws, int b, const LateralColumn& c,
     }
 }
 
-// Set-up of column b: assemble and factor in the work arrays w (column_work), N, the factor and b_c to the workspace, the column's active
-// flag.  Returns the column's flag; *nused and *chi2 are column_assemble's.  Every lane returns the same.
+// The tail of a set-up of column b, after the system's assembly in the work arrays w (nused: the column's used data, all kinds): N (copied
+// before the factorisation overwrites it) and b_c to the workspace, column_factor of ws.M unknowns, the factor to the workspace, the
+// column's active flag.  Returns the column's flag.  Every lane returns the same.
 template <class Sync>
-DSA_CS int lateral_setup(const ColumnIn& in, float smooth, float damp, const ColumnWork& w, const LateralWs& ws, int b, int* nused, double* chi2, int lane,
-                         int nlanes, Sync sync)
+DSA_CS int lateral_store_factor(const LateralWs& ws, int b, const ColumnWork& w, int nused, int lane, int nlanes, Sync sync)
 {
-    const double lambda2 = (double)smooth * (double)smooth, mu2 = (double)damp * (double)damp;
-    const int M = in.M, T = column_tri_size(M);
-    const LateralColumn c = lateral_column(ws, b);
-    *nused = column_assemble(in, lambda2, mu2, w, chi2, lane, nlanes, sync);
-    if (*nused == 0 && !ws.edges) {
+    if (nused == 0 && !ws.edges) {
         if (lane == 0) ws.active[b] = 0;
         return kColumnNoData;
     }
+    const int M = ws.M, T = column_tri_size(M);
+    const LateralColumn c = lateral_column(ws, b);
     for (int e = lane; e < T; e += nlanes) c.N[e] = w.tri[e];
     for (int l = lane; l < M; l += nlanes) c.b[l] = w.b[l];
     sync();
@@ -174,6 +181,17 @@ DSA_CS int lateral_setup(const ColumnIn& in, float smooth, float damp, const Col
     }
     if (lane == 0) ws.active[b] = flag == kColumnOk ? 1 : 0;
     return flag;
+}
+
+// Set-up of column b: assemble in the work arrays w (column_work), then lateral_store_factor.  Returns the column's flag; *nused and *chi2
+// are column_assemble's.  Every lane returns the same.
+template <class Sync>
+DSA_CS int lateral_setup(const ColumnIn& in, float smooth, float damp, const ColumnWork& w, const LateralWs& ws, int b, int* nused, double* chi2, int lane,
+                         int nlanes, Sync sync)
+{
+    const double lambda2 = (double)smooth * (double)smooth, mu2 = (double)damp * (double)damp;
+    *nused = column_assemble(in, lambda2, mu2, w, chi2, lane, nlanes, sync);
+    return lateral_store_factor(ws, b, w, *nused, lane, nlanes, sync);
 }
 
 // bt_c in place of b_c, x_c = M^-1 bt_c, p_old = 0, the column's figure of bt^T x.  vels: the model, element l of column c at l * v_stride + c.
@@ -203,16 +221,17 @@ DSA_CS void lateral_start(const LateralWs& ws, int b, const float* vels, long lo
 }
 
 // r = bt - A x, z = M^-1 r, the column's figure of r^T z
-template <class Sync>
-DSA_CS void lateral_residual(const LateralWs& ws, int b, int lane, int nlanes, Sync sync)
+template <class Sys, class Sync>
+DSA_CS void lateral_residual(const Sys& sys, int b, int lane, int nlanes, Sync sync)
 {
+    const LateralWs& ws = lateral_view(sys);
     if (!ws.active[b]) {
         if (lane == 0) ws.part[b] = 0.0;
         return;
     }
     const int M = ws.M;
     const LateralColumn c = lateral_column(ws, b);
-    lateral_operator(ws, b, c, c.x, 0, 0.0, 0, lane, nlanes);
+    lateral_operator(sys, b, c, c.x, 0, 0.0, 0, lane, nlanes);
     sync();
     for (int l = lane; l < M; l += nlanes) c.r[l] = c.b[l] - c.q[l];
     sync();
@@ -221,9 +240,10 @@ DSA_CS void lateral_residual(const LateralWs& ws, int b, int lane, int nlanes, S
 }
 
 // first half of an iteration: p = z + beta p_old (kept beside p_old), q = A p, the column's figure of p^T q
-template <class Sync>
-DSA_CS void lateral_direction(const LateralWs& ws, int b, int lane, int nlanes, Sync sync)
+template <class Sys, class Sync>
+DSA_CS void lateral_direction(const Sys& sys, int b, int lane, int nlanes, Sync sync)
 {
+    const LateralWs& ws = lateral_view(sys);
     if (ws.ic[kLatDone]) return;
     if (!ws.active[b]) {
         if (lane == 0) ws.part[b] = 0.0;
@@ -235,12 +255,12 @@ DSA_CS void lateral_direction(const LateralWs& ws, int b, int lane, int nlanes, 
     double* p = lateral_p(c, 1 - pold);
     for (int l = lane; l < M; l += nlanes) p[l] = lateral_operand(c, l, 1, beta, pold);
     sync();
-    lateral_operator(ws, b, c, p, 1, beta, pold, lane, nlanes);
+    lateral_operator(sys, b, c, p, 1, beta, pold, lane, nlanes);
     sync();
     if (lane == 0) ws.part[b] = lateral_dot(M, p, c.q);
 }
 
-// second half: x = x + alpha p, r = r - alpha q, z = M^-1 r, the column's figure of r^T z
+// second half, the same for every system: x = x + alpha p, r = r - alpha q, z = M^-1 r, the column's figure of r^T z
 template <class Sync>
 DSA_CS void lateral_update(const LateralWs& ws, int b, int lane, int nlanes, Sync sync)
 {
@@ -312,18 +332,31 @@ DSA_CS void lateral_reduce(const LateralWs& ws, int what, double tol, int maxit,
     if (lane == 0) lateral_scalars(ws, what, s, tol, maxit);
 }
 
-// the clipped step of column b and its stepped values; a column that is not active keeps its values and reports zeros.  dv may be null.
-DSA_CS void lateral_finish(const LateralWs& ws, int b, float dvmax, float minvel, float maxvel, float* vels, long long v_stride, float* dv, long long dv_stride,
-                           int lane, int nlanes)
+// the clipped step of column b and its stepped values; a column that is not active keeps its values and reports zeros.  The ws.M unknowns
+// are one block of the model vels0 (Mb = ws.M), or two blocks of Mb = ws.M / 2 rows: vels0's, then vels1's.  dv0 / dv1: null, or the blocks'
+// steps, element l of column c at l * dv_stride + c.
+DSA_CS void lateral_finish_blocks(const LateralWs& ws, int b, int Mb, float dvmax, float minvel, float maxvel, float* vels0, float* vels1, long long v_stride,
+                                  float* dv0, float* dv1, long long dv_stride, int lane, int nlanes)
 {
     const long long col = lateral_model_column(ws, b);
     const bool on = ws.active[b] != 0;
     const LateralColumn c = lateral_column(ws, b);
-    for (int l = lane; l < ws.M; l += nlanes) {
-        const float s = on ? column_clip(c.x[l], dvmax) : 0.0f;
+    for (int i = lane; i < ws.M; i += nlanes) {
+        const bool second = i >= Mb;
+        const int l = second ? i - Mb : i;
+        float* vel = second ? vels1 : vels0;
+        float* dv = second ? dv1 : dv0;
+        const float s = on ? column_clip(c.x[i], dvmax) : 0.0f;
         if (dv) dv[l * dv_stride + col] = s;
-        if (on) vels[l * v_stride + col] = column_stepped(vels[l * v_stride + col], s, minvel, maxvel);
+        if (on) vel[l * v_stride + col] = column_stepped(vel[l * v_stride + col], s, minvel, maxvel);
     }
+}
+
+// this system's finish: one block.  dv may be null.
+DSA_CS void lateral_finish(const LateralWs& ws, int b, float dvmax, float minvel, float maxvel, float* vels, long long v_stride, float* dv, long long dv_stride,
+                           int lane, int nlanes)
+{
+    lateral_finish_blocks(ws, b, ws.M, dvmax, minvel, maxvel, vels, nullptr, v_stride, dv, nullptr, dv_stride, lane, nlanes);
 }
 
 // info (4 doubles): itn, istop, rz0, the last rz

@@ -20,10 +20,12 @@
 //   A y       row i of the B-vector: f = t + w2 ((double)deg y_c[i] - s) -- column_lateral.h's figure: t = sum_j N_c[i][j] y_c[j], j ascending from
 //             0.0; s = the edge sum of y_c'[i] from 0.0 -- then, with l the depth of row i, u = y_c[M + l] - y_c[l], su = the edge sum from 0.0
 //             of (y_c'[M + l] - y_c'[l]) and g = wa2 ((double)deg u - su):  q_c[i] = f - g in the Vsv block, f + g in the Vsh block
-//   M^-1, dots, PCG   column_lateral.h's, word for word, by calling lateral_precondition, lateral_dot, lateral_update, lateral_sum,
-//             lateral_scalars, lateral_reduce and lateral_info on the B-sized workspace; without edges the loop stops at itn 0 whatever rz is,
-//             and rz is the residual of that direct solve
-//   apply     column_clip and column_stepped on both blocks of x of every active column; the others keep their values and report dv = 0
+//   M^-1, dots, PCG   column_lateral.h's, word for word: its phases lateral_store_factor, lateral_residual, lateral_direction and lateral_update
+//             run on this system through lateral_view and the lateral_operator overload below, its lateral_sum, lateral_scalars,
+//             lateral_reduce and lateral_info on the B-sized workspace; without edges the loop stops at itn 0 whatever rz is, and rz is the
+//             residual of that direct solve
+//   apply     lateral_finish_blocks over two blocks of rows: column_clip and column_stepped on both blocks of x of every active column; the others
+//             keep their values and report dv = 0
 //
 // A neighbour's operand during an iteration is its new direction z + beta p_old, computed here by the neighbour's own expression
 // (lateral_operand), so no column waits for another.  Without edges every output and both stepped models are radial_step's bit for bit.
@@ -49,38 +51,23 @@ DSA_CS size_t radial_lateral_ws_doubles(int nvx, int nvy, int M) { return latera
 DSA_CS RadialLateralWs radial_lateral_ws(double* base, int nvx, int nvy, int M, float lateral, float lateral_aniso)
 {
     RadialLateralWs rl;
-    rl.ws = lateral_ws(base, nvx, nvy, 2 * M, lateral);
-    rl.ws.edges = (lateral > 0.0f || lateral_aniso > 0.0f) ? 1 : 0;
+    rl.ws = lateral_ws(base, nvx, nvy, 2 * M, lateral, lateral > 0.0f || lateral_aniso > 0.0f);
     rl.M = M;
     rl.wa2 = (double)lateral_aniso * (double)lateral_aniso;
     return rl;
 }
 
-// Set-up of column b: radial_assemble and column_factor(2M) in the work arrays w (radial_work); N (copied before the factorisation overwrites
-// it), b_c and the factor to the workspace; the column's active flag.  vsv / vsh: the column's values at l * v_stride.  Returns the column's
-// flag; nused[2] and chi2[2] are radial_assemble's.  Every lane returns the same.
+DSA_CS const LateralWs& lateral_view(const RadialLateralWs& rl) { return rl.ws; }
+
+// Set-up of column b: radial_assemble in the work arrays w (radial_work), then lateral_store_factor on the 2M unknowns.  vsv / vsh: the
+// column's values at l * v_stride.  Returns the column's flag; nused[2] and chi2[2] are radial_assemble's.  Every lane returns the same.
 template <class Sync>
 DSA_CS int radial_lateral_setup(const RadialIn& in, float smooth, float damp, float aniso, const float* vsv, const float* vsh, long long v_stride,
                                 const ColumnWork& w, const RadialLateralWs& rl, int b, int* nused, double* chi2, int lane, int nlanes, Sync sync)
 {
     const double lambda2 = (double)smooth * (double)smooth, mu2 = (double)damp * (double)damp, gamma2 = (double)aniso * (double)aniso;
-    const int B = 2 * in.M, T = column_tri_size(B);
-    const LateralColumn c = lateral_column(rl.ws, b);
     radial_assemble(in, lambda2, mu2, gamma2, vsv, vsh, v_stride, w, nused, chi2, lane, nlanes, sync);
-    if (nused[0] + nused[1] == 0 && !rl.ws.edges) {
-        if (lane == 0) rl.ws.active[b] = 0;
-        return kColumnNoData;
-    }
-    for (int e = lane; e < T; e += nlanes) c.N[e] = w.tri[e];
-    for (int i = lane; i < B; i += nlanes) c.b[i] = w.b[i];
-    sync();
-    const int flag = column_factor(B, w, lane, nlanes, sync);
-    if (flag == kColumnOk) {
-        for (int e = lane; e < T; e += nlanes) c.F[e] = w.tri[e];
-        for (int i = lane; i < B; i += nlanes) c.d[i] = w.d[i];
-    }
-    if (lane == 0) rl.ws.active[b] = flag == kColumnOk ? 1 : 0;
-    return flag;
+    return lateral_store_factor(rl.ws, b, w, nused[0] + nused[1], lane, nlanes, sync);
 }
 
 // bt_c in place of b_c, x_c = M^-1 bt_c, p_old = 0, the column's figure of bt^T x.  vsv / vsh: the models, element l of column c at l * v_stride + c.
@@ -121,9 +108,9 @@ DSA_CS void radial_lateral_start(const RadialLateralWs& rl, int b, const float* 
     if (lane == 0) ws.part[b] = lateral_dot(B, c.b, c.x);
 }
 
-// c.q = (A y)_c, y_c = own; what, beta, pold: lateral_operand's, for the neighbours
-DSA_CS void radial_lateral_operator(const RadialLateralWs& rl, int b, const LateralColumn& c, const double* own, int what, double beta, int pold, int lane,
-                                    int nlanes)
+// The system's operator, under the name column_lateral.h's phases call: c.q = (A y)_c, y_c = own; what, beta, pold: lateral_operand's, for the
+// neighbours.  Not column_lateral.h's operator with a second term: f - g and f + g are chains of their own.
+DSA_CS void lateral_operator(const RadialLateralWs& rl, int b, const LateralColumn& c, const double* own, int what, double beta, int pold, int lane, int nlanes)
 {
     const LateralWs& ws = rl.ws;
     const int M = rl.M, B = ws.M;
@@ -150,65 +137,18 @@ DSA_CS void radial_lateral_operator(const RadialLateralWs& rl, int b, const Late
     }
 }
 
-// r = bt - A x, z = M^-1 r, the column's figure of r^T z
+// column_lateral.h's phases on this system, under the names the step's callers use: r = bt - A x, z = M^-1 r; the first half of an
+// iteration (the second is lateral_update); the finish over both models.  dv_v / dv_h: null, or the blocks' steps.
 template <class Sync>
-DSA_CS void radial_lateral_residual(const RadialLateralWs& rl, int b, int lane, int nlanes, Sync sync)
-{
-    const LateralWs& ws = rl.ws;
-    if (!ws.active[b]) {
-        if (lane == 0) ws.part[b] = 0.0;
-        return;
-    }
-    const int B = ws.M;
-    const LateralColumn c = lateral_column(ws, b);
-    radial_lateral_operator(rl, b, c, c.x, 0, 0.0, 0, lane, nlanes);
-    sync();
-    for (int i = lane; i < B; i += nlanes) c.r[i] = c.b[i] - c.q[i];
-    sync();
-    lateral_precondition(B, c, c.r, c.z, lane, nlanes, sync);
-    if (lane == 0) ws.part[b] = lateral_dot(B, c.r, c.z);
-}
+DSA_CS void radial_lateral_residual(const RadialLateralWs& rl, int b, int lane, int nlanes, Sync sync) { lateral_residual(rl, b, lane, nlanes, sync); }
 
-// first half of an iteration: p = z + beta p_old (kept beside p_old), q = A p, the column's figure of p^T q.  The second half is lateral_update.
 template <class Sync>
-DSA_CS void radial_lateral_direction(const RadialLateralWs& rl, int b, int lane, int nlanes, Sync sync)
-{
-    const LateralWs& ws = rl.ws;
-    if (ws.ic[kLatDone]) return;
-    if (!ws.active[b]) {
-        if (lane == 0) ws.part[b] = 0.0;
-        return;
-    }
-    const int B = ws.M, pold = ws.ic[kLatItn] & 1;
-    const double beta = ws.sc[kLatBeta];
-    const LateralColumn c = lateral_column(ws, b);
-    double* p = lateral_p(c, 1 - pold);
-    for (int i = lane; i < B; i += nlanes) p[i] = lateral_operand(c, i, 1, beta, pold);
-    sync();
-    radial_lateral_operator(rl, b, c, p, 1, beta, pold, lane, nlanes);
-    sync();
-    if (lane == 0) ws.part[b] = lateral_dot(B, p, c.q);
-}
+DSA_CS void radial_lateral_direction(const RadialLateralWs& rl, int b, int lane, int nlanes, Sync sync) { lateral_direction(rl, b, lane, nlanes, sync); }
 
-// the clipped steps of column b and the stepped values of both models; a column that is not active keeps its values and reports zeros.
-// dv_v / dv_h: null, or the blocks' steps, element l of column c at l * dv_stride + c.
 DSA_CS void radial_lateral_finish(const RadialLateralWs& rl, int b, float dvmax, float minvel, float maxvel, float* vsv, float* vsh, long long v_stride, float* dv_v,
                                   float* dv_h, long long dv_stride, int lane, int nlanes)
 {
-    const LateralWs& ws = rl.ws;
-    const int M = rl.M;
-    const long long col = lateral_model_column(ws, b);
-    const bool on = ws.active[b] != 0;
-    const LateralColumn c = lateral_column(ws, b);
-    for (int i = lane; i < ws.M; i += nlanes) {
-        const bool lv = i >= M;
-        const int l = lv ? i - M : i;
-        float* vel = lv ? vsh : vsv;
-        float* dv = lv ? dv_h : dv_v;
-        const float s = on ? column_clip(c.x[i], dvmax) : 0.0f;
-        if (dv) dv[l * dv_stride + col] = s;
-        if (on) vel[l * v_stride + col] = column_stepped(vel[l * v_stride + col], s, minvel, maxvel);
-    }
+    lateral_finish_blocks(rl.ws, b, rl.M, dvmax, minvel, maxvel, vsv, vsh, v_stride, dv_v, dv_h, dv_stride, lane, nlanes);
 }
 
 }  // namespace dsa

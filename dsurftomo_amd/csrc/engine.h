@@ -305,6 +305,15 @@ struct Engine {
     // in the step's order of refusals; step: also dvmax, minvel, maxvel; radial: the kind of stage the caller works on (the other kind is refused)
     int columns_front(const char* who, int nmaps_in, const float* obs, const float* wt, float smooth, float damp, bool step, float dvmax, float minvel, float maxvel,
                       bool radial = false);
+    // the named steps the five columns_* calls share (engine.hip, below columns_front): one argument check, the coupled steps' checks, the
+    // Love mask, stage-in for 1 or 2 models (step: with the step's zeroed outputs), the LDS refusal, the coupled loop, a step's stage-out
+    int columns_weight(const char* who, const char* name, float v);
+    int columns_coupled_front(const char* who, int blocks, float lateral, float lateral_aniso, double tol, int maxit);
+    unsigned long long columns_love() const;
+    int columns_stage_in(int models, const float* obs, const float* wt, bool step);
+    int columns_lds_refusal(const char* who, int rc, int unknowns, size_t lds, int limit);
+    int columns_coupled_loop(const CoupledSystem& s, double tol, int maxit, float dvmax, float minvel, float maxvel);
+    int columns_stage_out(int models, float* dv, int* nused, double* chi2, int* flag, const CoupledSystem* s, double* info);
     // depth resolution of the columns (dsa_columns_resolution, k_column_resolution): reads what the step reads, changes nothing
     OwnedBuf<double> col_meas, col_lev, col_trace, col_R;
     OwnedBuf<float> col_depz;
@@ -323,14 +332,14 @@ struct Engine {
                             float* dv, int* nused, double* chi2, int* flag);
     int dispersion_get_model_radial(float* vsv, float* vsh);
     // laterally coupled step (dsa_columns_step_lateral, k_lateral_*): dsa_columns_step's state, arguments and outputs; the
-    // workspace of the conjugate-gradient loop stays between calls.  The host looks at the loop's done flag every lateral_poll iterations.
+    // workspace of the conjugate-gradient loop is kept allocated between calls; no call reads what an earlier one left in it.  The host looks at
+    // the loop's done flag every lateral_poll iterations.
     OwnedBuf<double> col_lat;
     static constexpr int lateral_poll = 16;
     int columns_step_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel, float maxvel,
                              double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
-    // laterally coupled radial step (dsa_columns_step_radial_lateral, k_radial_lateral_*): dsa_columns_step_radial's state,
-    // arguments and outputs, the loop and the poll of the lateral step; a workspace of its own (2 (nz - 1) unknowns per column)
-    OwnedBuf<double> col_rlat;
+    // laterally coupled radial step (dsa_columns_step_radial_lateral, k_radial_lateral_setup / _start, then k_lateral_*):
+    // dsa_columns_step_radial's state, arguments and outputs, the loop, the poll and the workspace (2 (nz - 1) unknowns per column) of the lateral step
     int columns_step_radial_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral, float lateral_aniso,
                                     float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
 

@@ -447,40 +447,133 @@ int Engine::columns_front(const char* who, int nmaps_in, const float* obs, const
     return 0;
 }
 
-// dsa_columns_step (DESIGN.md section 21): one Gauss-Newton step of every interior column of the resident model towards the maps obs, from
-// the curves and depth kernels the dispersion runs left on the device.  Everything is checked before the device is touched.  The combined
-// sensitivities of all slots go to a buffer of the step's own (Srow, which the Frechet rows read, is not written); k_column_step moves
-// vels_d where it lies; h_vels follows, the marks are cleared: the next step needs new runs, which see the stepped model.
-int Engine::columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
-                         double* chi2, int* flag)
+// ---- the steps the five columns_* calls below are made of ----
+
+int Engine::columns_weight(const char* who, const char* name, float v)
 {
-    if (int rc = columns_front("columns_step", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
+    if (!std::isfinite(v) || v < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: %s %g must be finite and >= 0", who, name, (double)v); return DSA_ERR_ARGUMENT; }
+    return 0;
+}
+
+// what the coupled steps ask after columns_front (and aniso): lateral, for two blocks lateral_aniso, tol, maxit, and the size of the workspace
+// (alone against the whole of dsa_set_memory_budget, where one is set: not against what the budget leaves beside the other buffers)
+int Engine::columns_coupled_front(const char* who, int blocks, float lateral, float lateral_aniso, double tol, int maxit)
+{
+    if (int rc = columns_weight(who, "lateral", lateral)) return rc;
+    if (blocks == 2) if (int rc = columns_weight(who, "lateral_aniso", lateral_aniso)) return rc;
+    if (!std::isfinite(tol) || tol <= 0.0) { fail(DSA_ERR_ARGUMENT, "%s: tol %g must be finite and > 0", who, tol); return DSA_ERR_ARGUMENT; }
+    if (maxit < 1) { fail(DSA_ERR_ARGUMENT, "%s: maxit %d must be at least 1", who, maxit); return DSA_ERR_ARGUMENT; }
+    const size_t ws_bytes = coupled_ws_bytes(blocks, disp_nx, disp_ny, disp_nz);
+    if (mem_budget && ws_bytes > mem_budget) {
+        fail(DSA_ERR_CAPACITY, "%s: the workspace of %d x %d columns of %d unknowns needs %zu bytes, the memory budget is %zu", who, disp_nx - 2, disp_ny - 2, blocks * (disp_nz - 1), ws_bytes, mem_budget);
+        return DSA_ERR_CAPACITY;
+    }
+    return 0;
+}
+
+// bit k set where slot k is a Love slot, by the slots' marks
+unsigned long long Engine::columns_love() const
+{
+    unsigned long long love = 0ull;
+    for (int k = 0; k < disp_nmaps; ++k) if (disp_slot_mark[(size_t)k].iwave == 1) love |= 1ull << k;
+    return love;
+}
+
+// Stage-in: obs and wt to the device; the combined sensitivities of all slots, k_sen_combine's rule on the Vsv model and, for two models,
+// on the Vsh model, into buffers of the step's own (Srow, which the Frechet rows read, is not written); with step, the step's outputs of
+// 1 or 2 models, zeroed (the outer ring of columns reports zeros: the kernels run on the interior).
+int Engine::columns_stage_in(int models, const float* obs, const float* wt, bool step)
+{
     const int K = disp_nmaps, M = disp_nz - 1;
-    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
-    HIP_TRY(this, hipSetDevice(device));
-    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, ncol * M) || ensure(col_nused, ncol) ||
-        ensure(col_chi2, ncol) || ensure(col_flag, ncol)) return status;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K, nm = (size_t)models;
+    if (ensure(col_S, ncol * K * M) || (models == 2 && ensure(col_Sh, ncol * K * M)) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs))) return status;
+    if (step && (ensure(col_dv, nm * ncol * M) || ensure(col_nused, nm * ncol) || ensure(col_chi2, nm * ncol) || ensure(col_flag, ncol))) return status;
     HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
     if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
-    // (the outer ring of columns reports zeros: the kernel runs on the interior)
-    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, ncol * M * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, ncol * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
-    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
-    launch_column_step(disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, dvmax, minvel, maxvel, vels_d.p,
-                       col_dv.p, col_nused.p, col_chi2.p, col_flag.p, stream);
+    if (step) {
+        HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, nm * ncol * M * 4, stream));
+        HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, nm * ncol * 4, stream));
+        HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, nm * ncol * 8, stream));
+        HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    }
+    const int shallow = h_depz[disp_nz - 2] < 35.0f ? 1 : 0;
+    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_S.p, stream);
+    if (models == 2) launch_sen_combine((int)ncol, K, disp_nz, vsh_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_Sh.p, stream);
+    return 0;
+}
+
+// a launcher's refusal (rc 1 or 2: column_kernels.hip's rule for the dynamic LDS) as DSA_ERR_DEVICE
+int Engine::columns_lds_refusal(const char* who, int rc, int unknowns, size_t lds, int limit)
+{
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    if (rc == 1) fail(DSA_ERR_DEVICE, "%s: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", who, unknowns, disp_nmaps, lds, limit);
+    else fail(DSA_ERR_DEVICE, "%s: the device refuses %zu bytes of dynamic LDS per workgroup", who, lds);
+    return DSA_ERR_DEVICE;
+}
+
+// The conjugate-gradient loop of a coupled system after its set-up, and the finish.  The loop is bounded by maxit here; its scalars and its
+// done flag stay on the device, an iteration started after the flag is set does nothing, so how often the host looks at the flag (every
+// lateral_poll iterations) cannot change a bit.
+int Engine::columns_coupled_loop(const CoupledSystem& s, double tol, int maxit, float dvmax, float minvel, float maxvel)
+{
+    launch_coupled_first(s, tol, maxit, stream);
     HIP_TRY(this, hipGetLastError());
+    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
+    const bool edges = coupled_edges(s);
+    for (int it = 1; edges && it <= maxit; ++it) {
+        launch_coupled_iteration(s, tol, maxit, stream);
+        if (it % lateral_poll == 0 && it < maxit) {
+            HIP_TRY(this, hipMemcpyAsync(ints, coupled_ints(s), sizeof ints, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(this, hipStreamSynchronize(stream));
+            if (ints[1]) break;
+        }
+    }
+    launch_coupled_finish(s, dvmax, minvel, maxvel, vels_d.p, s.blocks == 2 ? vsh_d.p : nullptr, col_dv.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    return 0;
+}
+
+// Stage-out of a step of 1 or 2 models: the marks are cleared (the next step needs new runs, which see the stepped model), the host copies
+// of the model(s) follow, the optional outputs; s: the coupled system whose itn, istop, rz0 and last rz go to info, or null.
+int Engine::columns_stage_out(int models, float* dv, int* nused, double* chi2, int* flag, const CoupledSystem* s, double* info)
+{
+    const size_t ncol = (size_t)disp_nx * disp_ny, nm = (size_t)models, M = (size_t)disp_nz - 1;
     for (DispMark& m : disp_map_mark) m.fresh = false;
     for (DispMark& m : disp_slot_mark) m.fresh = false;
     h_vels.resize(ncol * disp_nz);
     HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
-    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, ncol * M * 4, hipMemcpyDeviceToHost, stream));
-    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
-    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (models == 2) {
+        h_vsh.resize(ncol * disp_nz);
+        HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, h_vsh.size() * 4, hipMemcpyDeviceToHost, stream));
+    }
+    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
+    double rz[2] = { 0.0, 0.0 };        // the last rz, rz0
+    if (s) {
+        HIP_TRY(this, hipMemcpyAsync(ints, coupled_ints(*s), sizeof ints, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(this, hipMemcpyAsync(rz, coupled_scalars(*s), sizeof rz, hipMemcpyDeviceToHost, stream));
+    }
+    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, nm * ncol * M * 4, hipMemcpyDeviceToHost, stream));
+    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, nm * ncol * 4, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, nm * ncol * 8, hipMemcpyDeviceToHost, stream));
     if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
+    if (s && info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
     return 0;
+}
+
+// dsa_columns_step (DESIGN.md section 21): one Gauss-Newton step of every interior column of the resident model towards the maps obs, from
+// the curves and depth kernels the dispersion runs left on the device.  Everything is checked before the device is touched.
+// k_column_step moves vels_d where it lies.
+int Engine::columns_step(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float dvmax, float minvel, float maxvel, float* dv, int* nused,
+                         double* chi2, int* flag)
+{
+    if (int rc = columns_front("columns_step", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
+    HIP_TRY(this, hipSetDevice(device));
+    if (int rc = columns_stage_in(1, obs, wt, true)) return rc;
+    launch_column_step(disp_nx, disp_ny, disp_nz, disp_nmaps, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, dvmax, minvel, maxvel, vels_d.p,
+                       col_dv.p, col_nused.p, col_chi2.p, col_flag.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    return columns_stage_out(1, dv, nused, chi2, flag, nullptr, nullptr);
 }
 
 // dsa_columns_resolution: the resolution measures of the same columns from the same resident curves and kernels.  The
@@ -493,10 +586,9 @@ int Engine::columns_resolution(int nmaps_in, const float* obs, const float* wt, 
     const int K = disp_nmaps, M = disp_nz - 1;
     const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
     HIP_TRY(this, hipSetDevice(device));
-    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_depz, (size_t)disp_nz) || ensure(col_meas, 4 * ncol * M) ||
-        ensure(col_lev, nobs) || ensure(col_trace, ncol) || (R && ensure(col_R, ncol * M * M)) || ensure(col_nused, ncol) || ensure(col_flag, ncol)) return status;
-    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
-    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (int rc = columns_stage_in(1, obs, wt, false)) return rc;
+    if (ensure(col_depz, (size_t)disp_nz) || ensure(col_meas, 4 * ncol * M) || ensure(col_lev, nobs) || ensure(col_trace, ncol) || (R && ensure(col_R, ncol * M * M)) ||
+        ensure(col_nused, ncol) || ensure(col_flag, ncol)) return status;
     HIP_TRY(this, hipMemcpyAsync(col_depz.p, h_depz.data(), (size_t)disp_nz * 4, hipMemcpyHostToDevice, stream));
     // (the outer ring of columns reports zeros: the kernel runs on the interior)
     HIP_TRY(this, hipMemsetAsync(col_meas.p, 0, 4 * ncol * M * 8, stream));
@@ -505,16 +597,10 @@ int Engine::columns_resolution(int nmaps_in, const float* obs, const float* wt, 
     if (R) HIP_TRY(this, hipMemsetAsync(col_R.p, 0, ncol * M * M * 8, stream));
     HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
     HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
-    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
     int limit = 0;
     const int rc = launch_column_resolution(device, disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_depz.p, smooth, damp,
                                             col_meas.p, col_lev.p, col_trace.p, R ? col_R.p : nullptr, col_nused.p, col_flag.p, stream, &limit);
-    if (rc) {
-        HIP_TRY(this, hipStreamSynchronize(stream));
-        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_resolution: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", M, K, column_resolution_lds_bytes(disp_nz, K), limit);
-        else fail(DSA_ERR_DEVICE, "columns_resolution: the device refuses %zu bytes of dynamic LDS per workgroup", column_resolution_lds_bytes(disp_nz, K));
-        return DSA_ERR_DEVICE;
-    }
+    if (rc) return columns_lds_refusal("columns_resolution", rc, M, column_resolution_lds_bytes(disp_nz, K), limit);
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipMemcpyAsync(measures, col_meas.p, 4 * ncol * M * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipMemcpyAsync(leverage, col_lev.p, nobs * 8, hipMemcpyDeviceToHost, stream));
@@ -550,193 +636,65 @@ int Engine::dispersion_get_model_radial(float* vsv, float* vsh)
 }
 
 // dsa_columns_step_radial: dsa_columns_step on a radial stage.  The state and argument rules are columns_front's, then
-// aniso; everything is checked before the device is touched.  The combined sensitivities are k_sen_combine's rule twice, on the Vsv and on
-// the Vsh model, into two buffers of the step's own (Srow is not written); the kernel reads the first at the Rayleigh slots and the second at
-// the Love slots, by the mask of the slots' marks.  Both models are stepped where they lie, the host copies follow, the marks are cleared.
+// aniso; everything is checked before the device is touched.  The kernel reads the Vsv model's sensitivities at the Rayleigh slots and the
+// Vsh model's at the Love slots, by the mask of the slots' marks.  Both models are stepped where they lie.
 int Engine::columns_step_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel,
                                 float* dv, int* nused, double* chi2, int* flag)
 {
-    if (int rc = columns_front("columns_step_radial", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
-    if (!std::isfinite(aniso) || aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial: aniso %g must be finite and >= 0", (double)aniso); return DSA_ERR_ARGUMENT; }
-    const int K = disp_nmaps, M = disp_nz - 1;
-    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
-    unsigned long long love = 0ull;
-    for (int k = 0; k < K; ++k) if (disp_slot_mark[(size_t)k].iwave == 1) love |= 1ull << k;
+    const char* who = "columns_step_radial";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
+    if (int rc = columns_weight(who, "aniso", aniso)) return rc;
     HIP_TRY(this, hipSetDevice(device));
-    if (ensure(col_S, ncol * K * M) || ensure(col_Sh, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, 2 * ncol * M) ||
-        ensure(col_nused, 2 * ncol) || ensure(col_chi2, 2 * ncol) || ensure(col_flag, ncol)) return status;
-    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
-    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
-    // (the outer ring of columns reports zeros: the kernel runs on the interior)
-    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, 2 * ncol * M * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, 2 * ncol * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, 2 * ncol * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
-    const int shallow = h_depz[disp_nz - 2] < 35.0f ? 1 : 0;
-    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_S.p, stream);
-    launch_sen_combine((int)ncol, K, disp_nz, vsh_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_Sh.p, stream);
+    if (int rc = columns_stage_in(2, obs, wt, true)) return rc;
     int limit = 0;
-    const int rc = launch_column_step_radial(device, disp_nx, disp_ny, disp_nz, K, love, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p, smooth, damp,
-                                             aniso, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, col_dv.p, col_nused.p, col_chi2.p, col_flag.p, stream, &limit);
-    if (rc) {
-        HIP_TRY(this, hipStreamSynchronize(stream));
-        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_step_radial: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", 2 * M, K, column_radial_lds_bytes(disp_nz, K), limit);
-        else fail(DSA_ERR_DEVICE, "columns_step_radial: the device refuses %zu bytes of dynamic LDS per workgroup", column_radial_lds_bytes(disp_nz, K));
-        return DSA_ERR_DEVICE;
-    }
+    const int rc = launch_column_step_radial(device, disp_nx, disp_ny, disp_nz, disp_nmaps, columns_love(), col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p,
+                                             col_Sh.p, smooth, damp, aniso, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, col_dv.p, col_nused.p, col_chi2.p, col_flag.p,
+                                             stream, &limit);
+    if (rc) return columns_lds_refusal(who, rc, 2 * (disp_nz - 1), column_radial_lds_bytes(disp_nz, disp_nmaps), limit);
     HIP_TRY(this, hipGetLastError());
-    for (DispMark& m : disp_map_mark) m.fresh = false;
-    for (DispMark& m : disp_slot_mark) m.fresh = false;
-    h_vels.resize(ncol * disp_nz);
-    h_vsh.resize(ncol * disp_nz);
-    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, h_vsh.size() * 4, hipMemcpyDeviceToHost, stream));
-    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, 2 * ncol * M * 4, hipMemcpyDeviceToHost, stream));
-    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, 2 * ncol * 4, hipMemcpyDeviceToHost, stream));
-    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
-    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipStreamSynchronize(stream));
-    return 0;
+    return columns_stage_out(2, dv, nused, chi2, flag, nullptr, nullptr);
 }
 
 // dsa_columns_step_lateral: dsa_columns_step with the interior columns tied to their neighbours, column_lateral.h's
-// preconditioned conjugate gradients.  The state and argument rules are columns_front's, then lateral, tol, maxit and the size of the
-// workspace (alone against the whole of dsa_set_memory_budget, where one is set: not against what the budget leaves beside the other buffers);
-// everything is checked before the device is touched.  The loop is bounded by maxit here; its scalars and its done flag stay on
-// the device, an iteration started after the flag is set does nothing, so how often the host looks at the flag cannot change a bit.
+// preconditioned conjugate gradients.  The state and argument rules are columns_front's, then columns_coupled_front's; everything is checked
+// before the device is touched.  The workspace (col_lat, shared with the radial coupled step) carries nothing from call to call: every word
+// a call reads, the set-up, the start or a reduction of the same call has written.
 int Engine::columns_step_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel, float maxvel,
                                  double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info)
 {
-    if (int rc = columns_front("columns_step_lateral", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
-    if (!std::isfinite(lateral) || lateral < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: lateral %g must be finite and >= 0", (double)lateral); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(tol) || tol <= 0.0) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: tol %g must be finite and > 0", tol); return DSA_ERR_ARGUMENT; }
-    if (maxit < 1) { fail(DSA_ERR_ARGUMENT, "columns_step_lateral: maxit %d must be at least 1", maxit); return DSA_ERR_ARGUMENT; }
-    const int K = disp_nmaps, M = disp_nz - 1;
-    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
-    const size_t ws_bytes = column_lateral_ws_bytes(disp_nx, disp_ny, disp_nz);
-    if (mem_budget && ws_bytes > mem_budget) {
-        fail(DSA_ERR_CAPACITY, "columns_step_lateral: the workspace of %d x %d columns of %d unknowns needs %zu bytes, the memory budget is %zu", disp_nx - 2, disp_ny - 2, M, ws_bytes, mem_budget);
-        return DSA_ERR_CAPACITY;
-    }
+    const char* who = "columns_step_lateral";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel)) return rc;
+    if (int rc = columns_coupled_front(who, 1, lateral, 0.0f, tol, maxit)) return rc;
     HIP_TRY(this, hipSetDevice(device));
-    if (ensure(col_S, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, ncol * M) || ensure(col_nused, ncol) ||
-        ensure(col_chi2, ncol) || ensure(col_flag, ncol) || ensure(col_lat, ws_bytes / sizeof(double))) return status;
-    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
-    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
-    // (the outer ring of columns reports zeros: the kernels run on the interior)
-    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, ncol * M * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, ncol * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
-    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, col_S.p, stream);
-    launch_lateral_setup(disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, lateral, tol, col_lat.p, vels_d.p, col_nused.p,
-                         col_chi2.p, col_flag.p, stream);
-    launch_lateral_first(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, tol, maxit, stream);
-    HIP_TRY(this, hipGetLastError());
-    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
-    const int* d_ints = column_lateral_ints(col_lat.p, disp_nx, disp_ny, disp_nz);
-    for (int it = 1; lateral > 0.0f && it <= maxit; ++it) {
-        launch_lateral_iteration(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, tol, maxit, stream);
-        if (it % lateral_poll == 0 && it < maxit) {
-            HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(this, hipStreamSynchronize(stream));
-            if (ints[1]) break;
-        }
-    }
-    launch_lateral_finish(disp_nx, disp_ny, disp_nz, lateral, col_lat.p, dvmax, minvel, maxvel, vels_d.p, col_dv.p, stream);
-    HIP_TRY(this, hipGetLastError());
-    for (DispMark& m : disp_map_mark) m.fresh = false;
-    for (DispMark& m : disp_slot_mark) m.fresh = false;
-    h_vels.resize(ncol * disp_nz);
-    double rz[2] = { 0.0, 0.0 };          // the last rz, rz0
-    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(rz, column_lateral_scalars(col_lat.p, disp_nx, disp_ny, disp_nz), sizeof rz, hipMemcpyDeviceToHost, stream));
-    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, ncol * M * 4, hipMemcpyDeviceToHost, stream));
-    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
-    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, ncol * 8, hipMemcpyDeviceToHost, stream));
-    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipStreamSynchronize(stream));
-    if (info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
-    return 0;
+    if (int rc = columns_stage_in(1, obs, wt, true)) return rc;
+    if (ensure(col_lat, coupled_ws_bytes(1, disp_nx, disp_ny, disp_nz) / sizeof(double))) return status;
+    const CoupledSystem s = { 1, disp_nx, disp_ny, disp_nz, lateral, 0.0f, col_lat.p };
+    launch_lateral_setup(s, disp_nmaps, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, tol, vels_d.p, col_nused.p, col_chi2.p, col_flag.p, stream);
+    if (int rc = columns_coupled_loop(s, tol, maxit, dvmax, minvel, maxvel)) return rc;
+    return columns_stage_out(1, dv, nused, chi2, flag, &s, info);
 }
 
 // dsa_columns_step_radial_lateral: dsa_columns_step_radial with the interior columns tied to their neighbours,
 // column_radial_lateral.h's system in column_lateral.h's conjugate gradients.  The state and argument rules are columns_step_radial's, then
-// lateral, lateral_aniso, tol, maxit and the size of the workspace against dsa_set_memory_budget (as columns_step_lateral holds its own);
-// everything is checked before the device is touched, except the LDS of the set-up kernel (DSA_ERR_DEVICE before anything is launched).  The
-// loop is columns_step_lateral's: bounded by maxit, the done flag looked at every lateral_poll iterations, which cannot change a bit.
+// columns_coupled_front's; everything is checked before the device is touched, except the LDS of the set-up kernel (DSA_ERR_DEVICE before
+// anything is launched).
 int Engine::columns_step_radial_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral, float lateral_aniso,
                                         float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info)
 {
-    if (int rc = columns_front("columns_step_radial_lateral", nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
-    if (!std::isfinite(aniso) || aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: aniso %g must be finite and >= 0", (double)aniso); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(lateral) || lateral < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: lateral %g must be finite and >= 0", (double)lateral); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(lateral_aniso) || lateral_aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: lateral_aniso %g must be finite and >= 0", (double)lateral_aniso); return DSA_ERR_ARGUMENT; }
-    if (!std::isfinite(tol) || tol <= 0.0) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: tol %g must be finite and > 0", tol); return DSA_ERR_ARGUMENT; }
-    if (maxit < 1) { fail(DSA_ERR_ARGUMENT, "columns_step_radial_lateral: maxit %d must be at least 1", maxit); return DSA_ERR_ARGUMENT; }
-    const int K = disp_nmaps, M = disp_nz - 1;
-    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
-    const size_t ws_bytes = column_radial_lateral_ws_bytes(disp_nx, disp_ny, disp_nz);
-    if (mem_budget && ws_bytes > mem_budget) {
-        fail(DSA_ERR_CAPACITY, "columns_step_radial_lateral: the workspace of %d x %d columns of %d unknowns needs %zu bytes, the memory budget is %zu", disp_nx - 2, disp_ny - 2, 2 * M, ws_bytes, mem_budget);
-        return DSA_ERR_CAPACITY;
-    }
-    const bool edges = lateral > 0.0f || lateral_aniso > 0.0f;
-    unsigned long long love = 0ull;
-    for (int k = 0; k < K; ++k) if (disp_slot_mark[(size_t)k].iwave == 1) love |= 1ull << k;
+    const char* who = "columns_step_radial_lateral";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, true, dvmax, minvel, maxvel, true)) return rc;
+    if (int rc = columns_weight(who, "aniso", aniso)) return rc;
+    if (int rc = columns_coupled_front(who, 2, lateral, lateral_aniso, tol, maxit)) return rc;
     HIP_TRY(this, hipSetDevice(device));
-    if (ensure(col_S, ncol * K * M) || ensure(col_Sh, ncol * K * M) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(col_dv, 2 * ncol * M) ||
-        ensure(col_nused, 2 * ncol) || ensure(col_chi2, 2 * ncol) || ensure(col_flag, ncol) || ensure(col_rlat, ws_bytes / sizeof(double))) return status;
-    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
-    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
-    // (the outer ring of columns reports zeros: the kernels run on the interior)
-    HIP_TRY(this, hipMemsetAsync(col_dv.p, 0, 2 * ncol * M * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, 2 * ncol * 4, stream));
-    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, 2 * ncol * 8, stream));
-    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
-    const int shallow = h_depz[disp_nz - 2] < 35.0f ? 1 : 0;
-    launch_sen_combine((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_S.p, stream);
-    launch_sen_combine((int)ncol, K, disp_nz, vsh_d.p, sen_vs.p, sen_vp.p, sen_rho.p, shallow, col_Sh.p, stream);
+    if (int rc = columns_stage_in(2, obs, wt, true)) return rc;
+    if (ensure(col_lat, coupled_ws_bytes(2, disp_nx, disp_ny, disp_nz) / sizeof(double))) return status;
+    const CoupledSystem s = { 2, disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_lat.p };
     int limit = 0;
-    const int rc = launch_radial_lateral_setup(device, disp_nx, disp_ny, disp_nz, K, love, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p, smooth, damp,
-                                               aniso, lateral, lateral_aniso, tol, col_rlat.p, vels_d.p, vsh_d.p, col_nused.p, col_chi2.p, col_flag.p, stream, &limit);
-    if (rc) {
-        HIP_TRY(this, hipStreamSynchronize(stream));
-        if (rc == 1) fail(DSA_ERR_DEVICE, "columns_step_radial_lateral: a column of %d unknowns and %d data needs %zu bytes of LDS, a block of this device may have %d", 2 * M, K, column_radial_lds_bytes(disp_nz, K), limit);
-        else fail(DSA_ERR_DEVICE, "columns_step_radial_lateral: the device refuses %zu bytes of dynamic LDS per workgroup", column_radial_lds_bytes(disp_nz, K));
-        return DSA_ERR_DEVICE;
-    }
-    launch_radial_lateral_first(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, tol, maxit, stream);
-    HIP_TRY(this, hipGetLastError());
-    int ints[3] = { 0, 0, 0 };          // the iteration count, the done flag, the stop code
-    const int* d_ints = column_radial_lateral_ints(col_rlat.p, disp_nx, disp_ny, disp_nz);
-    for (int it = 1; edges && it <= maxit; ++it) {
-        launch_radial_lateral_iteration(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, tol, maxit, stream);
-        if (it % lateral_poll == 0 && it < maxit) {
-            HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(this, hipStreamSynchronize(stream));
-            if (ints[1]) break;
-        }
-    }
-    launch_radial_lateral_finish(disp_nx, disp_ny, disp_nz, lateral, lateral_aniso, col_rlat.p, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, col_dv.p, stream);
-    HIP_TRY(this, hipGetLastError());
-    for (DispMark& m : disp_map_mark) m.fresh = false;
-    for (DispMark& m : disp_slot_mark) m.fresh = false;
-    h_vels.resize(ncol * disp_nz);
-    h_vsh.resize(ncol * disp_nz);
-    double rz[2] = { 0.0, 0.0 };          // the last rz, rz0
-    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, h_vsh.size() * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(ints, d_ints, sizeof ints, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipMemcpyAsync(rz, column_radial_lateral_scalars(col_rlat.p, disp_nx, disp_ny, disp_nz), sizeof rz, hipMemcpyDeviceToHost, stream));
-    if (dv) HIP_TRY(this, hipMemcpyAsync(dv, col_dv.p, 2 * ncol * M * 4, hipMemcpyDeviceToHost, stream));
-    if (nused) HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, 2 * ncol * 4, hipMemcpyDeviceToHost, stream));
-    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi2.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
-    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(this, hipStreamSynchronize(stream));
-    if (info) { info[0] = (double)ints[0]; info[1] = (double)ints[2]; info[2] = rz[1]; info[3] = rz[0]; }
-    return 0;
+    const int rc = launch_radial_lateral_setup(device, s, disp_nmaps, columns_love(), col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p, smooth, damp, aniso,
+                                               tol, vels_d.p, vsh_d.p, col_nused.p, col_chi2.p, col_flag.p, stream, &limit);
+    if (rc) return columns_lds_refusal(who, rc, 2 * (disp_nz - 1), column_radial_lds_bytes(disp_nz, disp_nmaps), limit);
+    if (int rc = columns_coupled_loop(s, tol, maxit, dvmax, minvel, maxvel)) return rc;
+    return columns_stage_out(2, dv, nused, chi2, flag, &s, info);
 }
 
 int Engine::maps_from_dispersion(float goxd, float gozd, float dvxd, float dvzd, int dicing)

@@ -317,38 +317,33 @@ int launch_column_resolution(int device, int nx, int ny, int nz, int K, const fl
 // The radially anisotropic step: the interior columns of the two (nz, ny, nx) models d_vsv and d_vsh in place.  love: bit k
 // set where slot k is a Love slot; d_Sv / d_Sh: launch_sen_combine's on the Vsv and on the Vsh model; d_dv: (2, nz - 1, ncol), the Vsv block then
 // the Vsh block; d_nused / d_chi2: (2, ncol), Rayleigh then Love; d_flag: (ncol).  Only interior columns are written.  The return values and
-// *limit_out are launch_column_resolution's; column_radial_lds_bytes: the dynamic LDS of a block.
+// *limit_out are launch_column_resolution's (one rule, column_kernels.hip: column_lds_opt_in); column_radial_lds_bytes: the dynamic LDS of a block.
 size_t column_radial_lds_bytes(int nz, int K);
 int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
                               const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
                               float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
-// The laterally coupled step (column_lateral.h).  d_ws: column_lateral_ws_bytes bytes.  launch_lateral_setup: assemble and
-// factor every interior column, the right-hand side, x0 and rz0 (three launches); launch_lateral_first: the first residual and the criterion
-// at iteration 0; launch_lateral_iteration: one iteration, four launches that do nothing once the done flag is set; launch_lateral_finish:
-// the clipped steps to d_dv (nz - 1, ncol) and the stepped model.  column_lateral_ints: the device address of the iteration count, the done
-// flag and the stop code (3 ints); column_lateral_scalars: of rz, rz0 (the first two doubles).
-size_t column_lateral_ws_bytes(int nx, int ny, int nz);
-void launch_lateral_setup(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
-                          float lateral, double tol, double* d_ws, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
-void launch_lateral_first(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream);
-void launch_lateral_iteration(int nx, int ny, int nz, float lateral, double* d_ws, double tol, int maxit, hipStream_t stream);
-void launch_lateral_finish(int nx, int ny, int nz, float lateral, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vels, float* d_dv, hipStream_t stream);
-const int* column_lateral_ints(double* d_ws, int nx, int ny, int nz);
-const double* column_lateral_scalars(double* d_ws, int nx, int ny, int nz);
-// The laterally coupled radial step (column_radial_lateral.h): the launches above on the two models, 2 (nz - 1) unknowns
-// per column.  d_ws: column_radial_lateral_ws_bytes bytes; love, d_Sv / d_Sh, d_nused / d_chi2 (2, ncol), d_dv (2, nz - 1, ncol) as
-// launch_column_step_radial's.  launch_radial_lateral_setup returns launch_column_step_radial's values (*limit_out always set): 1 or 2 before
-// anything is launched.  The iteration runs k_lateral_update and k_lateral_reduce on the workspace as they are.
-size_t column_radial_lateral_ws_bytes(int nx, int ny, int nz);
-int launch_radial_lateral_setup(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
-                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float lateral, float lateral_aniso, double tol,
-                                double* d_ws, const float* d_vsv, const float* d_vsh, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
-void launch_radial_lateral_first(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream);
-void launch_radial_lateral_iteration(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, double tol, int maxit, hipStream_t stream);
-void launch_radial_lateral_finish(int nx, int ny, int nz, float lateral, float lateral_aniso, double* d_ws, float dvmax, float minvel, float maxvel, float* d_vsv,
-                                  float* d_vsh, float* d_dv, hipStream_t stream);
-const int* column_radial_lateral_ints(double* d_ws, int nx, int ny, int nz);
-const double* column_radial_lateral_scalars(double* d_ws, int nx, int ny, int nz);
+// The laterally coupled steps (DESIGN.md sections 24 and 25): column_lateral.h's conjugate gradients on a system of blocks = 1 model
+// (column_lateral.h's own; lateral_aniso is not read) or blocks = 2 models (column_radial_lateral.h's, 2 (nz - 1) unknowns per column).
+// d_ws: coupled_ws_bytes bytes.  coupled_edges: whether the columns are coupled at all (else the loop stops at iteration 0).  coupled_ints: the
+// device address of the iteration count, the done flag and the stop code (3 ints); coupled_scalars: of rz, rz0 (the first two doubles).
+struct CoupledSystem { int blocks, nx, ny, nz; float lateral, lateral_aniso; double* d_ws; };
+size_t coupled_ws_bytes(int blocks, int nx, int ny, int nz);
+bool coupled_edges(const CoupledSystem& s);
+const int* coupled_ints(const CoupledSystem& s);
+const double* coupled_scalars(const CoupledSystem& s);
+// The set-up of each system: assemble and factor every interior column, the right-hand side, x0 and rz0 (three launches).  The arrays are
+// launch_column_step's, and launch_column_step_radial's with its return values and *limit_out: 1 or 2 before anything is launched.
+void launch_lateral_setup(const CoupledSystem& s, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                          double tol, const float* d_vels, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
+int launch_radial_lateral_setup(int device, const CoupledSystem& s, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, double tol, const float* d_vsv, const float* d_vsh,
+                                int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
+// The loop of either system.  launch_coupled_first: the first residual and the criterion at iteration 0 (two launches);
+// launch_coupled_iteration: one iteration, four launches that do nothing once the done flag is set; launch_coupled_finish: the clipped steps
+// to d_dv (blocks, nz - 1, ncol) and the stepped model(s) (d_vels1: the second model, null for one block).
+void launch_coupled_first(const CoupledSystem& s, double tol, int maxit, hipStream_t stream);
+void launch_coupled_iteration(const CoupledSystem& s, double tol, int maxit, hipStream_t stream);
+void launch_coupled_finish(const CoupledSystem& s, float dvmax, float minvel, float maxvel, float* d_vels0, float* d_vels1, float* d_dv, hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

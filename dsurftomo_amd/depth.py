@@ -154,6 +154,56 @@ def _twin_solve(Lm, d, b):
     return x.reshape(b.shape)
 
 
+def _twin_data(obs, wt, pv, S, love=None):
+    """The data of one column, as every twin reads them: obs, wt (K) fp32, pv (K) fp64, S (K, M) fp64.  Returns (used, rho (K), chi2, G (K, M)):
+    a datum is used where its weight, its observation and its curve are positive; rho = a (obs - pv), 0 where unused; chi2 the sum of rho^2
+    over the used k ascending from 0.0 -- two sums [Rayleigh, Love] by love (K) bool where one is given; G = diag(a) S on the used rows (the
+    S of an unused datum is never read: it may not be finite)."""
+    used = (wt > 0) & (obs > 0) & (pv > 0)
+    a = wt.astype(np.float64)
+    rho = np.where(used, a * (obs.astype(np.float64) - pv), 0.0)
+    chi2 = [0.0, 0.0]
+    for k in np.flatnonzero(used):
+        q = 0 if love is None else int(love[k])
+        chi2[q] = chi2[q] + rho[k] * rho[k]
+    G = np.zeros(S.shape)
+    G[used] = a[used, None] * S[used]
+    return used, rho, chi2[0] if love is None else chi2, G
+
+
+def _twin_radial_normal(G, used, love, rho, lam2, mu2, gam2, d):
+    """column_radial.h's radial_assemble: the 2M x 2M matrix of the unknowns [dVsv ; dVsh] -- _twin_normal of the Rayleigh and of the Love data
+    on the diagonal, each with gam2 added to its diagonal, -gam2 I beside them -- and b = [b_v + gam2 d ; b_h - gam2 d], d = vsh - vsv (M)"""
+    M = G.shape[1]
+    N = np.zeros((2 * M, 2 * M)); b = np.zeros(2 * M)
+    for q, sel in enumerate((used & ~love, used & love)):
+        Nq, bq = _twin_normal(G, sel, rho, lam2, mu2)
+        Nq[np.diag_indices(M)] = Nq[np.diag_indices(M)] + gam2
+        N[q * M:(q + 1) * M, q * M:(q + 1) * M] = Nq
+        t = gam2 * d
+        b[q * M:(q + 1) * M] = bq - t if q else bq + t
+    N[M:, :M][np.diag_indices(M)] = 0.0 - gam2
+    N[:M, M:] = N[M:, :M].T
+    return N, b
+
+
+def _twin_clip(delta, dvmax):
+    """column_clip: the step in fp32, clipped to +- dvmax (a NaN stays)"""
+    s = np.asarray(delta).astype(np.float32)
+    dvmax = np.float32(dvmax)
+    with np.errstate(invalid="ignore"):
+        s = np.where(s >= dvmax, dvmax, s)
+        return np.where(s <= -dvmax, -dvmax, s).astype(np.float32)
+
+
+def _twin_stepped(vel, s, minvel, maxvel):
+    """column_stepped: vel + s in fp32, clipped to [minvel, maxvel]"""
+    with np.errstate(invalid="ignore"):
+        v = (vel + s).astype(np.float32)
+        v = np.where(v < np.float32(minvel), np.float32(minvel), v)
+        return np.where(v > np.float32(maxvel), np.float32(maxvel), v)
+
+
 def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, solver="ldlt", n_override=None):
     """dsa_columns_step on one column in NumPy.  obs (K) fp32, wt (K) fp32 or None, pv (K) fp64, S (K, M) fp64 (k_sen_combine's d c / d Vs),
     vels (M or more) fp32: the column's values from the top; only the first M are stepped.  The sums run in column_system.h's order (k
@@ -166,19 +216,11 @@ def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, 
     K, M = S.shape
     wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
     vels = np.array(vels, f, copy=True)
-    used = (wt > 0) & (obs > 0) & (pv > 0)
-    a = wt.astype(np.float64)
-    rho = np.where(used, a * (obs.astype(np.float64) - pv), 0.0)
-    out = dict(delta=np.zeros(M), dv=np.zeros(M, f), vels=vels, nused=int(used.sum()), chi2=0.0, flag=0)
-    chi2 = 0.0
-    for k in np.flatnonzero(used):
-        chi2 = chi2 + rho[k] * rho[k]
-    out["chi2"] = float(chi2)
+    used, rho, chi2, G = _twin_data(obs, wt, pv, S)
+    out = dict(delta=np.zeros(M), dv=np.zeros(M, f), vels=vels, nused=int(used.sum()), chi2=float(chi2), flag=0)
     if out["nused"] == 0:
         out["flag"] = 2
         return out
-    G = np.zeros((K, M))
-    G[used] = a[used, None] * S[used]                                  # (the S of an unused datum is never read: it may not be finite)
     lam2, mu2 = float(f(smooth)) * float(f(smooth)), float(f(damp)) * float(f(damp))
     if solver == "lstsq":
         A = np.vstack([G[used], float(f(smooth)) * column_l(M), float(f(damp)) * np.eye(M)])
@@ -193,16 +235,9 @@ def column_step_twin(obs, wt, pv, S, vels, smooth, damp, dvmax, minvel, maxvel, 
             out["flag"] = 1
             return out
         delta = _twin_solve(*factor, b)
-    s = delta.astype(f)
-    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
-    with np.errstate(invalid="ignore"):
-        s = np.where(s >= dvmax, dvmax, s)
-        s = np.where(s <= -dvmax, -dvmax, s)
-        v = (vels[:M] + s).astype(f)
-        v = np.where(v < minvel, minvel, v)
-        v = np.where(v > maxvel, maxvel, v)
-    vels[:M] = v
-    out.update(delta=delta, dv=s.astype(f))
+    s = _twin_clip(delta, dvmax)
+    vels[:M] = _twin_stepped(vels[:M], s, minvel, maxvel)
+    out.update(delta=delta, dv=s)
     return out
 
 
@@ -219,21 +254,13 @@ def column_radial_twin(obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, dvma
     K, M = S.shape
     wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
     vsv = np.array(vsv, f, copy=True); vsh = np.array(vsh, f, copy=True)
-    used = (wt > 0) & (obs > 0) & (pv > 0)
-    a = wt.astype(np.float64)
-    rho = np.where(used, a * (obs.astype(np.float64) - pv), 0.0)
-    chi2 = [0.0, 0.0]
-    for k in np.flatnonzero(used):
-        chi2[int(love[k])] = chi2[int(love[k])] + rho[k] * rho[k]
+    used, rho, chi2, G = _twin_data(obs, wt, pv, S, love)
     out = dict(delta=np.zeros(2 * M), dv_sv=np.zeros(M, f), dv_sh=np.zeros(M, f), vsv=vsv, vsh=vsh, nused=[int((used & ~love).sum()), int((used & love).sum())],
                chi2=[float(chi2[0]), float(chi2[1])], flag=0)
     if not used.any():
         out["flag"] = 2
         return out
-    G = np.zeros((K, M))
-    G[used] = a[used, None] * S[used]
     lam, mu, gam = float(f(smooth)), float(f(damp)), float(f(aniso))
-    lam2, mu2, gam2 = lam * lam, mu * mu, gam * gam
     d = vsh[:M].astype(np.float64) - vsv[:M].astype(np.float64)
     if solver == "lstsq":
         nu = int(used.sum())
@@ -244,15 +271,7 @@ def column_radial_twin(obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, dvma
         rhs = np.concatenate([rho[used], np.zeros(2 * Lm.shape[0] + 2 * M), -gam * d])
         delta = np.linalg.lstsq(A, rhs, rcond=None)[0]
     else:
-        N = np.zeros((2 * M, 2 * M)); b = np.zeros(2 * M)
-        for q, sel in enumerate((used & ~love, used & love)):
-            Nq, bq = _twin_normal(G, sel, rho, lam2, mu2)
-            Nq[np.diag_indices(M)] = Nq[np.diag_indices(M)] + gam2
-            N[q * M:(q + 1) * M, q * M:(q + 1) * M] = Nq
-            t = gam2 * d
-            b[q * M:(q + 1) * M] = bq - t if q else bq + t
-        N[M:, :M][np.diag_indices(M)] = 0.0 - gam2
-        N[:M, M:] = N[M:, :M].T
+        N, b = _twin_radial_normal(G, used, love, rho, lam * lam, mu * mu, gam * gam, d)
         if n_override is not None:
             N = np.array(n_override, np.float64)
         factor = _twin_factor(N)
@@ -260,15 +279,9 @@ def column_radial_twin(obs, wt, pv, S, love, vsv, vsh, smooth, damp, aniso, dvma
             out["flag"] = 1
             return out
         delta = _twin_solve(*factor, b)
-    s = delta.astype(f)
-    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
-    with np.errstate(invalid="ignore"):
-        s = np.where(s >= dvmax, dvmax, s)
-        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
-        for vel, part in ((vsv, s[:M]), (vsh, s[M:])):
-            v = (vel[:M] + part).astype(f)
-            v = np.where(v < minvel, minvel, v)
-            vel[:M] = np.where(v > maxvel, maxvel, v)
+    s = _twin_clip(delta, dvmax)
+    vsv[:M] = _twin_stepped(vsv[:M], s[:M], minvel, maxvel)
+    vsh[:M] = _twin_stepped(vsh[:M], s[M:], minvel, maxvel)
     out.update(delta=delta, dv_sv=s[:M].copy(), dv_sh=s[M:].copy())
     return out
 
@@ -282,6 +295,68 @@ def lateral_sum(part):
             c = c + float(v)
         total = total + c
     return total
+
+
+def _twin_pcg(col, interior, bt, apply, coupled, tol, maxit):
+    """column_lateral.h's preconditioned conjugate gradients in its order.  col: {column: dict with "factor"} of the active columns; interior:
+    all interior columns in their order (the dots' figures lie in it, 0.0 where not active, then lateral_sum); bt: {column: right-hand
+    side}; apply(y) -> {column: (A y)_c}; coupled: False stops at iteration 0 whatever rz is.  Returns (x, itn, istop, rz0, rz)."""
+    solve = lambda r: {c: _twin_solve(*col[c]["factor"], r[c]) for c in col}
+    dot = lambda u, w: lateral_sum([_chain_dot(u[c], w[c]) if c in col else 0.0 for c in interior])
+    x = solve(bt)
+    rz0 = dot(bt, x)
+    thr = (float(tol) * float(tol)) * rz0
+    q = apply(x)
+    r = {c: bt[c] - q[c] for c in col}
+    z = solve(r)
+    rz = dot(r, z)
+    itn, istop = 0, 0
+    if not coupled or rz <= thr:
+        istop = 1
+    p_old = {c: np.zeros(len(bt[c])) for c in col}
+    beta = 0.0
+    while not istop:
+        p = {c: z[c] + beta * p_old[c] for c in col}
+        q = apply(p)
+        alpha = rz / dot(p, q)
+        x = {c: x[c] + alpha * p[c] for c in col}
+        r = {c: r[c] - alpha * q[c] for c in col}
+        z = solve(r)
+        new = dot(r, z)
+        beta = new / rz
+        rz = new
+        p_old = p
+        itn += 1
+        if rz <= thr:
+            istop = 1
+        elif itn >= maxit:
+            istop = 2
+    return x, itn, istop, float(rz0), float(rz)
+
+
+def _twin_stacked(col, edges, B, own, between):
+    """The other answer of a coupled twin: numpy.linalg.lstsq on the stacked system of the active columns col, B unknowns each.  own(c) ->
+    [(block (rows, B), right-hand side)] of column c alone; between(c, n) -> [(block (rows, B), right-hand side)] of the edge c < n, the
+    block applied to c and, negated, to n.  Returns {column: solution (B)}."""
+    index = {c: q * B for q, c in enumerate(col)}
+    rows, rhs = [], []
+
+    def put(parts, right):
+        full = np.zeros((len(right), len(col) * B))
+        for c, block in parts:
+            full[:, index[c]:index[c] + B] = block
+        rows.append(full); rhs.append(right)
+
+    for c in col:
+        for block, right in own(c):
+            put([(c, block)], right)
+    for c in col:
+        for n in edges[c]:
+            if n > c:
+                for block, right in between(c, n):
+                    put([(c, block), (n, -block)], right)
+    sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
+    return {c: sol[index[c]:index[c] + B] for c in col}
 
 
 def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
@@ -306,18 +381,11 @@ def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvm
     interior = [j * nx + i for j in range(1, ny - 1) for i in range(1, nx - 1)]
     col = {}                                                            # the active columns: G, used, rho, N, factor, b
     for c in interior:
-        used = (wt[:, c] > 0) & (obs[:, c] > 0) & (pv[:, c] > 0)
-        a = wt[:, c].astype(np.float64)
-        rho = np.where(used, a * (obs[:, c].astype(np.float64) - pv[:, c]), 0.0)
-        chi2 = 0.0
-        for k in np.flatnonzero(used):
-            chi2 = chi2 + rho[k] * rho[k]
+        used, rho, chi2, G = _twin_data(obs[:, c], wt[:, c], pv[:, c], S[:, :, c].T)
         out["nused"][c] = int(used.sum()); out["chi2"][c] = chi2
         if not used.any() and lat == 0.0:
             out["flag"][c] = 2
             continue
-        G = np.zeros((K, M))
-        G[used] = a[used, None] * S[:, used, c].T
         N, b = _twin_normal(G, used, rho, lam2, mu2)
         factor = _twin_factor(N)
         if factor is None:
@@ -328,8 +396,6 @@ def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvm
     for c in col:
         out["deg"][c] = len(edges[c])
     v64 = vels[:M].astype(np.float64)
-    order = [c for c in interior]                                       # the dots' figures lie in interior-column order, 0.0 where not active
-    dot = lambda u, w: lateral_sum([_chain_dot(u[c], w[c]) if c in col else 0.0 for c in order])
 
     def apply(y):
         q = {}
@@ -343,75 +409,23 @@ def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvm
             q[c] = t + lat2 * (float(len(edges[c])) * y[c] - s)
         return q
 
-    solve = lambda r: {c: _twin_solve(*col[c]["factor"], r[c]) for c in col}
     bt = {}
     for c, d in col.items():
         s = np.zeros(M)
         for n in edges[c]:
             s = s + (v64[:, c] - v64[:, n])
         bt[c] = d["b"] - lat2 * s if lat > 0.0 else d["b"].copy()
-    x = solve(bt)
-    rz0 = dot(bt, x)
-    thr = (float(tol) * float(tol)) * rz0
-    q = apply(x)
-    r = {c: bt[c] - q[c] for c in col}
-    z = solve(r)
-    rz = dot(r, z)
-    itn, istop = 0, 0
-    if lat == 0.0 or rz <= thr:
-        istop = 1
-    p_old = {c: np.zeros(M) for c in col}
-    beta = 0.0
-    while not istop:
-        p = {c: z[c] + beta * p_old[c] for c in col}
-        q = apply(p)
-        alpha = rz / dot(p, q)
-        x = {c: x[c] + alpha * p[c] for c in col}
-        r = {c: r[c] - alpha * q[c] for c in col}
-        z = solve(r)
-        new = dot(r, z)
-        beta = new / rz
-        rz = new
-        p_old = p
-        itn += 1
-        if rz <= thr:
-            istop = 1
-        elif itn >= maxit:
-            istop = 2
-    out.update(itn=itn, istop=istop, rz0=float(rz0), rz=float(rz))
+    x, out["itn"], out["istop"], out["rz0"], out["rz"] = _twin_pcg(col, interior, bt, apply, lat > 0.0, tol, maxit)
+    if col:
+        Lm = column_l(M)
+        own = lambda c: [(col[c]["G"][col[c]["used"]], col[c]["rho"][col[c]["used"]]), (lam * Lm, np.zeros(Lm.shape[0])), (mu * np.eye(M), np.zeros(M))]
+        other = _twin_stacked(col, edges, M, own, lambda c, n: [(lat * np.eye(M), -lat * (v64[:, c] - v64[:, n]))])
     for c in col:
         out["delta"][:, c] = x[c]
-    # the other answer
-    if col:
-        index = {c: q for q, c in enumerate(col)}
-        rows, rhs = [], []
-        Lm = column_l(M)
-        for c, d in col.items():
-            o = index[c] * M
-            for block, right in ((d["G"][d["used"]], d["rho"][d["used"]]), (lam * Lm, np.zeros(Lm.shape[0])), (mu * np.eye(M), np.zeros(M))):
-                full = np.zeros((block.shape[0], len(col) * M))
-                full[:, o:o + M] = block
-                rows.append(full); rhs.append(right)
-        for c in col:
-            for n in edges[c]:
-                if n > c:
-                    full = np.zeros((M, len(col) * M))
-                    full[:, index[c] * M:index[c] * M + M] = lat * np.eye(M)
-                    full[:, index[n] * M:index[n] * M + M] = -lat * np.eye(M)
-                    rows.append(full); rhs.append(-lat * (v64[:, c] - v64[:, n]))
-        sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
-        for c in col:
-            out["delta_lstsq"][:, c] = sol[index[c] * M:index[c] * M + M]
-    s = out["delta"].astype(f)
-    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
-    with np.errstate(invalid="ignore"):
-        s = np.where(s >= dvmax, dvmax, s)
-        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
-        for c in col:
-            v = (vels[:M, c] + s[:, c]).astype(f)
-            v = np.where(v < minvel, minvel, v)
-            vels[:M, c] = np.where(v > maxvel, maxvel, v)
-    out["dv"] = s
+        out["delta_lstsq"][:, c] = other[c]
+    out["dv"] = _twin_clip(out["delta"], dvmax)
+    for c in col:
+        vels[:M, c] = _twin_stepped(vels[:M, c], out["dv"][:, c], minvel, maxvel)
     return out
 
 
@@ -434,7 +448,7 @@ def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, d
     wt = np.ones((K, ncol), f) if wt is None else np.asarray(wt, f)
     vsv = np.array(vsv, f, copy=True); vsh = np.array(vsh, f, copy=True)
     lam, mu, gam, lat, lata = float(f(smooth)), float(f(damp)), float(f(aniso)), float(f(lateral)), float(f(lateral_aniso))
-    lam2, mu2, gam2, w2, wa2 = lam * lam, mu * mu, gam * gam, lat * lat, lata * lata
+    w2, wa2 = lat * lat, lata * lata
     with_edges = lat > 0.0 or lata > 0.0
     out = dict(delta=np.zeros((B, ncol)), delta_lstsq=np.zeros((B, ncol)), dv=np.zeros((2, M, ncol), f), vsv=vsv, vsh=vsh, nused=np.zeros((2, ncol), np.int32),
                chi2=np.zeros((2, ncol)), flag=np.zeros(ncol, np.int32), deg=np.zeros(ncol, np.int32), itn=0, istop=0, rz0=0.0, rz=0.0)
@@ -443,27 +457,12 @@ def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, d
     a64 = h64 - v64
     col = {}                                                            # the active columns: G, used, rho, N, factor, b
     for c in interior:
-        used = (wt[:, c] > 0) & (obs[:, c] > 0) & (pv[:, c] > 0)
-        a = wt[:, c].astype(np.float64)
-        rho = np.where(used, a * (obs[:, c].astype(np.float64) - pv[:, c]), 0.0)
-        chi2 = [0.0, 0.0]
-        for k in np.flatnonzero(used):
-            chi2[int(love[k])] = chi2[int(love[k])] + rho[k] * rho[k]
+        used, rho, chi2, G = _twin_data(obs[:, c], wt[:, c], pv[:, c], S[:, :, c].T, love)
         out["nused"][:, c] = [int((used & ~love).sum()), int((used & love).sum())]; out["chi2"][:, c] = chi2
         if not used.any() and not with_edges:
             out["flag"][c] = 2
             continue
-        G = np.zeros((K, M))
-        G[used] = a[used, None] * S[:, used, c].T
-        N = np.zeros((B, B)); b = np.zeros(B)
-        for q, sel in enumerate((used & ~love, used & love)):
-            Nq, bq = _twin_normal(G, sel, rho, lam2, mu2)
-            Nq[np.diag_indices(M)] = Nq[np.diag_indices(M)] + gam2
-            N[q * M:(q + 1) * M, q * M:(q + 1) * M] = Nq
-            t = gam2 * a64[:, c]
-            b[q * M:(q + 1) * M] = bq - t if q else bq + t
-        N[M:, :M][np.diag_indices(M)] = 0.0 - gam2
-        N[:M, M:] = N[M:, :M].T
+        N, b = _twin_radial_normal(G, used, love, rho, lam * lam, mu * mu, gam * gam, a64[:, c])
         factor = _twin_factor(N)
         if factor is None:
             out["flag"][c] = 1
@@ -472,7 +471,6 @@ def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, d
     edges = {c: [n for n in (c - 1, c + 1, c - nx, c + nx) if n in col] if with_edges else [] for c in col}
     for c in col:
         out["deg"][c] = len(edges[c])
-    dot = lambda u, w: lateral_sum([_chain_dot(u[c], w[c]) if c in col else 0.0 for c in interior])
 
     def apply(y):
         q = {}
@@ -490,7 +488,6 @@ def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, d
             q[c] = np.concatenate([fig[:M] - g, fig[M:] + g])
         return q
 
-    solve = lambda r: {c: _twin_solve(*col[c]["factor"], r[c]) for c in col}
     bt = {}
     for c, d in col.items():
         sv = np.zeros(M); sh = np.zeros(M); sa = np.zeros(M)
@@ -499,80 +496,27 @@ def column_radial_lateral_twin(nx, ny, obs, wt, pv, S, love, vsv, vsh, smooth, d
             sh = sh + (h64[:, c] - h64[:, n])
             sa = sa + (a64[:, c] - a64[:, n])
         bt[c] = np.concatenate([(d["b"][:M] - w2 * sv) + wa2 * sa, (d["b"][M:] - w2 * sh) - wa2 * sa]) if with_edges else d["b"].copy()
-    x = solve(bt)
-    rz0 = dot(bt, x)
-    thr = (float(tol) * float(tol)) * rz0
-    q = apply(x)
-    r = {c: bt[c] - q[c] for c in col}
-    z = solve(r)
-    rz = dot(r, z)
-    itn, istop = 0, 0
-    if not with_edges or rz <= thr:
-        istop = 1
-    p_old = {c: np.zeros(B) for c in col}
-    beta = 0.0
-    while not istop:
-        p = {c: z[c] + beta * p_old[c] for c in col}
-        q = apply(p)
-        alpha = rz / dot(p, q)
-        x = {c: x[c] + alpha * p[c] for c in col}
-        r = {c: r[c] - alpha * q[c] for c in col}
-        z = solve(r)
-        new = dot(r, z)
-        beta = new / rz
-        rz = new
-        p_old = p
-        itn += 1
-        if rz <= thr:
-            istop = 1
-        elif itn >= maxit:
-            istop = 2
-    out.update(itn=itn, istop=istop, rz0=float(rz0), rz=float(rz))
-    for c in col:
-        out["delta"][:, c] = x[c]
-    # the other answer
+    x, out["itn"], out["istop"], out["rz0"], out["rz"] = _twin_pcg(col, interior, bt, apply, with_edges, tol, maxit)
     if col:
-        index = {c: q for q, c in enumerate(col)}
-        width = len(col) * B
-        rows, rhs = [], []
         Lm = column_l(M); Z = np.zeros_like(Lm); I = np.eye(M)
 
-        def put(c, block, right):
-            full = np.zeros((block.shape[0], width))
-            full[:, index[c] * B:index[c] * B + B] = block
-            rows.append(full); rhs.append(right)
-
-        for c, d in col.items():
-            u = d["used"]
+        def own(c):
+            u = col[c]["used"]
             Gc = np.zeros((int(u.sum()), B))
-            Gc[:, :M] = np.where(love[u, None], 0.0, d["G"][u]); Gc[:, M:] = np.where(love[u, None], d["G"][u], 0.0)
-            put(c, Gc, d["rho"][u])
-            put(c, lam * np.hstack([Lm, Z]), np.zeros(Lm.shape[0]))
-            put(c, lam * np.hstack([Z, Lm]), np.zeros(Lm.shape[0]))
-            put(c, mu * np.eye(B), np.zeros(B))
-            put(c, gam * np.hstack([-I, I]), -gam * a64[:, c])
-        for c in col:
-            for n in edges[c]:
-                if n > c:
-                    for weight, pick, field in ((lat, np.hstack([I, 0 * I]), v64), (lat, np.hstack([0 * I, I]), h64), (lata, np.hstack([-I, I]), a64)):
-                        if weight > 0.0:
-                            full = np.zeros((M, width))
-                            full[:, index[c] * B:index[c] * B + B] = weight * pick
-                            full[:, index[n] * B:index[n] * B + B] = -weight * pick
-                            rows.append(full); rhs.append(-weight * (field[:, c] - field[:, n]))
-        sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
-        for c in col:
-            out["delta_lstsq"][:, c] = sol[index[c] * B:index[c] * B + B]
-    s = out["delta"].astype(f)
-    dvmax, minvel, maxvel = f(dvmax), f(minvel), f(maxvel)
-    with np.errstate(invalid="ignore"):
-        s = np.where(s >= dvmax, dvmax, s)
-        s = np.where(s <= -dvmax, -dvmax, s).astype(f)
-        for c in col:
-            for vel, part in ((vsv, s[:M, c]), (vsh, s[M:, c])):
-                v = (vel[:M, c] + part).astype(f)
-                v = np.where(v < minvel, minvel, v)
-                vel[:M, c] = np.where(v > maxvel, maxvel, v)
+            Gc[:, :M] = np.where(love[u, None], 0.0, col[c]["G"][u]); Gc[:, M:] = np.where(love[u, None], col[c]["G"][u], 0.0)
+            return [(Gc, col[c]["rho"][u]), (lam * np.hstack([Lm, Z]), np.zeros(Lm.shape[0])), (lam * np.hstack([Z, Lm]), np.zeros(Lm.shape[0])),
+                    (mu * np.eye(B), np.zeros(B)), (gam * np.hstack([-I, I]), -gam * a64[:, c])]
+
+        between = lambda c, n: [(weight * pick, -weight * (field[:, c] - field[:, n])) for weight, pick, field in
+                                ((lat, np.hstack([I, 0 * I]), v64), (lat, np.hstack([0 * I, I]), h64), (lata, np.hstack([-I, I]), a64)) if weight > 0.0]
+        other = _twin_stacked(col, edges, B, own, between)
+    for c in col:
+        out["delta"][:, c] = x[c]
+        out["delta_lstsq"][:, c] = other[c]
+    s = _twin_clip(out["delta"], dvmax)
+    for c in col:
+        vsv[:M, c] = _twin_stepped(vsv[:M, c], s[:M, c], minvel, maxvel)
+        vsh[:M, c] = _twin_stepped(vsh[:M, c], s[M:, c], minvel, maxvel)
     out["dv"] = np.ascontiguousarray(s.reshape(2, M, ncol))
     return out
 
@@ -621,14 +565,11 @@ def column_resolution_twin(obs, wt, pv, S, depz, smooth, damp, n_override=None):
     obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64)
     K, M = S.shape
     wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
-    used = (wt > 0) & (obs > 0) & (pv > 0)
-    a = wt.astype(np.float64)
+    used, _, _, G = _twin_data(obs, wt, pv, S)
     out = dict(T=np.zeros((K, M)), R=np.zeros((M, M)), measures=np.zeros((4, M)), leverage=np.zeros(K), trace=0.0, nused=int(used.sum()), flag=0, other=None)
     if out["nused"] == 0:
         out["flag"] = 2
         return out
-    G = np.zeros((K, M))
-    G[used] = a[used, None] * S[used]
     lam2, mu2 = float(f(smooth)) * float(f(smooth)), float(f(damp)) * float(f(damp))
     N, _ = _twin_normal(G, used, np.zeros(K), lam2, mu2)
     if n_override is not None:
@@ -724,31 +665,56 @@ def check_lateral(radial=False, resolution=False):
                          (("--radial", "radial step") if radial else ("--resolution", "resolution")))
 
 
+def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral, radial_lateral_aniso):
+    """every precondition on the flags, in the order run() and main() both refuse in (ValueError), before the library is loaded.  aniso None:
+    not looked at; --lateral-tol and --lateral-maxit are looked at only with a coupling."""
+    with_cg = lateral is not None or radial_lateral is not None
+    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, lateral, lateral_tol if with_cg else None, lateral_maxit if with_cg else None, radial_lateral,
+          radial_lateral_aniso)
+    if lateral is not None:
+        check_lateral(radial, resolution)
+    if radial:
+        check_radial(None, resolution)
+    check_radial_lateral(radial_lateral, radial_lateral_aniso, radial, lateral, resolution)
+
+
+def _iterate(eng, plan, iterations, step, entry, log, coupling):
+    """the loop of iterate and iterate_radial: per iteration the runs of plan, out = step(), h = entry(iteration, out) (the history's dict; it
+    logs the iteration's first line), and with coupling (the words in the second line's brackets; None: no coupling) itn, istop and carried"""
+    history, steps = [], []
+    for it in range(1, iterations + 1):
+        for wave, kind, t, first in plan:
+            eng.dispersion_run(wave, kind, t, True, first, first)
+        out = step()
+        h = entry(it, out)
+        if coupling is not None:
+            h.update(itn=out["itn"], istop=out["istop"], carried=out["carried"])
+            log(" depth iteration %d (%s): %d conjugate-gradient iterations, istop %d (%s), %d columns without data carried by their neighbours" %
+                (it, coupling, h["itn"], h["istop"], "the tolerance was met" if h["istop"] == 1 else "--lateral-maxit was reached", h["carried"]))
+        history.append(h)
+        steps.append(out)
+    return dict(history=history, steps=steps)
+
+
 def iterate(eng, plan, obs, wt, iterations, smooth, damp, dvmax, minvel, maxvel, log=print, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
             lateral_maxit=DEFAULT_LATERAL_MAXIT):
     """The loop on an engine whose dispersion stage holds the starting model (dispersion_begin with as many maps as kernel slots): per
     iteration one dispersion_run with kernels per entry of plan (slot_plan), then columns_step -- or, with lateral (not None),
     columns_step_lateral.  Returns dict(history: one dict per iteration {iteration, nused, chi2, rms (before the step), flagged1, flagged2;
     with lateral also itn, istop, carried (the step's own count)}, steps: the step's result per iteration)."""
-    history, steps = [], []
-    for it in range(1, iterations + 1):
-        for wave, kind, t, first in plan:
-            eng.dispersion_run(wave, kind, t, True, first, first)
-        if lateral is None:
-            out = eng.columns_step(obs, wt, smooth, damp, dvmax, minvel, maxvel)
-        else:
-            out = eng.columns_step_lateral(obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
+    if lateral is None:
+        step = lambda: eng.columns_step(obs, wt, smooth, damp, dvmax, minvel, maxvel)
+    else:
+        step = lambda: eng.columns_step_lateral(obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
+
+    def entry(it, out):
         h = dict(iteration=it, nused=int(out["nused"].sum()), chi2=float(out["chi2"].sum()), rms=rms_of(out["chi2"], out["nused"]),
                  flagged1=int((out["flag"] == 1).sum()), flagged2=int((out["flag"] == 2).sum()))
         log(" depth iteration %d: %d data used, rms %.6f km/s before the step, %d columns flagged (%d not positive definite, %d without data)" %
             (it, h["nused"], h["rms"], h["flagged1"] + h["flagged2"], h["flagged1"], h["flagged2"]))
-        if lateral is not None:
-            h.update(itn=out["itn"], istop=out["istop"], carried=out["carried"])
-            log(" depth iteration %d (lateral %g): %d conjugate-gradient iterations, istop %d (%s), %d columns without data carried by their neighbours" %
-                (it, lateral, h["itn"], h["istop"], "the tolerance was met" if h["istop"] == 1 else "--lateral-maxit was reached", h["carried"]))
-        history.append(h)
-        steps.append(out)
-    return dict(history=history, steps=steps)
+        return h
+
+    return _iterate(eng, plan, iterations, step, entry, log, None if lateral is None else "lateral %g" % lateral)
 
 
 # ---- the files ----
@@ -907,26 +873,20 @@ def iterate_radial(eng, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, m
     iteration)."""
     if lateral is not None and lateral_aniso is None:
         lateral_aniso = lateral
-    history, steps = [], []
-    for it in range(1, iterations + 1):
-        for wave, kind, t, first in plan:
-            eng.dispersion_run(wave, kind, t, True, first, first)
-        if lateral is None:
-            out = eng.columns_step_radial(obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel)
-        else:
-            out = eng.columns_step_radial_lateral(obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
+    if lateral is None:
+        step = lambda: eng.columns_step_radial(obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel)
+    else:
+        step = lambda: eng.columns_step_radial_lateral(obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, lateral_tol, lateral_maxit)
+
+    def entry(it, out):
         h = dict(iteration=it, nused=int(out["nused"].sum()), chi2=float(out["chi2"].sum()), rms=rms_of(out["chi2"], out["nused"]),
                  nused_r=int(out["nused"][0].sum()), nused_l=int(out["nused"][1].sum()), rms_r=rms_of(out["chi2"][0], out["nused"][0]),
                  rms_l=rms_of(out["chi2"][1], out["nused"][1]), flagged1=int((out["flag"] == 1).sum()), flagged2=int((out["flag"] == 2).sum()))
         log(" depth iteration %d (radial): %d Rayleigh data rms %.6f km/s, %d Love data rms %.6f km/s before the step, %d columns flagged (%d not positive definite, %d without data)" %
             (it, h["nused_r"], h["rms_r"], h["nused_l"], h["rms_l"], h["flagged1"] + h["flagged2"], h["flagged1"], h["flagged2"]))
-        if lateral is not None:
-            h.update(itn=out["itn"], istop=out["istop"], carried=out["carried"])
-            log(" depth iteration %d (radial, lateral %g, on Vsh - Vsv %g): %d conjugate-gradient iterations, istop %d (%s), %d columns without data carried by their neighbours" %
-                (it, lateral, lateral_aniso, h["itn"], h["istop"], "the tolerance was met" if h["istop"] == 1 else "--lateral-maxit was reached", h["carried"]))
-        history.append(h)
-        steps.append(out)
-    return dict(history=history, steps=steps)
+        return h
+
+    return _iterate(eng, plan, iterations, step, entry, log, None if lateral is None else "radial, lateral %g, on Vsh - Vsv %g" % (lateral, lateral_aniso))
 
 
 def voigt_xi(vsv, vsh):
@@ -1014,14 +974,8 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
     None): the loop steps with columns_step_lateral; the files are the same two.  With radial and radial_lateral (not None): the radial loop
     steps with columns_step_radial_lateral, radial_lateral_aniso (None: radial_lateral) the weight on Vsh - Vsv; the files are --radial's."""
-    with_cg = lateral is not None or radial_lateral is not None          # (the tolerance and the iteration limit are looked at with either coupling)
-    check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, lateral, lateral_tol if with_cg else None, lateral_maxit if with_cg else None,
-          radial_lateral, radial_lateral_aniso)
-    if lateral is not None:
-        check_lateral(radial, resolution)
-    if radial:
-        check_radial(None, resolution)
-    check_radial_lateral(radial_lateral, radial_lateral_aniso, radial, lateral, resolution)
+    check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral,
+                radial_lateral_aniso)
     c = io.load(directory)
     if radial:
         check_radial(c)
@@ -1083,14 +1037,8 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        with_lateral = a.lateral is not None or a.radial_lateral is not None          # (--lateral-tol and --lateral-maxit are looked at only with a coupling, as run() does)
-        check(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.lateral, a.lateral_tol if with_lateral else None,
-              a.lateral_maxit if with_lateral else None, a.radial_lateral, a.radial_lateral_aniso)
-        if a.lateral is not None:
-            check_lateral(a.radial, a.resolution)
-        if a.radial:
-            check_radial(None, a.resolution)
-        check_radial_lateral(a.radial_lateral, a.radial_lateral_aniso, a.radial, a.lateral, a.resolution)
+        check_flags(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.radial, a.resolution, a.lateral, a.lateral_tol, a.lateral_maxit,
+                    a.radial_lateral, a.radial_lateral_aniso)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)

@@ -424,44 +424,51 @@ class Engine:
     def kernels_from_dispersion(self):
         self._check(self._L.dsa_kernels_from_dispersion(self._h))
 
-    def columns_step(self, obs, wt, smooth, damp, dvmax, minvel, maxvel):
-        """dsa_columns_step on the model of dispersion_begin: obs (nmaps, ny * nx) fp32 maps in get_maps' layout, wt the same shape or None
-        (all 1).  Returns dict(dv (nz - 1, ny * nx) fp32, nused (ny * nx) int32, chi2 (ny * nx) fp64, flag (ny * nx) int32).  ValueError when
-        obs and wt differ in size or do not fill whole maps: the library reads nmaps * nx * ny values of each."""
+    def _columns_in(self, who, obs, wt, models=0):
+        """What opens every columns_* call: obs and wt as contiguous fp32 -- ValueError (in who's name) when they differ in size or do not
+        fill whole maps: the library reads nmaps * nx * ny values of each -- and, for a step of 1 or 2 models, its zeroed outputs.  Returns
+        (nmaps, obs, wt, dv, nused, chi2, flag), the last four None without models."""
         nx, ny, nz = self._disp
         ncol = nx * ny
         obs = np.ascontiguousarray(obs, np.float32)
         if ncol == 0 or obs.size == 0 or obs.size % ncol:
-            raise ValueError("columns_step: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
+            raise ValueError("%s: obs holds %d values, not whole maps of %d x %d" % (who, obs.size, nx, ny))
         if wt is not None:
             wt = np.ascontiguousarray(wt, np.float32)
             if wt.size != obs.size:
-                raise ValueError("columns_step: wt holds %d values, obs %d" % (wt.size, obs.size))
-        dv = np.zeros((nz - 1, ncol), np.float32); nused = np.zeros(ncol, np.int32); chi2 = np.zeros(ncol); flag = np.zeros(ncol, np.int32)
-        self._check(self._L.dsa_columns_step(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(dvmax),
-                                             float(minvel), float(maxvel), _p(dv), _p(nused), _p(chi2), _p(flag)))
+                raise ValueError("%s: wt holds %d values, obs %d" % (who, wt.size, obs.size))
+        lead = (2,) if models == 2 else ()
+        outs = (np.zeros(lead + (nz - 1, ncol), np.float32), np.zeros(lead + (ncol,), np.int32), np.zeros(lead + (ncol,)), np.zeros(ncol, np.int32)) if models else (None,) * 4
+        return (obs.size // ncol, obs, wt) + outs
+
+    def _carried(self, nused, flag):
+        """the interior columns without a used datum (of any type) that were stepped all the same: nused 0, flag 0"""
+        nx, ny, _ = self._disp
+        inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+        return int((inner.ravel() & (nused.reshape(-1, nx * ny).sum(axis=0) == 0) & (flag == 0)).sum())
+
+    def columns_step(self, obs, wt, smooth, damp, dvmax, minvel, maxvel):
+        """dsa_columns_step on the model of dispersion_begin: obs (nmaps, ny * nx) fp32 maps in get_maps' layout, wt the same shape or None
+        (all 1).  Returns dict(dv (nz - 1, ny * nx) fp32, nused (ny * nx) int32, chi2 (ny * nx) fp64, flag (ny * nx) int32).  ValueError when
+        obs and wt differ in size or do not fill whole maps: the library reads nmaps * nx * ny values of each."""
+        nmaps, obs, wt, dv, nused, chi2, flag = self._columns_in("columns_step", obs, wt, 1)
+        self._check(self._L.dsa_columns_step(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(dvmax), float(minvel), float(maxvel), _p(dv), _p(nused),
+                                             _p(chi2), _p(flag)))
         return dict(dv=dv, nused=nused, chi2=chi2, flag=flag)
 
     def columns_resolution(self, obs, wt, smooth, damp, full=False):
         """dsa_columns_resolution on the state columns_step needs, which it leaves as it is: obs and wt as columns_step's.  Returns
         dict(measures (4, nz - 1, ny * nx): R_jj, m1, m2, var; leverage (nmaps, ny * nx); trace (ny * nx); nused, flag (ny * nx) int32; and
         with full=True R (nz - 1, nz - 1, ny * nx), R[l, j] the response at depth l to unknown j), all fp64.  ValueError as columns_step."""
+        nmaps, obs, wt = self._columns_in("columns_resolution", obs, wt)[:3]
         nx, ny, nz = self._disp
         ncol = nx * ny
-        obs = np.ascontiguousarray(obs, np.float32)
-        if ncol == 0 or obs.size == 0 or obs.size % ncol:
-            raise ValueError("columns_resolution: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
-        if wt is not None:
-            wt = np.ascontiguousarray(wt, np.float32)
-            if wt.size != obs.size:
-                raise ValueError("columns_resolution: wt holds %d values, obs %d" % (wt.size, obs.size))
-        nmaps = obs.size // ncol
         out = dict(measures=np.zeros((4, nz - 1, ncol)), leverage=np.zeros((nmaps, ncol)), trace=np.zeros(ncol), nused=np.zeros(ncol, np.int32),
                    flag=np.zeros(ncol, np.int32))
         if full:
             out["R"] = np.zeros((nz - 1, nz - 1, ncol))
-        self._check(self._L.dsa_columns_resolution(self._h, nmaps, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), _p(out["measures"]),
-                                                   _p(out["leverage"]), _p(out["trace"]), _p(out["R"]) if full else None, _p(out["nused"]), _p(out["flag"])))
+        self._check(self._L.dsa_columns_resolution(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), _p(out["measures"]), _p(out["leverage"]),
+                                                   _p(out["trace"]), _p(out["R"]) if full else None, _p(out["nused"]), _p(out["flag"])))
         return out
 
     def dispersion_get_model(self):
@@ -486,18 +493,9 @@ class Engine:
         """dsa_columns_step_radial on the models of dispersion_begin_radial: obs and wt as columns_step's.  Returns dict(dv_sv, dv_sh (nz - 1,
         ny * nx) fp32, nused (2, ny * nx) int32 and chi2 (2, ny * nx) fp64 -- Rayleigh, then Love -- flag (ny * nx) int32).  ValueError as
         columns_step."""
-        nx, ny, nz = self._disp
-        ncol = nx * ny
-        obs = np.ascontiguousarray(obs, np.float32)
-        if ncol == 0 or obs.size == 0 or obs.size % ncol:
-            raise ValueError("columns_step_radial: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
-        if wt is not None:
-            wt = np.ascontiguousarray(wt, np.float32)
-            if wt.size != obs.size:
-                raise ValueError("columns_step_radial: wt holds %d values, obs %d" % (wt.size, obs.size))
-        dv = np.zeros((2, nz - 1, ncol), np.float32); nused = np.zeros((2, ncol), np.int32); chi2 = np.zeros((2, ncol)); flag = np.zeros(ncol, np.int32)
-        self._check(self._L.dsa_columns_step_radial(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(aniso),
-                                                    float(dvmax), float(minvel), float(maxvel), _p(dv), _p(nused), _p(chi2), _p(flag)))
+        nmaps, obs, wt, dv, nused, chi2, flag = self._columns_in("columns_step_radial", obs, wt, 2)
+        self._check(self._L.dsa_columns_step_radial(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(aniso), float(dvmax), float(minvel), float(maxvel),
+                                                    _p(dv), _p(nused), _p(chi2), _p(flag)))
         return dict(dv_sv=dv[0], dv_sh=dv[1], nused=nused, chi2=chi2, flag=flag)
 
     def columns_step_lateral(self, obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
@@ -505,21 +503,12 @@ class Engine:
         weight lateral (0: columns_step's bits), solved by preconditioned conjugate gradients to the relative tolerance tol in at most maxit
         iterations.  Returns columns_step's dict with itn, istop (1 converged, 2 maxit), rz0, rz and carried (the interior columns without a
         used datum that were stepped all the same: nused 0, flag 0) added.  ValueError as columns_step."""
-        nx, ny, nz = self._disp
-        ncol = nx * ny
-        obs = np.ascontiguousarray(obs, np.float32)
-        if ncol == 0 or obs.size == 0 or obs.size % ncol:
-            raise ValueError("columns_step_lateral: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
-        if wt is not None:
-            wt = np.ascontiguousarray(wt, np.float32)
-            if wt.size != obs.size:
-                raise ValueError("columns_step_lateral: wt holds %d values, obs %d" % (wt.size, obs.size))
-        dv = np.zeros((nz - 1, ncol), np.float32); nused = np.zeros(ncol, np.int32); chi2 = np.zeros(ncol); flag = np.zeros(ncol, np.int32); info = np.zeros(4)
-        self._check(self._L.dsa_columns_step_lateral(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(lateral),
-                                                     float(dvmax), float(minvel), float(maxvel), float(tol), int(maxit), _p(dv), _p(nused), _p(chi2), _p(flag), _p(info)))
-        inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
-        carried = int((inner.ravel() & (nused == 0) & (flag == 0)).sum())
-        return dict(dv=dv, nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]), carried=carried)
+        nmaps, obs, wt, dv, nused, chi2, flag = self._columns_in("columns_step_lateral", obs, wt, 1)
+        info = np.zeros(4)
+        self._check(self._L.dsa_columns_step_lateral(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(lateral), float(dvmax), float(minvel),
+                                                     float(maxvel), float(tol), int(maxit), _p(dv), _p(nused), _p(chi2), _p(flag), _p(info)))
+        return dict(dv=dv, nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]),
+                    carried=self._carried(nused, flag))
 
     def columns_step_radial_lateral(self, obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
         """dsa_columns_step_radial_lateral on the models of dispersion_begin_radial: columns_step_radial with the interior columns tied to their
@@ -527,24 +516,13 @@ class Engine:
         columns_step_radial's bits) -- solved by preconditioned conjugate gradients to the relative tolerance tol in at most maxit iterations.
         Returns columns_step_radial's dict with itn, istop (1 converged, 2 maxit), rz0, rz and carried (the interior columns without a used
         datum of either type that were stepped all the same: nused 0 0, flag 0) added.  ValueError as columns_step."""
-        nx, ny, nz = self._disp
-        ncol = nx * ny
-        obs = np.ascontiguousarray(obs, np.float32)
-        if ncol == 0 or obs.size == 0 or obs.size % ncol:
-            raise ValueError("columns_step_radial_lateral: obs holds %d values, not whole maps of %d x %d" % (obs.size, nx, ny))
-        if wt is not None:
-            wt = np.ascontiguousarray(wt, np.float32)
-            if wt.size != obs.size:
-                raise ValueError("columns_step_radial_lateral: wt holds %d values, obs %d" % (wt.size, obs.size))
-        dv = np.zeros((2, nz - 1, ncol), np.float32); nused = np.zeros((2, ncol), np.int32); chi2 = np.zeros((2, ncol)); flag = np.zeros(ncol, np.int32)
+        nmaps, obs, wt, dv, nused, chi2, flag = self._columns_in("columns_step_radial_lateral", obs, wt, 2)
         info = np.zeros(4)
-        self._check(self._L.dsa_columns_step_radial_lateral(self._h, obs.size // ncol, _p(obs), None if wt is None else _p(wt), float(smooth), float(damp), float(aniso),
-                                                            float(lateral), float(lateral_aniso), float(dvmax), float(minvel), float(maxvel), float(tol), int(maxit),
-                                                            _p(dv), _p(nused), _p(chi2), _p(flag), _p(info)))
-        inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
-        carried = int((inner.ravel() & (nused.sum(axis=0) == 0) & (flag == 0)).sum())
+        self._check(self._L.dsa_columns_step_radial_lateral(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(aniso), float(lateral), float(lateral_aniso),
+                                                            float(dvmax), float(minvel), float(maxvel), float(tol), int(maxit), _p(dv), _p(nused), _p(chi2), _p(flag),
+                                                            _p(info)))
         return dict(dv_sv=dv[0], dv_sh=dv[1], nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]),
-                    carried=carried)
+                    carried=self._carried(nused, flag))
 
     def dispersion_get_model_radial(self):
         """the radial stage's two resident models, (vsv, vsh), each (nz, ny, nx) fp32"""

@@ -1,5 +1,5 @@
-"""dsa_columns_step_radial_lateral (csrc/column_kernels.hip: k_radial_lateral_* with k_lateral_update and k_lateral_reduce; DESIGN.md
-section 25) on the device against the CPU build of the same header (tests/hostcheck_column_radial_lateral.cpp through
+"""dsa_columns_step_radial_lateral (csrc/column_kernels.hip: k_radial_lateral_setup and k_radial_lateral_start, then the k_lateral_*
+kernels every coupled system runs, k_lateral_residual and k_lateral_direction on RadialLateralWs) on the device against the CPU build of the same header (tests/hostcheck_column_radial_lateral.cpp through
 column_radial_lateral_ref), bit for bit: the kernels share column_radial_lateral.h's loops out over a wavefront per column, every figure is
 one sequential fp64 chain under -ffp-contract=off, the global sums have one shape (64 chains), and the scalars of the conjugate-gradient
 loop are computed once, so neither the lane mapping nor the number of launches can show.
@@ -11,6 +11,7 @@ from the device after the runs, so the dispersion stage's own arithmetic is not 
 import numpy as np
 import pytest
 
+import column_lateral_ref as IR
 import column_radial_lateral_ref as LR
 import column_radial_ref as RR
 import columns_ref as R
@@ -280,3 +281,42 @@ def test_workspace_beyond_the_memory_budget(eng, h):
         eng.set_memory_budget(0)
     runs(eng)
     assert not eng.columns_step_radial_lateral(obs, None, *BASE, 0.2, 0.4, *CLIP)["flag"].any()
+
+
+def test_both_coupled_steps_share_one_engine(eng, h, hs):
+    """(13): dsa_columns_step_lateral on a 6 x 4 grid (nz = 3, lateral 0.3), then dsa_columns_step_radial_lateral on 11 x 10 (nz = 8, at
+    0.3, 0.6), then the first call again on a fresh dispersion_begin with the same inputs, all on one engine, whose two steps share their
+    workspace: each result equals its host harness bit for bit, and the third equals the first bit for bit -- what a call that read what
+    an earlier one left in the workspace would break."""
+    hi = IR.load()
+
+    def lateral_call():
+        nz, nx, ny = 3, 6, 4
+        depz, vel, rng, wt = case("smooth", nz, nx, ny)
+        eng.dispersion_begin(vel, depz, R.MINTHK, K, K)
+        runs(eng)
+        pv, svs, svp, srho = eng.dispersion_fetch(0, K, True, 0)
+        obs = (pv * (1.0 + 0.02 * rng.standard_normal((K, nx * ny)))).astype(F)
+        S = R.host_combine(hs, vel.reshape(nz, nx * ny), depz, svs, svp, srho)
+        want = IR.host_step(hi, nx, ny, obs, wt, pv, S, vel.reshape(nz, nx * ny), R.SMOOTH, R.DAMP, 0.3, *CLIP)
+        got = eng.columns_step_lateral(obs, wt, R.SMOOTH, R.DAMP, 0.3, *CLIP, IR.TOL, IR.MAXIT)
+        got["vels"] = eng.dispersion_get_model().reshape(nz, nx * ny)
+        assert (got["itn"], got["istop"]) == (want["itn"], want["istop"]) and got["itn"] >= 1
+        assert same_bits(np.array([got["rz0"], got["rz"]]), np.array([want["rz0"], want["rz"]]))
+        for name in ("nused", "flag", "chi2", "dv", "vels"):
+            assert same_bits(got[name], want[name]), "%s differs from the host's" % name
+        return got
+
+    first = lateral_call()
+    nz, nx, ny = 8, 11, 10
+    depz, vsv, rng, wt = case("smooth", nz, nx, ny)
+    vsh = above(vsv)
+    eng.dispersion_begin_radial(vsv, vsh, depz, R.MINTHK, K, K)
+    runs(eng)
+    obs, clip = observations(eng, "smooth", rng, nx * ny)
+    got, _ = against_host(h, hs, eng, vsv, vsh, depz, obs, wt, 0.3, 0.6, clip)
+    assert got["itn"] >= 2
+    again = lateral_call()
+    assert (first["itn"], first["istop"], first["carried"]) == (again["itn"], again["istop"], again["carried"])
+    for name in ("nused", "flag", "chi2", "dv", "vels", "rz0", "rz"):
+        assert same_bits(np.asarray(first[name]), np.asarray(again[name])), "%s of the repeated call differs from the first" % name
