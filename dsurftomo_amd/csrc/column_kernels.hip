@@ -5,6 +5,7 @@
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
 // k_column_step_radial: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
+// k_column_resolution_radial: the resolution of that step's 2M unknowns, a block of two wavefronts per column.
 // k_lateral_* (DESIGN.md section 24): the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
 // the same loop and kernels on the radial step's 2M unknowns per column; only k_radial_lateral_setup and
 // k_radial_lateral_start are that system's own.
@@ -12,6 +13,7 @@
 #include "column_system.h"
 #include "column_resolution.h"
 #include "column_radial.h"
+#include "column_radial_resolution.h"
 #include "column_lateral.h"
 #include "column_radial_lateral.h"
 
@@ -114,6 +116,43 @@ __global__ void __launch_bounds__(64) k_column_step_radial(int nx, int ny, int n
     const int f = radial_step(in, smooth, damp, aniso, dvmax, minvel, maxvel, w, vsv + c, vsh + c, ncol, dv + c, dv + (long long)M * ncol + c, ncol, n, x2,
                               (int)threadIdx.x, 64, BlockBarrier());
     if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; chi2[c] = x2[0]; chi2[ncol + c] = x2[1]; flag[c] = f; }
+}
+
+// k_column_resolution_radial: column_radial_resolution.h on every interior column of the two resident models, one
+// block of two wavefronts per column (the header's nlanes: 2M reaches 126, one lane per unknown in the reductions; the K solves run on the
+// first K lanes).  The work arrays of the radial step and T (2M x K) lie in dynamic LDS and nowhere else: 6.7 KB for K = 26 on M = 8,
+// 158 712 B at the stage's limits (M = 63, K = 60) of the 163 840 B a workgroup may have, which the launcher has to ask for.
+// measures: (6, 2M, ncol); pair: (2, M, ncol); leverage: (K, ncol); trace / nused: (2, ncol); flag: (ncol); R: null or (2M, 2M, ncol).
+#ifndef DSA_RADIAL_RESOLUTION_LANES
+#define DSA_RADIAL_RESOLUTION_LANES 128          // 64 or 128: both were timed (section 26)
+#endif
+constexpr int kRadialResolutionLanes = DSA_RADIAL_RESOLUTION_LANES;
+
+__global__ void __launch_bounds__(kRadialResolutionLanes)
+k_column_resolution_radial(int nx, int ny, int nz, int K, unsigned long long love, const float* __restrict__ obs, const float* __restrict__ wt,
+                           const double* __restrict__ pv, const double* __restrict__ Sv, const double* __restrict__ Sh, const float* __restrict__ depz,
+                           const float* __restrict__ vsv, const float* __restrict__ vsh, float smooth, float damp, float aniso, double* __restrict__ measures,
+                           double* __restrict__ pair, double* __restrict__ leverage, double* __restrict__ trace, double* __restrict__ R, int* __restrict__ nused,
+                           int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
+    RadialIn in;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.love = love; in.Sv = Sv + c; in.Sh = Sh + c;
+    RadialResOut out;
+    out.measures = measures + c; out.m_qstride = 2ll * M * ncol; out.m_jstride = ncol;
+    out.pair = pair + c; out.p_qstride = (long long)M * ncol; out.p_lstride = ncol;
+    out.leverage = leverage + c; out.h_stride = ncol;
+    out.R = R ? R + c : nullptr; out.r_stride = ncol;
+    const ColumnWork w = radial_work(column_lds, M, K);
+    int n[2] = { 0, 0 };
+    double tr[2] = { 0.0, 0.0 };
+    const int f = radial_resolution(in, depz, smooth, damp, aniso, vsv + c, vsh + c, ncol, w, radial_resolution_t(column_lds, M, K), out, tr, n, (int)threadIdx.x,
+                                    (int)blockDim.x, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n[0]; nused[ncol + c] = n[1]; trace[c] = tr[0]; trace[ncol + c] = tr[1]; flag[c] = f; }
 }
 
 // The laterally coupled steps (DESIGN.md sections 24 and 25): column_lateral.h's conjugate gradients on every interior column, the launch
@@ -270,6 +309,22 @@ int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigne
     if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_step_radial), lds, limit_out)) return rc;
     hipLaunchKernelGGL(k_column_step_radial, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, love, d_obs, d_wt, d_pv, d_Sv, d_Sh,
                        smooth, damp, aniso, dvmax, minvel, maxvel, d_vsv, d_vsh, d_dv, d_nused, d_chi2, d_flag);
+    return 0;
+}
+
+size_t column_radial_resolution_lds_bytes(int nz, int K) { return radial_resolution_doubles(nz - 1, K) * sizeof(double); }
+
+// column_lds_opt_in's return values: nothing is launched unless 0
+int launch_column_resolution_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                    const double* d_Sv, const double* d_Sh, const float* d_depz, const float* d_vsv, const float* d_vsh, float smooth, float damp,
+                                    float aniso, double* d_measures, double* d_pair, double* d_leverage, double* d_trace, double* d_R, int* d_nused, int* d_flag,
+                                    hipStream_t stream, int* limit_out)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
+    const size_t lds = column_radial_resolution_lds_bytes(nz, K);
+    if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_resolution_radial), lds, limit_out)) return rc;
+    hipLaunchKernelGGL(k_column_resolution_radial, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(kRadialResolutionLanes), lds, stream, nx, ny, nz, K, love, d_obs,
+                       d_wt, d_pv, d_Sv, d_Sh, d_depz, d_vsv, d_vsh, smooth, damp, aniso, d_measures, d_pair, d_leverage, d_trace, d_R, d_nused, d_flag);
     return 0;
 }
 

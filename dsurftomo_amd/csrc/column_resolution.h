@@ -39,9 +39,23 @@ struct ColumnResOut {
     double* R; long long r_stride;
 };
 
-// T on a factored system (w.tri, w.d) with w.G and w.a assembled: lane k runs the solve of datum k
-template <class Sync>
-DSA_CS void column_resolution_solve(int M, int K, const ColumnWork& w, double* T, int lane, int nlanes, Sync sync)
+// DSA_CS for a member function
+#if defined(__HIPCC__)
+#define DSA_CS_MEMBER __host__ __device__ __forceinline__
+#else
+#define DSA_CS_MEMBER inline
+#endif
+
+// element i of the right-hand side of datum k: row k of G
+struct ColumnRowOfG {
+    const double* G; int M;
+    DSA_CS_MEMBER double operator()(int k, int i) const { return G[k * M + i]; }
+};
+
+// T on a factored system of M unknowns (w.tri, w.d) with w.a assembled: lane k runs the solve of datum k on the right-hand side
+// rhs(k, 0 .. M-1).  The one copy of the per-datum solve: section 22's on row k of G, section 26's on 2M unknowns.
+template <class Rhs, class Sync>
+DSA_CS void column_resolution_solve_rhs(int M, int K, const ColumnWork& w, const Rhs& rhs, double* T, int lane, int nlanes, Sync sync)
 {
     const int Kp = column_resolution_kpad(K);
     for (int k = lane; k < K; k += nlanes) {
@@ -49,7 +63,7 @@ DSA_CS void column_resolution_solve(int M, int K, const ColumnWork& w, double* T
             for (int i = 0; i < M; ++i) T[i * Kp + k] = 0.0;
             continue;
         }
-        for (int i = 0; i < M; ++i) T[i * Kp + k] = w.G[k * M + i];
+        for (int i = 0; i < M; ++i) T[i * Kp + k] = rhs(k, i);
         for (int p = 0; p + 1 < M; ++p) {
             const double tp = T[p * Kp + k];
             for (int i = p + 1; i < M; ++i) T[i * Kp + k] -= w.tri[column_tri(i, p)] * tp;
@@ -62,6 +76,15 @@ DSA_CS void column_resolution_solve(int M, int K, const ColumnWork& w, double* T
         }
     }
     sync();
+}
+
+// T of section 22: the right-hand sides are the rows of w.G
+template <class Sync>
+DSA_CS void column_resolution_solve(int M, int K, const ColumnWork& w, double* T, int lane, int nlanes, Sync sync)
+{
+    ColumnRowOfG rhs;
+    rhs.G = w.G; rhs.M = M;
+    column_resolution_solve_rhs(M, K, w, rhs, T, lane, nlanes, sync);
 }
 
 // the measures, the leverages and the trace from T and w.G; w.b gets the R_jj.  Every lane returns the same trace.

@@ -331,6 +331,11 @@ struct Engine {
     int columns_step_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel,
                             float* dv, int* nused, double* chi2, int* flag);
     int dispersion_get_model_radial(float* vsv, float* vsh);
+    // depth resolution of the radial step (dsa_columns_resolution_radial, k_column_resolution_radial): reads what
+    // dsa_columns_step_radial reads, changes nothing; col_meas, col_lev, col_trace and col_R are shared with the plain resolution
+    OwnedBuf<double> col_pair;
+    int columns_resolution_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, double* measures, double* pair,
+                                  double* leverage, double* trace, int* nused, int* flag, double* R);
     // laterally coupled step (dsa_columns_step_lateral, k_lateral_*): dsa_columns_step's state, arguments and outputs; the
     // workspace of the conjugate-gradient loop is kept allocated between calls; no call reads what an earlier one left in it.  The host looks at
     // the loop's done flag every lateral_poll iterations.

@@ -655,6 +655,49 @@ int Engine::columns_step_radial(int nmaps_in, const float* obs, const float* wt,
     return columns_stage_out(2, dv, nused, chi2, flag, nullptr, nullptr);
 }
 
+// dsa_columns_resolution_radial: the resolution measures of the radial step's 2M unknowns per column, from the resident
+// curves and kernels of a radial stage.  The state and argument rules are columns_step_radial's without dvmax, minvel and maxvel; everything is
+// checked before the device is touched, except the LDS of the kernel (DSA_ERR_DEVICE before anything is launched).  The stage is read only: no
+// mark is cleared, both models, their host copies and Srow stay, so a dsa_columns_step_radial after it gives the bits it would have given.
+int Engine::columns_resolution_radial(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, double* measures, double* pair,
+                                      double* leverage, double* trace, int* nused, int* flag, double* R)
+{
+    const char* who = "columns_resolution_radial";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f, true)) return rc;
+    if (int rc = columns_weight(who, "aniso", aniso)) return rc;
+    if (!measures || !pair || !leverage || !trace || !nused || !flag) { fail(DSA_ERR_ARGUMENT, "%s: measures, pair, leverage, trace, nused and flag are required", who); return DSA_ERR_ARGUMENT; }
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K, n2 = 2 * (size_t)M;
+    HIP_TRY(this, hipSetDevice(device));
+    if (int rc = columns_stage_in(2, obs, wt, false)) return rc;
+    if (ensure(col_depz, (size_t)disp_nz) || ensure(col_meas, 6 * ncol * n2) || ensure(col_pair, 2 * ncol * M) || ensure(col_lev, nobs) || ensure(col_trace, 2 * ncol) ||
+        (R && ensure(col_R, ncol * n2 * n2)) || ensure(col_nused, 2 * ncol) || ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_depz.p, h_depz.data(), (size_t)disp_nz * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernel runs on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_meas.p, 0, 6 * ncol * n2 * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_pair.p, 0, 2 * ncol * M * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_lev.p, 0, nobs * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_trace.p, 0, 2 * ncol * 8, stream));
+    if (R) HIP_TRY(this, hipMemsetAsync(col_R.p, 0, ncol * n2 * n2 * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, 2 * ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    int limit = 0;
+    const int rc = launch_column_resolution_radial(device, disp_nx, disp_ny, disp_nz, K, columns_love(), col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, col_Sh.p,
+                                                   col_depz.p, vels_d.p, vsh_d.p, smooth, damp, aniso, col_meas.p, col_pair.p, col_lev.p, col_trace.p,
+                                                   R ? col_R.p : nullptr, col_nused.p, col_flag.p, stream, &limit);
+    if (rc) return columns_lds_refusal(who, rc, (int)n2, column_radial_resolution_lds_bytes(disp_nz, K), limit);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(measures, col_meas.p, 6 * ncol * n2 * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(pair, col_pair.p, 2 * ncol * M * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(leverage, col_lev.p, nobs * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(trace, col_trace.p, 2 * ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (R) HIP_TRY(this, hipMemcpyAsync(R, col_R.p, ncol * n2 * n2 * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, 2 * ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
 // dsa_columns_step_lateral: dsa_columns_step with the interior columns tied to their neighbours, column_lateral.h's
 // preconditioned conjugate gradients.  The state and argument rules are columns_front's, then columns_coupled_front's; everything is checked
 // before the device is touched.  The workspace (col_lat, shared with the radial coupled step) carries nothing from call to call: every word
@@ -2193,6 +2236,13 @@ int dsa_columns_step_radial(dsa_engine* e, int nmaps, const float* obs, const fl
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_step_radial(nmaps, obs, wt, smooth, damp, aniso, dvmax, minvel, maxvel, dv, nused, chi2, flag);
+}
+
+int dsa_columns_resolution_radial(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, double* measures,
+                                  double* pair, double* leverage, double* trace, int* nused, int* flag, double* R)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_resolution_radial(nmaps, obs, wt, smooth, damp, aniso, measures, pair, leverage, trace, nused, flag, R);
 }
 
 int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax, float minvel,

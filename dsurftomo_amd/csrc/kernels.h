@@ -322,6 +322,15 @@ size_t column_radial_lds_bytes(int nz, int K);
 int launch_column_step_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
                               const double* d_Sv, const double* d_Sh, float smooth, float damp, float aniso, float dvmax, float minvel, float maxvel, float* d_vsv,
                               float* d_vsh, float* d_dv, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream, int* limit_out);
+// The depth resolution of the radial step's 2 (nz - 1) unknowns per column, nothing stepped: the inputs are
+// launch_column_step_radial's and d_depz.  d_measures (6, 2 (nz - 1), ncol): R_jj, m1_own, m2_own, m1_cross, R_cross, var; d_pair (2, nz - 1,
+// ncol): cov, vard; d_leverage (K, ncol); d_trace / d_nused (2, ncol); d_flag (ncol); d_R null or (2 (nz - 1), 2 (nz - 1), ncol).  Only interior
+// columns are written.  The return values and *limit_out are launch_column_resolution's; column_radial_resolution_lds_bytes: the dynamic LDS.
+size_t column_radial_resolution_lds_bytes(int nz, int K);
+int launch_column_resolution_radial(int device, int nx, int ny, int nz, int K, unsigned long long love, const float* d_obs, const float* d_wt, const double* d_pv,
+                                    const double* d_Sv, const double* d_Sh, const float* d_depz, const float* d_vsv, const float* d_vsh, float smooth, float damp,
+                                    float aniso, double* d_measures, double* d_pair, double* d_leverage, double* d_trace, double* d_R, int* d_nused, int* d_flag,
+                                    hipStream_t stream, int* limit_out);
 // The laterally coupled steps (DESIGN.md sections 24 and 25): column_lateral.h's conjugate gradients on a system of blocks = 1 model
 // (column_lateral.h's own; lateral_aniso is not read) or blocks = 2 models (column_radial_lateral.h's, 2 (nz - 1) unknowns per column).
 // d_ws: coupled_ws_bytes bytes.  coupled_edges: whether the columns are coupled at all (else the loop stops at iteration 0).  coupled_ints: the

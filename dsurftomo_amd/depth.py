@@ -2,7 +2,7 @@
 
     python -m dsurftomo_amd.depth <directory with DSurfTomo.in, the data file and MOD> [--maps FILE] [--iterations N] [--smooth L] [--damp D]
                                   [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]] [--radial [--aniso G]]
-                                  [--lateral W [--lateral-tol T] [--lateral-maxit N]]
+                                  [--lateral W [--lateral-tol T] [--lateral-maxit N]] [--radial-resolution]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -57,6 +57,19 @@ strongly than the velocities; a column without a used datum gets its xi from its
 --lateral-maxit apply.  --radial-lateral without --radial, --radial-lateral-aniso without --radial-lateral, and either with --lateral or
 --resolution are refused (--lateral with --radial stays refused as it was).  DepthRadial.dat and DepthRadialFit.dat keep their formats; the
 log adds per iteration what --lateral's adds.  column_radial_lateral_twin is the NumPy twin (csrc/column_radial_lateral.h is the arithmetic).
+
+--radial --radial-resolution [--sigma S]: after the last radial step the runs are done once more on the final models
+and columns_resolution_radial asks the 2 (nz - 1) x 2 (nz - 1) normal matrix of every column, with the loop's weights, --smooth, --damp and
+--aniso, how far Vsv, Vsh and xi can be trusted.  <input>DepthRadialResolution.dat (write_radial_resolution / read_radial_resolution): per
+node above the bottom depth longitude, latitude, depth; for Vsv and for Vsh R_jj, the vertical length sqrt(m2_own / m1_own) of the node's
+point-spread function inside its model in km, the leak share m1_cross / (m1_own + m1_cross) of a spike's answer that lies in the other
+model (0 where the denominator is 0) and sd = S sqrt(var); R_aniso = (R_vv + R_hh - R_hv - R_vh) / 2, the resolution of Vsh - Vsv at the
+node; sd_diff = S sqrt(vard), the standard deviation of Vsh - Vsv; sd_xi = 2 xi S sqrt(var_v / Vsv^2 + var_h / Vsh^2 - 2 cov / (Vsv Vsh)).
+S is --sigma in km/s or, by default, the rms before the last step.  <input>DepthRadialLeverage.dat (write_radial_leverage /
+read_radial_leverage): DepthLeverage.dat's layout.  The log gives the flagged columns, the median and range of each block's trace, the
+median leak share per block and how many unflagged nodes have |xi - 1| > 2 sd_xi.  --radial --resolution stays refused; the flag without
+--radial and the flag with --radial-lateral (the resolution of the laterally coupled system is not computed) are refused.  Without the flag
+nothing changes.  column_radial_resolution_twin is the NumPy twin (csrc/column_radial_resolution.h is the arithmetic).
 
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
@@ -589,6 +602,90 @@ def column_resolution_twin(obs, wt, pv, S, depz, smooth, damp, n_override=None):
     return out
 
 
+def _radial_expand(G, love):
+    """the expanded G^ (K, 2M): row k is G[k] in the block of its wave type (Vsv for Rayleigh, Vsh for Love) and 0.0 elsewhere"""
+    K, M = G.shape
+    Gx = np.zeros((K, 2 * M))
+    Gx[:, :M] = np.where(love[:, None], 0.0, G); Gx[:, M:] = np.where(love[:, None], G, 0.0)
+    return Gx
+
+
+def _radial_resolution_measures(T, G, used, love, depz):
+    """R = T^T G^ and what column_radial_resolution.h reduces from it, every sum from 0.0 in the header's order: over the used k ascending, over
+    i ascending within each block.  T (K, 2M), G (K, M) compact.  Returns dict(R (2M, 2M), measures (6, 2M): R_jj, m1_own, m2_own, m1_cross,
+    R_cross, var; pair (2, M): cov, vard; leverage (K); trace (2))."""
+    K, M = G.shape
+    n = 2 * M
+    z = np.asarray(depz, np.float32)[:M].astype(np.float64)
+    z2 = np.concatenate([z, z])
+    block = np.arange(n) >= M
+    R = np.zeros((n, n)); var = np.zeros(n); cov = np.zeros(M); vard = np.zeros(M)
+    for k in np.flatnonzero(used):
+        q = int(love[k])
+        R[:, q * M:(q + 1) * M] = R[:, q * M:(q + 1) * M] + np.outer(T[k], G[k])
+        var = var + T[k] * T[k]
+        cov = cov + T[k, :M] * T[k, M:]
+        d = T[k, M:] - T[k, :M]
+        vard = vard + d * d
+    m1 = np.zeros(n); m2 = np.zeros(n); mx = np.zeros(n)
+    for i in range(n):
+        r2 = R[i] * R[i]
+        dz = z2[i] - z2
+        own = block == block[i]
+        m1 = np.where(own, m1 + r2, m1)
+        m2 = np.where(own, m2 + r2 * (dz * dz), m2)
+        mx = np.where(own, mx, mx + r2)
+    rx = np.array([R[j - M if j >= M else j + M, j] for j in range(n)])
+    h = np.zeros(K)
+    first = np.where(love, M, 0)
+    for l in range(M):
+        h = h + G[:, l] * T[np.arange(K), first + l]
+    h[~used] = 0.0
+    trace = [0.0, 0.0]
+    for j in range(n):
+        trace[int(j >= M)] = trace[int(j >= M)] + R[j, j]
+    return dict(R=R, measures=np.stack([np.diag(R).copy(), m1, m2, mx, rx, var]), pair=np.stack([cov, vard]), leverage=h, trace=np.array(trace))
+
+
+def column_radial_resolution_twin(obs, wt, pv, S, love, depz, smooth, damp, aniso, n_override=None):
+    """dsa_columns_resolution_radial on one column in NumPy (csrc/column_radial_resolution.h).  obs, wt, pv, S and love as column_radial_twin's;
+    depz: the depths of the unknowns (M or more, fp32).  N is built as column_radial_twin builds it (the starting models enter b only, which
+    nothing here reads); row k of T (K, 2M) is the solution of N t = g^_k through the header's L D L^T order, rows of unused data 0;
+    R = T^T G^.  Returns dict(T, R (2M, 2M), measures (6, 2M), pair (2, M), leverage (K), trace (2), nused [Rayleigh, Love], flag, other) --
+    every array 0 where the flag is 1 or 2.  other: the same figures by another algorithm, numpy.linalg.pinv of the stacked
+    [G^; smooth L (+) smooth L; damp I; aniso (-I | I)], whose first K columns are N^-1 G^^T -- for the size of the rounding error; None where
+    the column is flagged.  n_override: a (2M, 2M) matrix in place of the assembled N (tests)."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64); love = np.asarray(love, bool)
+    K, M = S.shape
+    wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
+    used, _, _, G = _twin_data(obs, wt, pv, S, love)
+    out = dict(T=np.zeros((K, 2 * M)), R=np.zeros((2 * M, 2 * M)), measures=np.zeros((6, 2 * M)), pair=np.zeros((2, M)), leverage=np.zeros(K), trace=np.zeros(2),
+               nused=[int((used & ~love).sum()), int((used & love).sum())], flag=0, other=None)
+    if not used.any():
+        out["flag"] = 2
+        return out
+    lam, mu, gam = float(f(smooth)), float(f(damp)), float(f(aniso))
+    N, _ = _twin_radial_normal(G, used, love, np.zeros(K), lam * lam, mu * mu, gam * gam, np.zeros(M))
+    if n_override is not None:
+        N = np.array(n_override, np.float64)
+    factor = _twin_factor(N)
+    if factor is None:
+        out["flag"] = 1
+        return out
+    Gx = _radial_expand(G, love)
+    T = _twin_solve(*factor, Gx.T).T.copy()
+    T[~used] = 0.0
+    out.update(T=T, **_radial_resolution_measures(T, G, used, love, depz))
+    if n_override is None:
+        Lm = column_l(M); Z = np.zeros_like(Lm)
+        A = np.vstack([Gx, lam * np.hstack([Lm, Z]), lam * np.hstack([Z, Lm]), mu * np.eye(2 * M), gam * np.hstack([-np.eye(M), np.eye(M)])])
+        T2 = np.linalg.pinv(A)[:, :K].T.copy()
+        T2[~used] = 0.0
+        out["other"] = dict(T=T2, **_radial_resolution_measures(T2, G, used, love, depz))
+    return out
+
+
 # ---- the plan ----
 
 def slot_plan(c):
@@ -665,9 +762,10 @@ def check_lateral(radial=False, resolution=False):
                          (("--radial", "radial step") if radial else ("--resolution", "resolution")))
 
 
-def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral, radial_lateral_aniso):
+def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral, radial_lateral_aniso,
+                radial_resolution=False):
     """every precondition on the flags, in the order run() and main() both refuse in (ValueError), before the library is loaded.  aniso None:
-    not looked at; --lateral-tol and --lateral-maxit are looked at only with a coupling."""
+    not looked at; --lateral-tol and --lateral-maxit are looked at only with a coupling; --radial-resolution's come last."""
     with_cg = lateral is not None or radial_lateral is not None
     check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, lateral, lateral_tol if with_cg else None, lateral_maxit if with_cg else None, radial_lateral,
           radial_lateral_aniso)
@@ -676,6 +774,7 @@ def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, 
     if radial:
         check_radial(None, resolution)
     check_radial_lateral(radial_lateral, radial_lateral_aniso, radial, lateral, resolution)
+    check_radial_resolution(radial_resolution, radial, radial_lateral)
 
 
 def _iterate(eng, plan, iterations, step, entry, log, coupling):
@@ -966,16 +1065,148 @@ def run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, ou
     return out, path, fit
 
 
+# ---- the resolution of the radial step ----
+
+def check_radial_resolution(radial_resolution=False, radial=False, radial_lateral=None):
+    """what --radial-resolution asks of the other flags, before the library is loaded (ValueError)"""
+    if not radial_resolution:
+        return
+    if not radial:
+        raise ValueError("--radial-resolution needs --radial: it is the resolution of the radial step (--resolution is that of the isotropic one)")
+    if radial_lateral is not None:
+        raise ValueError("--radial-resolution and --radial-lateral exclude each other: the resolution of the laterally coupled system is not computed")
+
+
+def leak_share(m1_own, m1_cross):
+    """m1_cross / (m1_own + m1_cross): the share of a spike's answer that lies in the other model, 0 where the denominator is 0"""
+    own = np.asarray(m1_own, np.float64); cross = np.asarray(m1_cross, np.float64)
+    total = own + cross
+    return np.divide(cross, total, out=np.zeros(total.shape), where=total > 0)
+
+
+def radial_resolution_columns(res, vsv, vsh, sigma):
+    """The node figures of DepthRadialResolution.dat from columns_resolution_radial's result res, the models vsv, vsh ((nz, ...) with the
+    columns in res's order) and the data's standard deviation sigma (S, km/s).  Returns a dict of (nz - 1, columns) arrays: for q in v, h
+    rjj_q, length_q = sqrt(m2_own / m1_own), leak_q (leak_share), sd_q = S sqrt(var); r_aniso = (R_vv + R_hh - R_hv - R_vh) / 2 from R_jj
+    and R_cross; sd_diff = S sqrt(vard); sd_xi = 2 xi S sqrt(var_v / Vsv^2 + var_h / Vsh^2 - 2 cov / (Vsv Vsh)), the radicand clamped at 0
+    (0 where a velocity is 0); xi."""
+    m = np.asarray(res["measures"], np.float64)
+    M = m.shape[1] // 2
+    ncol = m.shape[2]
+    pair = np.asarray(res["pair"], np.float64)
+    v = np.asarray(vsv, np.float64).reshape(M + 1, ncol)[:M]; h = np.asarray(vsh, np.float64).reshape(M + 1, ncol)[:M]
+    S = float(sigma)
+    out = {}
+    for q, blk in (("v", slice(0, M)), ("h", slice(M, 2 * M))):
+        out["rjj_" + q] = m[0][blk]
+        out["length_" + q] = psf_length(m[1][blk], m[2][blk])
+        out["leak_" + q] = leak_share(m[1][blk], m[3][blk])
+        out["sd_" + q] = S * np.sqrt(m[5][blk])
+    out["r_aniso"] = 0.5 * (m[0][:M] + m[0][M:] - m[4][:M] - m[4][M:])
+    out["sd_diff"] = S * np.sqrt(pair[1])
+    xi = voigt_xi(v, h)[1]
+    ok = (v != 0) & (h != 0)
+    vs = np.where(ok, v, 1.0); hs = np.where(ok, h, 1.0)
+    rad = np.maximum(m[5][:M] / (vs * vs) + m[5][M:] / (hs * hs) - 2.0 * pair[0] / (vs * hs), 0.0)
+    out["sd_xi"] = np.where(ok, 2.0 * xi * S * np.sqrt(rad), 0.0)
+    out["xi"] = xi
+    return out
+
+
+RADIAL_RESOLUTION_NAMES = ("rjj_v", "length_v", "leak_v", "sd_v", "rjj_h", "length_h", "leak_h", "sd_h", "r_aniso", "sd_diff", "sd_xi")
+RADIAL_RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", *RADIAL_RESOLUTION_NAMES))
+
+
+def write_radial_resolution(path, c, res, vsv, vsh, sigma):
+    """<input>DepthRadialResolution.dat: radial_resolution_columns of every node above the bottom depth: depth slowest, then j, then i"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    cols = radial_resolution_columns(res, np.asarray(vsv).reshape(nz, ny * nx), np.asarray(vsh).reshape(nz, ny * nx), sigma)
+    rows = []
+    for k in range(nz - 1):
+        for j in range(ny):
+            for i in range(nx):
+                lon, lat = _lonlat(c, i - 1, j - 1)
+                row = dict(lon=float(lon), lat=float(lat), depth=float(c["depz"][k]))
+                row.update((name, cols[name][k, j * nx + i]) for name in RADIAL_RESOLUTION_NAMES)
+                rows.append(row)
+    io.write_table(path, RADIAL_RESOLUTION_TABLE, rows)
+
+
+def read_radial_resolution(path):
+    return io.read_table(path, RADIAL_RESOLUTION_TABLE)
+
+
+def write_radial_leverage(path, c, leverage):
+    """<input>DepthRadialLeverage.dat: leverage (nmaps, ny * nx) of columns_resolution_radial, in DepthLeverage.dat's layout"""
+    write_leverage(path, c, leverage)
+
+
+def read_radial_leverage(path):
+    return io.read_table(path, LEVERAGE_TABLE)
+
+
+def radial_resolution_summary(c, res, vsv, vsh, sigma):
+    """what the log says of columns_resolution_radial's result: dict(flagged1, flagged2, columns (interior and not flagged), trace_v, trace_h
+    ((median, min, max) of each block's trace over them), leak_v, leak_h (the median leak share of each block's nodes over them),
+    significant: how many of their nodes have |xi - 1| > 2 sd_xi, nodes: how many nodes they have)"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+    flag = np.asarray(res["flag"]).reshape(ny * nx)
+    ok = inner.ravel() & (flag == 0)
+    out = dict(flagged1=int((flag == 1).sum()), flagged2=int(((flag == 2) & inner.ravel()).sum()), columns=int(ok.sum()), trace_v=None, trace_h=None, leak_v=None,
+               leak_h=None, significant=0, nodes=int(ok.sum()) * (nz - 1))
+    if ok.any():
+        cols = radial_resolution_columns(res, np.asarray(vsv).reshape(nz, ny * nx), np.asarray(vsh).reshape(nz, ny * nx), sigma)
+        for q, name in enumerate(("v", "h")):
+            tr = np.asarray(res["trace"])[q][ok]
+            out["trace_" + name] = (float(np.median(tr)), float(tr.min()), float(tr.max()))
+            out["leak_" + name] = float(np.median(cols["leak_" + name][:, ok]))
+        out["significant"] = int((np.abs(cols["xi"][:, ok] - 1.0) > 2.0 * cols["sd_xi"][:, ok]).sum())
+    return out
+
+
+def resolve_radial(eng, c, plan, obs, wt, smooth, damp, aniso, sigma, out_dir, log=print):
+    """--radial-resolution on an engine whose radial stage holds the final models: the runs of plan once more, columns_resolution_radial, the
+    two files, the log.  Returns dict(resolution: the call's result, sigma, summary, resolution_path, leverage_path)."""
+    for wave, kind, t, first in plan:
+        eng.dispersion_run(wave, kind, t, True, first, first)
+    res = eng.columns_resolution_radial(obs, wt, smooth, damp, aniso)
+    vsv, vsh = eng.dispersion_get_model_radial()
+    rpath = os.path.join(out_dir, "DSurfTomo.inDepthRadialResolution.dat")
+    lpath = os.path.join(out_dir, "DSurfTomo.inDepthRadialLeverage.dat")
+    write_radial_resolution(rpath, c, res, vsv, vsh, sigma)
+    write_radial_leverage(lpath, c, res["leverage"])
+    sm = radial_resolution_summary(c, res, vsv, vsh, sigma)
+    for line in radial_resolution_log(c, sm):
+        log(line)
+    log(" depth radial resolution: written to %s (sd for a data standard deviation of %.6f km/s), the leverages to %s" % (rpath, sigma, lpath))
+    return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
+
+
+def radial_resolution_log(c, sm):
+    """the log's lines for radial_resolution_summary's dict"""
+    lines = [" depth radial resolution: %d columns resolved, %d flagged (%d not positive definite, %d without data)" %
+             (sm["columns"], sm["flagged1"] + sm["flagged2"], sm["flagged1"], sm["flagged2"])]
+    if sm["trace_v"] is not None:
+        for name, q in (("Vsv", "v"), ("Vsh", "h")):
+            lines.append(" depth radial resolution: trace of the %s block of R per column median %.4f, range %.4f to %.4f, of %d unknowns; median leak share %.4f" %
+                         (name, sm["trace_" + q][0], sm["trace_" + q][1], sm["trace_" + q][2], c["nz"] - 1, sm["leak_" + q]))
+        lines.append(" depth radial resolution: |xi - 1| > 2 sd_xi at %d of %d unflagged nodes" % (sm["significant"], sm["nodes"]))
+    return lines
+
+
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
         log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
-        lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None):
+        lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
     None): the loop steps with columns_step_lateral; the files are the same two.  With radial and radial_lateral (not None): the radial loop
-    steps with columns_step_radial_lateral, radial_lateral_aniso (None: radial_lateral) the weight on Vsh - Vsv; the files are --radial's."""
+    steps with columns_step_radial_lateral, radial_lateral_aniso (None: radial_lateral) the weight on Vsh - Vsv; the files are --radial's.
+    With radial and radial_resolution: after the loop resolve_radial's entries are added to the first item (DepthRadialResolution.dat and
+    DepthRadialLeverage.dat beside --radial's files); sigma as with resolution."""
     check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral,
-                radial_lateral_aniso)
+                radial_lateral_aniso, radial_resolution)
     c = io.load(directory)
     if radial:
         check_radial(c)
@@ -990,7 +1221,12 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     eng = Engine(0)
     if radial:
         try:
-            return run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log, radial_lateral, radial_lateral_aniso, lateral_tol, lateral_maxit)
+            result = run_radial(eng, c, plan, obs, wt, iterations, smooth, damp, aniso, dvmax, out_dir, log, radial_lateral, radial_lateral_aniso, lateral_tol, lateral_maxit)
+            if radial_resolution:
+                rms = result[0]["history"][-1]["rms"]
+                log(" depth radial resolution: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
+                result[0].update(resolve_radial(eng, c, plan, obs, wt, smooth, damp, aniso, rms if sigma is None else sigma, out_dir, log))
+            return result
         finally:
             eng.close()
     try:
@@ -1030,6 +1266,7 @@ def parser():
     ap.add_argument("--lateral-maxit", type=int, default=DEFAULT_LATERAL_MAXIT, metavar="N", help="with --lateral: most conjugate-gradient iterations per step (default %d)" % DEFAULT_LATERAL_MAXIT)
     ap.add_argument("--radial-lateral", type=float, default=None, metavar="W", help="with --radial: couple neighbouring columns, weight of the penalty on the differences of Vsv and of Vsh, >= 0 (default: columns alone); --lateral-tol and --lateral-maxit apply")
     ap.add_argument("--radial-lateral-aniso", type=float, default=None, metavar="A", help="with --radial-lateral: weight of the penalty on the differences of Vsh - Vsv between neighbours, >= 0 (default: W)")
+    ap.add_argument("--radial-resolution", action="store_true", help="with --radial: after the last step write the resolution measures of Vsv, Vsh and xi and the leverages of the final models (--sigma applies)")
     return ap
 
 
@@ -1038,12 +1275,13 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         check_flags(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.radial, a.resolution, a.lateral, a.lateral_tol, a.lateral_maxit,
-                    a.radial_lateral, a.radial_lateral_aniso)
+                    a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
     run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso,
-        lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso)
+        lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso,
+        radial_resolution=a.radial_resolution)
     return 0
 
 

@@ -108,6 +108,7 @@ def declare_solvers(L):
     L.dsa_dispersion_begin_radial.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _i32]
     L.dsa_columns_step_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [_vp] * 4
     L.dsa_dispersion_get_model_radial.argtypes = [_vp, _vp, _vp]
+    L.dsa_columns_resolution_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [_vp] * 7
     L.dsa_columns_step_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_step_radial_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 8 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
@@ -497,6 +498,24 @@ class Engine:
         self._check(self._L.dsa_columns_step_radial(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(aniso), float(dvmax), float(minvel), float(maxvel),
                                                     _p(dv), _p(nused), _p(chi2), _p(flag)))
         return dict(dv_sv=dv[0], dv_sh=dv[1], nused=nused, chi2=chi2, flag=flag)
+
+    def columns_resolution_radial(self, obs, wt, smooth, damp, aniso, full=False):
+        """dsa_columns_resolution_radial on the state columns_step_radial needs, which it leaves as it is: obs and wt as columns_step's.
+        Returns dict(measures (6, 2 (nz - 1), ny * nx): R_jj, m1_own, m2_own, m1_cross, R_cross, var of the Vsv block's unknowns, then the
+        Vsh block's; pair (2, nz - 1, ny * nx): cov, vard; leverage (nmaps, ny * nx); trace (2, ny * nx): the Vsv block's, the Vsh block's;
+        nused (2, ny * nx) and flag (ny * nx) int32; and with full=True R (2 (nz - 1), 2 (nz - 1), ny * nx), R[i, j] the response of unknown
+        i to a spike in unknown j), all fp64.  ValueError as columns_step."""
+        nmaps, obs, wt = self._columns_in("columns_resolution_radial", obs, wt)[:3]
+        nx, ny, nz = self._disp
+        ncol, n2 = nx * ny, 2 * (nz - 1)
+        out = dict(measures=np.zeros((6, n2, ncol)), pair=np.zeros((2, nz - 1, ncol)), leverage=np.zeros((nmaps, ncol)), trace=np.zeros((2, ncol)),
+                   nused=np.zeros((2, ncol), np.int32), flag=np.zeros(ncol, np.int32))
+        if full:
+            out["R"] = np.zeros((n2, n2, ncol))
+        self._check(self._L.dsa_columns_resolution_radial(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(aniso), _p(out["measures"]),
+                                                          _p(out["pair"]), _p(out["leverage"]), _p(out["trace"]), _p(out["nused"]), _p(out["flag"]),
+                                                          _p(out["R"]) if full else None))
+        return out
 
     def columns_step_lateral(self, obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
         """dsa_columns_step_lateral on the model of dispersion_begin: columns_step with the interior columns tied to their neighbours by the

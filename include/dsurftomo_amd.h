@@ -549,6 +549,32 @@ int dsa_columns_step_radial_lateral(dsa_engine* e, int nmaps, const float* obs, 
                                     float lateral_aniso, float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused,
                                     double* chi2, int* flag, double* info);
 
+/* dsa_columns_resolution_radial: how far the radial step's answer can be trusted, per interior column, from the 2M x 2M normal matrix
+ * dsa_columns_step_radial factors (extension).  The state and obs, wt, smooth, damp, aniso are dsa_columns_step_radial's, with
+ * its rules, messages and order of refusals; of obs only the sign is used.  Per column, M = nz-1, unknown i < M in the Vsv block and i >= M in
+ * the Vsh block at depth i mod M: T (nmaps x 2M) has in row k the solution of N t = g^_k for a used datum (g_k in the block of its wave type,
+ * 0 elsewhere; the step's substitutions) and zeros for any other; R = T^T G^, its column j the answer to a spike in unknown j.  Everything
+ * fp64, every sum sequential from 0.0 over the used data ascending (csrc/column_radial_resolution.h).
+ *   measures  6*2(nz-1)*nx*ny doubles, (measure, unknown, column): R_jj;  m1_own = sum R_ij^2 over i in j's block;  m2_own = sum R_ij^2
+ *             (depz_i - depz_j)^2 over that block -- the vertical length of the PSF is sqrt(m2_own / m1_own);  m1_cross = sum R_ij^2 over the
+ *             other block, the energy a spike in j leaks into the other model;  R_cross, the entry of column j at the co-located unknown of
+ *             the other block;  var_j = sum_k T_kj^2
+ *   pair      2*(nz-1)*nx*ny: cov_l = sum_k T_kl T_k,M+l;  vard_l = sum_k (T_k,M+l - T_kl)^2, the variance of dVsh - dVsv at depth l -- both
+ *             for unit variance of the weighted data
+ *   leverage  nmaps*nx*ny: h_k = sum_l g_kl T_k,l in the datum's own block; 0 for a datum not used
+ *   trace     2*nx*ny: sum_j R_jj over the Vsv block, then over the Vsh block;  nused 2*nx*ny, flag nx*ny: as dsa_columns_step_radial's
+ *   R         NULL, or 2(nz-1)*2(nz-1)*nx*ny doubles: R_ij at (i*2(nz-1) + j)*nx*ny + column.  NULL skips the store and changes no other bit.
+ * A column with flag 1 or 2 and the outer ring of columns have 0.0 everywhere; a column with one wave type unused still resolves.  At
+ * aniso = 0 the own-block measures, var and the leverages of each block have the bits of dsa_columns_resolution on that model with the other
+ * wave type's weights 0, and m1_cross, R_cross and cov are zeros.
+ * Nothing is changed: both models, the marks and the Frechet rows' sensitivities stay, so a dsa_columns_step_radial after the call gives the
+ * bits it would have given without it; after a step the call is DSA_ERR_STATE until the runs are repeated.
+ * Errors, all but the last found before the device is touched: as dsa_columns_step_radial, in its order (DSA_ERR_STATE on a stage that is not
+ * radial); DSA_ERR_ARGUMENT for a NULL measures, pair, leverage, trace, nused or flag; DSA_ERR_DEVICE when a column's work arrays (158 712
+ * bytes at nz = 64 with 60 maps) exceed the LDS a block of the device may have or the device refuses that size. */
+int dsa_columns_resolution_radial(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso,
+                                  double* measures, double* pair, double* leverage, double* trace, int* nused, int* flag, double* R);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);

@@ -23,7 +23,17 @@ The radial lateral leg: dsa_columns_step_radial_lateral o
 above Vsv) at (lateral, lateral_aniso) = (0.2, 0.2), (0.3, 0.6) and (0, 1) (tol 1e-8), timed as the lateral leg is, next to
 dsa_columns_step_radial on the same state.
 
-    python tools/depth_rate.py [repeats] [lateral | radial-lateral]      (needs the GPU; with a name: that leg alone)
+The radial resolution's leg: dsa_columns_resolution_radial on the radial leg's stage (the four-wave-type plan, Vsh 3 %
+above Vsv; K = 26, 2M = 16) after one set of runs, without and with the full R, and at the stage's limits on the 5 x 5 grid (nz = 64,
+K = 60: the one launch that asks for 158 712 bytes of LDS) -- the wall time of the whole call, `repeats` timed calls after a warm-up one.
+On each stage one dsa_columns_step_radial per timed call of the first series (after fresh runs) and, on a plain stage holding the same
+model, as many dsa_columns_resolution calls follow, so that one kernel trace of the leg holds k_column_resolution_radial,
+k_column_step_radial and k_column_resolution side by side:
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/depth_rate.py 9 radial-resolution
+    python tools/depth_rate.py trace-medians DIR/.../*_kernel_trace.csv
+prints per kernel and grid size the median duration of its launches, the first one (the warm-up) left out.
+
+    python tools/depth_rate.py [repeats] [lateral | radial-lateral | radial-resolution]      (needs the GPU; with a name: that leg alone)
 """
 import os
 import sys
@@ -38,7 +48,24 @@ from dsurftomo_amd import depth, io                  # noqa: E402
 from dsurftomo_amd.engine import Engine             # noqa: E402
 
 
+def trace_medians(path):
+    """per (kernel, grid size) of a rocprofv3 kernel trace (csv): the launches and the median of their durations in us without the first"""
+    import csv
+    rows = {}
+    with open(path, newline="") as fh:
+        for r in csv.DictReader(fh):
+            name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].split("::")[-1]
+            rows.setdefault((name, r.get("Grid_Size_X", r.get("Grid_Size", "?"))), []).append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+    for (name, grid), spans in sorted(rows.items()):
+        d = [1e-3 * (b - a) for a, b in sorted(spans)]
+        rest = d[1:] if len(d) > 1 else d
+        print("%-40s grid %-8s %3d launches, median without the first %.1f us (first %.1f, min %.1f, max %.1f)" % (name, grid, len(d), np.median(rest), d[0], min(rest), max(rest)))
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "trace-medians":
+        trace_medians(sys.argv[2])
+        return
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 9
     c = io.load()
     t = np.asarray(c["tRc"], np.float64)
@@ -52,6 +79,10 @@ def main():
         return
     if "radial-lateral" in sys.argv[2:]:
         radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
+        e.close()
+        return
+    if "radial-resolution" in sys.argv[2:]:
+        radial_resolution_legs(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
         e.close()
         return
     for name, case in cases:
@@ -76,16 +107,68 @@ def main():
               (name, c["nx"], c["ny"], c["nz"], kmax, len(plan), repeats, np.median(runs), np.median(dev), np.median(step), " ".join("%.3f" % s for s in step)))
     radial_leg(e, repeats, "radial, four types", vel, c["depz"], c["minthk"], depth.slot_plan(cases[1][1]), kmax, float(c["minvel"]), float(c["maxvel"]))
     resolution_leg(e, repeats, "the example's grid", vel, c["depz"], c["minthk"], depth.slot_plan(c), kmax)
+    limits, depz, minthk, lplan, lk = limits_case()
+    resolution_leg(e, repeats, "the limits", limits, depz, minthk, lplan, lk)
+    radial_leg(e, 1, "radial, the limits", limits, depz, minthk, lplan, lk, 0.5, 6.0)
+    lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+    radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
+    radial_resolution_legs(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
+    e.close()
+
+
+def limits_case():
+    """the stage's limits on a 5 x 5 grid: (model (64, 5, 5), depz, minthk, plan of 15 phase and 15 group periods of each wave type, 60)"""
     nz = 64
     k = np.arange(nz)[:, None, None]; i = np.arange(5)[None, None, :]; j = np.arange(5)[None, :, None]
     limits = np.ascontiguousarray((2.6 + 1.9 * k / (nz - 1)) * (1.0 + 0.05 * np.sin(0.7 * i + 0.3 * k) * np.cos(0.5 * j)), np.float32)
     depz = np.concatenate([[0.0], np.cumsum(np.round(2.0 + 4.0 * np.arange(nz - 1) / (nz - 2)))]).astype(np.float32)
     phase, group = np.linspace(3.0, 45.0, 15), np.linspace(4.0, 46.0, 15)
-    resolution_leg(e, repeats, "the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60)
-    radial_leg(e, 1, "radial, the limits", limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60, 0.5, 6.0)
-    lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
-    radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
-    e.close()
+    return limits, depz, 2.0, [(2, 0, phase, 0), (2, 1, group, 15), (1, 0, phase, 30), (1, 1, group, 45)], 60
+
+
+def radial_resolution_legs(e, repeats, vel, c, plan, kmax):
+    radial_resolution_leg(e, repeats, "the example's grid", vel, c["depz"], c["minthk"], plan, kmax, float(c["minvel"]), float(c["maxvel"]))
+    limits, depz, minthk, lplan, lk = limits_case()
+    radial_resolution_leg(e, repeats, "the limits", limits, depz, minthk, lplan, lk, 0.5, 6.0)
+
+
+def radial_resolution_leg(e, repeats, name, vel, depz, minthk, plan, kmax, minvel, maxvel):
+    nz, ny, nx = vel.shape
+    vsh = vel.copy()
+    vsh[:-1] = vsh[:-1] * np.float32(1.03)
+    args = (depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP, depth.DEFAULT_ANISO)
+
+    def runs():
+        for wave, kind, tt, first in plan:
+            e.dispersion_run(wave, kind, tt, True, first, first)
+
+    e.dispersion_begin_radial(vel, vsh, depz, minthk, kmax, kmax)
+    t0 = time.perf_counter()
+    runs()
+    t1 = time.perf_counter()
+    pv = e.dispersion_fetch(0, kmax)
+    obs = np.where(pv > 0, pv * 1.02, 0.0).astype(np.float32)
+    for full in (False, True):
+        wall = []
+        for it in range(repeats + 1):
+            t2 = time.perf_counter()
+            out = e.columns_resolution_radial(obs, None, *args, full)
+            if it:
+                wall.append(1e3 * (time.perf_counter() - t2))
+        ok = out["flag"].reshape(ny, nx)[1:-1, 1:-1] == 0
+        tr = out["trace"].sum(axis=0).reshape(ny, nx)[1:-1, 1:-1][ok]
+        print("%-20s %d x %d x %d, K = %d (runs %.1f ms): columns_resolution_radial %s, median of %d -- %.3f ms wall; %d of %d columns resolved, sum of the traces %.3f to %.3f; all calls: %s" %
+              (name, nx, ny, nz, kmax, 1e3 * (t1 - t0), "with the full R" if full else "without R", repeats, np.median(wall), int(ok.sum()), ok.size, tr.min(), tr.max(),
+               " ".join("%.3f" % w for w in wall)))
+    # the neighbours, for the kernel trace: the radial step on this stage, the plain resolution on a plain stage holding the Vsv model
+    for it in range(repeats + 1):
+        if it:
+            runs()
+        e.columns_step_radial(obs, None, *args, 1e-4, minvel, maxvel)
+    e.dispersion_begin(vel, depz, minthk, kmax, kmax)
+    runs()
+    for it in range(repeats + 1):
+        e.columns_resolution(obs, None, depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP)
 
 
 def radial_lateral_leg(e, repeats, vel, c, plan, kmax):
