@@ -9,6 +9,7 @@
 // k_lateral_* (DESIGN.md section 24): the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
 // the same loop and kernels on the radial step's 2M unknowns per column; only k_radial_lateral_setup and
 // k_radial_lateral_start are that system's own.
+// k_latres_* (DESIGN.md section 27): the resolution of the laterally coupled step, a batch of section 24's solves, one lane per member.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -16,6 +17,7 @@
 #include "column_radial_resolution.h"
 #include "column_lateral.h"
 #include "column_radial_lateral.h"
+#include "column_lateral_resolution.h"
 
 namespace dsa {
 
@@ -256,6 +258,61 @@ __global__ void __launch_bounds__(64) k_lateral_finish(LateralWs ws, int Mb, flo
     lateral_finish_blocks(ws, (int)blockIdx.x, Mb, dvmax, minvel, maxvel, vels0, vels1, ncol, dv, dv + (long long)Mb * ncol, ncol, (int)threadIdx.x, 64);
 }
 
+// The resolution of the laterally coupled step: column_lateral_resolution.h's batch of members.  Block (b, g) is one
+// wavefront: interior column b, the 64 members of lane group g, lane = member.  N_b, the factor and d_b (or H_b) are staged in LDS and read as
+// broadcasts; every lane runs its member's chains on its own operand vectors in LDS (element l of lane t at l * 64 + t: consecutive doubles
+// across the lanes, every bank once); the member vectors in global memory are member-fastest, so a wavefront's loads and stores of one
+// element are 512 contiguous bytes.  latres_work_doubles(M) doubles of dynamic LDS: 8.8 KB at M = 8, 97 272 B at M = 63, which the launcher
+// has to ask for.  No kernel waits for another block: what a column needs of its neighbours was written by an earlier launch.
+// k_latres_gram: H_b = G_b^T G_b of every active column, after k_lateral_setup, in k_column_step's work arrays.
+__global__ void __launch_bounds__(64) k_latres_gram(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                   const double* __restrict__ pv, const double* __restrict__ S, LateralWs ws, double* __restrict__ H)
+{
+    extern __shared__ double column_lds[];
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
+    ColumnIn in;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.S = S + c;
+    latres_gram(in, column_work(column_lds, M, K), ws, (int)blockIdx.x, H, (int)threadIdx.x, 64, BlockBarrier());
+}
+
+__device__ __forceinline__ bool latres_past(const LatResBatch& B)
+{
+    return (int)blockIdx.x >= B.ws.nvx * B.ws.nvy || ((int)blockIdx.y + 1) * kLatResGroup > B.Sc;
+}
+
+// phase: 0 the right-hand sides, 1 x0 and the figures of rz0, 2 r0, z0 and the figures of the first rz, 3 and 4 the two halves of an
+// iteration, 5 u and the figures of the measures
+template <int Phase>
+__global__ void __launch_bounds__(64) k_latres_phase(LatResBatch B)
+{
+    extern __shared__ double column_lds[];
+    if (latres_past(B)) return;
+    const LatResWork w = latres_work(column_lds, B.ws.M);
+    const int b = (int)blockIdx.x, g = (int)blockIdx.y, lane = (int)threadIdx.x;
+    if (Phase == 0) latres_form(B, b, g, w, lane, 64, BlockBarrier());
+    else if (Phase == 1) latres_start(B, b, g, w, lane, 64, BlockBarrier());
+    else if (Phase == 2) latres_residual(B, b, g, w, lane, 64, BlockBarrier());
+    else if (Phase == 3) latres_direction(B, b, g, w, lane, 64, BlockBarrier());
+    else if (Phase == 4) latres_update(B, b, g, w, lane, 64, BlockBarrier());
+    else latres_measure(B, b, g, w, lane, 64, BlockBarrier());
+}
+
+// the global sums and the scalars, one lane per member over coalesced reads of the columns' figures
+__global__ void __launch_bounds__(64) k_latres_reduce(LatResBatch B, int what, double tol, int maxit)
+{
+    if (((int)blockIdx.x + 1) * kLatResGroup > B.Sc) return;
+    latres_reduce(B, (int)blockIdx.x, what, tol, maxit, (int)threadIdx.x, 64);
+}
+
+__global__ void __launch_bounds__(64) k_latres_measures(LatResBatch B, double* __restrict__ measures)
+{
+    if (((int)blockIdx.x + 1) * kLatResGroup > B.Sc) return;
+    latres_measures(B, (int)blockIdx.x, measures, (int)threadIdx.x, 64);
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -407,6 +464,86 @@ void launch_coupled_finish(const CoupledSystem& s, float dvmax, float minvel, fl
 {
     if (coupled_empty(s)) return;
     hipLaunchKernelGGL(k_lateral_finish, coupled_grid(s), dim3(64), 0, stream, coupled_view(s), s.nz - 1, dvmax, minvel, maxvel, d_vels0, d_vels1, d_dv);
+}
+
+// ---- the resolution of the laterally coupled step ----
+
+size_t latres_lds_bytes(int nz) { return latres_work_doubles(nz - 1) * sizeof(double); }
+size_t latres_gram_bytes(int nx, int ny, int nz) { return (size_t)(nx - 2) * (ny - 2) * column_tri_size(nz - 1) * sizeof(double); }
+size_t latres_bytes_per_member(int nx, int ny, int nz) { return latres_member_bytes(nx - 2, ny - 2, nz - 1); }
+size_t latres_chunk_bytes(int nx, int ny, int nz, int Sc) { return latres_batch_doubles(nx - 2, ny - 2, nz - 1, Sc) * sizeof(double); }
+
+static LatResBatch latres_view(const LatResSystem& r)
+{
+    return latres_batch(coupled_iso(r.s), r.d_H, r.d_depz, r.d_models, r.d_batch, r.Sc);
+}
+static dim3 latres_grid(const LatResSystem& r) { return dim3((unsigned)((r.s.nx - 2) * (r.s.ny - 2)), (unsigned)(r.Sc / kLatResGroup)); }
+
+int* latres_ints(const LatResSystem& r) { return latres_view(r).ic; }
+int* latres_kinds(const LatResSystem& r) { return latres_view(r).kind; }
+const double* latres_scalars(const LatResSystem& r) { return latres_view(r).sc; }
+const double* latres_u(const LatResSystem& r) { return latres_view(r).q; }
+
+// column_lds_opt_in's return values for the six kernels of a phase: nothing may be launched unless 0
+int latres_prepare(int device, int nz, int* limit_out)
+{
+    const size_t lds = latres_lds_bytes(nz);
+    const void* kernels[6] = { reinterpret_cast<const void*>(&k_latres_phase<0>), reinterpret_cast<const void*>(&k_latres_phase<1>),
+                               reinterpret_cast<const void*>(&k_latres_phase<2>), reinterpret_cast<const void*>(&k_latres_phase<3>),
+                               reinterpret_cast<const void*>(&k_latres_phase<4>), reinterpret_cast<const void*>(&k_latres_phase<5>) };
+    for (const void* k : kernels)
+        if (int rc = column_lds_opt_in(device, k, lds, limit_out)) return rc;
+    return 0;
+}
+
+// section 24's set-up kernel as it is, then H
+void launch_latres_setup(const CoupledSystem& s, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                         double* d_H, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream)
+{
+    if (coupled_empty(s) || K < 1) return;
+    const size_t lds = column_work_doubles(s.nz - 1, K) * sizeof(double);
+    hipLaunchKernelGGL(k_lateral_setup, coupled_grid(s), dim3(64), lds, stream, s.nx, s.ny, s.nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, coupled_iso(s), d_nused,
+                       d_chi2, d_flag);
+    hipLaunchKernelGGL(k_latres_gram, coupled_grid(s), dim3(64), lds, stream, s.nx, s.ny, s.nz, K, d_obs, d_wt, d_pv, d_S, coupled_iso(s), d_H);
+}
+
+template <int Phase>
+static void latres_phase(const LatResSystem& r, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_latres_phase<Phase>, latres_grid(r), dim3(64), latres_lds_bytes(r.s.nz), stream, latres_view(r));
+}
+static void latres_sums(const LatResSystem& r, int what, double tol, int maxit, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_latres_reduce, dim3((unsigned)(r.Sc / kLatResGroup)), dim3(64), 0, stream, latres_view(r), what, tol, maxit);
+}
+
+// the right-hand sides, x0, the first residual and the criterion at iteration 0 (five launches)
+void launch_latres_first(const LatResSystem& r, double tol, int maxit, hipStream_t stream)
+{
+    if (coupled_empty(r.s)) return;
+    latres_phase<0>(r, stream);
+    latres_phase<1>(r, stream);
+    latres_sums(r, kLatSumRz0, tol, maxit, stream);
+    latres_phase<2>(r, stream);
+    latres_sums(r, kLatSumFirst, tol, maxit, stream);
+}
+
+// one iteration of every member that is not done: four launches
+void launch_latres_iteration(const LatResSystem& r, double tol, int maxit, hipStream_t stream)
+{
+    if (coupled_empty(r.s)) return;
+    latres_phase<3>(r, stream);
+    latres_sums(r, kLatSumPq, tol, maxit, stream);
+    latres_phase<4>(r, stream);
+    latres_sums(r, kLatSumRz, tol, maxit, stream);
+}
+
+// u and the measures (Sc, 7)
+void launch_latres_measures(const LatResSystem& r, double* d_measures, hipStream_t stream)
+{
+    if (coupled_empty(r.s)) return;
+    latres_phase<5>(r, stream);
+    hipLaunchKernelGGL(k_latres_measures, dim3((unsigned)(r.Sc / kLatResGroup)), dim3(64), 0, stream, latres_view(r), d_measures);
 }
 
 }  // namespace dsa

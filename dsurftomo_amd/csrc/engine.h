@@ -347,6 +347,14 @@ struct Engine {
     // dsa_columns_step_radial's state, arguments and outputs, the loop, the poll and the workspace (2 (nz - 1) unknowns per column) of the lateral step
     int columns_step_radial_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral, float lateral_aniso,
                                     float dvmax, float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
+    // resolution of the laterally coupled step (dsa_columns_resolution_lateral, k_latres_*): reads what
+    // dsa_columns_step_lateral reads, changes nothing.  col_lat holds the set-up, col_latH the columns' G^T G, col_latB one chunk of members,
+    // col_latM the test models.  A chunk is at most latres_default_cap bytes, or the memory budget where that is smaller.
+    OwnedBuf<double> col_latH, col_latB, col_latM;
+    static constexpr size_t latres_default_cap = (size_t)1 << 30;
+    int columns_resolution_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, double tol, int maxit, int nmembers,
+                                   const int* kind, const int* index, const double* models, int nrows, double* measures, double* info, double* full, int* nused,
+                                   int* flag);
 
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;

@@ -740,6 +740,115 @@ int Engine::columns_step_radial_lateral(int nmaps_in, const float* obs, const fl
     return columns_stage_out(2, dv, nused, chi2, flag, &s, info);
 }
 
+// dsa_columns_resolution_lateral: point-spread functions, rows of the averaging kernel, variances and test models of
+// the laterally coupled step, column_lateral_resolution.h's batch of section 24's solves.  The state and argument rules are columns_front's,
+// then columns_coupled_front's, then this call's own; everything is checked before the device is touched, except the LDS of the batched
+// kernels (DSA_ERR_DEVICE before anything is launched).  The stage is read only, as dsa_columns_resolution's.  The members are solved in
+// chunks of whole lane groups of 64: as many as fit the smaller of the memory budget (where one is set; the chunk alone against the whole
+// of it, as the coupled workspace) and latres_default_cap.  A member's arithmetic is its own, so the chunking cannot change a bit.
+int Engine::columns_resolution_lateral(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, float lateral, double tol, int maxit, int nmembers,
+                                       const int* kind, const int* index, const double* models, int nrows, double* measures, double* info, double* full, int* nused,
+                                       int* flag)
+{
+    const char* who = "columns_resolution_lateral";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f)) return rc;
+    if (int rc = columns_coupled_front(who, 1, lateral, 0.0f, tol, maxit)) return rc;
+    const int K = disp_nmaps, M = disp_nz - 1, nint = (disp_nx - 2) * (disp_ny - 2);
+    const size_t ncol = (size_t)disp_nx * disp_ny;
+    if (nmembers < 1) { fail(DSA_ERR_ARGUMENT, "%s: nmembers %d must be at least 1", who, nmembers); return DSA_ERR_ARGUMENT; }
+    if (!kind || !index || !measures || !info || !nused || !flag) { fail(DSA_ERR_ARGUMENT, "%s: kind, index, measures, info, nused and flag are required", who); return DSA_ERR_ARGUMENT; }
+    bool rows_used = false;
+    for (int s = 0; s < nmembers; ++s) {
+        if (kind[s] < 0 || kind[s] > 3) { fail(DSA_ERR_ARGUMENT, "%s: kind[%d] = %d must be 0 .. 3", who, s, kind[s]); return DSA_ERR_ARGUMENT; }
+        rows_used = rows_used || kind[s] >= 2;
+    }
+    if (rows_used && (!models || nrows < 1)) { fail(DSA_ERR_ARGUMENT, "%s: models is required by the members of kind 2 and 3", who); return DSA_ERR_ARGUMENT; }
+    for (int s = 0; s < nmembers; ++s) {
+        const long long limit = kind[s] >= 2 ? (long long)nrows : (long long)nint * M;
+        if (index[s] < 0 || index[s] >= limit) { fail(DSA_ERR_ARGUMENT, "%s: index[%d] = %d of kind %d must be in 0 .. %lld", who, s, index[s], kind[s], limit - 1); return DSA_ERR_ARGUMENT; }
+    }
+    if (rows_used) {
+        const size_t nm = (size_t)nrows * M * nint;
+        for (size_t q = 0; q < nm; ++q)
+            if (!std::isfinite(models[q])) { fail(DSA_ERR_ARGUMENT, "%s: models[%zu] is not finite", who, q); return DSA_ERR_ARGUMENT; }
+    }
+    const size_t per_member = latres_bytes_per_member(disp_nx, disp_ny, disp_nz);
+    const size_t room = mem_budget && mem_budget < latres_default_cap ? mem_budget : latres_default_cap;
+    const size_t groups_fit = room / (per_member * 64);
+    if (groups_fit == 0) {
+        fail(DSA_ERR_CAPACITY, "%s: one group of 64 members of %d x %d columns of %d unknowns needs %zu bytes, %zu are allowed (memory budget %zu, default cap %zu)", who,
+             disp_nx - 2, disp_ny - 2, M, per_member * 64, room, mem_budget, (size_t)latres_default_cap);
+        return DSA_ERR_CAPACITY;
+    }
+    const int all = (nmembers + 63) / 64 * 64;
+    const int chunk = (size_t)all / 64 <= groups_fit ? all : (int)groups_fit * 64;
+    HIP_TRY(this, hipSetDevice(device));
+    int limit = 0;
+    if (int rc = latres_prepare(device, disp_nz, &limit)) return columns_lds_refusal(who, rc, M, latres_lds_bytes(disp_nz), limit);
+    if (int rc = columns_stage_in(1, obs, wt, false)) return rc;
+    if (ensure(col_lat, coupled_ws_bytes(1, disp_nx, disp_ny, disp_nz) / sizeof(double)) || ensure(col_latH, latres_gram_bytes(disp_nx, disp_ny, disp_nz) / sizeof(double)) ||
+        ensure(col_latB, latres_chunk_bytes(disp_nx, disp_ny, disp_nz, chunk) / sizeof(double)) || ensure(col_meas, (size_t)chunk * 7) || ensure(col_depz, (size_t)disp_nz) ||
+        (rows_used && ensure(col_latM, (size_t)nrows * M * nint)) || ensure(col_nused, ncol) || ensure(col_chi2, ncol) || ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_depz.p, h_depz.data(), (size_t)disp_nz * 4, hipMemcpyHostToDevice, stream));
+    if (rows_used) HIP_TRY(this, hipMemcpyAsync(col_latM.p, models, (size_t)nrows * M * nint * 8, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernels run on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi2.p, 0, ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    const CoupledSystem s = { 1, disp_nx, disp_ny, disp_nz, lateral, 0.0f, col_lat.p };
+    launch_latres_setup(s, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, col_latH.p, col_nused.p, col_chi2.p, col_flag.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    const bool edges = coupled_edges(s);
+    std::vector<int> ki, ints;
+    std::vector<double> sc, u;
+    for (int first = 0; first < nmembers; first += chunk) {
+        const int count = std::min(chunk, nmembers - first), Sc = (count + 63) / 64 * 64;
+        const LatResSystem r = { s, col_latH.p, col_depz.p, rows_used ? col_latM.p : nullptr, col_latB.p, Sc };
+        ki.assign(2 * (size_t)Sc, -1);
+        for (int q = 0; q < count; ++q) { ki[(size_t)q] = kind[first + q]; ki[(size_t)Sc + q] = index[first + q]; }
+        for (int q = count; q < Sc; ++q) ki[(size_t)Sc + q] = 0;
+        HIP_TRY(this, hipMemsetAsync(col_latB.p, 0, latres_chunk_bytes(disp_nx, disp_ny, disp_nz, Sc), stream));
+        HIP_TRY(this, hipMemcpyAsync(latres_kinds(r), ki.data(), ki.size() * 4, hipMemcpyHostToDevice, stream));
+        launch_latres_first(r, tol, maxit, stream);
+        HIP_TRY(this, hipGetLastError());
+        ints.assign(4 * (size_t)Sc, 0);
+        for (int it = 1; edges && it <= maxit; ++it) {
+            launch_latres_iteration(r, tol, maxit, stream);
+            if (it % lateral_poll == 0 && it < maxit) {
+                HIP_TRY(this, hipMemcpyAsync(ints.data(), latres_ints(r) + (size_t)Sc, (size_t)Sc * 4, hipMemcpyDeviceToHost, stream));          // the done flags
+                HIP_TRY(this, hipStreamSynchronize(stream));
+                bool done = true;
+                for (int q = 0; q < Sc && done; ++q) done = ints[(size_t)q] != 0;
+                if (done) break;
+            }
+        }
+        launch_latres_measures(r, col_meas.p, stream);
+        HIP_TRY(this, hipGetLastError());
+        sc.resize(2 * (size_t)Sc);
+        HIP_TRY(this, hipMemcpyAsync(measures + (size_t)first * 7, col_meas.p, (size_t)count * 7 * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(this, hipMemcpyAsync(ints.data(), latres_ints(r), 4 * (size_t)Sc * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(this, hipMemcpyAsync(sc.data(), latres_scalars(r), 2 * (size_t)Sc * 8, hipMemcpyDeviceToHost, stream));                          // rz, then rz0
+        if (full) {
+            u.resize((size_t)nint * M * Sc);
+            HIP_TRY(this, hipMemcpyAsync(u.data(), latres_u(r), u.size() * 8, hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(this, hipStreamSynchronize(stream));
+        for (int q = 0; q < count; ++q) {
+            double* o = info + (size_t)(first + q) * 4;
+            o[0] = (double)ints[(size_t)q]; o[1] = (double)ints[2 * (size_t)Sc + q]; o[2] = sc[(size_t)Sc + q]; o[3] = sc[(size_t)q];
+            if (full)
+                for (size_t e = 0; e < (size_t)M * nint; ++e) {          // e = l nint + b
+                    const size_t l = e / nint, b = e - l * nint;
+                    full[(size_t)(first + q) * M * nint + e] = u[(b * M + l) * Sc + q];
+                }
+        }
+    }
+    HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
 int Engine::maps_from_dispersion(float goxd, float gozd, float dvxd, float dvzd, int dicing)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "maps: call dsa_dispersion_begin / run first"); return DSA_ERR_STATE; }
@@ -2250,6 +2359,15 @@ int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const f
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_step_lateral(nmaps, obs, wt, smooth, damp, lateral, dvmax, minvel, maxvel, tol, maxit, dv, nused, chi2, flag, info);
+}
+
+int dsa_columns_resolution_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, double tol, int maxit,
+                                   int nmembers, const int* kind, const int* index, const double* models, int nrows, double* measures, double* info, double* full,
+                                   int* nused, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_resolution_lateral(nmaps, obs, wt, smooth, damp, lateral, tol, maxit, nmembers, kind, index, models, nrows, measures,
+                                                                    info, full, nused, flag);
 }
 
 int dsa_columns_step_radial_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso, float lateral,

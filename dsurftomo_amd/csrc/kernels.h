@@ -354,6 +354,27 @@ void launch_coupled_first(const CoupledSystem& s, double tol, int maxit, hipStre
 void launch_coupled_iteration(const CoupledSystem& s, double tol, int maxit, hipStream_t stream);
 void launch_coupled_finish(const CoupledSystem& s, float dvmax, float minvel, float maxvel, float* d_vels0, float* d_vels1, float* d_dv, hipStream_t stream);
 
+// The resolution of the laterally coupled step (column_kernels.hip: k_latres_*).  s: the isotropic coupled system whose
+// workspace holds the set-up; d_H: latres_gram_bytes; d_batch: latres_chunk_bytes of a chunk of Sc members (a multiple of 64), zeroed by the
+// caller, with the members' kinds and indices (2 Sc ints, any other kind for the padding) at latres_kinds; d_models: null or (rows, M, nint).
+// latres_ints: (4, Sc) itn, done, istop; latres_scalars: (8, Sc) rz, rz0, ...; latres_u: (nint, M, Sc) after launch_latres_measures.
+struct LatResSystem { CoupledSystem s; const double* d_H; const float* d_depz; const double* d_models; double* d_batch; int Sc; };
+size_t latres_lds_bytes(int nz);
+size_t latres_gram_bytes(int nx, int ny, int nz);
+size_t latres_bytes_per_member(int nx, int ny, int nz);
+size_t latres_chunk_bytes(int nx, int ny, int nz, int Sc);
+int* latres_ints(const LatResSystem& r);
+int* latres_kinds(const LatResSystem& r);
+const double* latres_scalars(const LatResSystem& r);
+const double* latres_u(const LatResSystem& r);
+// column_lds_opt_in's return values for the batched kernels: nothing may be launched unless 0
+int latres_prepare(int device, int nz, int* limit_out);
+void launch_latres_setup(const CoupledSystem& s, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                         double* d_H, int* d_nused, double* d_chi2, int* d_flag, hipStream_t stream);
+void launch_latres_first(const LatResSystem& r, double tol, int maxit, hipStream_t stream);
+void launch_latres_iteration(const LatResSystem& r, double tol, int maxit, hipStream_t stream);
+void launch_latres_measures(const LatResSystem& r, double* d_measures, hipStream_t stream);
+
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times
 void launch_step_models(int nx, int ny, int nz, int nm, int m0, const float* d_vsf, const float* d_steps, const float* d_bx, int n, const float* d_alpha,

@@ -3,6 +3,7 @@
     python -m dsurftomo_amd.depth <directory with DSurfTomo.in, the data file and MOD> [--maps FILE] [--iterations N] [--smooth L] [--damp D]
                                   [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]] [--radial [--aniso G]]
                                   [--lateral W [--lateral-tol T] [--lateral-maxit N]] [--radial-resolution]
+                                  [--lateral-resolution [--lateral-resolution-stride N] [--lateral-checkerboard NX,NY,NZ[,AMP]]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -71,6 +72,20 @@ median leak share per block and how many unflagged nodes have |xi - 1| > 2 sd_xi
 --radial and the flag with --radial-lateral (the resolution of the laterally coupled system is not computed) are refused.  Without the flag
 nothing changes.  column_radial_resolution_twin is the NumPy twin (csrc/column_radial_resolution.h is the arithmetic).
 
+--lateral W --lateral-resolution [--lateral-resolution-stride N] [--lateral-checkerboard NX,NY,NZ[,AMP]] [--sigma S]:
+after the last coupled step the runs are done once more on the final model and columns_resolution_lateral solves, with the loop's weights,
+--smooth, --damp, W, --lateral-tol and --lateral-maxit, the coupled system once per resolved unknown for its point-spread function and once
+for its row of the averaging kernel -- every N-th unknown (default 1: all), all in one batched call.  <input>DepthLateralResolution.dat
+(write_lateral_resolution / read_lateral_resolution): per resolved node longitude, latitude, depth, R_jj, the vertical length
+sqrt(mz / m1) of its point-spread function in km, its lateral lengths sqrt(mx / m1) and sqrt(my / m1) in cells, the share own / m1 of the
+function that stays in the node's own column, sd_unit = sqrt(var) and sd = S sd_unit, S by --resolution's rule.  With
+--lateral-checkerboard a test model of blocks of NX x NY interior columns and NZ depths of alternating sign and amplitude AMP (default 0.1
+km/s) is recovered in the same way; <input>DepthLateralChecker.dat (write_lateral_checker / read_lateral_checker): per interior node above
+the bottom depth longitude, latitude, depth, the input and the recovered perturbation.  The log gives the median own share and lateral
+length, the range of the conjugate-gradient iterations and every member that stopped at --lateral-maxit.  The flag needs --lateral and
+refuses --radial; --resolution with --lateral stays refused.  Without the flag nothing changes.  column_lateral_resolution_twin is the NumPy
+twin (csrc/column_lateral_resolution.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -97,6 +112,9 @@ RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", "rjj", "length", "sd_unit"
 LEVERAGE_TABLE = (True, _F64("lon", "lat") + (("wave", "%d", "int"), ("kind", "%d", "int")) + _F64("period", "leverage"))
 FIT_TABLE = (True, _F64("lon", "lat") + (("nused", "%d", "int"),) + _F64("rms_first", "rms_last") + (("flag", "%d", "int"),))
 RADIAL_TABLE = (True, _F64("lon", "lat", "depth", "vsv", "vsh", "voigt", "xi"))
+LATERAL_RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", "rjj", "length_z", "length_x", "length_y", "own", "sd_unit", "sd"))
+LATERAL_CHECKER_TABLE = (True, _F64("lon", "lat", "depth", "input", "recovered"))
+DEFAULT_CHECKER_AMP = 0.1
 RADIAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused_r", "%d", "int"), ("nused_l", "%d", "int")) + _F64("rms_first_r", "rms_last_r", "rms_first_l", "rms_last_l") +
                     (("flag", "%d", "int"),))
 
@@ -347,10 +365,11 @@ def _twin_pcg(col, interior, bt, apply, coupled, tol, maxit):
     return x, itn, istop, float(rz0), float(rz)
 
 
-def _twin_stacked(col, edges, B, own, between):
+def _twin_stacked(col, edges, B, own, between, matrix=False):
     """The other answer of a coupled twin: numpy.linalg.lstsq on the stacked system of the active columns col, B unknowns each.  own(c) ->
     [(block (rows, B), right-hand side)] of column c alone; between(c, n) -> [(block (rows, B), right-hand side)] of the edge c < n, the
-    block applied to c and, negated, to n.  Returns {column: solution (B)}."""
+    block applied to c and, negated, to n.  Returns {column: solution (B)} -- or, with matrix, (the stacked matrix, {column: its first
+    unknown's place}) and solves nothing."""
     index = {c: q * B for q, c in enumerate(col)}
     rows, rhs = [], []
 
@@ -368,6 +387,8 @@ def _twin_stacked(col, edges, B, own, between):
             if n > c:
                 for block, right in between(c, n):
                     put([(c, block), (n, -block)], right)
+    if matrix:
+        return np.vstack(rows), index
     sol = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
     return {c: sol[index[c]:index[c] + B] for c in col}
 
@@ -439,6 +460,167 @@ def column_lateral_twin(nx, ny, obs, wt, pv, S, vels, smooth, damp, lateral, dvm
     out["dv"] = _twin_clip(out["delta"], dvmax)
     for c in col:
         vels[:M, c] = _twin_stepped(vels[:M, c], out["dv"][:, c], minvel, maxvel)
+    return out
+
+
+def column_lateral_resolution_twin(nx, ny, obs, wt, pv, S, depz, smooth, damp, lateral, kind, index, models=None, tol=1e-8, maxit=500):
+    """dsa_columns_resolution_lateral in NumPy (csrc/column_lateral_resolution.h) on an (ny, nx) grid of columns as column_lateral_twin takes
+    it; depz: the depths of the unknowns (M or more, fp32); kind, index (nmembers); models None or (rows, M, interior columns).  Two answers.
+    The header's: N_c, H_c = G_c^T G_c and the factors through _twin_normal / _twin_factor, every member's right-hand side by the header's
+    chain, its solve by _twin_pcg, its measures per column with l ascending and then lateral_sum.  And, independently, a dense one: with B
+    the stacked [blockdiag(G_c); smooth L; damp I; lateral E] of the active columns as _twin_stacked builds it and P = numpy.linalg.pinv(B),
+    A^-1 = P P^T; x = P [G m; 0] for kinds 0 and 2, x = P (P^T f) for kinds 1 and 3, the measures by plain NumPy sums.  Returns dict(measures
+    (nmembers, 7): val, m1, mz, mx, my, own, var; full (nmembers, M, interior columns): u; itn, istop (nmembers) int32; rz0, rz (nmembers);
+    measures_dense, full_dense; nused, flag (ny * nx); data_response(rw): A^-1 G^T rw (M, interior columns) of weighted residuals rw (K,
+    ny * nx), dense)."""
+    f32 = np.float32
+    obs = np.asarray(obs, f32); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64)
+    M, K, ncol = S.shape
+    assert ncol == nx * ny and obs.shape == (K, ncol)
+    wt = np.ones((K, ncol), f32) if wt is None else np.asarray(wt, f32)
+    kind = np.asarray(kind, np.int64).ravel(); index = np.asarray(index, np.int64).ravel()
+    lam, mu, lat = float(f32(smooth)), float(f32(damp)), float(f32(lateral))
+    lat2 = lat * lat
+    z = np.asarray(depz, f32)[:M].astype(np.float64)
+    nvx = nx - 2
+    interior = [j * nx + i for j in range(1, ny - 1) for i in range(1, nx - 1)]
+    nint, nm = len(interior), len(kind)
+    out = dict(measures=np.zeros((nm, 7)), full=np.zeros((nm, M, nint)), itn=np.zeros(nm, np.int32), istop=np.zeros(nm, np.int32), rz0=np.zeros(nm), rz=np.zeros(nm),
+               measures_dense=np.zeros((nm, 7)), full_dense=np.zeros((nm, M, nint)), nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32))
+    col = {}
+    for c in interior:
+        used, rho, _, G = _twin_data(obs[:, c], wt[:, c], pv[:, c], S[:, :, c].T)
+        out["nused"][c] = int(used.sum())
+        if not used.any() and lat == 0.0:
+            out["flag"][c] = 2
+            continue
+        N, _ = _twin_normal(G, used, rho, lam * lam, mu * mu)
+        factor = _twin_factor(N)
+        if factor is None:
+            out["flag"][c] = 1
+            continue
+        col[c] = dict(G=G, used=used, N=N, factor=factor, H=_twin_normal(G, used, rho, 0.0, 0.0)[0])
+    edges = {c: [n for n in (c - 1, c + 1, c - nx, c + nx) if n in col] if lat > 0.0 else [] for c in col}
+
+    def apply(y):
+        q = {}
+        for c, d in col.items():
+            t = np.zeros(M)
+            for j in range(M):
+                t = t + d["N"][:, j] * y[c][j]
+            s = np.zeros(M)
+            for n in edges[c]:
+                s = s + y[n]
+            q[c] = t + lat2 * (float(len(edges[c])) * y[c] - s)
+        return q
+
+    def gram(c, m):
+        t = np.zeros(M)
+        for j in range(M):
+            t = t + col[c]["H"][:, j] * m[j]
+        return t
+
+    def rhs(k, idx):
+        f = {c: np.zeros(M) for c in col}
+        for b, c in enumerate(interior):
+            if c not in col:
+                continue
+            if k == 0 and idx // M == b:
+                f[c] = gram(c, np.eye(M)[idx % M])
+            elif k == 1 and idx // M == b:
+                f[c] = np.eye(M)[idx % M].copy()
+            elif k == 2:
+                f[c] = gram(c, models[idx][:, b])
+            elif k == 3:
+                f[c] = np.array(models[idx][:, b], np.float64)
+        return f
+
+    def measure(k, idx, x, u):
+        """x, u (M, nint); the figures per column with l ascending, then lateral_sum; plain: NumPy's sums"""
+        b0, l0 = idx // M, idx % M
+        dz = z - z[l0]
+        di = np.array([(b % nvx) - (b0 % nvx) for b in range(nint)], np.float64); dj = np.array([(b // nvx) - (b0 // nvx) for b in range(nint)], np.float64)
+        fig = np.zeros((5, nint))
+        for l in range(M):
+            r2 = u[l] * u[l]
+            fig[0] = fig[0] + r2
+            fig[1] = fig[1] + r2 * (dz[l] * dz[l])
+            fig[2] = fig[2] + r2 * (di * di)
+            fig[3] = fig[3] + r2 * (dj * dj)
+            if k == 1:
+                fig[4] = fig[4] + x[l] * u[l]
+        return [u[l0, b0]] + [lateral_sum(fig[q]) for q in range(4)] + [fig[0, b0], lateral_sum(fig[4])]
+
+    if col:
+        Lm = column_l(M)
+        own = lambda c: [(col[c]["G"][col[c]["used"]], np.zeros(int(col[c]["used"].sum()))), (lam * Lm, np.zeros(Lm.shape[0])), (mu * np.eye(M), np.zeros(M))]
+        Bm, place = _twin_stacked(col, edges, M, own, lambda c, n: [(lat * np.eye(M), np.zeros(M))], matrix=True)
+        P = np.linalg.pinv(Bm)
+        data_rows = {}                                                  # the rows of B that hold column c's used data
+        at = 0
+        for c in col:
+            nu = int(col[c]["used"].sum())
+            data_rows[c] = np.arange(at, at + nu)
+            at += nu + Lm.shape[0] + M
+    pos = {c: b for b, c in enumerate(interior)}
+
+    def spread(sol):
+        full = np.zeros((M, nint))
+        for c in col:
+            full[:, pos[c]] = sol[place[c]:place[c] + M]
+        return full
+
+    def data_response(rw):
+        if not col:
+            return np.zeros((M, nint))
+        right = np.zeros(Bm.shape[0])
+        for c in col:
+            right[data_rows[c]] = np.asarray(rw, np.float64)[col[c]["used"], c]
+        return spread(P @ right)
+
+    out["data_response"] = data_response
+    for s in range(nm):
+        k, idx = int(kind[s]), int(index[s])
+        f = rhs(k, idx)
+        x, out["itn"][s], out["istop"][s], out["rz0"][s], out["rz"][s] = _twin_pcg(col, interior, f, apply, lat > 0.0, tol, maxit)
+        xf = np.zeros((M, nint)); uf = np.zeros((M, nint))
+        for c in col:
+            xf[:, pos[c]] = x[c]
+            uf[:, pos[c]] = gram(c, x[c]) if k == 1 else x[c]
+        out["full"][s] = uf
+        if k < 2:
+            out["measures"][s] = measure(k, idx, xf, uf)
+        if not col:
+            continue
+        if k in (0, 2):
+            m = np.zeros((M, nint))
+            if k == 0:
+                m[idx % M, idx // M] = 1.0
+            else:
+                m = np.asarray(models[idx], np.float64)
+            right = np.zeros(Bm.shape[0])
+            for c in col:
+                right[data_rows[c]] = col[c]["G"][col[c]["used"]] @ m[:, pos[c]]
+            xd = spread(P @ right)
+        else:
+            fv = np.zeros(Bm.shape[1])
+            for c in col:
+                fv[place[c]:place[c] + M] = f[c]
+            xd = spread(P @ (P.T @ fv))
+        ud = xd
+        if k == 1:
+            ud = np.zeros((M, nint))
+            for c in col:
+                Gu = col[c]["G"][col[c]["used"]]
+                ud[:, pos[c]] = Gu.T @ (Gu @ xd[:, pos[c]])
+        out["full_dense"][s] = ud
+        if k < 2:
+            b0, l0 = idx // M, idx % M
+            r2 = ud * ud
+            dz = (z - z[l0])[:, None]
+            di = np.array([(b % nvx) - (b0 % nvx) for b in range(nint)], np.float64)[None, :]; dj = np.array([(b // nvx) - (b0 // nvx) for b in range(nint)], np.float64)[None, :]
+            out["measures_dense"][s] = [ud[l0, b0], r2.sum(), (r2 * dz * dz).sum(), (r2 * di * di).sum(), (r2 * dj * dj).sum(), r2[:, b0].sum(),
+                                        float((xd * ud).sum()) if k == 1 else 0.0]
     return out
 
 
@@ -763,9 +945,10 @@ def check_lateral(radial=False, resolution=False):
 
 
 def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral, radial_lateral_aniso,
-                radial_resolution=False):
+                radial_resolution=False, lateral_resolution=False, lateral_resolution_stride=1, lateral_checkerboard=None):
     """every precondition on the flags, in the order run() and main() both refuse in (ValueError), before the library is loaded.  aniso None:
-    not looked at; --lateral-tol and --lateral-maxit are looked at only with a coupling; --radial-resolution's come last."""
+    not looked at; --lateral-tol and --lateral-maxit are looked at only with a coupling; --radial-resolution's come after the others, then
+    --lateral-resolution's.  Returns the parsed --lateral-checkerboard, or None."""
     with_cg = lateral is not None or radial_lateral is not None
     check(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, lateral, lateral_tol if with_cg else None, lateral_maxit if with_cg else None, radial_lateral,
           radial_lateral_aniso)
@@ -775,6 +958,7 @@ def check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso, radial, 
         check_radial(None, resolution)
     check_radial_lateral(radial_lateral, radial_lateral_aniso, radial, lateral, resolution)
     check_radial_resolution(radial_resolution, radial, radial_lateral)
+    return check_lateral_resolution(lateral_resolution, lateral_resolution_stride, lateral_checkerboard, lateral, radial)
 
 
 def _iterate(eng, plan, iterations, step, entry, log, coupling):
@@ -935,6 +1119,156 @@ def resolve(eng, c, plan, obs, wt, smooth, damp, sigma, out_dir, log=print):
             (sm["trace"] + (c["nz"] - 1, "stays under 0.1 from %g km down" % sm["depth"] if sm["depth"] is not None else "is 0.1 or more at the deepest unknown")))
     log(" depth resolution: written to %s (sd for a data standard deviation of %.6f km/s), the leverages to %s" % (rpath, sigma, lpath))
     return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
+
+
+# ---- the resolution of the laterally coupled step ----
+
+def parse_checkerboard(text):
+    """--lateral-checkerboard NX,NY,NZ[,AMP]: (nx, ny, nz, amp) -- block sizes in interior columns and depths, at least 1; AMP in km/s, finite
+    and not 0, default DEFAULT_CHECKER_AMP (ValueError)"""
+    parts = str(text).split(",")
+    try:
+        if len(parts) not in (3, 4):
+            raise ValueError
+        nx, ny, nz = (int(p) for p in parts[:3])
+        amp = float(parts[3]) if len(parts) == 4 else DEFAULT_CHECKER_AMP
+    except ValueError:
+        raise ValueError("--lateral-checkerboard takes NX,NY,NZ[,AMP], not %r" % (text,)) from None
+    if min(nx, ny, nz) < 1 or not np.isfinite(amp) or amp == 0:
+        raise ValueError("--lateral-checkerboard: the blocks must be at least 1 x 1 x 1 and AMP finite and not 0, not %r" % (text,))
+    return nx, ny, nz, amp
+
+
+def check_lateral_resolution(lateral_resolution=False, stride=1, checkerboard=None, lateral=None, radial=False):
+    """what --lateral-resolution and its companions ask of the other flags, before the library is loaded (ValueError).  Returns the parsed
+    checkerboard, or None."""
+    if not lateral_resolution:
+        if stride != 1 or checkerboard is not None:
+            raise ValueError("%s needs --lateral-resolution" % ("--lateral-resolution-stride" if stride != 1 else "--lateral-checkerboard"))
+        return None
+    if radial:
+        raise ValueError("--lateral-resolution and --radial exclude each other: the resolution of the laterally coupled radial system is not computed")
+    if lateral is None:
+        raise ValueError("--lateral-resolution needs --lateral: it is the resolution of that coupled step (--resolution is that of the columns alone)")
+    if stride < 1:
+        raise ValueError("--lateral-resolution-stride must be at least 1, not %r" % (stride,))
+    return None if checkerboard is None else parse_checkerboard(checkerboard)
+
+
+def checkerboard_model(nvx, nvy, M, spec):
+    """blocks of spec = (nx, ny, nz, amp): (M, nvy * nvx), +amp where the block indices add up to an even number"""
+    bx, by, bz, amp = spec
+    l = np.arange(M)[:, None, None] // bz; j = np.arange(nvy)[None, :, None] // by; i = np.arange(nvx)[None, None, :] // bx
+    return (amp * np.where((l + j + i) % 2 == 0, 1.0, -1.0)).reshape(M, nvy * nvx)
+
+
+def _ratio(a, b):
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    return np.divide(a, b, out=np.zeros(a.shape), where=b > 0)
+
+
+def lateral_resolution_columns(index, psf, unit, sigma):
+    """The node figures of DepthLateralResolution.dat: index (n) the resolved unknowns, psf and unit (n, 7) the measures of their members of
+    kind 0 and of kind 1 (val, m1, mz, mx, my, own, var).  Returns dict(rjj, length_z, length_x, length_y, own, sd_unit, sd), each (n); a
+    length and the share are 0 where m1 = 0."""
+    psf = np.asarray(psf, np.float64).reshape(-1, 7); unit = np.asarray(unit, np.float64).reshape(-1, 7)
+    sd_unit = np.sqrt(np.maximum(unit[:, 6], 0.0))
+    return dict(rjj=psf[:, 0].copy(), length_z=np.sqrt(_ratio(psf[:, 2], psf[:, 1])), length_x=np.sqrt(_ratio(psf[:, 3], psf[:, 1])),
+                length_y=np.sqrt(_ratio(psf[:, 4], psf[:, 1])), own=_ratio(psf[:, 5], psf[:, 1]), sd_unit=sd_unit, sd=float(sigma) * sd_unit)
+
+
+def _interior_node(c, unknown):
+    """(lon, lat, depth) of unknown = b (nz - 1) + l of interior column b"""
+    M, nvx = c["nz"] - 1, c["nx"] - 2
+    b, l = divmod(int(unknown), M)
+    lon, lat = _lonlat(c, b % nvx, b // nvx)
+    return float(lon), float(lat), float(c["depz"][l])
+
+
+def write_lateral_resolution(path, c, index, columns):
+    """<input>DepthLateralResolution.dat: one line per resolved unknown in index's order; columns: lateral_resolution_columns' dict"""
+    rows = []
+    for q, unknown in enumerate(index):
+        lon, lat, dep = _interior_node(c, unknown)
+        rows.append(dict(lon=lon, lat=lat, depth=dep, **{name: float(columns[name][q]) for name, _, _ in LATERAL_RESOLUTION_TABLE[1][3:]}))
+    io.write_table(path, LATERAL_RESOLUTION_TABLE, rows)
+
+
+def read_lateral_resolution(path):
+    return io.read_table(path, LATERAL_RESOLUTION_TABLE)
+
+
+def write_lateral_checker(path, c, model, recovered):
+    """<input>DepthLateralChecker.dat: model and recovered (nz - 1, interior columns), every interior node above the bottom depth: depth
+    slowest, then the interior columns in their order"""
+    M, nint = c["nz"] - 1, (c["nx"] - 2) * (c["ny"] - 2)
+    m = np.asarray(model, np.float64).reshape(M, nint); r = np.asarray(recovered, np.float64).reshape(M, nint)
+    rows = []
+    for l in range(M):
+        for b in range(nint):
+            lon, lat, dep = _interior_node(c, b * M + l)
+            rows.append(dict(lon=lon, lat=lat, depth=dep, input=m[l, b], recovered=r[l, b]))
+    io.write_table(path, LATERAL_CHECKER_TABLE, rows)
+
+
+def read_lateral_checker(path):
+    return io.read_table(path, LATERAL_CHECKER_TABLE)
+
+
+def lateral_resolution_log(columns, psf, res):
+    """the log's lines: the median own share and lateral length sqrt((mx + my) / m1) over the resolved nodes whose m1 > 0, the range of itn over
+    all members, and the members that stopped at --lateral-maxit"""
+    psf = np.asarray(psf, np.float64).reshape(-1, 7)
+    ok = psf[:, 1] > 0
+    lines = []
+    if ok.any():
+        length = np.sqrt(_ratio(psf[:, 3] + psf[:, 4], psf[:, 1]))
+        lines.append(" depth lateral resolution: %d of %d resolved nodes answer; median own share %.4f, median lateral length %.4f cells" %
+                     (int(ok.sum()), len(ok), float(np.median(np.asarray(columns["own"])[ok])), float(np.median(length[ok]))))
+    else:
+        lines.append(" depth lateral resolution: none of the %d resolved nodes answers" % len(ok))
+    itn = np.asarray(res["itn"]); istop = np.asarray(res["istop"])
+    lines.append(" depth lateral resolution: %d members, %d to %d conjugate-gradient iterations" % (len(itn), int(itn.min()), int(itn.max())))
+    late = np.flatnonzero(istop == 2)
+    if late.size:
+        lines.append(" depth lateral resolution: %d members stopped at --lateral-maxit (istop 2), the first: member %d (kind %d, index %d)" %
+                     (late.size, int(late[0]), int(res["kind"][late[0]]), int(res["index"][late[0]])))
+    return lines
+
+
+def resolve_lateral(eng, c, plan, obs, wt, smooth, damp, lateral, lateral_tol, lateral_maxit, sigma, out_dir, stride=1, checker=None, log=print):
+    """--lateral-resolution on an engine whose stage holds the final model: the runs of plan once more, then one columns_resolution_lateral
+    with every stride-th unknown as kind 0 and as kind 1 and, with checker (parse_checkerboard's tuple), the test model as kind 2 last; the
+    files, the log.  Returns dict(lateral_resolution: the call's result with kind and index added, sigma, columns, lateral_resolution_path,
+    and with checker lateral_checker_path, checker_model, checker_recovered)."""
+    for wave, kind, t, first in plan:
+        eng.dispersion_run(wave, kind, t, True, first, first)
+    M, nvx, nvy = c["nz"] - 1, c["nx"] - 2, c["ny"] - 2
+    unknowns = np.arange(0, nvx * nvy * M, stride, dtype=np.int32)
+    n = len(unknowns)
+    kind = np.concatenate([np.zeros(n, np.int32), np.ones(n, np.int32)]); index = np.concatenate([unknowns, unknowns])
+    models = None
+    if checker is not None:
+        models = checkerboard_model(nvx, nvy, M, checker)[None]
+        kind = np.append(kind, np.int32(2)); index = np.append(index, np.int32(0))
+    res = eng.columns_resolution_lateral(obs, wt, smooth, damp, lateral, kind, index, models, lateral_tol, lateral_maxit, full=checker is not None)
+    res = dict(res, kind=kind, index=index)
+    psf, unit = res["measures"][:n], res["measures"][n:2 * n]
+    columns = lateral_resolution_columns(unknowns, psf, unit, sigma)
+    rpath = os.path.join(out_dir, "DSurfTomo.inDepthLateralResolution.dat")
+    write_lateral_resolution(rpath, c, unknowns, columns)
+    for line in lateral_resolution_log(columns, psf, res):
+        log(line)
+    log(" depth lateral resolution: %d nodes written to %s (sd for a data standard deviation of %.6f km/s)" % (n, rpath, sigma))
+    out = dict(lateral_resolution=res, sigma=float(sigma), columns=columns, lateral_resolution_path=rpath)
+    if checker is not None:
+        cpath = os.path.join(out_dir, "DSurfTomo.inDepthLateralChecker.dat")
+        recovered = res["full"][2 * n]
+        write_lateral_checker(cpath, c, models[0], recovered)
+        log(" depth lateral resolution: checkerboard of %d x %d x %d blocks, amplitude %g km/s: recovered amplitude median %.4f of the input, written to %s" %
+            (checker[0], checker[1], checker[2], checker[3], float(np.median(recovered / models[0])), cpath))
+        out.update(lateral_checker_path=cpath, checker_model=models[0], checker_recovered=recovered)
+    return out
 
 
 # ---- radial anisotropy (DESIGN.md section 23) ----
@@ -1197,16 +1531,19 @@ def radial_resolution_log(c, sm):
 
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
         log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
-        lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False):
+        lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False, lateral_resolution=False,
+        lateral_resolution_stride=1, lateral_checkerboard=None):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
     None): the loop steps with columns_step_lateral; the files are the same two.  With radial and radial_lateral (not None): the radial loop
     steps with columns_step_radial_lateral, radial_lateral_aniso (None: radial_lateral) the weight on Vsh - Vsv; the files are --radial's.
     With radial and radial_resolution: after the loop resolve_radial's entries are added to the first item (DepthRadialResolution.dat and
-    DepthRadialLeverage.dat beside --radial's files); sigma as with resolution."""
-    check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit, radial_lateral,
-                radial_lateral_aniso, radial_resolution)
+    DepthRadialLeverage.dat beside --radial's files); sigma as with resolution.  With lateral and lateral_resolution: after the loop
+    resolve_lateral's entries are added to the first item (DepthLateralResolution.dat and, with lateral_checkerboard, DepthLateralChecker.dat
+    beside the two files); sigma as with resolution."""
+    checker = check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit,
+                          radial_lateral, radial_lateral_aniso, radial_resolution, lateral_resolution, lateral_resolution_stride, lateral_checkerboard)
     c = io.load(directory)
     if radial:
         check_radial(c)
@@ -1237,6 +1574,11 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
             rms = out["history"][-1]["rms"]
             log(" depth resolution: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
             out.update(resolve(eng, c, plan, obs, wt, smooth, damp, rms if sigma is None else sigma, out_dir, log))
+        if lateral_resolution:
+            rms = out["history"][-1]["rms"]
+            log(" depth lateral resolution: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
+            out.update(resolve_lateral(eng, c, plan, obs, wt, smooth, damp, lateral, lateral_tol, lateral_maxit, rms if sigma is None else sigma, out_dir,
+                                       lateral_resolution_stride, checker, log))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inDepth.dat")
@@ -1267,6 +1609,9 @@ def parser():
     ap.add_argument("--radial-lateral", type=float, default=None, metavar="W", help="with --radial: couple neighbouring columns, weight of the penalty on the differences of Vsv and of Vsh, >= 0 (default: columns alone); --lateral-tol and --lateral-maxit apply")
     ap.add_argument("--radial-lateral-aniso", type=float, default=None, metavar="A", help="with --radial-lateral: weight of the penalty on the differences of Vsh - Vsv between neighbours, >= 0 (default: W)")
     ap.add_argument("--radial-resolution", action="store_true", help="with --radial: after the last step write the resolution measures of Vsv, Vsh and xi and the leverages of the final models (--sigma applies)")
+    ap.add_argument("--lateral-resolution", action="store_true", help="with --lateral: after the last step write the point-spread lengths, own shares and standard deviations of the coupled system (--sigma applies)")
+    ap.add_argument("--lateral-resolution-stride", type=int, default=1, metavar="N", help="with --lateral-resolution: resolve every N-th unknown (default 1: all)")
+    ap.add_argument("--lateral-checkerboard", default=None, metavar="NX,NY,NZ[,AMP]", help="with --lateral-resolution: recover a checkerboard of NX x NY x NZ blocks of amplitude AMP km/s (default %g)" % DEFAULT_CHECKER_AMP)
     return ap
 
 
@@ -1275,13 +1620,14 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         check_flags(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.radial, a.resolution, a.lateral, a.lateral_tol, a.lateral_maxit,
-                    a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution)
+                    a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution, a.lateral_resolution, a.lateral_resolution_stride, a.lateral_checkerboard)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
     run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso,
         lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso,
-        radial_resolution=a.radial_resolution)
+        radial_resolution=a.radial_resolution, lateral_resolution=a.lateral_resolution, lateral_resolution_stride=a.lateral_resolution_stride,
+        lateral_checkerboard=a.lateral_checkerboard)
     return 0
 
 

@@ -111,6 +111,7 @@ def declare_solvers(L):
     L.dsa_columns_resolution_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [_vp] * 7
     L.dsa_columns_step_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_step_radial_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 8 + [C.c_double, _i32] + [_vp] * 5
+    L.dsa_columns_resolution_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [C.c_double, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 5
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -528,6 +529,36 @@ class Engine:
                                                      float(maxvel), float(tol), int(maxit), _p(dv), _p(nused), _p(chi2), _p(flag), _p(info)))
         return dict(dv=dv, nused=nused, chi2=chi2, flag=flag, itn=int(info[0]), istop=int(info[1]), rz0=float(info[2]), rz=float(info[3]),
                     carried=self._carried(nused, flag))
+
+    def columns_resolution_lateral(self, obs, wt, smooth, damp, lateral, kind, index, models=None, tol=1e-8, maxit=500, full=False):
+        """dsa_columns_resolution_lateral on the state columns_step_lateral needs, which it leaves as it is: obs and wt as columns_step's.  kind
+        and index (nmembers) int32: 0 the point-spread function of unknown index = b (nz - 1) + l of interior column b, 1 row index of the
+        averaging kernel and its variance, 2 the recovery of row index of models, 3 that row as the right-hand side; models (rows, nz - 1,
+        interior columns) fp64 or None.  Returns dict(measures (nmembers, 7): val, m1, mz, mx, my, own, var; itn, istop (nmembers) int32; rz0, rz
+        (nmembers); nused, flag (ny * nx) int32; and with full=True full (nmembers, nz - 1, interior columns): u of every member).  ValueError
+        as columns_step, and when kind and index differ in size or models is not (rows, nz - 1, interior columns)."""
+        nmaps, obs, wt = self._columns_in("columns_resolution_lateral", obs, wt)[:3]
+        nx, ny, nz = self._disp
+        ncol, nint = nx * ny, (nx - 2) * (ny - 2)
+        kind = np.ascontiguousarray(kind, np.int32).ravel(); index = np.ascontiguousarray(index, np.int32).ravel()
+        if kind.size != index.size:
+            raise ValueError("columns_resolution_lateral: kind holds %d values, index %d" % (kind.size, index.size))
+        nrows = 0
+        if models is not None:
+            models = np.ascontiguousarray(models, np.float64)
+            if models.ndim != 3 or models.shape[1:] != (nz - 1, nint):
+                raise ValueError("columns_resolution_lateral: models is %r, not (rows, %d, %d)" % (models.shape, nz - 1, nint))
+            nrows = models.shape[0]
+        n = kind.size
+        measures = np.zeros((n, 7)); info = np.zeros((n, 4))
+        out = dict(measures=measures, nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32))
+        if full:
+            out["full"] = np.zeros((n, nz - 1, nint))
+        self._check(self._L.dsa_columns_resolution_lateral(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), float(lateral), float(tol), int(maxit), n,
+                                                           _p(kind), _p(index), _p(models), nrows, _p(measures), _p(info), _p(out["full"]) if full else None,
+                                                           _p(out["nused"]), _p(out["flag"])))
+        out.update(itn=info[:, 0].astype(np.int32), istop=info[:, 1].astype(np.int32), rz0=info[:, 2].copy(), rz=info[:, 3].copy())
+        return out
 
     def columns_step_radial_lateral(self, obs, wt, smooth, damp, aniso, lateral, lateral_aniso, dvmax, minvel, maxvel, tol=1e-8, maxit=500):
         """dsa_columns_step_radial_lateral on the models of dispersion_begin_radial: columns_step_radial with the interior columns tied to their

@@ -528,6 +528,31 @@ int dsa_dispersion_get_model_radial(dsa_engine* e, float* vsv, float* vsh);
 int dsa_columns_step_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, float dvmax,
                              float minvel, float maxvel, double tol, int maxit, float* dv, int* nused, double* chi2, int* flag, double* info);
 
+/* dsa_columns_resolution_lateral: how far the laterally coupled step's answer can be trusted (extension).  The state, obs, wt,
+ * smooth, damp, lateral, tol and maxit are dsa_columns_step_lateral's, with its rules, messages and order of refusals.  With A the coupled
+ * normal matrix of that step and H = blockdiag(G_c^T G_c), each of the nmembers members is one solve A x = f by that step's preconditioned
+ * conjugate gradients (its arithmetic, criterion and istop), with its own iteration count:
+ *   kind 0  the point-spread function of unknown index = b*(nz-1) + l (b the interior column (bj*(nx-2) + bi), l the depth): f = H e_index
+ *   kind 1  row index of R = A^-1 H: f = e_index, u = H x; var = x^T u, the variance of that unknown for unit variance of the weighted data
+ *   kind 2  the recovery of a test model: f = H m, m row index of models
+ *   kind 3  f = row index of models
+ *   models  nrows*(nz-1)*(nx-2)*(ny-2) doubles, depth slowest within a row; may be NULL when no member is of kind 2 or 3
+ *   measures  nmembers*7: R_jj (the vector's own entry), m1 = sum u^2, mz = sum u^2 dz^2 (km^2), mx, my = sum u^2 di^2, dj^2 (cells^2), own =
+ *          the part of m1 in the unknown's own column, var; zeros for kinds 2 and 3.  u = x for kinds 0, 2, 3
+ *   info   nmembers*4: the iterations done, istop, rz0, the last r^T z of each member
+ *   full   NULL, or nmembers*(nz-1)*(nx-2)*(ny-2) doubles: u of every member, depth slowest
+ *   nused, flag  nx*ny, as dsa_columns_step_lateral's
+ * An entry of f in a column that takes no part is 0.0; lateral = 0 is no iteration.  fp64, every sum in a fixed order
+ * (csrc/column_lateral_resolution.h): a member's result has one value whatever its place in the batch and however the batch is cut into
+ * chunks.  The stage is read only, as dsa_columns_resolution's.
+ * Errors, all found before the device is touched: as dsa_columns_step_lateral without dvmax, minvel, maxvel, in its order; then
+ * DSA_ERR_ARGUMENT: nmembers < 1, a required pointer NULL, a kind outside 0 .. 3, an index out of range, models NULL or not finite where a
+ * member needs it; DSA_ERR_CAPACITY: not even one group of 64 members fits the smaller of dsa_set_memory_budget (where one is set) and
+ * 1 GiB.  DSA_ERR_DEVICE: the batched kernels' LDS (97 272 bytes at nz = 64) is refused, before anything is launched. */
+int dsa_columns_resolution_lateral(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float lateral, double tol,
+                                   int maxit, int nmembers, const int* kind, const int* index, const double* models, int nrows, double* measures,
+                                   double* info, double* full, int* nused, int* flag);
+
 /* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
  * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
  * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of

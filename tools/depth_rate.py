@@ -33,7 +33,12 @@ k_column_step_radial and k_column_resolution side by side:
     python tools/depth_rate.py trace-medians DIR/.../*_kernel_trace.csv
 prints per kernel and grid size the median duration of its launches, the first one (the warm-up) left out.
 
-    python tools/depth_rate.py [repeats] [lateral | radial-lateral | radial-resolution]      (needs the GPU; with a name: that leg alone)
+The lateral resolution's leg: dsa_columns_resolution_lateral on the lateral leg's stage and observations at lateral
+0.2 and 1 (tol 1e-8) after one set of runs (the call leaves the state as it is): every unknown as a point-spread function and as a row of
+the averaging kernel (2 x 2 048 members) in one call, next to the first 64 of them one per call -- the wall time of the calls, `repeats`
+timed series after a warm-up one, and from them the time per member of either way.
+
+    python tools/depth_rate.py [repeats] [lateral | radial-lateral | radial-resolution | lateral-resolution]      (needs the GPU; with a name: that leg alone)
 """
 import os
 import sys
@@ -77,6 +82,10 @@ def main():
         lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
         e.close()
         return
+    if "lateral-resolution" in sys.argv[2:]:
+        lateral_resolution_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+        e.close()
+        return
     if "radial-lateral" in sys.argv[2:]:
         radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
         e.close()
@@ -113,7 +122,39 @@ def main():
     lateral_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
     radial_lateral_leg(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
     radial_resolution_legs(e, repeats, vel, c, depth.slot_plan(cases[1][1]), kmax)
+    lateral_resolution_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
     e.close()
+
+
+def lateral_resolution_leg(e, repeats, vel, c, plan, kmax):
+    nz, ny, nx = vel.shape
+    e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, True, first, first)
+    i = np.arange(nx)[None, :]; j = np.arange(ny)[:, None]
+    obs = (e.dispersion_fetch(0, kmax) * (1.0 + 0.02 * np.cos(0.9 * i + 0.5 * j).ravel()[None, :])).astype(np.float32)      # the lateral leg's
+    args = (depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP)
+    n = (nx - 2) * (ny - 2) * (nz - 1)
+    kind = np.repeat(np.array([0, 1], np.int32), n); index = np.tile(np.arange(n, dtype=np.int32), 2)
+    single = 64
+    for lateral in (0.2, 1.0):
+        call = lambda k, q: e.columns_resolution_lateral(obs, None, *args, lateral, k, q, None, depth.DEFAULT_LATERAL_TOL, depth.DEFAULT_LATERAL_MAXIT)
+        batch, alone = [], []
+        for it in range(repeats + 1):
+            t0 = time.perf_counter()
+            out = call(kind, index)
+            t1 = time.perf_counter()
+            ones = [call(kind[s:s + 1], index[s:s + 1]) for s in range(single)]
+            t2 = time.perf_counter()
+            if it:
+                batch.append(1e3 * (t1 - t0)); alone.append(1e3 * (t2 - t1))
+        assert not out["flag"].any() and (out["istop"] == 1).all()
+        assert all(np.array_equal(o["measures"][0].view(np.uint64), out["measures"][s].view(np.uint64)) and o["itn"][0] == out["itn"][s] for s, o in enumerate(ones))
+        print("%-22s %d x %d x %d, K = %d: median of %d -- %d members in one call %.3f ms wall (%.1f us a member), itn %d to %d; the first %d one per call %.3f ms wall "
+              "(%.1f us a member, itn %d to %d): %.1f times as long a member; all batched calls: %s" %
+              ("lateral resolution %g" % lateral, nx, ny, nz, kmax, repeats, len(kind), np.median(batch), 1e3 * np.median(batch) / len(kind), out["itn"].min(), out["itn"].max(),
+               single, np.median(alone), 1e3 * np.median(alone) / single, out["itn"][:single].min(), out["itn"][:single].max(),
+               (np.median(alone) / single) / (np.median(batch) / len(kind)), " ".join("%.3f" % w for w in batch)))
 
 
 def limits_case():
