@@ -356,6 +356,16 @@ struct Engine {
                                    const int* kind, const int* index, const double* models, int nrows, double* measures, double* info, double* full, int* nused,
                                    int* flag);
 
+    // radial anisotropy in the direct inversion (dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial; DESIGN.md
+    // section 28).  radial_sens: Srow holds the depth factors of every slot on the model of its wave type (k_sen_combine_radial) and
+    // radial_block the slots' blocks (0 Vsv, 1 Vsh), both of the present models -- cleared by whatever changes the models, the marks or Srow.
+    // radial_now: the running solve emits radial rows (trace_chunk)
+    bool radial_sens = false, radial_now = false;
+    OwnedBuf<unsigned char> radial_block;
+    int kernels_from_dispersion_radial();
+    int solve_radial(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar);
+    int update_radial(int nx, int ny, int nz, const float* dv, float dvmax, float minvel, float maxvel);
+
     // optional growing host destination of the COO rows (used when several engines share one call)
     std::vector<float>* grow_rw = nullptr;
     std::vector<int>* grow_iw = nullptr;
@@ -372,7 +382,9 @@ struct Engine {
     // leaves kRowsJoint (its system, Laplacian rows included: not rows to build from again).
     // kRowsMaps: map rows (dsa_solve_rows_maps) of G_map_blocks blocks on G_map_nmaps maps of an nx x ny vertex grid; only
     // dsa_iteration_system_maps_device takes them, and leaves kRowsMapSystem
-    enum RowsKind { kRowsNone, kRowsIsotropic, kRowsAzimuthal, kRowsJoint, kRowsMaps, kRowsMapSystem };
+    // kRowsRadial: radial rows (dsa_solve_rows_radial) of a Vsv and a Vsh block; only dsa_iteration_system_radial_device
+    // takes them, and leaves kRowsRadialSystem
+    enum RowsKind { kRowsNone, kRowsIsotropic, kRowsAzimuthal, kRowsJoint, kRowsMaps, kRowsMapSystem, kRowsRadial, kRowsRadialSystem };
     RowsKind G_kind = kRowsNone;
     int G_map_blocks = 0, G_map_nmaps = 0, G_map_nx = 0, G_map_ny = 0;
     template <class T> int ensure_keep(DevBuf<T>& b, size_t n, size_t used);

@@ -241,7 +241,7 @@ int Engine::dispersion_commit(bool host_copy)
     disp_failures.clear();
     disp_map_mark.assign((size_t)disp_nmaps * disp_nmodels, DispMark{});
     disp_slot_mark.assign((size_t)disp_kmax_total, DispMark{});
-    have_sens = false; sazi_ready = false;
+    have_sens = false; sazi_ready = false; radial_sens = false;
     stats[DSA_STAT_MS_DISPERSION] = 0.0;
     stats[DSA_STAT_CURVES] = 0.0;
     return 0;
@@ -540,6 +540,7 @@ int Engine::columns_stage_out(int models, float* dv, int* nused, double* chi2, i
     const size_t ncol = (size_t)disp_nx * disp_ny, nm = (size_t)models, M = (size_t)disp_nz - 1;
     for (DispMark& m : disp_map_mark) m.fresh = false;
     for (DispMark& m : disp_slot_mark) m.fresh = false;
+    radial_sens = false;      // (the depth factors of the Frechet rows are those of the models before the step)
     h_vels.resize(ncol * disp_nz);
     HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, h_vels.size() * 4, hipMemcpyDeviceToHost, stream));
     if (models == 2) {
@@ -880,7 +881,33 @@ int Engine::kernels_from_dispersion()
     launch_sen_combine((int)ncol, disp_kmax_total, disp_nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0, Srow.p, stream);
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
-    sens_nz = disp_nz; sens_kmax = disp_kmax_total; have_sens = true; sazi_ready = false;
+    sens_nz = disp_nz; sens_kmax = disp_kmax_total; have_sens = true; sazi_ready = false; radial_sens = false;
+    return 0;
+}
+
+// dsa_kernels_from_dispersion_radial: the depth factors of the Frechet rows on a radial stage, slot by slot from the
+// model the slot's run read -- Vsh at a Love slot, Vsv at a Rayleigh slot, by the slots' marks, all of which must be fresh -- and the slots'
+// block table for the emitter.  Everything is checked before the device is touched.
+int Engine::kernels_from_dispersion_radial()
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "radial depth kernels: call dsa_dispersion_begin_radial / run first"); return DSA_ERR_STATE; }
+    if (!disp_radial || disp_nmodels != 1) { fail(DSA_ERR_STATE, "radial depth kernels: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    std::vector<unsigned char> block((size_t)disp_kmax_total, 0);
+    for (int s = 0; s < disp_kmax_total; ++s) {
+        const DispMark& m = disp_slot_mark[(size_t)s];
+        if (!m.fresh) { fail(DSA_ERR_STATE, "radial depth kernels: depth-kernel slot %d of %d holds no kernels of the present models (dsa_dispersion_run with kernels first)", s, disp_kmax_total); return DSA_ERR_STATE; }
+        block[(size_t)s] = m.iwave == 1 ? 1 : 0;
+    }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny;
+    radial_sens = false;
+    if (ensure(Srow, ncol * disp_kmax_total * (disp_nz - 1)) || ensure(radial_block, block.size())) return status;
+    HIP_TRY(this, hipMemcpyAsync(radial_block.p, block.data(), block.size(), hipMemcpyHostToDevice, stream));
+    launch_sen_combine_radial((int)ncol, disp_kmax_total, disp_nz, vels_d.p, vsh_d.p, radial_block.p, sen_vs.p, sen_vp.p, sen_rho.p, h_depz[disp_nz - 2] < 35.0f ? 1 : 0,
+                              Srow.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    sens_nz = disp_nz; sens_kmax = disp_kmax_total; have_sens = true; sazi_ready = false; radial_sens = true;
     return 0;
 }
 
@@ -1772,7 +1799,7 @@ int Engine::set_sensitivity(int nz, int kmax, const float* vels, const float* de
     launch_sen_combine((int)ncol, kmax, nz, vels_d.p, sen_vs.p, sen_vp.p, sen_rho.p, depz[nz - 2] < 35.0f ? 1 : 0, Srow.p, stream);
     HIP_TRY(this, hipGetLastError());
     HIP_TRY(this, hipStreamSynchronize(stream));
-    sens_nz = nz; sens_kmax = kmax; have_sens = true; sazi_ready = false;
+    sens_nz = nz; sens_kmax = kmax; have_sens = true; sazi_ready = false; radial_sens = false;
     return 0;
 }
 
@@ -1803,8 +1830,11 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
     z.Sazi = Sazi.p; z.slab_len = slab_len; z.slot_on = azi_slot_on.p; z.maxvp = g.nvx * g.nvz * (sens_nz - 1);
     RowMapArgs zm{};
     zm.slab_len = slab_len; zm.nblocks = azi_now ? 3 : 1; zm.nmaps = nmaps;
+    RowRadialArgs zr{};
+    zr.block = radial_block.p; zr.maxvp = z.maxvp;
     auto emit = [&](const RowArgs& a, bool write) {
-        if (maps_now) launch_row_emit_maps(g, a, zm, write, stream);
+        if (radial_now) launch_row_emit_radial(g, a, zr, write, stream);
+        else if (maps_now) launch_row_emit_maps(g, a, zm, write, stream);
         else if (azi_now) launch_row_emit_azi(g, a, z, write, stream);
         else launch_row_emit(g, a, write, stream);
     };
@@ -1851,7 +1881,7 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
                 HIP_TRY(this, hipMemcpyAsync(iw + *nar, a.iw, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
                 HIP_TRY(this, hipMemcpyAsync(col + *nar, a.col, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
             }
-            G_nar = *nar + total; G_kind = maps_now ? kRowsMaps : (azi_now ? kRowsAzimuthal : kRowsIsotropic);
+            G_nar = *nar + total; G_kind = radial_now ? kRowsRadial : maps_now ? kRowsMaps : (azi_now ? kRowsAzimuthal : kRowsIsotropic);
             if (maps_now) { G_map_blocks = azi_now ? 3 : 1; G_map_nmaps = nmaps; G_map_nx = g.nx; G_map_ny = g.ny; }
         } else if (total > 0) {
             if (ensure(coo_rw, (size_t)total) || ensure(coo_iw, (size_t)total) || ensure(coo_col, (size_t)total)) return status;
@@ -1978,6 +2008,57 @@ int Engine::update_maps(int nm, const float* dv, float dvmax, float minvel, floa
     for (float v : hv) if (v > 0.0f && 1.0f / v < hmin_slow) hmin_slow = 1.0f / v;
     mean_slowness_of_maps(hv.data(), nv, nm);
     return finish_maps(nm);
+}
+
+// dsa_solve_rows_radial: solve() whose rays emit radial rows (ray_kernels.hip: k_row_emit_radial) -- dsa_solve_rows'
+// entries with the columns of the units on Love slots in the Vsh block.  Host arrays, or (all three null) the rows stay on the device; the
+// option rows_on_device is left as it was found.
+int Engine::solve_radial(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar)
+{
+    const int given = (rw != nullptr) + (iw != nullptr) + (col != nullptr);
+    if (given != 0 && given != 3) { fail(DSA_ERR_ARGUMENT, "solve_rows_radial: rw / iw / col are all given or all NULL"); return DSA_ERR_ARGUMENT; }
+    if (!planned) { fail(DSA_ERR_STATE, "solve_rows_radial: call dsa_plan first"); return DSA_ERR_STATE; }
+    if (!have_sens || !radial_sens || !disp_ready || !disp_radial) { fail(DSA_ERR_STATE, "solve_rows_radial: no radial depth factors of the present models (the dispersion runs with kernels, then dsa_kernels_from_dispersion_radial, first)"); return DSA_ERR_STATE; }
+    if (g.nx != disp_nx || g.ny != disp_ny || sens_nz != disp_nz || sens_kmax != disp_kmax_total) { fail(DSA_ERR_STATE, "solve_rows_radial: the maps are %d x %d, the radial stage holds %d x %d columns (dsa_maps_from_dispersion first)", g.nx, g.ny, disp_nx, disp_ny); return DSA_ERR_STATE; }
+    if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_radial: one engine only"); return DSA_ERR_STATE; }
+    const long long maxvp = (long long)g.nvx * g.nvz * (sens_nz - 1);
+    if (2 * maxvp > 0x7fffffffLL) { fail(DSA_ERR_ARGUMENT, "solve_rows_radial: %lld columns do not fit an int", 2 * maxvp); return DSA_ERR_ARGUMENT; }
+    const bool option = rows_on_device;       // (as solve_maps: the option is left as it was found)
+    rows_on_device = given == 0;
+    radial_now = true;
+    const int rc = solve(dsurf, rw, iw, col, cap, nar);
+    rows_on_device = option;
+    radial_now = false;
+    return rc;
+}
+
+// dsa_update_radial: the step dv (2 maxvp values, the Vsv block then the Vsh block of a solution) applied to the two
+// resident models by k_update_radial; then what every step of the models owes the stage: the host copies follow, the marks are cleared, the
+// depth factors of the Frechet rows are stale.  The geometry stays, so the next dsa_dispersion_run works on the stepped models.
+int Engine::update_radial(int nx, int ny, int nz, const float* dv, float dvmax, float minvel, float maxvel)
+{
+    if (!disp_ready) { fail(DSA_ERR_STATE, "update_radial: call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    if (!disp_radial) { fail(DSA_ERR_STATE, "update_radial: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    if (nx != disp_nx || ny != disp_ny || nz != disp_nz) { fail(DSA_ERR_ARGUMENT, "update_radial: nx %d ny %d nz %d, the radial stage holds %d %d %d", nx, ny, nz, disp_nx, disp_ny, disp_nz); return DSA_ERR_ARGUMENT; }
+    if (nx < 3 || ny < 3 || nz < 2) { fail(DSA_ERR_ARGUMENT, "update_radial: a %d x %d x %d model has no unknowns", nx, ny, nz); return DSA_ERR_ARGUMENT; }
+    if (!dv) { fail(DSA_ERR_ARGUMENT, "update_radial: dv is required (dsa_lsmr returns its solution to the host)"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(dvmax) || dvmax <= 0.0f) { fail(DSA_ERR_ARGUMENT, "update_radial: dvmax %g must be finite and > 0", (double)dvmax); return DSA_ERR_ARGUMENT; }
+    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "update_radial: minvel %g > maxvel %g", (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t nn = (size_t)nx * ny * nz, nstep = 2 * (size_t)(nx - 2) * (ny - 2) * (nz - 1);
+    OwnedBuf<float> d_dv;
+    if (ensure(d_dv, nstep)) return status;
+    for (DispMark& m : disp_map_mark) m.fresh = false;
+    for (DispMark& m : disp_slot_mark) m.fresh = false;
+    radial_sens = false;
+    HIP_TRY(this, hipMemcpyAsync(d_dv.p, dv, nstep * 4, hipMemcpyHostToDevice, stream));
+    launch_update_radial(nx, ny, nz, d_dv.p, dvmax, minvel, maxvel, vels_d.p, vsh_d.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    h_vels.resize(nn); h_vsh.resize(nn);
+    HIP_TRY(this, hipMemcpyAsync(h_vels.data(), vels_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(h_vsh.data(), vsh_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
 }
 
 int Engine::get_maps(int nm, float* out_v)
@@ -2305,6 +2386,24 @@ int dsa_update_maps(dsa_engine* e, int nmaps, const float* dv, float dvmax, floa
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->update_maps(nmaps, dv, dvmax, minvel, maxvel);
+}
+
+int dsa_kernels_from_dispersion_radial(dsa_engine* e)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->kernels_from_dispersion_radial();
+}
+
+int dsa_solve_rows_radial(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar)
+{
+    if (!e || !nar) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->solve_radial(dsurf, rw, iw, col, capacity, nar);
+}
+
+int dsa_update_radial(dsa_engine* e, int nx, int ny, int nz, const float* dv, float dvmax, float minvel, float maxvel)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->update_radial(nx, ny, nz, dv, dvmax, minvel, maxvel);
 }
 
 int dsa_get_maps(dsa_engine* e, int nmaps, float* velv)

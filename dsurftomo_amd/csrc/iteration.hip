@@ -12,6 +12,7 @@
 #include "engine.h"
 #include "joint_system.h"
 #include "map_system.h"
+#include "radial_system.h"
 #include "spmv_state.h"
 
 namespace {
@@ -131,6 +132,29 @@ __global__ __launch_bounds__(256) void k_laplacian_maps(int nvx, int nvz, int nm
     }
 }
 
+// The rows below the data rows of the radial system (radial_system.h), written where the data rows are: thread t = (part, unknown `index`),
+// part 0 and 1 the Laplacian rows of the Vsv and Vsh blocks, part 2 the tie rows; every position, row, column and value is that header's.
+__global__ __launch_bounds__(256) void k_radial_system(int nvx, int nvz, int nl, int dall, long long first, float weight0, float weight_h, float aniso,
+                                                       float* __restrict__ rw, int* __restrict__ row, int* __restrict__ col)
+{
+    const long long maxvp = (long long)nvx * nvz * nl;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 3 * maxvp) return;
+    const int part = (int)(t / maxvp);
+    const long long index = t - part * maxvp;
+    const long long at = first + dsa::radial_first_entry(nvx, nvz, nl, part, index);
+    const int count = dsa::radial_row_entries(nvx, nvz, nl, part, index);
+    const int r = (int)dsa::radial_row(nvx, nvz, nl, dall, part, index);
+    for (int q = 0; q < count; ++q) {
+        long long c1;
+        int coef;
+        dsa::radial_entry(nvx, nvz, nl, part, index, q, &c1, &coef);
+        rw[at + q] = dsa::radial_value(part, coef, weight0, weight_h, aniso);
+        row[at + q] = r;
+        col[at + q] = (int)c1;
+    }
+}
+
 }  // namespace
 
 namespace dsa {
@@ -186,6 +210,8 @@ int dsa_iteration_system_device(dsa_engine* h, int nx, int ny, int nz, int dall,
     if (!h) return DSA_ERR_ARGUMENT;
     dsa::Engine* e = reinterpret_cast<dsa::Engine*>(h);
     if (nx < 3 || ny < 3 || nz < 2 || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_device: bad arguments"); return DSA_ERR_ARGUMENT; }
+    // (radial rows are resident whatever the option rows_on_device says: dsa_solve_rows_radial leaves them without it)
+    if (e->G_kind == dsa::Engine::kRowsRadial || e->G_kind == dsa::Engine::kRowsRadialSystem) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are radial rows (a Vsv and a Vsh block of columns): dsa_iteration_system_radial_device builds their system"); return DSA_ERR_STATE; }
     if (!e->rows_on_device || (e->G_nar > 0 && !e->G_rw.p)) { e->fail(DSA_ERR_STATE, "iteration_system_device: no rows on the device (option rows_on_device + dsa_solve_rows, or dsa_calsurfg with null arrays)"); return DSA_ERR_STATE; }
     if (e->G_kind == dsa::Engine::kRowsAzimuthal || e->G_kind == dsa::Engine::kRowsJoint) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are azimuthal rows (three blocks of columns): dsa_iteration_system_azimuthal_device builds their system"); return DSA_ERR_STATE; }
     if (e->G_kind == dsa::Engine::kRowsMaps || e->G_kind == dsa::Engine::kRowsMapSystem) { e->fail(DSA_ERR_STATE, "iteration_system_device: the rows on the device are map rows (columns per period): dsa_iteration_system_maps_device builds their system"); return DSA_ERR_STATE; }
@@ -357,6 +383,85 @@ int dsa_iteration_system_maps_device(dsa_engine* h, int nx, int ny, int nmaps, i
         float total = 0.0f, top = 0.0f;
         for (long long i = 0; i < per_block; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
         dws[2 * B] = top; dws[2 * B + 1] = total / (float)per_block;
+    }
+    *m_out = m;
+    *nar_out = nar;
+    return done(0);
+}
+
+// The radial Vsv | Vsh system of the direct inversion built where dsa_solve_rows_radial left its rows: the data rows
+// scaled exactly as in dsa_iteration_system_azimuthal_device (residual_weights, k_scale_rows, the right-hand side fl(residual * weight)), and
+// below the dall data rows what k_radial_system writes by radial_system.h -- the Laplacian rows of the Vsv block (weight0) and of the Vsh
+// block (weight_h), then maxvp tie rows {-aniso, +aniso} whose right-hand side is 0.0f - aniso * (vsh - vsv) at the unknown's node of the
+// resident models (their host copies, which every call that changes the models refreshes).  m = dall + 3 maxvp, n = 2 maxvp, the tie rows
+// also at aniso = 0.  norm[2 maxvp] adds |entry| over a column's data entries in storage order; dws[2 B], dws[2 B + 1] are block B's
+// {max, mean} of it.  Every argument is checked before the device is touched.
+int dsa_iteration_system_radial_device(dsa_engine* h, int nx, int ny, int nz, int dall, const float* obst, const float* dsyn, float threshold0,
+                                       float weight0, float weight_h, float aniso, float* cbst, float* datweight, float* norm, int* m_out,
+                                       long long* nar_out, float* dws)
+{
+    if (!h) return DSA_ERR_ARGUMENT;
+    dsa::Engine* e = reinterpret_cast<dsa::Engine*>(h);
+    if (nx < 3 || ny < 3 || nz < 2 || dall < 1 || !obst || !dsyn || !cbst || !datweight || !norm || !m_out || !nar_out || !dws) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_radial_device: bad arguments"); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(weight0) || weight0 < 0.0f || !std::isfinite(weight_h) || weight_h < 0.0f || !std::isfinite(aniso) || aniso < 0.0f) {
+        e->fail(DSA_ERR_ARGUMENT, "iteration_system_radial_device: weight0 %g, weight_h %g and aniso %g must be finite and >= 0", (double)weight0, (double)weight_h, (double)aniso);
+        return DSA_ERR_ARGUMENT;
+    }
+    const int nvx = nx - 2, nvz = ny - 2, nl = nz - 1;
+    const long long maxvp = (long long)nvx * nvz * nl;
+    if (dsa::radial_rows(nvx, nvz, nl, dall) > 0x7fffffffll) { e->fail(DSA_ERR_ARGUMENT, "iteration_system_radial_device: %lld rows do not fit an int", dsa::radial_rows(nvx, nvz, nl, dall)); return DSA_ERR_ARGUMENT; }
+    if (e->G_kind != dsa::Engine::kRowsRadial || e->G_nar < 1 || !e->G_rw.p) {
+        e->fail(DSA_ERR_STATE, "iteration_system_radial_device: %s (dsa_solve_rows_radial with null arrays first)",
+                e->G_kind == dsa::Engine::kRowsRadialSystem ? "the rows on the device are a radial system already" :
+                e->G_kind == dsa::Engine::kRowsNone ? "no radial rows on the device" : "the rows on the device are not radial rows");
+        return DSA_ERR_STATE;
+    }
+    if (!e->disp_ready || !e->disp_radial) { e->fail(DSA_ERR_STATE, "iteration_system_radial_device: no radial stage holds the models of the tie rows (dsa_dispersion_begin_radial first)"); return DSA_ERR_STATE; }
+    if (e->disp_nx != nx || e->disp_ny != ny || e->disp_nz != nz) {
+        e->fail(DSA_ERR_ARGUMENT, "iteration_system_radial_device: nx %d ny %d nz %d, the radial stage holds %d %d %d", nx, ny, nz, e->disp_nx, e->disp_ny, e->disp_nz);
+        return DSA_ERR_ARGUMENT;
+    }
+    const size_t nn = (size_t)nx * ny * nz;
+    if (e->h_vels.size() != nn || e->h_vsh.size() != nn) { e->fail(DSA_ERR_STATE, "iteration_system_radial_device: the radial stage's host copies of the models are missing"); return DSA_ERR_STATE; }
+    const long long nar_in = e->G_nar, nar = nar_in + dsa::radial_entries(nvx, nvz, nl);
+    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_radial_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_radial_device: too few data"); return rc; } }
+    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
+    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
+    for (long long i = 0; i < 2 * maxvp; ++i) cbst[dall + i] = 0.0f;
+    for (long long i = 0; i < maxvp; ++i) {
+        const size_t node = (size_t)dsa::radial_node(nvx, nvz, i);
+        const float d = e->h_vsh[node] - e->h_vels[node];
+        cbst[dall + 2 * maxvp + i] = 0.0f - aniso * d;
+    }
+    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_radial_device: hipSetDevice"); return DSA_ERR_DEVICE; }
+    dsa::DevBuf<float> d_w, d_norm;
+    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
+#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_radial_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
+    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)(2 * maxvp)) ||
+        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
+    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
+    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)(2 * maxvp) * 4, e->stream));
+    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
+    hipLaunchKernelGGL(k_radial_system, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, nar_in, weight0, weight_h, aniso,
+                       e->G_rw.p, e->G_row.p, e->G_col.p);
+    IT_TRY(hipGetLastError());
+    IT_TRY(hipStreamSynchronize(e->stream));
+    const int m = (int)dsa::radial_rows(nvx, nvz, nl, dall), n = (int)dsa::radial_columns(nvx, nvz, nl);
+    // (from here on the resident entries are a system, not rows to build from again -- also when a later step fails)
+    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsRadialSystem;
+    { const int rc = dsa::spmv_load_from_device(e, m, n, nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
+    e->spmv->radial = true;
+    dsa::spmv_abs_column_sums(e, d_norm.p);
+    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    IT_TRY(hipStreamSynchronize(e->stream));
+    IT_TRY(hipGetLastError());
+#undef IT_TRY
+    for (int B = 0; B < 2; ++B) {                                                              // main.f90:386-392, block by block
+        const float* nb = norm + (size_t)B * (size_t)maxvp;
+        float total = 0.0f, top = 0.0f;
+        for (long long i = 0; i < maxvp; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
+        dws[2 * B] = top; dws[2 * B + 1] = total / (float)maxvp;
     }
     *m_out = m;
     *nar_out = nar;

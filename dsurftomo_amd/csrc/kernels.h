@@ -277,6 +277,12 @@ void launch_row_emit_azi(const GridDesc& g, const RowArgs& a, const RowAziArgs& 
 // map rows: a.slab_stride spans nblocks slabs of slab_len floats; columns (B * nmaps + the unit's map) * layer + vertex
 struct RowMapArgs { size_t slab_len; int nblocks, nmaps; };
 void launch_row_emit_maps(const GridDesc& g, const RowArgs& a, const RowMapArgs& z, bool write, hipStream_t stream);
+// radial rows: launch_row_emit's entries with the column B * maxvp + k * layer + i + 1, B = block[the unit's sen_slot]
+struct RowRadialArgs { const unsigned char* block; int maxvp; };
+void launch_row_emit_radial(const GridDesc& g, const RowArgs& a, const RowRadialArgs& z, bool write, hipStream_t stream);
+// launch_sen_combine slot by slot from the right model: slot s reads d_vsh where block[s] != 0 (a Love slot) and d_vsv otherwise
+void launch_sen_combine_radial(int ncol, int kmax, int nz, const float* d_vsv, const float* d_vsh, const unsigned char* d_block, const double* d_sen_vs,
+                               const double* d_sen_vp, const double* d_sen_rho, int shallow, double* d_S, hipStream_t stream);
 // offsets[0..n] = exclusive prefix sums of counts[0..n-1]
 void launch_scan(const int* d_counts, int n, long long* d_offsets, hipStream_t stream);
 
@@ -301,6 +307,9 @@ void launch_pv_models(const double* d_curves, int ncol, int nmodels, int kmax, i
 void launch_to_float(const double* d_in, float* d_out, size_t n, hipStream_t stream);
 // velv[m][jj][kk + 1] += clamp(dv[m][jj - 1][kk], -dvmax, dvmax), clamped to [minvel, maxvel], for the interior vertices of nm maps; the outer ring keeps its values (stage_kernels.hip)
 void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_velv, hipStream_t stream);
+// the two (nz, ny, nx) models of a radial stage stepped in place: d_dv holds 2 maxvp values, the Vsv block then the Vsh
+// block, maxvp = (nx - 2)(ny - 2)(nz - 1); dsa_model_update's comparisons with dvmax in place of 0.5; the ring and the bottom depth stay
+void launch_update_radial(int nx, int ny, int nz, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_vsv, float* d_vsh, hipStream_t stream);
 // column_kernels.hip: the depth step of the interior columns of the (nz, ny, nx) model d_vels in place, one wavefront per
 // column.  d_obs / d_wt (null: 1): (K, ncol) fp32; d_pv: (K, ncol); d_S: (nz - 1, K, ncol), launch_sen_combine's; d_dv: (nz - 1, ncol);
 // d_nused / d_chi2 / d_flag: (ncol).  Only interior columns are written: the caller zeroes the outputs for the ring.  nz <= 64, K <= 60.

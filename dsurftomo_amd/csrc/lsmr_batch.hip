@@ -867,6 +867,12 @@ struct Entry {
         if (ndata && (*ndata < 1 || *ndata > m)) { e->fail(DSA_ERR_ARGUMENT, "%s: ndata %d outside 1..%d", name, *ndata, m); return DSA_ERR_ARGUMENT; }
         return 0;
     }
+    // the entry points that rebuild every row below the data with a member's weight: not on the radial system, whose tie rows lie there too
+    int no_tie_rows()
+    {
+        if (e->spmv && e->spmv->radial) { e->fail(DSA_ERR_STATE, "%s: the resident matrix is the radial system, whose tie rows below the data would be rescaled with the Laplacian rows", name); return DSA_ERR_STATE; }
+        return 0;
+    }
     // weight0 finite and > 0, then the `count` (weight, damp) pairs of the `noun`s ("member", "combo") finite and >= 0
     int weights(float weight0, int count, const char* noun, const float* weight, const float* damp)
     {
@@ -1365,6 +1371,7 @@ int dsa_lsmr_tradeoff(dsa_engine* h_, int nreal, int ndata, const float* b, floa
     Entry in{"lsmr_tradeoff"};
     LB_DO(in.open(h_, nreal >= 1 && nreal <= kMaxReal && b && weight && damp && istop && itn && est, "nreal < 1 or a null b / weight / damp / istop / itn / est"));
     LB_DO(in.matrix(&ndata));
+    LB_DO(in.no_tie_rows());
     LB_DO(in.weights(weight0, nreal, "member", weight, damp));
     return weighted_solve(in, nreal, 1, ndata, b, weight0, weight, damp, nullptr, atol, btol, conlim, itnlim, localSize, x, measures, nullptr, 0, istop, itn, est);
 }
@@ -1380,6 +1387,7 @@ int dsa_lsmr_crossval(dsa_engine* h_, int ncombo, int nfolds, int ndata, const f
     const long long members = (long long)ncombo * ((long long)nfolds + 1);
     if (members > kMaxReal) { e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: %d combos x (%d folds + 1) are more than the %d members one call takes", ncombo, nfolds, kMaxReal); return DSA_ERR_ARGUMENT; }
     LB_DO(in.matrix(&ndata));
+    LB_DO(in.no_tie_rows());
     size_t nres = 0;
     if (resid && (__builtin_mul_overflow((size_t)2 * (size_t)ncombo, (size_t)ndata, &nres) || nres > ((size_t)1 << 60) / 8)) {
         e->fail(DSA_ERR_ARGUMENT, "lsmr_crossval: resid of 2 x %d x %d values is more than one call takes", ncombo, ndata);

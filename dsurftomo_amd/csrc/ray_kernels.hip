@@ -105,6 +105,33 @@ void launch_sen_combine(int ncol, int kmax, int nz, const float* d_vels, const d
                        d_sen_vp, d_sen_rho, shallow, d_S);
 }
 
+// k_sen_combine slot by slot from the right model of a radial stage: slot s reads vsh where block[s] != 0 (a Love
+// slot) and vsv otherwise; the arithmetic of an element is k_sen_combine's, so its bits are launch_sen_combine's on that model
+__global__ void k_sen_combine_radial(int ncol, int kmax, int nz, const float* __restrict__ vsv, const float* __restrict__ vsh,
+                                     const unsigned char* __restrict__ block, const double* __restrict__ sen_vs, const double* __restrict__ sen_vp,
+                                     const double* __restrict__ sen_rho, int shallow, double* __restrict__ S)
+{
+    const size_t n = (size_t)ncol * kmax * (nz - 1);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % ncol);
+    const int slot = (int)((i / ncol) % kmax);
+    const int k = (int)(i / ((size_t)ncol * kmax));
+    const float* vels = block[slot] ? vsh : vsv;
+    float a, r;
+    brocher_chain(vels[(size_t)k * ncol + c], shallow != 0, &a, &r);
+    S[i] = (sen_vp[i] * (double)a + sen_rho[i] * (double)r) + sen_vs[i];
+}
+
+void launch_sen_combine_radial(int ncol, int kmax, int nz, const float* d_vsv, const float* d_vsh, const unsigned char* d_block, const double* d_sen_vs,
+                               const double* d_sen_vp, const double* d_sen_rho, int shallow, double* d_S, hipStream_t stream)
+{
+    const size_t n = (size_t)ncol * kmax * (nz - 1);
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_sen_combine_radial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ncol, kmax, nz, d_vsv, d_vsh, d_block, d_sen_vs,
+                       d_sen_vp, d_sen_rho, shallow, d_S);
+}
+
 // Sazi[(k * kmax + slot) * ncol + c] = sen_vs * (double)(0.5f * vels[k * ncol + c]): the depth factor of the gc / gs entries,
 // d c / d (Gc/L) = (Vs / 2) d c / d Vs per layer; fp64, one rounding
 __global__ void k_sen_azimuthal(int ncol, int kmax, int nz, const float* __restrict__ vels, const double* __restrict__ sen_vs,
@@ -313,6 +340,57 @@ void launch_row_emit_maps(const GridDesc& g, const RowArgs& a, const RowMapArgs&
     if (a.n <= 0) return;
     if (write) hipLaunchKernelGGL(k_row_emit_maps<true>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
     else hipLaunchKernelGGL(k_row_emit_maps<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
+}
+
+// The radial row of a ray: k_row_emit's entries, order and values -- S already holds the depth factor of the unit's
+// slot on the model of its wave type -- with the column moved into the block of that slot: B * maxvp + k * layer + i + 1, B = z.block[slot]
+// (0 a Rayleigh slot: Vsv, 1 a Love slot: Vsh).
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_row_emit_radial(GridDesc g, RowArgs a, RowRadialArgs z)
+{
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= a.n) return;
+    const RayDesc rd = a.rays[a.trace_ids[t]];
+    const int slot = a.src[rd.src - a.unit_base].sen_slot;
+    const float* slab = a.slabs + (size_t)t * a.slab_stride;
+    const int* vl = a.vlist + (size_t)t * a.vlist_stride;
+    const int nv = a.nv[t];
+    const int nvx = g.nvx, ldx = g.nvx + 2, ncol = g.nx * g.ny, layer = g.nvx * g.nvz;
+    const int col0 = (z.block[slot] ? z.maxvp : 0) + 1;
+    const long long off = WRITE ? a.offsets[t] : 0;
+    int cnt = 0;
+    for (int k = 0; k < a.nz - 1; ++k) {
+        const double* Sk = a.S + ((size_t)k * a.kmax + slot) * ncol;
+        for (int base = 0; base < nv; base += 64) {
+            const int e = base + lane;
+            bool keep = false;
+            float val = 0.0f;
+            int i = 0;
+            if (e < nv) {
+                i = vl[e];
+                const int jj = i / nvx + 1, kk = i - (jj - 1) * nvx + 1;
+                const float f = slab[(size_t)jj * ldx + kk];
+                val = (float)(Sk[jj * g.nx + kk] * (double)f);
+                keep = fabsf(val) > kFtol;
+            }
+            const unsigned long long m = __ballot(keep);
+            if (WRITE && keep) {
+                const long long p = off + cnt + lanes_below(m);
+                a.rw[p] = val;
+                a.iw[p] = rd.data + 1;
+                a.col[p] = col0 + k * layer + i;
+            }
+            cnt += __popcll(m);
+        }
+    }
+    if (!WRITE && lane == 0) a.counts[t] = cnt;
+}
+
+void launch_row_emit_radial(const GridDesc& g, const RowArgs& a, const RowRadialArgs& z, bool write, hipStream_t stream)
+{
+    if (a.n <= 0) return;
+    if (write) hipLaunchKernelGGL(k_row_emit_radial<true>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
+    else hipLaunchKernelGGL(k_row_emit_radial<false>, dim3((a.n + 3) / 4), dim3(256), 0, stream, g, a, z);
 }
 
 // one workgroup: per-thread segment sums, scan of the 1024 sums in LDS, segment rewrite

@@ -316,7 +316,7 @@ int load_from_device(Engine* e, int m, int n, long long nar, const float* d_rw, 
 {
     if (!e->spmv) e->spmv = new SpmvState();
     SpmvState& S = *e->spmv;
-    S.m = m; S.n = n; S.nar = nar;
+    S.m = m; S.n = n; S.nar = nar; S.radial = false;
     dsa::spmv_invalidate_contiguous(&S);
     int rc = 0;
     if (e->ensure(S.x, (size_t)n) || e->ensure(S.y, (size_t)m)) rc = e->status;

@@ -34,6 +34,9 @@ struct SpmvState {
         std::vector<DevBuf<int>> data_len;
     };
     Ordering by_row, by_col;
+    // the matrix is dsa_iteration_system_radial_device's: below the data rows it holds tie rows as well as Laplacian rows, which the entry
+    // points that rebuild every row below the data with another weight refuse (dsa_lsmr_tradeoff, dsa_lsmr_crossval); cleared by every load
+    bool radial = false;
     DevBuf<float> x, y;
     // LSMR work vectors (lsmr.hip)
     DevBuf<float> u, v, h, hbar, xs, localV, scal;

@@ -3,6 +3,7 @@
 #include "kernels.h"
 #include "receiver_core.h"
 #include "exact_march.h"
+#include "radial_system.h"
 
 namespace dsa {
 
@@ -87,6 +88,35 @@ void launch_update_maps(const GridDesc& g, int nm, const float* d_dv, float dvma
     const size_t n = (size_t)g.nvx * g.nvz * nm;
     if (n == 0) return;
     hipLaunchKernelGGL(k_update_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g.nvx, g.nvz, nm, d_dv, dvmax, minvel, maxvel, d_velv);
+}
+
+// The update of the two resident models of a radial stage (dsa_update_radial): thread t = (block B, unknown index) steps
+// node (k, j + 1, i + 1) of Vsv (B = 0) or Vsh (B = 1) by dv[t] clipped to +-dvmax, then clamps it to [minvel, maxvel], in dsa_model_update's
+// order of comparisons (plain fp32, a NaN stays a NaN).  The ring and the bottom depth are no unknowns: no thread writes them.
+__global__ void k_update_radial(int nvx, int nvz, int nl, const float* __restrict__ dv, float dvmax, float minvel, float maxvel, float* __restrict__ vsv,
+                                float* __restrict__ vsh)
+{
+    const size_t maxvp = (size_t)nvx * nvz * nl;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * maxvp) return;
+    const size_t B = t / maxvp;
+    const size_t at = (size_t)radial_node(nvx, nvz, (long long)(t - B * maxvp));
+    float* model = B == 0 ? vsv : vsh;
+    float d = dv[t];
+    if (d >= dvmax) d = dvmax;
+    if (d <= -dvmax) d = -dvmax;
+    float v = model[at];
+    v = v + d;
+    if (v < minvel) v = minvel;
+    if (v > maxvel) v = maxvel;
+    model[at] = v;
+}
+
+void launch_update_radial(int nx, int ny, int nz, const float* d_dv, float dvmax, float minvel, float maxvel, float* d_vsv, float* d_vsh, hipStream_t stream)
+{
+    const size_t n = 2 * (size_t)(nx - 2) * (ny - 2) * (nz - 1);
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_update_radial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, nx - 2, ny - 2, nz - 1, d_dv, dvmax, minvel, maxvel, d_vsv, d_vsh);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -112,6 +112,10 @@ def declare_solvers(L):
     L.dsa_columns_step_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_step_radial_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 8 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_resolution_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [C.c_double, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 5
+    L.dsa_kernels_from_dispersion_radial.argtypes = [_vp]
+    L.dsa_solve_rows_radial.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dsa_iteration_system_radial_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 4 + [_vp] * 6
+    L.dsa_update_radial.argtypes = [_vp] + [_i32] * 3 + [_vp] + [_f32] * 3
     L.dsa_spmv_load.argtypes = [_vp, _i32, _i32, C.c_longlong, _vp, _vp, _vp]
     L.dsa_lsmr.argtypes = [_vp, _vp, _f32] + solve + [_vp] * 8
     L.dsa_lsmr_batch.argtypes = [_vp, _i32, _vp, _vp, _f32] + solve + [_vp] * 4
@@ -580,6 +584,61 @@ class Engine:
         vsv = np.zeros((nz, ny, nx), np.float32); vsh = np.zeros((nz, ny, nx), np.float32)
         self._check(self._L.dsa_dispersion_get_model_radial(self._h, vsv.ctypes.data_as(_vp), vsh.ctypes.data_as(_vp)))
         return vsv, vsh
+
+    # ---- radial anisotropy in the direct inversion --------------------------
+    def kernels_from_dispersion_radial(self):
+        """dsa_kernels_from_dispersion_radial: the depth factors of the Frechet rows on a radial stage, every slot from the model of its
+        wave type; every slot must carry kernels of the present models"""
+        self._check(self._L.dsa_kernels_from_dispersion_radial(self._h))
+
+    def solve_rows_radial(self, capacity):
+        """solve_rows with the columns of the units on Love slots moved into the Vsh block (dsa_solve_rows_radial): column
+        B * maxvp + isotropic column, B = 0 (Vsv, Rayleigh), 1 (Vsh, Love); returns (times, rw, row, col)"""
+        out = np.zeros(self._ndata, np.float32)
+        rw = np.zeros(capacity, np.float32)
+        iw = np.zeros(capacity, np.int32)
+        col = np.zeros(capacity, np.int32)
+        nar = C.c_longlong(0)
+        self._check(self._L.dsa_solve_rows_radial(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
+                                                  C.c_longlong(capacity), C.byref(nar)))
+        n = nar.value
+        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+
+    def solve_rows_radial_device(self, capacity=1 << 62):
+        """solve_rows_radial with the rows left on the device for iteration_system_radial_device: returns (times, number of entries)"""
+        out = np.zeros(self._ndata, np.float32)
+        nar = C.c_longlong(0)
+        self._check(self._L.dsa_solve_rows_radial(self._h, _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
+        return out, nar.value
+
+    def iteration_system_radial_device(self, nx, ny, nz, obst, dsyn, threshold0, weight0, weight_h=None, aniso=0.0):
+        """dsa_iteration_system_radial_device on the radial rows left on the device.  Returns dict(m, n, nar, cbst (m,), datweight (dall,),
+        norm (n,), dws (2, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
+        f = np.float32
+        obst = np.ascontiguousarray(obst, f); dsyn = np.ascontiguousarray(dsyn, f)
+        dall = obst.size
+        if dsyn.size != dall:
+            raise ValueError("obst and dsyn differ in length")
+        maxvp = max(nx - 2, 0) * max(ny - 2, 0) * max(nz - 1, 0)
+        n = 2 * maxvp
+        cbst = np.zeros(dall + 3 * maxvp, f); datweight = np.zeros(dall, f); norm = np.zeros(max(n, 1), f); dws = np.zeros(4, f)
+        m, nar = C.c_int(0), C.c_longlong(0)
+        self._check(self._L.dsa_iteration_system_radial_device(self._h, int(nx), int(ny), int(nz), dall, _p(obst), _p(dsyn), float(threshold0), float(weight0),
+                                                               float(weight0 if weight_h is None else weight_h), float(aniso), cbst.ctypes.data_as(_vp),
+                                                               datweight.ctypes.data_as(_vp), norm.ctypes.data_as(_vp), C.byref(m), C.byref(nar), dws.ctypes.data_as(_vp)))
+        self._mn = (m.value, n)
+        return dict(m=m.value, n=n, nar=nar.value, cbst=cbst, datweight=datweight, norm=norm[:n], dws=dws.reshape(2, 2))
+
+    def update_radial(self, dv, dvmax, minvel, maxvel):
+        """dsa_update_radial: dv, 2 (nx - 2)(ny - 2)(nz - 1) values (the Vsv block then the Vsh block of a solution; any shape), applied to the
+        two resident models of dispersion_begin_radial; the runs and kernels_from_dispersion_radial again afterwards.  ValueError when dv
+        does not hold exactly that many values: the library reads that many."""
+        nx, ny, nz = self._disp
+        dv = np.ascontiguousarray(dv, np.float32)
+        want = 2 * max(nx - 2, 0) * max(ny - 2, 0) * max(nz - 1, 0)
+        if dv.size != want:
+            raise ValueError("update_radial: dv holds %d values, two models of %d x %d x %d nodes need %d" % (dv.size, nx, ny, nz, want))
+        self._check(self._L.dsa_update_radial(self._h, nx, ny, nz, _p(dv), float(dvmax), float(minvel), float(maxvel)))
 
     # ---- matrix-vector products of the inversion step (reference aprod) ---------------------------
     def spmv_load(self, m, n, rw, row, col):

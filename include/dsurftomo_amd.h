@@ -600,6 +600,44 @@ int dsa_columns_step_radial_lateral(dsa_engine* e, int nmaps, const float* obs, 
 int dsa_columns_resolution_radial(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, float aniso,
                                   double* measures, double* pair, double* leverage, double* trace, int* nused, int* flag, double* R);
 
+/* Radial anisotropy in the direct 3-D inversion (extension): a radial stage (dsa_dispersion_begin_radial) through the whole
+ * direct loop on the device.  Rayleigh data touch only Vsv, Love data only Vsh; the cross sensitivities are neglected; each period's rays
+ * are traced through the map of the model of its wave type.  n = 2*maxvp unknowns, maxvp = (nx-2)(ny-2)(nz-1): the Vsv block, then Vsh.
+ *
+ * dsa_kernels_from_dispersion_radial: dsa_kernels_from_dispersion for a radial stage.  The depth factor of slot s is
+ * dsa_kernels_from_dispersion's rule on Vsh where the slot was run with iwave == 1 (Love) and on Vsv otherwise, bit for bit; a per-slot
+ * block table (0 Vsv, 1 Vsh) stays on the device.  DSA_ERR_STATE: no stage, a stage that is not radial, or one of the kmax_total slots
+ * without a fresh mark of a dsa_dispersion_run with kernels.  Afterwards dsa_solve_rows works on these factors, columns unshifted.
+ *
+ * dsa_solve_rows_radial: dsa_solve_rows whose entries of a unit on a Love slot have their column shifted by maxvp -- column
+ * B*maxvp + k*layer + i + 1, B the block of the unit's sen_slot -- entries, order, values and the |val| > 1e-4 rule unchanged.  rw / iw /
+ * col are all given (host COO) or all NULL: the rows stay on the device for dsa_iteration_system_radial_device, whatever the option
+ * rows_on_device says, which is left as found.  DSA_ERR_ARGUMENT: only some of the three arrays, or 2*maxvp beyond an int; DSA_ERR_STATE:
+ * no plan, no radial depth factors of the present models, or several engines sharing the call; DSA_ERR_CAPACITY as dsa_solve_rows.
+ *
+ * dsa_iteration_system_radial_device: the joint system on the rows dsa_solve_rows_radial left on the device.  The data rows, datweight and
+ * cbst[0 .. dall) exactly as dsa_iteration_system_azimuthal_device.  Below them (csrc/radial_system.h): the Laplacian rows of block 0
+ * weighted weight0 at rows dall + index, those of block 1 weighted weight_h at rows dall + maxvp + index, and maxvp tie rows at
+ * dall + 2*maxvp + index with the two entries { column index + 1, 0.0f - aniso }, { column maxvp + index + 1, aniso } and the right-hand
+ * side cbst = 0.0f - aniso * (vsh - vsv) (fp32) at the unknown's node of the resident models: the tie penalises the anisotropy of the
+ * stepped model.  The tie rows are always present: m = dall + 3*maxvp, n = 2*maxvp.  norm[2*maxvp] and dws[4] = { max, mean } per block
+ * as the azimuthal builder's.  Every argument is checked before the device is touched.  DSA_ERR_ARGUMENT: a NULL, bad dimensions, or
+ * weight0, weight_h or aniso negative or not finite; DSA_ERR_STATE: no radial rows resident, or a system already built from them;
+ * DSA_ERR_CAPACITY as the azimuthal builder.  dsa_lsmr, dsa_lsmr_batch, dsa_lsmr_resolution and dsa_resolution_blocks (nblocks = 2) run
+ * on the system; dsa_lsmr_tradeoff and dsa_lsmr_crossval, which would rescale the tie rows too, are DSA_ERR_STATE on it.
+ *
+ * dsa_update_radial: dv[2*maxvp], the Vsv block then the Vsh block, applied to the two resident models where they lie, with
+ * dsa_model_update's comparisons and dvmax in place of 0.5; the ring and the bottom depth stay.  The marks are cleared and the radial
+ * depth factors are stale afterwards: dsa_solve_rows_radial is DSA_ERR_STATE until the runs and dsa_kernels_from_dispersion_radial have
+ * been repeated.  DSA_ERR_STATE on a stage that is not radial; DSA_ERR_ARGUMENT: dimensions other than the stage's, a NULL dv, dvmax not
+ * finite or <= 0, minvel > maxvel. */
+int dsa_kernels_from_dispersion_radial(dsa_engine* e);
+int dsa_solve_rows_radial(dsa_engine* e, float* dsurf, float* rw, int* iw, int* col, long long capacity, long long* nar);
+int dsa_iteration_system_radial_device(dsa_engine* e, int nx, int ny, int nz, int dall, const float* obst, const float* dsyn, float threshold0,
+                                       float weight0, float weight_h, float aniso, float* cbst, float* datweight, float* norm, int* m_out,
+                                       long long* nar_out, float* dws);
+int dsa_update_radial(dsa_engine* e, int nx, int ny, int nz, const float* dv, float dvmax, float minvel, float maxvel);
+
 /* copy one unit's coarse travel-time field (nnz, nnx column-major) back; valid after dsa_solve
  * for units of the last chunk only unless keep_fields was requested */
 int dsa_get_dims(const dsa_engine* e, int* nnx, int* nnz);
