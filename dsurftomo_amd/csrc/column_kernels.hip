@@ -10,6 +10,7 @@
 // the same loop and kernels on the radial step's 2M unknowns per column; only k_radial_lateral_setup and
 // k_radial_lateral_start are that system's own.
 // k_latres_* (DESIGN.md section 27): the resolution of the laterally coupled step, a batch of section 24's solves, one lane per member.
+// k_sample_* (DESIGN.md section 29): the Metropolis chains of the Monte-Carlo depth inversion, one thread per (column, chain).
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -18,6 +19,7 @@
 #include "column_lateral.h"
 #include "column_radial_lateral.h"
 #include "column_lateral_resolution.h"
+#include "column_sample.h"
 
 namespace dsa {
 
@@ -313,6 +315,55 @@ __global__ void __launch_bounds__(64) k_latres_measures(LatResBatch B, double* _
     latres_measures(B, (int)blockIdx.x, measures, (int)threadIdx.x, 64);
 }
 
+// The Monte-Carlo depth inversion: column_sample.h on every (column, chain) of a sample stage, thread t = chain *
+// ncol + column -- the column is the fastest index of the model store (depth, chain, column) and of the map store (chain, map, column), so
+// a wavefront's loads and stores of one depth or one map are consecutive.  The view is passed by value.  No thread reads what another one
+// writes in the same launch: the used mask, the flag and chain 0's figures a chain needs were written by an earlier launch or are computed
+// again by the chain itself.  No LDS, no atomics.
+constexpr int kSampleBlock = 256;
+
+__device__ __forceinline__ bool sample_thread(const SampleView& S, long long* c, int* q)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x;
+    if (t >= S.ncol * S.C) return false;
+    *q = (int)(t / S.ncol);
+    *c = t - (long long)*q * S.ncol;
+    return true;
+}
+
+// phase 0: the chains' start models and the cleared state, before the set-up's dispersion runs; phase 1: the used mask, phi, psi and the
+// chains put back, after them
+__global__ void __launch_bounds__(kSampleBlock) k_sample_setup(SampleView S, int phase)
+{
+    long long c; int q;
+    if (!sample_thread(S, &c, &q)) return;
+    if (phase == 0) sample_setup_models(S, c, q);
+    else sample_setup_state(S, c, q);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_propose(SampleView S, int sweep)
+{
+    long long c; int q;
+    if (!sample_thread(S, &c, &q)) return;
+    sample_propose(S, c, q, sweep);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_accept(SampleView S, int sweep)
+{
+    long long c; int q;
+    if (!sample_thread(S, &c, &q)) return;
+    sample_accept(S, c, q, sweep);
+}
+
+// one thread per (column, depth): t = depth * ncol + column.  nodes (5, M, ncol), cols (3, ncol), counts (8, ncol)
+__global__ void __launch_bounds__(kSampleBlock) k_sample_finish(SampleView S, double* __restrict__ nodes, double* __restrict__ cols, int* __restrict__ counts)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x;
+    if (t >= S.ncol * (S.nz - 1)) return;
+    const int l = (int)(t / S.ncol);
+    sample_finish(S, t - (long long)l * S.ncol, l, nodes, cols, counts);
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -544,6 +595,35 @@ void launch_latres_measures(const LatResSystem& r, double* d_measures, hipStream
     if (coupled_empty(r.s)) return;
     latres_phase<5>(r, stream);
     hipLaunchKernelGGL(k_latres_measures, dim3((unsigned)(r.Sc / kLatResGroup)), dim3(64), 0, stream, latres_view(r), d_measures);
+}
+
+// ---- the Monte-Carlo depth inversion ----
+
+static dim3 sample_grid(long long n) { return dim3((unsigned)((n + kSampleBlock - 1) / kSampleBlock)); }
+static bool sample_empty(const SampleView& S) { return S.ncol < 1 || S.C < 1 || S.nz < 2; }
+
+void launch_sample_setup(const SampleView& S, int phase, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_setup, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, phase);
+}
+
+void launch_sample_propose(const SampleView& S, int sweep, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_propose, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, sweep);
+}
+
+void launch_sample_accept(const SampleView& S, int sweep, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_accept, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, sweep);
+}
+
+void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_finish, sample_grid(S.ncol * (S.nz - 1)), dim3(kSampleBlock), 0, stream, S, d_nodes, d_cols, d_counts);
 }
 
 }  // namespace dsa

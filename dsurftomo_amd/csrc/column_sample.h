@@ -1,0 +1,387 @@
+// Monte-Carlo depth inversion of the period maps: C Metropolis chains per column of Vs(z), M = nz - 1 unknowns (the
+// bottom depth is kept), K data in slot order.  The chains are the models of a multi-model dispersion stage; this header is the rest of a
+// sweep -- the proposal, the misfit, the prior, the Metropolis test, the running moments -- and the finish.
+//
+//   box       per depth, fp32: lo_l = max(minvel, v0_l - width), hi_l = min(maxvel, v0_l + width)
+//   numbers   counter-based: x = seed; for w in (column, chain, sweep, draw): x = mix(x + 0x9E3779B97F4A7C15 + w), mix splitmix64's
+//             finaliser; k = x >> 11, u = k 2^-53 (exact).  Sweep 0 is the set-up (draw = the depth), the sweeps count from 1
+//             (draw 0: the node, 1: the step, 2: the Metropolis test)
+//   neglog    sample_neglog(k) = -ln(k 2^-53), k >= 1: exponent and mantissa by integer operations, the mantissa m in [sqrt(1/2), sqrt(2)),
+//             ln m = 2 s (1 + s^2/3 + ... + s^22/23), s = (m - 1) / (m + 1), eleven terms whatever k; plain fp64, no libm
+//   used      decided once per column on chain 0's curves at the set-up: wt_k > 0, obs_k > 0 and pv_k > 0.  nused = 0: flag 2, never moved
+//   data      a_k = (double)wt_k, r_k = (double)obs_k - pv_k, rho_k = a_k r_k, phi = sum rho_k^2 over the used k ascending, from 0.0
+//   prior     psi = (double)smooth^2 sum_rows (L v)^2_row, column_system.h's L, v in double; a row is summed from 0.0 over its unknowns
+//             ascending; the rows in order: top, the centred rows 1 .. M-2, bottom
+//   proposal  l = min((int)(u M), M - 1), delta = step (2u - 1), v' = v_l + (float)delta in fp32; outside [lo_l, hi_l]: nothing is written
+//   accept    any used pv <= 0 (or NaN): no root, rejected.  Delta = (phi' + psi') - (phi + psi); accepted when Delta is not NaN and
+//             (Delta <= 0 or k == 0 or Delta / (2 temperature) < sample_neglog(k)); a rejection puts the node's old value back
+//   moments   in the sweeps after burn, per chain and depth: d = (double)v_l - (double)v0_l, S1 += d, S2 += d d; phisum += phi, nkept += 1;
+//             the smallest phi + psi of the kept sweeps and its model (the first one wins a tie)
+//   finish    per (column, depth), chains ascending -- see sample_finish
+//
+// fp64 under -ffp-contract=off, no square root, IEEE division: one value per figure whatever computes it.  One thread per (column, chain)
+// (column_kernels.hip: k_sample_*) or a loop over them (tests/hostcheck_column_sample.cpp); a thread's sums are its own sequential chains and
+// no thread reads what another writes in the same launch, so the mapping cannot change a bit.
+// Layouts, column fastest everywhere: models and S1 / S2 / bestv (depth, chain, column); the maps (chain, map, column); obs / wt (map,
+// column); per-chain figures (chain, column); counters (4, chain, column): accepted, rejected (of any kind), out of box, no root.
+#pragma once
+
+#include "column_system.h"
+
+namespace dsa {
+
+// what the last sweep did with a chain's proposal
+enum { kSampleIdle = -1, kSamplePending = 0, kSampleOutOfBox = 1, kSampleAccepted = 2, kSampleRejected = 3, kSampleNoRoot = 4 };
+enum { kSampleCntAccepted = 0, kSampleCntRejected = 1, kSampleCntOutOfBox = 2, kSampleCntNoRoot = 3, kSampleCounters = 4 };
+// the finish: per (column, depth) five doubles, per column three doubles and eight ints
+enum { kSampleMean = 0, kSampleVar = 1, kSampleW = 2, kSampleB = 3, kSampleBest = 4, kSampleNodeFigures = 5 };
+enum { kSamplePhiStart = 0, kSampleBestE = 1, kSampleMeanPhi = 2, kSampleColumnFigures = 3 };
+enum { kSampleNused = 0, kSampleFlag = 1, kSampleSumAccepted = 2, kSampleSumRejected = 3, kSampleSumOutOfBox = 4, kSampleSumNoRoot = 5, kSampleReseeded = 6,
+       kSampleNkept = 7, kSampleColumnCounts = 8 };
+
+// the whole state of a sample stage and its inputs, where they lie
+struct SampleView {
+    int nx, ny, nz, K, C, burn;
+    long long ncol;
+    unsigned long long seed;
+    double lam2, step, spread, two_t;                  // smooth^2, step, spread, 2 temperature
+    float width, minvel, maxvel;
+    const float* obs; const float* wt;                 // (K, ncol); wt may be null (1)
+    const float* v0;                                   // (nz, ncol): the start model
+    const double* pv;                                  // (C, K, ncol): the stage's map store
+    float* v;                                          // (nz, C, ncol): the stage's model store
+    double* phi; double* psi;                          // (C, ncol)
+    int* cnt;                                          // (4, C, ncol)
+    double* S1; double* S2;                            // (M, C, ncol)
+    double* phisum; int* nkept;                        // (C, ncol)
+    double* best_e; float* best_v;                     // (C, ncol), (M, C, ncol)
+    int* pnode; float* pold; int* pmark;               // (C, ncol): the last sweep's proposal
+    int* reseed;                                       // (C, ncol): 1 where the set-up put the chain back to the start
+    unsigned long long* used;                          // (ncol): bit k set where datum k is used
+    int* nused; int* flag;                             // (ncol)
+    double* phi0;                                      // (ncol): phi of the start
+};
+
+DSA_CS unsigned long long sample_mix(unsigned long long x)
+{
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the 53 bits of draw (column, chain, sweep, draw)
+DSA_CS unsigned long long sample_bits(unsigned long long seed, unsigned long long column, unsigned long long chain, unsigned long long sweep, unsigned long long draw)
+{
+    unsigned long long x = seed;
+    x = sample_mix(x + 0x9E3779B97F4A7C15ull + column);
+    x = sample_mix(x + 0x9E3779B97F4A7C15ull + chain);
+    x = sample_mix(x + 0x9E3779B97F4A7C15ull + sweep);
+    x = sample_mix(x + 0x9E3779B97F4A7C15ull + draw);
+    return x >> 11;
+}
+
+// u = k 2^-53, exact: k < 2^53
+DSA_CS double sample_unit(unsigned long long k) { return (double)k * 1.1102230246251565404e-16; }
+
+DSA_CS double sample_from_bits(unsigned long long b)
+{
+    double d;
+    __builtin_memcpy(&d, &b, sizeof d);
+    return d;
+}
+
+// -ln(k 2^-53) for 1 <= k < 2^53
+DSA_CS double sample_neglog(unsigned long long k)
+{
+    const int p = 63 - __builtin_clzll(k);                                      // the top bit: k = 1.f x 2^p
+    const unsigned long long frac = (k << (52 - p)) & 0x000FFFFFFFFFFFFFull;    // f, 52 bits
+    int n = p - 53;
+    unsigned long long ex = 1023ull;
+    if (frac > 0x0006A09E667F3BCCull) { ex = 1022ull; n += 1; }                 // m > sqrt(2): halve it
+    const double m = sample_from_bits((ex << 52) | frac);
+    const double s = (m - 1.0) / (m + 1.0), z = s * s;
+    double t = 1.0 / 23.0;
+    t = t * z + 1.0 / 21.0;
+    t = t * z + 1.0 / 19.0;
+    t = t * z + 1.0 / 17.0;
+    t = t * z + 1.0 / 15.0;
+    t = t * z + 1.0 / 13.0;
+    t = t * z + 1.0 / 11.0;
+    t = t * z + 1.0 / 9.0;
+    t = t * z + 1.0 / 7.0;
+    t = t * z + 1.0 / 5.0;
+    t = t * z + 1.0 / 3.0;
+    t = t * z + 1.0;
+    const double lnm = 2.0 * s * t, dn = (double)n;
+    const double r = dn * 6.93147180369123816490e-01 + (lnm + dn * 1.90821492927058770002e-10);      // ln 2 in two parts
+    return -r;
+}
+
+DSA_CS bool sample_interior(int nx, int ny, long long c)
+{
+    const int j = (int)(c / nx), i = (int)(c - (long long)j * nx);
+    return i >= 1 && i <= nx - 2 && j >= 1 && j <= ny - 2;
+}
+
+DSA_CS long long sample_at(const SampleView& S, long long c, int q) { return (long long)q * S.ncol + c; }
+DSA_CS long long sample_node(const SampleView& S, long long c, int q, int l) { return ((long long)l * S.C + q) * S.ncol + c; }
+
+DSA_CS void sample_box(const SampleView& S, long long c, int l, float* lo, float* hi)
+{
+    const float b = S.v0[(long long)l * S.ncol + c];
+    float a = b - S.width, z = b + S.width;
+    if (a < S.minvel) a = S.minvel;
+    if (z > S.maxvel) z = S.maxvel;
+    *lo = a; *hi = z;
+}
+
+// the used mask of column c from the curves of chain 0
+DSA_CS unsigned long long sample_used(const SampleView& S, long long c, int* nused)
+{
+    unsigned long long used = 0ull;
+    int n = 0;
+    for (int k = 0; k < S.K; ++k) {
+        const float o = S.obs[(long long)k * S.ncol + c], w = S.wt ? S.wt[(long long)k * S.ncol + c] : 1.0f;
+        const double p = S.pv[(long long)k * S.ncol + c];
+        if (w > 0.0f && o > 0.0f && p > 0.0) { used |= 1ull << k; ++n; }
+    }
+    *nused = n;
+    return used;
+}
+
+// phi of chain q over the used data; *noroot where a used datum has no root (the value returned is then not a misfit)
+DSA_CS double sample_phi(const SampleView& S, long long c, int q, unsigned long long used, bool* noroot)
+{
+    double phi = 0.0;
+    bool bad = false;
+    for (int k = 0; k < S.K; ++k) {
+        if (!((used >> k) & 1ull)) continue;
+        const double p = S.pv[((long long)q * S.K + k) * S.ncol + c];
+        if (!(p > 0.0)) { bad = true; continue; }
+        const double a = S.wt ? (double)S.wt[(long long)k * S.ncol + c] : 1.0;
+        const double r = (double)S.obs[(long long)k * S.ncol + c] - p;
+        const double rho = a * r;
+        phi += rho * rho;
+    }
+    *noroot = bad;
+    return phi;
+}
+
+// psi of the M values v[l * stride]
+DSA_CS double sample_psi(int M, double lam2, const float* v, long long stride)
+{
+    if (M < 2) return 0.0;
+    double s = 0.0;
+    {
+        double t = 0.0;
+        t += (double)v[0];
+        t -= (double)v[stride];
+        s += t * t;
+    }
+    for (int l = 1; l <= M - 2; ++l) {
+        double t = 0.0;
+        t -= (double)v[(l - 1) * stride];
+        t += 2.0 * (double)v[l * stride];
+        t -= (double)v[(l + 1) * stride];
+        s += t * t;
+    }
+    {
+        double t = 0.0;
+        t -= (double)v[(M - 2) * stride];
+        t += (double)v[(M - 1) * stride];
+        s += t * t;
+    }
+    return lam2 * s;
+}
+
+// the set-up before its dispersion runs: chain 0 is the start, chain q > 0 the start spread by draws (c, q, 0, l) and clipped to the box; the
+// ring's chains are all the start; the bottom depth is the start's; every figure of the state is cleared
+DSA_CS void sample_setup_models(const SampleView& S, long long c, int q)
+{
+    const int M = S.nz - 1;
+    const bool moves = q > 0 && sample_interior(S.nx, S.ny, c);
+    for (int l = 0; l < S.nz; ++l) {
+        float x = S.v0[(long long)l * S.ncol + c];
+        if (moves && l < M) {
+            const double u = sample_unit(sample_bits(S.seed, (unsigned long long)c, (unsigned long long)q, 0ull, (unsigned long long)l));
+            float lo, hi;
+            sample_box(S, c, l, &lo, &hi);
+            x = x + (float)(S.spread * (2.0 * u - 1.0));
+            if (x < lo) x = lo;
+            if (x > hi) x = hi;
+        }
+        S.v[sample_node(S, c, q, l)] = x;
+    }
+    const long long at = sample_at(S, c, q);
+    S.phi[at] = 0.0; S.psi[at] = 0.0; S.phisum[at] = 0.0; S.nkept[at] = 0; S.best_e[at] = 0.0;
+    S.pnode[at] = 0; S.pold[at] = 0.0f; S.pmark[at] = kSampleIdle; S.reseed[at] = 0;
+    for (int w = 0; w < kSampleCounters; ++w) S.cnt[((long long)w * S.C + q) * S.ncol + c] = 0;
+    for (int l = 0; l < M; ++l) { S.S1[sample_node(S, c, q, l)] = 0.0; S.S2[sample_node(S, c, q, l)] = 0.0; S.best_v[sample_node(S, c, q, l)] = 0.0f; }
+    if (q == 0) { S.used[c] = 0ull; S.nused[c] = 0; S.flag[c] = kColumnOk; S.phi0[c] = 0.0; }
+}
+
+// the set-up after its dispersion runs: the used mask from chain 0's curves (every chain of the column computes the same; chain 0 stores
+// it), phi and psi of the chain; a chain with a used datum without a root goes back to the start with chain 0's phi and psi; a column
+// without a used datum is flagged and all its chains go back to the start.  The ring is left alone.
+DSA_CS void sample_setup_state(const SampleView& S, long long c, int q)
+{
+    if (!sample_interior(S.nx, S.ny, c)) return;
+    const int M = S.nz - 1;
+    const long long at = sample_at(S, c, q);
+    int nused = 0;
+    const unsigned long long used = sample_used(S, c, &nused);
+    bool noroot = false;
+    const double phi_start = nused ? sample_phi(S, c, 0, used, &noroot) : 0.0;
+    if (q == 0) { S.used[c] = used; S.nused[c] = nused; S.flag[c] = nused ? kColumnOk : kColumnNoData; S.phi0[c] = phi_start; }
+    if (nused == 0) {
+        for (int l = 0; l < M; ++l) S.v[sample_node(S, c, q, l)] = S.v0[(long long)l * S.ncol + c];
+        return;
+    }
+    double phi = q == 0 ? phi_start : sample_phi(S, c, q, used, &noroot);
+    if (noroot) {
+        for (int l = 0; l < M; ++l) S.v[sample_node(S, c, q, l)] = S.v0[(long long)l * S.ncol + c];
+        S.reseed[at] = 1;
+        phi = phi_start;
+    }
+    S.phi[at] = phi;
+    S.psi[at] = sample_psi(M, S.lam2, S.v + sample_node(S, c, q, 0), (long long)S.C * S.ncol);
+}
+
+// a chain that is never moved: the ring's and a flagged column's
+DSA_CS bool sample_idle(const SampleView& S, long long c) { return !sample_interior(S.nx, S.ny, c) || S.flag[c] != kColumnOk; }
+
+// the proposal of sweep `sweep` (>= 1), before its dispersion runs
+DSA_CS void sample_propose(const SampleView& S, long long c, int q, int sweep)
+{
+    const long long at = sample_at(S, c, q);
+    if (sample_idle(S, c)) { S.pmark[at] = kSampleIdle; return; }
+    const int M = S.nz - 1;
+    const double u0 = sample_unit(sample_bits(S.seed, (unsigned long long)c, (unsigned long long)q, (unsigned long long)sweep, 0ull));
+    const double u1 = sample_unit(sample_bits(S.seed, (unsigned long long)c, (unsigned long long)q, (unsigned long long)sweep, 1ull));
+    int l = (int)(u0 * (double)M);
+    if (l > M - 1) l = M - 1;
+    const double delta = S.step * (2.0 * u1 - 1.0);
+    const float old = S.v[sample_node(S, c, q, l)];
+    const float x = old + (float)delta;
+    float lo, hi;
+    sample_box(S, c, l, &lo, &hi);
+    S.pnode[at] = l; S.pold[at] = old;
+    if (x < lo || x > hi) { S.pmark[at] = kSampleOutOfBox; return; }
+    S.v[sample_node(S, c, q, l)] = x;
+    S.pmark[at] = kSamplePending;
+}
+
+// the Metropolis test of sweep `sweep` after its dispersion runs, and the sweep's share of the moments
+DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep)
+{
+    const long long at = sample_at(S, c, q);
+    const int mark = S.pmark[at];
+    if (mark == kSampleIdle) return;
+    const int M = S.nz - 1;
+    const long long stride = (long long)S.C * S.ncol;
+    int* cnt = S.cnt + at;                      // counter w at cnt[w * stride]
+    if (mark == kSampleOutOfBox) {
+        cnt[kSampleCntOutOfBox * stride] += 1; cnt[kSampleCntRejected * stride] += 1;
+    } else {
+        bool noroot = false;
+        const double phi_new = sample_phi(S, c, q, S.used[c], &noroot);
+        bool accepted = false;
+        double psi_new = 0.0;
+        if (!noroot) {
+            psi_new = sample_psi(M, S.lam2, S.v + sample_node(S, c, q, 0), stride);
+            const double delta = (phi_new + psi_new) - (S.phi[at] + S.psi[at]);
+            if (delta == delta) {
+                if (delta <= 0.0) accepted = true;
+                else {
+                    const unsigned long long k = sample_bits(S.seed, (unsigned long long)c, (unsigned long long)q, (unsigned long long)sweep, 2ull);
+                    accepted = k == 0ull || delta / S.two_t < sample_neglog(k);
+                }
+            }
+        }
+        if (accepted) {
+            S.phi[at] = phi_new; S.psi[at] = psi_new;
+            cnt[kSampleCntAccepted * stride] += 1;
+            S.pmark[at] = kSampleAccepted;
+        } else {
+            S.v[sample_node(S, c, q, S.pnode[at])] = S.pold[at];
+            cnt[kSampleCntRejected * stride] += 1;
+            if (noroot) cnt[kSampleCntNoRoot * stride] += 1;
+            S.pmark[at] = noroot ? kSampleNoRoot : kSampleRejected;
+        }
+    }
+    if (sweep <= S.burn) return;
+    for (int l = 0; l < M; ++l) {
+        const long long e = sample_node(S, c, q, l);
+        const double d = (double)S.v[e] - (double)S.v0[(long long)l * S.ncol + c];
+        S.S1[e] += d;
+        S.S2[e] += d * d;
+    }
+    const double energy = S.phi[at] + S.psi[at];
+    S.phisum[at] += S.phi[at];
+    if (S.nkept[at] == 0 || energy < S.best_e[at]) {
+        S.best_e[at] = energy;
+        for (int l = 0; l < M; ++l) S.best_v[sample_node(S, c, q, l)] = S.v[sample_node(S, c, q, l)];
+    }
+    S.nkept[at] += 1;
+}
+
+// The finish of (column c, depth l < M), chains ascending, every sum from 0.0; n = nkept (the same for every chain of a column), m_q =
+// S1_q / n, w_q = S2_q / n - m_q m_q.  nodes (5, M, ncol): the pooled mean v0 + sum S1 / (n C), the pooled variance sum S2 / (n C) -
+// (sum S1 / (n C))^2, W = sum w_q / C, B = sum (m_q - sum m_q / C)^2 / (C - 1) (0 for C = 1), and the node of the best model: the chain with
+// the smallest best phi + psi, the first one at a tie.  The thread of l = 0 also writes the column's figures: cols (3, ncol): phi of the
+// start, the best phi + psi, the mean kept phi; counts (8, ncol): nused, flag, the four counters summed over the chains, the chains put
+// back at the set-up, nkept.  Without a kept sweep (n = 0: the ring, a flagged column, burn >= the sweeps run) every figure of nodes, the
+// best phi + psi and the mean kept phi are 0.
+DSA_CS void sample_finish(const SampleView& S, long long c, int l, double* nodes, double* cols, int* counts)
+{
+    const int M = S.nz - 1, C = S.C;
+    const int n = S.nkept[sample_at(S, c, 0)];
+    const double dn = (double)n, dc = (double)C;
+    int best_q = 0;
+    for (int q = 1; q < C; ++q)
+        if (S.best_e[sample_at(S, c, q)] < S.best_e[sample_at(S, c, best_q)]) best_q = q;
+    double out[kSampleNodeFigures] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    if (n > 0) {
+        double s1 = 0.0, s2 = 0.0, sw = 0.0, sm = 0.0;
+        for (int q = 0; q < C; ++q) {
+            const long long e = sample_node(S, c, q, l);
+            const double m = S.S1[e] / dn;
+            s1 += S.S1[e];
+            s2 += S.S2[e];
+            sw += S.S2[e] / dn - m * m;
+            sm += m;
+        }
+        const double pm = s1 / (dn * dc), mbar = sm / dc;
+        double sb = 0.0;
+        for (int q = 0; q < C; ++q) {
+            const double d = S.S1[sample_node(S, c, q, l)] / dn - mbar;
+            sb += d * d;
+        }
+        out[kSampleMean] = (double)S.v0[(long long)l * S.ncol + c] + pm;
+        out[kSampleVar] = s2 / (dn * dc) - pm * pm;
+        out[kSampleW] = sw / dc;
+        out[kSampleB] = C > 1 ? sb / (dc - 1.0) : 0.0;
+        out[kSampleBest] = (double)S.best_v[sample_node(S, c, best_q, l)];
+    }
+    for (int f = 0; f < kSampleNodeFigures; ++f) nodes[((long long)f * M + l) * S.ncol + c] = out[f];
+    if (l != 0) return;
+    int sums[kSampleCounters] = { 0, 0, 0, 0 }, reseeded = 0;
+    double phis = 0.0;
+    for (int q = 0; q < C; ++q) {
+        const long long at = sample_at(S, c, q);
+        for (int w = 0; w < kSampleCounters; ++w) sums[w] += S.cnt[((long long)w * C + q) * S.ncol + c];
+        reseeded += S.reseed[at];
+        phis += S.phisum[at];
+    }
+    cols[kSamplePhiStart * S.ncol + c] = S.phi0[c];
+    cols[kSampleBestE * S.ncol + c] = n > 0 ? S.best_e[sample_at(S, c, best_q)] : 0.0;
+    cols[kSampleMeanPhi * S.ncol + c] = n > 0 ? phis / (dn * dc) : 0.0;
+    counts[kSampleNused * S.ncol + c] = S.nused[c];
+    counts[kSampleFlag * S.ncol + c] = S.flag[c];
+    for (int w = 0; w < kSampleCounters; ++w) counts[(kSampleSumAccepted + w) * S.ncol + c] = sums[w];
+    counts[kSampleReseeded * S.ncol + c] = reseeded;
+    counts[kSampleNkept * S.ncol + c] = n;
+}
+
+}  // namespace dsa

@@ -356,6 +356,30 @@ struct Engine {
                                    const int* kind, const int* index, const double* models, int nrows, double* measures, double* info, double* full, int* nused,
                                    int* flag);
 
+    // Monte-Carlo depth inversion (dsa_columns_sample_*, k_sample_*): a stage of sample_chains models whose model store
+    // (vels_d) holds the chains; everything a sweep reads or writes stays on the device, the host keeps the plan of the runs, the parameters
+    // and the number of the last sweep.  sample_open: set by columns_sample_begin, cleared by every dispersion_setup; while it is set the
+    // column steps, the resolutions, dispersion_get_model and dispersion_failure are refused.  obs and wt lie in col_obs / col_wt.
+    bool sample_open = false, sample_has_wt = false;
+    int sample_sweep = 0, sample_burn = 0;
+    unsigned long long sample_seed = 0ull;
+    double sample_lam2 = 0.0, sample_step = 0.0, sample_spread = 0.0, sample_two_t = 0.0;
+    float sample_width = 0.0f, sample_minvel = 0.0f, sample_maxvel = 0.0f;
+    struct SampleRun { int iwave, igr, first; std::vector<double> t; };
+    std::vector<SampleRun> sample_plan;
+    OwnedBuf<float> smp_v0, smp_bestv, smp_pold;
+    OwnedBuf<double> smp_phi, smp_psi, smp_S1, smp_S2, smp_phisum, smp_beste, smp_phi0, smp_nodes, smp_cols;
+    OwnedBuf<int> smp_cnt, smp_nkept, smp_pnode, smp_pmark, smp_reseed, smp_nused, smp_flag, smp_counts;
+    OwnedBuf<unsigned long long> smp_used;
+    int columns_sample_begin(int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns, const int* iwave, const int* igr,
+                             const int* nper, const double* periods, int nmaps_in, const float* obs, const float* wt, float smooth, float step, float spread,
+                             float width, float temperature, float minvel, float maxvel, unsigned long long seed, int burn);
+    int columns_sample_run(int nsweeps);
+    int columns_sample_fetch(double* nodes, double* cols, int* counts);
+    int columns_sample_state(float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept, double* best_e, float* best_v,
+                             int* pnode, float* pold, int* pmark, int* reseeded);
+    int sample_refused(const char* who);
+
     // radial anisotropy in the direct inversion (dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial; DESIGN.md
     // section 28).  radial_sens: Srow holds the depth factors of every slot on the model of its wave type (k_sen_combine_radial) and
     // radial_block the slots' blocks (0 Vsv, 1 Vsh), both of the present models -- cleared by whatever changes the models, the marks or Srow.

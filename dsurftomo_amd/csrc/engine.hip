@@ -21,6 +21,7 @@
 #include "column_radial.h"
 #include "column_lateral.h"
 #include "column_radial_lateral.h"
+#include "column_sample.h"
 
 namespace dsa {
 
@@ -211,6 +212,7 @@ int Engine::dispersion_setup(int nx, int ny, int nz, const float* depz, float mi
     const size_t ncol = (size_t)nx * ny;
     disp_ready = false;
     disp_radial = false;
+    sample_open = false;      // (any begin ends a sample stage; columns_sample_begin sets it again at its end)
     disp_nx = nx; disp_ny = ny; disp_nz = nz; disp_kmax_total = kmax_total; disp_nmaps = nmaps_total; disp_nmodels = nmodels;
     h_depz.assign(depz, depz + nz);
     // (depth kernels exist for one model only: dispersion_run refuses them otherwise)
@@ -369,6 +371,7 @@ int Engine::dispersion_run(int iwave, int igr, int nper, const double* t, int wi
 // the periods before k (60 doubles; c[k-1] on: 0 -- the reference prints an element of its array it never assigned there)
 int Engine::dispersion_failure(int index, int* info, double* vals, float* table, double* c) const
 {
+    if (sample_open) return DSA_ERR_STATE;      // (a sample stage keeps no host copy of its models: nothing to replay on)
     if (index < 0 || index >= (int)disp_failures.size() || !info || !vals || !table || !c) return DSA_ERR_ARGUMENT;
     const DispFailRec& r = disp_failures[(size_t)index];
     const std::vector<float>& h_model = disp_radial && r.iwave == 1 ? h_vsh : h_vels;      // (the model the failing run read)
@@ -419,6 +422,7 @@ int Engine::columns_front(const char* who, int nmaps_in, const float* obs, const
                           float maxvel, bool radial)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "%s: call dsa_dispersion_begin and dsa_dispersion_run (with kernels) first", who); return DSA_ERR_STATE; }
+    if (int rc = sample_refused(who)) return rc;
     if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "%s: the dispersion stage holds %d models, the step moves one", who, disp_nmodels); return DSA_ERR_STATE; }
     if (disp_radial != radial) {
         if (radial) fail(DSA_ERR_STATE, "%s: the dispersion stage is not radial, call dsa_dispersion_begin_radial first", who);
@@ -616,6 +620,7 @@ int Engine::columns_resolution(int nmaps_in, const float* obs, const float* wt, 
 int Engine::dispersion_get_model(float* vels)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model: call dsa_dispersion_begin first"); return DSA_ERR_STATE; }
+    if (int rc = sample_refused("dispersion_get_model")) return rc;
     if (disp_nmodels != 1) { fail(DSA_ERR_STATE, "dispersion_get_model: the dispersion stage holds %d models", disp_nmodels); return DSA_ERR_STATE; }
     if (disp_radial) { fail(DSA_ERR_STATE, "dispersion_get_model: the dispersion stage is radial and holds Vsv and Vsh, which dsa_dispersion_get_model_radial returns"); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
@@ -632,6 +637,163 @@ int Engine::dispersion_get_model_radial(float* vsv, float* vsh)
     const size_t nn = (size_t)disp_nx * disp_ny * disp_nz;
     if (vsv) HIP_TRY(this, hipMemcpyAsync(vsv, vels_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
     if (vsh) HIP_TRY(this, hipMemcpyAsync(vsh, vsh_d.p, nn * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// ---- the Monte-Carlo depth inversion ----
+
+int Engine::sample_refused(const char* who)
+{
+    if (!sample_open) return 0;
+    fail(DSA_ERR_STATE, "%s: the dispersion stage is a sample stage of %d chains (dsa_columns_sample_begin); a new dsa_dispersion_begin ends it", who, disp_nmodels);
+    return DSA_ERR_STATE;
+}
+
+// the stage's state and inputs where they lie (column_sample.h)
+static SampleView sample_view(Engine& e)
+{
+    SampleView S{};
+    S.nx = e.disp_nx; S.ny = e.disp_ny; S.nz = e.disp_nz; S.K = e.disp_nmaps; S.C = e.disp_nmodels; S.burn = e.sample_burn;
+    S.ncol = (long long)e.disp_nx * e.disp_ny;
+    S.seed = e.sample_seed;
+    S.lam2 = e.sample_lam2; S.step = e.sample_step; S.spread = e.sample_spread; S.two_t = e.sample_two_t;
+    S.width = e.sample_width; S.minvel = e.sample_minvel; S.maxvel = e.sample_maxvel;
+    S.obs = e.col_obs.p; S.wt = e.sample_has_wt ? e.col_wt.p : nullptr; S.v0 = e.smp_v0.p; S.pv = e.pvstore.p; S.v = e.vels_d.p;
+    S.phi = e.smp_phi.p; S.psi = e.smp_psi.p; S.cnt = e.smp_cnt.p; S.S1 = e.smp_S1.p; S.S2 = e.smp_S2.p; S.phisum = e.smp_phisum.p; S.nkept = e.smp_nkept.p;
+    S.best_e = e.smp_beste.p; S.best_v = e.smp_bestv.p; S.pnode = e.smp_pnode.p; S.pold = e.smp_pold.p; S.pmark = e.smp_pmark.p; S.reseed = e.smp_reseed.p;
+    S.used = e.smp_used.p; S.nused = e.smp_nused.p; S.flag = e.smp_flag.p; S.phi0 = e.smp_phi0.p;
+    return S;
+}
+
+// dsa_columns_sample_begin: everything is checked before the device is touched; then a stage of nchains models (dispersion_setup), whose
+// model store k_sample_setup writes where it lies, the set-up's runs of the plan (times only), and the chains' phi and psi.
+int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns, const int* iwave, const int* igr,
+                                 const int* nper, const double* periods, int nmaps_in, const float* obs, const float* wt, float smooth, float step, float spread,
+                                 float width, float temperature, float minvel, float maxvel, unsigned long long seed, int burn)
+{
+    const char* who = "columns_sample_begin";
+    if (nchains < 1) { fail(DSA_ERR_ARGUMENT, "%s: nchains %d must be at least 1", who, nchains); return DSA_ERR_ARGUMENT; }
+    if (nx < 3 || ny < 3) { fail(DSA_ERR_ARGUMENT, "%s: a %d x %d grid has no interior columns (at least 3 x 3)", who, nx, ny); return DSA_ERR_ARGUMENT; }
+    if (nz < 2 || nz > 64 || !vels || !depz || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: bad arguments (nz=%d, a null model or depths, minthk=%g)", who, nz, (double)minthk); return DSA_ERR_ARGUMENT; }
+    if (nmaps_in < 1 || nmaps_in > kColumnMaxK) { fail(DSA_ERR_ARGUMENT, "%s: %d maps (1 to %d)", who, nmaps_in, kColumnMaxK); return DSA_ERR_ARGUMENT; }
+    if ((unsigned long long)nx * ny * nchains > 0x7fffffffull || (unsigned long long)nmaps_in * nchains > 0x7fffffffull) { fail(DSA_ERR_ARGUMENT, "%s: %d chains of %d x %d columns and %d maps exceed the index range", who, nchains, nx, ny, nmaps_in); return DSA_ERR_ARGUMENT; }
+    if (nruns < 1 || !iwave || !igr || !nper || !periods) { fail(DSA_ERR_ARGUMENT, "%s: the plan of the runs is missing (nruns=%d)", who, nruns); return DSA_ERR_ARGUMENT; }
+    long long total = 0;
+    for (int r = 0; r < nruns; ++r) {
+        if ((iwave[r] != 1 && iwave[r] != 2) || nper[r] < 1 || nper[r] > kMaxPeriods) { fail(DSA_ERR_ARGUMENT, "%s: run %d of the plan (iwave=%d nper=%d)", who, r, iwave[r], nper[r]); return DSA_ERR_ARGUMENT; }
+        total += nper[r];
+    }
+    if (total != nmaps_in) { fail(DSA_ERR_ARGUMENT, "%s: the plan's periods add up to %lld, nmaps is %d", who, total, nmaps_in); return DSA_ERR_ARGUMENT; }
+    for (long long q = 0; q < total; ++q) if (!std::isfinite(periods[q])) { fail(DSA_ERR_ARGUMENT, "%s: period %lld of the plan is not finite", who, q); return DSA_ERR_ARGUMENT; }
+    if (!obs) { fail(DSA_ERR_ARGUMENT, "%s: obs is required", who); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(step) || step <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: step %g must be finite and > 0", who, (double)step); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(spread) || spread < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: spread %g must be finite and >= 0", who, (double)spread); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(width) || width <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: width %g must be finite and > 0", who, (double)width); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(temperature) || temperature <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: temperature %g must be finite and > 0", who, (double)temperature); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(smooth) || smooth < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: smooth %g must be finite and >= 0", who, (double)smooth); return DSA_ERR_ARGUMENT; }
+    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "%s: minvel %g > maxvel %g", who, (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    if (burn < 0) { fail(DSA_ERR_ARGUMENT, "%s: burn %d must be >= 0", who, burn); return DSA_ERR_ARGUMENT; }
+    const size_t ncol = (size_t)nx * ny, K = (size_t)nmaps_in, C = (size_t)nchains, M = (size_t)nz - 1, nobs = ncol * K, cc = C * ncol;
+    for (size_t q = 0; q < nobs; ++q) {
+        if (!std::isfinite(obs[q])) { fail(DSA_ERR_ARGUMENT, "%s: obs[%zu] is not finite", who, q); return DSA_ERR_ARGUMENT; }
+        if (wt && !(std::isfinite(wt[q]) && wt[q] >= 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: wt[%zu] = %g must be finite and >= 0", who, q, (double)wt[q]); return DSA_ERR_ARGUMENT; }
+    }
+    for (size_t q = 0; q < ncol * nz; ++q) if (!std::isfinite(vels[q])) { fail(DSA_ERR_ARGUMENT, "%s: the start model is not finite at %zu", who, q); return DSA_ERR_ARGUMENT; }
+    if (int rc = dispersion_setup(nx, ny, nz, depz, minthk, nmaps_in, nmaps_in, nchains)) return rc;
+    if (ensure(smp_v0, ncol * nz) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) || ensure(smp_phi, cc) || ensure(smp_psi, cc) ||
+        ensure(smp_cnt, kSampleCounters * cc) || ensure(smp_S1, M * cc) || ensure(smp_S2, M * cc) || ensure(smp_phisum, cc) || ensure(smp_nkept, cc) ||
+        ensure(smp_beste, cc) || ensure(smp_bestv, M * cc) || ensure(smp_pnode, cc) || ensure(smp_pold, cc) || ensure(smp_pmark, cc) || ensure(smp_reseed, cc) ||
+        ensure(smp_used, ncol) || ensure(smp_nused, ncol) || ensure(smp_flag, ncol) || ensure(smp_phi0, ncol) || ensure(smp_nodes, kSampleNodeFigures * M * ncol) ||
+        ensure(smp_cols, kSampleColumnFigures * ncol) || ensure(smp_counts, kSampleColumnCounts * ncol)) return status;
+    sample_plan.clear();
+    int first = 0;
+    for (int r = 0; r < nruns; ++r) {
+        SampleRun run;
+        run.iwave = iwave[r]; run.igr = igr[r]; run.first = first;
+        run.t.assign(periods + first, periods + first + nper[r]);
+        sample_plan.push_back(run);
+        first += nper[r];
+    }
+    sample_has_wt = wt != nullptr; sample_sweep = 0; sample_burn = burn; sample_seed = seed;
+    sample_lam2 = (double)smooth * (double)smooth; sample_step = (double)step; sample_spread = (double)spread; sample_two_t = 2.0 * (double)temperature;
+    sample_width = width; sample_minvel = minvel; sample_maxvel = maxvel;
+    HIP_TRY(this, hipMemcpyAsync(smp_v0.p, vels, ncol * nz * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    const SampleView S = sample_view(*this);
+    launch_sample_setup(S, 0, stream);
+    h_vels.clear();      // (no host copy of the chains is kept)
+    if (int rc = dispersion_commit(false)) return rc;
+    for (const SampleRun& run : sample_plan)
+        if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { disp_ready = false; return rc; }
+    launch_sample_setup(S, 1, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    sample_open = true;
+    return 0;
+}
+
+// dsa_columns_sample_run: whole sweeps, each the proposal, one dispersion_run per entry of the plan (times only) and the Metropolis test.
+// A sweep's only host traffic is dispersion_run's.
+int Engine::columns_sample_run(int nsweeps)
+{
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_run: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
+    if (nsweeps < 0 || (long long)sample_sweep + nsweeps > 0x7fffffffll) { fail(DSA_ERR_ARGUMENT, "columns_sample_run: nsweeps %d after %d sweeps", nsweeps, sample_sweep); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const SampleView S = sample_view(*this);
+    for (int s = 0; s < nsweeps; ++s) {
+        const int sweep = sample_sweep + 1;
+        launch_sample_propose(S, sweep, stream);
+        for (const SampleRun& run : sample_plan)
+            if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { sample_open = false; disp_ready = false; return rc; }
+        launch_sample_accept(S, sweep, stream);
+        sample_sweep = sweep;
+    }
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_fetch: the finish of the state as it is; nothing of the state is changed, the sweeps may go on.
+int Engine::columns_sample_fetch(double* nodes, double* cols, int* counts)
+{
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_fetch: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
+    if (!nodes || !cols || !counts) { fail(DSA_ERR_ARGUMENT, "columns_sample_fetch: nodes, cols and counts are required"); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny, M = (size_t)disp_nz - 1;
+    launch_sample_finish(sample_view(*this), smp_nodes.p, smp_cols.p, smp_counts.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(nodes, smp_nodes.p, kSampleNodeFigures * M * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(cols, smp_cols.p, kSampleColumnFigures * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(counts, smp_counts.p, kSampleColumnCounts * ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_state: the raw per-chain state, for the tests; every pointer may be null
+int Engine::columns_sample_state(float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept, double* best_e,
+                                 float* best_v, int* pnode, float* pold, int* pmark, int* reseeded)
+{
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_state: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny, cc = ncol * disp_nmodels, M = (size_t)disp_nz - 1;
+    #define DSA_SAMPLE_GET(dst, src, n) if (dst) HIP_TRY(this, hipMemcpyAsync(dst, src, (n) * sizeof *(dst), hipMemcpyDeviceToHost, stream))
+    DSA_SAMPLE_GET(models, vels_d.p, cc * disp_nz);
+    DSA_SAMPLE_GET(phi, smp_phi.p, cc);
+    DSA_SAMPLE_GET(psi, smp_psi.p, cc);
+    DSA_SAMPLE_GET(counters, smp_cnt.p, kSampleCounters * cc);
+    DSA_SAMPLE_GET(S1, smp_S1.p, M * cc);
+    DSA_SAMPLE_GET(S2, smp_S2.p, M * cc);
+    DSA_SAMPLE_GET(phisum, smp_phisum.p, cc);
+    DSA_SAMPLE_GET(nkept, smp_nkept.p, cc);
+    DSA_SAMPLE_GET(best_e, smp_beste.p, cc);
+    DSA_SAMPLE_GET(best_v, smp_bestv.p, M * cc);
+    DSA_SAMPLE_GET(pnode, smp_pnode.p, cc);
+    DSA_SAMPLE_GET(pold, smp_pold.p, cc);
+    DSA_SAMPLE_GET(pmark, smp_pmark.p, cc);
+    DSA_SAMPLE_GET(reseeded, smp_reseed.p, cc);
+    #undef DSA_SAMPLE_GET
     HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
@@ -2430,6 +2592,34 @@ int dsa_dispersion_get_model(dsa_engine* e, float* vels)
 {
     if (!e || !vels) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->dispersion_get_model(vels);
+}
+
+int dsa_columns_sample_begin(dsa_engine* e, int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns, const int* iwave,
+                             const int* igr, const int* nper, const double* periods, int nmaps, const float* obs, const float* wt, float smooth, float step,
+                             float spread, float width, float temperature, float minvel, float maxvel, unsigned long long seed, int burn)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_begin(nx, ny, nz, nchains, vels, depz, minthk, nruns, iwave, igr, nper, periods, nmaps, obs, wt, smooth, step,
+                                                              spread, width, temperature, minvel, maxvel, seed, burn);
+}
+
+int dsa_columns_sample_run(dsa_engine* e, int nsweeps)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_run(nsweeps);
+}
+
+int dsa_columns_sample_fetch(dsa_engine* e, double* nodes, double* cols, int* counts)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_fetch(nodes, cols, counts);
+}
+
+int dsa_columns_sample_state(dsa_engine* e, float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept,
+                             double* best_e, float* best_v, int* pnode, float* pold, int* pmark, int* reseeded)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_state(models, phi, psi, counters, S1, S2, phisum, nkept, best_e, best_v, pnode, pold, pmark, reseeded);
 }
 
 int dsa_dispersion_begin_radial(dsa_engine* e, int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total,

@@ -384,6 +384,15 @@ void launch_latres_first(const LatResSystem& r, double tol, int maxit, hipStream
 void launch_latres_iteration(const LatResSystem& r, double tol, int maxit, hipStream_t stream);
 void launch_latres_measures(const LatResSystem& r, double* d_measures, hipStream_t stream);
 
+// The Monte-Carlo depth inversion (column_kernels.hip: k_sample_*).  S (column_sample.h): the stage's state and inputs
+// where they lie.  launch_sample_setup: phase 0 before the set-up's dispersion runs, phase 1 after them; a sweep is launch_sample_propose,
+// the dispersion runs, launch_sample_accept; launch_sample_finish: d_nodes (5, nz - 1, ncol), d_cols (3, ncol), d_counts (8, ncol).
+struct SampleView;
+void launch_sample_setup(const SampleView& S, int phase, hipStream_t stream);
+void launch_sample_propose(const SampleView& S, int sweep, hipStream_t stream);
+void launch_sample_accept(const SampleView& S, int sweep, hipStream_t stream);
+void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream);
+
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times
 void launch_step_models(int nx, int ny, int nz, int nm, int m0, const float* d_vsf, const float* d_steps, const float* d_bx, int n, const float* d_alpha,

@@ -4,6 +4,8 @@
                                   [--dvmax V] [--min-dws X] [--out DIR] [--resolution [--sigma S]] [--radial [--aniso G]]
                                   [--lateral W [--lateral-tol T] [--lateral-maxit N]] [--radial-resolution]
                                   [--lateral-resolution [--lateral-resolution-stride N] [--lateral-checkerboard NX,NY,NZ[,AMP]]]
+                                  [--sample C,SWEEPS[,BURN] [--sample-step S] [--sample-spread P] [--sample-width W] [--sample-seed N]
+                                   [--sample-temperature T]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -86,6 +88,20 @@ length, the range of the conjugate-gradient iterations and every member that sto
 refuses --radial; --resolution with --lateral stays refused.  Without the flag nothing changes.  column_lateral_resolution_twin is the NumPy
 twin (csrc/column_lateral_resolution.h is the arithmetic).
 
+--sample C,SWEEPS[,BURN] [--sample-step S] [--sample-spread P] [--sample-width W] [--sample-seed N] [--sample-temperature T] [--sigma S]
+(DESIGN.md section 29): after the last step (and --resolution) the posterior of every interior column is sampled on the device by C
+Metropolis chains of SWEEPS sweeps, started at the loop's result (chain 0) and scattered by up to P km/s about it (default 0.05); a sweep
+proposes one node per chain, moved by up to S km/s (default 0.05), inside a box of half width W km/s about the start (default 0.5) and the
+input's [minvel, maxvel].  The weights are 1 / sigma where --min-dws keeps a datum, sigma = --sigma or, by default, the rms before the last
+step; --smooth is divided by sigma too, so that the prior keeps the step's balance between data and smoothing.  The first BURN sweeps
+(default SWEEPS / 2) are left out of the moments.  <input>DepthPosterior.dat (write_posterior / read_posterior): per node above the bottom
+depth longitude, latitude, depth, the start, the posterior mean, its standard deviation, the best model and R-hat, the Gelman-Rubin
+convergence figure of the C chains.  <input>DepthPosteriorFit.dat (write_posterior_fit / read_posterior_fit): per column longitude,
+latitude, the data used, phi of the start, the best phi + psi, the mean kept phi, the shares of the proposals that were accepted, fell
+out of the box and lost a root, the chains put back to the start at the set-up, and the flag (2: no datum, never moved).  The log gives the
+median and the worst R-hat and the share of the unknowns above 1.1.  --sample is refused with --radial and --lateral.  Without the flag
+nothing changes.  column_sample_twin is the Python twin (csrc/column_sample.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -115,6 +131,14 @@ RADIAL_TABLE = (True, _F64("lon", "lat", "depth", "vsv", "vsh", "voigt", "xi"))
 LATERAL_RESOLUTION_TABLE = (True, _F64("lon", "lat", "depth", "rjj", "length_z", "length_x", "length_y", "own", "sd_unit", "sd"))
 LATERAL_CHECKER_TABLE = (True, _F64("lon", "lat", "depth", "input", "recovered"))
 DEFAULT_CHECKER_AMP = 0.1
+POSTERIOR_TABLE = (True, _F64("lon", "lat", "depth", "start", "mean", "sd", "best", "rhat"))
+POSTERIOR_FIT_TABLE = (True, _F64("lon", "lat") + (("nused", "%d", "int"),) + _F64("phi_start", "phi_best", "phi_mean", "accepted", "out_of_box", "no_root") +
+                       (("reseeded", "%d", "int"), ("flag", "%d", "int")))
+DEFAULT_SAMPLE_STEP = 0.05
+DEFAULT_SAMPLE_SPREAD = 0.05
+DEFAULT_SAMPLE_WIDTH = 0.5
+DEFAULT_SAMPLE_SEED = 1
+DEFAULT_SAMPLE_TEMPERATURE = 1.0
 RADIAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused_r", "%d", "int"), ("nused_l", "%d", "int")) + _F64("rms_first_r", "rms_last_r", "rms_first_l", "rms_last_l") +
                     (("flag", "%d", "int"),))
 
@@ -868,6 +892,246 @@ def column_radial_resolution_twin(obs, wt, pv, S, love, depz, smooth, damp, anis
     return out
 
 
+# ---- the Monte-Carlo depth inversion: the twin of csrc/column_sample.h ----
+
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def sample_mix(x):
+    """splitmix64's finaliser on a Python integer, modulo 2^64"""
+    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27; x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def sample_bits(seed, column, chain, sweep, draw):
+    """the 53 bits k of draw (column, chain, sweep, draw): u = k 2^-53"""
+    x = int(seed) & _M64
+    for w in (column, chain, sweep, draw):
+        x = sample_mix((x + _GOLDEN + int(w)) & _M64)
+    return x >> 11
+
+
+def sample_unit(k):
+    return float(k) * 2.0 ** -53
+
+
+def sample_neglog(k):
+    """-ln(k 2^-53) for 1 <= k < 2^53 with the header's operations: the mantissa m in [sqrt(1/2), sqrt(2)) by integer operations, ln m = 2 s
+    (1 + s^2 / 3 + ... + s^22 / 23), s = (m - 1) / (m + 1), ln 2 in two parts"""
+    k = int(k)
+    p = k.bit_length() - 1
+    frac = (k << (52 - p)) & 0x000FFFFFFFFFFFFF
+    n, ex = p - 53, 1023
+    if frac > 0x0006A09E667F3BCC:
+        ex, n = 1022, n + 1
+    m = float(np.array([(ex << 52) | frac], np.uint64).view(np.float64)[0])
+    s = (m - 1.0) / (m + 1.0)
+    z = s * s
+    t = 1.0 / 23.0
+    for d in (21.0, 19.0, 17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0, 1.0):
+        t = t * z + 1.0 / d
+    lnm = 2.0 * s * t
+    dn = float(n)
+    return -(dn * 6.93147180369123816490e-01 + (lnm + dn * 1.90821492927058770002e-10))
+
+
+def sample_psi(v, lam2):
+    """smooth^2 |L v|^2 of one column's M values, the rows in the header's order, every row summed from 0.0 over its unknowns ascending"""
+    v = [float(x) for x in v]
+    M = len(v)
+    if M < 2:
+        return 0.0
+    s = 0.0
+    t = (0.0 + v[0]) - v[1]
+    s += t * t
+    for l in range(1, M - 1):
+        t = ((0.0 - v[l - 1]) + 2.0 * v[l]) - v[l + 1]
+        s += t * t
+    t = (0.0 - v[M - 2]) + v[M - 1]
+    s += t * t
+    return lam2 * s
+
+
+def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, smooth, step, spread, width, temperature, minvel, maxvel, seed, after=None):
+    """The Monte-Carlo depth inversion in Python integers and NumPy float64 / float32 scalars, the header's operations in the header's order.
+    start (nz, ny * nx) fp32; obs / wt (K, ny * nx) fp32, wt may be None (1); forward(models (nz, C, ncol) fp32) -> pv (C, K, ncol) fp64 in
+    place of the dispersion stage (a value <= 0: no root); after(sweep, state): a hook after the set-up (sweep 0) and every sweep.  Returns
+    dict(models, phi, psi, counters (4, C, ncol): accepted, rejected, out of box, no root; S1, S2, phisum, nkept, best_e, best_v, pnode,
+    pold, pmark, reseeded, used, nused, flag, phi_start, and the finish: mean, var, W, B, best (M, ncol), best_energy, mean_phi (ncol))."""
+    F = np.float32
+    start = np.asarray(start, F)
+    nz, ncol = start.shape
+    M, C = nz - 1, int(nchains)
+    obs = np.asarray(obs, F)
+    K = obs.shape[0]
+    lam2 = float(F(smooth)) * float(F(smooth)); step = float(F(step)); spread = float(F(spread)); two_t = 2.0 * float(F(temperature))
+    width, minvel, maxvel = F(width), F(minvel), F(maxvel)
+    interior = lambda c: 1 <= c % nx <= nx - 2 and 1 <= c // nx <= ny - 2
+    a_of = lambda k, c: 1.0 if wt is None else float(F(wt[k, c]))
+
+    def box(c, l):
+        lo, hi = F(start[l, c] - width), F(start[l, c] + width)
+        return (minvel if lo < minvel else lo), (maxvel if hi > maxvel else hi)
+
+    def phi_of(pv, c, q, used):
+        phi, bad = 0.0, False
+        for k in used:
+            p = float(pv[q, k, c])
+            if not p > 0.0:
+                bad = True
+                continue
+            rho = a_of(k, c) * (float(obs[k, c]) - p)
+            phi += rho * rho
+        return phi, bad
+
+    st = dict(models=np.zeros((nz, C, ncol), F), phi=np.zeros((C, ncol)), psi=np.zeros((C, ncol)), counters=np.zeros((4, C, ncol), np.int32),
+              S1=np.zeros((M, C, ncol)), S2=np.zeros((M, C, ncol)), phisum=np.zeros((C, ncol)), nkept=np.zeros((C, ncol), np.int32), best_e=np.zeros((C, ncol)),
+              best_v=np.zeros((M, C, ncol), F), pnode=np.zeros((C, ncol), np.int32), pold=np.zeros((C, ncol), F), pmark=np.full((C, ncol), -1, np.int32),
+              reseeded=np.zeros((C, ncol), np.int32), nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32), phi_start=np.zeros(ncol))
+    v = st["models"]
+    for q in range(C):
+        for c in range(ncol):
+            v[:, q, c] = start[:, c]
+            if q > 0 and interior(c):
+                for l in range(M):
+                    u = sample_unit(sample_bits(seed, c, q, 0, l))
+                    lo, hi = box(c, l)
+                    x = F(start[l, c] + F(spread * (2.0 * u - 1.0)))
+                    v[l, q, c] = lo if x < lo else hi if x > hi else x
+    pv = np.asarray(forward(v), np.float64).reshape(C, K, ncol)
+    used_of = {}
+    for c in range(ncol):
+        if not interior(c):
+            continue
+        used = [k for k in range(K) if a_of(k, c) > 0.0 and obs[k, c] > 0 and pv[0, k, c] > 0.0]
+        used_of[c] = used
+        st["nused"][c] = len(used)
+        st["flag"][c] = 0 if used else 2
+        if not used:
+            v[:M, :, c] = start[:M, c][:, None]
+            continue
+        st["phi_start"][c] = phi_of(pv, c, 0, used)[0]
+        for q in range(C):
+            phi, bad = phi_of(pv, c, q, used)
+            if bad:
+                v[:M, q, c] = start[:M, c]
+                st["reseeded"][q, c] = 1
+                phi = st["phi_start"][c]
+            st["phi"][q, c] = phi
+            st["psi"][q, c] = sample_psi(v[:M, q, c], lam2)
+    st["used"] = used_of
+    moving = [c for c in range(ncol) if interior(c) and used_of.get(c)]
+    if after is not None:
+        after(0, st)
+    cnt = st["counters"]
+    for sweep in range(1, int(sweeps) + 1):
+        st["pmark"][...] = -1
+        for q in range(C):
+            for c in moving:
+                u0 = sample_unit(sample_bits(seed, c, q, sweep, 0)); u1 = sample_unit(sample_bits(seed, c, q, sweep, 1))
+                l = min(int(u0 * float(M)), M - 1)
+                old = v[l, q, c]
+                x = F(old + F(step * (2.0 * u1 - 1.0)))
+                lo, hi = box(c, l)
+                st["pnode"][q, c] = l; st["pold"][q, c] = old
+                if x < lo or x > hi:
+                    st["pmark"][q, c] = 1
+                else:
+                    v[l, q, c] = x
+                    st["pmark"][q, c] = 0
+        pv = np.asarray(forward(v), np.float64).reshape(C, K, ncol)
+        for q in range(C):
+            for c in moving:
+                if st["pmark"][q, c] == 1:
+                    cnt[2, q, c] += 1; cnt[1, q, c] += 1
+                else:
+                    phi_new, bad = phi_of(pv, c, q, used_of[c])
+                    accepted, psi_new = False, 0.0
+                    if not bad:
+                        psi_new = sample_psi(v[:M, q, c], lam2)
+                        delta = (phi_new + psi_new) - (st["phi"][q, c] + st["psi"][q, c])
+                        if delta == delta:
+                            if delta <= 0.0:
+                                accepted = True
+                            else:
+                                k = sample_bits(seed, c, q, sweep, 2)
+                                accepted = k == 0 or delta / two_t < sample_neglog(k)
+                    if accepted:
+                        st["phi"][q, c] = phi_new; st["psi"][q, c] = psi_new
+                        cnt[0, q, c] += 1
+                        st["pmark"][q, c] = 2
+                    else:
+                        v[st["pnode"][q, c], q, c] = st["pold"][q, c]
+                        cnt[1, q, c] += 1
+                        if bad:
+                            cnt[3, q, c] += 1
+                        st["pmark"][q, c] = 4 if bad else 3
+                if sweep <= burn:
+                    continue
+                for l in range(M):
+                    d = float(v[l, q, c]) - float(start[l, c])
+                    st["S1"][l, q, c] += d
+                    st["S2"][l, q, c] += d * d
+                energy = float(st["phi"][q, c]) + float(st["psi"][q, c])
+                st["phisum"][q, c] += st["phi"][q, c]
+                if st["nkept"][q, c] == 0 or energy < st["best_e"][q, c]:
+                    st["best_e"][q, c] = energy
+                    st["best_v"][:, q, c] = v[:M, q, c]
+                st["nkept"][q, c] += 1
+        if after is not None:
+            after(sweep, st)
+    fin = dict(mean=np.zeros((M, ncol)), var=np.zeros((M, ncol)), W=np.zeros((M, ncol)), B=np.zeros((M, ncol)), best=np.zeros((M, ncol)), best_energy=np.zeros(ncol),
+               mean_phi=np.zeros(ncol))
+    for c in range(ncol):
+        n = int(st["nkept"][0, c])
+        if n == 0:
+            continue
+        dn, dc = float(n), float(C)
+        best_q = 0
+        for q in range(1, C):
+            if st["best_e"][q, c] < st["best_e"][best_q, c]:
+                best_q = q
+        for l in range(M):
+            s1 = s2 = sw = sm = 0.0
+            for q in range(C):
+                a, b = float(st["S1"][l, q, c]), float(st["S2"][l, q, c])
+                m = a / dn
+                s1 += a; s2 += b; sw += b / dn - m * m; sm += m
+            pm, mbar = s1 / (dn * dc), sm / dc
+            sb = 0.0
+            for q in range(C):
+                d = float(st["S1"][l, q, c]) / dn - mbar
+                sb += d * d
+            fin["mean"][l, c] = float(start[l, c]) + pm
+            fin["var"][l, c] = s2 / (dn * dc) - pm * pm
+            fin["W"][l, c] = sw / dc
+            fin["B"][l, c] = sb / (dc - 1.0) if C > 1 else 0.0
+            fin["best"][l, c] = float(st["best_v"][l, best_q, c])
+        phis = 0.0
+        for q in range(C):
+            phis += float(st["phisum"][q, c])
+        fin["best_energy"][c] = st["best_e"][best_q, c]
+        fin["mean_phi"][c] = phis / (dn * dc)
+    st.update(fin)
+    return st
+
+
+def sample_rhat(W, B, nkept):
+    """the convergence figure sqrt((W (n - 1) / n + B) / W) of every unknown, 1 where W = 0 (nothing moved) or nothing was kept"""
+    W = np.asarray(W, np.float64); B = np.asarray(B, np.float64)
+    n = np.broadcast_to(np.asarray(nkept, np.float64), W.shape)
+    ok = (W > 0) & (n > 0)
+    ratio = np.divide(W * (n - 1.0) / np.where(n > 0, n, 1.0) + B, W, out=np.ones(W.shape), where=ok)
+    return np.sqrt(ratio)
+
+
+def sample_sd(var):
+    """sqrt of the pooled variance, a rounding-negative variance taken as 0"""
+    return np.sqrt(np.maximum(np.asarray(var, np.float64), 0.0))
+
+
 # ---- the plan ----
 
 def slot_plan(c):
@@ -1119,6 +1383,140 @@ def resolve(eng, c, plan, obs, wt, smooth, damp, sigma, out_dir, log=print):
             (sm["trace"] + (c["nz"] - 1, "stays under 0.1 from %g km down" % sm["depth"] if sm["depth"] is not None else "is 0.1 or more at the deepest unknown")))
     log(" depth resolution: written to %s (sd for a data standard deviation of %.6f km/s), the leverages to %s" % (rpath, sigma, lpath))
     return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
+
+
+# ---- the Monte-Carlo depth inversion: the driver's side ----
+
+def parse_sample(text):
+    """--sample C,SWEEPS[,BURN]: (chains, sweeps, burn) -- at least one chain and one sweep, 0 <= BURN <= SWEEPS, BURN by default SWEEPS // 2"""
+    parts = str(text).split(",")
+    try:
+        vals = [int(x) for x in parts]
+    except ValueError:
+        vals = None
+    if vals is None or len(vals) not in (2, 3):
+        raise ValueError("--sample takes C,SWEEPS[,BURN] in whole numbers, not %r" % (text,))
+    chains, sweeps = vals[:2]
+    burn = vals[2] if len(vals) == 3 else sweeps // 2
+    if chains < 1 or sweeps < 1 or burn < 0 or burn > sweeps:
+        raise ValueError("--sample needs C >= 1, SWEEPS >= 1 and 0 <= BURN <= SWEEPS, not %r" % (text,))
+    return chains, sweeps, burn
+
+
+def check_sample(sample=None, radial=False, lateral=None, step=None, spread=None, width=None, temperature=None, seed=None):
+    """what --sample asks of the other flags, before the library is loaded (ValueError).  Returns parse_sample's tuple, or None."""
+    if sample is None:
+        return None
+    if radial or lateral is not None:
+        raise ValueError("--sample and %s exclude each other: the %s is not sampled" % (("--radial", "radial model") if radial else ("--lateral", "laterally coupled model")))
+    parsed = parse_sample(sample)
+    for name, v in (("--sample-step", step), ("--sample-width", width), ("--sample-temperature", temperature)):
+        if v is not None and not (np.isfinite(v) and v > 0):
+            raise ValueError("%s must be finite and > 0, not %r" % (name, v))
+    if spread is not None and not (np.isfinite(spread) and spread >= 0):
+        raise ValueError("--sample-spread must be finite and >= 0, not %r" % (spread,))
+    if seed is not None and seed < 0:
+        raise ValueError("--sample-seed must be >= 0, not %r" % (seed,))
+    return parsed
+
+
+def sample_scaling(wt, smooth, sigma, shape):
+    """The sampler's weights and prior weight for a data standard deviation sigma: (wt / sigma (1 / sigma where wt is None), smooth / sigma)
+    -- phi becomes the chi-square of the data and the prior keeps the balance between data and smoothing the step had at unit weights."""
+    sigma = float(sigma)
+    w = np.ones(shape, np.float32) if wt is None else np.asarray(wt, np.float32).reshape(shape)
+    return (w.astype(np.float64) / sigma).astype(np.float32), float(smooth) / sigma
+
+
+def _rate(count, total):
+    return np.divide(np.asarray(count, np.float64), total, out=np.zeros(np.shape(count)), where=np.asarray(total) > 0)
+
+
+def write_posterior(path, c, start, res):
+    """<input>DepthPosterior.dat: start (nz, ny, nx) and columns_sample_fetch's result; every node above the bottom depth: depth slowest, then
+    j, then i.  Where no sweep was kept (the ring, a column without data) mean and best are the start, sd 0 and rhat 1."""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    M = nz - 1
+    v0 = np.asarray(start, np.float64).reshape(nz, ny, nx)[:M]
+    kept = (np.asarray(res["nkept"]).reshape(ny, nx) > 0)[None]
+    grid = lambda a: np.asarray(a, np.float64).reshape(M, ny, nx)
+    mean = np.where(kept, grid(res["mean"]), v0); best = np.where(kept, grid(res["best"]), v0)
+    sd = np.where(kept, grid(sample_sd(res["var"])), 0.0)
+    rhat = grid(sample_rhat(res["W"], res["B"], np.asarray(res["nkept"])[None]))
+    rows = []
+    for k in range(M):
+        for j in range(ny):
+            for i in range(nx):
+                lon, lat = _lonlat(c, i - 1, j - 1)
+                rows.append(dict(lon=float(lon), lat=float(lat), depth=float(c["depz"][k]), start=v0[k, j, i], mean=mean[k, j, i], sd=sd[k, j, i], best=best[k, j, i],
+                                 rhat=rhat[k, j, i]))
+    io.write_table(path, POSTERIOR_TABLE, rows)
+
+
+def read_posterior(path):
+    return io.read_table(path, POSTERIOR_TABLE)
+
+
+def write_posterior_fit(path, c, res):
+    """<input>DepthPosteriorFit.dat: per column (j, then i) the data used, phi of the start, the best phi + psi, the mean kept phi,
+    the shares of the proposals (chains x sweeps) that were accepted, fell out of the box, lost a root; the chains put back; the flag"""
+    nx, ny = c["nx"], c["ny"]
+    total = np.asarray(res["accepted"], np.float64) + np.asarray(res["rejected"], np.float64)
+    acc, oob, noroot = (_rate(res[n], total) for n in ("accepted", "out_of_box", "no_root"))
+    rows = []
+    for j in range(ny):
+        for i in range(nx):
+            lon, lat = _lonlat(c, i - 1, j - 1)
+            q = j * nx + i
+            rows.append(dict(lon=float(lon), lat=float(lat), nused=int(res["nused"][q]), phi_start=float(res["phi_start"][q]), phi_best=float(res["best_energy"][q]),
+                             phi_mean=float(res["mean_phi"][q]), accepted=float(acc[q]), out_of_box=float(oob[q]), no_root=float(noroot[q]),
+                             reseeded=int(res["reseeded"][q]), flag=int(res["flag"][q])))
+    io.write_table(path, POSTERIOR_FIT_TABLE, rows)
+
+
+def read_posterior_fit(path):
+    return io.read_table(path, POSTERIOR_FIT_TABLE)
+
+
+def rhat_summary(res):
+    """what the log says of the convergence: dict(unknowns, median, worst, share of them above 1.1) over the unknowns of the columns with a kept
+    sweep, or None without one"""
+    kept = np.asarray(res["nkept"]) > 0
+    if not kept.any():
+        return None
+    r = sample_rhat(res["W"], res["B"], np.asarray(res["nkept"])[None])[:, kept]
+    return dict(unknowns=int(r.size), median=float(np.median(r)), worst=float(r.max()), above=float((r > 1.1).mean()))
+
+
+def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, step=DEFAULT_SAMPLE_STEP, spread=DEFAULT_SAMPLE_SPREAD, width=DEFAULT_SAMPLE_WIDTH,
+               seed=DEFAULT_SAMPLE_SEED, temperature=DEFAULT_SAMPLE_TEMPERATURE, log=print):
+    """--sample from the model start (nz, ny, nx): columns_sample_begin with the weights 1 / sigma where wt keeps a datum and smooth / sigma,
+    the sweeps, the two files, the log.  Returns dict(posterior: columns_sample_fetch's result, sample_sigma, rhat, posterior_path,
+    posterior_fit_path)."""
+    chains, sweeps, burn = sample
+    w, lam = sample_scaling(wt, smooth, sigma, np.shape(obs))
+    eng.columns_sample_begin(start, c["depz"], c["minthk"], plan, obs, w, chains, lam, step, spread, width, temperature, float(c["minvel"]), float(c["maxvel"]), seed, burn)
+    eng.columns_sample_run(sweeps)
+    res = eng.columns_sample_fetch()
+    ppath = os.path.join(out_dir, "DSurfTomo.inDepthPosterior.dat")
+    fpath = os.path.join(out_dir, "DSurfTomo.inDepthPosteriorFit.dat")
+    write_posterior(ppath, c, start, res)
+    write_posterior_fit(fpath, c, res)
+    moved = res["nkept"] > 0
+    tried = float(res["accepted"].sum() + res["rejected"].sum())
+    log(" depth sample: %d chains x %d sweeps (%d kept) on %d columns, data standard deviation %.6f km/s, %d columns without data, %d chains put back at the set-up" %
+        (chains, sweeps, sweeps - burn, int(moved.sum()), sigma, int((res["flag"] == 2).sum()), int(res["reseeded"].sum())))
+    if tried > 0:
+        log(" depth sample: %.1f %% of the proposals accepted, %.1f %% out of the box, %.1f %% without a root" %
+            tuple(100.0 * float(res[n].sum()) / tried for n in ("accepted", "out_of_box", "no_root")))
+    if moved.any():
+        log(" depth sample: phi per column from %.4g at the start to %.4g on average over the kept sweeps (median over the columns)" %
+            (float(np.median(res["phi_start"][moved])), float(np.median(res["mean_phi"][moved]))))
+    sm = rhat_summary(res)
+    if sm is not None:
+        log(" depth sample: R-hat of %d unknowns median %.4f, worst %.4f, %.1f %% above 1.1" % (sm["unknowns"], sm["median"], sm["worst"], 100.0 * sm["above"]))
+    log(" depth sample: the posterior written to %s, the fit of the columns to %s" % (ppath, fpath))
+    return dict(posterior=res, sample_sigma=float(sigma), rhat=sm, posterior_path=ppath, posterior_fit_path=fpath)
 
 
 # ---- the resolution of the laterally coupled step (DESIGN.md section 27) ----
@@ -1532,7 +1930,8 @@ def radial_resolution_log(c, sm):
 def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT_SMOOTH, damp=DEFAULT_DAMP, dvmax=DEFAULT_DVMAX, min_dws=0.0, out_dir=".",
         log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
         lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False, lateral_resolution=False,
-        lateral_resolution_stride=1, lateral_checkerboard=None):
+        lateral_resolution_stride=1, lateral_checkerboard=None, sample=None, sample_step=DEFAULT_SAMPLE_STEP, sample_spread=DEFAULT_SAMPLE_SPREAD,
+        sample_width=DEFAULT_SAMPLE_WIDTH, sample_seed=DEFAULT_SAMPLE_SEED, sample_temperature=DEFAULT_SAMPLE_TEMPERATURE):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
@@ -1541,7 +1940,9 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     With radial and radial_resolution: after the loop resolve_radial's entries are added to the first item (DepthRadialResolution.dat and
     DepthRadialLeverage.dat beside --radial's files); sigma as with resolution.  With lateral and lateral_resolution: after the loop
     resolve_lateral's entries are added to the first item (DepthLateralResolution.dat and, with lateral_checkerboard, DepthLateralChecker.dat
-    beside the two files); sigma as with resolution."""
+    beside the two files); sigma as with resolution.  With sample ("C,SWEEPS[,BURN]"): after the loop (and the resolution) run_sample's entries
+    are added to the first item (DepthPosterior.dat and DepthPosteriorFit.dat beside the two files); sigma as with resolution."""
+    sampling = check_sample(sample, radial, lateral, sample_step, sample_spread, sample_width, sample_temperature, sample_seed)
     checker = check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit,
                           radial_lateral, radial_lateral_aniso, radial_resolution, lateral_resolution, lateral_resolution_stride, lateral_checkerboard)
     c = io.load(directory)
@@ -1579,6 +1980,11 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
             log(" depth lateral resolution: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
             out.update(resolve_lateral(eng, c, plan, obs, wt, smooth, damp, lateral, lateral_tol, lateral_maxit, rms if sigma is None else sigma, out_dir,
                                        lateral_resolution_stride, checker, log))
+        if sampling is not None:
+            rms = out["history"][-1]["rms"]
+            log(" depth sample: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
+            out.update(run_sample(eng, c, plan, out["vels"], obs, wt, smooth, rms if sigma is None else sigma, sampling, out_dir, sample_step, sample_spread,
+                                  sample_width, sample_seed, sample_temperature, log))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inDepth.dat")
@@ -1612,6 +2018,12 @@ def parser():
     ap.add_argument("--lateral-resolution", action="store_true", help="with --lateral: after the last step write the point-spread lengths, own shares and standard deviations of the coupled system (--sigma applies)")
     ap.add_argument("--lateral-resolution-stride", type=int, default=1, metavar="N", help="with --lateral-resolution: resolve every N-th unknown (default 1: all)")
     ap.add_argument("--lateral-checkerboard", default=None, metavar="NX,NY,NZ[,AMP]", help="with --lateral-resolution: recover a checkerboard of NX x NY x NZ blocks of amplitude AMP km/s (default %g)" % DEFAULT_CHECKER_AMP)
+    ap.add_argument("--sample", default=None, metavar="C,SWEEPS[,BURN]", help="after the last step sample the posterior of every column with C Metropolis chains for SWEEPS sweeps, the first BURN (default SWEEPS / 2) left out (--sigma applies)")
+    ap.add_argument("--sample-step", type=float, default=DEFAULT_SAMPLE_STEP, metavar="S", help="with --sample: half width of the single-node proposal in km/s (default %g)" % DEFAULT_SAMPLE_STEP)
+    ap.add_argument("--sample-spread", type=float, default=DEFAULT_SAMPLE_SPREAD, metavar="P", help="with --sample: half width of the scatter of the chains' starts in km/s (default %g)" % DEFAULT_SAMPLE_SPREAD)
+    ap.add_argument("--sample-width", type=float, default=DEFAULT_SAMPLE_WIDTH, metavar="W", help="with --sample: half width of the prior box about the step's result in km/s (default %g)" % DEFAULT_SAMPLE_WIDTH)
+    ap.add_argument("--sample-seed", type=int, default=DEFAULT_SAMPLE_SEED, metavar="N", help="with --sample: seed of the counter-based generator (default %d)" % DEFAULT_SAMPLE_SEED)
+    ap.add_argument("--sample-temperature", type=float, default=DEFAULT_SAMPLE_TEMPERATURE, metavar="T", help="with --sample: the chains sample exp(-(phi + psi) / 2T) (default %g)" % DEFAULT_SAMPLE_TEMPERATURE)
     return ap
 
 
@@ -1621,13 +2033,15 @@ def main(argv=None):
     try:
         check_flags(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.radial, a.resolution, a.lateral, a.lateral_tol, a.lateral_maxit,
                     a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution, a.lateral_resolution, a.lateral_resolution_stride, a.lateral_checkerboard)
+        check_sample(a.sample, a.radial, a.lateral, a.sample_step, a.sample_spread, a.sample_width, a.sample_temperature, a.sample_seed)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
     run(a.directory, a.maps, a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.out, resolution=a.resolution, sigma=a.sigma, radial=a.radial, aniso=a.aniso,
         lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso,
         radial_resolution=a.radial_resolution, lateral_resolution=a.lateral_resolution, lateral_resolution_stride=a.lateral_resolution_stride,
-        lateral_checkerboard=a.lateral_checkerboard)
+        lateral_checkerboard=a.lateral_checkerboard, sample=a.sample, sample_step=a.sample_step, sample_spread=a.sample_spread, sample_width=a.sample_width,
+        sample_seed=a.sample_seed, sample_temperature=a.sample_temperature)
     return 0
 
 

@@ -112,6 +112,10 @@ def declare_solvers(L):
     L.dsa_columns_step_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_step_radial_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 8 + [C.c_double, _i32] + [_vp] * 5
     L.dsa_columns_resolution_lateral.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [C.c_double, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 5
+    L.dsa_columns_sample_begin.argtypes = [_vp] + [_i32] * 4 + [_vp, _vp, _f32, _i32] + [_vp] * 4 + [_i32, _vp, _vp] + [_f32] * 7 + [C.c_ulonglong, _i32]
+    L.dsa_columns_sample_run.argtypes = [_vp, _i32]
+    L.dsa_columns_sample_fetch.argtypes = [_vp] * 4
+    L.dsa_columns_sample_state.argtypes = [_vp] * 15
     L.dsa_kernels_from_dispersion_radial.argtypes = [_vp]
     L.dsa_solve_rows_radial.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_iteration_system_radial_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 4 + [_vp] * 6
@@ -169,6 +173,7 @@ class Engine:
         self._nrays = 0
         self._ndata = 0
         self._disp = (0, 0, 0)
+        self._sample = (0, 0)                       # (chains, maps) of the last columns_sample_begin
 
     def close(self):
         if getattr(self, "_h", None):
@@ -482,6 +487,64 @@ class Engine:
         nx, ny, nz = self._disp
         out = np.zeros((nz, ny, nx), np.float32)
         self._check(self._L.dsa_dispersion_get_model(self._h, out.ctypes.data_as(_vp)))
+        return out
+
+    # ---- Monte-Carlo depth inversion ----
+    def columns_sample_begin(self, vels, depz, minthk, plan, obs, wt, nchains, smooth, step, spread, width, temperature, minvel, maxvel, seed, burn):
+        """dsa_columns_sample_begin: a sample stage of nchains Metropolis chains per column, started at vels (nz, ny, nx) fp32, and its set-up
+        sweep.  plan: [(wave type, velocity kind, periods), ...] in slot order (further items of an entry, as depth.slot_plan's first slot,
+        are ignored: the maps are cumulative); obs (nmaps, ny * nx) fp32 as columns_step's, wt the same shape (1 / sigma, 0 drops a datum) or
+        None (all 1).  ValueError as columns_step's."""
+        vels = np.ascontiguousarray(vels, np.float32)
+        nz, ny, nx = vels.shape
+        was = self._disp
+        self._disp = (nx, ny, nz)
+        try:
+            nmaps, obs, wt = self._columns_in("columns_sample_begin", obs, wt)[:3]
+        finally:
+            self._disp = was                                                        # (a refused begin leaves the open stage, and its shapes, as they were)
+        iwave = np.array([int(r[0]) for r in plan], np.int32); igr = np.array([int(r[1]) for r in plan], np.int32)
+        nper = np.array([np.size(r[2]) for r in plan], np.int32)
+        t = np.ascontiguousarray(np.concatenate([np.asarray(r[2], np.float64).ravel() for r in plan]) if len(plan) else np.zeros(0), np.float64)
+        self._check(self._L.dsa_columns_sample_begin(self._h, nx, ny, nz, int(nchains), _p(vels), _p(np.ascontiguousarray(depz, np.float32)), float(minthk), len(plan),
+                                                     _p(iwave), _p(igr), _p(nper), _p(t), nmaps, _p(obs), _p(wt), float(smooth), float(step), float(spread), float(width),
+                                                     float(temperature), float(minvel), float(maxvel), int(seed) & 0xFFFFFFFFFFFFFFFF, int(burn)))
+        self._disp = (nx, ny, nz)
+        self._sample = (int(nchains), nmaps)
+
+    def columns_sample_run(self, nsweeps):
+        """dsa_columns_sample_run: nsweeps whole sweeps of every chain on the device"""
+        self._check(self._L.dsa_columns_sample_run(self._h, int(nsweeps)))
+
+    def columns_sample_fetch(self):
+        """dsa_columns_sample_fetch: the finish of the present state.  Returns dict(mean, var, W, B, best (nz - 1, ny * nx) fp64; phi_start,
+        best_energy, mean_phi (ny * nx) fp64; nused, flag, accepted, rejected, out_of_box, no_root, reseeded, nkept (ny * nx) int32); without
+        a kept sweep (the ring, flag 2, burn >= the sweeps run) the node figures, best_energy and mean_phi are 0."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        nodes = np.zeros((5, nz - 1, ncol)); cols = np.zeros((3, ncol)); counts = np.zeros((8, ncol), np.int32)
+        self._check(self._L.dsa_columns_sample_fetch(self._h, _p(nodes), _p(cols), _p(counts)))
+        out = dict(zip(("mean", "var", "W", "B", "best"), nodes))
+        out.update(zip(("phi_start", "best_energy", "mean_phi"), cols))
+        out.update(zip(("nused", "flag", "accepted", "rejected", "out_of_box", "no_root", "reseeded", "nkept"), counts))
+        return out
+
+    def columns_sample_state(self):
+        """dsa_columns_sample_state: the raw per-chain state.  Returns dict(models (nz, C, ncol) fp32; phi, psi, phisum, best_e (C, ncol);
+        counters (4, C, ncol) int32: accepted, rejected, out of box, no root; S1, S2 (nz - 1, C, ncol); best_v (nz - 1, C, ncol) fp32; nkept,
+        pnode, pmark, reseeded (C, ncol) int32; pold (C, ncol) fp32)."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        Cn = self._sample[0]
+        if Cn < 1:                                                                  # (no stage was ever begun here: the library's refusal)
+            self._check(self._L.dsa_columns_sample_state(self._h, *([None] * 14)))
+        f64 = lambda *shape: np.zeros(shape)
+        i32 = lambda *shape: np.zeros(shape, np.int32)
+        f32 = lambda *shape: np.zeros(shape, np.float32)
+        out = dict(models=f32(nz, Cn, ncol), phi=f64(Cn, ncol), psi=f64(Cn, ncol), counters=i32(4, Cn, ncol), S1=f64(nz - 1, Cn, ncol), S2=f64(nz - 1, Cn, ncol),
+                   phisum=f64(Cn, ncol), nkept=i32(Cn, ncol), best_e=f64(Cn, ncol), best_v=f32(nz - 1, Cn, ncol), pnode=i32(Cn, ncol), pold=f32(Cn, ncol),
+                   pmark=i32(Cn, ncol), reseeded=i32(Cn, ncol))
+        self._check(self._L.dsa_columns_sample_state(self._h, *[_p(a) for a in out.values()]))
         return out
 
     def dispersion_begin_radial(self, vsv, vsh, depz, minthk, kmax_total, nmaps_total):

@@ -553,6 +553,47 @@ int dsa_columns_resolution_lateral(dsa_engine* e, int nmaps, const float* obs, c
                                    int maxit, int nmembers, const int* kind, const int* index, const double* models, int nrows, double* measures,
                                    double* info, double* full, int* nused, int* flag);
 
+/* dsa_columns_sample_*: Monte-Carlo depth inversion, nchains Metropolis chains of Vs(z) per interior column kept on the device (extension;
+ * DESIGN.md 29; the arithmetic is csrc/column_sample.h).
+ * dsa_columns_sample_begin opens a dispersion stage of nchains models (dsa_dispersion_begin_models' stage, kmax = nmaps) whose models are the
+ * chains, and runs the set-up sweep.  vels, depz, minthk: the start model, dsa_dispersion_begin's; the plan of the runs: nruns entries iwave,
+ * igr, nper and all periods one run after the other -- run r writes the maps [sum of the nper before it, + nper[r]), which must add up to
+ * nmaps (1 .. 60); obs, wt: nmaps*nx*ny floats as dsa_columns_step's, wt = 1 / sigma of a datum, 0 to drop it, or NULL (all 1).  smooth: the
+ * weight of dsa_columns_step's depth Laplacian in the prior psi = smooth^2 |L v|^2; a chain samples exp(-(phi + psi) / (2 temperature)), phi
+ * the sum of the squared weighted residuals of the used data, inside the box [max(minvel, v0 - width), min(maxvel, v0 + width)] per node.
+ * step: half width of the uniform single-node proposal in km/s; spread: half width of the uniform scatter of chains 1 .. nchains-1 about
+ * the start (chain 0 starts at it); seed: of the counter-based generator; burn: sweeps before the moments are taken.  A datum is used where
+ * wt > 0, obs > 0 and the start model's curve has a root; a column without one gets flag 2 and is never moved, like the outer ring.
+ * dsa_columns_sample_run: nsweeps whole sweeps -- the proposals, one times-only dispersion run per plan entry, the Metropolis tests and the
+ * running moments, all on the device; n calls with 1 leave the bits one call with n leaves.
+ * dsa_columns_sample_fetch: the finish of the present state, which it leaves as it is.
+ *   nodes   5*(nz-1)*nx*ny doubles, (figure, depth, column): the pooled posterior mean, the pooled variance, the mean within-chain variance
+ *           W, the variance B of the chain means (/ (nchains - 1); 0 for one chain), the best model -- sd = sqrt(var) and the convergence
+ *           figure sqrt((W (n-1)/n + B) / W) are the caller's to take
+ *   cols    3*nx*ny doubles: phi of the start, the best phi + psi, the mean kept phi
+ *   counts  8*nx*ny ints: nused, flag, accepted, rejected, out of box, no root (summed over the chains; the last two are among the
+ *           rejected), the chains put back to the start at the set-up, the sweeps kept n
+ *   without a kept sweep (the ring, flag 2, burn >= the sweeps run) nodes and the last two of cols are 0
+ * dsa_columns_sample_state: the raw state for tests, every pointer may be NULL: models nz*nchains*nx*ny (depth, chain, column); phi, psi,
+ * phisum, nkept, best_e, pnode, pold, pmark (-1 idle, 1 out of box, 2 accepted, 3 rejected, 4 no root), reseeded: nchains*nx*ny (chain,
+ * column); counters 4*nchains*nx*ny (accepted, rejected, out of box, no root); S1, S2, best_v (nz-1)*nchains*nx*ny.
+ * While the stage is open dsa_columns_step*, dsa_columns_resolution*, dsa_dispersion_get_model and dsa_dispersion_failure return
+ * DSA_ERR_STATE (no host copy of the chains exists); dsa_dispersion_fetch works on global maps (chain * nmaps + map), the failure counts stay
+ * right; any dsa_dispersion_begin* ends the stage.
+ * Errors of begin, all found before the device is touched (a stage that was open stays as it was): DSA_ERR_ARGUMENT: nchains < 1, nx or ny
+ * < 3, nz outside 2 .. 64, nchains*nx*ny or nchains*nmaps beyond 2^31 - 1, a NULL vels / depz / obs / plan, a plan entry with iwave outside
+ * 1, 2 or nper outside 1 .. 60, periods that do not add up to nmaps, obs or the model not finite, wt negative or not finite, step <= 0,
+ * spread < 0, width <= 0, temperature <= 0, smooth < 0 (or any of them not finite), minvel > maxvel, burn < 0.  run, fetch, state without
+ * an open stage: DSA_ERR_STATE; nsweeps < 0 and a NULL output of fetch: DSA_ERR_ARGUMENT. */
+int dsa_columns_sample_begin(dsa_engine* e, int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns,
+                             const int* iwave, const int* igr, const int* nper, const double* periods, int nmaps, const float* obs, const float* wt,
+                             float smooth, float step, float spread, float width, float temperature, float minvel, float maxvel,
+                             unsigned long long seed, int burn);
+int dsa_columns_sample_run(dsa_engine* e, int nsweeps);
+int dsa_columns_sample_fetch(dsa_engine* e, double* nodes, double* cols, int* counts);
+int dsa_columns_sample_state(dsa_engine* e, float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept,
+                             double* best_e, float* best_v, int* pnode, float* pold, int* pmark, int* reseeded);
+
 /* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
  * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
  * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of

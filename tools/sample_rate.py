@@ -1,0 +1,86 @@
+"""What a sweep of the Monte-Carlo depth inversion costs: on the Taipei example's grid and model (18 x 18 x 9, its 26
+periods, one Rayleigh phase run), 64 chains per column -- 20 736 curves per sweep.  The observations are the model's own curves 2 % off, the
+data's standard deviation 0.05 km/s.  After the set-up and a warm-up sweep, `sweeps` calls of columns_sample_run(1) are timed one by one:
+the median wall time of a sweep, the median device time of its dispersion run (DSA_STAT_MS_DISPERSION) and the rest -- the four new
+kernels' two launches per sweep and the host's share.  One call of columns_sample_run(sweeps) follows, for the rate without the per-call
+overhead.
+
+The share of the sweep in the new kernels themselves is a kernel trace's:
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/sample_rate.py 50
+    python tools/sample_rate.py trace-shares DIR/.../*_kernel_trace.csv
+prints per kernel the launches, the median and the sum of their durations, and the share of the sum of all kernels that k_sample_* take.
+
+    python tools/sample_rate.py [sweeps] [chains]      (needs the GPU)
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from dsurftomo_amd import depth, io                  # noqa: E402
+from dsurftomo_amd.engine import Engine             # noqa: E402
+
+
+def trace_shares(path):
+    """per kernel of a rocprofv3 kernel trace (csv): the launches, the median and the sum of the durations; the share of k_sample_*"""
+    import csv
+    rows = {}
+    with open(path, newline="") as fh:
+        for r in csv.DictReader(fh):
+            name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].split("::")[-1]
+            rows.setdefault(name, []).append(1e-3 * (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
+    total = sum(sum(d) for d in rows.values())
+    for name, d in sorted(rows.items(), key=lambda kv: -sum(kv[1])):
+        print("%-28s %6d launches, median %9.1f us, sum %12.1f us (%5.2f %%)" % (name, len(d), np.median(d), sum(d), 100.0 * sum(d) / total))
+    new = sum(sum(d) for name, d in rows.items() if name.startswith("k_sample_"))
+    print("k_sample_*: %.1f us of %.1f us in all kernels, %.2f %%" % (new, total, 100.0 * new / total))
+
+
+def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "trace-shares":
+        trace_shares(sys.argv[2])
+        return
+    sweeps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+    chains = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+    c = io.load()
+    plan = depth.slot_plan(c)
+    vel = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
+    kmax, ncol = c["kmax"], c["nx"] * c["ny"]
+    e = Engine(0)
+    e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    obs = (e.dispersion_fetch(0, kmax) * 1.02).astype(np.float32)
+    sigma = 0.05
+    wt, lam = depth.sample_scaling(None, depth.DEFAULT_SMOOTH, sigma, obs.shape)
+    t0 = time.perf_counter()
+    e.columns_sample_begin(vel, c["depz"], c["minthk"], plan, obs, wt, chains, lam, depth.DEFAULT_SAMPLE_STEP, depth.DEFAULT_SAMPLE_SPREAD, depth.DEFAULT_SAMPLE_WIDTH,
+                           depth.DEFAULT_SAMPLE_TEMPERATURE, float(c["minvel"]), float(c["maxvel"]), depth.DEFAULT_SAMPLE_SEED, 0)
+    t_begin = 1e3 * (time.perf_counter() - t0)
+    e.columns_sample_run(1)
+    wall, dev = [], []
+    for s in range(sweeps):
+        ms0 = e.stats()["ms_dispersion"]
+        t0 = time.perf_counter()
+        e.columns_sample_run(1)
+        wall.append(1e3 * (time.perf_counter() - t0)); dev.append(e.stats()["ms_dispersion"] - ms0)
+    t0 = time.perf_counter()
+    e.columns_sample_run(sweeps)
+    one_call = 1e3 * (time.perf_counter() - t0) / sweeps
+    res = e.columns_sample_fetch()
+    e.close()
+    tried = float(res["accepted"].sum() + res["rejected"].sum())
+    w, d = float(np.median(wall)), float(np.median(dev))
+    print("%d x %d x %d, K = %d, %d chains, %d curves per sweep, %d dispersion_run per sweep: begin %.1f ms; median of %d sweeps -- %.3f ms wall, %.3f ms in the "
+          "dispersion run on the device, %.3f ms (%.1f %%) the rest: the two launches of the new kernels and the host; %.3f ms per sweep in one call of %d; "
+          "%.1f %% of the proposals accepted" %
+          (c["nx"], c["ny"], c["nz"], kmax, chains, ncol * chains, len(plan), t_begin, sweeps, w, d, w - d, 100.0 * (w - d) / w, one_call, sweeps,
+           100.0 * float(res["accepted"].sum()) / tried))
+
+
+if __name__ == "__main__":
+    main()
