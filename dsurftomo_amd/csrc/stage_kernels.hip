@@ -292,7 +292,8 @@ __global__ __launch_bounds__(256) void k_handoff(GridDesc g, BatchPtrs b)
 // Such nodes are collected, and the hand-off's outputs that reach the coarse grid (every kSgdl-th node of the box: status and time) are evaluated once more
 // with the tied node's answer inverted: a changed time is the tie's influence (counted into the unit's tie record like the census' ties: any / sum / above
 // the threshold); a changed STATUS on the lattice, or more ties than the probe holds, counts in word [6] of the record's refined half, which flags the
-// unit by itself (Engine::tie_verdict) -- except in a laterally homogeneous box, where such ties are the grid's symmetry and only count.
+// unit by itself (Engine::tie_verdict).  In a laterally homogeneous box the ties of the grid's symmetry that change a TIME are counted like the census' ties;
+// one that changes a STATUS is handled like anywhere else (the replay, or the flag): scan order is not always what the reference's tree decided there.
 __global__ __launch_bounds__(256) void k_handoff_probe(GridDesc g, BatchPtrs b, int32_t* tie, float tie_threshold, int32_t* replay, int replay_cap)
 {
     constexpr int kTiedMax = 8;
@@ -320,7 +321,9 @@ __global__ __launch_bounds__(256) void k_handoff_probe(GridDesc g, BatchPtrs b, 
     __syncthreads();
     if (s_ntied == 0) return;
     // (a laterally homogeneous box -- a 1-D starting model: every map of the Taipei example's first iteration -- ties like this BY SYMMETRY, one station of
-    // that example in 22 of its 26 periods; there the scan-order rule is the reference's behaviour, checked bit for bit, and a changed status only counts)
+    // that example in 22 of its 26 periods; there the scan-order rule was the reference's behaviour, checked bit for bit, and a changed TIME only counts.
+    // A changed STATUS does not: 3.12 km/s throughout, the source on node (5, 7) -- the reference's tree had the edge node (5, 0) still in the band where scan
+    // order calls it alive, and the two nodes beside it end 1.9e-4 s apart (tests/test_gpu_geometry.py, tests/test_gpu_exact.py))
     __shared__ unsigned s_smin, s_smax;          // (positive floats order like their bit patterns)
     if (tid == 0) { s_smin = 0x7f800000u; s_smax = 0u; }
     __syncthreads();
@@ -345,23 +348,23 @@ __global__ __launch_bounds__(256) void k_handoff_probe(GridDesc g, BatchPtrs b, 
     const int nt = s_ntied < kTiedMax ? s_ntied : kTiedMax;
     // thread z of the first nine looks at the tied node (z = 0) or at one of its eight stencil nodes
     const int dx = tid == 1 ? -1 : tid == 2 ? 1 : tid == 5 ? -2 : tid == 6 ? 2 : 0, dz = tid == 3 ? -1 : tid == 4 ? 1 : tid == 7 ? -2 : tid == 8 ? 2 : 0;
-    if (replay && !homogeneous) {
+    if (replay) {
         // (round 6, last) A tie that changes what the coarse grid receives is not guessed at and not flagged: the unit goes on a list, and
-        // k_handoff_replay marches its refined box literally (129^2 nodes: the reference's own tree decides) and hands off from that.  A full list,
-        // or a homogeneous box (the symmetric ties of a 1-D model: counted below), keeps the old way.
-        bool change = s_ntied > kTiedMax;
+        // k_handoff_replay marches its refined box literally (129^2 nodes: the reference's own tree decides) and hands off from that.  A full list
+        // keeps the old way, and so do the ties of a homogeneous box that change no status (the symmetric ties of a 1-D model: counted below).
+        bool change = !homogeneous && s_ntied > kTiedMax;
         for (int k = 0; k < nt && !change; ++k) {
             const int yid = s_tied[k], zx = yid / sd.rnz + 1 + dx, zz = yid % sd.rnz + 1 + dz;
             if (!(zx >= 1 && zx <= sd.rnx && zz >= 1 && zz <= sd.rnz && (zx - 1) % kSgdl == 0 && (zz - 1) % kSgdl == 0)) continue;
             float t1;
             const int st1 = handoff_node<true>(g, sd, w, 0, rstar, ez, ex, zz, zx, &t1, yid);
             const int zid = (zx - 1) * sd.rnz + (zz - 1);
-            change = st1 != w.S_r[zid] || (st1 >= 0 && t1 != Tfin[zid]);
+            change = st1 != w.S_r[zid] || (!homogeneous && st1 >= 0 && t1 != Tfin[zid]);
         }
-        if (!__any(change)) return;
+        if (!__any(change) && !homogeneous) return;
         int slot = 0;
-        if (tid == 0) slot = atomicAdd(replay, 1);
-        slot = __shfl(slot, 0);
+        if (!__any(change)) slot = replay_cap;
+        else { if (tid == 0) slot = atomicAdd(replay, 1); slot = __shfl(slot, 0); }
         if (slot < replay_cap) { if (tid == 0) replay[1 + slot] = s; return; }
     }
     if (s_ntied > kTiedMax && tid == 0) atomicAdd(tr + 6, 1);
@@ -375,8 +378,8 @@ __global__ __launch_bounds__(256) void k_handoff_probe(GridDesc g, BatchPtrs b, 
         const int st0 = w.S_r[zid];
         const float t0 = Tfin[zid];
         // (a changed STATUS on the lattice: the coarse grid starts from another band -- on small grids, where the box is a good part of the field, 2e-4 to
-        // 4.5e-4 s at a receiver (profiles/r06_tie_fuzz_symmetric_sources.log) --: the unit is flagged, word [6]; in a homogeneous box it only counts)
-        if (st1 != st0) { if (homogeneous) atomicAdd((unsigned*)tr + 2, 1u); else atomicAdd(tr + 6, 1); }
+        // 4.5e-4 s at a receiver (profiles/r06_tie_fuzz_symmetric_sources.log) --: the unit is flagged, word [6])
+        if (st1 != st0) atomicAdd(tr + 6, 1);
         else if (st0 >= 0 && t1 != t0) {
             const float ti = fabsf(t1 - t0);
             atomicAdd((unsigned*)tr + 2, 1u); atomicAdd((unsigned*)tr + 3, (unsigned)(fminf(ti, 1.0f) * (1.0f / kTieSumUnit)));

@@ -361,3 +361,33 @@ def test_a_tie_at_the_hand_off_is_resolved_by_the_refined_march(exact):
     same = (bits(t1[marched]) == bits(tx[marched])).all(axis=1)
     parity_log.add(f"hand-off replay N={e.nnx} smooth, dicing 5, sources on node lines: {int(st['handoffs_replayed'])} refined boxes marched, 0 units marched whole (without the replay: {int(st0['exact_units'])}); "
                    f"worst |dt| against exact_ties = 2 {d.max():.3g} s; of the {int(marched.sum())} units the old way marches {int(same.sum())} are bit-identical to the march after the replay")
+
+
+@pytest.mark.parametrize("scale", [1.0, 1.04, 1.06])
+def test_a_status_tie_at_the_hand_off_of_a_homogeneous_box_is_replayed(exact, scale):
+    """A homogeneous map (a 1-D starting model) with the source on node (5, 7) of the 121^2 grid: the edge node (5, 0) of the refined box ranks equal with
+    the node that ends the refined stage, and whether it is alive at the hand-off changes the status the coarse grid receives.  Scan order says alive; the
+    reference's tree says so at 3.0 km/s and not at 3.12 or 3.18 km/s, where the two nodes beside it then differ by 1.9e-4 s from the reference's.  The
+    default mode therefore marches the refined box of such a unit literally (k_handoff_probe no longer lets a changed status pass in a homogeneous box): the
+    whole field is the oracle's bit for bit; with the replay off the unit is flagged and marched whole."""
+    e = exact
+    nx = 18
+    g = L.grid(nx, nx, synth.GOXD, synth.GOZD, synth.DVD, synth.DVD, 8)
+    pv = synth.medium(nx, "homog") * scale
+    veln = L.o_gridder(g, pv)
+    sx, sz = np.float32(g.gox + np.float32(5.0) * g.dnx), np.float32(g.goz + np.float32(7.0) * g.dnz)
+    rx, rz = np.float32(g.gox + np.float32(4.0) * g.dnx), np.float32(g.goz + np.float32(0.3) * g.dnz)
+    o = L.o_solve(g, pv, veln, sx, sz)
+    want = L.o_srtimes(g, veln, o["T"], sx, sz, rx, rz)
+    e.set_maps(nx, nx, synth.GOXD, synth.GOZD, synth.DVD, synth.DVD, pv)
+    out = []
+    for replay in (1, 0):
+        e.set_option("exact_ties", 1); e.set_option("handoff_replay", replay)
+        t = e.traveltimes([0], [sx], [sz], [1], [rx], [rz])
+        st = e.stats()
+        nbad = int((bits(e.field(0)) != bits(o["T"])).sum())
+        out.append((int(st["handoffs_replayed"]), int(st["exact_units"]), nbad))
+        assert nbad == 0 and np.float32(t[0]).view(np.uint32) == np.float32(want).view(np.uint32), (scale, replay, nbad)
+    assert out[0][:2] == (1, 0) and out[1][:2] == (0, 1), out
+    parity_log.add(f"hand-off status tie in a homogeneous box, {3.0 * scale:.2f} km/s, source on node (5, 7) of 121^2: refined box replayed, field bit-identical to the oracle; "
+                   f"replay off: the unit marched whole")

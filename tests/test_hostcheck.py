@@ -315,3 +315,55 @@ def test_ray_trace_one_lane_and_four_lanes_against_oracle(H, nx, kind, gd):
             assert (bits(out[0][0]) != bits(ref)).sum() == 0 and out[0][2] == ns
             nrays += 1
     assert nrays == 24
+
+
+@pytest.mark.parametrize("name,kind", __import__("geometry_cases").PAIRS)
+def test_exact_march_and_rays_on_the_geometry_cases(H, name, kind):
+    """the shared host / device code on the geometries of tests/geometry_cases.py (rectangles, unequal spacings, latitudes 80 N to 50 S,
+    negative longitudes, the equator, dicing 3): make_grid and the gridder, the exact mode's march and trace_ray with one and four lanes,
+    against the oracle -- which tests/test_oracle_vs_ref.py pins to the reference on these very inputs -- bit for bit"""
+    import geometry_cases as G
+    geo = nx, ny, goxd, gozd, dvxd, dvzd, gd = G.geometry(name)
+    g = L.grid(*geo)
+    NX, NZ = g.nnx, g.nnz
+    pv = G.medium(nx, ny, kind)
+    veln = L.o_gridder(g, pv)
+    vh = np.zeros((NX, NZ), np.float32)
+    H.hc_gridder(*geo, L.ptr(pv), L.ptr(vh))
+    assert (bits(vh) != bits(veln)).sum() == 0
+    src, rec = G.plan(name)
+    sx, sz = G.radians(g.gox, g.goz, g.dnx, g.dnz, src)
+    rx, rz = G.radians(g.gox, g.goz, g.dnx, g.dnz, rec)
+    for s in range(G.NSRC):
+        o = L.o_solve(g, pv, veln, sx[s], sz[s])
+        T = np.zeros((NX, NZ), np.float32); Tr = np.zeros(129 * 129, np.float32); Sr = np.zeros(129 * 129, np.int32)
+        box = np.zeros(6, np.int32); st = np.zeros(4, np.int64)
+        assert H.hc_exact_solve(*geo, L.ptr(pv), sx[s], sz[s], 256, 16 * max(NX, NZ) + 4096, L.ptr(T), L.ptr(Tr), L.ptr(Sr), L.ptr(box), L.ptr(st)) == 0
+        n = box[4] * box[5]
+        assert (box[4], box[5]) == o["Sr"].shape
+        cls_o = np.sign(o["Sr"]).clip(-1, 1)
+        assert (cls_o != Sr[:n].reshape(box[4], box[5])).sum() == 0, (name, s)
+        alive = cls_o == 0
+        assert (bits(Tr[:n].reshape(box[4], box[5])[alive]) != bits(o["Tr"][alive])).sum() == 0, (name, s)
+        assert (bits(T) != bits(o["T"])).sum() == 0, (name, s)
+        for i in range(G.NREC):
+            ref, rb, ns = L.o_rpaths(g, o, veln, sx[s], sz[s], rx[s, i], rz[s, i])
+            for lanes in (1, 4):
+                fdm = np.zeros((g.nvx + 2, g.nvz + 2), np.float32)
+                fl, stp = L.i32(0), L.i32(0)
+                assert H.hc_trace_ray_lanes(*geo, L.ptr(veln), L.ptr(o["T"]), L.ptr(np.ascontiguousarray(o["Tr"])), L.ptr(np.ascontiguousarray(o["Sr"])),
+                                            sx[s], sz[s], rx[s, i], rz[s, i], L.ptr(fdm), C.byref(fl), C.byref(stp), lanes) == 0
+                assert fl.value == (rb & 1) and stp.value == ns and (bits(fdm) != bits(ref)).sum() == 0, (name, s, i, lanes)
+
+
+def test_sinf_libm_is_libms_sinf_in_every_reduction_branch(H):
+    """sinf_libm (ray_core.h) against this machine's sinf (glibc >= 2.28) on every fp32 colatitude a grid can have, 0.001 to 3.2 rad, swept per
+    branch of its reduction: none below pi / 4 (latitudes above 45 N: down past the 10 degrees of colatitude of latitude 80 N), n = 1 up to
+    3 pi / 4, n = 2 beyond (latitudes below 45 S)"""
+    H.hc_sinf_sweep.argtypes = [L.f32, L.f32]
+    H.hc_sinf_sweep.restype = C.c_long
+    q = np.float32(np.pi / 4)
+    assert np.radians(90.0 - 80.0) > 1e-3
+    for lo, hi in ((np.float32(1e-3), np.nextafter(q, np.float32(0))), (q, np.nextafter(np.float32(3 * np.pi / 4), np.float32(0))),
+                   (np.float32(3 * np.pi / 4), np.float32(3.2))):
+        assert H.hc_sinf_sweep(lo, hi) == 0, (lo, hi)

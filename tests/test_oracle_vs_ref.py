@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import _libs as L
+import dispersion_cases as D
+import geometry_cases as G
 import refrecord
 import synth
 
@@ -139,6 +141,93 @@ def test_boundary_bitwise(kw):
     out = refrecord.check("boundary%s" % json.dumps(kw, sort_keys=True), lambda side: boundary(side, kw))
     assert out["nar"] > 0
 
+def fields_rays_geometry(side, name, kind):
+    """the body of fields_rays on a row of geometry_cases.CASES: any nx x ny, origin, spacings and dicing"""
+    nx, ny, goxd, gozd, dvxd, dvzd, gd = G.geometry(name)
+    wb = side.grid(nx, ny, goxd, gozd, dvxd, dvzd, gd)
+    try:
+        assert (wb.nnx, wb.nnz) == G.nodes(name)
+        out = {"grid": f32([wb.gox, wb.goz, wb.dnx, wb.dnz])}
+        out["veln"] = wb.gridder(G.medium(nx, ny, kind))
+        src, rec = G.plan(name)
+        for s in range(G.NSRC):
+            sx, sz = G.radians(wb.gox, wb.goz, wb.dnx, wb.dnz, src[s])
+            for k, v in refrecord.canonical_solve(wb.solve(sx, sz)).items():
+                out["%s%d" % (k, s)] = v
+            rx, rz = G.radians(wb.gox, wb.goz, wb.dnx, wb.dnz, rec[s])
+            for i in range(G.NREC):
+                out["t%d_%d" % (s, i)] = f32(wb.srtimes(sx, sz, rx[i], rz[i]))
+                out["fdm%d_%d" % (s, i)] = wb.rpaths(sx, sz, rx[i], rz[i])
+        return out
+    finally:
+        wb.close()
+
+
+@pytest.mark.parametrize("name,kind", G.PAIRS)
+def test_fields_rays_geometry(name, kind):
+    """rectangles, unequal spacings, high latitudes north and south, negative longitudes, the equator, dicing 3 (geometry_cases.py): grid
+    constants, diced velocity, coarse field, status classes and live times of the refined box, receiver times and the vertex sums of
+    every ray (CalSurfG.f90:288-487, :1636-1759, :1771-2318) -- every branch that tells nnx from nnz or dnx from dnz shows here"""
+    out = refrecord.check("fields_rays_geometry[%s-%s]" % (name, kind), lambda side: fields_rays_geometry(side, name, kind))
+    NX, NZ = G.nodes(name)
+    nx, ny = G.geometry(name)[:2]
+    assert out["veln"].shape == (NX, NZ) and out["fdm0_0"].shape == (nx, ny)
+    # what the case is there for: finite fields everywhere, every refined box with live nodes, every ray leaving vertex sums behind
+    for s in range(G.NSRC):
+        assert np.isfinite(out["T%d" % s]).all() and out["T%d" % s].max() > 0 and (out["Sr%d" % s] == 0).any(), (name, s)
+        for i in range(G.NREC):
+            assert np.isfinite(out["fdm%d_%d" % (s, i)]).all() and np.abs(out["fdm%d_%d" % (s, i)]).max() > 0 and out["t%d_%d" % (s, i)] > 0
+    if (nx, ny) == (18, 35) or (nx, ny) == (35, 18):
+        assert NX != NZ
+    if name in ("unequal", "taipei", "north65", "north80", "south50", "dice3"):
+        assert out["grid"][2] != out["grid"][3]
+
+
+# ---- the dispersion inputs of tests/test_gpu_dispersion.py ------------------------------------------------------------------------------------
+
+def dispersion_envelope_cases():
+    """name -> (nx, ny, nz, minthk, model, periods, kernels, iwave, igr, rmax, failed roots expected): the model of
+    test_every_variant_gives_the_same_bits with kernels and of test_failure_count_and_first_failure without, all four wave kinds, and the
+    natural sizes whose models are there for the arithmetic (curves_34400 and curves_8600 are smooth models sized for the lane rule)"""
+    out = {}
+    for iwave, igr in DEPTH:
+        # Love: the columns without any contrast have no root at long periods; Rayleigh: the slow half space has none
+        out["variants-%d-%d" % (iwave, igr)] = (6, 4, 12, 3.0, D.edge_model, D.EDGE_T, True, iwave, igr, 45, True)
+        out["failures-%d-%d" % (iwave, igr)] = (6, 4, 12, 3.0, D.edge_model, D.EDGE_T[:10], False, iwave, igr, 45, True)
+    for name, (nx, ny, nz, minthk, model, t, kernels, iwave, igr, rmax, _) in D.NATURAL.items():
+        if name not in ("curves_34400", "curves_8600"):
+            out["%s-%d-%d" % (name, iwave, igr)] = (nx, ny, nz, minthk, model, t, kernels, iwave, igr, rmax, NATURAL_FAIL[name])
+    return out
+
+
+# whether a natural size holds failed roots (pv = 0): periods of 90 s and more on edge_model's columns without contrast / with a slow half
+# space; nz64 (there for rmax 127, the layer tables in global scratch) reaches 250 km depth and keeps every root up to its 200 s
+NATURAL_FAIL = {"rmax64": True, "rmax65": True, "curves_3870": True, "nz64": False, "nper60": True}
+
+
+def dispersion_envelope(side, case):
+    nx, ny, nz, minthk, model, t, kernels, iwave, igr = case[:9]
+    vel, depz = model(nx, ny, nz), D.depths(nz)
+    r = L.depthkernel(side.name, vel, depz, minthk, iwave, igr, t, kernels)
+    return dict(zip(("pv", "sen_vs", "sen_vp", "sen_rho"), r)) if kernels else {"pv": r}
+
+
+ENVELOPE = dispersion_envelope_cases()
+
+
+@pytest.mark.parametrize("name", list(ENVELOPE))
+def test_dispersion_envelope(name):
+    """depthkernel / caldespersion (CalSurfG.f90:1461-1597, :2320-2368) on the inputs the device dispersion tests trust the oracle on:
+    low-velocity zones, no contrast, a slow half space, a 1 km/s surface layer, a fast lid; periods from 0.02 s to 1000 s; failed roots;
+    rmax 45, 64, 65 and 127; 60 periods in one call"""
+    case = ENVELOPE[name]
+    nx, ny, nz, minthk = case[:4]
+    assert D.layer_count(D.depths(nz), minthk) == case[9]
+    out = refrecord.check("dispersion_envelope[%s]" % name, lambda side: dispersion_envelope(side, case))
+    failed = out["pv"] == 0
+    assert failed.any() == case[10] and not failed.all(axis=0).any(), "%s: %d of %d roots failed" % (name, failed.sum(), failed.size)
+    assert all(np.isfinite(a).all() for a in out.values())
+
 
 def aprod(side):
     import ctypes as C
@@ -174,3 +263,7 @@ def recorded_cases():
     for kw in BOUNDARY:
         yield "boundary%s" % json.dumps(kw, sort_keys=True), lambda side, kw=kw: boundary(side, kw)
     yield "aprod", aprod
+    for name, kind in G.PAIRS:
+        yield "fields_rays_geometry[%s-%s]" % (name, kind), lambda side, a=(name, kind): fields_rays_geometry(side, *a)
+    for name, case in ENVELOPE.items():
+        yield "dispersion_envelope[%s]" % name, lambda side, case=case: dispersion_envelope(side, case)
