@@ -117,6 +117,30 @@ def test_voronoi_boundary_case_against_the_oracle(boundary, local_size, itnlim):
         e.close(); e2.close()
 
 
+@pytest.mark.parametrize("ncells", [1, 2, 64, 65])
+def test_voronoi_tiny_cell_counts(boundary, ncells):
+    """ncells = 1 (k_b_chain's len == 1 exit, localVecs = 1: every member the same one-column system), 2, and 64 / 65 on the wave edge
+    of the chain: five members == the oracle's LSMR and dsa_lsmr on M_k under the three argument sets of the test above"""
+    c, fwd = boundary
+    S = system(c, weight0=2.0, fwd=fwd)
+    nd, n = c["ndata"], S["n"]
+    xyz = lattice_xyz(c)
+    seeds = invert.voronoi_seeds(n, ncells, 5, seed=3 + ncells)
+    e, e2 = Engine(0), Engine(0)
+    try:
+        load(e, S)
+        for local_size, itnlim in ((10, 400), (0, 100), (3, 7)):
+            kw = dict(itnlim=itnlim, local_size=local_size)
+            V = e.lsmr_voronoi(S["b"], nd, ncells, xyz, seeds, 0.5, **kw)
+            assert V["z"].shape == (5, ncells) and V["cell"].shape == (5, n)
+            assert np.array_equal(V["cell"], invert.voronoi_cells(xyz, seeds))
+            assert_members(V, S, nd, ncells, 0.5, range(5), engine=e2, **kw)
+            assert_stats(V)
+            assert min(int(v) for v in V["itn"]) >= 1
+    finally:
+        e.close(); e2.close()
+
+
 def test_voronoi_identity_tessellation(boundary):
     """ncells = n, seeds 0 .. n-1: every unknown is its own cell, and the result is the oracle's LSMR on the data rows alone"""
     c, fwd = boundary
