@@ -11,6 +11,7 @@
 // k_radial_lateral_start are that system's own.
 // k_latres_* (DESIGN.md section 27): the resolution of the laterally coupled step, a batch of section 24's solves, one lane per member.
 // k_sample_* (DESIGN.md section 29): the Metropolis chains of the Monte-Carlo depth inversion, one thread per (column, chain).
+// k_sample_shape, k_sample_propose_block, k_sample_accept_block: the columns' shapes and the block sweeps.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -355,6 +356,43 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_accept(SampleView S, in
     sample_accept(S, c, q, sweep);
 }
 
+// The block sweeps: the two kernels above with a SampleBlockView beside the view, launched in place of them in a
+// block sweep and in no other, so that the kernels above stay what they were.  A chain of a column whose shape is flagged takes the
+// single-node path inside them.  The block proposal keeps its M steps in a thread's own array (63 doubles: 512 bytes of scratch); all chains of a
+// column read the same L and r.
+__global__ void __launch_bounds__(kSampleBlock) k_sample_propose_block(SampleView S, SampleBlockView B, int sweep)
+{
+    long long c; int q;
+    if (!sample_thread(S, &c, &q)) return;
+    sample_propose_block(S, B, c, q, sweep);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_accept_block(SampleView S, SampleBlockView B, int sweep)
+{
+    long long c; int q;
+    if (!sample_thread(S, &c, &q)) return;
+    sample_accept_block(S, B, c, q, sweep);
+}
+
+// k_sample_shape: the shape of every interior column for the block proposals, k_column_step's launch shape and LDS work arrays: assemble
+// and factor, then the packed triangle (T, ncol), r (M, ncol) and the flag (ncol) to global memory, column fastest.  The model is not
+// touched.  The ring's and a flagged column's tri and r are the caller's zeros.
+__global__ void __launch_bounds__(64) k_sample_shape(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                    const double* __restrict__ pv, const double* __restrict__ S, float smooth, float damp,
+                                                    double* __restrict__ tri, double* __restrict__ r, int* __restrict__ nused, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
+    ColumnIn in;
+    column_in(in, M, K, c, ncol, obs, wt, pv);
+    in.S = S + c;
+    int n = 0;
+    const int f = sample_shape(in, smooth, damp, column_work(column_lds, M, K), tri + c, r + c, ncol, &n, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n; flag[c] = f; }
+}
+
 // one thread per (column, depth): t = depth * ncol + column.  nodes (5, M, ncol), cols (3, ncol), counts (8, ncol)
 __global__ void __launch_bounds__(kSampleBlock) k_sample_finish(SampleView S, double* __restrict__ nodes, double* __restrict__ cols, int* __restrict__ counts)
 {
@@ -618,6 +656,27 @@ void launch_sample_accept(const SampleView& S, int sweep, hipStream_t stream)
 {
     if (sample_empty(S)) return;
     hipLaunchKernelGGL(k_sample_accept, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, sweep);
+}
+
+void launch_sample_propose_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_propose_block, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, B, sweep);
+}
+
+void launch_sample_accept_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_accept_block, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, B, sweep);
+}
+
+void launch_sample_shape(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                         double* d_tri, double* d_r, int* d_nused, int* d_flag, hipStream_t stream)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return;
+    const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
+    hipLaunchKernelGGL(k_sample_shape, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, d_tri, d_r,
+                       d_nused, d_flag);
 }
 
 void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream)

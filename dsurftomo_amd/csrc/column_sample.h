@@ -19,6 +19,20 @@
 //             the smallest phi + psi of the kept sweeps and its model (the first one wins a tie)
 //   finish    per (column, depth), chains ascending -- see sample_finish
 //
+// Block proposals, switched on beside the above by a SampleBlockView; without one, or with block_every = 0, every bit is
+// the above's:
+//   shape     per column, once: column_system.h's column_assemble and column_factor on the column's curve and combined depth kernels, N = G^T G
+//             + smooth^2 L^T L + damp^2 I = L D L^T; kept: the packed triangle as column_factor leaves it (N's diagonal, L below it),
+//             r_l = sample_rsqrt(d_l), the flag (dsa_columns_step's: 2 without a used datum, 1 at a bad pivot; then tri and r stay 0)
+//   rsqrt     sample_rsqrt(d) = 1 / sqrt(d): the exponent halved by integer operations, a seed from the mantissa's bits, six Newton steps
+//             whatever d; plain fp64, no libm
+//   kind      sweep s >= 1 is a block sweep iff block_every > 0 and s % block_every == 0; in one, a chain of a column whose shape flag is 0
+//             makes a block proposal, any other chain the single-node proposal above
+//   block     draws 3 + l: z_l = 2u - 1, y_l = z_l r_l; L^T delta = y by column_solve's back substitution (i descending, the terms p = i+1 ..
+//             M-1 subtracted ascending); v'_l = v_l + (float)(block_scale delta_l) in fp32.  Any v'_l outside its box: only the mark is
+//             written.  Else pold_all gets the M old values, v the M new ones, pnode = -1.  The Metropolis test is the one above (draw 2);
+//             a rejection puts all M values back.  Block counters (3, chain, column): proposed, accepted, out of box
+//
 // fp64 under -ffp-contract=off, no square root, IEEE division: one value per figure whatever computes it.  One thread per (column, chain)
 // (column_kernels.hip: k_sample_*) or a loop over them (tests/hostcheck_column_sample.cpp); a thread's sums are its own sequential chains and
 // no thread reads what another writes in the same launch, so the mapping cannot change a bit.
@@ -33,6 +47,7 @@ namespace dsa {
 // what the last sweep did with a chain's proposal
 enum { kSampleIdle = -1, kSamplePending = 0, kSampleOutOfBox = 1, kSampleAccepted = 2, kSampleRejected = 3, kSampleNoRoot = 4 };
 enum { kSampleCntAccepted = 0, kSampleCntRejected = 1, kSampleCntOutOfBox = 2, kSampleCntNoRoot = 3, kSampleCounters = 4 };
+enum { kSampleBlkProposed = 0, kSampleBlkAccepted = 1, kSampleBlkOutOfBox = 2, kSampleBlockCounters = 3 };
 // the finish: per (column, depth) five doubles, per column three doubles and eight ints
 enum { kSampleMean = 0, kSampleVar = 1, kSampleW = 2, kSampleB = 3, kSampleBest = 4, kSampleNodeFigures = 5 };
 enum { kSamplePhiStart = 0, kSampleBestE = 1, kSampleMeanPhi = 2, kSampleColumnFigures = 3 };
@@ -60,6 +75,17 @@ struct SampleView {
     unsigned long long* used;                          // (ncol): bit k set where datum k is used
     int* nused; int* flag;                             // (ncol)
     double* phi0;                                      // (ncol): phi of the start
+};
+
+// the block proposals' state, passed beside the view: the shape of every column and what a block sweep keeps
+struct SampleBlockView {
+    const double* tri;                                 // (column_tri_size(M), ncol): N's diagonal, L below it, column_tri's order
+    const double* r;                                   // (M, ncol): r_l = sample_rsqrt(d_l)
+    const int* flag;                                   // (ncol): the shape's flag
+    float* pold_all;                                   // (M, C, ncol): the values a block proposal replaced
+    int* cnt;                                          // (3, C, ncol): block proposals made, accepted, out of the box
+    int block_every;                                   // 0: no block sweeps
+    double block_scale;
 };
 
 DSA_CS unsigned long long sample_mix(unsigned long long x)
@@ -116,6 +142,29 @@ DSA_CS double sample_neglog(unsigned long long k)
     const double lnm = 2.0 * s * t, dn = (double)n;
     const double r = dn * 6.93147180369123816490e-01 + (lnm + dn * 1.90821492927058770002e-10);      // ln 2 in two parts
     return -r;
+}
+
+// 1 / sqrt(d) for a normal positive finite d.  d = m 4^h with m in [1, 4) by integer operations on the exponent; the seed is the bits of m
+// halved and taken from a constant (relative error below 3.5 %), six Newton steps y = y (1.5 - (m / 2) y y) whatever d (the fourth is at
+// rounding level already), the result y 2^-h, an exact scaling.  Within 1e-15 relative of 1 / math.sqrt(d) (measured: tests/
+// test_hostcheck_column_sample_block.py); its last bit is not claimed, only that it is the same whatever computes it.  Outside that range
+// the sign is ignored, a zero or subnormal is read as if it had the hidden bit, an infinity or NaN as a number of exponent 1024: a finite
+// positive value that is not 1 / sqrt(d).  column_factor's pivots are finite and > 0.
+DSA_CS double sample_rsqrt(double d)
+{
+    unsigned long long b;
+    __builtin_memcpy(&b, &d, sizeof b);
+    const int e = (int)((b >> 52) & 0x7FFull) - 1023, odd = e & 1, h = (e - odd) / 2;
+    const unsigned long long mb = ((unsigned long long)(1023 + odd) << 52) | (b & 0x000FFFFFFFFFFFFFull);
+    const double m = sample_from_bits(mb), hm = 0.5 * m;
+    double y = sample_from_bits(0x5FE6EB50C7B537A9ull - (mb >> 1));
+    y = y * (1.5 - hm * y * y);
+    y = y * (1.5 - hm * y * y);
+    y = y * (1.5 - hm * y * y);
+    y = y * (1.5 - hm * y * y);
+    y = y * (1.5 - hm * y * y);
+    y = y * (1.5 - hm * y * y);
+    return y * sample_from_bits((unsigned long long)(1023 - h) << 52);
 }
 
 DSA_CS bool sample_interior(int nx, int ny, long long c)
@@ -272,8 +321,47 @@ DSA_CS void sample_propose(const SampleView& S, long long c, int q, int sweep)
     S.pmark[at] = kSamplePending;
 }
 
-// the Metropolis test of sweep `sweep` after its dispersion runs, and the sweep's share of the moments
-DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep)
+// a block sweep, and a chain that makes a block proposal in it
+DSA_CS bool sample_block_sweep(const SampleBlockView& B, int sweep) { return B.block_every > 0 && sweep % B.block_every == 0; }
+DSA_CS bool sample_block_chain(const SampleBlockView& B, long long c, int sweep) { return sample_block_sweep(B, sweep) && B.flag[c] == kColumnOk; }
+
+// the proposal of sweep `sweep` (>= 1) where block proposals are switched on: the block proposal of a chain of a column with a shape in a
+// block sweep, the single-node proposal above for every other
+DSA_CS void sample_propose_block(const SampleView& S, const SampleBlockView& B, long long c, int q, int sweep)
+{
+    const long long at = sample_at(S, c, q);
+    if (sample_idle(S, c)) { S.pmark[at] = kSampleIdle; return; }
+    if (!sample_block_chain(B, c, sweep)) { sample_propose(S, c, q, sweep); return; }
+    const int M = S.nz - 1;
+    double delta[kColumnMaxM];
+    for (int i = M - 1; i >= 0; --i) {
+        const double u = sample_unit(sample_bits(S.seed, (unsigned long long)c, (unsigned long long)q, (unsigned long long)sweep, (unsigned long long)(3 + i)));
+        double s = (2.0 * u - 1.0) * B.r[(long long)i * S.ncol + c];
+        for (int p = i + 1; p < M; ++p) s -= B.tri[(long long)column_tri(p, i) * S.ncol + c] * delta[p];
+        delta[i] = s;
+    }
+    bool outside = false;
+    for (int l = 0; l < M; ++l) {
+        const float x = S.v[sample_node(S, c, q, l)] + (float)(B.block_scale * delta[l]);
+        float lo, hi;
+        sample_box(S, c, l, &lo, &hi);
+        if (x < lo || x > hi) outside = true;
+    }
+    if (outside) { S.pmark[at] = kSampleOutOfBox; return; }
+    for (int l = 0; l < M; ++l) {
+        const long long e = sample_node(S, c, q, l);
+        const float old = S.v[e];
+        B.pold_all[e] = old;
+        S.v[e] = old + (float)(B.block_scale * delta[l]);
+    }
+    S.pnode[at] = -1;
+    S.pmark[at] = kSamplePending;
+}
+
+// the Metropolis test of sweep `sweep` after its dispersion runs, and the sweep's share of the moments.  Block: B is read, a chain that made
+// a block proposal counts it in B's counters too and a rejection puts all its M values back; without Block, B is not looked at.
+template <bool Block>
+DSA_CS void sample_accept_any(const SampleView& S, const SampleBlockView* B, long long c, int q, int sweep)
 {
     const long long at = sample_at(S, c, q);
     const int mark = S.pmark[at];
@@ -281,8 +369,12 @@ DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep)
     const int M = S.nz - 1;
     const long long stride = (long long)S.C * S.ncol;
     int* cnt = S.cnt + at;                      // counter w at cnt[w * stride]
+    bool block = false;
+    if (Block) block = sample_block_chain(*B, c, sweep);
+    if (Block && block) B->cnt[kSampleBlkProposed * stride + at] += 1;
     if (mark == kSampleOutOfBox) {
         cnt[kSampleCntOutOfBox * stride] += 1; cnt[kSampleCntRejected * stride] += 1;
+        if (Block && block) B->cnt[kSampleBlkOutOfBox * stride + at] += 1;
     } else {
         bool noroot = false;
         const double phi_new = sample_phi(S, c, q, S.used[c], &noroot);
@@ -303,8 +395,13 @@ DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep)
             S.phi[at] = phi_new; S.psi[at] = psi_new;
             cnt[kSampleCntAccepted * stride] += 1;
             S.pmark[at] = kSampleAccepted;
+            if (Block && block) B->cnt[kSampleBlkAccepted * stride + at] += 1;
         } else {
-            S.v[sample_node(S, c, q, S.pnode[at])] = S.pold[at];
+            if (Block && block) {
+                for (int l = 0; l < M; ++l) S.v[sample_node(S, c, q, l)] = B->pold_all[sample_node(S, c, q, l)];
+            } else {
+                S.v[sample_node(S, c, q, S.pnode[at])] = S.pold[at];
+            }
             cnt[kSampleCntRejected * stride] += 1;
             if (noroot) cnt[kSampleCntNoRoot * stride] += 1;
             S.pmark[at] = noroot ? kSampleNoRoot : kSampleRejected;
@@ -324,6 +421,27 @@ DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep)
         for (int l = 0; l < M; ++l) S.best_v[sample_node(S, c, q, l)] = S.v[sample_node(S, c, q, l)];
     }
     S.nkept[at] += 1;
+}
+
+DSA_CS void sample_accept(const SampleView& S, long long c, int q, int sweep) { sample_accept_any<false>(S, nullptr, c, q, sweep); }
+DSA_CS void sample_accept_block(const SampleView& S, const SampleBlockView& B, long long c, int q, int sweep) { sample_accept_any<true>(S, &B, c, q, sweep); }
+
+// The shape of one column (block proposals): column_assemble and column_factor, unchanged, on the column's inputs; where the column has a
+// used datum and every pivot is good, the packed triangle goes to tri[e * stride], r_l = sample_rsqrt(d_l) to r[l * stride] -- elsewhere
+// both stay as the caller left them.  The model is not stepped.  Returns the flag; every lane returns the same.
+template <class Sync>
+DSA_CS int sample_shape(const ColumnIn& in, float smooth, float damp, const ColumnWork& w, double* tri, double* r, long long stride, int* nused, int lane,
+                        int nlanes, Sync sync)
+{
+    const double lambda2 = (double)smooth * (double)smooth, mu2 = (double)damp * (double)damp;
+    double chi2 = 0.0;
+    *nused = column_assemble(in, lambda2, mu2, w, &chi2, lane, nlanes, sync);
+    if (*nused == 0) return kColumnNoData;
+    const int flag = column_factor(in.M, w, lane, nlanes, sync);
+    if (flag != kColumnOk) return flag;
+    for (int e = lane; e < column_tri_size(in.M); e += nlanes) tri[e * stride] = w.tri[e];
+    for (int l = lane; l < in.M; l += nlanes) r[l * stride] = sample_rsqrt(w.d[l]);
+    return kColumnOk;
 }
 
 // The finish of (column c, depth l < M), chains ascending, every sum from 0.0; n = nkept (the same for every chain of a column), m_q =

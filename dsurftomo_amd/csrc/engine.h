@@ -379,6 +379,20 @@ struct Engine {
     int columns_sample_state(float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept, double* best_e, float* best_v,
                              int* pnode, float* pold, int* pmark, int* reseeded);
     int sample_refused(const char* who);
+    // block proposals of the sample stage (dsa_columns_sample_shape, dsa_columns_sample_blocks, dsa_columns_sample_block_state; k_sample_shape,
+    // k_sample_*_block).  The shape (blk_tri, blk_r, blk_flag) is built on a single-model stage with columns_resolution's
+    // state, held with its dimensions until the next shape call, and read by no other call; sample_block_every > 0 (set by
+    // columns_sample_blocks on an open sample stage before its first sweep, cleared by every columns_sample_begin) makes every
+    // sample_block_every-th sweep a block sweep.
+    bool blk_held = false;
+    int blk_nx = 0, blk_ny = 0, blk_nz = 0, sample_block_every = 0;
+    double sample_block_scale = 0.0;
+    OwnedBuf<double> blk_tri, blk_r;
+    OwnedBuf<int> blk_flag, blk_nused, blk_cnt;
+    OwnedBuf<float> blk_pold;
+    int columns_sample_shape(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag);
+    int columns_sample_blocks(int block_every, double block_scale);
+    int columns_sample_block_state(float* pold_all, int* counters);
 
     // radial anisotropy in the direct inversion (dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial; DESIGN.md
     // section 28).  radial_sens: Srow holds the depth factors of every slot on the model of its wave type (k_sen_combine_radial) and

@@ -666,6 +666,15 @@ static SampleView sample_view(Engine& e)
     return S;
 }
 
+// the block proposals' state where it lies; block_every 0 while they are off (the buffers may then be empty: nothing reads them)
+static SampleBlockView sample_block_view(Engine& e)
+{
+    SampleBlockView B{};
+    B.tri = e.blk_tri.p; B.r = e.blk_r.p; B.flag = e.blk_flag.p; B.pold_all = e.blk_pold.p; B.cnt = e.blk_cnt.p;
+    B.block_every = e.sample_block_every; B.block_scale = e.sample_block_scale;
+    return B;
+}
+
 // dsa_columns_sample_begin: everything is checked before the device is touched; then a stage of nchains models (dispersion_setup), whose
 // model store k_sample_setup writes where it lies, the set-up's runs of the plan (times only), and the chains' phi and psi.
 int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns, const int* iwave, const int* igr,
@@ -716,6 +725,7 @@ int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const floa
         first += nper[r];
     }
     sample_has_wt = wt != nullptr; sample_sweep = 0; sample_burn = burn; sample_seed = seed;
+    sample_block_every = 0; sample_block_scale = 0.0;
     sample_lam2 = (double)smooth * (double)smooth; sample_step = (double)step; sample_spread = (double)spread; sample_two_t = 2.0 * (double)temperature;
     sample_width = width; sample_minvel = minvel; sample_maxvel = maxvel;
     HIP_TRY(this, hipMemcpyAsync(smp_v0.p, vels, ncol * nz * 4, hipMemcpyHostToDevice, stream));
@@ -742,12 +752,16 @@ int Engine::columns_sample_run(int nsweeps)
     if (nsweeps < 0 || (long long)sample_sweep + nsweeps > 0x7fffffffll) { fail(DSA_ERR_ARGUMENT, "columns_sample_run: nsweeps %d after %d sweeps", nsweeps, sample_sweep); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
     const SampleView S = sample_view(*this);
+    const SampleBlockView B = sample_block_view(*this);
     for (int s = 0; s < nsweeps; ++s) {
         const int sweep = sample_sweep + 1;
-        launch_sample_propose(S, sweep, stream);
+        const bool block = sample_block_sweep(B, sweep);      // (only the sweep's number decides its kind: run(n) is n times run(1))
+        if (block) launch_sample_propose_block(S, B, sweep, stream);
+        else launch_sample_propose(S, sweep, stream);
         for (const SampleRun& run : sample_plan)
             if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { sample_open = false; disp_ready = false; return rc; }
-        launch_sample_accept(S, sweep, stream);
+        if (block) launch_sample_accept_block(S, B, sweep, stream);
+        else launch_sample_accept(S, sweep, stream);
         sample_sweep = sweep;
     }
     HIP_TRY(this, hipGetLastError());
@@ -794,6 +808,75 @@ int Engine::columns_sample_state(float* models, double* phi, double* psi, int* c
     DSA_SAMPLE_GET(pmark, smp_pmark.p, cc);
     DSA_SAMPLE_GET(reseeded, smp_reseed.p, cc);
     #undef DSA_SAMPLE_GET
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_shape: the shape of every interior column for the block proposals, from the resident curves and
+// kernels dsa_columns_resolution reads, under its rules.  The stage is read only, as dsa_columns_resolution's.  The shape lies in buffers of
+// its own, which no other call but the block sweeps reads.
+int Engine::columns_sample_shape(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag)
+{
+    if (int rc = columns_front("columns_sample_shape", nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f)) return rc;
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, T = (size_t)column_tri_size(M);
+    HIP_TRY(this, hipSetDevice(device));
+    blk_held = false;
+    if (int rc = columns_stage_in(1, obs, wt, false)) return rc;
+    if (ensure(blk_tri, T * ncol) || ensure(blk_r, (size_t)M * ncol) || ensure(blk_flag, ncol) || ensure(blk_nused, ncol)) return status;
+    // (the outer ring of columns and a flagged column report zeros: the kernel runs on the interior and writes where it factored)
+    HIP_TRY(this, hipMemsetAsync(blk_tri.p, 0, T * ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(blk_r.p, 0, (size_t)M * ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(blk_flag.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(blk_nused.p, 0, ncol * 4, stream));
+    launch_sample_shape(disp_nx, disp_ny, disp_nz, K, col_obs.p, wt ? col_wt.p : nullptr, pvstore.p, col_S.p, smooth, damp, blk_tri.p, blk_r.p, blk_nused.p, blk_flag.p,
+                        stream);
+    HIP_TRY(this, hipGetLastError());
+    if (tri) HIP_TRY(this, hipMemcpyAsync(tri, blk_tri.p, T * ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (r) HIP_TRY(this, hipMemcpyAsync(r, blk_r.p, (size_t)M * ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (flag) HIP_TRY(this, hipMemcpyAsync(flag, blk_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    blk_nx = disp_nx; blk_ny = disp_ny; blk_nz = disp_nz; blk_held = true;
+    return 0;
+}
+
+// dsa_columns_sample_blocks: block sweeps on (block_every > 0) or off (0) on an open sample stage that has not run a sweep; a refusal
+// leaves the stage as it was.  The block state is cleared.
+int Engine::columns_sample_blocks(int block_every, double block_scale)
+{
+    const char* who = "columns_sample_blocks";
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
+    if (sample_sweep != 0) { fail(DSA_ERR_STATE, "%s: %d sweeps have been run; the kind of the sweeps is set before the first", who, sample_sweep); return DSA_ERR_STATE; }
+    if (!blk_held || blk_nx != disp_nx || blk_ny != disp_ny || blk_nz != disp_nz) {
+        if (blk_held) fail(DSA_ERR_STATE, "%s: the held shape is of %d x %d x %d nodes, the stage of %d x %d x %d; call dsa_columns_sample_shape on this model first", who, blk_nx, blk_ny, blk_nz, disp_nx, disp_ny, disp_nz);
+        else fail(DSA_ERR_STATE, "%s: no shape is held; call dsa_columns_sample_shape before dsa_columns_sample_begin", who);
+        return DSA_ERR_STATE;
+    }
+    if (block_every < 0) { fail(DSA_ERR_ARGUMENT, "%s: block_every %d must be >= 0", who, block_every); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(block_scale) || block_scale <= 0.0) { fail(DSA_ERR_ARGUMENT, "%s: block_scale %g must be finite and > 0", who, block_scale); return DSA_ERR_ARGUMENT; }
+    const size_t cc = (size_t)disp_nx * disp_ny * disp_nmodels, M = (size_t)disp_nz - 1;
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(blk_pold, M * cc) || ensure(blk_cnt, kSampleBlockCounters * cc)) return status;
+    HIP_TRY(this, hipMemsetAsync(blk_pold.p, 0, M * cc * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(blk_cnt.p, 0, kSampleBlockCounters * cc * 4, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    sample_block_every = block_every; sample_block_scale = block_scale;
+    return 0;
+}
+
+// dsa_columns_sample_block_state: the raw block state, for the tests; zeros while block sweeps are off; every pointer may be null
+int Engine::columns_sample_block_state(float* pold_all, int* counters)
+{
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_block_state: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
+    const size_t cc = (size_t)disp_nx * disp_ny * disp_nmodels, M = (size_t)disp_nz - 1;
+    if (sample_block_every == 0) {
+        if (pold_all) std::fill(pold_all, pold_all + M * cc, 0.0f);
+        if (counters) std::fill(counters, counters + kSampleBlockCounters * cc, 0);
+        return 0;
+    }
+    HIP_TRY(this, hipSetDevice(device));
+    if (pold_all) HIP_TRY(this, hipMemcpyAsync(pold_all, blk_pold.p, M * cc * 4, hipMemcpyDeviceToHost, stream));
+    if (counters) HIP_TRY(this, hipMemcpyAsync(counters, blk_cnt.p, kSampleBlockCounters * cc * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
@@ -2620,6 +2703,24 @@ int dsa_columns_sample_state(dsa_engine* e, float* models, double* phi, double* 
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_sample_state(models, phi, psi, counters, S1, S2, phisum, nkept, best_e, best_v, pnode, pold, pmark, reseeded);
+}
+
+int dsa_columns_sample_shape(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_shape(nmaps, obs, wt, smooth, damp, tri, r, flag);
+}
+
+int dsa_columns_sample_blocks(dsa_engine* e, int block_every, double block_scale)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_blocks(block_every, block_scale);
+}
+
+int dsa_columns_sample_block_state(dsa_engine* e, float* pold_all, int* counters)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_block_state(pold_all, counters);
 }
 
 int dsa_dispersion_begin_radial(dsa_engine* e, int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total,

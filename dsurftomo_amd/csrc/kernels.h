@@ -392,6 +392,15 @@ void launch_sample_setup(const SampleView& S, int phase, hipStream_t stream);
 void launch_sample_propose(const SampleView& S, int sweep, hipStream_t stream);
 void launch_sample_accept(const SampleView& S, int sweep, hipStream_t stream);
 void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream);
+// The block proposals (k_sample_shape, k_sample_propose_block, k_sample_accept_block).  launch_sample_shape: the
+// inputs of launch_column_step; d_tri (nz (nz - 1) / 2, ncol), d_r (nz - 1, ncol), d_nused, d_flag (ncol), zeroed by the caller (the kernel
+// runs on the interior and leaves a flagged column's tri and r alone).  A block sweep is launch_sample_propose_block, the dispersion runs,
+// launch_sample_accept_block, B (column_sample.h) beside S.
+struct SampleBlockView;
+void launch_sample_shape(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
+                         double* d_tri, double* d_r, int* d_nused, int* d_flag, hipStream_t stream);
+void launch_sample_propose_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream);
+void launch_sample_accept_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

@@ -5,7 +5,7 @@
                                   [--lateral W [--lateral-tol T] [--lateral-maxit N]] [--radial-resolution]
                                   [--lateral-resolution [--lateral-resolution-stride N] [--lateral-checkerboard NX,NY,NZ[,AMP]]]
                                   [--sample C,SWEEPS[,BURN] [--sample-step S] [--sample-spread P] [--sample-width W] [--sample-seed N]
-                                   [--sample-temperature T]]
+                                   [--sample-temperature T] [--sample-block EVERY [--sample-block-scale S]]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -102,10 +102,17 @@ out of the box and lost a root, the chains put back to the start at the set-up, 
 median and the worst R-hat and the share of the unknowns above 1.1.  --sample is refused with --radial and --lateral.  Without the flag
 nothing changes.  column_sample_twin is the Python twin (csrc/column_sample.h is the arithmetic).
 
+--sample-block EVERY [--sample-block-scale S], with --sample: every EVERY-th sweep proposes all nodes of a column at
+once, along the column's linearised posterior -- delta = S L^-T D^-1/2 z, z uniform in [-1, 1], L D L^T the factor of the step's normal matrix
+of the final model under the sampler's weights (columns_sample_shape, after the plan's runs with kernels once more).  S defaults to
+2.38 sqrt(3 T / M) for the M unknowns of a column.  A column whose factorisation fails keeps the single-node proposal.  The log gives the
+acceptance of the block and of the single-node proposals separately.  EVERY = 0 (the default) is the single-node sampler, bit for bit.
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -937,6 +944,67 @@ def sample_neglog(k):
     return -(dn * 6.93147180369123816490e-01 + (lnm + dn * 1.90821492927058770002e-10))
 
 
+def _f64_bits(x):
+    return int(np.array([x], np.float64).view(np.uint64)[0])
+
+
+def _f64_from_bits(b):
+    return float(np.array([b], np.uint64).view(np.float64)[0])
+
+
+def sample_rsqrt(d):
+    """1 / sqrt(d) for a normal positive finite d with the header's operations: d = m 4^h, m in [1, 4), by integer operations, the seed from m's
+    bits, six Newton steps y = y (1.5 - (m / 2) y y), the result y 2^-h"""
+    b = _f64_bits(float(d))
+    e = ((b >> 52) & 0x7FF) - 1023
+    odd = e & 1
+    h = (e - odd) // 2
+    mb = ((1023 + odd) << 52) | (b & 0x000FFFFFFFFFFFFF)
+    m = _f64_from_bits(mb)
+    hm = 0.5 * m
+    y = _f64_from_bits(0x5FE6EB50C7B537A9 - (mb >> 1))
+    for _ in range(6):
+        y = y * (1.5 - hm * y * y)
+    return y * _f64_from_bits((1023 - h) << 52)
+
+
+def sample_block_scale(M, temperature=1.0):
+    """the default scale of a block proposal: 2.38 sqrt(3 T / M) -- the random-walk optimum 2.38^2 / M of a proposal of M unknowns whose
+    draws z have variance 1 / 3, at temperature T"""
+    return 2.38 * math.sqrt(3.0 * float(temperature) / float(M))
+
+
+def column_tri(i, j):
+    """column_system.h's packed lower triangle, row by row: entry (i, j), j <= i"""
+    return i * (i + 1) // 2 + j
+
+
+def column_shape_twin(obs, wt, pv, S, smooth, damp):
+    """The shape of one column for the block proposals (csrc/column_sample.h: sample_shape): N = G^T G + smooth^2 L^T L + damp^2 I of the
+    column's data (obs, wt (K) fp32 or None, pv (K), S (K, M): column_step_twin's) factored as L D L^T.  Returns (tri (M (M + 1) / 2): N's
+    diagonal and L below it in column_tri's order, r (M) = sample_rsqrt(d), flag); flag 2 without a used datum, 1 at a bad pivot, tri and r
+    then zeros."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); S = np.asarray(S, np.float64)
+    K, M = S.shape
+    wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
+    tri = np.zeros(M * (M + 1) // 2); r = np.zeros(M)
+    used, rho, _, G = _twin_data(obs, wt, pv, S)
+    if not used.any():
+        return tri, r, 2
+    N, _ = _twin_normal(G, used, rho, float(f(smooth)) * float(f(smooth)), float(f(damp)) * float(f(damp)))
+    factor = _twin_factor(N)
+    if factor is None:
+        return tri, r, 1
+    Lm, d = factor
+    for i in range(M):
+        for j in range(i):
+            tri[column_tri(i, j)] = Lm[i, j]
+        tri[column_tri(i, i)] = N[i, i]
+        r[i] = sample_rsqrt(d[i])
+    return tri, r, 0
+
+
 def sample_psi(v, lam2):
     """smooth^2 |L v|^2 of one column's M values, the rows in the header's order, every row summed from 0.0 over its unknowns ascending"""
     v = [float(x) for x in v]
@@ -954,12 +1022,17 @@ def sample_psi(v, lam2):
     return lam2 * s
 
 
-def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, smooth, step, spread, width, temperature, minvel, maxvel, seed, after=None):
+def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, smooth, step, spread, width, temperature, minvel, maxvel, seed, after=None,
+                       shape=None, block_every=0, block_scale=None):
     """The Monte-Carlo depth inversion in Python integers and NumPy float64 / float32 scalars, the header's operations in the header's order.
     start (nz, ny * nx) fp32; obs / wt (K, ny * nx) fp32, wt may be None (1); forward(models (nz, C, ncol) fp32) -> pv (C, K, ncol) fp64 in
     place of the dispersion stage (a value <= 0: no root); after(sweep, state): a hook after the set-up (sweep 0) and every sweep.  Returns
     dict(models, phi, psi, counters (4, C, ncol): accepted, rejected, out of box, no root; S1, S2, phisum, nkept, best_e, best_v, pnode,
-    pold, pmark, reseeded, used, nused, flag, phi_start, and the finish: mean, var, W, B, best (M, ncol), best_energy, mean_phi (ncol))."""
+    pold, pmark, reseeded, used, nused, flag, phi_start, and the finish: mean, var, W, B, best (M, ncol), best_energy, mean_phi (ncol)).
+    Block proposals: shape = dict(tri (M (M + 1) / 2, ncol), r (M, ncol), flag (ncol)), column_shape_twin's figures of
+    every column; sweep s is a block sweep where block_every > 0 and s % block_every == 0; block_scale None: sample_block_scale(M,
+    temperature).  The state then also holds pold_all (M, C, ncol) fp32 and block_counters (3, C, ncol): proposed, accepted, out of box.
+    With block_every = 0 (the default) the shape is not looked at and every bit is the single-node sampler's."""
     F = np.float32
     start = np.asarray(start, F)
     nz, ncol = start.shape
@@ -970,6 +1043,12 @@ def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, s
     width, minvel, maxvel = F(width), F(minvel), F(maxvel)
     interior = lambda c: 1 <= c % nx <= nx - 2 and 1 <= c // nx <= ny - 2
     a_of = lambda k, c: 1.0 if wt is None else float(F(wt[k, c]))
+    block_every = int(block_every)
+    if block_every > 0:
+        if shape is None:
+            raise ValueError("column_sample_twin: block sweeps need a shape")
+        block_scale = sample_block_scale(M, float(F(temperature))) if block_scale is None else float(block_scale)
+        tri, rr, sflag = (np.asarray(shape[n]) for n in ("tri", "r", "flag"))
 
     def box(c, l):
         lo, hi = F(start[l, c] - width), F(start[l, c] + width)
@@ -989,7 +1068,8 @@ def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, s
     st = dict(models=np.zeros((nz, C, ncol), F), phi=np.zeros((C, ncol)), psi=np.zeros((C, ncol)), counters=np.zeros((4, C, ncol), np.int32),
               S1=np.zeros((M, C, ncol)), S2=np.zeros((M, C, ncol)), phisum=np.zeros((C, ncol)), nkept=np.zeros((C, ncol), np.int32), best_e=np.zeros((C, ncol)),
               best_v=np.zeros((M, C, ncol), F), pnode=np.zeros((C, ncol), np.int32), pold=np.zeros((C, ncol), F), pmark=np.full((C, ncol), -1, np.int32),
-              reseeded=np.zeros((C, ncol), np.int32), nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32), phi_start=np.zeros(ncol))
+              reseeded=np.zeros((C, ncol), np.int32), nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32), phi_start=np.zeros(ncol),
+              pold_all=np.zeros((M, C, ncol), F), block_counters=np.zeros((3, C, ncol), np.int32))
     v = st["models"]
     for q in range(C):
         for c in range(ncol):
@@ -1025,11 +1105,29 @@ def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, s
     moving = [c for c in range(ncol) if interior(c) and used_of.get(c)]
     if after is not None:
         after(0, st)
-    cnt = st["counters"]
+    cnt = st["counters"]; bcnt = st["block_counters"]
     for sweep in range(1, int(sweeps) + 1):
         st["pmark"][...] = -1
+        blocks = block_every > 0 and sweep % block_every == 0
         for q in range(C):
             for c in moving:
+                if blocks and sflag[c] == 0:
+                    delta = [0.0] * M
+                    for i in range(M - 1, -1, -1):
+                        u = sample_unit(sample_bits(seed, c, q, sweep, 3 + i))
+                        s = (2.0 * u - 1.0) * float(rr[i, c])
+                        for p in range(i + 1, M):
+                            s = s - float(tri[column_tri(p, i), c]) * delta[p]
+                        delta[i] = s
+                    new = [F(v[l, q, c] + F(block_scale * delta[l])) for l in range(M)]
+                    if any(new[l] < box(c, l)[0] or new[l] > box(c, l)[1] for l in range(M)):
+                        st["pmark"][q, c] = 1
+                        continue
+                    st["pold_all"][:, q, c] = v[:M, q, c]
+                    v[:M, q, c] = new
+                    st["pnode"][q, c] = -1
+                    st["pmark"][q, c] = 0
+                    continue
                 u0 = sample_unit(sample_bits(seed, c, q, sweep, 0)); u1 = sample_unit(sample_bits(seed, c, q, sweep, 1))
                 l = min(int(u0 * float(M)), M - 1)
                 old = v[l, q, c]
@@ -1044,8 +1142,13 @@ def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, s
         pv = np.asarray(forward(v), np.float64).reshape(C, K, ncol)
         for q in range(C):
             for c in moving:
+                block = blocks and sflag[c] == 0
+                if block:
+                    bcnt[0, q, c] += 1
                 if st["pmark"][q, c] == 1:
                     cnt[2, q, c] += 1; cnt[1, q, c] += 1
+                    if block:
+                        bcnt[2, q, c] += 1
                 else:
                     phi_new, bad = phi_of(pv, c, q, used_of[c])
                     accepted, psi_new = False, 0.0
@@ -1062,8 +1165,13 @@ def column_sample_twin(nx, ny, start, obs, wt, forward, nchains, sweeps, burn, s
                         st["phi"][q, c] = phi_new; st["psi"][q, c] = psi_new
                         cnt[0, q, c] += 1
                         st["pmark"][q, c] = 2
+                        if block:
+                            bcnt[1, q, c] += 1
                     else:
-                        v[st["pnode"][q, c], q, c] = st["pold"][q, c]
+                        if block:
+                            v[:M, q, c] = st["pold_all"][:, q, c]
+                        else:
+                            v[st["pnode"][q, c], q, c] = st["pold"][q, c]
                         cnt[1, q, c] += 1
                         if bad:
                             cnt[3, q, c] += 1
@@ -1403,9 +1511,16 @@ def parse_sample(text):
     return chains, sweeps, burn
 
 
-def check_sample(sample=None, radial=False, lateral=None, step=None, spread=None, width=None, temperature=None, seed=None):
-    """what --sample asks of the other flags, before the library is loaded (ValueError).  Returns parse_sample's tuple, or None."""
+def check_sample(sample=None, radial=False, lateral=None, step=None, spread=None, width=None, temperature=None, seed=None, block=0, block_scale=None):
+    """what --sample, --sample-block and --sample-block-scale ask of the other flags, before the library is loaded (ValueError).  Returns
+    parse_sample's tuple, or None."""
+    if block is not None and block < 0:
+        raise ValueError("--sample-block must be >= 0, not %r" % (block,))
+    if block_scale is not None and not (np.isfinite(block_scale) and block_scale > 0):
+        raise ValueError("--sample-block-scale must be finite and > 0, not %r" % (block_scale,))
     if sample is None:
+        if block:
+            raise ValueError("--sample-block needs --sample: the block proposals are the sampler's")
         return None
     if radial or lateral is not None:
         raise ValueError("--sample and %s exclude each other: the %s is not sampled" % (("--radial", "radial model") if radial else ("--lateral", "laterally coupled model")))
@@ -1489,15 +1604,30 @@ def rhat_summary(res):
 
 
 def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, step=DEFAULT_SAMPLE_STEP, spread=DEFAULT_SAMPLE_SPREAD, width=DEFAULT_SAMPLE_WIDTH,
-               seed=DEFAULT_SAMPLE_SEED, temperature=DEFAULT_SAMPLE_TEMPERATURE, log=print):
+               seed=DEFAULT_SAMPLE_SEED, temperature=DEFAULT_SAMPLE_TEMPERATURE, log=print, block_every=0, block_scale=None, damp=DEFAULT_DAMP):
     """--sample from the model start (nz, ny, nx): columns_sample_begin with the weights 1 / sigma where wt keeps a datum and smooth / sigma,
-    the sweeps, the two files, the log.  Returns dict(posterior: columns_sample_fetch's result, sample_sigma, rhat, posterior_path,
-    posterior_fit_path)."""
+    the sweeps, the two files, the log.  With block_every > 0 (--sample-block), on an engine whose stage holds start: first the runs of plan
+    once more with kernels and columns_sample_shape with the same weights and prior weight and damp / sigma, then, after the begin,
+    columns_sample_blocks(block_every, block_scale; None: sample_block_scale(nz - 1, temperature)).  Returns dict(posterior:
+    columns_sample_fetch's result, sample_sigma, rhat, posterior_path, posterior_fit_path; with block_every > 0 also block: dict(every, scale,
+    flagged: the columns whose shape was flagged, proposed, accepted, out_of_box: the block proposals summed over chains and columns))."""
     chains, sweeps, burn = sample
     w, lam = sample_scaling(wt, smooth, sigma, np.shape(obs))
+    block = None
+    if block_every > 0:
+        for wave, kind, t, first in plan:
+            eng.dispersion_run(wave, kind, t, True, first, first)
+        shape = eng.columns_sample_shape(obs, w, lam, float(damp) / float(sigma))
+        scale = sample_block_scale(c["nz"] - 1, temperature) if block_scale is None else float(block_scale)
+        block = dict(every=int(block_every), scale=scale, flagged=int((shape["flag"] == 1).sum()))
     eng.columns_sample_begin(start, c["depz"], c["minthk"], plan, obs, w, chains, lam, step, spread, width, temperature, float(c["minvel"]), float(c["maxvel"]), seed, burn)
+    if block is not None:
+        eng.columns_sample_blocks(block["every"], block["scale"])
     eng.columns_sample_run(sweeps)
     res = eng.columns_sample_fetch()
+    if block is not None:
+        bc = eng.columns_sample_block_state()["block_counters"]
+        block.update(proposed=int(bc[0].sum()), accepted=int(bc[1].sum()), out_of_box=int(bc[2].sum()))
     ppath = os.path.join(out_dir, "DSurfTomo.inDepthPosterior.dat")
     fpath = os.path.join(out_dir, "DSurfTomo.inDepthPosteriorFit.dat")
     write_posterior(ppath, c, start, res)
@@ -1509,6 +1639,13 @@ def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, ste
     if tried > 0:
         log(" depth sample: %.1f %% of the proposals accepted, %.1f %% out of the box, %.1f %% without a root" %
             tuple(100.0 * float(res[n].sum()) / tried for n in ("accepted", "out_of_box", "no_root")))
+    if block is not None:
+        single = tried - block["proposed"]
+        log(" depth sample: block proposals of scale %.4f every %s, %d columns with a flagged shape propose single nodes" %
+            (block["scale"], "sweep" if block["every"] == 1 else "%d sweeps" % block["every"], block["flagged"]))
+        log(" depth sample: %.1f %% of %d block proposals accepted (%.1f %% out of the box), %.1f %% of %d single-node proposals" %
+            (100.0 * float(_rate(block["accepted"], block["proposed"])), block["proposed"], 100.0 * float(_rate(block["out_of_box"], block["proposed"])),
+             100.0 * float(_rate(float(res["accepted"].sum()) - block["accepted"], single)), int(single)))
     if moved.any():
         log(" depth sample: phi per column from %.4g at the start to %.4g on average over the kept sweeps (median over the columns)" %
             (float(np.median(res["phi_start"][moved])), float(np.median(res["mean_phi"][moved]))))
@@ -1516,7 +1653,10 @@ def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, ste
     if sm is not None:
         log(" depth sample: R-hat of %d unknowns median %.4f, worst %.4f, %.1f %% above 1.1" % (sm["unknowns"], sm["median"], sm["worst"], 100.0 * sm["above"]))
     log(" depth sample: the posterior written to %s, the fit of the columns to %s" % (ppath, fpath))
-    return dict(posterior=res, sample_sigma=float(sigma), rhat=sm, posterior_path=ppath, posterior_fit_path=fpath)
+    out = dict(posterior=res, sample_sigma=float(sigma), rhat=sm, posterior_path=ppath, posterior_fit_path=fpath)
+    if block is not None:
+        out["block"] = block
+    return out
 
 
 # ---- the resolution of the laterally coupled step ----
@@ -1931,7 +2071,8 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
         log=print, resolution=False, sigma=None, radial=False, aniso=DEFAULT_ANISO, lateral=None, lateral_tol=DEFAULT_LATERAL_TOL,
         lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False, lateral_resolution=False,
         lateral_resolution_stride=1, lateral_checkerboard=None, sample=None, sample_step=DEFAULT_SAMPLE_STEP, sample_spread=DEFAULT_SAMPLE_SPREAD,
-        sample_width=DEFAULT_SAMPLE_WIDTH, sample_seed=DEFAULT_SAMPLE_SEED, sample_temperature=DEFAULT_SAMPLE_TEMPERATURE):
+        sample_width=DEFAULT_SAMPLE_WIDTH, sample_seed=DEFAULT_SAMPLE_SEED, sample_temperature=DEFAULT_SAMPLE_TEMPERATURE, sample_block=0,
+        sample_block_scale=None):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
@@ -1941,8 +2082,9 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     DepthRadialLeverage.dat beside --radial's files); sigma as with resolution.  With lateral and lateral_resolution: after the loop
     resolve_lateral's entries are added to the first item (DepthLateralResolution.dat and, with lateral_checkerboard, DepthLateralChecker.dat
     beside the two files); sigma as with resolution.  With sample ("C,SWEEPS[,BURN]"): after the loop (and the resolution) run_sample's entries
-    are added to the first item (DepthPosterior.dat and DepthPosteriorFit.dat beside the two files); sigma as with resolution."""
-    sampling = check_sample(sample, radial, lateral, sample_step, sample_spread, sample_width, sample_temperature, sample_seed)
+    are added to the first item (DepthPosterior.dat and DepthPosteriorFit.dat beside the two files); sigma as with resolution; sample_block
+    (EVERY > 0) makes every EVERY-th sweep a block proposal of scale sample_block_scale (None: sample_block_scale(nz - 1, temperature))."""
+    sampling = check_sample(sample, radial, lateral, sample_step, sample_spread, sample_width, sample_temperature, sample_seed, sample_block, sample_block_scale)
     checker = check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit,
                           radial_lateral, radial_lateral_aniso, radial_resolution, lateral_resolution, lateral_resolution_stride, lateral_checkerboard)
     c = io.load(directory)
@@ -1984,7 +2126,7 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
             rms = out["history"][-1]["rms"]
             log(" depth sample: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
             out.update(run_sample(eng, c, plan, out["vels"], obs, wt, smooth, rms if sigma is None else sigma, sampling, out_dir, sample_step, sample_spread,
-                                  sample_width, sample_seed, sample_temperature, log))
+                                  sample_width, sample_seed, sample_temperature, log, sample_block, sample_block_scale, damp))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inDepth.dat")
@@ -2024,6 +2166,8 @@ def parser():
     ap.add_argument("--sample-width", type=float, default=DEFAULT_SAMPLE_WIDTH, metavar="W", help="with --sample: half width of the prior box about the step's result in km/s (default %g)" % DEFAULT_SAMPLE_WIDTH)
     ap.add_argument("--sample-seed", type=int, default=DEFAULT_SAMPLE_SEED, metavar="N", help="with --sample: seed of the counter-based generator (default %d)" % DEFAULT_SAMPLE_SEED)
     ap.add_argument("--sample-temperature", type=float, default=DEFAULT_SAMPLE_TEMPERATURE, metavar="T", help="with --sample: the chains sample exp(-(phi + psi) / 2T) (default %g)" % DEFAULT_SAMPLE_TEMPERATURE)
+    ap.add_argument("--sample-block", type=int, default=0, metavar="EVERY", help="with --sample: every EVERY-th sweep proposes all nodes of a column at once, along its linearised posterior (default 0: single nodes only)")
+    ap.add_argument("--sample-block-scale", type=float, default=None, metavar="S", help="with --sample-block: scale of the block proposal (default 2.38 sqrt(3 T / M) for M unknowns per column at temperature T)")
     return ap
 
 
@@ -2033,7 +2177,8 @@ def main(argv=None):
     try:
         check_flags(a.iterations, a.smooth, a.damp, a.dvmax, a.min_dws, a.sigma, a.aniso, a.radial, a.resolution, a.lateral, a.lateral_tol, a.lateral_maxit,
                     a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution, a.lateral_resolution, a.lateral_resolution_stride, a.lateral_checkerboard)
-        check_sample(a.sample, a.radial, a.lateral, a.sample_step, a.sample_spread, a.sample_width, a.sample_temperature, a.sample_seed)
+        check_sample(a.sample, a.radial, a.lateral, a.sample_step, a.sample_spread, a.sample_width, a.sample_temperature, a.sample_seed, a.sample_block,
+                     a.sample_block_scale)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
@@ -2041,7 +2186,7 @@ def main(argv=None):
         lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso,
         radial_resolution=a.radial_resolution, lateral_resolution=a.lateral_resolution, lateral_resolution_stride=a.lateral_resolution_stride,
         lateral_checkerboard=a.lateral_checkerboard, sample=a.sample, sample_step=a.sample_step, sample_spread=a.sample_spread, sample_width=a.sample_width,
-        sample_seed=a.sample_seed, sample_temperature=a.sample_temperature)
+        sample_seed=a.sample_seed, sample_temperature=a.sample_temperature, sample_block=a.sample_block, sample_block_scale=a.sample_block_scale)
     return 0
 
 

@@ -116,6 +116,9 @@ def declare_solvers(L):
     L.dsa_columns_sample_run.argtypes = [_vp, _i32]
     L.dsa_columns_sample_fetch.argtypes = [_vp] * 4
     L.dsa_columns_sample_state.argtypes = [_vp] * 15
+    L.dsa_columns_sample_shape.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 3
+    L.dsa_columns_sample_blocks.argtypes = [_vp, _i32, C.c_double]
+    L.dsa_columns_sample_block_state.argtypes = [_vp] * 3
     L.dsa_kernels_from_dispersion_radial.argtypes = [_vp]
     L.dsa_solve_rows_radial.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_iteration_system_radial_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 4 + [_vp] * 6
@@ -545,6 +548,34 @@ class Engine:
                    phisum=f64(Cn, ncol), nkept=i32(Cn, ncol), best_e=f64(Cn, ncol), best_v=f32(nz - 1, Cn, ncol), pnode=i32(Cn, ncol), pold=f32(Cn, ncol),
                    pmark=i32(Cn, ncol), reseeded=i32(Cn, ncol))
         self._check(self._L.dsa_columns_sample_state(self._h, *[_p(a) for a in out.values()]))
+        return out
+
+    # ---- block proposals of the sample stage ----
+    def columns_sample_shape(self, obs, wt, smooth, damp):
+        """dsa_columns_sample_shape on the state columns_resolution needs, which it leaves as it is: obs and wt as columns_step's.  The engine
+        keeps the shape for columns_sample_blocks.  Returns dict(tri (nz (nz - 1) / 2, ny * nx): the packed lower triangle of L, N's diagonal
+        on its diagonal; r (nz - 1, ny * nx) = 1 / sqrt(d), fp64; flag (ny * nx) int32).  ValueError as columns_step."""
+        nmaps, obs, wt = self._columns_in("columns_sample_shape", obs, wt)[:3]
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        out = dict(tri=np.zeros((nz * (nz - 1) // 2, ncol)), r=np.zeros((nz - 1, ncol)), flag=np.zeros(ncol, np.int32))
+        self._check(self._L.dsa_columns_sample_shape(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), _p(out["tri"]), _p(out["r"]), _p(out["flag"])))
+        return out
+
+    def columns_sample_blocks(self, block_every, block_scale):
+        """dsa_columns_sample_blocks, between columns_sample_begin and the first sweep: every block_every-th sweep proposes a block shaped by
+        the held shape, scaled by block_scale; 0 switches the block sweeps off"""
+        self._check(self._L.dsa_columns_sample_blocks(self._h, int(block_every), float(block_scale)))
+
+    def columns_sample_block_state(self):
+        """dsa_columns_sample_block_state: dict(pold_all (nz - 1, C, ncol) fp32, block_counters (3, C, ncol) int32: proposed, accepted, out of
+        the box)"""
+        nx, ny, nz = self._disp
+        Cn = self._sample[0]
+        if Cn < 1:                                                                  # (no stage was ever begun here: the library's refusal)
+            self._check(self._L.dsa_columns_sample_block_state(self._h, None, None))
+        out = dict(pold_all=np.zeros((nz - 1, Cn, nx * ny), np.float32), block_counters=np.zeros((3, Cn, nx * ny), np.int32))
+        self._check(self._L.dsa_columns_sample_block_state(self._h, _p(out["pold_all"]), _p(out["block_counters"])))
         return out
 
     def dispersion_begin_radial(self, vsv, vsh, depz, minthk, kmax_total, nmaps_total):

@@ -594,6 +594,28 @@ int dsa_columns_sample_fetch(dsa_engine* e, double* nodes, double* cols, int* co
 int dsa_columns_sample_state(dsa_engine* e, float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept,
                              double* best_e, float* best_v, int* pnode, float* pold, int* pmark, int* reseeded);
 
+/* Block proposals of the sample stage, shaped by each column's linearised posterior (extension; csrc/column_sample.h).
+ * dsa_columns_sample_shape: the state, nmaps, obs, wt, smooth, damp and the refusals are dsa_columns_resolution's, in its order: a
+ * single-model stage whose maps and kernel slots were all run with kernels.  Per interior column the normal matrix dsa_columns_step
+ * assembles, N = G^T G + smooth^2 L^T L + damp^2 I, is factored as L D L^T on the device; the model is not stepped and the stage is left as
+ * it is (a dsa_columns_step after the call gives the bits it would have given).  tri: (nz-1)*nz/2*nx*ny doubles, (entry, column), the packed
+ * lower triangle row by row -- entry i (i + 1) / 2 + j is L_ij for j < i and N_ii for j = i; r: (nz-1)*nx*ny doubles, r_l = 1 / sqrt(d_l);
+ * flag: nx*ny ints, dsa_columns_step's (2: no used datum, 1: a pivot not positive; tri and r are then 0, as on the outer ring).  Each of the
+ * three may be NULL.  The engine holds the shape, with nx, ny, nz, until the next call or dsa_destroy; no other call reads it.
+ * dsa_columns_sample_blocks, between dsa_columns_sample_begin and the first sweep: sweep s >= 1 is a block sweep iff block_every > 0 and
+ * s % block_every == 0.  In one, a chain of a column with shape flag 0 proposes v' = v + (float)(block_scale delta) on all nz-1 nodes, L^T
+ * delta = y, y_l = (2 u_l - 1) r_l, u_l draw 3 + l of the sweep -- a symmetric proposal of covariance block_scale^2 N^-1 / 3; outside the
+ * box of any node nothing is written; the Metropolis test is the single-node one and a rejection restores every node.  A chain of a flagged
+ * column makes the single-node proposal.  block_every = 0: off (the default of every dsa_columns_sample_begin).  DSA_ERR_STATE: no open
+ * sample stage, a sweep already run, no held shape of the stage's nx, ny, nz; DSA_ERR_ARGUMENT: block_every < 0, block_scale not finite or
+ * <= 0; the stage stays as it was.
+ * dsa_columns_sample_block_state: the raw block state for tests, each pointer may be NULL: pold_all (nz-1)*nchains*nx*ny floats (depth,
+ * chain, column), the values the last block proposal of a chain replaced; counters 3*nchains*nx*ny ints: block proposals made, accepted,
+ * out of the box (each also counted by dsa_columns_sample_state's counters).  Zeros while block sweeps are off. */
+int dsa_columns_sample_shape(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag);
+int dsa_columns_sample_blocks(dsa_engine* e, int block_every, double block_scale);
+int dsa_columns_sample_block_state(dsa_engine* e, float* pold_all, int* counters);
+
 /* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
  * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
  * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of

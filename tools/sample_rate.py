@@ -11,6 +11,11 @@ The share of the sweep in the new kernels themselves is a kernel trace's:
 prints per kernel the launches, the median and the sum of their durations, and the share of the sum of all kernels that k_sample_* take.
 
     python tools/sample_rate.py [sweeps] [chains]      (needs the GPU)
+
+Block mode: the same stage twice in one run -- single-node sweeps, then every sweep a block sweep
+(columns_sample_blocks(1, the default scale)) -- and the time of the columns_sample_shape call that precedes them (its dispersion runs with
+kernels are timed apart):
+    python tools/sample_rate.py block [sweeps] [chains]
 """
 import os
 import sys
@@ -40,9 +45,57 @@ def trace_shares(path):
     print("k_sample_*: %.1f us of %.1f us in all kernels, %.2f %%" % (new, total, 100.0 * new / total))
 
 
+def block_mode(sweeps, chains):
+    """the median sweep with block_every = 1 against single-node sweeps of the same build in the same run, and the shape call"""
+    c = io.load()
+    plan = depth.slot_plan(c)
+    vel = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
+    kmax, M = c["kmax"], c["nz"] - 1
+    e = Engine(0)
+    e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
+    t0 = time.perf_counter()
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, True, first, first)
+    t_kernels = 1e3 * (time.perf_counter() - t0)
+    obs = (e.dispersion_fetch(0, kmax) * 1.02).astype(np.float32)
+    sigma = 0.05
+    wt, lam = depth.sample_scaling(None, depth.DEFAULT_SMOOTH, sigma, obs.shape)
+    t_shape = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        shape = e.columns_sample_shape(obs, wt, lam, depth.DEFAULT_DAMP / sigma)
+        t_shape.append(1e3 * (time.perf_counter() - t0))
+    out = {}
+    for every in (0, 1):
+        e.columns_sample_begin(vel, c["depz"], c["minthk"], plan, obs, wt, chains, lam, depth.DEFAULT_SAMPLE_STEP, depth.DEFAULT_SAMPLE_SPREAD, depth.DEFAULT_SAMPLE_WIDTH,
+                               depth.DEFAULT_SAMPLE_TEMPERATURE, float(c["minvel"]), float(c["maxvel"]), depth.DEFAULT_SAMPLE_SEED, 0)
+        if every:
+            e.columns_sample_blocks(every, depth.sample_block_scale(M, depth.DEFAULT_SAMPLE_TEMPERATURE))
+        e.columns_sample_run(1)
+        wall, dev = [], []
+        for s in range(sweeps):
+            ms0 = e.stats()["ms_dispersion"]
+            t0 = time.perf_counter()
+            e.columns_sample_run(1)
+            wall.append(1e3 * (time.perf_counter() - t0)); dev.append(e.stats()["ms_dispersion"] - ms0)
+        res = e.columns_sample_fetch()
+        out[every] = (float(np.median(wall)), float(np.median(dev)), 100.0 * float(res["accepted"].sum()) / float(res["accepted"].sum() + res["rejected"].sum()))
+    e.close()
+    print("%d x %d x %d, K = %d, %d chains: the plan's runs with kernels %.1f ms; columns_sample_shape %.3f ms (the first call), %.3f ms (the median of 3), %d columns flagged" %
+          (c["nx"], c["ny"], c["nz"], kmax, chains, t_kernels, t_shape[0], float(np.median(t_shape)), int((shape["flag"] == 1).sum())))
+    for every, name in ((0, "single-node sweeps"), (1, "block sweeps (block_every = 1)")):
+        w, d, acc = out[every]
+        print("%s: median of %d -- %.3f ms wall, %.3f ms in the dispersion run on the device, %.3f ms the rest; %.1f %% of the proposals accepted" %
+              (name, sweeps, w, d, w - d, acc))
+    print("a block sweep costs %.3f ms more than a single-node sweep (%.2f %%)" % (out[1][0] - out[0][0], 100.0 * (out[1][0] - out[0][0]) / out[0][0]))
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "trace-shares":
         trace_shares(sys.argv[2])
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "block":
+        block_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 30, int(sys.argv[3]) if len(sys.argv) > 3 else 64)
         return
     sweeps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     chains = int(sys.argv[2]) if len(sys.argv) > 2 else 64
