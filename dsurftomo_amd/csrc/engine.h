@@ -415,9 +415,11 @@ struct Engine {
     OwnedBuf<float> G_rw;
     OwnedBuf<int> G_row, G_col;        // 1-based datum (row) and model parameter (column)
     long long G_nar = 0;
-    // what the G_nar resident entries are: set by the launch that writes them, cleared wherever G_nar is reset.  The isotropic builder
-    // (dsa_iteration_system_device) refuses azimuthal rows, the joint one (dsa_iteration_system_azimuthal_device) takes nothing else and
-    // leaves kRowsJoint (its system, Laplacian rows included: not rows to build from again).
+    // what the G_nar resident entries are: set by the launch that writes them, cleared wherever G_nar is reset.  The four entries of
+    // iteration.hip check it, each taking its own kind of rows only, and its one builder (build_resident_system) commits G_nar and the kind
+    // an entry names.  dsa_iteration_system_device takes isotropic rows (or none) and leaves the kind as it is;
+    // dsa_iteration_system_azimuthal_device takes kRowsAzimuthal and leaves kRowsJoint (its system, Laplacian rows included: not rows to
+    // build from again).
     // kRowsMaps: map rows (dsa_solve_rows_maps) of G_map_blocks blocks on G_map_nmaps maps of an nx x ny vertex grid; only
     // dsa_iteration_system_maps_device takes them, and leaves kRowsMapSystem
     // kRowsRadial: radial rows (dsa_solve_rows_radial) of a Vsv and a Vsh block; only dsa_iteration_system_radial_device

@@ -2163,6 +2163,25 @@ int Engine::trace_chunk(int first_unit, int n, float* rw, int* iw, int* col, lon
     return 0;
 }
 
+// solve() emitting another kind of rows, for solve_azimuthal / solve_maps / solve_radial after their refusals: the rows stay on the device
+// (device_rows) or go to the host arrays whatever the option rows_on_device says, trace_chunk sees the flags azi_now / maps_now / radial_now,
+// and the option and the flags are as they were found on every return.  An azimuthal solve starts from cleared sums (dsa_ray_azimuths).
+static int solve_in_row_mode(Engine& e, bool device_rows, bool azimuthal, bool maps, bool radial, float* dsurf, float* rw, int* iw, int* col, long long cap,
+                             long long* nar)
+{
+    if (azimuthal) {
+        e.h_azi_sums.assign(2 * e.h_trace.size(), 0.0f);
+        e.h_azi_steps.assign(e.h_trace.size(), 0);
+    }
+    const bool option = e.rows_on_device;
+    e.rows_on_device = device_rows;
+    e.azi_now = azimuthal; e.maps_now = maps; e.radial_now = radial;
+    const int rc = e.solve(dsurf, rw, iw, col, cap, nar);
+    e.rows_on_device = option;
+    e.azi_now = e.maps_now = e.radial_now = false;
+    return rc;
+}
+
 // dsa_solve_rows_azimuthal: solve() with three slabs per ray and the gc / gs blocks behind every ray's isotropic entries (ray_kernels.hip:
 // k_rays<., true>, k_row_emit_azi).  The depth factor Sazi is built here, the first time it is needed for the current depth kernels.
 int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long long cap, long long* nar, bool device_rows)
@@ -2188,14 +2207,8 @@ int Engine::solve_azimuthal(float* dsurf, float* rw, int* iw, int* col, long lon
     if (ensure(azi_slot_on, on.size())) return status;
     HIP_TRY(this, hipMemcpyAsync(azi_slot_on.p, on.data(), on.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
-    h_azi_sums.assign(2 * h_trace.size(), 0.0f);
-    h_azi_steps.assign(h_trace.size(), 0);
-    azi_now = true;
-    const bool option = rows_on_device;       // (the device entry runs solve() as under the option and leaves the option as it found it)
-    if (device_rows) rows_on_device = true;
-    const int rc = solve(dsurf, rw, iw, col, cap, nar);
-    rows_on_device = option;
-    azi_now = false;
+    // (the host entry has refused a set option above: device_rows is what the option becomes for this solve in both entries)
+    const int rc = solve_in_row_mode(*this, device_rows, true, false, false, dsurf, rw, iw, col, cap, nar);
     have_azi = rc == 0;
     return rc;
 }
@@ -2214,16 +2227,7 @@ int Engine::solve_maps(int azimuthal, float* dsurf, float* rw, int* iw, int* col
     if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_maps: one engine only"); return DSA_ERR_STATE; }
     const long long ncols = (long long)(azimuthal ? 3 : 1) * nmaps * g.nvx * g.nvz;
     if (ncols > 0x7fffffffLL) { fail(DSA_ERR_ARGUMENT, "solve_rows_maps: %lld columns do not fit an int", ncols); return DSA_ERR_ARGUMENT; }
-    if (azimuthal) {
-        h_azi_sums.assign(2 * h_trace.size(), 0.0f);
-        h_azi_steps.assign(h_trace.size(), 0);
-    }
-    const bool option = rows_on_device;       // (as solve_azimuthal: the option is left as it was found)
-    rows_on_device = given == 0;
-    maps_now = true; azi_now = azimuthal != 0;
-    const int rc = solve(dsurf, rw, iw, col, cap, nar);
-    rows_on_device = option;
-    maps_now = false; azi_now = false;
+    const int rc = solve_in_row_mode(*this, given == 0, azimuthal != 0, true, false, dsurf, rw, iw, col, cap, nar);
     have_azi = azimuthal && rc == 0;
     return rc;
 }
@@ -2268,13 +2272,7 @@ int Engine::solve_radial(float* dsurf, float* rw, int* iw, int* col, long long c
     if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_radial: one engine only"); return DSA_ERR_STATE; }
     const long long maxvp = (long long)g.nvx * g.nvz * (sens_nz - 1);
     if (2 * maxvp > 0x7fffffffLL) { fail(DSA_ERR_ARGUMENT, "solve_rows_radial: %lld columns do not fit an int", 2 * maxvp); return DSA_ERR_ARGUMENT; }
-    const bool option = rows_on_device;       // (as solve_maps: the option is left as it was found)
-    rows_on_device = given == 0;
-    radial_now = true;
-    const int rc = solve(dsurf, rw, iw, col, cap, nar);
-    rows_on_device = option;
-    radial_now = false;
-    return rc;
+    return solve_in_row_mode(*this, given == 0, false, false, true, dsurf, rw, iw, col, cap, nar);
 }
 
 // dsa_update_radial: the step dv (2 maxvp values, the Vsv block then the Vsh block of a solution) applied to the two

@@ -1,7 +1,9 @@
 // Host side of one outer iteration around the device calls: what the reference's main program
 // does between CalSurfG and LSMR (main.f90:361-466) and after LSMR (main.f90:520-535).  Plain host code with the
 // reference's fp32 arithmetic, so that an iteration driven through this library (dsurftomo_amd/invert.py) produces the
-// reference's numbers; O(nar) work, no device involved.  The two *_device builders do the same step where the rows are.
+// reference's numbers; O(nar) work, no device involved.  The four *_device entries do the same step where the rows are: each checks its
+// arguments and the kind of the resident rows, makes the right-hand side, and describes its system to the one builder
+// (build_resident_system), which does everything that touches the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +16,11 @@
 #include "map_system.h"
 #include "radial_system.h"
 #include "spmv_state.h"
+
+namespace dsa {
+int spmv_load_from_device(Engine* e, int m, int n, long long nar, const float* d_rw, const int* d_row, const int* d_col, long long nar_data);
+void spmv_abs_column_sums(Engine* e, float* d_out);
+}
 
 namespace {
 
@@ -39,6 +46,30 @@ int residual_weights(int dall, const float* obst, const float* dsyn, float thres
         if (out) cbst[i] = 0.0f;
     }
     return 0;
+}
+
+// The right-hand side of the three block systems (joint, maps, radial): residual_weights, then the host route's product
+// fl(residual * weight) -- under a zero weight a zero with the residual's sign, where residual_weights alone leaves +0 -- and `zeros`
+// zero elements below the dall data rows.
+int block_rhs(int dall, const float* obst, const float* dsyn, float threshold0, long long zeros, float* cbst, float* datweight)
+{
+    const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight);
+    if (rc != 0) return rc;
+    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
+    for (long long i = 0; i < zeros; ++i) cbst[dall + i] = 0.0f;
+    return 0;
+}
+
+// DWS block by block (main.f90:386-392): dws[2 B], dws[2 B + 1] = {max, mean} of block B's per_block elements of norm; the sum is
+// sequential in fp32
+void block_max_mean(const float* norm, int nblocks, long long per_block, float* dws)
+{
+    for (int B = 0; B < nblocks; ++B) {
+        const float* nb = norm + (size_t)B * (size_t)per_block;
+        float total = 0.0f, top = 0.0f;
+        for (long long i = 0; i < per_block; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
+        dws[2 * B] = top; dws[2 * B + 1] = total / (float)per_block;
+    }
 }
 
 long long regularisation_entries(int nvx, int nvz, int nl)
@@ -155,12 +186,59 @@ __global__ __launch_bounds__(256) void k_radial_system(int nvx, int nvz, int nl,
     }
 }
 
-}  // namespace
+// What an entry asks build_resident_system to build on the nar_in resident entries, after its own checks
+struct ResidentSystem {
+    const char* who;                   // the entry's name in messages
+    int dall;                          // data rows
+    long long n, below;                // columns; rows below the data rows: m = dall + below
+    long long nar_in, appended;        // resident entries; entries of the rows below, written behind them
+    int nblocks;                       // dws: {max, mean} of norm over nblocks blocks ...
+    long long per_block;               // ... of per_block unknowns
+    dsa::Engine::RowsKind kind;        // what the entries are afterwards (the isotropic entry: what it found)
+    bool commit_before_load;           // G_nar / G_kind are set before the load (a later failure leaves a system) or after the column sums
+    bool radial;                       // the loaded matrix is a radial system (spmv_state.h)
+};
 
-namespace dsa {
-int spmv_load_from_device(Engine* e, int m, int n, long long nar, const float* d_rw, const int* d_row, const int* d_col, long long nar_data);
-void spmv_abs_column_sums(Engine* e, float* d_out);
+#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "%s: %s failed", s.who, #call); return DSA_ERR_DEVICE; } } while (0)
+
+// Everything the four device entries do on the device: the data rows scaled by the 0/1 weights (rw[k] *= datweight[row[k] - 1], one fp32
+// multiply per entry), the rows below them written at entry nar_in by append(nar_in) -- a copy of host-built rows or one kernel launch, which
+// returns its hipError_t --, both orderings of the matrix built where the entries are (spmv_load_from_device, nar_data = nar_in), norm[n] =
+// per column the sum of |entry| over the DATA entries, which lead every column in storage order (main.f90:378-392), and dws from it.
+template <class Append>
+int build_resident_system(dsa::Engine* e, const ResidentSystem& s, const float* datweight, float* norm, int* m_out, long long* nar_out, float* dws,
+                          Append append)
+{
+    IT_TRY(hipSetDevice(e->device));
+    const long long nar = s.nar_in + s.appended;
+    const size_t used = (size_t)s.nar_in;
+    dsa::OwnedBuf<float> d_w, d_norm;
+    if (e->ensure(d_w, (size_t)s.dall) || e->ensure(d_norm, (size_t)s.n) ||
+        e->ensure_keep(e->G_rw, (size_t)nar, used) || e->ensure_keep(e->G_row, (size_t)nar, used) || e->ensure_keep(e->G_col, (size_t)nar, used)) return e->status;
+    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)s.dall * 4, hipMemcpyHostToDevice, e->stream));
+    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)s.n * 4, e->stream));
+    if (s.nar_in > 0)
+        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((s.nar_in + 255) / 256)), dim3(256), 0, e->stream, s.nar_in, e->G_rw.p, e->G_row.p, d_w.p);
+    IT_TRY(append(s.nar_in));
+    IT_TRY(hipStreamSynchronize(e->stream));
+    const int m = s.dall + (int)s.below;
+    if (s.commit_before_load) { e->G_nar = nar; e->G_kind = s.kind; }
+    { const int rc = dsa::spmv_load_from_device(e, m, (int)s.n, nar, e->G_rw.p, e->G_row.p, e->G_col.p, s.nar_in); if (rc != 0) return rc; }
+    if (s.radial) e->spmv->radial = true;
+    dsa::spmv_abs_column_sums(e, d_norm.p);
+    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)s.n * 4, hipMemcpyDeviceToHost, e->stream));
+    IT_TRY(hipStreamSynchronize(e->stream));
+    IT_TRY(hipGetLastError());
+    block_max_mean(norm, s.nblocks, s.per_block, dws);
+    if (!s.commit_before_load) { e->G_nar = nar; e->G_kind = s.kind; }
+    *m_out = m;
+    *nar_out = nar;
+    return 0;
 }
+
+#undef IT_TRY
+
+}  // namespace
 
 extern "C" {
 
@@ -181,9 +259,7 @@ int dsa_iteration_system(int nx, int ny, int nz, int dall, long long nar_in, lon
         rw[k] = rw[k] * datweight[iw[1 + k] - 1];
         norm[col[k] - 1] = norm[col[k] - 1] + std::fabs(rw[k]);
     }
-    float total = 0.0f, top = 0.0f;                                                            // :386-392
-    for (long long i = 0; i < maxvp; ++i) { total = total + norm[i]; if (norm[i] > top) top = norm[i]; }
-    dws[0] = top; dws[1] = total / (float)maxvp;
+    block_max_mean(norm, 1, maxvp, dws);                                                       // :386-392
 
     // regularisation rows, one per model parameter in (k, j, i) order (:420-457)
     const long long nar_out_ = nar_in + regularisation_entries(nvx, nvz, nl);
@@ -219,46 +295,24 @@ int dsa_iteration_system_device(dsa_engine* h, int nx, int ny, int nz, int dall,
     const long long maxvp = (long long)nvx * nvz * nl, nar_in = e->G_nar;
     { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_device: too few data"); return rc; } }
     for (long long i = 0; i < maxvp; ++i) cbst[dall + i] = 0.0f;
-    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_device: hipSetDevice"); return DSA_ERR_DEVICE; }
-    const long long nreg = regularisation_entries(nvx, nvz, nl), nar = nar_in + nreg;
-    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    const long long nreg = regularisation_entries(nvx, nvz, nl);
+    if (nar_in + nreg > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
     std::vector<float> hrw((size_t)nreg);
     std::vector<int> hrow((size_t)nreg), hcol((size_t)nreg);
     regularisation_rows(nvx, nvz, nl, weight0, dall, hrw.data(), hrow.data(), hcol.data());
-    dsa::DevBuf<float> d_w, d_norm;
-    auto rel = [](auto& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; };
-    auto done = [&](int rc) { rel(d_w); rel(d_norm); return rc; };
-#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
-    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)maxvp) ||
-        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
-    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)maxvp * 4, e->stream));
-    if (nar_in > 0)
-        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
-    IT_TRY(hipMemcpyAsync(e->G_rw.p + nar_in, hrw.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemcpyAsync(e->G_row.p + nar_in, hrow.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemcpyAsync(e->G_col.p + nar_in, hcol.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipStreamSynchronize(e->stream));
-    const int m = dall + (int)maxvp;
-    { const int rc = dsa::spmv_load_from_device(e, m, (int)maxvp, nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
-    // DWS (main.f90:378-392): per column the sum of |entry| over the DATA entries, which lead every column in storage order
-    dsa::spmv_abs_column_sums(e, d_norm.p);
-    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)maxvp * 4, hipMemcpyDeviceToHost, e->stream));
-    IT_TRY(hipStreamSynchronize(e->stream));
-    IT_TRY(hipGetLastError());
-#undef IT_TRY
-    float total = 0.0f, top = 0.0f;                                                            // :386-392
-    for (long long i = 0; i < maxvp; ++i) { total = total + norm[i]; if (norm[i] > top) top = norm[i]; }
-    dws[0] = top; dws[1] = total / (float)maxvp;
-    e->G_nar = nar;
-    *m_out = m;
-    *nar_out = nar;
-    return done(0);
+    // (the kind of the entries stays what it was found to be: isotropic rows, or none where no ray left an entry)
+    const ResidentSystem s = { "iteration_system_device", dall, maxvp, maxvp, nar_in, nreg, 1, maxvp, e->G_kind, false, false };
+    return build_resident_system(e, s, datweight, norm, m_out, nar_out, dws, [&](long long first) {
+        hipError_t rc = hipMemcpyAsync(e->G_rw.p + first, hrw.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(e->G_row.p + first, hrow.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(e->G_col.p + first, hcol.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, e->stream);
+        return rc;
+    });
 }
 
 // The joint Vs | gc | gs system of the azimuthal step built where dsa_solve_rows_azimuthal_device, or
-// dsa_calsurfg_azimuthal called with null rw / iw / col, left its rows: the data rows scaled by the 0/1 weights (residual_weights,
-// k_scale_rows: dsa_iteration_system_device's), and below the dall data rows the Laplacian rows of the three blocks, written by
+// dsa_calsurfg_azimuthal called with null rw / iw / col, left its rows: the data rows scaled by the 0/1 weights (block_rhs,
+// build_resident_system), and below the dall data rows the Laplacian rows of the three blocks, written by
 // k_laplacian_blocks -- block B's rows dall + B maxvp + index, columns B maxvp + ..., weight0 on Vs and weight_azi on gc and gs.
 // m = dall + 3 maxvp, n = 3 maxvp.  Same bits as analyses/azimuthal.py's azimuthal_weights + azimuthal_system + dsa_spmv_load on the
 // host rows of the same call; norm[3 maxvp] adds |entry| over a column's data entries in storage order, dws[2 B], dws[2 B + 1] are
@@ -283,46 +337,19 @@ int dsa_iteration_system_azimuthal_device(dsa_engine* h, int nx, int ny, int nz,
                 e->G_kind == dsa::Engine::kRowsJoint ? "the rows on the device are a joint system already" : "no azimuthal rows on the device");
         return DSA_ERR_STATE;
     }
-    const long long nar_in = e->G_nar, per_block = dsa::joint_block_entries(nvx, nvz, nl), nar = nar_in + 3 * per_block;
-    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_azimuthal_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
-    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_azimuthal_device: too few data"); return rc; } }
-    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
-    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
-    for (long long i = 0; i < 3 * maxvp; ++i) cbst[dall + i] = 0.0f;
-    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_azimuthal_device: hipSetDevice"); return DSA_ERR_DEVICE; }
-    dsa::DevBuf<float> d_w, d_norm;
-    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
-#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_azimuthal_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
-    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)(3 * maxvp)) ||
-        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
-    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)(3 * maxvp) * 4, e->stream));
-    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
-    hipLaunchKernelGGL(k_laplacian_blocks, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, nar_in, per_block, weight0,
-                       weight_azi, e->G_rw.p, e->G_row.p, e->G_col.p);
-    IT_TRY(hipGetLastError());
-    IT_TRY(hipStreamSynchronize(e->stream));
-    const int m = dall + (int)(3 * maxvp);
-    { const int rc = dsa::spmv_load_from_device(e, m, (int)(3 * maxvp), nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
-    dsa::spmv_abs_column_sums(e, d_norm.p);
-    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)(3 * maxvp) * 4, hipMemcpyDeviceToHost, e->stream));
-    IT_TRY(hipStreamSynchronize(e->stream));
-    IT_TRY(hipGetLastError());
-#undef IT_TRY
-    for (int B = 0; B < 3; ++B) {                                                              // :386-392, block by block
-        const float* nb = norm + (size_t)B * (size_t)maxvp;
-        float total = 0.0f, top = 0.0f;
-        for (long long i = 0; i < maxvp; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
-        dws[2 * B] = top; dws[2 * B + 1] = total / (float)maxvp;
-    }
-    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsJoint;
-    *m_out = m;
-    *nar_out = nar;
-    return done(0);
+    const long long nar_in = e->G_nar, per_block = dsa::joint_block_entries(nvx, nvz, nl);
+    if (nar_in + 3 * per_block > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_azimuthal_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = block_rhs(dall, obst, dsyn, threshold0, 3 * maxvp, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_azimuthal_device: too few data"); return rc; } }
+    const ResidentSystem s = { "iteration_system_azimuthal_device", dall, 3 * maxvp, 3 * maxvp, nar_in, 3 * per_block, 3, maxvp, dsa::Engine::kRowsJoint, false, false };
+    return build_resident_system(e, s, datweight, norm, m_out, nar_out, dws, [&](long long first) {
+        hipLaunchKernelGGL(k_laplacian_blocks, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, first, per_block, weight0,
+                           weight_azi, e->G_rw.p, e->G_row.p, e->G_col.p);
+        return hipGetLastError();
+    });
 }
 
 // The per-period map system built where dsa_solve_rows_maps left its rows on the device: the data rows scaled by the
-// 0/1 weights exactly as in dsa_iteration_system_azimuthal_device (residual_weights, k_scale_rows, the right-hand side fl(residual * weight)),
+// 0/1 weights and the right-hand side fl(residual * weight) (block_rhs, build_resident_system: the same code as for the joint system),
 // and below the dall data rows one 2-D Laplacian row per unknown (k_laplacian_maps: map_system.h), weight0 on the planes of block 0 and
 // weight_azi on those of blocks 1 and 2.  n = nblocks nmaps layer columns, m = dall + n rows.  norm[n] adds |entry| over a column's data
 // entries in storage order; dws[2 B], dws[2 B + 1] are block B's {max, mean} of it.  Every argument is checked before the device is touched.
@@ -349,48 +376,20 @@ int dsa_iteration_system_maps_device(dsa_engine* h, int nx, int ny, int nmaps, i
         e->fail(DSA_ERR_ARGUMENT, "iteration_system_maps_device: nx %d ny %d nmaps %d, the map rows on the device were made with %d %d %d", nx, ny, nmaps, e->G_map_nx, e->G_map_ny, e->G_map_nmaps);
         return DSA_ERR_ARGUMENT;
     }
-    const long long nar_in = e->G_nar, nreg = (long long)nblocks * nmaps * dsa::map_plane_entries(nvx, nvz), nar = nar_in + nreg;
-    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_maps_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
-    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_maps_device: too few data"); return rc; } }
-    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
-    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
-    for (long long i = 0; i < n; ++i) cbst[dall + i] = 0.0f;
-    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_maps_device: hipSetDevice"); return DSA_ERR_DEVICE; }
-    dsa::DevBuf<float> d_w, d_norm;
-    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
-#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_maps_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
-    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)n) ||
-        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
-    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)n * 4, e->stream));
-    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
-    hipLaunchKernelGGL(k_laplacian_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nmaps, n, dall, nar_in, weight0, weight_azi,
-                       e->G_rw.p, e->G_row.p, e->G_col.p);
-    IT_TRY(hipGetLastError());
-    IT_TRY(hipStreamSynchronize(e->stream));
-    const int m = dall + (int)n;
-    // (from here on the resident entries are a system, not rows to build from again -- also when a later step fails)
-    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsMapSystem;
-    { const int rc = dsa::spmv_load_from_device(e, m, (int)n, nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
-    dsa::spmv_abs_column_sums(e, d_norm.p);
-    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    IT_TRY(hipStreamSynchronize(e->stream));
-    IT_TRY(hipGetLastError());
-#undef IT_TRY
-    const long long per_block = (long long)nmaps * layer;
-    for (int B = 0; B < nblocks; ++B) {                                                        // main.f90:386-392, block by block
-        const float* nb = norm + (size_t)B * (size_t)per_block;
-        float total = 0.0f, top = 0.0f;
-        for (long long i = 0; i < per_block; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
-        dws[2 * B] = top; dws[2 * B + 1] = total / (float)per_block;
-    }
-    *m_out = m;
-    *nar_out = nar;
-    return done(0);
+    const long long nar_in = e->G_nar, nreg = (long long)nblocks * nmaps * dsa::map_plane_entries(nvx, nvz);
+    if (nar_in + nreg > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_maps_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = block_rhs(dall, obst, dsyn, threshold0, n, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_maps_device: too few data"); return rc; } }
+    // (once the rows below are written the resident entries are a system, not rows to build from again -- also when a later step fails)
+    const ResidentSystem s = { "iteration_system_maps_device", dall, n, n, nar_in, nreg, nblocks, nmaps * layer, dsa::Engine::kRowsMapSystem, true, false };
+    return build_resident_system(e, s, datweight, norm, m_out, nar_out, dws, [&](long long first) {
+        hipLaunchKernelGGL(k_laplacian_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nmaps, n, dall, first, weight0, weight_azi,
+                           e->G_rw.p, e->G_row.p, e->G_col.p);
+        return hipGetLastError();
+    });
 }
 
 // The radial Vsv | Vsh system of the direct inversion built where dsa_solve_rows_radial left its rows: the data rows
-// scaled exactly as in dsa_iteration_system_azimuthal_device (residual_weights, k_scale_rows, the right-hand side fl(residual * weight)), and
+// scaled and the right-hand side fl(residual * weight) made by the same code as for the joint system (block_rhs, build_resident_system), and
 // below the dall data rows what k_radial_system writes by radial_system.h -- the Laplacian rows of the Vsv block (weight0) and of the Vsh
 // block (weight_h), then maxvp tie rows {-aniso, +aniso} whose right-hand side is 0.0f - aniso * (vsh - vsv) at the unknown's node of the
 // resident models (their host copies, which every call that changes the models refreshes).  m = dall + 3 maxvp, n = 2 maxvp, the tie rows
@@ -423,49 +422,22 @@ int dsa_iteration_system_radial_device(dsa_engine* h, int nx, int ny, int nz, in
     }
     const size_t nn = (size_t)nx * ny * nz;
     if (e->h_vels.size() != nn || e->h_vsh.size() != nn) { e->fail(DSA_ERR_STATE, "iteration_system_radial_device: the radial stage's host copies of the models are missing"); return DSA_ERR_STATE; }
-    const long long nar_in = e->G_nar, nar = nar_in + dsa::radial_entries(nvx, nvz, nl);
-    if (nar > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_radial_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
-    { const int rc = residual_weights(dall, obst, dsyn, threshold0, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_radial_device: too few data"); return rc; } }
-    // the host route's right-hand side is the product fl(residual * weight): under a zero weight a zero with the residual's sign
-    for (int i = 0; i < dall; ++i) cbst[i] = (obst[i] - dsyn[i]) * datweight[i];
-    for (long long i = 0; i < 2 * maxvp; ++i) cbst[dall + i] = 0.0f;
+    const long long nar_in = e->G_nar, nreg = dsa::radial_entries(nvx, nvz, nl);
+    if (nar_in + nreg > 0x7fffffffll) { e->fail(DSA_ERR_CAPACITY, "iteration_system_radial_device: more than 2^31-1 matrix entries"); return DSA_ERR_CAPACITY; }
+    { const int rc = block_rhs(dall, obst, dsyn, threshold0, 2 * maxvp, cbst, datweight); if (rc != 0) { e->fail(rc, "iteration_system_radial_device: too few data"); return rc; } }
     for (long long i = 0; i < maxvp; ++i) {
         const size_t node = (size_t)dsa::radial_node(nvx, nvz, i);
         const float d = e->h_vsh[node] - e->h_vels[node];
         cbst[dall + 2 * maxvp + i] = 0.0f - aniso * d;
     }
-    if (hipSetDevice(e->device) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_radial_device: hipSetDevice"); return DSA_ERR_DEVICE; }
-    dsa::DevBuf<float> d_w, d_norm;
-    auto done = [&](int rc) { d_w.release(); d_norm.release(); return rc; };
-#define IT_TRY(call) do { if ((call) != hipSuccess) { e->fail(DSA_ERR_DEVICE, "iteration_system_radial_device: %s failed", #call); return done(DSA_ERR_DEVICE); } } while (0)
-    if (e->ensure(d_w, (size_t)dall) || e->ensure(d_norm, (size_t)(2 * maxvp)) ||
-        e->ensure_keep(e->G_rw, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_row, (size_t)nar, (size_t)nar_in) || e->ensure_keep(e->G_col, (size_t)nar, (size_t)nar_in)) return done(e->status);
-    IT_TRY(hipMemcpyAsync(d_w.p, datweight, (size_t)dall * 4, hipMemcpyHostToDevice, e->stream));
-    IT_TRY(hipMemsetAsync(d_norm.p, 0, (size_t)(2 * maxvp) * 4, e->stream));
-    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((nar_in + 255) / 256)), dim3(256), 0, e->stream, nar_in, e->G_rw.p, e->G_row.p, d_w.p);
-    hipLaunchKernelGGL(k_radial_system, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, nar_in, weight0, weight_h, aniso,
-                       e->G_rw.p, e->G_row.p, e->G_col.p);
-    IT_TRY(hipGetLastError());
-    IT_TRY(hipStreamSynchronize(e->stream));
-    const int m = (int)dsa::radial_rows(nvx, nvz, nl, dall), n = (int)dsa::radial_columns(nvx, nvz, nl);
-    // (from here on the resident entries are a system, not rows to build from again -- also when a later step fails)
-    e->G_nar = nar; e->G_kind = dsa::Engine::kRowsRadialSystem;
-    { const int rc = dsa::spmv_load_from_device(e, m, n, nar, e->G_rw.p, e->G_row.p, e->G_col.p, nar_in); if (rc != 0) return done(rc); }
-    e->spmv->radial = true;
-    dsa::spmv_abs_column_sums(e, d_norm.p);
-    IT_TRY(hipMemcpyAsync(norm, d_norm.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    IT_TRY(hipStreamSynchronize(e->stream));
-    IT_TRY(hipGetLastError());
-#undef IT_TRY
-    for (int B = 0; B < 2; ++B) {                                                              // main.f90:386-392, block by block
-        const float* nb = norm + (size_t)B * (size_t)maxvp;
-        float total = 0.0f, top = 0.0f;
-        for (long long i = 0; i < maxvp; ++i) { total = total + nb[i]; if (nb[i] > top) top = nb[i]; }
-        dws[2 * B] = top; dws[2 * B + 1] = total / (float)maxvp;
-    }
-    *m_out = m;
-    *nar_out = nar;
-    return done(0);
+    // (once the rows below are written the resident entries are a system, not rows to build from again -- also when a later step fails)
+    const ResidentSystem s = { "iteration_system_radial_device", dall, dsa::radial_columns(nvx, nvz, nl), dsa::radial_rows(nvx, nvz, nl, dall) - dall, nar_in, nreg,
+                               2, maxvp, dsa::Engine::kRowsRadialSystem, true, true };
+    return build_resident_system(e, s, datweight, norm, m_out, nar_out, dws, [&](long long first) {
+        hipLaunchKernelGGL(k_radial_system, dim3((unsigned)((3 * maxvp + 255) / 256)), dim3(256), 0, e->stream, nvx, nvz, nl, dall, first, weight0, weight_h, aniso,
+                           e->G_rw.p, e->G_row.p, e->G_col.p);
+        return hipGetLastError();
+    });
 }
 
 // main.f90:520-535: the update is clipped to +-0.5 km/s, the model to [minvel, maxvel]; vsf(nx, ny, nz) column-major

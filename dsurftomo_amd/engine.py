@@ -246,91 +246,72 @@ class Engine:
         nz, kmax = sen[0].shape[0], sen[0].shape[1]
         self._check(self._L.dsa_set_depth_kernels(self._h, nz, kmax, _p(vels), _p(depz), *[_p(a) for a in sen]))
 
-    def solve_rows(self, capacity):
-        """receiver times plus Frechet rows as COO (rw, row, col), rows / columns 1-based"""
+    def _solve_rows(self, fn, lead, capacity, host=True, null_if_empty=False):
+        """one of the dsa_solve_rows* entries (fn, its arguments `lead` between the handle and the times).  host: the rows come to three
+        arrays of `capacity` entries, returns (times, rw, row, col) cut to the entries written; else the three arrays are NULL (the rows stay
+        on the device), returns (times, number of entries).  null_if_empty: arrays of capacity 0 are passed as NULL"""
         out = np.zeros(self._ndata, np.float32)
-        rw = np.zeros(capacity, np.float32)
-        iw = np.zeros(capacity, np.int32)
-        col = np.zeros(capacity, np.int32)
         nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows(self._h, _p(out), _p(rw), _p(iw), _p(col), capacity, C.byref(nar)))
+        if not host:
+            self._check(fn(self._h, *lead, _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
+            return out, nar.value
+        rw, iw, col = np.zeros(capacity, np.float32), np.zeros(capacity, np.int32), np.zeros(capacity, np.int32)
+        ptr = _p if null_if_empty else (lambda a: a.ctypes.data_as(_vp))
+        self._check(fn(self._h, *lead, _p(out), ptr(rw), ptr(iw), ptr(col), C.c_longlong(capacity), C.byref(nar)))
         n = nar.value
         return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
 
+    def solve_rows(self, capacity):
+        """receiver times plus Frechet rows as COO (rw, row, col), rows / columns 1-based"""
+        return self._solve_rows(self._L.dsa_solve_rows, (), capacity, null_if_empty=True)
+
     def solve_rows_device(self):
         """receiver times; the Frechet rows stay on the device (set_option('rows_on_device', 1) before it): returns (times, number of entries)"""
-        out = np.zeros(self._ndata, np.float32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows(self._h, _p(out), None, None, None, C.c_longlong(1 << 62), C.byref(nar)))
-        return out, nar.value
+        return self._solve_rows(self._L.dsa_solve_rows, (), 1 << 62, host=False)
 
     def solve_rows_azimuthal(self, capacity):
         """solve_rows with the gc and gs blocks behind every ray's isotropic entries (dsa_solve_rows_azimuthal): columns
         B * maxvp + isotropic column, B = 1 (gc), 2 (gs)"""
-        out = np.zeros(self._ndata, np.float32)
-        rw = np.zeros(capacity, np.float32)
-        iw = np.zeros(capacity, np.int32)
-        col = np.zeros(capacity, np.int32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows_azimuthal(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
-                                                     capacity, C.byref(nar)))
-        n = nar.value
-        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+        return self._solve_rows(self._L.dsa_solve_rows_azimuthal, (), capacity)
 
     def solve_rows_azimuthal_device(self, capacity, host_copy=True):
         """solve_rows_azimuthal with the rows left on the device (dsa_solve_rows_azimuthal_device), whatever the option rows_on_device says.
         host_copy: returns (times, rw, row, col), the copy bit for bit solve_rows_azimuthal's; else (times, number of entries) and no row
         leaves the device"""
-        out = np.zeros(self._ndata, np.float32)
-        nar = C.c_longlong(0)
-        if not host_copy:
-            self._check(self._L.dsa_solve_rows_azimuthal_device(self._h, _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
-            return out, nar.value
-        rw = np.zeros(capacity, np.float32)
-        iw = np.zeros(capacity, np.int32)
-        col = np.zeros(capacity, np.int32)
-        self._check(self._L.dsa_solve_rows_azimuthal_device(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
-                                                            C.c_longlong(capacity), C.byref(nar)))
-        n = nar.value
-        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+        return self._solve_rows(self._L.dsa_solve_rows_azimuthal_device, (), capacity, host=host_copy)
 
     # ---- per-period 2-D maps (DESIGN.md section 20) -------------------------------------------------
     def solve_rows_maps(self, capacity, azimuthal=False):
         """receiver times plus the map rows as COO (rw, row, col), 1-based: columns (B * nmaps + map) * layer + vertex + 1, B = 0 (c0) and, with
         azimuthal, 1 (A1, cos 2psi) and 2 (A2, sin 2psi) (dsa_solve_rows_maps); no depth kernels needed"""
-        out = np.zeros(self._ndata, np.float32)
-        rw = np.zeros(capacity, np.float32)
-        iw = np.zeros(capacity, np.int32)
-        col = np.zeros(capacity, np.int32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows_maps(self._h, int(bool(azimuthal)), _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
-                                                C.c_longlong(capacity), C.byref(nar)))
-        n = nar.value
-        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+        return self._solve_rows(self._L.dsa_solve_rows_maps, (int(bool(azimuthal)),), capacity)
 
     def solve_rows_maps_device(self, azimuthal=False, capacity=1 << 62):
         """solve_rows_maps with the rows left on the device for iteration_system_maps_device: returns (times, number of entries)"""
-        out = np.zeros(self._ndata, np.float32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows_maps(self._h, int(bool(azimuthal)), _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
-        return out, nar.value
+        return self._solve_rows(self._L.dsa_solve_rows_maps, (int(bool(azimuthal)),), capacity, host=False)
 
-    def iteration_system_maps_device(self, nx, ny, nmaps, nblocks, obst, dsyn, threshold0, weight0, weight_azi=None):
-        """dsa_iteration_system_maps_device on the map rows left on the device.  Returns dict(m, n, nar, cbst (m,), datweight (dall,), norm (n,),
-        dws (nblocks, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
+    def _iteration_system_device(self, fn, lead, obst, dsyn, floats, n, rows_below, nblocks):
+        """one of the dsa_iteration_system_*_device entries (fn, its leading integers `lead`, its floats from threshold0 on) on the rows left on
+        the device, for a system of n columns, rows_below rows below the data rows and nblocks blocks of unknowns.  Returns dict(m, n, nar,
+        cbst (dall + rows_below,), datweight (dall,), norm (n,), dws (nblocks, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
         f = np.float32
         obst = np.ascontiguousarray(obst, f); dsyn = np.ascontiguousarray(dsyn, f)
         dall = obst.size
         if dsyn.size != dall:
             raise ValueError("obst and dsyn differ in length")
-        n = max(int(nblocks), 0) * max(int(nmaps), 0) * max(nx - 2, 0) * max(ny - 2, 0)
-        cbst = np.zeros(dall + n, f); datweight = np.zeros(dall, f); norm = np.zeros(max(n, 1), f); dws = np.zeros(2 * max(int(nblocks), 1), f)
+        cbst = np.zeros(dall + rows_below, f); datweight = np.zeros(dall, f); norm = np.zeros(max(n, 1), f); dws = np.zeros(2 * nblocks, f)
         m, nar = C.c_int(0), C.c_longlong(0)
-        self._check(self._L.dsa_iteration_system_maps_device(self._h, int(nx), int(ny), int(nmaps), int(nblocks), dall, _p(obst), _p(dsyn), float(threshold0),
-                                                             float(weight0), float(weight0 if weight_azi is None else weight_azi), cbst.ctypes.data_as(_vp),
-                                                             datweight.ctypes.data_as(_vp), norm.ctypes.data_as(_vp), C.byref(m), C.byref(nar), dws.ctypes.data_as(_vp)))
+        self._check(fn(self._h, *[int(v) for v in lead], dall, _p(obst), _p(dsyn), *[float(v) for v in floats], cbst.ctypes.data_as(_vp),
+                       datweight.ctypes.data_as(_vp), norm.ctypes.data_as(_vp), C.byref(m), C.byref(nar), dws.ctypes.data_as(_vp)))
         self._mn = (m.value, n)
-        return dict(m=m.value, n=n, nar=nar.value, cbst=cbst, datweight=datweight, norm=norm[:n], dws=dws.reshape(-1, 2))
+        return dict(m=m.value, n=n, nar=nar.value, cbst=cbst, datweight=datweight, norm=norm[:n], dws=dws.reshape(nblocks, 2))
+
+    def iteration_system_maps_device(self, nx, ny, nmaps, nblocks, obst, dsyn, threshold0, weight0, weight_azi=None):
+        """dsa_iteration_system_maps_device on the map rows left on the device.  Returns dict(m, n, nar, cbst (m,), datweight (dall,), norm (n,),
+        dws (nblocks, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
+        n = max(int(nblocks), 0) * max(int(nmaps), 0) * max(nx - 2, 0) * max(ny - 2, 0)
+        return self._iteration_system_device(self._L.dsa_iteration_system_maps_device, (nx, ny, nmaps, nblocks), obst, dsyn,
+                                             (threshold0, weight0, weight0 if weight_azi is None else weight_azi), n, n, max(int(nblocks), 1))
 
     def update_maps(self, dv, dvmax, minvel, maxvel, nmaps, nx, ny):
         """dsa_update_maps: dv, nmaps * (nx - 2) * (ny - 2) values (the c0 block of a solution; any shape), applied to the resident vertex maps of
@@ -688,40 +669,18 @@ class Engine:
     def solve_rows_radial(self, capacity):
         """solve_rows with the columns of the units on Love slots moved into the Vsh block (dsa_solve_rows_radial): column
         B * maxvp + isotropic column, B = 0 (Vsv, Rayleigh), 1 (Vsh, Love); returns (times, rw, row, col)"""
-        out = np.zeros(self._ndata, np.float32)
-        rw = np.zeros(capacity, np.float32)
-        iw = np.zeros(capacity, np.int32)
-        col = np.zeros(capacity, np.int32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows_radial(self._h, _p(out), rw.ctypes.data_as(_vp), iw.ctypes.data_as(_vp), col.ctypes.data_as(_vp),
-                                                  C.c_longlong(capacity), C.byref(nar)))
-        n = nar.value
-        return out, rw[:n].copy(), iw[:n].copy(), col[:n].copy()
+        return self._solve_rows(self._L.dsa_solve_rows_radial, (), capacity)
 
     def solve_rows_radial_device(self, capacity=1 << 62):
         """solve_rows_radial with the rows left on the device for iteration_system_radial_device: returns (times, number of entries)"""
-        out = np.zeros(self._ndata, np.float32)
-        nar = C.c_longlong(0)
-        self._check(self._L.dsa_solve_rows_radial(self._h, _p(out), None, None, None, C.c_longlong(capacity), C.byref(nar)))
-        return out, nar.value
+        return self._solve_rows(self._L.dsa_solve_rows_radial, (), capacity, host=False)
 
     def iteration_system_radial_device(self, nx, ny, nz, obst, dsyn, threshold0, weight0, weight_h=None, aniso=0.0):
         """dsa_iteration_system_radial_device on the radial rows left on the device.  Returns dict(m, n, nar, cbst (m,), datweight (dall,),
         norm (n,), dws (2, 2)); afterwards lsmr(cbst, damp) solves on the resident matrix"""
-        f = np.float32
-        obst = np.ascontiguousarray(obst, f); dsyn = np.ascontiguousarray(dsyn, f)
-        dall = obst.size
-        if dsyn.size != dall:
-            raise ValueError("obst and dsyn differ in length")
         maxvp = max(nx - 2, 0) * max(ny - 2, 0) * max(nz - 1, 0)
-        n = 2 * maxvp
-        cbst = np.zeros(dall + 3 * maxvp, f); datweight = np.zeros(dall, f); norm = np.zeros(max(n, 1), f); dws = np.zeros(4, f)
-        m, nar = C.c_int(0), C.c_longlong(0)
-        self._check(self._L.dsa_iteration_system_radial_device(self._h, int(nx), int(ny), int(nz), dall, _p(obst), _p(dsyn), float(threshold0), float(weight0),
-                                                               float(weight0 if weight_h is None else weight_h), float(aniso), cbst.ctypes.data_as(_vp),
-                                                               datweight.ctypes.data_as(_vp), norm.ctypes.data_as(_vp), C.byref(m), C.byref(nar), dws.ctypes.data_as(_vp)))
-        self._mn = (m.value, n)
-        return dict(m=m.value, n=n, nar=nar.value, cbst=cbst, datweight=datweight, norm=norm[:n], dws=dws.reshape(2, 2))
+        return self._iteration_system_device(self._L.dsa_iteration_system_radial_device, (nx, ny, nz), obst, dsyn,
+                                             (threshold0, weight0, weight0 if weight_h is None else weight_h, aniso), 2 * maxvp, 3 * maxvp, 2)
 
     def update_radial(self, dv, dvmax, minvel, maxvel):
         """dsa_update_radial: dv, 2 (nx - 2)(ny - 2)(nz - 1) values (the Vsv block then the Vsh block of a solution; any shape), applied to the
