@@ -12,6 +12,7 @@
 // k_latres_* (DESIGN.md section 27): the resolution of the laterally coupled step, a batch of section 24's solves, one lane per member.
 // k_sample_* (DESIGN.md section 29): the Metropolis chains of the Monte-Carlo depth inversion, one thread per (column, chain).
 // k_sample_shape, k_sample_propose_block, k_sample_accept_block: the columns' shapes and the block sweeps.
+// k_sample_hist, k_sample_cov, k_sample_marginal_finish: the posterior marginals, one thread per counter or sum.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -402,6 +403,49 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_finish(SampleView S, do
     sample_finish(S, t - (long long)l * S.ncol, l, nodes, cols, counts);
 }
 
+// The posterior marginals, launched after the Metropolis test of a kept sweep while they are switched on.  Thread t =
+// (row * C + chain) * ncol + column, row a depth (k_sample_hist) or a packed triangle entry (k_sample_cov): the column is the fastest
+// index, so a wavefront's reads of v and v0 and its read-modify-write of P are consecutive; the counters of one depth and chain lie nbins
+// planes apart and a wavefront touches as many of them as its values have bins.  Every counter and every sum has one thread: no atomics,
+// no LDS.
+__device__ __forceinline__ bool marginal_thread(const SampleView& S, int rows, long long* c, int* q, int* row)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x, cc = S.ncol * S.C;
+    if (t >= cc * rows) return false;
+    *row = (int)(t / cc);
+    const long long r = t - (long long)*row * cc;
+    *q = (int)(r / S.ncol);
+    *c = r - (long long)*q * S.ncol;
+    return true;
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_hist(SampleView S, SampleMarginalView G, int sweep)
+{
+    long long c; int q, l;
+    if (!marginal_thread(S, S.nz - 1, &c, &q, &l)) return;
+    sample_marginal_hist(S, G, c, q, l, sweep);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_cov(SampleView S, SampleMarginalView G, int sweep)
+{
+    long long c; int q, e;
+    if (!marginal_thread(S, column_tri_size(S.nz - 1), &c, &q, &e)) return;
+    sample_marginal_cov(S, G, c, q, e, sweep);
+}
+
+// one thread per (column, row): t = row * ncol + column, rows = M (or the triangle's size where cov is asked for).  A row below M is a
+// depth: its pooled counts (nbins, M, ncol), mode and quantiles (1 + nlevels, M, ncol); every row is a triangle entry of cov (tri, ncol)
+__global__ void __launch_bounds__(kSampleBlock) k_sample_marginal_finish(SampleView S, SampleMarginalView G, SampleLevels lv, int rows, unsigned* __restrict__ pooled,
+                                                                         double* __restrict__ figures, double* __restrict__ cov)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x;
+    if (t >= S.ncol * rows) return;
+    const int row = (int)(t / S.ncol);
+    const long long c = t - (long long)row * S.ncol;
+    if (row < S.nz - 1) sample_marginal_finish(S, G, c, row, lv.n, lv.p, pooled, figures);
+    if (cov) sample_marginal_cov_finish(S, G, c, row, cov);
+}
+
 }  // namespace
 
 void launch_column_step(int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S, float smooth, float damp,
@@ -677,6 +721,22 @@ void launch_sample_shape(int nx, int ny, int nz, int K, const float* d_obs, cons
     const size_t lds = column_work_doubles(nz - 1, K) * sizeof(double);
     hipLaunchKernelGGL(k_sample_shape, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, smooth, damp, d_tri, d_r,
                        d_nused, d_flag);
+}
+
+void launch_sample_marginals(const SampleView& S, const SampleMarginalView& G, int sweep, hipStream_t stream)
+{
+    if (sample_empty(S) || sweep <= S.burn) return;
+    const long long cc = S.ncol * S.C;
+    hipLaunchKernelGGL(k_sample_hist, sample_grid(cc * (S.nz - 1)), dim3(kSampleBlock), 0, stream, S, G, sweep);
+    if (G.P) hipLaunchKernelGGL(k_sample_cov, sample_grid(cc * column_tri_size(S.nz - 1)), dim3(kSampleBlock), 0, stream, S, G, sweep);
+}
+
+void launch_sample_marginal_finish(const SampleView& S, const SampleMarginalView& G, const SampleLevels& levels, unsigned* d_pooled, double* d_figures, double* d_cov,
+                                   hipStream_t stream)
+{
+    if (sample_empty(S)) return;
+    const int rows = d_cov ? column_tri_size(S.nz - 1) : S.nz - 1;
+    hipLaunchKernelGGL(k_sample_marginal_finish, sample_grid(S.ncol * rows), dim3(kSampleBlock), 0, stream, S, G, levels, rows, d_pooled, d_figures, d_cov);
 }
 
 void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream)

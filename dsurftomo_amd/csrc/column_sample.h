@@ -33,6 +33,18 @@
 //             written.  Else pold_all gets the M old values, v the M new ones, pnode = -1.  The Metropolis test is the one above (draw 2);
 //             a rejection puts all M values back.  Block counters (3, chain, column): proposed, accepted, out of box
 //
+// Posterior marginals, switched on beside the above by a SampleMarginalView; they observe the kept sweeps and write
+// nothing of the above:
+//   bin       of a value v at depth l: dlo = (double)lo_l, w = (double)hi_l - dlo; w <= 0 (or NaN): bin 0; else x = (((double)v - dlo) / w)
+//             nbins, b = 0 for x < 0, nbins - 1 for x >= nbins, else (int)x (chain 0 starts at the unclipped start: an end bin)
+//   counts    where the moments are taken (a chain that is not idle, a sweep after burn, the Metropolis test settled): hist (bin, depth,
+//             chain, column) += 1 for every depth; with the covariance P (column_tri(i, j), chain, column) += d_i d_j, j <= i, d the
+//             moments' own: P's diagonal has the bits of S2
+//   finish    per (column, depth): the pooled counts, the mode, the quantiles -- see sample_marginal_finish; per (column, triangle entry):
+//             the pooled covariance -- see sample_marginal_cov_finish
+// One thread per counter or sum (k_sample_hist: (depth, chain, column); k_sample_cov: (entry, chain, column)), launched after the sweep's
+// Metropolis test.
+//
 // fp64 under -ffp-contract=off, no square root, IEEE division: one value per figure whatever computes it.  One thread per (column, chain)
 // (column_kernels.hip: k_sample_*) or a loop over them (tests/hostcheck_column_sample.cpp); a thread's sums are its own sequential chains and
 // no thread reads what another writes in the same launch, so the mapping cannot change a bit.
@@ -86,6 +98,13 @@ struct SampleBlockView {
     int* cnt;                                          // (3, C, ncol): block proposals made, accepted, out of the box
     int block_every;                                   // 0: no block sweeps
     double block_scale;
+};
+
+// the posterior marginals' state, passed beside the view while they are switched on
+struct SampleMarginalView {
+    int nbins;                                         // 2 .. 256: equal bins of every node's box
+    unsigned* hist;                                    // (nbins, M, C, ncol): the kept sweeps of a chain per bin
+    double* P;                                         // (column_tri_size(M), C, ncol): sum of d_i d_j over the kept sweeps, j <= i; null: no covariance
 };
 
 DSA_CS unsigned long long sample_mix(unsigned long long x)
@@ -500,6 +519,107 @@ DSA_CS void sample_finish(const SampleView& S, long long c, int l, double* nodes
     for (int w = 0; w < kSampleCounters; ++w) counts[(kSampleSumAccepted + w) * S.ncol + c] = sums[w];
     counts[kSampleReseeded * S.ncol + c] = reseeded;
     counts[kSampleNkept * S.ncol + c] = n;
+}
+
+// ---- the posterior marginals: observers of the kept sweeps; they write nothing of the above ----
+
+// the bin of value v in the box of (column c, depth l) cut into nbins equal bins: 0 in a box without width, an end bin outside the box
+DSA_CS int sample_bin(const SampleView& S, long long c, int l, int nbins, float v)
+{
+    float lo, hi;
+    sample_box(S, c, l, &lo, &hi);
+    const double dlo = (double)lo, w = (double)hi - dlo;
+    if (!(w > 0.0)) return 0;
+    const double t = ((double)v - dlo) / w;
+    const double x = t * (double)nbins;
+    if (x < 0.0) return 0;
+    if (x >= (double)nbins) return nbins - 1;
+    return (int)x;
+}
+
+// a chain whose state sweep `sweep` added to the moments (sample_accept_any's rule, read after it)
+DSA_CS bool sample_marginal_kept(const SampleView& S, long long c, int q, int sweep) { return sweep > S.burn && S.pmark[sample_at(S, c, q)] != kSampleIdle; }
+
+// the sweep's count of (column c, chain q, depth l < M), after the sweep's Metropolis test
+DSA_CS void sample_marginal_hist(const SampleView& S, const SampleMarginalView& G, long long c, int q, int l, int sweep)
+{
+    if (!sample_marginal_kept(S, c, q, sweep)) return;
+    const int M = S.nz - 1;
+    const int b = sample_bin(S, c, l, G.nbins, S.v[sample_node(S, c, q, l)]);
+    G.hist[(((long long)b * M + l) * S.C + q) * S.ncol + c] += 1u;
+}
+
+// the sweep's product of (column c, chain q, triangle entry e = column_tri(i, j), j <= i), after the sweep's Metropolis test
+DSA_CS void sample_marginal_cov(const SampleView& S, const SampleMarginalView& G, long long c, int q, int e, int sweep)
+{
+    if (!sample_marginal_kept(S, c, q, sweep)) return;
+    const int i = column_tri_row(e), j = e - column_tri(i, 0);
+    const double di = (double)S.v[sample_node(S, c, q, i)] - (double)S.v0[(long long)i * S.ncol + c];
+    const double dj = (double)S.v[sample_node(S, c, q, j)] - (double)S.v0[(long long)j * S.ncol + c];
+    G.P[((long long)e * S.C + q) * S.ncol + c] += di * dj;
+}
+
+// The marginal of (column c, depth l < M): pooled (nbins, M, ncol), the counts summed over the chains ascending; figures (1 + nlevels, M,
+// ncol), the mode -- the centre of the first fullest pooled bin -- and the quantiles of the levels p (each in (0, 1)): N the pooled total,
+// target = p N; at the first bin b, ascending, with h_b > 0 and cum + h_b >= target (cum the total of the bins below), the value
+// lo + ((b + (target - cum) / h_b) / nbins) w.  N = 0 (the ring, a flagged column, no kept sweep): zeros, as sample_finish.
+DSA_CS void sample_marginal_finish(const SampleView& S, const SampleMarginalView& G, long long c, int l, int nlevels, const double* levels, unsigned* pooled,
+                                   double* figures)
+{
+    const int M = S.nz - 1, C = S.C, nb = G.nbins;
+    float lo, hi;
+    sample_box(S, c, l, &lo, &hi);
+    const double dlo = (double)lo, w = (double)hi - dlo, dnb = (double)nb;
+    unsigned long long N = 0ull;
+    unsigned top = 0u;
+    int bstar = 0;
+    for (int b = 0; b < nb; ++b) {
+        unsigned h = 0u;
+        for (int q = 0; q < C; ++q) h += G.hist[(((long long)b * M + l) * C + q) * S.ncol + c];
+        pooled[((long long)b * M + l) * S.ncol + c] = h;
+        N += h;
+        if (h > top) { top = h; bstar = b; }
+    }
+    figures[(long long)l * S.ncol + c] = N ? dlo + (((double)bstar + 0.5) / dnb) * w : 0.0;
+    for (int k = 0; k < nlevels; ++k) {
+        double out = 0.0;
+        if (N) {
+            const double target = levels[k] * (double)N;
+            unsigned long long cum = 0ull;
+            for (int b = 0; b < nb; ++b) {
+                const unsigned h = pooled[((long long)b * M + l) * S.ncol + c];
+                if (h > 0u && (double)(cum + h) >= target) {
+                    const double frac = (target - (double)cum) / (double)h;
+                    out = dlo + (((double)b + frac) / dnb) * w;
+                    break;
+                }
+                cum += h;
+            }
+        }
+        figures[((long long)(1 + k) * M + l) * S.ncol + c] = out;
+    }
+}
+
+// The pooled covariance of (column c, triangle entry e = column_tri(i, j)): cov (tri, ncol) = sum_q P_q / (n C) - pm_i pm_j, chains ascending,
+// pm sample_finish's pooled mean offset; the diagonal has the bits of sample_finish's variance.  n = 0: 0.
+DSA_CS void sample_marginal_cov_finish(const SampleView& S, const SampleMarginalView& G, long long c, int e, double* cov)
+{
+    const int C = S.C;
+    const int n = S.nkept[sample_at(S, c, 0)];
+    double out = 0.0;
+    if (n > 0) {
+        const int i = column_tri_row(e), j = e - column_tri(i, 0);
+        const double dn = (double)n, dc = (double)C;
+        double si = 0.0, sj = 0.0, sp = 0.0;
+        for (int q = 0; q < C; ++q) {
+            si += S.S1[sample_node(S, c, q, i)];
+            sj += S.S1[sample_node(S, c, q, j)];
+            sp += G.P[((long long)e * C + q) * S.ncol + c];
+        }
+        const double pmi = si / (dn * dc), pmj = sj / (dn * dc);
+        out = sp / (dn * dc) - pmi * pmj;
+    }
+    cov[(long long)e * S.ncol + c] = out;
 }
 
 }  // namespace dsa

@@ -393,6 +393,17 @@ struct Engine {
     int columns_sample_shape(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag);
     int columns_sample_blocks(int block_every, double block_scale);
     int columns_sample_block_state(float* pold_all, int* counters);
+    // posterior marginals of the sample stage (dsa_columns_sample_marginals, _marginals_fetch, _marginals_state; k_sample_hist, k_sample_cov,
+    // k_sample_marginal_finish).  sample_nbins > 0 (set by columns_sample_marginals on an open sample stage before its
+    // first sweep, cleared by every columns_sample_begin) makes every sweep after burn count the chains' states in mrg_hist and, with
+    // sample_cov, add their products to mrg_P; nothing else of the stage is written.
+    int sample_nbins = 0;
+    bool sample_cov = false;
+    OwnedBuf<unsigned> mrg_hist, mrg_pooled;
+    OwnedBuf<double> mrg_P, mrg_fig, mrg_covout;
+    int columns_sample_marginals(int nbins, int with_cov);
+    int columns_sample_marginals_fetch(int nlevels, const double* levels, unsigned* hist, double* figures, double* cov);
+    int columns_sample_marginals_state(unsigned* hist, double* P);
 
     // radial anisotropy in the direct inversion (dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial; DESIGN.md
     // section 28).  radial_sens: Srow holds the depth factors of every slot on the model of its wave type (k_sen_combine_radial) and

@@ -675,6 +675,14 @@ static SampleBlockView sample_block_view(Engine& e)
     return B;
 }
 
+// the marginals' state where it lies; nbins 0 while they are off (the buffers may then be empty: nothing reads them)
+static SampleMarginalView sample_marginal_view(Engine& e)
+{
+    SampleMarginalView G{};
+    G.nbins = e.sample_nbins; G.hist = e.mrg_hist.p; G.P = e.sample_cov ? e.mrg_P.p : nullptr;
+    return G;
+}
+
 // dsa_columns_sample_begin: everything is checked before the device is touched; then a stage of nchains models (dispersion_setup), whose
 // model store k_sample_setup writes where it lies, the set-up's runs of the plan (times only), and the chains' phi and psi.
 int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const float* vels, const float* depz, float minthk, int nruns, const int* iwave, const int* igr,
@@ -726,6 +734,7 @@ int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const floa
     }
     sample_has_wt = wt != nullptr; sample_sweep = 0; sample_burn = burn; sample_seed = seed;
     sample_block_every = 0; sample_block_scale = 0.0;
+    sample_nbins = 0; sample_cov = false;
     sample_lam2 = (double)smooth * (double)smooth; sample_step = (double)step; sample_spread = (double)spread; sample_two_t = 2.0 * (double)temperature;
     sample_width = width; sample_minvel = minvel; sample_maxvel = maxvel;
     HIP_TRY(this, hipMemcpyAsync(smp_v0.p, vels, ncol * nz * 4, hipMemcpyHostToDevice, stream));
@@ -744,8 +753,9 @@ int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const floa
     return 0;
 }
 
-// dsa_columns_sample_run: whole sweeps, each the proposal, one dispersion_run per entry of the plan (times only) and the Metropolis test.
-// A sweep's only host traffic is dispersion_run's.
+// dsa_columns_sample_run: whole sweeps, each the proposal, one dispersion_run per entry of the plan (times only) and the Metropolis test;
+// with the marginals on, after it, their two observers in a sweep after burn.  A sweep's only host traffic is
+// dispersion_run's.
 int Engine::columns_sample_run(int nsweeps)
 {
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_run: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
@@ -753,6 +763,7 @@ int Engine::columns_sample_run(int nsweeps)
     HIP_TRY(this, hipSetDevice(device));
     const SampleView S = sample_view(*this);
     const SampleBlockView B = sample_block_view(*this);
+    const SampleMarginalView G = sample_marginal_view(*this);
     for (int s = 0; s < nsweeps; ++s) {
         const int sweep = sample_sweep + 1;
         const bool block = sample_block_sweep(B, sweep);      // (only the sweep's number decides its kind: run(n) is n times run(1))
@@ -762,6 +773,7 @@ int Engine::columns_sample_run(int nsweeps)
             if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { sample_open = false; disp_ready = false; return rc; }
         if (block) launch_sample_accept_block(S, B, sweep, stream);
         else launch_sample_accept(S, sweep, stream);
+        if (G.nbins) launch_sample_marginals(S, G, sweep, stream);      // (observers of a kept sweep; nothing is launched while they are off)
         sample_sweep = sweep;
     }
     HIP_TRY(this, hipGetLastError());
@@ -877,6 +889,69 @@ int Engine::columns_sample_block_state(float* pold_all, int* counters)
     HIP_TRY(this, hipSetDevice(device));
     if (pold_all) HIP_TRY(this, hipMemcpyAsync(pold_all, blk_pold.p, M * cc * 4, hipMemcpyDeviceToHost, stream));
     if (counters) HIP_TRY(this, hipMemcpyAsync(counters, blk_cnt.p, kSampleBlockCounters * cc * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_marginals: the posterior marginals on (nbins 2 .. 256) or off (0) on an open sample stage that
+// has not run a sweep.  The buffers are sized before anything of the state changes: a refusal leaves the stage as it was.  The counts and
+// sums are cleared.
+int Engine::columns_sample_marginals(int nbins, int with_cov)
+{
+    const char* who = "columns_sample_marginals";
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
+    if (sample_sweep != 0) { fail(DSA_ERR_STATE, "%s: %d sweeps have been run; the marginals are switched before the first", who, sample_sweep); return DSA_ERR_STATE; }
+    if (nbins < 0 || nbins == 1 || nbins > 256) { fail(DSA_ERR_ARGUMENT, "%s: nbins %d must be 0 (off) or 2 to 256", who, nbins); return DSA_ERR_ARGUMENT; }
+    if (with_cov != 0 && with_cov != 1) { fail(DSA_ERR_ARGUMENT, "%s: with_cov %d must be 0 or 1", who, with_cov); return DSA_ERR_ARGUMENT; }
+    if (nbins == 0) { sample_nbins = 0; sample_cov = false; return 0; }
+    const size_t ncol = (size_t)disp_nx * disp_ny, cc = ncol * disp_nmodels, M = (size_t)disp_nz - 1, T = (size_t)column_tri_size((int)M), nb = (size_t)nbins;
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(mrg_hist, nb * M * cc) || (with_cov && ensure(mrg_P, T * cc)) || ensure(mrg_pooled, nb * M * ncol) ||
+        ensure(mrg_fig, (size_t)(1 + kSampleMaxLevels) * M * ncol) || (with_cov && ensure(mrg_covout, T * ncol))) return status;
+    HIP_TRY(this, hipMemsetAsync(mrg_hist.p, 0, nb * M * cc * 4, stream));
+    if (with_cov) HIP_TRY(this, hipMemsetAsync(mrg_P.p, 0, T * cc * 8, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    sample_nbins = nbins; sample_cov = with_cov != 0;
+    return 0;
+}
+
+// dsa_columns_sample_marginals_fetch: the finish of the marginals as they are; nothing of the state is changed, the sweeps may go on.
+int Engine::columns_sample_marginals_fetch(int nlevels, const double* levels, unsigned* hist, double* figures, double* cov)
+{
+    const char* who = "columns_sample_marginals_fetch";
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
+    if (sample_nbins == 0) { fail(DSA_ERR_STATE, "%s: the marginals are off; call dsa_columns_sample_marginals before the first sweep", who); return DSA_ERR_STATE; }
+    if (cov && !sample_cov) { fail(DSA_ERR_STATE, "%s: cov is asked for, but dsa_columns_sample_marginals was called without with_cov", who); return DSA_ERR_STATE; }
+    if (nlevels < 0 || nlevels > kSampleMaxLevels || (nlevels > 0 && !levels)) { fail(DSA_ERR_ARGUMENT, "%s: nlevels %d (0 to %d, with the levels)", who, nlevels, kSampleMaxLevels); return DSA_ERR_ARGUMENT; }
+    if (!figures) { fail(DSA_ERR_ARGUMENT, "%s: figures is required", who); return DSA_ERR_ARGUMENT; }
+    SampleLevels lv{};
+    lv.n = nlevels;
+    for (int k = 0; k < nlevels; ++k) {
+        if (!std::isfinite(levels[k]) || !(levels[k] > 0.0 && levels[k] < 1.0)) { fail(DSA_ERR_ARGUMENT, "%s: level %d = %g must lie inside (0, 1)", who, k, levels[k]); return DSA_ERR_ARGUMENT; }
+        lv.p[k] = levels[k];
+    }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny, M = (size_t)disp_nz - 1, T = (size_t)column_tri_size((int)M), nb = (size_t)sample_nbins;
+    launch_sample_marginal_finish(sample_view(*this), sample_marginal_view(*this), lv, mrg_pooled.p, mrg_fig.p, cov ? mrg_covout.p : nullptr, stream);
+    HIP_TRY(this, hipGetLastError());
+    if (hist) HIP_TRY(this, hipMemcpyAsync(hist, mrg_pooled.p, nb * M * ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(figures, mrg_fig.p, (size_t)(1 + nlevels) * M * ncol * 8, hipMemcpyDeviceToHost, stream));
+    if (cov) HIP_TRY(this, hipMemcpyAsync(cov, mrg_covout.p, T * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_marginals_state: the raw per-chain counts and sums, for the tests; each pointer may be null
+int Engine::columns_sample_marginals_state(unsigned* hist, double* P)
+{
+    const char* who = "columns_sample_marginals_state";
+    if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
+    if (sample_nbins == 0) { fail(DSA_ERR_STATE, "%s: the marginals are off; call dsa_columns_sample_marginals before the first sweep", who); return DSA_ERR_STATE; }
+    if (P && !sample_cov) { fail(DSA_ERR_STATE, "%s: P is asked for, but dsa_columns_sample_marginals was called without with_cov", who); return DSA_ERR_STATE; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t cc = (size_t)disp_nx * disp_ny * disp_nmodels, M = (size_t)disp_nz - 1, T = (size_t)column_tri_size((int)M);
+    if (hist) HIP_TRY(this, hipMemcpyAsync(hist, mrg_hist.p, (size_t)sample_nbins * M * cc * 4, hipMemcpyDeviceToHost, stream));
+    if (P) HIP_TRY(this, hipMemcpyAsync(P, mrg_P.p, T * cc * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     return 0;
 }
@@ -2713,6 +2788,24 @@ int dsa_columns_sample_blocks(dsa_engine* e, int block_every, double block_scale
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_sample_blocks(block_every, block_scale);
+}
+
+int dsa_columns_sample_marginals(dsa_engine* e, int nbins, int with_cov)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_marginals(nbins, with_cov);
+}
+
+int dsa_columns_sample_marginals_fetch(dsa_engine* e, int nlevels, const double* levels, unsigned* hist, double* figures, double* cov)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_marginals_fetch(nlevels, levels, hist, figures, cov);
+}
+
+int dsa_columns_sample_marginals_state(dsa_engine* e, unsigned* hist, double* P)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_marginals_state(hist, P);
 }
 
 int dsa_columns_sample_block_state(dsa_engine* e, float* pold_all, int* counters)

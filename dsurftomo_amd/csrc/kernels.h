@@ -401,6 +401,16 @@ void launch_sample_shape(int nx, int ny, int nz, int K, const float* d_obs, cons
                          double* d_tri, double* d_r, int* d_nused, int* d_flag, hipStream_t stream);
 void launch_sample_propose_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream);
 void launch_sample_accept_block(const SampleView& S, const SampleBlockView& B, int sweep, hipStream_t stream);
+// The posterior marginals (k_sample_hist, k_sample_cov, k_sample_marginal_finish), G (column_sample.h) beside S.
+// launch_sample_marginals: after the Metropolis test of sweep `sweep`; launches nothing in a sweep <= burn, k_sample_cov only where G.P is
+// set.  launch_sample_marginal_finish: d_pooled (nbins, nz - 1, ncol), d_figures (1 + levels.n, nz - 1, ncol), d_cov (nz (nz - 1) / 2,
+// ncol) or null (G.P must be set where it is not).
+struct SampleMarginalView;
+constexpr int kSampleMaxLevels = 16;
+struct SampleLevels { int n; double p[kSampleMaxLevels]; };
+void launch_sample_marginals(const SampleView& S, const SampleMarginalView& G, int sweep, hipStream_t stream);
+void launch_sample_marginal_finish(const SampleView& S, const SampleMarginalView& G, const SampleLevels& levels, unsigned* d_pooled, double* d_figures, double* d_cov,
+                                   hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

@@ -5,7 +5,8 @@
                                   [--lateral W [--lateral-tol T] [--lateral-maxit N]] [--radial-resolution]
                                   [--lateral-resolution [--lateral-resolution-stride N] [--lateral-checkerboard NX,NY,NZ[,AMP]]]
                                   [--sample C,SWEEPS[,BURN] [--sample-step S] [--sample-spread P] [--sample-width W] [--sample-seed N]
-                                   [--sample-temperature T] [--sample-block EVERY [--sample-block-scale S]]]
+                                   [--sample-temperature T] [--sample-block EVERY [--sample-block-scale S]]
+                                   [--sample-bins NB [--sample-quantiles P1,P2,...] [--sample-covariance]]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -108,6 +109,16 @@ of the final model under the sampler's weights (columns_sample_shape, after the 
 2.38 sqrt(3 T / M) for the M unknowns of a column.  A column whose factorisation fails keeps the single-node proposal.  The log gives the
 acceptance of the block and of the single-node proposals separately.  EVERY = 0 (the default) is the single-node sampler, bit for bit.
 
+--sample-bins NB [--sample-quantiles P1,P2,...] [--sample-covariance], with --sample: in every kept sweep the device
+counts each chain's value at each node in one of NB (2 to 256) equal bins of the node's box, and with --sample-covariance adds the products
+of the offsets of a column's depths; the sampler's own figures keep their bits.  <input>DepthPosteriorQuantiles.dat (write_ / read_
+posterior_quantiles): per node longitude, latitude, depth, the box, the mode and the quantiles of the levels (default 0.025, 0.16, 0.5,
+0.84, 0.975), linear inside a bin.  <input>DepthPosteriorMarginals.dat (write_ / read_posterior_marginals): per node the NB counts pooled
+over the chains.  <input>DepthPosteriorCorrelation.dat (write_ / read_posterior_correlation), with --sample-covariance: per column the
+correlations between its depths.  The log gives the median width of the interval between the outermost levels and the median and largest
+share of a node's states in the end bins of its box -- the sign of a posterior that leans on the prior box.  NB = 0 (the default) launches
+nothing.  sample_marginal_bin, sample_marginal_mode and sample_marginal_quantile restate the rules in NumPy.
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -146,6 +157,7 @@ DEFAULT_SAMPLE_SPREAD = 0.05
 DEFAULT_SAMPLE_WIDTH = 0.5
 DEFAULT_SAMPLE_SEED = 1
 DEFAULT_SAMPLE_TEMPERATURE = 1.0
+DEFAULT_SAMPLE_QUANTILES = "0.025,0.16,0.5,0.84,0.975"
 RADIAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused_r", "%d", "int"), ("nused_l", "%d", "int")) + _F64("rms_first_r", "rms_last_r", "rms_first_l", "rms_last_l") +
                     (("flag", "%d", "int"),))
 
@@ -1240,6 +1252,141 @@ def sample_sd(var):
     return np.sqrt(np.maximum(np.asarray(var, np.float64), 0.0))
 
 
+# ---- the posterior marginals: the twin of csrc/column_sample.h's bin, mode and quantile rules ----
+
+def sample_box(v0, width, minvel, maxvel):
+    """the box of every node in fp32, as sample_box: (max(minvel, v0 - width), min(maxvel, v0 + width))"""
+    F = np.float32
+    v0 = np.asarray(v0, F)
+    return np.maximum(v0 - F(width), F(minvel)), np.minimum(v0 + F(width), F(maxvel))
+
+
+def sample_marginal_bin(v, lo, hi, nbins):
+    """sample_bin of every value of v (fp32) in the box [lo, hi] (fp32, broadcast against v) cut into nbins bins: int32.  Bin 0 in a box
+    without width; a value outside the box falls into an end bin."""
+    v, lo, hi = (np.asarray(a, np.float32).astype(np.float64) for a in (v, lo, hi))
+    v, lo, hi = np.broadcast_arrays(v, lo, hi)
+    w = hi - lo
+    ok = w > 0
+    with np.errstate(all="ignore"):
+        x = ((v - lo) / np.where(ok, w, 1.0)) * float(nbins)
+    b = np.where(x < 0, 0.0, np.where(x >= nbins, float(nbins - 1), np.floor(x)))      # ((int)x of an x >= 0 is its floor)
+    return np.where(ok, b, 0.0).astype(np.int32)
+
+
+def sample_marginal_counts(models, start, width, minvel, maxvel, nbins):
+    """what one kept sweep adds to the pooled histogram: models (nz, C, ncol) fp32, the chains' states, start (nz, ncol) fp32.  Returns
+    (nbins, nz - 1, ncol) int64, the chains of every node per bin.  The caller leaves out the columns whose chains are idle."""
+    models = np.asarray(models, np.float32)
+    nz, Cn, ncol = models.shape
+    M = nz - 1
+    lo, hi = sample_box(np.asarray(start, np.float32).reshape(nz, ncol)[:M], width, minvel, maxvel)
+    b = sample_marginal_bin(models[:M], lo[:, None, :], hi[:, None, :], nbins)
+    out = np.zeros((nbins, M, ncol), np.int64)
+    li, ci = np.meshgrid(np.arange(M), np.arange(ncol), indexing="ij")
+    for q in range(Cn):
+        np.add.at(out, (b[:, q], li, ci), 1)
+    return out
+
+
+def sample_marginal_mode(h, lo, hi):
+    """sample_marginal_finish's mode of the pooled counts h (nbins) of one node: the centre of the first fullest bin; 0.0 without a count"""
+    h = [int(x) for x in h]
+    nb = len(h)
+    if sum(h) == 0:
+        return 0.0
+    dlo = float(np.float32(lo)); w = float(np.float32(hi)) - dlo
+    b = h.index(max(h))
+    return dlo + ((float(b) + 0.5) / float(nb)) * w
+
+
+def sample_marginal_quantile(h, lo, hi, p):
+    """sample_marginal_finish's quantile of level p of the pooled counts h (nbins) of one node, linear inside the bin that reaches p of the
+    total; 0.0 without a count"""
+    h = [int(x) for x in h]
+    nb, N = len(h), sum(h)
+    if N == 0:
+        return 0.0
+    dlo = float(np.float32(lo)); w = float(np.float32(hi)) - dlo
+    target = float(p) * float(N)
+    cum = 0
+    for b in range(nb):
+        if h[b] > 0 and float(cum + h[b]) >= target:
+            frac = (target - float(cum)) / float(h[b])
+            return dlo + ((float(b) + frac) / float(nb)) * w
+        cum += h[b]
+    return 0.0
+
+
+class SampleMarginalTwin:
+    """The marginals' state beside column_sample_twin: pass `after` as its hook.  hist (nbins, M, C, ncol) uint32 and, with_cov, P
+    (M (M + 1) / 2, C, ncol): after every sweep > burn the state of every chain that is not idle is counted and its products are added,
+    as sample_marginal_hist and sample_marginal_cov do.  finish(state, levels): dict(hist: the pooled counts, mode, quantiles, cov)."""
+
+    def __init__(self, start, nchains, width, minvel, maxvel, burn, nbins, with_cov=False):
+        self.start = np.asarray(start, np.float32)
+        nz, ncol = self.start.shape
+        self.M, self.C, self.ncol, self.burn, self.nbins = nz - 1, int(nchains), ncol, int(burn), int(nbins)
+        self.box = (width, minvel, maxvel)
+        self.lo, self.hi = sample_box(self.start[:self.M], width, minvel, maxvel)
+        self.hist = np.zeros((self.nbins, self.M, self.C, ncol), np.uint32)
+        self.P = np.zeros((self.M * (self.M + 1) // 2, self.C, ncol)) if with_cov else None
+
+    def after(self, sweep, st):
+        if sweep <= self.burn:
+            return
+        M = self.M
+        v = np.asarray(st["models"], np.float32)[:M]
+        kept = np.asarray(st["pmark"]) != -1                                         # (C, ncol)
+        b = sample_marginal_bin(v, self.lo[:, None, :], self.hi[:, None, :], self.nbins)
+        li, qi, ci = np.nonzero(np.broadcast_to(kept[None], b.shape))
+        np.add.at(self.hist, (b[li, qi, ci], li, qi, ci), 1)
+        if self.P is not None:
+            d = v.astype(np.float64) - self.start[:M].astype(np.float64)[:, None, :]
+            for i in range(M):
+                for j in range(i + 1):
+                    e = column_tri(i, j)
+                    self.P[e] = np.where(kept, self.P[e] + d[i] * d[j], self.P[e])
+
+    def finish(self, st, levels):
+        M, C = self.M, self.C
+        pooled = np.zeros((self.nbins, M, self.ncol), np.uint32)
+        for q in range(C):
+            pooled += self.hist[:, :, q]
+        mode, quant = sample_marginal_twin(pooled, self.start, *self.box, levels)
+        out = dict(hist=pooled, mode=mode, quantiles=quant)
+        if self.P is not None:
+            n = np.asarray(st["nkept"])[0].astype(np.float64)
+            ok = n > 0
+            den = np.where(ok, n, 1.0) * float(C)
+            s1 = np.zeros((M, self.ncol)); sp = np.zeros(self.P.shape[::2])
+            for q in range(C):
+                s1 = s1 + np.asarray(st["S1"])[:, q]
+                sp = sp + self.P[:, q]
+            pm = s1 / den
+            cov = np.zeros(sp.shape)
+            for i in range(M):
+                for j in range(i + 1):
+                    e = column_tri(i, j)
+                    cov[e] = np.where(ok, sp[e] / den - pm[i] * pm[j], 0.0)
+            out["cov"] = cov
+        return out
+
+
+def sample_marginal_twin(hist, start, width, minvel, maxvel, levels):
+    """mode (M, ncol) and quantiles (len(levels), M, ncol) of the pooled counts hist (nbins, M, ncol) by the two rules above"""
+    hist = np.asarray(hist)
+    nb, M, ncol = hist.shape
+    lo, hi = sample_box(np.asarray(start, np.float32).reshape(-1, ncol)[:M], width, minvel, maxvel)
+    mode = np.zeros((M, ncol)); quant = np.zeros((len(levels), M, ncol))
+    for l in range(M):
+        for c in range(ncol):
+            mode[l, c] = sample_marginal_mode(hist[:, l, c], lo[l, c], hi[l, c])
+            for k, p in enumerate(levels):
+                quant[k, l, c] = sample_marginal_quantile(hist[:, l, c], lo[l, c], hi[l, c], p)
+    return mode, quant
+
+
 # ---- the plan ----
 
 def slot_plan(c):
@@ -1593,6 +1740,141 @@ def read_posterior_fit(path):
     return io.read_table(path, POSTERIOR_FIT_TABLE)
 
 
+def parse_quantiles(text):
+    """--sample-quantiles P1,P2,...: a tuple of 1 to 16 probabilities, each finite and inside (0, 1) (ValueError)"""
+    try:
+        vals = tuple(float(x) for x in str(text).split(","))
+    except ValueError:
+        vals = ()
+    if not 1 <= len(vals) <= 16 or not all(np.isfinite(p) and 0.0 < p < 1.0 for p in vals):
+        raise ValueError("--sample-quantiles takes 1 to 16 probabilities inside (0, 1) separated by commas, not %r" % (text,))
+    return vals
+
+
+def check_marginals(sample=None, bins=0, quantiles=DEFAULT_SAMPLE_QUANTILES, covariance=False):
+    """what --sample-bins, --sample-quantiles and --sample-covariance ask of the other flags, before the library is loaded (ValueError).
+    Returns None while the marginals are off, else (bins, the levels, covariance)."""
+    if bins is None or int(bins) != bins or bins < 0 or bins == 1 or bins > 256:
+        raise ValueError("--sample-bins must be 0 (off) or 2 to 256, not %r" % (bins,))
+    given = quantiles is not None and str(quantiles) != DEFAULT_SAMPLE_QUANTILES
+    levels = parse_quantiles(DEFAULT_SAMPLE_QUANTILES if quantiles is None else quantiles)
+    if sample is None and (bins or given or covariance):
+        raise ValueError("%s needs --sample: the marginals are the sampler's" % ("--sample-bins" if bins else "--sample-quantiles" if given else "--sample-covariance"))
+    if not bins and (given or covariance):
+        raise ValueError("%s needs --sample-bins: the marginals are off without it" % ("--sample-quantiles" if given else "--sample-covariance"))
+    return (int(bins), levels, bool(covariance)) if bins else None
+
+
+def posterior_quantiles_table(levels):
+    return (True, _F64("lon", "lat", "depth", "lo", "hi", "mode") + _F64(*("q%.17g" % p for p in levels)))
+
+
+def posterior_marginals_table(nbins):
+    return (True, _F64("lon", "lat", "depth") + tuple(("n%d" % b, "%d", "int") for b in range(nbins)))
+
+
+def posterior_correlation_table(M):
+    return (True, _F64("lon", "lat") + _F64(*("r%d_%d" % (i, j) for i in range(M) for j in range(M))))
+
+
+def _header_names(path):
+    with open(path) as fh:
+        return fh.readline().lstrip("#").split()
+
+
+def _node_rows(c, M):
+    """lon, lat, depth of every node above the bottom depth: depth slowest, then j, then i -- with its place (k, j * nx + i)"""
+    nx, ny = c["nx"], c["ny"]
+    for k in range(M):
+        for j in range(ny):
+            for i in range(nx):
+                lon, lat = _lonlat(c, i - 1, j - 1)
+                yield k, j * nx + i, dict(lon=float(lon), lat=float(lat), depth=float(c["depz"][k]))
+
+
+def write_posterior_quantiles(path, c, start, width, levels, mg):
+    """<input>DepthPosteriorQuantiles.dat: per node above the bottom depth (depth slowest, then j, then i) longitude, latitude, depth, the
+    box [lo, hi] of the node, the mode and the quantile of every level of columns_sample_marginals_fetch's result mg (zeros where no sweep
+    was kept)"""
+    M = c["nz"] - 1
+    lo, hi = sample_box(np.asarray(start, np.float32).reshape(c["nz"], -1)[:M], width, float(c["minvel"]), float(c["maxvel"]))
+    rows = []
+    for k, q, row in _node_rows(c, M):
+        row.update(lo=float(lo[k, q]), hi=float(hi[k, q]), mode=float(mg["mode"][k, q]))
+        row.update(("q%.17g" % p, float(mg["quantiles"][n, k, q])) for n, p in enumerate(levels))
+        rows.append(row)
+    io.write_table(path, posterior_quantiles_table(levels), rows)
+
+
+def read_posterior_quantiles(path):
+    """the rows of write_posterior_quantiles; the levels are read from the header's names"""
+    return io.read_table(path, posterior_quantiles_table([float(n[1:]) for n in _header_names(path)[6:]]))
+
+
+def write_posterior_marginals(path, c, hist):
+    """<input>DepthPosteriorMarginals.dat: per node (as the quantiles' file) longitude, latitude, depth and the nbins pooled counts n0 ..,
+    bin b the b-th of the nbins equal parts of the node's box"""
+    hist = np.asarray(hist)
+    rows = []
+    for k, q, row in _node_rows(c, c["nz"] - 1):
+        row.update(("n%d" % b, int(hist[b, k, q])) for b in range(hist.shape[0]))
+        rows.append(row)
+    io.write_table(path, posterior_marginals_table(hist.shape[0]), rows)
+
+
+def read_posterior_marginals(path):
+    return io.read_table(path, posterior_marginals_table(len(_header_names(path)) - 3))
+
+
+def sample_correlation(cov, M):
+    """the M x M correlation of every column from the packed lower triangle cov (M (M + 1) / 2, ncol): cov_ij / sqrt(cov_ii cov_jj), 0
+    where a variance is not positive.  Returns (M, M, ncol)."""
+    cov = np.asarray(cov, np.float64)
+    full = np.zeros((M, M, cov.shape[1]))
+    for i in range(M):
+        for j in range(i + 1):
+            full[i, j] = full[j, i] = cov[i * (i + 1) // 2 + j]
+    var = np.stack([full[i, i] for i in range(M)])
+    den = var[:, None] * var[None, :]
+    ok = (var[:, None] > 0) & (var[None, :] > 0)
+    return np.divide(full, np.sqrt(np.where(ok, den, 1.0)), out=np.zeros(full.shape), where=ok)
+
+
+def write_posterior_correlation(path, c, cov):
+    """<input>DepthPosteriorCorrelation.dat: per column (j, then i) longitude, latitude and the (nz - 1)^2 correlations r<i>_<j> between its
+    depths, row by row"""
+    nx, ny, M = c["nx"], c["ny"], c["nz"] - 1
+    corr = sample_correlation(cov, M)
+    rows = []
+    for j in range(ny):
+        for i in range(nx):
+            lon, lat = _lonlat(c, i - 1, j - 1)
+            row = dict(lon=float(lon), lat=float(lat))
+            row.update(("r%d_%d" % (a, b), float(corr[a, b, j * nx + i])) for a in range(M) for b in range(M))
+            rows.append(row)
+    io.write_table(path, posterior_correlation_table(M), rows)
+
+
+def read_posterior_correlation(path):
+    return io.read_table(path, posterior_correlation_table(int(round(math.sqrt(len(_header_names(path)) - 2)))))
+
+
+def marginals_summary(levels, mg, nkept):
+    """what the log says of the marginals: dict(nodes, width: the median over the nodes with a kept sweep of the distance between the
+    quantiles of the smallest and the largest level (None with fewer than two levels), end_median, end_max: the median and the largest
+    share of a node's counts in the two end bins), or None without a kept sweep"""
+    kept = np.asarray(nkept) > 0
+    if not kept.any():
+        return None
+    h = np.asarray(mg["hist"], np.float64)[:, :, kept]
+    share = (h[0] + h[-1]) / h.sum(axis=0)
+    width = None
+    if len(levels) >= 2:
+        q = np.asarray(mg["quantiles"])[:, :, kept]
+        width = float(np.median(q[int(np.argmax(levels))] - q[int(np.argmin(levels))]))
+    return dict(nodes=int(share.size), width=width, end_median=float(np.median(share)), end_max=float(share.max()))
+
+
 def rhat_summary(res):
     """what the log says of the convergence: dict(unknowns, median, worst, share of them above 1.1) over the unknowns of the columns with a kept
     sweep, or None without one"""
@@ -1604,13 +1886,17 @@ def rhat_summary(res):
 
 
 def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, step=DEFAULT_SAMPLE_STEP, spread=DEFAULT_SAMPLE_SPREAD, width=DEFAULT_SAMPLE_WIDTH,
-               seed=DEFAULT_SAMPLE_SEED, temperature=DEFAULT_SAMPLE_TEMPERATURE, log=print, block_every=0, block_scale=None, damp=DEFAULT_DAMP):
+               seed=DEFAULT_SAMPLE_SEED, temperature=DEFAULT_SAMPLE_TEMPERATURE, log=print, block_every=0, block_scale=None, damp=DEFAULT_DAMP, marginals=None):
     """--sample from the model start (nz, ny, nx): columns_sample_begin with the weights 1 / sigma where wt keeps a datum and smooth / sigma,
     the sweeps, the two files, the log.  With block_every > 0 (--sample-block), on an engine whose stage holds start: first the runs of plan
     once more with kernels and columns_sample_shape with the same weights and prior weight and damp / sigma, then, after the begin,
     columns_sample_blocks(block_every, block_scale; None: sample_block_scale(nz - 1, temperature)).  Returns dict(posterior:
     columns_sample_fetch's result, sample_sigma, rhat, posterior_path, posterior_fit_path; with block_every > 0 also block: dict(every, scale,
-    flagged: the columns whose shape was flagged, proposed, accepted, out_of_box: the block proposals summed over chains and columns))."""
+    flagged: the columns whose shape was flagged, proposed, accepted, out_of_box: the block proposals summed over chains and columns)).
+    With marginals = (bins, levels, covariance) (check_marginals'; --sample-bins): columns_sample_marginals(bins, covariance) after the
+    begin and the blocks, before the sweeps; after them columns_sample_marginals_fetch(levels), DepthPosteriorQuantiles.dat,
+    DepthPosteriorMarginals.dat and, with the covariance, DepthPosteriorCorrelation.dat; the result gains marginals: the fetch's result,
+    marginals_summary: its figures in the log, quantiles_path, marginals_path and correlation_path (None without the covariance)."""
     chains, sweeps, burn = sample
     w, lam = sample_scaling(wt, smooth, sigma, np.shape(obs))
     block = None
@@ -1623,8 +1909,11 @@ def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, ste
     eng.columns_sample_begin(start, c["depz"], c["minthk"], plan, obs, w, chains, lam, step, spread, width, temperature, float(c["minvel"]), float(c["maxvel"]), seed, burn)
     if block is not None:
         eng.columns_sample_blocks(block["every"], block["scale"])
+    if marginals is not None:
+        eng.columns_sample_marginals(marginals[0], marginals[2])
     eng.columns_sample_run(sweeps)
     res = eng.columns_sample_fetch()
+    mg = eng.columns_sample_marginals_fetch(marginals[1]) if marginals is not None else None
     if block is not None:
         bc = eng.columns_sample_block_state()["block_counters"]
         block.update(proposed=int(bc[0].sum()), accepted=int(bc[1].sum()), out_of_box=int(bc[2].sum()))
@@ -1654,6 +1943,23 @@ def run_sample(eng, c, plan, start, obs, wt, smooth, sigma, sample, out_dir, ste
         log(" depth sample: R-hat of %d unknowns median %.4f, worst %.4f, %.1f %% above 1.1" % (sm["unknowns"], sm["median"], sm["worst"], 100.0 * sm["above"]))
     log(" depth sample: the posterior written to %s, the fit of the columns to %s" % (ppath, fpath))
     out = dict(posterior=res, sample_sigma=float(sigma), rhat=sm, posterior_path=ppath, posterior_fit_path=fpath)
+    if mg is not None:
+        bins, levels, covariance = marginals
+        qpath = os.path.join(out_dir, "DSurfTomo.inDepthPosteriorQuantiles.dat")
+        mpath = os.path.join(out_dir, "DSurfTomo.inDepthPosteriorMarginals.dat")
+        cpath = os.path.join(out_dir, "DSurfTomo.inDepthPosteriorCorrelation.dat") if covariance else None
+        write_posterior_quantiles(qpath, c, start, width, levels, mg)
+        write_posterior_marginals(mpath, c, mg["hist"])
+        if covariance:
+            write_posterior_correlation(cpath, c, mg["cov"])
+        ms = marginals_summary(levels, mg, res["nkept"])
+        if ms is not None:
+            if ms["width"] is not None:
+                log(" depth sample: marginals of %d nodes in %d bins; the %g to %g interval is %.4f km/s wide (median over the nodes)" %
+                    (ms["nodes"], bins, min(levels), max(levels), ms["width"]))
+            log(" depth sample: share of a node's kept states in the end bins of its box: median %.2f %%, largest %.2f %%" % (100.0 * ms["end_median"], 100.0 * ms["end_max"]))
+        log(" depth sample: the quantiles written to %s, the marginals to %s%s" % (qpath, mpath, ", the correlations of the depths to %s" % cpath if covariance else ""))
+        out.update(marginals=mg, marginals_summary=ms, quantiles_path=qpath, marginals_path=mpath, correlation_path=cpath)
     if block is not None:
         out["block"] = block
     return out
@@ -2072,7 +2378,7 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
         lateral_maxit=DEFAULT_LATERAL_MAXIT, radial_lateral=None, radial_lateral_aniso=None, radial_resolution=False, lateral_resolution=False,
         lateral_resolution_stride=1, lateral_checkerboard=None, sample=None, sample_step=DEFAULT_SAMPLE_STEP, sample_spread=DEFAULT_SAMPLE_SPREAD,
         sample_width=DEFAULT_SAMPLE_WIDTH, sample_seed=DEFAULT_SAMPLE_SEED, sample_temperature=DEFAULT_SAMPLE_TEMPERATURE, sample_block=0,
-        sample_block_scale=None):
+        sample_block_scale=None, sample_bins=0, sample_quantiles=DEFAULT_SAMPLE_QUANTILES, sample_covariance=False):
     """the driver behind main(); returns (iterate's result with vels (nz, ny, nx) added, the paths of Depth.dat and DepthFit.dat).  With
     resolution the first item also holds resolve's entries (resolution_path and leverage_path among them); sigma None: the rms before the
     last step.  With radial: run_radial's result (DepthRadial.dat and DepthRadialFit.dat in place of the two files).  With lateral (not
@@ -2083,8 +2389,11 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
     resolve_lateral's entries are added to the first item (DepthLateralResolution.dat and, with lateral_checkerboard, DepthLateralChecker.dat
     beside the two files); sigma as with resolution.  With sample ("C,SWEEPS[,BURN]"): after the loop (and the resolution) run_sample's entries
     are added to the first item (DepthPosterior.dat and DepthPosteriorFit.dat beside the two files); sigma as with resolution; sample_block
-    (EVERY > 0) makes every EVERY-th sweep a block proposal of scale sample_block_scale (None: sample_block_scale(nz - 1, temperature))."""
+    (EVERY > 0) makes every EVERY-th sweep a block proposal of scale sample_block_scale (None: sample_block_scale(nz - 1, temperature));
+    sample_bins (2 .. 256) adds the posterior marginals at the levels sample_quantiles ("P1,P2,...") and, with sample_covariance, the
+    correlations between a column's depths (run_sample's three files)."""
     sampling = check_sample(sample, radial, lateral, sample_step, sample_spread, sample_width, sample_temperature, sample_seed, sample_block, sample_block_scale)
+    marginals = check_marginals(sample, sample_bins, sample_quantiles, sample_covariance)
     checker = check_flags(iterations, smooth, damp, dvmax, min_dws, sigma, aniso if radial else None, radial, resolution, lateral, lateral_tol, lateral_maxit,
                           radial_lateral, radial_lateral_aniso, radial_resolution, lateral_resolution, lateral_resolution_stride, lateral_checkerboard)
     c = io.load(directory)
@@ -2126,7 +2435,7 @@ def run(directory, maps_file=None, iterations=DEFAULT_ITERATIONS, smooth=DEFAULT
             rms = out["history"][-1]["rms"]
             log(" depth sample: the data's standard deviation is %s" % ("--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
             out.update(run_sample(eng, c, plan, out["vels"], obs, wt, smooth, rms if sigma is None else sigma, sampling, out_dir, sample_step, sample_spread,
-                                  sample_width, sample_seed, sample_temperature, log, sample_block, sample_block_scale, damp))
+                                  sample_width, sample_seed, sample_temperature, log, sample_block, sample_block_scale, damp, marginals))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inDepth.dat")
@@ -2168,6 +2477,9 @@ def parser():
     ap.add_argument("--sample-temperature", type=float, default=DEFAULT_SAMPLE_TEMPERATURE, metavar="T", help="with --sample: the chains sample exp(-(phi + psi) / 2T) (default %g)" % DEFAULT_SAMPLE_TEMPERATURE)
     ap.add_argument("--sample-block", type=int, default=0, metavar="EVERY", help="with --sample: every EVERY-th sweep proposes all nodes of a column at once, along its linearised posterior (default 0: single nodes only)")
     ap.add_argument("--sample-block-scale", type=float, default=None, metavar="S", help="with --sample-block: scale of the block proposal (default 2.38 sqrt(3 T / M) for M unknowns per column at temperature T)")
+    ap.add_argument("--sample-bins", type=int, default=0, metavar="NB", help="with --sample: histogram every node's kept states in NB (2 to 256) equal bins of its box and write mode, quantiles and marginals (default 0: off)")
+    ap.add_argument("--sample-quantiles", default=DEFAULT_SAMPLE_QUANTILES, metavar="P1,P2,...", help="with --sample-bins: the levels of the quantiles, at most 16 inside (0, 1) (default %s)" % DEFAULT_SAMPLE_QUANTILES)
+    ap.add_argument("--sample-covariance", action="store_true", help="with --sample-bins: also accumulate the covariance between the depths of a column and write their correlations")
     return ap
 
 
@@ -2179,6 +2491,7 @@ def main(argv=None):
                     a.radial_lateral, a.radial_lateral_aniso, a.radial_resolution, a.lateral_resolution, a.lateral_resolution_stride, a.lateral_checkerboard)
         check_sample(a.sample, a.radial, a.lateral, a.sample_step, a.sample_spread, a.sample_width, a.sample_temperature, a.sample_seed, a.sample_block,
                      a.sample_block_scale)
+        check_marginals(a.sample, a.sample_bins, a.sample_quantiles, a.sample_covariance)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
@@ -2186,7 +2499,8 @@ def main(argv=None):
         lateral=a.lateral, lateral_tol=a.lateral_tol, lateral_maxit=a.lateral_maxit, radial_lateral=a.radial_lateral, radial_lateral_aniso=a.radial_lateral_aniso,
         radial_resolution=a.radial_resolution, lateral_resolution=a.lateral_resolution, lateral_resolution_stride=a.lateral_resolution_stride,
         lateral_checkerboard=a.lateral_checkerboard, sample=a.sample, sample_step=a.sample_step, sample_spread=a.sample_spread, sample_width=a.sample_width,
-        sample_seed=a.sample_seed, sample_temperature=a.sample_temperature, sample_block=a.sample_block, sample_block_scale=a.sample_block_scale)
+        sample_seed=a.sample_seed, sample_temperature=a.sample_temperature, sample_block=a.sample_block, sample_block_scale=a.sample_block_scale,
+        sample_bins=a.sample_bins, sample_quantiles=a.sample_quantiles, sample_covariance=a.sample_covariance)
     return 0
 
 

@@ -119,6 +119,9 @@ def declare_solvers(L):
     L.dsa_columns_sample_shape.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 3
     L.dsa_columns_sample_blocks.argtypes = [_vp, _i32, C.c_double]
     L.dsa_columns_sample_block_state.argtypes = [_vp] * 3
+    L.dsa_columns_sample_marginals.argtypes = [_vp, _i32, _i32]
+    L.dsa_columns_sample_marginals_fetch.argtypes = [_vp, _i32] + [_vp] * 4
+    L.dsa_columns_sample_marginals_state.argtypes = [_vp] * 3
     L.dsa_kernels_from_dispersion_radial.argtypes = [_vp]
     L.dsa_solve_rows_radial.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_iteration_system_radial_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 4 + [_vp] * 6
@@ -177,6 +180,7 @@ class Engine:
         self._ndata = 0
         self._disp = (0, 0, 0)
         self._sample = (0, 0)                       # (chains, maps) of the last columns_sample_begin
+        self._marginals = (0, False)                # (nbins, with_cov) of the last columns_sample_marginals since then
 
     def close(self):
         if getattr(self, "_h", None):
@@ -495,6 +499,7 @@ class Engine:
                                                      float(temperature), float(minvel), float(maxvel), int(seed) & 0xFFFFFFFFFFFFFFFF, int(burn)))
         self._disp = (nx, ny, nz)
         self._sample = (int(nchains), nmaps)
+        self._marginals = (0, False)
 
     def columns_sample_run(self, nsweeps):
         """dsa_columns_sample_run: nsweeps whole sweeps of every chain on the device"""
@@ -557,6 +562,50 @@ class Engine:
             self._check(self._L.dsa_columns_sample_block_state(self._h, None, None))
         out = dict(pold_all=np.zeros((nz - 1, Cn, nx * ny), np.float32), block_counters=np.zeros((3, Cn, nx * ny), np.int32))
         self._check(self._L.dsa_columns_sample_block_state(self._h, _p(out["pold_all"]), _p(out["block_counters"])))
+        return out
+
+    # ---- posterior marginals of the sample stage ----
+    def columns_sample_marginals(self, nbins, with_cov=False):
+        """dsa_columns_sample_marginals, between columns_sample_begin and the first sweep: every sweep after burn counts each chain's value
+        at each depth in one of nbins (2 .. 256) equal bins of the node's box and, with_cov, adds the products of its offsets from the start;
+        nbins = 0 switches them off.  The sampler's own state keeps its bits."""
+        self._check(self._L.dsa_columns_sample_marginals(self._h, int(nbins), int(with_cov)))
+        self._marginals = (int(nbins), bool(with_cov) and int(nbins) > 0)
+
+    def columns_sample_marginals_fetch(self, levels=(), hist=True, cov=None):
+        """dsa_columns_sample_marginals_fetch: the finish of the present counts for the probabilities levels (at most 16, each inside (0, 1)).
+        Returns dict(mode (nz - 1, ny * nx), quantiles (len(levels), nz - 1, ny * nx) fp64; hist (nbins, nz - 1, ny * nx) uint32, the counts
+        pooled over the chains, unless hist is false; cov (nz (nz - 1) / 2, ny * nx) fp64, the packed lower triangle of the pooled
+        covariance, where cov is true -- by default where columns_sample_marginals was called with_cov).  A node without a kept sweep has
+        zeros."""
+        nx, ny, nz = self._disp
+        ncol, M = nx * ny, nz - 1
+        nbins, with_cov = self._marginals
+        cov = with_cov if cov is None else bool(cov)
+        lv = np.ascontiguousarray(levels, np.float64).reshape(-1)
+        figures = np.zeros((1 + lv.size, M, ncol))
+        out = dict(mode=figures[0], quantiles=figures[1:])
+        if hist:
+            out["hist"] = np.zeros((max(nbins, 0), M, ncol), np.uint32)
+        if cov:
+            out["cov"] = np.zeros((M * (M + 1) // 2, ncol))
+        self._check(self._L.dsa_columns_sample_marginals_fetch(self._h, int(lv.size), _p(lv) if lv.size else None, _p(out["hist"]) if hist and nbins > 0 else None,
+                                                              _p(figures), _p(out["cov"]) if cov else None))
+        return out
+
+    def columns_sample_marginals_state(self):
+        """dsa_columns_sample_marginals_state: dict(hist (nbins, nz - 1, C, ncol) uint32; with the covariance P (nz (nz - 1) / 2, C, ncol)
+        fp64: the per-chain sums of d_i d_j, whose diagonal is S2)"""
+        nx, ny, nz = self._disp
+        ncol, M = nx * ny, nz - 1
+        Cn = self._sample[0]
+        nbins, with_cov = self._marginals
+        if Cn < 1 or nbins < 1:                                                     # (no stage, or the marginals are off: the library's refusal)
+            self._check(self._L.dsa_columns_sample_marginals_state(self._h, None, None))
+        out = dict(hist=np.zeros((nbins, M, Cn, ncol), np.uint32))
+        if with_cov:
+            out["P"] = np.zeros((M * (M + 1) // 2, Cn, ncol))
+        self._check(self._L.dsa_columns_sample_marginals_state(self._h, _p(out["hist"]), _p(out["P"]) if with_cov else None))
         return out
 
     def dispersion_begin_radial(self, vsv, vsh, depz, minthk, kmax_total, nmaps_total):

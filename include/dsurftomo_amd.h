@@ -616,6 +616,34 @@ int dsa_columns_sample_shape(dsa_engine* e, int nmaps, const float* obs, const f
 int dsa_columns_sample_blocks(dsa_engine* e, int block_every, double block_scale);
 int dsa_columns_sample_block_state(dsa_engine* e, float* pold_all, int* counters);
 
+/* Posterior marginals of the sample stage: per-node histograms, mode and quantiles, and the covariance between the depths of a column
+ * (extension; csrc/column_sample.h).  They only observe: with them on, every array of dsa_columns_sample_state,
+ * dsa_columns_sample_block_state and dsa_columns_sample_fetch has the bits it has with them off.
+ * dsa_columns_sample_marginals, between dsa_columns_sample_begin and the first sweep (before or after dsa_columns_sample_blocks): nbins = 0
+ * is off (the default of every dsa_columns_sample_begin); nbins = 2 .. 256 cuts the box [lo, hi] of every node (dsa_columns_sample_begin's)
+ * into nbins equal bins.  In every sweep after burn, where the moments are taken, a chain's value v at a depth counts in bin
+ * min(nbins - 1, max(0, (int)(((double)v - lo) / (hi - lo) * nbins))) -- bin 0 in a box without width; chain 0 starts at the unclipped
+ * start, so a value outside its box is possible and counts in an end bin.  with_cov = 1 also adds d_i d_j, d = v - start, for every pair
+ * of depths j <= i of the chain.  The counts and sums are cleared; the buffers come out of the memory budget before anything changes.
+ * DSA_ERR_STATE: no open sample stage, a sweep already run; DSA_ERR_ARGUMENT: nbins < 0, 1 or > 256, with_cov not 0 or 1; the stage stays
+ * as it was.
+ * dsa_columns_sample_marginals_fetch: the finish of the present counts; the state is left as it is and the sweeps may go on.  levels:
+ * nlevels (0 .. 16) probabilities, each finite and inside (0, 1).  hist (may be NULL): nbins*(nz-1)*nx*ny unsigned, (bin, depth, column),
+ * the counts summed over the chains.  figures (required): (1+nlevels)*(nz-1)*nx*ny doubles, (figure, depth, column): the mode -- the centre
+ * lo + (b + 0.5) (hi - lo) / nbins of the first fullest pooled bin b -- then the quantile of every level p: with N the pooled total and
+ * target = p N, at the first bin b (ascending) that is not empty and whose cumulated count reaches target, lo + (b + (target - cum) / h_b)
+ * (hi - lo) / nbins, cum the count below the bin (linear inside a bin).  cov (may be NULL; needs with_cov): (nz-1)*nz/2*nx*ny doubles,
+ * (entry, column), entry i (i + 1) / 2 + j, j <= i: sum over the chains of the products / (nkept nchains) - pm_i pm_j, pm the pooled mean
+ * of d; its diagonal has the bits of dsa_columns_sample_fetch's variance.  A node without a kept sweep (the outer ring, flag 2, burn >=
+ * the sweeps run) has zeros everywhere.  DSA_ERR_STATE: no open sample stage, the marginals are off, cov without with_cov;
+ * DSA_ERR_ARGUMENT: nlevels outside 0 .. 16, a level not finite or outside (0, 1), figures NULL.
+ * dsa_columns_sample_marginals_state: the raw per-chain state for tests, each pointer may be NULL: hist nbins*(nz-1)*nchains*nx*ny unsigned,
+ * (bin, depth, chain, column); P (nz-1)*nz/2*nchains*nx*ny doubles, (entry, chain, column) (needs with_cov), whose diagonal has the bits of
+ * dsa_columns_sample_state's S2.  DSA_ERR_STATE as the fetch. */
+int dsa_columns_sample_marginals(dsa_engine* e, int nbins, int with_cov);
+int dsa_columns_sample_marginals_fetch(dsa_engine* e, int nlevels, const double* levels, unsigned* hist, double* figures, double* cov);
+int dsa_columns_sample_marginals_state(dsa_engine* e, unsigned* hist, double* P);
+
 /* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
  * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
  * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of

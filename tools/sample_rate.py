@@ -16,6 +16,11 @@ Block mode: the same stage twice in one run -- single-nod
 (columns_sample_blocks(1, the default scale)) -- and the time of the columns_sample_shape call that precedes them (its dispersion runs with
 kernels are timed apart):
     python tools/sample_rate.py block [sweeps] [chains]
+
+Marginals mode: the same stage twice in one run -- the marginals off, then on with `bins` bins and the covariance
+(columns_sample_marginals(bins, True)), burn 0 so that every timed sweep is a kept one -- and the time of a columns_sample_marginals_fetch:
+    python tools/sample_rate.py marginals [sweeps] [chains] [bins]
+The plain mode above is the figure to compare with an older build.
 """
 import os
 import sys
@@ -90,7 +95,57 @@ def block_mode(sweeps, chains):
     print("a block sweep costs %.3f ms more than a single-node sweep (%.2f %%)" % (out[1][0] - out[0][0], 100.0 * (out[1][0] - out[0][0]) / out[0][0]))
 
 
+def marginals_mode(sweeps, chains, bins):
+    """the median sweep with the marginals and the covariance on against the same build with them off in the same run, and the fetch"""
+    c = io.load()
+    plan = depth.slot_plan(c)
+    vel = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
+    kmax = c["kmax"]
+    e = Engine(0)
+    e.dispersion_begin(vel, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    obs = (e.dispersion_fetch(0, kmax) * 1.02).astype(np.float32)
+    sigma = 0.05
+    wt, lam = depth.sample_scaling(None, depth.DEFAULT_SMOOTH, sigma, obs.shape)
+    out, t_fetch = {}, []
+    for on in (0, 1, 0, 1):                                                          # twice each, interleaved: the second pair is reported
+        e.columns_sample_begin(vel, c["depz"], c["minthk"], plan, obs, wt, chains, lam, depth.DEFAULT_SAMPLE_STEP, depth.DEFAULT_SAMPLE_SPREAD, depth.DEFAULT_SAMPLE_WIDTH,
+                               depth.DEFAULT_SAMPLE_TEMPERATURE, float(c["minvel"]), float(c["maxvel"]), depth.DEFAULT_SAMPLE_SEED, 0)
+        if on:
+            e.columns_sample_marginals(bins, True)
+        e.columns_sample_run(1)
+        wall, dev = [], []
+        for s in range(sweeps):
+            ms0 = e.stats()["ms_dispersion"]
+            t0 = time.perf_counter()
+            e.columns_sample_run(1)
+            wall.append(1e3 * (time.perf_counter() - t0)); dev.append(e.stats()["ms_dispersion"] - ms0)
+        t0 = time.perf_counter()
+        e.columns_sample_run(sweeps)
+        one_call = 1e3 * (time.perf_counter() - t0) / sweeps
+        if on:
+            for _ in range(3):
+                t0 = time.perf_counter()
+                mg = e.columns_sample_marginals_fetch((0.025, 0.16, 0.5, 0.84, 0.975))
+                t_fetch.append(1e3 * (time.perf_counter() - t0))
+        out[on] = (float(np.median(wall)), float(np.median(dev)), one_call)
+    kept = e.columns_sample_fetch()["nkept"] > 0
+    e.close()
+    print("%d x %d x %d, K = %d, %d chains, %d bins with the covariance: columns_sample_marginals_fetch %.3f ms (the median of 3 of the last stage), %d counts in all" %
+          (c["nx"], c["ny"], c["nz"], kmax, chains, bins, float(np.median(t_fetch[-3:])), int(mg["hist"].sum(dtype=np.int64))))
+    for on, name in ((0, "marginals off"), (1, "marginals on")):
+        w, d, one = out[on]
+        print("%s: median of %d -- %.3f ms wall, %.3f ms in the dispersion run on the device, %.3f ms the rest; %.3f ms per sweep in one call of %d" % (name, sweeps, w, d, w - d, one, sweeps))
+    print("a sweep with the marginals costs %.3f ms more (%.2f %%); in one call %.3f ms more (%.2f %%); %d columns sampled" %
+          (out[1][0] - out[0][0], 100.0 * (out[1][0] - out[0][0]) / out[0][0], out[1][2] - out[0][2], 100.0 * (out[1][2] - out[0][2]) / out[0][2], int(kept.sum())))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "marginals":
+        arg = lambda k, default: int(sys.argv[k]) if len(sys.argv) > k else default
+        marginals_mode(arg(2, 30), arg(3, 64), arg(4, 64))
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "trace-shares":
         trace_shares(sys.argv[2])
         return
