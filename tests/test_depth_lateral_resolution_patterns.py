@@ -22,8 +22,11 @@ def test_parser_defaults_and_old_attributes():
     a = depth.parser().parse_args(["dir", "--lateral", "0.7", "--lateral-resolution", "--lateral-resolution-stride", "3", "--lateral-checkerboard", "2,2,3,0.05", "--sigma", "0.02"])
     assert (a.lateral, a.lateral_resolution, a.lateral_resolution_stride, a.lateral_checkerboard, a.sigma) == (0.7, True, 3, "2,2,3,0.05", 0.02)
     assert depth.parse_checkerboard("2,2,3,0.05") == (2, 2, 3, 0.05) and depth.parse_checkerboard("1,4,2") == (1, 4, 2, 0.1)
-    assert depth.check_flags(4, 0.5, 0.1, 0.5, 0.0, None, None, False, False, 0.3, 1e-8, 500, None, None, False, True, 2, "3,1,2") == (3, 1, 2, 0.1)
-    assert depth.check_flags(4, 0.5, 0.1, 0.5, 0.0, None, None, False, False, 0.3, 1e-8, 500, None, None) is None                 # the old call
+    old = dict(iterations=4, smooth=0.5, damp=0.1, dvmax=0.5, min_dws=0.0, sigma=None, aniso=None, radial=False, resolution=False, lateral=0.3, lateral_tol=1e-8,
+               lateral_maxit=500, radial_lateral=None, radial_lateral_aniso=None)
+    new = dict(old, radial_resolution=False, lateral_resolution=True, lateral_resolution_stride=2, lateral_checkerboard="3,1,2")
+    assert depth.check_options(depth.options_over_defaults(new)) == (None, None, (3, 1, 2, 0.1))
+    assert depth.check_options(depth.options_over_defaults(old)) == (None, None, None)              # the old call: the later options at their defaults
 
 
 @pytest.mark.parametrize("argv,message", [

@@ -79,8 +79,10 @@ def test_run_refuses_before_the_input_is_read(monkeypatch, tmp_path):
         depth.run(str(tmp_path), radial=True, resolution=True, radial_resolution=True)
     depth.check_radial_resolution(False, False, 0.2)
     depth.check_radial_resolution(True, True, None)
-    depth.check_flags(4, 0.5, 0.1, 0.5, 0.0, None, 0.2, True, False, None, 1e-8, 500, None, None)                     # the old signature still answers
-    depth.check_flags(4, 0.5, 0.1, 0.5, 0.0, 0.05, 0.2, True, False, None, 1e-8, 500, None, None, True)
+    old = dict(iterations=4, smooth=0.5, damp=0.1, dvmax=0.5, min_dws=0.0, sigma=None, aniso=0.2, radial=True, resolution=False, lateral=None, lateral_tol=1e-8,
+               lateral_maxit=500, radial_lateral=None, radial_lateral_aniso=None)
+    depth.check_options(depth.options_over_defaults(old))                            # the old call still answers: the later options at their defaults
+    depth.check_options(depth.options_over_defaults(dict(old, sigma=0.05, radial_resolution=True)))
 
 
 def test_files_round_trip(tmp_path, taipei):
