@@ -4,6 +4,7 @@
 // triangle of N (then L), and five short vectors -- 2.5 KB for the Taipei example (M = 8, K = 26: a CU's 160 KB hold more blocks than its
 // wave slots), 49 KB at the stage's limits (M = 63, K = 60: three columns per CU, where the triangle alone is 16 KB).
 // k_column_resolution, below it: the depth resolution of the same columns on the same factor, the same launch shape.
+// k_column_azimuthal: gc(z), gs(z) from the maps' 2 psi terms on that factor, the same launch shape.
 // k_column_step_radial: the step on two models, Vsv and Vsh, 2M unknowns per column, the same launch shape.
 // k_column_resolution_radial: the resolution of that step's 2M unknowns, a block of two wavefronts per column.
 // k_lateral_* (DESIGN.md section 24): the laterally coupled step, a preconditioned conjugate-gradient loop of small launches of that shape.
@@ -16,6 +17,7 @@
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
+#include "column_azimuthal.h"
 #include "column_radial.h"
 #include "column_radial_resolution.h"
 #include "column_lateral.h"
@@ -96,6 +98,36 @@ __global__ void __launch_bounds__(64) k_column_resolution(int nx, int ny, int nz
     double tr = 0.0;
     const int f = column_resolution(in, depz, smooth, damp, w, column_resolution_t(column_lds, M, K), out, &tr, &n, (int)threadIdx.x, 64, BlockBarrier());
     if (threadIdx.x == 0) { nused[c] = n; trace[c] = tr; flag[c] = f; }
+}
+
+// k_column_azimuthal: column_azimuthal.h on every interior column, the launch shape and the column of a block as
+// above.  The work arrays of the resolution, the two right-hand sides and the two rho vectors lie in dynamic LDS:
+// column_azimuthal_doubles(M, K) doubles -- 4.6 KB for the Taipei example (M = 8, K = 26), 81 048 B at the stage's limits (M = 63, K = 60),
+// which the launcher has to ask for.  wt: the effective weights, 0 at a Love slot; Z: (M, K, ncol), launch_sen_azimuthal's; a1 / a2: (K, ncol)
+// fp32; g: (2, M, ncol), gc then gs; measures: (4, M, ncol); leverage: (K, ncol); chi2: (4, ncol); nused / flag: (ncol).
+__global__ void __launch_bounds__(64) k_column_azimuthal(int nx, int ny, int nz, int K, const float* __restrict__ obs, const float* __restrict__ wt,
+                                                        const double* __restrict__ pv, const double* __restrict__ Z, const float* __restrict__ a1,
+                                                        const float* __restrict__ a2, const float* __restrict__ depz, float smooth, float damp,
+                                                        double* __restrict__ g, double* __restrict__ measures, double* __restrict__ leverage,
+                                                        double* __restrict__ chi2, int* __restrict__ nused, int* __restrict__ flag)
+{
+    extern __shared__ double column_lds[];
+    const int M = nz - 1;
+    const long long ncol = (long long)nx * ny, c = block_column(nx, ny);
+    if (c < 0) return;
+    ColumnAziIn in;
+    column_in(in.col, M, K, c, ncol, obs, wt, pv);
+    in.col.S = Z + c;
+    in.a1 = a1 + c; in.a2 = a2 + c; in.a_stride = ncol;
+    ColumnAziOut out;
+    out.g = g + c; out.g_qstride = (long long)M * ncol; out.g_lstride = ncol;
+    out.chi2 = chi2 + c; out.chi2_stride = ncol;
+    out.res.measures = measures + c; out.res.m_qstride = (long long)M * ncol; out.res.m_jstride = ncol;
+    out.res.leverage = leverage + c; out.res.h_stride = ncol;
+    out.res.R = nullptr; out.res.r_stride = 0;
+    int n = 0;
+    const int f = column_azimuthal(in, depz, smooth, damp, column_azimuthal_work(column_lds, M, K), out, &n, (int)threadIdx.x, 64, BlockBarrier());
+    if (threadIdx.x == 0) { nused[c] = n; flag[c] = f; }
 }
 
 // k_column_step_radial: column_radial.h on every interior column of the two resident models, the launch shape and the
@@ -485,6 +517,21 @@ int launch_column_resolution(int device, int nx, int ny, int nz, int K, const fl
     if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_resolution), lds, limit_out)) return rc;
     hipLaunchKernelGGL(k_column_resolution, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_S, d_depz, smooth,
                        damp, d_measures, d_leverage, d_trace, d_R, d_nused, d_flag);
+    return 0;
+}
+
+size_t column_azimuthal_lds_bytes(int nz, int K) { return column_azimuthal_doubles(nz - 1, K) * sizeof(double); }
+
+// column_lds_opt_in's return values: nothing is launched unless 0
+int launch_column_azimuthal(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_Z,
+                            const float* d_a1, const float* d_a2, const float* d_depz, float smooth, float damp, double* d_g, double* d_measures,
+                            double* d_leverage, double* d_chi2, int* d_nused, int* d_flag, hipStream_t stream, int* limit_out)
+{
+    if (nx < 3 || ny < 3 || nz < 2 || K < 1) return 0;
+    const size_t lds = column_azimuthal_lds_bytes(nz, K);
+    if (int rc = column_lds_opt_in(device, reinterpret_cast<const void*>(&k_column_azimuthal), lds, limit_out)) return rc;
+    hipLaunchKernelGGL(k_column_azimuthal, dim3((unsigned)((nx - 2) * (ny - 2))), dim3(64), lds, stream, nx, ny, nz, K, d_obs, d_wt, d_pv, d_Z, d_a1, d_a2, d_depz,
+                       smooth, damp, d_g, d_measures, d_leverage, d_chi2, d_nused, d_flag);
     return 0;
 }
 

@@ -319,6 +319,13 @@ struct Engine {
     OwnedBuf<float> col_depz;
     int columns_resolution(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* measures, double* leverage, double* trace, double* R,
                            int* nused, int* flag);
+    // depth inversion of the maps' 2 psi terms (dsa_columns_azimuthal, k_column_azimuthal): reads what the step reads
+    // and the call's own depth factors col_Z (k_sen_azimuthal's rule; Sazi and Srow are not written), changes nothing.  col_wt gets the
+    // effective weights (0 at a Love slot); col_meas, col_lev and col_depz are shared with the plain resolution.
+    OwnedBuf<double> col_Z, col_g, col_chi4;
+    OwnedBuf<float> col_a1, col_a2;
+    int columns_azimuthal(int nmaps_in, const float* obs, const float* a1, const float* a2, const float* wt, float smooth, float damp, double* g, double* measures,
+                          double* leverage, double* chi2, int* nused, int* flag);
     int dispersion_get_model(float* vels);
     // radially anisotropic stage and step (dsa_dispersion_begin_radial, dsa_columns_step_radial, k_column_step_radial): a
     // one-model stage in every other sense that keeps a second resident model -- vels_d / h_vels hold Vsv, which the Rayleigh runs read, vsh_d /

@@ -617,6 +617,57 @@ int Engine::columns_resolution(int nmaps_in, const float* obs, const float* wt, 
     return 0;
 }
 
+// dsa_columns_azimuthal: gc(z), gs(z) of every interior column from the maps' A1, A2, on the normal matrix of the
+// resolution with section 18's depth factor in place of the combined sensitivities.  The stage is read only, as dsa_columns_resolution's: no
+// mark is cleared, vels_d, h_vels, Srow and Sazi stay.  A Love slot is a slot of weight 0: the effective weights are made here.
+int Engine::columns_azimuthal(int nmaps_in, const float* obs, const float* a1, const float* a2, const float* wt, float smooth, float damp, double* g,
+                              double* measures, double* leverage, double* chi2, int* nused, int* flag)
+{
+    const char* who = "columns_azimuthal";
+    if (int rc = columns_front(who, nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f)) return rc;
+    const int K = disp_nmaps, M = disp_nz - 1;
+    const size_t ncol = (size_t)disp_nx * disp_ny, nobs = ncol * K;
+    if (!a1 || !a2) { fail(DSA_ERR_ARGUMENT, "%s: a1 and a2 are required", who); return DSA_ERR_ARGUMENT; }
+    for (size_t q = 0; q < nobs; ++q)
+        if (!std::isfinite(a1[q]) || !std::isfinite(a2[q])) { fail(DSA_ERR_ARGUMENT, "%s: a1[%zu] or a2[%zu] is not finite", who, q, q); return DSA_ERR_ARGUMENT; }
+    if (!g || !nused || !flag) { fail(DSA_ERR_ARGUMENT, "%s: g, nused and flag are required", who); return DSA_ERR_ARGUMENT; }
+    const unsigned long long love = columns_love();
+    if (love == (K >= 64 ? ~0ull : (1ull << K) - 1ull)) { fail(DSA_ERR_STATE, "%s: none of the %d slots is a Rayleigh slot, the 2 psi terms of Love waves are not inverted", who, K); return DSA_ERR_STATE; }
+    std::vector<float> weff(nobs);
+    for (int k = 0; k < K; ++k)
+        for (size_t c = 0; c < ncol; ++c) weff[(size_t)k * ncol + c] = ((love >> k) & 1ull) ? 0.0f : (wt ? wt[(size_t)k * ncol + c] : 1.0f);
+    HIP_TRY(this, hipSetDevice(device));
+    if (ensure(col_obs, nobs) || ensure(col_wt, nobs) || ensure(col_a1, nobs) || ensure(col_a2, nobs) || ensure(col_Z, ncol * K * M) || ensure(col_depz, (size_t)disp_nz) ||
+        ensure(col_g, 2 * ncol * M) || ensure(col_meas, 4 * ncol * M) || ensure(col_lev, nobs) || ensure(col_chi4, 4 * ncol) || ensure(col_nused, ncol) ||
+        ensure(col_flag, ncol)) return status;
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_wt.p, weff.data(), nobs * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_a1.p, a1, nobs * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_a2.p, a2, nobs * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_depz.p, h_depz.data(), (size_t)disp_nz * 4, hipMemcpyHostToDevice, stream));
+    // (the outer ring of columns reports zeros: the kernel runs on the interior)
+    HIP_TRY(this, hipMemsetAsync(col_g.p, 0, 2 * ncol * M * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_meas.p, 0, 4 * ncol * M * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_lev.p, 0, nobs * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_chi4.p, 0, 4 * ncol * 8, stream));
+    HIP_TRY(this, hipMemsetAsync(col_nused.p, 0, ncol * 4, stream));
+    HIP_TRY(this, hipMemsetAsync(col_flag.p, 0, ncol * 4, stream));
+    launch_sen_azimuthal((int)ncol, K, disp_nz, vels_d.p, sen_vs.p, col_Z.p, stream);
+    int limit = 0;
+    const int rc = launch_column_azimuthal(device, disp_nx, disp_ny, disp_nz, K, col_obs.p, col_wt.p, pvstore.p, col_Z.p, col_a1.p, col_a2.p, col_depz.p, smooth, damp,
+                                           col_g.p, col_meas.p, col_lev.p, col_chi4.p, col_nused.p, col_flag.p, stream, &limit);
+    if (rc) return columns_lds_refusal(who, rc, M, column_azimuthal_lds_bytes(disp_nz, K), limit);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(g, col_g.p, 2 * ncol * M * 8, hipMemcpyDeviceToHost, stream));
+    if (measures) HIP_TRY(this, hipMemcpyAsync(measures, col_meas.p, 4 * ncol * M * 8, hipMemcpyDeviceToHost, stream));
+    if (leverage) HIP_TRY(this, hipMemcpyAsync(leverage, col_lev.p, nobs * 8, hipMemcpyDeviceToHost, stream));
+    if (chi2) HIP_TRY(this, hipMemcpyAsync(chi2, col_chi4.p, 4 * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(nused, col_nused.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(flag, col_flag.p, ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
 int Engine::dispersion_get_model(float* vels)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model: call dsa_dispersion_begin first"); return DSA_ERR_STATE; }
@@ -2742,6 +2793,13 @@ int dsa_columns_resolution(dsa_engine* e, int nmaps, const float* obs, const flo
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_resolution(nmaps, obs, wt, smooth, damp, measures, leverage, trace, R, nused, flag);
+}
+
+int dsa_columns_azimuthal(dsa_engine* e, int nmaps, const float* obs, const float* a1, const float* a2, const float* wt, float smooth, float damp, double* g,
+                          double* measures, double* leverage, double* chi2, int* nused, int* flag)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_azimuthal(nmaps, obs, a1, a2, wt, smooth, damp, g, measures, leverage, chi2, nused, flag);
 }
 
 int dsa_dispersion_get_model(dsa_engine* e, float* vels)

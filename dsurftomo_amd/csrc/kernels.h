@@ -323,6 +323,14 @@ size_t column_resolution_lds_bytes(int nz, int K);
 int launch_column_resolution(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_S,
                              const float* d_depz, float smooth, float damp, double* d_measures, double* d_leverage, double* d_trace, double* d_R, int* d_nused,
                              int* d_flag, hipStream_t stream, int* limit_out);
+// The depth inversion of the maps' 2 psi terms on the same columns, nothing stepped: d_wt the effective weights (0 at a
+// Love slot; null: 1); d_Z (nz - 1, K, ncol), launch_sen_azimuthal's; d_a1 / d_a2 (K, ncol) fp32; d_g (2, nz - 1, ncol): gc, then gs; d_measures
+// and d_leverage as launch_column_resolution's; d_chi2 (4, ncol): before c, before s, after c, after s; d_nused / d_flag (ncol).  Only interior
+// columns are written.  The return values and *limit_out are launch_column_resolution's; column_azimuthal_lds_bytes: the dynamic LDS of a block.
+size_t column_azimuthal_lds_bytes(int nz, int K);
+int launch_column_azimuthal(int device, int nx, int ny, int nz, int K, const float* d_obs, const float* d_wt, const double* d_pv, const double* d_Z,
+                            const float* d_a1, const float* d_a2, const float* d_depz, float smooth, float damp, double* d_g, double* d_measures,
+                            double* d_leverage, double* d_chi2, int* d_nused, int* d_flag, hipStream_t stream, int* limit_out);
 // The radially anisotropic step: the interior columns of the two (nz, ny, nx) models d_vsv and d_vsh in place.  love: bit k
 // set where slot k is a Love slot; d_Sv / d_Sh: launch_sen_combine's on the Vsv and on the Vsh model; d_dv: (2, nz - 1, ncol), the Vsv block then
 // the Vsh block; d_nused / d_chi2: (2, ncol), Rayleigh then Love; d_flag: (ncol).  Only interior columns are written.  The return values and

@@ -7,6 +7,7 @@
                                   [--sample C,SWEEPS[,BURN] [--sample-step S] [--sample-spread P] [--sample-width W] [--sample-seed N]
                                    [--sample-temperature T] [--sample-block EVERY [--sample-block-scale S]]
                                    [--sample-bins NB [--sample-quantiles P1,P2,...] [--sample-covariance]]]
+                                  [--azimuthal [--azimuthal-smooth L] [--azimuthal-damp D] [--azimuthal-sigma S]]
 
 The second step of the "two-step" method: the phase- and group-velocity maps of dsurftomo_amd.maps (<input>Maps.dat, --maps; read with
 maps.read_maps) are inverted, column by column, for the Vs model the direct inversion is compared with.  The maps' period order -- Rayleigh
@@ -119,6 +120,21 @@ correlations between its depths.  The log gives the median width of the interval
 share of a node's states in the end bins of its box -- the sign of a posterior that leans on the prior box.  NB = 0 (the default) launches
 nothing.  sample_marginal_bin, sample_marginal_mode and sample_marginal_quantile restate the rules in NumPy.
 
+--azimuthal [--azimuthal-smooth L] [--azimuthal-damp D] [--azimuthal-sigma S]: the maps file must be one of
+maps --azimuthal, whose A1(T), A2(T) of c(psi) = c0 + A1 cos 2psi + A2 sin 2psi are inverted for gc(z) = Gc/L and gs(z) = Gs/L.  After the
+last step (and the resolutions, before --sample) the runs are done once more on the final model and columns_azimuthal solves, per interior
+column and with the loop's weights, (G^T G + L^2 L^T L + D^2 I) g = G^T rho for gc (rho from A1) and gs (rho from A2), G the Rayleigh data's
+depth factor (Vs / 2) dc/dVs (Love periods are dropped), L and D defaulting to --smooth and --damp.  <input>DepthAzim.dat (write_azimuthal /
+read_azimuthal): per node above the bottom depth longitude, latitude, depth, Vs, gc, gs, the strength 50 sqrt(gc^2 + gs^2) in per cent of
+Vs, the fast axis 0.5 atan2(gs, gc) in degrees from north, R_jj, the vertical length of the point-spread function in km, sd_g = S sqrt(var),
+sd_strength = 50 sd_g and sd_axis = (90 / pi) sd_g / sqrt(gc^2 + gs^2) degrees, capped at 90 / sqrt(3) (an axis uniform on a half circle);
+S = --azimuthal-sigma in km/s or, by default, the rms of the fit's residual sqrt((chi2c + chi2s) / (2 nused)).  <input>DepthAzimFit.dat
+(write_azimuthal_fit / read_azimuthal_fit): per column longitude, latitude, the data used, the rms of (A1, A2) before and after, the flag.
+The log gives the columns solved and flagged, the rms before and after, S and where it came from, the median and largest strength, the
+share of nodes whose amplitude exceeds 2 sd_g and the median R_jj per depth.  Refused with --radial and, for the three sub-options, without
+--azimuthal; a maps file without the A1, A2 columns is refused by name.  Without the flag nothing changes.  column_azimuthal_twin is the
+NumPy twin (csrc/column_azimuthal.h is the arithmetic).
+
 column_l, column_ltl and column_step_twin restate the regulariser and the step in NumPy for the tests (csrc/column_system.h is the arithmetic
 the device runs).  Every precondition is checked before the library is loaded.  There is no CPU path.
 """
@@ -164,7 +180,7 @@ RADIAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused_r", "%d", "int"), ("nuse
 
 
 from .depth_twins import (       # the NumPy twins of the device headers, under the names callers reach them by: depth.<name>
-    SampleMarginalTwin, _radial_expand, _twin_data, _twin_factor, _twin_normal, column_l, column_lateral_resolution_twin, column_lateral_twin, column_ltl,
+    SampleMarginalTwin, _radial_expand, azimuthal_factor, column_azimuthal_twin, _twin_data, _twin_factor, _twin_normal, column_l, column_lateral_resolution_twin, column_lateral_twin, column_ltl,
     column_radial_lateral_twin, column_radial_resolution_twin, column_radial_twin, column_resolution_twin, column_sample_twin, column_shape_twin, column_step_twin,
     column_tri, lateral_sum, sample_bits, sample_block_scale, sample_box, sample_marginal_bin, sample_marginal_counts, sample_marginal_mode, sample_marginal_quantile,
     sample_marginal_twin, sample_mix, sample_neglog, sample_psi, sample_rhat, sample_rsqrt, sample_sd, sample_unit)
@@ -398,6 +414,156 @@ def resolve(eng, c, plan, obs, wt, smooth, damp, sigma, out_dir, log=print):
             (sm["trace"] + (c["nz"] - 1, "stays under 0.1 from %g km down" % sm["depth"] if sm["depth"] is not None else "is 0.1 or more at the deepest unknown")))
     log(" depth resolution: written to %s (sd for a data standard deviation of %.6f km/s), the leverages to %s" % (rpath, sigma, lpath))
     return dict(resolution=res, sigma=float(sigma), summary=sm, resolution_path=rpath, leverage_path=lpath)
+
+
+# ---- the depth inversion of the maps' 2 psi terms: the driver's side ----
+
+AZIMUTHAL_TABLE = (True, _F64("lon", "lat", "depth", "vs", "gc", "gs", "strength", "axis", "rjj", "length", "sd_g", "sd_strength", "sd_axis"))
+AZIMUTHAL_FIT_TABLE = (True, _F64("lon", "lat") + (("nused", "%d", "int"),) + _F64("rms_before", "rms_after") + (("flag", "%d", "int"),))
+SD_AXIS_CAP = 90.0 / math.sqrt(3.0)                 # the sd in degrees of an axis uniform on a half circle
+
+
+def check_azimuthal(azimuthal=False, radial=False, smooth=None, damp=None, sigma=None):
+    """what --azimuthal and its three sub-options ask, before the library is loaded (ValueError)"""
+    if not azimuthal:
+        for name, v in (("--azimuthal-smooth", smooth), ("--azimuthal-damp", damp), ("--azimuthal-sigma", sigma)):
+            if v is not None:
+                raise ValueError("%s needs --azimuthal" % name)
+        return
+    if radial:
+        raise ValueError("--azimuthal and --radial exclude each other: the 2 psi terms are not inverted on the radial stage")
+    if smooth is not None and not (np.isfinite(smooth) and smooth >= 0):
+        raise ValueError("--azimuthal-smooth must be finite and >= 0, not %r" % (smooth,))
+    for name, v in (("--azimuthal-damp", damp), ("--azimuthal-sigma", sigma)):
+        if v is not None and not (np.isfinite(v) and v > 0):
+            raise ValueError("%s must be finite and > 0, not %r" % (name, v))
+
+
+def maps_to_azimuthal(rows, c):
+    """The A1, A2 columns of <input>Maps.dat (maps.read_maps of a file maps --azimuthal wrote) in maps_to_obs's layout: (a1, a2), both
+    (nmaps, ny * nx) fp32, 0 on the outer ring.  ValueError as maps_to_obs, and when the rows carry no a1 / a2."""
+    nx, ny = c["nx"], c["ny"]
+    nvx, nvz = nx - 2, ny - 2
+    layer = nvx * nvz
+    per = maps.period_list(c)
+    if len(rows) != len(per) * layer:
+        raise ValueError("depth: the maps file holds %d lines, %d periods of %d x %d interior vertices need %d" % (len(rows), len(per), nvx, nvz, len(per) * layer))
+    if any("a1" not in r or "a2" not in r for r in rows):
+        raise ValueError("depth: the maps file has no a1 / a2 columns; write it with maps --azimuthal")
+    out = np.zeros((2, len(per), ny, nx), np.float32)
+    for m, (wave, kind, t) in enumerate(per):
+        block = rows[m * layer:(m + 1) * layer]
+        if any((r["wave"], r["kind"], r["period"]) != (wave, kind, t) for r in block):
+            raise ValueError("depth: map %d of the maps file is not wave %d kind %d period %g of the input" % (m, wave, kind, t))
+        for q, key in enumerate(("a1", "a2")):
+            out[q, m, 1:-1, 1:-1] = np.array([r[key] for r in block]).reshape(nvz, nvx)
+    return out[0].reshape(len(per), ny * nx), out[1].reshape(len(per), ny * nx)
+
+
+def azimuthal_sigma(chi2, nused):
+    """the rms of the weighted residual of the fit of A1 and A2 together: sqrt((chi2c_after + chi2s_after) / (2 sum nused)), 0 without data"""
+    chi2 = np.asarray(chi2, np.float64)
+    return rms_of(chi2[2] + chi2[3], 2 * np.asarray(nused, np.int64))
+
+
+def azimuthal_sd_axis(gc, gs, sd_g):
+    """the standard deviation of the fast axis in degrees, (90 / pi) sd_g / sqrt(gc^2 + gs^2), capped at SD_AXIS_CAP -- also where the
+    amplitude is 0"""
+    amp = np.hypot(np.asarray(gc, np.float64), np.asarray(gs, np.float64))
+    sd = np.full(amp.shape, SD_AXIS_CAP)
+    np.divide((90.0 / math.pi) * np.asarray(sd_g, np.float64), amp, out=sd, where=amp > 0)
+    return np.minimum(sd, SD_AXIS_CAP)
+
+
+def azimuthal_columns(res, sigma):
+    """The node figures of DepthAzim.dat from columns_azimuthal's result and the standard deviation sigma of the weighted A1, A2: dict(strength,
+    axis, rjj, length, sd_g, sd_strength, sd_axis), each (nz - 1, ny * nx).  Every root and atan2 is taken here."""
+    from .analyses.azimuthal import azimuthal_axis, azimuthal_strength
+    gc, gs, m = np.asarray(res["gc"], np.float64), np.asarray(res["gs"], np.float64), np.asarray(res["measures"], np.float64)
+    sd_g = float(sigma) * np.sqrt(m[3])
+    return dict(strength=azimuthal_strength(gc, gs), axis=azimuthal_axis(gc, gs), rjj=m[0], length=psf_length(m[1], m[2]), sd_g=sd_g, sd_strength=50.0 * sd_g,
+                sd_axis=azimuthal_sd_axis(gc, gs, sd_g))
+
+
+def write_azimuthal(path, c, vels, res, sigma):
+    """<input>DepthAzim.dat: per node above the bottom depth (depth slowest, then j, then i) longitude, latitude, depth, Vs, gc, gs, the
+    strength 50 sqrt(gc^2 + gs^2) in per cent of Vs, the fast axis 0.5 atan2(gs, gc) in degrees from north, R_jj, the vertical length of the
+    point-spread function in km, sd_g = sigma sqrt(var), sd_strength = 50 sd_g and sd_axis (azimuthal_sd_axis)"""
+    nx, ny, nz = c["nx"], c["ny"], c["nz"]
+    v = np.asarray(vels, np.float64).reshape(nz, ny * nx)
+    col = azimuthal_columns(res, sigma)
+    io.write_table(path, AZIMUTHAL_TABLE, [dict(row, vs=v[k, q], gc=float(res["gc"][k, q]), gs=float(res["gs"][k, q]), **{n: float(a[k, q]) for n, a in col.items()})
+                                           for k, q, row in _node_rows(c, nz - 1)])
+
+
+def read_azimuthal(path):
+    return io.read_table(path, AZIMUTHAL_TABLE)
+
+
+def azimuthal_column_rms(chi2, nused):
+    """per column the rms of (A1, A2) before and after: sqrt((chi2c + chi2s) / (2 nused)), 0 without data.  Returns (before, after)."""
+    chi2 = np.asarray(chi2, np.float64); n = 2.0 * np.asarray(nused, np.float64)
+    rms = lambda s: np.sqrt(np.divide(s, n, out=np.zeros(n.shape), where=n > 0))
+    return rms(chi2[0] + chi2[1]), rms(chi2[2] + chi2[3])
+
+
+def write_azimuthal_fit(path, c, res):
+    """<input>DepthAzimFit.dat: per column (j, then i) longitude, latitude, the data used, the rms of (A1, A2) before and after, the flag"""
+    r0, r1 = azimuthal_column_rms(res["chi2"], res["nused"])
+    io.write_table(path, AZIMUTHAL_FIT_TABLE, [dict(row, nused=int(res["nused"][q]), rms_before=float(r0[q]), rms_after=float(r1[q]), flag=int(res["flag"][q]))
+                                               for q, row in _column_rows(c)])
+
+
+def read_azimuthal_fit(path):
+    return io.read_table(path, AZIMUTHAL_FIT_TABLE)
+
+
+def azimuthal_summary(c, res, sigma):
+    """what the log says of columns_azimuthal's result: resolution_summary's entries (the trace is the sum of the R_jj), rms_before,
+    rms_after over all columns, and over the nodes of the interior columns that are not flagged the median and the largest strength, the
+    share whose amplitude exceeds 2 sd_g and the median R_jj per depth (None without such a column)"""
+    m = np.asarray(res["measures"], np.float64)
+    sm = resolution_summary(c, dict(res, trace=m[0].sum(axis=0)))
+    chi2 = np.asarray(res["chi2"], np.float64)
+    sm.update(rms_before=rms_of(chi2[0] + chi2[1], 2 * np.asarray(res["nused"], np.int64)), rms_after=azimuthal_sigma(chi2, res["nused"]), strength=None,
+              significant=None, rjj=None)
+    nx, ny = c["nx"], c["ny"]
+    inner = np.zeros((ny, nx), bool); inner[1:-1, 1:-1] = True
+    ok = inner.ravel() & (np.asarray(res["flag"]).reshape(ny * nx) == 0)
+    if ok.any():
+        col = azimuthal_columns(res, sigma)
+        st = col["strength"][:, ok]
+        sm["strength"] = (float(np.median(st)), float(st.max()))
+        sm["significant"] = float((st / 50.0 > 2.0 * col["sd_g"][:, ok]).mean())
+        sm["rjj"] = [float(x) for x in np.median(m[0][:, ok], axis=1)]
+    return sm
+
+
+def run_azimuthal(eng, c, plan, vels, obs, a1, a2, wt, smooth, damp, sigma, out_dir, log=print):
+    """--azimuthal on an engine whose stage holds the final model vels: the runs of plan once more, columns_azimuthal, the two files, the log.
+    sigma: the standard deviation of the weighted A1, A2, or None for the rms of the fit's residual.  Returns dict(azimuthal: the call's
+    result, azimuthal_sigma, azimuthal_summary, azimuthal_path, azimuthal_fit_path)."""
+    for wave, kind, t, first in plan:
+        eng.dispersion_run(wave, kind, t, True, first, first)
+    res = eng.columns_azimuthal(obs, a1, a2, wt, smooth, damp)
+    own = sigma is None
+    sigma = azimuthal_sigma(res["chi2"], res["nused"]) if own else float(sigma)
+    apath = os.path.join(out_dir, "DSurfTomo.inDepthAzim.dat")
+    fpath = os.path.join(out_dir, "DSurfTomo.inDepthAzimFit.dat")
+    write_azimuthal(apath, c, vels, res, sigma)
+    write_azimuthal_fit(fpath, c, res)
+    sm = azimuthal_summary(c, res, sigma)
+    log(" depth azimuthal: %d columns solved, %d flagged (%d not positive definite, %d without data), smooth %g damp %g" %
+        (sm["columns"], sm["flagged1"] + sm["flagged2"], sm["flagged1"], sm["flagged2"], smooth, damp))
+    log(" depth azimuthal: rms of (A1, A2) %.6f km/s before, %.6f km/s after; sigma %.6f km/s (%s)" %
+        (sm["rms_before"], sm["rms_after"], sigma, "the rms of the fit's residual" if own else "--azimuthal-sigma"))
+    if sm["strength"] is not None:
+        log(" depth azimuthal: strength median %.4f %%, largest %.4f %% of Vs; the amplitude exceeds 2 sd_g at %.1f %% of the nodes" %
+            (sm["strength"] + (100.0 * sm["significant"],)))
+        log(" depth azimuthal: median R_jj per depth %s; the median R_jj %s" %
+            (" ".join("%.4f" % x for x in sm["rjj"]), "stays under 0.1 from %g km down" % sm["depth"] if sm["depth"] is not None else "is 0.1 or more at the deepest unknown"))
+    log(" depth azimuthal: written to %s, the fit to %s" % (apath, fpath))
+    return dict(azimuthal=res, azimuthal_sigma=sigma, azimuthal_summary=sm, azimuthal_path=apath, azimuthal_fit_path=fpath)
 
 
 # ---- the Monte-Carlo depth inversion (DESIGN.md section 29): the driver's side ----
@@ -1111,6 +1277,10 @@ OPTIONS = (
     ("--lateral-resolution", "lateral_resolution", False, dict(action="store_true", help="with --lateral: after the last step write the point-spread lengths, own shares and standard deviations of the coupled system (--sigma applies)")),
     ("--lateral-resolution-stride", "lateral_resolution_stride", 1, dict(type=int, metavar="N", help="with --lateral-resolution: resolve every N-th unknown (default 1: all)")),
     ("--lateral-checkerboard", "lateral_checkerboard", None, dict(metavar="NX,NY,NZ[,AMP]", help="with --lateral-resolution: recover a checkerboard of NX x NY x NZ blocks of amplitude AMP km/s (default %g)" % DEFAULT_CHECKER_AMP)),
+    ("--azimuthal", "azimuthal", False, dict(action="store_true", help="after the last step invert the maps' 2psi terms A1(T), A2(T) (maps --azimuthal) of every column for gc(z), gs(z): strength, fast axis, resolution and standard deviations of the final model")),
+    ("--azimuthal-smooth", "azimuthal_smooth", None, dict(type=float, metavar="L", help="with --azimuthal: weight of the depth Laplacian on gc and gs, >= 0 (default: --smooth)")),
+    ("--azimuthal-damp", "azimuthal_damp", None, dict(type=float, metavar="D", help="with --azimuthal: damping of gc and gs, > 0 (default: --damp)")),
+    ("--azimuthal-sigma", "azimuthal_sigma", None, dict(type=float, metavar="S", help="with --azimuthal: standard deviation of the A1, A2 values in km/s for the sd columns (default: the rms of the fit's residual)")),
     ("--sample", "sample", None, dict(metavar="C,SWEEPS[,BURN]", help="after the last step sample the posterior of every column with C Metropolis chains for SWEEPS sweeps, the first BURN (default SWEEPS / 2) left out (--sigma applies)")),
     ("--sample-step", "sample_step", DEFAULT_SAMPLE_STEP, dict(type=float, metavar="S", help="with --sample: half width of the single-node proposal in km/s (default %g)" % DEFAULT_SAMPLE_STEP)),
     ("--sample-spread", "sample_spread", DEFAULT_SAMPLE_SPREAD, dict(type=float, metavar="P", help="with --sample: half width of the scatter of the chains' starts in km/s (default %g)" % DEFAULT_SAMPLE_SPREAD)),
@@ -1138,7 +1308,7 @@ def options_over_defaults(options):
 def check_options(o):
     """Every precondition on the options o (options_over_defaults'), in the one order run() and main() both refuse in (ValueError), before the
     library is loaded: --sample's, the marginals', then the loop's (aniso only with radial; --lateral-tol and --lateral-maxit only with a
-    coupling), --lateral's, --radial's, --radial-lateral's, --radial-resolution's, --lateral-resolution's.  Returns (parse_sample's tuple or
+    coupling), --lateral's, --radial's, --radial-lateral's, --radial-resolution's, --lateral-resolution's, --azimuthal's.  Returns (parse_sample's tuple or
     None, check_marginals' tuple or None, the parsed --lateral-checkerboard or None)."""
     sampling = check_sample(o.sample, o.radial, o.lateral, o.sample_step, o.sample_spread, o.sample_width, o.sample_temperature, o.sample_seed, o.sample_block,
                             o.sample_block_scale)
@@ -1152,6 +1322,7 @@ def check_options(o):
     check_radial_lateral(o.radial_lateral, o.radial_lateral_aniso, o.radial, o.lateral, o.resolution)
     check_radial_resolution(o.radial_resolution, o.radial, o.radial_lateral)
     checker = check_lateral_resolution(o.lateral_resolution, o.lateral_resolution_stride, o.lateral_checkerboard, o.lateral, o.radial)
+    check_azimuthal(o.azimuthal, o.radial, o.azimuthal_smooth, o.azimuthal_damp, o.azimuthal_sigma)
     return sampling, marginals, checker
 
 
@@ -1163,12 +1334,17 @@ def stage_sigma(label, sigma, history, log):
 
 
 # the stages after the loop, in the order they run: (the label of their log lines, the path: radial or not, wanted(o), call(r, o, sigma) -> the
-# entries the result gains); r: what run() holds (eng, c, plan, obs, wt, out_dir, log, out: the loop's result, sampling, marginals, checker)
+# entries the result gains); r: what run() holds (eng, c, plan, obs, wt, out_dir, log, out: the loop's result, sampling, marginals, checker,
+# azi: (a1, a2) or None).  A label of None: the stage has a sigma of its own and stage_sigma is not asked (sigma None).  "depth sample" leaves
+# the stage in sample mode, which refuses the column calls: it comes last on its path.
 STAGES = (
     ("depth resolution", False, lambda o: o.resolution, lambda r, o, sigma: resolve(r.eng, r.c, r.plan, r.obs, r.wt, o.smooth, o.damp, sigma, r.out_dir, r.log)),
     ("depth lateral resolution", False, lambda o: o.lateral_resolution,
      lambda r, o, sigma: resolve_lateral(r.eng, r.c, r.plan, r.obs, r.wt, o.smooth, o.damp, o.lateral, o.lateral_tol, o.lateral_maxit, sigma, r.out_dir,
                                          o.lateral_resolution_stride, r.checker, r.log)),
+    (None, False, lambda o: o.azimuthal,
+     lambda r, o, sigma: run_azimuthal(r.eng, r.c, r.plan, r.out["vels"], r.obs, r.azi[0], r.azi[1], r.wt, o.smooth if o.azimuthal_smooth is None else o.azimuthal_smooth,
+                                       o.damp if o.azimuthal_damp is None else o.azimuthal_damp, o.azimuthal_sigma, r.out_dir, r.log)),
     ("depth sample", False, lambda o: o.sample is not None,
      lambda r, o, sigma: run_sample(r.eng, r.c, r.plan, r.out["vels"], r.obs, r.wt, o.smooth, sigma, r.sampling, r.out_dir, o.sample_step, o.sample_spread, o.sample_width,
                                     o.sample_seed, o.sample_temperature, r.log, o.sample_block, o.sample_block_scale, o.damp, r.marginals)),
@@ -1190,7 +1366,10 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
     the loop (and the resolution) run_sample's entries are added to the first item (DepthPosterior.dat and DepthPosteriorFit.dat beside the
     two files); sigma as with resolution; sample_block (EVERY > 0) makes every EVERY-th sweep a block proposal of scale sample_block_scale
     (None: sample_block_scale(nz - 1, temperature)); sample_bins (2 .. 256) adds the posterior marginals at the levels sample_quantiles
-    ("P1,P2,...") and, with sample_covariance, the correlations between a column's depths (run_sample's three files).  The radial path writes
+    ("P1,P2,...") and, with sample_covariance, the correlations between a column's depths (run_sample's three files).  With azimuthal: after
+    the resolutions and before the sample stage run_azimuthal's entries are added to the first item (DepthAzim.dat and DepthAzimFit.dat beside
+    the two files); azimuthal_smooth / azimuthal_damp None: smooth / damp; azimuthal_sigma None: the rms of the fit's residual; a maps file
+    without a1 / a2 columns is a ValueError naming it, before the library is loaded.  The radial path writes
     its two files in run_radial, before its stage; the isotropic path writes Depth.dat and DepthFit.dat after its stages, the engine closed."""
     o = options_over_defaults(options)
     sampling, marginals, checker = check_options(o)
@@ -1198,14 +1377,18 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
     if o.radial:
         check_radial(c)
     maps_file = os.path.join(out_dir, "DSurfTomo.inMaps.dat") if maps_file is None else maps_file
-    obs, dws = maps_to_obs(maps.read_maps(maps_file), c)
+    rows = maps.read_maps(maps_file)
+    obs, dws = maps_to_obs(rows, c)
+    if o.azimuthal and not (rows and "a1" in rows[0] and "a2" in rows[0]):
+        raise ValueError("depth: --azimuthal needs the a1 and a2 columns, which %s does not have; write it with maps --azimuthal" % maps_file)
+    azi = maps_to_azimuthal(rows, c) if o.azimuthal else None
     plan = slot_plan(c)
     kmax = c["kmax"]
     if not plan or kmax > 60:
         raise ValueError("depth: %d periods; the step takes 1 to 60" % kmax)
     wt = dws_weights(dws, o.min_dws) if o.min_dws > 0 else None
     from .engine import Engine
-    r = types.SimpleNamespace(eng=Engine(0), c=c, plan=plan, obs=obs, wt=wt, out_dir=out_dir, log=log, sampling=sampling, marginals=marginals, checker=checker)
+    r = types.SimpleNamespace(eng=Engine(0), c=c, plan=plan, obs=obs, wt=wt, out_dir=out_dir, log=log, sampling=sampling, marginals=marginals, checker=checker, azi=azi)
     try:
         if o.radial:
             r.out, path, fit = run_radial(r.eng, c, plan, obs, wt, o.iterations, o.smooth, o.damp, o.aniso, o.dvmax, out_dir, log, o.radial_lateral, o.radial_lateral_aniso,
@@ -1216,7 +1399,7 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
             r.out["vels"] = r.eng.dispersion_get_model()
         for label, radial, wanted, call in STAGES:
             if radial == o.radial and wanted(o):
-                r.out.update(call(r, o, stage_sigma(label, o.sigma, r.out["history"], log)))
+                r.out.update(call(r, o, None if label is None else stage_sigma(label, o.sigma, r.out["history"], log)))
     finally:
         r.eng.close()
     if not o.radial:

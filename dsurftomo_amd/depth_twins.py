@@ -1,5 +1,5 @@
-"""The NumPy twins of the depth inversion's device headers (dsurftomo_amd/depth.py is the driver; DESIGN.md sections 21 to 33): the column steps,
-their resolutions, the Monte-Carlo sampler and its marginals restated operation by operation for the tests, the tools and the golden
+"""The NumPy twins of the depth inversion's device headers (dsurftomo_amd/depth.py is the driver; DESIGN.md sections 21 to 33 and 35): the column steps,
+their resolutions, the Monte-Carlo sampler and its marginals and the inversion of the maps' 2 psi terms restated operation by operation for the tests, the tools and the golden
 scripts.  The driver takes a handful of small rules from here (sample_block_scale, sample_box, sample_rhat, sample_sd); callers reach the
 twins as depth.<name>, which imports them back.  csrc/column_*.h is the arithmetic the device runs.  Nothing here touches the GPU."""
 import math
@@ -669,6 +669,69 @@ def column_resolution_twin(obs, wt, pv, S, depz, smooth, damp, n_override=None):
         T2 = np.linalg.pinv(A)[:, :K].T.copy()
         T2[~used] = 0.0
         out["other"] = dict(T=T2, **_resolution_measures(T2, G, used, depz))
+    return out
+
+
+def azimuthal_factor(svs, vels):
+    """The depth factor of the gc / gs unknowns with k_sen_azimuthal's roundings (DESIGN.md sections 18 and 35): Z = svs (double)(0.5f v), one
+    fp32 product and one fp64 product.  svs: (nz, K, ncol) fp64, dispersion_fetch's d c / d Vs; vels: the fp32 model, (nz, ...) with ncol
+    values per depth.  Returns Z (nz - 1, K, ncol) fp64: the bottom depth carries no unknown."""
+    svs = np.asarray(svs, np.float64)
+    v = np.asarray(vels, np.float32).reshape(np.shape(vels)[0], -1)
+    M = v.shape[0] - 1
+    half = (np.float32(0.5) * v[:M]).astype(np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return svs[:M] * half[:, None, :]
+
+
+def column_azimuthal_twin(obs, a1, a2, wt, pv, Z, love, depz, smooth, damp, n_override=None):
+    """dsa_columns_azimuthal on one column in NumPy (csrc/column_azimuthal.h).  obs (the c0 values), wt, pv as column_step_twin's; a1, a2 (K)
+    fp32, the 2 psi terms; Z (K, M) fp64, azimuthal_factor's rows of this column; love (K) bool or None: a Love slot is a slot of weight 0.
+    The operator is column_resolution_twin's on (obs, the effective weights, pv, Z); rhoc = a a1, rhos = a a2, bc = G^T rhoc, bs = G^T rhos
+    over the used k ascending; gc and gs through the header's L D L^T order; f = G g with l ascending.  Returns dict(gc, gs (M); chi2 (4):
+    before c, before s, after c, after s; measures (4, M); leverage (K); nused; flag; T (K, M); R (M, M); other) -- every array 0 where the
+    flag is 1 or 2.  other: gc, gs and chi2 by another algorithm, numpy.linalg.lstsq on the stacked [diag(a) Z; smooth L; damp I], with
+    column_resolution_twin's second measures and leverage -- for the size of the rounding error; None where the column is flagged or N is
+    overridden."""
+    f = np.float32
+    obs = np.asarray(obs, f); pv = np.asarray(pv, np.float64); Z = np.asarray(Z, np.float64)
+    K, M = Z.shape
+    wt = np.ones(K, f) if wt is None else np.asarray(wt, f)
+    if love is not None:
+        wt = np.where(np.asarray(love, bool), f(0.0), wt).astype(f)
+    res = column_resolution_twin(obs, wt, pv, Z, depz, smooth, damp, n_override)
+    out = dict(gc=np.zeros(M), gs=np.zeros(M), chi2=np.zeros(4), measures=res["measures"], leverage=res["leverage"], nused=res["nused"], flag=res["flag"],
+               T=res["T"], R=res["R"], other=None)
+    if out["flag"]:
+        return out
+    used, _, _, G = _twin_data(obs, wt, pv, Z)
+    a = wt.astype(np.float64)
+    rho = [np.where(used, a * np.where(used, np.asarray(x, f), f(0.0)).astype(np.float64), 0.0) for x in (a1, a2)]
+    lam2, mu2 = float(f(smooth)) * float(f(smooth)), float(f(damp)) * float(f(damp))
+    rows = np.flatnonzero(used)
+
+    def misfit(r):
+        s = 0.0
+        for k in rows:
+            s = s + r[k] * r[k]
+        return s
+
+    def fit(g):
+        return np.array([_chain_dot(G[k], g) if used[k] else 0.0 for k in range(K)])
+
+    g, chi2 = [], [misfit(rho[0]), misfit(rho[1]), 0.0, 0.0]
+    for q in range(2):
+        N, b = _twin_normal(G, used, rho[q], lam2, mu2)
+        if n_override is not None:
+            N = np.array(n_override, np.float64)
+        g.append(_twin_solve(*_twin_factor(N), b))
+        chi2[2 + q] = misfit(rho[q] - fit(g[q]))
+    out.update(gc=g[0], gs=g[1], chi2=np.array(chi2))
+    if n_override is None:
+        A = np.vstack([G[used], float(f(smooth)) * column_l(M), float(f(damp)) * np.eye(M)])
+        g2 = [np.linalg.lstsq(A, np.concatenate([rho[q][used], np.zeros(A.shape[0] - rows.size)]), rcond=None)[0] for q in range(2)]
+        out["other"] = dict(gc=g2[0], gs=g2[1], chi2=np.array(chi2[:2] + [misfit(rho[q] - fit(g2[q])) for q in range(2)]),
+                            measures=res["other"]["measures"], leverage=res["other"]["leverage"])
     return out
 
 

@@ -105,7 +105,8 @@ def declare_solvers(L):
     L.dsa_columns_step.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 5 + [_vp] * 4
     L.dsa_dispersion_get_model.argtypes = [_vp, _vp]
     L.dsa_columns_resolution.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 6
-    L.dsa_dispersion_begin_radial.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _i32]
+    L.dsa_columns_azimuthal.argtypes = [_vp, _i32] + [_vp] * 4 + [_f32] * 2 + [_vp] * 6
+    L.dsa_dispersion_begin_radial.argtypes =[_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _i32]
     L.dsa_columns_step_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 6 + [_vp] * 4
     L.dsa_dispersion_get_model_radial.argtypes = [_vp, _vp, _vp]
     L.dsa_columns_resolution_radial.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 3 + [_vp] * 7
@@ -468,6 +469,24 @@ class Engine:
             out["R"] = np.zeros((nz - 1, nz - 1, ncol))
         self._check(self._L.dsa_columns_resolution(self._h, nmaps, _p(obs), _p(wt), float(smooth), float(damp), _p(out["measures"]), _p(out["leverage"]),
                                                    _p(out["trace"]), _p(out["R"]) if full else None, _p(out["nused"]), _p(out["flag"])))
+        return out
+
+    def columns_azimuthal(self, obs, a1, a2, wt, smooth, damp):
+        """dsa_columns_azimuthal on the state columns_resolution needs, which it leaves as it is: obs (the c0 maps) and wt as columns_step's,
+        a1 and a2 (the maps' 2 psi terms) in obs's layout.  Returns dict(gc, gs (nz - 1, ny * nx); measures (4, nz - 1, ny * nx): R_jj, m1, m2,
+        var, one set for both components; leverage (nmaps, ny * nx), 0 at Love and unused slots; chi2 (4, ny * nx): before c, before s, after
+        c, after s; nused, flag (ny * nx) int32), all else fp64.  ValueError as columns_step, and when a1 or a2 differ from obs in size."""
+        nmaps, obs, wt = self._columns_in("columns_azimuthal", obs, wt)[:3]
+        a1, a2 = np.ascontiguousarray(a1, np.float32), np.ascontiguousarray(a2, np.float32)
+        if a1.size != obs.size or a2.size != obs.size:
+            raise ValueError("columns_azimuthal: a1 holds %d values, a2 %d, obs %d" % (a1.size, a2.size, obs.size))
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        g = np.zeros((2, nz - 1, ncol))
+        out = dict(gc=g[0], gs=g[1], measures=np.zeros((4, nz - 1, ncol)), leverage=np.zeros((nmaps, ncol)), chi2=np.zeros((4, ncol)),
+                   nused=np.zeros(ncol, np.int32), flag=np.zeros(ncol, np.int32))
+        self._check(self._L.dsa_columns_azimuthal(self._h, nmaps, _p(obs), _p(a1), _p(a2), _p(wt), float(smooth), float(damp), _p(g), _p(out["measures"]),
+                                                  _p(out["leverage"]), _p(out["chi2"]), _p(out["nused"]), _p(out["flag"])))
         return out
 
     def dispersion_get_model(self):

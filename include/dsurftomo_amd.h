@@ -480,6 +480,31 @@ int dsa_dispersion_get_model(dsa_engine* e, float* vels);
 int dsa_columns_resolution(dsa_engine* e, int nmaps, const float* obs, const float* wt, float smooth, float damp, double* measures,
                            double* leverage, double* trace, double* R, int* nused, int* flag);
 
+/* dsa_columns_azimuthal: the depth inversion of the maps' 2 psi terms, gc(z) = Gc/L and gs(z) = Gs/L of every interior column from the
+ * A1(T), A2(T) of c(psi) = c0 + A1 cos 2 psi + A2 sin 2 psi that the map step leaves per period (extension).  The state and obs
+ * (the c0 maps), wt, smooth, damp are dsa_columns_resolution's, with its rules and refusals; a1, a2: obs's layout and type.  Slot k is a
+ * Rayleigh slot iff it was run with iwave != 1 (phase and group); a Love slot is a slot of weight 0.  Datum k of a column is used iff slot k
+ * is a Rayleigh slot and dsa_columns_step would use it (wt > 0, obs > 0, pv > 0); the a1, a2 of any other datum are not read.  Per column,
+ * with M = nz-1 unknowns per component, Z_kl = sen_vs_kl (double)(0.5f v_l) the depth factor of the gc / gs entries of dsa_solve_rows_azimuthal (only
+ * the Vs kernel), a = (double)wt, g_kl = a Z_kl, rhoc = a (double)a1, rhos = a (double)a2:
+ *   (G^T G + smooth^2 L^T L + damp^2 I) gc = G^T rhoc,  the same matrix for gs and rhos,
+ * one L D L^T factorisation and the step's substitutions for both; everything fp64, every sum sequential from 0.0 over the used data ascending.
+ *   g         2*(nz-1)*nx*ny doubles: gc, then gs, each (depth, column).  Required.
+ *   measures  NULL, or 4*(nz-1)*nx*ny doubles as dsa_columns_resolution's (R_jj, m1, m2, var) of this operator: gc and gs share it, so one
+ *             set serves both; var_j is the variance of gc_j and of gs_j for unit variance of the weighted a1 and a2, which are uncorrelated
+ *   leverage  NULL, or nmaps*nx*ny: h_k as dsa_columns_resolution's; 0 for a datum not used and for a Love slot
+ *   chi2      NULL, or 4*nx*ny: sum rhoc^2, sum rhos^2 before, then sum (rhoc - G gc)^2, sum (rhos - G gs)^2 after
+ *   nused, flag  nx*ny, required: as dsa_columns_step's (flag 1: a pivot not finite or <= 0; flag 2: no datum used)
+ * A column with flag 1 or 2 and the outer ring of columns have 0.0 everywhere.  No root and no atan2 is taken: strength and fast axis are
+ * the caller's.  Nothing is changed: the model, the marks of the maps and slots and the Frechet rows' sensitivities stay, so a
+ * dsa_columns_step after the call gives the bits it would have given without it.
+ * Errors, all but the last found before the device is touched: DSA_ERR_STATE and DSA_ERR_ARGUMENT as dsa_columns_resolution, in its order
+ * (a radial stage, several models and an open sample stage are DSA_ERR_STATE); then DSA_ERR_ARGUMENT for a NULL or not finite a1 / a2 and
+ * for a NULL g, nused or flag; DSA_ERR_STATE where no slot is a Rayleigh slot; DSA_ERR_DEVICE when a column's work arrays (about 79 KB at
+ * nz = 64 with 60 maps) exceed the LDS a block of the device may have or the device refuses that size. */
+int dsa_columns_azimuthal(dsa_engine* e, int nmaps, const float* obs, const float* a1, const float* a2, const float* wt, float smooth, float damp,
+                          double* g, double* measures, double* leverage, double* chi2, int* nused, int* flag);
+
 /* Radial anisotropy in the depth inversion (extension): Rayleigh waves see Vsv, Love waves see Vsh.
  * dsa_dispersion_begin_radial: dsa_dispersion_begin with two models vsv and vsh (each in its layout) on one set of depths.  The stage stays a
  * one-model stage -- depth kernels allowed, every size and limit dsa_dispersion_begin's -- that keeps Vsh resident beside Vsv: afterwards

@@ -38,7 +38,13 @@ The lateral resolution's leg: dsa_columns_resolution_late
 the averaging kernel (2 x 2 048 members) in one call, next to the first 64 of them one per call -- the wall time of the calls, `repeats`
 timed series after a warm-up one, and from them the time per member of either way.
 
-    python tools/depth_rate.py [repeats] [lateral | radial-lateral | radial-resolution | lateral-resolution]      (needs the GPU; with a name: that leg alone)
+The azimuthal leg: dsa_columns_azimuthal next to dsa_columns_resolution (without R) on the example's grid and plan
+(K = 26 Rayleigh periods, M = 8) and at the stage's limits on the 5 x 5 grid (nz = 64, K = 60, 30 of them Love slots: the one launch that
+asks for 81 048 bytes of LDS) after one set of runs, the two calls in turn -- the wall time of the whole calls, `repeats` timed pairs after
+a warm-up one.  One kernel trace of the leg holds k_column_azimuthal, k_sen_azimuthal, k_column_resolution and k_sen_combine side by side
+(trace-medians, as above).
+
+    python tools/depth_rate.py [repeats] [lateral | radial-lateral | radial-resolution | lateral-resolution | azimuthal]      (needs the GPU; with a name: that leg alone)
 """
 import os
 import sys
@@ -84,6 +90,12 @@ def main():
         return
     if "lateral-resolution" in sys.argv[2:]:
         lateral_resolution_leg(e, repeats, vel, c, depth.slot_plan(c), kmax)
+        e.close()
+        return
+    if "azimuthal" in sys.argv[2:]:
+        azimuthal_leg(e, repeats, "the example's grid", vel, c["depz"], c["minthk"], depth.slot_plan(c), kmax)
+        limits, depz, minthk, lplan, lk = limits_case()
+        azimuthal_leg(e, repeats, "the limits", limits, depz, minthk, lplan, lk)
         e.close()
         return
     if "radial-lateral" in sys.argv[2:]:
@@ -322,6 +334,32 @@ def resolution_leg(e, repeats, name, vel, depz, minthk, plan, kmax):
         print("%-20s %d x %d x %d, K = %d (runs %.1f ms): columns_resolution %s, median of %d -- %.3f ms wall; %d of %d columns resolved, trace %.3f to %.3f; all calls: %s" %
               (name, nx, ny, nz, kmax, 1e3 * (t1 - t0), "with the full R" if full else "without R", repeats, np.median(wall), int(ok.sum()), ok.size,
                out["trace"].reshape(ny, nx)[1:-1, 1:-1][ok].min(), out["trace"].reshape(ny, nx)[1:-1, 1:-1][ok].max(), " ".join("%.3f" % w for w in wall)))
+
+
+def azimuthal_leg(e, repeats, name, vel, depz, minthk, plan, kmax):
+    nz, ny, nx = vel.shape
+    e.dispersion_begin(vel, depz, minthk, kmax, kmax)
+    t0 = time.perf_counter()
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, True, first, first)
+    t1 = time.perf_counter()
+    pv = e.dispersion_fetch(0, kmax)
+    obs = np.where(pv > 0, pv, 0.0).astype(np.float32)
+    rng = np.random.default_rng(35)
+    a1 = (0.02 * obs * rng.standard_normal(obs.shape)).astype(np.float32); a2 = (0.02 * obs * rng.standard_normal(obs.shape)).astype(np.float32)
+    res, azi = [], []
+    for it in range(repeats + 1):
+        t2 = time.perf_counter()
+        e.columns_resolution(obs, None, depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP)
+        t3 = time.perf_counter()
+        out = e.columns_azimuthal(obs, a1, a2, None, depth.DEFAULT_SMOOTH, depth.DEFAULT_DAMP)
+        t4 = time.perf_counter()
+        if it:
+            res.append(1e3 * (t3 - t2)); azi.append(1e3 * (t4 - t3))
+    ok = out["flag"].reshape(ny, nx)[1:-1, 1:-1] == 0
+    print("%-20s %d x %d x %d, K = %d (runs %.1f ms), median of %d -- columns_resolution without R %.3f ms wall, columns_azimuthal %.3f ms wall; %d of %d columns solved, "
+          "%d data used; all azimuthal calls: %s" % (name, nx, ny, nz, kmax, 1e3 * (t1 - t0), repeats, np.median(res), np.median(azi), int(ok.sum()), ok.size,
+                                                      int(out["nused"].sum()), " ".join("%.3f" % w for w in azi)))
 
 
 if __name__ == "__main__":
