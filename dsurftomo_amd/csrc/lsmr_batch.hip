@@ -443,6 +443,20 @@ int build_contiguous(Engine* e, const SpmvState::Ordering& O, int nseg, long lon
     return rc;
 }
 
+}  // namespace
+
+int spmv_ensure_contiguous(Engine* e)
+{
+    SpmvState& S = *e->spmv;
+    if (S.contiguous_valid) return 0;
+    LB_DO(build_contiguous(e, S.by_row, S.m, S.nar, S.row_csr));
+    LB_DO(build_contiguous(e, S.by_col, S.n, S.nar, S.col_csr));
+    S.contiguous_valid = true;
+    return 0;
+}
+
+namespace {
+
 // element-wise launch over every group's len * 64 elements
 dim3 grid_of(int len, int G) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, ((size_t)len * 64 + 255) / 256)), (unsigned)G); }
 
@@ -986,12 +1000,7 @@ int batch_begin(Engine* e, int nreal, int localSize, size_t tmp, Batch& B, int r
     B.st = e->stream;
     const size_t vm = B.vm, vn = B.vn;
     LB_TRY(e, hipSetDevice(e->device));
-    if (!S.contiguous_valid) {
-        int rc = build_contiguous(e, S.by_row, S.m, S.nar, S.row_csr);
-        if (rc == 0) rc = build_contiguous(e, S.by_col, S.n, S.nar, S.col_csr);
-        if (rc != 0) return rc;
-        S.contiguous_valid = true;
-    }
+    LB_DO(spmv_ensure_contiguous(e));
     B.rval = S.row_csr.val.p; B.cval = S.col_csr.val.p;
     if (e->ensure(S.bu, vm) || e->ensure(S.bscale, vm) || e->ensure(S.bv, vn) || e->ensure(S.bh, vn) || e->ensure(S.bhbar, vn) || e->ensure(S.bx, vn) ||
         e->ensure(S.blocalV, std::max<size_t>(vn * (size_t)B.localVecs, 1)) || e->ensure(S.bparam, (size_t)kNParam * Rp) || e->ensure(S.bred, 3 * (size_t)Rp) ||

@@ -86,6 +86,8 @@ struct SpmvState {
 // y += A x (mode 1; x: n, y: m) or x += A^T y (mode 2) on device vectors, on the engine's stream; every output
 // element adds its entries in storage order (reference aprod.f90:7-60)
 void spmv_device(Engine* e, int mode, float* d_x, float* d_y);
+// row_csr / col_csr of the resident matrix (e->spmv is not null), built on the first call after a load (lsmr_batch.hip); the engine's device is current
+int spmv_ensure_contiguous(Engine* e);
 // the resident matrix was replaced or edited: the contiguous copies of dsa_lsmr_batch (and dsa_lsmr_tradeoff's coefficient copy of them) are stale,
 // and the batch solutions in bx no longer belong to it
 inline void spmv_invalidate_contiguous(SpmvState* s) { if (s) s->contiguous_valid = s->coef_valid = s->bx_valid = false; }

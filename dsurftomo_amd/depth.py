@@ -220,6 +220,38 @@ def maps_to_obs(rows, c):
     return obs.reshape(len(per), ny * nx), dws.reshape(len(per), ny * nx)
 
 
+def map_sigma_weights(rows, c, min_dws_mask=None, azimuthal=False):
+    """The step's weights from the rows of <input>MapsResolution.dat (maps.read_maps_resolution): (wt, sigma_ref).  wt
+    (nmaps, ny * nx) fp32 in maps_to_obs's layout = sigma_ref / sd where min_dws_mask (the same shape, None: all) keeps the datum, sd > 0 and
+    the map's flag is 0; 0 elsewhere and on the outer ring.  sigma_ref: the median sd over the kept data (0 without any), so that a typical
+    weight is 1 and --smooth and --damp keep their meaning.  azimuthal: the weights of the 2psi stage, from sqrt((sd_a1^2 + sd_a2^2) / 2).
+    ValueError as maps_to_obs when the file does not hold the case's periods and vertices."""
+    nx, ny = c["nx"], c["ny"]
+    nvx, nvz = nx - 2, ny - 2
+    layer = nvx * nvz
+    per = maps.period_list(c)
+    if len(rows) != len(per) * layer:
+        raise ValueError("depth: the map sigma file holds %d lines, %d periods of %d x %d interior vertices need %d" % (len(rows), len(per), nvx, nvz, len(per) * layer))
+    sd = np.zeros((len(per), ny, nx)); ok = np.zeros((len(per), ny, nx), bool)
+    for m, (wave, kind, t) in enumerate(per):
+        block = rows[m * layer:(m + 1) * layer]
+        if any((r["wave"], r["kind"], r["period"]) != (wave, kind, t) for r in block):
+            raise ValueError("depth: map %d of the map sigma file is not wave %d kind %d period %g of the input" % (m, wave, kind, t))
+        if azimuthal:
+            v = np.sqrt(0.5 * (np.array([r["sd_a1"] for r in block]) ** 2 + np.array([r["sd_a2"] for r in block]) ** 2))
+        else:
+            v = np.array([r["sd"] for r in block])
+        sd[m, 1:-1, 1:-1] = v.reshape(nvz, nvx)
+        ok[m, 1:-1, 1:-1] = np.array([r["flag"] == 0 for r in block]).reshape(nvz, nvx)
+    sd = sd.reshape(len(per), ny * nx); ok = ok.reshape(len(per), ny * nx)
+    keep = ok & (sd > 0) & np.isfinite(sd)
+    if min_dws_mask is not None:
+        keep &= np.asarray(min_dws_mask, bool).reshape(keep.shape)
+    sigma_ref = float(np.median(sd[keep])) if keep.any() else 0.0
+    wt = np.divide(sigma_ref, sd, out=np.zeros(sd.shape), where=keep)
+    return wt.astype(np.float32), sigma_ref
+
+
 def dws_weights(dws, min_dws):
     """the step's weights: 1, or 0 where the map's column DWS is below min_dws"""
     return np.where(np.asarray(dws, np.float64) < float(min_dws), 0.0, 1.0).astype(np.float32)
@@ -1266,6 +1298,7 @@ OPTIONS = (
     ("--out", "out_dir", ".", dict()),
     ("--resolution", "resolution", False, dict(action="store_true", help="after the last step write the resolution measures and the leverages of the final model")),
     ("--sigma", "sigma", None, dict(type=float, metavar="S", help="standard deviation of the map values in km/s for the sd column (default: the rms before the last step)")),
+    ("--map-sigma", "map_sigma", None, dict(metavar="FILE", help="the MapsResolution.dat of maps --resolution: every map value weighs sigma_ref / sd, sigma_ref the median sd of the kept values (default: weights 0 / 1); without --sigma the stages' standard deviation is sigma_ref")),
     ("--radial", "radial", False, dict(action="store_true", help="radial anisotropy: invert the Rayleigh maps for Vsv(z) and the Love maps for Vsh(z) together")),
     ("--aniso", "aniso", DEFAULT_ANISO, dict(type=float, metavar="G", help="with --radial: weight of the tie between Vsh and Vsv, >= 0 (default %g)" % DEFAULT_ANISO)),
     ("--lateral", "lateral", None, dict(type=float, metavar="W", help="couple neighbouring columns: weight of the penalty on their differences, >= 0 (default: columns alone)")),
@@ -1308,7 +1341,7 @@ def options_over_defaults(options):
 def check_options(o):
     """Every precondition on the options o (options_over_defaults'), in the one order run() and main() both refuse in (ValueError), before the
     library is loaded: --sample's, the marginals', then the loop's (aniso only with radial; --lateral-tol and --lateral-maxit only with a
-    coupling), --lateral's, --radial's, --radial-lateral's, --radial-resolution's, --lateral-resolution's, --azimuthal's.  Returns (parse_sample's tuple or
+    coupling), --lateral's, --radial's, --radial-lateral's, --radial-resolution's, --lateral-resolution's, --azimuthal's, then --map-sigma's file (its header names the needed columns).  Returns (parse_sample's tuple or
     None, check_marginals' tuple or None, the parsed --lateral-checkerboard or None)."""
     sampling = check_sample(o.sample, o.radial, o.lateral, o.sample_step, o.sample_spread, o.sample_width, o.sample_temperature, o.sample_seed, o.sample_block,
                             o.sample_block_scale)
@@ -1323,12 +1356,19 @@ def check_options(o):
     check_radial_resolution(o.radial_resolution, o.radial, o.radial_lateral)
     checker = check_lateral_resolution(o.lateral_resolution, o.lateral_resolution_stride, o.lateral_checkerboard, o.lateral, o.radial)
     check_azimuthal(o.azimuthal, o.radial, o.azimuthal_smooth, o.azimuthal_damp, o.azimuthal_sigma)
+    if o.map_sigma is not None:
+        maps.resolution_header(o.map_sigma, o.azimuthal)
     return sampling, marginals, checker
 
 
-def stage_sigma(label, sigma, history, log):
-    """the data's standard deviation of an after-loop stage: --sigma, or the rms before the last step; the log says which"""
+def stage_sigma(label, sigma, history, log, sigma_ref=None):
+    """the data's standard deviation of an after-loop stage: --sigma, or with --map-sigma its sigma_ref (the weights are sigma_ref / sd: a
+    datum of weight w then has the standard deviation sigma_ref / w = its sd), or the rms before the last step; the log says which"""
     rms = history[-1]["rms"]
+    if sigma is None and sigma_ref is not None:
+        log(" %s: the data's standard deviation is --map-sigma's reference, the median sd of the kept map values, %.6f km/s (the weighted rms before the last step was %.6f)" %
+            (label, sigma_ref, rms))
+        return sigma_ref
     log(" %s: the data's standard deviation is %s" % (label, "--sigma %.6f km/s" % sigma if sigma is not None else "the rms before the last step, %.6f km/s" % rms))
     return rms if sigma is None else sigma
 
@@ -1343,7 +1383,7 @@ STAGES = (
      lambda r, o, sigma: resolve_lateral(r.eng, r.c, r.plan, r.obs, r.wt, o.smooth, o.damp, o.lateral, o.lateral_tol, o.lateral_maxit, sigma, r.out_dir,
                                          o.lateral_resolution_stride, r.checker, r.log)),
     (None, False, lambda o: o.azimuthal,
-     lambda r, o, sigma: run_azimuthal(r.eng, r.c, r.plan, r.out["vels"], r.obs, r.azi[0], r.azi[1], r.wt, o.smooth if o.azimuthal_smooth is None else o.azimuthal_smooth,
+     lambda r, o, sigma: run_azimuthal(r.eng, r.c, r.plan, r.out["vels"], r.obs, r.azi[0], r.azi[1], r.wt if r.wt_azi is None else r.wt_azi, o.smooth if o.azimuthal_smooth is None else o.azimuthal_smooth,
                                        o.damp if o.azimuthal_damp is None else o.azimuthal_damp, o.azimuthal_sigma, r.out_dir, r.log)),
     ("depth sample", False, lambda o: o.sample is not None,
      lambda r, o, sigma: run_sample(r.eng, r.c, r.plan, r.out["vels"], r.obs, r.wt, o.smooth, sigma, r.sampling, r.out_dir, o.sample_step, o.sample_spread, o.sample_width,
@@ -1369,7 +1409,10 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
     ("P1,P2,...") and, with sample_covariance, the correlations between a column's depths (run_sample's three files).  With azimuthal: after
     the resolutions and before the sample stage run_azimuthal's entries are added to the first item (DepthAzim.dat and DepthAzimFit.dat beside
     the two files); azimuthal_smooth / azimuthal_damp None: smooth / damp; azimuthal_sigma None: the rms of the fit's residual; a maps file
-    without a1 / a2 columns is a ValueError naming it, before the library is loaded.  The radial path writes
+    without a1 / a2 columns is a ValueError naming it, before the library is loaded.  With map_sigma (the MapsResolution.dat of maps
+    --resolution): every stage's wt is map_sigma_weights' sigma_ref / sd under the --min-dws mask, the 2psi stage's its own from the sd of A1
+    and A2, and without sigma the stages take sigma_ref, so that the sampler's weights are 1 / sd; a file without the needed columns is a
+    ValueError naming it, before the library is loaded.  The radial path writes
     its two files in run_radial, before its stage; the isotropic path writes Depth.dat and DepthFit.dat after its stages, the engine closed."""
     o = options_over_defaults(options)
     sampling, marginals, checker = check_options(o)
@@ -1387,8 +1430,21 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
     if not plan or kmax > 60:
         raise ValueError("depth: %d periods; the step takes 1 to 60" % kmax)
     wt = dws_weights(dws, o.min_dws) if o.min_dws > 0 else None
+    wt_azi = sigma_ref = None
+    if o.map_sigma is not None:
+        sd_rows = maps.read_maps_resolution(o.map_sigma, o.azimuthal)
+        mask = None if wt is None else wt > 0
+        wt, sigma_ref = map_sigma_weights(sd_rows, c, mask)
+        log(" depth: weights sigma_ref / sd from %s: sigma_ref %.6f km/s, %d of %d map values kept, weights %.4f to %.4f" %
+            (o.map_sigma, sigma_ref, int((wt > 0).sum()), kmax * (c["nx"] - 2) * (c["ny"] - 2), float(wt[wt > 0].min()) if (wt > 0).any() else 0.0, float(wt.max())))
+        if wt.max() > 10.0:
+            log(" depth: weights above 10 belong to map values the rays hardly resolve -- damping pulls them to the start and their variance with them; --min-dws masks them")
+        if o.azimuthal:
+            wt_azi, azi_ref = map_sigma_weights(sd_rows, c, mask, azimuthal=True)
+            log(" depth: weights of the 2psi stage from sqrt((sd_a1^2 + sd_a2^2) / 2): reference %.6f km/s, %d values kept" % (azi_ref, int((wt_azi > 0).sum())))
     from .engine import Engine
-    r = types.SimpleNamespace(eng=Engine(0), c=c, plan=plan, obs=obs, wt=wt, out_dir=out_dir, log=log, sampling=sampling, marginals=marginals, checker=checker, azi=azi)
+    r = types.SimpleNamespace(eng=Engine(0), c=c, plan=plan, obs=obs, wt=wt, out_dir=out_dir, log=log, sampling=sampling, marginals=marginals, checker=checker, azi=azi,
+                              wt_azi=wt_azi)
     try:
         if o.radial:
             r.out, path, fit = run_radial(r.eng, c, plan, obs, wt, o.iterations, o.smooth, o.damp, o.aniso, o.dvmax, out_dir, log, o.radial_lateral, o.radial_lateral_aniso,
@@ -1399,7 +1455,7 @@ def run(directory, maps_file=None, out_dir=".", log=print, **options):
             r.out["vels"] = r.eng.dispersion_get_model()
         for label, radial, wanted, call in STAGES:
             if radial == o.radial and wanted(o):
-                r.out.update(call(r, o, None if label is None else stage_sigma(label, o.sigma, r.out["history"], log)))
+                r.out.update(call(r, o, None if label is None else stage_sigma(label, o.sigma, r.out["history"], log, sigma_ref)))
     finally:
         r.eng.close()
     if not o.radial:

@@ -102,6 +102,7 @@ def declare_solvers(L):
     L.dsa_iteration_system_maps_device.argtypes = [_vp] + [_i32] * 5 + [_vp] * 2 + [_f32] * 3 + [_vp] * 6
     L.dsa_update_maps.argtypes = [_vp, _i32, _vp] + [_f32] * 3
     L.dsa_get_maps.argtypes = [_vp, _i32, _vp]
+    L.dsa_maps_resolution.argtypes = [_vp] + [_i32] * 5 + [_f32, _i32] + [_vp] * 6
     L.dsa_columns_step.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 5 + [_vp] * 4
     L.dsa_dispersion_get_model.argtypes = [_vp, _vp]
     L.dsa_columns_resolution.argtypes = [_vp, _i32, _vp, _vp] + [_f32] * 2 + [_vp] * 6
@@ -331,6 +332,22 @@ class Engine:
         """the resident fp32 vertex maps, (nmaps, nx * ny) in set_maps' layout"""
         out = np.zeros((int(nmaps), nx * ny), np.float32)
         self._check(self._L.dsa_get_maps(self._h, int(nmaps), out.ctypes.data_as(_vp)))
+        return out
+
+    def maps_resolution(self, nx, ny, nmaps, nblocks, ndata, damp, r_map=-1):
+        """dsa_maps_resolution on the resident map system (iteration_system_maps_device's, or a spmv_load of one in row order): the exact
+        resolution and covariance of every map from one dense fp64 factorisation per map.  Returns dict(measures (9, nblocks, nmaps, layer)
+        {R_qq, var, sum R^2 over the plane, that sum weighted with dx^2 and with dy^2 in vertex units, sum R^2 over the map, R at the
+        co-located unknowns of the next two planes, the covariance with the next plane's}, leverage (ndata), trace (nblocks, nmaps), nused,
+        flag (nmaps), and with r_map >= 0 R (n_m, n_m) of that map)."""
+        layer = (int(nx) - 2) * (int(ny) - 2)
+        nm = int(nblocks) * layer
+        out = dict(measures=np.zeros((9, max(int(nblocks), 1), max(int(nmaps), 1), max(layer, 1))), leverage=np.zeros(max(int(ndata), 1)),
+                   trace=np.zeros((max(int(nblocks), 1), max(int(nmaps), 1))), nused=np.zeros(max(int(nmaps), 1), np.int32), flag=np.zeros(max(int(nmaps), 1), np.int32))
+        if r_map >= 0:
+            out["R"] = np.zeros((max(nm, 1), max(nm, 1)))
+        self._check(self._L.dsa_maps_resolution(self._h, int(nx), int(ny), int(nmaps), int(nblocks), int(ndata), float(damp), int(r_map), _p(out["measures"]),
+                                                _p(out["leverage"]), _p(out["trace"]), _p(out["nused"]), _p(out["flag"]), _p(out["R"]) if r_map >= 0 else None))
         return out
 
     def set_azimuthal_slots(self, on):

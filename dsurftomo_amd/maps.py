@@ -1,7 +1,7 @@
 """Period-by-period 2-D phase- and group-velocity maps on the bent rays, optionally with 2psi terms.
 
     python -m dsurftomo_amd.maps <directory with DSurfTomo.in, the data file and MOD> [--start model|mean] [--iterations N] [--weight W] [--damp D]
-                                 [--dvmax V] [--azimuthal [--azimuthal-weight W]] [--out DIR]
+                                 [--dvmax V] [--azimuthal [--azimuthal-weight W]] [--resolution [--sigma-time S]] [--out DIR]
 
 The first step of the "two-step" method, which the direct inversion is routinely compared with: the travel times of every period are
 inverted for a 2-D velocity map of that period, on rays bent through that map.  There is one map per period of the input file, in the
@@ -24,7 +24,15 @@ accumulated, and the rays are not traced through the anisotropic medium.
 100 sqrt(A1^2 + A2^2) / c0 in per cent and the fast axis 0.5 atan2(A2, A1) in degrees from north.  The log gives, per iteration and per
 map, the number of data and the weighted mean and rms residual before the step, and the solver's itn / istop.
 
-laplacian_rows_2d, map_system and update_maps_twin restate the regulariser, the system and the update rule in NumPy for the tests.
+--resolution: after the last iteration the rows are traced on the final maps, the system is built once more with
+the run's weights and dsa_maps_resolution factors every map's normal matrix exactly.  <input>MapsResolution.dat (write_maps_resolution /
+read_maps_resolution), per (map, interior vertex): wave, kind, period, longitude, latitude, R_jj, the point-spread lengths in x and y in km,
+the own share of the point-spread function, sd_unit = sqrt(var), sd = sigma sd_unit in km/s, sigma -- --sigma-time S in seconds or, by
+default, that map's weighted rms residual on the final maps -- and the map's flag; after --azimuthal also R_jj and sd of A1 and A2, their
+covariance and the first-order sd of strength (per cent) and fast axis (degrees).  <input>MapsLeverage.dat: per datum its map, weight and
+leverage.  Maps.dat and the loop are untouched.  depth --map-sigma reads the file as weights.
+
+laplacian_rows_2d, map_system, update_maps_twin and map_resolution_twin restate the regulariser, the system and the update rule in NumPy for the tests.
 Every precondition is checked before the library is loaded.  There is no CPU path.
 """
 import argparse
@@ -43,6 +51,10 @@ DEFAULT_ITERATIONS = 3
 _F64 = lambda *names: tuple((n, "%.17g", "f64") for n in names)
 MAPS_TABLE = (True, (("wave", "%d", "int"), ("kind", "%d", "int")) + _F64("period", "lon", "lat", "c0", "dws"))
 MAPS_AZI_TABLE = (True, MAPS_TABLE[1] + _F64("a1", "a2", "strength", "axis"))
+RESOLUTION_TABLE = (True, MAPS_TABLE[1][:5] + _F64("rjj", "psf_x", "psf_y", "share", "sd_unit", "sd", "sigma") + (("flag", "%d", "int"),))
+RESOLUTION_AZI_TABLE = (True, RESOLUTION_TABLE[1] + _F64("rjj_a1", "sd_a1", "rjj_a2", "sd_a2", "cov_a12", "sd_strength", "sd_axis"))
+MAPS_LEVERAGE_TABLE = (True, (("datum", "%d", "int"), ("map", "%d", "int")) + _F64("weight", "leverage"))
+EARTH_RADIUS_KM = 6371.0
 
 
 # ---- NumPy twins ----
@@ -120,6 +132,81 @@ def fast_axis(a1, a2):
     return np.degrees(0.5 * np.arctan2(np.asarray(a2, np.float64), np.asarray(a1, np.float64)))
 
 
+def map_resolution_twin(nx, ny, nmaps, nblocks, S, ndata, damp, route="normal"):
+    """dsa_maps_resolution in NumPy: per map a dense fp64 numpy.linalg route with the library's definitions.  S: the
+    system as map_system returns it (m, n, rw, row, col; 1-based COO).  route "normal": N = A_m^T A_m + damp^2 I by a Cholesky check and
+    numpy.linalg.solve; route "pinv": the generalised inverse of [A_m; damp I] by numpy.linalg.pinv -- independent of the first, used only
+    to size tolerances.  Returns dict(measures (9, nblocks, nmaps, layer), leverage (ndata), trace (nblocks, nmaps), nused, flag (nmaps),
+    R: one (n_m, n_m) array per map, zeros where the map is flagged).  ValueError for a row with entries in two maps or a column stored
+    twice in a row."""
+    nvx, nvz = nx - 2, ny - 2
+    layer = nvx * nvz
+    nm, n, m = nblocks * layer, nblocks * nmaps * layer, int(S["m"])
+    damp = float(np.float32(damp))                                     # (the library's argument is fp32)
+    if int(S["n"]) != n:
+        raise ValueError("map_resolution_twin: the system has %d unknowns, not %d" % (S["n"], n))
+    row = np.asarray(S["row"], np.int64) - 1; col = np.asarray(S["col"], np.int64) - 1
+    val = np.asarray(S["rw"], np.float32).astype(np.float64)
+    if np.unique(row * n + col).size != row.size:
+        raise ValueError("map_resolution_twin: a row stores one column twice")
+    emap = (col // layer) % nmaps
+    owner = np.full(m, -1, np.int64)
+    lo = np.full(m, nmaps, np.int64); hi = np.full(m, -1, np.int64)
+    np.minimum.at(lo, row, emap); np.maximum.at(hi, row, emap)
+    if (lo[hi >= 0] != hi[hi >= 0]).any():
+        raise ValueError("map_resolution_twin: row %d has entries in two maps" % (int(np.flatnonzero((hi >= 0) & (lo != hi))[0]) + 1))
+    owner[hi >= 0] = hi[hi >= 0]
+    A = np.zeros((m, n))
+    A[row, col] = val
+    used_row = (np.abs(A).sum(axis=1) > 0) & (np.arange(m) < ndata)
+    out = dict(measures=np.zeros((9, nblocks, nmaps, layer)), leverage=np.zeros(ndata), trace=np.zeros((nblocks, nmaps)), nused=np.zeros(nmaps, np.int32),
+               flag=np.zeros(nmaps, np.int32), R=[np.zeros((nm, nm)) for _ in range(nmaps)])
+    ix, iy = np.arange(layer) % nvx, np.arange(layer) // nvx
+    dx2 = (ix[:, None] - ix[None, :]).astype(np.float64) ** 2; dy2 = (iy[:, None] - iy[None, :]).astype(np.float64) ** 2
+    for k in range(nmaps):
+        cols = np.concatenate([np.arange((B * nmaps + k) * layer, (B * nmaps + k + 1) * layer) for B in range(nblocks)])
+        rows = np.flatnonzero(owner == k)
+        data = np.flatnonzero(used_row & (owner == k))
+        out["nused"][k] = data.size
+        if data.size == 0:
+            out["flag"][k] = 2
+            continue
+        Am, G = A[np.ix_(rows, cols)], A[np.ix_(data, cols)]
+        if route == "normal":
+            N = Am.T @ Am + (float(damp) ** 2) * np.eye(nm)
+            try:
+                if not np.isfinite(N).all():
+                    raise np.linalg.LinAlgError
+                np.linalg.cholesky(N)
+                T = np.linalg.solve(N, G.T).T
+            except np.linalg.LinAlgError:
+                out["flag"][k] = 1
+                continue
+        else:
+            full = np.vstack([Am, float(damp) * np.eye(nm)])
+            if np.linalg.matrix_rank(full) < nm:
+                out["flag"][k] = 1
+                continue
+            T = np.linalg.pinv(full)[:, np.searchsorted(rows, data)].T
+        R = T.T @ G                                                    # R_lq = sum_d t_dl g_dq
+        out["R"][k] = R
+        R2 = R * R
+        meas = np.zeros((9, nm))
+        meas[0] = R.diagonal(); meas[1] = (T * T).sum(axis=0); meas[5] = R2.sum(axis=0)
+        for B in range(nblocks):
+            own = slice(B * layer, (B + 1) * layer)
+            blk = R2[own, own]
+            meas[2, own] = blk.sum(axis=0); meas[3, own] = (blk * dx2).sum(axis=0); meas[4, own] = (blk * dy2).sum(axis=0)
+            if nblocks > 1:
+                q = np.arange(layer) + B * layer
+                q1, q2 = np.arange(layer) + ((B + 1) % nblocks) * layer, np.arange(layer) + ((B + 2) % nblocks) * layer
+                meas[6, own] = R[q1, q]; meas[7, own] = R[q2, q]; meas[8, own] = (T[:, q] * T[:, q1]).sum(axis=0)
+        out["measures"][:, :, k, :] = meas.reshape(9, nblocks, layer)
+        out["leverage"][data] = (G * T).sum(axis=1)
+        out["trace"][:, k] = meas[0].reshape(nblocks, layer).sum(axis=1)
+    return out
+
+
 # ---- the plan ----
 
 def period_list(c):
@@ -162,8 +249,12 @@ def datum_maps(u):
 
 # ---- the loop ----
 
-def check(iterations=None, weight=None, damp=None, dvmax=None, azimuthal=False, azimuthal_weight=None, start=None):
+def check(iterations=None, weight=None, damp=None, dvmax=None, azimuthal=False, azimuthal_weight=None, start=None, resolution=False, sigma_time=None):
     """the driver's preconditions, checked before the library is loaded (ValueError)"""
+    if sigma_time is not None and not resolution:
+        raise ValueError("--sigma-time needs --resolution")
+    if sigma_time is not None and not (np.isfinite(sigma_time) and sigma_time > 0):
+        raise ValueError("--sigma-time must be finite and > 0, not %r" % (sigma_time,))
     if start is not None and start not in ("model", "mean"):
         raise ValueError("--start is model or mean, not %r" % (start,))
     if iterations is not None and iterations < 1:
@@ -245,6 +336,133 @@ def start_maps(eng, c, u, start):
     eng.set_maps(nx, ny, c["goxd"], c["gozd"], c["dvxd"], c["dvzd"], pv, dicing=8)
 
 
+# ---- the resolution of the maps ----
+
+def strength_variance(c0, a1, a2, v1, v2, c12):
+    """first-order variance of the strength s = 100 sqrt(A1^2 + A2^2) / c0 in per cent^2 from the variances v1, v2 of A1, A2 and their covariance
+    c12 (c0 taken as known): (100 / c0)^2 (A1^2 v1 + A2^2 v2 + 2 A1 A2 c12) / (A1^2 + A2^2); 0 where A1 = A2 = 0; clamped at 0"""
+    c0, a1, a2, v1, v2, c12 = (np.asarray(x, np.float64) for x in (c0, a1, a2, v1, v2, c12))
+    r2 = a1 * a1 + a2 * a2
+    num = (100.0 / c0) ** 2 * (a1 * a1 * v1 + a2 * a2 * v2 + 2.0 * a1 * a2 * c12)
+    return np.maximum(np.divide(num, r2, out=np.zeros(np.broadcast(num, r2).shape), where=r2 > 0), 0.0)
+
+
+def axis_variance(a1, a2, v1, v2, c12):
+    """first-order variance of the fast axis phi = atan2(A2, A1) / 2 in rad^2: (A2^2 v1 + A1^2 v2 - 2 A1 A2 c12) / (4 (A1^2 + A2^2)^2); 0 where
+    A1 = A2 = 0; clamped at 0"""
+    a1, a2, v1, v2, c12 = (np.asarray(x, np.float64) for x in (a1, a2, v1, v2, c12))
+    r2 = a1 * a1 + a2 * a2
+    num = 0.25 * (a2 * a2 * v1 + a1 * a1 * v2 - 2.0 * a1 * a2 * c12)
+    return np.maximum(np.divide(num, r2 * r2, out=np.zeros(np.broadcast(num, r2).shape), where=r2 > 0), 0.0)
+
+
+def _ratio_root(num, den):
+    num = np.asarray(num, np.float64); den = np.asarray(den, np.float64)
+    return np.sqrt(np.maximum(np.divide(num, den, out=np.zeros(num.shape), where=den > 0), 0.0))
+
+
+def resolution_columns(c, res, sigma_m, velv=None, a1=None, a2=None):
+    """The columns of MapsResolution.dat from maps_resolution's result res (measures (9, nblocks, nmaps, layer), flag) and the data's
+    standard deviation per map sigma_m (nmaps, s): a dict of (nmaps, layer) arrays -- rjj, psf_x, psf_y (km: sqrt(m3 / m2) and sqrt(m4 / m2)
+    times the vertex spacing; x is the fast vertex index, which runs along latitude), share = m2 / m5, sd_unit = sqrt(var), sd = sigma_m
+    sd_unit (km/s), sigma, flag; with three blocks (velv (nmaps, nx * ny), a1, a2 (nmaps, layer) given) also rjj and sd of A1 and A2, their
+    covariance sigma_m^2 times measure 8 of the A1 unknown, and the sd of strength (per cent) and fast axis (degrees)."""
+    nx, ny = c["nx"], c["ny"]
+    nvx, nvz = nx - 2, ny - 2
+    m = np.asarray(res["measures"], np.float64)
+    nblocks, nmaps = m.shape[1], m.shape[2]
+    sig = np.asarray(sigma_m, np.float64).reshape(nmaps, 1)
+    lat = np.array([[float(_lonlat(c, i, j)[1]) for i in range(nvx)] for j in range(nvz)]).reshape(-1)
+    dx_km = EARTH_RADIUS_KM * np.radians(float(c["dvxd"]))
+    dy_km = EARTH_RADIUS_KM * np.radians(float(c["dvzd"])) * np.cos(np.radians(lat))
+    out = dict(rjj=m[0, 0], psf_x=_ratio_root(m[3, 0], m[2, 0]) * dx_km, psf_y=_ratio_root(m[4, 0], m[2, 0]) * dy_km[None, :],
+               share=np.divide(m[2, 0], m[5, 0], out=np.zeros(m[2, 0].shape), where=m[5, 0] > 0), sd_unit=np.sqrt(np.maximum(m[1, 0], 0.0)),
+               sigma=np.broadcast_to(sig, m[0, 0].shape).copy(), flag=np.broadcast_to(np.asarray(res["flag"]).reshape(nmaps, 1), m[0, 0].shape).copy())
+    out["sd"] = sig * out["sd_unit"]
+    if nblocks == 3:
+        v1, v2, c12 = sig ** 2 * m[1, 1], sig ** 2 * m[1, 2], sig ** 2 * m[8, 1]
+        c0 = np.asarray(velv, np.float64).reshape(nmaps, ny, nx)[:, 1:-1, 1:-1].reshape(nmaps, -1)
+        out.update(rjj_a1=m[0, 1], sd_a1=np.sqrt(np.maximum(v1, 0.0)), rjj_a2=m[0, 2], sd_a2=np.sqrt(np.maximum(v2, 0.0)), cov_a12=c12,
+                   sd_strength=np.sqrt(strength_variance(c0, a1, a2, v1, v2, c12)), sd_axis=np.degrees(np.sqrt(axis_variance(a1, a2, v1, v2, c12))))
+    return out
+
+
+def write_maps_resolution(path, c, cols):
+    """<input>MapsResolution.dat: resolution_columns' arrays, one line per (map, interior vertex) in Maps.dat's order"""
+    nvx, nvz = c["nx"] - 2, c["ny"] - 2
+    azi = "rjj_a1" in cols
+    table = RESOLUTION_AZI_TABLE if azi else RESOLUTION_TABLE
+    names = [n for n, _, _ in table[1][5:]]
+    rows = []
+    for m, (wave, kind, t) in enumerate(period_list(c)):
+        for j in range(nvz):
+            for i in range(nvx):
+                lon, lat = _lonlat(c, i, j)
+                r = dict(wave=wave, kind=kind, period=t, lon=float(lon), lat=float(lat))
+                r.update({n: (int if n == "flag" else float)(cols[n][m, j * nvx + i]) for n in names})
+                rows.append(r)
+    io.write_table(path, table, rows)
+
+
+def read_maps_resolution(path, azimuthal=False):
+    """the rows write_maps_resolution wrote; the header line says whether the file carries the 2psi columns.  ValueError naming the file when
+    it is not such a file (no sd and flag columns), or, with azimuthal, when it lacks the sd of A1 and A2."""
+    return io.read_table(path, RESOLUTION_AZI_TABLE if "rjj_a1" in resolution_header(path, azimuthal) else RESOLUTION_TABLE)
+
+
+def resolution_header(path, azimuthal=False):
+    """the column names of a MapsResolution.dat; ValueError naming the file when it cannot be read, when it has no sd and flag columns or,
+    with azimuthal, no sd of A1 and A2"""
+    try:
+        with open(path) as fh:
+            head = fh.readline().split()
+    except OSError as exc:
+        raise ValueError("%s cannot be read (%s)" % (path, exc.strerror))
+    if not {"sd", "flag", "rjj"} <= set(head):
+        raise ValueError("%s has no sd / flag columns: it is not a MapsResolution.dat of maps --resolution" % path)
+    if azimuthal and not {"sd_a1", "sd_a2"} <= set(head):
+        raise ValueError("%s has no sd_a1 / sd_a2 columns; write it with maps --azimuthal --resolution" % path)
+    return head
+
+
+def write_maps_leverage(path, dmap, datweight, leverage):
+    """<input>MapsLeverage.dat: one line per datum in data order -- its map, its weight and its leverage"""
+    io.write_table(path, MAPS_LEVERAGE_TABLE, [dict(datum=d, map=int(dmap[d]), weight=float(datweight[d]), leverage=float(leverage[d])) for d in range(len(leverage))])
+
+
+def read_maps_leverage(path):
+    return io.read_table(path, MAPS_LEVERAGE_TABLE)
+
+
+def resolve(eng, c, u, obst, weight, damp, threshold0, out, sigma_time=None, azimuthal=False, weight_azi=None, out_dir=".", log=print):
+    """--resolution on an engine that holds the final maps and their plan: the rows traced on them, the system once more with the run's
+    weights, maps_resolution, the two files and the log.  out: iterate's result with velv.  sigma per map: sigma_time (s), or that map's
+    weighted rms residual on the final maps.  Returns dict(resolution, sigma_m, columns, resolution_path, leverage_path)."""
+    f = np.float32
+    nx, ny, nmaps = c["nx"], c["ny"], u["nmaps"]
+    nblocks = 3 if azimuthal else 1
+    obst = np.ascontiguousarray(obst, f)
+    dsyn, _ = eng.solve_rows_maps_device(azimuthal)
+    S = eng.iteration_system_maps_device(nx, ny, nmaps, nblocks, obst, dsyn, threshold0, weight, weight if weight_azi is None else weight_azi)
+    res = eng.maps_resolution(nx, ny, nmaps, nblocks, obst.size, damp)
+    dmap = datum_maps(u)
+    per_map = residual_report((obst - dsyn).astype(f), S["datweight"], dmap, nmaps)
+    sigma_m = np.full(nmaps, float(sigma_time)) if sigma_time is not None else np.array([r for _, _, r in per_map])
+    cols = resolution_columns(c, res, sigma_m, out["velv"], out.get("a1"), out.get("a2"))
+    rpath = os.path.join(out_dir, "DSurfTomo.inMapsResolution.dat")
+    lpath = os.path.join(out_dir, "DSurfTomo.inMapsLeverage.dat")
+    write_maps_resolution(rpath, c, cols)
+    write_maps_leverage(lpath, dmap, S["datweight"], res["leverage"])
+    log(" maps resolution: sigma per map is %s" % ("--sigma-time %.6f s" % sigma_time if sigma_time is not None else "its weighted rms residual on the final maps"))
+    for m in range(nmaps):
+        lev = res["leverage"][dmap == m]
+        log(" maps resolution map %3d: flag %d, %5d data used, trace %s of %d unknowns per block, median R_jj %.4f, sigma %.5f s, median sd %.5f km/s, largest leverage %.4f" %
+            (m, int(res["flag"][m]), int(res["nused"][m]), " ".join("%.3f" % t for t in res["trace"][:, m]), (nx - 2) * (ny - 2), float(np.median(cols["rjj"][m])),
+             float(sigma_m[m]), float(np.median(cols["sd"][m])), float(lev.max()) if lev.size else 0.0))
+    log(" maps resolution: written to %s, the leverages of %d data to %s" % (rpath, obst.size, lpath))
+    return dict(resolution=res, sigma_m=sigma_m, columns=cols, resolution_path=rpath, leverage_path=lpath)
+
+
 # ---- the file ----
 
 def write_maps(path, c, velv, norm, a1=None, a2=None):
@@ -278,9 +496,10 @@ def read_maps(path):
 
 
 def run(directory, start="mean", iterations=DEFAULT_ITERATIONS, weight=None, damp=None, dvmax=DEFAULT_DVMAX, azimuthal=False, azimuthal_weight=None,
-        out_dir=".", log=print):
-    """the driver behind main(); returns (iterate's result with velv (nmaps, nx * ny) added, the path of Maps.dat)"""
-    check(iterations, weight, damp, dvmax, azimuthal, azimuthal_weight, start)
+        out_dir=".", log=print, resolution=False, sigma_time=None):
+    """the driver behind main(); returns (iterate's result with velv (nmaps, nx * ny) added, the path of Maps.dat).  With resolution the
+    result also holds resolve's entries; Maps.dat and the loop are what they are without it."""
+    check(iterations, weight, damp, dvmax, azimuthal, azimuthal_weight, start, resolution, sigma_time)
     c = io.load(directory)
     if c["ifsyn"] == 1:
         raise ValueError("maps: a synthetic input (ifsyn = 1) has no observed data to invert")
@@ -297,6 +516,8 @@ def run(directory, start="mean", iterations=DEFAULT_ITERATIONS, weight=None, dam
         out = iterate(eng, u, c["nx"], c["ny"], u["nmaps"], c["obst"], iterations, weight, damp, float(c["threshold0"]), dvmax, float(c["minvel"]), float(c["maxvel"]),
                       azimuthal, azimuthal_weight, log)
         out["velv"] = eng.get_maps(u["nmaps"], c["nx"], c["ny"])
+        if resolution:
+            out.update(resolve(eng, c, u, c["obst"], weight, damp, float(c["threshold0"]), out, sigma_time, azimuthal, azimuthal_weight, out_dir, log))
     finally:
         eng.close()
     path = os.path.join(out_dir, "DSurfTomo.inMaps.dat")
@@ -315,6 +536,8 @@ def parser():
     ap.add_argument("--dvmax", type=float, default=DEFAULT_DVMAX, metavar="V", help="largest change of a vertex per iteration in km/s (default %g)" % DEFAULT_DVMAX)
     ap.add_argument("--azimuthal", action="store_true", help="three blocks per map: c0, A1 (cos 2psi), A2 (sin 2psi)")
     ap.add_argument("--azimuthal-weight", type=float, default=None, metavar="W", help="smoothing weight of the A1 and A2 blocks (default: --weight)")
+    ap.add_argument("--resolution", action="store_true", help="after the last iteration write the exact resolution and standard deviation of every map value (MapsResolution.dat, MapsLeverage.dat)")
+    ap.add_argument("--sigma-time", type=float, default=None, metavar="S", help="with --resolution: standard deviation of the travel times in s (default: each map's weighted rms residual)")
     ap.add_argument("--out", default=".")
     return ap
 
@@ -323,11 +546,11 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     try:
-        check(a.iterations, a.weight, a.damp, a.dvmax, a.azimuthal, a.azimuthal_weight, a.start)
+        check(a.iterations, a.weight, a.damp, a.dvmax, a.azimuthal, a.azimuthal_weight, a.start, a.resolution, a.sigma_time)
     except ValueError as exc:
         ap.error(str(exc))
     os.makedirs(a.out, exist_ok=True)
-    run(a.directory, a.start, a.iterations, a.weight, a.damp, a.dvmax, a.azimuthal, a.azimuthal_weight, a.out)
+    run(a.directory, a.start, a.iterations, a.weight, a.damp, a.dvmax, a.azimuthal, a.azimuthal_weight, a.out, resolution=a.resolution, sigma_time=a.sigma_time)
     return 0
 
 

@@ -436,6 +436,33 @@ int dsa_iteration_system_maps_device(dsa_engine* e, int nx, int ny, int nmaps, i
 int dsa_update_maps(dsa_engine* e, int nmaps, const float* dv, float dvmax, float minvel, float maxvel);
 int dsa_get_maps(dsa_engine* e, int nmaps, float* velv);
 
+/* dsa_maps_resolution: how well every value of the period maps is known (extension).  The resident matrix is a map system
+ * of nblocks*nmaps planes of layer = (nx-2)*(ny-2) unknowns with ndata data rows on top: dsa_iteration_system_maps_device's, or a
+ * dsa_spmv_load of one in row order.  Maps never couple, so the normal matrix A^T A + damp^2 I is one dense block of n_m = nblocks*layer
+ * unknowns per map; each block is factored exactly (fp64 L D L^T, csrc/map_resolution.h) and solved for every used datum of the map, which
+ * gives the generalised inverse T, the resolution matrix R = T^T G and the covariance for unit data variance, T^T T.  A row belongs to the map that
+ * all of its entries lie in; a data row is used iff an entry of it is not zero (the builder scales unweighted rows to zero).
+ *   measures  9*n doubles, (measure, unknown in column order); for local unknown q of plane B: 0 R_qq; 1 var_q = sum_d t_dq^2; 2 the sum
+ *             of R_lq^2 over the l of plane B; 3, 4 that sum weighted with the squared vertex distance in x and in y; 5 the sum of R_lq^2 over
+ *             the whole map; 6, 7 R at the co-located unknowns of planes (B+1) and (B+2) mod nblocks; 8 sum_d t_dq t_dq' with q' the
+ *             co-located unknown of plane (B+1) mod nblocks.  6, 7, 8 are 0 for nblocks = 1.
+ *   leverage  NULL, or ndata: h_d = g_d . t_d, 0 for a datum that is not used
+ *   trace     NULL, or nblocks*nmaps: the sum of R_qq per plane, (block, map)
+ *   nused     NULL, or nmaps: used data per map
+ *   flag      NULL, or nmaps: 0; 1 a pivot that is not finite or <= 0; 2 no used datum.  Every output of a flagged map is 0.
+ *   R         NULL with r_map = -1, or the n_m*n_m doubles of map r_map's R, R_lq at l*n_m + q
+ * Maps are processed in groups whose factor, R and T (8*(2 n_m^2 + K_m n_m) bytes per map of K_m used data) fit dsa_set_memory_budget,
+ * or half of the free memory, at most 16 GiB, where none is set.  The call is read-only on the resident matrix and on every solver's
+ * state: dsa_lsmr and the batch solvers give the bits they gave without it, the solutions a batch solve left stay valid.
+ * Errors: DSA_ERR_ARGUMENT (a NULL e / measures, nx or ny < 3, nmaps < 1, nblocks not 1 or 3, n other than nblocks*nmaps*layer, ndata
+ * outside [1, m], damp negative or not finite, r_map outside -1 .. nmaps-1, R and r_map disagreeing), DSA_ERR_STATE (no resident matrix,
+ * or the radial system), DSA_ERR_CAPACITY (the factor and R of one map alone exceed a set budget): all found before the device is touched.
+ * Then, found by a pass over the matrix before anything is factored: DSA_ERR_ARGUMENT (a row with entries in two maps; a row that stores a
+ * column twice; a column whose rows do not ascend, i.e. a matrix that was not loaded in row order), DSA_ERR_CAPACITY (one map with its T
+ * does not fit).  DSA_ERR_DEVICE.  The engine stays usable after every refusal. */
+int dsa_maps_resolution(dsa_engine* e, int nx, int ny, int nmaps, int nblocks, int ndata, float damp, int r_map, double* measures,
+                        double* leverage, double* trace, int* nused, int* flag, double* R);
+
 /* dsa_columns_step: the depth inversion of the period maps, one Gauss-Newton step of every interior column's Vs(z) on the device (extension;
  * DESIGN.md 21).  The dispersion stage holds one model, as many maps as kernel slots (nmaps == nmaps_total == kmax_total of
  * dsa_dispersion_begin, at most 60), and every map k and kernel slot k has been written by a dsa_dispersion_run with_kernels = 1 (sen_slot ==
