@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdsurftomo_amd.so")
 SOURCES = ["fim_kernel.hip", "bundle_kernel.hip", "exact_kernel.hip", "stage_kernels.hip", "ray_kernels.hip", "disp_kernels.hip", "step_kernels.hip", "column_kernels.hip", "map_kernels.hip", "spmv.hip", "lsmr.hip", "lsmr_batch.hip", "iteration.hip", "engine.hip", "dropin.hip", "selfcheck.hip"]
-HEADERS = ["eikonal_core.h", "source_stage.h", "host_geometry.h", "bundle_plan.h", "joint_system.h", "map_system.h", "map_resolution.h", "radial_system.h", "column_system.h", "column_resolution.h", "column_azimuthal.h", "column_radial.h", "column_radial_resolution.h", "column_lateral.h", "column_radial_lateral.h", "column_lateral_resolution.h", "column_sample.h", "kernels.h", "engine.h", "ray_core.h", "dispersion_core.h", "spmv_state.h", "lsmr_core.h", "exact_march.h", "wave_ops.h", "receiver_core.h"]
+HEADERS = ["eikonal_core.h", "source_stage.h", "host_geometry.h", "bundle_plan.h", "joint_system.h", "map_system.h", "map_resolution.h", "radial_system.h", "column_system.h", "column_resolution.h", "column_azimuthal.h", "column_radial.h", "column_radial_resolution.h", "column_lateral.h", "column_radial_lateral.h", "column_lateral_resolution.h", "column_sample.h", "column_sample_radial.h", "kernels.h", "engine.h", "ray_core.h", "dispersion_core.h", "spmv_state.h", "lsmr_core.h", "exact_march.h", "wave_ops.h", "receiver_core.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function"]
 

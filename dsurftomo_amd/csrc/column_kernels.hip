@@ -14,6 +14,7 @@
 // k_sample_* (DESIGN.md section 29): the Metropolis chains of the Monte-Carlo depth inversion, one thread per (column, chain).
 // k_sample_shape, k_sample_propose_block, k_sample_accept_block: the columns' shapes and the block sweeps.
 // k_sample_hist, k_sample_cov, k_sample_marginal_finish: the posterior marginals, one thread per counter or sum.
+// k_sample_radial_* (DESIGN.md section 37): the Metropolis chains of [Vsv ; Vsh] of the Monte-Carlo radial depth inversion.
 #include "kernels.h"
 #include "column_system.h"
 #include "column_resolution.h"
@@ -24,6 +25,7 @@
 #include "column_radial_lateral.h"
 #include "column_lateral_resolution.h"
 #include "column_sample.h"
+#include "column_sample_radial.h"
 
 namespace dsa {
 
@@ -435,6 +437,52 @@ __global__ void __launch_bounds__(kSampleBlock) k_sample_finish(SampleView S, do
     sample_finish(S, t - (long long)l * S.ncol, l, nodes, cols, counts);
 }
 
+// The Monte-Carlo radial depth inversion: column_sample_radial.h on every (column, chain) of a radial sample stage,
+// k_sample_*'s mapping (thread t = chain * ncol + column, the column fastest in both model stores and in the map store) and rules: the view
+// by value, no thread reads what another writes in the same launch, no LDS, no atomics.
+__device__ __forceinline__ bool sample_radial_thread(const SampleRadialView& S, long long* c, int* q)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x;
+    if (t >= S.ncol * S.C) return false;
+    *q = (int)(t / S.ncol);
+    *c = t - (long long)*q * S.ncol;
+    return true;
+}
+
+// phase 0: both stores of every chain and the cleared state, before the set-up's dispersion runs; phase 1: the used mask, phi, psi and the
+// chains put back, after them
+__global__ void __launch_bounds__(kSampleBlock) k_sample_radial_setup(SampleRadialView S, int phase)
+{
+    long long c; int q;
+    if (!sample_radial_thread(S, &c, &q)) return;
+    if (phase == 0) sample_radial_setup_models(S, c, q);
+    else sample_radial_setup_state(S, c, q);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_radial_propose(SampleRadialView S, int sweep)
+{
+    long long c; int q;
+    if (!sample_radial_thread(S, &c, &q)) return;
+    sample_radial_propose(S, c, q, sweep);
+}
+
+__global__ void __launch_bounds__(kSampleBlock) k_sample_radial_accept(SampleRadialView S, int sweep)
+{
+    long long c; int q;
+    if (!sample_radial_thread(S, &c, &q)) return;
+    sample_radial_accept(S, c, q, sweep);
+}
+
+// one thread per (column, depth): t = depth * ncol + column.  nodes (16, M, ncol), cols (3, ncol), counts (15, ncol)
+__global__ void __launch_bounds__(kSampleBlock) k_sample_radial_finish(SampleRadialView S, double* __restrict__ nodes, double* __restrict__ cols,
+                                                                       int* __restrict__ counts)
+{
+    const long long t = (long long)blockIdx.x * kSampleBlock + threadIdx.x;
+    if (t >= S.ncol * (S.nz - 1)) return;
+    const int l = (int)(t / S.ncol);
+    sample_radial_finish(S, t - (long long)l * S.ncol, l, nodes, cols, counts);
+}
+
 // The posterior marginals, launched after the Metropolis test of a kept sweep while they are switched on.  Thread t =
 // (row * C + chain) * ncol + column, row a depth (k_sample_hist) or a packed triangle entry (k_sample_cov): the column is the fastest
 // index, so a wavefront's reads of v and v0 and its read-modify-write of P are consecutive; the counters of one depth and chain lie nbins
@@ -790,6 +838,32 @@ void launch_sample_finish(const SampleView& S, double* d_nodes, double* d_cols, 
 {
     if (sample_empty(S)) return;
     hipLaunchKernelGGL(k_sample_finish, sample_grid(S.ncol * (S.nz - 1)), dim3(kSampleBlock), 0, stream, S, d_nodes, d_cols, d_counts);
+}
+
+static bool sample_radial_empty(const SampleRadialView& S) { return S.ncol < 1 || S.C < 1 || S.nz < 2; }
+
+void launch_sample_radial_setup(const SampleRadialView& S, int phase, hipStream_t stream)
+{
+    if (sample_radial_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_radial_setup, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, phase);
+}
+
+void launch_sample_radial_propose(const SampleRadialView& S, int sweep, hipStream_t stream)
+{
+    if (sample_radial_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_radial_propose, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, sweep);
+}
+
+void launch_sample_radial_accept(const SampleRadialView& S, int sweep, hipStream_t stream)
+{
+    if (sample_radial_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_radial_accept, sample_grid(S.ncol * S.C), dim3(kSampleBlock), 0, stream, S, sweep);
+}
+
+void launch_sample_radial_finish(const SampleRadialView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream)
+{
+    if (sample_radial_empty(S)) return;
+    hipLaunchKernelGGL(k_sample_radial_finish, sample_grid(S.ncol * (S.nz - 1)), dim3(kSampleBlock), 0, stream, S, d_nodes, d_cols, d_counts);
 }
 
 }  // namespace dsa

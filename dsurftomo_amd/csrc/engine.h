@@ -411,6 +411,28 @@ struct Engine {
     int columns_sample_marginals(int nbins, int with_cov);
     int columns_sample_marginals_fetch(int nlevels, const double* levels, unsigned* hist, double* figures, double* cov);
     int columns_sample_marginals_state(unsigned* hist, double* P);
+    // Monte-Carlo radial depth inversion (dsa_columns_sample_radial_*, k_sample_radial_*): a radial stage of nchains
+    // models -- vels_d holds the chains' Vsv, vsh_d their Vsh, dispersion_run picks by wave type -- with the sample stage's plan, parameters
+    // and rules.  sample_radial: set beside sample_open by columns_sample_radial_begin, cleared with it by every dispersion_setup; while it is
+    // set everything a sample stage refuses is refused, and so are the isotropic dsa_columns_sample_* entries, dsa_dispersion_get_model_radial
+    // and the radial depth-kernel and row entries.  The per-chain figures that have the isotropic stage's shape lie in its buffers (smp_*).
+    bool sample_radial = false;
+    int sample_pairs = 0;
+    unsigned long long sample_love = 0ull;
+    double sample_gam2 = 0.0;
+    OwnedBuf<float> smr_v0h, smr_bestvh, smr_poldh;
+    OwnedBuf<double> smr_S1h, smr_S2h, smr_Pvh, smr_X1, smr_X2, smr_nodes;
+    OwnedBuf<int> smr_kcnt, smr_npos, smr_nusedl, smr_counts;
+    int columns_sample_radial_begin(int nx, int ny, int nz, int nchains, const float* vsv, const float* vsh, const float* depz, float minthk, int nruns,
+                                    const int* iwave, const int* igr, const int* nper, const double* periods, int nmaps_in, const float* obs, const float* wt,
+                                    float smooth, float aniso, float step, float spread, float width, float temperature, float minvel, float maxvel,
+                                    unsigned long long seed, int burn, int pairs);
+    int columns_sample_radial_run(int nsweeps);
+    int columns_sample_radial_fetch(double* nodes, double* cols, int* counts);
+    int columns_sample_radial_state(float* vsv, float* vsh, double* phi, double* psi, int* counters, int* kinds, double* S1v, double* S2v, double* S1h, double* S2h,
+                                    double* Pvh, double* X1, double* X2, int* npos, double* phisum, int* nkept, double* best_e, float* best_vsv, float* best_vsh,
+                                    int* pnode, float* pold_v, float* pold_h, int* pmark, int* reseeded);
+    int sample_radial_refused(const char* who);      // the entry `who` is an isotropic sample stage's: refused on a radial one
 
     // radial anisotropy in the direct inversion (dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial; DESIGN.md
     // section 28).  radial_sens: Srow holds the depth factors of every slot on the model of its wave type (k_sen_combine_radial) and

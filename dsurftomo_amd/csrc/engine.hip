@@ -22,6 +22,7 @@
 #include "column_lateral.h"
 #include "column_radial_lateral.h"
 #include "column_sample.h"
+#include "column_sample_radial.h"
 
 namespace dsa {
 
@@ -213,6 +214,7 @@ int Engine::dispersion_setup(int nx, int ny, int nz, const float* depz, float mi
     disp_ready = false;
     disp_radial = false;
     sample_open = false;      // (any begin ends a sample stage; columns_sample_begin sets it again at its end)
+    sample_radial = false;
     disp_nx = nx; disp_ny = ny; disp_nz = nz; disp_kmax_total = kmax_total; disp_nmaps = nmaps_total; disp_nmodels = nmodels;
     h_depz.assign(depz, depz + nz);
     // (depth kernels exist for one model only: dispersion_run refuses them otherwise)
@@ -683,6 +685,7 @@ int Engine::dispersion_get_model(float* vels)
 int Engine::dispersion_get_model_radial(float* vsv, float* vsh)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "dispersion_get_model_radial: call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    if (int rc = sample_refused("dispersion_get_model_radial")) return rc;
     if (!disp_radial) { fail(DSA_ERR_STATE, "dispersion_get_model_radial: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
     const size_t nn = (size_t)disp_nx * disp_ny * disp_nz;
@@ -741,6 +744,7 @@ int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const floa
                                  float width, float temperature, float minvel, float maxvel, unsigned long long seed, int burn)
 {
     const char* who = "columns_sample_begin";
+    if (int rc = sample_radial_refused(who)) return rc;
     if (nchains < 1) { fail(DSA_ERR_ARGUMENT, "%s: nchains %d must be at least 1", who, nchains); return DSA_ERR_ARGUMENT; }
     if (nx < 3 || ny < 3) { fail(DSA_ERR_ARGUMENT, "%s: a %d x %d grid has no interior columns (at least 3 x 3)", who, nx, ny); return DSA_ERR_ARGUMENT; }
     if (nz < 2 || nz > 64 || !vels || !depz || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: bad arguments (nz=%d, a null model or depths, minthk=%g)", who, nz, (double)minthk); return DSA_ERR_ARGUMENT; }
@@ -809,6 +813,7 @@ int Engine::columns_sample_begin(int nx, int ny, int nz, int nchains, const floa
 // dispersion_run's.
 int Engine::columns_sample_run(int nsweeps)
 {
+    if (int rc = sample_radial_refused("columns_sample_run")) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_run: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
     if (nsweeps < 0 || (long long)sample_sweep + nsweeps > 0x7fffffffll) { fail(DSA_ERR_ARGUMENT, "columns_sample_run: nsweeps %d after %d sweeps", nsweeps, sample_sweep); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
@@ -835,6 +840,7 @@ int Engine::columns_sample_run(int nsweeps)
 // dsa_columns_sample_fetch: the finish of the state as it is; nothing of the state is changed, the sweeps may go on.
 int Engine::columns_sample_fetch(double* nodes, double* cols, int* counts)
 {
+    if (int rc = sample_radial_refused("columns_sample_fetch")) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_fetch: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
     if (!nodes || !cols || !counts) { fail(DSA_ERR_ARGUMENT, "columns_sample_fetch: nodes, cols and counts are required"); return DSA_ERR_ARGUMENT; }
     HIP_TRY(this, hipSetDevice(device));
@@ -852,6 +858,7 @@ int Engine::columns_sample_fetch(double* nodes, double* cols, int* counts)
 int Engine::columns_sample_state(float* models, double* phi, double* psi, int* counters, double* S1, double* S2, double* phisum, int* nkept, double* best_e,
                                  float* best_v, int* pnode, float* pold, int* pmark, int* reseeded)
 {
+    if (int rc = sample_radial_refused("columns_sample_state")) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_state: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
     HIP_TRY(this, hipSetDevice(device));
     const size_t ncol = (size_t)disp_nx * disp_ny, cc = ncol * disp_nmodels, M = (size_t)disp_nz - 1;
@@ -875,11 +882,201 @@ int Engine::columns_sample_state(float* models, double* phi, double* psi, int* c
     return 0;
 }
 
+// ---- the Monte-Carlo radial depth inversion ----
+
+int Engine::sample_radial_refused(const char* who)
+{
+    if (!sample_open || !sample_radial) return 0;
+    fail(DSA_ERR_STATE, "%s: the dispersion stage is a radial sample stage of %d chains (dsa_columns_sample_radial_begin); a new dsa_dispersion_begin ends it", who, disp_nmodels);
+    return DSA_ERR_STATE;
+}
+
+// the radial stage's state and inputs where they lie (column_sample_radial.h); what has the isotropic stage's shape lies in its buffers
+static SampleRadialView sample_radial_view(Engine& e)
+{
+    SampleRadialView S{};
+    S.nx = e.disp_nx; S.ny = e.disp_ny; S.nz = e.disp_nz; S.K = e.disp_nmaps; S.C = e.disp_nmodels; S.burn = e.sample_burn; S.pairs = e.sample_pairs;
+    S.ncol = (long long)e.disp_nx * e.disp_ny;
+    S.seed = e.sample_seed; S.love = e.sample_love;
+    S.lam2 = e.sample_lam2; S.gam2 = e.sample_gam2; S.step = e.sample_step; S.spread = e.sample_spread; S.two_t = e.sample_two_t;
+    S.width = e.sample_width; S.minvel = e.sample_minvel; S.maxvel = e.sample_maxvel;
+    S.obs = e.col_obs.p; S.wt = e.sample_has_wt ? e.col_wt.p : nullptr; S.v0v = e.smp_v0.p; S.v0h = e.smr_v0h.p; S.pv = e.pvstore.p;
+    S.vv = e.vels_d.p; S.vh = e.vsh_d.p;
+    S.phi = e.smp_phi.p; S.psi = e.smp_psi.p; S.cnt = e.smp_cnt.p; S.kcnt = e.smr_kcnt.p;
+    S.S1v = e.smp_S1.p; S.S2v = e.smp_S2.p; S.S1h = e.smr_S1h.p; S.S2h = e.smr_S2h.p; S.Pvh = e.smr_Pvh.p; S.X1 = e.smr_X1.p; S.X2 = e.smr_X2.p; S.npos = e.smr_npos.p;
+    S.phisum = e.smp_phisum.p; S.nkept = e.smp_nkept.p; S.best_e = e.smp_beste.p; S.best_vv = e.smp_bestv.p; S.best_vh = e.smr_bestvh.p;
+    S.pnode = e.smp_pnode.p; S.pold_v = e.smp_pold.p; S.pold_h = e.smr_poldh.p; S.pmark = e.smp_pmark.p; S.reseed = e.smp_reseed.p;
+    S.used = e.smp_used.p; S.nused_r = e.smp_nused.p; S.nused_l = e.smr_nusedl.p; S.flag = e.smp_flag.p; S.phi0 = e.smp_phi0.p;
+    return S;
+}
+
+// dsa_columns_sample_radial_begin: everything is checked before the device is touched; then a radial stage of nchains models
+// (dispersion_setup, vsh_d sized beside vels_d), whose two stores k_sample_radial_setup writes where they lie, the set-up's runs of the plan
+// (times only), and the chains' phi and psi.
+int Engine::columns_sample_radial_begin(int nx, int ny, int nz, int nchains, const float* vsv, const float* vsh, const float* depz, float minthk, int nruns,
+                                        const int* iwave, const int* igr, const int* nper, const double* periods, int nmaps_in, const float* obs, const float* wt,
+                                        float smooth, float aniso, float step, float spread, float width, float temperature, float minvel, float maxvel,
+                                        unsigned long long seed, int burn, int pairs)
+{
+    const char* who = "columns_sample_radial_begin";
+    if (nchains < 1) { fail(DSA_ERR_ARGUMENT, "%s: nchains %d must be at least 1", who, nchains); return DSA_ERR_ARGUMENT; }
+    if (nx < 3 || ny < 3) { fail(DSA_ERR_ARGUMENT, "%s: a %d x %d grid has no interior columns (at least 3 x 3)", who, nx, ny); return DSA_ERR_ARGUMENT; }
+    if (nz < 2 || nz > 64 || !vsv || !vsh || !depz || !(minthk > 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: bad arguments (nz=%d, a null model or depths, minthk=%g)", who, nz, (double)minthk); return DSA_ERR_ARGUMENT; }
+    if (nmaps_in < 1 || nmaps_in > kColumnMaxK) { fail(DSA_ERR_ARGUMENT, "%s: %d maps (1 to %d)", who, nmaps_in, kColumnMaxK); return DSA_ERR_ARGUMENT; }
+    if ((unsigned long long)nx * ny * nchains > 0x7fffffffull || (unsigned long long)nmaps_in * nchains > 0x7fffffffull) { fail(DSA_ERR_ARGUMENT, "%s: %d chains of %d x %d columns and %d maps exceed the index range", who, nchains, nx, ny, nmaps_in); return DSA_ERR_ARGUMENT; }
+    if (nruns < 1 || !iwave || !igr || !nper || !periods) { fail(DSA_ERR_ARGUMENT, "%s: the plan of the runs is missing (nruns=%d)", who, nruns); return DSA_ERR_ARGUMENT; }
+    long long total = 0;
+    unsigned long long love = 0ull;
+    for (int r = 0; r < nruns; ++r) {
+        if ((iwave[r] != 1 && iwave[r] != 2) || nper[r] < 1 || nper[r] > kMaxPeriods) { fail(DSA_ERR_ARGUMENT, "%s: run %d of the plan (iwave=%d nper=%d)", who, r, iwave[r], nper[r]); return DSA_ERR_ARGUMENT; }
+        if (iwave[r] == 1)
+            for (long long k = total; k < total + nper[r] && k < 64; ++k) love |= 1ull << k;
+        total += nper[r];
+    }
+    if (total != nmaps_in) { fail(DSA_ERR_ARGUMENT, "%s: the plan's periods add up to %lld, nmaps is %d", who, total, nmaps_in); return DSA_ERR_ARGUMENT; }
+    for (long long q = 0; q < total; ++q) if (!std::isfinite(periods[q])) { fail(DSA_ERR_ARGUMENT, "%s: period %lld of the plan is not finite", who, q); return DSA_ERR_ARGUMENT; }
+    if (!obs) { fail(DSA_ERR_ARGUMENT, "%s: obs is required", who); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(step) || step <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: step %g must be finite and > 0", who, (double)step); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(spread) || spread < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: spread %g must be finite and >= 0", who, (double)spread); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(width) || width <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: width %g must be finite and > 0", who, (double)width); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(temperature) || temperature <= 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: temperature %g must be finite and > 0", who, (double)temperature); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(smooth) || smooth < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: smooth %g must be finite and >= 0", who, (double)smooth); return DSA_ERR_ARGUMENT; }
+    if (!std::isfinite(aniso) || aniso < 0.0f) { fail(DSA_ERR_ARGUMENT, "%s: aniso %g must be finite and >= 0", who, (double)aniso); return DSA_ERR_ARGUMENT; }
+    if (!(minvel > 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: minvel %g must be > 0 (xi divides by Vsv)", who, (double)minvel); return DSA_ERR_ARGUMENT; }
+    if (!(minvel <= maxvel)) { fail(DSA_ERR_ARGUMENT, "%s: minvel %g > maxvel %g", who, (double)minvel, (double)maxvel); return DSA_ERR_ARGUMENT; }
+    if (burn < 0) { fail(DSA_ERR_ARGUMENT, "%s: burn %d must be >= 0", who, burn); return DSA_ERR_ARGUMENT; }
+    if (pairs != 0 && pairs != 1) { fail(DSA_ERR_ARGUMENT, "%s: pairs %d must be 0 or 1", who, pairs); return DSA_ERR_ARGUMENT; }
+    const size_t ncol = (size_t)nx * ny, K = (size_t)nmaps_in, C = (size_t)nchains, M = (size_t)nz - 1, nobs = ncol * K, cc = C * ncol;
+    for (size_t q = 0; q < nobs; ++q) {
+        if (!std::isfinite(obs[q])) { fail(DSA_ERR_ARGUMENT, "%s: obs[%zu] is not finite", who, q); return DSA_ERR_ARGUMENT; }
+        if (wt && !(std::isfinite(wt[q]) && wt[q] >= 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: wt[%zu] = %g must be finite and >= 0", who, q, (double)wt[q]); return DSA_ERR_ARGUMENT; }
+    }
+    for (size_t q = 0; q < ncol * nz; ++q) {
+        if (!std::isfinite(vsv[q]) || !std::isfinite(vsh[q])) { fail(DSA_ERR_ARGUMENT, "%s: the start models are not finite at %zu", who, q); return DSA_ERR_ARGUMENT; }
+        if (!(vsv[q] > 0.0f)) { fail(DSA_ERR_ARGUMENT, "%s: the start Vsv %g at %zu must be > 0 (xi divides by it)", who, (double)vsv[q], q); return DSA_ERR_ARGUMENT; }
+    }
+    if (int rc = dispersion_setup(nx, ny, nz, depz, minthk, nmaps_in, nmaps_in, nchains)) return rc;
+    if (ensure(vsh_d, ncol * nz * C) || ensure(smp_v0, ncol * nz) || ensure(smr_v0h, ncol * nz) || ensure(col_obs, nobs) || (wt && ensure(col_wt, nobs)) ||
+        ensure(smp_phi, cc) || ensure(smp_psi, cc) || ensure(smp_cnt, kSampleCounters * cc) || ensure(smr_kcnt, kSampleKindCounters * cc) ||
+        ensure(smp_S1, M * cc) || ensure(smp_S2, M * cc) || ensure(smr_S1h, M * cc) || ensure(smr_S2h, M * cc) || ensure(smr_Pvh, M * cc) || ensure(smr_X1, M * cc) ||
+        ensure(smr_X2, M * cc) || ensure(smr_npos, M * cc) || ensure(smp_phisum, cc) || ensure(smp_nkept, cc) || ensure(smp_beste, cc) || ensure(smp_bestv, M * cc) ||
+        ensure(smr_bestvh, M * cc) || ensure(smp_pnode, cc) || ensure(smp_pold, cc) || ensure(smr_poldh, cc) || ensure(smp_pmark, cc) || ensure(smp_reseed, cc) ||
+        ensure(smp_used, ncol) || ensure(smp_nused, ncol) || ensure(smr_nusedl, ncol) || ensure(smp_flag, ncol) || ensure(smp_phi0, ncol) ||
+        ensure(smr_nodes, kSrNodeFigures * M * ncol) || ensure(smp_cols, kSampleColumnFigures * ncol) || ensure(smr_counts, kSrColumnCounts * ncol)) return status;
+    sample_plan.clear();
+    int first = 0;
+    for (int r = 0; r < nruns; ++r) {
+        SampleRun run;
+        run.iwave = iwave[r]; run.igr = igr[r]; run.first = first;
+        run.t.assign(periods + first, periods + first + nper[r]);
+        sample_plan.push_back(run);
+        first += nper[r];
+    }
+    sample_has_wt = wt != nullptr; sample_sweep = 0; sample_burn = burn; sample_seed = seed; sample_pairs = pairs; sample_love = love;
+    sample_block_every = 0; sample_block_scale = 0.0;
+    sample_nbins = 0; sample_cov = false;
+    sample_lam2 = (double)smooth * (double)smooth; sample_gam2 = (double)aniso * (double)aniso;
+    sample_step = (double)step; sample_spread = (double)spread; sample_two_t = 2.0 * (double)temperature;
+    sample_width = width; sample_minvel = minvel; sample_maxvel = maxvel;
+    HIP_TRY(this, hipMemcpyAsync(smp_v0.p, vsv, ncol * nz * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(smr_v0h.p, vsh, ncol * nz * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(this, hipMemcpyAsync(col_obs.p, obs, nobs * 4, hipMemcpyHostToDevice, stream));
+    if (wt) HIP_TRY(this, hipMemcpyAsync(col_wt.p, wt, nobs * 4, hipMemcpyHostToDevice, stream));
+    const SampleRadialView S = sample_radial_view(*this);
+    launch_sample_radial_setup(S, 0, stream);
+    h_vels.clear(); h_vsh.clear();      // (no host copy of the chains is kept)
+    if (int rc = dispersion_commit(false)) return rc;
+    disp_radial = true;                 // (dispersion_run: a Love run reads vsh_d, a Rayleigh run vels_d)
+    for (const SampleRun& run : sample_plan)
+        if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { disp_ready = false; disp_radial = false; return rc; }
+    launch_sample_radial_setup(S, 1, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    sample_open = true; sample_radial = true;
+    return 0;
+}
+
+// dsa_columns_sample_radial_run: whole sweeps, each the proposal, one dispersion_run per entry of the plan (times only) and the Metropolis
+// test.  A sweep's only host traffic is dispersion_run's; only the sweep's number enters a sweep, so run(n) is n times run(1).
+int Engine::columns_sample_radial_run(int nsweeps)
+{
+    if (!disp_ready || !sample_open || !sample_radial) { fail(DSA_ERR_STATE, "columns_sample_radial_run: call dsa_columns_sample_radial_begin first"); return DSA_ERR_STATE; }
+    if (nsweeps < 0 || (long long)sample_sweep + nsweeps > 0x7fffffffll) { fail(DSA_ERR_ARGUMENT, "columns_sample_radial_run: nsweeps %d after %d sweeps", nsweeps, sample_sweep); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const SampleRadialView S = sample_radial_view(*this);
+    for (int s = 0; s < nsweeps; ++s) {
+        const int sweep = sample_sweep + 1;
+        launch_sample_radial_propose(S, sweep, stream);
+        for (const SampleRun& run : sample_plan)
+            if (int rc = dispersion_run(run.iwave, run.igr, (int)run.t.size(), run.t.data(), 0, 0, run.first)) { sample_open = false; sample_radial = false; disp_ready = false; return rc; }
+        launch_sample_radial_accept(S, sweep, stream);
+        sample_sweep = sweep;
+    }
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_radial_fetch: the finish of the state as it is; nothing of the state is changed, the sweeps may go on.
+int Engine::columns_sample_radial_fetch(double* nodes, double* cols, int* counts)
+{
+    if (!disp_ready || !sample_open || !sample_radial) { fail(DSA_ERR_STATE, "columns_sample_radial_fetch: call dsa_columns_sample_radial_begin first"); return DSA_ERR_STATE; }
+    if (!nodes || !cols || !counts) { fail(DSA_ERR_ARGUMENT, "columns_sample_radial_fetch: nodes, cols and counts are required"); return DSA_ERR_ARGUMENT; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny, M = (size_t)disp_nz - 1;
+    launch_sample_radial_finish(sample_radial_view(*this), smr_nodes.p, smp_cols.p, smr_counts.p, stream);
+    HIP_TRY(this, hipGetLastError());
+    HIP_TRY(this, hipMemcpyAsync(nodes, smr_nodes.p, kSrNodeFigures * M * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(cols, smp_cols.p, kSampleColumnFigures * ncol * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(counts, smr_counts.p, kSrColumnCounts * ncol * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
+// dsa_columns_sample_radial_state: the raw per-chain state, for the tests; every pointer may be null
+int Engine::columns_sample_radial_state(float* vsv, float* vsh, double* phi, double* psi, int* counters, int* kinds, double* S1v, double* S2v, double* S1h,
+                                        double* S2h, double* Pvh, double* X1, double* X2, int* npos, double* phisum, int* nkept, double* best_e, float* best_vsv,
+                                        float* best_vsh, int* pnode, float* pold_v, float* pold_h, int* pmark, int* reseeded)
+{
+    if (!disp_ready || !sample_open || !sample_radial) { fail(DSA_ERR_STATE, "columns_sample_radial_state: call dsa_columns_sample_radial_begin first"); return DSA_ERR_STATE; }
+    HIP_TRY(this, hipSetDevice(device));
+    const size_t ncol = (size_t)disp_nx * disp_ny, cc = ncol * disp_nmodels, M = (size_t)disp_nz - 1;
+    #define DSA_SAMPLE_GET(dst, src, n) if (dst) HIP_TRY(this, hipMemcpyAsync(dst, src, (n) * sizeof *(dst), hipMemcpyDeviceToHost, stream))
+    DSA_SAMPLE_GET(vsv, vels_d.p, cc * disp_nz);
+    DSA_SAMPLE_GET(vsh, vsh_d.p, cc * disp_nz);
+    DSA_SAMPLE_GET(phi, smp_phi.p, cc);
+    DSA_SAMPLE_GET(psi, smp_psi.p, cc);
+    DSA_SAMPLE_GET(counters, smp_cnt.p, kSampleCounters * cc);
+    DSA_SAMPLE_GET(kinds, smr_kcnt.p, kSampleKindCounters * cc);
+    DSA_SAMPLE_GET(S1v, smp_S1.p, M * cc);
+    DSA_SAMPLE_GET(S2v, smp_S2.p, M * cc);
+    DSA_SAMPLE_GET(S1h, smr_S1h.p, M * cc);
+    DSA_SAMPLE_GET(S2h, smr_S2h.p, M * cc);
+    DSA_SAMPLE_GET(Pvh, smr_Pvh.p, M * cc);
+    DSA_SAMPLE_GET(X1, smr_X1.p, M * cc);
+    DSA_SAMPLE_GET(X2, smr_X2.p, M * cc);
+    DSA_SAMPLE_GET(npos, smr_npos.p, M * cc);
+    DSA_SAMPLE_GET(phisum, smp_phisum.p, cc);
+    DSA_SAMPLE_GET(nkept, smp_nkept.p, cc);
+    DSA_SAMPLE_GET(best_e, smp_beste.p, cc);
+    DSA_SAMPLE_GET(best_vsv, smp_bestv.p, M * cc);
+    DSA_SAMPLE_GET(best_vsh, smr_bestvh.p, M * cc);
+    DSA_SAMPLE_GET(pnode, smp_pnode.p, cc);
+    DSA_SAMPLE_GET(pold_v, smp_pold.p, cc);
+    DSA_SAMPLE_GET(pold_h, smr_poldh.p, cc);
+    DSA_SAMPLE_GET(pmark, smp_pmark.p, cc);
+    DSA_SAMPLE_GET(reseeded, smp_reseed.p, cc);
+    #undef DSA_SAMPLE_GET
+    HIP_TRY(this, hipStreamSynchronize(stream));
+    return 0;
+}
+
 // dsa_columns_sample_shape: the shape of every interior column for the block proposals, from the resident curves and
 // kernels dsa_columns_resolution reads, under its rules.  The stage is read only, as dsa_columns_resolution's.  The shape lies in buffers of
 // its own, which no other call but the block sweeps reads.
 int Engine::columns_sample_shape(int nmaps_in, const float* obs, const float* wt, float smooth, float damp, double* tri, double* r, int* flag)
 {
+    if (int rc = sample_radial_refused("columns_sample_shape")) return rc;
     if (int rc = columns_front("columns_sample_shape", nmaps_in, obs, wt, smooth, damp, false, 0.0f, 0.0f, 0.0f)) return rc;
     const int K = disp_nmaps, M = disp_nz - 1;
     const size_t ncol = (size_t)disp_nx * disp_ny, T = (size_t)column_tri_size(M);
@@ -908,6 +1105,7 @@ int Engine::columns_sample_shape(int nmaps_in, const float* obs, const float* wt
 int Engine::columns_sample_blocks(int block_every, double block_scale)
 {
     const char* who = "columns_sample_blocks";
+    if (int rc = sample_radial_refused(who)) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
     if (sample_sweep != 0) { fail(DSA_ERR_STATE, "%s: %d sweeps have been run; the kind of the sweeps is set before the first", who, sample_sweep); return DSA_ERR_STATE; }
     if (!blk_held || blk_nx != disp_nx || blk_ny != disp_ny || blk_nz != disp_nz) {
@@ -930,6 +1128,7 @@ int Engine::columns_sample_blocks(int block_every, double block_scale)
 // dsa_columns_sample_block_state: the raw block state, for the tests; zeros while block sweeps are off; every pointer may be null
 int Engine::columns_sample_block_state(float* pold_all, int* counters)
 {
+    if (int rc = sample_radial_refused("columns_sample_block_state")) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "columns_sample_block_state: call dsa_columns_sample_begin first"); return DSA_ERR_STATE; }
     const size_t cc = (size_t)disp_nx * disp_ny * disp_nmodels, M = (size_t)disp_nz - 1;
     if (sample_block_every == 0) {
@@ -950,6 +1149,7 @@ int Engine::columns_sample_block_state(float* pold_all, int* counters)
 int Engine::columns_sample_marginals(int nbins, int with_cov)
 {
     const char* who = "columns_sample_marginals";
+    if (int rc = sample_radial_refused(who)) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
     if (sample_sweep != 0) { fail(DSA_ERR_STATE, "%s: %d sweeps have been run; the marginals are switched before the first", who, sample_sweep); return DSA_ERR_STATE; }
     if (nbins < 0 || nbins == 1 || nbins > 256) { fail(DSA_ERR_ARGUMENT, "%s: nbins %d must be 0 (off) or 2 to 256", who, nbins); return DSA_ERR_ARGUMENT; }
@@ -970,6 +1170,7 @@ int Engine::columns_sample_marginals(int nbins, int with_cov)
 int Engine::columns_sample_marginals_fetch(int nlevels, const double* levels, unsigned* hist, double* figures, double* cov)
 {
     const char* who = "columns_sample_marginals_fetch";
+    if (int rc = sample_radial_refused(who)) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
     if (sample_nbins == 0) { fail(DSA_ERR_STATE, "%s: the marginals are off; call dsa_columns_sample_marginals before the first sweep", who); return DSA_ERR_STATE; }
     if (cov && !sample_cov) { fail(DSA_ERR_STATE, "%s: cov is asked for, but dsa_columns_sample_marginals was called without with_cov", who); return DSA_ERR_STATE; }
@@ -996,6 +1197,7 @@ int Engine::columns_sample_marginals_fetch(int nlevels, const double* levels, un
 int Engine::columns_sample_marginals_state(unsigned* hist, double* P)
 {
     const char* who = "columns_sample_marginals_state";
+    if (int rc = sample_radial_refused(who)) return rc;
     if (!disp_ready || !sample_open) { fail(DSA_ERR_STATE, "%s: call dsa_columns_sample_begin first", who); return DSA_ERR_STATE; }
     if (sample_nbins == 0) { fail(DSA_ERR_STATE, "%s: the marginals are off; call dsa_columns_sample_marginals before the first sweep", who); return DSA_ERR_STATE; }
     if (P && !sample_cov) { fail(DSA_ERR_STATE, "%s: P is asked for, but dsa_columns_sample_marginals was called without with_cov", who); return DSA_ERR_STATE; }
@@ -1262,6 +1464,7 @@ int Engine::kernels_from_dispersion()
 int Engine::kernels_from_dispersion_radial()
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "radial depth kernels: call dsa_dispersion_begin_radial / run first"); return DSA_ERR_STATE; }
+    if (int rc = sample_refused("radial depth kernels")) return rc;
     if (!disp_radial || disp_nmodels != 1) { fail(DSA_ERR_STATE, "radial depth kernels: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
     std::vector<unsigned char> block((size_t)disp_kmax_total, 0);
     for (int s = 0; s < disp_kmax_total; ++s) {
@@ -2393,6 +2596,7 @@ int Engine::solve_radial(float* dsurf, float* rw, int* iw, int* col, long long c
     const int given = (rw != nullptr) + (iw != nullptr) + (col != nullptr);
     if (given != 0 && given != 3) { fail(DSA_ERR_ARGUMENT, "solve_rows_radial: rw / iw / col are all given or all NULL"); return DSA_ERR_ARGUMENT; }
     if (!planned) { fail(DSA_ERR_STATE, "solve_rows_radial: call dsa_plan first"); return DSA_ERR_STATE; }
+    if (int rc = sample_refused("solve_rows_radial")) return rc;
     if (!have_sens || !radial_sens || !disp_ready || !disp_radial) { fail(DSA_ERR_STATE, "solve_rows_radial: no radial depth factors of the present models (the dispersion runs with kernels, then dsa_kernels_from_dispersion_radial, first)"); return DSA_ERR_STATE; }
     if (g.nx != disp_nx || g.ny != disp_ny || sens_nz != disp_nz || sens_kmax != disp_kmax_total) { fail(DSA_ERR_STATE, "solve_rows_radial: the maps are %d x %d, the radial stage holds %d x %d columns (dsa_maps_from_dispersion first)", g.nx, g.ny, disp_nx, disp_ny); return DSA_ERR_STATE; }
     if (grow_rw || grow_iw || grow_col) { fail(DSA_ERR_STATE, "solve_rows_radial: one engine only"); return DSA_ERR_STATE; }
@@ -2407,6 +2611,7 @@ int Engine::solve_radial(float* dsurf, float* rw, int* iw, int* col, long long c
 int Engine::update_radial(int nx, int ny, int nz, const float* dv, float dvmax, float minvel, float maxvel)
 {
     if (!disp_ready) { fail(DSA_ERR_STATE, "update_radial: call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
+    if (int rc = sample_refused("update_radial")) return rc;
     if (!disp_radial) { fail(DSA_ERR_STATE, "update_radial: the dispersion stage is not radial, call dsa_dispersion_begin_radial first"); return DSA_ERR_STATE; }
     if (nx != disp_nx || ny != disp_ny || nz != disp_nz) { fail(DSA_ERR_ARGUMENT, "update_radial: nx %d ny %d nz %d, the radial stage holds %d %d %d", nx, ny, nz, disp_nx, disp_ny, disp_nz); return DSA_ERR_ARGUMENT; }
     if (nx < 3 || ny < 3 || nz < 2) { fail(DSA_ERR_ARGUMENT, "update_radial: a %d x %d x %d model has no unknowns", nx, ny, nz); return DSA_ERR_ARGUMENT; }
@@ -2870,6 +3075,37 @@ int dsa_columns_sample_block_state(dsa_engine* e, float* pold_all, int* counters
 {
     if (!e) return DSA_ERR_ARGUMENT;
     return reinterpret_cast<Engine*>(e)->columns_sample_block_state(pold_all, counters);
+}
+
+int dsa_columns_sample_radial_begin(dsa_engine* e, int nx, int ny, int nz, int nchains, const float* vsv, const float* vsh, const float* depz, float minthk, int nruns,
+                                    const int* iwave, const int* igr, const int* nper, const double* periods, int nmaps, const float* obs, const float* wt,
+                                    float smooth, float aniso, float step, float spread, float width, float temperature, float minvel, float maxvel,
+                                    unsigned long long seed, int burn, int pairs)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_radial_begin(nx, ny, nz, nchains, vsv, vsh, depz, minthk, nruns, iwave, igr, nper, periods, nmaps, obs, wt, smooth,
+                                                                     aniso, step, spread, width, temperature, minvel, maxvel, seed, burn, pairs);
+}
+
+int dsa_columns_sample_radial_run(dsa_engine* e, int nsweeps)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_radial_run(nsweeps);
+}
+
+int dsa_columns_sample_radial_fetch(dsa_engine* e, double* nodes, double* cols, int* counts)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_radial_fetch(nodes, cols, counts);
+}
+
+int dsa_columns_sample_radial_state(dsa_engine* e, float* vsv, float* vsh, double* phi, double* psi, int* counters, int* kinds, double* S1v, double* S2v, double* S1h,
+                                    double* S2h, double* Pvh, double* X1, double* X2, int* npos, double* phisum, int* nkept, double* best_e, float* best_vsv,
+                                    float* best_vsh, int* pnode, float* pold_v, float* pold_h, int* pmark, int* reseeded)
+{
+    if (!e) return DSA_ERR_ARGUMENT;
+    return reinterpret_cast<Engine*>(e)->columns_sample_radial_state(vsv, vsh, phi, psi, counters, kinds, S1v, S2v, S1h, S2h, Pvh, X1, X2, npos, phisum, nkept, best_e,
+                                                                     best_vsv, best_vsh, pnode, pold_v, pold_h, pmark, reseeded);
 }
 
 int dsa_dispersion_begin_radial(dsa_engine* e, int nx, int ny, int nz, const float* vsv, const float* vsh, const float* depz, float minthk, int kmax_total,

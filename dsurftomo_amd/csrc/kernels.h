@@ -419,6 +419,14 @@ struct SampleLevels { int n; double p[kSampleMaxLevels]; };
 void launch_sample_marginals(const SampleView& S, const SampleMarginalView& G, int sweep, hipStream_t stream);
 void launch_sample_marginal_finish(const SampleView& S, const SampleMarginalView& G, const SampleLevels& levels, unsigned* d_pooled, double* d_figures, double* d_cov,
                                    hipStream_t stream);
+// The Monte-Carlo radial depth inversion (k_sample_radial_*).  S (column_sample_radial.h): the radial stage's state and
+// inputs where they lie; the calls are launch_sample_*'s.  launch_sample_radial_finish: d_nodes (16, nz - 1, ncol), d_cols (3, ncol), d_counts
+// (15, ncol).
+struct SampleRadialView;
+void launch_sample_radial_setup(const SampleRadialView& S, int phase, hipStream_t stream);
+void launch_sample_radial_propose(const SampleRadialView& S, int sweep, hipStream_t stream);
+void launch_sample_radial_accept(const SampleRadialView& S, int sweep, hipStream_t stream);
+void launch_sample_radial_finish(const SampleRadialView& S, double* d_nodes, double* d_cols, int* d_counts, hipStream_t stream);
 
 // step_kernels.hip: nm models (members m0 .. m0 + nm - 1) from a base model and their steps (d_steps: the pass's, member-major; null: the resident
 // batch solutions d_bx), written to d_out[depth * stride_depth + model * stride_model + column]; the misfit sums of nm models' receiver times

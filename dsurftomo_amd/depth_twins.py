@@ -1293,3 +1293,236 @@ def sample_marginal_twin(hist, start, width, minvel, maxvel, levels):
             for k, p in enumerate(levels):
                 quant[k, l, c] = sample_marginal_quantile(hist[:, l, c], lo[l, c], hi[l, c], p)
     return mode, quant
+
+
+# ---- the Monte-Carlo radial depth inversion: the twin of csrc/column_sample_radial.h ----
+
+RADIAL_SAMPLE_NODES = ("mean_v", "var_v", "W_v", "B_v", "mean_h", "var_h", "W_h", "B_h", "mean_xi", "var_xi", "W_xi", "B_xi", "best_v", "best_h", "cov_vh", "p_pos")
+
+
+def sample_radial_psi(vv, vh, lam2, gam2):
+    """psi of one chain: (sample_psi(Vsv) + sample_psi(Vsh)) + gam2 sum_l ((double)vh_l - (double)vv_l)^2, l ascending from 0.0"""
+    s = 0.0
+    for a, b in zip(vv, vh):
+        t = float(b) - float(a)
+        s += t * t
+    return (sample_psi(vv, lam2) + sample_psi(vh, lam2)) + gam2 * s
+
+
+def column_sample_radial_twin(nx, ny, start_v, start_h, obs, wt, love, forward, nchains, sweeps, burn, smooth, aniso, step, spread, width, temperature, minvel,
+                              maxvel, seed, pairs=True, after=None):
+    """The Monte-Carlo radial depth inversion in Python integers and NumPy float64 / float32 scalars, the header's operations in the header's
+    order.  start_v, start_h (nz, ny * nx) fp32; obs / wt (K, ny * nx) fp32, wt may be None (1); love (K) bool; forward(vsv, vsh (nz, C, ncol)
+    fp32) -> pv (C, K, ncol) fp64 in place of the dispersion stage (a value <= 0: no root); after(sweep, state): a hook after the set-up
+    (sweep 0) and every sweep.  Returns dict(vsv, vsh, phi, psi, counters (4, C, ncol), kinds (6, C, ncol): proposed per kind (Vsv, Vsh, pair),
+    accepted per kind; S1v, S2v, S1h, S2h, Pvh, X1, X2, npos, phisum, nkept, best_e, best_vsv, best_vsh, pnode, pold_v, pold_h, pmark,
+    reseeded, used, nused_r, nused_l, flag, phi_start, and the finish: RADIAL_SAMPLE_NODES (M, ncol), best_energy, mean_phi (ncol))."""
+    F = np.float32
+    start_v = np.asarray(start_v, F); start_h = np.asarray(start_h, F)
+    nz, ncol = start_v.shape
+    M, C = nz - 1, int(nchains)
+    obs = np.asarray(obs, F)
+    K = obs.shape[0]
+    love = [bool(x) for x in love]
+    lam2 = float(F(smooth)) * float(F(smooth)); gam2 = float(F(aniso)) * float(F(aniso))
+    step = float(F(step)); spread = float(F(spread)); two_t = 2.0 * float(F(temperature))
+    width, minvel, maxvel = F(width), F(minvel), F(maxvel)
+    interior = lambda c: 1 <= c % nx <= nx - 2 and 1 <= c // nx <= ny - 2
+    a_of = lambda k, c: 1.0 if wt is None else float(F(wt[k, c]))
+    starts = (start_v, start_h)
+
+    def box(b):
+        lo, hi = F(b - width), F(b + width)
+        return (minvel if lo < minvel else lo), (maxvel if hi > maxvel else hi)
+
+    def phi_of(pv, c, q, used):
+        phi, bad = 0.0, False
+        for k in used:
+            p = float(pv[q, k, c])
+            if not p > 0.0:
+                bad = True
+                continue
+            rho = a_of(k, c) * (float(obs[k, c]) - p)
+            phi += rho * rho
+        return phi, bad
+
+    f64 = lambda *s: np.zeros(s)
+    i32 = lambda *s: np.zeros(s, np.int32)
+    f32 = lambda *s: np.zeros(s, F)
+    st = dict(vsv=f32(nz, C, ncol), vsh=f32(nz, C, ncol), phi=f64(C, ncol), psi=f64(C, ncol), counters=i32(4, C, ncol), kinds=i32(6, C, ncol), S1v=f64(M, C, ncol),
+              S2v=f64(M, C, ncol), S1h=f64(M, C, ncol), S2h=f64(M, C, ncol), Pvh=f64(M, C, ncol), X1=f64(M, C, ncol), X2=f64(M, C, ncol), npos=i32(M, C, ncol),
+              phisum=f64(C, ncol), nkept=i32(C, ncol), best_e=f64(C, ncol), best_vsv=f32(M, C, ncol), best_vsh=f32(M, C, ncol), pnode=i32(C, ncol), pold_v=f32(C, ncol),
+              pold_h=f32(C, ncol), pmark=np.full((C, ncol), -1, np.int32), reseeded=i32(C, ncol), nused_r=i32(ncol), nused_l=i32(ncol), flag=i32(ncol),
+              phi_start=f64(ncol))
+    vs = (st["vsv"], st["vsh"])
+    for q in range(C):
+        for c in range(ncol):
+            for b in range(2):
+                vs[b][:, q, c] = starts[b][:, c]
+                if q > 0 and interior(c):
+                    for l in range(M):
+                        u = sample_unit(sample_bits(seed, c, q, 0, b * M + l))
+                        lo, hi = box(starts[b][l, c])
+                        x = F(starts[b][l, c] + F(spread * (2.0 * u - 1.0)))
+                        vs[b][l, q, c] = lo if x < lo else hi if x > hi else x
+    vv, vh = vs
+    pv = np.asarray(forward(vv, vh), np.float64).reshape(C, K, ncol)
+    used_of = {}
+    for c in range(ncol):
+        if not interior(c):
+            continue
+        used = [k for k in range(K) if a_of(k, c) > 0.0 and obs[k, c] > 0 and pv[0, k, c] > 0.0]
+        used_of[c] = used
+        st["nused_l"][c] = sum(1 for k in used if love[k])
+        st["nused_r"][c] = len(used) - st["nused_l"][c]
+        st["flag"][c] = 0 if used else 2
+        if not used:
+            for b in range(2):
+                vs[b][:M, :, c] = starts[b][:M, c][:, None]
+            continue
+        st["phi_start"][c] = phi_of(pv, c, 0, used)[0]
+        for q in range(C):
+            phi, bad = phi_of(pv, c, q, used)
+            if bad:
+                for b in range(2):
+                    vs[b][:M, q, c] = starts[b][:M, c]
+                st["reseeded"][q, c] = 1
+                phi = st["phi_start"][c]
+            st["phi"][q, c] = phi
+            st["psi"][q, c] = sample_radial_psi(vv[:M, q, c], vh[:M, q, c], lam2, gam2)
+    st["used"] = used_of
+    moving = [c for c in range(ncol) if interior(c) and used_of.get(c)]
+    if after is not None:
+        after(0, st)
+    cnt, kcnt = st["counters"], st["kinds"]
+    n = (3 if pairs else 2) * M
+    for sweep in range(1, int(sweeps) + 1):
+        st["pmark"][...] = -1
+        for q in range(C):
+            for c in moving:
+                u0 = sample_unit(sample_bits(seed, c, q, sweep, 0)); u1 = sample_unit(sample_bits(seed, c, q, sweep, 1))
+                i = min(int(u0 * float(n)), n - 1)
+                kind = i // M
+                l = i - kind * M
+                fd = F(step * (2.0 * u1 - 1.0))
+                old_v, old_h = vv[l, q, c], vh[l, q, c]
+                new_v, new_h = F(old_v + fd), F(old_h + fd)
+                kcnt[kind, q, c] += 1
+                outside = False
+                if kind != 1:
+                    lo, hi = box(start_v[l, c])
+                    outside = outside or new_v < lo or new_v > hi
+                if kind != 0:
+                    lo, hi = box(start_h[l, c])
+                    outside = outside or new_h < lo or new_h > hi
+                if outside:
+                    st["pmark"][q, c] = 1
+                    continue
+                st["pnode"][q, c] = i; st["pold_v"][q, c] = old_v; st["pold_h"][q, c] = old_h
+                if kind != 1:
+                    vv[l, q, c] = new_v
+                if kind != 0:
+                    vh[l, q, c] = new_h
+                st["pmark"][q, c] = 0
+        pv = np.asarray(forward(vv, vh), np.float64).reshape(C, K, ncol)
+        for q in range(C):
+            for c in moving:
+                if st["pmark"][q, c] == 1:
+                    cnt[2, q, c] += 1; cnt[1, q, c] += 1
+                else:
+                    kind = int(st["pnode"][q, c]) // M
+                    l = int(st["pnode"][q, c]) - kind * M
+                    phi_new, bad = phi_of(pv, c, q, used_of[c])
+                    accepted, psi_new = False, 0.0
+                    if not bad:
+                        psi_new = sample_radial_psi(vv[:M, q, c], vh[:M, q, c], lam2, gam2)
+                        delta = (phi_new + psi_new) - (st["phi"][q, c] + st["psi"][q, c])
+                        if delta == delta:
+                            if delta <= 0.0:
+                                accepted = True
+                            else:
+                                k = sample_bits(seed, c, q, sweep, 2)
+                                accepted = k == 0 or delta / two_t < sample_neglog(k)
+                    if accepted:
+                        st["phi"][q, c] = phi_new; st["psi"][q, c] = psi_new
+                        cnt[0, q, c] += 1
+                        kcnt[3 + kind, q, c] += 1
+                        st["pmark"][q, c] = 2
+                    else:
+                        if kind != 1:
+                            vv[l, q, c] = st["pold_v"][q, c]
+                        if kind != 0:
+                            vh[l, q, c] = st["pold_h"][q, c]
+                        cnt[1, q, c] += 1
+                        if bad:
+                            cnt[3, q, c] += 1
+                        st["pmark"][q, c] = 4 if bad else 3
+                if sweep <= burn:
+                    continue
+                for l in range(M):
+                    fv, fh = vv[l, q, c], vh[l, q, c]
+                    s_v, s_h = float(start_v[l, c]), float(start_h[l, c])
+                    dv, dh = float(fv) - s_v, float(fh) - s_h
+                    st["S1v"][l, q, c] += dv; st["S2v"][l, q, c] += dv * dv
+                    st["S1h"][l, q, c] += dh; st["S2h"][l, q, c] += dh * dh
+                    st["Pvh"][l, q, c] += dv * dh
+                    x, x0 = float(fh) / float(fv), s_h / s_v
+                    dx = x * x - x0 * x0
+                    st["X1"][l, q, c] += dx; st["X2"][l, q, c] += dx * dx
+                    if fh > fv:
+                        st["npos"][l, q, c] += 1
+                energy = float(st["phi"][q, c]) + float(st["psi"][q, c])
+                st["phisum"][q, c] += st["phi"][q, c]
+                if st["nkept"][q, c] == 0 or energy < st["best_e"][q, c]:
+                    st["best_e"][q, c] = energy
+                    st["best_vsv"][:, q, c] = vv[:M, q, c]
+                    st["best_vsh"][:, q, c] = vh[:M, q, c]
+                st["nkept"][q, c] += 1
+        if after is not None:
+            after(sweep, st)
+    fin = {name: np.zeros((M, ncol)) for name in RADIAL_SAMPLE_NODES}
+    fin.update(best_energy=np.zeros(ncol), mean_phi=np.zeros(ncol))
+
+    def pool(s1, s2, l, c, dn, dc):
+        a1 = a2 = sw = sm = 0.0
+        for q in range(C):
+            a, b = float(s1[l, q, c]), float(s2[l, q, c])
+            m = a / dn
+            a1 += a; a2 += b; sw += b / dn - m * m; sm += m
+        pm, mbar = a1 / (dn * dc), sm / dc
+        sb = 0.0
+        for q in range(C):
+            d = float(s1[l, q, c]) / dn - mbar
+            sb += d * d
+        return pm, a2 / (dn * dc) - pm * pm, sw / dc, (sb / (dc - 1.0) if C > 1 else 0.0)
+
+    for c in range(ncol):
+        nk = int(st["nkept"][0, c])
+        if nk == 0:
+            continue
+        dn, dc = float(nk), float(C)
+        best_q = 0
+        for q in range(1, C):
+            if st["best_e"][q, c] < st["best_e"][best_q, c]:
+                best_q = q
+        for l in range(M):
+            s_v, s_h = float(start_v[l, c]), float(start_h[l, c])
+            x0 = s_h / s_v
+            pmv, fin["var_v"][l, c], fin["W_v"][l, c], fin["B_v"][l, c] = pool(st["S1v"], st["S2v"], l, c, dn, dc)
+            pmh, fin["var_h"][l, c], fin["W_h"][l, c], fin["B_h"][l, c] = pool(st["S1h"], st["S2h"], l, c, dn, dc)
+            pmx, fin["var_xi"][l, c], fin["W_xi"][l, c], fin["B_xi"][l, c] = pool(st["X1"], st["X2"], l, c, dn, dc)
+            fin["mean_v"][l, c] = s_v + pmv; fin["mean_h"][l, c] = s_h + pmh; fin["mean_xi"][l, c] = x0 * x0 + pmx
+            sp, npos = 0.0, 0
+            for q in range(C):
+                sp += float(st["Pvh"][l, q, c])
+                npos += int(st["npos"][l, q, c])
+            fin["best_v"][l, c] = float(st["best_vsv"][l, best_q, c]); fin["best_h"][l, c] = float(st["best_vsh"][l, best_q, c])
+            fin["cov_vh"][l, c] = sp / (dn * dc) - pmv * pmh
+            fin["p_pos"][l, c] = float(npos) / (dn * dc)
+        phis = 0.0
+        for q in range(C):
+            phis += float(st["phisum"][q, c])
+        fin["best_energy"][c] = st["best_e"][best_q, c]
+        fin["mean_phi"][c] = phis / (dn * dc)
+    st.update(fin)
+    return st

@@ -124,6 +124,10 @@ def declare_solvers(L):
     L.dsa_columns_sample_marginals.argtypes = [_vp, _i32, _i32]
     L.dsa_columns_sample_marginals_fetch.argtypes = [_vp, _i32] + [_vp] * 4
     L.dsa_columns_sample_marginals_state.argtypes = [_vp] * 3
+    L.dsa_columns_sample_radial_begin.argtypes = [_vp] + [_i32] * 4 + [_vp, _vp, _vp, _f32, _i32] + [_vp] * 4 + [_i32, _vp, _vp] + [_f32] * 8 + [C.c_ulonglong, _i32, _i32]
+    L.dsa_columns_sample_radial_run.argtypes = [_vp, _i32]
+    L.dsa_columns_sample_radial_fetch.argtypes = [_vp] * 4
+    L.dsa_columns_sample_radial_state.argtypes = [_vp] * 25
     L.dsa_kernels_from_dispersion_radial.argtypes = [_vp]
     L.dsa_solve_rows_radial.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dsa_iteration_system_radial_device.argtypes = [_vp] + [_i32] * 4 + [_vp] * 2 + [_f32] * 4 + [_vp] * 6
@@ -183,6 +187,7 @@ class Engine:
         self._disp = (0, 0, 0)
         self._sample = (0, 0)                       # (chains, maps) of the last columns_sample_begin
         self._marginals = (0, False)                # (nbins, with_cov) of the last columns_sample_marginals since then
+        self._sample_radial = (0, 0)                # (chains, maps) of the last columns_sample_radial_begin
 
     def close(self):
         if getattr(self, "_h", None):
@@ -570,6 +575,78 @@ class Engine:
                    phisum=f64(Cn, ncol), nkept=i32(Cn, ncol), best_e=f64(Cn, ncol), best_v=f32(nz - 1, Cn, ncol), pnode=i32(Cn, ncol), pold=f32(Cn, ncol),
                    pmark=i32(Cn, ncol), reseeded=i32(Cn, ncol))
         self._check(self._L.dsa_columns_sample_state(self._h, *[_p(a) for a in out.values()]))
+        return out
+
+    # ---- Monte-Carlo radial depth inversion ----
+    RADIAL_NODE_FIGURES = ("mean_v", "var_v", "W_v", "B_v", "mean_h", "var_h", "W_h", "B_h", "mean_xi", "var_xi", "W_xi", "B_xi", "best_v", "best_h", "cov_vh", "p_pos")
+    RADIAL_COLUMN_COUNTS = ("nused_r", "nused_l", "flag", "accepted", "rejected", "out_of_box", "no_root", "proposed_v", "proposed_h", "proposed_pair", "accepted_v",
+                            "accepted_h", "accepted_pair", "reseeded", "nkept")
+
+    def columns_sample_radial_begin(self, vsv, vsh, depz, minthk, plan, obs, wt, nchains, smooth, aniso, step, spread, width, temperature, minvel, maxvel, seed,
+                                    burn, pairs=True):
+        """dsa_columns_sample_radial_begin: a radial sample stage of nchains Metropolis chains of [Vsv ; Vsh] per column, started at vsv, vsh
+        (nz, ny, nx) fp32, and its set-up sweep.  plan, obs, wt as columns_sample_begin's: a slot of a run of wave type 1 (Love) is computed
+        on a chain's Vsh, every other on its Vsv.  pairs: a third of the proposals move Vsv and Vsh of one depth together.  ValueError as
+        columns_step's, and when vsh differs from vsv in shape."""
+        vsv = np.ascontiguousarray(vsv, np.float32)
+        nz, ny, nx = vsv.shape
+        if vsh is not None:
+            vsh = np.ascontiguousarray(vsh, np.float32)
+            if vsh.shape != vsv.shape:
+                raise ValueError("columns_sample_radial_begin: vsh is %s, vsv %s" % (vsh.shape, vsv.shape))
+        was = self._disp
+        self._disp = (nx, ny, nz)
+        try:
+            nmaps, obs, wt = self._columns_in("columns_sample_radial_begin", obs, wt)[:3]
+        finally:
+            self._disp = was                                                        # (a refused begin leaves the open stage, and its shapes, as they were)
+        iwave = np.array([int(r[0]) for r in plan], np.int32); igr = np.array([int(r[1]) for r in plan], np.int32)
+        nper = np.array([np.size(r[2]) for r in plan], np.int32)
+        t = np.ascontiguousarray(np.concatenate([np.asarray(r[2], np.float64).ravel() for r in plan]) if len(plan) else np.zeros(0), np.float64)
+        self._check(self._L.dsa_columns_sample_radial_begin(self._h, nx, ny, nz, int(nchains), _p(vsv), _p(vsh), _p(np.ascontiguousarray(depz, np.float32)), float(minthk),
+                                                            len(plan), _p(iwave), _p(igr), _p(nper), _p(t), nmaps, _p(obs), _p(wt), float(smooth), float(aniso), float(step),
+                                                            float(spread), float(width), float(temperature), float(minvel), float(maxvel),
+                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(burn), int(pairs)))
+        self._disp = (nx, ny, nz)
+        self._sample_radial = (int(nchains), nmaps)
+
+    def columns_sample_radial_run(self, nsweeps):
+        """dsa_columns_sample_radial_run: nsweeps whole sweeps of every chain on the device"""
+        self._check(self._L.dsa_columns_sample_radial_run(self._h, int(nsweeps)))
+
+    def columns_sample_radial_fetch(self):
+        """dsa_columns_sample_radial_fetch: the finish of the present state.  Returns a dict of RADIAL_NODE_FIGURES (nz - 1, ny * nx) fp64 -- mean,
+        var, W, B of Vsv (_v), Vsh (_h) and xi = (Vsh / Vsv)^2 (_xi), the best model, the pooled covariance of Vsv and Vsh, the share of kept
+        states with Vsh > Vsv --, phi_start, best_energy, mean_phi (ny * nx) fp64 and RADIAL_COLUMN_COUNTS (ny * nx) int32; without a kept sweep
+        the node figures, best_energy and mean_phi are 0."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        nodes = np.zeros((16, nz - 1, ncol)); cols = np.zeros((3, ncol)); counts = np.zeros((15, ncol), np.int32)
+        self._check(self._L.dsa_columns_sample_radial_fetch(self._h, _p(nodes), _p(cols), _p(counts)))
+        out = dict(zip(self.RADIAL_NODE_FIGURES, nodes))
+        out.update(zip(("phi_start", "best_energy", "mean_phi"), cols))
+        out.update(zip(self.RADIAL_COLUMN_COUNTS, counts))
+        return out
+
+    def columns_sample_radial_state(self):
+        """dsa_columns_sample_radial_state: the raw per-chain state.  Returns dict(vsv, vsh (nz, C, ncol) fp32; phi, psi (C, ncol); counters (4, C,
+        ncol), kinds (6, C, ncol) int32: proposed per kind, accepted per kind; S1v, S2v, S1h, S2h, Pvh, X1, X2 (nz - 1, C, ncol); npos (nz - 1,
+        C, ncol) int32; phisum (C, ncol); nkept (C, ncol) int32; best_e (C, ncol); best_vsv, best_vsh (nz - 1, C, ncol) fp32; pnode (C, ncol)
+        int32; pold_v, pold_h (C, ncol) fp32; pmark, reseeded (C, ncol) int32)."""
+        nx, ny, nz = self._disp
+        ncol = nx * ny
+        Cn = self._sample_radial[0]
+        if Cn < 1:                                                                  # (no radial stage was ever begun here: the library's refusal)
+            self._check(self._L.dsa_columns_sample_radial_state(self._h, *([None] * 24)))
+        f64 = lambda *shape: np.zeros(shape)
+        i32 = lambda *shape: np.zeros(shape, np.int32)
+        f32 = lambda *shape: np.zeros(shape, np.float32)
+        M = nz - 1
+        out = dict(vsv=f32(nz, Cn, ncol), vsh=f32(nz, Cn, ncol), phi=f64(Cn, ncol), psi=f64(Cn, ncol), counters=i32(4, Cn, ncol), kinds=i32(6, Cn, ncol),
+                   S1v=f64(M, Cn, ncol), S2v=f64(M, Cn, ncol), S1h=f64(M, Cn, ncol), S2h=f64(M, Cn, ncol), Pvh=f64(M, Cn, ncol), X1=f64(M, Cn, ncol), X2=f64(M, Cn, ncol),
+                   npos=i32(M, Cn, ncol), phisum=f64(Cn, ncol), nkept=i32(Cn, ncol), best_e=f64(Cn, ncol), best_vsv=f32(M, Cn, ncol), best_vsh=f32(M, Cn, ncol),
+                   pnode=i32(Cn, ncol), pold_v=f32(Cn, ncol), pold_h=f32(Cn, ncol), pmark=i32(Cn, ncol), reseeded=i32(Cn, ncol))
+        self._check(self._L.dsa_columns_sample_radial_state(self._h, *[_p(a) for a in out.values()]))
         return out
 
     # ---- block proposals of the sample stage (DESIGN.md section 32) ----

@@ -696,6 +696,47 @@ int dsa_columns_sample_marginals(dsa_engine* e, int nbins, int with_cov);
 int dsa_columns_sample_marginals_fetch(dsa_engine* e, int nlevels, const double* levels, unsigned* hist, double* figures, double* cov);
 int dsa_columns_sample_marginals_state(dsa_engine* e, unsigned* hist, double* P);
 
+/* dsa_columns_sample_radial_*: Monte-Carlo radial depth inversion, nchains Metropolis chains of [Vsv ; Vsh] per interior column kept on the
+ * device (extension; the arithmetic is csrc/column_sample_radial.h).
+ * dsa_columns_sample_radial_begin opens a radial dispersion stage of nchains models -- a Rayleigh run (iwave 2) reads a chain's Vsv, a Love
+ * run (iwave 1) its Vsh -- and runs the set-up sweep.  vsv, vsh: the start models (nz*nx*ny floats each, Vsv > 0); depz, minthk, the plan,
+ * nmaps, obs, wt, smooth, step, spread, width, temperature, seed, burn: dsa_columns_sample_begin's.  A chain samples exp(-(phi + psi) / (2
+ * temperature)) with psi = smooth^2 (|L vsv|^2 + |L vsh|^2) + aniso^2 |vsh - vsv|^2 inside a box per model and node, [max(minvel, v0 - width),
+ * min(maxvel, v0 + width)] about the model's own start; minvel > 0.  A proposal moves one Vsv node, one Vsh node or, with pairs = 1, the Vsv
+ * and the Vsh of one depth together by the same amount (a third of the proposals each).  A datum is used as in dsa_columns_sample_begin; a
+ * column without a used datum of either type gets flag 2 and is never moved, a column with one type missing samples.
+ * dsa_columns_sample_radial_run: nsweeps whole sweeps; n calls with 1 leave the bits one call with n leaves.
+ * dsa_columns_sample_radial_fetch: the finish of the present state, which it leaves as it is.
+ *   nodes   16*(nz-1)*nx*ny doubles, (figure, depth, column): the pooled mean, the pooled variance, W and B (dsa_columns_sample_fetch's) of
+ *           Vsv, then of Vsh, then of xi = (Vsh / Vsv)^2; the best model's Vsv and Vsh; the pooled covariance of Vsv and Vsh; the share of
+ *           the kept states with Vsh > Vsv
+ *   cols    3*nx*ny doubles: phi of the start, the best phi + psi, the mean kept phi
+ *   counts  15*nx*ny ints: nused (Rayleigh), nused (Love), flag, accepted, rejected, out of box, no root, proposed per kind (Vsv, Vsh,
+ *           pair), accepted per kind, the chains put back to the start at the set-up, the sweeps kept n
+ *   without a kept sweep nodes and the last two of cols are 0
+ * dsa_columns_sample_radial_state: the raw state for tests, every pointer may be NULL: vsv, vsh nz*nchains*nx*ny (depth, chain, column); phi,
+ * psi, phisum, nkept, best_e, pnode (kind * (nz-1) + depth), pold_v, pold_h, pmark, reseeded: nchains*nx*ny; counters 4*nchains*nx*ny; kinds
+ * 6*nchains*nx*ny; S1v, S2v, S1h, S2h, Pvh, X1, X2, npos (int), best_vsv, best_vsh (nz-1)*nchains*nx*ny.
+ * While the stage is open everything an open dsa_columns_sample_begin stage refuses returns DSA_ERR_STATE, and so do
+ * dsa_dispersion_get_model_radial, dsa_kernels_from_dispersion_radial, dsa_solve_rows_radial, dsa_update_radial and every
+ * dsa_columns_sample_* entry above.  Leaving the stage: only a dsa_dispersion_begin* (dsa_dispersion_begin, _begin_models, _begin_radial)
+ * or another dsa_columns_sample_radial_begin ends it.  dsa_columns_sample_begin does not: on an open radial stage it is refused like the
+ * other isotropic entries, before its arguments are looked at and with the radial stage left as it was, so that a caller who mixes the two
+ * families up loses no chains; call dsa_dispersion_begin first, then dsa_columns_sample_begin -- the isotropic stage that follows has a
+ * fresh engine's bits.  run, fetch and state return DSA_ERR_STATE without an open radial stage (an open dsa_columns_sample_begin stage
+ * is none).
+ * Errors of begin, all found before the device is touched (a stage that was open stays as it was): dsa_columns_sample_begin's, and
+ * DSA_ERR_ARGUMENT: a NULL vsh, vsh not finite, vsv not > 0, aniso < 0 or not finite, minvel <= 0, pairs outside 0, 1. */
+int dsa_columns_sample_radial_begin(dsa_engine* e, int nx, int ny, int nz, int nchains, const float* vsv, const float* vsh, const float* depz, float minthk,
+                                    int nruns, const int* iwave, const int* igr, const int* nper, const double* periods, int nmaps, const float* obs,
+                                    const float* wt, float smooth, float aniso, float step, float spread, float width, float temperature, float minvel,
+                                    float maxvel, unsigned long long seed, int burn, int pairs);
+int dsa_columns_sample_radial_run(dsa_engine* e, int nsweeps);
+int dsa_columns_sample_radial_fetch(dsa_engine* e, double* nodes, double* cols, int* counts);
+int dsa_columns_sample_radial_state(dsa_engine* e, float* vsv, float* vsh, double* phi, double* psi, int* counters, int* kinds, double* S1v, double* S2v,
+                                    double* S1h, double* S2h, double* Pvh, double* X1, double* X2, int* npos, double* phisum, int* nkept, double* best_e,
+                                    float* best_vsv, float* best_vsh, int* pnode, float* pold_v, float* pold_h, int* pmark, int* reseeded);
+
 /* dsa_columns_step_radial_lateral: dsa_columns_step_radial with neighbouring columns coupled (extension).  The state, obs, wt,
  * smooth, damp, aniso, dvmax, minvel, maxvel and the outputs dv, nused, chi2, flag are dsa_columns_step_radial's, with its rules and order of
  * refusals (a stage that is not radial is DSA_ERR_STATE).  The step of all interior columns together minimises the sum of

@@ -21,6 +21,11 @@ Marginals mode: the same stage twice in one run -- the ma
 (columns_sample_marginals(bins, True)), burn 0 so that every timed sweep is a kept one -- and the time of a columns_sample_marginals_fetch:
     python tools/sample_rate.py marginals [sweeps] [chains] [bins]
 The plain mode above is the figure to compare with an older build.
+
+Radial mode: the radial sample stage on the same grid and model, the example's 26 periods dealt out over the four wave
+types (it lists no Love periods of its own), Vsv and Vsh both the model, 4 dispersion runs per sweep: the median sweep as above, then
+`long` sweeps in one call (burn long / 2) and the chains' figures -- the acceptance per kind of proposal, R-hat of Vsv, Vsh and xi:
+    python tools/sample_rate.py radial [sweeps] [chains] [long]
 """
 import os
 import sys
@@ -141,7 +146,56 @@ def marginals_mode(sweeps, chains, bins):
           (out[1][0] - out[0][0], 100.0 * (out[1][0] - out[0][0]) / out[0][0], out[1][2] - out[0][2], 100.0 * (out[1][2] - out[0][2]) / out[0][2], int(kept.sum())))
 
 
+def radial_mode(sweeps, chains, long):
+    """the median sweep of the radial sample stage, and the chains' figures after `long` more sweeps in one call"""
+    from dsurftomo_amd import radial_posterior as rp
+    c = io.load()
+    t = np.asarray(c["tRc"], np.float64)
+    c = dict(c, tRc=t[:7], tRg=t[7:14], tLc=t[14:20], tLg=t[20:])
+    plan = depth.slot_plan(c)
+    vel = np.ascontiguousarray(np.asarray(c["vels"], np.float32).transpose(2, 1, 0))
+    kmax, ncol = c["kmax"], c["nx"] * c["ny"]
+    e = Engine(0)
+    e.dispersion_begin_radial(vel, vel, c["depz"], c["minthk"], kmax, kmax)
+    for wave, kind, tt, first in plan:
+        e.dispersion_run(wave, kind, tt, False, 0, first)
+    obs = (e.dispersion_fetch(0, kmax) * 1.02).astype(np.float32)
+    sigma = 0.05
+    wt, lam, gam = rp.sample_scaling(None, depth.DEFAULT_SMOOTH, depth.DEFAULT_ANISO, sigma, obs.shape)
+    burn = 1 + sweeps + long // 2
+    t0 = time.perf_counter()
+    e.columns_sample_radial_begin(vel, vel, c["depz"], c["minthk"], plan, obs, wt, chains, lam, gam, depth.DEFAULT_SAMPLE_STEP, depth.DEFAULT_SAMPLE_SPREAD,
+                                  depth.DEFAULT_SAMPLE_WIDTH, depth.DEFAULT_SAMPLE_TEMPERATURE, float(c["minvel"]), float(c["maxvel"]), depth.DEFAULT_SAMPLE_SEED, burn, True)
+    t_begin = 1e3 * (time.perf_counter() - t0)
+    e.columns_sample_radial_run(1)
+    wall, dev = [], []
+    for s in range(sweeps):
+        ms0 = e.stats()["ms_dispersion"]
+        t0 = time.perf_counter()
+        e.columns_sample_radial_run(1)
+        wall.append(1e3 * (time.perf_counter() - t0)); dev.append(e.stats()["ms_dispersion"] - ms0)
+    t0 = time.perf_counter()
+    e.columns_sample_radial_run(long)
+    one_call = 1e3 * (time.perf_counter() - t0) / long
+    res = e.columns_sample_radial_fetch()
+    e.close()
+    w, d = float(np.median(wall)), float(np.median(dev))
+    sm = rp.summary(res)
+    print("radial: %d x %d x %d, K = %d, %d chains, %d curves per sweep, %d dispersion_run per sweep: begin %.1f ms; median of %d sweeps -- %.3f ms wall, %.3f ms in "
+          "the dispersion runs on the device, %.3f ms (%.1f %%) the rest; %.3f ms per sweep in one call of %d" %
+          (c["nx"], c["ny"], c["nz"], kmax, chains, ncol * chains, len(plan), t_begin, sweeps, w, d, w - d, 100.0 * (w - d) / w, one_call, long))
+    print("radial: after %d sweeps (%d kept): accepted %.1f %% of the Vsv, %.1f %% of the Vsh, %.1f %% of the pair proposals; R-hat median / worst: Vsv %.4f / %.4f, "
+          "Vsh %.4f / %.4f, xi %.4f / %.4f; %.1f %% of %d unknowns above 1.1; P(Vsh > Vsv) outside [0.025, 0.975] at %.1f %% of the nodes" %
+          (1 + sweeps + long, int(res["nkept"].max()), 100 * sm["accepted"]["v"], 100 * sm["accepted"]["h"], 100 * sm["accepted"]["pair"], sm["rhat"]["v"]["median"],
+           sm["rhat"]["v"]["worst"], sm["rhat"]["h"]["median"], sm["rhat"]["h"]["worst"], sm["rhat"]["xi"]["median"], sm["rhat"]["xi"]["worst"], 100 * sm["above"],
+           sm["unknowns"], 100 * sm["sure"]))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "radial":
+        arg = lambda k, default: int(sys.argv[k]) if len(sys.argv) > k else default
+        radial_mode(arg(2, 30), arg(3, 64), arg(4, 400))
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "marginals":
         arg = lambda k, default: int(sys.argv[k]) if len(sys.argv) > k else default
         marginals_mode(arg(2, 30), arg(3, 64), arg(4, 64))
